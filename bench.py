@@ -15,6 +15,8 @@ N GPUs: every rank aligns its own pair (pair index = rank, weak scaling, indepen
 then ONE gather of the 16-float poses per step (ncclAllGather issued from the C ABI, icp_gather_poses; RCCL over xGMI).
 value = ICP iterations/s summed over all ranks; correspondences/s = value x 370 488.
 `--eth-dir DIR` runs the same settings on real ETH scans (PCD + pose CSV in the reference's layout) instead.
+`--dump-outputs DIR` writes what the timed path returned in its last step (poses, iterations run, status codes) as DIR/<name>.npy:
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -83,6 +85,21 @@ def cpu_baseline_detail(pair, threads):
     out["threads"] = threads
     out["note"] = "SURVEY.md 8d (i) brute force extrapolated from a 2048-query sample, (ii) exact kd-tree over all queries, (iii) rest of one iteration"
     return out
+
+
+def poses_4x4(c16):
+    """(n,16) column-major poses as the C ABI hands them out -> (n,4,4) float32 in (row, col) indexing."""
+    return np.ascontiguousarray(np.asarray(c16, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 kept, everything else as float64."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _free_port():
@@ -177,7 +194,7 @@ def dry_run(args, world, rank):
         T = np.eye(4, dtype=np.float32); T[:3, 3] = [p, 2 * p, -p]
         return np.ascontiguousarray(T.T).reshape(16)
     t0 = time.perf_counter()
-    for _ in range(max(1, args.steps)):
+    for _ in range(args.steps):
         poses = batch.align_batch(n_pairs, fake, device="cpu")
     if world > 1:
         dist.barrier()
@@ -189,6 +206,8 @@ def dry_run(args, world, rank):
                           "vs_baseline": None, "dtype": "f32", "data": "synthetic", "dry_run": True, "config": {"workload": "dry run", "pairs": n_pairs},
                           "gather_ok": ok, "pairs_of_rank0": mine, "pose_gather": gather_kind,
                           "pairs_per_rank": [len(batch.shard_pairs(n_pairs, r, world)) for r in range(world)]}), flush=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"poses": poses_4x4(poses)})
     if world > 1:
         dist.destroy_process_group()
     if not ok:
@@ -238,7 +257,7 @@ def batch_mode(args, world, rank, local_rank):
         local, status, rc = binding.batch_run(ctxs, scans, init)
         if rc != 0:
             raise SystemExit("icp_batch_run failed: %s" % status.tolist())
-        return gather.gather(local, args.pairs)
+        return gather.gather(local, args.pairs), status
 
     for _ in range(args.warmup):
         step()
@@ -247,7 +266,7 @@ def batch_mode(args, world, rank, local_rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        poses = step()
+        poses, status = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -275,6 +294,8 @@ def batch_mode(args, world, rank, local_rank):
         out["pose_gather_error"] = gather.error
     if rank == 0:
         print(json.dumps(out), flush=True)
+        if args.dump_outputs:                                           # status codes: this rank's pairs, in shard order
+            dump_outputs(args.dump_outputs, {"poses": poses_4x4(poses), "status_rank0": status})
     if world > 1:
         dist.destroy_process_group()
 
@@ -328,7 +349,11 @@ def main():
                     "run the configs[1] settings on real ETH scans instead of the synthetic pair")
     ap.add_argument("--eth-csv", default="apartment_global.csv")
     ap.add_argument("--eth-index", type=int, default=0, help="first CSV row (rank r uses row index + r)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned in its last step "
+                    "(poses as (n, 4, 4) float32, iterations run / status codes as float64) as DIR/<name>.npy, on rank 0")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # ---- rank bookkeeping BEFORE anything touches the GPU ------------------------------------------------------------
     env_world = os.environ.get("WORLD_SIZE")
@@ -381,18 +406,19 @@ def main():
     pools = [ThreadPoolExecutor(1) for _ in extra]
 
     def run_extra(cx):
-        q = eye.copy(); cx.run_raw(q)
-        return q
+        q = eye.copy(); n = cx.run_raw(q)
+        return q, n
 
     def step():
+        """Returns the pose of this rank's pair, and what the whole step computed for --dump-outputs."""
         futs = [pl.submit(run_extra, cx) for pl, cx in zip(pools, extra)]
         pose = eye.copy()
-        ctx.run_raw(pose)                                               # 50 ICP iterations, no host round trip inside
-        for f in futs:
-            f.result()
+        n = ctx.run_raw(pose)                                           # 50 ICP iterations, no host round trip inside
+        res = [(pose, n)] + [f.result() for f in futs]
+        gathered = None
         if world > 1:
-            gather.gather(pose.reshape(1, 16), world)                   # the single pose gather of the batch (one pair per rank)
-        return pose
+            gathered = gather.gather(pose.reshape(1, 16), world)        # the single pose gather of the batch (one pair per rank)
+        return pose, (res, gathered)
 
     for _ in range(args.warmup):
         step()
@@ -403,7 +429,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        pose = step()
+        pose, last = step()
         tm = ctx.timing()
         for k in acc:
             acc[k] += tm[k]
@@ -526,6 +552,12 @@ def main():
             out["cpu_baseline"]["detail"] = cpu_baseline_detail(pair, out["cpu_baseline"]["cores"])
     if rank == 0:
         print(json.dumps(out), flush=True)
+        if args.dump_outputs:
+            res, gathered = last
+            d = {"poses": poses_4x4([q for q, _ in res]), "iterations_run": np.array([n for _, n in res], np.float64)}
+            if gathered is not None:
+                d["gathered_poses"] = poses_4x4(gathered)
+            dump_outputs(args.dump_outputs, d)
     if world > 1:
         dist.destroy_process_group()
 

@@ -1,9 +1,9 @@
-"""Generates the committed fixtures under tests/golden/ (run in the build container only).
+"""Generates the committed fixtures under tests/golden/.  usage: python tests/golden/make_golden.py <the reference's Data/ directory>
 
 Inputs  : the bunny pair shipped with the reference (Data/bunny_part1.off = target, Data/bunny_part2_trans.off
           = source, BunnyDataLoader.h:10-11), parsed with icp_amd.meshio (SimpleMesh::loadMesh semantics) and turned
           into point clouds with PointCloud(SimpleMesh) semantics.  The .off files are DATA of the reference,
-          stored here as float32 arrays (bunny_pair.npz) because /root/reference does not exist on the GPU box.
+          stored here as float32 arrays (bunny_pair.npz) so that the tests need nothing outside this repository.
 Outputs : what the CPU oracle (oracle/icp_oracle.cpp, "faithful" fp32 mode and "exact" fp64 mode) produces for the
           linear rows of Data/bunny_experiments.csv (bunny003-005, 203-205, 303-305) plus normals weighting:
           per-iteration poses / valid counts, iteration-0 matches, weights after pruning.
@@ -20,13 +20,12 @@ sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 from icp_amd import meshio          # noqa: E402
 from oracle import oracle as orc     # noqa: E402
 
-REF_DATA = "/root/reference/Data"
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 
-def main():
-    tv, _, tt = meshio.load_off(os.path.join(REF_DATA, "bunny_part1.off"))
-    sv, _, st = meshio.load_off(os.path.join(REF_DATA, "bunny_part2_trans.off"))
+def main(ref_data):
+    tv, _, tt = meshio.load_off(os.path.join(ref_data, "bunny_part1.off"))
+    sv, _, st = meshio.load_off(os.path.join(ref_data, "bunny_part2_trans.off"))
     tp, tn, tc = meshio.mesh_to_cloud(tv, tt)
     sp, sn, sc = meshio.mesh_to_cloud(sv, st)
     np.savez_compressed(os.path.join(OUT, "bunny_pair.npz"), src_pts=sp, src_nrm=sn, src_rgba=sc, tgt_pts=tp, tgt_nrm=tn, tgt_rgba=tc,
@@ -60,4 +59,6 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) != 2:
+        raise SystemExit(__doc__.splitlines()[0])
+    main(sys.argv[1])

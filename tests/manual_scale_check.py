@@ -1,7 +1,7 @@
 """Dev check at 4x the bench size (1.48 M x 1.48 M points): match indices bit-exact against the oracle's kd-tree, incremental
 run equal to the non-incremental one, timings.  usage (GPU box, not collected by pytest): python tests/manual_scale_check.py"""
 import sys, os, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

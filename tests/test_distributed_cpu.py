@@ -84,6 +84,25 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     assert bad.returncode != 0 and b"refusing" in bad.stderr
 
 
+def test_bench_dump_outputs_and_steps(tmp_path):
+    """--dump-outputs DIR writes the poses of the last step as float32 (n, 4, 4); --steps below 1 is refused, not rounded up."""
+    import json, subprocess, sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "3", "--dump-outputs", str(tmp_path / "d")],
+                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    assert json.loads(out.stdout.decode().splitlines()[0])["steps"] == 3
+    assert sorted(os.listdir(tmp_path / "d")) == ["poses.npy"]
+    poses = np.load(tmp_path / "d" / "poses.npy")
+    assert poses.dtype == np.float32 and poses.shape == (2, 4, 4)
+    exp = np.tile(np.eye(4, dtype=np.float32), (2, 1, 1)); exp[:, :3, 3] = [[p, 2 * p, -p] for p in range(2)]    # bench.py's dry-run poses
+    assert np.array_equal(poses, exp)                                   # translation in the last column: (row, col) indexing
+    bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dry-run", "--steps", "0"], env=env, stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, timeout=120)
+    assert bad.returncode != 0 and b"--steps" in bad.stderr
+
+
 def test_cabi_shard_rule_matches_python():
     from icp_amd import batch, binding
     for n_pairs, world in ((44, 8), (7, 2), (3, 4), (0, 2)):

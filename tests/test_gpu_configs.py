@@ -199,6 +199,30 @@ def test_bench_eth_dir_is_one_command(tmp_path):
     assert line["per_regime_ms"]["match_iteration_0"] > 0 and line["no_incremental_value"] > 0
 
 
+def test_bench_dump_outputs_are_what_the_timed_path_returned(tmp_path):
+    """`python bench.py --dump-outputs DIR` writes the pose icp_run returned in the last timed step: bit for bit the pose of a run of
+    the same seeded pair with bench.py's settings outside bench.py."""
+    import types
+    import bench
+    from icp_amd import binding, synth
+    d = tmp_path / "d"
+    subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--n-tilt", "96", "--n-beam", "200",
+                             "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(d)], timeout=600)
+    assert sorted(os.listdir(d)) == ["iterations_run.npy", "poses.npy"]
+    poses, its = np.load(d / "poses.npy"), np.load(d / "iterations_run.npy")
+    assert poses.dtype == np.float32 and poses.shape == (1, 4, 4) and its.dtype == np.float64 and its.tolist() == [50.0]
+    pair = synth.eth_like_pair(0, n_tilt=96, n_beam=200)
+    opt = bench.make_optimizer(binding, 0, types.SimpleNamespace(iterations=50, knn="lbvh"))
+    try:
+        opt.ctx.set_target(pair["tgt_pts"], pair["tgt_nrm"], None); opt.ctx.set_source(pair["src_pts"], pair["src_nrm"], None)
+        for _ in range(2):
+            q = binding.pose_to_c(np.eye(4, dtype=f32))
+            assert opt.ctx.run_raw(q) == 50
+            assert np.array_equal(binding.pose_from_c(q), poses[0])
+    finally:
+        opt.ctx.close()
+
+
 # ------------------------------------------------------------------------------------------------ advisor findings of round 1
 def test_backproject_depth_without_colours(gpu_ctx_factory, orc):
     """rgbx == NULL (the header allows it): the staging layout must still hold the valid mask; compared with the oracle."""

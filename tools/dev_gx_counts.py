@@ -1,6 +1,6 @@
 """Dev tool (times build): events of the hand-over between blocks (GX), per launch of a run.  usage: ICP_HIP_LIB=.../libicp_hip_times.so python tools/dev_gx_counts.py [iterations ...]"""
 import sys, os, ctypes as C
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

@@ -2,7 +2,7 @@
 the wave start over on the general path?  (a) the cloud of tests/test_gpu_seeded.py::test_seeded_search_lone_walkers_small_and_huge_radius,
 (b) a 50-iteration run of configs[1].  usage: ICP_HIP_LIB=.../libicp_hip_times.so python tools/dev_lone_counts.py"""
 import sys, os, ctypes as C
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 from icp_amd import binding, synth

@@ -3,7 +3,7 @@ Lane 0 of every matcher wave stamps the 100 MHz clock at: iteration top, pose re
 wave at: polling starts, fold complete, total published; block 0 also at: totals received, pose published.  All times relative to the moment
 the pose of that iteration went out.  usage: ICP_HIP_LIB=... ICP_HIP_DBG_ITER=30 python tools/dev_loop_times.py"""
 import sys, os, ctypes as C
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

@@ -3,7 +3,7 @@ the reducer blocks of the iteration before (start, folded, total published; bloc
 the matcher waves (start, front = pose received + verify, walks, post, reduce, end).  All times in us after the first stamp of the launch.
 usage: ICP_HIP_LIB=... python tools/dev_ring_times.py [iterations ...]   (the last launch of a run of that many iterations is shown)"""
 import sys, os, ctypes as C
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

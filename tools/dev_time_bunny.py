@@ -1,6 +1,6 @@
 """Dev timing helper: configs[0] (bunny pair, 1054 x 1359, point-to-point, 20 iterations) on the GPU, both matchers."""
 import sys, os, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding

@@ -1,7 +1,7 @@
 """Times the other BASELINE configs at full size on the GPU (dev tool): config 3 (projective + symmetric, 1077x344 and 640x480)
 and config 5 (6-D colour k-NN, multires, 640x480)."""
 import sys, os, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

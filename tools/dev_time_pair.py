@@ -1,7 +1,7 @@
 """Dev timing helper: end-to-end wall clock of one pair -- icp_set_target (upload + index build), icp_set_source, first icp_run
 (builds the Morton-sorted source level), second icp_run.  usage: python tools/dev_time_pair.py"""
 import sys, os, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

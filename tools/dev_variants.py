@@ -1,7 +1,7 @@
 """Dev timing helper: 50 full-size point-to-plane iterations; prints the HIP-event stage split and the wall clock per iteration.
 usage: python tools/dev_variants.py <library file under icp-variants_amd/lib>   (knobs: ICP_HIP_FUSE_POST, ICP_HIP_STAGE_EVENTS)"""
 import sys, os, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

@@ -1,7 +1,7 @@
 """Dev tool (a build with ICP_DEBUG_STEPS=1 ICP_DEBUG_TIMES=1 ICP_DEBUG_WALK_ENDS=1): where do the seeded walks of the last launch of a run end -- in the old neighbour's leaf, in the old runner-up's leaf
 (the second leaf of the two-leaf tier), or elsewhere?  usage: ICP_HIP_LIB=.../libicp_hip_times.so python tools/dev_walk_ends.py [iterations ...]"""
 import sys, os, ctypes as C
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

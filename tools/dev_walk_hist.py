@@ -1,7 +1,7 @@
 """Dev tool (needs a build with ICP_DEBUG_STEPS=1 ICP_SHARE_WALKS=0 -- a shared walk has no per-query length --: ICP_HIP_LIB=.../libicp_hip_dbg.so): distribution of the tree-walk length per query
 and per wave for chosen ICP iterations of configs[1].  usage: ICP_HIP_LIB=... python tools/dev_walk_hist.py"""
 import sys, os, ctypes as C
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

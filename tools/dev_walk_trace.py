@@ -2,7 +2,7 @@
 walkers, spread start) of the last launch of a run: clock at entry, after the spread start, at the top of every pass of the hand-over loop, at exit.
 usage: ICP_HIP_LIB=.../libicp_hip_trace.so python tools/dev_walk_trace.py [iterations ...]"""
 import sys, os, ctypes as C
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

@@ -2,7 +2,7 @@
 fused matcher spend their time.  Lane 0 of every wave stamps the 100 MHz clock at the start, after the front end (loads + verify test), after the
 walks, after weighting/rejection, after the wave reduction and at the end.  usage: ICP_HIP_LIB=... python tools/dev_wave_times.py [iterations ...]"""
 import sys, os, ctypes as C
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

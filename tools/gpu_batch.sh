@@ -3,7 +3,7 @@
 # a killed GPU step says something is wrong, nothing else may start on that box.  Other failures are recorded and the batch goes on.
 # usage: bash tools/gpu_batch.sh <outdir> <<< "name|timeout_s|command" lines on stdin
 OUT=$1; mkdir -p $OUT
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 while IFS='|' read -r name limit cmd; do
   [ -z "$name" ] && continue
   echo "== $name (limit ${limit}s): $cmd"

@@ -2,7 +2,7 @@
 # Per-dispatch PMC values of the fused matcher for the first launches of one icp_run (which iteration is bound by what).
 # usage: tools/pmc_per_dispatch.sh <outdir> <iters>
 OUT=$1; ITERS=${2:-6}
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p $OUT
+export TMPDIR=/tmp && cd "$(dirname "$0")/.." && mkdir -p $OUT
 i=0
 for P in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS" \
          "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INST_LEVEL_VMEM SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INSTS_SALU" \

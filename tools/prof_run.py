@@ -1,7 +1,7 @@
 """Small driver for rocprofv3 passes: config 2 (370k ETH-like pair, k-NN + point-to-plane), one icp_run of N iterations.
 usage: python tools/prof_run.py [lbvh|brute] [iterations]"""
 import sys, os
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
 import numpy as np
 from icp_amd import binding, synth

@@ -2,7 +2,7 @@
 # Regenerates everything under profiles/<round>/ on a GPU box: bench lines, rocprofv3 kernel stats, PMC passes, traffic_latest.json.
 # usage (through gpurun):  bash tools/refresh_profiles.sh gpurun_out/r03p    -> copy the results into profiles/r03/
 OUT=${1:-gpurun_out/r03p}; mkdir -p $OUT
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 run() { name=$1; shift; echo "== $name"; timeout -k 10 300 "$@" > $OUT/$name.json 2> $OUT/$name.err; rc=$?; echo "$name rc=$rc" >> $OUT/status.txt; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "step $name hit its limit: stopping"; exit 1; fi; }
 run bench_lbvh python bench.py --steps 20 --warmup 5
 run bench_lbvh_noincremental python bench.py --no-incremental --no-cpu-baseline
