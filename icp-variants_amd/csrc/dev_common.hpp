@@ -47,18 +47,22 @@ __global__ void k_deinterleave3(const float* __restrict__ aos, int n, int pad_to
     if (i < n) { x[i] = aos[(size_t)i * 3]; y[i] = aos[(size_t)i * 3 + 1]; z[i] = aos[(size_t)i * 3 + 2]; }
     else if (i < pad_to) { x[i] = pad_value; y[i] = pad_value; z[i] = pad_value; }
 }
-// RGBA bytes -> packed u32 + colour features (color_scale*color_normalize)*float(c), NearestNeighbor.h:212-221
+// colour features (color_scale*color_normalize)*float(c) of one packed RGBA word, NearestNeighbor.h:212-221
+__device__ __forceinline__ void color_features(uint32_t v, float& r, float& g, float& b) {
+    const float color_normalize = 1 / float(255);
+    const float color_scale = 1;
+    r = color_scale * color_normalize * (float)(int)(v & 0xFF);
+    g = color_scale * color_normalize * (float)(int)((v >> 8) & 0xFF);
+    b = color_scale * color_normalize * (float)(int)((v >> 16) & 0xFF);
+}
+// RGBA bytes -> packed u32 + colour features
 __global__ void k_colors(const uint8_t* __restrict__ rgba, int n, int pad_to, uint32_t* __restrict__ packed,
                          float* __restrict__ cr, float* __restrict__ cg, float* __restrict__ cb) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const float color_normalize = 1 / float(255);
-    const float color_scale = 1;
     if (i < n) {
         uint32_t v = ((const uint32_t*)rgba)[i];
         packed[i] = v;
-        cr[i] = color_scale * color_normalize * (float)(int)(v & 0xFF);
-        cg[i] = color_scale * color_normalize * (float)(int)((v >> 8) & 0xFF);
-        cb[i] = color_scale * color_normalize * (float)(int)((v >> 16) & 0xFF);
+        color_features(v, cr[i], cg[i], cb[i]);
     } else if (i < pad_to) { cr[i] = 0.f; cg[i] = 0.f; cb[i] = 0.f; }
 }
 

@@ -6,7 +6,7 @@
 // (oracle/icp_oracle.cpp), so match indices / distances / weights are bit-identical to it.
 // fp32 sqrt and divide are correctly rounded (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt).
 //
-// Files: dev_common.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_solve.hpp,
+// Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_solve.hpp,
 // dev_fused.hpp, dev_persist.hpp, dev_measures.hpp (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -27,6 +27,8 @@
 //   k_reduce_solve      fixed-order reduction of block partials + fp64 solve + pose composition
 //                       (ICPOptimizer.h:614-620,753-781,855-897; ProcrustesAligner.h:56-66)
 //   k_rmse_partial      ConvergenceMeasure::rmseAlignmentError (ConvergenceMeasure.h:50-66)
+//   k_depth_count /     PointCloud(depthMap, colorFrame, ...) (PointCloud.h:78-165): back-projection, normals, stride and filter of a
+//   k_depth_scatter     depth frame as a stable two-pass compaction straight into a context cloud (dev_depth.hpp)
 // =====================================================================================
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,6 +39,7 @@
 namespace icpdev {
 
 #include "dev_common.hpp"
+#include "dev_depth.hpp"
 #include "dev_knn_brute.hpp"
 #include "dev_bvh.hpp"
 #include "dev_normals.hpp"

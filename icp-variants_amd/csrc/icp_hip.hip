@@ -108,6 +108,12 @@ struct icp_ctx {
     DevBuf dbg_steps;                    // development builds only (ICP_DEBUG_STEPS)
     DevBuf ps, matches, d2, best64, nn_raw, partials, partials2, ring, pring, totals, sums, stats, staging, rmse_partials, rmse_out, fontana_partials;
     Cloud conv_src, conv_ref; int conv_n = 0;
+    // depth frames (icp_set_*_depth, icp_track_depth_frames): two upload slots, each a page-locked staging block + a device copy of
+    // [depth 4n | rgbx 4n]; the next frame of a sequence goes up on depth_stream while the current one iterates
+    void* depth_pin[2] = {nullptr, nullptr}; size_t depth_pin_cap[2] = {0, 0}; DevBuf depth_dev[2]; hipEvent_t depth_up[2] = {nullptr, nullptr}; bool depth_pending[2] = {false, false};
+    hipStream_t depth_stream = nullptr;
+    DevBuf depth_blocks, track_rmse;     // block counts / offsets of the depth compaction; per-frame initial + final RMSE of a tracked sequence
+    PoseState* pin_track = nullptr;      // page-locked pose staging of a tracked frame's initial / final RMSE: two slots of its own, apart from `pinned`
     float cos_reject = 0.5f;
     std::vector<hipEvent_t> events;
     hipEvent_t build_ev[2] = {nullptr, nullptr};   // index-build bracket (build_bvh)
@@ -260,15 +266,20 @@ int finite_list(icp_ctx* c, const Cloud& cl, bool with_normals, DevBuf& flag, De
 
 // Upload the pose state.  Staged through the context's page-locked buffer: no synchronisation here -- every entry point
 // that uses the pose synchronises the stream before it returns, so the staging area is free again by the next call.
-int write_pose(icp_ctx* c, const float pose[16]) {
+// write_pose_via: the same through a page-locked PoseState h the caller owns (and keeps untouched until the stream has passed the copy).
+int write_pose_via(icp_ctx* c, PoseState* h, const float pose[16]) {
     int rc;
-    if ((rc = ensure_pinned(c, sizeof(PoseState)))) return rc;
-    PoseState* h = (PoseState*)c->pinned; memset(h, 0, sizeof(*h));
+    memset(h, 0, sizeof(*h));
     memcpy(h->pose, pose, 64);
     normal_matrix_from_pose(h->pose, h->nmat);
     if ((rc = ensure(c, c->ps, sizeof(PoseState)))) return rc;
     HIPCK(c, hipMemcpyAsync(c->ps.p, h, sizeof(*h), hipMemcpyHostToDevice, c->stream));
     return ICP_OK;
+}
+int write_pose(icp_ctx* c, const float pose[16]) {
+    int rc;
+    if ((rc = ensure_pinned(c, sizeof(PoseState)))) return rc;
+    return write_pose_via(c, (PoseState*)c->pinned, pose);
 }
 
 // One launch of the merged loop: the pose slot its matcher blocks wait for, where they leave their partials, and the reducer that rides in front.
@@ -756,6 +767,135 @@ int ensure_events(icp_ctx* c, size_t count) {
     return ICP_OK;
 }
 
+// Bookkeeping behind a freshly written target (icp_set_target, the promotion of a batch's source, icp_set_target_depth): the finite
+// list (non-finite targets can never win the strict-< argmin: they stay out of the tree) and, for the k-NN BVH backend, buildIndex.
+int finish_target(icp_ctx* c, bool with_colors) {
+    int rc;
+    Bvh& b = c->bvh;
+    c->bvh6.valid = false;
+    b.valid = false; b.n_valid = 0;
+    if ((rc = finite_list(c, c->tgt, false, c->tgt_flag, c->tgt_finite, &b.n_valid))) return rc;
+    b.d_finite = c->tgt_finite.as<int>(); b.n_ids = c->tgt.n;
+    c->bvh6.d_finite = b.d_finite; c->bvh6.n_valid = b.n_valid; c->bvh6.n_ids = c->tgt.n;
+    b.attrs = &c->tgt; c->bvh6.attrs = &c->tgt;
+    if (c->prm.knn_backend == ICP_KNN_LBVH && c->prm.matching == ICP_MATCH_KNN) {                         // buildIndex; otherwise built on first use
+        if (c->prm.color_icp && with_colors) return build_bvh<6>(c, c->bvh6, target_coords6(c));
+        return build_bvh<3>(c, b, target_coords3(c));
+    }
+    return ICP_OK;
+}
+// Bookkeeping behind a freshly written source (icp_set_source, icp_set_source_depth): validity of a source point for the multi-resolution
+// selections (finite point && finite normal, PointCloud.h:334), the bounding box of the finite points (Morton order of the queries), and the
+// selections of the previous source dropped.  Enqueued only: nothing waits for the device here.
+int finish_source(icp_ctx* c) {
+    int rc;
+    const int n = c->src.n; const Cloud& s = c->src;
+    for (auto& kv : c->levels) release(kv.second);
+    c->levels.clear();
+    if (n <= 0) return ICP_OK;
+    if ((rc = ensure(c, c->src_flag, (size_t)n))) return rc;
+    if ((rc = ensure(c, c->src_box, 32))) return rc;
+    hipLaunchKernelGGL(k_mark_finite, dim3((n + 255) / 256), dim3(256), 0, c->stream, s.x.as<float>(), s.y.as<float>(), s.z.as<float>(),
+                       s.has_normals ? s.nx.as<float>() : nullptr, s.has_normals ? s.ny.as<float>() : nullptr, s.has_normals ? s.nz.as<float>() : nullptr, n, c->src_flag.as<uint8_t>());
+    HIPCK(c, hipMemsetAsync(c->src_box.p, 0xFF, 12, c->stream));
+    HIPCK(c, hipMemsetAsync((char*)c->src_box.p + 12, 0x00, 12, c->stream));
+    hipLaunchKernelGGL(k_bbox, dim3(256), dim3(256), 0, c->stream, s.x.as<float>(), s.y.as<float>(), s.z.as<float>(), n, c->src_box.as<unsigned int>());
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+
+// depthExtrinsics.inverse() (PointCloud.h:88-90): rigid/affine 4x4 (column-major), inverted in fp64 and rounded once -> 3x3 row-major R^-1, t^-1
+void invert_extrinsics(const float* extrinsics, float inv[12]) {
+    double R[9], t[3];
+    for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) R[r * 3 + k] = extrinsics[k * 4 + r]; t[r] = extrinsics[12 + r]; }
+    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    double Ri[9] = {(R[4] * R[8] - R[5] * R[7]) / det, (R[2] * R[7] - R[1] * R[8]) / det, (R[1] * R[5] - R[2] * R[4]) / det,
+                    (R[5] * R[6] - R[3] * R[8]) / det, (R[0] * R[8] - R[2] * R[6]) / det, (R[2] * R[3] - R[0] * R[5]) / det,
+                    (R[3] * R[7] - R[4] * R[6]) / det, (R[1] * R[6] - R[0] * R[7]) / det, (R[0] * R[4] - R[1] * R[3]) / det};
+    for (int i = 0; i < 9; i++) inv[i] = (float)Ri[i];
+    for (int r = 0; r < 3; r++) inv[9 + r] = (float)(-(Ri[r * 3] * t[0] + Ri[r * 3 + 1] * t[1] + Ri[r * 3 + 2] * t[2]));
+}
+
+int check_depth_args(icp_ctx* c, const icp_depth_camera* cam, const icp_depth_options* opt, const char* who) {
+    if (!cam || !opt || cam->width <= 0 || cam->height <= 0 || (long long)cam->width * cam->height > 0x7FFFFFFFll || opt->downsample_factor < 1 ||
+        std::isnan(opt->max_distance) || !std::isfinite(cam->fx) || !std::isfinite(cam->fy) || !std::isfinite(cam->cx) || !std::isfinite(cam->cy)) {
+        c->err = std::string(who) + ": bad camera or options (width, height > 0, downsample_factor >= 1)"; return ICP_ERR_INVALID_ARG;
+    }
+    return ICP_OK;
+}
+
+// One depth frame [depth 4n | rgbx 4n] into upload slot `slot`: host -> page-locked block -> device, on stream s (the context's own stream,
+// or depth_stream when the frame goes up while the previous one iterates); depth_up[slot] marks its arrival.  The only host-side wait is for
+// the slot's previous copy to have left the page-locked block.
+int stage_depth(icp_ctx* c, int slot, const float* depth, const uint8_t* rgbx, int n, hipStream_t s) {
+    if (!c->depth_up[slot]) HIPCK(c, hipEventCreateWithFlags(&c->depth_up[slot], hipEventDisableTiming));
+    if (c->depth_pending[slot]) { HIPCK(c, hipEventSynchronize(c->depth_up[slot])); c->depth_pending[slot] = false; }
+    const size_t bytes = (size_t)n * (rgbx ? 8 : 4);
+    if (bytes > c->depth_pin_cap[slot] || !c->depth_pin[slot]) {
+        if (c->depth_pin[slot]) { HIPCK(c, hipHostFree(c->depth_pin[slot])); c->depth_pin[slot] = nullptr; c->depth_pin_cap[slot] = 0; }
+        HIPCK(c, hipHostMalloc(&c->depth_pin[slot], (size_t)n * 8, hipHostMallocDefault));
+        c->depth_pin_cap[slot] = (size_t)n * 8;
+    }
+    int rc;
+    if ((rc = ensure(c, c->depth_dev[slot], (size_t)n * 8))) return rc;
+    memcpy(c->depth_pin[slot], depth, (size_t)n * 4);
+    if (rgbx) memcpy((char*)c->depth_pin[slot] + (size_t)n * 4, rgbx, (size_t)n * 4);
+    HIPCK(c, hipMemcpyAsync(c->depth_dev[slot].p, c->depth_pin[slot], bytes, hipMemcpyHostToDevice, s));
+    HIPCK(c, hipEventRecord(c->depth_up[slot], s)); c->depth_pending[slot] = true;
+    return ICP_OK;
+}
+
+// PointCloud(depthMap, colorFrame, K, extrinsics, width, height, keepOriginalSize, downsampleFactor, maxDistance) (PointCloud.h:78-165) from
+// the frame in upload slot `slot` straight into the SoA planes of `cl` (dev_depth.hpp): count -> scan -> scatter on the context's stream,
+// then ONE 4-byte copy of the kept-point count back to the host (the cloud's size decides every launch after it).  Leaves the planes as
+// upload_cloud leaves them for the same arrays (pad: +inf padding of a target).
+int depth_to_cloud(icp_ctx* c, int slot, const icp_depth_camera& cam, const icp_depth_options& opt, bool with_colors, Cloud& cl, bool pad, int* n_out) {
+    int rc;
+    const int n = cam.width * cam.height, f = opt.downsample_factor;
+    const int count = (int)(((long long)n + f - 1) / f);
+    const int nb = (count + 255) / 256, cap = (count + 63) / 64 * 64;
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->depth_up[slot], 0));
+    DepthFrame fr;
+    fr.depth = c->depth_dev[slot].as<float>(); fr.rgbx = with_colors ? c->depth_dev[slot].as<uint8_t>() + (size_t)n * 4 : nullptr;
+    fr.width = cam.width; fr.height = cam.height; fr.factor = f; fr.count = count;
+    fr.fx = cam.fx; fr.fy = cam.fy; fr.cx = cam.cx; fr.cy = cam.cy; fr.max_distance_halved = opt.max_distance / 2.f;
+    invert_extrinsics(cam.extrinsics, fr.inv);
+    fr.keep_all = opt.keep_original_size ? 1 : 0; fr.fix_color_index = opt.fix_color_index ? 1 : 0;
+    for (DevBuf* pl : {&cl.x, &cl.y, &cl.z, &cl.nx, &cl.ny, &cl.nz}) if ((rc = ensure(c, *pl, (size_t)cap * 4))) return rc;
+    if (with_colors) { for (DevBuf* pl : {&cl.rgba, &cl.cr, &cl.cg, &cl.cb}) if ((rc = ensure(c, *pl, (size_t)cap * 4))) return rc; }
+    else for (DevBuf* pl : {&cl.rgba, &cl.cr, &cl.cg, &cl.cb}) release(*pl);      // no colour planes of an earlier, differently sized cloud stay behind
+    if ((rc = ensure(c, c->depth_blocks, (size_t)nb * 4))) return rc;
+    if ((rc = ensure(c, c->d_count, 16))) return rc;
+    if ((rc = ensure_pinned(c, 4096))) return rc;
+    DepthOut o;
+    o.x = cl.x.as<float>(); o.y = cl.y.as<float>(); o.z = cl.z.as<float>(); o.nx = cl.nx.as<float>(); o.ny = cl.ny.as<float>(); o.nz = cl.nz.as<float>();
+    o.cr = with_colors ? cl.cr.as<float>() : nullptr; o.cg = with_colors ? cl.cg.as<float>() : nullptr; o.cb = with_colors ? cl.cb.as<float>() : nullptr;
+    o.rgba = with_colors ? cl.rgba.as<uint32_t>() : nullptr;
+    hipLaunchKernelGGL(k_depth_count, dim3(nb), dim3(256), 0, c->stream, fr, c->depth_blocks.as<int>());
+    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, c->stream, c->depth_blocks.as<int>(), nb, c->d_count.as<int>());
+    hipLaunchKernelGGL(k_depth_scatter, dim3(nb), dim3(256), 0, c->stream, fr, (const int*)c->depth_blocks.as<int>(), (const int*)c->d_count.as<int>(), pad ? 1 : 0, o);
+    HIPCK(c, hipGetLastError());
+    int* h = (int*)((char*)c->pinned + 2048);            // (the first bytes of the pinned block stage the pose)
+    HIPCK(c, hipMemcpyAsync(h, c->d_count.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    const int kept = *h;
+    cl.n = kept; cl.npad = pad ? (kept + 63) / 64 * 64 : kept;
+    cl.has_normals = true; cl.has_colors = with_colors;
+    *n_out = kept;
+    return ICP_OK;
+}
+
+// ConvergenceMeasure::rmseAlignmentError of the resident convergence reference under the device pose state -> *d_out (device)
+int enqueue_rmse(icp_ctx* c, float* d_out) {
+    int rc;
+    if ((rc = ensure(c, c->rmse_partials, 256 * 2 * 8))) return rc;
+    hipLaunchKernelGGL(k_rmse_partial, dim3(256), dim3(256), 0, c->stream, c->conv_src.x.as<float>(), c->conv_src.y.as<float>(), c->conv_src.z.as<float>(),
+                       c->conv_ref.x.as<float>(), c->conv_ref.y.as<float>(), c->conv_ref.z.as<float>(), c->conv_n, c->ps.as<PoseState>(), c->rmse_partials.as<double>());
+    hipLaunchKernelGGL(k_rmse_finish, dim3(1), dim3(64), 0, c->stream, c->rmse_partials.as<double>(), 256, d_out);
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -828,6 +968,14 @@ int icp_ctx_destroy(icp_ctx* c) {
     release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->pring); release(c->totals); release(c->dbg_steps); release(c->sums); release(c->gx_slots); release(c->gx_hdr);
     release(c->stats); release(c->staging); release(c->rmse_partials); release(c->rmse_out); release(c->fontana_partials);
     for (DevBuf* d : {&c->src_flag, &c->src_box, &c->tgt_flag, &c->tgt_finite, &c->nrm_finite, &c->sel_temp, &c->d_count}) release(*d);
+    if (c->depth_stream) { (void)hipStreamSynchronize(c->depth_stream); (void)hipStreamDestroy(c->depth_stream); }
+    for (int k = 0; k < 2; k++) {
+        release(c->depth_dev[k]);
+        if (c->depth_pin[k]) (void)hipHostFree(c->depth_pin[k]);
+        if (c->depth_up[k]) (void)hipEventDestroy(c->depth_up[k]);
+    }
+    release(c->depth_blocks); release(c->track_rmse);
+    if (c->pin_track) (void)hipHostFree(c->pin_track);
     if (c->pin_up) (void)hipHostFree(c->pin_up);
     if (c->up_ev) (void)hipEventDestroy(c->up_ev);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -861,19 +1009,7 @@ int icp_set_target(icp_ctx* c, const float* xyz, const float* normals, const uin
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if ((rc = upload_cloud(c, c->tgt, xyz, normals, rgba, n, true))) return rc;
-    Bvh& b = c->bvh;
-    c->bvh6.valid = false;
-    b.valid = false; b.n_valid = 0;
-    // non-finite targets can never win the strict-< argmin: they stay out of the tree (filter + compaction on the device)
-    if ((rc = finite_list(c, c->tgt, false, c->tgt_flag, c->tgt_finite, &b.n_valid))) return rc;
-    b.d_finite = c->tgt_finite.as<int>(); b.n_ids = n;
-    c->bvh6.d_finite = b.d_finite; c->bvh6.n_valid = b.n_valid; c->bvh6.n_ids = n;
-    b.attrs = &c->tgt; c->bvh6.attrs = &c->tgt;
-    if (c->prm.knn_backend == ICP_KNN_LBVH && c->prm.matching == ICP_MATCH_KNN) {                         // buildIndex; otherwise built on first use
-        if (c->prm.color_icp && rgba) return guard.done(build_bvh<6>(c, c->bvh6, target_coords6(c)));
-        return guard.done(build_bvh<3>(c, b, target_coords3(c)));
-    }
-    return guard.done();
+    return guard.done(finish_target(c, rgba != nullptr));
 }
 
 // Not part of icp_hip.h (icp_batch_run's own): the resident SOURCE becomes the target -- what icp_set_target(the same arrays) would leave,
@@ -899,15 +1035,7 @@ int icp_internal_promote_source_to_target(icp_ctx* c) {
     hipLaunchKernelGGL(k_copy_planes_pad, dim3((npad + 255) / 256, 6), dim3(256), 0, c->stream, pl, n, npad);
     HIPCK(c, hipGetLastError());
     tg.n = n; tg.npad = npad; tg.has_normals = sc.has_normals; tg.has_colors = false;
-    Bvh& b = c->bvh;
-    c->bvh6.valid = false;
-    b.valid = false; b.n_valid = 0;
-    if ((rc = finite_list(c, c->tgt, false, c->tgt_flag, c->tgt_finite, &b.n_valid))) return rc;
-    b.d_finite = c->tgt_finite.as<int>(); b.n_ids = n;
-    c->bvh6.d_finite = b.d_finite; c->bvh6.n_valid = b.n_valid; c->bvh6.n_ids = n;
-    b.attrs = &c->tgt; c->bvh6.attrs = &c->tgt;
-    if (c->prm.knn_backend == ICP_KNN_LBVH && c->prm.matching == ICP_MATCH_KNN) return guard.done(build_bvh<3>(c, b, target_coords3(c)));
-    return guard.done();
+    return guard.done(finish_target(c, false));
 }
 
 int icp_set_source(icp_ctx* c, const float* xyz, const float* normals, const uint8_t* rgba, int32_t n) {
@@ -916,19 +1044,8 @@ int icp_set_source(icp_ctx* c, const float* xyz, const float* normals, const uin
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if ((rc = upload_cloud(c, c->src, xyz, normals, rgba, n, false))) return rc;
-    // validity of a source point for the multi-resolution selections (finite point && finite normal, PointCloud.h:334) and the
-    // bounding box of the finite points (Morton order of the queries): both on the device, nothing waits for them here
-    if ((rc = ensure(c, c->src_flag, (size_t)n))) return rc;
-    if ((rc = ensure(c, c->src_box, 32))) return rc;
-    hipLaunchKernelGGL(k_mark_finite, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->src.x.as<float>(), c->src.y.as<float>(), c->src.z.as<float>(),
-                       normals ? c->src.nx.as<float>() : nullptr, normals ? c->src.ny.as<float>() : nullptr, normals ? c->src.nz.as<float>() : nullptr, n, c->src_flag.as<uint8_t>());
-    HIPCK(c, hipMemsetAsync(c->src_box.p, 0xFF, 12, c->stream));
-    HIPCK(c, hipMemsetAsync((char*)c->src_box.p + 12, 0x00, 12, c->stream));
-    hipLaunchKernelGGL(k_bbox, dim3(256), dim3(256), 0, c->stream, c->src.x.as<float>(), c->src.y.as<float>(), c->src.z.as<float>(), n, c->src_box.as<unsigned int>());
-    HIPCK(c, hipGetLastError());
+    if ((rc = finish_source(c))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));           // entry-point contract: the caller's arrays are free, the stream is idle
-    for (auto& kv : c->levels) release(kv.second);
-    c->levels.clear();
     return guard.done();
 }
 
@@ -1470,12 +1587,8 @@ int icp_rmse(icp_ctx* c, const float pose[16], float* rmse_out) {
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if ((rc = write_pose(c, pose))) return rc;
-    if ((rc = ensure(c, c->rmse_partials, 256 * 2 * 8))) return rc;
     if ((rc = ensure(c, c->rmse_out, 4))) return rc;
-    hipLaunchKernelGGL(k_rmse_partial, dim3(256), dim3(256), 0, c->stream, c->conv_src.x.as<float>(), c->conv_src.y.as<float>(), c->conv_src.z.as<float>(),
-                       c->conv_ref.x.as<float>(), c->conv_ref.y.as<float>(), c->conv_ref.z.as<float>(), c->conv_n, c->ps.as<PoseState>(), c->rmse_partials.as<double>());
-    hipLaunchKernelGGL(k_rmse_finish, dim3(1), dim3(64), 0, c->stream, c->rmse_partials.as<double>(), 256, c->rmse_out.as<float>());
-    HIPCK(c, hipGetLastError());
+    if ((rc = enqueue_rmse(c, c->rmse_out.as<float>()))) return rc;
     HIPCK(c, hipMemcpyAsync(rmse_out, c->rmse_out.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return guard.done();
@@ -1489,16 +1602,8 @@ int icp_backproject_depth(icp_ctx* c, const float* depth, const uint8_t* rgbx, f
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     const size_t n = (size_t)width * height;
-    // depthExtrinsics.inverse() (PointCloud.h:88-90): rigid/affine 4x4, inverted in fp64 and rounded once
-    double R[9], t[3];
-    for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) R[r * 3 + k] = extrinsics[k * 4 + r]; t[r] = extrinsics[12 + r]; }
-    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-    double Ri[9] = {(R[4] * R[8] - R[5] * R[7]) / det, (R[2] * R[7] - R[1] * R[8]) / det, (R[1] * R[5] - R[2] * R[4]) / det,
-                    (R[5] * R[6] - R[3] * R[8]) / det, (R[0] * R[8] - R[2] * R[6]) / det, (R[2] * R[3] - R[0] * R[5]) / det,
-                    (R[3] * R[7] - R[4] * R[6]) / det, (R[1] * R[6] - R[0] * R[7]) / det, (R[0] * R[4] - R[1] * R[3]) / det};
     float inv[12];
-    for (int i = 0; i < 9; i++) inv[i] = (float)Ri[i];
-    for (int r = 0; r < 3; r++) inv[9 + r] = (float)(-(Ri[r * 3] * t[0] + Ri[r * 3 + 1] * t[1] + Ri[r * 3 + 2] * t[2]));
+    invert_extrinsics(extrinsics, inv);
     // fixed layout, colour slots always reserved: [depth 4n | rgbx 4n | inverse 64 | xyz 12n | normals 12n | rgba 4n | valid n]
     const size_t bytes = n * 4 + n * 4 + 64 + n * 12 * 2 + n * 4 + n;
     if ((rc = ensure(c, c->staging, bytes + 256))) return rc;
@@ -1517,6 +1622,127 @@ int icp_backproject_depth(icp_ctx* c, const float* depth, const uint8_t* rgbx, f
     if (valid_out) HIPCK(c, hipMemcpyAsync(valid_out, d_valid, n, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return guard.done();
+}
+
+static int set_cloud_depth(icp_ctx* c, bool target, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const icp_depth_options* opt, int32_t* n_points_out) {
+    const char* who = target ? "icp_set_target_depth" : "icp_set_source_depth";
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (n_points_out) *n_points_out = 0;
+    if (!depth) { c->err = std::string(who) + ": null depth frame"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = check_depth_args(c, cam, opt, who))) return rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    int kept = 0;
+    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = depth_to_cloud(c, 0, *cam, *opt, rgbx != nullptr, target ? c->tgt : c->src, target, &kept))) return rc;
+    if (n_points_out) *n_points_out = kept;
+    if (target) {
+        if (kept == 0) { c->bvh.valid = false; c->bvh6.valid = false; c->err = "icp_set_target_depth: the frame keeps no points"; return guard.done(ICP_ERR_NO_TARGET); }
+        if ((rc = finish_target(c, rgbx != nullptr))) return rc;
+    } else {
+        if ((rc = finish_source(c))) return rc;
+        if (kept == 0) { c->err = "icp_set_source_depth: the frame keeps no points"; return guard.done(ICP_ERR_NO_SOURCE); }
+    }
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+int icp_set_target_depth(icp_ctx* c, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const icp_depth_options* opt, int32_t* n_points_out) {
+    return set_cloud_depth(c, true, depth, rgbx, cam, opt, n_points_out);
+}
+int icp_set_source_depth(icp_ctx* c, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const icp_depth_options* opt, int32_t* n_points_out) {
+    return set_cloud_depth(c, false, depth, rgbx, cam, opt, n_points_out);
+}
+
+int icp_track_depth_frames(icp_ctx* c, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames, const icp_depth_camera* cam,
+                           const icp_depth_options* target_opt, const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16],
+                           icp_track_frame* out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!depth_frames || n_frames < 1 || !pose_inout || (n_frames > 1 && !out)) { c->err = "icp_track_depth_frames: bad argument"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = check_depth_args(c, cam, target_opt, "icp_track_depth_frames")) || (rc = check_depth_args(c, cam, source_opt, "icp_track_depth_frames"))) return rc;
+    const icp_params& p = c->prm;
+    if (p.matching == ICP_MATCH_PROJECTIVE) {
+        // the projective matcher indexes the target by pixel: the organised frame 0 (main.cpp:201-207) seen through the same camera
+        if (!target_opt->keep_original_size || target_opt->downsample_factor != 1) { c->err = "icp_track_depth_frames: projective matching needs an organised target (keep_original_size = 1, factor 1)"; return ICP_ERR_INVALID_ARG; }
+        if (p.fx != cam->fx || p.fy != cam->fy || p.cx != cam->cx || p.cy != cam->cy || p.width != cam->width || p.height != cam->height) {
+            c->err = "icp_track_depth_frames: the camera of the params differs from the depth camera"; return ICP_ERR_INVALID_ARG;
+        }
+    }
+    if (!rgbx_frames && ((p.matching == ICP_MATCH_KNN && p.color_icp) || p.weighting == ICP_WEIGHT_COLORS)) { c->err = "icp_track_depth_frames: colour ICP needs the colour frames"; return ICP_ERR_INVALID_ARG; }
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const int n = cam->width * cam->height;
+    const size_t fbytes = (size_t)n * 4;
+    auto frame_rgbx = [&](int k) { return rgbx_frames ? rgbx_frames + (size_t)k * fbytes : nullptr; };
+    if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream, hipStreamNonBlocking));
+    // frame 0 = the target, its index built once (main.cpp:200-207); frame 1 goes up meanwhile
+    int kept = 0;
+    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
+    if ((rc = depth_to_cloud(c, 0, *cam, *target_opt, rgbx_frames != nullptr, c->tgt, true, &kept))) return rc;
+    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream))) return rc;
+    if (kept == 0) {
+        c->bvh.valid = false; c->bvh6.valid = false;
+        for (int k = 1; k < n_frames; k++) { icp_track_frame& r = out[k - 1]; memset(&r, 0, sizeof(r)); r.status = ICP_ERR_NO_TARGET; r.initial_rmse = r.final_rmse = -1.f; memcpy(r.pose, pose_inout, 64); }
+        c->err = "icp_track_depth_frames: frame 0 keeps no points";
+        HIPCK(c, hipStreamSynchronize(c->depth_stream));
+        return guard.done(ICP_ERR_NO_TARGET);
+    }
+    if ((rc = finish_target(c, rgbx_frames != nullptr))) return rc;
+    if (gt_frames && n_frames > 1) {
+        if ((rc = ensure(c, c->track_rmse, (size_t)(n_frames - 1) * 8))) return rc;
+        if (!c->pin_track) HIPCK(c, hipHostMalloc((void**)&c->pin_track, 2 * sizeof(PoseState), hipHostMallocDefault));
+    }
+    int first_err = ICP_OK;
+    for (int k = 1; k < n_frames; k++) {
+        icp_track_frame& r = out[k - 1];
+        memset(&r, 0, sizeof(r)); r.initial_rmse = r.final_rmse = -1.f;
+        const int slot = k & 1;
+        if ((rc = depth_to_cloud(c, slot, *cam, *source_opt, rgbx_frames != nullptr, c->src, false, &kept))) return rc;
+        // frame k + 1 goes up on the second stream while frame k iterates (its slot was last read by frame k - 1, which has finished)
+        if (k + 1 < n_frames && (rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream))) return rc;
+        if ((rc = finish_source(c))) return rc;
+        r.n_src = kept;
+        if (kept == 0) {                                   // nothing to align: the pose is carried unchanged, tracking goes on
+            r.status = ICP_ERR_NO_SOURCE; memcpy(r.pose, pose_inout, 64);
+            if (first_err == ICP_OK) { first_err = ICP_ERR_NO_SOURCE; c->err = "icp_track_depth_frames: a frame keeps no points"; }
+            continue;
+        }
+        float* d_rmse = gt_frames ? c->track_rmse.as<float>() + (size_t)(k - 1) * 2 : nullptr;
+        if (gt_frames) {
+            // ConvergenceMeasure(source, transformPoints(source, targetTrajectory * trajectory_k^-1)) (main.cpp:296-305), on the device
+            Pose16 g; memcpy(g.m, gt_frames + (size_t)(k - 1) * 16, 64);
+            for (DevBuf* pl : {&c->conv_src.x, &c->conv_src.y, &c->conv_src.z, &c->conv_ref.x, &c->conv_ref.y, &c->conv_ref.z}) if ((rc = ensure(c, *pl, (size_t)kept * 4))) return rc;
+            hipLaunchKernelGGL(k_conv_from_source, dim3((kept + 255) / 256), dim3(256), 0, c->stream, c->src.x.as<float>(), c->src.y.as<float>(), c->src.z.as<float>(), kept, g,
+                               c->conv_src.x.as<float>(), c->conv_src.y.as<float>(), c->conv_src.z.as<float>(), c->conv_ref.x.as<float>(), c->conv_ref.y.as<float>(), c->conv_ref.z.as<float>());
+            HIPCK(c, hipGetLastError());
+            c->conv_n = kept;
+            // initial_rmse = rmseAlignmentError(currentCameraToWorld) (:305).  Its pose is staged in pin_track[0], not in `pinned`: run_loop's
+            // write_pose rewrites `pinned` right after this, while this copy may still wait behind the kernels above.  pin_track[0] / [1]
+            // are rewritten only by the next frame, after depth_to_cloud has synchronised the stream (the count read), i.e. after both
+            // copies have left them; the end of the call synchronises before the last ones matter.
+            if ((rc = write_pose_via(c, &c->pin_track[0], pose_inout))) return rc;
+            if ((rc = enqueue_rmse(c, d_rmse))) return rc;
+        }
+        int32_t iters = 0;
+        rc = run_loop(c, pose_inout, nullptr, 0, &iters, false);          // estimatePose(source, target, currentCameraToWorld) (:308)
+        if (rc == ICP_ERR_HIP) return rc;
+        r.iterations = iters; r.status = rc;
+        memcpy(r.pose, pose_inout, 64);
+        if (rc != ICP_OK && first_err == ICP_OK) first_err = rc;
+        if (gt_frames) {
+            if ((rc = write_pose_via(c, &c->pin_track[1], pose_inout))) return rc;   // final RMSE (:311)
+            if ((rc = enqueue_rmse(c, d_rmse + 1))) return rc;
+        }
+    }
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (gt_frames && n_frames > 1) {
+        std::vector<float> h((size_t)(n_frames - 1) * 2);
+        HIPCK(c, hipMemcpy(h.data(), c->track_rmse.p, h.size() * 4, hipMemcpyDeviceToHost));
+        for (int k = 1; k < n_frames; k++) if (out[k - 1].n_src > 0) { out[k - 1].initial_rmse = h[(size_t)(k - 1) * 2]; out[k - 1].final_rmse = h[(size_t)(k - 1) * 2 + 1]; }
+    }
+    guard.ok = true;
+    return first_err;
 }
 
 int icp_estimate_normals(icp_ctx* c, const float* xyz, int32_t n, int32_t k, const float viewpoint[3], float* normals_out, float* curvature_out) {

@@ -20,6 +20,7 @@ ICP_OK = 0
 ERR_NAMES = {1: "INVALID_ARG", 2: "HIP", 3: "NO_TARGET", 4: "NO_SOURCE", 5: "NO_CAMERA", 6: "TARGET_SIZE",
              7: "COLOR_MISMATCH", 8: "NO_CORRESPONDENCES", 9: "NO_DEVICE", 10: "COMM"}
 ERR_NO_CORRESPONDENCES = 8
+ERR_NO_SOURCE = 4
 
 
 class IcpError(RuntimeError):
@@ -53,6 +54,35 @@ class IcpPair(C.Structure):
                 ("initial_pose", C.c_float * 16)]
 
 
+class IcpDepthCamera(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_int32), ("height", C.c_int32),
+                ("extrinsics", C.c_float * 16)]
+
+
+class IcpDepthOptions(C.Structure):
+    _fields_ = [("keep_original_size", C.c_int32), ("downsample_factor", C.c_int32), ("max_distance", C.c_float), ("fix_color_index", C.c_int32)]
+
+
+class IcpTrackFrame(C.Structure):
+    _fields_ = [("n_src", C.c_int32), ("iterations", C.c_int32), ("status", C.c_int32), ("initial_rmse", C.c_float), ("final_rmse", C.c_float),
+                ("pose", C.c_float * 16)]
+
+
+def depth_camera(K, width, height, extrinsics=None):
+    """icp_depth_camera from a 3x3 intrinsic matrix (K(0,0), K(1,1), K(0,2), K(1,2)) and an optional 4x4 depthExtrinsics."""
+    K = np.asarray(K, dtype=np.float32)
+    cam = IcpDepthCamera(float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), int(width), int(height))
+    E = pose_to_c(np.eye(4) if extrinsics is None else extrinsics)
+    for k in range(16):
+        cam.extrinsics[k] = float(E[k])
+    return cam
+
+
+def depth_options(keep_original_size=False, downsample_factor=1, max_distance=0.1, fix_color_index=False):
+    """icp_depth_options: the constructor arguments of PointCloud(depthMap, ...) (PointCloud.h:78)."""
+    return IcpDepthOptions(int(bool(keep_original_size)), int(downsample_factor), float(max_distance), int(bool(fix_color_index)))
+
+
 COMM_ID_BYTES = 128
 
 # every symbol include/icp_hip.h declares (tests check the library exports all of them)
@@ -60,6 +90,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_set_params", "icp_get_params", "icp_set_target", "icp_set_source", "icp_query_matches", "icp_match", "icp_match_seeded",
            "icp_correspond", "icp_iterate", "icp_run", "icp_get_timing", "icp_get_iteration_times", "icp_set_stage_timing", "icp_set_convergence_reference", "icp_rmse", "icp_benchmark_error",
            "icp_transform_points", "icp_transform_normals", "icp_version", "icp_schedule", "icp_select_hash", "icp_backproject_depth", "icp_estimate_normals",
+           "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
 
@@ -247,6 +278,56 @@ class Context:
                                                 _ptr(E), C.c_int32(w), C.c_int32(h), C.c_float(max_distance), C.c_int32(int(fix_color_index)),
                                                 _ptr(xyz), _ptr(nrm), _ptr(rgba), _ptr(valid)))
         return xyz, nrm, rgba, valid.astype(bool)
+
+    def _set_depth(self, fn, depth, rgbx, cam, opt, check):
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if depth.size != cam.width * cam.height:
+            raise ValueError("depth frame has %d pixels, the camera %d x %d" % (depth.size, cam.width, cam.height))
+        rgbx = None if rgbx is None else np.ascontiguousarray(rgbx, dtype=np.uint8)
+        if rgbx is not None and rgbx.size != 4 * depth.size:
+            raise ValueError("colour frame must hold 4 bytes per pixel")
+        n = C.c_int32(0)
+        rc = fn(self.h, _ptr(depth), _ptr(rgbx), C.byref(cam), C.byref(opt), C.byref(n))
+        if check:
+            self._ck(rc)
+        return n.value, rc
+
+    def set_target_depth(self, depth, rgbx, cam, opt, check=True):
+        """icp_set_target_depth: PointCloud(depthMap, colorFrame, ...) (PointCloud.h:78-165) built on the device as the target.
+        cam / opt: depth_camera(...) / depth_options(...).  Returns the number of kept points (and the status with check=False)."""
+        n, rc = self._set_depth(self.lib.icp_set_target_depth, depth, rgbx, cam, opt, check)
+        self.n_tgt = n
+        return n if check else (n, rc)
+
+    def set_source_depth(self, depth, rgbx, cam, opt, check=True):
+        """icp_set_source_depth: the same constructor on the device, as the source."""
+        n, rc = self._set_depth(self.lib.icp_set_source_depth, depth, rgbx, cam, opt, check)
+        self.n_src = n
+        return n if check else (n, rc)
+
+    def track_depth_frames(self, depth_frames, rgbx_frames, cam, target_opt, source_opt, gt=None, pose=None):
+        """icp_track_depth_frames: reconstructRoom's tracking loop (main.cpp:183-341) over frames (n, h, w) [+ colours (n, h*w, 4)].
+        gt: (n - 1) 4x4 transforms frame k -> frame 0, or None.  pose: initial currentCameraToWorld (identity by default).
+        Returns (final pose, list of per-frame records for frames 1 .. n-1, status)."""
+        d = np.ascontiguousarray(depth_frames, dtype=np.float32)
+        nf = d.shape[0]
+        if d.size != nf * cam.width * cam.height:
+            raise ValueError("depth frames do not match the camera size")
+        cols = None if rgbx_frames is None else np.ascontiguousarray(rgbx_frames, dtype=np.uint8)
+        if cols is not None and cols.size != 4 * d.size:
+            raise ValueError("colour frames must hold 4 bytes per pixel")
+        g = None if gt is None else np.ascontiguousarray(np.stack([pose_to_c(T) for T in gt]) if len(gt) else np.zeros((0, 16)), dtype=np.float32)
+        if g is not None and len(g) != nf - 1:
+            raise ValueError("gt needs one transform per tracked frame")
+        p = pose_to_c(np.eye(4) if pose is None else pose)
+        out = (IcpTrackFrame * max(nf - 1, 1))()
+        rc = self.lib.icp_track_depth_frames(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(target_opt), C.byref(source_opt),
+                                             _ptr(g), _ptr(p), out)
+        if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
+            self._ck(rc)
+        recs = [dict(n_src=out[i].n_src, iterations=out[i].iterations, status=out[i].status, initial_rmse=out[i].initial_rmse,
+                     final_rmse=out[i].final_rmse, pose=pose_from_c(out[i].pose)) for i in range(nf - 1)]
+        return pose_from_c(p), recs, rc
 
     def estimate_normals(self, xyz, k=5, viewpoint=(0.0, 0.0, 0.0)):
         """PointCloud(pcl cloud): k-NN PCA normals flipped towards the viewpoint (PointCloud.h:41-76)."""

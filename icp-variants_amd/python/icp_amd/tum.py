@@ -1,0 +1,136 @@
+"""Host side of the RGB-D tracking runner (reference: VirtualSensor.h and reconstructRoom, main.cpp:183-341).
+
+Pure host logic over `formats.py`; the tracking itself is one library call (`icp_track_depth_frames`):
+  seq            = load_sequence(tum_dir)                     # VirtualSensor(frameStep).init + processFrameIndex(0, (i+1) * step, ...)
+  tgt_o, src_o   = reconstruct_room_options(params)           # the reference's choice of clouds, 35 iterations, max distance 0.1
+  poses, recs    = track(ctx, seq, params)                    # estimatedPoses (currentCameraToWorld^-1 per frame) + per-frame records
+Layout on disk, as the reference expects it under Data/: <tum_dir>/depth.txt, rgb.txt, groundtruth.txt and the PNGs they list (TUM RGB-D).
+`write_synthetic_sequence` writes that layout from `synth.depth_frame` / `synth.camera_pose`, for the tests and for rehearsing a real
+freiburg1_xyz run offline.
+"""
+import os
+import numpy as np
+
+from . import binding, formats, synth
+
+TUM_K = np.array([[525.0, 0.0, 319.5], [0.0, 525.0, 239.5], [0.0, 0.0, 1.0]], np.float32)     # VirtualSensor.h:44-46
+TUM_WIDTH, TUM_HEIGHT = 640, 480
+
+
+def frame_schedule(n_frames, frame_step=10, i_max=10):
+    """Frame indices reconstructRoom processes: 0, then (i + 1) * frame_step while that frame exists and i <= i_max (main.cpp:278-281)."""
+    out = [0]
+    i = 0
+    while (i + 1) * frame_step < n_frames and i <= i_max:
+        out.append((i + 1) * frame_step)
+        i += 1
+    return out
+
+
+def load_sequence(tum_dir, frame_step=10, i_max=10, K=None):
+    """Depth (MINF holes), RGBX bytes and ground-truth pose of every scheduled frame.  Returns a dict with
+    frames (indices), depth (n, h, w) float32, rgbx (n, h*w, 4) uint8, trajectory (n 4x4: the nearest-timestamp pose, stored inverted as
+    readTrajectoryFile does), gt ((n - 1) 4x4: targetTrajectory * trajectory_k^-1, main.cpp:298-300), K, width, height."""
+    d_ts, d_names = formats.read_tum_file_list(os.path.join(tum_dir, "depth.txt"))
+    c_ts, c_names = formats.read_tum_file_list(os.path.join(tum_dir, "rgb.txt"))
+    t_ts, t_poses = formats.read_tum_trajectory(os.path.join(tum_dir, "groundtruth.txt"))
+    if len(d_names) != len(c_names):
+        raise ValueError("depth.txt and rgb.txt list different numbers of frames (VirtualSensor.h:35)")
+    frames = frame_schedule(len(c_names), frame_step, i_max)
+    depth, rgbx, traj = [], [], []
+    for k in frames:
+        d, c = formats.load_tum_frame(tum_dir, d_names[k], c_names[k])
+        depth.append(d); rgbx.append(c)
+        traj.append(np.asarray(formats.nearest_pose(t_ts, t_poses, d_ts[k]), np.float32))
+    h, w = depth[0].shape
+    target_traj = traj[0]
+    gt = [(target_traj @ np.linalg.inv(T)).astype(np.float32) for T in traj[1:]]
+    return dict(frames=frames, depth=np.stack(depth), rgbx=np.stack(rgbx), trajectory=traj, gt=gt,
+                K=np.asarray(TUM_K if K is None else K, np.float32), width=w, height=h)
+
+
+def reconstruct_room_options(params):
+    """(target, source) icp_depth_options of reconstructRoom for the given icp_params: target keepOriginalSize = projective matching,
+    factor 1 (main.cpp:201-207); source (true, 1) with multi-resolution, else (false, 8) (main.cpp:287-292); maxDistance 0.1 (PointCloud.h:78)."""
+    tgt = binding.depth_options(keep_original_size=params.matching == 1, downsample_factor=1)
+    src = binding.depth_options(keep_original_size=True, downsample_factor=1) if params.multires else binding.depth_options(False, 8)
+    return tgt, src
+
+
+def reconstruct_room_params(params, K=TUM_K, width=TUM_WIDTH, height=TUM_HEIGHT):
+    """The optimizer settings reconstructRoom adds on top of the chosen variant: 35 iterations, setMatchingMaxDistance(0.1), and the
+    depth camera for projective matching (main.cpp:227-250).  Modifies and returns `params`."""
+    params.n_iterations = 35
+    params.max_distance = 0.1
+    if params.matching == 1:
+        K = np.asarray(K, np.float32)
+        params.fx, params.fy, params.cx, params.cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+        params.width, params.height = int(width), int(height)
+    return params
+
+
+def track(ctx, seq, params=None, with_gt=True):
+    """reconstructRoom's loop on the device.  params: the variant's icp_params (metric, matching, colour ICP, weighting, multires, ...;
+    ctx.params when None); reconstruct_room_params then sets what reconstructRoom sets on top of them -- 35 iterations, max distance 0.1
+    and, for projective matching, the sequence's camera.  Returns (camera poses: the identity for frame 0, then currentCameraToWorld^-1
+    after every frame (main.cpp:267-269,318-320), per-frame records, status)."""
+    if params is not None:
+        ctx.params = params
+    reconstruct_room_params(ctx.params, seq["K"], seq["width"], seq["height"])
+    ctx.push_params()
+    cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
+    tgt_o, src_o = reconstruct_room_options(ctx.params)
+    _, recs, rc = ctx.track_depth_frames(seq["depth"], seq["rgbx"], cam, tgt_o, src_o, gt=seq["gt"] if with_gt else None)
+    poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
+    return poses, recs, rc
+
+
+def _write_list(path, header, rows):
+    with open(path, "w") as f:
+        f.write("# %s\n# file: synthetic\n# timestamp filename\n" % header)
+        for r in rows:
+            f.write(r + "\n")
+
+
+def write_synthetic_sequence(tum_dir, n_frames, width=TUM_WIDTH, height=TUM_HEIGHT, K=None, seed=0x7A11, hole_frac=0.05, dt=1.0 / 30):
+    """Writes frames 0 .. n_frames-1 of `synth.camera_pose` in the TUM RGB-D layout: 16-bit depth PNGs (metres x 5000, 0 = hole),
+    RGB PNGs, depth.txt / rgb.txt and groundtruth.txt ('t tx ty tz qx qy qz qw' of the camera-to-world pose, which
+    read_tum_trajectory stores inverted).  Returns dict(depth=(n, h, w) float32 metres as written, with MINF holes, poses=camera-to-world)."""
+    from PIL import Image
+    K = np.asarray(TUM_K if K is None else K, np.float64)
+    os.makedirs(os.path.join(tum_dir, "depth"), exist_ok=True)
+    os.makedirs(os.path.join(tum_dir, "rgb"), exist_ok=True)
+    d_rows, c_rows, g_rows, depths, poses = [], [], [], [], []
+    for k in range(n_frames):
+        T = synth.camera_pose(k, seed)
+        pts, _, rgba = synth.depth_frame(T, K, width, height, seed + k, hole_frac)
+        z = pts[:, 2].astype(np.float64)
+        raw = np.where(np.isfinite(z), np.round(z * 5000.0), 0.0)
+        raw = np.clip(raw, 0, 65535).astype(np.uint16).reshape(height, width)
+        ts = 1000.0 + k * dt
+        dn, cn = "depth/%.6f.png" % ts, "rgb/%.6f.png" % ts
+        Image.fromarray(raw).save(os.path.join(tum_dir, dn))
+        Image.fromarray(rgba[:, :3].reshape(height, width, 3)).save(os.path.join(tum_dir, cn))
+        d_rows.append("%.6f %s" % (ts, dn)); c_rows.append("%.6f %s" % (ts, cn))
+        q = _rot_to_quat(T[:3, :3])
+        g_rows.append("%.6f %.9f %.9f %.9f %.9f %.9f %.9f %.9f" % ((ts,) + tuple(T[:3, 3]) + tuple(q)))
+        depths.append(formats.decode_tum_depth(raw)); poses.append(T)
+    _write_list(os.path.join(tum_dir, "depth.txt"), "depth maps", d_rows)
+    _write_list(os.path.join(tum_dir, "rgb.txt"), "color images", c_rows)
+    with open(os.path.join(tum_dir, "groundtruth.txt"), "w") as f:
+        f.write("# ground truth trajectory\n# file: synthetic\n# timestamp tx ty tz qx qy qz qw\n")
+        for r in g_rows:
+            f.write(r + "\n")
+    return dict(depth=np.stack(depths), poses=poses)
+
+
+def _rot_to_quat(R):
+    """(qx, qy, qz, qw) of a rotation matrix, qw >= 0."""
+    R = np.asarray(R, np.float64)
+    w = np.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2
+    x = np.sqrt(max(0.0, 1.0 + R[0, 0] - R[1, 1] - R[2, 2])) / 2
+    y = np.sqrt(max(0.0, 1.0 - R[0, 0] + R[1, 1] - R[2, 2])) / 2
+    z = np.sqrt(max(0.0, 1.0 - R[0, 0] - R[1, 1] + R[2, 2])) / 2
+    x = np.copysign(x, R[2, 1] - R[1, 2]); y = np.copysign(y, R[0, 2] - R[2, 0]); z = np.copysign(z, R[1, 0] - R[0, 1])
+    q = np.array([x, y, z, w])
+    return q / np.linalg.norm(q)

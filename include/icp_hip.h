@@ -180,6 +180,50 @@ int icp_backproject_depth(icp_ctx* ctx, const float* depth, const uint8_t* rgbx,
                           const float extrinsics[16], int32_t width, int32_t height, float max_distance, int32_t fix_color_index,
                           float* xyz_out, float* normals_out, uint8_t* rgba_out, uint8_t* valid_out);
 
+/* -------- depth frames straight into the resident clouds: PointCloud(depthMap, colorFrame, K, extrinsics, width, height,
+ * keepOriginalSize, downsampleFactor, maxDistance) (PointCloud.h:78-165) on the device --------
+ * Back-projection and normals as icp_backproject_depth computes them, then the constructor's stride and filter: pixels i = 0, f, 2f, ...
+ * (f = downsample_factor), kept when keep_original_size is set or point and normal are both finite, in pixel order.  The kept points go
+ * directly into the context's target / source (what icp_set_target / icp_set_source with the same arrays leave, index build included);
+ * only the kept-point count comes back to the host (*n_points_out, optional).  depth: width*height fp32 metres, MINF (-inf) = no
+ * measurement; rgbx: width*height*4 bytes or NULL (no colours on the cloud).  A frame that keeps no points leaves an empty cloud and
+ * returns ICP_ERR_NO_TARGET / ICP_ERR_NO_SOURCE. */
+typedef struct icp_depth_camera {
+    float fx, fy, cx, cy;            /* depth intrinsics, K(0,0), K(1,1), K(0,2), K(1,2) */
+    int32_t width, height;
+    float extrinsics[16];            /* depthExtrinsics, column-major (the points are moved by its inverse, the normals are not: PointCloud.h:128-129) */
+} icp_depth_camera;
+typedef struct icp_depth_options {
+    int32_t keep_original_size;      /* keepOriginalSize: keep invalid pixels as MINF entries (organised cloud when downsample_factor == 1) */
+    int32_t downsample_factor;       /* >= 1 */
+    float   max_distance;            /* maxDistance of the constructor (metres, NOT squared; default 0.1): normals need |gradient| <= max_distance / 2 */
+    int32_t fix_color_index;         /* 0: the reference's colour bytes i..i+3 for pixel i (PointCloud.h:156-157); 1: pixel i's own 4 bytes */
+} icp_depth_options;
+int icp_set_target_depth(icp_ctx* ctx, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const icp_depth_options* opt, int32_t* n_points_out);
+int icp_set_source_depth(icp_ctx* ctx, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const icp_depth_options* opt, int32_t* n_points_out);
+
+/* One record per tracked frame k >= 1 of icp_track_depth_frames. */
+typedef struct icp_track_frame {
+    int32_t n_src;                   /* points the frame kept (source size) */
+    int32_t iterations;              /* iterations icp_run ran */
+    int32_t status;                  /* ICP_OK, ICP_ERR_NO_SOURCE (frame kept no points: pose carried unchanged) or icp_run's status */
+    float   initial_rmse, final_rmse;/* rmseAlignmentError before / after estimatePose (main.cpp:305,311) with gt_frames, else -1 */
+    float   pose[16];                /* currentCameraToWorld after frame k, column-major */
+} icp_track_frame;
+/* The frame-to-reference tracking loop of reconstructRoom (main.cpp:183-341): frame 0 becomes the target (index built once), every later
+ * frame k the source of one icp_run with the context's params, starting from pose_inout (currentCameraToWorld, carried from frame to frame).
+ * depth_frames: n_frames x width*height fp32; rgbx_frames: n_frames x width*height*4 bytes or NULL (needed for colour ICP / colour
+ * weighting).  gt_frames (optional): (n_frames - 1) x 16 floats, the column-major transform of frame k's camera into frame 0's
+ * (targetTrajectory * trajectory_k^-1, main.cpp:298-300): the convergence reference of frame k is its source moved by it, built on the
+ * device.  Frame k + 1 is uploaded while frame k iterates.  With ICP_MATCH_PROJECTIVE the target options must be (1, 1) and the params'
+ * camera must equal cam (ICP_ERR_INVALID_ARG otherwise).  out: n_frames - 1 records.  Returns ICP_OK or the first error in frame order
+ * (like icp_batch_run); tracking continues past frames that keep no points.
+ * The context keeps what the call left: frame 0 as the target, the last tracked frame as the source and -- with gt_frames -- the last
+ * tracked frame's convergence reference, which REPLACES one set earlier with icp_set_convergence_reference (icp_rmse, record_rmse). */
+int icp_track_depth_frames(icp_ctx* ctx, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames,
+                           const icp_depth_camera* cam, const icp_depth_options* target_opt, const icp_depth_options* source_opt,
+                           const float* gt_frames, float pose_inout[16], icp_track_frame* out);
+
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
  * towards the viewpoint.  k in {3..8}.  Non-finite points get NaN normals.  curvature_out may be NULL.  Uses scratch
