@@ -5,7 +5,8 @@
 // PointCloud.h:41-76: setKSearch(5), viewpoint (0,0,0)): K-NN over the cloud's own kd-ordered BVH (the point itself is its
 // first neighbour, as with pcl::search::KdTree), fp64 covariance of the K points, eigenvector of the smallest eigenvalue
 // (fp64 Jacobi), flipped towards the viewpoint (pcl::flipNormalTowardsViewpoint), curvature = l0 / (l0 + l1 + l2).
-// Neighbour sets are the exact K smallest (d2, index) pairs.  PCL itself is absent here: parity unpinned, checked against numpy.
+// Neighbour sets are the exact K smallest (d2, index) pairs.  PCL itself is absent here: parity unpinned; every point is checked
+// against the oracle's orc_estimate_normals (tests/test_gpu_normals.py), which is cross-checked against numpy.
 template <int n> __device__ inline void jacobi_eig_sym(double* A, double* V, double* ev);     // defined with the solvers below
 
 template <int K>

@@ -226,7 +226,9 @@ int icp_track_depth_frames(icp_ctx* ctx, const float* depth_frames, const uint8_
 
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
- * towards the viewpoint.  k in {3..8}.  Non-finite points get NaN normals.  curvature_out may be NULL.  Uses scratch
+ * towards the viewpoint.  k in {3..8} (else ICP_ERR_INVALID_ARG).  Non-finite points, and every point of a cloud with fewer than
+ * 3 finite points, get NaN normals and curvature; fewer than k finite points: all of them are the neighbours; coincident
+ * neighbours (zero covariance): (+-1, 0, 0) flipped, curvature 0.  curvature_out may be NULL.  Uses scratch
  * buffers of the context only (target / source stay untouched). */
 int icp_estimate_normals(icp_ctx* ctx, const float* xyz, int32_t n, int32_t k, const float viewpoint[3], float* normals_out, float* curvature_out);
 

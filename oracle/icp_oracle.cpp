@@ -431,6 +431,58 @@ static void kd_query(const KdTree& t, int id, const float* p, float& best, int& 
     if (!(d2 * (1.0 - 1e-5) > (double)best)) kd_query(t, second, p, best, bi);
 }
 
+// K-candidate form of kd_query for the k-NN normals: (bd, bj) holds the K smallest (d2, index) pairs, sorted ascending
+// lexicographically, FLT_MAX / INT_MAX where nothing has been found yet.  Same leaf distance, same 1e-5 pruning margin
+// against the current K-th best; a candidate enters iff it beats the K-th pair lexicographically.
+static void kd_query_k(const KdTree& t, int id, const float* p, int K, float* bd, int* bj) {
+    const KdNode& nd = t.nodes[id];
+    if (nd.left < 0) {
+        for (int i = nd.begin; i < nd.end; i++) {
+            const float* q = &t.pts[(size_t)i*3];
+            float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+            float dist = (dx*dx + dy*dy) + dz*dz;
+            int j = t.perm[i];
+            if (dist < bd[K-1] || (dist == bd[K-1] && j < bj[K-1])) {
+                int q2 = K - 1;
+                while (q2 > 0 && (dist < bd[q2-1] || (dist == bd[q2-1] && j < bj[q2-1]))) { bd[q2] = bd[q2-1]; bj[q2] = bj[q2-1]; q2--; }
+                bd[q2] = dist; bj[q2] = j;
+            }
+        }
+        return;
+    }
+    const KdNode& L = t.nodes[nd.left]; const KdNode& R = t.nodes[nd.right];
+    double dl = kd_box_d2(L, p), dr = kd_box_d2(R, p);
+    int first = nd.left, second = nd.right; double d1 = dl, d2 = dr;
+    if (dr < dl) { first = nd.right; second = nd.left; d1 = dr; d2 = dl; }
+    if (!(d1 * (1.0 - 1e-5) > (double)bd[K-1])) kd_query_k(t, first, p, K, bd, bj);
+    if (!(d2 * (1.0 - 1e-5) > (double)bd[K-1])) kd_query_k(t, second, p, K, bd, bj);
+}
+
+// Cyclic Jacobi eigen-decomposition of a symmetric 3x3 in fp64 (A destroyed; eigenvalues on its diagonal, eigenvectors in the
+// columns of V).  Written to the device solver's contract: pairs p < q in row order, up to 50 sweeps, stop when the squared
+// off-diagonal mass is <= 1e-300 or <= 1e-34 x the squared diagonal mass, the rotated a_pq (and a_qp) set to an exact zero.
+static void jacobi3(double* A, double* V, double* ev) {
+    const int n = 3;
+    for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) V[i*n+j] = (i == j) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 50; sweep++) {
+        double off = 0.0, dg = 0.0;
+        for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) { if (i != j) off += A[i*n+j] * A[i*n+j]; else dg += A[i*n+j] * A[i*n+j]; }
+        if (off <= 1e-300 || off <= 1e-34 * dg) break;
+        for (int p = 0; p < n - 1; p++) for (int q = p + 1; q < n; q++) {
+            const double apq = A[p*n+q];
+            if (apq == 0.0) continue;
+            const double theta = (A[q*n+q] - A[p*n+p]) / (2.0 * apq);
+            const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+            const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+            for (int k = 0; k < n; k++) { const double a = A[k*n+p], b = A[k*n+q]; A[k*n+p] = c * a - s * b; A[k*n+q] = s * a + c * b; }
+            for (int k = 0; k < n; k++) { const double a = A[p*n+k], b = A[q*n+k]; A[p*n+k] = c * a - s * b; A[q*n+k] = s * a + c * b; }
+            for (int k = 0; k < n; k++) { const double a = V[k*n+p], b = V[k*n+q]; V[k*n+p] = c * a - s * b; V[k*n+q] = s * a + c * b; }
+            A[p*n+q] = 0.0; A[q*n+p] = 0.0;
+        }
+    }
+    for (int i = 0; i < n; i++) ev[i] = A[i*n+i];
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -833,6 +885,65 @@ int orc_estimate_pose(const OrcParams* prm, const float* sp, const float* sn, co
         }
     }
     return it;
+}
+
+// PointCloud(pcl::PointCloud<PointXYZ>::Ptr), PointCloud.h:41-76: pcl::NormalEstimation with setKSearch(k) (5 there) over a
+// pcl::search::KdTree, normals flipped towards the viewpoint (PCL's default (0,0,0)).  PCL PARITY UNPINNED: PCL is absent here;
+// what its computePointNormal / solvePlaneParameters and flipNormalTowardsViewpoint do is read from their source only (centroid,
+// 3x3 covariance, eigenvector of the smallest eigenvalue, curvature l0 / (l0 + l1 + l2)).  What this restates exactly is the
+// device contract of k_normals_knn<K>:
+//   * neighbours: the k smallest (fp32 (dx*dx + dy*dy) + dz*dz, index) pairs over the finite points, lowest index first on ties,
+//     the query itself included (distance 0); fewer than k finite points -> all of them;
+//   * fp64 mean, then fp64 covariance / cnt, both summed in that neighbour order over the fp32 coordinates;
+//   * jacobi3 above; the first smallest eigenvalue's column, divided by its fp64 length; flipped iff
+//     ((vp - p) in fp32) . v in fp64 < 0; curvature |l_min| / ((l0 + l1) + l2), 0 when that trace is not > 0.
+// Rules: fewer than 3 finite points in the cloud, or a non-finite query -> NaN normal and NaN curvature.  Zero covariance
+// (coincident neighbours) -> Jacobi's first axis (1,0,0), flipped, curvature 0.
+// nbr_out (optional, n x k): the neighbour indices in (d2, index) order, -1 past the neighbour count.  Returns 0, or -1 for a bad k.
+int orc_estimate_normals(const float* pts, int n, int k, const float* vp, float* nrm_out, float* curv_out, int* nbr_out) {
+    if (k < 3 || k > 8 || n < 0) return -1;
+    KdTree* t = (KdTree*)orc_kdtree_build(pts, n);
+    const int n_valid = (int)t->perm.size();
+    const float NaN = std::numeric_limits<float>::quiet_NaN();
+    #pragma omp parallel for schedule(dynamic, 256)
+    for (int i = 0; i < n; i++) {
+        const float* p = pts + (size_t)i*3;
+        float bd[8]; int bj[8];
+        for (int q = 0; q < k; q++) { bd[q] = FLT_MAX; bj[q] = 0x7fffffff; }
+        float nrm[3] = {NaN, NaN, NaN}, curv = NaN;
+        int cnt = 0;
+        if (finite3(p) && n_valid >= 3) {
+            kd_query_k(*t, 0, p, k, bd, bj);
+            while (cnt < k && bd[cnt] < FLT_MAX) cnt++;
+        }
+        if (cnt >= 3) {
+            double m[3] = {0, 0, 0};
+            for (int q = 0; q < cnt; q++) for (int d = 0; d < 3; d++) m[d] += pts[(size_t)bj[q]*3+d];
+            for (int d = 0; d < 3; d++) m[d] /= cnt;
+            double cxx = 0, cxy = 0, cxz = 0, cyy = 0, cyz = 0, czz = 0;
+            for (int q = 0; q < cnt; q++) {
+                const float* r = pts + (size_t)bj[q]*3;
+                const double a = r[0] - m[0], b = r[1] - m[1], c = r[2] - m[2];
+                cxx += a * a; cxy += a * b; cxz += a * c; cyy += b * b; cyz += b * c; czz += c * c;
+            }
+            double A[9] = {cxx / cnt, cxy / cnt, cxz / cnt, cxy / cnt, cyy / cnt, cyz / cnt, cxz / cnt, cyz / cnt, czz / cnt}, V[9], ev[3];
+            jacobi3(A, V, ev);
+            int s0 = 0; if (ev[1] < ev[s0]) s0 = 1; if (ev[2] < ev[s0]) s0 = 2;
+            double vx = V[0*3+s0], vy = V[1*3+s0], vz = V[2*3+s0];
+            const double len = std::sqrt(vx * vx + vy * vy + vz * vz);
+            vx /= len; vy /= len; vz /= len;
+            const float ex = vp[0] - p[0], ey = vp[1] - p[1], ez = vp[2] - p[2];
+            if ((double)ex * vx + (double)ey * vy + (double)ez * vz < 0) { vx = -vx; vy = -vy; vz = -vz; }
+            nrm[0] = (float)vx; nrm[1] = (float)vy; nrm[2] = (float)vz;
+            const double tr = ev[0] + ev[1] + ev[2];
+            curv = tr > 0 ? (float)(std::fabs(ev[s0]) / tr) : 0.f;
+        }
+        std::memcpy(nrm_out + (size_t)i*3, nrm, 12);
+        if (curv_out) curv_out[i] = curv;
+        if (nbr_out) for (int q = 0; q < k; q++) nbr_out[(size_t)i*k+q] = q < cnt ? bj[q] : -1;
+    }
+    orc_kdtree_free(t);
+    return 0;
 }
 
 int orc_num_threads() {

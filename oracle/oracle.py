@@ -153,6 +153,19 @@ class KdTree:
             pass
 
 
+def estimate_normals(pts, k=5, viewpoint=(0.0, 0.0, 0.0), return_neighbours=False):
+    """PointCloud(pcl cloud) normals (PointCloud.h:41-76) as the device computes them: exact k-NN over the finite points
+    ((d2, index) order, the point itself included), fp64 PCA, flip towards the viewpoint (icp_oracle.cpp, orc_estimate_normals).
+    Returns (normals (n,3) f32, curvature (n,) f32[, neighbours (n,k) int32, -1 past the neighbour count])."""
+    pts = _f32(pts).reshape(-1, 3); vp = _f32(viewpoint).reshape(3)
+    n = len(pts)
+    nrm = np.empty((n, 3), np.float32); curv = np.empty(n, np.float32)
+    nbr = np.empty((n, k), np.int32) if return_neighbours else None
+    if lib().orc_estimate_normals(_p(pts), C.c_int(n), C.c_int(k), _p(vp), _p(nrm), _p(curv), _p(nbr)):
+        raise ValueError("estimate_normals: k must be 3..8")
+    return (nrm, curv, nbr) if return_neighbours else (nrm, curv)
+
+
 def knn6(q, qrgba, tgt, trgba, max_dist):
     q, tgt, qrgba, trgba = _f32(q), _f32(tgt), _u8(qrgba), _u8(trgba)
     out = np.empty(len(q), MATCH_DTYPE); d2 = np.empty(len(q), np.float32)

@@ -166,6 +166,7 @@ def test_eth_files_to_pose_end_to_end(gpu_ctx_factory, orc, tmp_path):
     perturbation -> 50 point-to-plane iterations; checked against the oracle on the same prepared clouds."""
     from conftest import pose_error
     from icp_amd import eth, binding
+    from test_gpu_normals import check_normals
     written = _write_eth_dataset(tmp_path)
     rows = eth.load_rows(str(tmp_path), "apartment_global.csv")
     assert len(rows) == 2 and eth.dataset_name("apartment_global.csv") == "apartment" and eth.dataset_name("eth/plain_global.csv") == "eth/plain"
@@ -175,6 +176,14 @@ def test_eth_files_to_pose_end_to_end(gpu_ctx_factory, orc, tmp_path):
         assert np.array_equal(src, w["src_unperturbed"]) and np.array_equal(tgt, w["tgt_pts"])      # binary PCD round trip is exact
         pair = eth.prepare_pair(c, src, tgt, row["pose"])
         assert np.isfinite(pair["src_nrm"]).all() and np.allclose(np.linalg.norm(pair["tgt_nrm"], axis=1), 1.0, atol=1e-4)
+        # the device normals prepare_pair fed the run: the target's as they are, the source's before change_pose moved them
+        # (a second call gives the curvature and the unmoved source normals; it must repeat the first bit for bit)
+        tgt_nrm, tgt_curv = c.estimate_normals(tgt, 5)
+        src_nrm, src_curv = c.estimate_normals(src, 5)
+        assert np.array_equal(tgt_nrm.view(np.uint32), pair["tgt_nrm"].view(np.uint32))
+        assert np.array_equal(eth.change_pose(pair["initial"], src, src_nrm)[1].view(np.uint32), pair["src_nrm"].view(np.uint32))
+        check_normals(orc, tgt, 5, (0, 0, 0), pair["tgt_nrm"], tgt_curv, "eth target")
+        check_normals(orc, src, 5, (0, 0, 0), src_nrm, src_curv, "eth source")
         c.params.max_distance = 10.0; c.params.metric = 1; c.params.n_iterations = 50; c.params.knn_backend = 1; c.params.record_rmse = 3
         c.push_params()
         c.set_convergence_reference(pair["src_pts"], pair["src_unperturbed"])        # ConvergenceMeasure(source, original_source, true)
