@@ -804,21 +804,31 @@ int finish_source(icp_ctx* c) {
     return ICP_OK;
 }
 
+// Inverse of a rigid/affine 4x4 (column-major, bottom row ignored) in fp64: 3x3 row-major R^-1 and t^-1 = -R^-1 t.
+void invert_affine(const float* m, double Ri[9], double ti[3]) {
+    double R[9], t[3];
+    for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) R[r * 3 + k] = m[k * 4 + r]; t[r] = m[12 + r]; }
+    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    const double q[9] = {(R[4] * R[8] - R[5] * R[7]) / det, (R[2] * R[7] - R[1] * R[8]) / det, (R[1] * R[5] - R[2] * R[4]) / det,
+                         (R[5] * R[6] - R[3] * R[8]) / det, (R[0] * R[8] - R[2] * R[6]) / det, (R[2] * R[3] - R[0] * R[5]) / det,
+                         (R[3] * R[7] - R[4] * R[6]) / det, (R[1] * R[6] - R[0] * R[7]) / det, (R[0] * R[4] - R[1] * R[3]) / det};
+    for (int i = 0; i < 9; i++) Ri[i] = q[i];
+    for (int r = 0; r < 3; r++) ti[r] = -(q[r * 3] * t[0] + q[r * 3 + 1] * t[1] + q[r * 3 + 2] * t[2]);
+}
 // depthExtrinsics.inverse() (PointCloud.h:88-90): rigid/affine 4x4 (column-major), inverted in fp64 and rounded once -> 3x3 row-major R^-1, t^-1
 void invert_extrinsics(const float* extrinsics, float inv[12]) {
-    double R[9], t[3];
-    for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) R[r * 3 + k] = extrinsics[k * 4 + r]; t[r] = extrinsics[12 + r]; }
-    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-    double Ri[9] = {(R[4] * R[8] - R[5] * R[7]) / det, (R[2] * R[7] - R[1] * R[8]) / det, (R[1] * R[5] - R[2] * R[4]) / det,
-                    (R[5] * R[6] - R[3] * R[8]) / det, (R[0] * R[8] - R[2] * R[6]) / det, (R[2] * R[3] - R[0] * R[5]) / det,
-                    (R[3] * R[7] - R[4] * R[6]) / det, (R[1] * R[6] - R[0] * R[7]) / det, (R[0] * R[4] - R[1] * R[3]) / det};
+    double Ri[9], ti[3];
+    invert_affine(extrinsics, Ri, ti);
     for (int i = 0; i < 9; i++) inv[i] = (float)Ri[i];
-    for (int r = 0; r < 3; r++) inv[9 + r] = (float)(-(Ri[r * 3] * t[0] + Ri[r * 3 + 1] * t[1] + Ri[r * 3 + 2] * t[2]));
+    for (int r = 0; r < 3; r++) inv[9 + r] = (float)ti[r];
 }
 
+bool depth_camera_ok(const icp_depth_camera* cam) {
+    return cam && cam->width > 0 && cam->height > 0 && (long long)cam->width * cam->height <= 0x7FFFFFFFll &&
+           std::isfinite(cam->fx) && std::isfinite(cam->fy) && std::isfinite(cam->cx) && std::isfinite(cam->cy);
+}
 int check_depth_args(icp_ctx* c, const icp_depth_camera* cam, const icp_depth_options* opt, const char* who) {
-    if (!cam || !opt || cam->width <= 0 || cam->height <= 0 || (long long)cam->width * cam->height > 0x7FFFFFFFll || opt->downsample_factor < 1 ||
-        std::isnan(opt->max_distance) || !std::isfinite(cam->fx) || !std::isfinite(cam->fy) || !std::isfinite(cam->cx) || !std::isfinite(cam->cy)) {
+    if (!depth_camera_ok(cam) || !opt || opt->downsample_factor < 1 || std::isnan(opt->max_distance)) {
         c->err = std::string(who) + ": bad camera or options (width, height > 0, downsample_factor >= 1)"; return ICP_ERR_INVALID_ARG;
     }
     return ICP_OK;
@@ -827,19 +837,21 @@ int check_depth_args(icp_ctx* c, const icp_depth_camera* cam, const icp_depth_op
 // One depth frame [depth 4n | rgbx 4n] into upload slot `slot`: host -> page-locked block -> device, on stream s (the context's own stream,
 // or depth_stream when the frame goes up while the previous one iterates); depth_up[slot] marks its arrival.  The only host-side wait is for
 // the slot's previous copy to have left the page-locked block.
-int stage_depth(icp_ctx* c, int slot, const float* depth, const uint8_t* rgbx, int n, hipStream_t s) {
+// The colour frame has n pixels unless n_color says otherwise (icp_depth_mesh's colour camera).
+int stage_depth(icp_ctx* c, int slot, const float* depth, const uint8_t* rgbx, int n, hipStream_t s, int n_color = -1) {
+    if (n_color < 0) n_color = n;
     if (!c->depth_up[slot]) HIPCK(c, hipEventCreateWithFlags(&c->depth_up[slot], hipEventDisableTiming));
     if (c->depth_pending[slot]) { HIPCK(c, hipEventSynchronize(c->depth_up[slot])); c->depth_pending[slot] = false; }
-    const size_t bytes = (size_t)n * (rgbx ? 8 : 4);
+    const size_t bytes = (size_t)n * 4 + (rgbx ? (size_t)n_color * 4 : 0), cap = (size_t)n * 4 + (size_t)(n_color > n ? n_color : n) * 4;
     if (bytes > c->depth_pin_cap[slot] || !c->depth_pin[slot]) {
         if (c->depth_pin[slot]) { HIPCK(c, hipHostFree(c->depth_pin[slot])); c->depth_pin[slot] = nullptr; c->depth_pin_cap[slot] = 0; }
-        HIPCK(c, hipHostMalloc(&c->depth_pin[slot], (size_t)n * 8, hipHostMallocDefault));
-        c->depth_pin_cap[slot] = (size_t)n * 8;
+        HIPCK(c, hipHostMalloc(&c->depth_pin[slot], cap, hipHostMallocDefault));
+        c->depth_pin_cap[slot] = cap;
     }
     int rc;
-    if ((rc = ensure(c, c->depth_dev[slot], (size_t)n * 8))) return rc;
+    if ((rc = ensure(c, c->depth_dev[slot], cap))) return rc;
     memcpy(c->depth_pin[slot], depth, (size_t)n * 4);
-    if (rgbx) memcpy((char*)c->depth_pin[slot] + (size_t)n * 4, rgbx, (size_t)n * 4);
+    if (rgbx) memcpy((char*)c->depth_pin[slot] + (size_t)n * 4, rgbx, (size_t)n_color * 4);
     HIPCK(c, hipMemcpyAsync(c->depth_dev[slot].p, c->depth_pin[slot], bytes, hipMemcpyHostToDevice, s));
     HIPCK(c, hipEventRecord(c->depth_up[slot], s)); c->depth_pending[slot] = true;
     return ICP_OK;
@@ -1743,6 +1755,80 @@ int icp_track_depth_frames(icp_ctx* c, const float* depth_frames, const uint8_t*
     }
     guard.ok = true;
     return first_err;
+}
+
+// SimpleMesh(sensor, cameraPose, edgeThreshold) (SimpleMesh.h:36-119, dev_mesh.hpp).  The two matrices are composed on the host in fp64 and
+// rounded once: M = P^-1 E^-1 (both affine) for the vertices, C = Kc Ec P for the colour re-projection.  Scratch: upload slot 0 of the
+// depth frames, `staging` = [xyz 12n | rgba 4n | triangles 24 (w - 1)(h - 1)], the depth compaction's block counts and d_count.
+int icp_depth_mesh(icp_ctx* c, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const icp_color_camera* color_cam,
+                   const float camera_pose[16], float edge_threshold, float* vertices_out, uint8_t* colors_out, uint32_t* triangles_out,
+                   int32_t* n_triangles_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (n_triangles_out) *n_triangles_out = 0;
+    if (!depth || !camera_pose || !vertices_out || !triangles_out || !n_triangles_out || (colors_out && !rgbx) || !depth_camera_ok(cam) ||
+        2 * (long long)(cam->width - 1) * (cam->height - 1) > 0x7FFFFFFFll ||
+        (color_cam && (color_cam->width <= 0 || color_cam->height <= 0 || (long long)color_cam->width * color_cam->height > 0x7FFFFFFFll ||
+                       !std::isfinite(color_cam->fx) || !std::isfinite(color_cam->fy) || !std::isfinite(color_cam->cx) || !std::isfinite(color_cam->cy)))) {
+        c->err = "icp_depth_mesh: bad argument (null pointer, colours without a colour frame, or a bad camera)"; return ICP_ERR_INVALID_ARG;
+    }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const int w = cam->width, h = cam->height, n = w * h;
+    const int nq = (w - 1) * (h - 1), nb = (nq + 255) / 256;
+    MeshFrame f;
+    f.width = w; f.height = h; f.fx = cam->fx; f.fy = cam->fy; f.cx = cam->cx; f.cy = cam->cy;
+    f.color_width = color_cam ? color_cam->width : w; f.color_height = color_cam ? color_cam->height : h;
+    {
+        double Pi[9], pt[3], Ei[9], et[3];
+        invert_affine(camera_pose, Pi, pt);
+        invert_affine(cam->extrinsics, Ei, et);
+        for (int r = 0; r < 3; r++) {
+            for (int k = 0; k < 3; k++) f.m[r * 3 + k] = (float)((Pi[r * 3] * Ei[k] + Pi[r * 3 + 1] * Ei[3 + k]) + Pi[r * 3 + 2] * Ei[6 + k]);
+            f.m[9 + r] = (float)(((Pi[r * 3] * et[0] + Pi[r * 3 + 1] * et[1]) + Pi[r * 3 + 2] * et[2]) + pt[r]);
+        }
+        static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        const float* Ec = color_cam ? color_cam->extrinsics : identity;
+        const double K[9] = {color_cam ? color_cam->fx : cam->fx, 0, color_cam ? color_cam->cx : cam->cx,
+                             0, color_cam ? color_cam->fy : cam->fy, color_cam ? color_cam->cy : cam->cy, 0, 0, 1};
+        double A[12];                                    // rows 0..2 of Ec P (column-major 4x4 operands)
+        for (int r = 0; r < 3; r++)
+            for (int k = 0; k < 4; k++)
+                A[r * 4 + k] = (((double)Ec[r] * camera_pose[k * 4] + (double)Ec[4 + r] * camera_pose[k * 4 + 1]) + (double)Ec[8 + r] * camera_pose[k * 4 + 2]) +
+                               (double)Ec[12 + r] * camera_pose[k * 4 + 3];
+        for (int r = 0; r < 3; r++)
+            for (int k = 0; k < 4; k++) f.c[r * 4 + k] = (float)((K[r * 3] * A[k] + K[r * 3 + 1] * A[4 + k]) + K[r * 3 + 2] * A[8 + k]);
+    }
+    const bool with_colors = colors_out != nullptr;
+    if ((rc = stage_depth(c, 0, depth, with_colors ? rgbx : nullptr, n, c->stream, f.color_width * f.color_height))) return rc;
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->depth_up[0], 0));
+    f.depth = c->depth_dev[0].as<float>(); f.rgbx = with_colors ? c->depth_dev[0].as<uint8_t>() + (size_t)n * 4 : nullptr;
+    if ((rc = ensure(c, c->staging, (size_t)n * 16 + (size_t)nq * 24))) return rc;
+    float* d_xyz = c->staging.as<float>(); uint32_t* d_rgba = (uint32_t*)(d_xyz + (size_t)n * 3); uint32_t* d_tris = d_rgba + n;
+    if ((rc = ensure_pinned(c, 4096))) return rc;
+    int* hn = (int*)((char*)c->pinned + 2048);            // (the first bytes of the pinned block stage the pose)
+    *hn = 0;
+    hipLaunchKernelGGL(k_mesh_vertices, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, f, d_xyz, with_colors ? d_rgba : nullptr);
+    if (nq > 0) {
+        if ((rc = ensure(c, c->depth_blocks, (size_t)nb * 4))) return rc;
+        if ((rc = ensure(c, c->d_count, 16))) return rc;
+        hipLaunchKernelGGL(k_mesh_count, dim3(nb), dim3(256), 0, c->stream, (const float*)d_xyz, w, nq, edge_threshold, c->depth_blocks.as<int>());
+        hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, c->stream, c->depth_blocks.as<int>(), nb, c->d_count.as<int>());
+        hipLaunchKernelGGL(k_mesh_scatter, dim3(nb), dim3(256), 0, c->stream, (const float*)d_xyz, w, nq, edge_threshold, (const int*)c->depth_blocks.as<int>(), d_tris);
+        HIPCK(c, hipMemcpyAsync(hn, c->d_count.p, 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipMemcpyAsync(vertices_out, d_xyz, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (with_colors) HIPCK(c, hipMemcpyAsync(colors_out, d_rgba, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    const int nt = *hn;
+    if (nt < 0 || nt > 2 * nq) { c->err = "icp_depth_mesh: triangle count out of range"; return ICP_ERR_HIP; }
+    if (nt > 0) {
+        HIPCK(c, hipMemcpyAsync(triangles_out, d_tris, (size_t)nt * 12, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+    }
+    *n_triangles_out = nt;
+    return guard.done();
 }
 
 int icp_estimate_normals(icp_ctx* c, const float* xyz, int32_t n, int32_t k, const float viewpoint[3], float* normals_out, float* curvature_out) {

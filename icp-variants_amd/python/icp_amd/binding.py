@@ -78,6 +78,21 @@ def depth_camera(K, width, height, extrinsics=None):
     return cam
 
 
+class IcpColorCamera(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_int32), ("height", C.c_int32),
+                ("extrinsics", C.c_float * 16)]
+
+
+def color_camera(K, width, height, extrinsics=None):
+    """icp_color_camera: colour intrinsics (K(0,0), K(1,1), K(0,2), K(1,2)), the RGBX frame's size and optional 4x4 colour extrinsics."""
+    K = np.asarray(K, dtype=np.float32)
+    cam = IcpColorCamera(float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), int(width), int(height))
+    E = pose_to_c(np.eye(4) if extrinsics is None else extrinsics)
+    for k in range(16):
+        cam.extrinsics[k] = float(E[k])
+    return cam
+
+
 def depth_options(keep_original_size=False, downsample_factor=1, max_distance=0.1, fix_color_index=False):
     """icp_depth_options: the constructor arguments of PointCloud(depthMap, ...) (PointCloud.h:78)."""
     return IcpDepthOptions(int(bool(keep_original_size)), int(downsample_factor), float(max_distance), int(bool(fix_color_index)))
@@ -90,7 +105,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_set_params", "icp_get_params", "icp_set_target", "icp_set_source", "icp_query_matches", "icp_match", "icp_match_seeded",
            "icp_correspond", "icp_iterate", "icp_run", "icp_get_timing", "icp_get_iteration_times", "icp_set_stage_timing", "icp_set_convergence_reference", "icp_rmse", "icp_benchmark_error",
            "icp_transform_points", "icp_transform_normals", "icp_version", "icp_schedule", "icp_select_hash", "icp_backproject_depth", "icp_estimate_normals",
-           "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames",
+           "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames", "icp_depth_mesh",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
 
@@ -328,6 +343,26 @@ class Context:
         recs = [dict(n_src=out[i].n_src, iterations=out[i].iterations, status=out[i].status, initial_rmse=out[i].initial_rmse,
                      final_rmse=out[i].final_rmse, pose=pose_from_c(out[i].pose)) for i in range(nf - 1)]
         return pose_from_c(p), recs, rc
+
+    def depth_mesh(self, depth, rgbx, cam, camera_pose, edge_threshold=0.01, color_cam=None):
+        """icp_depth_mesh: SimpleMesh(sensor, cameraPose, edgeThreshold) (SimpleMesh.h:36-119) on the device.  depth: the frame of `cam`;
+        rgbx: the RGBX colour frame (color_cam's size, or the depth frame's when color_cam is None), or None for no colours;
+        camera_pose: 4x4 world -> camera.  Returns (vertices (w*h, 3) f32, colours (w*h, 4) u8 or None, triangles (T, 3) u32)."""
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if depth.size != cam.width * cam.height:
+            raise ValueError("depth frame has %d pixels, the camera %d x %d" % (depth.size, cam.width, cam.height))
+        n_color = (color_cam.width * color_cam.height) if color_cam is not None else depth.size
+        rgbx = None if rgbx is None else np.ascontiguousarray(rgbx, dtype=np.uint8)
+        if rgbx is not None and rgbx.size != 4 * n_color:
+            raise ValueError("colour frame must hold 4 bytes per pixel of the colour camera")
+        n = depth.size
+        verts = np.empty((n, 3), np.float32)
+        cols = np.empty((n, 4), np.uint8) if rgbx is not None else None
+        tris = np.empty((2 * max(cam.width - 1, 0) * max(cam.height - 1, 0), 3), np.uint32)
+        nt = C.c_int32(0)
+        self._ck(self.lib.icp_depth_mesh(self.h, _ptr(depth), _ptr(rgbx), C.byref(cam), None if color_cam is None else C.byref(color_cam),
+                                         _ptr(pose_to_c(camera_pose)), C.c_float(edge_threshold), _ptr(verts), _ptr(cols), _ptr(tris), C.byref(nt)))
+        return verts, cols, tris[:nt.value]
 
     def estimate_normals(self, xyz, k=5, viewpoint=(0.0, 0.0, 0.0)):
         """PointCloud(pcl cloud): k-NN PCA normals flipped towards the viewpoint (PointCloud.h:41-76)."""

@@ -1,9 +1,11 @@
-"""OFF/COFF mesh reader and mesh -> point-cloud conversion (host-side data model).
+"""OFF/COFF mesh reader and writer, mesh -> point-cloud conversion, and the camera glyph reconstructRoom adds (host-side data model).
 
 Follows SimpleMesh::loadMesh (reference SimpleMesh.h:161-229) and PointCloud(const SimpleMesh&)
 (PointCloud.h:12-39): vertex normals are the normalised fp32 sum of un-normalised face normals,
 accumulated in file order; colours of mesh-derived clouds are all zero (PointCloud.h:26).
 Pre-processing outside the timed ICP loop -- plain numpy, fp32.
+write_off / camera_glyph / join_meshes follow writeMesh, camera and joinMeshes (SimpleMesh.h:231-302,336-359): the output side of
+saveRoomToFile (utils.h:179-193).  A mesh is a tuple (vertices (V,3) f32, colors (V,4) u8, triangles (T,3) u32).
 """
 import numpy as np
 
@@ -51,3 +53,56 @@ def mesh_to_cloud(verts, tris):
             nrm[i] = v / np.sqrt(z, dtype=np.float32)
     cols = np.zeros((len(pts), 4), np.uint8)
     return pts, nrm, cols
+
+
+# SimpleMesh::camera (SimpleMesh.h:336-359): eight corners of a frustum and its twelve faces.
+CAMERA_VERTICES = (25, 25, 0, -50, 50, 100, 49.99986, 49.9922, 99.99993, -24.99998, 25.00426, 0.005185,
+                   25.00261, -25.00023, 0.004757, 49.99226, -49.99986, 99.99997, -50, -50, 100, -25.00449, -25.00492, 0.019877)
+CAMERA_FACES = (1, 2, 3, 2, 0, 3, 2, 5, 4, 4, 0, 2, 5, 6, 7, 7, 4, 5, 6, 1, 7, 1, 3, 7, 3, 0, 4, 7, 3, 4, 5, 2, 1, 5, 1, 6)
+
+
+def _affine_apply(T, v):
+    """Matrix4f * Vector4f(x, y, z, 1) in fp32 for every row of v: ((c0 x + c1 y) + c2 z) + c3, the columns c of T."""
+    T = np.asarray(T, np.float32)
+    x, y, z = v[:, 0:1], v[:, 1:2], v[:, 2:3]
+    return ((T[:3, 0] * x + T[:3, 1] * y) + T[:3, 2] * z) + T[:3, 3]
+
+
+def camera_glyph(camera_pose, scale=0.0015, color=(255, 0, 0, 255)):
+    """SimpleMesh::camera(cameraPose, scale, color): the frustum moved by cameraPose^-1 (inverted in fp64, rounded once to fp32)."""
+    to_world = np.linalg.inv(np.asarray(camera_pose, np.float64)).astype(np.float32)
+    local = np.float32(scale) * np.array(CAMERA_VERTICES, np.float64).astype(np.float32).reshape(8, 3)
+    verts = _affine_apply(to_world, local).astype(np.float32)
+    cols = np.tile(np.array(color, np.uint8), (8, 1))
+    return verts, cols, np.array(CAMERA_FACES, np.uint32).reshape(12, 3)
+
+
+def join_meshes(m1, m2, pose1to2=None):
+    """SimpleMesh::joinMeshes(mesh1, mesh2, pose1to2): mesh1's vertices moved by pose1to2 (left as they are when None, the identity),
+    then mesh2's; mesh2's triangles offset by the vertex count of mesh1 (unsigned arithmetic)."""
+    v1, c1, t1 = m1
+    v2, c2, t2 = m2
+    v1 = np.asarray(v1, np.float32)
+    if pose1to2 is not None:
+        with np.errstate(invalid="ignore"):
+            v1 = _affine_apply(pose1to2, v1).astype(np.float32)
+    verts = np.concatenate([v1, np.asarray(v2, np.float32)]).reshape(-1, 3)
+    cols = np.concatenate([np.asarray(c1, np.uint8), np.asarray(c2, np.uint8)]).reshape(-1, 4)
+    tris = np.concatenate([np.asarray(t1, np.uint32), np.asarray(t2, np.uint32) + np.uint32(len(v1))]).reshape(-1, 3)
+    return verts, cols, tris
+
+
+def write_off(path, vertices, colors, triangles):
+    """SimpleMesh::writeMesh (SimpleMesh.h:231-259), byte for byte: 'COFF', 'nv nt 0', one line per vertex -- the floats as
+    std::ostream prints them by default (%g, 6 significant digits) and the colour bytes as integers, or '0.0 0.0 0.0 0 0 0 0' for a
+    vertex that is not finite -- then '3 a b c' per triangle."""
+    v = np.asarray(vertices, np.float32).reshape(-1, 3)
+    c = np.asarray(colors, np.uint8).reshape(-1, 4)
+    t = np.asarray(triangles, np.uint32).reshape(-1, 3)
+    finite = np.isfinite(v).all(axis=1)
+    line = np.where(finite, "%g %g %g %d %d %d %d\n", "0.0 0.0 0.0 0 0 0 0\n")
+    values = np.concatenate([v[finite].astype(np.float64), c[finite].astype(np.float64)], axis=1).ravel().tolist()
+    with open(path, "w") as f:
+        f.write("COFF\n%d %d 0\n" % (len(v), len(t)))
+        f.write("".join(line.tolist()) % tuple(values))
+        f.write(("3 %d %d %d\n" * len(t)) % tuple(t.ravel().tolist()))

@@ -4,6 +4,7 @@ Pure host logic over `formats.py`; the tracking itself is one library call (`icp
   seq            = load_sequence(tum_dir)                     # VirtualSensor(frameStep).init + processFrameIndex(0, (i+1) * step, ...)
   tgt_o, src_o   = reconstruct_room_options(params)           # the reference's choice of clouds, 35 iterations, max distance 0.1
   poses, recs    = track(ctx, seq, params)                    # estimatedPoses (currentCameraToWorld^-1 per frame) + per-frame records
+  reconstruct_room(ctx, seq, params, out_dir)                 # track + saveRoomToFile per frame: mesh_<frame>.off (utils.h:179-193)
 Layout on disk, as the reference expects it under Data/: <tum_dir>/depth.txt, rgb.txt, groundtruth.txt and the PNGs they list (TUM RGB-D).
 `write_synthetic_sequence` writes that layout from `synth.depth_frame` / `synth.camera_pose`, for the tests and for rehearsing a real
 freiburg1_xyz run offline.
@@ -11,7 +12,7 @@ freiburg1_xyz run offline.
 import os
 import numpy as np
 
-from . import binding, formats, synth
+from . import binding, formats, meshio, synth
 
 TUM_K = np.array([[525.0, 0.0, 319.5], [0.0, 525.0, 239.5], [0.0, 0.0, 1.0]], np.float32)     # VirtualSensor.h:44-46
 TUM_WIDTH, TUM_HEIGHT = 640, 480
@@ -83,6 +84,28 @@ def track(ctx, seq, params=None, with_gt=True):
     _, recs, rc = ctx.track_depth_frames(seq["depth"], seq["rgbx"], cam, tgt_o, src_o, gt=seq["gt"] if with_gt else None)
     poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
     return poses, recs, rc
+
+
+def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015):
+    """reconstructRoom end to end: `track`, then saveRoomToFile (utils.h:179-193) for every scheduled frame k --
+    joinMeshes(SimpleMesh(sensor, pose_k, edge_threshold) on the device, SimpleMesh::camera(pose_k, camera_scale), identity) with pose_k
+    the camera pose `track` returned (the identity for frame 0).  With out_dir the meshes are written as mesh_<frame index>.off
+    (getCurrentFrameCnt, VirtualSensor.h:142-144).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    poses, recs, rc = track(ctx, seq, params, with_gt=with_gt)
+    cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+    out = []
+    for k, pose in enumerate(poses):
+        depth_mesh = ctx.depth_mesh(seq["depth"][k], seq["rgbx"][k], cam, pose, edge_threshold)
+        mesh = meshio.join_meshes(depth_mesh, meshio.camera_glyph(pose, camera_scale))
+        if out_dir is None:
+            out.append(mesh)
+        else:
+            path = os.path.join(out_dir, "mesh_%d.off" % seq["frames"][k])
+            meshio.write_off(path, *mesh)
+            out.append(path)
+    return poses, recs, rc, out
 
 
 def _write_list(path, header, rows):

@@ -224,6 +224,29 @@ int icp_track_depth_frames(icp_ctx* ctx, const float* depth_frames, const uint8_
                            const icp_depth_camera* cam, const icp_depth_options* target_opt, const icp_depth_options* source_opt,
                            const float* gt_frames, float pose_inout[16], icp_track_frame* out);
 
+/* -------- the depth mesh reconstructRoom writes after every frame: SimpleMesh(sensor, cameraPose, edgeThreshold) (SimpleMesh.h:36-119)
+ * on the device (saveRoomToFile, utils.h:179-193) --------
+ * Vertices: all width*height of them, never compacted: MINF (-inf) where the depth is MINF, else the pixel back-projected as
+ * icp_backproject_depth does it and moved by cameraPose^-1 (P^-1 E^-1 composed in fp64, both affine, rounded once to fp32).  NaN and
+ * +inf depths are not holes: they go through the arithmetic.  Colours: 0 for a MINF pixel, else the RGBX bytes the vertex re-projects
+ * to in the colour frame (Kc Ec P composed in fp64, rounded once; floor, the x86-64 (unsigned int) cast, clamped to the frame).
+ * Triangles: per 2x2 quad (i0 = i*width + j, i1 = i0 + width, i2 = i0 + 1, i3 = i1 + 1), (i0, i1, i2) then (i1, i3, i2), each kept when
+ * its three vertices are finite and every edge is shorter than edge_threshold; in the reference's addFace order.
+ * depth: width*height fp32 metres (cam's size limits, and 2 (width - 1)(height - 1) <= INT32_MAX); camera_pose: world -> camera,
+ * column-major (reconstructRoom passes currentCameraToWorld^-1).  color_cam NULL = the depth intrinsics, the depth frame size and
+ * identity extrinsics (the TUM sensor, VirtualSensor.h:44-51).  rgbx: the colour frame, color width*height*4 bytes; NULL only when
+ * colors_out is NULL.  Outputs: vertices_out width*height*3 floats, colors_out (optional) width*height*4 bytes, triangles_out room for
+ * 2 (width - 1)(height - 1) * 3 indices, *n_triangles_out the number written.  Uses scratch buffers of the context only (target,
+ * source, index, params and convergence reference stay untouched). */
+typedef struct icp_color_camera {
+    float fx, fy, cx, cy;            /* colour intrinsics, Kc(0,0), Kc(1,1), Kc(0,2), Kc(1,2) */
+    int32_t width, height;           /* size of the RGBX colour frame */
+    float extrinsics[16];            /* colour extrinsics Ec, column-major */
+} icp_color_camera;
+int icp_depth_mesh(icp_ctx* ctx, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const icp_color_camera* color_cam,
+                   const float camera_pose[16], float edge_threshold, float* vertices_out, uint8_t* colors_out, uint32_t* triangles_out,
+                   int32_t* n_triangles_out);
+
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
  * towards the viewpoint.  k in {3..8} (else ICP_ERR_INVALID_ARG).  Non-finite points, and every point of a cloud with fewer than
