@@ -7,7 +7,7 @@
 // fp32 sqrt and divide are correctly rounded (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt).
 //
 // Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_solve.hpp,
-// dev_fused.hpp, dev_persist.hpp, dev_measures.hpp, dev_mesh.hpp (included below, in this order, inside namespace icpdev).
+// dev_fused.hpp, dev_persist.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
 //   k_deinterleave      AoS -> SoA upload conversion (+ colour features NearestNeighbor.h:212-221)
@@ -29,6 +29,8 @@
 //   k_rmse_partial      ConvergenceMeasure::rmseAlignmentError (ConvergenceMeasure.h:50-66)
 //   k_depth_count /     PointCloud(depthMap, colorFrame, ...) (PointCloud.h:78-165): back-projection, normals, stride and filter of a
 //   k_depth_scatter     depth frame as a stable two-pass compaction straight into a context cloud (dev_depth.hpp)
+//   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
+//   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,5 +52,6 @@ namespace icpdev {
 #include "dev_persist.hpp"
 #include "dev_measures.hpp"
 #include "dev_mesh.hpp"
+#include "dev_lm.hpp"
 
 }  // namespace icpdev

@@ -93,6 +93,9 @@ struct icp_ctx {
     bool gx_on = ICP_GX != 0; int gx_start = 16, gx_empty = 3;   // hand-over between the blocks of the fused matcher (dev_bvh.hpp, GX): ICP_HIP_GX=0 disables; ICP_HIP_GX_START / ICP_HIP_GX_EMPTY
     DevBuf gx_slots, gx_hdr; int gx_blocks = 0; bool gx_dirty = false;      // the outboxes (armed once: every launch leaves them as it found them; gx_dirty: a run was cut short)
     bool keep_fused_records = false;     // icp_match_seeded: the fused matcher also writes its Match records and distances (the loop itself never reads them)
+    bool lm_on = false; icp_lm_options lm_opt;   // icp_set_optimizer: the non-linear optimiser (k_lm_eval / k_lm_step) instead of the linear solve
+    DevBuf lm_state, lm_partials, lm_sums;       // its minimiser state, eval partials, per-iteration records of the run in flight
+    std::vector<icp_lm_summary> lm_last;         // the records of the last run (icp_get_lm_summaries)
     icp_params prm;
     Cloud tgt, src, qry;                 // qry: scratch cloud of icp_query_matches
     Cloud nrm_cloud; Bvh nrm_bvh;        // scratch of icp_estimate_normals
@@ -655,6 +658,41 @@ int launch_post_and_solve(icp_ctx* c, const Cloud& src, const int* sel, int n, i
     return ICP_OK;
 }
 
+// The non-linear optimiser in place of the reduce / solve (no sync): the post stage with its records kept (unless the fused matcher
+// already left them), then one ceres::Solve as k_lm_eval at x = 0 + k_lm_step, and max_num_iterations more (k_lm_eval, k_lm_step)
+// pairs -- enough for any solve: every step launch either ends it or leaves one candidate for the next eval, one LM iteration further
+// on.  Launches after the end find the state's `done` and return.
+int launch_post_and_lm(icp_ctx* c, const Cloud& src, const int* sel, int n, icp_iter_stats* d_stats, icp_lm_summary* d_summary,
+                       hipEvent_t ev_after_post, int fused_blocks) {
+    int rc;
+    if (!fused_blocks) {
+        if ((rc = ensure(c, c->partials, (size_t)POST_BLOCKS * NSUM * 8))) return rc;
+        int nb = (n + POST_THREADS - 1) / POST_THREADS; if (nb > POST_BLOCKS) nb = POST_BLOCKS; if (nb < 1) nb = 1;
+        hipLaunchKernelGGL(k_post, dim3(nb), dim3(POST_THREADS), 0, c->stream, make_post_params(c, src, sel, n));
+    }
+    if (ev_after_post) HIPCK(c, hipEventRecord(ev_after_post, c->stream));
+    // [LmState | evaluation point x = 0 | the candidate's]: slot 0 written once, when the buffer is made
+    const bool fresh = c->lm_state.p == nullptr;
+    if ((rc = ensure(c, c->lm_state, sizeof(LmState) + 2 * sizeof(LmRot)))) return rc;
+    LmRot* rots = (LmRot*)(c->lm_state.as<char>() + sizeof(LmState));
+    if (fresh) hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(WAVE), 0, c->stream, rots);
+    if ((rc = ensure(c, c->lm_partials, (size_t)LM_NSUM * LM_BLOCKS * 8))) return rc;
+    int nb = (n + LM_THREADS - 1) / LM_THREADS; if (nb > LM_BLOCKS) nb = LM_BLOCKS; if (nb < 1) nb = 1;
+    LmEvalParams ep; memset(&ep, 0, sizeof(ep));
+    ep.pp = make_post_params(c, src, sel, n); ep.st = c->lm_state.as<LmState>(); ep.partials = c->lm_partials.as<double>();
+    static_assert(sizeof(LmState) % 8 == 0, "the evaluation points follow the state");
+    LmStepParams sp; memset(&sp, 0, sizeof(sp));
+    sp.partials = c->lm_partials.as<double>(); sp.nblocks = nb; sp.st = c->lm_state.as<LmState>(); sp.rot = rots + 1; sp.opt = c->lm_opt;
+    sp.ps = c->ps.as<PoseState>(); sp.stats = d_stats; sp.summary = d_summary; sp.n_src = n;
+    for (int k = 0; k <= c->lm_opt.max_num_iterations; k++) {
+        ep.first = sp.first = k == 0 ? 1 : 0; ep.rot = rots + (k == 0 ? 0 : 1);
+        hipLaunchKernelGGL(k_lm_eval, dim3(nb), dim3(LM_THREADS), 0, c->stream, ep);
+        hipLaunchKernelGGL(k_lm_step, dim3(1), dim3(WAVE), 0, c->stream, sp);
+    }
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+
 // How many blocks of k_icp_loop the device holds at once (its waiters wait for blocks of the same grid: the whole grid must be resident).
 template <int DIM, bool WIDE>
 int loop_capacity_of(icp_ctx* c, int* out) {
@@ -978,6 +1016,7 @@ int icp_ctx_destroy(icp_ctx* c) {
     release(c->bvh.keys); release(c->bvh.keys2); release(c->bvh.vals); release(c->bvh.vals2); release(c->bvh.temp); release(c->bvh.leaves); release(c->okeys); release(c->okeys2); release(c->ovals); release(c->otemp); release(c->bvh.nodes); release(c->bvh.lvl); release(c->bvh.wbox);
     for (auto& kv : c->levels) release(kv.second);
     release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->pring); release(c->totals); release(c->dbg_steps); release(c->sums); release(c->gx_slots); release(c->gx_hdr);
+    release(c->lm_state); release(c->lm_partials); release(c->lm_sums);
     release(c->stats); release(c->staging); release(c->rmse_partials); release(c->rmse_out); release(c->fontana_partials);
     for (DevBuf* d : {&c->src_flag, &c->src_box, &c->tgt_flag, &c->tgt_finite, &c->nrm_finite, &c->sel_temp, &c->d_count}) release(*d);
     if (c->depth_stream) { (void)hipStreamSynchronize(c->depth_stream); (void)hipStreamDestroy(c->depth_stream); }
@@ -1227,10 +1266,16 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     }
     const int iters = (int)factors.size();
     if (n_run) *n_run = 0;
+    const bool lm = c->lm_on;             // the non-linear optimiser: the generic per-iteration form, its records kept for k_lm_eval
+    c->lm_last.clear();
     if (iters == 0) return guard.done();
     // page-locked staging for the whole run up front: [pose state up | per-iteration records down | pose state down]
     const size_t pin_stats = 256, pin_pose = pin_stats + (((size_t)iters * sizeof(icp_iter_stats) + 255) & ~(size_t)255);
-    if ((rc = ensure_pinned(c, pin_pose + 512 + (size_t)(iters + 1) * 8))) return rc;
+    const size_t pin_lm = (pin_pose + 512 + (size_t)(iters + 1) * 8 + 255) & ~(size_t)255;      // [LM records down] behind it, non-linear runs only
+    if ((rc = ensure_pinned(c, lm ? pin_lm + (size_t)iters * sizeof(icp_lm_summary) : pin_pose + 512 + (size_t)(iters + 1) * 8))) return rc;
+    if (lm && (rc = ensure(c, c->lm_sums, (size_t)iters * sizeof(icp_lm_summary)))) return rc;
+    struct KeepRecords { icp_ctx* c; bool prev; ~KeepRecords() { c->keep_fused_records = prev; } } keep_records{c, c->keep_fused_records};
+    if (lm) c->keep_fused_records = true;   // (the fused matcher writes its records for k_lm_eval)
     float pose_in[16]; memcpy(pose_in, pose_inout, 64);        // the record of an empty iteration 0 carries the incoming pose
     if ((rc = write_pose(c, pose_inout))) return rc;
     // the records of the run, and behind them (merged / one-launch loops) the final pose state, the fault word and the device clocks:
@@ -1281,7 +1326,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     // The merged loop (dev_solve.hpp, "the ring form"): point-to-plane through the fused BVH matcher on sorted levels, nothing else on
     // the stream between two iterations.  Launch i = [reducer of iteration i - 1 | matcher of iteration i]; one reducer-only launch closes
     // the run.  Pose slots and totals rows are written once per run; both rings are reset here, so nothing survives an aborted run.
-    bool merged = c->merge_loop && !single && iters >= 2 && sorted_levels && c->fuse_post && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
+    bool merged = !lm && c->merge_loop && !single && iters >= 2 && sorted_levels && c->fuse_post && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
     for (int i = 0; merged && i < iters; i++) if (ns[i] <= 0) merged = false;
     PoseState* slots = nullptr; unsigned long long* trows = nullptr; int* run_fault = nullptr;
     // k_icp_loop (dev_persist.hpp): all iterations of a resolution level in ONE launch, the waves resident from iteration to iteration.
@@ -1398,7 +1443,10 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
             if (merged && !fused) { c->err = "merged loop: the matcher did not take the fused path"; return ICP_ERR_HIP; }
             if (ev && !ext_ev) HIPCK(c, hipEventRecord(E(i, 1), c->stream));
             // fused epilogue: there is no separate post stage to bracket
-            if (!merged) {
+            if (lm) {
+                if ((rc = launch_post_and_lm(c, *clouds[i], sels[i], ns[i], d_st, c->lm_sums.as<icp_lm_summary>() + i, (ev && !fused) ? E(i, 2) : nullptr, fused))) return rc;
+                post_event[i] = ev && !fused;
+            } else if (!merged) {
                 if ((rc = launch_post_and_solve(c, *clouds[i], sels[i], ns[i], d_st, nullptr, 1, (ev && !fused) ? E(i, 2) : nullptr, fused))) return rc;
                 post_event[i] = ev && !fused;
             }
@@ -1453,6 +1501,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     else {
         HIPCK(c, hipMemcpyAsync((char*)c->pinned + pin_stats, c->stats.p, (size_t)iters * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
         HIPCK(c, hipMemcpyAsync((char*)c->pinned + pin_pose, c->ps.p, sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));
+        if (lm) HIPCK(c, hipMemcpyAsync((char*)c->pinned + pin_lm, c->lm_sums.p, (size_t)iters * sizeof(icp_lm_summary), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (merged) {
@@ -1478,6 +1527,12 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     memcpy(pose_inout, ((const PoseState*)((char*)c->pinned + pin_pose))->pose, 64);
     if (((const PoseState*)((char*)c->pinned + pin_pose))->fault) { c->gx_dirty = true; c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
     int status = ICP_OK;
+    if (lm) {
+        c->lm_last.resize((size_t)iters);
+        memcpy(c->lm_last.data(), (char*)c->pinned + pin_lm, (size_t)iters * sizeof(icp_lm_summary));
+        for (int i = 0; i < iters; i++)
+            if (ns[i] <= 0) { memset(&c->lm_last[(size_t)i], 0, sizeof(icp_lm_summary)); c->lm_last[(size_t)i].termination = ICP_LM_NO_RESIDUALS; }
+    }
     for (int i = 0; i < iters; i++) {
         if (ns[i] <= 0) { hs[i].n_src = 0; hs[i].n_valid = 0; hs[i].status = ICP_ERR_NO_CORRESPONDENCES; memcpy(hs[i].pose, i ? hs[i - 1].pose : pose_in, 64); hs[i].rmse = -1.f; hs[i].benchmark_error = -1.f; }
         if (!rmse) hs[i].rmse = -1.f;
@@ -1521,6 +1576,40 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     if (status != ICP_OK) c->err = "no valid correspondences in at least one iteration (reference would hang in ASSERT)";
     guard.ok = true;                                     // synchronised above; `status` reports empty iterations, not a HIP failure
     return status;
+}
+
+int icp_lm_options_default(icp_lm_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    memset(o, 0, sizeof(*o));
+    o->initial_trust_region_radius = 1e4; o->max_trust_region_radius = 1e16; o->min_trust_region_radius = 1e-32;
+    o->min_relative_decrease = 1e-3; o->min_lm_diagonal = 1e-6; o->max_lm_diagonal = 1e32;
+    o->function_tolerance = 1e-6; o->gradient_tolerance = 1e-10; o->parameter_tolerance = 1e-8;
+    o->max_num_iterations = 10;                            // configureSolver (ICPOptimizer.h:359)
+    o->max_num_consecutive_invalid_steps = 5; o->jacobi_scaling = 1;
+    return ICP_OK;
+}
+
+int icp_set_optimizer(icp_ctx* c, const icp_lm_options* o) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!o) { c->lm_on = false; return ICP_OK; }
+    const bool ok = o->max_num_iterations >= 0 && o->max_num_iterations <= 1000 && o->max_num_consecutive_invalid_steps >= 1 &&
+                    o->min_trust_region_radius > 0 && o->min_trust_region_radius <= o->initial_trust_region_radius &&
+                    o->initial_trust_region_radius <= o->max_trust_region_radius && std::isfinite(o->max_trust_region_radius) &&
+                    o->min_lm_diagonal > 0 && o->min_lm_diagonal <= o->max_lm_diagonal && std::isfinite(o->max_lm_diagonal) &&
+                    o->min_relative_decrease >= 0 && o->function_tolerance >= 0 && o->gradient_tolerance >= 0 && o->parameter_tolerance >= 0 &&
+                    std::isfinite(o->min_relative_decrease) && std::isfinite(o->function_tolerance) && std::isfinite(o->gradient_tolerance) &&
+                    std::isfinite(o->parameter_tolerance) && (o->jacobi_scaling == 0 || o->jacobi_scaling == 1);
+    if (!ok) { c->err = "icp_set_optimizer: options out of range"; return ICP_ERR_INVALID_ARG; }
+    c->lm_opt = *o; c->lm_on = true;
+    return ICP_OK;
+}
+
+int icp_get_lm_summaries(const icp_ctx* c, icp_lm_summary* out, int32_t max, int32_t* count) {
+    if (!c || !count || max < 0 || (max > 0 && !out)) return ICP_ERR_INVALID_ARG;
+    const int32_t n = (int32_t)c->lm_last.size();
+    for (int32_t i = 0; i < n && i < max; i++) out[i] = c->lm_last[(size_t)i];
+    *count = n;
+    return ICP_OK;
 }
 
 int icp_iterate(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats) {

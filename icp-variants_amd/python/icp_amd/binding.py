@@ -68,6 +68,42 @@ class IcpTrackFrame(C.Structure):
                 ("pose", C.c_float * 16)]
 
 
+class IcpLmOptions(C.Structure):
+    _fields_ = [("initial_trust_region_radius", C.c_double), ("max_trust_region_radius", C.c_double), ("min_trust_region_radius", C.c_double),
+                ("min_relative_decrease", C.c_double), ("min_lm_diagonal", C.c_double), ("max_lm_diagonal", C.c_double),
+                ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+                ("max_num_iterations", C.c_int32), ("max_num_consecutive_invalid_steps", C.c_int32), ("jacobi_scaling", C.c_int32)]
+
+
+class IcpLmSummary(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("successful_steps", C.c_int32), ("unsuccessful_steps", C.c_int32), ("invalid_steps", C.c_int32),
+                ("termination", C.c_int32), ("n_residual_blocks", C.c_int32),
+                ("accepted_steps_mask", C.c_uint32), ("invalid_steps_mask", C.c_uint32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("trust_region_radius", C.c_double), ("x", C.c_double * 6)]
+
+
+LM_CONVERGENCE, LM_NO_CONVERGENCE, LM_FAILURE, LM_NO_RESIDUALS = 0, 1, 2, 3
+
+
+def lm_options(**kw):
+    """icp_lm_options: Ceres' defaults with configureSolver's max_num_iterations = 10 (icp_lm_options_default), fields overridden by name."""
+    o = IcpLmOptions()
+    rc = load_library().icp_lm_options_default(C.byref(o))
+    if rc != ICP_OK:
+        raise IcpError(rc, "icp_lm_options_default")
+    for k, v in kw.items():
+        if not any(k == f[0] for f in IcpLmOptions._fields_):
+            raise TypeError("icp_lm_options has no field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def select_optimizer(ctx, nonlinear):
+    """The runners' `nonlinear=` argument: True / an IcpLmOptions -> the non-linear optimiser, False -> the linear one, None -> unchanged."""
+    if nonlinear is not None:
+        ctx.set_optimizer(nonlinear)
+
+
 def depth_camera(K, width, height, extrinsics=None):
     """icp_depth_camera from a 3x3 intrinsic matrix (K(0,0), K(1,1), K(0,2), K(1,2)) and an optional 4x4 depthExtrinsics."""
     K = np.asarray(K, dtype=np.float32)
@@ -106,6 +142,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_correspond", "icp_iterate", "icp_run", "icp_get_timing", "icp_get_iteration_times", "icp_set_stage_timing", "icp_set_convergence_reference", "icp_rmse", "icp_benchmark_error",
            "icp_transform_points", "icp_transform_normals", "icp_version", "icp_schedule", "icp_select_hash", "icp_backproject_depth", "icp_estimate_normals",
            "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames", "icp_depth_mesh",
+           "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
 
@@ -191,6 +228,37 @@ class Context:
     def _ck(self, rc):
         if rc != ICP_OK:
             raise IcpError(rc, self.lib.icp_last_error(self.h).decode())
+
+    def set_optimizer(self, options=True, **kw):
+        """icp_set_optimizer: options True (the defaults, fields overridden by kw) or an IcpLmOptions selects the non-linear optimiser
+        (CeresICPOptimizer); None / False return to the linear one."""
+        if options is None or options is False:
+            if kw:
+                raise TypeError("set_optimizer: field overrides need the non-linear optimiser (options True)")
+            self._ck(self.lib.icp_set_optimizer(self.h, None))
+            return None
+        if isinstance(options, IcpLmOptions):
+            if kw:
+                raise TypeError("set_optimizer: give either an IcpLmOptions or field overrides, not both")
+            o = options
+        elif options is True:
+            o = lm_options(**kw)
+        else:
+            raise TypeError("set_optimizer: options must be True, None, False or an IcpLmOptions")
+        self._ck(self.lib.icp_set_optimizer(self.h, C.byref(o)))
+        return o
+
+    def lm_summaries(self):
+        """icp_get_lm_summaries: one dict per ICP iteration of the last run (Solver::Summary of its ceres::Solve), all of them."""
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_get_lm_summaries(self.h, None, C.c_int32(0), C.byref(n)))
+        buf = (IcpLmSummary * max(n.value, 1))()
+        self._ck(self.lib.icp_get_lm_summaries(self.h, buf, C.c_int32(n.value), C.byref(n)))
+        return [dict(iterations=b.iterations, successful_steps=b.successful_steps, unsuccessful_steps=b.unsuccessful_steps,
+                     invalid_steps=b.invalid_steps, termination=b.termination, n_residual_blocks=b.n_residual_blocks,
+                     accepted_steps_mask=b.accepted_steps_mask, invalid_steps_mask=b.invalid_steps_mask,
+                     initial_cost=b.initial_cost, final_cost=b.final_cost, trust_region_radius=b.trust_region_radius, x=np.array(b.x[:], np.float64))
+                for b in buf[:n.value]]
 
     def push_params(self):
         self._ck(self.lib.icp_set_params(self.h, C.byref(self.params)))
@@ -496,3 +564,12 @@ class LinearICPOptimizer:
         pose, recs, rc = self.ctx.run(initialPose, check=check)
         self.last_status = rc
         return pose, recs
+
+
+class CeresICPOptimizer(LinearICPOptimizer):
+    """The reference's CeresICPOptimizer (ICPOptimizer.h:181-483): the same setters and loop, one Levenberg-Marquardt solve per
+    iteration on the device (icp_set_optimizer).  lm_options: field overrides of icp_lm_options."""
+
+    def __init__(self, device=0, stream=None, **options):
+        super().__init__(device, stream)
+        self.ctx.set_optimizer(True, **options)

@@ -5,6 +5,7 @@ Pure host logic over `formats.py` plus the two device steps in front of the loop
   src, tgt  = load_scans(eth_dir, csv_name, row)           # loadPCDFile<PointXYZ> x 2          (ETHDataLoader.h:66-98)
   pair      = prepare_pair(ctx, src, tgt, row["pose"])     # PointCloud(pcl) normals k = 5       (PointCloud.h:41-76)
                                                            # + pose_scaling 0.1 and change_pose  (main.cpp:420-429, PointCloud.h:277-282)
+  pose      = align(ctx, pair, nonlinear=...)              # estimatePose (main.cpp:457), USE_LINEAR_ICP 0 -> nonlinear=True
 `pair` has the keys of `synth.eth_like_pair` (src_pts, src_nrm, tgt_pts, tgt_nrm, src_unperturbed, gt), so the bench and the
 tests drive real files and synthetic scans through the same code.
 Layout on disk, as the reference expects it under Data/: <eth_dir>/<name>_global.csv and <eth_dir>/<name>/<scan>.pcd.
@@ -53,6 +54,18 @@ def prepare_pair(ctx, src_xyz, tgt_xyz, benchmark_pose, pose_scaling=0.1, k=5):
     return dict(src_pts=moved, src_nrm=moved_nrm, src_rgba=rgba, src_unperturbed=src_xyz,
                 tgt_pts=tgt_xyz, tgt_nrm=tgt_nrm, tgt_rgba=np.tile(np.array([255, 255, 255, 1], np.uint8), (len(tgt_xyz), 1)),
                 gt=np.linalg.inv(np.asarray(S, np.float64)), initial=S)
+
+
+def align(ctx, pair, nonlinear=None, check=True):
+    """estimatePose of alignETH (main.cpp:457) on a prepared pair with the context's params: the optimiser the reference's
+    USE_LINEAR_ICP picks (main.cpp:26) -- nonlinear True (or an IcpLmOptions): CeresICPOptimizer, False: LinearICPOptimizer, None: the
+    context's current choice.  Returns (4x4 pose, per-iteration records, status)."""
+    from . import binding
+    binding.select_optimizer(ctx, nonlinear)
+    ctx.push_params()
+    ctx.set_target(pair["tgt_pts"], pair["tgt_nrm"], pair.get("tgt_rgba"))
+    ctx.set_source(pair["src_pts"], pair["src_nrm"], pair.get("src_rgba"))
+    return ctx.run(np.eye(4, dtype=np.float32), check=check)
 
 
 def write_synthetic_dataset(eth_dir, csv_name, pairs, binary=True):

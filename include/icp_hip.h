@@ -158,6 +158,48 @@ int icp_set_stage_timing(icp_ctx* ctx, int32_t every_nth);
  * iteration, 0 = full cloud without selection.  ICPOptimizer.h:503-516,540,634-655 / PointCloud.h:325-343. */
 int icp_schedule(const icp_params* p, int32_t n_src, int32_t* factors_out, int32_t max_out, int32_t* count_out);
 
+/* -------- the non-linear optimiser: CeresICPOptimizer (ICPOptimizer.h:181-483), selected per context --------
+ * With it selected, icp_run / icp_iterate / icp_track_depth_frames / icp_batch_run keep the linear path's loop (schedule, selection,
+ * matching, weighting, rejection) and replace its solve by one Levenberg-Marquardt minimisation per ICP iteration over the residual
+ * blocks of constraints.h, from x = 0 (angle-axis rotation, translation), composed from the left: estimatedPose = T(x) * estimatedPose.
+ * The options are those of configureSolver (ICPOptimizer.h:352-360) and otherwise Ceres' defaults; DESIGN.md gives the contract.
+ * Iterations whose solve finds no residual block report ICP_ERR_NO_CORRESPONDENCES with the pose unchanged, like the linear path. */
+typedef struct icp_lm_options {
+    double initial_trust_region_radius;    /* 1e4   */
+    double max_trust_region_radius;        /* 1e16  */
+    double min_trust_region_radius;        /* 1e-32 */
+    double min_relative_decrease;          /* 1e-3  */
+    double min_lm_diagonal;                /* 1e-6  */
+    double max_lm_diagonal;                /* 1e32  */
+    double function_tolerance;             /* 1e-6  */
+    double gradient_tolerance;             /* 1e-10 */
+    double parameter_tolerance;            /* 1e-8  */
+    int32_t max_num_iterations;            /* 10 (configureSolver); 0 .. 1000 */
+    int32_t max_num_consecutive_invalid_steps;   /* 5 (>= 1) */
+    int32_t jacobi_scaling;                /* 1 */
+} icp_lm_options;
+enum { ICP_LM_CONVERGENCE = 0, ICP_LM_NO_CONVERGENCE = 1, ICP_LM_FAILURE = 2, ICP_LM_NO_RESIDUALS = 3 };   /* ceres::TerminationType + the empty problem */
+/* One record per ICP iteration of the last run (Solver::Summary). */
+typedef struct icp_lm_summary {
+    int32_t iterations;          /* LM iterations after iteration 0 (the index of the last one) */
+    int32_t successful_steps;    /* Ceres' count: iteration 0 included */
+    int32_t unsuccessful_steps;  /* rejected and invalid steps that completed an iteration */
+    int32_t invalid_steps;       /* steps the damped system or the model change refused */
+    int32_t termination;         /* ICP_LM_* */
+    int32_t n_residual_blocks;
+    uint32_t accepted_steps_mask;  /* bit k - 1: LM iteration k (1 .. 32) took its step (accepted) */
+    uint32_t invalid_steps_mask;   /* bit k - 1: LM iteration k had an invalid step; the other iterations < `iterations` were rejected,
+                                      and iteration `iterations` ended the solve on a tolerance when its bit is in neither mask */
+    double initial_cost, final_cost;     /* 1/2 sum r^2 at x = 0 and at the final x */
+    double trust_region_radius;          /* at termination */
+    double x[6];                         /* the increment composed into the pose (0 after ICP_LM_FAILURE) */
+} icp_lm_summary;
+int icp_lm_options_default(icp_lm_options* opt);
+/* opt != NULL selects the non-linear optimiser with these options (copied), NULL returns to the linear one. */
+int icp_set_optimizer(icp_ctx* ctx, const icp_lm_options* opt);
+/* The records of the last run through the non-linear optimiser: out[0 .. min(max, count)), *count = ICP iterations of that run. */
+int icp_get_lm_summaries(const icp_ctx* ctx, icp_lm_summary* out, int32_t max, int32_t* count);
+
 /* -------- ConvergenceMeasure (ConvergenceMeasure.h:30-66): known-correspondence RMSE --------
  * src_xyz[i] (moved by the estimated pose) is compared with ref_xyz[i]. */
 int icp_set_convergence_reference(icp_ctx* ctx, const float* src_xyz, const float* ref_xyz, int32_t n);

@@ -260,10 +260,36 @@ public:
     void setSelectionSeed(uint32_t seed) { m_seed = seed; m_seedPinned = true; }
     int lastStatus() const { return m_status; }
     const std::vector<icp_iter_stats>& iterations() const { return m_iterations; }
+protected:
+    icp_ctx* context() const { return m_ctx.get(); }
 private:
     icp_hip_detail::CtxPtr m_ctx; int m_status; bool m_hasCamera; float m_cam[4]; unsigned m_camW, m_camH;
     uint32_t m_seed = 0; bool m_seedPinned = false;
     std::vector<icp_iter_stats> m_iterations;
+};
+
+// CeresICPOptimizer, ICPOptimizer.h:181-483 (what USE_LINEAR_ICP 0 selects, main.cpp:26): the same setters and loop as
+// HipLinearICPOptimizer, with one Levenberg-Marquardt solve per iteration on the device (icp_set_optimizer; configureSolver's options,
+// ICPOptimizer.h:352-360, are icp_lm_options_default).  summaries() holds the Solver::Summary records of the last estimatePose.
+class HipCeresICPOptimizer : public HipLinearICPOptimizer {
+public:
+    explicit HipCeresICPOptimizer(int device = 0) : HipLinearICPOptimizer(device) {
+        icp_lm_options o; icp_lm_options_default(&o);
+        setSolverOptions(o);
+    }
+    int setSolverOptions(const icp_lm_options& o) { return context() ? icp_set_optimizer(context(), &o) : ICP_ERR_NO_DEVICE; }
+    void estimatePose(const PointCloud& source, const PointCloud& target, Matrix4f& initialPose, bool calculateRMSE = true) override {
+        HipLinearICPOptimizer::estimatePose(source, target, initialPose, calculateRMSE);
+        int32_t n = 0;
+        m_summaries.clear();
+        if (context() && icp_get_lm_summaries(context(), nullptr, 0, &n) == ICP_OK && n > 0) {       // (every record: the count first)
+            m_summaries.resize((size_t)n);
+            icp_get_lm_summaries(context(), m_summaries.data(), n, &n);
+        }
+    }
+    const std::vector<icp_lm_summary>& summaries() const { return m_summaries; }
+private:
+    std::vector<icp_lm_summary> m_summaries;
 };
 
 #endif  // ICP_HIP_ADAPTOR_HPP
