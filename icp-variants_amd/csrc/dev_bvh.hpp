@@ -830,7 +830,8 @@ constexpr int XW_SLOTS = 64, XW_CTRL = 32;
 constexpr int GX_SLOTS = 32, GX_GRANULES = 16;
 constexpr unsigned long long GX_EMPTY = ~0ull;
 #if defined(ICP_DEBUG_TIMES) && ICP_DEBUG_TIMES
-__device__ unsigned int g_gx_dbg[16];    // development builds: 0 posted, 1 claimed by helpers, 2 taken back, 3 results folded, 4 helper waves, 5 helper rounds, 6 helper rounds with a claim
+__device__ unsigned int g_gx_dbg[16];    // development builds: 0 posted, 1 claimed by helpers, 2 taken back, 3 results folded, 4 helper waves, 5 helper rounds, 6 helper rounds with a claim,
+                                         // 8-10 walk ends (ICP_DEBUG_WALK_ENDS), 11-12 lone searches, 13 cross-wave position repairs of a query with no candidate
 #define GX_COUNT(i, n) atomicAdd(&g_gx_dbg[i], (unsigned int)(n))
 #ifndef ICP_DEBUG_WALK_TRACE
 #define ICP_DEBUG_WALK_TRACE 0
@@ -1337,8 +1338,10 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
         lb3 = sqrt_dn(rest);
         l2o = key2 == ~0ull ? -1 : (int)(unsigned int)key2;
         if (XW && __builtin_amdgcn_readfirstlane(__hip_atomic_load(xc + 12 + myw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) {
-            // lanes of other waves folded into this record: the position written beside the key may belong to a fold that lost
-            if (bpos < 0 || bv.recs[bpos].idx != bi) bpos = bv.pos_of[bi];
+            // lanes of other waves folded into this record: the position written beside the key may belong to a fold that lost.
+            // No candidate at all (every squared distance overflowed): no position either -- pos_of has no entry for index -1.
+            if (bi < 0) { bpos = -1; GX_COUNT(13, 1); }
+            else if (bpos < 0 || bv.recs[bpos].idx != bi) bpos = bv.pos_of[bi];
         }
     } else {
         const uint2 a = R[3 * NT + lane], b = R[4 * NT + lane], c = R[5 * NT + lane];

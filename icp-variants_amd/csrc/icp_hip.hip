@@ -4,6 +4,7 @@
 // There is NO CPU fallback: every entry point needs a HIP device and fails with ICP_ERR_HIP /
 // ICP_ERR_NO_DEVICE when none is usable.
 // =====================================================================================
+#include <atomic>
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
@@ -129,13 +130,16 @@ namespace {
 
 constexpr int POST_BLOCKS = 512;
 
+// Device bytes held through ensure / release by every context of the process (views not counted): icp_debug_live_bytes.
+std::atomic<long long> g_live_bytes{0};
+
 int ensure(icp_ctx* c, DevBuf& b, size_t bytes) {
     if (bytes <= b.cap && b.p) return ICP_OK;
     if (b.view) { b.p = nullptr; b.cap = 0; b.view = false; }      // outgrown: becomes an allocation of its own
-    if (b.p) { HIPCK(c, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+    if (b.p) { HIPCK(c, hipFree(b.p)); g_live_bytes -= (long long)b.cap; b.p = nullptr; b.cap = 0; }
     size_t want = bytes < 256 ? 256 : bytes;
     HIPCK(c, hipMalloc(&b.p, want));
-    b.cap = want;
+    b.cap = want; g_live_bytes += (long long)want;
     return ICP_OK;
 }
 int ensure_pinned(icp_ctx* c, size_t bytes) {
@@ -146,7 +150,7 @@ int ensure_pinned(icp_ctx* c, size_t bytes) {
     c->pinned_cap = want;
     return ICP_OK;
 }
-void release(DevBuf& b) { if (b.p && !b.view) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; b.view = false; }
+void release(DevBuf& b) { if (b.p && !b.view) { (void)hipFree(b.p); g_live_bytes -= (long long)b.cap; } b.p = nullptr; b.cap = 0; b.view = false; }
 void set_view(DevBuf& b, void* p, size_t bytes) { release(b); b.p = p; b.cap = bytes; b.view = true; }
 void release(Cloud& c) { release(c.x); release(c.y); release(c.z); release(c.nx); release(c.ny); release(c.nz); release(c.cr); release(c.cg); release(c.cb); release(c.rgba); }
 void release(Level& lv) { release(lv.idx); release(lv.order); release(lv.sorted_idx); release(lv.sorted); release(lv.pack); lv.sorted_valid = false; }
@@ -1011,7 +1015,7 @@ int icp_ctx_destroy(icp_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     release(c->tgt); release(c->src); release(c->qry); release(c->conv_src); release(c->conv_ref);
     release(c->nrm_cloud);
-    for (Bvh* b : {&c->bvh, &c->bvh6, &c->nrm_bvh}) { release(b->qnodes); release(b->recs); for (DevBuf& d : b->axl) release(d); release(b->side); release(b->scanr); release(b->axis_of_node); }
+    for (Bvh* b : {&c->bvh, &c->bvh6, &c->nrm_bvh}) { release(b->qnodes); release(b->recs); release(b->pos_of); for (DevBuf& d : b->axl) release(d); release(b->side); release(b->scanr); release(b->axis_of_node); }
     for (Bvh* b : {&c->bvh6, &c->nrm_bvh}) { release(b->keys); release(b->keys2); release(b->vals); release(b->vals2); release(b->temp); release(b->leaves); release(b->nodes); release(b->lvl); release(b->wbox); }
     release(c->bvh.keys); release(c->bvh.keys2); release(c->bvh.vals); release(c->bvh.vals2); release(c->bvh.temp); release(c->bvh.leaves); release(c->okeys); release(c->okeys2); release(c->ovals); release(c->otemp); release(c->bvh.nodes); release(c->bvh.lvl); release(c->bvh.wbox);
     for (auto& kv : c->levels) release(kv.second);
@@ -1162,7 +1166,8 @@ int icp_correspond(icp_ctx* c, const float pose[16], icp_match_t* out, double* s
 }
 
 // The fused matcher driven launch by launch with caller-dictated poses: launch 0 unseeded, launch j > 0 seeded + incremental exactly
-// as iteration j of run_loop (same kernel, same buffers, same launch parameters); the last launch's records come back in source order.
+// as iteration j of icp_run runs it, in the form icp_run takes for the configuration (k_icp_loop, the merged ring launches or the
+// separate launches: same kernel, same buffers, same grid); the last launch's records come back in source order.
 int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_t* out, float* d2_out) {
     if (!c || !poses || n_poses <= 0) { if (c) c->err = "icp_match_seeded: bad argument"; return ICP_ERR_INVALID_ARG; }
     const icp_params& p = c->prm;
@@ -1176,7 +1181,8 @@ int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_
     const Cloud* cloud = nullptr; int n = 0;
     if ((rc = get_sorted_level(c, 0, &cloud, &n))) return rc;
     struct Keep { icp_ctx* c; ~Keep() { c->keep_fused_records = false; } } keep{c};
-    if (c->persist_loop && c->merge_loop && p.metric == ICP_METRIC_POINT_TO_PLANE) {
+    const bool one_launch = c->persist_loop && c->merge_loop && p.metric == ICP_METRIC_POINT_TO_PLANE;
+    if (one_launch) {
         // what icp_run launches for this configuration: k_icp_loop, all the launches' worth of iterations in ONE launch -- here with every pose
         // slot filled in up front (replica 0 of each; nobody reduces, nobody solves), the last iteration writing its records
         const int nb = fused_nblocks(n);
@@ -1203,15 +1209,68 @@ int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_
         HIPCK(c, hipMemcpyAsync(&hf, fault, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCK(c, hipStreamSynchronize(c->stream));           // (hp is read by the copies above)
         if (hf) { c->err = "icp_match_seeded: k_icp_loop gave up waiting"; return ICP_ERR_HIP; }
-    } else
-    for (int j = 0; j < n_poses; j++) {
-        if ((rc = write_pose(c, poses + (size_t)16 * j))) return rc;
+    }
+    // ring: what run_loop launches for this configuration one launch per iteration (the merged loop, dev_solve.hpp "the ring form"):
+    // k_knn_bvh_post_ring, launch j > 0 with the reducer of launch j - 1 in its first NSUM_USED blocks and the matcher blocks behind them.
+    // Every matcher waits on slot j, filled here up front with the caller's pose j; the reducers fold the previous launch's partials
+    // (the same double buffering as run_loop) and publish into a scratch slot nobody waits on.  Otherwise (point-to-point, ICP_HIP_MERGE=0):
+    // the separate k_knn_bvh_post launches, each at the pose written in front of it.
+    const bool ring = !one_launch && c->merge_loop && !c->lm_on && p.metric == ICP_METRIC_POINT_TO_PLANE;
+    std::vector<unsigned long long> slot_image;              // (read by the copy below until the synchronisation at the end)
+    PoseState* slots = nullptr; unsigned long long* trows = nullptr; int* run_fault = nullptr;
+    if (ring) {
+        const int nb = fused_nblocks(n), nbmax = nb > POST_BLOCKS ? nb : POST_BLOCKS;
+        const int n_rows = n_poses > 1 ? n_poses - 1 : 1;    // totals rows: one per reduced launch
+        const size_t slot_bytes = (size_t)(n_poses + 1) * POSE_REPLICAS * POSE_REPLICA_STRIDE, tot_bytes = (size_t)n_rows * NSUM * 8;
+        if ((rc = ensure(c, c->ring, slot_bytes + tot_bytes + 64))) return rc;
+        if ((rc = ensure(c, c->partials, (size_t)nbmax * NSUM * 8))) return rc;
+        if ((rc = ensure(c, c->partials2, (size_t)nbmax * NSUM * 8))) return rc;
+        slots = c->ring.as<PoseState>(); trows = (unsigned long long*)(c->ring.as<char>() + slot_bytes); run_fault = (int*)(c->ring.as<char>() + slot_bytes + tot_bytes);
+        // slots 0 .. n_poses - 1 in every replica, encoded as the reducer publishes a slot (16 granules of PoseState, fault word zero);
+        // slot n_poses, the reducers' scratch, starts empty
+        slot_image.assign(slot_bytes / 8, GRANULE_EMPTY);
+        for (int j = 0; j < n_poses; j++) {
+            PoseState ps; memset(&ps, 0, sizeof(ps)); memcpy(ps.pose, poses + (size_t)16 * j, 64); normal_matrix_from_pose(ps.pose, ps.nmat);
+            const unsigned long long* g = (const unsigned long long*)&ps;
+            for (int r = 0; r < POSE_REPLICAS; r++)
+                for (int q = 0; q < 16; q++)
+                    slot_image[((size_t)j * POSE_REPLICAS + r) * (POSE_REPLICA_STRIDE / 8) + q] = g[q] == GRANULE_EMPTY ? g[q] ^ 1ull : g[q];
+        }
+        HIPCK(c, hipMemcpyAsync(slots, slot_image.data(), slot_bytes, hipMemcpyHostToDevice, c->stream));
+        const int n_init = n_rows * NSUM + 16;               // the totals rows empty, the fault word zero (k_run_init without its pose slots)
+        hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, nullptr, slots, 0, trows, n_rows * NSUM, run_fault, 16);
+        HIPCK(c, hipGetLastError());
+    }
+    for (int j = 0; !one_launch && j < n_poses; j++) {
+        if (!ring && (rc = write_pose(c, poses + (size_t)16 * j))) return rc;
         c->keep_fused_records = (j == n_poses - 1);
         QuerySet q{cloud, nullptr, n, 0, p.color_icp != 0, j > 0, nullptr};
+        MergeLaunch ml; memset(&ml.rp, 0, sizeof(ml.rp)); ml.slot = nullptr; ml.partials = nullptr;
+        if (ring) {                                          // as ring_params(j) of run_loop, but the reducer's pose goes to the scratch slot
+            ml.rp.run_fault = run_fault;
+            if (j > 0) {
+                ml.rp.n_red = NSUM_USED;
+                ml.rp.red_partials = ((j - 1) & 1) ? c->partials2.as<double>() : c->partials.as<double>(); ml.rp.red_nblocks = fused_nblocks(n);
+                ml.rp.totals_row = trows + (size_t)(j - 1) * NSUM; ml.rp.ps_in = loop_slot(slots, j - 1, 0); ml.rp.ps_out = loop_slot(slots, n_poses, 0);
+                ml.rp.n_src = n;
+            }
+            ml.slot = loop_slot(slots, j, 0); ml.partials = (j & 1) ? c->partials2.as<double>() : c->partials.as<double>();
+        }
         int fused = 0;
-        if ((rc = launch_match(c, q, &fused))) return rc;
+        if ((rc = launch_match(c, q, &fused, ring ? &ml : nullptr))) return rc;
         if (!fused) { c->err = "icp_match_seeded: the matcher did not take the fused path"; return ICP_ERR_INVALID_ARG; }
-        HIPCK(c, hipStreamSynchronize(c->stream));           // the pose staging area is reused by the next launch
+        if (!ring) {
+            int hf = 0;
+            HIPCK(c, hipMemcpyAsync(&hf, &c->ps.as<PoseState>()->fault, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCK(c, hipStreamSynchronize(c->stream));       // the pose staging area is reused by the next launch
+            if (hf) { c->err = "icp_match_seeded: a bounded wait of the matcher ran out (k_knn_bvh_post)"; return ICP_ERR_HIP; }
+        }
+    }
+    if (ring) {
+        int hf = 0;
+        HIPCK(c, hipMemcpyAsync(&hf, run_fault, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (hf) { c->err = "icp_match_seeded: a bounded wait of the merged launches ran out (k_knn_bvh_post_ring)"; return ICP_ERR_HIP; }
     }
     std::vector<int> pos((size_t)n); std::vector<icp_match_t> m((size_t)n); std::vector<float> d((size_t)n);
     HIPCK(c, hipMemcpyAsync(pos.data(), c->levels[0].sorted_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2035,6 +2094,13 @@ int icp_debug_pos_of_mismatches(icp_ctx* c, int32_t* n_bad, int32_t* n_checked) 
     HIPCK(c, hipMemcpyAsync(n_bad, c->d_count.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (n_checked) *n_checked = c->bvh.n_valid;
+    return ICP_OK;
+}
+//   icp_debug_live_bytes      : device bytes the library holds right now, over every context of the process (its own allocations, views
+//                               not counted): a create -> use -> destroy cycle must leave it where it found it.  No context needed.
+int icp_debug_live_bytes(int64_t* out) {
+    if (!out) return ICP_ERR_INVALID_ARG;
+    *out = (int64_t)g_live_bytes.load();
     return ICP_OK;
 }
 int icp_debug_counters(icp_ctx* c, int32_t* merged_runs, int32_t* merged_fallbacks) {
