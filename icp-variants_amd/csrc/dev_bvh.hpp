@@ -1499,14 +1499,6 @@ __device__ __forceinline__ int knn_bvh_lane_query(const KnnParams& kp, const int
 
 template <int DIM>
 __global__ __launch_bounds__(BVH_THREADS) void k_knn_bvh(const KnnParams kp, const BvhViewT<DIM> bv, const int* __restrict__ qorder) {
-    extern __shared__ uint2 bvh_lbq[];                    // [ICP_SHARE_ROWS][BVH_THREADS]: the shared walk's records
-    const int tid = threadIdx.x;
-    const int k = knn_bvh_lane_query(kp, qorder, tid);
-    float best; int bi, bpos;
-    knn_bvh_query<DIM>(kp, bv, k, bvh_lbq, tid, best, bi, bpos);
-    if (k < 0) return;
-    icp_match_t m;
-    if (best <= kp.max_dist) { m.idx = bi; m.weight = 1.f; } else { m.idx = -1; m.weight = 0.f; }
-    kp.out[k] = m;
+#include "dev_body_knn_bvh.hpp"
 }
 

@@ -7,7 +7,7 @@
 // (fp64 Jacobi), flipped towards the viewpoint (pcl::flipNormalTowardsViewpoint), curvature = l0 / (l0 + l1 + l2).
 // Neighbour sets are the exact K smallest (d2, index) pairs.  PCL itself is absent here: parity unpinned; every point is checked
 // against the oracle's orc_estimate_normals (tests/test_gpu_normals.py), which is cross-checked against numpy.
-template <int n> __device__ inline void jacobi_eig_sym(double* A, double* V, double* ev);     // defined with the solvers below
+template <int n, int COPY = 0> __device__ inline void jacobi_eig_sym(double* A, double* V, double* ev);     // defined with the solvers below (COPY: see solve_tail)
 
 template <int K>
 __device__ __forceinline__ void knn_insert(float (&bd)[K], int (&bj)[K], float d, int j) {

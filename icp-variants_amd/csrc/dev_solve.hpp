@@ -2,7 +2,7 @@
 // Part of icp_device.hpp (included from there, inside namespace icpdev); see that file for the build contract.
 // ------------------------------------------------------------------------------------------------
 // fp64 small dense solvers, run by one thread of k_reduce_solve.
-template <int n>
+template <int n, int COPY>           // (default COPY = 0 on the declaration in dev_normals.hpp; see solve_tail)
 __device__ inline void jacobi_eig_sym(double* A /* n x n, destroyed */, double* V, double* ev) {
 #pragma unroll
     for (int i = 0; i < n; i++) {
@@ -101,6 +101,7 @@ __device__ __forceinline__ bool solve_ldlt6(const double* sums, double* x) {
     return true;
 }
 
+template <int COPY = 0>
 __device__ inline void solve_normal_svd(const double* sums /* 21 + 6 */, double* x) {
     if (solve_ldlt6(sums, x)) return;
     // workspaces in LDS, not in registers / scratch: this runs on ONE thread, and inside the fused matcher it must not raise the
@@ -109,7 +110,7 @@ __device__ inline void solve_normal_svd(const double* sums /* 21 + 6 */, double*
     int q = 0;
     for (int a = 0; a < 6; a++) for (int c = a; c < 6; c++) { A[a * 6 + c] = sums[q]; A[c * 6 + a] = sums[q]; q++; }
     const double* g = sums + 21;
-    jacobi_eig_sym<6>(A, V, ev);
+    jacobi_eig_sym<6, COPY>(A, V, ev);
     double emax = 0.0;
     for (int i = 0; i < 6; i++) emax = fmax(emax, ev[i]);
     const double thr = 6.0 * 1.1920928955078125e-07;
@@ -126,6 +127,7 @@ __device__ inline void solve_normal_svd(const double* sums /* 21 + 6 */, double*
 // FullPivLU::solve with its rank rule in fp64 (ICPOptimizer.h:866-868).
 // M, rhs, x, colp and y are caller-provided workspaces (LDS in k_reduce_solve: dynamically indexed local arrays would live in
 // scratch memory, two orders of magnitude slower per access for this single-thread code).
+template <int COPY = 0>
 __device__ inline void solve_fullpiv_lu6(double* M, double* rhs, double* x, int* colp, double* y) {
     const int n = 6;
     for (int i = 0; i < n; i++) colp[i] = i;
@@ -156,10 +158,11 @@ __device__ inline void solve_fullpiv_lu6(double* M, double* rhs, double* x, int*
 // for the two leading columns.  With c = U_0 x U_1 the reference's product collapses to
 //   R = U_0 V_0^T + U_1 V_1^T + det(V) * c * V_2^T
 // (flipping the sign of the third left vector flips det(UV^T) too), which stays well defined when sigma_3 -> 0.
+template <int COPY = 0>
 __device__ inline void procrustes_rotation(const double* A /* 3x3 row-major */, double* R) {
     __shared__ double B[9], V[9], ev[3], Vs[9], U[9];     // LDS workspaces (single thread): see solve_normal_svd
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { double s = 0; for (int k = 0; k < 3; k++) s += A[k * 3 + i] * A[k * 3 + j]; B[i * 3 + j] = s; }
-    jacobi_eig_sym<3>(B, V, ev);
+    jacobi_eig_sym<3, COPY>(B, V, ev);
     int o[3] = {0, 1, 2};
     for (int a = 0; a < 2; a++) for (int b = a + 1; b < 3; b++) if (ev[o[b]] > ev[o[a]]) { const int t = o[a]; o[a] = o[b]; o[b] = t; }
     for (int c = 0; c < 3; c++) for (int r = 0; r < 3; r++) Vs[r * 3 + c] = V[r * 3 + o[c]];
@@ -266,6 +269,7 @@ struct SolveParams {
 // the compiler must keep the order (wave_sync).  Measured in the merged launch (tools/dev_ring_times.py): 2.8 us with twelve block barriers,
 // six sequential divisions in the back substitution and the rotation composed by one thread.
 __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+template <int COPY = 0>
 __device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* shared */, const float* pose_in) {
     __shared__ double A[6][7], Lm[6][6], od[6], zs[6];
     __shared__ float npose[16];
@@ -339,10 +343,11 @@ __device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* sh
 }
 // The k_reduce_solve form: pose state updated in place.  Returns false (nothing written) when the fast path does not apply: other
 // metrics, no valid pair, or a pivot fails the rank test -> the caller's single-thread path with the eigen fallback.
+template <int COPY = 0>
 __device__ __forceinline__ bool solve_p2plane_lanes(const SolveParams& sp, const double* tot /* shared */) {
     if (!(sp.update_pose && sp.metric == ICP_METRIC_POINT_TO_PLANE && sp.phase == 0 && tot[SUM_N] > 0)) return false;   // uniform
     PoseState* ps = sp.ps;
-    const float* npose = p2plane_lanes_core(tot + SUM_M, ps->pose);
+    const float* npose = p2plane_lanes_core<COPY>(tot + SUM_M, ps->pose);
     if (!npose) return false;
     const int tid = threadIdx.x;
     if (tid == 0 && sp.sums_out) for (int a = 0; a < NSUM; a++) sp.sums_out[a] = tot[a];
@@ -363,7 +368,7 @@ __device__ __forceinline__ bool solve_p2plane_lanes(const SolveParams& sp, const
 // that holds the NSUM totals in `tot` (shared memory).  (A real call would not help the fused matcher, which inlines it too: on
 // AMDGPU a kernel reserves the registers of everything it may call -- 254 here.  The matcher caps its own budget instead, so this
 // cold code spills there rather than costing the tree walk a wave per SIMD.)
-template <bool WITH_SYMMETRIC>
+template <bool WITH_SYMMETRIC, int COPY = 0>
 __device__ inline void solve_generic(const SolveParams& sp, const double* tot) {
     if (sp.sums_out) for (int a = 0; a < NSUM; a++) sp.sums_out[a] = tot[a];
     PoseState* ps = sp.ps;
@@ -383,7 +388,7 @@ __device__ inline void solve_generic(const SolveParams& sp, const double* tot) {
         status = ICP_ERR_NO_CORRESPONDENCES;
     } else if (sp.metric == ICP_METRIC_POINT_TO_PLANE) {
         double x[6];
-        solve_normal_svd(tot + SUM_M, x);
+        solve_normal_svd<COPY>(tot + SUM_M, x);
         const float al = (float)x[0], be = (float)x[1], ga = (float)x[2];       // ICPOptimizer.h:768
         const float ca = (float)cos((double)al), sa = (float)sin((double)al);
         const float cb = (float)cos((double)be), sb = (float)sin((double)be);
@@ -401,7 +406,7 @@ __device__ inline void solve_generic(const SolveParams& sp, const double* tot) {
         for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++)
             A[j * 3 + k] = m[7 + j * 3 + k] - m[4 + j] * (double)msf[k] - (double)mdf[j] * m[1 + k] + m[0] * (double)mdf[j] * (double)msf[k];
         float R[9];
-        procrustes_rotation(A, Rd);
+        procrustes_rotation<COPY>(A, Rd);
         for (int i = 0; i < 9; i++) R[i] = (float)Rd[i];
         const float tr[3] = {mdf[0] - msf[0], mdf[1] - msf[1], mdf[2] - msf[2]};     // ProcrustesAligner.h:70
         float t[3];
@@ -420,7 +425,7 @@ __device__ inline void solve_generic(const SolveParams& sp, const double* tot) {
         for (int a = 0; a < 6; a++) g[a] = tot[SUM_M + 21 + a];
         const float lambda = 0.0001f; const float l2 = lambda * lambda;
         for (int a = 0; a < 6; a++) M[a * 6 + a] += (double)l2;
-        solve_fullpiv_lu6(M, g, x, colp, ywork);
+        solve_fullpiv_lu6<COPY>(M, g, x, colp, ywork);
         const float at[3] = {(float)x[0], (float)x[1], (float)x[2]}, tt[3] = {(float)x[3], (float)x[4], (float)x[5]};
         const float tan_theta = sqrtf(at[0] * at[0] + (at[1] * at[1] + at[2] * at[2]));     // :878
         const float ax[3] = {at[0] / tan_theta, at[1] / tan_theta, at[2] / tan_theta};      // :879
@@ -456,10 +461,12 @@ __device__ inline void solve_generic(const SolveParams& sp, const double* tot) {
 }
 
 // Reduced sums -> pose update.  All threads of the block call it (>= 64 threads); `tot` = NSUM totals in shared memory.
-template <bool WITH_SYMMETRIC = true>
+// COPY: an instantiation of the whole solve of its own -- its own LDS workspaces and call sites -- for a new kernel (k_reduce_solve_multi),
+// so that the kernels that had the solve before keep exactly the code they had.
+template <bool WITH_SYMMETRIC = true, int COPY = 0>
 __device__ __forceinline__ void solve_tail(const SolveParams& sp, const double* tot) {
-    if (solve_p2plane_lanes(sp, tot)) return;             // common case, spread over the lanes of this block
-    if (threadIdx.x == 0) solve_generic<WITH_SYMMETRIC>(sp, tot);
+    if (solve_p2plane_lanes<COPY>(sp, tot)) return;       // common case, spread over the lanes of this block
+    if (threadIdx.x == 0) solve_generic<WITH_SYMMETRIC, COPY>(sp, tot);
 }
 
 // Grid of NSUM_USED blocks: block a folds the partials of sum a in a fixed order (lanes stride the producer blocks, shuffle tree,
@@ -470,79 +477,7 @@ constexpr unsigned long long TOTAL_SENTINEL = 0xFFF8D1CEC0DE5EEDull;      // a N
 constexpr int SPIN_LIMIT = 1 << 22;                        // polls of ~1 us: seconds, not a hang
 constexpr int SOLVE_INFLIGHT = 12;                        // loads in flight per thread: 12 x 256 = 3072 partials in ONE memory round trip
 __global__ __launch_bounds__(SOLVE_THREADS) void k_reduce_solve(const SolveParams sp) {
-    __shared__ double tot[NSUM];
-    __shared__ double wsum[SOLVE_THREADS / WAVE];
-    __shared__ int is_last;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, a = blockIdx.x;
-    {
-        const double* __restrict__ row = sp.partials + (size_t)a * sp.nblocks;
-        // The partials come from the producer kernel's write-back: every load is a trip to memory, and what this kernel costs is the
-        // number of DEPENDENT trips.  All of a thread's loads are issued before the first add (fixed assignment b = t + 256 j, added in
-        // the order of j: the same sum on every run); 2 895 partials are one round, not three.
-        double x = 0.0;
-        for (int b0 = 0; b0 < sp.nblocks; b0 += SOLVE_INFLIGHT * SOLVE_THREADS) {
-            double v[SOLVE_INFLIGHT];
-#pragma unroll
-            for (int j = 0; j < SOLVE_INFLIGHT; j++) { const int b = b0 + j * SOLVE_THREADS + (int)threadIdx.x; v[j] = b < sp.nblocks ? row[b] : 0.0; }
-#pragma unroll
-            for (int j = 0; j < SOLVE_INFLIGHT; j++) { const int b = b0 + j * SOLVE_THREADS + (int)threadIdx.x; if (b < sp.nblocks) x += v[j]; }
-        }
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, WAVE);
-        if (lane == 0) wsum[w] = x;
-    }
-    __syncthreads();
-    if (sp.spin) {
-        // Hand-over without a ticket: every total is ONE naturally aligned 8-byte write-through store and validates itself (anything
-        // but the sentinel the slots hold between launches), so nothing has to be ordered against anything: block 0 -- always
-        // resident, like the other 33 -- polls the 34 slots with sc1 loads, one lane per slot, takes the values, puts the sentinels
-        // back and solves.  Against store -> drain -> ticket -> re-load that is two dependent trips to memory less per launch.  The
-        // wait is bounded: after SPIN_LIMIT polls (seconds) the launch gives up, raises PoseState::fault and the run reports
-        // ICP_ERR_HIP instead of hanging or solving with a slot that was never written.
-        if (threadIdx.x == 0) {
-            double x = wsum[0];
-            for (int k = 1; k < SOLVE_THREADS / WAVE; k++) x += wsum[k];
-            unsigned long long bits = (unsigned long long)__double_as_longlong(x);
-            if (bits == TOTAL_SENTINEL) bits ^= 1ull;         // (still a NaN: the solve's result is the same)
-            __hip_atomic_store((unsigned long long*)sp.totals + a, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (a != 0) return;
-        if (threadIdx.x < NSUM) {
-            double v = 0.0;
-            if (threadIdx.x < NSUM_USED) {
-                unsigned long long* slot = (unsigned long long*)sp.totals + threadIdx.x;
-                unsigned long long bits = TOTAL_SENTINEL;
-                for (int spin = 0; spin < SPIN_LIMIT; spin++) {
-                    bits = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (bits != TOTAL_SENTINEL) break;
-                    __builtin_amdgcn_s_sleep(2);
-                }
-                if (bits == TOTAL_SENTINEL) sp.ps->fault = 1;         // never written within the bound
-                v = __longlong_as_double((long long)bits);
-                __hip_atomic_store(slot, TOTAL_SENTINEL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
-            }
-            tot[threadIdx.x] = v;
-        }
-        __syncthreads();
-        solve_tail(sp, tot);
-        return;
-    }
-    if (threadIdx.x == 0) {
-        double x = wsum[0];
-        for (int k = 1; k < SOLVE_THREADS / WAVE; k++) x += wsum[k];
-        // hand-over without fences (MI355X_MICROARCH.md, valid forms): write-through store of the total, drained, then the ticket; the
-        // last arriver reads the totals with sc1 loads issued after its add has returned.  A release / acquire fence pair here is an L2
-        // write-back plus an L1 invalidate per block, ~3 us of this kernel's ~9.
-        __hip_atomic_store(sp.totals + a, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned t = __hip_atomic_fetch_add(sp.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (t == (unsigned)(NSUM_USED - 1));
-    }
-    __syncthreads();
-    if (!is_last) return;
-    if (threadIdx.x < NSUM) tot[threadIdx.x] = threadIdx.x < NSUM_USED ? __hip_atomic_load(sp.totals + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;   // rows NSUM_USED.. are padding
-    __syncthreads();
-    if (threadIdx.x == 0) *sp.ticket = 0u;                // ready for the next launch on this stream
-    solve_tail(sp, tot);
+#include "dev_body_reduce_solve.hpp"
 }
 
 // Measured and NOT adopted (round 2): the same reduction + solve as ONE block of 1024 threads for producers that leave few partials

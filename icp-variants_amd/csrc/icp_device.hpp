@@ -29,6 +29,8 @@
 //   k_rmse_partial      ConvergenceMeasure::rmseAlignmentError (ConvergenceMeasure.h:50-66)
 //   k_depth_count /     PointCloud(depthMap, colorFrame, ...) (PointCloud.h:78-165): back-projection, normals, stride and filter of a
 //   k_depth_scatter     depth frame as a stable two-pass compaction straight into a context cloud (dev_depth.hpp)
+//   k_*_multi           multi-start ICP (icp_run_multistart): the matcher, post stage and reduce / solve of every start in ONE launch,
+//                       start = blockIdx.y; k_score_multi / k_score_fold score the final poses (dev_multi.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -53,5 +55,6 @@ namespace icpdev {
 #include "dev_measures.hpp"
 #include "dev_mesh.hpp"
 #include "dev_lm.hpp"
+#include "dev_multi.hpp"
 
 }  // namespace icpdev

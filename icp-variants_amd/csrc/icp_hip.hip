@@ -97,6 +97,7 @@ struct icp_ctx {
     bool lm_on = false; icp_lm_options lm_opt;   // icp_set_optimizer: the non-linear optimiser (k_lm_eval / k_lm_step) instead of the linear solve
     DevBuf lm_state, lm_partials, lm_sums;       // its minimiser state, eval partials, per-iteration records of the run in flight
     std::vector<icp_lm_summary> lm_last;         // the records of the last run (icp_get_lm_summaries)
+    DevBuf ms_ps, ms_nn, ms_st, ms_st2, ms_rec, ms_d2, ms_partials, ms_totals, ms_stats, ms_score, ms_res;   // icp_run_multistart: one slice per start (dev_multi.hpp)
     icp_params prm;
     Cloud tgt, src, qry;                 // qry: scratch cloud of icp_query_matches
     Cloud nrm_cloud; Bvh nrm_bvh;        // scratch of icp_estimate_normals
@@ -1021,6 +1022,7 @@ int icp_ctx_destroy(icp_ctx* c) {
     for (auto& kv : c->levels) release(kv.second);
     release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->pring); release(c->totals); release(c->dbg_steps); release(c->sums); release(c->gx_slots); release(c->gx_hdr);
     release(c->lm_state); release(c->lm_partials); release(c->lm_sums);
+    for (DevBuf* d : {&c->ms_ps, &c->ms_nn, &c->ms_st, &c->ms_st2, &c->ms_rec, &c->ms_d2, &c->ms_partials, &c->ms_totals, &c->ms_stats, &c->ms_score, &c->ms_res}) release(*d);
     release(c->stats); release(c->staging); release(c->rmse_partials); release(c->rmse_out); release(c->fontana_partials);
     for (DevBuf* d : {&c->src_flag, &c->src_box, &c->tgt_flag, &c->tgt_finite, &c->nrm_finite, &c->sel_temp, &c->d_count}) release(*d);
     if (c->depth_stream) { (void)hipStreamSynchronize(c->depth_stream); (void)hipStreamDestroy(c->depth_stream); }
@@ -1309,6 +1311,49 @@ int icp_schedule(const icp_params* p, int32_t n_src, int32_t* factors_out, int32
 
 static int enqueue_fontana(icp_ctx* c, float* d_out);
 
+// The query set of every iteration of a run (icp_run, icp_run_multistart), resolved up front (uploads) so that the loop itself is
+// launch-only: the level's cloud (a Morton-sorted copy for the BVH matcher without resampling), its selection, its size.
+static int resolve_queries(icp_ctx* c, const std::vector<int>& factors, bool single, std::vector<const Cloud*>& clouds, std::vector<const int*>& sels,
+                           std::vector<int>& ns, std::vector<const int*>& orders) {
+    const icp_params& p = c->prm;
+    const int iters = (int)factors.size();
+    int rc;
+    sels.assign((size_t)iters, nullptr); ns.assign((size_t)iters, c->src.n); orders.assign((size_t)iters, nullptr); clouds.assign((size_t)iters, &c->src);
+    // BVH matcher without resampling: every level is a physical, Morton-sorted copy -> no index lists in the loop at all
+    const bool sorted_levels = p.matching == ICP_MATCH_KNN && p.knn_backend == ICP_KNN_LBVH && !(!single && p.selection == 1);
+    for (int i = 0; i < iters; i++) {
+        if (sorted_levels) { if ((rc = get_sorted_level(c, factors[i], &clouds[i], &ns[i]))) return rc; }
+        else if (factors[i] > 0) { if ((rc = get_level(c, factors[i], &sels[i], &ns[i], nullptr))) return rc; }
+    }
+    if (!single && p.selection == 1) {
+        // RANDOM_SAMPLING (ICPOptimizer.h:549-550: resample at the start of every iteration, over the current level's cloud).
+        // All resamples are drawn up front on the device; one small copy returns their sizes so the loop stays launch-only.
+        double th = (double)p.selection_proba * 4294967296.0;
+        const int take_all = th >= 4294967296.0 ? 1 : 0;
+        const uint32_t threshold = th <= 0.0 ? 0u : (take_all ? 0xFFFFFFFFu : (uint32_t)th);
+        const size_t cap = (size_t)c->src.n;
+        if ((rc = ensure(c, c->sel_lists, (size_t)iters * cap * 4))) return rc;
+        if ((rc = ensure(c, c->sel_counts, (size_t)iters * 4))) return rc;
+        if ((rc = ensure(c, c->sel_blocks, (size_t)((cap + 255) / 256 + 1) * 4))) return rc;
+        for (int i = 0; i < iters; i++) {
+            const int nb = (ns[i] + 255) / 256;
+            int* out = c->sel_lists.as<int>() + (size_t)i * cap;
+            if (ns[i] > 0) {
+                hipLaunchKernelGGL(k_select_count, dim3(nb), dim3(256), 0, c->stream, sels[i], ns[i], p.selection_seed, (uint32_t)i, threshold, take_all, c->sel_blocks.as<int>());
+                hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, c->stream, c->sel_blocks.as<int>(), nb, c->sel_counts.as<int>() + i);
+                hipLaunchKernelGGL(k_select_scatter, dim3(nb), dim3(256), 0, c->stream, sels[i], ns[i], p.selection_seed, (uint32_t)i, threshold, take_all, c->sel_blocks.as<int>(), out);
+            } else HIPCK(c, hipMemsetAsync(c->sel_counts.as<int>() + i, 0, 4, c->stream));
+            sels[i] = out; orders[i] = nullptr;
+        }
+        HIPCK(c, hipGetLastError());
+        std::vector<int> counts((size_t)iters);
+        HIPCK(c, hipMemcpyAsync(counts.data(), c->sel_counts.p, (size_t)iters * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < iters; i++) ns[i] = counts[i];
+    }
+    return ICP_OK;
+}
+
 static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t max_stats, int32_t* n_run, bool single) {
     const icp_params& p = c->prm;
     int rc;
@@ -1344,41 +1389,9 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     // (every record of an iteration with work is written in full by k_reduce_solve; empty iterations are filled in on the host)
     if ((rc = ensure_events(c, (size_t)iters * 4 + 2))) return rc;
     // resolve selections up front (uploads) so the loop itself is launch-only
-    std::vector<const int*> sels(iters, nullptr); std::vector<int> ns(iters, c->src.n);
-    std::vector<const int*> orders(iters, nullptr);
-    std::vector<const Cloud*> clouds(iters, &c->src);
-    // BVH matcher without resampling: every level is a physical, Morton-sorted copy -> no index lists in the loop at all
+    std::vector<const int*> sels, orders; std::vector<int> ns; std::vector<const Cloud*> clouds;
     const bool sorted_levels = p.matching == ICP_MATCH_KNN && p.knn_backend == ICP_KNN_LBVH && !(!single && p.selection == 1);
-    for (int i = 0; i < iters; i++) {
-        if (sorted_levels) { if ((rc = get_sorted_level(c, factors[i], &clouds[i], &ns[i]))) return rc; }
-        else if (factors[i] > 0) { if ((rc = get_level(c, factors[i], &sels[i], &ns[i], nullptr))) return rc; }
-    }
-    if (!single && p.selection == 1) {
-        // RANDOM_SAMPLING (ICPOptimizer.h:549-550: resample at the start of every iteration, over the current level's cloud).
-        // All resamples are drawn up front on the device; one small copy returns their sizes so the loop stays launch-only.
-        double th = (double)p.selection_proba * 4294967296.0;
-        const int take_all = th >= 4294967296.0 ? 1 : 0;
-        const uint32_t threshold = th <= 0.0 ? 0u : (take_all ? 0xFFFFFFFFu : (uint32_t)th);
-        const size_t cap = (size_t)c->src.n;
-        if ((rc = ensure(c, c->sel_lists, (size_t)iters * cap * 4))) return rc;
-        if ((rc = ensure(c, c->sel_counts, (size_t)iters * 4))) return rc;
-        if ((rc = ensure(c, c->sel_blocks, (size_t)((cap + 255) / 256 + 1) * 4))) return rc;
-        for (int i = 0; i < iters; i++) {
-            const int nb = (ns[i] + 255) / 256;
-            int* out = c->sel_lists.as<int>() + (size_t)i * cap;
-            if (ns[i] > 0) {
-                hipLaunchKernelGGL(k_select_count, dim3(nb), dim3(256), 0, c->stream, sels[i], ns[i], p.selection_seed, (uint32_t)i, threshold, take_all, c->sel_blocks.as<int>());
-                hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, c->stream, c->sel_blocks.as<int>(), nb, c->sel_counts.as<int>() + i);
-                hipLaunchKernelGGL(k_select_scatter, dim3(nb), dim3(256), 0, c->stream, sels[i], ns[i], p.selection_seed, (uint32_t)i, threshold, take_all, c->sel_blocks.as<int>(), out);
-            } else HIPCK(c, hipMemsetAsync(c->sel_counts.as<int>() + i, 0, 4, c->stream));
-            sels[i] = out; orders[i] = nullptr;
-        }
-        HIPCK(c, hipGetLastError());
-        std::vector<int> counts((size_t)iters);
-        HIPCK(c, hipMemcpyAsync(counts.data(), c->sel_counts.p, (size_t)iters * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < iters; i++) ns[i] = counts[i];
-    }
+    if ((rc = resolve_queries(c, factors, single, clouds, sels, ns, orders))) return rc;
     const bool rmse = (p.record_rmse & 1) && c->conv_n > 0;
     const bool fontana = (p.record_rmse & 2) && c->conv_n > 0;
     if (rmse) { if ((rc = ensure(c, c->rmse_partials, 256 * 2 * 8))) return rc; }
@@ -1680,6 +1693,168 @@ int icp_iterate(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats) {
 int icp_run(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t max_stats, int32_t* n_iterations_run) {
     if (!c || !pose_inout) { if (c) c->err = "icp_run: bad argument"; return ICP_ERR_INVALID_ARG; }
     return run_loop(c, pose_inout, stats, stats ? max_stats : 0, n_iterations_run, false);
+}
+
+// Multi-start ICP (dev_multi.hpp): run_loop's generic per-iteration form -- matcher (+ post) and reduce / solve -- with start s as blockIdx.y
+// of every launch, each start in slices of its own (pose state, search state, records, partials, hand-over, iteration records).  The ticket
+// hand-over of k_reduce_solve, not the polling one: no block waits for another, so the K x 34 reducer blocks need not be resident together.
+constexpr int MULTISTART_MAX = 256;
+int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts, icp_start_result* results, icp_iter_stats* stats,
+                       int32_t max_stats, int32_t* n_iterations_run, int32_t* best_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!initial_poses || !results || n_starts < 1 || n_starts > MULTISTART_MAX || max_stats < 0) {
+        c->err = "icp_run_multistart: bad argument (initial_poses and results non-NULL, 1 <= n_starts <= 256, max_stats >= 0)"; return ICP_ERR_INVALID_ARG;
+    }
+    const icp_params& p = c->prm;
+    if (p.matching != ICP_MATCH_KNN) { c->err = "icp_run_multistart: projective matching is not supported"; return ICP_ERR_INVALID_ARG; }
+    if (p.knn_backend != ICP_KNN_LBVH) { c->err = "icp_run_multistart: the brute-force k-NN backend is not supported"; return ICP_ERR_INVALID_ARG; }
+    if (p.record_rmse != 0) { c->err = "icp_run_multistart: record_rmse is not supported"; return ICP_ERR_INVALID_ARG; }
+    if (c->lm_on) { c->err = "icp_run_multistart: the non-linear optimiser is not supported"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = check_ready(c, true, true))) return rc;
+    const int K = n_starts;
+    std::vector<int> factors;
+    {
+        int32_t cnt = 0;
+        if ((rc = icp_schedule(&p, c->src.n, nullptr, 0, &cnt))) { c->err = "multires with n_iterations < 1 never terminates in the reference"; return rc; }
+        factors.resize((size_t)cnt);
+        if (cnt > 0) icp_schedule(&p, c->src.n, factors.data(), cnt, &cnt);
+    }
+    const int iters = (int)factors.size();
+    if (n_iterations_run) *n_iterations_run = 0;
+    std::vector<const int*> sels, orders; std::vector<int> ns; std::vector<const Cloud*> clouds;
+    if ((rc = resolve_queries(c, factors, false, clouds, sels, ns, orders))) return rc;
+    // the score's queries: the full-resolution source, Morton-sorted; its index: the 3-D tree over the target's xyz (built on demand)
+    const Cloud* full = nullptr; int n_full = 0;
+    if ((rc = get_sorted_level(c, 0, &full, &n_full))) return rc;
+    if (!c->bvh.valid && (rc = build_bvh<3>(c, c->bvh, target_coords3(c)))) return rc;
+    const bool colors = p.color_icp != 0;
+    if (colors && !c->bvh6.valid && (rc = build_bvh<6>(c, c->bvh6, target_coords6(c)))) return rc;
+    const bool fused = c->fuse_post && p.metric != ICP_METRIC_SYMMETRIC;
+    // per-start slices, sized for the largest query set of the run
+    int nmax = n_full, nbmax = POST_BLOCKS;
+    for (int i = 0; i < iters; i++) { if (ns[i] > nmax) nmax = ns[i]; if (fused && fused_nblocks(ns[i]) > nbmax) nbmax = fused_nblocks(ns[i]); }
+    MultiStride ms;
+    ms.q = ((size_t)nmax + 63) / 64 * 64; ms.partials = (size_t)nbmax * NSUM; ms.totals = NSUM + 1; ms.stats = iters > 0 ? iters : 1;
+    const size_t Kz = (size_t)K;
+    if ((rc = ensure(c, c->ms_ps, Kz * sizeof(PoseState)))) return rc;
+    if ((rc = ensure(c, c->ms_nn, Kz * ms.q * 4))) return rc;
+    if ((rc = ensure(c, c->ms_st, Kz * ms.q * 16))) return rc;
+    if ((rc = ensure(c, c->ms_st2, Kz * ms.q * 8))) return rc;
+    if ((rc = ensure(c, c->ms_rec, Kz * ms.q * sizeof(icp_match_t)))) return rc;
+    if ((rc = ensure(c, c->ms_d2, Kz * ms.q * 4))) return rc;
+    if ((rc = ensure(c, c->ms_partials, Kz * ms.partials * 8))) return rc;
+    if ((rc = ensure(c, c->ms_totals, Kz * ms.totals * 8))) return rc;
+    if ((rc = ensure(c, c->ms_stats, Kz * (size_t)ms.stats * sizeof(icp_iter_stats)))) return rc;
+    if ((rc = ensure(c, c->ms_score, Kz * MSCORE_BLOCKS * 3 * 8))) return rc;
+    if ((rc = ensure(c, c->ms_res, Kz * sizeof(icp_start_result)))) return rc;
+    // page-locked staging: [pose states up | records down | results down]
+    const size_t pin_rec = (Kz * sizeof(PoseState) + 255) & ~(size_t)255, pin_res = pin_rec + ((Kz * (size_t)ms.stats * sizeof(icp_iter_stats) + 255) & ~(size_t)255);
+    if ((rc = ensure_pinned(c, pin_res + Kz * sizeof(icp_start_result)))) return rc;
+    PoseState* hps = (PoseState*)c->pinned;
+    for (int s = 0; s < K; s++) {
+        memset(&hps[s], 0, sizeof(PoseState)); memcpy(hps[s].pose, initial_poses + (size_t)16 * s, 64); normal_matrix_from_pose(hps[s].pose, hps[s].nmat);
+    }
+    PoseState* d_ps = c->ms_ps.as<PoseState>();
+    HIPCK(c, hipMemcpyAsync(d_ps, hps, Kz * sizeof(PoseState), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemsetAsync(c->ms_totals.p, 0, Kz * ms.totals * 8, c->stream));      // K tickets (and totals) armed: rearm_handover's ticket form
+    // what every launch shares
+    KnnParams kb; memset(&kb, 0, sizeof(kb));
+    kb.tx = c->tgt.x.as<float>(); kb.ty = c->tgt.y.as<float>(); kb.tz = c->tgt.z.as<float>();
+    kb.tcr = c->tgt.cr.as<float>(); kb.tcg = c->tgt.cg.as<float>(); kb.tcb = c->tgt.cb.as<float>();
+    kb.mpad = c->tgt.npad; kb.ps = d_ps; kb.pretransformed = 0; kb.max_dist = p.max_distance; kb.nseg = 1;
+    kb.fault = &d_ps->fault; kb.gx = GxParams{nullptr, nullptr, 0, 0};
+    auto view3 = [&]() { BvhViewT<3> v; Bvh& b = c->bvh; v.leaves = b.leaves.as<BvhLeafT<3>>(); v.nodes = b.nodes.as<BvhNodeT<3>>(); v.n_valid = b.n_valid; v.Lp = b.Lp; v.tgt = target_coords3(c);
+                          v.qnodes = b.qnodes.as<BvhQuadT<3>>(); v.Lq = b.Lq; v.recs = b.recs.as<TgtRec>(); v.pos_of = b.pos_of.as<int>(); return v; };
+    auto view6 = [&]() { BvhViewT<6> v; Bvh& b = c->bvh6; v.leaves = b.leaves.as<BvhLeafT<6>>(); v.nodes = b.nodes.as<BvhNodeT<6>>(); v.n_valid = b.n_valid; v.Lp = b.Lp; v.tgt = target_coords6(c);
+                          v.qnodes = b.qnodes.as<BvhQuadT<6>>(); v.Lq = b.Lq; v.recs = b.recs.as<TgtRec>(); v.pos_of = b.pos_of.as<int>(); return v; };
+    const size_t stack_bytes = (size_t)(ICP_SHARE_WALKS ? ICP_SHARE_ROWS : 1) * BVH_THREADS * 8, red_bytes = (size_t)(BVH_THREADS / WAVE) * 33 * 8;
+    const size_t lds_fused = (stack_bytes > red_bytes ? stack_bytes : red_bytes) + (colors ? xw_lds_bytes<6, BVH_THREADS>() : xw_lds_bytes<3, BVH_THREADS>());
+    for (int i = 0; i < iters; i++) {
+        if (ns[i] <= 0) continue;                                // an empty iteration: nothing runs, the records are filled in below
+        const int n = ns[i];
+        const Cloud* q = clouds[i];
+        KnnParams kp = kb;
+        kp.sx = q->x.as<float>(); kp.sy = q->y.as<float>(); kp.sz = q->z.as<float>(); kp.scr = q->cr.as<float>(); kp.scg = q->cg.as<float>(); kp.scb = q->cb.as<float>();
+        kp.sel = sels[i]; kp.n = n;
+        kp.nn_raw = c->ms_nn.as<int>();
+        kp.use_prev = (i > 0 && factors[i] == factors[i - 1] && ns[i - 1] > 0 && p.selection == 0) ? 1 : 0;      // run_loop's seeding rule
+        if (p.knn_incremental) { kp.qstate = c->ms_st.as<float4>(); kp.qstate2 = c->tier2 ? c->ms_st2.as<float2>() : nullptr; kp.incremental = 1; }
+        PostParams pp = make_post_params(c, *q, sels[i], n);
+        pp.ps = d_ps; pp.partials = c->ms_partials.as<double>();
+        int nb;
+        if (fused) {                                             // k_knn_bvh_post: records not kept
+            kp.out = nullptr; kp.d2_out = nullptr; pp.matches = nullptr;
+            nb = fused_nblocks(n);
+            const dim3 g((unsigned)nb, (unsigned)K);
+            if (colors) { const BvhViewT<6> bv = view6();
+                if (bv.Lq <= 8) hipLaunchKernelGGL((k_knn_bvh_post_multi<6, false>), g, dim3(BVH_THREADS), lds_fused, c->stream, kp, bv, orders[i], pp, ms);
+                else hipLaunchKernelGGL((k_knn_bvh_post_multi<6, true>), g, dim3(BVH_THREADS), lds_fused, c->stream, kp, bv, orders[i], pp, ms); }
+            else { const BvhViewT<3> bv = view3();
+                if (bv.Lq <= 8) hipLaunchKernelGGL((k_knn_bvh_post_multi<3, false>), g, dim3(BVH_THREADS), lds_fused, c->stream, kp, bv, orders[i], pp, ms);
+                else hipLaunchKernelGGL((k_knn_bvh_post_multi<3, true>), g, dim3(BVH_THREADS), lds_fused, c->stream, kp, bv, orders[i], pp, ms); }
+        } else {                                                 // k_knn_bvh, then k_post
+            kp.out = c->ms_rec.as<icp_match_t>(); kp.d2_out = c->ms_d2.as<float>(); pp.matches = c->ms_rec.as<icp_match_t>();
+            const dim3 g((unsigned)((n + BVH_THREADS - 1) / BVH_THREADS), (unsigned)K);
+            if (colors) hipLaunchKernelGGL(k_knn_bvh_multi<6>, g, dim3(BVH_THREADS), stack_bytes, c->stream, kp, view6(), orders[i], ms);
+            else hipLaunchKernelGGL(k_knn_bvh_multi<3>, g, dim3(BVH_THREADS), stack_bytes, c->stream, kp, view3(), orders[i], ms);
+            nb = (n + POST_THREADS - 1) / POST_THREADS; if (nb > POST_BLOCKS) nb = POST_BLOCKS; if (nb < 1) nb = 1;
+            hipLaunchKernelGGL(k_post_multi, dim3((unsigned)nb, (unsigned)K), dim3(POST_THREADS), 0, c->stream, pp, ms);
+        }
+        SolveParams sp; memset(&sp, 0, sizeof(sp));
+        sp.partials = c->ms_partials.as<double>(); sp.nblocks = nb; sp.ps = d_ps; sp.metric = p.metric;
+        sp.totals = c->ms_totals.as<double>(); sp.n_src = n; sp.update_pose = 1; sp.spin = 0;
+        icp_iter_stats* d_st = c->ms_stats.as<icp_iter_stats>() + i;
+        const dim3 gr(NSUM_USED, (unsigned)K);
+        if (p.metric == ICP_METRIC_SYMMETRIC) {
+            sp.phase = 0; sp.stats = nullptr;
+            hipLaunchKernelGGL(k_reduce_solve_multi, gr, dim3(SOLVE_THREADS), 0, c->stream, sp, ms);      // means
+            hipLaunchKernelGGL(k_sym_accumulate_multi, dim3((unsigned)nb, (unsigned)K), dim3(POST_THREADS), 0, c->stream, pp, ms);
+            sp.phase = 1;
+        } else sp.phase = 0;
+        sp.stats = d_st;
+        hipLaunchKernelGGL(k_reduce_solve_multi, gr, dim3(SOLVE_THREADS), 0, c->stream, sp, ms);
+        HIPCK(c, hipGetLastError());
+    }
+    {   // score at the final poses: every full-resolution source point, unseeded, in 3-D
+        KnnParams kp = kb;
+        kp.sx = full->x.as<float>(); kp.sy = full->y.as<float>(); kp.sz = full->z.as<float>(); kp.n = n_full;
+        kp.out = c->ms_rec.as<icp_match_t>(); kp.d2_out = c->ms_d2.as<float>();
+        if (n_full > 0) hipLaunchKernelGGL(k_knn_bvh_multi<3>, dim3((unsigned)((n_full + BVH_THREADS - 1) / BVH_THREADS), (unsigned)K), dim3(BVH_THREADS), stack_bytes, c->stream, kp, view3(), nullptr, ms);
+        ScoreParams sc; sc.sx = kp.sx; sc.sy = kp.sy; sc.sz = kp.sz; sc.n = n_full; sc.matches = kp.out; sc.d2 = kp.d2_out; sc.q = ms.q; sc.partials = c->ms_score.as<double>();
+        hipLaunchKernelGGL(k_score_multi, dim3(MSCORE_BLOCKS, (unsigned)K), dim3(MSCORE_THREADS), 0, c->stream, sc);
+        hipLaunchKernelGGL(k_score_fold, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, c->stream, c->ms_score.as<double>(), MSCORE_BLOCKS, d_ps, K, c->ms_res.as<icp_start_result>());
+        HIPCK(c, hipGetLastError());
+    }
+    icp_iter_stats* hrec = (icp_iter_stats*)((char*)c->pinned + pin_rec);
+    icp_start_result* hres = (icp_start_result*)((char*)c->pinned + pin_res);
+    if (iters > 0) HIPCK(c, hipMemcpyAsync(hrec, c->ms_stats.p, Kz * (size_t)ms.stats * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(hres, c->ms_res.p, Kz * sizeof(icp_start_result), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(hps, d_ps, Kz * sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));     // (the fault words)
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    guard.ok = true;
+    for (int s = 0; s < K; s++)
+        if (hps[s].fault) { c->err = "icp_run_multistart: a bounded wait of the matcher ran out on the device"; return ICP_ERR_HIP; }
+    int best = 0;
+    for (int s = 0; s < K; s++) {
+        icp_iter_stats* hs = hrec + (size_t)s * ms.stats;
+        int status = ICP_OK;
+        for (int i = 0; i < iters; i++) {                        // run_loop's host side, per start
+            if (ns[i] <= 0) { hs[i].n_src = 0; hs[i].n_valid = 0; hs[i].status = ICP_ERR_NO_CORRESPONDENCES; memcpy(hs[i].pose, i ? hs[i - 1].pose : initial_poses + (size_t)16 * s, 64); }
+            hs[i].rmse = -1.f; hs[i].benchmark_error = -1.f;
+            if (hs[i].status != ICP_OK && status == ICP_OK) status = hs[i].status;
+            if (stats && i < max_stats) stats[(size_t)s * max_stats + i] = hs[i];
+        }
+        results[s] = hres[s];
+        results[s].status = status;
+        const icp_start_result& a = results[s], &b = results[best];
+        if (a.n_inliers > b.n_inliers || (a.n_inliers == b.n_inliers && a.inlier_rmse < b.inlier_rmse)) best = s;      // ties: smaller rmse, then lower index
+    }
+    if (n_iterations_run) *n_iterations_run = iters;
+    if (best_out) *best_out = best;
+    return ICP_OK;
 }
 
 int icp_set_stage_timing(icp_ctx* c, int32_t every_nth) {

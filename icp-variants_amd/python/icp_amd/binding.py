@@ -43,6 +43,10 @@ class IcpIterStats(C.Structure):
                 ("status", C.c_int32)]
 
 
+class IcpStartResult(C.Structure):
+    _fields_ = [("pose", C.c_float * 16), ("status", C.c_int32), ("n_inliers", C.c_int32), ("fitness", C.c_float), ("inlier_rmse", C.c_float)]
+
+
 class IcpTiming(C.Structure):
     _fields_ = [("match_ms", C.c_double), ("weight_reject_build_ms", C.c_double), ("solve_ms", C.c_double),
                 ("total_ms", C.c_double), ("iterations", C.c_int32), ("sampled_iterations", C.c_int32)]
@@ -139,7 +143,7 @@ COMM_ID_BYTES = 128
 # every symbol include/icp_hip.h declares (tests check the library exports all of them)
 EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp_last_error", "icp_params_default",
            "icp_set_params", "icp_get_params", "icp_set_target", "icp_set_source", "icp_query_matches", "icp_match", "icp_match_seeded",
-           "icp_correspond", "icp_iterate", "icp_run", "icp_get_timing", "icp_get_iteration_times", "icp_set_stage_timing", "icp_set_convergence_reference", "icp_rmse", "icp_benchmark_error",
+           "icp_correspond", "icp_iterate", "icp_run", "icp_run_multistart", "icp_get_timing", "icp_get_iteration_times", "icp_set_stage_timing", "icp_set_convergence_reference", "icp_rmse", "icp_benchmark_error",
            "icp_transform_points", "icp_transform_normals", "icp_version", "icp_schedule", "icp_select_hash", "icp_backproject_depth", "icp_estimate_normals",
            "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames", "icp_depth_mesh",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
@@ -312,6 +316,20 @@ class Context:
         recs = [dict(n_src=st[i].n_src, n_valid=st[i].n_valid, pose=pose_from_c(st[i].pose), rmse=st[i].rmse, benchmark_error=st[i].benchmark_error, status=st[i].status)
                 for i in range(min(n.value, max_stats))]
         return pose_from_c(p), recs, rc
+
+    def run_multistart(self, poses, max_stats=512):
+        """icp_run_multistart: ICP from every pose of `poses` (K x 4 x 4) at once.  Returns (results, stats, best): one dict per start
+        (pose, status, n_inliers, fitness, inlier_rmse), the iteration records of each start (a list of record lists, as `run` gives
+        them), and the index of the best start."""
+        poses = list(poses)
+        K = len(poses)
+        ps = np.ascontiguousarray(np.stack([pose_to_c(p) for p in poses]) if K else np.zeros((0, 16)), dtype=np.float32)
+        res = (IcpStartResult * max(K, 1))(); st = (IcpIterStats * max(K * max_stats, 1))(); n = C.c_int32(0); best = C.c_int32(-1)
+        self._ck(self.lib.icp_run_multistart(self.h, _ptr(ps) if K else None, C.c_int32(K), res, st, C.c_int32(max_stats), C.byref(n), C.byref(best)))
+        results = [dict(pose=pose_from_c(r.pose), status=r.status, n_inliers=r.n_inliers, fitness=r.fitness, inlier_rmse=r.inlier_rmse) for r in res[:K]]
+        stats = [[dict(n_src=r.n_src, n_valid=r.n_valid, pose=pose_from_c(r.pose), rmse=r.rmse, benchmark_error=r.benchmark_error, status=r.status)
+                  for r in st[k * max_stats:k * max_stats + min(n.value, max_stats)]] for k in range(K)]
+        return results, stats, best.value
 
     def run_raw(self, pose_c16):
         """Timed-loop entry for bench.py: pose buffer in/out (column-major float32[16]), no record marshalling."""

@@ -150,6 +150,32 @@ int icp_correspond(icp_ctx* ctx, const float pose[16], icp_match_t* out, double*
 int icp_iterate(icp_ctx* ctx, float pose_inout[16], icp_iter_stats* stats);
 int icp_run(icp_ctx* ctx, float pose_inout[16], icp_iter_stats* stats, int32_t max_stats, int32_t* n_iterations_run);
 int icp_get_timing(const icp_ctx* ctx, icp_timing* out);
+
+/* -------- multi-start ICP (extension: the reference has no counterpart) --------
+ * ICP is local: from a poor initial pose it settles in a wrong minimum.  icp_run_multistart aligns the context's pair from
+ * n_starts initial poses at once (initial_poses: n_starts x 16 floats, column-major) -- one set of launches per ICP iteration for
+ * all starts, the target index, the source levels and the random draws shared.  Start k's trajectory equals icp_run from
+ * initial_poses[k] on the same context with the same params, bit for bit: every record of stats[k * max_stats ..] (n_src, n_valid,
+ * pose, status; rmse and benchmark_error -1) and results[k].pose.  A start that loses all its correspondences reports it in its own
+ * status (ICP_ERR_NO_CORRESPONDENCES, pose left where icp_run leaves it); the call returns ICP_OK unless an argument is invalid or a
+ * HIP call fails.  Score of a start, at its final pose, on the FULL-resolution source (no multires level, no random sample): every
+ * finite source point moved by the pose (utils.h:113-115) and matched in 3-D against the target's xyz (also with color_icp on) is an
+ * inlier when its squared distance is <= max_distance -- exactly when icp_match would return idx >= 0 for it; n_inliers, fitness =
+ * n_inliers / finite source points, inlier_rmse = sqrt(sum d^2 / n_inliers) (fp64 sum in a fixed order), -1 without inliers.
+ * *best_out (optional): the start with the most inliers, ties to the smaller inlier_rmse, then to the lower index.
+ * Supported: k-NN matching on the LBVH backend (3-D or colour 6-D), every metric, weighting, rejection, multires, SELECT_ALL and
+ * RANDOM_SAMPLING; 1 <= n_starts <= 256.  NOT supported (ICP_ERR_INVALID_ARG, see icp_last_error): projective matching, the
+ * brute-force backend, record_rmse != 0 and the non-linear optimiser.  stats may be NULL; n_iterations_run (optional) receives the
+ * iterations of the schedule, the same for every start. */
+typedef struct icp_start_result {
+    float   pose[16];      /* final pose of this start, column-major */
+    int32_t status;        /* what icp_run would have returned for this start alone */
+    int32_t n_inliers;     /* full-resolution source points with a 3-D neighbour within max_distance at the final pose */
+    float   fitness;       /* n_inliers / finite source points */
+    float   inlier_rmse;   /* sqrt(sum d2 / n_inliers), -1 when n_inliers == 0 */
+} icp_start_result;
+int icp_run_multistart(icp_ctx* ctx, const float* initial_poses, int32_t n_starts, icp_start_result* results, icp_iter_stats* stats,
+                       int32_t max_stats, int32_t* n_iterations_run, int32_t* best_out);
 /* The same breakdown iteration by iteration for the last icp_run (what TimeMeasure accumulates, before the sum): entry i is the
  * device time of iteration i in milliseconds, or -1 when that iteration was not bracketed (icp_set_stage_timing(N != 1)).  Any of
  * the three arrays may be NULL; *count_out = iterations of the last run. */
