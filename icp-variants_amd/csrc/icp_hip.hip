@@ -98,6 +98,9 @@ struct icp_ctx {
     DevBuf lm_state, lm_partials, lm_sums;       // its minimiser state, eval partials, per-iteration records of the run in flight
     std::vector<icp_lm_summary> lm_last;         // the records of the last run (icp_get_lm_summaries)
     DevBuf ms_ps, ms_nn, ms_st, ms_st2, ms_rec, ms_d2, ms_partials, ms_totals, ms_stats, ms_score, ms_res;   // icp_run_multistart: one slice per start (dev_multi.hpp)
+    icp_gicp_options gicp_opt = {1e-3f, 20};     // icp_set_gicp_options
+    DevBuf gicp_n[2][3], gicp_flag;              // GICP normals of the target [0] / source [1] (SoA, original order), finite flags of their scratch tree
+    bool gicp_ready[2] = {false, false};         // the cache is current (dropped by every call that replaces the cloud and by new options)
     icp_params prm;
     Cloud tgt, src, qry;                 // qry: scratch cloud of icp_query_matches
     Cloud nrm_cloud; Bvh nrm_bvh;        // scratch of icp_estimate_normals
@@ -595,7 +598,7 @@ int launch_match(icp_ctx* c, const QuerySet& q, int* fused_blocks = nullptr, con
         if (p.knn_incremental && !q.pretransformed) {
             kp.qstate = c->qstate.as<float4>(); kp.qstate2 = c->tier2 ? c->qstate2.as<float2>() : nullptr; kp.incremental = 1;
         }
-        const Cloud* fuse = (fused_blocks != nullptr && p.metric != ICP_METRIC_SYMMETRIC && !q.pretransformed) ? q.cl : nullptr;
+        const Cloud* fuse = (fused_blocks != nullptr && p.metric != ICP_METRIC_SYMMETRIC && p.metric != ICP_METRIC_GICP && !q.pretransformed) ? q.cl : nullptr;
         if (q.use_colors) return launch_bvh_query<6>(c, c->bvh6, target_coords6(c), kp, q.order, q.n, fuse, fused_blocks, fuse ? ml : nullptr);
         return launch_bvh_query<3>(c, c->bvh, target_coords3(c), kp, q.order, q.n, fuse, fused_blocks, fuse ? ml : nullptr);
     }
@@ -631,6 +634,20 @@ int rearm_handover(icp_ctx* c) {
     return ICP_OK;
 }
 
+// What k_post_gicp reads beside the post parameters: the cached GICP normals (gicp_prepare has made them current) and, when the post stage
+// runs over a Morton-sorted level, that level's sorted position -> original index map.
+GicpPost gicp_post_params(icp_ctx* c, const Cloud& src) {
+    GicpPost g; memset(&g, 0, sizeof(g));
+    const bool own_t = c->gicp_opt.covariance_k == 0, own_s = own_t;
+    g.tnx = own_t ? c->tgt.nx.as<float>() : c->gicp_n[0][0].as<float>(); g.tny = own_t ? c->tgt.ny.as<float>() : c->gicp_n[0][1].as<float>(); g.tnz = own_t ? c->tgt.nz.as<float>() : c->gicp_n[0][2].as<float>();
+    g.snx = own_s ? c->src.nx.as<float>() : c->gicp_n[1][0].as<float>(); g.sny = own_s ? c->src.ny.as<float>() : c->gicp_n[1][1].as<float>(); g.snz = own_s ? c->src.nz.as<float>() : c->gicp_n[1][2].as<float>();
+    g.src_orig = nullptr;
+    if (&src != &c->src)
+        for (auto& kv : c->levels) if (&kv.second.sorted == &src) g.src_orig = kv.second.sorted_idx.as<int>();
+    g.one_minus_eps = 1.0 - (double)c->gicp_opt.epsilon;
+    return g;
+}
+
 // Enqueue weight + reject + accumulate (+ symmetric second pass) + reduce/solve (no sync).
 int launch_post_and_solve(icp_ctx* c, const Cloud& src, const int* sel, int n, icp_iter_stats* d_stats, double* d_sums_out, int update_pose,
                           hipEvent_t ev_after_post, int fused_blocks = 0) {
@@ -641,9 +658,11 @@ int launch_post_and_solve(icp_ctx* c, const Cloud& src, const int* sel, int n, i
     const PostParams pp = make_post_params(c, src, sel, n);
     int nb = (n + POST_THREADS - 1) / POST_THREADS; if (nb > POST_BLOCKS) nb = POST_BLOCKS; if (nb < 1) nb = 1;
     if (fused_blocks) nb = fused_blocks;                    // the matcher already wrote the block partials
+    else if (p.metric == ICP_METRIC_GICP) hipLaunchKernelGGL(k_post_gicp, dim3(nb), dim3(POST_THREADS), 0, c->stream, pp, gicp_post_params(c, src));
     else hipLaunchKernelGGL(k_post, dim3(nb), dim3(POST_THREADS), 0, c->stream, pp);
     SolveParams sp; memset(&sp, 0, sizeof(sp));
-    sp.partials = c->partials.as<double>(); sp.nblocks = nb; sp.ps = c->ps.as<PoseState>(); sp.metric = p.metric;
+    // (GICP's sums have point-to-plane's layout and take its solve and composition: k_reduce_solve as it is, dev_gicp.hpp)
+    sp.partials = c->partials.as<double>(); sp.nblocks = nb; sp.ps = c->ps.as<PoseState>(); sp.metric = p.metric == ICP_METRIC_GICP ? ICP_METRIC_POINT_TO_PLANE : p.metric;
     sp.totals = c->totals.as<double>(); sp.ticket = (unsigned*)(c->totals.as<double>() + NSUM);
     sp.n_src = n; sp.update_pose = update_pose; sp.spin = c->spin_reduce ? 1 : 0;
     auto reduce_solve = [&]() { hipLaunchKernelGGL(k_reduce_solve, dim3(NSUM_USED), dim3(SOLVE_THREADS), 0, c->stream, sp); };
@@ -817,6 +836,7 @@ int finish_target(icp_ctx* c, bool with_colors) {
     Bvh& b = c->bvh;
     c->bvh6.valid = false;
     b.valid = false; b.n_valid = 0;
+    c->gicp_ready[0] = false;
     if ((rc = finite_list(c, c->tgt, false, c->tgt_flag, c->tgt_finite, &b.n_valid))) return rc;
     b.d_finite = c->tgt_finite.as<int>(); b.n_ids = c->tgt.n;
     c->bvh6.d_finite = b.d_finite; c->bvh6.n_valid = b.n_valid; c->bvh6.n_ids = c->tgt.n;
@@ -835,6 +855,7 @@ int finish_source(icp_ctx* c) {
     const int n = c->src.n; const Cloud& s = c->src;
     for (auto& kv : c->levels) release(kv.second);
     c->levels.clear();
+    c->gicp_ready[1] = false;
     if (n <= 0) return ICP_OK;
     if ((rc = ensure(c, c->src_flag, (size_t)n))) return rc;
     if ((rc = ensure(c, c->src_box, 32))) return rc;
@@ -951,6 +972,50 @@ int enqueue_rmse(icp_ctx* c, float* d_out) {
     return ICP_OK;
 }
 
+// GICP normals of the target (which 0) or the source (1) into the context's cache (icp_gicp_options, dev_gicp.hpp): covariance_k = 0 reads
+// the cloud's own normals (nothing to compute); otherwise k_gicp_normals<k> over the target's own BVH when it exists, else over a scratch
+// tree of the cloud (icp_estimate_normals' tree and finite list: they are rebuilt by every call that uses them).  Enqueued only.
+int gicp_normals(icp_ctx* c, int which) {
+    Cloud& cl = which ? c->src : c->tgt;
+    const int k = c->gicp_opt.covariance_k;
+    if (k == 0) {
+        if (!cl.has_normals) { c->err = "GICP with covariance_k = 0 needs normals on both clouds"; return ICP_ERR_INVALID_ARG; }
+        return ICP_OK;
+    }
+    if (c->gicp_ready[which]) return ICP_OK;
+    const int n = cl.n;
+    int rc;
+    for (DevBuf& d : c->gicp_n[which]) if ((rc = ensure(c, d, (size_t)n * 4))) return rc;
+    CoordPtrs<3> cp; cp.c[0] = cl.x.as<float>(); cp.c[1] = cl.y.as<float>(); cp.c[2] = cl.z.as<float>();
+    Bvh* b = &c->bvh;
+    if (which == 1 || !c->bvh.valid) {
+        b = &c->nrm_bvh; b->valid = false;
+        if ((rc = finite_list(c, cl, false, c->gicp_flag, c->nrm_finite, &b->n_valid))) return rc;
+        b->d_finite = c->nrm_finite.as<int>(); b->n_ids = n;
+        if ((rc = build_bvh<3>(c, *b, cp))) return rc;
+    }
+    BvhViewT<3> bv; bv.leaves = b->leaves.as<BvhLeafT<3>>(); bv.nodes = b->nodes.as<BvhNodeT<3>>(); bv.n_valid = b->n_valid; bv.Lp = b->Lp; bv.tgt = cp;
+    bv.qnodes = b->qnodes.as<BvhQuadT<3>>(); bv.Lq = b->Lq; bv.recs = b->recs.as<TgtRec>(); bv.pos_of = b->pos_of.as<int>();
+    int depth = 0; while ((1 << depth) < b->Lp) depth++;
+    const dim3 grid((n + BVH_THREADS - 1) / BVH_THREADS), block(BVH_THREADS); const size_t lds = (size_t)(depth + 1) * BVH_THREADS * 2;
+    float* o[3] = {c->gicp_n[which][0].as<float>(), c->gicp_n[which][1].as<float>(), c->gicp_n[which][2].as<float>()};
+    if (k == 5) hipLaunchKernelGGL(k_gicp_normals<5>, grid, block, lds, c->stream, bv, n, depth, o[0], o[1], o[2]);
+    else if (k == 10) hipLaunchKernelGGL(k_gicp_normals<10>, grid, block, lds, c->stream, bv, n, depth, o[0], o[1], o[2]);
+    else hipLaunchKernelGGL(k_gicp_normals<20>, grid, block, lds, c->stream, bv, n, depth, o[0], o[1], o[2]);
+    HIPCK(c, hipGetLastError());
+    c->gicp_ready[which] = true;
+    return ICP_OK;
+}
+// Loop start with metric = GICP (run_loop, icp_correspond): the unsupported forms refused, both clouds' GICP normals current.
+int gicp_prepare(icp_ctx* c) {
+    if (c->prm.metric != ICP_METRIC_GICP) return ICP_OK;
+    if (c->prm.matching != ICP_MATCH_KNN) { c->err = "GICP needs k-NN matching (projective matching is not supported)"; return ICP_ERR_INVALID_ARG; }
+    if (c->lm_on) { c->err = "GICP is not supported by the non-linear optimiser"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = gicp_normals(c, 0))) return rc;
+    return gicp_normals(c, 1);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1022,6 +1087,8 @@ int icp_ctx_destroy(icp_ctx* c) {
     for (auto& kv : c->levels) release(kv.second);
     release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->pring); release(c->totals); release(c->dbg_steps); release(c->sums); release(c->gx_slots); release(c->gx_hdr);
     release(c->lm_state); release(c->lm_partials); release(c->lm_sums);
+    for (auto& pl : c->gicp_n) for (DevBuf& d : pl) release(d);
+    release(c->gicp_flag);
     for (DevBuf* d : {&c->ms_ps, &c->ms_nn, &c->ms_st, &c->ms_st2, &c->ms_rec, &c->ms_d2, &c->ms_partials, &c->ms_totals, &c->ms_stats, &c->ms_score, &c->ms_res}) release(*d);
     release(c->stats); release(c->staging); release(c->rmse_partials); release(c->rmse_out); release(c->fontana_partials);
     for (DevBuf* d : {&c->src_flag, &c->src_box, &c->tgt_flag, &c->tgt_finite, &c->nrm_finite, &c->sel_temp, &c->d_count}) release(*d);
@@ -1050,7 +1117,7 @@ const char* icp_last_error(const icp_ctx* c) { return c ? c->err.c_str() : "null
 
 int icp_set_params(icp_ctx* c, const icp_params* p) {
     if (!c || !p) return ICP_ERR_INVALID_ARG;
-    if (p->metric < 0 || p->metric > 2 || p->matching < 0 || p->matching > 1 || p->weighting < 0 || p->weighting > 3 || p->n_iterations < 0 || p->selection < 0 || p->selection > 1 ||
+    if (p->metric < 0 || p->metric > 3 || p->matching < 0 || p->matching > 1 || p->weighting < 0 || p->weighting > 3 || p->n_iterations < 0 || p->selection < 0 || p->selection > 1 ||
         (p->knn_backend != ICP_KNN_BRUTE_FORCE && p->knn_backend != ICP_KNN_LBVH) || p->width < 0 || p->height < 0 || (long long)p->width * p->height > 0x7FFFFFFFll ||
         std::isnan(p->max_distance) || std::isnan(p->selection_proba) || !std::isfinite(p->fx) || !std::isfinite(p->fy) || !std::isfinite(p->cx) || !std::isfinite(p->cy)) {
         c->err = "icp_set_params: value out of range"; return ICP_ERR_INVALID_ARG;
@@ -1148,6 +1215,7 @@ int icp_correspond(icp_ctx* c, const float pose[16], icp_match_t* out, double* s
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if ((rc = check_ready(c, true, true))) return rc;
+    if ((rc = gicp_prepare(c))) return rc;
     if ((rc = write_pose(c, pose))) return rc;
     const int* full_order = nullptr;
     if ((rc = get_full_order(c, &full_order))) return rc;
@@ -1173,6 +1241,7 @@ int icp_correspond(icp_ctx* c, const float pose[16], icp_match_t* out, double* s
 int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_t* out, float* d2_out) {
     if (!c || !poses || n_poses <= 0) { if (c) c->err = "icp_match_seeded: bad argument"; return ICP_ERR_INVALID_ARG; }
     const icp_params& p = c->prm;
+    if (p.metric == ICP_METRIC_GICP) { c->err = "icp_match_seeded: GICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
     if (p.matching != ICP_MATCH_KNN || p.knn_backend != ICP_KNN_LBVH || p.metric == ICP_METRIC_SYMMETRIC || !c->fuse_post) {
         c->err = "icp_match_seeded: needs k-NN matching on the LBVH backend with the fused point-to-point / point-to-plane matcher"; return ICP_ERR_INVALID_ARG;
     }
@@ -1360,6 +1429,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if ((rc = check_ready(c, true, true))) return rc;
+    if ((rc = gicp_prepare(c))) return rc;
     std::vector<int> factors;          // decimation factor per iteration; 0 = no selection (full cloud)
     if (single) factors.push_back(0);
     else {
@@ -1684,6 +1754,44 @@ int icp_get_lm_summaries(const icp_ctx* c, icp_lm_summary* out, int32_t max, int
     return ICP_OK;
 }
 
+int icp_gicp_options_default(icp_gicp_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    o->epsilon = 1e-3f; o->covariance_k = 20;
+    return ICP_OK;
+}
+int icp_set_gicp_options(icp_ctx* c, const icp_gicp_options* o) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    icp_gicp_options v;
+    if (o) v = *o; else icp_gicp_options_default(&v);
+    const int k = v.covariance_k;
+    if (!(v.epsilon > 0.f && v.epsilon <= 1.f) || !(k == 0 || k == 5 || k == 10 || k == 20)) {
+        c->err = "icp_set_gicp_options: need 0 < epsilon <= 1 and covariance_k in {0, 5, 10, 20}"; return ICP_ERR_INVALID_ARG;
+    }
+    c->gicp_opt = v;
+    c->gicp_ready[0] = c->gicp_ready[1] = false;
+    return ICP_OK;
+}
+int icp_get_gicp_options(const icp_ctx* c, icp_gicp_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->gicp_opt; return ICP_OK; }
+int icp_get_gicp_normals(icp_ctx* c, int32_t which, float* out, int32_t max_points, int32_t* n_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if ((which != 0 && which != 1) || max_points < 0 || (!out && max_points > 0)) { c->err = "icp_get_gicp_normals: bad argument (which 0 or 1, max_points >= 0)"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const Cloud& cl = which ? c->src : c->tgt;
+    if (cl.n <= 0) { c->err = which ? "no source cloud (icp_set_source)" : "no target cloud (icp_set_target)"; return which ? ICP_ERR_NO_SOURCE : ICP_ERR_NO_TARGET; }
+    if ((rc = gicp_normals(c, which))) return rc;
+    const int n = cl.n, m = max_points < n ? max_points : n;
+    const bool own = c->gicp_opt.covariance_k == 0;
+    const DevBuf* pl[3] = {own ? &cl.nx : &c->gicp_n[which][0], own ? &cl.ny : &c->gicp_n[which][1], own ? &cl.nz : &c->gicp_n[which][2]};
+    std::vector<float> h((size_t)m * 3);
+    for (int q = 0; q < 3 && m > 0; q++) HIPCK(c, hipMemcpyAsync(h.data() + (size_t)q * m, pl[q]->p, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < m; i++) for (int q = 0; q < 3; q++) out[(size_t)i * 3 + q] = h[(size_t)q * m + i];
+    if (n_out) *n_out = n;
+    return guard.done();
+}
+
 int icp_iterate(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats) {
     if (!c || !pose_inout) { if (c) c->err = "icp_iterate: bad argument"; return ICP_ERR_INVALID_ARG; }
     int32_t n = 0;
@@ -1710,6 +1818,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
     if (p.knn_backend != ICP_KNN_LBVH) { c->err = "icp_run_multistart: the brute-force k-NN backend is not supported"; return ICP_ERR_INVALID_ARG; }
     if (p.record_rmse != 0) { c->err = "icp_run_multistart: record_rmse is not supported"; return ICP_ERR_INVALID_ARG; }
     if (c->lm_on) { c->err = "icp_run_multistart: the non-linear optimiser is not supported"; return ICP_ERR_INVALID_ARG; }
+    if (c->prm.metric == ICP_METRIC_GICP) { c->err = "icp_run_multistart: GICP is not supported"; return ICP_ERR_INVALID_ARG; }
     int rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;

@@ -88,6 +88,12 @@ class IcpLmSummary(C.Structure):
 
 LM_CONVERGENCE, LM_NO_CONVERGENCE, LM_FAILURE, LM_NO_RESIDUALS = 0, 1, 2, 3
 
+METRIC_POINT_TO_POINT, METRIC_POINT_TO_PLANE, METRIC_SYMMETRIC, METRIC_GICP = 0, 1, 2, 3
+
+
+class IcpGicpOptions(C.Structure):
+    _fields_ = [("epsilon", C.c_float), ("covariance_k", C.c_int32)]
+
 
 def lm_options(**kw):
     """icp_lm_options: Ceres' defaults with configureSolver's max_num_iterations = 10 (icp_lm_options_default), fields overridden by name."""
@@ -147,6 +153,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_transform_points", "icp_transform_normals", "icp_version", "icp_schedule", "icp_select_hash", "icp_backproject_depth", "icp_estimate_normals",
            "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames", "icp_depth_mesh",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
+           "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
 
@@ -263,6 +270,26 @@ class Context:
                      accepted_steps_mask=b.accepted_steps_mask, invalid_steps_mask=b.invalid_steps_mask,
                      initial_cost=b.initial_cost, final_cost=b.final_cost, trust_region_radius=b.trust_region_radius, x=np.array(b.x[:], np.float64))
                 for b in buf[:n.value]]
+
+    def set_gicp_options(self, epsilon=1e-3, k=20):
+        """icp_set_gicp_options: the plane-to-plane regulariser and the neighbours of the GICP normals (0: the clouds' own normals)."""
+        o = IcpGicpOptions(float(epsilon), int(k))
+        self._ck(self.lib.icp_set_gicp_options(self.h, C.byref(o)))
+        return o
+
+    def gicp_options(self):
+        o = IcpGicpOptions()
+        self._ck(self.lib.icp_get_gicp_options(self.h, C.byref(o)))
+        return o
+
+    def gicp_normals(self, which="target"):
+        """icp_get_gicp_normals: the per-point GICP normals of the target or the source, n x 3 fp32 in the cloud's order (NaN where undefined)."""
+        w = {"target": 0, "source": 1}[which]
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_get_gicp_normals(self.h, C.c_int32(w), None, C.c_int32(0), C.byref(n)))
+        out = np.empty((n.value, 3), np.float32)
+        self._ck(self.lib.icp_get_gicp_normals(self.h, C.c_int32(w), _ptr(out), C.c_int32(n.value), C.byref(n)))
+        return out
 
     def push_params(self):
         self._ck(self.lib.icp_set_params(self.h, C.byref(self.params)))
@@ -561,6 +588,7 @@ class LinearICPOptimizer:
     def setMatchingMethod(self, m): self.ctx.params.matching = m                               # :71-78
     def setNbOfIterations(self, n): self.ctx.params.n_iterations = n                           # :84-86
     def setKnnBackend(self, b): self.ctx.params.knn_backend = b
+    def setGICPOptions(self, epsilon=1e-3, k=20): self.ctx.set_gicp_options(epsilon, k)         # setMetric(METRIC_GICP) selects it
 
     def setSelectionMethod(self, method, proba=1.0, seed=0):                                   # :58-61 (+ explicit seed)
         self.ctx.params.selection = int(method); self.ctx.params.selection_proba = float(proba); self.ctx.params.selection_seed = int(seed)

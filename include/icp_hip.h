@@ -47,14 +47,15 @@ enum icp_status {
 };
 
 /* enum values mirror the reference */
-enum { ICP_METRIC_POINT_TO_POINT = 0, ICP_METRIC_POINT_TO_PLANE = 1, ICP_METRIC_SYMMETRIC = 2 };   /* ICPOptimizer.h:46-48,131-136 */
+enum { ICP_METRIC_POINT_TO_POINT = 0, ICP_METRIC_POINT_TO_PLANE = 1, ICP_METRIC_SYMMETRIC = 2,   /* ICPOptimizer.h:46-48,131-136 */
+       ICP_METRIC_GICP = 3 };        /* extension: Generalized-ICP, plane-to-plane (Segal, Haehnel, Thrun 2009); see icp_gicp_options */
 enum { ICP_MATCH_KNN = 0, ICP_MATCH_PROJECTIVE = 1 };                                               /* ICPOptimizer.h:71-78 */
 enum { ICP_WEIGHT_CONSTANT = 0, ICP_WEIGHT_DISTANCES = 1, ICP_WEIGHT_NORMALS = 2, ICP_WEIGHT_COLORS = 3 };   /* weighting.h:8 */
 enum { ICP_KNN_BRUTE_FORCE = 0, ICP_KNN_LBVH = 1 };   /* both exact: identical (d2, lowest-index) argmin, bit for bit */
 
 /* The setter surface of ICPOptimizer (ICPOptimizer.h:41-95) as one POD. */
 typedef struct icp_params {
-    int32_t metric;          /* setMetric                     default 0           */
+    int32_t metric;          /* setMetric                     default 0 (ICP_METRIC_*; 3 = GICP, an extension) */
     int32_t matching;        /* setMatchingMethod             default 0 (k-NN)    */
     int32_t weighting;       /* setWeightingMethod            default 0           */
     int32_t rejection;       /* setRejectionMethod            default 1 (60 deg)  */
@@ -229,6 +230,35 @@ int icp_lm_options_default(icp_lm_options* opt);
 int icp_set_optimizer(icp_ctx* ctx, const icp_lm_options* opt);
 /* The records of the last run through the non-linear optimiser: out[0 .. min(max, count)), *count = ICP iterations of that run. */
 int icp_get_lm_summaries(const icp_ctx* ctx, icp_lm_summary* out, int32_t max, int32_t* count);
+
+/* -------- Generalized-ICP, plane-to-plane (extension: the reference has no counterpart), params.metric = ICP_METRIC_GICP --------
+ * Every point carries the covariance C = I - (1 - epsilon) n n^T of a plane with unit normal n (= V diag(epsilon, 1, 1) V^T).
+ * GICP normal of a point, computed once per cloud on the full-resolution cloud and cached (every call that replaces a cloud, and
+ * icp_set_gicp_options, drops the cache; multires levels and random samples read the normal of their original point):
+ *   covariance_k = k > 0: the k smallest (fp32 d^2, index) pairs over the cloud's finite points (the point itself included), fp64 mean
+ *     and covariance, fp64 Jacobi; the eigenvector of the smallest eigenvalue rounded once to fp32, no viewpoint flip.  A non-finite
+ *     point, or a cloud with fewer than 3 finite points: NaN; fewer than k finite points: all of them; zero covariance: (1, 0, 0).
+ *   covariance_k = 0: the cloud's own normals (the loop returns ICP_ERR_INVALID_ARG for a cloud without them).
+ * One correspondence (the record after weighting and rejection, as icp_correspond returns it): p = the fp32 transformed source point
+ * (icp_transform_points), q = the fp32 target point, r = q - p in fp64; a = the target's GICP normal, b = the source's moved by the pose
+ * in fp32 (icp_transform_normals), both normalised in fp64; Sigma = 2I - (1 - epsilon)(a a^T + b b^T) = C_t + R C_s R^T, M = Sigma^-1
+ * (adjugate / determinant, fp64); J = [ -[p]x | I ] (x = (alpha, beta, gamma, tx, ty, tz), the point-to-plane linearisation).  The pair
+ * enters when the validity filter passes and a, b are finite with non-zero norm: H += w^2 J^T M J, g += w^2 J^T M r, in the sums
+ * icp_correspond returns ([0] n, [1..3] sum s, [4..6] sum d, [7..27] upper triangle of H row-major, [28..33] g; fixed-order fp64).
+ * Solve: H x = g as point-to-plane's (LDL^T, eigen fallback), then the point-to-plane composition Rx Ry Rz, dT * pose in fp32.
+ * Supported: k-NN matching (both backends, 3-D and colour), every weighting, rejection, multires, selection, record_rmse, icp_iterate,
+ * icp_run, icp_correspond, icp_batch_run, icp_track_depth_frames.  ICP_ERR_INVALID_ARG at loop start (see icp_last_error): projective
+ * matching, the non-linear optimiser, icp_run_multistart, icp_match_seeded. */
+typedef struct icp_gicp_options {
+    float   epsilon;        /* plane-to-plane regulariser, default 1e-3, 0 < epsilon <= 1 */
+    int32_t covariance_k;   /* 20 (default): n from the k-NN PCA of the cloud; 0: n = the cloud's own normals; allowed {0, 5, 10, 20} */
+} icp_gicp_options;
+int icp_gicp_options_default(icp_gicp_options* opt);
+int icp_set_gicp_options(icp_ctx* ctx, const icp_gicp_options* opt);   /* NULL = defaults */
+int icp_get_gicp_options(const icp_ctx* ctx, icp_gicp_options* opt);
+/* The per-point GICP normals the loop uses, original point order, n x 3 floats (NaN where undefined); computed on demand.
+   which: 0 target, 1 source.  out[0 .. min(n, max_points)) is written, *n_out (optional) = n. */
+int icp_get_gicp_normals(icp_ctx* ctx, int32_t which, float* out, int32_t max_points, int32_t* n_out);
 
 /* -------- ConvergenceMeasure (ConvergenceMeasure.h:30-66): known-correspondence RMSE --------
  * src_xyz[i] (moved by the estimated pose) is compared with ref_xyz[i]. */

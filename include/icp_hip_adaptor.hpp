@@ -209,6 +209,13 @@ public:
     {
         m_cam[0] = K(0, 0); m_cam[1] = K(1, 1); m_cam[2] = K(0, 2); m_cam[3] = K(1, 2); m_camW = width; m_camH = height; m_hasCamera = true;
     }
+    // Generalized-ICP (setMetric(ICP_METRIC_GICP), an extension): plane-to-plane regulariser and neighbours of the GICP normals (0: the
+    // clouds' own normals); icp_set_gicp_options.  Returns its status (ICP_ERR_INVALID_ARG: epsilon outside (0, 1] or k not in {0, 5, 10, 20}).
+    int setGICPOptions(float epsilon, unsigned k) {
+        if (!context()) return ICP_ERR_NO_DEVICE;
+        icp_gicp_options o; o.epsilon = epsilon; o.covariance_k = (int32_t)k;
+        return icp_set_gicp_options(context(), &o);
+    }
     // LinearICPOptimizer::estimatePose, ICPOptimizer.h:493-663
     void estimatePose(const PointCloud& source, const PointCloud& target, Matrix4f& initialPose, bool calculateRMSE = true) override {
         icp_params p; icp_params_default(&p);
