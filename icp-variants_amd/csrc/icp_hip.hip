@@ -101,6 +101,9 @@ struct icp_ctx {
     icp_gicp_options gicp_opt = {1e-3f, 20};     // icp_set_gicp_options
     DevBuf gicp_n[2][3], gicp_flag;              // GICP normals of the target [0] / source [1] (SoA, original order), finite flags of their scratch tree
     bool gicp_ready[2] = {false, false};         // the cache is current (dropped by every call that replaces the cloud and by new options)
+    icp_robust_options rob_opt = {ICP_ROBUST_NONE, 0.f, 0.f, 1.f};   // icp_set_robust_options
+    DevBuf rob_keys, rob_state, rob_stats;      // trimmed / robust mode (dev_robust.hpp): r^2 keys per query, the chain's state, per-iteration records
+    std::vector<icp_robust_stats> rob_last;      // the records of the last call (icp_get_robust_stats)
     icp_params prm;
     Cloud tgt, src, qry;                 // qry: scratch cloud of icp_query_matches
     Cloud nrm_cloud; Bvh nrm_bvh;        // scratch of icp_estimate_normals
@@ -648,15 +651,55 @@ GicpPost gicp_post_params(icp_ctx* c, const Cloud& src) {
     return g;
 }
 
-// Enqueue weight + reject + accumulate (+ symmetric second pass) + reduce/solve (no sync).
+// Trimmed / robust mode (icp_robust_options, dev_robust.hpp) is on: anything but kernel NONE with overlap 1.
+bool robust_on(const icp_ctx* c) { return c->rob_opt.kernel != ICP_ROBUST_NONE || c->rob_opt.overlap < 1.f; }
+
+// Loop start with robust mode on (run_loop, icp_correspond): the chain's state and `slots` per-iteration records allocated, the histograms
+// cleared (k_robust_finish leaves them cleared; this covers a first use and a call cut short), the key buffer sized for the whole source.
+int robust_prepare(icp_ctx* c, int slots) {
+    int rc;
+    if ((rc = ensure(c, c->rob_state, sizeof(RobustState)))) return rc;
+    if ((rc = ensure(c, c->rob_stats, (size_t)(slots > 0 ? slots : 1) * sizeof(icp_robust_stats)))) return rc;
+    if ((rc = ensure(c, c->rob_keys, (size_t)(c->src.n > 0 ? c->src.n : 1) * 4))) return rc;      // (no iteration queries more points)
+    HIPCK(c, hipMemsetAsync(c->rob_state.p, 0, sizeof(RobustState), c->stream));
+    return ICP_OK;
+}
+
+// The robust chain over the records the matcher left (no sync): keys + first histogram, two select passes, the one-block finish, trim and
+// reweight.  The post kernels behind it get the records as they are (weighting CONSTANT, no rejection): see launch_post_and_solve.
+int launch_robust(icp_ctx* c, const PostParams& pp, int n, icp_robust_stats* d_rstats) {
+    int rc;
+    if ((rc = ensure(c, c->rob_keys, (size_t)(n > 0 ? n : 1) * 4))) return rc;
+    static const float standard[4] = {0.f, 1.345f, 2.3849f, 4.6851f};
+    const icp_robust_options& o = c->rob_opt;
+    RobustParams rp;
+    rp.st = c->rob_state.as<RobustState>(); rp.keys = c->rob_keys.as<unsigned int>(); rp.stats = d_rstats;
+    rp.kernel = o.kernel; rp.linear_weight = c->prm.metric == ICP_METRIC_POINT_TO_POINT ? 1 : 0;
+    rp.tuning = o.tuning > 0.f ? o.tuning : standard[o.kernel]; rp.sigma = o.sigma; rp.overlap = o.overlap; rp.n = n;
+    int nb = (n + ROBUST_THREADS - 1) / ROBUST_THREADS; if (nb > ROBUST_BLOCKS) nb = ROBUST_BLOCKS; if (nb < 1) nb = 1;
+    hipLaunchKernelGGL(k_robust_eval, dim3(nb), dim3(ROBUST_THREADS), 0, c->stream, pp, rp);
+    hipLaunchKernelGGL(k_robust_select<1>, dim3(nb), dim3(ROBUST_THREADS), 0, c->stream, rp);
+    hipLaunchKernelGGL(k_robust_select<2>, dim3(nb), dim3(ROBUST_THREADS), 0, c->stream, rp);
+    hipLaunchKernelGGL(k_robust_finish, dim3(1), dim3(ROBUST_THREADS), 0, c->stream, rp);
+    hipLaunchKernelGGL(k_robust_apply, dim3(nb), dim3(ROBUST_THREADS), 0, c->stream, pp, rp);
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+
+// Enqueue weight + reject + accumulate (+ symmetric second pass) + reduce/solve (no sync).  Robust mode (d_rstats: the iteration's record,
+// robust_prepare has run): the robust chain first, then the post kernels on its final records.
 int launch_post_and_solve(icp_ctx* c, const Cloud& src, const int* sel, int n, icp_iter_stats* d_stats, double* d_sums_out, int update_pose,
-                          hipEvent_t ev_after_post, int fused_blocks = 0) {
+                          hipEvent_t ev_after_post, int fused_blocks = 0, icp_robust_stats* d_rstats = nullptr) {
     const icp_params& p = c->prm;
     int rc;
     if (!fused_blocks && (rc = ensure(c, c->partials, (size_t)POST_BLOCKS * NSUM * 8))) return rc;
     if (!c->totals.p && (rc = rearm_handover(c))) return rc;      // (the entry points re-arm before their first launch; this covers a first use)
-    const PostParams pp = make_post_params(c, src, sel, n);
+    PostParams pp = make_post_params(c, src, sel, n);
     int nb = (n + POST_THREADS - 1) / POST_THREADS; if (nb > POST_BLOCKS) nb = POST_BLOCKS; if (nb < 1) nb = 1;
+    if (d_rstats && !fused_blocks) {
+        if ((rc = launch_robust(c, pp, n, d_rstats))) return rc;
+        pp.weighting = ICP_WEIGHT_CONSTANT; pp.rejection = 0;      // post_eval takes each final weight as it is, re-applies only the validity filter
+    }
     if (fused_blocks) nb = fused_blocks;                    // the matcher already wrote the block partials
     else if (p.metric == ICP_METRIC_GICP) hipLaunchKernelGGL(k_post_gicp, dim3(nb), dim3(POST_THREADS), 0, c->stream, pp, gicp_post_params(c, src));
     else hipLaunchKernelGGL(k_post, dim3(nb), dim3(POST_THREADS), 0, c->stream, pp);
@@ -1089,6 +1132,7 @@ int icp_ctx_destroy(icp_ctx* c) {
     release(c->lm_state); release(c->lm_partials); release(c->lm_sums);
     for (auto& pl : c->gicp_n) for (DevBuf& d : pl) release(d);
     release(c->gicp_flag);
+    release(c->rob_keys); release(c->rob_state); release(c->rob_stats);
     for (DevBuf* d : {&c->ms_ps, &c->ms_nn, &c->ms_st, &c->ms_st2, &c->ms_rec, &c->ms_d2, &c->ms_partials, &c->ms_totals, &c->ms_stats, &c->ms_score, &c->ms_res}) release(*d);
     release(c->stats); release(c->staging); release(c->rmse_partials); release(c->rmse_out); release(c->fontana_partials);
     for (DevBuf* d : {&c->src_flag, &c->src_box, &c->tgt_flag, &c->tgt_finite, &c->nrm_finite, &c->sel_temp, &c->d_count}) release(*d);
@@ -1216,6 +1260,9 @@ int icp_correspond(icp_ctx* c, const float pose[16], icp_match_t* out, double* s
     if ((rc = set_device(c))) return rc;
     if ((rc = check_ready(c, true, true))) return rc;
     if ((rc = gicp_prepare(c))) return rc;
+    const bool robust = robust_on(c);
+    c->rob_last.clear();
+    if (robust && (rc = robust_prepare(c, 1))) return rc;
     if ((rc = write_pose(c, pose))) return rc;
     const int* full_order = nullptr;
     if ((rc = get_full_order(c, &full_order))) return rc;
@@ -1223,12 +1270,15 @@ int icp_correspond(icp_ctx* c, const float pose[16], icp_match_t* out, double* s
     if ((rc = launch_match(c, q))) return rc;
     if ((rc = ensure(c, c->sums, NSUM * 8))) return rc;
     if ((rc = rearm_handover(c))) return rc;
-    if ((rc = launch_post_and_solve(c, c->src, nullptr, q.n, nullptr, c->sums.as<double>(), 0, nullptr))) return rc;
+    if ((rc = launch_post_and_solve(c, c->src, nullptr, q.n, nullptr, c->sums.as<double>(), 0, nullptr, 0, robust ? c->rob_stats.as<icp_robust_stats>() : nullptr))) return rc;
     double hs[NSUM]; int fault = 0;
+    icp_robust_stats rs;
     if (out) HIPCK(c, hipMemcpyAsync(out, c->matches.p, (size_t)q.n * sizeof(icp_match_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(hs, c->sums.p, NSUM * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(&fault, &c->ps.as<PoseState>()->fault, 4, hipMemcpyDeviceToHost, c->stream));
+    if (robust) HIPCK(c, hipMemcpyAsync(&rs, c->rob_stats.p, sizeof(rs), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    if (robust) c->rob_last.assign(1, rs);
     if (fault) { c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
     if (sums_out) { memset(sums_out, 0, 64 * 8); memcpy(sums_out, hs, NSUM * 8); }
     if (n_valid_out) *n_valid_out = (int32_t)hs[SUM_N];
@@ -1242,6 +1292,7 @@ int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_
     if (!c || !poses || n_poses <= 0) { if (c) c->err = "icp_match_seeded: bad argument"; return ICP_ERR_INVALID_ARG; }
     const icp_params& p = c->prm;
     if (p.metric == ICP_METRIC_GICP) { c->err = "icp_match_seeded: GICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
+    if (robust_on(c)) { c->err = "icp_match_seeded: robust mode (icp_set_robust_options) has no fused matcher"; return ICP_ERR_INVALID_ARG; }
     if (p.matching != ICP_MATCH_KNN || p.knn_backend != ICP_KNN_LBVH || p.metric == ICP_METRIC_SYMMETRIC || !c->fuse_post) {
         c->err = "icp_match_seeded: needs k-NN matching on the LBVH backend with the fused point-to-point / point-to-plane matcher"; return ICP_ERR_INVALID_ARG;
     }
@@ -1442,7 +1493,12 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     if (n_run) *n_run = 0;
     const bool lm = c->lm_on;             // the non-linear optimiser: the generic per-iteration form, its records kept for k_lm_eval
     c->lm_last.clear();
+    // trimmed / robust mode: the generic per-iteration form (stand-alone matcher, robust chain, post, reduce / solve), as GICP runs
+    const bool robust = robust_on(c);
+    c->rob_last.clear();
+    if (robust && lm) { c->err = "the non-linear optimiser does not support robust mode (icp_set_robust_options)"; return ICP_ERR_INVALID_ARG; }
     if (iters == 0) return guard.done();
+    if (robust && (rc = robust_prepare(c, iters))) return rc;
     // page-locked staging for the whole run up front: [pose state up | per-iteration records down | pose state down]
     const size_t pin_stats = 256, pin_pose = pin_stats + (((size_t)iters * sizeof(icp_iter_stats) + 255) & ~(size_t)255);
     const size_t pin_lm = (pin_pose + 512 + (size_t)(iters + 1) * 8 + 255) & ~(size_t)255;      // [LM records down] behind it, non-linear runs only
@@ -1468,7 +1524,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     // The merged loop (dev_solve.hpp, "the ring form"): point-to-plane through the fused BVH matcher on sorted levels, nothing else on
     // the stream between two iterations.  Launch i = [reducer of iteration i - 1 | matcher of iteration i]; one reducer-only launch closes
     // the run.  Pose slots and totals rows are written once per run; both rings are reset here, so nothing survives an aborted run.
-    bool merged = !lm && c->merge_loop && !single && iters >= 2 && sorted_levels && c->fuse_post && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
+    bool merged = !lm && !robust && c->merge_loop && !single && iters >= 2 && sorted_levels && c->fuse_post && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
     for (int i = 0; merged && i < iters; i++) if (ns[i] <= 0) merged = false;
     PoseState* slots = nullptr; unsigned long long* trows = nullptr; int* run_fault = nullptr;
     // k_icp_loop (dev_persist.hpp): all iterations of a resolution level in ONE launch, the waves resident from iteration to iteration.
@@ -1581,7 +1637,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
             MergeLaunch ml;
             if (merged) { ml.rp = ring_params(i); ml.slot = loop_slot(slots, i, 0); ml.partials = (i & 1) ? c->partials2.as<double>() : c->partials.as<double>(); }
             if (ext_ev) { ml.ev_start = E(i, 0); ml.ev_stop = E(i, 1); }
-            if ((rc = launch_match(c, q, c->fuse_post ? &fused : nullptr, merged ? &ml : nullptr))) return rc;
+            if ((rc = launch_match(c, q, (c->fuse_post && !robust) ? &fused : nullptr, merged ? &ml : nullptr))) return rc;
             if (merged && !fused) { c->err = "merged loop: the matcher did not take the fused path"; return ICP_ERR_HIP; }
             if (ev && !ext_ev) HIPCK(c, hipEventRecord(E(i, 1), c->stream));
             // fused epilogue: there is no separate post stage to bracket
@@ -1589,7 +1645,8 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
                 if ((rc = launch_post_and_lm(c, *clouds[i], sels[i], ns[i], d_st, c->lm_sums.as<icp_lm_summary>() + i, (ev && !fused) ? E(i, 2) : nullptr, fused))) return rc;
                 post_event[i] = ev && !fused;
             } else if (!merged) {
-                if ((rc = launch_post_and_solve(c, *clouds[i], sels[i], ns[i], d_st, nullptr, 1, (ev && !fused) ? E(i, 2) : nullptr, fused))) return rc;
+                if ((rc = launch_post_and_solve(c, *clouds[i], sels[i], ns[i], d_st, nullptr, 1, (ev && !fused) ? E(i, 2) : nullptr, fused,
+                                                robust ? c->rob_stats.as<icp_robust_stats>() + i : nullptr))) return rc;
                 post_event[i] = ev && !fused;
             }
         } else if (ev) {
@@ -1645,7 +1702,11 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
         HIPCK(c, hipMemcpyAsync((char*)c->pinned + pin_pose, c->ps.p, sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));
         if (lm) HIPCK(c, hipMemcpyAsync((char*)c->pinned + pin_lm, c->lm_sums.p, (size_t)iters * sizeof(icp_lm_summary), hipMemcpyDeviceToHost, c->stream));
     }
+    std::vector<icp_robust_stats> rob((size_t)(robust ? iters : 0));
+    if (robust) HIPCK(c, hipMemcpyAsync(rob.data(), c->rob_stats.p, (size_t)iters * sizeof(icp_robust_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; robust && i < iters; i++) if (ns[i] <= 0) rob[(size_t)i] = icp_robust_stats{0, 0, -1.f, -1.f};      // (no work: nothing was written)
+    c->rob_last.swap(rob);
     if (merged) {
         if (persist) c->loop_runs++; else c->merged_runs++;
         const PoseState* hp = (const PoseState*)((char*)c->pinned + pin_pose);
@@ -1792,6 +1853,30 @@ int icp_get_gicp_normals(icp_ctx* c, int32_t which, float* out, int32_t max_poin
     return guard.done();
 }
 
+int icp_robust_options_default(icp_robust_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    o->kernel = ICP_ROBUST_NONE; o->tuning = 0.f; o->sigma = 0.f; o->overlap = 1.f;
+    return ICP_OK;
+}
+int icp_set_robust_options(icp_ctx* c, const icp_robust_options* o) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    icp_robust_options v;
+    if (o) v = *o; else icp_robust_options_default(&v);
+    if (v.kernel < ICP_ROBUST_NONE || v.kernel > ICP_ROBUST_TUKEY) { c->err = "icp_set_robust_options: kernel must be one of ICP_ROBUST_NONE / HUBER / CAUCHY / TUKEY (0..3)"; return ICP_ERR_INVALID_ARG; }
+    if (!(std::isfinite(v.tuning) && v.tuning >= 0.f) || !(std::isfinite(v.sigma) && v.sigma >= 0.f)) { c->err = "icp_set_robust_options: tuning and sigma must be finite and >= 0"; return ICP_ERR_INVALID_ARG; }
+    if (!(v.overlap > 0.f && v.overlap <= 1.f)) { c->err = "icp_set_robust_options: need 0 < overlap <= 1"; return ICP_ERR_INVALID_ARG; }
+    c->rob_opt = v;
+    return ICP_OK;
+}
+int icp_get_robust_options(const icp_ctx* c, icp_robust_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->rob_opt; return ICP_OK; }
+int icp_get_robust_stats(const icp_ctx* c, icp_robust_stats* out, int32_t max_out, int32_t* count_out) {
+    if (!c || max_out < 0 || (!out && max_out > 0)) return ICP_ERR_INVALID_ARG;
+    const int32_t n = (int32_t)c->rob_last.size();
+    for (int32_t i = 0; i < n && i < max_out; i++) out[i] = c->rob_last[(size_t)i];
+    if (count_out) *count_out = n;
+    return ICP_OK;
+}
+
 int icp_iterate(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats) {
     if (!c || !pose_inout) { if (c) c->err = "icp_iterate: bad argument"; return ICP_ERR_INVALID_ARG; }
     int32_t n = 0;
@@ -1819,6 +1904,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
     if (p.record_rmse != 0) { c->err = "icp_run_multistart: record_rmse is not supported"; return ICP_ERR_INVALID_ARG; }
     if (c->lm_on) { c->err = "icp_run_multistart: the non-linear optimiser is not supported"; return ICP_ERR_INVALID_ARG; }
     if (c->prm.metric == ICP_METRIC_GICP) { c->err = "icp_run_multistart: GICP is not supported"; return ICP_ERR_INVALID_ARG; }
+    if (robust_on(c)) { c->err = "icp_run_multistart: robust mode (icp_set_robust_options) is not supported"; return ICP_ERR_INVALID_ARG; }
     int rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;

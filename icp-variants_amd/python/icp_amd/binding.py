@@ -124,6 +124,18 @@ def depth_camera(K, width, height, extrinsics=None):
     return cam
 
 
+class IcpRobustOptions(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("tuning", C.c_float), ("sigma", C.c_float), ("overlap", C.c_float)]
+
+
+class IcpRobustStats(C.Structure):
+    _fields_ = [("n_entering", C.c_int32), ("n_kept", C.c_int32), ("trim_d2", C.c_float), ("sigma", C.c_float)]
+
+
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY = 0, 1, 2, 3
+ROBUST_KERNELS = {"none": ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY, "tukey": ROBUST_TUKEY}
+
+
 class IcpColorCamera(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_int32), ("height", C.c_int32),
                 ("extrinsics", C.c_float * 16)]
@@ -154,6 +166,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames", "icp_depth_mesh",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
+           "icp_robust_options_default", "icp_set_robust_options", "icp_get_robust_options", "icp_get_robust_stats",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
 
@@ -290,6 +303,27 @@ class Context:
         out = np.empty((n.value, 3), np.float32)
         self._ck(self.lib.icp_get_gicp_normals(self.h, C.c_int32(w), _ptr(out), C.c_int32(n.value), C.byref(n)))
         return out
+
+    def set_robust_options(self, kernel="none", tuning=0.0, sigma=0.0, overlap=1.0):
+        """icp_set_robust_options: trimmed ICP (overlap < 1) and an M-estimator ("none", "huber", "cauchy", "tukey" or ICP_ROBUST_*) with
+        tuning constant c (0: the kernel's standard one) and scale sigma (0: adaptive, from the median residual)."""
+        k = ROBUST_KERNELS[kernel.lower()] if isinstance(kernel, str) else int(kernel)
+        o = IcpRobustOptions(k, float(tuning), float(sigma), float(overlap))
+        self._ck(self.lib.icp_set_robust_options(self.h, C.byref(o)))
+        return o
+
+    def robust_options(self):
+        o = IcpRobustOptions()
+        self._ck(self.lib.icp_get_robust_options(self.h, C.byref(o)))
+        return o
+
+    def robust_stats(self):
+        """icp_get_robust_stats: one dict per ICP iteration of the last icp_iterate / icp_run / icp_correspond (none when robust mode was off)."""
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_get_robust_stats(self.h, None, C.c_int32(0), C.byref(n)))
+        buf = (IcpRobustStats * max(n.value, 1))()
+        self._ck(self.lib.icp_get_robust_stats(self.h, buf, C.c_int32(n.value), C.byref(n)))
+        return [dict(n_entering=b.n_entering, n_kept=b.n_kept, trim_d2=b.trim_d2, sigma=b.sigma) for b in buf[:n.value]]
 
     def push_params(self):
         self._ck(self.lib.icp_set_params(self.h, C.byref(self.params)))
@@ -589,6 +623,7 @@ class LinearICPOptimizer:
     def setNbOfIterations(self, n): self.ctx.params.n_iterations = n                           # :84-86
     def setKnnBackend(self, b): self.ctx.params.knn_backend = b
     def setGICPOptions(self, epsilon=1e-3, k=20): self.ctx.set_gicp_options(epsilon, k)         # setMetric(METRIC_GICP) selects it
+    def setRobustOptions(self, kernel="none", tuning=0.0, sigma=0.0, overlap=1.0): self.ctx.set_robust_options(kernel, tuning, sigma, overlap)
 
     def setSelectionMethod(self, method, proba=1.0, seed=0):                                   # :58-61 (+ explicit seed)
         self.ctx.params.selection = int(method); self.ctx.params.selection_proba = float(proba); self.ctx.params.selection_seed = int(seed)

@@ -260,6 +260,47 @@ int icp_get_gicp_options(const icp_ctx* ctx, icp_gicp_options* opt);
    which: 0 target, 1 source.  out[0 .. min(n, max_points)) is written, *n_out (optional) = n. */
 int icp_get_gicp_normals(icp_ctx* ctx, int32_t which, float* out, int32_t max_points, int32_t* n_out);
 
+/* -------- Trimmed ICP and robust kernels (extension: the reference has no counterpart), per context --------
+ * Off (kernel = NONE and overlap = 1, the default): nothing changes, every loop form is chosen as without this call.
+ * On, per ICP iteration over that iteration's query set (multires level or random sample):
+ *   1. weighting, rejection and the validity filter as icp_correspond runs them give each record (idx, w) and the m pairs that enter;
+ *   2. r2 = ((e0*e0 + e1*e1) + e2*e2) in fp32, e = s - d (s: the transformed source point, d: the record's target xyz; for every metric
+ *      and matcher, colour ICP included); r2 may be +inf, never NaN; residuals are ordered by their uint32 bit pattern;
+ *   3. K = clamp(ceil((double)overlap * m), 1, m); t = the K-th smallest r2; a pair with r2 > t is trimmed: its record becomes {-1, w};
+ *      ties at t are kept, so M >= K;
+ *   4. sigma = (double)options.sigma when > 0, else 1.4826 * sqrt((double)med), med = the ceil(K/2)-th smallest r2;
+ *   5. per kept pair, fp64: u = sqrt((double)r2) / sigma, c = (double)tuning (the kernel's standard constant when 0), q = u / c;
+ *      HUBER rho = u <= c ? 1 : c / u;  CAUCHY rho = 1 / (1 + q*q);  TUKEY rho = u < c ? (1 - q*q)*(1 - q*q) : 0;  NONE rho = 1;
+ *      rho = 1 when sigma is 0 or +inf;
+ *   6. point-to-point: w' = (float)((double)w * rho); point-to-plane, symmetric, GICP (rows scaled by w): w' = (float)((double)w * sqrt(rho));
+ *   7. the metric's sums and solve as without robust mode, on these records: n_valid = the kept pairs that pass the validity filter
+ *      (GICP's own normal filter included); Tukey's rho = 0 pairs stay in with weight 0.
+ * m = 0: ICP_ERR_NO_CORRESPONDENCES as today.  Supported: k-NN (both backends, 3-D and colour) and projective matching, every metric,
+ * weighting, rejection, multires, selection, record_rmse; icp_iterate, icp_run, icp_correspond (its records and sums are the robust
+ * ones), icp_batch_run, icp_track_depth_frames.  ICP_ERR_INVALID_ARG while on: the non-linear optimiser (at loop start),
+ * icp_run_multistart, icp_match_seeded. */
+enum { ICP_ROBUST_NONE = 0, ICP_ROBUST_HUBER = 1, ICP_ROBUST_CAUCHY = 2, ICP_ROBUST_TUKEY = 3 };
+typedef struct icp_robust_options {
+    int32_t kernel;    /* ICP_ROBUST_*                                                                  default NONE */
+    float   tuning;    /* c; 0 = the kernel's standard constant (1.345 / 2.3849 / 4.6851, as fp32)     default 0 */
+    float   sigma;     /* > 0: fixed scale in metres; 0: adaptive, from the median                      default 0 */
+    float   overlap;   /* trim ratio xi, 0 < xi <= 1; 1 = no trimming                                   default 1 */
+} icp_robust_options;
+typedef struct icp_robust_stats {   /* one per ICP iteration of the last call */
+    int32_t n_entering;  /* m: pairs that passed weighting, rejection and the validity filter */
+    int32_t n_kept;      /* M: pairs kept after trimming (ties at the threshold kept, so M >= K) */
+    float   trim_d2;     /* t: the K-th smallest r^2 (-1 when m = 0) */
+    float   sigma;       /* the scale used, rounded to fp32; -1 when kernel == NONE or m = 0 */
+} icp_robust_stats;
+int icp_robust_options_default(icp_robust_options* opt);
+/* Validation: kernel in 0..3, tuning and sigma finite and >= 0, 0 < overlap <= 1; else ICP_ERR_INVALID_ARG (reason in icp_last_error). */
+int icp_set_robust_options(icp_ctx* ctx, const icp_robust_options* opt);   /* NULL = defaults */
+int icp_get_robust_options(const icp_ctx* ctx, icp_robust_options* opt);
+/* One record per iteration of the last icp_iterate, icp_run or icp_correspond call on the context (icp_track_depth_frames: the last
+ * tracked frame's run; icp_batch_run: each context's own last pair); none when robust mode was off for that call.  Iterations with no
+ * work: {0, 0, -1, -1}.  out[0 .. min(max_out, count)), *count_out = the number of records. */
+int icp_get_robust_stats(const icp_ctx* ctx, icp_robust_stats* out, int32_t max_out, int32_t* count_out);
+
 /* -------- ConvergenceMeasure (ConvergenceMeasure.h:30-66): known-correspondence RMSE --------
  * src_xyz[i] (moved by the estimated pose) is compared with ref_xyz[i]. */
 int icp_set_convergence_reference(icp_ctx* ctx, const float* src_xyz, const float* ref_xyz, int32_t n);

@@ -216,6 +216,13 @@ public:
         icp_gicp_options o; o.epsilon = epsilon; o.covariance_k = (int32_t)k;
         return icp_set_gicp_options(context(), &o);
     }
+    // Trimmed ICP and robust kernels (an extension): ICP_ROBUST_* kernel, tuning constant (0: the kernel's standard one), fixed scale
+    // (0: adaptive) and trim ratio (1: no trimming); icp_set_robust_options.  Returns its status (ICP_ERR_INVALID_ARG: a value out of range).
+    int setRobustOptions(int kernel, float tuning, float sigma, float overlap) {
+        if (!context()) return ICP_ERR_NO_DEVICE;
+        icp_robust_options o; o.kernel = (int32_t)kernel; o.tuning = tuning; o.sigma = sigma; o.overlap = overlap;
+        return icp_set_robust_options(context(), &o);
+    }
     // LinearICPOptimizer::estimatePose, ICPOptimizer.h:493-663
     void estimatePose(const PointCloud& source, const PointCloud& target, Matrix4f& initialPose, bool calculateRMSE = true) override {
         icp_params p; icp_params_default(&p);
