@@ -101,6 +101,9 @@ struct icp_ctx {
     icp_gicp_options gicp_opt = {1e-3f, 20};     // icp_set_gicp_options
     DevBuf gicp_n[2][3], gicp_flag;              // GICP normals of the target [0] / source [1] (SoA, original order), finite flags of their scratch tree
     bool gicp_ready[2] = {false, false};         // the cache is current (dropped by every call that replaces the cloud and by new options)
+    icp_colored_options col_opt = {0.968f, 20};  // icp_set_colored_options
+    DevBuf col_grad[3];                          // colour gradients of the target (SoA, original order, dev_colored.hpp)
+    bool col_ready = false;                      // the cache is current (dropped by every call that replaces the target and by new options)
     icp_robust_options rob_opt = {ICP_ROBUST_NONE, 0.f, 0.f, 1.f};   // icp_set_robust_options
     DevBuf rob_keys, rob_state, rob_stats;      // trimmed / robust mode (dev_robust.hpp): r^2 keys per query, the chain's state, per-iteration records
     std::vector<icp_robust_stats> rob_last;      // the records of the last call (icp_get_robust_stats)
@@ -601,7 +604,7 @@ int launch_match(icp_ctx* c, const QuerySet& q, int* fused_blocks = nullptr, con
         if (p.knn_incremental && !q.pretransformed) {
             kp.qstate = c->qstate.as<float4>(); kp.qstate2 = c->tier2 ? c->qstate2.as<float2>() : nullptr; kp.incremental = 1;
         }
-        const Cloud* fuse = (fused_blocks != nullptr && p.metric != ICP_METRIC_SYMMETRIC && p.metric != ICP_METRIC_GICP && !q.pretransformed) ? q.cl : nullptr;
+        const Cloud* fuse = (fused_blocks != nullptr && p.metric != ICP_METRIC_SYMMETRIC && p.metric != ICP_METRIC_GICP && p.metric != ICP_METRIC_COLORED && !q.pretransformed) ? q.cl : nullptr;
         if (q.use_colors) return launch_bvh_query<6>(c, c->bvh6, target_coords6(c), kp, q.order, q.n, fuse, fused_blocks, fuse ? ml : nullptr);
         return launch_bvh_query<3>(c, c->bvh, target_coords3(c), kp, q.order, q.n, fuse, fused_blocks, fuse ? ml : nullptr);
     }
@@ -648,6 +651,14 @@ GicpPost gicp_post_params(icp_ctx* c, const Cloud& src) {
     if (&src != &c->src)
         for (auto& kv : c->levels) if (&kv.second.sorted == &src) g.src_orig = kv.second.sorted_idx.as<int>();
     g.one_minus_eps = 1.0 - (double)c->gicp_opt.epsilon;
+    return g;
+}
+
+// What k_post_colored reads beside the post parameters: the cached colour gradients of the target (colored_prepare has made them current).
+ColoredPost colored_post_params(icp_ctx* c) {
+    ColoredPost g;
+    g.gx = c->col_grad[0].as<float>(); g.gy = c->col_grad[1].as<float>(); g.gz = c->col_grad[2].as<float>();
+    g.lambda = (double)c->col_opt.lambda_geometric;
     return g;
 }
 
@@ -702,10 +713,12 @@ int launch_post_and_solve(icp_ctx* c, const Cloud& src, const int* sel, int n, i
     }
     if (fused_blocks) nb = fused_blocks;                    // the matcher already wrote the block partials
     else if (p.metric == ICP_METRIC_GICP) hipLaunchKernelGGL(k_post_gicp, dim3(nb), dim3(POST_THREADS), 0, c->stream, pp, gicp_post_params(c, src));
+    else if (p.metric == ICP_METRIC_COLORED) hipLaunchKernelGGL(k_post_colored, dim3(nb), dim3(POST_THREADS), 0, c->stream, pp, colored_post_params(c));
     else hipLaunchKernelGGL(k_post, dim3(nb), dim3(POST_THREADS), 0, c->stream, pp);
     SolveParams sp; memset(&sp, 0, sizeof(sp));
-    // (GICP's sums have point-to-plane's layout and take its solve and composition: k_reduce_solve as it is, dev_gicp.hpp)
-    sp.partials = c->partials.as<double>(); sp.nblocks = nb; sp.ps = c->ps.as<PoseState>(); sp.metric = p.metric == ICP_METRIC_GICP ? ICP_METRIC_POINT_TO_PLANE : p.metric;
+    // (GICP's and colored ICP's sums have point-to-plane's layout and take its solve and composition: k_reduce_solve as it is, dev_gicp.hpp)
+    sp.partials = c->partials.as<double>(); sp.nblocks = nb; sp.ps = c->ps.as<PoseState>();
+    sp.metric = (p.metric == ICP_METRIC_GICP || p.metric == ICP_METRIC_COLORED) ? ICP_METRIC_POINT_TO_PLANE : p.metric;
     sp.totals = c->totals.as<double>(); sp.ticket = (unsigned*)(c->totals.as<double>() + NSUM);
     sp.n_src = n; sp.update_pose = update_pose; sp.spin = c->spin_reduce ? 1 : 0;
     auto reduce_solve = [&]() { hipLaunchKernelGGL(k_reduce_solve, dim3(NSUM_USED), dim3(SOLVE_THREADS), 0, c->stream, sp); };
@@ -880,6 +893,7 @@ int finish_target(icp_ctx* c, bool with_colors) {
     c->bvh6.valid = false;
     b.valid = false; b.n_valid = 0;
     c->gicp_ready[0] = false;
+    c->col_ready = false;
     if ((rc = finite_list(c, c->tgt, false, c->tgt_flag, c->tgt_finite, &b.n_valid))) return rc;
     b.d_finite = c->tgt_finite.as<int>(); b.n_ids = c->tgt.n;
     c->bvh6.d_finite = b.d_finite; c->bvh6.n_valid = b.n_valid; c->bvh6.n_ids = c->tgt.n;
@@ -1059,6 +1073,46 @@ int gicp_prepare(icp_ctx* c) {
     return gicp_normals(c, 1);
 }
 
+// Colour gradients of the target into the context's cache (icp_colored_options, dev_colored.hpp): k_color_gradients<k> over the target's
+// own BVH when it exists, else over the scratch tree of icp_estimate_normals, as gicp_normals builds it.  Enqueued only.
+int color_gradients(icp_ctx* c) {
+    Cloud& cl = c->tgt;
+    if (!cl.has_normals || !cl.has_colors) { c->err = "colored ICP needs a target with normals and colours"; return ICP_ERR_INVALID_ARG; }
+    if (c->col_ready) return ICP_OK;
+    const int n = cl.n, k = c->col_opt.gradient_k;
+    int rc;
+    for (DevBuf& d : c->col_grad) if ((rc = ensure(c, d, (size_t)n * 4))) return rc;
+    CoordPtrs<3> cp; cp.c[0] = cl.x.as<float>(); cp.c[1] = cl.y.as<float>(); cp.c[2] = cl.z.as<float>();
+    Bvh* b = &c->bvh;
+    if (!c->bvh.valid) {
+        b = &c->nrm_bvh; b->valid = false;
+        if ((rc = finite_list(c, cl, false, c->gicp_flag, c->nrm_finite, &b->n_valid))) return rc;
+        b->d_finite = c->nrm_finite.as<int>(); b->n_ids = n;
+        if ((rc = build_bvh<3>(c, *b, cp))) return rc;
+    }
+    BvhViewT<3> bv; bv.leaves = b->leaves.as<BvhLeafT<3>>(); bv.nodes = b->nodes.as<BvhNodeT<3>>(); bv.n_valid = b->n_valid; bv.Lp = b->Lp; bv.tgt = cp;
+    bv.qnodes = b->qnodes.as<BvhQuadT<3>>(); bv.Lq = b->Lq; bv.recs = b->recs.as<TgtRec>(); bv.pos_of = b->pos_of.as<int>();
+    int depth = 0; while ((1 << depth) < b->Lp) depth++;
+    const dim3 grid((n + BVH_THREADS - 1) / BVH_THREADS), block(BVH_THREADS); const size_t lds = (size_t)(depth + 1) * BVH_THREADS * 2;
+    const float *nx = cl.nx.as<float>(), *ny = cl.ny.as<float>(), *nz = cl.nz.as<float>();
+    const uint32_t* rgba = cl.rgba.as<uint32_t>();
+    float* o[3] = {c->col_grad[0].as<float>(), c->col_grad[1].as<float>(), c->col_grad[2].as<float>()};
+    if (k == 5) hipLaunchKernelGGL(k_color_gradients<5>, grid, block, lds, c->stream, bv, n, depth, nx, ny, nz, rgba, o[0], o[1], o[2]);
+    else if (k == 10) hipLaunchKernelGGL(k_color_gradients<10>, grid, block, lds, c->stream, bv, n, depth, nx, ny, nz, rgba, o[0], o[1], o[2]);
+    else hipLaunchKernelGGL(k_color_gradients<20>, grid, block, lds, c->stream, bv, n, depth, nx, ny, nz, rgba, o[0], o[1], o[2]);
+    HIPCK(c, hipGetLastError());
+    c->col_ready = true;
+    return ICP_OK;
+}
+// Loop start with metric = colored (run_loop, icp_correspond): the unsupported forms refused, the target's colour gradients current.
+int colored_prepare(icp_ctx* c) {
+    if (c->prm.metric != ICP_METRIC_COLORED) return ICP_OK;
+    if (c->prm.matching != ICP_MATCH_KNN) { c->err = "colored ICP needs k-NN matching (projective matching is not supported)"; return ICP_ERR_INVALID_ARG; }
+    if (c->lm_on) { c->err = "colored ICP is not supported by the non-linear optimiser"; return ICP_ERR_INVALID_ARG; }
+    if (!c->src.has_colors) { c->err = "colored ICP needs colours on the source"; return ICP_ERR_INVALID_ARG; }
+    return color_gradients(c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1131,6 +1185,7 @@ int icp_ctx_destroy(icp_ctx* c) {
     release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->pring); release(c->totals); release(c->dbg_steps); release(c->sums); release(c->gx_slots); release(c->gx_hdr);
     release(c->lm_state); release(c->lm_partials); release(c->lm_sums);
     for (auto& pl : c->gicp_n) for (DevBuf& d : pl) release(d);
+    for (DevBuf& d : c->col_grad) release(d);
     release(c->gicp_flag);
     release(c->rob_keys); release(c->rob_state); release(c->rob_stats);
     for (DevBuf* d : {&c->ms_ps, &c->ms_nn, &c->ms_st, &c->ms_st2, &c->ms_rec, &c->ms_d2, &c->ms_partials, &c->ms_totals, &c->ms_stats, &c->ms_score, &c->ms_res}) release(*d);
@@ -1161,7 +1216,7 @@ const char* icp_last_error(const icp_ctx* c) { return c ? c->err.c_str() : "null
 
 int icp_set_params(icp_ctx* c, const icp_params* p) {
     if (!c || !p) return ICP_ERR_INVALID_ARG;
-    if (p->metric < 0 || p->metric > 3 || p->matching < 0 || p->matching > 1 || p->weighting < 0 || p->weighting > 3 || p->n_iterations < 0 || p->selection < 0 || p->selection > 1 ||
+    if (p->metric < 0 || p->metric > 4 || p->matching < 0 || p->matching > 1 || p->weighting < 0 || p->weighting > 3 || p->n_iterations < 0 || p->selection < 0 || p->selection > 1 ||
         (p->knn_backend != ICP_KNN_BRUTE_FORCE && p->knn_backend != ICP_KNN_LBVH) || p->width < 0 || p->height < 0 || (long long)p->width * p->height > 0x7FFFFFFFll ||
         std::isnan(p->max_distance) || std::isnan(p->selection_proba) || !std::isfinite(p->fx) || !std::isfinite(p->fy) || !std::isfinite(p->cx) || !std::isfinite(p->cy)) {
         c->err = "icp_set_params: value out of range"; return ICP_ERR_INVALID_ARG;
@@ -1260,6 +1315,7 @@ int icp_correspond(icp_ctx* c, const float pose[16], icp_match_t* out, double* s
     if ((rc = set_device(c))) return rc;
     if ((rc = check_ready(c, true, true))) return rc;
     if ((rc = gicp_prepare(c))) return rc;
+    if ((rc = colored_prepare(c))) return rc;
     const bool robust = robust_on(c);
     c->rob_last.clear();
     if (robust && (rc = robust_prepare(c, 1))) return rc;
@@ -1292,6 +1348,7 @@ int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_
     if (!c || !poses || n_poses <= 0) { if (c) c->err = "icp_match_seeded: bad argument"; return ICP_ERR_INVALID_ARG; }
     const icp_params& p = c->prm;
     if (p.metric == ICP_METRIC_GICP) { c->err = "icp_match_seeded: GICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
+    if (p.metric == ICP_METRIC_COLORED) { c->err = "icp_match_seeded: colored ICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
     if (robust_on(c)) { c->err = "icp_match_seeded: robust mode (icp_set_robust_options) has no fused matcher"; return ICP_ERR_INVALID_ARG; }
     if (p.matching != ICP_MATCH_KNN || p.knn_backend != ICP_KNN_LBVH || p.metric == ICP_METRIC_SYMMETRIC || !c->fuse_post) {
         c->err = "icp_match_seeded: needs k-NN matching on the LBVH backend with the fused point-to-point / point-to-plane matcher"; return ICP_ERR_INVALID_ARG;
@@ -1481,6 +1538,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     if ((rc = set_device(c))) return rc;
     if ((rc = check_ready(c, true, true))) return rc;
     if ((rc = gicp_prepare(c))) return rc;
+    if ((rc = colored_prepare(c))) return rc;
     std::vector<int> factors;          // decimation factor per iteration; 0 = no selection (full cloud)
     if (single) factors.push_back(0);
     else {
@@ -1833,6 +1891,41 @@ int icp_set_gicp_options(icp_ctx* c, const icp_gicp_options* o) {
     return ICP_OK;
 }
 int icp_get_gicp_options(const icp_ctx* c, icp_gicp_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->gicp_opt; return ICP_OK; }
+int icp_colored_options_default(icp_colored_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    o->lambda_geometric = 0.968f; o->gradient_k = 20;
+    return ICP_OK;
+}
+int icp_set_colored_options(icp_ctx* c, const icp_colored_options* o) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    icp_colored_options v;
+    if (o) v = *o; else icp_colored_options_default(&v);
+    const int k = v.gradient_k;
+    if (!(v.lambda_geometric >= 0.f && v.lambda_geometric <= 1.f) || !(k == 5 || k == 10 || k == 20)) {
+        c->err = "icp_set_colored_options: need 0 <= lambda_geometric <= 1 and gradient_k in {5, 10, 20}"; return ICP_ERR_INVALID_ARG;
+    }
+    c->col_opt = v;
+    c->col_ready = false;
+    return ICP_OK;
+}
+int icp_get_colored_options(const icp_ctx* c, icp_colored_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->col_opt; return ICP_OK; }
+int icp_get_color_gradients(icp_ctx* c, float* out, int32_t max_points, int32_t* n_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (max_points < 0 || (!out && max_points > 0)) { c->err = "icp_get_color_gradients: bad argument (max_points >= 0)"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const Cloud& cl = c->tgt;
+    if (cl.n <= 0) { c->err = "no target cloud (icp_set_target)"; return ICP_ERR_NO_TARGET; }
+    if ((rc = color_gradients(c))) return rc;
+    const int n = cl.n, m = max_points < n ? max_points : n;
+    std::vector<float> h((size_t)m * 3);
+    for (int q = 0; q < 3 && m > 0; q++) HIPCK(c, hipMemcpyAsync(h.data() + (size_t)q * m, c->col_grad[q].p, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < m; i++) for (int q = 0; q < 3; q++) out[(size_t)i * 3 + q] = h[(size_t)q * m + i];
+    if (n_out) *n_out = n;
+    return guard.done();
+}
 int icp_get_gicp_normals(icp_ctx* c, int32_t which, float* out, int32_t max_points, int32_t* n_out) {
     if (!c) return ICP_ERR_INVALID_ARG;
     if ((which != 0 && which != 1) || max_points < 0 || (!out && max_points > 0)) { c->err = "icp_get_gicp_normals: bad argument (which 0 or 1, max_points >= 0)"; return ICP_ERR_INVALID_ARG; }
@@ -1904,6 +1997,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
     if (p.record_rmse != 0) { c->err = "icp_run_multistart: record_rmse is not supported"; return ICP_ERR_INVALID_ARG; }
     if (c->lm_on) { c->err = "icp_run_multistart: the non-linear optimiser is not supported"; return ICP_ERR_INVALID_ARG; }
     if (c->prm.metric == ICP_METRIC_GICP) { c->err = "icp_run_multistart: GICP is not supported"; return ICP_ERR_INVALID_ARG; }
+    if (c->prm.metric == ICP_METRIC_COLORED) { c->err = "icp_run_multistart: colored ICP is not supported"; return ICP_ERR_INVALID_ARG; }
     if (robust_on(c)) { c->err = "icp_run_multistart: robust mode (icp_set_robust_options) is not supported"; return ICP_ERR_INVALID_ARG; }
     int rc;
     DrainOnError guard(c);

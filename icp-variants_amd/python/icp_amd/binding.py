@@ -88,11 +88,15 @@ class IcpLmSummary(C.Structure):
 
 LM_CONVERGENCE, LM_NO_CONVERGENCE, LM_FAILURE, LM_NO_RESIDUALS = 0, 1, 2, 3
 
-METRIC_POINT_TO_POINT, METRIC_POINT_TO_PLANE, METRIC_SYMMETRIC, METRIC_GICP = 0, 1, 2, 3
+METRIC_POINT_TO_POINT, METRIC_POINT_TO_PLANE, METRIC_SYMMETRIC, METRIC_GICP, METRIC_COLORED = 0, 1, 2, 3, 4
 
 
 class IcpGicpOptions(C.Structure):
     _fields_ = [("epsilon", C.c_float), ("covariance_k", C.c_int32)]
+
+
+class IcpColoredOptions(C.Structure):
+    _fields_ = [("lambda_geometric", C.c_float), ("gradient_k", C.c_int32)]
 
 
 def lm_options(**kw):
@@ -166,6 +170,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames", "icp_depth_mesh",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
+           "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
            "icp_robust_options_default", "icp_set_robust_options", "icp_get_robust_options", "icp_get_robust_stats",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
@@ -302,6 +307,25 @@ class Context:
         self._ck(self.lib.icp_get_gicp_normals(self.h, C.c_int32(w), None, C.c_int32(0), C.byref(n)))
         out = np.empty((n.value, 3), np.float32)
         self._ck(self.lib.icp_get_gicp_normals(self.h, C.c_int32(w), _ptr(out), C.c_int32(n.value), C.byref(n)))
+        return out
+
+    def set_colored_options(self, lambda_geometric=0.968, k=20):
+        """icp_set_colored_options: the weight of the geometric term and the neighbours of the target's colour gradients."""
+        o = IcpColoredOptions(float(lambda_geometric), int(k))
+        self._ck(self.lib.icp_set_colored_options(self.h, C.byref(o)))
+        return o
+
+    def colored_options(self):
+        o = IcpColoredOptions()
+        self._ck(self.lib.icp_get_colored_options(self.h, C.byref(o)))
+        return o
+
+    def color_gradients(self):
+        """icp_get_color_gradients: the target's per-point colour gradients, n x 3 fp32 in the cloud's order (NaN where undefined)."""
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_get_color_gradients(self.h, None, C.c_int32(0), C.byref(n)))
+        out = np.empty((n.value, 3), np.float32)
+        self._ck(self.lib.icp_get_color_gradients(self.h, _ptr(out), C.c_int32(n.value), C.byref(n)))
         return out
 
     def set_robust_options(self, kernel="none", tuning=0.0, sigma=0.0, overlap=1.0):
@@ -623,6 +647,7 @@ class LinearICPOptimizer:
     def setNbOfIterations(self, n): self.ctx.params.n_iterations = n                           # :84-86
     def setKnnBackend(self, b): self.ctx.params.knn_backend = b
     def setGICPOptions(self, epsilon=1e-3, k=20): self.ctx.set_gicp_options(epsilon, k)         # setMetric(METRIC_GICP) selects it
+    def setColoredICPOptions(self, lambda_geometric=0.968, k=20): self.ctx.set_colored_options(lambda_geometric, k)   # setMetric(METRIC_COLORED)
     def setRobustOptions(self, kernel="none", tuning=0.0, sigma=0.0, overlap=1.0): self.ctx.set_robust_options(kernel, tuning, sigma, overlap)
 
     def setSelectionMethod(self, method, proba=1.0, seed=0):                                   # :58-61 (+ explicit seed)

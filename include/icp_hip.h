@@ -48,14 +48,15 @@ enum icp_status {
 
 /* enum values mirror the reference */
 enum { ICP_METRIC_POINT_TO_POINT = 0, ICP_METRIC_POINT_TO_PLANE = 1, ICP_METRIC_SYMMETRIC = 2,   /* ICPOptimizer.h:46-48,131-136 */
-       ICP_METRIC_GICP = 3 };        /* extension: Generalized-ICP, plane-to-plane (Segal, Haehnel, Thrun 2009); see icp_gicp_options */
+       ICP_METRIC_GICP = 3,          /* extension: Generalized-ICP, plane-to-plane (Segal, Haehnel, Thrun 2009); see icp_gicp_options */
+       ICP_METRIC_COLORED = 4 };     /* extension: colored ICP (Park, Zhou, Koltun 2017); see icp_colored_options */
 enum { ICP_MATCH_KNN = 0, ICP_MATCH_PROJECTIVE = 1 };                                               /* ICPOptimizer.h:71-78 */
 enum { ICP_WEIGHT_CONSTANT = 0, ICP_WEIGHT_DISTANCES = 1, ICP_WEIGHT_NORMALS = 2, ICP_WEIGHT_COLORS = 3 };   /* weighting.h:8 */
 enum { ICP_KNN_BRUTE_FORCE = 0, ICP_KNN_LBVH = 1 };   /* both exact: identical (d2, lowest-index) argmin, bit for bit */
 
 /* The setter surface of ICPOptimizer (ICPOptimizer.h:41-95) as one POD. */
 typedef struct icp_params {
-    int32_t metric;          /* setMetric                     default 0 (ICP_METRIC_*; 3 = GICP, an extension) */
+    int32_t metric;          /* setMetric                     default 0 (ICP_METRIC_*; 3 = GICP, 4 = colored, extensions) */
     int32_t matching;        /* setMatchingMethod             default 0 (k-NN)    */
     int32_t weighting;       /* setWeightingMethod            default 0           */
     int32_t rejection;       /* setRejectionMethod            default 1 (60 deg)  */
@@ -300,6 +301,35 @@ int icp_get_robust_options(const icp_ctx* ctx, icp_robust_options* opt);
  * tracked frame's run; icp_batch_run: each context's own last pair); none when robust mode was off for that call.  Iterations with no
  * work: {0, 0, -1, -1}.  out[0 .. min(max_out, count)), *count_out = the number of records. */
 int icp_get_robust_stats(const icp_ctx* ctx, icp_robust_stats* out, int32_t max_out, int32_t* count_out);
+
+/* -------- Colored ICP (extension: the reference has no counterpart), params.metric = ICP_METRIC_COLORED --------
+ * Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017): point-to-plane plus a photometric term along the
+ * target's tangent planes.  Both clouds need colours, the target needs normals.  Intensity of a point: I = (R + G + B) / 765.0 in fp64.
+ * Colour gradient of target point i, computed once per target on the device and cached (every call that replaces the target, and
+ * icp_set_colored_options, drops the cache): n = i's own normal normalised in fp64; the k smallest (fp32 d^2, index) pairs over the target's
+ * finite points (the point itself included), m of them; one row per neighbour j != i, a_j = q'_j - p with q'_j = q_j - n ((q_j - p).n),
+ * b_j = I_j - I_i; one constraint row a = (m - 1) n, b = 0; (A^T A) d = A^T b by adjugate and determinant in fp64, d rounded once to fp32.
+ * A non-finite point or normal, or a zero normal: NaN; fewer than 3 neighbours or det(A^T A) <= 1e-12 (tr(A^T A) / 3)^3: (0, 0, 0).
+ * One correspondence (the record after weighting and rejection, as icp_correspond returns it): p = the fp32 transformed source point,
+ * q = the fp32 target point, n = the target normal (unit, fp64), d = its gradient widened to fp64, J = [ -[p]x | I ], lambda = the fp32
+ * field widened: j_G = n^T J, r_G = n.(q - p); j_C = d^T (I - n n^T) J, r_C = I_s - I_q - d^T (I - n n^T)(p - q), with
+ * I_s - I_q = ((R + G + B)_s - (R + G + B)_q) / 765.0 (one rounding).  The pair enters when the
+ * validity filter passes and n, d are finite with |n| > 0: H += w^2 (lambda j_G^T j_G + (1 - lambda) j_C^T j_C),
+ * g += w^2 (lambda j_G^T r_G + (1 - lambda) j_C^T r_C), in the sums icp_correspond returns (GICP's layout).  Solve and composition:
+ * point-to-plane's.  Supported: k-NN matching (both backends, 3-D and colour), every weighting, rejection, multires, selection,
+ * record_rmse, robust mode, icp_iterate, icp_run, icp_correspond, icp_batch_run, icp_track_depth_frames.  ICP_ERR_INVALID_ARG at loop
+ * start (see icp_last_error): projective matching, the non-linear optimiser, a cloud without colours, a target without normals; always:
+ * icp_run_multistart, icp_match_seeded. */
+typedef struct icp_colored_options {
+    float   lambda_geometric;   /* weight of the geometric term, 0 <= lambda <= 1, default 0.968 (Park's sigma) */
+    int32_t gradient_k;         /* neighbours of a colour gradient, {5, 10, 20}, default 20 */
+} icp_colored_options;
+int icp_colored_options_default(icp_colored_options* opt);
+int icp_set_colored_options(icp_ctx* ctx, const icp_colored_options* opt);   /* NULL = defaults */
+int icp_get_colored_options(const icp_ctx* ctx, icp_colored_options* opt);
+/* The target's colour gradients the loop uses, original point order, n x 3 floats (NaN where undefined); computed on demand.
+   out[0 .. min(n, max_points)) is written, *n_out (optional) = n. */
+int icp_get_color_gradients(icp_ctx* ctx, float* out, int32_t max_points, int32_t* n_out);
 
 /* -------- ConvergenceMeasure (ConvergenceMeasure.h:30-66): known-correspondence RMSE --------
  * src_xyz[i] (moved by the estimated pose) is compared with ref_xyz[i]. */

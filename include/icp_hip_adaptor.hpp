@@ -216,6 +216,13 @@ public:
         icp_gicp_options o; o.epsilon = epsilon; o.covariance_k = (int32_t)k;
         return icp_set_gicp_options(context(), &o);
     }
+    // Colored ICP (setMetric(ICP_METRIC_COLORED), an extension): weight of the geometric term and neighbours of the target's colour
+    // gradients; icp_set_colored_options.  Returns its status (ICP_ERR_INVALID_ARG: lambda outside [0, 1] or k not in {5, 10, 20}).
+    int setColoredICPOptions(float lambda_geometric, unsigned k) {
+        if (!context()) return ICP_ERR_NO_DEVICE;
+        icp_colored_options o; o.lambda_geometric = lambda_geometric; o.gradient_k = (int32_t)k;
+        return icp_set_colored_options(context(), &o);
+    }
     // Trimmed ICP and robust kernels (an extension): ICP_ROBUST_* kernel, tuning constant (0: the kernel's standard one), fixed scale
     // (0: adaptive) and trim ratio (1: no trimming); icp_set_robust_options.  Returns its status (ICP_ERR_INVALID_ARG: a value out of range).
     int setRobustOptions(int kernel, float tuning, float sigma, float overlap) {
