@@ -53,8 +53,7 @@ struct P2pGen {                                           // values 0..21 = sum 
 
 // What a query brings along that does not depend on the pose: requested in ONE batch (point, normal, previous neighbour, search
 // state), then the neighbour's record -- two memory round trips before the verify test instead of one per array; in the late
-// iterations, where almost no query walks, those round trips ARE the per-launch kernels.  The persistent loop (dev_persist.hpp) keeps
-// all of it in registers from one iteration to the next for as long as the wave's queries verify.
+// iterations, where almost no query walks, those round trips ARE the per-launch kernels.
 template <int DIM> struct QueryIn {
     float r0, r1, r2;            // source point (untransformed)
     float c3, c4, c5;            // colour features (DIM == 6)
@@ -108,13 +107,10 @@ __host__ __device__ __forceinline__ int fused_wave_slot(int lb, int w, int mgrid
 struct PairOut { bool valid; float s0, s1, s2, d0, d1, d2, n0, n1, n2, wt; };
 
 // Transform, verify (both tiers), search what does not verify (walks shared over the wave), weigh / reject: everything of one
-// iteration between "the pose is known" and "the lane holds its pair".  `searched` = this lane's query walked or took the two-leaf tier
-// (its search state was rewritten).  renewed (the persistent loop, DIM == 3): set for a lane whose query took the two-leaf tier in a wave that
-// did not walk -- `in` then holds its NEW state (anchor, bound, neighbour's record), ready to be parked again; a lane whose new state
-// cannot be given that way (no record fetched: the neighbour is past the distance threshold) leaves `searched` set instead.
+// iteration between "the pose is known" and "the lane holds its pair".
 template <int DIM, bool WIDE, bool XW = false>
 __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const BvhViewT<DIM>& bv, const PostParams& pp, int k, bool seeded, bool inc, const float* Pm, const float* Nm,
-                                                  QueryIn<DIM>& in, uint2* __restrict__ bvh_lbq, int tid, int wave_slot, PairOut& o, bool& searched, bool* renewed = nullptr, int gx_block = 0) {
+                                                  QueryIn<DIM>& in, uint2* __restrict__ bvh_lbq, int tid, int wave_slot, PairOut& o) {
     const int lane = tid & 63; (void)lane; (void)wave_slot; (void)seeded;
     o.valid = false; o.s0 = 0.f; o.s1 = 0.f; o.s2 = 0.f; o.d0 = 0.f; o.d1 = 0.f; o.d2 = 0.f; o.n0 = 0.f; o.n1 = 0.f; o.n2 = 0.f; o.wt = 0.f;
     float p[DIM];
@@ -167,8 +163,6 @@ __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const Bvh
         }
     }
     ICP_STAMP(1);
-    searched = need_walk || two_leaf;
-    if (renewed) *renewed = false;
 #if ICP_DEBUG_TIMES
     if (kp.dbg_steps && k >= 0 && (need_walk || two_leaf) && seeded) {      // who is it that still searches?  (slot by query index; the clock tells the launch)
         int* r = kp.dbg_steps + 8 * kp.dbg_waves + 8 * (k & 4095);
@@ -178,7 +172,6 @@ __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const Bvh
             // where the wave runs: HW_ID (id 4: simd [5:4], cu [11:8], sh [12], se [15:13]) and XCC_ID (id 20) -> bits 16.. of the second word
             kp.dbg_steps[8 * wave_slot + 7] = (int)((__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu) | (__builtin_amdgcn_s_getreg((31 << 11) | 20) << 16)); } }
 #endif
-    const bool took_two_leaf = two_leaf;
     if (two_leaf) {
         f2 p2[DIM];
 #pragma unroll
@@ -204,11 +197,11 @@ __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const Bvh
     if (__any(need_walk)) {
         walked = true;
         float rn[3] = {rn0, rn1, rn2};
-        knn_walk_shared<DIM, BVH_THREADS, typename std::conditional<WIDE, unsigned long long, unsigned int>::type, XW ? 1 : 0>(bv, p, rn, need_walk, best, bi, bpos, lb_others, lb3, l2, bvh_lbq, tid, kp.fault, &kp.gx, gx_block);
+        knn_walk_shared<DIM, BVH_THREADS, typename std::conditional<WIDE, unsigned long long, unsigned int>::type, XW ? 1 : 0>(bv, p, rn, need_walk, best, bi, bpos, lb_others, lb3, l2, bvh_lbq, tid, kp.fault);
         rn0 = rn[0]; rn1 = rn[1]; rn2 = rn[2];
         q0 = -2;                                          // the neighbour's record is read again below: it need not stay in registers while this lane helps
-        // (the persistent loop: a wave that walked reloads its queries' data in the next iteration -- said here in a way the register
-        //  allocator can see, so that none of it stays alive across the walk)
+        // (nothing of `in` is read after the walk -- said here in a way the register allocator can see, so that none of it stays alive
+        //  across the walk.  Without it the 6-D matchers are allocated differently: k_knn_bvh_post_ring<6, true> 90 -> 92 VGPRs)
         fused_front_clear<DIM>(in);
     }
 #else
@@ -217,9 +210,9 @@ __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const Bvh
     ICP_STAMP(2);
 #if ICP_DEBUG_TIMES && ICP_DEBUG_WALK_ENDS                  // (one atomic per walking query on ONE word: it distorts every time stamp -- a build of its own, tools/dev_walk_ends.py)
     if (k >= 0 && need_walk && seeded) {                       // where did the seeded walk end: in the old neighbour's leaf, in the old runner-up's leaf, elsewhere?
-        GX_COUNT(8, 1);
-        if (dbg_q0old >= 0 && (bpos >> 3) == (dbg_q0old >> 3)) GX_COUNT(9, 1);
-        if (dbg_l2old >= 0 && (bpos >> 3) == dbg_l2old) GX_COUNT(10, 1);
+        DEV_COUNT(8, 1);
+        if (dbg_q0old >= 0 && (bpos >> 3) == (dbg_q0old >> 3)) DEV_COUNT(9, 1);
+        if (dbg_l2old >= 0 && (bpos >> 3) == dbg_l2old) DEV_COUNT(10, 1);
     }
 #endif
     asm volatile("" : "+v"(k));                           // (the addresses of this query's state and records are formed HERE, not held in registers across the walk)
@@ -238,12 +231,6 @@ __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const Bvh
             o.d0 = ra.x; o.d1 = ra.y; o.d2 = ra.z; o.n0 = rb.x; o.n1 = rb.y; o.n2 = rb.z;
             o.s0 = p[0]; o.s1 = p[1]; o.s2 = p[2];
             o.valid = post_eval<true>(pp, k, m, o.d0, o.d1, o.d2, o.n0, o.n1, o.n2, __float_as_uint(rb.w), o.s0, o.s1, o.s2, o.wt, rn0, rn1, rn2, Nm);
-        }
-        if (DIM == 3 && renewed && took_two_leaf && !walked && (m.idx >= 0 || bpos == q0)) {
-            // the two-leaf tier re-anchored this query (knn_store_state above wrote the same to memory): hand the new state back
-            in.st.x = p[0]; in.st.y = p[1]; in.st.z = p[2]; in.st.w = lb_others; in.q0 = bpos; in.ra = ra; in.rb = rb;
-            in.tq[0] = ra.x; in.tq[1] = ra.y; in.tq[2] = ra.z; in.j0 = __float_as_int(ra.w);
-            *renewed = true; searched = false;
         }
     }
     ICP_STAMP(3);
@@ -333,8 +320,8 @@ __device__ __forceinline__ void fused_matcher_body(const KnnParams& kp, const Bv
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
     if constexpr (MERGED) { if (!ring_wait_pose(loop_slot((PoseState*)kp.ps, 0, (int)((blockIdx.x * 2u + (unsigned int)w) % (unsigned int)POSE_REPLICAS)), lane, rp.run_fault, Pm, Nm)) return; }
-    PairOut o; bool searched;
-    fused_search_post<DIM, WIDE, XW>(kp, bv, pp, k, seeded, inc, Pm, Nm, in, bvh_lbq, tid, wave_slot, o, searched, nullptr, lb);
+    PairOut o;
+    fused_search_post<DIM, WIDE, XW>(kp, bv, pp, k, seeded, inc, Pm, Nm, in, bvh_lbq, tid, wave_slot, o);
     if constexpr (XW) {
         // this wave holds its pairs; before the block's sums, it helps the waves of the block that still search (the pair waits in the
         // wave's own LDS rows, which nobody reads once its queries are complete)
@@ -343,7 +330,7 @@ __device__ __forceinline__ void fused_matcher_body(const KnnParams& kp, const Bv
             bvh_lbq[3 * NT + tid] = make_uint2(__float_as_uint(o.s0), __float_as_uint(o.s1)); bvh_lbq[4 * NT + tid] = make_uint2(__float_as_uint(o.s2), __float_as_uint(o.d0));
             bvh_lbq[5 * NT + tid] = make_uint2(__float_as_uint(o.d1), __float_as_uint(o.d2)); bvh_lbq[7 * NT + tid] = make_uint2(__float_as_uint(o.n0), __float_as_uint(o.n1));
             bvh_lbq[8 * NT + tid] = make_uint2(__float_as_uint(o.n2), __float_as_uint(o.wt)); bvh_lbq[9 * NT + tid] = make_uint2(o.valid ? 1u : 0u, 0u);
-            xw_help<DIM, NT, typename std::conditional<WIDE, unsigned long long, unsigned int>::type>(bv, bvh_lbq, tid, kp.fault, &kp.gx, lb);
+            xw_help<DIM, NT, typename std::conditional<WIDE, unsigned long long, unsigned int>::type>(bv, bvh_lbq, tid, kp.fault);
             const uint2 a = bvh_lbq[3 * NT + tid], b = bvh_lbq[4 * NT + tid], c = bvh_lbq[5 * NT + tid], d = bvh_lbq[7 * NT + tid], e = bvh_lbq[8 * NT + tid], f = bvh_lbq[9 * NT + tid];
             o.s0 = __uint_as_float(a.x); o.s1 = __uint_as_float(a.y); o.s2 = __uint_as_float(b.x); o.d0 = __uint_as_float(b.y); o.d1 = __uint_as_float(c.x); o.d2 = __uint_as_float(c.y);
             o.n0 = __uint_as_float(d.x); o.n1 = __uint_as_float(d.y); o.n2 = __uint_as_float(e.x); o.wt = __uint_as_float(e.y); o.valid = f.x != 0u;
@@ -351,16 +338,6 @@ __device__ __forceinline__ void fused_matcher_body(const KnnParams& kp, const Bv
     }
     double* partials = pp.partials;
     fused_block_epilogue(kp, pp, o, bvh_lbq, tid, wave_slot, [=](int a, double v) { partials[(size_t)a * mgrid + lb] = v; });
-    if constexpr (XW && ICP_GX) {
-        if (kp.gx.slots) {
-            // GX: the block's partial is on its way.  Its outbox is as it was found (every posted slot was folded or taken back before the
-            // block's sums) -- the header still says otherwise; and if this block walked for long, so do others: wave 0 goes and helps.
-            const int* xc = (const int*)(bvh_lbq + ICP_SHARE_ROWS * BVH_THREADS);
-            const int posted = xc[20], walked_long = xc[21];
-            if (tid == 0 && posted > 0) gx_store((unsigned long long*)kp.gx.hdr + lb, 0ull);
-            if (tid < WAVE && walked_long) gx_help<DIM, BVH_THREADS, typename std::conditional<WIDE, unsigned long long, unsigned int>::type>(bv, kp.gx, lb, mgrid, bvh_lbq, tid);
-        }
-    }
 }
 template <int DIM, bool WIDE>
 __global__ __launch_bounds__(BVH_THREADS, DIM == 3 ? ICP_FUSED_WAVES : 4) void k_knn_bvh_post(const KnnParams kp, const BvhViewT<DIM> bv, const int* __restrict__ qorder, const PostParams pp) {

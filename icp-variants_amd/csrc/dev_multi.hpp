@@ -30,7 +30,7 @@ __device__ __forceinline__ void multi_shift_post(PostParams& pp, const MultiStri
     pp.partials += ms.partials * s;
 }
 
-// The fused matcher (k_knn_bvh_post) for every start.  No hand-over between blocks (GX): its outboxes are per block of ONE grid.
+// The fused matcher (k_knn_bvh_post) for every start.
 template <int DIM, bool WIDE>
 __global__ __launch_bounds__(BVH_THREADS, DIM == 3 ? ICP_FUSED_WAVES : 4) void k_knn_bvh_post_multi(const KnnParams kp, const BvhViewT<DIM> bv, const int* __restrict__ qorder, const PostParams pp, const MultiStride ms) {
     KnnParams k = kp; PostParams p = pp;

@@ -514,13 +514,8 @@ constexpr size_t POSE_REPLICA_STRIDE = 4096 + 128;
 __device__ __host__ __forceinline__ PoseState* loop_slot(PoseState* base, int g, int replica) {
     return (PoseState*)((char*)base + ((size_t)g * POSE_REPLICAS + (size_t)replica) * POSE_REPLICA_STRIDE);
 }
-#if ICP_DEBUG_TIMES
-#define LOOP_STAMP(slot, j) do { if (L.dbg && g == L.dbg_iter && (threadIdx.x & 63) == 0) L.dbg[8 * (slot) + (j)] = (int)(unsigned int)wall_clock64(); } while (0)
-#else
-#define LOOP_STAMP(slot, j)
-#endif
-// One launch in front of a run of the merged / one-launch loop: slot 0 = the incoming pose in every replica, every other slot's granules
-// and the totals rows "empty", the fault word and the clocks zero.  (Only the 128 bytes of a replica that are ever read are touched --
+// One launch in front of a run of the merged loop: slot 0 = the incoming pose in every replica, every other slot's granules
+// and the totals rows "empty", the fault word zero.  (Only the 128 bytes of a replica that are ever read are touched --
 // the replicas sit 4 KB apart.)
 __global__ void k_run_init(const PoseState* __restrict__ src, PoseState* slots, int n_slots, unsigned long long* totals, int n_totals, int* zero_words, int n_zero) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;

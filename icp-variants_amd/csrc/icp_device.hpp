@@ -7,7 +7,7 @@
 // fp32 sqrt and divide are correctly rounded (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt).
 //
 // Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_solve.hpp,
-// dev_fused.hpp, dev_persist.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp
+// dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -23,8 +23,6 @@
 //                       pruneCorrespondences (ICPOptimizer.h:157-174) + validity filter (:594-610) +
 //                       normal-equation / moment accumulation (ICPOptimizer.h:676-751, ProcrustesAligner.h:43-55)
 //   k_sym_accumulate    second pass of the symmetric objective with the means (ICPOptimizer.h:797-853)
-//   k_icp_loop          the whole loop of one resolution level as ONE launch (point-to-plane, fused BVH matcher): resident waves keep their
-//                       queries in registers, reducer blocks fold / solve / publish the pose through self-validating granules (dev_persist.hpp)
 //   k_reduce_solve      fixed-order reduction of block partials + fp64 solve + pose composition
 //                       (ICPOptimizer.h:614-620,753-781,855-897; ProcrustesAligner.h:56-66)
 //   k_rmse_partial      ConvergenceMeasure::rmseAlignmentError (ConvergenceMeasure.h:50-66)
@@ -58,7 +56,6 @@ namespace icpdev {
 #include "dev_post.hpp"
 #include "dev_solve.hpp"
 #include "dev_fused.hpp"
-#include "dev_persist.hpp"
 #include "dev_measures.hpp"
 #include "dev_mesh.hpp"
 #include "dev_lm.hpp"

@@ -52,7 +52,7 @@ struct Cloud {
 // One resolution level of the source: the selection (original indices, increasing), and -- for the BVH matcher -- a physical
 // copy of the selected points in Morton order, so that everything the ICP loop touches per query (source planes, search
 // state, matches) is indexed by the same sorted position and streams coalesced.  factor 0 = the whole cloud, unfiltered.
-struct Level { DevBuf idx; DevBuf order; DevBuf sorted_idx; DevBuf pack; Cloud sorted; bool sorted_valid = false; int n = 0; };   // pack: the sorted copy's planes in ONE allocation (x y z nx ny nz cr cg cb rgba, a fixed stride apart: k_icp_loop)
+struct Level { DevBuf idx; DevBuf order; DevBuf sorted_idx; DevBuf pack; Cloud sorted; bool sorted_valid = false; int n = 0; };   // pack: the sorted copy's planes in ONE allocation (x y z nx ny nz cr cg cb rgba, a fixed stride apart)
 
 // LBVH over the target (buildIndex): device buffers + the host-side facts needed to launch the build.
 struct Bvh {
@@ -83,16 +83,8 @@ struct icp_ctx {
     bool trace = false;                  // ICP_HIP_TRACE=1: per-iteration stage times on stderr
     bool fuse_post = true;               // BVH matcher runs weight / reject / accumulate as its epilogue (ICP_HIP_FUSE_POST=0 disables)
     bool merge_loop = true;              // point-to-plane loop through the fused BVH matcher: reduce + solve ride in front of the next matcher launch (ICP_HIP_MERGE=0: separate k_reduce_solve launches)
-    int loop_from = 0;                   // k_icp_loop takes over at this iteration of a run; the ones before it run one (merged) launch each (ICP_HIP_LOOP_FROM)
-    bool persist_loop = false;           // ICP_HIP_PERSIST=1 (experimental, measured slower than the merged loop so far: DESIGN.md): when the whole grid fits the device at once, the loop of a resolution level as ONE launch (k_icp_loop; ICP_HIP_PERSIST=0 disables)
-    bool shared_gpu = false;             // other contexts work on this device at the same time (icp_batch_run with several contexts): one launch per iteration
-    int loop_runs = 0;                   // runs that took k_icp_loop (icp_debug_counters)
-    hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // k_icp_loop_reducer runs BESIDE the matcher grid: its own stream, forked off / joined to the context's
-    int loop_capacity[4] = {0, 0, 0, 0}; // resident blocks of k_icp_loop<3/6, false/true> on this device (0: not asked yet)
     int merged_runs = 0, merged_fallbacks = 0;   // runs that took the merged loop / that had to be repeated with the separate launches (icp_debug_counters)
     bool ext_events = true;              // merged form: stage times from hipExtLaunchKernel's start / stop events (ICP_HIP_EXT_EVENTS=0: hipEventRecord brackets)
-    bool gx_on = ICP_GX != 0; int gx_start = 16, gx_empty = 3;   // hand-over between the blocks of the fused matcher (dev_bvh.hpp, GX): ICP_HIP_GX=0 disables; ICP_HIP_GX_START / ICP_HIP_GX_EMPTY
-    DevBuf gx_slots, gx_hdr; int gx_blocks = 0; bool gx_dirty = false;      // the outboxes (armed once: every launch leaves them as it found them; gx_dirty: a run was cut short)
     bool keep_fused_records = false;     // icp_match_seeded: the fused matcher also writes its Match records and distances (the loop itself never reads them)
     bool lm_on = false; icp_lm_options lm_opt;   // icp_set_optimizer: the non-linear optimiser (k_lm_eval / k_lm_step) instead of the linear solve
     DevBuf lm_state, lm_partials, lm_sums;       // its minimiser state, eval partials, per-iteration records of the run in flight
@@ -120,7 +112,7 @@ struct icp_ctx {
     DevBuf qpack; size_t q_cap = 0;                      // nn_raw | qstate | qstate2 (views below), q_cap elements each
     DevBuf qstate, qstate2;                              // incremental k-NN: per-query anchor + bound on the other targets; bound on the targets outside the neighbour's leaf
     DevBuf dbg_steps;                    // development builds only (ICP_DEBUG_STEPS)
-    DevBuf ps, matches, d2, best64, nn_raw, partials, partials2, ring, pring, totals, sums, stats, staging, rmse_partials, rmse_out, fontana_partials;
+    DevBuf ps, matches, d2, best64, nn_raw, partials, partials2, ring, totals, sums, stats, staging, rmse_partials, rmse_out, fontana_partials;
     Cloud conv_src, conv_ref; int conv_n = 0;
     // depth frames (icp_set_*_depth, icp_track_depth_frames): two upload slots, each a page-locked staging block + a device copy of
     // [depth 4n | rgbx 4n]; the next frame of a sequence goes up on depth_stream while the current one iterates
@@ -188,7 +180,7 @@ int set_device(icp_ctx* c) { HIPCK(c, hipSetDevice(c->device)); return ICP_OK; }
 struct DrainOnError {
     icp_ctx* c; bool ok = false;
     explicit DrainOnError(icp_ctx* ctx) : c(ctx) {}
-    ~DrainOnError() { if (!ok && c && c->stream) { if (c->stream2) (void)hipStreamSynchronize(c->stream2); (void)hipStreamSynchronize(c->stream); } }
+    ~DrainOnError() { if (!ok && c && c->stream) (void)hipStreamSynchronize(c->stream); }
     int done(int rc = ICP_OK) { ok = (rc == ICP_OK); return rc; }
 };
 
@@ -300,7 +292,7 @@ int write_pose(icp_ctx* c, const float pose[16]) {
 }
 
 // One launch of the merged loop: the pose slot its matcher blocks wait for, where they leave their partials, and the reducer that rides in front.
-struct MergeLaunch { RingParams rp; const PoseState* slot; double* partials; const LoopParams* loop = nullptr; hipEvent_t ev_start = nullptr, ev_stop = nullptr; };   // ev_start / ev_stop: the launch's own start / stop times go into these events (hipExtLaunchKernel: taken from the dispatch itself, no bracket on the stream)   // loop != nullptr: k_icp_loop (all iterations of a level in one launch)
+struct MergeLaunch { RingParams rp; const PoseState* slot; double* partials; hipEvent_t ev_start = nullptr, ev_stop = nullptr; };   // ev_start / ev_stop: the launch's own start / stop times go into these events (hipExtLaunchKernel: taken from the dispatch itself, no bracket on the stream)
 
 struct QuerySet { const Cloud* cl; const int* sel; int n; int pretransformed; bool use_colors; bool seed_prev; const int* order; };   // cl/sel: also what the post stage reads
 
@@ -485,27 +477,6 @@ PostParams make_post_params(icp_ctx* c, const Cloud& src, const int* sel, int n)
     return pp;
 }
 
-// The outboxes of the hand-over between blocks (GX): armed for `blocks` blocks -- granules all-ones, claim words and headers zero.
-__global__ void k_gx_init(unsigned long long* slots, size_t n_granules, unsigned int* hdr, size_t n_hdr) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_granules) slots[i] = (i % GX_GRANULES == 4) ? 0ull : GX_EMPTY;
-    if (i < n_hdr) hdr[i] = 0u;
-}
-static int ensure_gx(icp_ctx* c, int blocks) {
-    if (!c->gx_on || c->shared_gpu) return ICP_OK;
-    int rc;
-    if (blocks > c->gx_blocks || c->gx_dirty) {
-        const int nbk = blocks > c->gx_blocks ? blocks : c->gx_blocks;
-        const size_t ng = (size_t)nbk * GX_SLOTS * GX_GRANULES;
-        if ((rc = ensure(c, c->gx_slots, ng * 8))) return rc;
-        if ((rc = ensure(c, c->gx_hdr, (size_t)nbk * 8))) return rc;
-        hipLaunchKernelGGL(k_gx_init, dim3((unsigned int)((ng + 255) / 256)), dim3(256), 0, c->stream, c->gx_slots.as<unsigned long long>(), ng, c->gx_hdr.as<unsigned int>(), (size_t)nbk * 2);
-        HIPCK(c, hipGetLastError());
-        c->gx_blocks = nbk; c->gx_dirty = false;
-    }
-    return ICP_OK;
-}
-
 // fuse != nullptr: run the post stage (weight / reject / accumulate) as the epilogue of the search; *fused_blocks receives the
 // number of block partials written.
 template <int DIM>
@@ -520,33 +491,11 @@ int launch_bvh_query(icp_ctx* c, Bvh& b, const CoordPtrs<DIM>& cp, const KnnPara
         if ((rc = ensure(c, c->partials, (size_t)(nb > POST_BLOCKS ? nb : POST_BLOCKS) * NSUM * 8))) return rc;
         PostParams pp = make_post_params(c, *fuse, kp.sel, n);
         KnnParams kf = kp; kf.out = nullptr;
-        if (DIM == 3 && c->gx_on && !c->shared_gpu && !(ml && ml->loop)) {
-            if ((rc = ensure_gx(c, nb))) return rc;
-            kf.gx = GxParams{c->gx_slots.as<unsigned long long>(), c->gx_hdr.as<unsigned int>(), c->gx_start, c->gx_empty};
-        }
         if (!c->keep_fused_records) { pp.matches = nullptr; kf.d2_out = nullptr; }     // the loop never reads the records of a fused iteration, nor the distances
         const size_t red_bytes = (size_t)(BVH_THREADS / WAVE) * 33 * 8;           // the reduction reuses the (dead) traversal stacks
         static const size_t lds_pad = getenv("ICP_HIP_LDS_PAD") ? (size_t)atoi(getenv("ICP_HIP_LDS_PAD")) : 0;      // development: fewer resident blocks per CU
         const size_t lds = (stack_bytes > red_bytes ? stack_bytes : red_bytes) + xw_lds_bytes<DIM, BVH_THREADS>() + lds_pad;      // + the board of the cross-wave hand-over
-        if (ml && ml->loop) {                                                      // the level's whole loop in one launch
-            LoopK<DIM> K; memset(&K, 0, sizeof(K));
-            // (the level's planes and the search state are packed: get_sorted_level / launch_match; anything else cannot take this path)
-            const float* x0 = fuse->x.as<float>(); const long long S = fuse->y.as<float>() - x0;
-            const bool packed_src = S > 0 && fuse->z.as<float>() == x0 + 2 * S && fuse->nx.as<float>() == x0 + 3 * S && fuse->ny.as<float>() == x0 + 4 * S && fuse->nz.as<float>() == x0 + 5 * S &&
-                                    (!fuse->cr.p || (fuse->cr.as<float>() == x0 + 6 * S && fuse->cg.as<float>() == x0 + 7 * S && fuse->cb.as<float>() == x0 + 8 * S && fuse->rgba.as<float>() == x0 + 9 * S));
-            const bool packed_q = kf.nn_raw == c->qpack.as<int>() && (!kf.qstate || (char*)kf.qstate == c->qpack.as<char>() + c->q_cap * 4) && (!kf.qstate2 || (char*)kf.qstate2 == c->qpack.as<char>() + c->q_cap * 20);
-            if (!packed_src || !packed_q || kf.sel || order) { c->err = "k_icp_loop: level or search state not in the packed layout"; return ICP_ERR_INVALID_ARG; }
-            K.src = x0; K.src_stride = (int)S; K.qpack = c->qpack.as<char>(); K.q_cap = (int)c->q_cap;
-            K.leaves = bv.leaves; K.qnodes = bv.qnodes; K.recs = bv.recs; K.Lq = bv.Lq; K.n_valid = bv.n_valid;
-            K.matches = pp.matches; K.d2_out = kf.d2_out; K.dbg_steps = kf.dbg_steps;
-            K.n = kf.n; K.max_dist = kf.max_dist; K.incremental = kf.incremental; K.tier2 = kf.qstate2 ? 1 : 0;
-            K.metric = pp.metric; K.weighting = pp.weighting; K.rejection = pp.rejection; K.cos_reject = pp.cos_reject;
-            K.L = *ml->loop; K.L.nb = nb;
-            const size_t lds_loop = (size_t)LOOP_LDS_ROWS * BVH_THREADS * 8;
-            if (b.Lq <= 8) hipLaunchKernelGGL((k_icp_loop<DIM, false>), dim3(nb), dim3(BVH_THREADS), lds_loop, c->stream, K);
-            else hipLaunchKernelGGL((k_icp_loop<DIM, true>), dim3(nb), dim3(BVH_THREADS), lds_loop, c->stream, K);
-        }
-        else if (ml) {                                                             // merged loop: reducer blocks in front, pose through the ring
+        if (ml) {                                                                  // merged loop: reducer blocks in front, pose through the ring
             kf.ps = ml->slot; pp.ps = ml->slot; pp.partials = ml->partials; kf.fault = ml->rp.run_fault;
             if (ml->ev_start) {
                 if (b.Lq <= 8) hipExtLaunchKernelGGL((k_knn_bvh_post_ring<DIM, false>), dim3(nb + ml->rp.n_red), dim3(BVH_THREADS), (uint32_t)lds, c->stream, ml->ev_start, ml->ev_stop, 0, kf, bv, order, pp, ml->rp);
@@ -590,11 +539,11 @@ int launch_match(icp_ctx* c, const QuerySet& q, int* fused_blocks = nullptr, con
     kp.tx = c->tgt.x.as<float>(); kp.ty = c->tgt.y.as<float>(); kp.tz = c->tgt.z.as<float>();
     kp.tcr = c->tgt.cr.as<float>(); kp.tcg = c->tgt.cg.as<float>(); kp.tcb = c->tgt.cb.as<float>();
     kp.mpad = c->tgt.npad; kp.ps = c->ps.as<PoseState>(); kp.pretransformed = q.pretransformed; kp.max_dist = p.max_distance;
-    kp.out = c->matches.as<icp_match_t>(); kp.d2_out = c->d2.as<float>(); kp.best64 = nullptr; kp.nn_raw = nullptr; kp.use_prev = 0; kp.qstate = nullptr; kp.qstate2 = nullptr; kp.incremental = 0; kp.dbg_steps = nullptr; kp.dbg_waves = 0; kp.fault = &c->ps.as<PoseState>()->fault; kp.gx = GxParams{nullptr, nullptr, 0, 0};
+    kp.out = c->matches.as<icp_match_t>(); kp.d2_out = c->d2.as<float>(); kp.best64 = nullptr; kp.nn_raw = nullptr; kp.use_prev = 0; kp.qstate = nullptr; kp.qstate2 = nullptr; kp.incremental = 0; kp.dbg_steps = nullptr; kp.dbg_waves = 0; kp.fault = &c->ps.as<PoseState>()->fault;
     if (p.knn_backend == ICP_KNN_LBVH) {
         kp.nseg = 1;
         // neighbour positions and the incremental search's state in ONE allocation, sections a fixed number of elements apart
-        // (int nn_raw[q_cap] | float4 qstate[q_cap] | float2 qstate2[q_cap]): k_icp_loop is handed a base and a stride
+        // (int nn_raw[q_cap] | float4 qstate[q_cap] | float2 qstate2[q_cap])
         if ((rc = ensure_qpack(c, q.n))) return rc;
         kp.nn_raw = c->nn_raw.as<int>(); kp.use_prev = q.seed_prev ? 1 : 0;
 #if ICP_DEBUG_STEPS
@@ -772,29 +721,6 @@ int launch_post_and_lm(icp_ctx* c, const Cloud& src, const int* sel, int n, icp_
     HIPCK(c, hipGetLastError());
     return ICP_OK;
 }
-
-// How many blocks of k_icp_loop the device holds at once (its waiters wait for blocks of the same grid: the whole grid must be resident).
-template <int DIM, bool WIDE>
-int loop_capacity_of(icp_ctx* c, int* out) {
-    int& cap = c->loop_capacity[(DIM == 6 ? 2 : 0) + (WIDE ? 1 : 0)];
-    if (cap == 0) {
-        int per_cu = 0, cus = 0;
-        const size_t lds = (size_t)LOOP_LDS_ROWS * BVH_THREADS * 8;
-        HIPCK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)&k_icp_loop<DIM, WIDE>, BVH_THREADS, lds));
-        HIPCK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        cap = per_cu * cus > 0 ? per_cu * cus : -1;
-    }
-    *out = cap;
-    return ICP_OK;
-}
-// One k_icp_loop at a time per process: two resident grids that each wait for blocks of their own that the other keeps from being
-// dispatched would wait for each other (bounded, but seconds).  A context that does not get the token runs one launch per iteration.
-std::atomic<int> g_loop_token{0};
-struct LoopToken {
-    bool held = false;
-    bool try_take() { int expect = 0; held = g_loop_token.compare_exchange_strong(expect, 1); return held; }
-    ~LoopToken() { if (held) g_loop_token.store(0); }
-};
 
 int check_ready(icp_ctx* c, bool need_source, bool full_pipeline) {
     const icp_params& p = c->prm;
@@ -1147,12 +1073,7 @@ int icp_ctx_create_on_stream(int device, void* hip_stream, icp_ctx** out) {
     { const char* e = getenv("ICP_HIP_SPIN_REDUCE"); if (e) c->spin_reduce = e[0] == '1'; }
     { const char* e = getenv("ICP_HIP_TIER2"); if (e && e[0] == '0') c->tier2 = false; }
     { const char* e = getenv("ICP_HIP_MERGE"); if (e && e[0] == '0') c->merge_loop = false; }
-    { const char* e = getenv("ICP_HIP_GX"); if (e && e[0] == '0') c->gx_on = false; }
-    { const char* e = getenv("ICP_HIP_GX_START"); if (e && atoi(e) > 1) c->gx_start = atoi(e); }
-    { const char* e = getenv("ICP_HIP_GX_EMPTY"); if (e && atoi(e) > 0) c->gx_empty = atoi(e); }
-    { const char* e = getenv("ICP_HIP_PERSIST"); if (e) c->persist_loop = e[0] == '1'; }
     { const char* e = getenv("ICP_HIP_EXT_EVENTS"); if (e && e[0] == '0') c->ext_events = false; }
-    { const char* e = getenv("ICP_HIP_LOOP_FROM"); if (e) c->loop_from = atoi(e); }
     { const char* e = getenv("ICP_HIP_PRESORT"); if (e && e[0] == '0') c->presort = false; }
     { const char* e = getenv("ICP_HIP_BLOCK_LEVELS"); if (e && e[0] == '0') c->block_levels = false; }
     { const char* e = getenv("ICP_HIP_TRACE"); if (e && e[0] == '1') c->trace = true; }
@@ -1182,7 +1103,7 @@ int icp_ctx_destroy(icp_ctx* c) {
     for (Bvh* b : {&c->bvh6, &c->nrm_bvh}) { release(b->keys); release(b->keys2); release(b->vals); release(b->vals2); release(b->temp); release(b->leaves); release(b->nodes); release(b->lvl); release(b->wbox); }
     release(c->bvh.keys); release(c->bvh.keys2); release(c->bvh.vals); release(c->bvh.vals2); release(c->bvh.temp); release(c->bvh.leaves); release(c->okeys); release(c->okeys2); release(c->ovals); release(c->otemp); release(c->bvh.nodes); release(c->bvh.lvl); release(c->bvh.wbox);
     for (auto& kv : c->levels) release(kv.second);
-    release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->pring); release(c->totals); release(c->dbg_steps); release(c->sums); release(c->gx_slots); release(c->gx_hdr);
+    release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->totals); release(c->dbg_steps); release(c->sums);
     release(c->lm_state); release(c->lm_partials); release(c->lm_sums);
     for (auto& pl : c->gicp_n) for (DevBuf& d : pl) release(d);
     for (DevBuf& d : c->col_grad) release(d);
@@ -1204,9 +1125,6 @@ int icp_ctx_destroy(icp_ctx* c) {
     if (c->pinned) (void)hipHostFree(c->pinned);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->build_ev) if (e) (void)hipEventDestroy(e);
-    if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return ICP_OK;
@@ -1342,8 +1260,8 @@ int icp_correspond(icp_ctx* c, const float pose[16], icp_match_t* out, double* s
 }
 
 // The fused matcher driven launch by launch with caller-dictated poses: launch 0 unseeded, launch j > 0 seeded + incremental exactly
-// as iteration j of icp_run runs it, in the form icp_run takes for the configuration (k_icp_loop, the merged ring launches or the
-// separate launches: same kernel, same buffers, same grid); the last launch's records come back in source order.
+// as iteration j of icp_run runs it, in the form icp_run takes for the configuration (the merged ring launches or the separate
+// launches: same kernel, same buffers, same grid); the last launch's records come back in source order.
 int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_t* out, float* d2_out) {
     if (!c || !poses || n_poses <= 0) { if (c) c->err = "icp_match_seeded: bad argument"; return ICP_ERR_INVALID_ARG; }
     const icp_params& p = c->prm;
@@ -1360,41 +1278,12 @@ int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_
     const Cloud* cloud = nullptr; int n = 0;
     if ((rc = get_sorted_level(c, 0, &cloud, &n))) return rc;
     struct Keep { icp_ctx* c; ~Keep() { c->keep_fused_records = false; } } keep{c};
-    const bool one_launch = c->persist_loop && c->merge_loop && p.metric == ICP_METRIC_POINT_TO_PLANE;
-    if (one_launch) {
-        // what icp_run launches for this configuration: k_icp_loop, all the launches' worth of iterations in ONE launch -- here with every pose
-        // slot filled in up front (replica 0 of each; nobody reduces, nobody solves), the last iteration writing its records
-        const int nb = fused_nblocks(n);
-        const size_t slot_bytes = (size_t)(n_poses + 1) * POSE_REPLICAS * POSE_REPLICA_STRIDE;
-        if ((rc = ensure(c, c->ring, slot_bytes + 64))) return rc;
-        if ((rc = ensure(c, c->pring, (size_t)PRING_DEPTH * NSUM_USED * nb * 8))) return rc;
-        PoseState* slots = c->ring.as<PoseState>(); int* fault = (int*)(c->ring.as<char>() + slot_bytes);
-        HIPCK(c, hipMemsetAsync(fault, 0, 64, c->stream));
-        std::vector<PoseState> hp((size_t)n_poses);
-        for (int j = 0; j < n_poses; j++) {
-            memset(&hp[(size_t)j], 0, sizeof(PoseState)); memcpy(hp[(size_t)j].pose, poses + (size_t)16 * j, 64); normal_matrix_from_pose(hp[(size_t)j].pose, hp[(size_t)j].nmat);
-            HIPCK(c, hipMemcpyAsync(loop_slot(slots, j, 0), &hp[(size_t)j], sizeof(PoseState), hipMemcpyHostToDevice, c->stream));
-        }
-        LoopParams L; memset(&L, 0, sizeof(L));
-        L.iters = n_poses; L.first = 0; L.seed_first = 0; L.slots = slots; L.totals = nullptr; L.pring = c->pring.as<unsigned long long>(); L.nb = nb;
-        L.dictated = 1; L.stats = nullptr; L.n_src = n; L.abort_word = fault; L.record_last = 1; L.clocks = nullptr;
-        c->keep_fused_records = true;
-        QuerySet q{cloud, nullptr, n, 0, p.color_icp != 0, false, nullptr};
-        MergeLaunch ml; ml.loop = &L; ml.slot = nullptr; ml.partials = nullptr; memset(&ml.rp, 0, sizeof(ml.rp));
-        int fused = 0;
-        if ((rc = launch_match(c, q, &fused, &ml))) return rc;
-        if (!fused) { c->err = "icp_match_seeded: the matcher did not take the fused path"; return ICP_ERR_INVALID_ARG; }
-        int hf = 0;
-        HIPCK(c, hipMemcpyAsync(&hf, fault, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCK(c, hipStreamSynchronize(c->stream));           // (hp is read by the copies above)
-        if (hf) { c->err = "icp_match_seeded: k_icp_loop gave up waiting"; return ICP_ERR_HIP; }
-    }
     // ring: what run_loop launches for this configuration one launch per iteration (the merged loop, dev_solve.hpp "the ring form"):
     // k_knn_bvh_post_ring, launch j > 0 with the reducer of launch j - 1 in its first NSUM_USED blocks and the matcher blocks behind them.
     // Every matcher waits on slot j, filled here up front with the caller's pose j; the reducers fold the previous launch's partials
     // (the same double buffering as run_loop) and publish into a scratch slot nobody waits on.  Otherwise (point-to-point, ICP_HIP_MERGE=0):
     // the separate k_knn_bvh_post launches, each at the pose written in front of it.
-    const bool ring = !one_launch && c->merge_loop && !c->lm_on && p.metric == ICP_METRIC_POINT_TO_PLANE;
+    const bool ring = c->merge_loop && !c->lm_on && p.metric == ICP_METRIC_POINT_TO_PLANE;
     std::vector<unsigned long long> slot_image;              // (read by the copy below until the synchronisation at the end)
     PoseState* slots = nullptr; unsigned long long* trows = nullptr; int* run_fault = nullptr;
     if (ring) {
@@ -1420,7 +1309,7 @@ int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_
         hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, nullptr, slots, 0, trows, n_rows * NSUM, run_fault, 16);
         HIPCK(c, hipGetLastError());
     }
-    for (int j = 0; !one_launch && j < n_poses; j++) {
+    for (int j = 0; j < n_poses; j++) {
         if (!ring && (rc = write_pose(c, poses + (size_t)16 * j))) return rc;
         c->keep_fused_records = (j == n_poses - 1);
         QuerySet q{cloud, nullptr, n, 0, p.color_icp != 0, j > 0, nullptr};
@@ -1559,17 +1448,17 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     if (robust && (rc = robust_prepare(c, iters))) return rc;
     // page-locked staging for the whole run up front: [pose state up | per-iteration records down | pose state down]
     const size_t pin_stats = 256, pin_pose = pin_stats + (((size_t)iters * sizeof(icp_iter_stats) + 255) & ~(size_t)255);
-    const size_t pin_lm = (pin_pose + 512 + (size_t)(iters + 1) * 8 + 255) & ~(size_t)255;      // [LM records down] behind it, non-linear runs only
-    if ((rc = ensure_pinned(c, lm ? pin_lm + (size_t)iters * sizeof(icp_lm_summary) : pin_pose + 512 + (size_t)(iters + 1) * 8))) return rc;
+    const size_t pin_lm = pin_pose + 512;                       // [LM records down] behind it, non-linear runs only
+    if ((rc = ensure_pinned(c, lm ? pin_lm + (size_t)iters * sizeof(icp_lm_summary) : pin_pose + 512))) return rc;
     if (lm && (rc = ensure(c, c->lm_sums, (size_t)iters * sizeof(icp_lm_summary)))) return rc;
     struct KeepRecords { icp_ctx* c; bool prev; ~KeepRecords() { c->keep_fused_records = prev; } } keep_records{c, c->keep_fused_records};
     if (lm) c->keep_fused_records = true;   // (the fused matcher writes its records for k_lm_eval)
     float pose_in[16]; memcpy(pose_in, pose_inout, 64);        // the record of an empty iteration 0 carries the incoming pose
     if ((rc = write_pose(c, pose_inout))) return rc;
-    // the records of the run, and behind them (merged / one-launch loops) the final pose state, the fault word and the device clocks:
-    // ONE block, ONE copy back -- laid out like the page-locked block it lands in (pin_stats .. pin_pose .. + 128 .. + 192)
+    // the records of the run, and behind them (merged loop) the final pose state and the fault word: ONE block, ONE copy back --
+    // laid out like the page-locked block it lands in (pin_stats .. pin_pose .. + 128 .. + 192)
     const size_t stats_pad = pin_pose - pin_stats;
-    if ((rc = ensure(c, c->stats, stats_pad + 192 + (size_t)(iters + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->stats, stats_pad + 192))) return rc;
     // (every record of an iteration with work is written in full by k_reduce_solve; empty iterations are filled in on the host)
     if ((rc = ensure_events(c, (size_t)iters * 4 + 2))) return rc;
     // resolve selections up front (uploads) so the loop itself is launch-only
@@ -1585,63 +1474,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     bool merged = !lm && !robust && c->merge_loop && !single && iters >= 2 && sorted_levels && c->fuse_post && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
     for (int i = 0; merged && i < iters; i++) if (ns[i] <= 0) merged = false;
     PoseState* slots = nullptr; unsigned long long* trows = nullptr; int* run_fault = nullptr;
-    // k_icp_loop (dev_persist.hpp): all iterations of a resolution level in ONE launch, the waves resident from iteration to iteration.
-    // Needs the whole grid on the device at once (its blocks wait for each other) and the device to itself: checked against the kernel's
-    // occupancy; a context marked shared, or one that finds another context's loop in flight, runs one launch per iteration instead.
-    struct Seg { int i0, i1; };
-    std::vector<Seg> segs;
-    LoopToken token;
-    bool persist = merged && c->persist_loop && !c->shared_gpu;
-    long long* d_clocks = nullptr;
-    // The first loop_from iterations -- every query walks, a launch lasts 50-150 us, and the walk is ~5 % slower in k_icp_loop (it pays for
-    // its residency with a few spilled registers) -- run one launch per iteration in the merged form; k_icp_loop takes over from there.
-    int loop_from = c->loop_from < 0 ? 0 : c->loop_from;
-    if (persist && loop_from >= iters) persist = false;
-    if (persist) {
-        Bvh& tb = p.color_icp ? c->bvh6 : c->bvh;
-        int cap = -1;
-        if (!tb.valid) persist = false;                    // (built on first use: the first run of such a context takes the per-launch loop)
-        else if (p.color_icp) { if ((rc = tb.Lq <= 8 ? loop_capacity_of<6, false>(c, &cap) : loop_capacity_of<6, true>(c, &cap))) return rc; }
-        else { if ((rc = tb.Lq <= 8 ? loop_capacity_of<3, false>(c, &cap) : loop_capacity_of<3, true>(c, &cap))) return rc; }
-        int nbmax = 1;
-        for (int i = 0; i < iters; i++) { const int nb = fused_nblocks(ns[i]); if (nb > nbmax) nbmax = nb; }
-        for (int i = loop_from; persist && i < iters; ) {
-            int j = i + 1;
-            while (j < iters && clouds[j] == clouds[i] && ns[j] == ns[i] && factors[j] == factors[i]) j++;
-            const int nb = fused_nblocks(ns[i]);
-            if (nb + LOOP_RED + 1 > cap) persist = false;      // (the reducer's two-wave blocks sit in the holes the matcher grid leaves: dev_persist.hpp)
-            if (nb > nbmax) nbmax = nb;
-            segs.push_back(Seg{i, j});
-            i = j;
-        }
-        if (persist && !token.try_take()) persist = false;
-        if (persist) {
-            // every buffer the launches below touch is sized for the largest level NOW: an allocation that grows between two launches frees its
-            // old block, and hipFree waits for the device -- for a reducer kernel that is itself waiting for the matcher launch still to come
-            { int nmax = 1; for (int i = 0; i < iters; i++) if (ns[i] > nmax) nmax = ns[i];
-              if ((rc = ensure_match_buffers(c, nmax))) return rc;
-              if ((rc = ensure_qpack(c, nmax))) return rc;
-              if ((rc = ensure(c, c->partials, (size_t)(nbmax > POST_BLOCKS ? nbmax : POST_BLOCKS) * NSUM * 8))) return rc;
-              if ((rc = ensure(c, c->partials2, (size_t)(nbmax > POST_BLOCKS ? nbmax : POST_BLOCKS) * NSUM * 8))) return rc; }
-            size_t pring_granules = 0;
-            for (const Seg& sg : segs) pring_granules += (size_t)PRING_DEPTH * NSUM_USED * (fused_nblocks(ns[sg.i0]));
-            if ((rc = ensure(c, c->pring, pring_granules * 8))) return rc;
-            HIPCK(c, hipMemsetAsync(c->pring.p, 0xFF, pring_granules * 8, c->stream));
-            if (!c->stream2) {
-                HIPCK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-                HIPCK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-                HIPCK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-            }
-            // its rings: [pose slots x POSE_REPLICAS | totals]; fault word and clocks sit behind the records (see above)
-            const size_t slot_bytes = (size_t)(iters + 1) * POSE_REPLICAS * POSE_REPLICA_STRIDE, tot_bytes = (size_t)iters * TOTALS_ROW * 8;
-            if ((rc = ensure(c, c->ring, slot_bytes + tot_bytes))) return rc;
-            slots = c->ring.as<PoseState>(); trows = (unsigned long long*)(c->ring.as<char>() + slot_bytes);
-            run_fault = (int*)(c->stats.as<char>() + stats_pad + 128); d_clocks = (long long*)(c->stats.as<char>() + stats_pad + 192);
-            const int n_init = (iters + 1) * POSE_REPLICAS * 16 + iters * TOTALS_ROW + 16 + (iters + 1) * 2;
-            hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, c->ps.as<PoseState>(), slots, iters + 1, trows, iters * TOTALS_ROW, run_fault, 16 + (iters + 1) * 2);
-        }
-    }
-    if (merged && !persist) {
+    if (merged) {
         static_assert(sizeof(PoseState) == 128, "a pose slot is 16 granules");
         const size_t slot_bytes = (size_t)(iters + 1) * POSE_REPLICAS * POSE_REPLICA_STRIDE, tot_bytes = (size_t)iters * NSUM * 8;
         int nbmax = POST_BLOCKS;
@@ -1649,15 +1482,12 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
         if ((rc = ensure(c, c->ring, slot_bytes + tot_bytes))) return rc;
         if ((rc = ensure(c, c->partials, (size_t)nbmax * NSUM * 8))) return rc;
         if ((rc = ensure(c, c->partials2, (size_t)nbmax * NSUM * 8))) return rc;
-        if (!p.color_icp && (rc = ensure_gx(c, nbmax))) return rc;
         slots = c->ring.as<PoseState>(); trows = (unsigned long long*)(c->ring.as<char>() + slot_bytes); run_fault = (int*)(c->stats.as<char>() + stats_pad + 128);
         const int n_init = (iters + 1) * POSE_REPLICAS * 16 + iters * NSUM + 16;
         hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, c->ps.as<PoseState>(), slots, iters + 1, trows, iters * NSUM, run_fault, 16);      // (both rings are reset: nothing survives an aborted run)
     }
     // Stage timing (TimeMeasure.h:20-26).  A HIP event costs ~4 us of stream time, two to three per iteration are ~10 % of a
     // 0.07 ms iteration: mode N > 1 brackets only every Nth iteration (offset rotating from run to run) and scales the sums.
-    // (k_icp_loop: no events inside a launch -- its reducer block 0 leaves the 100 MHz clock at every pose it publishes instead:
-    //  "match" of iteration i = the time from pose i to pose i + 1, every iteration, at no cost.)
     // Event slots: 4 per iteration (start, after match, after post, end) + run start / run end.  In the merged loop an iteration is ONE
     // launch (its reduce + solve happen inside the next one): "match" is that launch, "solve" only the closing reducer-only launch.
     const int tmode = c->stage_timing;
@@ -1665,7 +1495,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     for (int i = 0; i < iters; i++) sampled[i] = tmode == 1 || (tmode > 1 && (i + (int)(c->timing_phase % (unsigned)tmode)) % tmode == 0);
     c->timing_phase++;
     auto E = [&](int i, int k) { return c->events[(size_t)2 + 4 * i + k]; };
-    auto end_event = [&](int i) { return (merged && i < (persist ? loop_from : iters) - 1) ? E(i, 1) : E(i, 3); };
+    auto end_event = [&](int i) { return (merged && i < iters - 1) ? E(i, 1) : E(i, 3); };
     auto start_event = [&](int i) { return (i > 0 && sampled[i - 1] && !(merged && c->ext_events)) ? end_event(i - 1) : E(i, 0); };
     auto ring_params = [&](int i) {                      // the reducer of iteration i - 1, riding in launch i (i = iters: the closing launch)
         RingParams rp; memset(&rp, 0, sizeof(rp));
@@ -1681,8 +1511,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     };
     if (!merged && (rc = rearm_handover(c))) return rc;
     HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    const int m_end = persist ? loop_from : iters;       // iterations [0, m_end) run one launch each
-    for (int i = 0; i < m_end; i++) {
+    for (int i = 0; i < iters; i++) {
         icp_iter_stats* d_st = c->stats.as<icp_iter_stats>() + i;
         const bool ev = sampled[i] != 0;
         const bool ext_ev = ev && merged && ns[i] > 0 && c->ext_events;      // merged form: the launch's own start / stop times, no bracket on the stream
@@ -1716,45 +1545,15 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
             hipLaunchKernelGGL(k_rmse_finish, dim3(1), dim3(64), 0, c->stream, c->rmse_partials.as<double>(), 256, &d_st->rmse);
         }
         if (fontana && (rc = enqueue_fontana(c, &d_st->benchmark_error))) return rc;
-        if (merged && i == m_end - 1) {                  // the closing launch: reducer of the last of these iterations, nothing behind it to ride in
-            hipLaunchKernelGGL(k_ring_reduce_solve, dim3(NSUM_USED), dim3(RING_THREADS), 0, c->stream, ring_params(m_end));
+        if (merged && i == iters - 1) {                  // the closing launch: reducer of the last iteration, nothing behind it to ride in
+            hipLaunchKernelGGL(k_ring_reduce_solve, dim3(NSUM_USED), dim3(RING_THREADS), 0, c->stream, ring_params(iters));
             HIPCK(c, hipGetLastError());
         }
-        if (ev && !(merged && i < m_end - 1)) HIPCK(c, hipEventRecord(E(i, 3), c->stream));
-    }
-    if (persist) {
-        // every level: the reducer on the second stream (forked off here, joined below), the matcher grid on the context's; each level has
-        // its own section of the partial ring, so that a level's matcher never writes where the level before is still being re-armed
-        HIPCK(c, hipEventRecord(c->ev_fork, c->stream));
-        HIPCK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        size_t pring_off = 0;
-        for (const Seg& sg : segs) {
-            const int i = sg.i0, nb = fused_nblocks(ns[i]);
-            LoopParams L; memset(&L, 0, sizeof(L));
-            L.iters = sg.i1 - sg.i0; L.first = i; L.seed_first = (i > 0 && i == loop_from && factors[i] == factors[i - 1] && ns[i - 1] == ns[i] && clouds[i] == clouds[i - 1]) ? 1 : 0; L.slots = slots; L.totals = trows; L.pring = c->pring.as<unsigned long long>() + pring_off; L.nb = nb;
-            { const char* e = getenv("ICP_HIP_LOOP_PRESLEEP"); L.presleep_eighths = e ? atoi(e) : 5; }
-            { const char* e = getenv("ICP_HIP_LOOP_WAVESLEEP"); L.wave_presleep_eighths = e ? atoi(e) : 0; }
-            L.dictated = 0; L.stats = c->stats.as<icp_iter_stats>(); L.n_src = ns[i]; L.abort_word = run_fault; L.record_last = 0; L.clocks = d_clocks;
-            L.final_out = (PoseState*)(c->stats.as<char>() + stats_pad); L.final_g = iters;
-#if ICP_DEBUG_TIMES
-            if ((rc = ensure(c, c->dbg_steps, (size_t)(ns[i] > 65536 ? ns[i] : 65536) * 4))) return rc;
-            L.dbg = c->dbg_steps.as<int>(); L.dbg_waves = nb * (BVH_THREADS / WAVE); { const char* e = getenv("ICP_HIP_DBG_ITER"); L.dbg_iter = e ? atoi(e) : -1; }
-#endif
-            pring_off += (size_t)PRING_DEPTH * NSUM_USED * nb;
-            QuerySet q{clouds[i], sels[i], ns[i], 0, p.color_icp != 0, false, orders[i]};
-            MergeLaunch ml; ml.loop = &L; ml.slot = nullptr; ml.partials = nullptr; memset(&ml.rp, 0, sizeof(ml.rp));
-            int fused = 0;
-            if ((rc = launch_match(c, q, &fused, &ml))) return rc;      // (first: nothing on the host may block between the two launches of a level)
-            if (!fused) { c->err = "k_icp_loop: the matcher did not take the fused path"; return ICP_ERR_HIP; }
-            hipLaunchKernelGGL(k_icp_loop_reducer, dim3(LOOP_RED + 1), dim3(RING_THREADS), 0, c->stream2, L);      // 2 x 34 fold blocks + the solver
-            HIPCK(c, hipGetLastError());
-        }
-        HIPCK(c, hipEventRecord(c->ev_join, c->stream2));
-        HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+        if (ev && !(merged && i < iters - 1)) HIPCK(c, hipEventRecord(E(i, 3), c->stream));
     }
     HIPCK(c, hipEventRecord(c->events[1], c->stream));
     std::vector<icp_iter_stats> hs((size_t)iters);
-    if (merged) HIPCK(c, hipMemcpyAsync((char*)c->pinned + pin_stats, c->stats.p, stats_pad + 192 + (persist ? (size_t)(iters + 1) * 8 : 0), hipMemcpyDeviceToHost, c->stream));      // records | final pose state | fault | clocks
+    if (merged) HIPCK(c, hipMemcpyAsync((char*)c->pinned + pin_stats, c->stats.p, stats_pad + 192, hipMemcpyDeviceToHost, c->stream));      // records | final pose state | fault
     else {
         HIPCK(c, hipMemcpyAsync((char*)c->pinned + pin_stats, c->stats.p, (size_t)iters * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
         HIPCK(c, hipMemcpyAsync((char*)c->pinned + pin_pose, c->ps.p, sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));
@@ -1766,19 +1565,18 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     for (int i = 0; robust && i < iters; i++) if (ns[i] <= 0) rob[(size_t)i] = icp_robust_stats{0, 0, -1.f, -1.f};      // (no work: nothing was written)
     c->rob_last.swap(rob);
     if (merged) {
-        if (persist) c->loop_runs++; else c->merged_runs++;
+        c->merged_runs++;
         const PoseState* hp = (const PoseState*)((char*)c->pinned + pin_pose);
         const int rf = *(const int*)((char*)c->pinned + pin_pose + 128);
         if (hp->fault || rf) {
             // a pivot of the 6 x 6 system failed the rank test (the eigen fallback lives in k_reduce_solve only), or a bounded wait ran out:
             // the same run again, from the incoming pose, with the separate launches
-            c->merged_fallbacks++; c->gx_dirty = true;     // (a run cut short may have left claimed slots in the outboxes)
-            if (c->trace) fprintf(stderr, "[icp_hip] %s gave up: slot fault %d, abort word %d -> the run again with separate launches\n", persist ? "k_icp_loop" : "merged loop", hp->fault, rf);
+            c->merged_fallbacks++;
+            if (c->trace) fprintf(stderr, "[icp_hip] merged loop gave up: slot fault %d, abort word %d -> the run again with separate launches\n", hp->fault, rf);
             guard.ok = true;                                 // synchronised
             memcpy(pose_inout, pose_in, 64);
             const bool m0 = c->merge_loop;
             c->merge_loop = false;
-            token.~LoopToken(); token.held = false;
             const int rc2 = run_loop(c, pose_inout, stats, max_stats, n_run, single);
             c->merge_loop = m0;
             return rc2;
@@ -1786,7 +1584,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     }
     memcpy(hs.data(), (char*)c->pinned + pin_stats, (size_t)iters * sizeof(icp_iter_stats));
     memcpy(pose_inout, ((const PoseState*)((char*)c->pinned + pin_pose))->pose, 64);
-    if (((const PoseState*)((char*)c->pinned + pin_pose))->fault) { c->gx_dirty = true; c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
+    if (((const PoseState*)((char*)c->pinned + pin_pose))->fault) { c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
     int status = ICP_OK;
     if (lm) {
         c->lm_last.resize((size_t)iters);
@@ -1803,36 +1601,24 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     }
     if (n_run) *n_run = iters;
     icp_timing& t = c->timing; memset(&t, 0, sizeof(t)); t.iterations = iters;
-    int n_sampled = 0;
     c->it_match_ms.assign((size_t)iters, -1.f); c->it_post_ms.assign((size_t)iters, -1.f); c->it_solve_ms.assign((size_t)iters, -1.f);
     double ev_match = 0, ev_post = 0, ev_solve = 0; int n_ev = 0;
-    for (int i = 0; i < m_end; i++) {
+    for (int i = 0; i < iters; i++) {
         if (!sampled[i]) continue;
         n_ev++;
         float a = 0, b = 0, d = 0;
         HIPCK(c, hipEventElapsedTime(&a, start_event(i), E(i, 1)));
         if (post_event[i]) HIPCK(c, hipEventElapsedTime(&b, E(i, 1), E(i, 2)));
-        if (!(merged && i < m_end - 1)) HIPCK(c, hipEventElapsedTime(&d, post_event[i] ? E(i, 2) : E(i, 1), E(i, 3)));
+        if (!(merged && i < iters - 1)) HIPCK(c, hipEventElapsedTime(&d, post_event[i] ? E(i, 2) : E(i, 1), E(i, 3)));
         ev_match += a; ev_post += b; ev_solve += d;
         c->it_match_ms[(size_t)i] = a; c->it_post_ms[(size_t)i] = b; c->it_solve_ms[(size_t)i] = d;
         if (c->trace) fprintf(stderr, "[icp_hip] it %2d  n %d  match %.4f  post %.4f  solve %.4f ms\n", i, ns[i], a, b, d);
     }
-    if (n_ev > 0) {                                       // sampled: scale to all the iterations that ran one launch each
-        const double f = (double)m_end / n_ev;
+    if (n_ev > 0) {                                       // sampled: scale to all the iterations
+        const double f = (double)iters / n_ev;
         t.match_ms += ev_match * f; t.weight_reject_build_ms += ev_post * f; t.solve_ms += ev_solve * f;
     }
-    n_sampled = n_ev;
-    if (persist) {                                        // k_icp_loop: the device's own clock at every published pose, 100 MHz ticks, every iteration
-        const long long* clk = (const long long*)((char*)c->pinned + pin_pose + 192);
-        for (int i = loop_from; i < iters; i++) {
-            const float a = (float)((double)(clk[i + 1] - clk[i]) * 1e-5);
-            t.match_ms += a; c->it_match_ms[(size_t)i] = a; c->it_post_ms[(size_t)i] = 0.f; c->it_solve_ms[(size_t)i] = 0.f;
-            if (c->trace) fprintf(stderr, "[icp_hip] it %2d  n %d  iteration %.4f ms (k_icp_loop)\n", i, ns[i], a);
-        }
-        n_sampled += iters - loop_from;
-        if (n_ev == 0 && m_end > 0) { const double f = (double)iters / (iters - loop_from); t.match_ms *= f; }      // nothing timed in front: the loop's iterations stand for all
-    }
-    t.sampled_iterations = n_sampled;
+    t.sampled_iterations = n_ev;
     float tot = 0; HIPCK(c, hipEventElapsedTime(&tot, c->events[0], c->events[1])); t.total_ms = tot;
     if (status != ICP_OK) c->err = "no valid correspondences in at least one iteration (reference would hang in ASSERT)";
     guard.ok = true;                                     // synchronised above; `status` reports empty iterations, not a HIP failure
@@ -2054,7 +1840,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
     kb.tx = c->tgt.x.as<float>(); kb.ty = c->tgt.y.as<float>(); kb.tz = c->tgt.z.as<float>();
     kb.tcr = c->tgt.cr.as<float>(); kb.tcg = c->tgt.cg.as<float>(); kb.tcb = c->tgt.cb.as<float>();
     kb.mpad = c->tgt.npad; kb.ps = d_ps; kb.pretransformed = 0; kb.max_dist = p.max_distance; kb.nseg = 1;
-    kb.fault = &d_ps->fault; kb.gx = GxParams{nullptr, nullptr, 0, 0};
+    kb.fault = &d_ps->fault;
     auto view3 = [&]() { BvhViewT<3> v; Bvh& b = c->bvh; v.leaves = b.leaves.as<BvhLeafT<3>>(); v.nodes = b.nodes.as<BvhNodeT<3>>(); v.n_valid = b.n_valid; v.Lp = b.Lp; v.tgt = target_coords3(c);
                           v.qnodes = b.qnodes.as<BvhQuadT<3>>(); v.Lq = b.Lq; v.recs = b.recs.as<TgtRec>(); v.pos_of = b.pos_of.as<int>(); return v; };
     auto view6 = [&]() { BvhViewT<6> v; Bvh& b = c->bvh6; v.leaves = b.leaves.as<BvhLeafT<6>>(); v.nodes = b.nodes.as<BvhNodeT<6>>(); v.n_valid = b.n_valid; v.Lp = b.Lp; v.tgt = target_coords6(c);
@@ -2520,15 +2306,15 @@ int icp_debug_ring_times(icp_ctx* c, int32_t* out, int32_t n) {     // developme
     return ICP_ERR_INVALID_ARG;
 #endif
 }
-int icp_debug_gx_counters(icp_ctx* c, uint32_t* out16, int32_t reset) {     // development builds (ICP_DEBUG_TIMES): events of the hand-over between blocks since the last reset
+int icp_debug_dev_counters(icp_ctx* c, uint32_t* out16, int32_t reset) {     // development builds (ICP_DEBUG_TIMES): the device's event counters (g_dev_counts) since the last reset
 #if ICP_DEBUG_TIMES
     if (!c || !out16) return ICP_ERR_INVALID_ARG;
     int rc;
     if ((rc = set_device(c))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipMemcpyFromSymbol(out16, HIP_SYMBOL(icpdev::g_gx_dbg), 64));
+    HIPCK(c, hipMemcpyFromSymbol(out16, HIP_SYMBOL(icpdev::g_dev_counts), 64));
     if (reset == 2) HIPCK(c, hipMemcpyFromSymbol(out16, HIP_SYMBOL(icpdev::g_walk_trace), 256));      // (reset == 2: the caller's buffer has 64 words and wants the trace of the last sparse walk instead, tools/dev_walk_trace.py)
-    if (reset) { uint32_t z[16] = {0}; HIPCK(c, hipMemcpyToSymbol(HIP_SYMBOL(icpdev::g_gx_dbg), z, 64)); }
+    if (reset) { uint32_t z[16] = {0}; HIPCK(c, hipMemcpyToSymbol(HIP_SYMBOL(icpdev::g_dev_counts), z, 64)); }
     return ICP_OK;
 #else
     (void)c; (void)out16; (void)reset;
@@ -2569,7 +2355,7 @@ int icp_debug_live_bytes(int64_t* out) {
 }
 int icp_debug_counters(icp_ctx* c, int32_t* merged_runs, int32_t* merged_fallbacks) {
     if (!c) return ICP_ERR_INVALID_ARG;
-    if (merged_runs) *merged_runs = c->merged_runs + c->loop_runs;
+    if (merged_runs) *merged_runs = c->merged_runs;
     if (merged_fallbacks) *merged_fallbacks = c->merged_fallbacks;
     return ICP_OK;
 }

@@ -135,8 +135,8 @@ int icp_match(icp_ctx* ctx, const float pose[16], icp_match_t* out, float* d2_ou
  * neighbours and search state (verify-and-skip tiers, shared walks, spread start: whatever knn_incremental and the build enable),
  * i.e. launch j is iteration j of a run whose poses are dictated by the caller, in the form icp_run takes for the configuration:
  * point-to-plane by default = the merged loop's launches (k_knn_bvh_post_ring: launch j > 0 carries a reducer of launch j - 1 in its
- * first blocks, every matcher block reads pose j from its slot of the pose ring); point-to-plane with ICP_HIP_PERSIST=1 = ONE k_icp_loop
- * launch; point-to-point, ICP_HIP_MERGE=0 or the non-linear optimiser = one k_knn_bvh_post launch per pose.  A bounded wait of the
+ * first blocks, every matcher block reads pose j from its slot of the pose ring); point-to-point, ICP_HIP_MERGE=0 or the non-linear
+ * optimiser = one k_knn_bvh_post launch per pose.  A bounded wait of the
  * device that ran out returns ICP_ERR_HIP.  out / d2_out (optional) receive the LAST launch's
  * records in source order: the Match after weighting + rejection (= what icp_correspond returns; with rejection 0 and constant
  * weights the raw {idx, 1} / {-1, 0} of queryMatches) and the winning squared distance (FLT_MAX when there was no candidate).

@@ -1,10 +1,9 @@
-"""The three forms of the point-to-plane loop -- "loop": k_icp_loop, all iterations of a level in ONE launch beside its reducer kernel
-(dev_persist.hpp; ICP_HIP_PERSIST=1); "merged": one launch per iteration with the reducer of iteration i - 1 riding in front of the
-matcher of iteration i (dev_solve.hpp "the ring form"; the default); "separate": k_reduce_solve as a launch of its own (ICP_HIP_MERGE=0).
-In all of them the pose and the sums travel through self-validating granules or kernel boundaries, the fold order and the solve are
-the same operations, so every iteration's pose and valid count must be equal bit for bit -- any stale or torn hand-over shows up as a
-different pose.  Plus the routes out of the first two (rank-deficient system -> repeated with the separate launches; an iteration
-without correspondences) and the re-arming of k_reduce_solve's own hand-over slots."""
+"""The two forms of the point-to-plane loop -- "merged": one launch per iteration with the reducer of iteration i - 1 riding in front
+of the matcher of iteration i (dev_solve.hpp "the ring form"; the default); "separate": k_reduce_solve as a launch of its own
+(ICP_HIP_MERGE=0).  In both the pose and the sums travel through self-validating granules or kernel boundaries, the fold order and the
+solve are the same operations, so every iteration's pose and valid count must be equal bit for bit -- any stale or torn hand-over shows
+up as a different pose.  Plus the routes out of the merged form (rank-deficient system -> repeated with the separate launches; an
+iteration without correspondences) and the re-arming of k_reduce_solve's own hand-over slots."""
 import ctypes as C
 import os
 import numpy as np
@@ -15,7 +14,7 @@ f32 = np.float32
 LBVH = 1
 
 
-FORMS = ("loop", "hybrid", "merged", "separate")      # hybrid: merged launches for the first 7 iterations, k_icp_loop from there (ICP_HIP_LOOP_FROM)
+FORMS = ("merged", "separate")
 
 
 def make_ctx(factory, form, **params):
@@ -23,8 +22,7 @@ def make_ctx(factory, form, **params):
         form = "merged"
     elif form is False:
         form = "separate"
-    env = {"ICP_HIP_MERGE": "0" if form == "separate" else "1", "ICP_HIP_PERSIST": "1" if form in ("loop", "hybrid") else "0",
-           "ICP_HIP_LOOP_FROM": "7" if form == "hybrid" else "0"}                                              # read once, at icp_ctx_create
+    env = {"ICP_HIP_MERGE": "0" if form == "separate" else "1"}                                              # read once, at icp_ctx_create
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
@@ -69,10 +67,6 @@ def test_merged_loop_fullsize_is_bit_identical_to_separate_launches(gpu_ctx_fact
             out.append((pose, recs))
         runs, fallbacks = counters(c)
         assert (runs, fallbacks) == ((0, 0) if form == "separate" else (3, 0))
-        if form in ("loop", "hybrid"):                          # its iteration times come from the device's own clock, every iteration
-            a, _, _ = c.iteration_times()
-            lf = 7 if form == "hybrid" else 0                   # (iterations in front of it run one launch each: event-sampled)
-            assert len(a) == 50 and (a[lf:] > 0).all() and a[lf] > a[-1]
         t = c.timing()
         assert t["iterations"] == 50 and t["match_ms"] > 0
         c.close()
@@ -117,7 +111,7 @@ def test_rank_deficient_system_leaves_the_merged_loop(gpu_ctx_factory, bunny):
     sp = (tp[:40] + f32(1.0)).copy(); sn = tn[:40].copy()          # 39 sources a metre away from everything ...
     sp[7] = tp[7] + f32(1e-4)                                      # ... and one on the surface
     res = []
-    for merge in ("loop", "separate", "merged", "separate"):      # (results 0 and 2 against 1)
+    for merge in ("separate", "merged", "separate"):              # (result 1 against 0)
         c = make_ctx(gpu_ctx_factory, merge, max_distance=0.0003, n_iterations=6, rejection=0)
         c.set_target(tp, tn); c.set_source(sp, sn)
         pose, recs, rc = c.run(np.eye(4), check=False)
@@ -126,10 +120,9 @@ def test_rank_deficient_system_leaves_the_merged_loop(gpu_ctx_factory, bunny):
         assert rc2 == rc and np.array_equal(pose2, pose)
         c.close()
     assert res[0][2][0]["n_valid"] == 1
-    for a in (0, 2):
-        assert res[a][0] == res[1][0] and np.array_equal(res[a][1], res[1][1])
-        assert_same_run(res[a][2], res[1][2])
-        assert res[a][3] == (1, 1)                              # one run in that form, one fallback (counted before the second run)
+    assert res[1][0] == res[0][0] and np.array_equal(res[1][1], res[0][1])
+    assert_same_run(res[1][2], res[0][2])
+    assert res[1][3] == (1, 1)                                  # one run in the merged form, one fallback (counted before the second run)
 
 
 def test_iteration_without_correspondences_in_the_merged_loop(gpu_ctx_factory, bunny):
@@ -137,7 +130,7 @@ def test_iteration_without_correspondences_in_the_merged_loop(gpu_ctx_factory, b
     ICPOptimizer.h:680) -- inside the merged loop, without a fallback."""
     from icp_amd import binding
     res = []
-    for merge in ("loop", "separate", "merged"):
+    for merge in ("separate", "merged"):
         c = make_ctx(gpu_ctx_factory, merge, max_distance=1e-12, n_iterations=4)
         c.set_target(bunny["tgt_pts"], bunny["tgt_nrm"]); c.set_source(bunny["src_pts"] + f32(3.0), bunny["src_nrm"])
         pose, recs, rc = c.run(np.eye(4), check=False)
@@ -145,8 +138,8 @@ def test_iteration_without_correspondences_in_the_merged_loop(gpu_ctx_factory, b
         assert all(r["status"] == binding.ERR_NO_CORRESPONDENCES and r["n_valid"] == 0 for r in recs) and len(recs) == 4
         res.append((recs, counters(c)))
         c.close()
-    assert_same_run(res[0][0], res[1][0]); assert_same_run(res[2][0], res[1][0])
-    assert res[0][1] == (1, 0) and res[2][1] == (1, 0)
+    assert_same_run(res[1][0], res[0][0])
+    assert res[1][1] == (1, 0)
 
 
 def test_stale_total_in_the_handover_slots_is_never_consumed(gpu_ctx_factory, bunny):

@@ -4,8 +4,8 @@ launch by launch with poses the test dictates (launch 0 unseeded, launch j seede
 last launch's Match records and squared distances; they must equal the oracle's exact search at that pose bit for bit
 (NearestNeighbor.h:81-97 semantics: squared L2 in FLANN order, first = lowest-index minimum, threshold on the squared distance).
 Every seeded test runs in the forms icp_run takes: "merged" (the default point-to-plane loop: k_knn_bvh_post_ring, the reducer of the
-previous launch in front of the matcher blocks, the pose read from the ring), "separate" (ICP_HIP_MERGE=0: k_knn_bvh_post; also what
-point-to-point always runs) and, where the file has it, "loop" (ICP_HIP_PERSIST=1: k_icp_loop).
+previous launch in front of the matcher blocks, the pose read from the ring) and "separate" (ICP_HIP_MERGE=0: k_knn_bvh_post; also what
+point-to-point always runs).
 Plus: the free-running 50-iteration configs[1] run at full size against orc.estimate_pose, every iteration; queries with no
 candidate at all (every squared distance overflows) in seeded chains and in a free run."""
 import os
@@ -41,7 +41,7 @@ FORMS = ("merged", "separate")
 def new_ctx(factory, form="merged"):
     """A context whose icp_run -- and with it icp_match_seeded -- takes `form` (the keys test_gpu_merged.py::make_ctx sets; read once,
     at icp_ctx_create)."""
-    env = {"ICP_HIP_MERGE": "0" if form == "separate" else "1", "ICP_HIP_PERSIST": "1" if form == "loop" else "0"}
+    env = {"ICP_HIP_MERGE": "0" if form == "separate" else "1"}
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
@@ -64,13 +64,12 @@ def make_ctx(factory, pair, rejection, form="merged", **kw):
     return c
 
 
-@pytest.mark.parametrize("upto,loop", [(1, False), (5, False), (12, False), (30, False), (5, True), (30, True)])
-def test_seeded_search_fullsize_bit_exact_vs_kdtree_oracle(gpu_ctx_factory, eth_pair, eth_oracle_run, orc, upto, loop):
+@pytest.mark.parametrize("upto", (1, 5, 12, 30), ids=lambda u: "%d-False" % u)      # (the ids these cases had beside the removed one-launch ones)
+def test_seeded_search_fullsize_bit_exact_vs_kdtree_oracle(gpu_ctx_factory, eth_pair, eth_oracle_run, orc, upto):
     """370 488 x 370 488, the oracle's own pose sequence of iterations 0..upto replayed through the fused matcher: the records of launch
-    `upto` -- reached through `upto` seeded, incremental launches (merged ring launches, the default; loop: iterations of ONE k_icp_loop
-    launch, the waves resident, their queries' data parked from iteration to iteration) -- equal the oracle's kd-tree search at that
-    pose, idx and d2 bits."""
-    check_fullsize_chain(gpu_ctx_factory, eth_pair, eth_oracle_run, orc, upto, "loop" if loop else "merged")
+    `upto` -- reached through `upto` seeded, incremental launches (merged ring launches, the default) -- equal the oracle's kd-tree
+    search at that pose, idx and d2 bits."""
+    check_fullsize_chain(gpu_ctx_factory, eth_pair, eth_oracle_run, orc, upto, "merged")
 
 
 @pytest.mark.parametrize("upto", (1, 5, 12, 30))
@@ -404,7 +403,7 @@ def no_candidate_cloud(seed, huge_targets=False):
 
 
 @pytest.mark.parametrize("huge_targets", (False, True))
-@pytest.mark.parametrize("form", FORMS + ("loop",))
+@pytest.mark.parametrize("form", FORMS)
 def test_seeded_search_queries_without_candidate_vs_oracle(gpu_ctx_factory, orc, form, huge_targets):
     """Queries with no candidate at all, in waves whose other queries walk for long and get helped by other waves (the cross-wave
     hand-over repairs the winner's position of every query in such a wave -- for a query without a winner there is none to repair;

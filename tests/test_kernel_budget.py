@@ -36,15 +36,9 @@ def test_fused_matcher_keeps_six_waves_per_simd_and_no_scratch(tmp_path):
     # colour ICP (6-D boxes, QueryPt<6>, six shuffles per hand-over) and the stage-level matchers: 5 / 4 waves per SIMD, and -- what the
     # comments in dev_solve.hpp warn about -- no scratch: a dispatch with a scratch demand stalls the queue
     for prefix, cap in (("14k_knn_bvh_postILi6ELb", 96), ("19k_knn_bvh_post_ringILi6ELb", 96), ("9k_knn_bvhILi3E", 80), ("9k_knn_bvhILi6E", 112),
-                        ("19k_ring_reduce_solve", 64), ("18k_icp_loop_reducer", 112)):      # (the loop's reducer sits in 112-register holes: dev_persist.hpp)
+                        ("19k_ring_reduce_solve", 64)):
         ks = kernels(prefix)
         assert ks, prefix
         for name, f in ks.items():
             assert f["num_vgpr"] <= cap, (name, f)
             assert f["private_seg_size"] == 0, (name, f)
-    # k_icp_loop (experimental: ICP_HIP_PERSIST=1): the whole grid must be resident -> 6 waves per SIMD by decree (__launch_bounds__), which the
-    # allocator currently pays for with a few spilled dwords
-    ks = kernels("10k_icp_loopILi")
-    assert len(ks) == 4, list(ks)
-    for name, f in ks.items():
-        assert f["num_vgpr"] <= 80 and f["private_seg_size"] <= 64, (name, f)

@@ -9,7 +9,7 @@ from icp_amd import binding, synth
 f32 = np.float32
 def counters(c, reset=1):
     buf = np.zeros(16, np.uint32)
-    assert c.lib.icp_debug_gx_counters(c.h, buf.ctypes.data_as(C.c_void_p), C.c_int32(reset)) == 0
+    assert c.lib.icp_debug_dev_counters(c.h, buf.ctypes.data_as(C.c_void_p), C.c_int32(reset)) == 0
     return buf.astype(np.int64)
 def small_motion(rng, scale):
     w = rng.normal(size=3) * scale; t = rng.normal(size=3) * scale

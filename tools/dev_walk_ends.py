@@ -14,9 +14,9 @@ prev = np.zeros(16, np.int64); last = 0
 for iters in [int(a) for a in sys.argv[1:]] or [2, 3, 4, 6, 8, 10, 12, 14, 16, 20, 30]:
     c.params.n_iterations = iters; c.push_params()
     buf = np.zeros(16, np.uint32)
-    c.lib.icp_debug_gx_counters(c.h, buf.ctypes.data_as(C.c_void_p), C.c_int32(1))
+    c.lib.icp_debug_dev_counters(c.h, buf.ctypes.data_as(C.c_void_p), C.c_int32(1))
     c.run(np.eye(4))
-    assert c.lib.icp_debug_gx_counters(c.h, buf.ctypes.data_as(C.c_void_p), C.c_int32(1)) == 0
+    assert c.lib.icp_debug_dev_counters(c.h, buf.ctypes.data_as(C.c_void_p), C.c_int32(1)) == 0
     cur = buf.astype(np.int64); d = cur - prev                # a run of `iters` iterations minus the run before = iterations last .. iters - 1
     print("iterations %2d..%2d: seeded walks %7d, ending in the old neighbour's leaf %5.1f %%, in the old runner-up's leaf %5.1f %%"
           % (last, iters - 1, d[8], 100.0 * d[9] / max(d[8], 1), 100.0 * d[10] / max(d[8], 1)))

@@ -15,7 +15,7 @@ for iters in [int(a) for a in sys.argv[1:]] or [31, 34, 37, 40]:
     c.params.n_iterations = iters; c.push_params()
     c.run(np.eye(4))
     buf = np.zeros(64, np.uint32)
-    assert c.lib.icp_debug_gx_counters(c.h, buf.ctypes.data_as(C.c_void_p), C.c_int32(2)) == 0
+    assert c.lib.icp_debug_dev_counters(c.h, buf.ctypes.data_as(C.c_void_p), C.c_int32(2)) == 0
     t = buf.astype(np.int64)
     trips = int(t[4])
     us = lambda x: ((x - t[2]) & 0xFFFFFFFF) * 0.01

@@ -8,9 +8,6 @@ run bench_lbvh python bench.py --steps 20 --warmup 5
 run bench_lbvh_noincremental python bench.py --no-incremental --no-cpu-baseline
 run bench_lbvh_separate env ICP_HIP_MERGE=0 python bench.py --no-cpu-baseline --no-extras
 run bench_lbvh_separate_nostageevents env ICP_HIP_MERGE=0 python bench.py --no-cpu-baseline --no-extras --stage-timing 0
-run bench_lbvh_loop env ICP_HIP_PERSIST=1 ICP_HIP_LOOP_WAVESLEEP=6 python bench.py --no-cpu-baseline --no-extras --per-iteration
-run bench_lbvh_loop_nostageevents env ICP_HIP_PERSIST=1 ICP_HIP_LOOP_WAVESLEEP=6 python bench.py --no-cpu-baseline --no-extras --stage-timing 0
-run bench_lbvh_hybrid10_nostageevents env ICP_HIP_PERSIST=1 ICP_HIP_LOOP_FROM=10 ICP_HIP_LOOP_WAVESLEEP=6 python bench.py --no-cpu-baseline --no-extras --stage-timing 0
 run bench_lbvh_alltimed python bench.py --stage-timing 1 --no-cpu-baseline
 run bench_lbvh_nostageevents python bench.py --stage-timing 0 --no-cpu-baseline
 run bench_brute python bench.py --knn brute --steps 2 --no-cpu-baseline
@@ -44,7 +41,6 @@ if [ -f icp-variants_amd/lib/libicp_hip_times.so ]; then      # development buil
   echo "== wave phase times"
   ICP_HIP_MERGE=0 ICP_HIP_LIB=icp-variants_amd/lib/libicp_hip_times.so timeout -k 10 300 python tools/dev_wave_times.py 1 3 6 12 20 45 > $OUT/wave_phase_times.txt 2> $OUT/wave_phase_times.err
   ICP_HIP_LIB=icp-variants_amd/lib/libicp_hip_times.so timeout -k 10 300 python tools/dev_ring_times.py 3 12 30 40 > $OUT/ring_phase_times.txt 2> $OUT/ring_phase_times.err
-  for it in 2 12 30 40; do ICP_HIP_PERSIST=1 ICP_HIP_LOOP_WAVESLEEP=6 ICP_HIP_DBG_ITER=$it ICP_HIP_LIB=icp-variants_amd/lib/libicp_hip_times.so timeout -k 10 300 python tools/dev_loop_times.py; done > $OUT/loop_phase_times.txt 2> $OUT/loop_phase_times.err
 fi
 rm -rf $OUT/kt $OUT/ktb $OUT/ktp $OUT/pmc/p*/
 echo done
