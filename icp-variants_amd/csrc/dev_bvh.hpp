@@ -1,4 +1,4 @@
-// dev_bvh.hpp -- exact kd-ordered BVH: build kernels, 4-wide nodes, the walk (per lane, and shared over the wave), k_knn_bvh.
+// dev_bvh.hpp -- exact kd-ordered BVH: build kernels, 4-wide nodes, the walk (shared over the wave), k_knn_bvh.
 // Part of icp_device.hpp (included from there, inside namespace icpdev); see that file for the build contract.
 // ------------------------------------------------------------------------------------------------
 // Exact kd-ordered BVH 1-NN: the index the reference builds once per pair (NearestNeighbor.h:122-141 / :209-232, a FLANN
@@ -7,8 +7,8 @@
 // bit-identical results, O(log M) nodes per query instead of M distance evaluations.  DIM = 3 or 6.
 //   build : level by level, every node's points are sorted along the widest axis of the node's bounding box; the implicit
 //           node k covers a fixed, leaf-aligned slice of the array, so the count-balanced median split is simply "first
-//           half / second half".  Slices > 2048 points: one rocPRIM sort per level over keys (node id << 32 | ordered
-//           coordinate bits); below that, all remaining levels in one LDS kernel (k_bvh_block_levels).  Leaves hold
+//           half / second half".  Slices > 2048 points: stable partitions of the axis lists sorted once up front (k_presort_*);
+//           below that, all remaining levels in one LDS kernel (k_bvh_block_levels).  Leaves hold
 //           BVH_LEAF points SoA + original indices; binary node records hold BOTH child boxes, pair-interleaved for
 //           packed-f32 math, filled bottom-up; the 1-NN walk uses 4-wide nodes derived from them (two levels collapsed)
 //           and 32-byte target records in leaf order.
@@ -20,20 +20,12 @@
 #ifndef ICP_ISEL_NATURAL
 #define ICP_ISEL_NATURAL 0        // 1: the natural spellings of two expressions in k_bvh_block_levels that crash the ROCm 7.2 gfx950 instruction selector
 #endif
-#ifndef ICP_SEED_DESCENT
-#define ICP_SEED_DESCENT 1
-#endif
 #ifndef ICP_PRUNE_SLACK
 // A box is skipped when its (squared) bound exceeds best * ICP_PRUNE_SLACK.  Anything above 1 + a few ulp is exact.  But a box skipped with a
 // bound barely above the neighbour's distance leaves the query a bound on "everything else" with no margin, and it can then never be
 // verified without a search: 1.001 (0.05 % in distance, far more than a query moves per iteration once ICP has converged) costs a
 // handful of extra box visits and retires those queries.  (Until round 2: 1.00002.)
 #define ICP_PRUNE_SLACK 1.001f
-#endif
-#ifndef ICP_PREFETCH_PATH
-// 1: a seeded walk first touches the nodes of its seed's root-to-leaf path (quad_prefetch_path).  It paid while every lane walked alone
-// (round 1 / early round 2); with the shared walk it no longer does (iterations 1-9 0.0567 ms without, 0.0578 with): off.
-#define ICP_PREFETCH_PATH 0
 #endif
 constexpr int BVH_LEAF = 8;
 #ifndef ICP_BVH_THREADS
@@ -96,70 +88,6 @@ __device__ __forceinline__ unsigned int ordered_bits(float f) {          // mono
 }
 __device__ __forceinline__ float from_ordered_bits(unsigned int u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-
-// Per-level bounding boxes of the nodes, without contended atomics:
-//   k_bvh_wave_boxes : every wave (or aligned sub-wave segment of 32 / 16 positions, for the last levels) reduces the box
-//                      of its consecutive positions with a shuffle tree -> segbox[segment][2*DIM]
-//   k_bvh_node_boxes : one wave per node folds the node's wave boxes (segments of >= 64 positions are wave-aligned)
-template <int DIM>
-__global__ void k_bvh_wave_boxes(const CoordPtrs<DIM> cp, const int* __restrict__ perm, int n_valid, int seg_shift /* <= 6 */, unsigned int* __restrict__ segbox) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool act = i < n_valid;
-    const int j = act ? perm[i] : 0;
-    unsigned int v[2 * DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; k++) { const unsigned int a = act ? ordered_bits(cp.c[k][j]) : 0u; v[k] = act ? a : 0xFFFFFFFFu; v[DIM + k] = a; }
-    const int seg = 1 << seg_shift;                       // 64 (whole wave) or a sub-wave segment of 32 / 16 positions
-    for (int off = seg >> 1; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < DIM; k++) { v[k] = min(v[k], (unsigned int)__shfl_down((int)v[k], off, 64)); v[DIM + k] = max(v[DIM + k], (unsigned int)__shfl_down((int)v[DIM + k], off, 64)); }
-    }
-    if ((threadIdx.x & (seg - 1)) == 0 && (i < n_valid || seg == 64)) {
-        unsigned int* o = segbox + (size_t)(i >> seg_shift) * 2 * DIM;
-#pragma unroll
-        for (int k = 0; k < 2 * DIM; k++) o[k] = v[k];
-    }
-}
-template <int DIM>
-__global__ void k_bvh_node_boxes(const unsigned int* __restrict__ wavebox, int n_waves, int waves_per_node_shift, int n_nodes, unsigned int* __restrict__ boxes) {
-    const int node = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-    if (node >= n_nodes) return;
-    const int w0 = node << waves_per_node_shift, w1 = min(w0 + (1 << waves_per_node_shift), n_waves);
-    unsigned int v[2 * DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; k++) { v[k] = 0xFFFFFFFFu; v[DIM + k] = 0u; }
-    for (int w = w0 + lane; w < w1; w += 64) {
-        const unsigned int* b = wavebox + (size_t)w * 2 * DIM;
-#pragma unroll
-        for (int k = 0; k < DIM; k++) { v[k] = min(v[k], b[k]); v[DIM + k] = max(v[DIM + k], b[DIM + k]); }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < DIM; k++) { v[k] = min(v[k], (unsigned int)__shfl_down((int)v[k], off, 64)); v[DIM + k] = max(v[DIM + k], (unsigned int)__shfl_down((int)v[DIM + k], off, 64)); }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 2 * DIM; k++) boxes[(size_t)node * 2 * DIM + k] = v[k];
-    }
-}
-// sort key of every point at this level: (node id, coordinate along the node's widest axis)
-template <int DIM>
-__global__ void k_bvh_level_keys(const CoordPtrs<DIM> cp, const int* __restrict__ perm, int n_valid, int seg_shift, const unsigned int* __restrict__ boxes,
-                                 unsigned long long* __restrict__ keys) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_valid) return;
-    const int node = i >> seg_shift;
-    const unsigned int* b = boxes + (size_t)node * 2 * DIM;
-    int axis = 0; float ext = -1.f;
-#pragma unroll
-    for (int k = 0; k < DIM; k++) { const float e = from_ordered_bits(b[DIM + k]) - from_ordered_bits(b[k]); if (e > ext) { ext = e; axis = k; } }
-    const int j = perm[i];
-    float c = cp.c[0][j];
-#pragma unroll
-    for (int k = 1; k < DIM; k++) c = (axis == k) ? cp.c[k][j] : c;
-    keys[i] = ((unsigned long long)(unsigned int)node << 32) | ordered_bits(c);
 }
 
 // ---- upper levels from PRESORTED axes ---------------------------------------------------------------------------------------
@@ -265,8 +193,8 @@ __global__ __launch_bounds__(PRS_THREADS) void k_presort_scatter(const AxisLists
 // The lower levels of the build in one kernel.  Once a node's slice is <= 2048 points the remaining levels only permute
 // points INSIDE that slice, so a block takes 2048 consecutive positions into LDS and runs all of them there: per level the
 // boxes of the slices (shuffle tree + at most 4 wave boxes), the widest axis, and a bitonic sort of every slice on
-// (ordered coordinate bits, position) -- the position makes the keys unique and reproduces the stable order of the global
-// radix sort, so the tree is exactly the one the level-by-level build produces.  Replaces 8 global sorts (~120 us each).
+// (ordered coordinate bits, position) -- the position makes the keys unique, so the sort is stable.  (Round 1 ran these
+// levels as 8 global sorts of ~120 us each.)
 constexpr int BLV_POINTS = 2048, BLV_THREADS = 256, BLV_PER = BLV_POINTS / BLV_THREADS;
 template <int DIM>
 __global__ __launch_bounds__(BLV_THREADS) void k_bvh_block_levels(const CoordPtrs<DIM> cp, const int* __restrict__ perm_in, int n_valid, int first_shift /* <= 11 */,
@@ -552,7 +480,7 @@ __device__ __forceinline__ void trav_pop(TravState& st, const unsigned short* __
 // ---- 4-wide walk -------------------------------------------------------------------------------------------------------
 // Same exactness argument as the binary walk (a box is skipped only if its lower bound, computed with the operation order
 // of the point distance, exceeds the running best), half the depth.  Per-lane state: level, index within the level and
-// 4 pending-child bits per level in one mask register (see quad_run for why bits are enough).
+// 4 pending-child bits per level in one mask register (see quad_pop_bits for why bits are enough).
 template <class MaskT> struct QuadStateT { int L; int idx; MaskT pending; bool alive; };     // MaskT: 32 bits hold 8 levels, 64 bits 16
 
 template <int DIM>
@@ -582,29 +510,6 @@ __device__ __forceinline__ void quad_lb_at(const BvhViewT<DIM>& bv, unsigned int
     quad_lb<DIM>(bv.qnodes + node, q.p2, l01, l23);
 }
 
-// The walk is a chain of dependent loads, each a trip to L2 or HBM.  A seeded query already knows where it will most
-// likely end up: in or next to the leaf of its previous neighbour, whose ancestors are known arithmetically in the implicit
-// layout.  Touching that whole root-to-leaf path up front turns the chain of misses into ONE round of parallel misses followed
-// by cache hits.  (The lowest 8 levels; anything above is shared by everybody and hot.)
-template <int DIM>
-__device__ __forceinline__ unsigned int quad_prefetch_path(const BvhViewT<DIM>& bv, int leaf) {
-    // plain loads whose values are only consumed (by an empty asm) AFTER the walk: nothing waits for them specially, they
-    // simply travel together with the walk's first node load
-    unsigned int sink = *(const unsigned int*)(bv.leaves + leaf);
-    if (DIM == 6) sink |= *((const unsigned int*)(bv.leaves + leaf) + 32);
-    unsigned int t[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) {                         // branch-free (levels above the root clamp to the root): the loads issue back to back
-        const int L = max(bv.Lq - 1 - u, 0), sh = min(2 * (u + 1), 2 * bv.Lq);
-        const unsigned int* nd = (const unsigned int*)(bv.qnodes + ((0x5555555555555555ull & ((1ull << (2 * L)) - 1ull)) + (unsigned long long)(leaf >> sh)));
-        t[u] = nd[31];
-        if (DIM == 6) t[u] |= nd[63];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++) sink |= t[u];
-    return sink;
-}
-
 // The pending siblings are remembered as BITS only (4 per level, one register), not with their bounds.  A seeded walk is in
 // effect a range query -- its prune threshold is almost final from the first step on -- so re-testing a parked sibling against the
 // improved threshold when it is popped (round 1 kept 16-bit bounds in LDS for that) buys next to nothing, while the packing, the LDS
@@ -624,54 +529,8 @@ __device__ __forceinline__ void quad_pop_bits(QuadStateT<MaskT>& st) {
     }
 }
 #ifndef ICP_DEBUG_STEPS
-#define ICP_DEBUG_STEPS 0        // 1: development build that records nodes + leaves visited per query (icp_debug_steps)
+#define ICP_DEBUG_STEPS 0        // 1: development build that records how each query was resolved (icp_debug_steps)
 #endif
-#if ICP_DEBUG_STEPS
-#define ICP_COUNT_STEP(x) ((x)++)
-__device__ int g_dbg_nodes_dummy;
-#else
-#define ICP_COUNT_STEP(x)
-#endif
-template <int DIM, class MaskT>
-__device__ __forceinline__ void quad_run(const BvhViewT<DIM>& bv, const QueryPt<DIM>& qp, QuadStateT<MaskT>& st,
-                                         float& best, int& bi, int& bpos, float& b2, int& l2, float& b3, float& minlb, int& dbg_nodes, int& dbg_leaves) {
-    const int Lq = bv.Lq;
-    // A box is skipped when its lower bound exceeds thr = best * ICP_PRUNE_SLACK (clamped so that the +inf bound of an empty box is
-    // always skipped): that implies bound > best with margin, one multiply per change of `best` instead of one per box test.
-    float thr = fminf(best * ICP_PRUNE_SLACK, FLT_MAX);
-    // smallest skipped bound, kept as its bit pattern: bounds are >= +0, so unsigned order is value order and the integer minimum
-    // needs none of the NaN canonicalisation a float minimum of selected values drags in
-    unsigned int mlb = __float_as_uint(minlb);
-    constexpr unsigned int NONE = 0x7F800000u;            // +inf
-    while (st.alive) {
-        while (st.alive && st.L < Lq) {
-            f2 l01, l23;
-            ICP_COUNT_STEP(dbg_nodes);
-            quad_lb_at<DIM>(bv, (0x55555555u & ((1u << (2 * st.L)) - 1u)) + (unsigned int)st.idx, qp, l01, l23);
-            const float m = fminf(fminf(l01.x, l01.y), fminf(l23.x, l23.y));
-            const bool s0 = !(l01.x > thr), s1 = !(l01.y > thr), s2 = !(l23.x > thr), s3 = !(l23.y > thr);
-            mlb = min(min(mlb, min(s0 ? NONE : __float_as_uint(l01.x), s1 ? NONE : __float_as_uint(l01.y))), min(s2 ? NONE : __float_as_uint(l23.x), s3 ? NONE : __float_as_uint(l23.y)));   // skipped right here
-            if (!(m > thr)) {
-                // nearest child first (selects, not branches).  Measured: taking the survivors in index order instead saves 5 instructions
-                // per node and costs 0.080 -> 0.096 ms in iterations 1-9 (0.17 -> 0.80 ms unseeded): the order is worth its price.
-                const bool c0 = l01.x == m, c1 = l01.y == m, c2 = l23.x == m;
-                int c = 3; c = c2 ? 2 : c; c = c1 ? 1 : c; c = c0 ? 0 : c;
-                const unsigned int pend = ((s0 ? 1u : 0u) | (s1 ? 2u : 0u) | (s2 ? 4u : 0u) | (s3 ? 8u : 0u)) & ~(1u << c);
-                st.pending |= (MaskT)pend << (4 * st.L);
-                st.idx = (st.idx << 2) | c; st.L++;
-            } else st.alive = false;                      // all four children pruned
-            quad_pop_bits(st);
-        }
-        if (st.alive) {
-            ICP_COUNT_STEP(dbg_leaves);
-            leaf_eval<DIM>(bv.leaves + st.idx, st.idx, qp.p2, best, bi, bpos, b2, l2, b3);
-            thr = fminf(best * ICP_PRUNE_SLACK, FLT_MAX);
-            st.alive = false;
-            quad_pop_bits(st);
-        }
-    }
-    minlb = __uint_as_float(mlb);
-}
 
 // XCD-aware block mapping: workgroups are dealt round-robin over the 8 XCDs (block b runs on the XCD group b % 8), each
 // with a private 4 MiB L2.  With Morton-sorted queries, giving an XCD consecutive blocks of the order means its L2 only has to hold
@@ -681,26 +540,17 @@ __device__ __forceinline__ void quad_run(const BvhViewT<DIM>& bv, const QueryPt<
 // the work: iterations 1-9 0.0615 -> 0.058 ms (chunks of 1 / 4 / 8 / 32 / 64: 0.061 / 0.0595 / 0.059 / 0.058 / 0.059).
 // Measured on top of that and dropped: a wave made of 2 / 4 / 8 / 16 runs of consecutive queries from as many places of its chunk
 // instead of 64 consecutive ones (evens out the waves, costs coherence: no gain beyond noise).
-#ifndef ICP_XCD_CHUNK
-#define ICP_XCD_CHUNK 16         // chunks of this many consecutive blocks dealt to the XCDs in turn; 0: one contiguous slice per XCD
-#endif
 __device__ __forceinline__ int xcd_contiguous_block(int b, int nb) {
-#if ICP_XCD_CHUNK
-    {
-        constexpr int C = ICP_XCD_CHUNK;
-        const int full = nb / (8 * C) * (8 * C);                      // the part of the grid that deals out evenly; the rest keeps its order
-        if (b >= full) return b;
-        const int x = b & 7, j = b >> 3;
-        return ((j / C) * 8 + x) * C + j % C;
-    }
-#endif
-    const int q = nb >> 3, r = nb & 7, x = b & 7, j = b >> 3;        // XCD group x owns q (+1 if x < r) consecutive logical blocks
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
+    constexpr int C = 16;                                             // chunks of this many consecutive blocks dealt to the XCDs in turn
+    const int full = nb / (8 * C) * (8 * C);                          // the part of the grid that deals out evenly; the rest keeps its order
+    if (b >= full) return b;
+    const int x = b & 7, j = b >> 3;
+    return ((j / C) * 8 + x) * C + j % C;
 }
 
-// Every lane walks the tree on its own for its own query.  Measured on MI355X (370k x 370k, DIM 3): 12.5 4-wide nodes and
-// 3.1 leaves per walked query, ~40 % of the lanes active on average (walk lengths differ per lane: 15.6 steps on average,
-// ~70 for the longest), a third of the wave time waiting on dependent loads.  The kernel lasts as long as its longest walks.
+// Before the walks were shared over the wave, every lane walked the tree on its own for its own query.  Measured on MI355X (370k x 370k,
+// DIM 3): 12.5 4-wide nodes and 3.1 leaves per walked query, ~40 % of the lanes active on average (walk lengths differ per lane: 15.6
+// steps on average, ~70 for the longest), a third of the wave time waiting on dependent loads.  The kernel lasted as long as its longest walks.
 // What moved it: kd-ordered tree, Morton-sorted queries + XCD-contiguous slices, compact per-level stack in LDS, temporal
 // seeding, the verify-and-skip test below (which retires whole waves without a walk once ICP has converged), 4-wide nodes.
 // Measured and not adopted: wave-packet traversal with scalar node loads, persistent lanes with
@@ -741,20 +591,8 @@ __device__ __forceinline__ void knn_store_state(const KnnParams& kp, int k, cons
     if (kp.d2_out) kp.d2_out[k] = best;
 }
 
-#ifndef ICP_SHARE_WALKS
-#define ICP_SHARE_WALKS 1        // 1: the lanes of a wave that have nothing (left) to search take pending subtrees off the lanes that still walk
-#endif
 #ifndef ICP_SHARE_ROUNDS
 #define ICP_SHARE_ROUNDS 2       // hand-over rounds per pass (each pairs the idle lanes with as many donors, one subtree per donor)
-#endif
-#ifndef ICP_SHARE_SPREAD
-#define ICP_SHARE_SPREAD 1       // 1: few seeded walkers in a wave -> the levels of their seeds' paths are searched side by side by the idle lanes
-#endif
-#ifndef ICP_LONE_WALK
-#define ICP_LONE_WALK 1          // 1: a wave with ONE (seeded) walker searches level-synchronously, two levels per dependent load (knn_walk_shared)
-#endif
-#ifndef ICP_SPREAD_TWO
-#define ICP_SPREAD_TWO 1         // 1: ... and, while the lanes suffice, the levels of the path to the last search's runner-up leaf as well
 #endif
 #define ICP_SHARE_ROWS 10        // LDS rows (of NT uint2) the shared walk needs per wave
 // The walks of one wave, shared.  A wave lasts as long as its longest walk while the lanes whose queries verified, or whose
@@ -797,9 +635,6 @@ __device__ __forceinline__ void knn_store_state(const KnnParams& kp, int k, cons
 // another wave checks the record at that position against the key's index and, on a mismatch, takes the position from the inverse
 // map (BvhViewT::pos_of).  Results are the exact neighbours as before; the bounds kept for the verify tests may differ from run to run
 // (never larger than what is true), i.e. WHICH queries search in a later iteration may differ, not what they find.
-#ifndef ICP_XW
-#define ICP_XW 1                 // 1: blocks of more than one wave share walks between their waves (DIM 3)
-#endif
 #ifndef ICP_XW_SLEEP
 #define ICP_XW_SLEEP 4
 #endif
@@ -819,7 +654,7 @@ __device__ unsigned int g_walk_trace[64];   // ICP_DEBUG_WALK_TRACE: the last sp
 #endif
 constexpr int XW_INTS = XW_CTRL + XW_SLOTS + XW_SLOTS * 5;      // control words, slot states, items (2 x uint2 + int per slot)
 constexpr int XW_SPIN_LIMIT = 1 << 22;                   // polls of an idle wave (~0.3 us each) before it gives up and raises the fault word
-template <int DIM, int NT> constexpr bool xw_enabled() { return ICP_XW && DIM == 3 && NT > WAVE && NT / WAVE <= 8; }
+template <int DIM, int NT> constexpr bool xw_enabled() { return DIM == 3 && NT > WAVE && NT / WAVE <= 8; }
 template <int DIM, int NT> constexpr size_t xw_lds_bytes() { return xw_enabled<DIM, NT>() ? (size_t)XW_INTS * 4 : 0; }
 // (block start, before the first __syncthreads of the kernel: thread t clears word t of the control block and the slot states)
 template <int NT> __device__ __forceinline__ void xw_init(uint2* lbq, int tid) { if (tid < XW_CTRL + XW_SLOTS) ((int*)(lbq + ICP_SHARE_ROWS * NT))[tid] = 0; }
@@ -889,7 +724,7 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
     // exact neighbour, bounds that are valid in the same way.
     bool lone_done = false;
     const unsigned long long wm0 = __ballot(need_walk);
-    if (ICP_LONE_WALK && MODE == 1 && DIM == 3 && sizeof(MaskT) == 4 && ICP_SHARE_SPREAD && Lq > 0 && __popcll(wm0) == 1 && wm0 == __ballot(need_walk && bpos >= 0)) {
+    if (MODE == 1 && DIM == 3 && sizeof(MaskT) == 4 && Lq > 0 && __popcll(wm0) == 1 && wm0 == __ballot(need_walk && bpos >= 0)) {
         int* tbl = (int*)(R + 6 * NT);
         const int wl = (int)__ffsll((long long)wm0) - 1;
         QueryPt<DIM> lq;
@@ -948,7 +783,7 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
     }
     QueryPt<DIM> qp;
     float wb; int wi, wp;
-    if constexpr (DIM == 3 && MODE == 1 && sizeof(MaskT) == 4 && ICP_LONE_WALK) {
+    if constexpr (DIM == 3 && MODE == 1 && sizeof(MaskT) == 4) {
         // (read back from the rows written above rather than kept in registers across the lone walker's search: six registers of the budget)
         const uint2 ra_ = R[3 * NT + lane], rb_ = R[4 * NT + lane], rc_ = R[5 * NT + lane], rd_ = R[7 * NT + lane];
         float pq[3] = {__uint_as_float(rc_.y), __uint_as_float(rd_.x), __uint_as_float(rd_.y)};
@@ -958,9 +793,11 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
         make_query<DIM>(bv, p, qp);
         wb = best; wi = bi; wp = bpos;
     }
-    unsigned int touched = 0u;
     if (!HELP && need_walk && !lone_done) {
-        if (ICP_SEED_DESCENT && wp < 0) {                                 // first iteration: a greedy descent yields a real candidate (see knn_walk)
+        if (wp < 0) {
+            // No candidate yet (first iteration): one greedy root-to-leaf descent -- nearest child at every level, nothing parked --
+            // yields a real candidate first.  The proper walk below then prunes from the root on; without it every level parks
+            // three siblings that are popped and discarded later, which costs more instructions than these Lq extra node visits.
             int idx = 0;
             for (int L = 0; L < Lq; L++) {
                 f2 l01, l23;
@@ -984,12 +821,15 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
     if (tracer) { g_walk_trace[0] = (unsigned int)W; g_walk_trace[2] = (unsigned int)wall_clock64(); }
 #endif
     if (MODE == 1 && lane == 0 && !lone_done) __hip_atomic_fetch_add(xc + 0, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // nreg: this wave has queries that search
-    const bool spread = !HELP && ICP_SHARE_SPREAD && Lq > 0 && W > 0 && W * (Lq + 1) <= WAVE && wm == __ballot(need_walk && wp >= 0);
-    if (ICP_PREFETCH_PATH && !spread && need_walk && wp >= 0) touched = quad_prefetch_path<DIM>(bv, wp >> 3);
+    const bool spread = !HELP && Lq > 0 && W > 0 && W * (Lq + 1) <= WAVE && wm == __ballot(need_walk && wp >= 0);
     float b2 = FLT_MAX, b3 = FLT_MAX; int l2 = -1;
+    // smallest skipped bound, kept as its bit pattern: bounds are >= +0, so unsigned order is value order and the integer minimum
+    // needs none of the NaN canonicalisation a float minimum of selected values drags in
     unsigned int mlb = FMAXB;
     int owner = need_walk ? tid : -1;                                     // whose query this lane is searching for (thread of the block); -1: idle
     QuadStateT<MaskT> st; st.L = 0; st.idx = 0; st.pending = 0; st.alive = need_walk;
+    // A box is skipped when its lower bound exceeds thr = best * ICP_PRUNE_SLACK (clamped so that the +inf bound of an empty box is
+    // always skipped): that implies bound > best with margin, one multiply per change of `best` instead of one per box test.
     float thr = fminf(wb * ICP_PRUNE_SLACK, FLT_MAX);
     // one node step on the child bounds of node (st.L, st.idx): nearest surviving child next, the other survivors parked
     auto descend = [&](const f2& l01, const f2& l23) {
@@ -997,6 +837,8 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
         const bool s0 = !(l01.x > thr), s1 = !(l01.y > thr), s2 = !(l23.x > thr), s3 = !(l23.y > thr);
         mlb = min(min(mlb, min(s0 ? NONE : __float_as_uint(l01.x), s1 ? NONE : __float_as_uint(l01.y))), min(s2 ? NONE : __float_as_uint(l23.x), s3 ? NONE : __float_as_uint(l23.y)));
         if (!(m > thr)) {
+            // nearest child first (selects, not branches).  Measured: taking the survivors in index order instead saves 5 instructions
+            // per node and costs 0.080 -> 0.096 ms in iterations 1-9 (0.17 -> 0.80 ms unseeded): the order is worth its price.
             const bool c0 = l01.x == m, c1 = l01.y == m, c2 = l23.x == m;
             int c = 3; c = c2 ? 2 : c; c = c1 ? 1 : c; c = c0 ? 0 : c;
             const unsigned int pend = ((s0 ? 1u : 0u) | (s1 ? 2u : 0u) | (s2 ? 4u : 0u) | (s3 ? 8u : 0u)) & ~(1u << c);
@@ -1008,14 +850,14 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
     if (spread && !lone_done) {
         int* tbl = (int*)(R + 6 * NT);
         if (need_walk) tbl[__builtin_amdgcn_mbcnt_hi((unsigned int)(wm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)wm, 0u))] = lane;
-        // Two paths per walker when the lanes suffice (ICP_SPREAD_TWO): besides the path to the seed's leaf (A) the path to the leaf the
+        // Two paths per walker when the lanes suffice: besides the path to the seed's leaf (A) the path to the leaf the
         // RUNNER-UP of the last search lives in (B; l2o on entry = the second leaf of the two-leaf tier, -1: none).  A query that searches
         // although ICP has converged sits between two (or more) targets: the subtree that holds the other one survives every bound, and a
         // helper lane would walk down to it level by level -- Lq - D dependent steps below the level D where the paths part.  Here the
         // levels of B below D go to idle lanes as well, and B's leaf to one more: roles 0 .. Lq - 1 = the nodes of A (a node both paths
         // pass through skips BOTH on-path children), Lq .. 2 Lq - 1 = the nodes of B (idle where B still runs with A), 2 Lq = leaf B.
         // Every subtree that hangs off either path is tested by exactly one lane, every on-path child by the lane of the next level.
-        const bool two = ICP_SPREAD_TWO && W * (2 * Lq + 2) <= WAVE;        // (wave-uniform)
+        const bool two = W * (2 * Lq + 2) <= WAVE;                          // (wave-uniform)
         const int roles = two ? 2 * Lq + 1 : Lq;
 #if ICP_DEBUG_TIMES && ICP_DEBUG_WALK_TRACE
         if (tracer) g_walk_trace[1] = two ? 2u : 1u;
@@ -1205,7 +1047,9 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
 #if ICP_DEBUG_TIMES && ICP_DEBUG_WALK_TRACE
     if (tracer) { g_walk_trace[4] = (unsigned int)trips; g_walk_trace[5] = (unsigned int)polls; g_walk_trace[6] = (unsigned int)wall_clock64(); }
 #endif
-    asm volatile("" ::"v"(touched));
+    // (An empty asm reading a zero VGPR, left by the set-aside path prefetch.  Dropping it changes the walk kernels' code: a change to
+    //  measure on its own.)
+    asm volatile("" ::"v"(0u));
     if (HELP) return;
     {
         const uint2 c = R[5 * NT + lane], d = R[7 * NT + lane], e = R[8 * NT + lane], f = R[9 * NT + lane];
@@ -1246,57 +1090,6 @@ __device__ __forceinline__ void xw_help(const BvhViewT<DIM>& bv, uint2* __restri
     knn_walk_shared<DIM, NT, MaskT, 2>(bv, p, k3, false, best, bi, bpos, lbo, lb3, l2, lbq, tid, fault);
 }
 
-__device__ __forceinline__ float wave_min_f32(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-
-// The tree walk proper for query p, starting from the seed (best, bi, bpos); returns the lower bound on the distance to every
-// target other than the winner.  NT = threads of the block (layout of the LDS stacks).
-template <int DIM, int NT>
-__device__ __forceinline__ float knn_walk(const BvhViewT<DIM>& bv, const float* p, float& best, int& bi, int& bpos, float& lb3, int& l2, uint2* __restrict__ lbq, int tid, int* dbg_out = nullptr) {
-    int dbg_nodes = 0, dbg_leaves = 0;
-    QueryPt<DIM> qp;
-    make_query<DIM>(bv, p, qp);
-    float b2 = FLT_MAX, b3 = FLT_MAX, minlb = FLT_MAX; l2 = -1;
-    unsigned int touched = 0u;
-    if (ICP_SEED_DESCENT && bpos < 0 && bv.Lq > 0) {
-        // No candidate yet (first iteration): one greedy root-to-leaf descent -- nearest child at every level, nothing parked --
-        // yields a real candidate first.  The proper walk below then prunes from the root on; without it every level parks
-        // three siblings that are popped and discarded later, which costs more instructions than these Lq extra node visits.
-        int idx = 0;
-        for (int L = 0; L < bv.Lq; L++) {
-            f2 l01, l23;
-            quad_lb_at<DIM>(bv, (0x55555555u & ((1u << (2 * L)) - 1u)) + (unsigned int)idx, qp, l01, l23);
-            const float m = fminf(fminf(l01.x, l01.y), fminf(l23.x, l23.y));
-            const int c = (l01.x == m) ? 0 : (l01.y == m) ? 1 : (l23.x == m) ? 2 : 3;
-            idx = (idx << 2) | c;
-        }
-        float u2 = FLT_MAX, u3 = FLT_MAX; int ul = -1;
-        leaf_eval<DIM>(bv.leaves + idx, idx, qp.p2, best, bi, bpos, u2, ul, u3);      // (the walk re-evaluates this leaf: the bound bookkeeping stays in one place)
-    }
-    if (ICP_PREFETCH_PATH && bpos >= 0) touched = quad_prefetch_path<DIM>(bv, bpos >> 3);
-    if (bv.Lq <= 8) {                                     // uniform: up to 8 levels (524 288 targets) the pending bits fit 32 bits
-        QuadStateT<unsigned int> st; st.L = 0; st.idx = 0; st.pending = 0u; st.alive = true;
-        quad_run<DIM>(bv, qp, st, best, bi, bpos, b2, l2, b3, minlb, dbg_nodes, dbg_leaves);
-    } else {
-        QuadStateT<unsigned long long> st; st.L = 0; st.idx = 0; st.pending = 0ull; st.alive = true;
-        quad_run<DIM>(bv, qp, st, best, bi, bpos, b2, l2, b3, minlb, dbg_nodes, dbg_leaves);
-    }
-#if ICP_DEBUG_STEPS
-    if (dbg_out) *dbg_out = dbg_nodes | (dbg_leaves << 16);
-#endif
-    asm volatile("" ::"v"(touched));
-    lb3 = sqrt_dn(fminf(b3, minlb));
-    return sqrt_dn(fminf(b2, minlb));
-}
-
 // One query per lane (k < 0: none), the whole wave together: the lanes without a walk of their own help with the others'.
 template <int DIM>
 __device__ __forceinline__ void knn_bvh_query(const KnnParams& kp, const BvhViewT<DIM>& bv, int k, uint2* __restrict__ lbq, int tid,
@@ -1313,15 +1106,11 @@ __device__ __forceinline__ void knn_bvh_query(const KnnParams& kp, const BvhView
         if (knn_try_verify<DIM>(kp, bv, k, p, best, bi, bpos, lb_others)) lb3 = lb_others;
         else need_walk = true;
     }
-#if ICP_SHARE_WALKS
     if (__any(need_walk)) {
         float none[3] = {0.f, 0.f, 0.f};
         if (bv.Lq <= 8) knn_walk_shared<DIM, BVH_THREADS, unsigned int>(bv, p, none, need_walk, best, bi, bpos, lb_others, lb3, l2, lbq, tid);
         else knn_walk_shared<DIM, BVH_THREADS, unsigned long long>(bv, p, none, need_walk, best, bi, bpos, lb_others, lb3, l2, lbq, tid);
     }
-#else
-    if (need_walk) lb_others = knn_walk<DIM, BVH_THREADS>(bv, p, best, bi, bpos, lb3, l2, lbq, tid);
-#endif
     if (k >= 0) knn_store_state<DIM>(kp, k, p, best, bpos, lb_others, lb3, l2);
 }
 

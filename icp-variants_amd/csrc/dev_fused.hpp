@@ -37,7 +37,7 @@ struct P2pGen {                                           // values 0..21 = sum 
 #define ICP_FUSED_WAVES 6        // waves per SIMD the 3-D fused matchers are compiled for (80 registers)
 #endif
 #ifndef ICP_WAVE_STRIDE
-#define ICP_WAVE_STRIDE ((ICP_XW && ICP_BVH_THREADS > 64) ? 128 : 0)      // 1: the waves of a block come from BVH_THREADS / 64 places of the query order (hard and easy regions meet in one block: knn_walk_shared, XW)
+#define ICP_WAVE_STRIDE (ICP_BVH_THREADS > 64 ? 128 : 0)      // 1: the waves of a block come from BVH_THREADS / 64 places of the query order (hard and easy regions meet in one block: knn_walk_shared, XW)
 #endif
 #ifndef ICP_DEBUG_WALK_ENDS
 #define ICP_DEBUG_WALK_ENDS 0
@@ -190,10 +190,9 @@ __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const Bvh
     // groups instead; the shared walk does that case as well, 0.0281 vs 0.0306 ms in iterations 10-16, and the kernel without the second
     // code path needs 68 instead of 80 VGPRs.)
 #if ICP_DEBUG_STEPS && !ICP_DEBUG_TIMES
-    if (k >= 0 && kp.dbg_steps) kp.dbg_steps[k] = need_walk ? -1 : two_leaf ? -2 : 0;      // -1: walk (overwritten with its length); -2: second tier, two leaves
+    if (k >= 0 && kp.dbg_steps) kp.dbg_steps[k] = need_walk ? -1 : two_leaf ? -2 : 0;      // -1: walk; -2: second tier, two leaves
 #endif
     bool walked = false;                                  // wave-uniform: this wave's lanes searched (or helped): their neighbours' records are read again
-#if ICP_SHARE_WALKS
     if (__any(need_walk)) {
         walked = true;
         float rn[3] = {rn0, rn1, rn2};
@@ -204,9 +203,6 @@ __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const Bvh
         //  across the walk.  Without it the 6-D matchers are allocated differently: k_knn_bvh_post_ring<6, true> 90 -> 92 VGPRs)
         fused_front_clear<DIM>(in);
     }
-#else
-    if (need_walk) lb_others = knn_walk<DIM, BVH_THREADS>(bv, p, best, bi, bpos, lb3, l2, bvh_lbq, tid, (ICP_DEBUG_STEPS && kp.dbg_steps) ? kp.dbg_steps + k : nullptr);
-#endif
     ICP_STAMP(2);
 #if ICP_DEBUG_TIMES && ICP_DEBUG_WALK_ENDS                  // (one atomic per walking query on ONE word: it distorts every time stamp -- a build of its own, tools/dev_walk_ends.py)
     if (k >= 0 && need_walk && seeded) {                       // where did the seeded walk end: in the old neighbour's leaf, in the old runner-up's leaf, elsewhere?

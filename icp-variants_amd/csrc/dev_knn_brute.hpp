@@ -28,7 +28,7 @@ struct KnnParams {
     float4* qstate;                                          // [n] (query xyz when last searched or verified, lower bound on the distance to every OTHER target)
     int incremental;                                         // 1: verify-and-skip with qstate (needs use_prev)
     float2* qstate2;                                         // [n] (lower bound, at the same anchor, on every target outside the neighbour's leaf and the runner-up's leaf; that second leaf as int bits, -1: none)
-    int* dbg_steps;                                          // development builds (ICP_DEBUG_STEPS): [n] nodes | leaves << 16 visited by the walk of query k; nullptr otherwise
+    int* dbg_steps;                                          // development builds (ICP_DEBUG_STEPS): [n] how query k was resolved (0 verified, -2 second tier, -1 walk); nullptr otherwise
     int* fault;                                              // fused BVH matcher: raised when a bounded wait of the cross-wave hand-over runs out (cannot happen; knn_walk_shared)
     int dbg_waves;                                           // development builds (ICP_DEBUG_TIMES): waves of the launch = where the per-query records start in dbg_steps
 };

@@ -58,7 +58,7 @@ struct Level { DevBuf idx; DevBuf order; DevBuf sorted_idx; DevBuf pack; Cloud s
 struct Bvh {
     bool valid = false;
     int n_valid = 0, n_leaves = 0, Lp = 1;
-    DevBuf keys, keys2, vals, vals2, temp, leaves, recs, nodes, qnodes, lvl, wbox, pos_of;
+    DevBuf keys, keys2, vals, vals2, temp, leaves, recs, nodes, qnodes, pos_of;
     DevBuf axl[12], side, scanr, axis_of_node;      // presorted-axes build: DIM index lists (ping-pong), side flag per point id, scan result, widest axis per node
     int n_ids = 0;                                   // size of the id space the lists index (points of the cloud the tree is built over)
     const Cloud* attrs = nullptr;                     // cloud whose normals / colours go into the records (nullptr: none)
@@ -76,15 +76,9 @@ struct icp_ctx {
     int stage_timing = 1;                // icp_set_stage_timing: 0 none, 1 every iteration, N > 1 every Nth iteration (scaled)
     unsigned timing_phase = 0;           // rotates the sampled iterations from run to run
     void* pinned = nullptr; size_t pinned_cap = 0;   // page-locked host staging: pose upload, stats + pose download (truly asynchronous copies)
-    bool block_levels = true;            // BVH build: levels with slices <= 2048 points in one LDS kernel (ICP_HIP_BLOCK_LEVELS=0: global sorts)
-    bool spin_reduce = true;             // k_reduce_solve: block 0 polls the self-validating totals (ICP_HIP_SPIN_REDUCE=0: ticket hand-over, last arriver solves)
-    bool tier2 = true;                   // incremental k-NN: second verification tier (one leaf instead of a walk; ICP_HIP_TIER2=0 disables)
-    bool presort = true;                 // BVH build: upper levels from presorted axes (ICP_HIP_PRESORT=0: one global sort per level)
     bool trace = false;                  // ICP_HIP_TRACE=1: per-iteration stage times on stderr
-    bool fuse_post = true;               // BVH matcher runs weight / reject / accumulate as its epilogue (ICP_HIP_FUSE_POST=0 disables)
     bool merge_loop = true;              // point-to-plane loop through the fused BVH matcher: reduce + solve ride in front of the next matcher launch (ICP_HIP_MERGE=0: separate k_reduce_solve launches)
     int merged_runs = 0, merged_fallbacks = 0;   // runs that took the merged loop / that had to be repeated with the separate launches (icp_debug_counters)
-    bool ext_events = true;              // merged form: stage times from hipExtLaunchKernel's start / stop events (ICP_HIP_EXT_EVENTS=0: hipEventRecord brackets)
     bool keep_fused_records = false;     // icp_match_seeded: the fused matcher also writes its Match records and distances (the loop itself never reads them)
     bool lm_on = false; icp_lm_options lm_opt;   // icp_set_optimizer: the non-linear optimiser (k_lm_eval / k_lm_step) instead of the linear solve
     DevBuf lm_state, lm_partials, lm_sums;       // its minimiser state, eval partials, per-iteration records of the run in flight
@@ -315,13 +309,9 @@ int ensure_match_buffers(icp_ctx* c, int n) {
 // Morton order of the query positions [0, n) of a selection (sel == nullptr: the full source): out[t] = position.
 // rocPRIM sorts 370 k pairs with its MERGE sort (radix_sort_config's limit: 1 M items): a block sort and nine merge passes of two
 // launches each -- 19 launches of ~8 us per sort, four sorts per scan (three axis orders for the index, the Morton order of the queries).
-// ICP_SORT_MERGE_LIMIT=0 sends them to the Onesweep radix sort instead (a histogram launch and one pass per 8 key bits).  Measured
-// (round 3, same results -- both are stable): icp_set_target 1.34-1.39 ms against 1.31-1.35, the first icp_run (Morton sort of 64-bit
-// keys) 1.88 against 1.76-1.79 ms, a batch of 16 pairs 480-523 against 523-541 pairs/s: fewer launches, more time.  Merge sort stays.
-#ifndef ICP_SORT_MERGE_LIMIT
-#define ICP_SORT_MERGE_LIMIT (1024 * 1024)
-#endif
-using SortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, ICP_SORT_MERGE_LIMIT>;
+// rocPRIM's Onesweep radix sort instead (merge limit 0: a histogram launch and one pass per 8 key bits) was measured in round 3 and set
+// aside: fewer launches, more time (icp_set_target 1.34-1.39 against 1.31-1.35 ms, a batch of 16 pairs 480-523 against 523-541 pairs/s).
+using SortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 1024 * 1024>;
 int build_query_order(icp_ctx* c, const int* d_sel, int n, DevBuf& out) {
     int rc;
     if ((rc = ensure(c, c->okeys, (size_t)n * 8))) return rc;
@@ -353,81 +343,57 @@ int build_bvh(icp_ctx* c, Bvh& b, const CoordPtrs<DIM>& cp) {
     const int n_inner = b.Lp - 1;
     const int n_slots = (b.n_leaves > 0 ? b.n_leaves : 1) * BVH_LEAF;
     const int cap = nv > 0 ? nv : 1;
-    if ((rc = ensure(c, b.keys, (size_t)cap * 8))) return rc;
-    if ((rc = ensure(c, b.keys2, (size_t)cap * 8))) return rc;
+    if ((rc = ensure(c, b.keys, (size_t)cap * 4))) return rc;
+    if ((rc = ensure(c, b.keys2, (size_t)cap * 4))) return rc;
     if ((rc = ensure(c, b.vals, (size_t)cap * 4))) return rc;
     if ((rc = ensure(c, b.vals2, (size_t)cap * 4))) return rc;
     if ((rc = ensure(c, b.leaves, (size_t)(n_slots / BVH_LEAF) * sizeof(BvhLeafT<DIM>)))) return rc;
     if ((rc = ensure(c, b.recs, (size_t)n_slots * sizeof(TgtRec)))) return rc;
     if ((rc = ensure(c, b.pos_of, (size_t)(b.n_ids > 0 ? b.n_ids : 1) * 4))) return rc;      // position by original index (knn_walk_shared, XW)
     if ((rc = ensure(c, b.nodes, (size_t)(n_inner > 0 ? n_inner : 1) * sizeof(BvhNodeT<DIM>)))) return rc;
-    if ((rc = ensure(c, b.lvl, (size_t)(b.Lp > 1 ? b.Lp / 2 : 1) * 2 * DIM * 4))) return rc;
-    if ((rc = ensure(c, b.wbox, (size_t)((cap + 63) / 64) * 2 * DIM * 4))) return rc;
     int* perm = b.vals.as<int>(); int* perm2 = b.vals2.as<int>();
     if (nv > 0) {
         // finite targets in index order (device list from icp_set_target)
         HIPCK(c, hipMemcpyAsync(perm, b.d_finite, (size_t)nv * 4, hipMemcpyDeviceToDevice, c->stream));
-        size_t temp_bytes = 0;
-        HIPCK(c, rocprim::radix_sort_pairs<SortCfg>(nullptr, temp_bytes, b.keys.as<unsigned long long>(), b.keys2.as<unsigned long long>(), perm, perm2, (size_t)nv, 0, 64, c->stream));
-        if ((rc = ensure(c, b.temp, temp_bytes))) return rc;
         const int gb = (nv + 255) / 256;
-        int d_first = 0;
-        if (c->presort && c->block_levels) {
-            // upper levels (slices > 2048 points) from presorted axes: see dev_bvh.hpp
-            int n_upper = 0;
-            for (int d = 0; d < depth; d++) { int sh = 0; { long long seg = (long long)BVH_LEAF * b.Lp >> d; while ((1LL << sh) < seg) sh++; } if (sh <= 11) break; n_upper++; }
-            if (n_upper > 0) {
-                for (int k = 0; k < 2 * DIM; k++) if ((rc = ensure(c, b.axl[k], (size_t)cap * 4))) return rc;
-                if ((rc = ensure(c, b.side, (size_t)(b.n_ids > 0 ? b.n_ids : 1)))) return rc;
-                if ((rc = ensure(c, b.axis_of_node, (size_t)1 << n_upper))) return rc;
-                unsigned int* k32 = b.keys.as<unsigned int>(); unsigned int* k32b = b.keys2.as<unsigned int>();
-                size_t tb = 0;
-                HIPCK(c, rocprim::radix_sort_pairs<SortCfg>(nullptr, tb, k32, k32b, perm, perm2, (size_t)nv, 0, 32, c->stream));
-                if ((rc = ensure(c, b.temp, tb > temp_bytes ? tb : temp_bytes))) return rc;
-                const int nblk = (nv + PRS_THREADS - 1) / PRS_THREADS;
-                if ((rc = ensure(c, b.scanr, (size_t)2 * DIM * nblk * 4))) return rc;
-                int* blk_cnt = b.scanr.as<int>(); int* blk_off = blk_cnt + (size_t)DIM * nblk;
-                int* cur[DIM]; int* alt[DIM];
-                for (int k = 0; k < DIM; k++) {           // one stable sort per axis (ids arrive in increasing order: ties keep index order)
-                    cur[k] = b.axl[k].as<int>(); alt[k] = b.axl[DIM + k].as<int>();
-                    hipLaunchKernelGGL(k_axis_keys, dim3(gb), dim3(256), 0, c->stream, cp.c[k], b.d_finite, nv, k32);
-                    HIPCK(c, rocprim::radix_sort_pairs<SortCfg>(b.temp.p, tb, k32, k32b, b.d_finite, cur[k], (size_t)nv, 0, 32, c->stream));
-                }
-                for (int d = 0; d < n_upper; d++) {
-                    int sh = 0; { long long seg = (long long)BVH_LEAF * b.Lp >> d; while ((1LL << sh) < seg) sh++; }
-                    AxisLists<DIM> al, ao; for (int k = 0; k < DIM; k++) { al.L[k] = cur[k]; ao.L[k] = alt[k]; }
-                    const int n_nodes = 1 << d;
-                    hipLaunchKernelGGL(k_presort_axis<DIM>, dim3((n_nodes + 255) / 256), dim3(256), 0, c->stream, cp, al, nv, sh, n_nodes, b.axis_of_node.as<unsigned char>());
-                    hipLaunchKernelGGL(k_presort_side<DIM>, dim3(gb), dim3(256), 0, c->stream, al, nv, sh, b.axis_of_node.as<unsigned char>(), b.side.as<unsigned char>());
-                    hipLaunchKernelGGL(k_presort_count<DIM>, dim3(nblk, DIM), dim3(PRS_THREADS), 0, c->stream, al, b.side.as<unsigned char>(), nv, blk_cnt);
-                    hipLaunchKernelGGL(k_presort_blockscan, dim3(DIM), dim3(1024), 0, c->stream, blk_cnt, nblk, blk_off);
-                    hipLaunchKernelGGL(k_presort_scatter<DIM>, dim3(nblk, DIM), dim3(PRS_THREADS), 0, c->stream, al, b.side.as<unsigned char>(), blk_off, nv, sh, ao);
-                    for (int k = 0; k < DIM; k++) { int* t = cur[k]; cur[k] = alt[k]; alt[k] = t; }
-                }
-                HIPCK(c, hipMemcpyAsync(perm, cur[0], (size_t)nv * 4, hipMemcpyDeviceToDevice, c->stream));      // any list: the block kernel sorts inside its slices
-                HIPCK(c, hipGetLastError());
-                d_first = n_upper;
+        // segment (node) size at level d in points: BVH_LEAF * Lp / 2^d = 1 << seg_shift(d)
+        auto seg_shift = [&](int d) { int sh = 0; const long long seg = (long long)BVH_LEAF * b.Lp >> d; while ((1LL << sh) < seg) sh++; return sh; };
+        // upper levels (slices > 2048 points) from presorted axes: see dev_bvh.hpp
+        int n_upper = 0;
+        while (n_upper < depth && seg_shift(n_upper) > 11) n_upper++;
+        if (n_upper > 0) {
+            for (int k = 0; k < 2 * DIM; k++) if ((rc = ensure(c, b.axl[k], (size_t)cap * 4))) return rc;
+            if ((rc = ensure(c, b.side, (size_t)(b.n_ids > 0 ? b.n_ids : 1)))) return rc;
+            if ((rc = ensure(c, b.axis_of_node, (size_t)1 << n_upper))) return rc;
+            unsigned int* k32 = b.keys.as<unsigned int>(); unsigned int* k32b = b.keys2.as<unsigned int>();
+            size_t tb = 0;
+            HIPCK(c, rocprim::radix_sort_pairs<SortCfg>(nullptr, tb, k32, k32b, perm, perm2, (size_t)nv, 0, 32, c->stream));
+            if ((rc = ensure(c, b.temp, tb))) return rc;
+            const int nblk = (nv + PRS_THREADS - 1) / PRS_THREADS;
+            if ((rc = ensure(c, b.scanr, (size_t)2 * DIM * nblk * 4))) return rc;
+            int* blk_cnt = b.scanr.as<int>(); int* blk_off = blk_cnt + (size_t)DIM * nblk;
+            int* cur[DIM]; int* alt[DIM];
+            for (int k = 0; k < DIM; k++) {           // one stable sort per axis (ids arrive in increasing order: ties keep index order)
+                cur[k] = b.axl[k].as<int>(); alt[k] = b.axl[DIM + k].as<int>();
+                hipLaunchKernelGGL(k_axis_keys, dim3(gb), dim3(256), 0, c->stream, cp.c[k], b.d_finite, nv, k32);
+                HIPCK(c, rocprim::radix_sort_pairs<SortCfg>(b.temp.p, tb, k32, k32b, b.d_finite, cur[k], (size_t)nv, 0, 32, c->stream));
             }
+            for (int d = 0; d < n_upper; d++) {
+                const int sh = seg_shift(d);
+                AxisLists<DIM> al, ao; for (int k = 0; k < DIM; k++) { al.L[k] = cur[k]; ao.L[k] = alt[k]; }
+                const int n_nodes = 1 << d;
+                hipLaunchKernelGGL(k_presort_axis<DIM>, dim3((n_nodes + 255) / 256), dim3(256), 0, c->stream, cp, al, nv, sh, n_nodes, b.axis_of_node.as<unsigned char>());
+                hipLaunchKernelGGL(k_presort_side<DIM>, dim3(gb), dim3(256), 0, c->stream, al, nv, sh, b.axis_of_node.as<unsigned char>(), b.side.as<unsigned char>());
+                hipLaunchKernelGGL(k_presort_count<DIM>, dim3(nblk, DIM), dim3(PRS_THREADS), 0, c->stream, al, b.side.as<unsigned char>(), nv, blk_cnt);
+                hipLaunchKernelGGL(k_presort_blockscan, dim3(DIM), dim3(1024), 0, c->stream, blk_cnt, nblk, blk_off);
+                hipLaunchKernelGGL(k_presort_scatter<DIM>, dim3(nblk, DIM), dim3(PRS_THREADS), 0, c->stream, al, b.side.as<unsigned char>(), blk_off, nv, sh, ao);
+                for (int k = 0; k < DIM; k++) { int* t = cur[k]; cur[k] = alt[k]; alt[k] = t; }
+            }
+            HIPCK(c, hipMemcpyAsync(perm, cur[0], (size_t)nv * 4, hipMemcpyDeviceToDevice, c->stream));      // any list: the block kernel sorts inside its slices
+            HIPCK(c, hipGetLastError());
         }
-        for (int d = d_first; d < depth; d++) {
-            // segment (node) size at level d in points: BVH_LEAF * Lp / 2^d  = 1 << seg_shift
-            int seg_shift = 0; { long long seg = (long long)BVH_LEAF * b.Lp >> d; while ((1LL << seg_shift) < seg) seg_shift++; }
-            if (c->block_levels && seg_shift <= 11) {        // slices of <= 2048 points: all remaining levels inside LDS, one launch
-                hipLaunchKernelGGL(k_bvh_block_levels<DIM>, dim3((nv + BLV_POINTS - 1) / BLV_POINTS), dim3(BLV_THREADS), 0, c->stream, cp, perm, nv, seg_shift, perm2);
-                int* t = perm; perm = perm2; perm2 = t;
-                break;
-            }
-            const int n_nodes = 1 << d;
-            if (seg_shift >= 6) {            // wave-aligned segments: per-wave boxes, then one wave per node folds them
-                const int n_waves = (nv + 63) / 64;
-                hipLaunchKernelGGL(k_bvh_wave_boxes<DIM>, dim3(gb), dim3(256), 0, c->stream, cp, perm, nv, 6, b.wbox.as<unsigned int>());
-                hipLaunchKernelGGL(k_bvh_node_boxes<DIM>, dim3((n_nodes * 64 + 255) / 256), dim3(256), 0, c->stream, b.wbox.as<unsigned int>(), n_waves, seg_shift - 6, n_nodes,
-                                   b.lvl.as<unsigned int>());
-            } else {                         // sub-wave segments (last levels): the segment heads write the node boxes directly
-                hipLaunchKernelGGL(k_bvh_wave_boxes<DIM>, dim3(gb), dim3(256), 0, c->stream, cp, perm, nv, seg_shift, b.lvl.as<unsigned int>());
-            }
-            hipLaunchKernelGGL(k_bvh_level_keys<DIM>, dim3(gb), dim3(256), 0, c->stream, cp, perm, nv, seg_shift, b.lvl.as<unsigned int>(), b.keys.as<unsigned long long>());
-            HIPCK(c, rocprim::radix_sort_pairs<SortCfg>(b.temp.p, temp_bytes, b.keys.as<unsigned long long>(), b.keys2.as<unsigned long long>(), perm, perm2, (size_t)nv, 0, 32 + d, c->stream));
+        if (n_upper < depth) {                       // slices of <= 2048 points: all remaining levels inside LDS, one launch
+            hipLaunchKernelGGL(k_bvh_block_levels<DIM>, dim3((nv + BLV_POINTS - 1) / BLV_POINTS), dim3(BLV_THREADS), 0, c->stream, cp, perm, nv, seg_shift(n_upper), perm2);
             int* t = perm; perm = perm2; perm2 = t;
         }
     }
@@ -486,15 +452,14 @@ int launch_bvh_query(icp_ctx* c, Bvh& b, const CoordPtrs<DIM>& cp, const KnnPara
     BvhViewT<DIM> bv; bv.leaves = b.leaves.as<BvhLeafT<DIM>>(); bv.nodes = b.nodes.as<BvhNodeT<DIM>>(); bv.n_valid = b.n_valid; bv.Lp = b.Lp; bv.tgt = cp;
     bv.qnodes = b.qnodes.as<BvhQuadT<DIM>>(); bv.Lq = b.Lq; bv.recs = b.recs.as<TgtRec>(); bv.pos_of = b.pos_of.as<int>();
     const int nb = fuse ? fused_nblocks(n) : (n + BVH_THREADS - 1) / BVH_THREADS;
-    const size_t stack_bytes = (size_t)(ICP_SHARE_WALKS ? ICP_SHARE_ROWS : 1) * BVH_THREADS * 8;          // the shared walk's records in LDS
+    const size_t stack_bytes = (size_t)ICP_SHARE_ROWS * BVH_THREADS * 8;          // the shared walk's records in LDS
     if (fuse) {
         if ((rc = ensure(c, c->partials, (size_t)(nb > POST_BLOCKS ? nb : POST_BLOCKS) * NSUM * 8))) return rc;
         PostParams pp = make_post_params(c, *fuse, kp.sel, n);
         KnnParams kf = kp; kf.out = nullptr;
         if (!c->keep_fused_records) { pp.matches = nullptr; kf.d2_out = nullptr; }     // the loop never reads the records of a fused iteration, nor the distances
         const size_t red_bytes = (size_t)(BVH_THREADS / WAVE) * 33 * 8;           // the reduction reuses the (dead) traversal stacks
-        static const size_t lds_pad = getenv("ICP_HIP_LDS_PAD") ? (size_t)atoi(getenv("ICP_HIP_LDS_PAD")) : 0;      // development: fewer resident blocks per CU
-        const size_t lds = (stack_bytes > red_bytes ? stack_bytes : red_bytes) + xw_lds_bytes<DIM, BVH_THREADS>() + lds_pad;      // + the board of the cross-wave hand-over
+        const size_t lds = (stack_bytes > red_bytes ? stack_bytes : red_bytes) + xw_lds_bytes<DIM, BVH_THREADS>();      // + the board of the cross-wave hand-over
         if (ml) {                                                                  // merged loop: reducer blocks in front, pose through the ring
             kf.ps = ml->slot; pp.ps = ml->slot; pp.partials = ml->partials; kf.fault = ml->rp.run_fault;
             if (ml->ev_start) {
@@ -551,7 +516,7 @@ int launch_match(icp_ctx* c, const QuerySet& q, int* fused_blocks = nullptr, con
         kp.dbg_steps = c->dbg_steps.as<int>(); kp.dbg_waves = fused_nblocks(q.n) * (BVH_THREADS / WAVE);
 #endif
         if (p.knn_incremental && !q.pretransformed) {
-            kp.qstate = c->qstate.as<float4>(); kp.qstate2 = c->tier2 ? c->qstate2.as<float2>() : nullptr; kp.incremental = 1;
+            kp.qstate = c->qstate.as<float4>(); kp.qstate2 = c->qstate2.as<float2>(); kp.incremental = 1;
         }
         const Cloud* fuse = (fused_blocks != nullptr && p.metric != ICP_METRIC_SYMMETRIC && p.metric != ICP_METRIC_GICP && p.metric != ICP_METRIC_COLORED && !q.pretransformed) ? q.cl : nullptr;
         if (q.use_colors) return launch_bvh_query<6>(c, c->bvh6, target_coords6(c), kp, q.order, q.n, fuse, fused_blocks, fuse ? ml : nullptr);
@@ -584,7 +549,7 @@ int rearm_handover(icp_ctx* c) {
     int rc;
     if ((rc = ensure(c, c->totals, NSUM * 8 + 8))) return rc;
     HIPCK(c, hipMemsetAsync(c->totals.p, 0, NSUM * 8 + 8, c->stream));
-    if (c->spin_reduce) hipLaunchKernelGGL(k_fill_u64, dim3(1), dim3(64), 0, c->stream, c->totals.as<unsigned long long>(), NSUM, TOTAL_SENTINEL);
+    hipLaunchKernelGGL(k_fill_u64, dim3(1), dim3(64), 0, c->stream, c->totals.as<unsigned long long>(), NSUM, TOTAL_SENTINEL);
     HIPCK(c, hipGetLastError());
     return ICP_OK;
 }
@@ -669,7 +634,7 @@ int launch_post_and_solve(icp_ctx* c, const Cloud& src, const int* sel, int n, i
     sp.partials = c->partials.as<double>(); sp.nblocks = nb; sp.ps = c->ps.as<PoseState>();
     sp.metric = (p.metric == ICP_METRIC_GICP || p.metric == ICP_METRIC_COLORED) ? ICP_METRIC_POINT_TO_PLANE : p.metric;
     sp.totals = c->totals.as<double>(); sp.ticket = (unsigned*)(c->totals.as<double>() + NSUM);
-    sp.n_src = n; sp.update_pose = update_pose; sp.spin = c->spin_reduce ? 1 : 0;
+    sp.n_src = n; sp.update_pose = update_pose; sp.spin = 1;
     auto reduce_solve = [&]() { hipLaunchKernelGGL(k_reduce_solve, dim3(NSUM_USED), dim3(SOLVE_THREADS), 0, c->stream, sp); };
     if (p.metric == ICP_METRIC_SYMMETRIC) {
         sp.phase = 0; sp.stats = nullptr; sp.sums_out = nullptr;
@@ -1069,13 +1034,7 @@ int icp_ctx_create_on_stream(int device, void* hip_stream, icp_ctx** out) {
     icp_params_default(&c->prm);
     memset(&c->timing, 0, sizeof(c->timing));
     if (hipSetDevice(device) != hipSuccess) { delete c; return ICP_ERR_HIP; }
-    { const char* e = getenv("ICP_HIP_FUSE_POST"); if (e && e[0] == '0') c->fuse_post = false; }
-    { const char* e = getenv("ICP_HIP_SPIN_REDUCE"); if (e) c->spin_reduce = e[0] == '1'; }
-    { const char* e = getenv("ICP_HIP_TIER2"); if (e && e[0] == '0') c->tier2 = false; }
     { const char* e = getenv("ICP_HIP_MERGE"); if (e && e[0] == '0') c->merge_loop = false; }
-    { const char* e = getenv("ICP_HIP_EXT_EVENTS"); if (e && e[0] == '0') c->ext_events = false; }
-    { const char* e = getenv("ICP_HIP_PRESORT"); if (e && e[0] == '0') c->presort = false; }
-    { const char* e = getenv("ICP_HIP_BLOCK_LEVELS"); if (e && e[0] == '0') c->block_levels = false; }
     { const char* e = getenv("ICP_HIP_TRACE"); if (e && e[0] == '1') c->trace = true; }
     { const char* e = getenv("ICP_HIP_STAGE_EVENTS"); if (e && e[0] >= '0' && e[0] <= '9') c->stage_timing = atoi(e); }
     if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->owns_stream = false; }
@@ -1100,8 +1059,8 @@ int icp_ctx_destroy(icp_ctx* c) {
     release(c->tgt); release(c->src); release(c->qry); release(c->conv_src); release(c->conv_ref);
     release(c->nrm_cloud);
     for (Bvh* b : {&c->bvh, &c->bvh6, &c->nrm_bvh}) { release(b->qnodes); release(b->recs); release(b->pos_of); for (DevBuf& d : b->axl) release(d); release(b->side); release(b->scanr); release(b->axis_of_node); }
-    for (Bvh* b : {&c->bvh6, &c->nrm_bvh}) { release(b->keys); release(b->keys2); release(b->vals); release(b->vals2); release(b->temp); release(b->leaves); release(b->nodes); release(b->lvl); release(b->wbox); }
-    release(c->bvh.keys); release(c->bvh.keys2); release(c->bvh.vals); release(c->bvh.vals2); release(c->bvh.temp); release(c->bvh.leaves); release(c->okeys); release(c->okeys2); release(c->ovals); release(c->otemp); release(c->bvh.nodes); release(c->bvh.lvl); release(c->bvh.wbox);
+    for (Bvh* b : {&c->bvh6, &c->nrm_bvh}) { release(b->keys); release(b->keys2); release(b->vals); release(b->vals2); release(b->temp); release(b->leaves); release(b->nodes); }
+    release(c->bvh.keys); release(c->bvh.keys2); release(c->bvh.vals); release(c->bvh.vals2); release(c->bvh.temp); release(c->bvh.leaves); release(c->okeys); release(c->okeys2); release(c->ovals); release(c->otemp); release(c->bvh.nodes);
     for (auto& kv : c->levels) release(kv.second);
     release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->totals); release(c->dbg_steps); release(c->sums);
     release(c->lm_state); release(c->lm_partials); release(c->lm_sums);
@@ -1268,7 +1227,7 @@ int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_
     if (p.metric == ICP_METRIC_GICP) { c->err = "icp_match_seeded: GICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
     if (p.metric == ICP_METRIC_COLORED) { c->err = "icp_match_seeded: colored ICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
     if (robust_on(c)) { c->err = "icp_match_seeded: robust mode (icp_set_robust_options) has no fused matcher"; return ICP_ERR_INVALID_ARG; }
-    if (p.matching != ICP_MATCH_KNN || p.knn_backend != ICP_KNN_LBVH || p.metric == ICP_METRIC_SYMMETRIC || !c->fuse_post) {
+    if (p.matching != ICP_MATCH_KNN || p.knn_backend != ICP_KNN_LBVH || p.metric == ICP_METRIC_SYMMETRIC) {
         c->err = "icp_match_seeded: needs k-NN matching on the LBVH backend with the fused point-to-point / point-to-plane matcher"; return ICP_ERR_INVALID_ARG;
     }
     int rc;
@@ -1471,7 +1430,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     // The merged loop (dev_solve.hpp, "the ring form"): point-to-plane through the fused BVH matcher on sorted levels, nothing else on
     // the stream between two iterations.  Launch i = [reducer of iteration i - 1 | matcher of iteration i]; one reducer-only launch closes
     // the run.  Pose slots and totals rows are written once per run; both rings are reset here, so nothing survives an aborted run.
-    bool merged = !lm && !robust && c->merge_loop && !single && iters >= 2 && sorted_levels && c->fuse_post && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
+    bool merged = !lm && !robust && c->merge_loop && !single && iters >= 2 && sorted_levels && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
     for (int i = 0; merged && i < iters; i++) if (ns[i] <= 0) merged = false;
     PoseState* slots = nullptr; unsigned long long* trows = nullptr; int* run_fault = nullptr;
     if (merged) {
@@ -1495,8 +1454,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     for (int i = 0; i < iters; i++) sampled[i] = tmode == 1 || (tmode > 1 && (i + (int)(c->timing_phase % (unsigned)tmode)) % tmode == 0);
     c->timing_phase++;
     auto E = [&](int i, int k) { return c->events[(size_t)2 + 4 * i + k]; };
-    auto end_event = [&](int i) { return (merged && i < iters - 1) ? E(i, 1) : E(i, 3); };
-    auto start_event = [&](int i) { return (i > 0 && sampled[i - 1] && !(merged && c->ext_events)) ? end_event(i - 1) : E(i, 0); };
+    auto start_event = [&](int i) { return (!merged && i > 0 && sampled[i - 1]) ? E(i - 1, 3) : E(i, 0); };
     auto ring_params = [&](int i) {                      // the reducer of iteration i - 1, riding in launch i (i = iters: the closing launch)
         RingParams rp; memset(&rp, 0, sizeof(rp));
         rp.run_fault = run_fault;
@@ -1514,8 +1472,8 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
     for (int i = 0; i < iters; i++) {
         icp_iter_stats* d_st = c->stats.as<icp_iter_stats>() + i;
         const bool ev = sampled[i] != 0;
-        const bool ext_ev = ev && merged && ns[i] > 0 && c->ext_events;      // merged form: the launch's own start / stop times, no bracket on the stream
-        if (ev && !ext_ev && !(i > 0 && sampled[i - 1] && !c->ext_events)) HIPCK(c, hipEventRecord(E(i, 0), c->stream));
+        const bool ext_ev = ev && merged && ns[i] > 0;      // merged form: the launch's own start / stop times, no bracket on the stream
+        if (ev && !ext_ev) HIPCK(c, hipEventRecord(E(i, 0), c->stream));
         if (ns[i] > 0) {
             // seed the search with the previous iteration's neighbours when it matched the same queries (same level)
             const bool seed = i > 0 && factors[i] == factors[i - 1] && ns[i - 1] > 0 && p.selection == 0;
@@ -1524,7 +1482,7 @@ static int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int
             MergeLaunch ml;
             if (merged) { ml.rp = ring_params(i); ml.slot = loop_slot(slots, i, 0); ml.partials = (i & 1) ? c->partials2.as<double>() : c->partials.as<double>(); }
             if (ext_ev) { ml.ev_start = E(i, 0); ml.ev_stop = E(i, 1); }
-            if ((rc = launch_match(c, q, (c->fuse_post && !robust) ? &fused : nullptr, merged ? &ml : nullptr))) return rc;
+            if ((rc = launch_match(c, q, !robust ? &fused : nullptr, merged ? &ml : nullptr))) return rc;
             if (merged && !fused) { c->err = "merged loop: the matcher did not take the fused path"; return ICP_ERR_HIP; }
             if (ev && !ext_ev) HIPCK(c, hipEventRecord(E(i, 1), c->stream));
             // fused epilogue: there is no separate post stage to bracket
@@ -1807,7 +1765,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
     if (!c->bvh.valid && (rc = build_bvh<3>(c, c->bvh, target_coords3(c)))) return rc;
     const bool colors = p.color_icp != 0;
     if (colors && !c->bvh6.valid && (rc = build_bvh<6>(c, c->bvh6, target_coords6(c)))) return rc;
-    const bool fused = c->fuse_post && p.metric != ICP_METRIC_SYMMETRIC;
+    const bool fused = p.metric != ICP_METRIC_SYMMETRIC;
     // per-start slices, sized for the largest query set of the run
     int nmax = n_full, nbmax = POST_BLOCKS;
     for (int i = 0; i < iters; i++) { if (ns[i] > nmax) nmax = ns[i]; if (fused && fused_nblocks(ns[i]) > nbmax) nbmax = fused_nblocks(ns[i]); }
@@ -1845,7 +1803,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
                           v.qnodes = b.qnodes.as<BvhQuadT<3>>(); v.Lq = b.Lq; v.recs = b.recs.as<TgtRec>(); v.pos_of = b.pos_of.as<int>(); return v; };
     auto view6 = [&]() { BvhViewT<6> v; Bvh& b = c->bvh6; v.leaves = b.leaves.as<BvhLeafT<6>>(); v.nodes = b.nodes.as<BvhNodeT<6>>(); v.n_valid = b.n_valid; v.Lp = b.Lp; v.tgt = target_coords6(c);
                           v.qnodes = b.qnodes.as<BvhQuadT<6>>(); v.Lq = b.Lq; v.recs = b.recs.as<TgtRec>(); v.pos_of = b.pos_of.as<int>(); return v; };
-    const size_t stack_bytes = (size_t)(ICP_SHARE_WALKS ? ICP_SHARE_ROWS : 1) * BVH_THREADS * 8, red_bytes = (size_t)(BVH_THREADS / WAVE) * 33 * 8;
+    const size_t stack_bytes = (size_t)ICP_SHARE_ROWS * BVH_THREADS * 8, red_bytes = (size_t)(BVH_THREADS / WAVE) * 33 * 8;
     const size_t lds_fused = (stack_bytes > red_bytes ? stack_bytes : red_bytes) + (colors ? xw_lds_bytes<6, BVH_THREADS>() : xw_lds_bytes<3, BVH_THREADS>());
     for (int i = 0; i < iters; i++) {
         if (ns[i] <= 0) continue;                                // an empty iteration: nothing runs, the records are filled in below
@@ -1856,7 +1814,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
         kp.sel = sels[i]; kp.n = n;
         kp.nn_raw = c->ms_nn.as<int>();
         kp.use_prev = (i > 0 && factors[i] == factors[i - 1] && ns[i - 1] > 0 && p.selection == 0) ? 1 : 0;      // run_loop's seeding rule
-        if (p.knn_incremental) { kp.qstate = c->ms_st.as<float4>(); kp.qstate2 = c->tier2 ? c->ms_st2.as<float2>() : nullptr; kp.incremental = 1; }
+        if (p.knn_incremental) { kp.qstate = c->ms_st.as<float4>(); kp.qstate2 = c->ms_st2.as<float2>(); kp.incremental = 1; }
         PostParams pp = make_post_params(c, *q, sels[i], n);
         pp.ps = d_ps; pp.partials = c->ms_partials.as<double>();
         int nb;
@@ -2278,9 +2236,9 @@ static int transform_common(icp_ctx* c, const float* in, int32_t n, const float 
     HIPCK(c, hipStreamSynchronize(c->stream));
     return guard.done();
 }
-// Development builds (ICP_DEBUG_STEPS=1): nodes | leaves << 16 visited by the walk of each query of the LAST matcher launch, in the
-// order the launch indexed its queries (Morton order for a run); 0 = verified without a walk, -2 = second tier (two leaves), -1 = a walk whose length was not recorded.  Per-query lengths need
-// ICP_SHARE_WALKS=0 (a shared walk has no per-query length); with ICP_DEBUG_TIMES=1 the buffer holds per-wave phase stamps instead (tools/dev_wave_times.py).
+// Development builds (ICP_DEBUG_STEPS=1): how each query of the LAST matcher launch was resolved, in the order the launch indexed its
+// queries (Morton order for a run): 0 = verified without a walk, -2 = second tier (two leaves), -1 = a walk (a walk shared over the wave
+// has no per-query length); with ICP_DEBUG_TIMES=1 the buffer holds per-wave phase stamps instead (tools/dev_wave_times.py).
 int icp_debug_steps(icp_ctx* c, int32_t* out, int32_t n) {
     if (!c || !out || n <= 0 || !c->dbg_steps.p || (size_t)n * 4 > c->dbg_steps.cap) return ICP_ERR_INVALID_ARG;
     int rc;

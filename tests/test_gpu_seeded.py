@@ -206,7 +206,7 @@ def test_seeded_search_point_to_point_on_tie_clouds_vs_brute_force_oracle(gpu_ct
 
 @pytest.mark.parametrize("seed", range(3))
 def test_seeded_search_lone_walkers_small_and_huge_radius(gpu_ctx_factory, orc, seed):
-    """Waves with exactly ONE walker take the level-synchronous search (knn_walk_shared, ICP_LONE_WALK): most queries sit on the target
+    """Waves with exactly ONE walker take the level-synchronous search (knn_walk_shared, the lone walker): most queries sit on the target
     surface and verify from the second launch on; a sprinkling of queries on the bisector of two targets keeps walking with a small
     radius (the frontier stays small: the lone search completes), a few far outliers keep walking with a larger one, and one query sits at the centre
     of a spherical shell of 4 000 targets (every box of the shell survives: the frontier overflows and the wave must start over on the general

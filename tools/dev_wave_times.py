@@ -61,7 +61,7 @@ for iters in [int(a) for a in sys.argv[1:]] or [1, 3, 6, 12, 45]:
         print("  placement of hardware blocks 0, 8, 16, ...: " + " ".join("%d:%d" % s_ for s_ in seq))
         seq1 = [(int(simd[2 * logical(b)] // 4096), int((simd[2 * logical(b)] // 4) % 1024)) for b in range(0, 24)]
         print("  placement of hardware blocks 0..23: " + " ".join("%d:%d" % s_ for s_ in seq1))
-    # which XCD ran which logical block (xcd_contiguous_block with ICP_XCD_CHUNK = 16): is one of them the tail?
+    # which XCD ran which logical block (xcd_contiguous_block: chunks of 16 blocks): is one of them the tail?
     NWB = BT // 64; nb = nw // NWB; CH = 16; full = nb // (8 * CH) * (8 * CH)
     lbs = np.arange(nw) % nb if os.environ.get('ICP_DEV_STRIDE', '1') == '1' and NWB > 1 else np.arange(nw) // NWB      # logical block of every wave slot
     wx = np.where(lbs < full, (lbs // CH) % 8, lbs % 8)
