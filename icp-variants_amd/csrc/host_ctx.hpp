@@ -1,0 +1,284 @@
+// host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
+// and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_debug.
+using namespace icpdev;
+
+#define HIPCK(ctx, expr)                                                                        \
+    do {                                                                                        \
+        hipError_t e__ = (expr);                                                                \
+        if (e__ != hipSuccess) {                                                                \
+            char buf__[256];                                                                    \
+            snprintf(buf__, sizeof(buf__), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            (ctx)->err = buf__;                                                                 \
+            return ICP_ERR_HIP;                                                                 \
+        }                                                                                       \
+    } while (0)
+
+namespace {
+struct DevBuf {
+    void* p = nullptr; size_t cap = 0;
+    bool view = false;                   // part of another allocation (a plane of a packed level, a section of the search-state pack): never freed on its own
+    template <class T> T* as() const { return (T*)p; }
+};
+
+struct Cloud {
+    int n = 0, npad = 0;
+    DevBuf x, y, z, nx, ny, nz, cr, cg, cb, rgba;
+    bool has_normals = false, has_colors = false;
+};
+
+// One resolution level of the source: the selection (original indices, increasing), and -- for the BVH matcher -- a physical
+// copy of the selected points in Morton order, so that everything the ICP loop touches per query (source planes, search
+// state, matches) is indexed by the same sorted position and streams coalesced.  factor 0 = the whole cloud, unfiltered.
+struct Level { DevBuf idx; DevBuf order; DevBuf sorted_idx; DevBuf pack; Cloud sorted; bool sorted_valid = false; int n = 0; };   // pack: the sorted copy's planes in ONE allocation (x y z nx ny nz cr cg cb rgba, a fixed stride apart)
+
+// LBVH over the target (buildIndex): device buffers + the host-side facts needed to launch the build.
+struct Bvh {
+    bool valid = false;
+    int n_valid = 0, n_leaves = 0, Lp = 1;
+    DevBuf keys, keys2, vals, vals2, temp, leaves, recs, nodes, qnodes, pos_of;
+    DevBuf axl[12], side, scanr, axis_of_node;      // presorted-axes build: DIM index lists (ping-pong), side flag per point id, scan result, widest axis per node
+    int n_ids = 0;                                   // size of the id space the lists index (points of the cloud the tree is built over)
+    const Cloud* attrs = nullptr;                     // cloud whose normals / colours go into the records (nullptr: none)
+    int Lq = 0;                                       // 4-wide levels
+    const int* d_finite = nullptr;                    // device list of the finite points' indices, increasing (owned by the context)
+    double build_ms = 0.0;
+};
+}  // namespace
+
+struct icp_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool owns_stream = false;
+    int stage_timing = 1;                // icp_set_stage_timing: 0 none, 1 every iteration, N > 1 every Nth iteration (scaled)
+    unsigned timing_phase = 0;           // rotates the sampled iterations from run to run
+    void* pinned = nullptr; size_t pinned_cap = 0;   // page-locked host staging: pose upload, stats + pose download (truly asynchronous copies)
+    bool trace = false;                  // ICP_HIP_TRACE=1: per-iteration stage times on stderr
+    bool merge_loop = true;              // point-to-plane loop through the fused BVH matcher: reduce + solve ride in front of the next matcher launch (ICP_HIP_MERGE=0: separate k_reduce_solve launches)
+    int merged_runs = 0, merged_fallbacks = 0;   // runs that took the merged loop / that had to be repeated with the separate launches (icp_debug_counters)
+    bool lm_on = false; icp_lm_options lm_opt;   // icp_set_optimizer: the non-linear optimiser (k_lm_eval / k_lm_step) instead of the linear solve
+    DevBuf lm_state, lm_partials, lm_sums;       // its minimiser state, eval partials, per-iteration records of the run in flight
+    std::vector<icp_lm_summary> lm_last;         // the records of the last run (icp_get_lm_summaries)
+    DevBuf ms_ps, ms_nn, ms_st, ms_st2, ms_rec, ms_d2, ms_partials, ms_totals, ms_stats, ms_score, ms_res;   // icp_run_multistart: one slice per start (dev_multi.hpp)
+    icp_gicp_options gicp_opt = {1e-3f, 20};     // icp_set_gicp_options
+    DevBuf gicp_n[2][3], gicp_flag;              // GICP normals of the target [0] / source [1] (SoA, original order), finite flags of their scratch tree
+    bool gicp_ready[2] = {false, false};         // the cache is current (dropped by every call that replaces the cloud and by new options)
+    icp_colored_options col_opt = {0.968f, 20};  // icp_set_colored_options
+    DevBuf col_grad[3];                          // colour gradients of the target (SoA, original order, dev_colored.hpp)
+    bool col_ready = false;                      // the cache is current (dropped by every call that replaces the target and by new options)
+    icp_robust_options rob_opt = {ICP_ROBUST_NONE, 0.f, 0.f, 1.f};   // icp_set_robust_options
+    DevBuf rob_keys, rob_state, rob_stats;      // trimmed / robust mode (dev_robust.hpp): r^2 keys per query, the chain's state, per-iteration records
+    std::vector<icp_robust_stats> rob_last;      // the records of the last call (icp_get_robust_stats)
+    icp_params prm;
+    Cloud tgt, src, qry;                 // qry: scratch cloud of icp_query_matches
+    Cloud nrm_cloud; Bvh nrm_bvh;        // scratch of icp_estimate_normals
+    Bvh bvh, bvh6;                       // exact kd-ordered BVH of the target over xyz / over xyz+rgb (knn_backend == ICP_KNN_LBVH)
+    DevBuf src_flag, src_box;            // per source point: finite point && finite normal (PointCloud.h:334); bounding box of the finite points (ordered bits)
+    DevBuf tgt_flag, tgt_finite, nrm_finite, sel_temp, d_count;   // finite filters of the index builds, compaction scratch
+    void* pin_up = nullptr; size_t pin_up_cap = 0; hipEvent_t up_ev = nullptr; bool up_pending = false;   // page-locked upload staging + "copy has left it" event
+    DevBuf okeys, okeys2, ovals, otemp;  // scratch of the Morton sort of the queries
+    std::map<int, Level> levels;         // multires selections by decimation factor
+    DevBuf sel_lists, sel_counts, sel_blocks;            // RANDOM_SAMPLING: per-iteration index lists, their sizes, scan scratch
+    DevBuf qpack; size_t q_cap = 0;                      // nn_raw | qstate | qstate2 (views below), q_cap elements each
+    DevBuf qstate, qstate2;                              // incremental k-NN: per-query anchor + bound on the other targets; bound on the targets outside the neighbour's leaf
+    DevBuf dbg_steps;                    // development builds only (ICP_DEBUG_STEPS)
+    DevBuf ps, matches, d2, best64, nn_raw, partials, partials2, ring, totals, sums, stats, staging, rmse_partials, rmse_out, fontana_partials;
+    Cloud conv_src, conv_ref; int conv_n = 0;
+    // depth frames (icp_set_*_depth, icp_track_depth_frames): two upload slots, each a page-locked staging block + a device copy of
+    // [depth 4n | rgbx 4n]; the next frame of a sequence goes up on depth_stream while the current one iterates
+    void* depth_pin[2] = {nullptr, nullptr}; size_t depth_pin_cap[2] = {0, 0}; DevBuf depth_dev[2]; hipEvent_t depth_up[2] = {nullptr, nullptr}; bool depth_pending[2] = {false, false};
+    hipStream_t depth_stream = nullptr;
+    DevBuf depth_blocks, track_rmse;     // block counts / offsets of the depth compaction; per-frame initial + final RMSE of a tracked sequence
+    PoseState* pin_track = nullptr;      // page-locked pose staging of a tracked frame's initial / final RMSE: two slots of its own, apart from `pinned`
+    float cos_reject = 0.5f;
+    std::vector<hipEvent_t> events;
+    hipEvent_t build_ev[2] = {nullptr, nullptr};   // index-build bracket (build_bvh)
+    icp_timing timing;
+    std::vector<float> it_match_ms, it_post_ms, it_solve_ms;   // per iteration of the last run; -1 where the iteration was not bracketed
+    std::string err;
+};
+
+namespace {
+constexpr int POST_BLOCKS = 512;
+
+// Device bytes held through ensure / release by every context of the process (views not counted): icp_debug_live_bytes.
+std::atomic<long long> g_live_bytes{0};
+
+int ensure(icp_ctx* c, DevBuf& b, size_t bytes) {
+    if (bytes <= b.cap && b.p) return ICP_OK;
+    if (b.view) { b.p = nullptr; b.cap = 0; b.view = false; }      // outgrown: becomes an allocation of its own
+    if (b.p) { HIPCK(c, hipFree(b.p)); g_live_bytes -= (long long)b.cap; b.p = nullptr; b.cap = 0; }
+    size_t want = bytes < 256 ? 256 : bytes;
+    HIPCK(c, hipMalloc(&b.p, want));
+    b.cap = want; g_live_bytes += (long long)want;
+    return ICP_OK;
+}
+int ensure_pinned(icp_ctx* c, size_t bytes) {
+    if (bytes <= c->pinned_cap && c->pinned) return ICP_OK;
+    if (c->pinned) { HIPCK(c, hipHostFree(c->pinned)); c->pinned = nullptr; c->pinned_cap = 0; }
+    const size_t want = bytes < 4096 ? 4096 : bytes;
+    HIPCK(c, hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
+    c->pinned_cap = want;
+    return ICP_OK;
+}
+void release(DevBuf& b) { if (b.p && !b.view) { (void)hipFree(b.p); g_live_bytes -= (long long)b.cap; } b.p = nullptr; b.cap = 0; b.view = false; }
+void set_view(DevBuf& b, void* p, size_t bytes) { release(b); b.p = p; b.cap = bytes; b.view = true; }
+void release(Cloud& c) { release(c.x); release(c.y); release(c.z); release(c.nx); release(c.ny); release(c.nz); release(c.cr); release(c.cg); release(c.cb); release(c.rgba); }
+void release(Level& lv) { release(lv.idx); release(lv.order); release(lv.sorted_idx); release(lv.sorted); release(lv.pack); lv.sorted_valid = false; }
+
+// Largest float c with (double)acosf(c) > 60*pi/180 on THIS host's libm: the device rejection test
+// `c <= cos_reject` is then bit-identical to the reference's `acos(c) > threshold` (ICPOptimizer.h:161,170)
+// as evaluated by the host the reference would run on (acosf is monotone on [0.25, 0.75]).
+float compute_cos_reject() {
+    const double threshold = 60 * 3.141592653589793238462643383279502884 / 180.0;
+    uint32_t lo, hi; float flo = 0.25f, fhi = 0.75f;
+    memcpy(&lo, &flo, 4); memcpy(&hi, &fhi, 4);       // predicate true at lo, false at hi
+    while (hi - lo > 1) {
+        uint32_t mid = lo + (hi - lo) / 2; float fm; memcpy(&fm, &mid, 4);
+        if ((double)acosf(fm) > threshold) lo = mid; else hi = mid;
+    }
+    float r; memcpy(&r, &lo, 4);
+    return r;
+}
+
+int set_device(icp_ctx* c) { HIPCK(c, hipSetDevice(c->device)); return ICP_OK; }
+
+// Every entry point that enqueues work synchronises the stream before it returns (write_pose's contract: the page-locked staging
+// area and the scratch buffers are free again by the next call).  On the success paths that is the entry point's own final
+// hipStreamSynchronize; this guard covers the error returns in between.
+struct DrainOnError {
+    icp_ctx* c; bool ok = false;
+    explicit DrainOnError(icp_ctx* ctx) : c(ctx) {}
+    ~DrainOnError() { if (!ok && c && c->stream) (void)hipStreamSynchronize(c->stream); }
+    int done(int rc = ICP_OK) { ok = (rc == ICP_OK); return rc; }
+};
+
+// Host clouds -> device SoA planes.  The whole cloud (points, normals, colours) goes through ONE page-locked staging buffer and
+// ONE asynchronous copy, the AoS -> SoA kernels follow on the stream, and nothing here waits for the device: the only host-side
+// wait is for the previous upload to have left the staging buffer.  (Round 1: pageable copies + one synchronisation per plane.)
+int ensure_pin_up(icp_ctx* c, size_t bytes) {
+    if (c->up_pending) { HIPCK(c, hipEventSynchronize(c->up_ev)); c->up_pending = false; }
+    if (bytes <= c->pin_up_cap && c->pin_up) return ICP_OK;
+    if (c->pin_up) { HIPCK(c, hipHostFree(c->pin_up)); c->pin_up = nullptr; c->pin_up_cap = 0; }
+    const size_t want = bytes < 65536 ? 65536 : bytes + bytes / 8;
+    HIPCK(c, hipHostMalloc(&c->pin_up, want, hipHostMallocDefault));
+    c->pin_up_cap = want;
+    if (!c->up_ev) HIPCK(c, hipEventCreateWithFlags(&c->up_ev, hipEventDisableTiming));
+    return ICP_OK;
+}
+int upload_cloud(icp_ctx* c, Cloud& cl, const float* xyz, const float* nrm, const uint8_t* rgba, int n, bool pad_inf) {
+    const int npad = pad_inf ? ((n + 63) / 64) * 64 : n;
+    const size_t b_xyz = (size_t)n * 12, b_nrm = nrm ? (size_t)n * 12 : 0, b_col = rgba ? (size_t)n * 4 : 0, total = b_xyz + b_nrm + b_col;
+    int rc;
+    if ((rc = ensure_pin_up(c, total))) return rc;
+    if ((rc = ensure(c, c->staging, total))) return rc;
+    char* h = (char*)c->pin_up;
+    memcpy(h, xyz, b_xyz);
+    if (nrm) memcpy(h + b_xyz, nrm, b_nrm);
+    if (rgba) memcpy(h + b_xyz + b_nrm, rgba, b_col);
+    HIPCK(c, hipMemcpyAsync(c->staging.p, h, total, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(c->up_ev, c->stream)); c->up_pending = true;
+    const char* d = c->staging.as<char>();
+    const dim3 g((npad + 255) / 256), b(256);
+    for (DevBuf* pl : {&cl.x, &cl.y, &cl.z}) if ((rc = ensure(c, *pl, (size_t)npad * 4))) return rc;
+    hipLaunchKernelGGL(k_deinterleave3, g, b, 0, c->stream, (const float*)d, n, npad, INFINITY, cl.x.as<float>(), cl.y.as<float>(), cl.z.as<float>());
+    cl.has_normals = nrm != nullptr;
+    if (nrm) {
+        for (DevBuf* pl : {&cl.nx, &cl.ny, &cl.nz}) if ((rc = ensure(c, *pl, (size_t)n * 4))) return rc;
+        hipLaunchKernelGGL(k_deinterleave3, dim3((n + 255) / 256), b, 0, c->stream, (const float*)(d + b_xyz), n, n, 0.f, cl.nx.as<float>(), cl.ny.as<float>(), cl.nz.as<float>());
+    }
+    cl.has_colors = rgba != nullptr;
+    if (rgba) {
+        for (DevBuf* pl : {&cl.rgba, &cl.cr, &cl.cg, &cl.cb}) if ((rc = ensure(c, *pl, (size_t)npad * 4))) return rc;
+        hipLaunchKernelGGL(k_colors, g, b, 0, c->stream, (const uint8_t*)(d + b_xyz + b_nrm), n, npad, cl.rgba.as<uint32_t>(), cl.cr.as<float>(), cl.cg.as<float>(), cl.cb.as<float>());
+    }
+    HIPCK(c, hipGetLastError());
+    cl.n = n; cl.npad = npad;
+    return ICP_OK;
+}
+// one plane triple through the same staging path (convergence reference)
+int upload3(icp_ctx* c, const float* aos, int n, int npad, float pad_value, DevBuf& x, DevBuf& y, DevBuf& z) {
+    int rc;
+    if ((rc = ensure_pin_up(c, (size_t)n * 12))) return rc;
+    if ((rc = ensure(c, c->staging, (size_t)n * 12))) return rc;
+    for (DevBuf* pl : {&x, &y, &z}) if ((rc = ensure(c, *pl, (size_t)npad * 4))) return rc;
+    memcpy(c->pin_up, aos, (size_t)n * 12);
+    HIPCK(c, hipMemcpyAsync(c->staging.p, c->pin_up, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(c->up_ev, c->stream)); c->up_pending = true;
+    hipLaunchKernelGGL(k_deinterleave3, dim3((npad + 255) / 256), dim3(256), 0, c->stream, c->staging.as<float>(), n, npad, pad_value, x.as<float>(), y.as<float>(), z.as<float>());
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipStreamSynchronize(c->stream));      // staging is reused by the caller's next plane
+    return ICP_OK;
+}
+
+// Indices j * factor (j = 0 .. count - 1) whose flag is set, in increasing order, compacted on the device (rocPRIM select); one
+// 4-byte copy returns how many there are.  flags: one byte per j.
+int compact_flagged(icp_ctx* c, const uint8_t* d_flags, int count, int factor, DevBuf& out, int* n_out) {
+    int rc;
+    if ((rc = ensure(c, out, (size_t)(count > 0 ? count : 1) * 4))) return rc;
+    if ((rc = ensure(c, c->d_count, 16))) return rc;
+    *n_out = 0;
+    if (count <= 0) return ICP_OK;
+    auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), MulBy{factor});
+    size_t tb = 0;
+    HIPCK(c, rocprim::select(nullptr, tb, in, d_flags, out.as<int>(), c->d_count.as<int>(), (size_t)count, c->stream));
+    if ((rc = ensure(c, c->sel_temp, tb))) return rc;
+    HIPCK(c, rocprim::select(c->sel_temp.p, tb, in, d_flags, out.as<int>(), c->d_count.as<int>(), (size_t)count, c->stream));
+    if ((rc = ensure_pinned(c, 4096))) return rc;
+    int* h = (int*)((char*)c->pinned + 2048);            // (the first bytes of the pinned block stage the pose)
+    HIPCK(c, hipMemcpyAsync(h, c->d_count.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    *n_out = *h;
+    return ICP_OK;
+}
+// finite filter of a cloud that is already on the device -> flag bytes + compacted index list
+int finite_list(icp_ctx* c, const Cloud& cl, bool with_normals, DevBuf& flag, DevBuf& list, int* n_out) {
+    int rc;
+    if ((rc = ensure(c, flag, (size_t)cl.n))) return rc;
+    const bool nrm = with_normals && cl.has_normals;
+    hipLaunchKernelGGL(k_mark_finite, dim3((cl.n + 255) / 256), dim3(256), 0, c->stream, cl.x.as<float>(), cl.y.as<float>(), cl.z.as<float>(),
+                       nrm ? cl.nx.as<float>() : nullptr, nrm ? cl.ny.as<float>() : nullptr, nrm ? cl.nz.as<float>() : nullptr, cl.n, flag.as<uint8_t>());
+    HIPCK(c, hipGetLastError());
+    return compact_flagged(c, flag.as<uint8_t>(), cl.n, 1, list, n_out);
+}
+
+// Upload the pose state.  Staged through the context's page-locked buffer: no synchronisation here -- every entry point
+// that uses the pose synchronises the stream before it returns, so the staging area is free again by the next call.
+// write_pose_via: the same through a page-locked PoseState h the caller owns (and keeps untouched until the stream has passed the copy).
+int write_pose_via(icp_ctx* c, PoseState* h, const float pose[16]) {
+    int rc;
+    memset(h, 0, sizeof(*h));
+    memcpy(h->pose, pose, 64);
+    normal_matrix_from_pose(h->pose, h->nmat);
+    if ((rc = ensure(c, c->ps, sizeof(PoseState)))) return rc;
+    HIPCK(c, hipMemcpyAsync(c->ps.p, h, sizeof(*h), hipMemcpyHostToDevice, c->stream));
+    return ICP_OK;
+}
+int write_pose(icp_ctx* c, const float pose[16]) {
+    int rc;
+    if ((rc = ensure_pinned(c, sizeof(PoseState)))) return rc;
+    return write_pose_via(c, (PoseState*)c->pinned, pose);
+}
+
+int check_ready(icp_ctx* c, bool need_source, bool full_pipeline) {
+    const icp_params& p = c->prm;
+    if (c->tgt.n <= 0) { c->err = "target index needs to be built before querying (icp_set_target)"; return ICP_ERR_NO_TARGET; }
+    if (need_source && c->src.n <= 0) { c->err = "no source cloud (icp_set_source)"; return ICP_ERR_NO_SOURCE; }
+    if (p.matching == ICP_MATCH_PROJECTIVE) {
+        if (p.height <= 0 || p.width <= 0) { c->err = "set camera params before querying any matches"; return ICP_ERR_NO_CAMERA; }
+        if ((long long)p.width * p.height != c->tgt.n) { c->err = "invalid size of target points (must be width*height)"; return ICP_ERR_TARGET_SIZE; }
+    } else if (p.color_icp) {
+        if (!c->tgt.has_colors || (need_source && !c->src.has_colors)) { c->err = "colour ICP needs colours on target and source"; return ICP_ERR_COLOR_MISMATCH; }
+    }
+    if (full_pipeline) {
+        if (!c->tgt.has_normals || !c->src.has_normals) { c->err = "normals required on source and target"; return ICP_ERR_INVALID_ARG; }
+        if (p.weighting == ICP_WEIGHT_COLORS && (!c->tgt.has_colors || !c->src.has_colors)) { c->err = "colour weighting needs colours"; return ICP_ERR_COLOR_MISMATCH; }
+    }
+    return ICP_OK;
+}
+
+int ensure_events(icp_ctx* c, size_t count) {
+    while (c->events.size() < count) { hipEvent_t e; HIPCK(c, hipEventCreate(&e)); c->events.push_back(e); }
+    return ICP_OK;
+}
+}  // namespace

@@ -1,0 +1,113 @@
+// host_debug.hpp -- development and test hooks that are not part of icp_hip.h (tests/ and tools/ call them through ctypes): icp_debug_*,
+// the hardware self test, and the one kernel they own (k_debug_pos_of).  Part of icp_hip.hip (included from there, last).
+extern "C" {
+// Development builds (ICP_DEBUG_STEPS=1): how each query of the LAST matcher launch was resolved, in the order the launch indexed its
+// queries (Morton order for a run): 0 = verified without a walk, -2 = second tier (two leaves), -1 = a walk (a walk shared over the wave
+// has no per-query length); with ICP_DEBUG_TIMES=1 the buffer holds per-wave phase stamps instead (tools/dev_wave_times.py).
+int icp_debug_steps(icp_ctx* c, int32_t* out, int32_t n) {
+    if (!c || !out || n <= 0 || !c->dbg_steps.p || (size_t)n * 4 > c->dbg_steps.cap) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipMemcpy(out, c->dbg_steps.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return ICP_OK;
+}
+
+// Development / test hooks (not part of icp_hip.h; called by tests/ through ctypes).
+//   icp_debug_counters        : how many runs of this context took the merged loop, and how many of those had to be repeated with the
+//                               separate k_reduce_solve launches (rank-deficient system, or a bounded wait that ran out).
+//   icp_debug_poison_handover : leaves a stale, valid-looking total in slot `slot` of k_reduce_solve's hand-over area -- what a run cut
+//                               short between a block's publish and block 0's re-arm would leave behind.  The next call must not see it.
+int icp_debug_ring_times(icp_ctx* c, int32_t* out, int32_t n) {     // development builds (ICP_DEBUG_TIMES): the reducer blocks' clock stamps of the last merged launch
+#if ICP_DEBUG_TIMES
+    if (!c || !out || n < (NSUM_USED + 1) * 8) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipMemcpyFromSymbol(out, HIP_SYMBOL(icpdev::g_ring_dbg), (size_t)(NSUM_USED + 1) * 8 * 4));
+    return ICP_OK;
+#else
+    (void)c; (void)out; (void)n;
+    return ICP_ERR_INVALID_ARG;
+#endif
+}
+int icp_debug_dev_counters(icp_ctx* c, uint32_t* out16, int32_t reset) {     // development builds (ICP_DEBUG_TIMES): the device's event counters (g_dev_counts) since the last reset
+#if ICP_DEBUG_TIMES
+    if (!c || !out16) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    HIPCK(c, hipMemcpyFromSymbol(out16, HIP_SYMBOL(icpdev::g_dev_counts), 64));
+    if (reset == 2) HIPCK(c, hipMemcpyFromSymbol(out16, HIP_SYMBOL(icpdev::g_walk_trace), 256));      // (reset == 2: the caller's buffer has 64 words and wants the trace of the last sparse walk instead, tools/dev_walk_trace.py)
+    if (reset) { uint32_t z[16] = {0}; HIPCK(c, hipMemcpyToSymbol(HIP_SYMBOL(icpdev::g_dev_counts), z, 64)); }
+    return ICP_OK;
+#else
+    (void)c; (void)out16; (void)reset;
+    return ICP_ERR_INVALID_ARG;
+#endif
+}
+//   icp_debug_wave_slot       : host evaluation of the fused matcher's block -> wave mapping (fused_wave_slot): which stretch of 64 queries
+//                               wave w of logical block lb takes in a grid of mgrid blocks; *waves_per_block receives BVH_THREADS / 64.  No GPU needed.
+//   icp_debug_pos_of_mismatches: entries of the resident target's position-by-index map that do not point back at their record (must be 0).
+int icp_debug_wave_slot(int32_t lb, int32_t w, int32_t mgrid, int32_t* waves_per_block) {
+    if (waves_per_block) *waves_per_block = BVH_THREADS / WAVE;
+    if (lb < 0 || lb >= mgrid || w < 0 || w >= BVH_THREADS / WAVE) return -1;
+    return icpdev::fused_wave_slot(lb, w, mgrid);
+}
+__global__ void k_debug_pos_of(const icpdev::TgtRec* recs, const int* pos_of, int n_slots, int* bad) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_slots && recs[i].idx >= 0 && pos_of[recs[i].idx] != i) atomicAdd(bad, 1);
+}
+int icp_debug_pos_of_mismatches(icp_ctx* c, int32_t* n_bad, int32_t* n_checked) {
+    if (!c || !n_bad || !c->bvh.valid) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    const int n_slots = (c->bvh.n_leaves > 0 ? c->bvh.n_leaves : 1) * BVH_LEAF;
+    if ((rc = ensure(c, c->d_count, 4))) return rc;
+    HIPCK(c, hipMemsetAsync(c->d_count.p, 0, 4, c->stream));
+    hipLaunchKernelGGL(k_debug_pos_of, dim3((n_slots + 255) / 256), dim3(256), 0, c->stream, c->bvh.recs.as<icpdev::TgtRec>(), c->bvh.pos_of.as<int>(), n_slots, c->d_count.as<int>());
+    HIPCK(c, hipMemcpyAsync(n_bad, c->d_count.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (n_checked) *n_checked = c->bvh.n_valid;
+    return ICP_OK;
+}
+//   icp_debug_live_bytes      : device bytes the library holds right now, over every context of the process (its own allocations, views
+//                               not counted): a create -> use -> destroy cycle must leave it where it found it.  No context needed.
+int icp_debug_live_bytes(int64_t* out) {
+    if (!out) return ICP_ERR_INVALID_ARG;
+    *out = (int64_t)g_live_bytes.load();
+    return ICP_OK;
+}
+int icp_debug_counters(icp_ctx* c, int32_t* merged_runs, int32_t* merged_fallbacks) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (merged_runs) *merged_runs = c->merged_runs;
+    if (merged_fallbacks) *merged_fallbacks = c->merged_fallbacks;
+    return ICP_OK;
+}
+int icp_debug_poison_handover(icp_ctx* c, int32_t slot, double value) {
+    if (!c || slot < 0 || slot >= NSUM) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    if (!c->totals.p && (rc = rearm_handover(c))) return rc;
+    HIPCK(c, hipMemcpyAsync(c->totals.as<double>() + slot, &value, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return ICP_OK;
+}
+
+// ---- hardware self test (not part of icp_hip.h; called by tests/ through ctypes) ------------------------------------------
+// One wave folds n_values (<= 32) doubles per lane with wave_transpose_reduce_gen; out[v] = the wave total of value v read from
+// the lane wave_value_of_lane says holds it.  tests/test_gpu_selftest.py replays the same pairing with numpy: bit-identical.
+int icp_selftest_wave_reduce(icp_ctx* c, const double* in, double* out, int32_t* lane_of) {
+    if (!c || !in || !out || !lane_of) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    DrainOnError guard(c);
+    if ((rc = ensure(c, c->staging, 64 * 27 * 8 + 27 * 8 + 27 * 4 + 64))) return rc;
+    double* d_in = c->staging.as<double>(); double* d_out = d_in + 64 * 27; int* d_lane = (int*)(d_out + 27);
+    HIPCK(c, hipMemcpyAsync(d_in, in, 64 * 27 * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_selftest_wave_reduce, dim3(1), dim3(64), 0, c->stream, d_in, d_out, d_lane);
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipMemcpyAsync(out, d_out, 27 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(lane_of, d_lane, 27 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+}  // extern "C"

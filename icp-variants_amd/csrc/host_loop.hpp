@@ -1,0 +1,466 @@
+// host_loop.hpp -- the ICP loop of one pose (icp_run, icp_iterate) and the stage-level entry points that drive the same launches by hand
+// (icp_query_matches, icp_match, icp_correspond, icp_match_seeded).  Part of icp_hip.hip (included from there, after host_launch.hpp).
+namespace {
+// The plan of a run (icp_run, icp_iterate, icp_run_multistart), resolved up front (uploads) so that the loop itself is launch-only: the
+// decimation factor of every iteration (icp_schedule; 0 = no selection, the full cloud) and its query set -- the level's cloud (a
+// Morton-sorted copy for the BVH matcher without resampling), its selection, its size, its Morton order.
+struct RunPlan {
+    std::vector<int> factors, ns; std::vector<const Cloud*> clouds; std::vector<const int*> sels, orders;
+    bool sorted_levels = false;      // BVH matcher without resampling: every level is a physical, Morton-sorted copy -> no index lists in the loop at all
+    int iters() const { return (int)factors.size(); }
+    // seed the search with the previous iteration's neighbours when it matched the same queries: same level, it had work, no resampling
+    bool seeded(int i, const icp_params& p) const { return i > 0 && factors[i] == factors[i - 1] && ns[i - 1] > 0 && p.selection == 0; }
+};
+int make_plan(icp_ctx* c, bool single, RunPlan& pl) {
+    const icp_params& p = c->prm;
+    int rc;
+    if (single) pl.factors.assign(1, 0);
+    else {
+        int32_t cnt = 0;
+        if ((rc = icp_schedule(&p, c->src.n, nullptr, 0, &cnt))) { c->err = "multires with n_iterations < 1 never terminates in the reference"; return rc; }
+        pl.factors.resize((size_t)cnt);
+        if (cnt > 0) icp_schedule(&p, c->src.n, pl.factors.data(), cnt, &cnt);
+    }
+    const std::vector<int>& factors = pl.factors; std::vector<int>& ns = pl.ns; std::vector<const int*>& sels = pl.sels; std::vector<const int*>& orders = pl.orders;
+    const int iters = pl.iters();
+    const bool resample = !single && p.selection == 1;
+    sels.assign((size_t)iters, nullptr); ns.assign((size_t)iters, c->src.n); orders.assign((size_t)iters, nullptr); pl.clouds.assign((size_t)iters, &c->src);
+    pl.sorted_levels = p.matching == ICP_MATCH_KNN && p.knn_backend == ICP_KNN_LBVH && !resample;
+    if (iters == 0) return ICP_OK;
+    for (int i = 0; i < iters; i++) {
+        if (pl.sorted_levels) { if ((rc = get_sorted_level(c, factors[i], &pl.clouds[i], &ns[i]))) return rc; }
+        else if (factors[i] > 0) { if ((rc = get_level(c, factors[i], &sels[i], &ns[i], nullptr))) return rc; }
+    }
+    if (resample) {
+        // RANDOM_SAMPLING (ICPOptimizer.h:549-550: resample at the start of every iteration, over the current level's cloud).
+        // All resamples are drawn up front on the device; one small copy returns their sizes so the loop stays launch-only.
+        double th = (double)p.selection_proba * 4294967296.0;
+        const int take_all = th >= 4294967296.0 ? 1 : 0;
+        const uint32_t threshold = th <= 0.0 ? 0u : (take_all ? 0xFFFFFFFFu : (uint32_t)th);
+        const size_t cap = (size_t)c->src.n;
+        if ((rc = ensure(c, c->sel_lists, (size_t)iters * cap * 4))) return rc;
+        if ((rc = ensure(c, c->sel_counts, (size_t)iters * 4))) return rc;
+        if ((rc = ensure(c, c->sel_blocks, (size_t)((cap + 255) / 256 + 1) * 4))) return rc;
+        for (int i = 0; i < iters; i++) {
+            const int nb = (ns[i] + 255) / 256;
+            int* out = c->sel_lists.as<int>() + (size_t)i * cap;
+            if (ns[i] > 0) {
+                hipLaunchKernelGGL(k_select_count, dim3(nb), dim3(256), 0, c->stream, sels[i], ns[i], p.selection_seed, (uint32_t)i, threshold, take_all, c->sel_blocks.as<int>());
+                hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, c->stream, c->sel_blocks.as<int>(), nb, c->sel_counts.as<int>() + i);
+                hipLaunchKernelGGL(k_select_scatter, dim3(nb), dim3(256), 0, c->stream, sels[i], ns[i], p.selection_seed, (uint32_t)i, threshold, take_all, c->sel_blocks.as<int>(), out);
+            } else HIPCK(c, hipMemsetAsync(c->sel_counts.as<int>() + i, 0, 4, c->stream));
+            sels[i] = out; orders[i] = nullptr;
+        }
+        HIPCK(c, hipGetLastError());
+        std::vector<int> counts((size_t)iters);
+        HIPCK(c, hipMemcpyAsync(counts.data(), c->sel_counts.p, (size_t)iters * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < iters; i++) ns[i] = counts[i];
+    }
+    return ICP_OK;
+}
+
+// Finishes the host copy hs of a run's records (every record of an iteration with work was written in full on the device): an empty
+// iteration carries the pose before it (pose_in for iteration 0), rmse / benchmark_error are -1 where not recorded.  Copies up to max_out
+// records to out and returns the first failing status.
+int finish_records(const RunPlan& pl, icp_iter_stats* hs, const float* pose_in, bool rmse, bool fontana, icp_iter_stats* out, int max_out) {
+    int status = ICP_OK;
+    for (int i = 0; i < pl.iters(); i++) {
+        const bool empty = pl.ns[i] <= 0;
+        if (empty) { hs[i].n_src = 0; hs[i].n_valid = 0; hs[i].status = ICP_ERR_NO_CORRESPONDENCES; memcpy(hs[i].pose, i ? hs[i - 1].pose : pose_in, 64); }
+        if (empty || !rmse) hs[i].rmse = -1.f;
+        if (empty || !fontana) hs[i].benchmark_error = -1.f;
+        if (hs[i].status != ICP_OK && status == ICP_OK) status = hs[i].status;
+        if (out && i < max_out) out[i] = hs[i];
+    }
+    return status;
+}
+
+// The ring of a run of merged launches (dev_solve.hpp, "the ring form"), inside c->ring: n_slots pose slots in every replica, then
+// n_rows totals rows (one per reduced launch), then -- unless the caller keeps it elsewhere (fault != nullptr) -- the run's fault word.
+// Both partials buffers hold nbmax blocks: launch j writes one while the reducer riding in it folds the other.
+struct Ring { PoseState* slots; unsigned long long* trows; int* run_fault; size_t slot_bytes; };
+int make_ring(icp_ctx* c, int n_slots, int n_rows, int nbmax, int* fault, Ring& r) {
+    static_assert(sizeof(PoseState) == 128, "a pose slot is 16 granules");
+    int rc;
+    r.slot_bytes = (size_t)n_slots * POSE_REPLICAS * POSE_REPLICA_STRIDE; const size_t tot_bytes = (size_t)n_rows * NSUM * 8;
+    if ((rc = ensure(c, c->ring, r.slot_bytes + tot_bytes + (fault ? 0 : 64)))) return rc;
+    if ((rc = ensure(c, c->partials, (size_t)nbmax * NSUM * 8))) return rc;
+    if ((rc = ensure(c, c->partials2, (size_t)nbmax * NSUM * 8))) return rc;
+    r.slots = c->ring.as<PoseState>(); r.trows = (unsigned long long*)(c->ring.as<char>() + r.slot_bytes);
+    r.run_fault = fault ? fault : (int*)(c->ring.as<char>() + r.slot_bytes + tot_bytes);
+    return ICP_OK;
+}
+double* ring_partials(const icp_ctx* c, int j) { return (j & 1) ? c->partials2.as<double>() : c->partials.as<double>(); }
+// The reducer riding in launch j of the ring (j = 0: none): it folds launch j - 1's partials (n_prev queries) at the pose of slot j - 1
+// and publishes the next pose into ps_out.
+RingParams ring_params(const icp_ctx* c, const Ring& r, int j, int n_prev, PoseState* ps_out) {
+    RingParams rp; memset(&rp, 0, sizeof(rp));
+    rp.run_fault = r.run_fault;
+    if (j > 0) {
+        rp.n_red = NSUM_USED;
+        rp.red_partials = ring_partials(c, j - 1); rp.red_nblocks = fused_nblocks(n_prev);
+        rp.totals_row = r.trows + (size_t)(j - 1) * NSUM; rp.ps_in = loop_slot(r.slots, j - 1, 0); rp.ps_out = ps_out; rp.n_src = n_prev;
+    }
+    return rp;
+}
+
+// What run_loop's prologue hands the form that enqueues the run.  Page-locked staging of the whole run: [pose state up | records down
+// (pin_stats) | pose state down (pin_pose) | LM records down (pin_lm), non-linear runs only]; c->stats is laid out like pin_stats ..
+// pin_pose .. + 128 .. + 192 (records | final pose state | fault word of the merged form).  Stage timing (TimeMeasure.h:20-26): a HIP event
+// costs ~4 us of stream time, so mode N > 1 brackets only every Nth iteration (`sampled`, offset rotating from run to run) and scales the
+// sums.  Event slots: 4 per iteration + run start / run end; each form fills ev[i] of a sampled iteration with the ones it records.
+struct IterEvents { hipEvent_t start = nullptr, matched = nullptr, posted = nullptr, end = nullptr; };   // posted / end: nullptr = the form has no such stage to bracket
+struct LoopRun { RunPlan pl; bool lm, robust, rmse, fontana; size_t pin_stats = 256, pin_pose, pin_lm; std::vector<char> sampled; std::vector<IterEvents> ev; };
+hipEvent_t loop_event(const icp_ctx* c, int i, int k) { return c->events[(size_t)2 + 4 * i + k]; }
+
+// The merged form: point-to-plane through the fused BVH matcher on sorted levels, nothing else on the stream between two iterations.
+// Launch i = [reducer of iteration i - 1 | matcher of iteration i]; one reducer-only launch closes the run.  Pose slots and totals rows
+// are written once per run; both rings are reset here, so nothing survives an aborted run.  Back comes ONE block: records | final pose
+// state | fault word.  Events: an iteration is ONE launch, whose own start / stop times go into slots 0 / 1 (hipExtLaunchKernel: taken
+// from the dispatch itself, no bracket on the stream); a "solve" exists only for the last iteration: the closing launch, up to slot 3.
+int enqueue_merged(icp_ctx* c, LoopRun& r) {
+    const icp_params& p = c->prm; const RunPlan& pl = r.pl;
+    const int iters = pl.iters(); const size_t stats_pad = r.pin_pose - r.pin_stats;
+    int rc, nbmax = POST_BLOCKS;
+    for (int i = 0; i < iters; i++) { const int nb = fused_nblocks(pl.ns[i]); if (nb > nbmax) nbmax = nb; }
+    Ring ring;
+    if ((rc = make_ring(c, iters + 1, iters, nbmax, (int*)(c->stats.as<char>() + stats_pad + 128), ring))) return rc;
+    const int n_init = (iters + 1) * POSE_REPLICAS * 16 + iters * NSUM + 16;
+    hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, c->ps.as<PoseState>(), ring.slots, iters + 1, ring.trows, iters * NSUM, ring.run_fault, 16);
+    auto reducer = [&](int i) {                          // of iteration i - 1, riding in launch i (i = iters: the closing launch)
+        RingParams rp = ring_params(c, ring, i, i > 0 ? pl.ns[i - 1] : 0, loop_slot(ring.slots, i, 0));
+        if (i > 0) rp.stats = c->stats.as<icp_iter_stats>() + (i - 1);
+        if (i == iters) rp.final_out = (PoseState*)(c->stats.as<char>() + stats_pad);
+        return rp;
+    };
+    HIPCK(c, hipEventRecord(c->events[0], c->stream));
+    for (int i = 0; i < iters; i++) {
+        QuerySet q{pl.clouds[i], pl.sels[i], pl.ns[i], 0, p.color_icp != 0 && p.matching == ICP_MATCH_KNN, pl.seeded(i, p), pl.orders[i]};
+        MergeLaunch ml; ml.rp = reducer(i); ml.slot = loop_slot(ring.slots, i, 0); ml.partials = ring_partials(c, i);
+        if (r.sampled[i]) { r.ev[i].start = ml.ev_start = loop_event(c, i, 0); r.ev[i].matched = ml.ev_stop = loop_event(c, i, 1); }
+        int fused = 0;
+        if ((rc = launch_match(c, q, &fused, &ml))) return rc;
+        if (!fused) { c->err = "merged loop: the matcher did not take the fused path"; return ICP_ERR_HIP; }
+    }
+    hipLaunchKernelGGL(k_ring_reduce_solve, dim3(NSUM_USED), dim3(RING_THREADS), 0, c->stream, reducer(iters));      // nothing behind the last iteration to ride in
+    HIPCK(c, hipGetLastError());
+    if (r.sampled[iters - 1]) { r.ev[iters - 1].end = loop_event(c, iters - 1, 3); HIPCK(c, hipEventRecord(r.ev[iters - 1].end, c->stream)); }
+    HIPCK(c, hipEventRecord(c->events[1], c->stream));
+    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_stats, c->stats.p, stats_pad + 192, hipMemcpyDeviceToHost, c->stream));
+    return ICP_OK;
+}
+
+// The separate form, which every configuration can take: per iteration the matcher (its post stage fused where the matcher can), then
+// the post stage and the reduce / solve -- or the robust chain in front, or the non-linear optimiser behind -- and the convergence
+// measures.  Back come the records, the pose state and the LM records.  Events: slot 0 in front of the matcher, 1 behind it, 2 behind a
+// post stage of its own (none behind a fused matcher), 3 at the iteration's end; the matcher's time counts from the previous iteration's
+// slot 3 when that one was sampled.
+int enqueue_separate(icp_ctx* c, LoopRun& r) {
+    const icp_params& p = c->prm; const RunPlan& pl = r.pl;
+    const int iters = pl.iters(); int rc;
+    if ((rc = rearm_handover(c))) return rc;
+    HIPCK(c, hipEventRecord(c->events[0], c->stream));
+    for (int i = 0; i < iters; i++) {
+        icp_iter_stats* d_st = c->stats.as<icp_iter_stats>() + i;
+        const bool ev = r.sampled[i] != 0;
+        if (ev) {
+            r.ev[i].start = (i > 0 && r.sampled[i - 1]) ? loop_event(c, i - 1, 3) : loop_event(c, i, 0);
+            r.ev[i].matched = loop_event(c, i, 1); r.ev[i].end = loop_event(c, i, 3);
+            HIPCK(c, hipEventRecord(loop_event(c, i, 0), c->stream));
+        }
+        if (pl.ns[i] > 0) {
+            // (keep_records: the fused matcher writes its records for k_lm_eval)
+            QuerySet q{pl.clouds[i], pl.sels[i], pl.ns[i], 0, p.color_icp != 0 && p.matching == ICP_MATCH_KNN, pl.seeded(i, p), pl.orders[i], r.lm};
+            int fused = 0;
+            if ((rc = launch_match(c, q, !r.robust ? &fused : nullptr))) return rc;
+            if (ev) HIPCK(c, hipEventRecord(r.ev[i].matched, c->stream));
+            if (ev && !fused) r.ev[i].posted = loop_event(c, i, 2);      // fused epilogue: there is no separate post stage to bracket
+            if (r.lm) rc = launch_post_and_lm(c, *pl.clouds[i], pl.sels[i], pl.ns[i], d_st, c->lm_sums.as<icp_lm_summary>() + i, r.ev[i].posted, fused);
+            else rc = launch_post_and_solve(c, *pl.clouds[i], pl.sels[i], pl.ns[i], d_st, nullptr, 1, r.ev[i].posted, fused, r.robust ? c->rob_stats.as<icp_robust_stats>() + i : nullptr);
+            if (rc) return rc;
+        } else if (ev) HIPCK(c, hipEventRecord(r.ev[i].matched, c->stream));
+        if (r.rmse && (rc = enqueue_rmse(c, &d_st->rmse))) return rc;
+        if (r.fontana && (rc = enqueue_fontana(c, &d_st->benchmark_error))) return rc;
+        if (ev) HIPCK(c, hipEventRecord(r.ev[i].end, c->stream));
+    }
+    HIPCK(c, hipEventRecord(c->events[1], c->stream));
+    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_stats, c->stats.p, (size_t)iters * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_pose, c->ps.p, sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));
+    if (r.lm) HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_lm, c->lm_sums.p, (size_t)iters * sizeof(icp_lm_summary), hipMemcpyDeviceToHost, c->stream));
+    return ICP_OK;
+}
+
+// try_merged: take the merged form when the configuration allows it (the context's merge_loop; false when a merged run has given up).
+int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t max_stats, int32_t* n_run, bool single, bool try_merged) {
+    const icp_params& p = c->prm;
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = check_ready(c, true, true))) return rc;
+    if ((rc = gicp_prepare(c))) return rc;
+    if ((rc = colored_prepare(c))) return rc;
+    LoopRun r{};
+    const RunPlan& pl = r.pl;
+    if ((rc = make_plan(c, single, r.pl))) return rc;
+    const int iters = pl.iters();
+    if (n_run) *n_run = 0;
+    const bool lm = r.lm = c->lm_on;      // the non-linear optimiser: the separate form, its records kept for k_lm_eval
+    const bool robust = r.robust = robust_on(c);      // trimmed / robust mode: the separate form with the stand-alone matcher, as GICP runs
+    c->lm_last.clear(); c->rob_last.clear();
+    if (robust && lm) { c->err = "the non-linear optimiser does not support robust mode (icp_set_robust_options)"; return ICP_ERR_INVALID_ARG; }
+    if (iters == 0) return guard.done();
+    if (robust && (rc = robust_prepare(c, iters))) return rc;
+    r.pin_pose = r.pin_stats + (((size_t)iters * sizeof(icp_iter_stats) + 255) & ~(size_t)255); r.pin_lm = r.pin_pose + 512;
+    if ((rc = ensure_pinned(c, lm ? r.pin_lm + (size_t)iters * sizeof(icp_lm_summary) : r.pin_pose + 512))) return rc;
+    if (lm && (rc = ensure(c, c->lm_sums, (size_t)iters * sizeof(icp_lm_summary)))) return rc;
+    float pose_in[16]; memcpy(pose_in, pose_inout, 64);        // the record of an empty iteration 0 carries the incoming pose
+    if ((rc = write_pose(c, pose_inout))) return rc;
+    if ((rc = ensure(c, c->stats, r.pin_pose - r.pin_stats + 192))) return rc;
+    if ((rc = ensure_events(c, (size_t)iters * 4 + 2))) return rc;
+    const bool rmse = r.rmse = (p.record_rmse & 1) && c->conv_n > 0;
+    const bool fontana = r.fontana = (p.record_rmse & 2) && c->conv_n > 0;
+    bool merged = try_merged && !lm && !robust && !single && iters >= 2 && pl.sorted_levels && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
+    for (int i = 0; merged && i < iters; i++) if (pl.ns[i] <= 0) merged = false;
+    const int tmode = c->stage_timing;
+    r.sampled.assign((size_t)iters, 0); r.ev.assign((size_t)iters, IterEvents());
+    for (int i = 0; i < iters; i++) r.sampled[i] = tmode == 1 || (tmode > 1 && (i + (int)(c->timing_phase % (unsigned)tmode)) % tmode == 0);
+    c->timing_phase++;
+    if ((rc = merged ? enqueue_merged(c, r) : enqueue_separate(c, r))) return rc;
+    std::vector<icp_robust_stats> rob((size_t)(robust ? iters : 0));
+    if (robust) HIPCK(c, hipMemcpyAsync(rob.data(), c->rob_stats.p, (size_t)iters * sizeof(icp_robust_stats), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; robust && i < iters; i++) if (pl.ns[i] <= 0) rob[(size_t)i] = icp_robust_stats{0, 0, -1.f, -1.f};      // (no work: nothing was written)
+    c->rob_last.swap(rob);
+    const PoseState* hp = (const PoseState*)((char*)c->pinned + r.pin_pose);
+    if (merged) {
+        c->merged_runs++;
+        const int rf = *(const int*)((char*)c->pinned + r.pin_pose + 128);
+        if (hp->fault || rf) {
+            // a pivot of the 6 x 6 system failed the rank test (the eigen fallback lives in k_reduce_solve only), or a bounded wait ran out:
+            // the same run again, from the incoming pose, in the separate form
+            c->merged_fallbacks++;
+            if (c->trace) fprintf(stderr, "[icp_hip] merged loop gave up: slot fault %d, abort word %d -> the run again with separate launches\n", hp->fault, rf);
+            guard.ok = true;                                 // synchronised
+            memcpy(pose_inout, pose_in, 64);
+            return run_loop(c, pose_inout, stats, max_stats, n_run, single, false);
+        }
+    }
+    memcpy(pose_inout, hp->pose, 64);
+    if (hp->fault) { c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
+    if (lm) {
+        c->lm_last.resize((size_t)iters);
+        memcpy(c->lm_last.data(), (char*)c->pinned + r.pin_lm, (size_t)iters * sizeof(icp_lm_summary));
+        for (int i = 0; i < iters; i++)
+            if (pl.ns[i] <= 0) { memset(&c->lm_last[(size_t)i], 0, sizeof(icp_lm_summary)); c->lm_last[(size_t)i].termination = ICP_LM_NO_RESIDUALS; }
+    }
+    const int status = finish_records(pl, (icp_iter_stats*)((char*)c->pinned + r.pin_stats), pose_in, rmse, fontana, stats, max_stats);
+    if (n_run) *n_run = iters;
+    icp_timing& t = c->timing; memset(&t, 0, sizeof(t)); t.iterations = iters;
+    c->it_match_ms.assign((size_t)iters, -1.f); c->it_post_ms.assign((size_t)iters, -1.f); c->it_solve_ms.assign((size_t)iters, -1.f);
+    double ev_match = 0, ev_post = 0, ev_solve = 0; int n_ev = 0;
+    for (int i = 0; i < iters; i++) {
+        if (!r.sampled[i]) continue;
+        n_ev++;
+        const IterEvents& e = r.ev[i];
+        float a = 0, b = 0, d = 0;
+        HIPCK(c, hipEventElapsedTime(&a, e.start, e.matched));
+        if (e.posted) HIPCK(c, hipEventElapsedTime(&b, e.matched, e.posted));
+        if (e.end) HIPCK(c, hipEventElapsedTime(&d, e.posted ? e.posted : e.matched, e.end));
+        ev_match += a; ev_post += b; ev_solve += d;
+        c->it_match_ms[(size_t)i] = a; c->it_post_ms[(size_t)i] = b; c->it_solve_ms[(size_t)i] = d;
+        if (c->trace) fprintf(stderr, "[icp_hip] it %2d  n %d  match %.4f  post %.4f  solve %.4f ms\n", i, pl.ns[i], a, b, d);
+    }
+    if (n_ev > 0) {                                       // sampled: scale to all the iterations
+        const double f = (double)iters / n_ev;
+        t.match_ms += ev_match * f; t.weight_reject_build_ms += ev_post * f; t.solve_ms += ev_solve * f;
+    }
+    t.sampled_iterations = n_ev;
+    float tot = 0; HIPCK(c, hipEventElapsedTime(&tot, c->events[0], c->events[1])); t.total_ms = tot;
+    if (status != ICP_OK) c->err = "no valid correspondences in at least one iteration (reference would hang in ASSERT)";
+    guard.ok = true;                                     // synchronised above; `status` reports empty iterations, not a HIP failure
+    return status;
+}
+}  // namespace
+
+// Iteration schedule of LinearICPOptimizer::estimatePose: ICPOptimizer.h:503-516 (coarsest level),
+// :540 (loop condition `i < nIter || multires`) and :634-655 (refinement).  Pure host logic.
+int icp_schedule(const icp_params* p, int32_t n_src, int32_t* factors_out, int32_t max_out, int32_t* count_out) {
+    if (!p || !count_out || n_src < 0) return ICP_ERR_INVALID_ARG;
+    int cnt = 0;
+    if (!p->multires) {
+        for (int i = 0; i < p->n_iterations; i++) { if (factors_out && cnt < max_out) factors_out[cnt] = 0; cnt++; }
+    } else {
+        if (p->n_iterations < 1) return ICP_ERR_INVALID_ARG;     // `i >= m_nIterations - 1` is unsigned in the reference: never true
+        float res = 1.0f; int osz = n_src;
+        while (1) { osz = (int)(osz / 2.0); if (osz < 100) break; res *= 2.0f; }      // MULTI_RESOLUTION_MINIMUM_POINTS :21
+        for (int i = 0;; ++i) {
+            if (factors_out && cnt < max_out) factors_out[cnt] = (int)res;
+            cnt++;
+            if (res == 1.0f && i >= p->n_iterations - 1) break;
+            if (res == 1.0f) continue;
+            res /= 2.0f; if (res < 1.0f) res = 1.0f;
+        }
+    }
+    *count_out = cnt;
+    return ICP_OK;
+}
+
+int icp_iterate(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats) {
+    if (!c || !pose_inout) { if (c) c->err = "icp_iterate: bad argument"; return ICP_ERR_INVALID_ARG; }
+    return run_loop(c, pose_inout, stats, stats ? 1 : 0, nullptr, true, c->merge_loop);
+}
+
+int icp_run(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t max_stats, int32_t* n_iterations_run) {
+    if (!c || !pose_inout) { if (c) c->err = "icp_run: bad argument"; return ICP_ERR_INVALID_ARG; }
+    return run_loop(c, pose_inout, stats, stats ? max_stats : 0, n_iterations_run, false, c->merge_loop);
+}
+
+int icp_query_matches(icp_ctx* c, const float* transformed_xyz, const uint8_t* rgba, int32_t n, icp_match_t* out) {
+    if (!c || !transformed_xyz || !out || n <= 0) { if (c) c->err = "icp_query_matches: bad argument"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = check_ready(c, false, false))) return rc;
+    const bool colors = rgba != nullptr;
+    if (c->prm.matching == ICP_MATCH_KNN && colors && !c->tgt.has_colors) {      // NearestNeighbor.h:240-243
+        c->err = "index built without colours: call queryMatches without colours";
+        return ICP_ERR_COLOR_MISMATCH;
+    }
+    if ((rc = upload_cloud(c, c->qry, transformed_xyz, nullptr, rgba, n, false))) return rc;
+    QuerySet q{&c->qry, nullptr, n, 1, colors && c->prm.matching == ICP_MATCH_KNN, false, nullptr};
+    if ((rc = launch_match(c, q))) return rc;
+    HIPCK(c, hipMemcpyAsync(out, c->matches.p, (size_t)n * sizeof(icp_match_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+
+int icp_match(icp_ctx* c, const float pose[16], icp_match_t* out, float* d2_out) {
+    if (!c || !pose || !out) { if (c) c->err = "icp_match_t: bad argument"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = check_ready(c, true, false))) return rc;
+    if ((rc = write_pose(c, pose))) return rc;
+    const int* full_order = nullptr;
+    if ((rc = get_full_order(c, &full_order))) return rc;
+    QuerySet q{&c->src, nullptr, c->src.n, 0, c->prm.color_icp != 0 && c->prm.matching == ICP_MATCH_KNN, false, full_order};
+    if ((rc = launch_match(c, q))) return rc;
+    HIPCK(c, hipMemcpyAsync(out, c->matches.p, (size_t)q.n * sizeof(icp_match_t), hipMemcpyDeviceToHost, c->stream));
+    if (d2_out) HIPCK(c, hipMemcpyAsync(d2_out, c->d2.p, (size_t)q.n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+
+int icp_correspond(icp_ctx* c, const float pose[16], icp_match_t* out, double* sums_out, int32_t* n_valid_out) {
+    if (!c || !pose) { if (c) c->err = "icp_correspond: bad argument"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = check_ready(c, true, true))) return rc;
+    if ((rc = gicp_prepare(c))) return rc;
+    if ((rc = colored_prepare(c))) return rc;
+    const bool robust = robust_on(c);
+    c->rob_last.clear();
+    if (robust && (rc = robust_prepare(c, 1))) return rc;
+    if ((rc = write_pose(c, pose))) return rc;
+    const int* full_order = nullptr;
+    if ((rc = get_full_order(c, &full_order))) return rc;
+    QuerySet q{&c->src, nullptr, c->src.n, 0, c->prm.color_icp != 0 && c->prm.matching == ICP_MATCH_KNN, false, full_order};
+    if ((rc = launch_match(c, q))) return rc;
+    if ((rc = ensure(c, c->sums, NSUM * 8))) return rc;
+    if ((rc = rearm_handover(c))) return rc;
+    if ((rc = launch_post_and_solve(c, c->src, nullptr, q.n, nullptr, c->sums.as<double>(), 0, nullptr, 0, robust ? c->rob_stats.as<icp_robust_stats>() : nullptr))) return rc;
+    double hs[NSUM]; int fault = 0;
+    icp_robust_stats rs;
+    if (out) HIPCK(c, hipMemcpyAsync(out, c->matches.p, (size_t)q.n * sizeof(icp_match_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(hs, c->sums.p, NSUM * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(&fault, &c->ps.as<PoseState>()->fault, 4, hipMemcpyDeviceToHost, c->stream));
+    if (robust) HIPCK(c, hipMemcpyAsync(&rs, c->rob_stats.p, sizeof(rs), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (robust) c->rob_last.assign(1, rs);
+    if (fault) { c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
+    if (sums_out) { memset(sums_out, 0, 64 * 8); memcpy(sums_out, hs, NSUM * 8); }
+    if (n_valid_out) *n_valid_out = (int32_t)hs[SUM_N];
+    return guard.done();
+}
+
+// The fused matcher driven launch by launch with caller-dictated poses: launch 0 unseeded, launch j > 0 seeded + incremental exactly
+// as iteration j of icp_run runs it, in the form icp_run takes for the configuration (the merged ring launches or the separate
+// launches: same kernel, same buffers, same grid); the last launch's records come back in source order.
+int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_t* out, float* d2_out) {
+    if (!c || !poses || n_poses <= 0) { if (c) c->err = "icp_match_seeded: bad argument"; return ICP_ERR_INVALID_ARG; }
+    const icp_params& p = c->prm;
+    if (p.metric == ICP_METRIC_GICP) { c->err = "icp_match_seeded: GICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
+    if (p.metric == ICP_METRIC_COLORED) { c->err = "icp_match_seeded: colored ICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
+    if (robust_on(c)) { c->err = "icp_match_seeded: robust mode (icp_set_robust_options) has no fused matcher"; return ICP_ERR_INVALID_ARG; }
+    if (p.matching != ICP_MATCH_KNN || p.knn_backend != ICP_KNN_LBVH || p.metric == ICP_METRIC_SYMMETRIC) {
+        c->err = "icp_match_seeded: needs k-NN matching on the LBVH backend with the fused point-to-point / point-to-plane matcher"; return ICP_ERR_INVALID_ARG;
+    }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = check_ready(c, true, true))) return rc;
+    const Cloud* cloud = nullptr; int n = 0;
+    if ((rc = get_sorted_level(c, 0, &cloud, &n))) return rc;
+    // ring: what run_loop launches for this configuration one launch per iteration (the merged loop, dev_solve.hpp "the ring form"):
+    // k_knn_bvh_post_ring, launch j > 0 with the reducer of launch j - 1 in its first NSUM_USED blocks and the matcher blocks behind them.
+    // Every matcher waits on slot j, filled here up front with the caller's pose j; the reducers fold the previous launch's partials
+    // (the same ring as run_loop's) and publish into a scratch slot nobody waits on.  Otherwise (point-to-point, ICP_HIP_MERGE=0):
+    // the separate k_knn_bvh_post launches, each at the pose written in front of it.
+    const bool ring = c->merge_loop && !c->lm_on && p.metric == ICP_METRIC_POINT_TO_PLANE;
+    std::vector<unsigned long long> slot_image;              // (read by the copy below until the synchronisation at the end)
+    Ring rg{nullptr, nullptr, nullptr, 0};
+    if (ring) {
+        const int nb = fused_nblocks(n), n_rows = n_poses > 1 ? n_poses - 1 : 1;    // totals rows: one per reduced launch
+        if ((rc = make_ring(c, n_poses + 1, n_rows, nb > POST_BLOCKS ? nb : POST_BLOCKS, nullptr, rg))) return rc;
+        // slots 0 .. n_poses - 1 in every replica, encoded as the reducer publishes a slot (16 granules of PoseState, fault word zero);
+        // slot n_poses, the reducers' scratch, starts empty
+        slot_image.assign(rg.slot_bytes / 8, GRANULE_EMPTY);
+        for (int j = 0; j < n_poses; j++) {
+            PoseState ps; memset(&ps, 0, sizeof(ps)); memcpy(ps.pose, poses + (size_t)16 * j, 64); normal_matrix_from_pose(ps.pose, ps.nmat);
+            const unsigned long long* g = (const unsigned long long*)&ps;
+            for (int r = 0; r < POSE_REPLICAS; r++)
+                for (int q = 0; q < 16; q++)
+                    slot_image[((size_t)j * POSE_REPLICAS + r) * (POSE_REPLICA_STRIDE / 8) + q] = g[q] == GRANULE_EMPTY ? g[q] ^ 1ull : g[q];
+        }
+        HIPCK(c, hipMemcpyAsync(rg.slots, slot_image.data(), rg.slot_bytes, hipMemcpyHostToDevice, c->stream));
+        const int n_init = n_rows * NSUM + 16;               // the totals rows empty, the fault word zero (k_run_init without its pose slots)
+        hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, nullptr, rg.slots, 0, rg.trows, n_rows * NSUM, rg.run_fault, 16);
+        HIPCK(c, hipGetLastError());
+    }
+    for (int j = 0; j < n_poses; j++) {
+        if (!ring && (rc = write_pose(c, poses + (size_t)16 * j))) return rc;
+        QuerySet q{cloud, nullptr, n, 0, p.color_icp != 0, j > 0, nullptr, j == n_poses - 1};      // (only the last launch's records are read)
+        MergeLaunch ml; memset(&ml.rp, 0, sizeof(ml.rp)); ml.slot = nullptr; ml.partials = nullptr;
+        if (ring) {                                          // the reducer's pose goes to the scratch slot
+            ml.rp = ring_params(c, rg, j, n, loop_slot(rg.slots, n_poses, 0));
+            ml.slot = loop_slot(rg.slots, j, 0); ml.partials = ring_partials(c, j);
+        }
+        int fused = 0;
+        if ((rc = launch_match(c, q, &fused, ring ? &ml : nullptr))) return rc;
+        if (!fused) { c->err = "icp_match_seeded: the matcher did not take the fused path"; return ICP_ERR_INVALID_ARG; }
+        if (!ring) {
+            int hf = 0;
+            HIPCK(c, hipMemcpyAsync(&hf, &c->ps.as<PoseState>()->fault, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCK(c, hipStreamSynchronize(c->stream));       // the pose staging area is reused by the next launch
+            if (hf) { c->err = "icp_match_seeded: a bounded wait of the matcher ran out (k_knn_bvh_post)"; return ICP_ERR_HIP; }
+        }
+    }
+    if (ring) {
+        int hf = 0;
+        HIPCK(c, hipMemcpyAsync(&hf, rg.run_fault, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (hf) { c->err = "icp_match_seeded: a bounded wait of the merged launches ran out (k_knn_bvh_post_ring)"; return ICP_ERR_HIP; }
+    }
+    std::vector<int> pos((size_t)n); std::vector<icp_match_t> m((size_t)n); std::vector<float> d((size_t)n);
+    HIPCK(c, hipMemcpyAsync(pos.data(), c->levels[0].sorted_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(m.data(), c->matches.p, (size_t)n * sizeof(icp_match_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(d.data(), c->d2.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    for (int t = 0; t < n; t++) {                            // sorted position -> source index
+        if (out) out[pos[(size_t)t]] = m[(size_t)t];
+        if (d2_out) d2_out[pos[(size_t)t]] = d[(size_t)t];
+    }
+    return guard.done();
+}

@@ -4,12 +4,11 @@ the new kernels (compile only)."""
 import ctypes
 import os
 import re
-import subprocess
-import sys
 import numpy as np
 from scipy.spatial import cKDTree
 
 import colored_restatement as CR
+from device_asm import device_asm, kernel_resources
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 f32 = np.float32
@@ -147,19 +146,10 @@ def test_step_recovers_textured_plane_pose():
     assert tr1 > 0.02, (ang1, tr1)
 
 
-def test_new_kernels_register_budget(tmp_path):
+def test_new_kernels_register_budget():
     """k_color_gradients<5|10|20>: no scratch, at most 128 VGPRs; k_post_colored: no scratch, at most 136 VGPRs (it holds 34 fp64
     accumulators and two Jacobian rows)."""
-    src = os.path.join(ROOT, "icp-variants_amd", "csrc", "icp_hip.hip")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = str(tmp_path / "icp_hip.s")
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    flags = [f for f in g.HIPCC_FLAGS if f not in ("-shared", "-Wall")]
-    subprocess.check_call([hipcc] + flags + ["--cuda-device-only", "-w", "-I", os.path.join(ROOT, "include"), "-S", src, "-o", out], timeout=900)
-    seen = {}
-    for name, field, val in re.findall(r"\.set (_ZN6icpdev\S*?)\.(num_vgpr|private_seg_size), (\d+)", open(out).read()):
-        seen.setdefault(name, {})[field] = int(val)
+    seen = kernel_resources(device_asm())
     grads = {n: f for n, f in seen.items() if n.startswith("_ZN6icpdev17k_color_gradientsILi")}
     assert sorted(re.search(r"ILi(\d+)E", n).group(1) for n in grads) == ["10", "20", "5"], list(grads)
     post = {n: f for n, f in seen.items() if n.startswith("_ZN6icpdev14k_post_colored")}

@@ -8,12 +8,11 @@ against a literal per-pixel transcription of the reference loop.  Also: the COFF
 import ctypes as C
 import math
 import os
-import re
 import shutil
 import subprocess
-import sys
 import numpy as np
 import pytest
+from device_asm import device_asm, kernel_resources
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 f32 = np.float32
@@ -393,19 +392,10 @@ def test_color_camera_struct_matches_the_c_header(tmp_path):
     assert (cam.fx, cam.fy, cam.cx, cam.cy, cam.width, cam.height) == (2, 4, 3, 5, 7, 6) and list(cam.extrinsics)[12:15] == [1, 2, 3]
 
 
-def test_mesh_kernels_register_budget(tmp_path):
+def test_mesh_kernels_register_budget():
     """The three mesh kernels: no scratch and at most 32 VGPRs (full occupancy for a memory-bound pass).  Compiled: k_mesh_vertices 13,
     k_mesh_count 22, k_mesh_scatter 21."""
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = str(tmp_path / "icp_hip.s")
-    flags = [f for f in g.HIPCC_FLAGS if f not in ("-shared", "-Wall")]
-    subprocess.check_call([hipcc] + flags + ["--cuda-device-only", "-w", "-I", os.path.join(ROOT, "include"), "-S",
-                           os.path.join(ROOT, "icp-variants_amd", "csrc", "icp_hip.hip"), "-o", out], timeout=900)
-    seen = {}
-    for name, field, val in re.findall(r"\.set (_ZN6icpdev\S*?)\.(num_vgpr|private_seg_size), (\d+)", open(out).read()):
-        seen.setdefault(name, {})[field] = int(val)
+    seen = kernel_resources(device_asm())
     for prefix in ("15k_mesh_vertices", "12k_mesh_count", "14k_mesh_scatter"):
         ks = {n: f for n, f in seen.items() if n.startswith("_ZN6icpdev" + prefix)}
         assert len(ks) == 1, (prefix, list(ks))

@@ -3,11 +3,10 @@
 import ctypes
 import os
 import re
-import subprocess
-import sys
 import numpy as np
 
 import gicp_restatement as G
+from device_asm import device_asm, kernel_resources
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
@@ -126,18 +125,9 @@ def test_covariance_equals_eigendecomposition_form():
         assert np.array_equal(nb[i], fin[o][:k])
 
 
-def test_new_kernels_register_budget(tmp_path):
+def test_new_kernels_register_budget():
     """k_gicp_normals<5|10|20> and k_post_gicp: no scratch; k_post_gicp within 128 VGPRs (4 waves per SIMD)."""
-    src = os.path.join(ROOT, "icp-variants_amd", "csrc", "icp_hip.hip")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = str(tmp_path / "icp_hip.s")
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    flags = [f for f in g.HIPCC_FLAGS if f not in ("-shared", "-Wall")]
-    subprocess.check_call([hipcc] + flags + ["--cuda-device-only", "-w", "-I", os.path.join(ROOT, "include"), "-S", src, "-o", out], timeout=900)
-    seen = {}
-    for name, field, val in re.findall(r"\.set (_ZN6icpdev\S*?)\.(num_vgpr|private_seg_size), (\d+)", open(out).read()):
-        seen.setdefault(name, {})[field] = int(val)
+    seen = kernel_resources(device_asm())
     normals = {n: f for n, f in seen.items() if n.startswith("_ZN6icpdev14k_gicp_normalsILi")}
     assert sorted(re.search(r"ILi(\d+)E", n).group(1) for n in normals) == ["10", "20", "5"], list(normals)
     for name, f in normals.items():

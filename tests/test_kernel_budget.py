@@ -2,26 +2,11 @@
 SIMD lane: 80 registers are 6 resident waves per SIMD, 81 are 5 -- and an innocent-looking edit moves the count by two or three
 (measured in round 2: 82 registers cost 10 % in the iterations where every query walks the tree).  Compiles the device code to
 assembly and reads the counts the compiler reports; no GPU needed."""
-import os
-import re
-import subprocess
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+from device_asm import device_asm, kernel_resources
 
 
-def test_fused_matcher_keeps_six_waves_per_simd_and_no_scratch(tmp_path):
-    src = os.path.join(ROOT, "icp-variants_amd", "csrc", "icp_hip.hip")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = str(tmp_path / "icp_hip.s")
-    import sys
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    flags = [f for f in g.HIPCC_FLAGS if f not in ("-shared", "-Wall")]      # the product's own flags
-    subprocess.check_call([hipcc] + flags + ["--cuda-device-only", "-w", "-I", os.path.join(ROOT, "include"), "-S", src, "-o", out], timeout=900)
-    text = open(out).read()
-    seen = {}
-    for name, field, val in re.findall(r"\.set (_ZN6icpdev\S*?)\.(num_vgpr|private_seg_size), (\d+)", text):
-        seen.setdefault(name, {})[field] = int(val)
+def test_fused_matcher_keeps_six_waves_per_simd_and_no_scratch():
+    seen = kernel_resources(device_asm())
 
     def kernels(prefix):
         return {n: f for n, f in seen.items() if n.startswith("_ZN6icpdev" + prefix)}

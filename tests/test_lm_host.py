@@ -2,7 +2,6 @@
 trust-region rules one by one, the C ABI's new types against the header, and the new kernels' register budget."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -11,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import lm_restatement as lm          # noqa: E402
+from device_asm import device_asm, kernel_resources
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 MATCH = np.dtype([("idx", np.int32), ("weight", np.float32)])
@@ -220,20 +220,10 @@ def test_entry_points_without_a_device():
     assert lib.icp_get_lm_summaries(None, None, 0, ctypes.byref(cnt)) == 1
 
 
-def test_lm_kernels_register_budget(tmp_path):
+def test_lm_kernels_register_budget():
     """k_lm_eval / k_lm_step / k_lm_init: no scratch; k_lm_eval keeps three waves per SIMD (<= 168 VGPRs) and no AGPRs.  k_lm_step is one
     wave with nothing to overlap: it may use the whole register file, AGPRs included, but never scratch."""
-    src = os.path.join(ROOT, "icp-variants_amd", "csrc", "icp_hip.hip")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = str(tmp_path / "icp_hip.s")
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    flags = [f for f in g.HIPCC_FLAGS if f not in ("-shared", "-Wall")]
-    subprocess.check_call([hipcc] + flags + ["--cuda-device-only", "-w", "-I", os.path.join(ROOT, "include"), "-S", src, "-o", out], timeout=900)
-    text = open(out).read()
-    seen = {}
-    for name, field, val in re.findall(r"\.set (_ZN6icpdev\S*?k_lm_\S*?)\.(num_vgpr|num_agpr|private_seg_size), (\d+)", text):
-        seen.setdefault(name, {})[field] = int(val)
+    seen = {n: r for n, r in kernel_resources(device_asm()).items() if "k_lm_" in n}
     assert len(seen) == 3, seen
     for name, f in seen.items():
         assert f["private_seg_size"] == 0, (name, f)

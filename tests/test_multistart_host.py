@@ -2,10 +2,8 @@
 budget of the new kernels (compile only; no GPU needed)."""
 import ctypes
 import os
-import re
-import subprocess
-import sys
 import numpy as np
+from device_asm import device_asm, kernel_resources
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
@@ -55,19 +53,10 @@ def test_start_poses():
     assert np.allclose(Q[0][:3, :3], rotation((1, 0, 0), 30.0), atol=1e-6) and np.allclose(Q[0][:3, 3], 0.0)
 
 
-def test_new_kernels_register_budget(tmp_path):
+def test_new_kernels_register_budget():
     """k_knn_bvh_post_multi<3, .> keeps its single-start sibling's budget (80 VGPRs: 6 waves per SIMD, no scratch); the colour matcher,
     the stand-alone matcher, the post stages and k_reduce_solve_multi have no scratch either."""
-    src = os.path.join(ROOT, "icp-variants_amd", "csrc", "icp_hip.hip")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = str(tmp_path / "icp_hip.s")
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    flags = [f for f in g.HIPCC_FLAGS if f not in ("-shared", "-Wall")]
-    subprocess.check_call([hipcc] + flags + ["--cuda-device-only", "-w", "-I", os.path.join(ROOT, "include"), "-S", src, "-o", out], timeout=900)
-    seen = {}
-    for name, field, val in re.findall(r"\.set (_ZN6icpdev\S*?)\.(num_vgpr|private_seg_size), (\d+)", open(out).read()):
-        seen.setdefault(name, {})[field] = int(val)
+    seen = kernel_resources(device_asm())
 
     def kernels(prefix):
         return {n: f for n, f in seen.items() if n.startswith("_ZN6icpdev" + prefix)}

@@ -4,12 +4,11 @@ register / scratch budget of the new kernels (compile only)."""
 import ctypes
 import os
 import re
-import subprocess
-import sys
 import numpy as np
 import pytest
 
 import robust_restatement as R
+from device_asm import device_asm, kernel_resources
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 f32 = np.float32
@@ -140,18 +139,9 @@ def test_sums_of_kept_pairs():
     assert np.all(np.linalg.eigvalsh(H) > 0)
 
 
-def test_new_kernels_register_budget(tmp_path):
+def test_new_kernels_register_budget():
     """k_robust_*: no scratch, within 64 VGPRs (8 waves per SIMD)."""
-    src = os.path.join(ROOT, "icp-variants_amd", "csrc", "icp_hip.hip")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = str(tmp_path / "icp_hip.s")
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    flags = [f for f in g.HIPCC_FLAGS if f not in ("-shared", "-Wall")]
-    subprocess.check_call([hipcc] + flags + ["--cuda-device-only", "-w", "-I", os.path.join(ROOT, "include"), "-S", src, "-o", out], timeout=900)
-    seen = {}
-    for name, field, val in re.findall(r"\.set (_ZN6icpdev\S*?)\.(num_vgpr|private_seg_size), (\d+)", open(out).read()):
-        seen.setdefault(name, {})[field] = int(val)
+    seen = kernel_resources(device_asm())
     rob = {n: f for n, f in seen.items() if "k_robust_" in n}
     assert len(rob) == 5, list(rob)                     # eval, select<1>, select<2>, finish, apply
     for name, f in rob.items():

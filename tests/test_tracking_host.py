@@ -2,12 +2,11 @@
 header, the register budget of the depth kernels, and icp_amd/tum.py on a directory written by write_synthetic_sequence."""
 import ctypes as C
 import os
-import re
 import shutil
 import subprocess
-import sys
 import numpy as np
 import pytest
+from device_asm import device_asm, kernel_resources
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
@@ -57,19 +56,10 @@ def test_ctypes_structs_match_the_c_header(tmp_path):
             assert int(facts["%s.%s" % (name, field)]) == getattr(cls, field).offset, (name, field)
 
 
-def test_depth_kernels_register_budget(tmp_path):
+def test_depth_kernels_register_budget():
     """The depth-frame kernels (dev_depth.hpp) and k_backproject, which shares their arithmetic: no scratch, and few enough VGPRs for
     full occupancy of a memory-bound pass (<= 32: 16 waves per SIMD)."""
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = str(tmp_path / "icp_hip.s")
-    flags = [f for f in g.HIPCC_FLAGS if f not in ("-shared", "-Wall")]
-    subprocess.check_call([hipcc] + flags + ["--cuda-device-only", "-w", "-I", os.path.join(ROOT, "include"), "-S",
-                           os.path.join(ROOT, "icp-variants_amd", "csrc", "icp_hip.hip"), "-o", out], timeout=900)
-    seen = {}
-    for name, field, val in re.findall(r"\.set (_ZN6icpdev\S*?)\.(num_vgpr|private_seg_size), (\d+)", open(out).read()):
-        seen.setdefault(name, {})[field] = int(val)
+    seen = kernel_resources(device_asm())
     for prefix in ("13k_depth_count", "15k_depth_scatter", "18k_conv_from_source", "13k_backproject"):
         ks = {n: f for n, f in seen.items() if n.startswith("_ZN6icpdev" + prefix)}
         assert len(ks) == 1, (prefix, list(ks))
