@@ -43,67 +43,14 @@ __device__ inline void jacobi_eig_sym(double* A /* n x n, destroyed */, double* 
     for (int i = 0; i < n; i++) ev[i] = A[i * n + i];
 }
 
-// Fast path: when the 6x6 normal matrix is comfortably full rank (every LDL^T pivot > 1e-9 x its diagonal entry,
-// i.e. far above the (6 eps_f32)^2 = 5e-13 relative eigenvalue cut of the SVD rule) the truncated-SVD solution IS the
-// plain solution and an unrolled fp64 LDL^T gives it in ~100 flops.  Otherwise: Jacobi eigen-decomposition.
-__device__ __forceinline__ bool solve_ldlt6(const double* sums, double* x) {
-    double a00 = sums[0], a01 = sums[1], a02 = sums[2], a03 = sums[3], a04 = sums[4], a05 = sums[5];
-    double a11 = sums[6], a12 = sums[7], a13 = sums[8], a14 = sums[9], a15 = sums[10];
-    double a22 = sums[11], a23 = sums[12], a24 = sums[13], a25 = sums[14];
-    double a33 = sums[15], a34 = sums[16], a35 = sums[17];
-    double a44 = sums[18], a45 = sums[19];
-    double a55 = sums[20];
-    const double g0 = sums[21], g1 = sums[22], g2 = sums[23], g3 = sums[24], g4 = sums[25], g5 = sums[26];
-    const double tol = 1e-9;
-    const double o00 = a00, o11 = a11, o22 = a22, o33 = a33, o44 = a44, o55 = a55;
-    // column 0
-    const double d0 = a00; if (!(d0 > tol * o00) || !(o00 > 0)) return false;
-    const double l10 = a01 / d0, l20 = a02 / d0, l30 = a03 / d0, l40 = a04 / d0, l50 = a05 / d0;
-    a11 -= l10 * a01; a12 -= l10 * a02; a13 -= l10 * a03; a14 -= l10 * a04; a15 -= l10 * a05;
-    a22 -= l20 * a02; a23 -= l20 * a03; a24 -= l20 * a04; a25 -= l20 * a05;
-    a33 -= l30 * a03; a34 -= l30 * a04; a35 -= l30 * a05;
-    a44 -= l40 * a04; a45 -= l40 * a05;
-    a55 -= l50 * a05;
-    const double d1 = a11; if (!(d1 > tol * o11)) return false;
-    const double l21 = a12 / d1, l31 = a13 / d1, l41 = a14 / d1, l51 = a15 / d1;
-    a22 -= l21 * a12; a23 -= l21 * a13; a24 -= l21 * a14; a25 -= l21 * a15;
-    a33 -= l31 * a13; a34 -= l31 * a14; a35 -= l31 * a15;
-    a44 -= l41 * a14; a45 -= l41 * a15;
-    a55 -= l51 * a15;
-    const double d2 = a22; if (!(d2 > tol * o22)) return false;
-    const double l32 = a23 / d2, l42 = a24 / d2, l52 = a25 / d2;
-    a33 -= l32 * a23; a34 -= l32 * a24; a35 -= l32 * a25;
-    a44 -= l42 * a24; a45 -= l42 * a25;
-    a55 -= l52 * a25;
-    const double d3 = a33; if (!(d3 > tol * o33)) return false;
-    const double l43 = a34 / d3, l53 = a35 / d3;
-    a44 -= l43 * a34; a45 -= l43 * a35;
-    a55 -= l53 * a35;
-    const double d4 = a44; if (!(d4 > tol * o44)) return false;
-    const double l54 = a45 / d4;
-    a55 -= l54 * a45;
-    const double d5 = a55; if (!(d5 > tol * o55)) return false;
-    // L z = g
-    const double z0 = g0;
-    const double z1 = g1 - l10 * z0;
-    const double z2 = g2 - l20 * z0 - l21 * z1;
-    const double z3 = g3 - l30 * z0 - l31 * z1 - l32 * z2;
-    const double z4 = g4 - l40 * z0 - l41 * z1 - l42 * z2 - l43 * z3;
-    const double z5 = g5 - l50 * z0 - l51 * z1 - l52 * z2 - l53 * z3 - l54 * z4;
-    // D y = z ; L^T x = y
-    const double x5 = z5 / d5;
-    const double x4 = z4 / d4 - l54 * x5;
-    const double x3 = z3 / d3 - l43 * x4 - l53 * x5;
-    const double x2 = z2 / d2 - l32 * x3 - l42 * x4 - l52 * x5;
-    const double x1 = z1 / d1 - l21 * x2 - l31 * x3 - l41 * x4 - l51 * x5;
-    const double x0 = z0 / d0 - l10 * x1 - l20 * x2 - l30 * x3 - l40 * x4 - l50 * x5;
-    x[0] = x0; x[1] = x1; x[2] = x2; x[3] = x3; x[4] = x4; x[5] = x5;
-    return true;
-}
-
+// Point-to-plane: the reference solves the 4n x 6 system with JacobiSVD and drops singular values <= 6 eps_f32 sigma_max
+// (ICPOptimizer.h:757-758).  On the normal matrix H = A^T A that is an eigenvalue cut at (6 eps_f32)^2 lambda_max, which is what
+// solve_normal_svd applies after a Jacobi eigen-decomposition.  The LDL^T fast path (p2plane_lanes_core) gives the same solution only
+// when the rule keeps all six directions, and it decides that itself (see there); whatever it refuses comes here.
+constexpr double RANK_CUT6 = 6.0 * 1.1920928955078125e-07;      // 6 eps_f32
+constexpr double RANK_CUT3 = 3.0 * 1.1920928955078125e-07;      // 3 eps_f32: the same rule for the 3 x 3 Procrustes matrix
 template <int COPY = 0>
 __device__ inline void solve_normal_svd(const double* sums /* 21 + 6 */, double* x) {
-    if (solve_ldlt6(sums, x)) return;
     // workspaces in LDS, not in registers / scratch: this runs on ONE thread, and inside the fused matcher it must not raise the
     // kernel's register or scratch footprint (a dispatch with a large scratch demand stalls the queue)
     __shared__ double A[36], V[36], ev[6];
@@ -113,7 +60,7 @@ __device__ inline void solve_normal_svd(const double* sums /* 21 + 6 */, double*
     jacobi_eig_sym<6, COPY>(A, V, ev);
     double emax = 0.0;
     for (int i = 0; i < 6; i++) emax = fmax(emax, ev[i]);
-    const double thr = 6.0 * 1.1920928955078125e-07;
+    const double thr = RANK_CUT6;
     for (int i = 0; i < 6; i++) x[i] = 0.0;
     for (int j = 0; j < 6; j++) {
         if (!(ev[j] > thr * thr * emax)) continue;
@@ -158,15 +105,23 @@ __device__ inline void solve_fullpiv_lu6(double* M, double* rhs, double* x, int*
 // for the two leading columns.  With c = U_0 x U_1 the reference's product collapses to
 //   R = U_0 V_0^T + U_1 V_1^T + det(V) * c * V_2^T
 // (flipping the sign of the third left vector flips det(UV^T) too), which stays well defined when sigma_3 -> 0.
+// Rank <= 1 leaves a whole family of optimal rotations; the contract (icp_hip.h, icp_iterate; the oracle's solve_p2p_t follows it) picks
+//   rank 0, sigma_1 <= noise_floor:                             R = I (what the reference's JacobiSVD of a zero matrix gives);
+//   rank 1, sigma_2 <= max(3 eps_f32 sigma_1, noise_floor):     the rotation by the smallest angle that takes v_1 to u_1 (axis v_1 x u_1;
+//           for u_1 = -v_1 the half turn about e_k - (e_k . v_1) v_1, k the smallest |v_1k|) -- independent of the null-space basis the
+//           Jacobi sweeps happen to return, I when nothing has to turn, continuous in A.  (Parity unpinned: Eigen's own pick for a rank-1
+//           matrix cannot be obtained without Eigen.)
+// noise_floor = (3 eps_f32)^2 x the largest uncentred moment |sum w d_j s_k|: a centred cloud smaller than that is below the resolution
+// of its own fp32 coordinates, and the cancellation noise of the moment expansion (~1e-16 of the same moment) stays 1000 x below it.
 template <int COPY = 0>
-__device__ inline void procrustes_rotation(const double* A /* 3x3 row-major */, double* R) {
+__device__ inline void procrustes_rotation(const double* A /* 3x3 row-major */, double noise_floor, double* R) {
     __shared__ double B[9], V[9], ev[3], Vs[9], U[9];     // LDS workspaces (single thread): see solve_normal_svd
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { double s = 0; for (int k = 0; k < 3; k++) s += A[k * 3 + i] * A[k * 3 + j]; B[i * 3 + j] = s; }
     jacobi_eig_sym<3, COPY>(B, V, ev);
     int o[3] = {0, 1, 2};
     for (int a = 0; a < 2; a++) for (int b = a + 1; b < 3; b++) if (ev[o[b]] > ev[o[a]]) { const int t = o[a]; o[a] = o[b]; o[b] = t; }
     for (int c = 0; c < 3; c++) for (int r = 0; r < 3; r++) Vs[r * 3 + c] = V[r * 3 + o[c]];
-    const double s0 = sqrt(fmax(ev[o[0]], 0.0));
+    double s0 = 0.0;
     for (int c = 0; c < 2; c++) {
         double u[3];
         for (int r = 0; r < 3; r++) { u[r] = 0; for (int k = 0; k < 3; k++) u[r] += A[r * 3 + k] * Vs[k * 3 + c]; }
@@ -174,16 +129,29 @@ __device__ inline void procrustes_rotation(const double* A /* 3x3 row-major */, 
             const double dp = u[0] * U[0] + u[1] * U[3] + u[2] * U[6];
             u[0] -= dp * U[0]; u[1] -= dp * U[3]; u[2] -= dp * U[6];
         }
-        double nr = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-        if (!(nr > 1e-13 * s0) || !(nr > 0.0)) {   // rank-deficient A: any unit vector orthogonal to what we have
-            if (c == 0) { u[0] = 1; u[1] = 0; u[2] = 0; }
-            else {
-                const double a0 = U[0], a1 = U[3], a2 = U[6];
-                const int kmin = fabs(a0) < fabs(a1) ? (fabs(a0) < fabs(a2) ? 0 : 2) : (fabs(a1) < fabs(a2) ? 1 : 2);
-                const double dp = (kmin == 0 ? a0 : (kmin == 1 ? a1 : a2));
-                u[0] = (kmin == 0 ? 1.0 : 0.0) - dp * a0; u[1] = (kmin == 1 ? 1.0 : 0.0) - dp * a1; u[2] = (kmin == 2 ? 1.0 : 0.0) - dp * a2;
+        const double nr = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);      // sigma_1, sigma_2
+        if (c == 0) {
+            s0 = nr;
+            if (!(nr > noise_floor)) { for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.0 : 0.0; return; }      // rank 0
+        } else if (!(nr > fmax(RANK_CUT3 * s0, noise_floor))) {                                                   // rank 1
+            const double v0 = Vs[0], v1 = Vs[3], v2 = Vs[6], u0 = U[0], u1 = U[3], u2 = U[6];
+            const double cs = v0 * u0 + v1 * u1 + v2 * u2;
+            if (1.0 + cs < 1e-8) {
+                const int kmin = fabs(v0) < fabs(v1) ? (fabs(v0) < fabs(v2) ? 0 : 2) : (fabs(v1) < fabs(v2) ? 1 : 2);
+                const double dp = (kmin == 0 ? v0 : (kmin == 1 ? v1 : v2));
+                double a[3] = {(kmin == 0 ? 1.0 : 0.0) - dp * v0, (kmin == 1 ? 1.0 : 0.0) - dp * v1, (kmin == 2 ? 1.0 : 0.0) - dp * v2};
+                const double an = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+                for (int i = 0; i < 3; i++) a[i] /= an;
+                for (int r = 0; r < 3; r++) for (int q = 0; q < 3; q++) R[r * 3 + q] = 2.0 * a[r] * a[q] - (r == q ? 1.0 : 0.0);
+            } else {
+                const double k0 = v1 * u2 - v2 * u1, k1 = v2 * u0 - v0 * u2, k2 = v0 * u1 - v1 * u0, f = 1.0 / (1.0 + cs);
+                // I + K + K^2 / (1 + cos), K = [k]x, K^2 = k k^T - |k|^2 I
+                const double kk = k0 * k0 + k1 * k1 + k2 * k2;
+                R[0] = 1.0 + f * (k0 * k0 - kk); R[1] = -k2 + f * (k0 * k1);      R[2] = k1 + f * (k0 * k2);
+                R[3] = k2 + f * (k1 * k0);       R[4] = 1.0 + f * (k1 * k1 - kk); R[5] = -k0 + f * (k1 * k2);
+                R[6] = -k1 + f * (k2 * k0);      R[7] = k0 + f * (k2 * k1);       R[8] = 1.0 + f * (k2 * k2 - kk);
             }
-            nr = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+            return;
         }
         for (int r = 0; r < 3; r++) U[r * 3 + c] = u[r] / nr;
     }
@@ -258,22 +226,30 @@ struct SolveParams {
     int spin;                      // 1: block 0 waits for the other blocks' totals (self-validating 8-byte values) instead of the ticket hand-over
 };
 
-// Point-to-plane fast path of k_reduce_solve on the lanes of the (last) block instead of one thread: the same LDL^T recurrences
-// as solve_ldlt6 (every element sees the same operations in the same order, so the result is bit-identical to it), the three
-// sincos on three lanes, the pose product on sixteen.  A single lane runs ~13 cycles per dependent fp64 operation with nothing
-// to overlap; this cuts the serial tail of every iteration from ~5 us to ~2 us.
+// Point-to-plane fast path of k_reduce_solve on the lanes of the (last) block instead of one thread: an unrolled fp64 LDL^T of the
+// 6 x 6 normal matrix, the three sincos on three lanes, the pose product on sixteen.  A single lane runs ~13 cycles per dependent fp64
+// operation with nothing to overlap; this cuts the serial tail of every iteration from ~5 us to ~2 us.
+// When it may be taken: the plain solution IS the reference's truncated-SVD solution only if the rank rule keeps all six directions,
+// i.e. lambda_min(H) > (6 eps_f32)^2 lambda_max(H).  Pivots that pass a test against their OWN diagonal entry do not show that: the test
+// is invariant under a rescaling of the unknowns, the rule is not (a cloud of +-1 m at 3000 m from the origin has every pivot above
+// 1e-9 of its diagonal and two singular values below the cut).  What does: lambda_max <= trace H and lambda_min >= 1 / trace H^-1, so
+//     (6 eps_f32)^2 * trace(H) * trace(H^-1) < 1
+// proves it, and holds whenever sigma_min / sigma_max > 6 * 6 eps_f32 = 4.3e-6 (each trace overestimates by at most 6).  trace(H^-1) =
+// sum_k |D^-1/2 L^-1 e_k|^2 comes out of the factors: lane k of the block's SECOND wave solves L z = e_k while the first wave runs the back
+// substitution, the sincos and the pose product (the longer chain): the guard costs the iteration one block barrier, not its arithmetic.
+// The pivot test against 1e-9 of the diagonal stays in front of it: it keeps zero and negative pivots out of the divisions.
 // p2plane_lanes_core: m = the 27 point-to-plane sums (shared memory), pose_in = the pose the iteration searched at (16 floats, global or
 // shared).  Returns the composed pose dT * pose_in (16 floats in shared memory, valid for every thread after the call) or nullptr when
-// a pivot fails the rank test (nothing computed).  All threads of the block must call it (>= 64 threads).
-// One wave does it: its LDS operations execute in program order, so the hand-overs between its lanes need no workgroup barrier -- only
+// the system fails the rank guard.  All threads of the block must call it (>= 128 threads: two waves).
+// One wave does the solve: its LDS operations execute in program order, so the hand-overs between its lanes need no workgroup barrier -- only
 // the compiler must keep the order (wave_sync).  Measured in the merged launch (tools/dev_ring_times.py): 2.8 us with twelve block barriers,
 // six sequential divisions in the back substitution and the rotation composed by one thread.
 __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 template <int COPY = 0>
 __device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* shared */, const float* pose_in) {
-    __shared__ double A[6][7], Lm[6][6], od[6], zs[6];
+    __shared__ double A[6][7], Lm[6][6], od[6], zs[6], rd[6], hinv[6];
     __shared__ float npose[16];
-    __shared__ int okflag;
+    __shared__ int okflag, guardflag;
     const int tid = threadIdx.x;
     if (tid < WAVE) {
         const int i = tid / 7, j = tid % 7;
@@ -283,7 +259,7 @@ __device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* sh
         bool ok_all = true;
         for (int k = 0; k < 6; k++) {
             const double d = A[k][k];
-            const bool ok = (d > 1e-9 * od[k]) && (k > 0 || od[0] > 0);          // solve_ldlt6's pivot tests
+            const bool ok = (d > 1e-9 * od[k]) && (k > 0 || od[0] > 0);          // positive, and not rounding noise of its own column
             if (!ok) { ok_all = false; break; }                                   // every lane sees the same values
             if (tid < 42 && i > k && j >= i) {
                 const double lik = A[k][i] / d;
@@ -293,7 +269,34 @@ __device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* sh
             wave_sync();
         }
         if (tid == 0) okflag = ok_all ? 1 : 0;
-        if (ok_all) {
+    }
+    __syncthreads();
+    const bool factored = okflag != 0;                                           // uniform
+    if (factored && tid >= WAVE && tid < 2 * WAVE) {
+        // the rank guard, on the second wave while the first one solves: lane k < 6 takes column k of L^-1 (forward substitution on e_k)
+        // and its share |D^-1/2 L^-1 e_k|^2 of trace(H^-1)
+        const int l = tid - WAVE;
+        if (l < 6) rd[l] = 1.0 / A[l][l];
+        wave_sync();
+        const int kk = l < 6 ? l : 0;
+        double z[6], h = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            double v = (r == kk) ? 1.0 : 0.0;
+#pragma unroll
+            for (int c = 0; c < r; c++) v = v - Lm[r][c] * z[c];
+            z[r] = v;
+            h = h + (v * v) * rd[r];
+        }
+        if (l < 6) hinv[l] = h;
+        wave_sync();
+        if (l == 0) {
+            const double tr = ((((od[0] + od[1]) + od[2]) + od[3]) + od[4]) + od[5], tri = ((((hinv[0] + hinv[1]) + hinv[2]) + hinv[3]) + hinv[4]) + hinv[5];
+            guardflag = (RANK_CUT6 * RANK_CUT6) * tr * tri < 1.0 ? 1 : 0;       // (0 for a NaN)
+        }
+    }
+    if (tid < WAVE) {
+        if (factored) {
             if (tid < 6) zs[tid] = A[tid][6] / A[tid][tid];                      // D y = z: the six quotients side by side ...
             wave_sync();
             // ... L^T x = y: the same subtractions in the same order as ever, by EVERY lane for itself (a wave pays per instruction, not per
@@ -338,11 +341,11 @@ __device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* sh
         }
     }
     __syncthreads();
-    if (!okflag) return nullptr;
+    if (!factored || !guardflag) return nullptr;
     return npose;
 }
 // The k_reduce_solve form: pose state updated in place.  Returns false (nothing written) when the fast path does not apply: other
-// metrics, no valid pair, or a pivot fails the rank test -> the caller's single-thread path with the eigen fallback.
+// metrics, no valid pair, or the system fails the rank guard -> the caller's single-thread path with the eigen-decomposition.
 template <int COPY = 0>
 __device__ __forceinline__ bool solve_p2plane_lanes(const SolveParams& sp, const double* tot /* shared */) {
     if (!(sp.update_pose && sp.metric == ICP_METRIC_POINT_TO_PLANE && sp.phase == 0 && tot[SUM_N] > 0)) return false;   // uniform
@@ -364,7 +367,7 @@ __device__ __forceinline__ bool solve_p2plane_lanes(const SolveParams& sp, const
     return true;
 }
 
-// The single-thread part of the solve (every metric, and point-to-plane when a pivot fails the rank test): thread 0 of the block
+// The single-thread part of the solve (every metric, and point-to-plane when the system fails the rank guard): thread 0 of the block
 // that holds the NSUM totals in `tot` (shared memory).  (A real call would not help the fused matcher, which inlines it too: on
 // AMDGPU a kernel reserves the registers of everything it may call -- 254 here.  The matcher caps its own budget instead, so this
 // cold code spills there rather than costing the tree walk a wave per SIMD.)
@@ -405,8 +408,10 @@ __device__ inline void solve_generic(const SolveParams& sp, const double* tot) {
         __shared__ double A[9], Rd[9];
         for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++)
             A[j * 3 + k] = m[7 + j * 3 + k] - m[4 + j] * (double)msf[k] - (double)mdf[j] * m[1 + k] + m[0] * (double)mdf[j] * (double)msf[k];
+        double mom = 0.0;
+        for (int i = 0; i < 9; i++) mom = fmax(mom, fabs(m[7 + i]));
         float R[9];
-        procrustes_rotation<COPY>(A, Rd);
+        procrustes_rotation<COPY>(A, (RANK_CUT3 * RANK_CUT3) * mom, Rd);
         for (int i = 0; i < 9; i++) R[i] = (float)Rd[i];
         const float tr[3] = {mdf[0] - msf[0], mdf[1] - msf[1], mdf[2] - msf[2]};     // ProcrustesAligner.h:70
         float t[3];
@@ -500,8 +505,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_reduce_solve(const SolveParam
 //   nothing has to be re-armed -- a run that was cut short leaves nothing behind that the next run could mistake for a result.
 //   Every wait is bounded (SPIN_LIMIT polls, seconds): a waiter that gives up raises *run_fault and the host repeats the run with the
 //   separate k_reduce_solve launches.  The same happens (PoseState::fault = 2 in the published slot, the rest of the chain passes it on
-//   without touching anything) when a pivot of the 6 x 6 system fails the rank test, i.e. when the solve needs the eigen fallback that
-//   only k_reduce_solve carries (131 VGPRs: it must not ride in the matcher).
+//   without touching anything) when the 6 x 6 system fails the rank guard of p2plane_lanes_core, i.e. when the solve needs the eigen-decomposition that
+//   only k_reduce_solve carries (99 VGPRs: it must not ride in the matcher, which is held to 80).
 // Thousands of waves polling ONE 128-byte line is a hot spot, not a broadcast: sc1 loads are served behind the L2, one memory channel
 // hands out a line every ~2 ns, so a round of 5 790 polls takes 11 us (measured: 24-28 us per converged iteration with a single slot,
 // against 14 + 7 with one launch per iteration).  Every slot therefore exists POSE_REPLICAS times on lines far enough apart to land on

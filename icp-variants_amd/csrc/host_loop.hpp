@@ -237,7 +237,7 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
         c->merged_runs++;
         const int rf = *(const int*)((char*)c->pinned + r.pin_pose + 128);
         if (hp->fault || rf) {
-            // a pivot of the 6 x 6 system failed the rank test (the eigen fallback lives in k_reduce_solve only), or a bounded wait ran out:
+            // the 6 x 6 system failed the rank guard (the eigen-decomposition lives in k_reduce_solve only), or a bounded wait ran out:
             // the same run again, from the incoming pose, in the separate form
             c->merged_fallbacks++;
             if (c->trace) fprintf(stderr, "[icp_hip] merged loop gave up: slot fault %d, abort word %d -> the run again with separate launches\n", hp->fault, rf);

@@ -148,7 +148,20 @@ int icp_correspond(icp_ctx* ctx, const float pose[16], icp_match_t* out, double*
  * pose_inout is the caller-owned in/out initialPose (ICPOptimizer.h:140,538,659).
  * icp_iterate runs stages 2-5 once on the full-resolution source (no multires bookkeeping).
  * icp_run runs n_iterations (or the multi-resolution schedule, ICPOptimizer.h:503-525,634-655) without
- * any host round trip inside the loop; stats (optional) receives up to max_stats records. */
+ * any host round trip inside the loop; stats (optional) receives up to max_stats records.
+ * Degenerate systems (few or badly placed correspondences) are solved by the reference's own rank rules, in fp64:
+ *   point-to-plane: singular values <= 6 eps_f32 sigma_max of the 4n x 6 system are dropped (JacobiSVD::solve, ICPOptimizer.h:757-758),
+ *     the minimum-norm solution of the rest is taken (an eigenvalue cut at (6 eps_f32)^2 on the normal matrix; the LDL^T fast path is
+ *     taken only where that rule provably keeps all six directions); GICP and colored ICP share this solve;
+ *   symmetric: FullPivLU's rule, pivots <= 6 eps_f32 |max pivot| are zero and their unknowns 0 (:866-868).  When the rotation part of
+ *     the solution is exactly 0 (source on target, one correspondence) the reference divides by tan_theta = 0 (:878-885): the pose of
+ *     that iteration is all NaN with status ICP_OK and the true n_valid, and the next iteration reports ICP_ERR_NO_CORRESPONDENCES;
+ *   point-to-point: Kabsch with the reflection guard, R = U diag(1, 1, det(U V^T)) V^T (ProcrustesAligner.h:55-64).  A Procrustes matrix
+ *     of rank <= 1 leaves a family of optimal rotations, of which this library returns: rank 0 (sigma_1 <= f, f = (3 eps_f32)^2 x the
+ *     largest |sum w d_j s_k|: one correspondence, coincident points) R = I, as the reference does; rank 1 (sigma_2 <= max(3 eps_f32
+ *     sigma_1, f): two correspondences, a line) the rotation by the smallest angle that takes v_1 to u_1 -- about v_1 x u_1, and for
+ *     u_1 = -v_1 the half turn about e_k - (e_k . v_1) v_1 with k the smallest |v_1k|.  Parity unpinned for rank 1: what Eigen's JacobiSVD
+ *     returns there cannot be obtained without Eigen. */
 int icp_iterate(icp_ctx* ctx, float pose_inout[16], icp_iter_stats* stats);
 int icp_run(icp_ctx* ctx, float pose_inout[16], icp_iter_stats* stats, int32_t max_stats, int32_t* n_iterations_run);
 int icp_get_timing(const icp_ctx* ctx, icp_timing* out);

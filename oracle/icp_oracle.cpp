@@ -254,18 +254,41 @@ int solve_p2p_t(const float* s, const float* d, const float* w, size_t n, float*
     std::sort(ord, ord + 3, [&](int a, int b) { return sv[a] > sv[b]; });
     T U[9], Vs[9];
     for (int c = 0; c < 3; c++) for (int r = 0; r < 3; r++) { U[r*3+c] = M[r*3+ord[c]]; Vs[r*3+c] = V[r*3+ord[c]]; }
-    // a zero singular value leaves its U column undefined: complete U to an orthonormal basis
-    if (!(sv[ord[2]] > T(0))) {
-        if (!(sv[ord[1]] > T(0))) {
-            if (!(sv[ord[0]] > T(0))) { for (int i = 0; i < 9; i++) U[i] = (i % 4 == 0) ? T(1) : T(0); }
-            else {
-                T u0[3] = {U[0], U[3], U[6]}; int k = std::fabs(u0[0]) < std::fabs(u0[1]) ? (std::fabs(u0[0]) < std::fabs(u0[2]) ? 0 : 2) : (std::fabs(u0[1]) < std::fabs(u0[2]) ? 1 : 2);
-                T e[3] = {0,0,0}; e[k] = 1; T dp = u0[k];
-                T u1[3] = {e[0] - dp*u0[0], e[1] - dp*u0[1], e[2] - dp*u0[2]};
-                T nr = std::sqrt(u1[0]*u1[0] + u1[1]*u1[1] + u1[2]*u1[2]);
-                for (int r = 0; r < 3; r++) U[r*3+1] = u1[r] / nr;
-            }
+    // Rank rule of the project (include/icp_hip.h, icp_iterate; the device's procrustes_rotation applies the same): a singular value
+    // <= 3 eps_f32 sigma_1 counts as zero (JacobiSVD's threshold for a 3 x 3), and so does anything <= noise_floor = (3 eps_f32)^2 x the
+    // largest uncentred moment |sum w d_j s_k| (a centred cloud below the resolution of its own fp32 coordinates).
+    //   rank 0: R = I, what the reference's JacobiSVD of a zero matrix gives (ProcrustesAligner.h:56: U = V = I);
+    //   rank 1: the rotation by the smallest angle that takes v_1 to u_1 -- the optimal rotations only share R v_1 = u_1, and which one a
+    //           completed basis yields depends on the null-space basis the sweeps return (PARITY UNPINNED: Eigen's own pick is not known);
+    //   rank 2: the third left vector is u_1 x u_2 (its sign cancels in U diag(1,1,det(UV^T)) V^T).
+    const T c3 = T(3) * (T)std::numeric_limits<float>::epsilon();
+    T mom = 0;
+    for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++) {
+        T acc = 0; for (size_t i = 0; i < n; i++) acc += ((T)w[i] * (T)d[i*3+j]) * (T)s[i*3+k];
+        mom = std::max(mom, std::fabs(acc));
+    }
+    const T noise_floor = c3 * c3 * mom, s0 = sv[ord[0]], s1 = sv[ord[1]];
+    bool have_R = false;
+    T Rt9[9];
+    if (!(s0 > noise_floor)) {
+        for (int i = 0; i < 9; i++) Rt9[i] = (i % 4 == 0) ? T(1) : T(0);
+        have_R = true;
+    } else if (!(s1 > std::max(c3 * s0, noise_floor))) {
+        const T v[3] = {Vs[0], Vs[3], Vs[6]}, u[3] = {U[0], U[3], U[6]};
+        const T cs = v[0]*u[0] + v[1]*u[1] + v[2]*u[2];
+        if (T(1) + cs < T(1e-8)) {                                // half turn: about e_k - (e_k . v) v, k the smallest |v_k|
+            int k = std::fabs(v[0]) < std::fabs(v[1]) ? (std::fabs(v[0]) < std::fabs(v[2]) ? 0 : 2) : (std::fabs(v[1]) < std::fabs(v[2]) ? 1 : 2);
+            T a[3] = {-v[k]*v[0], -v[k]*v[1], -v[k]*v[2]}; a[k] += T(1);
+            T an = std::sqrt(a[0]*a[0] + a[1]*a[1] + a[2]*a[2]);
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Rt9[r*3+c] = T(2) * (a[r] / an) * (a[c] / an) - (r == c ? T(1) : T(0));
+        } else {                                                  // I + K + K^2 / (1 + cos), K = [v x u]x
+            const T k[3] = {v[1]*u[2] - v[2]*u[1], v[2]*u[0] - v[0]*u[2], v[0]*u[1] - v[1]*u[0]}, f = T(1) / (T(1) + cs);
+            const T kk = k[0]*k[0] + k[1]*k[1] + k[2]*k[2];
+            const T K[9] = {0, -k[2], k[1], k[2], 0, -k[0], -k[1], k[0], 0};
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Rt9[r*3+c] = (r == c ? T(1) : T(0)) + K[r*3+c] + f * (k[r]*k[c] - (r == c ? kk : T(0)));
         }
+        have_R = true;
+    } else if (!(sv[ord[2]] > c3 * s0)) {
         T a0[3] = {U[0], U[3], U[6]}, a1[3] = {U[1], U[4], U[7]};
         U[2] = a0[1]*a1[2] - a0[2]*a1[1]; U[5] = a0[2]*a1[0] - a0[0]*a1[2]; U[8] = a0[0]*a1[1] - a0[1]*a1[0];
     }
@@ -275,7 +298,7 @@ int solve_p2p_t(const float* s, const float* d, const float* w, size_t n, float*
     float R[9];
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) {
         T acc = 0; for (int k = 0; k < 3; k++) acc += U[r*3+k] * (k == 2 ? dd : T(1)) * Vs[c*3+k];
-        R[r*3+c] = (float)acc;                                // :64
+        R[r*3+c] = (float)(have_R ? Rt9[r*3+c] : acc);        // :64
     }
     float tr[3] = {dm[0] - sm[0], dm[1] - sm[1], dm[2] - sm[2]};   // :70
     float Rt[3], Rd[3], t[3];

@@ -129,9 +129,15 @@ def unpack(s):
     return H, np.asarray(s[28:34], np.float64)
 
 
-def solve(s):
+def solve(s, lstsq=False):
+    """lstsq: the minimum-norm step with the point-to-plane solve's rank rule (eigenvalues <= (6 eps_f32)^2 lambda_max of H dropped) --
+    for systems that one or two pairs leave rank-deficient."""
     H, g = unpack(s)
-    return np.linalg.solve(H, g)
+    if not lstsq:
+        return np.linalg.solve(H, g)
+    ev, V = np.linalg.eigh(H)
+    keep = ev > (6.0 * float(np.finfo(f32).eps)) ** 2 * ev.max()
+    return V[:, keep] @ ((V[:, keep].T @ g) / ev[keep])
 
 
 def delta_f32(x):
