@@ -32,6 +32,12 @@ struct Cloud {
 // state, matches) is indexed by the same sorted position and streams coalesced.  factor 0 = the whole cloud, unfiltered.
 struct Level { DevBuf idx; DevBuf order; DevBuf sorted_idx; DevBuf pack; Cloud sorted; bool sorted_valid = false; int n = 0; };   // pack: the sorted copy's planes in ONE allocation (x y z nx ny nz cr cg cb rgba, a fixed stride apart)
 
+// Normal-space sampling (dev_nss.hpp).  NssLevel: a level's candidates sorted by bucket (cand), the segment starts (seg: nb + 1 ints), its long
+// segments (longs: one NssLongs); max_long / max_chunks: host-side bounds of their number and of their chunks, from the level's size alone.
+// NssHeld: the draw a run with resample = 0 holds for a decimation factor, as a level of its own; word = the iteration it was drawn for.
+struct NssLevel { DevBuf cand, seg, longs; int n_base = 0, max_long = 0, max_chunks = 0; };
+struct NssHeld { Level lv; uint32_t word = 0; };
+
 // LBVH over the target (buildIndex): device buffers + the host-side facts needed to launch the build.
 struct Bvh {
     bool valid = false;
@@ -78,7 +84,14 @@ struct icp_ctx {
     void* pin_up = nullptr; size_t pin_up_cap = 0; hipEvent_t up_ev = nullptr; bool up_pending = false;   // page-locked upload staging + "copy has left it" event
     DevBuf okeys, okeys2, ovals, otemp;  // scratch of the Morton sort of the queries
     std::map<int, Level> levels;         // multires selections by decimation factor
-    DevBuf sel_lists, sel_counts, sel_blocks;            // RANDOM_SAMPLING: per-iteration index lists, their sizes, scan scratch
+    DevBuf sel_lists, sel_counts, sel_blocks;            // RANDOM_SAMPLING / normal-space sampling: per-iteration index lists, their sizes, scan scratch
+    icp_nss_options nss_opt = {5, 1};                    // icp_set_nss_options
+    DevBuf nss_bkt; int nss_bkt_grid = 0;                // bucket of every source point for grid nss_bkt_grid (0: none computed for this source)
+    std::map<int, NssLevel> nss_levels;                  // by decimation factor, for nss_bkt_grid
+    std::map<int, NssHeld> nss_held;                     // by decimation factor, drawn for (nss_opt, nss_held_proba, nss_held_seed)
+    float nss_held_proba = 0.f; uint32_t nss_held_seed = 0u; bool nss_held_stale = false;   // stale: the options changed; dropped at the next loop start
+    DevBuf nss_table, nss_quota, nss_thr, nss_state, nss_hist, nss_total;   // scratch: the level sort's count table; per draw the quotas, thresholds, long-segment select state and histograms (left cleared)
+    std::vector<std::pair<const int*, int>> sel_last;    // icp_get_selection: the query set (device list, size) of every iteration of the last run with selection != 0
     DevBuf qpack; size_t q_cap = 0;                      // nn_raw | qstate | qstate2 (views below), q_cap elements each
     DevBuf qstate, qstate2;                              // incremental k-NN: per-query anchor + bound on the other targets; bound on the targets outside the neighbour's leaf
     DevBuf dbg_steps;                    // development builds only (ICP_DEBUG_STEPS)
@@ -125,6 +138,9 @@ void release(DevBuf& b) { if (b.p && !b.view) { (void)hipFree(b.p); g_live_bytes
 void set_view(DevBuf& b, void* p, size_t bytes) { release(b); b.p = p; b.cap = bytes; b.view = true; }
 void release(Cloud& c) { release(c.x); release(c.y); release(c.z); release(c.nx); release(c.ny); release(c.nz); release(c.cr); release(c.cg); release(c.cb); release(c.rgba); }
 void release(Level& lv) { release(lv.idx); release(lv.order); release(lv.sorted_idx); release(lv.sorted); release(lv.pack); lv.sorted_valid = false; }
+void release(NssLevel& nl) { release(nl.cand); release(nl.seg); release(nl.longs); }
+// the normal-space sampling caches that belong to the resident source (held: only the held draws, which also depend on the options)
+void drop_nss(icp_ctx* c, bool held_only);
 
 // Largest float c with (double)acosf(c) > 60*pi/180 on THIS host's libm: the device rejection test
 // `c <= cos_reject` is then bit-identical to the reference's `acos(c) > threshold` (ICPOptimizer.h:161,170)

@@ -189,35 +189,56 @@ int get_full_order(icp_ctx* c, const int** out) {
     return get_level(c, 0, &idx, &n, out);
 }
 
+// A level's points physically permuted into Morton order (d_idx: its selection, d_order: its Morton order; n > 0).
+int build_sorted_copy(icp_ctx* c, Level& lv, const int* d_idx, const int* d_order, int n) {
+    int rc;
+    if ((rc = ensure(c, lv.sorted_idx, (size_t)n * 4))) return rc;
+    const dim3 g((n + 255) / 256), b(256);
+    hipLaunchKernelGGL(k_compose_idx, g, b, 0, c->stream, d_idx, d_order, n, lv.sorted_idx.as<int>());
+    const int* si = lv.sorted_idx.as<int>();
+    Cloud& d = lv.sorted; const Cloud& s = c->src;
+    d.n = n; d.npad = n; d.has_normals = s.has_normals; d.has_colors = s.has_colors;
+    DevBuf* dst[9] = {&d.x, &d.y, &d.z, &d.nx, &d.ny, &d.nz, &d.cr, &d.cg, &d.cb};
+    const DevBuf* srcp[9] = {&s.x, &s.y, &s.z, &s.nx, &s.ny, &s.nz, &s.cr, &s.cg, &s.cb};
+    const size_t stride = ((size_t)n + 63) / 64 * 64;                         // elements between two planes
+    if ((rc = ensure(c, lv.pack, 10 * stride * 4))) return rc;
+    for (int k = 0; k < 9; k++) set_view(*dst[k], lv.pack.as<float>() + (size_t)k * stride, stride * 4);
+    set_view(d.rgba, lv.pack.as<float>() + 9 * stride, stride * 4);
+    for (int k = 0; k < 9; k++) {
+        if (!srcp[k]->p) continue;
+        hipLaunchKernelGGL(k_gather_f32, g, b, 0, c->stream, srcp[k]->as<float>(), si, n, dst[k]->as<float>());
+    }
+    if (s.rgba.p) hipLaunchKernelGGL(k_gather_u32, g, b, 0, c->stream, s.rgba.as<uint32_t>(), si, n, d.rgba.as<uint32_t>());
+    HIPCK(c, hipGetLastError());
+    lv.sorted_valid = true;
+    return ICP_OK;
+}
 // The level's points physically permuted into Morton order (built once per icp_set_source and level).
 int get_sorted_level(icp_ctx* c, int factor, const Cloud** cloud, int* n_out) {
     const int* d_idx; const int* d_order; int n, rc;
     if ((rc = get_level(c, factor, &d_idx, &n, &d_order))) return rc;
     Level& lv = c->levels[factor];
     *n_out = n;
-    if (!lv.sorted_valid && n > 0) {
-        if ((rc = ensure(c, lv.sorted_idx, (size_t)n * 4))) return rc;
-        const dim3 g((n + 255) / 256), b(256);
-        hipLaunchKernelGGL(k_compose_idx, g, b, 0, c->stream, d_idx, d_order, n, lv.sorted_idx.as<int>());
-        const int* si = lv.sorted_idx.as<int>();
-        Cloud& d = lv.sorted; const Cloud& s = c->src;
-        d.n = n; d.npad = n; d.has_normals = s.has_normals; d.has_colors = s.has_colors;
-        DevBuf* dst[9] = {&d.x, &d.y, &d.z, &d.nx, &d.ny, &d.nz, &d.cr, &d.cg, &d.cb};
-        const DevBuf* srcp[9] = {&s.x, &s.y, &s.z, &s.nx, &s.ny, &s.nz, &s.cr, &s.cg, &s.cb};
-        const size_t stride = ((size_t)n + 63) / 64 * 64;                         // elements between two planes
-        if ((rc = ensure(c, lv.pack, 10 * stride * 4))) return rc;
-        for (int k = 0; k < 9; k++) set_view(*dst[k], lv.pack.as<float>() + (size_t)k * stride, stride * 4);
-        set_view(d.rgba, lv.pack.as<float>() + 9 * stride, stride * 4);
-        for (int k = 0; k < 9; k++) {
-            if (!srcp[k]->p) continue;
-            hipLaunchKernelGGL(k_gather_f32, g, b, 0, c->stream, srcp[k]->as<float>(), si, n, dst[k]->as<float>());
-        }
-        if (s.rgba.p) hipLaunchKernelGGL(k_gather_u32, g, b, 0, c->stream, s.rgba.as<uint32_t>(), si, n, d.rgba.as<uint32_t>());
-        HIPCK(c, hipGetLastError());
-        lv.sorted_valid = true;
+    if (!lv.sorted_valid && n > 0 && (rc = build_sorted_copy(c, lv, d_idx, d_order, n))) return rc;
+    *cloud = &lv.sorted;
+    return ICP_OK;
+}
+// The same for a held normal-space draw, a level of its own (its index list is there already).
+int get_sorted_held(icp_ctx* c, Level& lv, const Cloud** cloud) {
+    int rc;
+    if (!lv.sorted_valid && lv.n > 0) {
+        if (!lv.order.p && (rc = build_query_order(c, lv.idx.as<int>(), lv.n, lv.order))) return rc;
+        if ((rc = build_sorted_copy(c, lv, lv.idx.as<int>(), lv.order.as<int>(), lv.n))) return rc;
     }
     *cloud = &lv.sorted;
     return ICP_OK;
+}
+void drop_nss(icp_ctx* c, bool held_only) {
+    for (auto& kv : c->nss_held) release(kv.second.lv);
+    c->nss_held.clear(); c->nss_held_stale = false;
+    if (held_only) return;
+    for (auto& kv : c->nss_levels) release(kv.second);
+    c->nss_levels.clear(); c->nss_bkt_grid = 0;
 }
 
 // Bookkeeping behind a freshly written target (icp_set_target, the promotion of a batch's source, icp_set_target_depth): the finite
@@ -247,6 +268,7 @@ int finish_source(icp_ctx* c) {
     const int n = c->src.n; const Cloud& s = c->src;
     for (auto& kv : c->levels) release(kv.second);
     c->levels.clear();
+    drop_nss(c, false); c->sel_last.clear();
     c->gicp_ready[1] = false;
     if (n <= 0) return ICP_OK;
     if ((rc = ensure(c, c->src_flag, (size_t)n))) return rc;

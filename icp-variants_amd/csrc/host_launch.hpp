@@ -159,8 +159,10 @@ GicpPost gicp_post_params(icp_ctx* c, const Cloud& src) {
     g.tnx = own_t ? c->tgt.nx.as<float>() : c->gicp_n[0][0].as<float>(); g.tny = own_t ? c->tgt.ny.as<float>() : c->gicp_n[0][1].as<float>(); g.tnz = own_t ? c->tgt.nz.as<float>() : c->gicp_n[0][2].as<float>();
     g.snx = own_s ? c->src.nx.as<float>() : c->gicp_n[1][0].as<float>(); g.sny = own_s ? c->src.ny.as<float>() : c->gicp_n[1][1].as<float>(); g.snz = own_s ? c->src.nz.as<float>() : c->gicp_n[1][2].as<float>();
     g.src_orig = nullptr;
-    if (&src != &c->src)
+    if (&src != &c->src) {
         for (auto& kv : c->levels) if (&kv.second.sorted == &src) g.src_orig = kv.second.sorted_idx.as<int>();
+        for (auto& kv : c->nss_held) if (&kv.second.lv.sorted == &src) g.src_orig = kv.second.lv.sorted_idx.as<int>();
+    }
     g.one_minus_eps = 1.0 - (double)c->gicp_opt.epsilon;
     return g;
 }

@@ -7,13 +7,147 @@ namespace {
 struct RunPlan {
     std::vector<int> factors, ns; std::vector<const Cloud*> clouds; std::vector<const int*> sels, orders;
     bool sorted_levels = false;      // BVH matcher without resampling: every level is a physical, Morton-sorted copy -> no index lists in the loop at all
+    bool fixed_sets = true;          // no resampling: SELECT_ALL, or a normal-space draw held for the run
     int iters() const { return (int)factors.size(); }
     // seed the search with the previous iteration's neighbours when it matched the same queries: same level, it had work, no resampling
-    bool seeded(int i, const icp_params& p) const { return i > 0 && factors[i] == factors[i - 1] && ns[i - 1] > 0 && p.selection == 0; }
+    bool seeded(int i) const { return i > 0 && factors[i] == factors[i - 1] && ns[i - 1] > 0 && fixed_sets; }
 };
+
+// ---- normal-space sampling: the launches of dev_nss.hpp ----
+// The bucket of every source point for the current grid (cached per source and grid; a new grid also drops the levels sorted by it).
+int nss_buckets(icp_ctx* c) {
+    const int grid = c->nss_opt.grid, n = c->src.n;
+    if (c->nss_bkt_grid == grid) return ICP_OK;
+    int rc;
+    for (auto& kv : c->nss_levels) release(kv.second);      // sorted by the buckets of another grid
+    c->nss_levels.clear();
+    const Cloud& s = c->src;
+    if ((rc = ensure(c, c->nss_bkt, (size_t)n * 2))) return rc;
+    hipLaunchKernelGGL(k_nss_bucket, dim3((n + 255) / 256), dim3(256), 0, c->stream, s.x.as<float>(), s.y.as<float>(), s.z.as<float>(),
+                       s.nx.as<float>(), s.ny.as<float>(), s.nz.as<float>(), n, grid, c->nss_bkt.as<unsigned short>());
+    HIPCK(c, hipGetLastError());
+    c->nss_bkt_grid = grid;
+    return ICP_OK;
+}
+// Once per level: the base set's candidates in a stable counting sort by bucket, the segment starts, the long segments.  Enqueued only.
+int nss_level(icp_ctx* c, int factor, const int* base, int n_base, const NssLevel** out) {
+    auto it = c->nss_levels.find(factor);
+    if (it == c->nss_levels.end()) {
+        NssLevel nl; int rc;
+        const int nb = 6 * c->nss_opt.grid * c->nss_opt.grid, nblocks = (n_base + NSS_LEVEL_THREADS - 1) / NSS_LEVEL_THREADS;
+        nl.n_base = n_base; nl.max_long = n_base / NSS_LONG; nl.max_chunks = n_base / NSS_CHUNK + nl.max_long;      // (a long segment has > NSS_LONG points; one partial chunk each)
+        const int n_table = (nb + 1) * nblocks;
+        if ((rc = ensure(c, nl.cand, (size_t)n_base * 4)) || (rc = ensure(c, nl.seg, (NSS_MAX_BUCKETS + 2) * 4)) || (rc = ensure(c, nl.longs, sizeof(NssLongs)))) { release(nl); return rc; }
+        if ((rc = ensure(c, c->nss_table, (size_t)n_table * 4)) || (rc = ensure(c, c->nss_total, 4))) { release(nl); return rc; }
+        const unsigned short* bkt = c->nss_bkt.as<unsigned short>();
+        hipLaunchKernelGGL(k_nss_level_hist, dim3(nblocks), dim3(NSS_LEVEL_THREADS), 0, c->stream, base, n_base, bkt, nb, c->nss_table.as<int>(), nblocks);
+        hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, c->stream, c->nss_table.as<int>(), n_table, c->nss_total.as<int>());
+        hipLaunchKernelGGL(k_nss_level_scatter, dim3(nblocks), dim3(NSS_LEVEL_THREADS), 0, c->stream, base, n_base, bkt, nb, c->nss_table.as<int>(), nblocks, nl.cand.as<int>());
+        hipLaunchKernelGGL(k_nss_level_segs, dim3(1), dim3(NSS_QUOTA_THREADS), 0, c->stream, c->nss_table.as<int>(), nblocks, nb, nl.seg.as<int>(), nl.longs.as<NssLongs>());
+        if (hipGetLastError() != hipSuccess) { release(nl); c->err = "normal-space sampling: a level launch failed"; return ICP_ERR_HIP; }
+        it = c->nss_levels.emplace(factor, nl).first;
+    }
+    *out = &it->second;
+    return ICP_OK;
+}
+// n_draws draws of one level, for iterations word0 .. word0 + n_draws - 1, into slots word0 .. of sel_lists / sel_counts (slot stride cap).
+// Scratch per slot: 2 rows of NSS_ROW words (quotas, thresholds) and, per possible long segment (max_long_all = n_src / NSS_LONG of them),
+// 8 bytes of state and one 2048-bin histogram: 8 KB * n_src / 16384 = n_src / 2 bytes, an eighth of the slot's index list.
+int nss_draw(icp_ctx* c, const NssLevel& nl, const int* base, uint32_t word0, int n_draws, int max_long_all, size_t cap) {
+    const icp_params& p = c->prm;
+    const int nb = 6 * c->nss_opt.grid * c->nss_opt.grid, n = nl.n_base, nblk = (n + 255) / 256, stride = nblk + 1;
+    unsigned int* quota = c->nss_quota.as<unsigned int>() + (size_t)word0 * NSS_ROW; unsigned int* thr = c->nss_thr.as<unsigned int>() + (size_t)word0 * NSS_ROW;
+    NssLongState* state = c->nss_state.as<NssLongState>() + (size_t)word0 * max_long_all;
+    unsigned int* hist = c->nss_hist.as<unsigned int>() + (size_t)word0 * max_long_all * NSS_BINS;
+    int* counts = c->sel_counts.as<int>() + word0; int* blocks = c->sel_blocks.as<int>();
+    const int* cand = nl.cand.as<int>(); const int* seg = nl.seg.as<int>(); const NssLongs* longs = nl.longs.as<NssLongs>();
+    const unsigned short* bkt = c->nss_bkt.as<unsigned short>();
+    const uint32_t seed = p.selection_seed;
+    const dim3 B(NSS_THREADS);
+    hipLaunchKernelGGL(k_nss_quota, dim3(n_draws), dim3(NSS_QUOTA_THREADS), 0, c->stream, seg, nb, p.selection_proba, seed, word0, quota, thr);
+    hipLaunchKernelGGL(k_nss_select_small, dim3(nb, n_draws), B, 0, c->stream, cand, seg, seed, word0, quota, thr);
+    if (nl.max_long > 0) {
+        const dim3 gh(nl.max_chunks, n_draws), gp(nl.max_long, n_draws);
+        hipLaunchKernelGGL(k_nss_long_hist<1>, gh, B, 0, c->stream, cand, seg, longs, max_long_all, seed, word0, quota, state, hist);
+        hipLaunchKernelGGL(k_nss_long_pick<1>, gp, B, 0, c->stream, seg, longs, max_long_all, quota, state, hist, thr);
+        hipLaunchKernelGGL(k_nss_long_hist<2>, gh, B, 0, c->stream, cand, seg, longs, max_long_all, seed, word0, quota, state, hist);
+        hipLaunchKernelGGL(k_nss_long_pick<2>, gp, B, 0, c->stream, seg, longs, max_long_all, quota, state, hist, thr);
+        hipLaunchKernelGGL(k_nss_long_hist<3>, gh, B, 0, c->stream, cand, seg, longs, max_long_all, seed, word0, quota, state, hist);
+        hipLaunchKernelGGL(k_nss_long_pick<3>, gp, B, 0, c->stream, seg, longs, max_long_all, quota, state, hist, thr);
+    }
+    hipLaunchKernelGGL(k_nss_count, dim3(nblk, n_draws), dim3(256), 0, c->stream, base, n, bkt, seed, word0, quota, thr, blocks, stride);
+    hipLaunchKernelGGL(k_nss_scan, dim3(n_draws), dim3(1024), 0, c->stream, blocks, nblk, stride, counts);
+    hipLaunchKernelGGL(k_nss_scatter, dim3(nblk, n_draws), dim3(256), 0, c->stream, base, n, bkt, seed, word0, quota, thr, blocks, stride, c->sel_lists.as<int>() + (size_t)word0 * cap, cap);
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+// The query sets of a run with selection = ICP_SELECT_NORMAL_SPACE: every draw made up front on the device, ONE copy of their sizes.
+// resample: iteration i draws with word i from its level's base set (sels[i], ns[i] on entry).  Held: a factor's first iteration draws for
+// all of them, and the list becomes a level of its own (c->nss_held), Morton-sorted for the BVH matcher like a multires level.
+int nss_plan(icp_ctx* c, RunPlan& pl) {
+    const icp_params& p = c->prm;
+    const int iters = pl.iters(); int rc;
+    const bool held = c->nss_opt.resample == 0;
+    if (!c->src.has_normals) { c->err = "normal-space sampling (selection = 2) needs normals on the source"; return ICP_ERR_INVALID_ARG; }
+    if (c->nss_held_stale || c->nss_held_proba != p.selection_proba || c->nss_held_seed != p.selection_seed) drop_nss(c, true);
+    c->nss_held_proba = p.selection_proba; c->nss_held_seed = p.selection_seed;
+    if ((rc = nss_buckets(c))) return rc;
+    const size_t cap = (size_t)c->src.n; const int max_long_all = c->src.n / NSS_LONG;
+    const size_t hist_bytes = (size_t)iters * max_long_all * NSS_BINS * 4;
+    if ((rc = ensure(c, c->sel_lists, (size_t)iters * cap * 4)) || (rc = ensure(c, c->sel_counts, (size_t)iters * 4))) return rc;
+    if ((rc = ensure(c, c->sel_blocks, (size_t)iters * ((cap + 255) / 256 + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->nss_quota, (size_t)iters * NSS_ROW * 4)) || (rc = ensure(c, c->nss_thr, (size_t)iters * NSS_ROW * 4))) return rc;
+    if ((rc = ensure(c, c->nss_state, (size_t)iters * (max_long_all + 1) * sizeof(NssLongState)))) return rc;
+    if (hist_bytes > c->nss_hist.cap || !c->nss_hist.p) {
+        if ((rc = ensure(c, c->nss_hist, hist_bytes))) return rc;
+        HIPCK(c, hipMemsetAsync(c->nss_hist.p, 0, c->nss_hist.cap, c->stream));      // every pick leaves its histogram cleared
+    }
+    HIPCK(c, hipMemsetAsync(c->sel_counts.p, 0, (size_t)iters * 4, c->stream));
+    std::vector<int> first((size_t)iters);                   // the iteration whose draw iteration i uses
+    std::vector<char> drawn((size_t)iters, 0);
+    for (int i = 0; i < iters; i++) {
+        first[i] = i;
+        if (held) for (int j = 0; j < i; j++) if (pl.factors[j] == pl.factors[i]) { first[i] = j; break; }
+    }
+    for (int i = 0; i < iters;) {
+        int run = 1;
+        if (held) {
+            auto it = c->nss_held.find(pl.factors[i]);
+            if (first[i] != i || (it != c->nss_held.end() && it->second.word == (uint32_t)i)) { i++; continue; }
+            if (it != c->nss_held.end()) { release(it->second.lv); c->nss_held.erase(it); }
+        } else while (i + run < iters && pl.factors[i + run] == pl.factors[i]) run++;
+        if (pl.ns[i] > 0) {
+            const NssLevel* nl = nullptr;
+            if ((rc = nss_level(c, pl.factors[i], pl.sels[i], pl.ns[i], &nl))) return rc;
+            // (sel_blocks: the draws of a level use the buffer from its start; the next level's launches follow on the stream)
+            if ((rc = nss_draw(c, *nl, pl.sels[i], (uint32_t)i, run, max_long_all, cap))) return rc;
+        }
+        for (int k = 0; k < run; k++) drawn[i + k] = 1;
+        i += run;
+    }
+    std::vector<int> counts((size_t)iters);
+    HIPCK(c, hipMemcpyAsync(counts.data(), c->sel_counts.p, (size_t)iters * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < iters; i++) {
+        if (!held) { pl.sels[i] = c->sel_lists.as<int>() + (size_t)i * cap; pl.ns[i] = counts[i]; pl.orders[i] = nullptr; continue; }
+        if (drawn[i]) {                                      // the list leaves the scratch: a level of its own
+            NssHeld& h = c->nss_held[pl.factors[i]];
+            h.word = (uint32_t)i; h.lv.n = counts[i];
+            if ((rc = ensure(c, h.lv.idx, (size_t)(counts[i] > 0 ? counts[i] : 1) * 4))) return rc;
+            if (counts[i] > 0) HIPCK(c, hipMemcpyAsync(h.lv.idx.p, c->sel_lists.as<int>() + (size_t)i * cap, (size_t)counts[i] * 4, hipMemcpyDeviceToDevice, c->stream));
+        }
+        Level& lv = c->nss_held[pl.factors[i]].lv;
+        pl.ns[i] = lv.n; pl.orders[i] = nullptr;
+        if (pl.sorted_levels) { pl.sels[i] = nullptr; if ((rc = get_sorted_held(c, lv, &pl.clouds[i]))) return rc; }
+        else pl.sels[i] = lv.idx.as<int>();
+    }
+    return ICP_OK;
+}
+
 int make_plan(icp_ctx* c, bool single, RunPlan& pl) {
     const icp_params& p = c->prm;
     int rc;
+    c->sel_last.clear();
     if (single) pl.factors.assign(1, 0);
     else {
         int32_t cnt = 0;
@@ -23,14 +157,17 @@ int make_plan(icp_ctx* c, bool single, RunPlan& pl) {
     }
     const std::vector<int>& factors = pl.factors; std::vector<int>& ns = pl.ns; std::vector<const int*>& sels = pl.sels; std::vector<const int*>& orders = pl.orders;
     const int iters = pl.iters();
-    const bool resample = !single && p.selection == 1;
+    const bool nss = !single && p.selection == ICP_SELECT_NORMAL_SPACE;
+    const bool resample = !single && p.selection == ICP_SELECT_RANDOM;
+    pl.fixed_sets = !resample && !(nss && c->nss_opt.resample != 0);
     sels.assign((size_t)iters, nullptr); ns.assign((size_t)iters, c->src.n); orders.assign((size_t)iters, nullptr); pl.clouds.assign((size_t)iters, &c->src);
-    pl.sorted_levels = p.matching == ICP_MATCH_KNN && p.knn_backend == ICP_KNN_LBVH && !resample;
+    pl.sorted_levels = p.matching == ICP_MATCH_KNN && p.knn_backend == ICP_KNN_LBVH && pl.fixed_sets;
     if (iters == 0) return ICP_OK;
     for (int i = 0; i < iters; i++) {
-        if (pl.sorted_levels) { if ((rc = get_sorted_level(c, factors[i], &pl.clouds[i], &ns[i]))) return rc; }
+        if (pl.sorted_levels && !nss) { if ((rc = get_sorted_level(c, factors[i], &pl.clouds[i], &ns[i]))) return rc; }
         else if (factors[i] > 0) { if ((rc = get_level(c, factors[i], &sels[i], &ns[i], nullptr))) return rc; }
     }
+    if (nss && (rc = nss_plan(c, pl))) return rc;
     if (resample) {
         // RANDOM_SAMPLING (ICPOptimizer.h:549-550: resample at the start of every iteration, over the current level's cloud).
         // All resamples are drawn up front on the device; one small copy returns their sizes so the loop stays launch-only.
@@ -56,6 +193,14 @@ int make_plan(icp_ctx* c, bool single, RunPlan& pl) {
         HIPCK(c, hipMemcpyAsync(counts.data(), c->sel_counts.p, (size_t)iters * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCK(c, hipStreamSynchronize(c->stream));
         for (int i = 0; i < iters; i++) ns[i] = counts[i];
+    }
+    if (resample || nss) {                                   // icp_get_selection
+        c->sel_last.resize((size_t)iters);
+        for (int i = 0; i < iters; i++) {
+            const int* list = sels[i];
+            if (nss && pl.fixed_sets) list = c->nss_held[factors[i]].lv.idx.as<int>();
+            c->sel_last[(size_t)i] = std::make_pair(ns[i] > 0 ? list : nullptr, ns[i]);
+        }
     }
     return ICP_OK;
 }
@@ -136,7 +281,7 @@ int enqueue_merged(icp_ctx* c, LoopRun& r) {
     };
     HIPCK(c, hipEventRecord(c->events[0], c->stream));
     for (int i = 0; i < iters; i++) {
-        QuerySet q{pl.clouds[i], pl.sels[i], pl.ns[i], 0, p.color_icp != 0 && p.matching == ICP_MATCH_KNN, pl.seeded(i, p), pl.orders[i]};
+        QuerySet q{pl.clouds[i], pl.sels[i], pl.ns[i], 0, p.color_icp != 0 && p.matching == ICP_MATCH_KNN, pl.seeded(i), pl.orders[i]};
         MergeLaunch ml; ml.rp = reducer(i); ml.slot = loop_slot(ring.slots, i, 0); ml.partials = ring_partials(c, i);
         if (r.sampled[i]) { r.ev[i].start = ml.ev_start = loop_event(c, i, 0); r.ev[i].matched = ml.ev_stop = loop_event(c, i, 1); }
         int fused = 0;
@@ -171,7 +316,7 @@ int enqueue_separate(icp_ctx* c, LoopRun& r) {
         }
         if (pl.ns[i] > 0) {
             // (keep_records: the fused matcher writes its records for k_lm_eval)
-            QuerySet q{pl.clouds[i], pl.sels[i], pl.ns[i], 0, p.color_icp != 0 && p.matching == ICP_MATCH_KNN, pl.seeded(i, p), pl.orders[i], r.lm};
+            QuerySet q{pl.clouds[i], pl.sels[i], pl.ns[i], 0, p.color_icp != 0 && p.matching == ICP_MATCH_KNN, pl.seeded(i), pl.orders[i], r.lm};
             int fused = 0;
             if ((rc = launch_match(c, q, !r.robust ? &fused : nullptr))) return rc;
             if (ev) HIPCK(c, hipEventRecord(r.ev[i].matched, c->stream));

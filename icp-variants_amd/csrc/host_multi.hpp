@@ -66,7 +66,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
         KnnParams kp = knn_params(c, *q, sels[i], n);
         kp.ps = d_ps; kp.fault = &d_ps->fault;
         kp.nn_raw = c->ms_nn.as<int>();
-        kp.use_prev = pl.seeded(i, p) ? 1 : 0;
+        kp.use_prev = pl.seeded(i) ? 1 : 0;
         if (p.knn_incremental) { kp.qstate = c->ms_st.as<float4>(); kp.qstate2 = c->ms_st2.as<float2>(); kp.incremental = 1; }
         PostParams pp = make_post_params(c, *q, sels[i], n);
         pp.ps = d_ps; pp.partials = c->ms_partials.as<double>();

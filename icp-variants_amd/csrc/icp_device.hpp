@@ -7,7 +7,7 @@
 // fp32 sqrt and divide are correctly rounded (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt).
 //
 // Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_solve.hpp,
-// dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp
+// dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -36,6 +36,8 @@
 //                       r^2, trimming and IRLS reweighting of the records in place, before the unchanged post kernels (dev_robust.hpp)
 //   k_color_gradients<K> colored ICP (Park, Zhou, Koltun 2017): per-point colour gradients of the target from its K nearest neighbours;
 //   k_post_colored      k_post_colored weights, rejects and filters as k_post does, then adds the geometric and photometric rows (dev_colored.hpp)
+//   k_nss_*             normal-space sampling (Rusinkiewicz and Levoy 2001): buckets of the source normals on a cube map, water-filled
+//                       quotas and an exact radix select of each bucket's smallest hashes (dev_nss.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -63,5 +65,6 @@ namespace icpdev {
 #include "dev_gicp.hpp"
 #include "dev_robust.hpp"
 #include "dev_colored.hpp"
+#include "dev_nss.hpp"
 
 }  // namespace icpdev

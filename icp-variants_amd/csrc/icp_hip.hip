@@ -86,6 +86,8 @@ int icp_ctx_destroy(icp_ctx* c) {
     for (Bvh* b : {&c->bvh6, &c->nrm_bvh}) { release(b->keys); release(b->keys2); release(b->vals); release(b->vals2); release(b->temp); release(b->leaves); release(b->nodes); }
     release(c->bvh.keys); release(c->bvh.keys2); release(c->bvh.vals); release(c->bvh.vals2); release(c->bvh.temp); release(c->bvh.leaves); release(c->okeys); release(c->okeys2); release(c->ovals); release(c->otemp); release(c->bvh.nodes);
     for (auto& kv : c->levels) release(kv.second);
+    drop_nss(c, false);
+    for (DevBuf* d : {&c->nss_bkt, &c->nss_table, &c->nss_quota, &c->nss_thr, &c->nss_state, &c->nss_hist, &c->nss_total}) release(*d);
     release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->totals); release(c->dbg_steps); release(c->sums);
     release(c->lm_state); release(c->lm_partials); release(c->lm_sums);
     for (auto& pl : c->gicp_n) for (DevBuf& d : pl) release(d);
@@ -117,7 +119,7 @@ const char* icp_last_error(const icp_ctx* c) { return c ? c->err.c_str() : "null
 
 int icp_set_params(icp_ctx* c, const icp_params* p) {
     if (!c || !p) return ICP_ERR_INVALID_ARG;
-    if (p->metric < 0 || p->metric > 4 || p->matching < 0 || p->matching > 1 || p->weighting < 0 || p->weighting > 3 || p->n_iterations < 0 || p->selection < 0 || p->selection > 1 ||
+    if (p->metric < 0 || p->metric > 4 || p->matching < 0 || p->matching > 1 || p->weighting < 0 || p->weighting > 3 || p->n_iterations < 0 || p->selection < ICP_SELECT_ALL || p->selection > ICP_SELECT_NORMAL_SPACE ||
         (p->knn_backend != ICP_KNN_BRUTE_FORCE && p->knn_backend != ICP_KNN_LBVH) || p->width < 0 || p->height < 0 || (long long)p->width * p->height > 0x7FFFFFFFll ||
         std::isnan(p->max_distance) || std::isnan(p->selection_proba) || !std::isfinite(p->fx) || !std::isfinite(p->fy) || !std::isfinite(p->cx) || !std::isfinite(p->cy)) {
         c->err = "icp_set_params: value out of range"; return ICP_ERR_INVALID_ARG;
@@ -220,6 +222,54 @@ int icp_get_robust_stats(const icp_ctx* c, icp_robust_stats* out, int32_t max_ou
     for (int32_t i = 0; i < n && i < max_out; i++) out[i] = c->rob_last[(size_t)i];
     if (count_out) *count_out = n;
     return ICP_OK;
+}
+
+int icp_nss_options_default(icp_nss_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    o->grid = 5; o->resample = 1;
+    return ICP_OK;
+}
+int icp_set_nss_options(icp_ctx* c, const icp_nss_options* o) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    icp_nss_options v;
+    if (o) v = *o; else icp_nss_options_default(&v);
+    if (!(v.grid == 3 || v.grid == 5 || v.grid == 7) || !(v.resample == 0 || v.resample == 1)) {
+        c->err = "icp_set_nss_options: need grid in {3, 5, 7} and resample in {0, 1}"; return ICP_ERR_INVALID_ARG;
+    }
+    c->nss_opt = v;
+    c->nss_held_stale = true;                                // the bucket cache and the sorted levels follow the grid at their next use (nss_buckets)
+    return ICP_OK;
+}
+int icp_get_nss_options(const icp_ctx* c, icp_nss_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->nss_opt; return ICP_OK; }
+int icp_get_normal_buckets(icp_ctx* c, uint16_t* out, int32_t max_points, int32_t* n_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (max_points < 0 || (!out && max_points > 0)) { c->err = "icp_get_normal_buckets: bad argument (max_points >= 0)"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if (c->src.n <= 0) { c->err = "no source cloud (icp_set_source)"; return ICP_ERR_NO_SOURCE; }
+    if (!c->src.has_normals) { c->err = "icp_get_normal_buckets: the source has no normals"; return ICP_ERR_INVALID_ARG; }
+    if ((rc = nss_buckets(c))) return rc;
+    const int m = max_points < c->src.n ? max_points : c->src.n;
+    if (n_out) *n_out = c->src.n;
+    if (m > 0) HIPCK(c, hipMemcpyAsync(out, c->nss_bkt.p, (size_t)m * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+int icp_get_selection(icp_ctx* c, int32_t iteration, int32_t* out, int32_t max_out, int32_t* n_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (max_out < 0 || (!out && max_out > 0)) { c->err = "icp_get_selection: bad argument (max_out >= 0)"; return ICP_ERR_INVALID_ARG; }
+    if (c->sel_last.empty()) { c->err = "icp_get_selection: the last run on this context made no selection (selection = 0, or no run since the source was set)"; return ICP_ERR_INVALID_ARG; }
+    if (iteration < 0 || (size_t)iteration >= c->sel_last.size()) { c->err = "icp_get_selection: iteration out of range"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const std::pair<const int*, int>& s = c->sel_last[(size_t)iteration];
+    const int m = max_out < s.second ? max_out : s.second;
+    if (n_out) *n_out = s.second;
+    if (m > 0) HIPCK(c, hipMemcpyAsync(out, s.first, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
 }
 
 int icp_set_stage_timing(icp_ctx* c, int32_t every_nth) {

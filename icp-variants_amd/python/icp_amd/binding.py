@@ -140,6 +140,13 @@ ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY = 0, 1, 2, 3
 ROBUST_KERNELS = {"none": ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY, "tukey": ROBUST_TUKEY}
 
 
+class IcpNssOptions(C.Structure):
+    _fields_ = [("grid", C.c_int32), ("resample", C.c_int32)]
+
+
+SELECT_ALL, SELECT_RANDOM, SELECT_NORMAL_SPACE = 0, 1, 2
+
+
 class IcpColorCamera(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_int32), ("height", C.c_int32),
                 ("extrinsics", C.c_float * 16)]
@@ -172,6 +179,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
            "icp_robust_options_default", "icp_set_robust_options", "icp_get_robust_options", "icp_get_robust_stats",
+           "icp_nss_options_default", "icp_set_nss_options", "icp_get_nss_options", "icp_get_normal_buckets", "icp_get_selection",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
 
@@ -348,6 +356,34 @@ class Context:
         buf = (IcpRobustStats * max(n.value, 1))()
         self._ck(self.lib.icp_get_robust_stats(self.h, buf, C.c_int32(n.value), C.byref(n)))
         return [dict(n_entering=b.n_entering, n_kept=b.n_kept, trim_d2=b.trim_d2, sigma=b.sigma) for b in buf[:n.value]]
+
+    def set_nss_options(self, grid=5, resample=True):
+        """icp_set_nss_options: normal-space sampling (params.selection = SELECT_NORMAL_SPACE): cells per cube-face edge (3, 5 or 7) and
+        whether every iteration draws anew (True) or one draw per level is held for the run (False)."""
+        o = IcpNssOptions(int(grid), int(resample))
+        self._ck(self.lib.icp_set_nss_options(self.h, C.byref(o)))
+        return o
+
+    def nss_options(self):
+        o = IcpNssOptions()
+        self._ck(self.lib.icp_get_nss_options(self.h, C.byref(o)))
+        return o
+
+    def normal_buckets(self):
+        """icp_get_normal_buckets: the normal-space bucket of every source point, uint16 in the cloud's order (0xFFFF: none)."""
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_get_normal_buckets(self.h, None, C.c_int32(0), C.byref(n)))
+        out = np.empty(n.value, np.uint16)
+        self._ck(self.lib.icp_get_normal_buckets(self.h, _ptr(out), C.c_int32(n.value), C.byref(n)))
+        return out
+
+    def selection(self, iteration):
+        """icp_get_selection: the query set (original source indices, increasing) of one iteration of the last run with selection 1 or 2."""
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_get_selection(self.h, C.c_int32(iteration), None, C.c_int32(0), C.byref(n)))
+        out = np.empty(n.value, np.int32)
+        self._ck(self.lib.icp_get_selection(self.h, C.c_int32(iteration), _ptr(out), C.c_int32(n.value), C.byref(n)))
+        return out
 
     def push_params(self):
         self._ck(self.lib.icp_set_params(self.h, C.byref(self.params)))
@@ -649,6 +685,8 @@ class LinearICPOptimizer:
     def setGICPOptions(self, epsilon=1e-3, k=20): self.ctx.set_gicp_options(epsilon, k)         # setMetric(METRIC_GICP) selects it
     def setColoredICPOptions(self, lambda_geometric=0.968, k=20): self.ctx.set_colored_options(lambda_geometric, k)   # setMetric(METRIC_COLORED)
     def setRobustOptions(self, kernel="none", tuning=0.0, sigma=0.0, overlap=1.0): self.ctx.set_robust_options(kernel, tuning, sigma, overlap)
+
+    def setNormalSpaceOptions(self, grid=5, resample=True): self.ctx.set_nss_options(grid, resample)   # setSelectionMethod(SELECT_NORMAL_SPACE) selects it
 
     def setSelectionMethod(self, method, proba=1.0, seed=0):                                   # :58-61 (+ explicit seed)
         self.ctx.params.selection = int(method); self.ctx.params.selection_proba = float(proba); self.ctx.params.selection_seed = int(seed)

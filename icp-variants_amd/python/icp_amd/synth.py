@@ -220,3 +220,38 @@ def compact_valid(pts, nrm, rgba):
     """keepOriginalSize=false filtering of PointCloud(depth...) (PointCloud.h:148-163): drop invalid pixels."""
     ok = np.isfinite(pts).all(axis=1) & np.isfinite(nrm).all(axis=1)
     return pts[ok], nrm[ok], rgba[ok]
+
+
+def incised_plane(n_grid=160, groove_x=0.37, groove_y=0.61, width=0.02, depth=0.01, sigma=0.0005, normal_sigma=0.02,
+                  yaw_deg=1.0, shift=(0.006, -0.0036), seed=0x51AB):
+    """A unit square with two V-grooves, the scene normal-space sampling is made for: nearly every point lies on the plane z = 0 and
+    says nothing about x, y or yaw; the few points on the groove flanks pin them.  Target: the n_grid x n_grid grid (i / n_grid); source:
+    the half-cell-shifted grid, moved by yaw_deg about the square's centre plus `shift`.  Analytic normals (the deeper groove's flank where
+    they cross), Gaussian position noise sigma, normal noise normal_sigma then renormalised; float64 math rounded once to float32.
+    Returns dict(src_pts, src_nrm, tgt_pts, tgt_nrm, truth, centre): truth = the 4x4 pose that takes the source back onto the target."""
+    rng = _rng(seed)
+    hw = 0.5 * width
+
+    def surface(offset):
+        g = (np.arange(n_grid) + offset) / n_grid
+        x, y = [a.ravel() for a in np.meshgrid(g, g, indexing="xy")]
+        dx, dy = x - groove_x, y - groove_y
+        zx = np.where(np.abs(dx) < hw, -depth * (1.0 - np.abs(dx) / hw), 0.0)
+        zy = np.where(np.abs(dy) < hw, -depth * (1.0 - np.abs(dy) / hw), 0.0)
+        s = depth / hw
+        nrm = np.zeros((x.size, 3)); nrm[:, 2] = 1.0
+        on_x = (zx < 0) & (zx <= zy); on_y = (zy < 0) & ~on_x
+        nrm[on_x, 0] = -s * np.sign(dx[on_x]); nrm[on_y, 1] = -s * np.sign(dy[on_y])
+        pts = np.stack([x, y, np.minimum(zx, zy)], axis=1) + rng.normal(0.0, sigma, (x.size, 3))
+        nrm = nrm / np.linalg.norm(nrm, axis=1, keepdims=True) + rng.normal(0.0, normal_sigma, (x.size, 3))
+        return pts, nrm / np.linalg.norm(nrm, axis=1, keepdims=True)
+
+    tp, tn = surface(0.0)
+    sp, sn = surface(0.5)
+    centre = np.array([0.5, 0.5, 0.0])
+    move = np.eye(4)
+    move[:3, :3] = rot_xyz(0.0, 0.0, np.deg2rad(yaw_deg))
+    move[:3, 3] = centre - move[:3, :3] @ centre + np.array([shift[0], shift[1], 0.0])
+    sp, sn = apply_pose(move, sp, sn)
+    f = np.float32
+    return dict(src_pts=sp.astype(f), src_nrm=sn.astype(f), tgt_pts=tp.astype(f), tgt_nrm=tn.astype(f), truth=np.linalg.inv(move), centre=centre)

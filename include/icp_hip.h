@@ -67,7 +67,8 @@ typedef struct icp_params {
     float   fx, fy, cx, cy;  /* setCameraParamsMatchingMethod (ICPOptimizer.h:80-82) */
     int32_t width, height;
     int32_t knn_backend;     /* ICP_KNN_* (extension; the reference's own index is an approximate, randomised FLANN kd-tree) */
-    int32_t selection;       /* setSelectionMethod: 0 SELECT_ALL, 1 RANDOM_SAMPLING (selection.h:9)                          */
+    int32_t selection;       /* setSelectionMethod: 0 SELECT_ALL, 1 RANDOM_SAMPLING (selection.h:9); 2 normal-space sampling
+                                (ICP_SELECT_*, an extension: see icp_nss_options)                                            */
     float   selection_proba; /* Bernoulli probability per point and per iteration (selection.h:88-106)                     */
     uint32_t selection_seed; /* the reference seeds std::mt19937 from random_device (selection.h:76-79: not reproducible);
                                 here a counter-based hash of (seed, iteration, point index) decides -- see icp_select_hash */
@@ -178,8 +179,8 @@ int icp_get_timing(const icp_ctx* ctx, icp_timing* out);
  * inlier when its squared distance is <= max_distance -- exactly when icp_match would return idx >= 0 for it; n_inliers, fitness =
  * n_inliers / finite source points, inlier_rmse = sqrt(sum d^2 / n_inliers) (fp64 sum in a fixed order), -1 without inliers.
  * *best_out (optional): the start with the most inliers, ties to the smaller inlier_rmse, then to the lower index.
- * Supported: k-NN matching on the LBVH backend (3-D or colour 6-D), every metric, weighting, rejection, multires, SELECT_ALL and
- * RANDOM_SAMPLING; 1 <= n_starts <= 256.  NOT supported (ICP_ERR_INVALID_ARG, see icp_last_error): projective matching, the
+ * Supported: k-NN matching on the LBVH backend (3-D or colour 6-D), every metric, weighting, rejection, multires and selection (the draws
+ * of RANDOM_SAMPLING and of normal-space sampling are shared between the starts); 1 <= n_starts <= 256.  NOT supported (ICP_ERR_INVALID_ARG, see icp_last_error): projective matching, the
  * brute-force backend, record_rmse != 0 and the non-linear optimiser.  stats may be NULL; n_iterations_run (optional) receives the
  * iterations of the schedule, the same for every start. */
 typedef struct icp_start_result {
@@ -314,6 +315,48 @@ int icp_get_robust_options(const icp_ctx* ctx, icp_robust_options* opt);
  * tracked frame's run; icp_batch_run: each context's own last pair); none when robust mode was off for that call.  Iterations with no
  * work: {0, 0, -1, -1}.  out[0 .. min(max_out, count)), *count_out = the number of records. */
 int icp_get_robust_stats(const icp_ctx* ctx, icp_robust_stats* out, int32_t max_out, int32_t* count_out);
+
+/* -------- Normal-space sampling (extension: the reference has SELECT_ALL and RANDOM_SAMPLING only), params.selection = 2 --------
+ * Rusinkiewicz and Levoy, "Efficient Variants of the ICP Algorithm" (3DIM 2001): the source points are bucketed by normal direction and
+ * sampled uniformly across the buckets, so that the few points on small features survive subsampling beside the big planes.
+ * selection_proba and selection_seed keep their meaning; grid and resample are per context (icp_nss_options).
+ * Bucket of a source point, from its stored, untransformed fp32 normal (x, y, z), every operation in fp32 with IEEE division:
+ *   none when a component of the point or of the normal is non-finite or m = max(|x|, |y|, |z|) is 0; else a = the lowest axis with
+ *   |n_a| == m, face = 2a + (n_a < 0), (u, v) = the other two components in axis order, each divided by m,
+ *   cell(t) = min(grid - 1, (int)floorf((t + 1.0f) * (0.5f * grid))), bucket = face * grid^2 + cell(v) * grid + cell(u).
+ *   (grid is odd so that an axis-aligned normal falls in the middle of a cell, not on a corner.)
+ * Draw of iteration i: the base set is RANDOM_SAMPLING's (the iteration's multires level list, or all points for factor 0); its points with
+ *   a bucket are the m candidates, cnt_b of them in bucket b.  M = clamp(ceil((double)selection_proba * m), 0, m): proba <= 0 gives an empty
+ *   iteration (ICP_ERR_NO_CORRESPONDENCES, as an empty random draw); proba >= 1 gives all CANDIDATES -- unlike RANDOM_SAMPLING's take-all,
+ *   which also keeps the points without a usable normal.  Quotas by water-filling: c = the smallest integer with sum_b min(cnt_b, c) >= M,
+ *   q_b = min(cnt_b, c); the excess E = sum q_b - M is taken, one each, from the E buckets with cnt_b >= c whose key
+ *   icp_select_hash(seed, i, 0x80000000u | b) is smallest.  Bucket b contributes its q_b candidates with the smallest
+ *   icp_select_hash(seed, i, original index).  For a fixed (seed, iteration) that hash is a bijection of the index, so keys never tie and
+ *   exactly M points are selected.  The list is in increasing original index.
+ * resample = 0 (held draws): iteration i uses the draw of the first iteration of the schedule with the same decimation factor, whose index
+ *   is the hash's iteration word.  A held draw is a level of its own: on the LBVH backend it is Morton-sorted like a multires level, and the
+ *   run takes the seeded (and, for point-to-plane, merged) form a SELECT_ALL run on a cloud of that size takes.
+ * Applies wherever RANDOM_SAMPLING does: icp_run, icp_run_multistart (draws shared between the starts), icp_batch_run,
+ * icp_track_depth_frames, with every matcher, metric, weighting, rejection, multires, robust mode and the non-linear optimiser;
+ * icp_iterate, icp_correspond, icp_match and icp_match_seeded ignore `selection`.  A source without normals: ICP_ERR_INVALID_ARG at loop
+ * start (see icp_last_error). */
+enum { ICP_SELECT_ALL = 0, ICP_SELECT_RANDOM = 1, ICP_SELECT_NORMAL_SPACE = 2 };
+typedef struct icp_nss_options {
+    int32_t grid;      /* cells per cube-face edge, {3, 5, 7}, default 5 -> 6*grid^2 buckets (54 / 150 / 294) */
+    int32_t resample;  /* 1 (default): a new draw every iteration, like RANDOM_SAMPLING; 0: one draw per level, held for the run */
+} icp_nss_options;
+int icp_nss_options_default(icp_nss_options* opt);
+/* Validation: grid in {3, 5, 7}, resample in {0, 1}; else ICP_ERR_INVALID_ARG (reason in icp_last_error). */
+int icp_set_nss_options(icp_ctx* ctx, const icp_nss_options* opt);   /* NULL = defaults */
+int icp_get_nss_options(const icp_ctx* ctx, icp_nss_options* opt);
+/* The bucket of every source point, original order, 0xFFFF = none; computed on demand, cached per source and grid.
+   out[0 .. min(n, max_points)) is written, *n_out (optional) = n. */
+int icp_get_normal_buckets(icp_ctx* ctx, uint16_t* out, int32_t max_points, int32_t* n_out);
+/* The query set (original source indices, increasing) of iteration `iteration` of the last icp_run / icp_run_multistart / the context's
+   last batch pair / last tracked frame, for selection 1 and 2; ICP_ERR_INVALID_ARG when that run had selection 0 or iteration is out of
+   range.  Valid until the next call on the context that runs a loop or replaces the source.  out[0 .. min(count, max_out)) is written,
+   *n_out (optional) = count. */
+int icp_get_selection(icp_ctx* ctx, int32_t iteration, int32_t* out, int32_t max_out, int32_t* n_out);
 
 /* -------- Colored ICP (extension: the reference has no counterpart), params.metric = ICP_METRIC_COLORED --------
  * Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017): point-to-plane plus a photometric term along the

@@ -101,7 +101,7 @@ struct ConvergenceMeasure {                         // ConvergenceMeasure.h:69-7
     void recordAlignmentError(const Matrix4f& pose) { recordedPoses.push_back(pose); }
 };
 
-enum selection_methods { SELECT_ALL = 0, RANDOM_SAMPLING };                                      // selection.h:9
+enum selection_methods { SELECT_ALL = 0, RANDOM_SAMPLING, NORMAL_SPACE_SAMPLING };               // selection.h:9 (+ ICP_SELECT_NORMAL_SPACE, an extension)
 enum weighting_methods { CONSTANT_WEIGHTING = 0, DISTANCES_WEIGHTING, NORMALS_WEIGHTING, COLORS_WEIGHTING };   // weighting.h:8
 
 class ICPOptimizer {                                // ICPOptimizer.h:27-175 (setter surface + protected state)
@@ -229,6 +229,13 @@ public:
         if (!context()) return ICP_ERR_NO_DEVICE;
         icp_robust_options o; o.kernel = (int32_t)kernel; o.tuning = tuning; o.sigma = sigma; o.overlap = overlap;
         return icp_set_robust_options(context(), &o);
+    }
+    // Normal-space sampling (setSelectionMethod(NORMAL_SPACE_SAMPLING, proba), an extension): cells per cube-face edge and whether every
+    // iteration draws anew; icp_set_nss_options.  Returns its status (ICP_ERR_INVALID_ARG: grid not in {3, 5, 7}).
+    int setNormalSpaceOptions(int grid, bool resample) {
+        if (!context()) return ICP_ERR_NO_DEVICE;
+        icp_nss_options o; o.grid = (int32_t)grid; o.resample = resample ? 1 : 0;
+        return icp_set_nss_options(context(), &o);
     }
     // LinearICPOptimizer::estimatePose, ICPOptimizer.h:493-663
     void estimatePose(const PointCloud& source, const PointCloud& target, Matrix4f& initialPose, bool calculateRMSE = true) override {
