@@ -507,6 +507,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_reduce_solve(const SolveParam
 //   separate k_reduce_solve launches.  The same happens (PoseState::fault = 2 in the published slot, the rest of the chain passes it on
 //   without touching anything) when the 6 x 6 system fails the rank guard of p2plane_lanes_core, i.e. when the solve needs the eigen-decomposition that
 //   only k_reduce_solve carries (99 VGPRs: it must not ride in the matcher, which is held to 80).
+//   The same path carries a run that has converged (icp_set_convergence_options, dev_converge.hpp): block 0 publishes the final pose with
+//   PoseState::fault = SLOT_STOPPED, the matcher blocks of the launches left leave at once, their reducers pass the slot on to the closing
+//   launch's copy, and the host reads it as the run's result.
 // Thousands of waves polling ONE 128-byte line is a hot spot, not a broadcast: sc1 loads are served behind the L2, one memory channel
 // hands out a line every ~2 ns, so a round of 5 790 polls takes 11 us (measured: 24-28 us per converged iteration with a single slot,
 // against 14 + 7 with one launch per iteration).  Every slot therefore exists POSE_REPLICAS times on lines far enough apart to land on
@@ -545,6 +548,7 @@ struct RingParams {
     PoseState* final_out;                          // the closing launch of a run: the final pose state also goes here (beside the records: ONE copy back); else nullptr
     int* run_fault;                                // raised by any waiter that ran out of polls
     int n_red;                                     // reducer blocks in front of this grid: 0 (first launch of a run) or NSUM_USED
+    ConvergeParams cv;                             // stopping on a converged pose (dev_converge.hpp), for the reduced iteration; cv.on == 0: off
 };
 __device__ __forceinline__ unsigned long long granule_of(unsigned int lo, unsigned int hi) {
     const unsigned long long g = ((unsigned long long)hi << 32) | lo;
@@ -573,7 +577,7 @@ __device__ __forceinline__ void ring_reduce_solve(const RingParams& rp) {
     __shared__ int give_up;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, a = blockIdx.x;
     RING_STAMP(a, 0);
-    if (a == 0 && rp.ps_in->fault) {                      // the chain was cut further up: pass it on, touch nothing else
+    if (a == 0 && rp.ps_in->fault) {                      // the chain was cut further up, or the run has stopped (SLOT_STOPPED: the slot is the final pose): pass it on, touch nothing else
         { const unsigned int* src = (const unsigned int*)rp.ps_in; for (int q = tid; q < 16 * POSE_REPLICAS; q += RING_THREADS) __hip_atomic_store((unsigned long long*)loop_slot(rp.ps_out, 0, q >> 4) + (q & 15), granule_of(src[2 * (q & 15)], src[2 * (q & 15) + 1]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (rp.final_out && tid < 32) ((unsigned int*)rp.final_out)[tid] = src[tid]; }
         return;
@@ -635,6 +639,10 @@ __device__ __forceinline__ void ring_reduce_solve(const RingParams& rp) {
     else if (n > 0) { npose = p2plane_lanes_core(tot + SUM_M, pin->pose); if (!npose) fault = 2; }      // (uniform: every thread of the block takes the same branch)
     else status = ICP_ERR_NO_CORRESPONDENCES;              // the pose stays (ICPOptimizer.h:668,680: the reference would hang in ASSERT)
     RING_STAMP(NSUM_USED, 1);
+    int code = fault;                                      // the slot's last word
+    if (rp.cv.on && !fault) {                              // (uniform; off: this one branch)
+        if (tid < WAVE && converge_step(rp.cv, npose ? npose : pin->pose, pin->pose, status == ICP_OK, tid)) code = SLOT_STOPPED;      // (code: wave 0 only, which tid 0 below is part of)
+    }
     // the slot: pose, normal matrix, means, fault -- assembled in LDS, published as 16 granules
     if (tid < 16) slot_words[tid] = __float_as_uint(npose ? npose[tid] : pin->pose[tid]);
     if (tid >= 32 && tid < 41) slot_words[16 + tid - 32] = __float_as_uint(npose ? normal_matrix_entry(npose, tid - 32) : pin->nmat[tid - 32]);      // nine lanes, one quotient each
@@ -642,7 +650,7 @@ __device__ __forceinline__ void ring_reduce_solve(const RingParams& rp) {
         const int k = tid - 64;
         slot_words[25 + k] = __float_as_uint(n > 0 ? (float)(tot[(k < 3 ? SUM_S : SUM_D - 3) + k] / n) : 0.f);
     }
-    if (tid == 70) slot_words[31] = (unsigned int)fault;
+    if (tid == 0) slot_words[31] = (unsigned int)code;
     __syncthreads();
     for (int q = tid; q < 16 * POSE_REPLICAS; q += RING_THREADS)      // every replica of the slot, 16 granules each
         __hip_atomic_store((unsigned long long*)loop_slot(rp.ps_out, 0, q >> 4) + (q & 15), granule_of(slot_words[2 * (q & 15)], slot_words[2 * (q & 15) + 1]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -75,6 +75,9 @@ struct icp_ctx {
     icp_robust_options rob_opt = {ICP_ROBUST_NONE, 0.f, 0.f, 1.f};   // icp_set_robust_options
     DevBuf rob_keys, rob_state, rob_stats;      // trimmed / robust mode (dev_robust.hpp): r^2 keys per query, the chain's state, per-iteration records
     std::vector<icp_robust_stats> rob_last;      // the records of the last call (icp_get_robust_stats)
+    icp_convergence_options cvg_opt = {0, 1e-6f, 1e-6f, 1, 1};      // icp_set_convergence_options: stopping on a converged pose
+    icp_convergence_result cvg_last = {0, 0, 0, -1.f, -1.f};        // the last run (icp_get_convergence) ...
+    std::vector<icp_convergence_step> cvg_trace;                    // ... and its trace, one step per iteration that ran (icp_get_convergence_trace)
     icp_params prm;
     Cloud tgt, src, qry;                 // qry: scratch cloud of icp_query_matches
     Cloud nrm_cloud; Bvh nrm_bvh;        // scratch of icp_estimate_normals

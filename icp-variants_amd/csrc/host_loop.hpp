@@ -207,10 +207,11 @@ int make_plan(icp_ctx* c, bool single, RunPlan& pl) {
 
 // Finishes the host copy hs of a run's records (every record of an iteration with work was written in full on the device): an empty
 // iteration carries the pose before it (pose_in for iteration 0), rmse / benchmark_error are -1 where not recorded.  Copies up to max_out
-// records to out and returns the first failing status.
-int finish_records(const RunPlan& pl, icp_iter_stats* hs, const float* pose_in, bool rmse, bool fontana, icp_iter_stats* out, int max_out) {
+// of the n_run records (all of the plan's, or those up to the iteration a converged run stopped after) to out and returns their first
+// failing status.
+int finish_records(const RunPlan& pl, int n_run, icp_iter_stats* hs, const float* pose_in, bool rmse, bool fontana, icp_iter_stats* out, int max_out) {
     int status = ICP_OK;
-    for (int i = 0; i < pl.iters(); i++) {
+    for (int i = 0; i < n_run; i++) {
         const bool empty = pl.ns[i] <= 0;
         if (empty) { hs[i].n_src = 0; hs[i].n_valid = 0; hs[i].status = ICP_ERR_NO_CORRESPONDENCES; memcpy(hs[i].pose, i ? hs[i - 1].pose : pose_in, 64); }
         if (empty || !rmse) hs[i].rmse = -1.f;
@@ -255,12 +256,34 @@ RingParams ring_params(const icp_ctx* c, const Ring& r, int j, int n_prev, PoseS
 // pin_pose .. + 128 .. + 192 (records | final pose state | fault word of the merged form).  Stage timing (TimeMeasure.h:20-26): a HIP event
 // costs ~4 us of stream time, so mode N > 1 brackets only every Nth iteration (`sampled`, offset rotating from run to run) and scales the
 // sums.  Event slots: 4 per iteration + run start / run end; each form fills ev[i] of a sampled iteration with the ones it records.
+// Stopping on a converged pose (cvg, dev_converge.hpp) adds, at the same offsets behind the records on the device and in the staging:
+// + 144 the merged form's control words (the spare words beside its fault word), + 256 the separate form's state block (control words |
+// search pose | final pose state), + 512 the trace; eligible[i] = the host's half of iteration i's eligibility, from the plan's factors.
 struct IterEvents { hipEvent_t start = nullptr, matched = nullptr, posted = nullptr, end = nullptr; };   // posted / end: nullptr = the form has no such stage to bracket
-struct LoopRun { RunPlan pl; bool lm, robust, rmse, fontana; size_t pin_stats = 256, pin_pose, pin_lm; std::vector<char> sampled; std::vector<IterEvents> ev; };
+struct LoopRun { RunPlan pl; bool lm, robust, rmse, fontana, cvg; size_t pin_stats = 256, pin_pose, pin_lm; std::vector<char> sampled, eligible; std::vector<IterEvents> ev; int n_enqueued = 0; };
+constexpr size_t CVG_MERGED_WORDS = 128 + 16, CVG_STATE = 256, CVG_TRACE = 512;      // offsets from the final pose state
+// The separate form enqueues a run that may stop in chunks of this many iterations and reads the stop word between them: the chunk size
+// trades host round trips against iterations enqueued in vain.  Time only, never results.  2: the fastest of {1, 2, 4, 8} on the bench
+// pair with GICP (1.17 / 1.16 / 1.19 / 1.17 ms for a run that stops after 13 of 50 iterations; tools/time_converge.py).
+#ifndef ICP_CONVERGE_CHUNK
+#define ICP_CONVERGE_CHUNK 2
+#endif
+constexpr int CONVERGE_CHUNK = ICP_CONVERGE_CHUNK;
+ConvergeParams converge_params(const icp_ctx* c, const LoopRun& r, int i, size_t words_at) {
+    ConvergeParams cp; memset(&cp, 0, sizeof(cp));
+    if (!r.cvg) return cp;
+    const icp_convergence_options& o = c->cvg_opt;
+    char* base = c->stats.as<char>() + (r.pin_pose - r.pin_stats);
+    cp.on = 1; cp.eligible = r.eligible[(size_t)i]; cp.index = i; cp.min_iterations = o.min_iterations; cp.patience = o.patience;
+    cp.rotation_eps = o.rotation_eps; cp.translation_eps = o.translation_eps;
+    cp.trace = (icp_convergence_step*)(base + CVG_TRACE); cp.words = (int*)(base + words_at);
+    return cp;
+}
 hipEvent_t loop_event(const icp_ctx* c, int i, int k) { return c->events[(size_t)2 + 4 * i + k]; }
 
 // The merged form: point-to-plane through the fused BVH matcher on sorted levels, nothing else on the stream between two iterations.
-// Launch i = [reducer of iteration i - 1 | matcher of iteration i]; one reducer-only launch closes the run.  Pose slots and totals rows
+// Launch i = [reducer of iteration i - 1 | matcher of iteration i]; one reducer-only launch closes the run.  A run that stops on a converged
+// pose (dev_converge.hpp) is still enqueued whole: the launches behind the stop find a stopped slot and drain at launch cost.  Pose slots and totals rows
 // are written once per run; both rings are reset here, so nothing survives an aborted run.  Back comes ONE block: records | final pose
 // state | fault word.  Events: an iteration is ONE launch, whose own start / stop times go into slots 0 / 1 (hipExtLaunchKernel: taken
 // from the dispatch itself, no bracket on the stream); a "solve" exists only for the last iteration: the closing launch, up to slot 3.
@@ -275,7 +298,7 @@ int enqueue_merged(icp_ctx* c, LoopRun& r) {
     hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, c->ps.as<PoseState>(), ring.slots, iters + 1, ring.trows, iters * NSUM, ring.run_fault, 16);
     auto reducer = [&](int i) {                          // of iteration i - 1, riding in launch i (i = iters: the closing launch)
         RingParams rp = ring_params(c, ring, i, i > 0 ? pl.ns[i - 1] : 0, loop_slot(ring.slots, i, 0));
-        if (i > 0) rp.stats = c->stats.as<icp_iter_stats>() + (i - 1);
+        if (i > 0) { rp.stats = c->stats.as<icp_iter_stats>() + (i - 1); rp.cv = converge_params(c, r, i - 1, CVG_MERGED_WORDS); }
         if (i == iters) rp.final_out = (PoseState*)(c->stats.as<char>() + stats_pad);
         return rp;
     };
@@ -292,7 +315,8 @@ int enqueue_merged(icp_ctx* c, LoopRun& r) {
     HIPCK(c, hipGetLastError());
     if (r.sampled[iters - 1]) { r.ev[iters - 1].end = loop_event(c, iters - 1, 3); HIPCK(c, hipEventRecord(r.ev[iters - 1].end, c->stream)); }
     HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_stats, c->stats.p, stats_pad + 192, hipMemcpyDeviceToHost, c->stream));
+    r.n_enqueued = iters;
+    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_stats, c->stats.p, stats_pad + (r.cvg ? CVG_TRACE + (size_t)iters * sizeof(icp_convergence_step) : 192), hipMemcpyDeviceToHost, c->stream));
     return ICP_OK;
 }
 
@@ -300,13 +324,28 @@ int enqueue_merged(icp_ctx* c, LoopRun& r) {
 // the post stage and the reduce / solve -- or the robust chain in front, or the non-linear optimiser behind -- and the convergence
 // measures.  Back come the records, the pose state and the LM records.  Events: slot 0 in front of the matcher, 1 behind it, 2 behind a
 // post stage of its own (none behind a fused matcher), 3 at the iteration's end; the matcher's time counts from the previous iteration's
-// slot 3 when that one was sampled.
+// slot 3 when that one was sampled.  Stopping on a converged pose: k_converge_step closes every iteration, and the iterations go out in
+// chunks of CONVERGE_CHUNK with one 4-byte read of the stop word between two chunks; with the option off the sequence is unchanged.
 int enqueue_separate(icp_ctx* c, LoopRun& r) {
     const icp_params& p = c->prm; const RunPlan& pl = r.pl;
     const int iters = pl.iters(); int rc;
     if ((rc = rearm_handover(c))) return rc;
+    const size_t stats_pad = r.pin_pose - r.pin_stats;
+    if (r.cvg) {
+        hipLaunchKernelGGL(k_converge_init, dim3(1), dim3(64), 0, c->stream, c->ps.as<PoseState>(), (int*)(c->stats.as<char>() + stats_pad + CVG_STATE));
+        HIPCK(c, hipGetLastError());
+    }
     HIPCK(c, hipEventRecord(c->events[0], c->stream));
+    int n_enq = 0;
     for (int i = 0; i < iters; i++) {
+        if (r.cvg && i > 0 && i % CONVERGE_CHUNK == 0) {      // between two chunks: has the run stopped?
+            const size_t at = stats_pad + CVG_STATE + CONV_STOPPED * 4;
+            const int* stop = (const int*)((char*)c->pinned + r.pin_stats + at);
+            HIPCK(c, hipMemcpyAsync((void*)stop, c->stats.as<char>() + at, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCK(c, hipStreamSynchronize(c->stream));
+            if (*stop) break;
+        }
+        n_enq = i + 1;
         icp_iter_stats* d_st = c->stats.as<icp_iter_stats>() + i;
         const bool ev = r.sampled[i] != 0;
         if (ev) {
@@ -327,12 +366,18 @@ int enqueue_separate(icp_ctx* c, LoopRun& r) {
         } else if (ev) HIPCK(c, hipEventRecord(r.ev[i].matched, c->stream));
         if (r.rmse && (rc = enqueue_rmse(c, &d_st->rmse))) return rc;
         if (r.fontana && (rc = enqueue_fontana(c, &d_st->benchmark_error))) return rc;
+        if (r.cvg) {
+            hipLaunchKernelGGL(k_converge_step, dim3(1), dim3(64), 0, c->stream, converge_params(c, r, i, CVG_STATE), c->ps.as<PoseState>(), pl.ns[i] > 0 ? d_st : nullptr);
+            HIPCK(c, hipGetLastError());
+        }
         if (ev) HIPCK(c, hipEventRecord(r.ev[i].end, c->stream));
     }
+    r.n_enqueued = n_enq;
     HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_stats, c->stats.p, (size_t)iters * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_stats, c->stats.p, (size_t)n_enq * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_pose, c->ps.p, sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));
-    if (r.lm) HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_lm, c->lm_sums.p, (size_t)iters * sizeof(icp_lm_summary), hipMemcpyDeviceToHost, c->stream));
+    if (r.cvg) HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_pose + CVG_STATE, c->stats.as<char>() + stats_pad + CVG_STATE, CVG_TRACE - CVG_STATE + (size_t)n_enq * sizeof(icp_convergence_step), hipMemcpyDeviceToHost, c->stream));
+    if (r.lm) HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_lm, c->lm_sums.p, (size_t)n_enq * sizeof(icp_lm_summary), hipMemcpyDeviceToHost, c->stream));
     return ICP_OK;
 }
 
@@ -353,15 +398,20 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     const bool lm = r.lm = c->lm_on;      // the non-linear optimiser: the separate form, its records kept for k_lm_eval
     const bool robust = r.robust = robust_on(c);      // trimmed / robust mode: the separate form with the stand-alone matcher, as GICP runs
     c->lm_last.clear(); c->rob_last.clear();
+    const bool cvg = r.cvg = !single && c->cvg_opt.enabled != 0;      // icp_iterate ignores the option and leaves the last run's result alone
+    if (!single) { c->cvg_trace.clear(); c->cvg_last = icp_convergence_result{0, 0, iters, -1.f, -1.f}; }
     if (robust && lm) { c->err = "the non-linear optimiser does not support robust mode (icp_set_robust_options)"; return ICP_ERR_INVALID_ARG; }
     if (iters == 0) return guard.done();
     if (robust && (rc = robust_prepare(c, iters))) return rc;
-    r.pin_pose = r.pin_stats + (((size_t)iters * sizeof(icp_iter_stats) + 255) & ~(size_t)255); r.pin_lm = r.pin_pose + 512;
-    if ((rc = ensure_pinned(c, lm ? r.pin_lm + (size_t)iters * sizeof(icp_lm_summary) : r.pin_pose + 512))) return rc;
+    const size_t cvg_bytes = cvg ? ((size_t)iters * sizeof(icp_convergence_step) + 255) & ~(size_t)255 : 0;
+    r.pin_pose = r.pin_stats + (((size_t)iters * sizeof(icp_iter_stats) + 255) & ~(size_t)255); r.pin_lm = r.pin_pose + 512 + cvg_bytes;
+    if ((rc = ensure_pinned(c, lm ? r.pin_lm + (size_t)iters * sizeof(icp_lm_summary) : r.pin_lm))) return rc;
     if (lm && (rc = ensure(c, c->lm_sums, (size_t)iters * sizeof(icp_lm_summary)))) return rc;
     float pose_in[16]; memcpy(pose_in, pose_inout, 64);        // the record of an empty iteration 0 carries the incoming pose
     if ((rc = write_pose(c, pose_inout))) return rc;
-    if ((rc = ensure(c, c->stats, r.pin_pose - r.pin_stats + 192))) return rc;
+    if ((rc = ensure(c, c->stats, r.pin_pose - r.pin_stats + (cvg ? CVG_TRACE + cvg_bytes : 192)))) return rc;
+    r.eligible.assign((size_t)iters, 0);
+    for (int i = 0; i < iters; i++) r.eligible[(size_t)i] = pl.factors[i] == pl.factors[iters - 1] && (i == 0 || pl.factors[i] == pl.factors[i - 1]);
     if ((rc = ensure_events(c, (size_t)iters * 4 + 2))) return rc;
     const bool rmse = r.rmse = (p.record_rmse & 1) && c->conv_n > 0;
     const bool fontana = r.fontana = (p.record_rmse & 2) && c->conv_n > 0;
@@ -381,7 +431,7 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     if (merged) {
         c->merged_runs++;
         const int rf = *(const int*)((char*)c->pinned + r.pin_pose + 128);
-        if (hp->fault || rf) {
+        if ((hp->fault && hp->fault != SLOT_STOPPED) || rf) {      // (a stopped slot is the run's result, not a fault)
             // the 6 x 6 system failed the rank guard (the eigen-decomposition lives in k_reduce_solve only), or a bounded wait ran out:
             // the same run again, from the incoming pose, in the separate form
             c->merged_fallbacks++;
@@ -391,20 +441,36 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
             return run_loop(c, pose_inout, stats, max_stats, n_run, single, false);
         }
     }
+    int n_done = iters; bool stopped = false;
+    if (cvg) {
+        const int* cw = (const int*)((char*)c->pinned + r.pin_pose + (merged ? CVG_MERGED_WORDS : CVG_STATE));
+        if (cw[CONV_STOPPED]) {
+            stopped = true; n_done = cw[CONV_RUN];
+            if (n_done < 1 || n_done > r.n_enqueued) { c->err = "the device reports a stop outside the iterations that were enqueued"; return ICP_ERR_HIP; }
+            if (!merged) hp = (const PoseState*)(cw + CONV_FINAL);      // c->ps has moved on with the iterations enqueued behind the stop
+        }
+    }
     memcpy(pose_inout, hp->pose, 64);
-    if (hp->fault) { c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
+    if (!merged && hp->fault) { c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
     if (lm) {
-        c->lm_last.resize((size_t)iters);
-        memcpy(c->lm_last.data(), (char*)c->pinned + r.pin_lm, (size_t)iters * sizeof(icp_lm_summary));
-        for (int i = 0; i < iters; i++)
+        c->lm_last.resize((size_t)n_done);
+        memcpy(c->lm_last.data(), (char*)c->pinned + r.pin_lm, (size_t)n_done * sizeof(icp_lm_summary));
+        for (int i = 0; i < n_done; i++)
             if (pl.ns[i] <= 0) { memset(&c->lm_last[(size_t)i], 0, sizeof(icp_lm_summary)); c->lm_last[(size_t)i].termination = ICP_LM_NO_RESIDUALS; }
     }
-    const int status = finish_records(pl, (icp_iter_stats*)((char*)c->pinned + r.pin_stats), pose_in, rmse, fontana, stats, max_stats);
-    if (n_run) *n_run = iters;
-    icp_timing& t = c->timing; memset(&t, 0, sizeof(t)); t.iterations = iters;
-    c->it_match_ms.assign((size_t)iters, -1.f); c->it_post_ms.assign((size_t)iters, -1.f); c->it_solve_ms.assign((size_t)iters, -1.f);
+    if (robust) c->rob_last.resize((size_t)n_done);
+    const int status = finish_records(pl, n_done, (icp_iter_stats*)((char*)c->pinned + r.pin_stats), pose_in, rmse, fontana, stats, max_stats);
+    if (n_run) *n_run = n_done;
+    if (!single) { c->cvg_last.converged = stopped; c->cvg_last.iterations_run = n_done; }
+    if (cvg) {
+        const icp_convergence_step* tr = (const icp_convergence_step*)((char*)c->pinned + r.pin_pose + CVG_TRACE);
+        c->cvg_trace.assign(tr, tr + n_done);
+        c->cvg_last.rotation = tr[n_done - 1].rotation; c->cvg_last.translation = tr[n_done - 1].translation;
+    }
+    icp_timing& t = c->timing; memset(&t, 0, sizeof(t)); t.iterations = n_done;
+    c->it_match_ms.assign((size_t)n_done, -1.f); c->it_post_ms.assign((size_t)n_done, -1.f); c->it_solve_ms.assign((size_t)n_done, -1.f);
     double ev_match = 0, ev_post = 0, ev_solve = 0; int n_ev = 0;
-    for (int i = 0; i < iters; i++) {
+    for (int i = 0; i < n_done; i++) {
         if (!r.sampled[i]) continue;
         n_ev++;
         const IterEvents& e = r.ev[i];
@@ -417,7 +483,7 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
         if (c->trace) fprintf(stderr, "[icp_hip] it %2d  n %d  match %.4f  post %.4f  solve %.4f ms\n", i, pl.ns[i], a, b, d);
     }
     if (n_ev > 0) {                                       // sampled: scale to all the iterations
-        const double f = (double)iters / n_ev;
+        const double f = (double)n_done / n_ev;
         t.match_ms += ev_match * f; t.weight_reject_build_ms += ev_post * f; t.solve_ms += ev_solve * f;
     }
     t.sampled_iterations = n_ev;

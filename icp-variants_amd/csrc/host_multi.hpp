@@ -18,6 +18,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
     if (c->prm.metric == ICP_METRIC_GICP) { c->err = "icp_run_multistart: GICP is not supported"; return ICP_ERR_INVALID_ARG; }
     if (c->prm.metric == ICP_METRIC_COLORED) { c->err = "icp_run_multistart: colored ICP is not supported"; return ICP_ERR_INVALID_ARG; }
     if (robust_on(c)) { c->err = "icp_run_multistart: robust mode (icp_set_robust_options) is not supported"; return ICP_ERR_INVALID_ARG; }
+    if (c->cvg_opt.enabled) { c->err = "icp_run_multistart: stopping on a converged pose (icp_set_convergence_options) is not supported: the starts share their launches"; return ICP_ERR_INVALID_ARG; }
     int rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
@@ -122,7 +123,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
     int best = 0;
     for (int s = 0; s < K; s++) {
         icp_iter_stats* hs = hrec + (size_t)s * ms.stats;
-        const int status = finish_records(pl, hs, initial_poses + (size_t)16 * s, false, false, stats ? stats + (size_t)s * max_stats : nullptr, max_stats);
+        const int status = finish_records(pl, iters, hs, initial_poses + (size_t)16 * s, false, false, stats ? stats + (size_t)s * max_stats : nullptr, max_stats);
         results[s] = hres[s];
         results[s].status = status;
         const icp_start_result& a = results[s], &b = results[best];

@@ -6,7 +6,7 @@
 // (oracle/icp_oracle.cpp), so match indices / distances / weights are bit-identical to it.
 // fp32 sqrt and divide are correctly rounded (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt).
 //
-// Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_solve.hpp,
+// Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_converge.hpp, dev_solve.hpp,
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp
 // (included below, in this order, inside namespace icpdev).
 //
@@ -25,6 +25,8 @@
 //   k_sym_accumulate    second pass of the symmetric objective with the means (ICPOptimizer.h:797-853)
 //   k_reduce_solve      fixed-order reduction of block partials + fp64 solve + pose composition
 //                       (ICPOptimizer.h:614-620,753-781,855-897; ProcrustesAligner.h:56-66)
+//   k_converge_step     stopping on a converged pose (icp_set_convergence_options): the pose increment of an iteration against the
+//                       bounds, the streak and the stop word, for the loop forms that launch reduce / solve on their own (dev_converge.hpp)
 //   k_rmse_partial      ConvergenceMeasure::rmseAlignmentError (ConvergenceMeasure.h:50-66)
 //   k_depth_count /     PointCloud(depthMap, colorFrame, ...) (PointCloud.h:78-165): back-projection, normals, stride and filter of a
 //   k_depth_scatter     depth frame as a stable two-pass compaction straight into a context cloud (dev_depth.hpp)
@@ -56,6 +58,7 @@ namespace icpdev {
 #include "dev_normals.hpp"
 #include "dev_projective.hpp"
 #include "dev_post.hpp"
+#include "dev_converge.hpp"
 #include "dev_solve.hpp"
 #include "dev_fused.hpp"
 #include "dev_measures.hpp"

@@ -224,6 +224,32 @@ int icp_get_robust_stats(const icp_ctx* c, icp_robust_stats* out, int32_t max_ou
     return ICP_OK;
 }
 
+int icp_convergence_options_default(icp_convergence_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    o->enabled = 0; o->rotation_eps = 1e-6f; o->translation_eps = 1e-6f; o->min_iterations = 1; o->patience = 1;
+    return ICP_OK;
+}
+int icp_set_convergence_options(icp_ctx* c, const icp_convergence_options* o) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    icp_convergence_options v;
+    if (o) v = *o; else icp_convergence_options_default(&v);
+    if (v.enabled != 0 && v.enabled != 1) { c->err = "icp_set_convergence_options: enabled must be 0 or 1"; return ICP_ERR_INVALID_ARG; }
+    if (!(std::isfinite(v.rotation_eps) && v.rotation_eps > 0.f) || !(std::isfinite(v.translation_eps) && v.translation_eps > 0.f)) { c->err = "icp_set_convergence_options: rotation_eps and translation_eps must be finite and > 0"; return ICP_ERR_INVALID_ARG; }
+    if (v.min_iterations < 1) { c->err = "icp_set_convergence_options: need min_iterations >= 1"; return ICP_ERR_INVALID_ARG; }
+    if (v.patience < 1 || v.patience > 8) { c->err = "icp_set_convergence_options: need 1 <= patience <= 8"; return ICP_ERR_INVALID_ARG; }
+    c->cvg_opt = v;
+    return ICP_OK;
+}
+int icp_get_convergence_options(const icp_ctx* c, icp_convergence_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->cvg_opt; return ICP_OK; }
+int icp_get_convergence(const icp_ctx* c, icp_convergence_result* out) { if (!c || !out) return ICP_ERR_INVALID_ARG; *out = c->cvg_last; return ICP_OK; }
+int icp_get_convergence_trace(const icp_ctx* c, icp_convergence_step* out, int32_t max_out, int32_t* count_out) {
+    if (!c || max_out < 0 || (!out && max_out > 0)) return ICP_ERR_INVALID_ARG;
+    const int32_t n = (int32_t)c->cvg_trace.size();
+    for (int32_t i = 0; i < n && i < max_out; i++) out[i] = c->cvg_trace[(size_t)i];
+    if (count_out) *count_out = n;
+    return ICP_OK;
+}
+
 int icp_nss_options_default(icp_nss_options* o) {
     if (!o) return ICP_ERR_INVALID_ARG;
     o->grid = 5; o->resample = 1;

@@ -118,6 +118,14 @@ def select_optimizer(ctx, nonlinear):
         ctx.set_optimizer(nonlinear)
 
 
+def select_convergence(ctx, convergence):
+    """The runners' `convergence=` argument: a dict of set_convergence_options' arguments -> on, False -> off, None -> unchanged."""
+    if convergence is False:
+        ctx.set_convergence_options(None)
+    elif convergence is not None:
+        ctx.set_convergence_options(**convergence)
+
+
 def depth_camera(K, width, height, extrinsics=None):
     """icp_depth_camera from a 3x3 intrinsic matrix (K(0,0), K(1,1), K(0,2), K(1,2)) and an optional 4x4 depthExtrinsics."""
     K = np.asarray(K, dtype=np.float32)
@@ -138,6 +146,21 @@ class IcpRobustStats(C.Structure):
 
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY = 0, 1, 2, 3
 ROBUST_KERNELS = {"none": ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY, "tukey": ROBUST_TUKEY}
+
+
+class IcpConvergenceOptions(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("rotation_eps", C.c_float), ("translation_eps", C.c_float), ("min_iterations", C.c_int32), ("patience", C.c_int32)]
+
+
+class IcpConvergenceStep(C.Structure):
+    _fields_ = [("rotation", C.c_float), ("translation", C.c_float), ("eligible", C.c_int32), ("streak", C.c_int32)]
+
+
+class IcpConvergenceResult(C.Structure):
+    _fields_ = [("converged", C.c_int32), ("iterations_run", C.c_int32), ("iterations_planned", C.c_int32), ("rotation", C.c_float), ("translation", C.c_float)]
+
+
+CONVERGENCE_STEP_DTYPE = np.dtype([("rotation", np.float32), ("translation", np.float32), ("eligible", np.int32), ("streak", np.int32)])
 
 
 class IcpNssOptions(C.Structure):
@@ -179,6 +202,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
            "icp_robust_options_default", "icp_set_robust_options", "icp_get_robust_options", "icp_get_robust_stats",
+           "icp_convergence_options_default", "icp_set_convergence_options", "icp_get_convergence_options", "icp_get_convergence", "icp_get_convergence_trace",
            "icp_nss_options_default", "icp_set_nss_options", "icp_get_nss_options", "icp_get_normal_buckets", "icp_get_selection",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
@@ -356,6 +380,39 @@ class Context:
         buf = (IcpRobustStats * max(n.value, 1))()
         self._ck(self.lib.icp_get_robust_stats(self.h, buf, C.c_int32(n.value), C.byref(n)))
         return [dict(n_entering=b.n_entering, n_kept=b.n_kept, trim_d2=b.trim_d2, sigma=b.sigma) for b in buf[:n.value]]
+
+    def set_convergence_options(self, rotation=None, translation=None, min_iterations=1, patience=1):
+        """icp_set_convergence_options: stop run / batch_run / track_depth_frames on the device once `patience` consecutive eligible
+        iterations moved the pose by at most `rotation` (|sin theta|, ~radians) and `translation` (metres), not before `min_iterations`.
+        set_convergence_options(None) turns the option off."""
+        if rotation is None and translation is None:
+            self._ck(self.lib.icp_set_convergence_options(self.h, None))
+            return self.convergence_options()
+        if rotation is None or translation is None:
+            raise TypeError("set_convergence_options: give both rotation and translation, or neither (off)")
+        o = IcpConvergenceOptions(1, float(rotation), float(translation), int(min_iterations), int(patience))
+        self._ck(self.lib.icp_set_convergence_options(self.h, C.byref(o)))
+        return o
+
+    def convergence_options(self):
+        o = IcpConvergenceOptions()
+        self._ck(self.lib.icp_get_convergence_options(self.h, C.byref(o)))
+        return o
+
+    def convergence(self):
+        """icp_get_convergence: the last run on the context: converged, iterations_run, iterations_planned and the measure (rotation,
+        translation) of the last iteration that ran (-1 with the option off)."""
+        r = IcpConvergenceResult()
+        self._ck(self.lib.icp_get_convergence(self.h, C.byref(r)))
+        return dict(converged=bool(r.converged), iterations_run=r.iterations_run, iterations_planned=r.iterations_planned, rotation=r.rotation, translation=r.translation)
+
+    def convergence_trace(self):
+        """icp_get_convergence_trace: one (rotation, translation, eligible, streak) record per iteration that ran (none with the option off)."""
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_get_convergence_trace(self.h, None, C.c_int32(0), C.byref(n)))
+        out = np.zeros(n.value, CONVERGENCE_STEP_DTYPE)
+        self._ck(self.lib.icp_get_convergence_trace(self.h, _ptr(out), C.c_int32(n.value), C.byref(n)))
+        return out
 
     def set_nss_options(self, grid=5, resample=True):
         """icp_set_nss_options: normal-space sampling (params.selection = SELECT_NORMAL_SPACE): cells per cube-face edge (3, 5 or 7) and
@@ -685,6 +742,9 @@ class LinearICPOptimizer:
     def setGICPOptions(self, epsilon=1e-3, k=20): self.ctx.set_gicp_options(epsilon, k)         # setMetric(METRIC_GICP) selects it
     def setColoredICPOptions(self, lambda_geometric=0.968, k=20): self.ctx.set_colored_options(lambda_geometric, k)   # setMetric(METRIC_COLORED)
     def setRobustOptions(self, kernel="none", tuning=0.0, sigma=0.0, overlap=1.0): self.ctx.set_robust_options(kernel, tuning, sigma, overlap)
+
+    def setConvergenceCriteria(self, rotation_eps, translation_eps, min_iterations=1, patience=1):
+        self.ctx.set_convergence_options(rotation_eps, translation_eps, min_iterations, patience)
 
     def setNormalSpaceOptions(self, grid=5, resample=True): self.ctx.set_nss_options(grid, resample)   # setSelectionMethod(SELECT_NORMAL_SPACE) selects it
 

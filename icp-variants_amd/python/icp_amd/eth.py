@@ -56,12 +56,15 @@ def prepare_pair(ctx, src_xyz, tgt_xyz, benchmark_pose, pose_scaling=0.1, k=5):
                 gt=np.linalg.inv(np.asarray(S, np.float64)), initial=S)
 
 
-def align(ctx, pair, nonlinear=None, check=True):
+def align(ctx, pair, nonlinear=None, check=True, convergence=None):
     """estimatePose of alignETH (main.cpp:457) on a prepared pair with the context's params: the optimiser the reference's
     USE_LINEAR_ICP picks (main.cpp:26) -- nonlinear True (or an IcpLmOptions): CeresICPOptimizer, False: LinearICPOptimizer, None: the
-    context's current choice.  Returns (4x4 pose, per-iteration records, status)."""
+    context's current choice.  convergence: dict(rotation=..., translation=...[, min_iterations, patience]) stops the run on a converged
+    pose (Context.set_convergence_options), False turns that off, None keeps the context's setting.
+    Returns (4x4 pose, per-iteration records, status)."""
     from . import binding
     binding.select_optimizer(ctx, nonlinear)
+    binding.select_convergence(ctx, convergence)
     ctx.push_params()
     ctx.set_target(pair["tgt_pts"], pair["tgt_nrm"], pair.get("tgt_rgba"))
     ctx.set_source(pair["src_pts"], pair["src_nrm"], pair.get("src_rgba"))

@@ -387,6 +387,47 @@ int icp_get_colored_options(const icp_ctx* ctx, icp_colored_options* opt);
    out[0 .. min(n, max_points)) is written, *n_out (optional) = n. */
 int icp_get_color_gradients(icp_ctx* ctx, float* out, int32_t max_points, int32_t* n_out);
 
+/* -------- Stopping on a converged pose (extension: the reference always runs its whole schedule), per context --------
+ * Off (the default): every loop runs its whole schedule, exactly as without this call.  On: the loop stops, decided on the device, after
+ * the first iteration i with streak >= patience and i + 1 >= min_iterations.
+ * The measure of iteration i, from two fp32 poses widened to fp64: A = the pose after the iteration, B = the pose it searched at (the
+ * incoming pose for iteration 0); dR = R_A R_B^T (each entry (a0 b0 + a1 b1) + a2 b2), dt = t_A - dR t_B;
+ *   rotation    = 0.5 * sqrt(((dR21 - dR12)^2 + (dR02 - dR20)^2) + (dR10 - dR01)^2) = |sin theta|; +inf when trace(dR) - 1 <= 0 (> 90 deg);
+ *   translation = |dt|;   both rounded once to fp32.
+ * The iteration MEETS the criterion when rotation <= rotation_eps && translation <= translation_eps (a NaN fails it).
+ * Iteration i is ELIGIBLE when its status is ICP_OK, its decimation factor (icp_schedule) equals that of the schedule's last iteration
+ * and, for i > 0, that of iteration i - 1 (coarse multires levels and the first iteration of a new level never count).
+ * streak: 0 after an ineligible iteration or an eligible one that misses the criterion, + 1 after an eligible one that meets it.
+ * A stopped run: pose_inout = the pose after iteration i, *n_iterations_run = i + 1, records 0 .. i are bit for bit those of the same run
+ * with the option off (icp_iter_stats, icp_robust_stats, icp_lm_summary), nothing is reported beyond record i; icp_timing.iterations,
+ * icp_get_iteration_times and icp_track_frame.iterations report i + 1; the return status is that of the records reported;
+ * icp_get_selection keeps serving the planned draws.  A run that never meets the criterion is the run with the option off.
+ * Honoured by icp_run, icp_batch_run (each context's own options) and icp_track_depth_frames, with every matcher, metric, weighting,
+ * rejection, multires, selection, robust mode and the non-linear optimiser; icp_iterate, icp_correspond, icp_match and icp_match_seeded
+ * ignore it; icp_run_multistart returns ICP_ERR_INVALID_ARG while it is enabled (its starts share their launches). */
+typedef struct icp_convergence_options {
+    int32_t enabled;          /* 0 (default): every loop runs its whole schedule */
+    float   rotation_eps;     /* > 0, finite: bound on the rotation measure (|sin theta|, ~radians)       default 1e-6 */
+    float   translation_eps;  /* > 0, finite: bound on the translation measure, metres                     default 1e-6 */
+    int32_t min_iterations;   /* >= 1: no stop before this many iterations have run                        default 1 */
+    int32_t patience;         /* 1..8: consecutive eligible iterations that must meet both bounds          default 1 */
+} icp_convergence_options;
+typedef struct icp_convergence_step { float rotation, translation; int32_t eligible, streak; } icp_convergence_step;
+typedef struct icp_convergence_result {
+    int32_t converged;            /* 1: the last run stopped on the criterion */
+    int32_t iterations_run, iterations_planned;
+    float   rotation, translation;/* the measure of the last iteration that ran; -1 when the option was off or nothing ran */
+} icp_convergence_result;
+int icp_convergence_options_default(icp_convergence_options* opt);
+/* NULL = defaults (off).  Validation (also while enabled == 0): enabled in {0, 1}, both eps finite and > 0, min_iterations >= 1,
+ * patience in 1..8; else ICP_ERR_INVALID_ARG (reason in icp_last_error). */
+int icp_set_convergence_options(icp_ctx* ctx, const icp_convergence_options* opt);
+int icp_get_convergence_options(const icp_ctx* ctx, icp_convergence_options* opt);
+/* The last icp_run on the context (icp_batch_run: the context's own last pair; icp_track_depth_frames: the last tracked frame). */
+int icp_get_convergence(const icp_ctx* ctx, icp_convergence_result* out);
+/* One step per iteration that ran, of the same run; none when the option was off.  out[0 .. min(max_out, count)), *count_out = count. */
+int icp_get_convergence_trace(const icp_ctx* ctx, icp_convergence_step* out, int32_t max_out, int32_t* count_out);
+
 /* -------- ConvergenceMeasure (ConvergenceMeasure.h:30-66): known-correspondence RMSE --------
  * src_xyz[i] (moved by the estimated pose) is compared with ref_xyz[i]. */
 int icp_set_convergence_reference(icp_ctx* ctx, const float* src_xyz, const float* ref_xyz, int32_t n);

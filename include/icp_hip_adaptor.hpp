@@ -237,6 +237,16 @@ public:
         icp_nss_options o; o.grid = (int32_t)grid; o.resample = resample ? 1 : 0;
         return icp_set_nss_options(context(), &o);
     }
+    // Stopping on a converged pose (an extension): estimatePose ends once `patience` consecutive iterations at the finest level moved the
+    // pose by at most rotation_eps (|sin theta|, ~radians) and translation_eps (metres), not before min_iterations; decided on the device
+    // (icp_set_convergence_options).  Returns its status (ICP_ERR_INVALID_ARG: a value out of range).  clearConvergenceCriteria: off again.
+    int setConvergenceCriteria(float rotation_eps, float translation_eps, int min_iterations = 1, int patience = 1) {
+        if (!context()) return ICP_ERR_NO_DEVICE;
+        icp_convergence_options o; o.enabled = 1; o.rotation_eps = rotation_eps; o.translation_eps = translation_eps;
+        o.min_iterations = (int32_t)min_iterations; o.patience = (int32_t)patience;
+        return icp_set_convergence_options(context(), &o);
+    }
+    int clearConvergenceCriteria() { return context() ? icp_set_convergence_options(context(), nullptr) : ICP_ERR_NO_DEVICE; }
     // LinearICPOptimizer::estimatePose, ICPOptimizer.h:493-663
     void estimatePose(const PointCloud& source, const PointCloud& target, Matrix4f& initialPose, bool calculateRMSE = true) override {
         icp_params p; icp_params_default(&p);

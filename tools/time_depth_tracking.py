@@ -4,8 +4,9 @@
            filter in numpy, icp_set_source, icp_run (frame 0: the same, keepOriginalSize per the options, icp_set_target)
 Both run point-to-plane k-NN (LBVH), 35 iterations, max distance 0.1, source (false, 8) -- the reference's default variant -- from the
 same frames, and the tool checks that both end on the same poses.  Stage timing is off in both.  Frames/s counts the 11 tracked frames
-and the wall clock includes frame 0's target.
-usage: python tools/time_depth_tracking.py [--reps 5] [--json out.json]"""
+and the wall clock includes frame 0's target.  --convergence ROT,TRANS stops every frame's run on a converged pose
+(icp_set_convergence_options) in both routes; the iterations every frame ran are reported.
+usage: python tools/time_depth_tracking.py [--reps 5] [--convergence 1e-6,1e-6] [--json out.json]"""
 import argparse
 import json
 import os
@@ -47,6 +48,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--frames", type=int, default=12)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--convergence", default=None, help="rotation_eps,translation_eps")
     a = ap.parse_args()
     W, H = tum.TUM_WIDTH, tum.TUM_HEIGHT
     K, depth, rgbx = make_frames(a.frames, W, H)
@@ -54,6 +56,9 @@ def main():
     ctx.params.metric = 1; ctx.params.knn_backend = 1
     tum.reconstruct_room_params(ctx.params)
     ctx.push_params(); ctx.set_stage_timing(0)
+    if a.convergence:
+        rot, trans = (float(x) for x in a.convergence.split(","))
+        ctx.set_convergence_options(rot, trans)
     to, so = tum.reconstruct_room_options(ctx.params)
     cam = binding.depth_camera(K, W, H)
     res = {}
@@ -63,14 +68,14 @@ def main():
             t0 = time.perf_counter()
             if route == "device":
                 _, recs, rc = ctx.track_depth_frames(depth, rgbx, cam, to, so)
-                poses = [r["pose"] for r in recs]
+                poses = [r["pose"] for r in recs]; iterations = [r["iterations"] for r in recs]
             else:
                 poses = host_route(ctx, K, depth, rgbx, to, so)
             times.append(time.perf_counter() - t0)
         res[route] = dict(seconds=sorted(times), poses=poses)
     same = all(np.array_equal(p.view(np.uint32), q.view(np.uint32)) for p, q in zip(res["device"]["poses"], res["host"]["poses"]))
     n = a.frames - 1
-    out = dict(frames=a.frames, width=W, height=H, reps=a.reps, poses_bit_identical=bool(same))
+    out = dict(frames=a.frames, width=W, height=H, reps=a.reps, poses_bit_identical=bool(same), convergence=a.convergence, iterations=iterations)
     for route in ("device", "host"):
         s = res[route]["seconds"]
         out[route] = dict(median_s=s[len(s) // 2], min_s=s[0], frames_per_s_median=n / s[len(s) // 2], frames_per_s_best=n / s[0])
