@@ -1,6 +1,6 @@
 // host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
 // and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
-// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_debug.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_global, host_debug.
 using namespace icpdev;
 
 #define HIPCK(ctx, expr)                                                                        \
@@ -37,6 +37,10 @@ struct Level { DevBuf idx; DevBuf order; DevBuf sorted_idx; DevBuf pack; Cloud s
 // NssHeld: the draw a run with resample = 0 holds for a decimation factor, as a level of its own; word = the iteration it was drawn for.
 struct NssLevel { DevBuf cand, seg, longs; int n_base = 0, max_long = 0, max_chunks = 0; };
 struct NssHeld { Level lv; uint32_t word = 0; };
+
+// Global registration (dev_fpfh.hpp): the features of one resident cloud -- per point the neighbour list (idx, d2: n x k) and the SPFH
+// (counts n x 33, pairs n), per keypoint the FPFH rows (feat: nk x 33) -- for the (k, stride) they were computed with.
+struct FpfhCache { DevBuf nb_idx, nb_d2, counts, pairs, feat; bool ready = false; int k = 0, stride = 0, n = 0, nk = 0; };
 
 // LBVH over the target (buildIndex): device buffers + the host-side facts needed to launch the build.
 struct Bvh {
@@ -78,6 +82,10 @@ struct icp_ctx {
     icp_convergence_options cvg_opt = {0, 1e-6f, 1e-6f, 1, 1};      // icp_set_convergence_options: stopping on a converged pose
     icp_convergence_result cvg_last = {0, 0, 0, -1.f, -1.f};        // the last run (icp_get_convergence) ...
     std::vector<icp_convergence_step> cvg_trace;                    // ... and its trace, one step per iteration that ran (icp_get_convergence_trace)
+    icp_global_options glob_opt = {20, 1, 1, 4096, 0.9f, 0.005f, 0u, 16};   // icp_set_global_options
+    FpfhCache fpfh[2];                           // features of the target [0] / source [1] (dropped by every call that replaces the cloud and by new options)
+    DevBuf gm_best[2], gm_fwd, gm_keep, gm_list, gm_idx, gm_pts, gm_hyp;   // matcher results (forward / backward), kept flags and list, the pairs' indices and points, the hypotheses
+    std::vector<icp_global_hypothesis> glob_last;                          // the hypotheses of the last icp_register_global
     icp_params prm;
     Cloud tgt, src, qry;                 // qry: scratch cloud of icp_query_matches
     Cloud nrm_cloud; Bvh nrm_bvh;        // scratch of icp_estimate_normals

@@ -250,6 +250,7 @@ int finish_target(icp_ctx* c, bool with_colors) {
     b.valid = false; b.n_valid = 0;
     c->gicp_ready[0] = false;
     c->col_ready = false;
+    c->fpfh[0].ready = false;
     if ((rc = finite_list(c, c->tgt, false, c->tgt_flag, c->tgt_finite, &b.n_valid))) return rc;
     b.d_finite = c->tgt_finite.as<int>(); b.n_ids = c->tgt.n;
     c->bvh6.d_finite = b.d_finite; c->bvh6.n_valid = b.n_valid; c->bvh6.n_ids = c->tgt.n;
@@ -270,6 +271,7 @@ int finish_source(icp_ctx* c) {
     c->levels.clear();
     drop_nss(c, false); c->sel_last.clear();
     c->gicp_ready[1] = false;
+    c->fpfh[1].ready = false;
     if (n <= 0) return ICP_OK;
     if ((rc = ensure(c, c->src_flag, (size_t)n))) return rc;
     if ((rc = ensure(c, c->src_box, 32))) return rc;

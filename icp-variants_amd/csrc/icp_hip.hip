@@ -4,6 +4,7 @@
 // There is NO CPU fallback: every entry point needs a HIP device and fails with ICP_ERR_HIP /
 // ICP_ERR_NO_DEVICE when none is usable.
 // =====================================================================================
+#include <algorithm>
 #include <atomic>
 #include <cstring>
 #include <cstdio>
@@ -28,6 +29,7 @@
 #include "host_loop.hpp"
 #include "host_multi.hpp"
 #include "host_depth.hpp"
+#include "host_global.hpp"
 #include "host_debug.hpp"
 
 // What stays here: context create / destroy, the option setters and getters, and the small one-shot entry points.
@@ -93,6 +95,8 @@ int icp_ctx_destroy(icp_ctx* c) {
     for (auto& pl : c->gicp_n) for (DevBuf& d : pl) release(d);
     for (DevBuf& d : c->col_grad) release(d);
     release(c->gicp_flag);
+    for (FpfhCache& f : c->fpfh) for (DevBuf* d : {&f.nb_idx, &f.nb_d2, &f.counts, &f.pairs, &f.feat}) release(*d);
+    for (DevBuf* d : {&c->gm_best[0], &c->gm_best[1], &c->gm_fwd, &c->gm_keep, &c->gm_list, &c->gm_idx, &c->gm_pts, &c->gm_hyp}) release(*d);
     release(c->rob_keys); release(c->rob_state); release(c->rob_stats);
     for (DevBuf* d : {&c->ms_ps, &c->ms_nn, &c->ms_st, &c->ms_st2, &c->ms_rec, &c->ms_d2, &c->ms_partials, &c->ms_totals, &c->ms_stats, &c->ms_score, &c->ms_res}) release(*d);
     release(c->stats); release(c->staging); release(c->rmse_partials); release(c->rmse_out); release(c->fontana_partials);

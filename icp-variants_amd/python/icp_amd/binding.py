@@ -170,6 +170,26 @@ class IcpNssOptions(C.Structure):
 SELECT_ALL, SELECT_RANDOM, SELECT_NORMAL_SPACE = 0, 1, 2
 
 
+class IcpGlobalOptions(C.Structure):
+    _fields_ = [("k", C.c_int32), ("feature_stride", C.c_int32), ("mutual", C.c_int32), ("n_hypotheses", C.c_int32), ("edge_similarity", C.c_float),
+                ("inlier_distance", C.c_float), ("seed", C.c_uint32), ("n_best", C.c_int32)]
+
+
+class IcpGlobalHypothesis(C.Structure):
+    _fields_ = [("pose", C.c_float * 16), ("n_inliers", C.c_int32), ("reserved", C.c_int32), ("sum_d2", C.c_double), ("status", C.c_int32), ("draw", C.c_int32 * 3)]
+
+
+GLOBAL_HYPOTHESIS_DTYPE = np.dtype([("pose", np.float32, 16), ("n_inliers", np.int32), ("reserved", np.int32), ("sum_d2", np.float64), ("status", np.int32), ("draw", np.int32, 3)], align=True)
+CLOUD_TARGET, CLOUD_SOURCE, CLOUD_BOTH = 0, 1, 2
+GLOBAL_VALID, GLOBAL_REPEATED, GLOBAL_EDGES, GLOBAL_DEGENERATE = 0, 1, 2, 3
+FPFH_DIM = 33
+_CLOUDS = {"target": CLOUD_TARGET, "source": CLOUD_SOURCE, "both": CLOUD_BOTH}
+
+
+def _cloud(which):
+    return _CLOUDS[which] if isinstance(which, str) else int(which)
+
+
 class IcpColorCamera(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_int32), ("height", C.c_int32),
                 ("extrinsics", C.c_float * 16)]
@@ -204,6 +224,8 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_robust_options_default", "icp_set_robust_options", "icp_get_robust_options", "icp_get_robust_stats",
            "icp_convergence_options_default", "icp_set_convergence_options", "icp_get_convergence_options", "icp_get_convergence", "icp_get_convergence_trace",
            "icp_nss_options_default", "icp_set_nss_options", "icp_get_nss_options", "icp_get_normal_buckets", "icp_get_selection",
+           "icp_global_options_default", "icp_set_global_options", "icp_get_global_options", "icp_compute_features", "icp_get_features", "icp_get_spfh",
+           "icp_get_feature_neighbours", "icp_match_features", "icp_register_global", "icp_get_global_hypotheses",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
 
@@ -440,6 +462,86 @@ class Context:
         self._ck(self.lib.icp_get_selection(self.h, C.c_int32(iteration), None, C.c_int32(0), C.byref(n)))
         out = np.empty(n.value, np.int32)
         self._ck(self.lib.icp_get_selection(self.h, C.c_int32(iteration), _ptr(out), C.c_int32(n.value), C.byref(n)))
+        return out
+
+    def set_global_options(self, **kw):
+        """icp_set_global_options: global registration (FPFH features, feature matching, RANSAC).  Keywords: k (5, 10, 20), feature_stride,
+        mutual, n_hypotheses, edge_similarity, inlier_distance (metres), seed, n_best; what is not given keeps its default."""
+        o = IcpGlobalOptions()
+        self.lib.icp_global_options_default(C.byref(o))
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise TypeError("unknown global option %r" % k)
+            setattr(o, k, type(getattr(o, k))(v))
+        self._ck(self.lib.icp_set_global_options(self.h, C.byref(o)))
+        return o
+
+    def global_options(self):
+        o = IcpGlobalOptions()
+        self._ck(self.lib.icp_get_global_options(self.h, C.byref(o)))
+        return o
+
+    def compute_features(self, which="both"):
+        """icp_compute_features: the features of "target", "source" or "both" into the context's cache."""
+        self._ck(self.lib.icp_compute_features(self.h, C.c_int32(_cloud(which))))
+
+    def features(self, which="source"):
+        """icp_get_features: the FPFH rows of the keypoints, (n_keypoints, 33) float32; row r is point r * feature_stride, NaN rows: no feature."""
+        w = C.c_int32(_cloud(which)); n = C.c_int32(0)
+        self._ck(self.lib.icp_get_features(self.h, w, None, C.c_int32(0), C.byref(n)))
+        out = np.empty((n.value, FPFH_DIM), np.float32)
+        self._ck(self.lib.icp_get_features(self.h, w, _ptr(out), C.c_int32(n.value), C.byref(n)))
+        return out
+
+    def spfh(self, which="source"):
+        """icp_get_spfh: (counts (n, 33) uint8, pairs (n,) int32) of every point."""
+        w = C.c_int32(_cloud(which)); n = C.c_int32(0)
+        self._ck(self.lib.icp_get_spfh(self.h, w, None, None, C.c_int32(0), C.byref(n)))
+        counts = np.empty((n.value, FPFH_DIM), np.uint8); pairs = np.empty(n.value, np.int32)
+        self._ck(self.lib.icp_get_spfh(self.h, w, _ptr(counts), _ptr(pairs), C.c_int32(n.value), C.byref(n)))
+        return counts, pairs
+
+    def feature_neighbours(self, which="source"):
+        """icp_get_feature_neighbours: (idx (n, k) int32, d2 (n, k) float32), ascending (d2, index) per point; unfilled slots (-1, inf)."""
+        w = C.c_int32(_cloud(which)); n = C.c_int32(0)
+        k = self.global_options().k
+        self._ck(self.lib.icp_get_feature_neighbours(self.h, w, None, None, C.c_int32(0), C.byref(n)))
+        idx = np.empty((n.value, k), np.int32); d2 = np.empty((n.value, k), np.float32)
+        self._ck(self.lib.icp_get_feature_neighbours(self.h, w, _ptr(idx), _ptr(d2), C.c_int32(n.value), C.byref(n)))
+        return idx, d2
+
+    def match_features(self):
+        """icp_match_features: (src_idx, tgt_idx) int32 arrays of the feature correspondences, ascending in src_idx."""
+        # at most one pair per source keypoint: buffers of that size make it one matcher run, not two
+        cap = (int(getattr(self, "n_src", 0)) + self.global_options().feature_stride - 1) // self.global_options().feature_stride
+        m = C.c_int32(0)
+        if cap <= 0:                                        # (a source this wrapper did not upload: ask for the count first)
+            self._ck(self.lib.icp_match_features(self.h, None, None, C.c_int32(0), C.byref(m)))
+            cap = m.value
+        si = np.empty(max(cap, 1), np.int32); ti = np.empty(max(cap, 1), np.int32)
+        self._ck(self.lib.icp_match_features(self.h, _ptr(si), _ptr(ti), C.c_int32(cap), C.byref(m)))
+        if m.value > cap:                                   # (the resident source is larger than n_src says: once more with room)
+            cap = m.value
+            si = np.empty(cap, np.int32); ti = np.empty(cap, np.int32)
+            self._ck(self.lib.icp_match_features(self.h, _ptr(si), _ptr(ti), C.c_int32(cap), C.byref(m)))
+        return si[:m.value].copy(), ti[:m.value].copy()
+
+    def register_global(self, check=True):
+        """icp_register_global: features, matching, RANSAC.  Returns (poses, records, status): the best poses (a list of 4 x 4, best first),
+        their hypothesis records (GLOBAL_HYPOTHESIS_DTYPE) and the status code (check=False: ERR_NO_CORRESPONDENCES comes back as a code)."""
+        nb = self.global_options().n_best
+        poses = np.zeros((nb, 16), np.float32); recs = np.zeros(nb, GLOBAL_HYPOTHESIS_DTYPE); n = C.c_int32(0)
+        rc = self.lib.icp_register_global(self.h, _ptr(poses), _ptr(recs), C.byref(n))
+        if check or rc not in (ICP_OK, ERR_NO_CORRESPONDENCES):
+            self._ck(rc)
+        return [pose_from_c(p) for p in poses[:n.value]], recs[:n.value].copy(), rc
+
+    def global_hypotheses(self):
+        """icp_get_global_hypotheses: every hypothesis of the last register_global, in order of h (GLOBAL_HYPOTHESIS_DTYPE)."""
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_get_global_hypotheses(self.h, None, C.c_int32(0), C.byref(n)))
+        out = np.zeros(n.value, GLOBAL_HYPOTHESIS_DTYPE)
+        self._ck(self.lib.icp_get_global_hypotheses(self.h, _ptr(out), C.c_int32(n.value), C.byref(n)))
         return out
 
     def push_params(self):

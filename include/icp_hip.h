@@ -529,6 +529,81 @@ int icp_estimate_normals(icp_ctx* ctx, const float* xyz, int32_t n, int32_t k, c
  * 32-bit hash is < proba * 2^32.  Exposed so host code (and the test oracle) can reproduce the device's choice exactly. */
 uint32_t icp_select_hash(uint32_t seed, uint32_t iteration, uint32_t index);
 
+/* -------- global registration (an extension): FPFH features, feature matching, RANSAC --------
+ * ICP is local; these entry points find initial poses for it from the two resident clouds alone (both need normals): Fast Point
+ * Feature Histograms (Rusu, Blodow, Beetz, ICRA 2009), an exact nearest neighbour in feature space, RANSAC over three-point
+ * hypotheses.  The winners go to icp_run_multistart.  Nothing else in the library changes behaviour.
+ *
+ * Features, once per cloud and cached (a new target / source, a depth upload of that cloud, or new options drop the cache):
+ *   neighbourhood  the k smallest (fp32 d^2 = (dx^2 + dy^2) + dz^2, index) pairs over the cloud's finite points, the point itself
+ *                  included -- icp_estimate_normals' rule; k in {5, 10, 20}; fewer than k finite points: all of them.  Stored per point
+ *                  in ascending (d^2, index) order; unfilled slots are (-1, +inf); a non-finite point has none.
+ *   pair features  of point p and each neighbour q with d^2 > 0, in fp64 from the fp32 coordinates and normals: dp = q - p, f4 = |dp|,
+ *                  a1 = n_p.dp / f4, a2 = n_q.dp / f4; if |a1| < |a2| the pair is taken from q's side (the normals swapped, dp <- -dp,
+ *                  f3 = -a2), otherwise f3 = a1; v = dp x n1, the pair skipped when |v| = 0 or an input is not finite; v <- v / |v|,
+ *                  w = n1 x v, f1 = v.n2, f2 = atan2(w.n2, n1.n2).  (Dot products and squared norms add as (x + y) + z.)
+ *   bins           11 per feature, floor(11 (x - lo) / (hi - lo)) clamped to 0..10, over [-1, 1] (f1), [-pi, pi] (f2), [-1, 1] (f3).
+ *   SPFH           33 integer counts per point (uint8: bins of f1, f2, f3) and the number of contributing pairs, for EVERY point.
+ *   FPFH           h(p) = SPFH(p) / max(pairs(p), 1);  F(p) = h(p) + sum_i w_i h(q_i) over the neighbours with d_i > 0 in stored order,
+ *                  w_i = (1 / d_i) / sum_j (1 / d_j), d = sqrt(d^2) in fp64; fp64 sums, one rounding to fp32.  33 NaNs for a point with a
+ *                  non-finite position or normal or with no contributing pair: such a row takes no part in matching.
+ *   keypoints      the points whose index is a multiple of feature_stride (PointCloud.h:325-343's stride idiom): FPFH, matching and RANSAC
+ *                  use keypoints only, neighbourhoods and SPFH the whole cloud.  Keypoint r is point r * feature_stride.
+ * Matching: for every source keypoint the target keypoint with the smallest d = sum over the 33 bins, in order, of (a_b - c_b)^2 (fp32, one
+ *   rounding per operation); ties: the lowest target index; NaN rows never match and are never matched.  mutual = 1: pair (i, j) is kept
+ *   only if i is also the match of j in the other direction.  The M pairs are listed in ascending source order.
+ * RANSAC: hypothesis h (0 .. n_hypotheses - 1) draws c_j = icp_select_hash(seed, h, j) mod M, j = 0, 1, 2.  Its status is, in this order,
+ *   ICP_GLOBAL_REPEATED   two draws are equal;
+ *   ICP_GLOBAL_EDGES      for one of the edges (0,1), (1,2), (2,0): min(l_src, l_tgt) < edge_similarity max(l_src, l_tgt), fp64 lengths;
+ *   ICP_GLOBAL_DEGENERATE on either side |e1 x e2|^2 <= 1e-6 |e1|^2 |e2|^2, e1 = p1 - p0, e2 = p2 - p0 in fp64 (collinear within 1e-3 rad),
+ *                         or a pose that is not finite;
+ *   ICP_GLOBAL_VALID      else: the three-point Kabsch fit in fp64 (unweighted centroids, R = U diag(1, 1, det(U V^T)) V^T, t = tm - R sm),
+ *                         rounded once to fp32.
+ *   A valid hypothesis is scored over all M pairs: the source point moved by the fp32 pose (((R_i0 x + R_i1 y) + R_i2 z) + t_i),
+ *   d^2 = (dx^2 + dy^2) + dz^2 in fp32, an inlier when d^2 <= inlier_distance^2 (squared once in fp32); n_inliers and the fp64 sum of the
+ *   inliers' d^2, reduced in a fixed order (two runs agree bit for bit).  Ranking of the valid ones: more inliers, then the smaller sum,
+ *   then the lower h. */
+enum { ICP_CLOUD_TARGET = 0, ICP_CLOUD_SOURCE = 1, ICP_CLOUD_BOTH = 2 };
+enum { ICP_GLOBAL_VALID = 0, ICP_GLOBAL_REPEATED = 1, ICP_GLOBAL_EDGES = 2, ICP_GLOBAL_DEGENERATE = 3 };
+typedef struct icp_global_options {
+    int32_t k;                /* neighbours per point, 5, 10 or 20                       default 20   */
+    int32_t feature_stride;   /* keypoints: every feature_stride-th point, >= 1          default 1    */
+    int32_t mutual;           /* 1: keep mutual matches only                             default 1    */
+    int32_t n_hypotheses;     /* 1 .. 65536                                              default 4096 */
+    float   edge_similarity;  /* 0 .. 1                                                  default 0.9  */
+    float   inlier_distance;  /* metres (NOT squared), > 0                               default 0.005 */
+    uint32_t seed;            /*                                                         default 0    */
+    int32_t n_best;           /* poses icp_register_global returns, 1 .. 256             default 16   */
+} icp_global_options;
+typedef struct icp_global_hypothesis {
+    float   pose[16];         /* column-major; identity unless status == ICP_GLOBAL_VALID */
+    int32_t n_inliers;
+    int32_t reserved;         /* 0 (keeps the double on an 8-byte boundary with no hidden padding: records compare byte for byte) */
+    double  sum_d2;           /* of the inliers' fp32 d^2 */
+    int32_t status;           /* ICP_GLOBAL_* */
+    int32_t draw[3];          /* the three correspondences drawn (positions in icp_match_features' list) */
+} icp_global_hypothesis;
+int icp_global_options_default(icp_global_options* o);
+int icp_set_global_options(icp_ctx* ctx, const icp_global_options* o);      /* NULL: the defaults; out of range: ICP_ERR_INVALID_ARG */
+int icp_get_global_options(const icp_ctx* ctx, icp_global_options* o);
+/* Computes (or finds cached) the features of the target, the source or both (ICP_CLOUD_*).  A cloud without normals:
+ * ICP_ERR_INVALID_ARG. */
+int icp_compute_features(icp_ctx* ctx, int32_t which);
+/* which = ICP_CLOUD_TARGET or ICP_CLOUD_SOURCE below.  Each computes what is not cached, copies min(max_points, n) rows and sets *n_out
+ * to n: the number of keypoints (features: n x 33 floats row-major, row r = point r * feature_stride) or of points (SPFH: n x 33 counts
+ * and n pair counts; neighbours: n x k indices and n x k d^2).  Output pointers may be NULL with max_points = 0. */
+int icp_get_features(icp_ctx* ctx, int32_t which, float* out, int32_t max_points, int32_t* n_out);
+int icp_get_spfh(icp_ctx* ctx, int32_t which, uint8_t* counts, int32_t* pairs, int32_t max_points, int32_t* n_out);
+int icp_get_feature_neighbours(icp_ctx* ctx, int32_t which, int32_t* idx, float* d2, int32_t max_points, int32_t* n_out);
+/* The correspondences (original point indices), ascending in src_idx; *m_out = M.  M = 0 is not an error here. */
+int icp_match_features(icp_ctx* ctx, int32_t* src_idx, int32_t* tgt_idx, int32_t max_pairs, int32_t* m_out);
+/* Features, matching, RANSAC.  poses_out: n_best x 16 floats (column-major poses, best first); best_out (optional): their records;
+ * *n_out: how many there are (min(n_best, valid hypotheses)).  Fewer than 3 correspondences, or no valid hypothesis:
+ * ICP_ERR_NO_CORRESPONDENCES with *n_out = 0 -- reported, never a hang. */
+int icp_register_global(icp_ctx* ctx, float* poses_out, icp_global_hypothesis* best_out, int32_t* n_out);
+/* Every hypothesis of the last icp_register_global, in order of h. */
+int icp_get_global_hypotheses(const icp_ctx* ctx, icp_global_hypothesis* out, int32_t max_out, int32_t* count_out);
+
 /* -------- batches of independent scan pairs: the loop over ETH indices, main.cpp:411-498 / experiment.cpp:319-396 --------
  * The reference aligns the pairs one after the other and carries no state between them, so a batch shards with no
  * data-path exchange: pair p belongs to rank p % n_ranks (icp_pair_owner), and the only collective is ONE gather of the

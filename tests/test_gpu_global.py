@@ -1,0 +1,372 @@
+"""Global registration on the device (icp_register_global: FPFH features, feature matching, RANSAC) against the numpy restatement of its
+contract (tests/global_restatement.py), stage by stage and teacher-forced: each stage's restatement is fed what the device produced for
+the stage before, so every comparison is exact or has a bound that follows from the contract."""
+import numpy as np
+import pytest
+
+import global_restatement as gr
+from conftest import pose_error
+
+pytestmark = pytest.mark.gpu
+
+POSE_TOL = 1e-5
+EXCLUDE_MARGIN, EXCLUDE_GAP = 1e-6, 1e-9      # a point may be left out of the SPFH comparison only inside these (bin units; ||a1| - |a2||)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def ulps(a, b):
+    """distance in fp32 units in the last place between finite arrays of equal sign structure (FPFH values are >= 0)"""
+    return np.abs(bits(a).astype(np.int64) - bits(b).astype(np.int64))
+
+
+def configure(ctx, knn_backend=1, metric=1, n_iterations=20, max_distance=0.0003):
+    p = ctx.params
+    p.metric = metric; p.matching = 0; p.weighting = 0; p.rejection = 1; p.color_icp = 0; p.multires = 0
+    p.n_iterations = n_iterations; p.max_distance = max_distance; p.knn_backend = knn_backend
+    ctx.push_params()
+
+
+def load(ctx, b, knn_backend=1):
+    configure(ctx, knn_backend)
+    ctx.set_target(b["tgt_pts"], b["tgt_nrm"])
+    ctx.set_source(b["src_pts"], b["src_nrm"])
+
+
+_REST = {}
+
+
+def restated(bunny, which, k):
+    """the restatement's features of a bunny cloud, computed once per (cloud, k) and shared"""
+    if (which, k) not in _REST:
+        p, n = (bunny["src_pts"], bunny["src_nrm"]) if which == "source" else (bunny["tgt_pts"], bunny["tgt_nrm"])
+        _REST[(which, k)] = gr.features(p, n, k)
+    return _REST[(which, k)]
+
+
+@pytest.mark.parametrize("knn_backend", [0, 1])
+@pytest.mark.parametrize("k", [5, 10, 20])
+def test_neighbours_equal_a_brute_force_sort(gpu_ctx_factory, bunny, k, knn_backend):
+    """knn_backend 1: the target's lists come from its own tree, 0: from the scratch tree (the source's always do)."""
+    ctx = gpu_ctx_factory()
+    load(ctx, bunny, knn_backend)
+    ctx.set_global_options(k=k)
+    for which in ("source", "target"):
+        idx, d2 = ctx.feature_neighbours(which)
+        r = restated(bunny, which, k)
+        assert np.array_equal(idx, r["idx"]), which
+        assert np.array_equal(bits(d2), bits(r["d2"])), which
+
+
+@pytest.mark.parametrize("k", [5, 10, 20])
+def test_spfh_equals_restatement(gpu_ctx_factory, bunny, k):
+    ctx = gpu_ctx_factory()
+    load(ctx, bunny)
+    ctx.set_global_options(k=k)
+    for which in ("source", "target"):
+        counts, pairs = ctx.spfh(which)
+        r = restated(bunny, which, k)
+        excluded = (r["margin"] < EXCLUDE_MARGIN) | (r["gap"] < EXCLUDE_GAP)
+        print("%s k=%d: min margin %.3g bin units, min ||a1|-|a2|| %.3g, excluded %d" % (which, k, r["margin"].min(), r["gap"].min(), excluded.sum()))
+        assert not excluded.any()                      # none on the bunny (measured on the CPU); the contract would allow 0.1 %
+        assert np.array_equal(pairs, r["pairs"]), which
+        assert np.array_equal(counts, r["counts"]), which
+
+
+def handmade_cloud():
+    """40 points: 30 scattered ones with unit normals, then the special cases (indices in the comments)."""
+    rng = np.random.default_rng(42)
+    p = rng.uniform(-0.05, 0.05, (40, 3)).astype(np.float32)
+    n = rng.normal(size=(40, 3)); n = (n / np.linalg.norm(n, axis=1)[:, None]).astype(np.float32)
+    p[30] = [np.nan, 0.0, 0.0]                                   # NaN position
+    p[31] = [0.01, np.inf, 0.0]                                  # Inf position
+    n[32] = [0.0, np.nan, 0.0]                                   # NaN normal
+    n[33] = [0.0, 0.0, 0.0]                                      # zero normal
+    p[34] = p[0]; p[35] = p[0]                                   # coincident points (d2 = 0: listed, no pair)
+    p[36] = [0.2, 0.0, 0.0]; p[37] = [0.2 + 2.0 ** -9, 0.0, 0.0]   # far from the rest, nearest to each other ...
+    n[36] = [1.0, 0.0, 0.0]; n[37] = [1.0, 0.0, 0.0]             # ... with normals parallel to dp: |dp x n1| = 0 exactly, the pair skipped
+    n[38] = [0.0, 0.0, -np.inf]                                  # Inf normal
+    return p, n
+
+
+def test_handmade_cloud(gpu_ctx_factory):
+    p, n = handmade_cloud()
+    ctx = gpu_ctx_factory()
+    configure(ctx)
+    ctx.set_target(p, n); ctx.set_source(p, n)
+    for k in (5, 10):
+        ctx.set_global_options(k=k)
+        r = gr.features(p, n, k)
+        fin = np.isfinite(r["margin"])
+        assert r["margin"][fin].min() > EXCLUDE_MARGIN and r["gap"][np.isfinite(r["gap"])].min() > EXCLUDE_GAP      # (the comparison below is exact: no pair near a boundary)
+        for which in ("source", "target"):
+            idx, d2 = ctx.feature_neighbours(which)
+            counts, pairs = ctx.spfh(which)
+            F = ctx.features(which)
+            assert np.array_equal(idx, r["idx"]) and np.array_equal(bits(d2), bits(r["d2"]))
+            assert np.array_equal(counts, r["counts"]) and np.array_equal(pairs, r["pairs"])
+            assert np.array_equal(np.isnan(F), np.isnan(r["F"]))
+            ok = ~np.isnan(F)
+            assert ulps(F[ok], r["F"][ok]).max() <= 2
+        # what the special points must show
+        assert (r["idx"][30] == -1).all() and (r["idx"][31] == -1).all() and r["pairs"][30] == 0 and r["pairs"][31] == 0
+        assert r["pairs"][32] == 0 and np.isnan(r["F"][[30, 31, 32, 38]]).all()
+        assert set(r["idx"][0][:3]) == {0, 34, 35} and (r["d2"][0][:3] == 0).all()
+        assert r["idx"][36][1] == 37 and r["pairs"][36] == k - 2                     # the parallel pair is skipped, the other neighbours count
+
+
+def test_two_valid_points(gpu_ctx_factory):
+    """A cloud of 2 valid points (and a NaN one): each has one pair; registration has fewer than 3 correspondences: a status code."""
+    from icp_amd import binding
+    p = np.array([[0, 0, 0], [np.nan, 0, 0], [0.01, 0.002, 0]], np.float32)
+    n = np.array([[0, 0, 1], [0, 0, 1], [0, 0.6, 0.8]], np.float32)
+    ctx = gpu_ctx_factory()
+    configure(ctx)
+    ctx.set_target(p, n); ctx.set_source(p, n)
+    ctx.set_global_options(k=5)
+    r = gr.features(p, n, 5)
+    counts, pairs = ctx.spfh("source")
+    assert pairs.tolist() == [1, 0, 1] and np.array_equal(counts, r["counts"]) and np.array_equal(pairs, r["pairs"])
+    F = ctx.features("target")
+    assert np.array_equal(np.isnan(F), np.isnan(r["F"])) and np.isnan(F[1]).all() and not np.isnan(F[[0, 2]]).any()
+    si, ti = ctx.match_features()
+    es, et = gr.correspondences(F, F, 1, True)          # (the two rows are equal: both match row 0, the mutual test keeps (0, 0) only)
+    assert np.array_equal(si, es) and np.array_equal(ti, et) and len(si) < 3
+    poses, recs, rc = ctx.register_global(check=False)
+    assert rc == binding.ERR_NO_CORRESPONDENCES and poses == [] and len(recs) == 0
+    with pytest.raises(binding.IcpError):
+        ctx.register_global()
+
+
+@pytest.mark.parametrize("stride", [1, 3])
+@pytest.mark.parametrize("k", [5, 20])
+def test_fpfh_values(gpu_ctx_factory, bunny, k, stride):
+    """Device F against the restatement fed the device's own SPFH and neighbour lists: the same fp64 sums in the same order, so 0 or 1 ulp
+    (fp64 division and sqrt are correctly rounded on both sides); 2 ulp asserted."""
+    ctx = gpu_ctx_factory()
+    load(ctx, bunny)
+    ctx.set_global_options(k=k, feature_stride=stride)
+    for which, p, n in (("source", bunny["src_pts"], bunny["src_nrm"]), ("target", bunny["tgt_pts"], bunny["tgt_nrm"])):
+        idx, d2 = ctx.feature_neighbours(which)
+        counts, pairs = ctx.spfh(which)
+        F = ctx.features(which)
+        R = gr.fpfh(p, n, idx, d2, counts, pairs, stride)
+        assert F.shape == R.shape == ((len(p) + stride - 1) // stride, 33)
+        assert not np.isnan(F).any() and not np.isnan(R).any()
+        u = ulps(F, R)
+        print("%s k=%d stride=%d: max |F - restatement| = %d ulp (%d of %d values differ)" % (which, k, stride, u.max(), (u > 0).sum(), u.size))
+        assert u.max() <= 2
+
+
+def matcher_clouds(bunny, case):
+    sp, sn, tp, tn = bunny["src_pts"], bunny["src_nrm"], bunny["tgt_pts"], bunny["tgt_nrm"]
+    if case == "1x1":                               # one keypoint on either side (stride beyond the cloud), a valid feature each
+        return sp[:63], sn[:63], tp[:65], tn[:65], 100
+    if case == "63x65":
+        return sp[:63], sn[:63], tp[:65], tn[:65], 1
+    if case == "257x256":
+        return sp[:257], sn[:257], tp[:256], tn[:256], 1
+    if case == "full":
+        return sp, sn, tp, tn, 1
+    if case == "full_stride3":
+        return sp, sn, tp, tn, 3
+    if case == "duplicates":                        # every target point twice: rows i and i + 300 are equal bit for bit, the lower index must win
+        return sp[:300], sn[:300], np.concatenate([tp[:300], tp[:300]]), np.concatenate([tn[:300], tn[:300]]), 1
+    if case == "nan_rows":
+        sn = sn[:400].copy(); tn = tn[:500].copy()
+        sn[::7] = np.nan; tn[::5] = np.nan; tn[3] = np.nan
+        return sp[:400], sn, tp[:500], tn, 1
+    raise ValueError(case)
+
+
+@pytest.mark.parametrize("mutual", [1, 0])
+@pytest.mark.parametrize("case", ["1x1", "63x65", "257x256", "full", "full_stride3", "duplicates", "nan_rows"])
+def test_matcher_equals_restatement(gpu_ctx_factory, bunny, case, mutual):
+    sp, sn, tp, tn, stride = matcher_clouds(bunny, case)
+    ctx = gpu_ctx_factory()
+    configure(ctx)
+    ctx.set_target(tp, tn); ctx.set_source(sp, sn)
+    ctx.set_global_options(k=10, feature_stride=stride, mutual=mutual)
+    si, ti = ctx.match_features()
+    Fs, Ft = ctx.features("source"), ctx.features("target")
+    es, et = gr.correspondences(Fs, Ft, stride, bool(mutual))
+    assert np.array_equal(si, es) and np.array_equal(ti, et)
+    assert (np.diff(si) > 0).all()
+    if case == "1x1":
+        assert Fs.shape == (1, 33) and Ft.shape == (1, 33) and si.tolist() == [0] and ti.tolist() == [0]
+    if case == "duplicates":
+        assert np.array_equal(bits(Ft[:300]), bits(Ft[300:])) and (ti < 300).all() and len(ti) > 0
+        if mutual:                                  # (the backward match of a duplicated row is the same for both copies: the pairs survive)
+            assert len(si) > 30
+    if case == "nan_rows":
+        assert np.isnan(Fs[::7]).all() and np.isnan(Ft[::5]).all()
+        assert not np.isin(si, np.arange(0, 400, 7)).any() and not np.isin(ti, np.arange(0, 500, 5)).any() and 3 not in ti
+    if case == "full" and not mutual:
+        assert len(si) == len(sp)
+
+
+@pytest.mark.parametrize("seed", [0, 7])
+def test_ransac_teacher_forced(gpu_ctx_factory, bunny, seed):
+    from icp_amd import binding
+    ctx = gpu_ctx_factory()
+    load(ctx, bunny)
+    H = 4096
+    ctx.set_global_options(k=20, mutual=1, n_hypotheses=H, edge_similarity=0.9, inlier_distance=0.005, seed=seed, n_best=16)
+    poses, recs, rc = ctx.register_global()
+    hyp = ctx.global_hypotheses()
+    si, ti = ctx.match_features()
+    cs, ct = bunny["src_pts"][si], bunny["tgt_pts"][ti]
+    assert rc == 0 and len(hyp) == H and len(si) >= 3
+    dr = gr.draws(seed, H, len(si))
+    assert np.array_equal(hyp["draw"], dr)
+    status, rposes = gr.ransac_fit(cs, ct, dr, 0.9)
+    assert np.array_equal(hyp["status"] == gr.REPEATED, status == gr.REPEATED)
+    assert np.array_equal(hyp["status"] == gr.EDGES, status == gr.EDGES)
+    assert np.array_equal(hyp["status"], status)
+    valid = status == gr.VALID
+    assert valid.sum() > 100
+    err = np.abs(hyp["pose"][valid] - rposes[valid]).max()
+    print("seed %d: M = %d, %d valid hypotheses, max |pose - restatement| = %.3g" % (seed, len(si), valid.sum(), err))
+    assert err < POSE_TOL
+    eye = np.eye(4, dtype=np.float32).reshape(16)
+    assert (hyp["pose"][~valid] == eye).all() and (hyp["n_inliers"][~valid] == 0).all() and (hyp["sum_d2"][~valid] == 0).all()
+    n_in, sums = gr.ransac_score(hyp["pose"], hyp["status"], cs, ct, 0.005)      # scored at the DEVICE's fp32 poses
+    assert np.array_equal(hyp["n_inliers"], n_in)
+    assert np.allclose(hyp["sum_d2"], sums, rtol=1e-12, atol=0.0)
+    order = gr.ranking(hyp["status"], hyp["n_inliers"], hyp["sum_d2"])            # a host re-sort of the device's records
+    assert len(poses) == 16 and len(recs) == 16
+    assert np.array_equal(recs, hyp[order[:16]])
+    for r in range(16):
+        assert np.array_equal(binding.pose_to_c(poses[r]), hyp["pose"][order[r]])
+    poses2, recs2, _ = ctx.register_global()                                      # two runs agree bit for bit
+    assert hyp.tobytes() == ctx.global_hypotheses().tobytes() and recs.tobytes() == recs2.tobytes()
+
+
+def rigid_fit(a, b):
+    """the rigid pose taking points a onto b (fp64 Kabsch)"""
+    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
+    am, bm = a.mean(0), b.mean(0)
+    U, _, Vt = np.linalg.svd((b - bm).T @ (a - am))
+    R = U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt
+    T = np.eye(4); T[:3, :3] = R; T[:3, 3] = bm - R @ am
+    return T
+
+
+def moved_source(bunny, trial):
+    """the bunny source under the seeded motion of a trial, and the true pose that takes it onto the target"""
+    rng = np.random.default_rng(trial)
+    axis = rng.normal(size=3); angle = rng.uniform(1, 3); tr = 0.1 * rng.normal(size=3)
+    axis /= np.linalg.norm(axis)
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    R = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
+    Mv = np.eye(4); Mv[:3, :3] = R; Mv[:3, 3] = tr
+    p = (bunny["src_pts"].astype(np.float64) @ R.T + tr).astype(np.float32)
+    n = (bunny["src_nrm"].astype(np.float64) @ R.T).astype(np.float32)
+    T0 = rigid_fit(bunny["src_pts"][bunny["gt_src_idx"]], bunny["tgt_pts"][bunny["gt_tgt_idx"]])
+    return p, n, T0 @ np.linalg.inv(Mv)
+
+
+# The largest difference between globalreg.align's pose and the pose icp_run reaches from the true pose, over the four trials, as measured
+# on an MI355X (4.88e-5 / 4.88e-5 / 4.89e-5 / 4.88e-5 rad and 7.75e-6 / 5.36e-6 / 4.77e-6 / 6.31e-6 m); the test asserts 10 x these, and they must stay below 0.01 rad and 1 mm: beyond that it is another minimum.
+E2E_MEASURED_RAD, E2E_MEASURED_M = 4.89e-5, 7.75e-6
+
+
+@pytest.mark.parametrize("trial", [0, 1, 2, 3])
+def test_end_to_end_from_an_unknown_pose(gpu_ctx_factory, bunny, trial):
+    from icp_amd import globalreg
+    p, n, truth = moved_source(bunny, trial)
+    ctx = gpu_ctx_factory()
+    configure(ctx, knn_backend=1, metric=1, n_iterations=20, max_distance=0.0003)
+    ctx.set_target(bunny["tgt_pts"], bunny["tgt_nrm"]); ctx.set_source(p, n)
+    pose, results, records, best = globalreg.align(ctx, k=20, mutual=1, n_hypotheses=4096, inlier_distance=0.005, n_best=16)
+    ref, _, rc = ctx.run(truth.astype(np.float32))
+    plain, _, _ = ctx.run(np.eye(4, dtype=np.float32), check=False)
+    ang, dist = pose_error(pose, ref)
+    print("trial %d: |align - run(truth)| = %.3g rad, %.3g m; RANSAC best vs truth %s; run(truth) vs truth %s; plain icp_run from identity ends %s from run(truth)"
+          % (trial, ang, dist, "%.3g rad %.3g m" % pose_error(binding_pose(records[0]), truth), "%.3g rad %.3g m" % pose_error(ref, truth), "%.3g rad %.3g m" % pose_error(plain, ref)))
+    assert rc == 0 and len(results) == 16 and results[best]["status"] == 0
+    assert E2E_MEASURED_RAD <= 0.001 and E2E_MEASURED_M <= 0.0001          # 10 x must not exceed 0.01 rad and 1 mm
+    assert ang <= 10 * E2E_MEASURED_RAD and dist <= 10 * E2E_MEASURED_M, (ang, dist)
+
+
+def binding_pose(rec):
+    return np.asarray(rec["pose"], np.float32).reshape(4, 4).T
+
+
+def test_eth_align_with_a_global_start(gpu_ctx_factory, bunny):
+    """eth.align(initial="global"): the run starts from RANSAC's best pose instead of the identity and ends where the run from the true pose ends."""
+    from icp_amd import eth
+    p, n, truth = moved_source(bunny, 1)
+    ctx = gpu_ctx_factory()
+    configure(ctx)
+    pair = dict(src_pts=p, src_nrm=n, tgt_pts=bunny["tgt_pts"], tgt_nrm=bunny["tgt_nrm"])
+    pose, recs, rc = eth.align(ctx, pair, initial="global", k=20, inlier_distance=0.005)
+    ref, _, _ = ctx.run(truth.astype(np.float32))
+    ang, dist = pose_error(pose, ref)
+    print("eth.align(initial='global'): %.3g rad, %.3g m from run(truth)" % (ang, dist))
+    assert rc == 0 and len(recs) == 20
+    assert ang <= 10 * E2E_MEASURED_RAD and dist <= 10 * E2E_MEASURED_M, (ang, dist)
+    with pytest.raises(ValueError):
+        eth.align(ctx, pair, initial="nowhere")
+    with pytest.raises(TypeError):
+        eth.align(ctx, pair, k=20)
+
+
+def test_refusals_and_statuses(gpu_ctx_factory, bunny):
+    from icp_amd import binding
+    ctx = gpu_ctx_factory()
+    configure(ctx)
+
+    def code(fn, *a, **kw):
+        with pytest.raises(binding.IcpError) as e:
+            fn(*a, **kw)
+        return e.value.code
+    assert code(ctx.compute_features, "target") == 3 and code(ctx.features, "source") == 4           # no clouds yet
+    ctx.set_target(bunny["tgt_pts"], bunny["tgt_nrm"]); ctx.set_source(bunny["src_pts"])               # a source without normals
+    assert code(ctx.compute_features, "source") == 1 and code(ctx.compute_features, "both") == 1
+    assert code(ctx.match_features) == 1 and code(ctx.register_global) == 1
+    ctx.compute_features("target")
+    ctx.set_source(bunny["src_pts"], bunny["src_nrm"])
+    before = ctx.global_options()
+    for bad in (dict(k=7), dict(k=0), dict(feature_stride=0), dict(mutual=2), dict(n_hypotheses=0), dict(n_hypotheses=65537), dict(n_best=0), dict(n_best=257),
+                dict(edge_similarity=1.5), dict(inlier_distance=0.0), dict(inlier_distance=float("nan"))):
+        assert code(ctx.set_global_options, **bad) == 1, bad
+    after = ctx.global_options()
+    assert (before.k, before.n_hypotheses, before.n_best) == (after.k, after.n_hypotheses, after.n_best)
+    assert ctx.lib.icp_compute_features(ctx.h, 3) == 1 and ctx.lib.icp_get_features(ctx.h, 2, None, 0, None) == 1
+    # every hypothesis invalid: edge_similarity = 1 on the pairs of two different scans (no two edges have equal fp64 lengths)
+    ctx.set_global_options(k=10, edge_similarity=1.0, n_hypotheses=512)
+    poses, recs, rc = ctx.register_global(check=False)
+    hyp = ctx.global_hypotheses()
+    assert rc == binding.ERR_NO_CORRESPONDENCES and poses == [] and len(hyp) == 512
+    assert np.isin(hyp["status"], (gr.REPEATED, gr.EDGES)).all() and (hyp["status"] == gr.EDGES).sum() > 400
+    assert "no valid hypothesis" in ctx.lib.icp_last_error(ctx.h).decode()
+    # and the context still works
+    ctx.set_global_options(k=10, n_hypotheses=512)
+    poses, recs, rc = ctx.register_global()
+    assert rc == 0 and len(poses) == 16
+
+
+def test_cache_follows_the_clouds_and_the_options(gpu_ctx_factory, bunny):
+    ctx = gpu_ctx_factory()
+    load(ctx, bunny)
+    ctx.set_global_options(k=10)
+    Fa = ctx.features("source"); Ta = ctx.features("target")
+    assert np.array_equal(bits(Fa), bits(ctx.features("source")))               # served from the cache
+    sub = slice(0, 700)
+    ctx.set_source(bunny["src_pts"][sub][::-1].copy(), bunny["src_nrm"][sub][::-1].copy())
+    Fb = ctx.features("source")
+    fresh = gpu_ctx_factory()
+    configure(fresh)
+    fresh.set_target(bunny["tgt_pts"], bunny["tgt_nrm"]); fresh.set_source(bunny["src_pts"][sub][::-1].copy(), bunny["src_nrm"][sub][::-1].copy())
+    fresh.set_global_options(k=10)
+    assert Fb.shape == (700, 33) and np.array_equal(bits(Fb), bits(fresh.features("source")))
+    assert np.array_equal(bits(Ta), bits(ctx.features("target")))               # the target's stay
+    ctx.set_target(bunny["tgt_pts"][:900], bunny["tgt_nrm"][:900])
+    assert ctx.features("target").shape == (900, 33)
+    ctx.set_global_options(k=5, feature_stride=2)                              # new options: both recomputed
+    assert ctx.features("source").shape == (350, 33) and ctx.feature_neighbours("target")[0].shape == (900, 5)
+    fresh.set_global_options(k=5, feature_stride=2)
+    assert np.array_equal(bits(ctx.features("source")), bits(fresh.features("source")))
