@@ -347,6 +347,7 @@ __global__ void k_bvh_nodes(const BvhLeafT<DIM>* __restrict__ leaves, int n_leav
 // 4-wide nodes from the finished binary records.  Virtual binary depth v = real depth + pad (pad = 1 when the real depth of
 // the leaves is odd: a virtual root whose second half is empty); 4-wide node (l, idx) is virtual node (2l, idx) and stores the
 // boxes of the virtual nodes (2l + 2, 4 idx + c), each of which is a child box of a real binary record one level up.
+constexpr float BVH_QUAD_EMPTY_LO = INFINITY, BVH_QUAD_EMPTY_HI = INFINITY;      // an empty child of a 4-wide node (see k_bvh_quad_nodes)
 template <int DIM>
 __global__ void k_bvh_quad_nodes(const BvhNodeT<DIM>* __restrict__ nodes, int pad, int Lq, BvhQuadT<DIM>* __restrict__ qnodes) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -363,6 +364,13 @@ __global__ void k_bvh_quad_nodes(const BvhNodeT<DIM>* __restrict__ nodes, int pa
         const BvhNodeT<DIM>* nd = nodes + ((1 << (rd - 1)) - 1 + (ri >> 1));
 #pragma unroll
         for (int k = 0; k < DIM; k++) { lo[k] = nd->lo[k][ri & 1]; hi[k] = nd->hi[k][ri & 1]; }
+    }
+    // An empty child (beyond the last leaf, or the empty half under a virtual root) is [+inf, -inf] in the binary records, where boxes are
+    // merged with min / max.  The 4-wide nodes are only ever tested (quad_lb): there it is stored as [+inf, +inf], whose median with any
+    // finite p is +inf, so that the bound stays +inf.
+    if (lo[0] > hi[0]) {
+#pragma unroll
+        for (int k = 0; k < DIM; k++) { lo[k] = BVH_QUAD_EMPTY_LO; hi[k] = BVH_QUAD_EMPTY_HI; }
     }
 #pragma unroll
     for (int k = 0; k < DIM; k++) { qnodes[q].lo[k][c] = lo[k]; qnodes[q].hi[k][c] = hi[k]; }
@@ -396,18 +404,28 @@ __device__ __forceinline__ float sqrt_dn(float x) { return __builtin_amdgcn_sqrt
 // way b3 stays a valid (if smaller) bound.
 __device__ __forceinline__ void others_insert(float x, int xl, float& b2, int& l2, float& b3) {
     const bool better = x < b2, same = xl == l2;
-    b3 = same ? b3 : fminf(b3, better ? b2 : x);
+    // (distances are >= +0 and never NaN: the unsigned minimum of the bit patterns is the float minimum, without the canonicalising
+    //  instructions a float minimum of selected values drags in)
+    b3 = same ? b3 : __uint_as_float(min(__float_as_uint(b3), __float_as_uint(better ? b2 : x)));
     l2 = better ? xl : l2; b2 = better ? x : b2;
 }
 
 // Evaluate the 8 points of a leaf against the lane's query; exact lexicographic (d2, lowest index) update.  The leaf's non-winners
 // enter (b2, l2, b3) as ONE entry (their minimum); when the win moves here from another leaf, the dethroned winner -- the minimum of
 // the leaf it lives in, as far as this search has seen it -- enters under that leaf.
+//   The update is stated twice.  leaf_update_sequential is the definition: the strict-< scan over the 8 slots in slot order.  The walk
+// executes every step for the whole wave, and that scan is ~120 instructions around ~35 of arithmetic, so the common case takes a closed
+// form instead: exactly ONE slot is at the leaf minimum m, and it either beats the running best strictly or IS the running best (same
+// index).  Then the scan's result is: winner = that slot if m < best, and the non-winners' minimum = the minimum over the other seven
+// slots -- slots the scan took and dethroned again on its way are among those seven, and so is a running best that lives in this leaf
+// (its slot carries the bits of `best`: same query, same formula).  One min / max network yields m and the second smallest distance
+// (counted with multiplicity, so "second == m" is the tie test), the compares dd[t] == m select the slot and the index.  Any tie -- two
+// equal minima in the leaf, m == best at another index -- needs the lowest original index and takes the scan (a branch the wave skips when
+// no lane needs it).  Precondition of the closed form, which every caller meets: original indices are unique among the slots (pads: -1),
+// and a running best that lives in this leaf has the distance this evaluation computes for its slot.
+// Returns bit 0: this lane ran the winner update (m <= best), bit 1: it took the sequential scan.
 template <int DIM>
-__device__ __forceinline__ void leaf_eval(const BvhLeafT<DIM>* __restrict__ lf, int leaf, const f2* p2, float& best, int& bi, int& bpos, float& b2, int& l2, float& b3) {
-    const int prev_leaf = bpos >> 3; const float prev_best = best;
-    float dd[BVH_LEAF];
-    float m = FLT_MAX;
+__device__ __forceinline__ void leaf_distances(const BvhLeafT<DIM>* __restrict__ lf, const f2* p2, float* dd) {
 #pragma unroll
     for (int t = 0; t < BVH_LEAF; t += 2) {
         f2 d;
@@ -419,23 +437,81 @@ __device__ __forceinline__ void leaf_eval(const BvhLeafT<DIM>* __restrict__ lf, 
             d = (k == 0) ? sq : d + sq;
         }
         dd[t] = d.x; dd[t + 1] = d.y;
-        m = fminf(fminf(m, d.x), d.y);
     }
-    if (m <= best) {                     // something in this leaf ties or beats the running best (or IS the running best)
-        float mo = FLT_MAX;              // smallest distance among this leaf's points that do not end up as the winner
-        bool here = prev_leaf == leaf;   // the running winner lives in this leaf
+}
+template <int DIM>
+__device__ __forceinline__ void leaf_update_sequential(const BvhLeafT<DIM>* __restrict__ lf, int leaf, const f2* p2, bool here, float& best, int& bi, int& bpos, float& mo) {
+    // (The distances are computed once more, two slots at a time, each pair behind a barrier the compiler cannot schedule across: kept
+    //  from the closed form's, or loaded all at once, they cost the fused matchers registers they do not have -- and this path is rare.)
+    mo = FLT_MAX;                        // smallest distance among this leaf's points that do not end up as the winner
 #pragma unroll
-        for (int t = 0; t < BVH_LEAF; t++) {
-            const int j = lf->idx[t];
-            const bool take = (dd[t] < best) | ((dd[t] == best) & (j < bi));     // first minimum = lowest original index
-            const float other = take ? (here ? best : FLT_MAX) : ((j != bi) ? dd[t] : FLT_MAX);      // a winner of this leaf dethroned by a later one, or a plain non-winner
+    for (int t = 0; t < BVH_LEAF; t += 2) {
+        asm volatile("" : "+v"(mo), "+v"(best), "+v"(lf));
+        f2 d;
+#pragma unroll
+        for (int k = 0; k < DIM; k++) {
+            const f2 q = *(const f2*)(&lf->c[k][t]);
+            const f2 e = p2[k] - q;
+            const f2 sq = e * e;
+            d = (k == 0) ? sq : d + sq;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const float du = u ? d.y : d.x;
+            const int j = lf->idx[t + u];
+            const bool take = (du < best) | ((du == best) & (j < bi));     // first minimum = lowest original index
+            const float other = take ? (here ? best : FLT_MAX) : ((j != bi) ? du : FLT_MAX);      // a winner of this leaf dethroned by a later one, or a plain non-winner
             mo = fminf(mo, other);
             here = here | take;
-            best = take ? dd[t] : best; bi = take ? j : bi; bpos = take ? leaf * BVH_LEAF + t : bpos;
+            best = take ? du : best; bi = take ? j : bi; bpos = take ? leaf * BVH_LEAF + t + u : bpos;
         }
-        others_insert(mo, leaf, b2, l2, b3);
-        if (prev_leaf != leaf && (bpos >> 3) == leaf) others_insert(prev_best, prev_leaf, b2, l2, b3);      // the win moved here (an unseeded start enters (FLT_MAX, -1): nothing)
-    } else others_insert(m, leaf, b2, l2, b3);      // nobody here can win: all 8 are "others"
+    }
+}
+template <int DIM>
+__device__ __forceinline__ int leaf_eval(const BvhLeafT<DIM>* __restrict__ lf, int leaf, const f2* p2, float& best, int& bi, int& bpos, float& b2, int& l2, float& b3) {
+    const int prev_leaf = bpos >> 3; const float prev_best = best;
+    float dd[BVH_LEAF];
+    leaf_distances<DIM>(lf, p2, dd);
+    // the smallest of the 8, by threes
+    const float lo0 = fminf(fminf(dd[0], dd[1]), dd[2]), lo1 = fminf(fminf(dd[3], dd[4]), dd[5]), lo2 = fminf(dd[6], dd[7]);
+    const float m1 = fminf(fminf(lo0, lo1), lo2);
+    const float m = fminf(m1, FLT_MAX);
+    float x = m;                         // what this leaf's non-winners enter with; nobody here can win: all 8 are "others"
+    bool moved = false, scan = false;
+    int flags = 0;
+    if (m <= best) {                     // something in this leaf ties or beats the running best (or IS the running best)
+        flags = 1;
+        bool e[BVH_LEAF];
+#pragma unroll
+        for (int t = 1; t < BVH_LEAF; t++) e[t] = dd[t] == m1;
+        // the slot at the minimum, from the compare masks (slot 0 when none of the others is); its index is ONE load from the line the
+        // coordinates came from, where the scan holds all eight
+        const int ts = ((e[1] | e[3] | e[5] | e[7]) ? 1 : 0) | ((e[2] | e[3] | e[6] | e[7]) ? 2 : 0) | ((e[4] | e[5] | e[6] | e[7]) ? 4 : 0);
+        const int js = lf->idx[ts];
+        // the second smallest of the 8, counted with multiplicity (a second slot at the minimum: m2 == m1).  Of two groups with smallest
+        // and second smallest (la, ha), (lb, hb) the second smallest of the union is the median of la, lb and min(ha, hb).  (Minimum and
+        // maximum of two spelled as medians with -inf / +inf, which the compiler may turn back as it sees fit.  Measured at compile
+        // time: adding slots 6 and 7 one by one, without the maximum, is two instructions shorter and costs k_knn_bvh_post_ring<6, true>
+        // four registers, 98 against a budget of 96.)
+        const float hi0 = __builtin_amdgcn_fmed3f(dd[0], dd[1], dd[2]), hi1 = __builtin_amdgcn_fmed3f(dd[3], dd[4], dd[5]), hi2 = __builtin_amdgcn_fmed3f(dd[6], dd[7], INFINITY);
+        const float lo01 = __builtin_amdgcn_fmed3f(lo0, lo1, -INFINITY), hi01 = __builtin_amdgcn_fmed3f(lo0, lo1, __builtin_amdgcn_fmed3f(hi0, hi1, -INFINITY));
+        const float m2 = __builtin_amdgcn_fmed3f(lo01, lo2, __builtin_amdgcn_fmed3f(hi01, hi2, -INFINITY));
+        const bool lt = m < best;
+        scan = !((m2 > m1) & (lt | (js == bi)));     // (all 8 at +inf: m2 == m1, the scan)
+        if (!scan) {
+            x = __uint_as_float(min(__float_as_uint(m2), __float_as_uint(FLT_MAX)));      // min(m2, FLT_MAX) (see others_insert)
+            moved = lt & (prev_leaf != leaf);
+            best = lt ? m : best; bi = lt ? js : bi; bpos = lt ? leaf * BVH_LEAF + ts : bpos;
+        }
+    }
+    if (scan) {
+        flags = 3;
+        leaf_update_sequential<DIM>(lf, leaf, p2, prev_leaf == leaf, best, bi, bpos, x);
+        moved = prev_leaf != leaf && (bpos >> 3) == leaf;
+    }
+    others_insert(x, leaf, b2, l2, b3);
+    if (moved) others_insert(prev_best, prev_leaf, b2, l2, b3);      // the win moved here (an unseeded start enters (FLT_MAX, -1): nothing)
+    return flags;
 }
 
 // Temporal seeding: ICP moves the queries a little per iteration, so the previous iteration's neighbour j0 is a
@@ -488,9 +564,12 @@ __device__ __forceinline__ void quad_lb(const BvhQuadT<DIM>* __restrict__ nd, co
 #pragma unroll
     for (int k = 0; k < DIM; k++) {
         const f2 lo0 = *(const f2*)&nd->lo[k][0], lo1 = *(const f2*)&nd->lo[k][2], hi0 = *(const f2*)&nd->hi[k][0], hi1 = *(const f2*)&nd->hi[k][2];
-        const f2 a0 = lo0 - p2[k], b0 = p2[k] - hi0, a1 = lo1 - p2[k], b1 = p2[k] - hi1;
-        const f2 e0 = {fmaxf(fmaxf(a0.x, b0.x), 0.f), fmaxf(fmaxf(a0.y, b0.y), 0.f)};
-        const f2 e1 = {fmaxf(fmaxf(a1.x, b1.x), 0.f), fmaxf(fmaxf(a1.y, b1.y), 0.f)};
+        // e = p - median(p, lo, hi): where lo <= hi that is p - lo, p - hi or p - p = 0 -- the magnitude max(max(lo - p, p - hi), 0) has, from
+        // the same subtraction of the same operands, so the square and the bound are the same to the bit; one median and one packed
+        // subtraction per pair instead of two packed subtractions and two three-way maxima.  (An empty child: see BVH_QUAD_EMPTY_HI.)
+        const f2 c0 = {__builtin_amdgcn_fmed3f(p2[k].x, lo0.x, hi0.x), __builtin_amdgcn_fmed3f(p2[k].y, lo0.y, hi0.y)};
+        const f2 c1 = {__builtin_amdgcn_fmed3f(p2[k].x, lo1.x, hi1.x), __builtin_amdgcn_fmed3f(p2[k].y, lo1.y, hi1.y)};
+        const f2 e0 = p2[k] - c0, e1 = p2[k] - c1;
         const f2 s0 = e0 * e0, s1 = e1 * e1;
         l01 = (k == 0) ? s0 : l01 + s0;
         l23 = (k == 0) ? s1 : l23 + s1;
@@ -649,8 +728,14 @@ __device__ unsigned int g_dev_counts[16];   // development builds: 8-10 walk end
 #define ICP_DEBUG_WALK_TRACE 0
 #endif
 __device__ unsigned int g_walk_trace[64];   // ICP_DEBUG_WALK_TRACE: the last sparse walk (<= 3 walkers in the wave: spread start) of the launch: 0 walkers, 1 paths per walker, 2 clock at entry, 3 after the spread, 4 passes, 5 polls, 6 clock at exit, 8.. clock at the top of every pass (tools/dev_walk_trace.py)
+// The walk's budget: how many times a WAVE executes each step of knn_walk_shared in one launch (0 node steps, 1 leaf evaluations, 2 leaf
+// winner updates, 3 sequential leaf scans, 4 hand-over rounds, 5 folds, 6 board posts and claims, 7 passes of the outer loop).  A step
+// counts once however many lanes take part: the first active lane counts, the lanes' counts are summed when the walk ends and go to the
+// wave's budget row behind the time stamps in dbg_steps (tools/dev_walk_budget.py).
+#define WALK_BUDGET(i) do { if (lane == (int)__ffsll((long long)__ballot(true)) - 1) bud[i]++; } while (0)
 #else
 #define DEV_COUNT(i, n)
+#define WALK_BUDGET(i)
 #endif
 constexpr int XW_INTS = XW_CTRL + XW_SLOTS + XW_SLOTS * 5;      // control words, slot states, items (2 x uint2 + int per slot)
 constexpr int XW_SPIN_LIMIT = 1 << 22;                   // polls of an idle wave (~0.3 us each) before it gives up and raises the fault word
@@ -669,8 +754,12 @@ template <int NT> __device__ __forceinline__ bool xw_block_is_searching(uint2* l
 // waits for parts of them that other waves hold); 2: XW, help only (xw_help: no queries of its own, rows 3.. of the wave untouched).
 template <int DIM, int NT, class MaskT, int MODE = 0>
 __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* p, float* keep3, bool need_walk, float& best, int& bi, int& bpos, float& lb_others, float& lb3, int& l2o,
-                                                uint2* __restrict__ lbq, int tid, int* fault = nullptr) {
+                                                uint2* __restrict__ lbq, int tid, int* fault = nullptr, int* budget = nullptr) {
     constexpr bool XW = MODE == 1 || MODE == 2, HELP = MODE == 2;
+#if ICP_DEBUG_TIMES
+    int bud[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    (void)budget;
     static_assert(!XW || xw_enabled<DIM, NT>(), "cross-wave sharing: DIM 3, 2..8 waves per block");
     const int lane = tid & 63, Lq = bv.Lq, wbase = tid & ~63, myw = tid >> 6;
     uint2* R = lbq + wbase;                                               // this wave's columns of the rows
@@ -741,6 +830,7 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
             const int n = act ? tbl[lane >> 2] : 0, j = lane & 3;
             f2 a01, a23;
             quad_lb_at<DIM>(bv, (0x55555555u & ((1u << (2 * L)) - 1u)) + (unsigned int)n, lq, a01, a23);
+            WALK_BUDGET(0);
             const float lbj = j == 0 ? a01.x : j == 1 ? a01.y : j == 2 ? a23.x : a23.y;
             const bool alive = act && !(lbj > thr_u);
             if (act && !alive) lmlb = min(lmlb, __float_as_uint(lbj));
@@ -771,8 +861,10 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
             if (lane < nf) {
                 const int leaf = tbl[lane];
                 float xb = sb, x2 = FLT_MAX, x3 = FLT_MAX; int xi = si, xp = sp, xl = -1;
-                leaf_eval<DIM>(bv.leaves + leaf, leaf, lq.p2, xb, xi, xp, x2, xl, x3);
+                const int fl = leaf_eval<DIM>(bv.leaves + leaf, leaf, lq.p2, xb, xi, xp, x2, xl, x3); (void)fl;
+                WALK_BUDGET(1); if (fl & 1) WALK_BUDGET(2); if (fl & 2) WALK_BUDGET(3);
                 fold_part(wbase + wl, xb, xi, xp, x2, xl, x3, lmlb);
+                WALK_BUDGET(5);
             } else __hip_atomic_fetch_min((unsigned int*)(lbq + 6 * NT + wbase) + WAVE + wl, lmlb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             // (XW: the wave has not registered as searching -- it neither offers nor needs help)
             lone_done = true;
@@ -783,8 +875,8 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
     }
     QueryPt<DIM> qp;
     float wb; int wi, wp;
-    if constexpr (DIM == 3 && MODE == 1 && sizeof(MaskT) == 4) {
-        // (read back from the rows written above rather than kept in registers across the lone walker's search: six registers of the budget)
+    if constexpr (DIM == 3 && MODE == 1) {
+        // (read back from the rows written above rather than kept in registers across the lone walker's search and the walk: six registers of the budget)
         const uint2 ra_ = R[3 * NT + lane], rb_ = R[4 * NT + lane], rc_ = R[5 * NT + lane], rd_ = R[7 * NT + lane];
         float pq[3] = {__uint_as_float(rc_.y), __uint_as_float(rd_.x), __uint_as_float(rd_.y)};
         make_query<DIM>(bv, pq, qp);
@@ -802,12 +894,14 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
             for (int L = 0; L < Lq; L++) {
                 f2 l01, l23;
                 quad_lb_at<DIM>(bv, (0x55555555u & ((1u << (2 * L)) - 1u)) + (unsigned int)idx, qp, l01, l23);
+                WALK_BUDGET(0);
                 const float m = fminf(fminf(l01.x, l01.y), fminf(l23.x, l23.y));
                 const int c = (l01.x == m) ? 0 : (l01.y == m) ? 1 : (l23.x == m) ? 2 : 3;
                 idx = (idx << 2) | c;
             }
             float u2 = FLT_MAX, u3 = FLT_MAX; int ul = -1;
-            leaf_eval<DIM>(bv.leaves + idx, idx, qp.p2, wb, wi, wp, u2, ul, u3);
+            const int fl = leaf_eval<DIM>(bv.leaves + idx, idx, qp.p2, wb, wi, wp, u2, ul, u3); (void)fl;
+            WALK_BUDGET(1); if (fl & 1) WALK_BUDGET(2); if (fl & 2) WALK_BUDGET(3);
         }
     }
     // Few walkers, all with a seed: the seed's root-to-leaf path is known, so its Lq nodes need not be visited one after the other.
@@ -833,14 +927,15 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
     float thr = fminf(wb * ICP_PRUNE_SLACK, FLT_MAX);
     // one node step on the child bounds of node (st.L, st.idx): nearest surviving child next, the other survivors parked
     auto descend = [&](const f2& l01, const f2& l23) {
-        const float m = fminf(fminf(l01.x, l01.y), fminf(l23.x, l23.y));
         const bool s0 = !(l01.x > thr), s1 = !(l01.y > thr), s2 = !(l23.x > thr), s3 = !(l23.y > thr);
         mlb = min(min(mlb, min(s0 ? NONE : __float_as_uint(l01.x), s1 ? NONE : __float_as_uint(l01.y))), min(s2 ? NONE : __float_as_uint(l23.x), s3 ? NONE : __float_as_uint(l23.y)));
-        if (!(m > thr)) {
+        if (s0 | s1 | s2 | s3) {                           // (the nearest child survives iff any does: the survive masks, no compare of its own)
             // nearest child first (selects, not branches).  Measured: taking the survivors in index order instead saves 5 instructions
             // per node and costs 0.080 -> 0.096 ms in iterations 1-9 (0.17 -> 0.80 ms unseeded): the order is worth its price.
-            const bool c0 = l01.x == m, c1 = l01.y == m, c2 = l23.x == m;
-            int c = 3; c = c2 ? 2 : c; c = c1 ? 1 : c; c = c0 ? 0 : c;
+            // (a tournament on strict compares: the lowest child number among equal bounds, as a scan for the minimum would give)
+            const bool c01 = l01.y < l01.x, c23 = l23.y < l23.x;
+            const float m01 = c01 ? l01.y : l01.x, m23 = c23 ? l23.y : l23.x;
+            const int c = (m23 < m01) ? (c23 ? 3 : 2) : (c01 ? 1 : 0);
             const unsigned int pend = ((s0 ? 1u : 0u) | (s1 ? 2u : 0u) | (s2 ? 4u : 0u) | (s3 ? 8u : 0u)) & ~(1u << c);
             st.pending |= (MaskT)pend << (4 * st.L);
             st.idx = (st.idx << 2) | c; st.L++;
@@ -893,6 +988,7 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
                 l01.x = (skip == 0 || skipB == 0) ? inf : l01.x; l01.y = (skip == 1 || skipB == 1) ? inf : l01.y;
                 l23.x = (skip == 2 || skipB == 2) ? inf : l23.x; l23.y = (skip == 3 || skipB == 3) ? inf : l23.y;
                 descend(l01, l23);
+                WALK_BUDGET(0);
             }                                                                 // (role 2 Lq: leaf B, evaluated by the loop below like any adopted leaf)
         }
         if (need_walk) { st.L = Lq; st.idx = wp >> 3; }                   // the walker itself: straight to the seed's leaf
@@ -910,7 +1006,9 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
         trips++;
         if (tracer && trips < 56) g_walk_trace[7 + trips] = (unsigned int)wall_clock64();
 #endif
+        WALK_BUDGET(7);
         if (!st.alive && owner >= 0) {
+            WALK_BUDGET(5);
             // this lane's (part of the) search is over: fold it into the owner's record.  Winner: 64-bit minimum of (distance, index).
             // Runner-up entry (distance, leaf): 64-bit minimum as well; whatever loses there -- and is not in the same leaf as what beat
             // it: such a point is bounded by that entry for as long as it stands, and by its distance in the rest once it falls -- goes to
@@ -930,6 +1028,7 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
             bool mine = false;
             if (sv == 1) { int expect = 1; mine = __hip_atomic_compare_exchange_strong(xstate + lane, &expect, 3, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
             if (mine) {
+                WALK_BUDGET(6);
                 const uint2 ia = xa[lane], ib = xb[lane]; const int ip = xp[lane];
                 __hip_atomic_store(xstate + lane, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 owner = (int)(ia.x & 0xFFFFu);
@@ -965,6 +1064,7 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
             const unsigned long long dm = __ballot(can);
             served = __popcll(im) <= __popcll(dm);
             if (!dm) break;
+            WALK_BUDGET(4);
             {
                 const int n = min(__popcll(im), __popcll(dm));
                 int* tbl = (int*)(R + 6 * NT);
@@ -1003,6 +1103,7 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
             const bool can = st.alive && st.pending != 0;
             const unsigned long long dm = __ballot(can);
             if (dm) {
+                WALK_BUDGET(6);
                 const int sv = __hip_atomic_load(xstate + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 const unsigned long long fm = __ballot(sv == 0);
                 const int n = min(__popcll(dm), __popcll(fm));
@@ -1031,13 +1132,15 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
             f2 l01, l23;
             quad_lb_at<DIM>(bv, (0x55555555u & ((1u << (2 * st.L)) - 1u)) + (unsigned int)st.idx, qp, l01, l23);
             descend(l01, l23);
+            WALK_BUDGET(0);
             // Back to the hand-over as soon as it has something to do: while every idle lane found work last time (lanes are what is
             // scarce) when a lane runs out of work; otherwise (lanes idle, parked subtrees scarce) when a lane parks one.  Measured against
             // handing over only between leaves: iteration 0 0.142 -> 0.126 ms, iterations 1-9 0.065 -> 0.061, 10-16 0.033 -> 0.028.
             if (served ? __any(!st.alive) : __any(st.pending != 0)) break;
         }
         if (st.alive && st.L == Lq) {                                      // (a lane that left the loop above early is still at a node)
-            leaf_eval<DIM>(bv.leaves + st.idx, st.idx, qp.p2, wb, wi, wp, b2, l2, b3);
+            const int fl = leaf_eval<DIM>(bv.leaves + st.idx, st.idx, qp.p2, wb, wi, wp, b2, l2, b3); (void)fl;
+            WALK_BUDGET(1); if (fl & 1) WALK_BUDGET(2); if (fl & 2) WALK_BUDGET(3);
             thr = fminf(wb * ICP_PRUNE_SLACK, FLT_MAX);
             st.alive = false;
             quad_pop_bits(st);
@@ -1050,6 +1153,16 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
     // (An empty asm reading a zero VGPR, left by the set-aside path prefetch.  Dropping it changes the walk kernels' code: a change to
     //  measure on its own.)
     asm volatile("" ::"v"(0u));
+#if ICP_DEBUG_TIMES
+    if (budget) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            int v = bud[i];
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
+            if (lane == 0 && v) atomicAdd(budget + i, v);
+        }
+    }
+#endif
     if (HELP) return;
     {
         const uint2 c = R[5 * NT + lane], d = R[7 * NT + lane], e = R[8 * NT + lane], f = R[9 * NT + lane];
@@ -1083,11 +1196,11 @@ __device__ __forceinline__ void knn_walk_shared(const BvhViewT<DIM>& bv, float* 
 // XW, a wave that has nothing of its own left to do (its pairs are weighed, only the block's sums remain): help the block's other waves
 // until every wave that searched is complete.  The wave's rows 3.. are not touched (the caller parks its pair there).
 template <int DIM, int NT, class MaskT>
-__device__ __forceinline__ void xw_help(const BvhViewT<DIM>& bv, uint2* __restrict__ lbq, int tid, int* fault) {
+__device__ __forceinline__ void xw_help(const BvhViewT<DIM>& bv, uint2* __restrict__ lbq, int tid, int* fault, int* budget = nullptr) {
     float p[DIM], k3[3] = {0.f, 0.f, 0.f}, best = FLT_MAX, lbo = 0.f, lb3 = 0.f; int bi = -1, bpos = -1, l2 = -1;
 #pragma unroll
     for (int q = 0; q < DIM; q++) p[q] = 0.f;
-    knn_walk_shared<DIM, NT, MaskT, 2>(bv, p, k3, false, best, bi, bpos, lbo, lb3, l2, lbq, tid, fault);
+    knn_walk_shared<DIM, NT, MaskT, 2>(bv, p, k3, false, best, bi, bpos, lbo, lb3, l2, lbq, tid, fault, budget);
 }
 
 // One query per lane (k < 0: none), the whole wave together: the lanes without a walk of their own help with the others'.

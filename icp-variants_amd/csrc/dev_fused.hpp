@@ -47,8 +47,11 @@ struct P2pGen {                                           // values 0..21 = sum 
 #endif
 #if ICP_DEBUG_TIMES
 #define ICP_STAMP(j) do { if (kp.dbg_steps && lane == 0) kp.dbg_steps[8 * (wave_slot) + (j)] = (int)(unsigned int)wall_clock64(); } while (0)
+// (the wave's row of the walk's budget, WALK_BUDGET in dev_bvh.hpp: behind the time stamps and the 4096 per-query records, where the buffer has room)
+#define ICP_BUDGET_ROW(slot) ((kp.dbg_steps && 16 * kp.dbg_waves + 8 * 4096 <= kp.n) ? kp.dbg_steps + 8 * kp.dbg_waves + 8 * 4096 + 8 * (slot) : nullptr)
 #else
 #define ICP_STAMP(j)
+#define ICP_BUDGET_ROW(slot) nullptr
 #endif
 
 // What a query brings along that does not depend on the pose: requested in ONE batch (point, normal, previous neighbour, search
@@ -178,8 +181,19 @@ __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const Bvh
         for (int q = 0; q < DIM; q++) { p2[q].x = p[q]; p2[q].y = p[q]; }
         float b2 = FLT_MAX, b3 = FLT_MAX; int nl2 = -1;
         const int lf = q0 >> 3;
-        leaf_eval<DIM>(bv.leaves + lf, lf, p2, best, bi, bpos, b2, nl2, b3);      // exact argmin over the two leaves, seeded with the old neighbour
-        if (l2 >= 0 && l2 != lf) leaf_eval<DIM>(bv.leaves + l2, l2, p2, best, bi, bpos, b2, nl2, b3);
+        // exact argmin over the two leaves, seeded with the old neighbour.  (DIM 3: one copy of leaf_eval in a rolled loop of two trips --
+        //  two copies in a row, each with its rare sequential scan, cost k_knn_bvh_post_multi<3, true> three registers it does not have;
+        //  the 6-D matchers are the other way round, 98 against 94 registers.)
+        if constexpr (DIM == 3) {
+#pragma unroll 1
+            for (int r = 0; r < 2; r++) {
+                const int lx = r ? l2 : lf;
+                if (r == 0 || (l2 >= 0 && l2 != lf)) leaf_eval<DIM>(bv.leaves + lx, lx, p2, best, bi, bpos, b2, nl2, b3);
+            }
+        } else {
+            leaf_eval<DIM>(bv.leaves + lf, lf, p2, best, bi, bpos, b2, nl2, b3);
+            if (l2 >= 0 && l2 != lf) leaf_eval<DIM>(bv.leaves + l2, l2, p2, best, bi, bpos, b2, nl2, b3);
+        }
         lb_others = fminf(sqrt_dn(b2), lb3);                             // re-anchored here: the runner-up among the 16, or anything outside the two leaves
         lb3 = fminf(sqrt_dn(b3), lb3);
         l2 = nl2;
@@ -192,11 +206,14 @@ __device__ __forceinline__ void fused_search_post(const KnnParams& kp, const Bvh
 #if ICP_DEBUG_STEPS && !ICP_DEBUG_TIMES
     if (k >= 0 && kp.dbg_steps) kp.dbg_steps[k] = need_walk ? -1 : two_leaf ? -2 : 0;      // -1: walk; -2: second tier, two leaves
 #endif
+#if ICP_DEBUG_TIMES
+    if (int* row = ICP_BUDGET_ROW(wave_slot)) { if (lane < 8) row[lane] = 0; }      // (this launch's counts: the walk and xw_help add to it)
+#endif
     bool walked = false;                                  // wave-uniform: this wave's lanes searched (or helped): their neighbours' records are read again
     if (__any(need_walk)) {
         walked = true;
         float rn[3] = {rn0, rn1, rn2};
-        knn_walk_shared<DIM, BVH_THREADS, typename std::conditional<WIDE, unsigned long long, unsigned int>::type, XW ? 1 : 0>(bv, p, rn, need_walk, best, bi, bpos, lb_others, lb3, l2, bvh_lbq, tid, kp.fault);
+        knn_walk_shared<DIM, BVH_THREADS, typename std::conditional<WIDE, unsigned long long, unsigned int>::type, XW ? 1 : 0>(bv, p, rn, need_walk, best, bi, bpos, lb_others, lb3, l2, bvh_lbq, tid, kp.fault, ICP_BUDGET_ROW(wave_slot));
         rn0 = rn[0]; rn1 = rn[1]; rn2 = rn[2];
         q0 = -2;                                          // the neighbour's record is read again below: it need not stay in registers while this lane helps
         // (nothing of `in` is read after the walk -- said here in a way the register allocator can see, so that none of it stays alive
@@ -326,7 +343,7 @@ __device__ __forceinline__ void fused_matcher_body(const KnnParams& kp, const Bv
             bvh_lbq[3 * NT + tid] = make_uint2(__float_as_uint(o.s0), __float_as_uint(o.s1)); bvh_lbq[4 * NT + tid] = make_uint2(__float_as_uint(o.s2), __float_as_uint(o.d0));
             bvh_lbq[5 * NT + tid] = make_uint2(__float_as_uint(o.d1), __float_as_uint(o.d2)); bvh_lbq[7 * NT + tid] = make_uint2(__float_as_uint(o.n0), __float_as_uint(o.n1));
             bvh_lbq[8 * NT + tid] = make_uint2(__float_as_uint(o.n2), __float_as_uint(o.wt)); bvh_lbq[9 * NT + tid] = make_uint2(o.valid ? 1u : 0u, 0u);
-            xw_help<DIM, NT, typename std::conditional<WIDE, unsigned long long, unsigned int>::type>(bv, bvh_lbq, tid, kp.fault);
+            xw_help<DIM, NT, typename std::conditional<WIDE, unsigned long long, unsigned int>::type>(bv, bvh_lbq, tid, kp.fault, ICP_BUDGET_ROW(wave_slot));
             const uint2 a = bvh_lbq[3 * NT + tid], b = bvh_lbq[4 * NT + tid], c = bvh_lbq[5 * NT + tid], d = bvh_lbq[7 * NT + tid], e = bvh_lbq[8 * NT + tid], f = bvh_lbq[9 * NT + tid];
             o.s0 = __uint_as_float(a.x); o.s1 = __uint_as_float(a.y); o.s2 = __uint_as_float(b.x); o.d0 = __uint_as_float(b.y); o.d1 = __uint_as_float(c.x); o.d2 = __uint_as_float(c.y);
             o.n0 = __uint_as_float(d.x); o.n1 = __uint_as_float(d.y); o.n2 = __uint_as_float(e.x); o.wt = __uint_as_float(e.y); o.valid = f.x != 0u;

@@ -92,6 +92,70 @@ int icp_debug_poison_handover(icp_ctx* c, int32_t slot, double value) {
     return ICP_OK;
 }
 
+//   icp_debug_walk_steps      : the two steps of the shared walk on the caller's arrays, one lane per item, with the device functions the
+//                               matchers run (dev_bvh.hpp: leaf_eval<3>, quad_lb<3>).  Leaves and nodes are 128-byte records in the layouts
+//                               of BvhLeafT<3> / BvhQuadT<3>.  Per leaf: query lq[3], leaf number, state in (best, b2, b3 | bi, bpos, l2) ->
+//                               state out in the same order, and leaf_eval's flags (bit 0: winner update, bit 1: sequential scan).  Per
+//                               node: query nq[3] -> the four child bounds.  empty_box[2] receives (lo, hi) of an empty child as
+//                               k_bvh_quad_nodes stores it.  tests/test_gpu_walk_steps.py compares all of it bitwise with NumPy.
+__global__ void k_debug_walk_steps(int n_leaves, const icpdev::BvhLeafT<3>* leaves, const float* lq, const int* leaf_no, const float* sf, const int* si, float* of, int* oi,
+                                   int n_nodes, const icpdev::BvhQuadT<3>* nodes, const float* nq, float* bounds) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_leaves) {
+        icpdev::f2 p2[3];
+        for (int k = 0; k < 3; k++) { p2[k].x = lq[3 * i + k]; p2[k].y = p2[k].x; }
+        float best = sf[3 * i], b2 = sf[3 * i + 1], b3 = sf[3 * i + 2]; int bi = si[3 * i], bpos = si[3 * i + 1], l2 = si[3 * i + 2];
+        const int flags = icpdev::leaf_eval<3>(leaves + i, leaf_no[i], p2, best, bi, bpos, b2, l2, b3);
+        of[3 * i] = best; of[3 * i + 1] = b2; of[3 * i + 2] = b3; oi[4 * i] = bi; oi[4 * i + 1] = bpos; oi[4 * i + 2] = l2; oi[4 * i + 3] = flags;
+    }
+    if (i < n_nodes) {
+        icpdev::f2 p2[3], l01, l23;
+        for (int k = 0; k < 3; k++) { p2[k].x = nq[3 * i + k]; p2[k].y = p2[k].x; }
+        icpdev::quad_lb<3>(nodes + i, p2, l01, l23);
+        bounds[4 * i] = l01.x; bounds[4 * i + 1] = l01.y; bounds[4 * i + 2] = l23.x; bounds[4 * i + 3] = l23.y;
+    }
+}
+int icp_debug_walk_steps(icp_ctx* c, int32_t n_leaves, const void* leaves, const float* lq, const int32_t* leaf_no, const float* sf, const int32_t* si, float* of, int32_t* oi,
+                         int32_t n_nodes, const void* nodes, const float* nq, float* bounds, float* empty_box) {
+    if (!c || n_leaves < 0 || n_nodes < 0 || n_leaves > (1 << 20) || n_nodes > (1 << 20)) return ICP_ERR_INVALID_ARG;
+    if (n_leaves > 0 && (!leaves || !lq || !leaf_no || !sf || !si || !of || !oi)) return ICP_ERR_INVALID_ARG;
+    if (n_nodes > 0 && (!nodes || !nq || !bounds)) return ICP_ERR_INVALID_ARG;
+    if (empty_box) { empty_box[0] = icpdev::BVH_QUAD_EMPTY_LO; empty_box[1] = icpdev::BVH_QUAD_EMPTY_HI; }
+    const int n = n_leaves > n_nodes ? n_leaves : n_nodes;
+    if (n == 0) return ICP_OK;
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    DrainOnError guard(c);
+    // one staging area: inputs (leaves, lq, leaf_no, sf, si, nodes, nq), then outputs (of, oi, bounds)
+    const size_t L = (size_t)n_leaves, N = (size_t)n_nodes;
+    auto up = [](size_t x) { return (x + 127) & ~(size_t)127; };      // (every section on a 128-byte line, as the records are in the tree)
+    const size_t o_lq = 128 * L, o_no = up(o_lq + 12 * L), o_sf = up(o_no + 4 * L), o_si = up(o_sf + 12 * L), o_nd = up(o_si + 12 * L), o_nq = o_nd + 128 * N, o_of = up(o_nq + 12 * N),
+                 o_oi = up(o_of + 12 * L), o_bd = up(o_oi + 16 * L), total = o_bd + 16 * N;
+    if ((rc = ensure(c, c->staging, total))) return rc;
+    char* d = c->staging.as<char>();
+    if (L) {
+        HIPCK(c, hipMemcpyAsync(d, leaves, 128 * L, hipMemcpyHostToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(d + o_lq, lq, 12 * L, hipMemcpyHostToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(d + o_no, leaf_no, 4 * L, hipMemcpyHostToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(d + o_sf, sf, 12 * L, hipMemcpyHostToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(d + o_si, si, 12 * L, hipMemcpyHostToDevice, c->stream));
+    }
+    if (N) {
+        HIPCK(c, hipMemcpyAsync(d + o_nd, nodes, 128 * N, hipMemcpyHostToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(d + o_nq, nq, 12 * N, hipMemcpyHostToDevice, c->stream));
+    }
+    hipLaunchKernelGGL(k_debug_walk_steps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n_leaves, (const icpdev::BvhLeafT<3>*)d, (const float*)(d + o_lq), (const int*)(d + o_no),
+                       (const float*)(d + o_sf), (const int*)(d + o_si), (float*)(d + o_of), (int*)(d + o_oi), n_nodes, (const icpdev::BvhQuadT<3>*)(d + o_nd), (const float*)(d + o_nq), (float*)(d + o_bd));
+    HIPCK(c, hipGetLastError());
+    if (L) {
+        HIPCK(c, hipMemcpyAsync(of, d + o_of, 12 * L, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipMemcpyAsync(oi, d + o_oi, 16 * L, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (N) HIPCK(c, hipMemcpyAsync(bounds, d + o_bd, 16 * N, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+
 // ---- hardware self test (not part of icp_hip.h; called by tests/ through ctypes) ------------------------------------------
 // One wave folds n_values (<= 32) doubles per lane with wave_transpose_reduce_gen; out[v] = the wave total of value v read from
 // the lane wave_value_of_lane says holds it.  tests/test_gpu_selftest.py replays the same pairing with numpy: bit-identical.
