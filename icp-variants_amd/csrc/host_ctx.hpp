@@ -79,6 +79,11 @@ struct icp_ctx {
     icp_robust_options rob_opt = {ICP_ROBUST_NONE, 0.f, 0.f, 1.f};   // icp_set_robust_options
     DevBuf rob_keys, rob_state, rob_stats;      // trimmed / robust mode (dev_robust.hpp): r^2 keys per query, the chain's state, per-iteration records
     std::vector<icp_robust_stats> rob_last;      // the records of the last call (icp_get_robust_stats)
+    icp_reciprocal_options rcp_opt = {0};        // icp_set_reciprocal_options: mutual nearest-neighbour rejection (dev_reciprocal.hpp)
+    Bvh src_bvh; DevBuf src_rflag, src_finite;   // its reverse index: the BVH over the resident source (built on first use, dropped with the source), finite flags and list
+    DevBuf rcp_stats;                            // per-iteration records of the run in flight
+    bool rcp_naive = false; DevBuf rcp_q[3], rcp_nn;   // icp_debug_reciprocal_naive (tools/time_reciprocal.py): the reverse test as a full search of a written-out query cloud
+    std::vector<icp_reciprocal_stats> rcp_last;  // the records of the last call (icp_get_reciprocal_stats)
     icp_convergence_options cvg_opt = {0, 1e-6f, 1e-6f, 1, 1};      // icp_set_convergence_options: stopping on a converged pose
     icp_convergence_result cvg_last = {0, 0, 0, -1.f, -1.f};        // the last run (icp_get_convergence) ...
     std::vector<icp_convergence_step> cvg_trace;                    // ... and its trace, one step per iteration that ran (icp_get_convergence_trace)
@@ -149,6 +154,11 @@ void release(DevBuf& b) { if (b.p && !b.view) { (void)hipFree(b.p); g_live_bytes
 void set_view(DevBuf& b, void* p, size_t bytes) { release(b); b.p = p; b.cap = bytes; b.view = true; }
 void release(Cloud& c) { release(c.x); release(c.y); release(c.z); release(c.nx); release(c.ny); release(c.nz); release(c.cr); release(c.cg); release(c.cb); release(c.rgba); }
 void release(Level& lv) { release(lv.idx); release(lv.order); release(lv.sorted_idx); release(lv.sorted); release(lv.pack); lv.sorted_valid = false; }
+void release(Bvh& b) {
+    for (DevBuf* d : {&b.keys, &b.keys2, &b.vals, &b.vals2, &b.temp, &b.leaves, &b.recs, &b.nodes, &b.qnodes, &b.pos_of, &b.side, &b.scanr, &b.axis_of_node}) release(*d);
+    for (DevBuf& d : b.axl) release(d);
+    b.valid = false;
+}
 void release(NssLevel& nl) { release(nl.cand); release(nl.seg); release(nl.longs); }
 // the normal-space sampling caches that belong to the resident source (held: only the held draws, which also depend on the options)
 void drop_nss(icp_ctx* c, bool held_only);

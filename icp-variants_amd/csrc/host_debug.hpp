@@ -76,6 +76,13 @@ int icp_debug_live_bytes(int64_t* out) {
     *out = (int64_t)g_live_bytes.load();
     return ICP_OK;
 }
+//   icp_debug_reciprocal_naive: on != 0 makes reciprocal rejection take the naive route on this context (a written-out query cloud, a full
+//                               k_knn_bvh search against the source tree, a compare pass) -- the yardstick of tools/time_reciprocal.py.
+int icp_debug_reciprocal_naive(icp_ctx* c, int32_t on) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    c->rcp_naive = on != 0;
+    return ICP_OK;
+}
 int icp_debug_counters(icp_ctx* c, int32_t* merged_runs, int32_t* merged_fallbacks) {
     if (!c) return ICP_ERR_INVALID_ARG;
     if (merged_runs) *merged_runs = c->merged_runs;

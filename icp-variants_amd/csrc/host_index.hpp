@@ -272,6 +272,7 @@ int finish_source(icp_ctx* c) {
     drop_nss(c, false); c->sel_last.clear();
     c->gicp_ready[1] = false;
     c->fpfh[1].ready = false;
+    c->src_bvh.valid = false;                                // the reverse index of reciprocal rejection: rebuilt at its next use
     if (n <= 0) return ICP_OK;
     if ((rc = ensure(c, c->src_flag, (size_t)n))) return rc;
     if ((rc = ensure(c, c->src_box, 32))) return rc;
@@ -390,6 +391,7 @@ extern "C" int icp_internal_promote_source_to_target(icp_ctx* c) {
     hipLaunchKernelGGL(k_copy_planes_pad, dim3((npad + 255) / 256, 6), dim3(256), 0, c->stream, pl, n, npad);
     HIPCK(c, hipGetLastError());
     tg.n = n; tg.npad = npad; tg.has_normals = sc.has_normals; tg.has_colors = false;
+    c->src_bvh.valid = false;                                // the promoted scan's pair is over: its reverse index goes with it
     return guard.done(finish_target(c, false));
 }
 

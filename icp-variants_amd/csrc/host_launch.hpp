@@ -151,6 +151,14 @@ int rearm_handover(icp_ctx* c) {
     return ICP_OK;
 }
 
+// The sorted position -> original source index map of a Morton-sorted level's cloud; nullptr for the resident source itself.
+const int* level_src_orig(icp_ctx* c, const Cloud& src) {
+    if (&src == &c->src) return nullptr;
+    for (auto& kv : c->levels) if (&kv.second.sorted == &src) return kv.second.sorted_idx.as<int>();
+    for (auto& kv : c->nss_held) if (&kv.second.lv.sorted == &src) return kv.second.lv.sorted_idx.as<int>();
+    return nullptr;
+}
+
 // What k_post_gicp reads beside the post parameters: the cached GICP normals (gicp_prepare has made them current) and, when the post stage
 // runs over a Morton-sorted level, that level's sorted position -> original index map.
 GicpPost gicp_post_params(icp_ctx* c, const Cloud& src) {
@@ -158,11 +166,7 @@ GicpPost gicp_post_params(icp_ctx* c, const Cloud& src) {
     const bool own_t = c->gicp_opt.covariance_k == 0, own_s = own_t;
     g.tnx = own_t ? c->tgt.nx.as<float>() : c->gicp_n[0][0].as<float>(); g.tny = own_t ? c->tgt.ny.as<float>() : c->gicp_n[0][1].as<float>(); g.tnz = own_t ? c->tgt.nz.as<float>() : c->gicp_n[0][2].as<float>();
     g.snx = own_s ? c->src.nx.as<float>() : c->gicp_n[1][0].as<float>(); g.sny = own_s ? c->src.ny.as<float>() : c->gicp_n[1][1].as<float>(); g.snz = own_s ? c->src.nz.as<float>() : c->gicp_n[1][2].as<float>();
-    g.src_orig = nullptr;
-    if (&src != &c->src) {
-        for (auto& kv : c->levels) if (&kv.second.sorted == &src) g.src_orig = kv.second.sorted_idx.as<int>();
-        for (auto& kv : c->nss_held) if (&kv.second.lv.sorted == &src) g.src_orig = kv.second.lv.sorted_idx.as<int>();
-    }
+    g.src_orig = level_src_orig(c, src);
     g.one_minus_eps = 1.0 - (double)c->gicp_opt.epsilon;
     return g;
 }
@@ -206,6 +210,64 @@ int launch_robust(icp_ctx* c, const PostParams& pp, int n, icp_robust_stats* d_r
     hipLaunchKernelGGL(k_robust_select<2>, dim3(nb), dim3(ROBUST_THREADS), 0, c->stream, rp);
     hipLaunchKernelGGL(k_robust_finish, dim3(1), dim3(ROBUST_THREADS), 0, c->stream, rp);
     hipLaunchKernelGGL(k_robust_apply, dim3(nb), dim3(ROBUST_THREADS), 0, c->stream, pp, rp);
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+
+// Reciprocal rejection (icp_reciprocal_options, dev_reciprocal.hpp) is on.
+bool reciprocal_on(const icp_ctx* c) { return c->rcp_opt.enabled != 0; }
+
+// The configurations a loop with reciprocal rejection refuses (run_loop, icp_correspond).
+int reciprocal_check(icp_ctx* c) {
+    if (c->prm.color_icp) { c->err = "reciprocal rejection (icp_set_reciprocal_options) does not support color_icp = 1: a 6-D forward search against a 3-D reverse one is not a mutual test"; return ICP_ERR_INVALID_ARG; }
+    if (c->lm_on) { c->err = "the non-linear optimiser does not support reciprocal rejection (icp_set_reciprocal_options)"; return ICP_ERR_INVALID_ARG; }
+    return ICP_OK;
+}
+
+// Loop start with reciprocal rejection on (run_loop, icp_correspond): the BVH over the full-resolution resident source current (built on
+// first use; finish_source drops it), `slots` per-iteration records allocated and zero.  The build waits for the device; the loop does not.
+int reciprocal_prepare(icp_ctx* c, int slots) {
+    int rc;
+    Bvh& b = c->src_bvh;
+    if (!b.valid) {
+        if ((rc = finite_list(c, c->src, false, c->src_rflag, c->src_finite, &b.n_valid))) return rc;
+        b.d_finite = c->src_finite.as<int>(); b.n_ids = c->src.n; b.attrs = nullptr;
+        CoordPtrs<3> cp; cp.c[0] = c->src.x.as<float>(); cp.c[1] = c->src.y.as<float>(); cp.c[2] = c->src.z.as<float>();
+        if ((rc = build_bvh<3>(c, b, cp))) return rc;
+    }
+    const size_t bytes = (size_t)(slots > 0 ? slots : 1) * sizeof(icp_reciprocal_stats);
+    if ((rc = ensure(c, c->rcp_stats, bytes))) return rc;
+    HIPCK(c, hipMemsetAsync(c->rcp_stats.p, 0, bytes, c->stream));
+    return ICP_OK;
+}
+
+// The reciprocal test over the records the matcher left for the query set q (no sync): one launch, one thread per query in the level's
+// Morton order; non-mutual records become {-1, 0}, the counts go to d_stats (reciprocal_prepare has run).
+int launch_reciprocal(icp_ctx* c, const QuerySet& q, icp_reciprocal_stats* d_stats) {
+    const Bvh& b = c->src_bvh;
+    CoordPtrs<3> cp; cp.c[0] = c->src.x.as<float>(); cp.c[1] = c->src.y.as<float>(); cp.c[2] = c->src.z.as<float>();
+    RecipParams rp; memset(&rp, 0, sizeof(rp));
+    rp.matches = c->matches.as<icp_match_t>(); rp.n = q.n; rp.order = q.order; rp.sel = q.sel; rp.src_orig = level_src_orig(c, *q.cl);
+    rp.tx = c->tgt.x.as<float>(); rp.ty = c->tgt.y.as<float>(); rp.tz = c->tgt.z.as<float>();
+    rp.ps = c->ps.as<PoseState>(); rp.stats = d_stats;
+    rp.tree_depth = 0; while ((1 << rp.tree_depth) < b.Lp) rp.tree_depth++;
+    if (c->rcp_naive) {                                      // the comparison route of tools/time_reciprocal.py: never the product's
+        int rc;
+        for (DevBuf& d : c->rcp_q) if ((rc = ensure(c, d, (size_t)q.n * 4))) return rc;
+        if ((rc = ensure(c, c->rcp_nn, (size_t)q.n * sizeof(icp_match_t)))) return rc;
+        float* qx = c->rcp_q[0].as<float>(); float* qy = c->rcp_q[1].as<float>(); float* qz = c->rcp_q[2].as<float>();
+        hipLaunchKernelGGL(k_reciprocal_queries, dim3((q.n + 255) / 256), dim3(256), 0, c->stream, rp, qx, qy, qz);
+        KnnParams kp; memset(&kp, 0, sizeof(kp));
+        kp.sx = qx; kp.sy = qy; kp.sz = qz; kp.n = q.n; kp.tx = cp.c[0]; kp.ty = cp.c[1]; kp.tz = cp.c[2]; kp.mpad = c->src.npad;
+        kp.ps = rp.ps; kp.pretransformed = 1; kp.max_dist = FLT_MAX; kp.out = c->rcp_nn.as<icp_match_t>(); kp.nseg = 1;
+        kp.fault = &c->ps.as<PoseState>()->fault;
+        hipLaunchKernelGGL(k_knn_bvh<3>, dim3((q.n + BVH_THREADS - 1) / BVH_THREADS), dim3(BVH_THREADS), WALK_LDS_BYTES, c->stream, kp, make_view<3>(b, cp), q.order);
+        hipLaunchKernelGGL(k_reciprocal_compare, dim3((q.n + BVH_THREADS - 1) / BVH_THREADS), dim3(BVH_THREADS), 0, c->stream, rp, c->rcp_nn.as<icp_match_t>());
+        HIPCK(c, hipGetLastError());
+        return ICP_OK;
+    }
+    const size_t lds = (size_t)(rp.tree_depth + 1) * BVH_THREADS * 2;
+    hipLaunchKernelGGL(k_reciprocal, dim3((q.n + BVH_THREADS - 1) / BVH_THREADS), dim3(BVH_THREADS), lds, c->stream, rp, make_view<3>(b, cp));
     HIPCK(c, hipGetLastError());
     return ICP_OK;
 }

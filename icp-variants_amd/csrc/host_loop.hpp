@@ -260,7 +260,7 @@ RingParams ring_params(const icp_ctx* c, const Ring& r, int j, int n_prev, PoseS
 // + 144 the merged form's control words (the spare words beside its fault word), + 256 the separate form's state block (control words |
 // search pose | final pose state), + 512 the trace; eligible[i] = the host's half of iteration i's eligibility, from the plan's factors.
 struct IterEvents { hipEvent_t start = nullptr, matched = nullptr, posted = nullptr, end = nullptr; };   // posted / end: nullptr = the form has no such stage to bracket
-struct LoopRun { RunPlan pl; bool lm, robust, rmse, fontana, cvg; size_t pin_stats = 256, pin_pose, pin_lm; std::vector<char> sampled, eligible; std::vector<IterEvents> ev; int n_enqueued = 0; };
+struct LoopRun { RunPlan pl; bool lm, robust, recip, rmse, fontana, cvg; size_t pin_stats = 256, pin_pose, pin_lm; std::vector<char> sampled, eligible; std::vector<IterEvents> ev; int n_enqueued = 0; };
 constexpr size_t CVG_MERGED_WORDS = 128 + 16, CVG_STATE = 256, CVG_TRACE = 512;      // offsets from the final pose state
 // The separate form enqueues a run that may stop in chunks of this many iterations and reads the stop word between them: the chunk size
 // trades host round trips against iterations enqueued in vain.  Time only, never results.  2: the fastest of {1, 2, 4, 8} on the bench
@@ -357,7 +357,8 @@ int enqueue_separate(icp_ctx* c, LoopRun& r) {
             // (keep_records: the fused matcher writes its records for k_lm_eval)
             QuerySet q{pl.clouds[i], pl.sels[i], pl.ns[i], 0, p.color_icp != 0 && p.matching == ICP_MATCH_KNN, pl.seeded(i), pl.orders[i], r.lm};
             int fused = 0;
-            if ((rc = launch_match(c, q, !r.robust ? &fused : nullptr))) return rc;
+            if ((rc = launch_match(c, q, !r.robust && !r.recip ? &fused : nullptr))) return rc;
+            if (r.recip && (rc = launch_reciprocal(c, q, c->rcp_stats.as<icp_reciprocal_stats>() + i))) return rc;      // in front of the robust chain
             if (ev) HIPCK(c, hipEventRecord(r.ev[i].matched, c->stream));
             if (ev && !fused) r.ev[i].posted = loop_event(c, i, 2);      // fused epilogue: there is no separate post stage to bracket
             if (r.lm) rc = launch_post_and_lm(c, *pl.clouds[i], pl.sels[i], pl.ns[i], d_st, c->lm_sums.as<icp_lm_summary>() + i, r.ev[i].posted, fused);
@@ -397,12 +398,15 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     if (n_run) *n_run = 0;
     const bool lm = r.lm = c->lm_on;      // the non-linear optimiser: the separate form, its records kept for k_lm_eval
     const bool robust = r.robust = robust_on(c);      // trimmed / robust mode: the separate form with the stand-alone matcher, as GICP runs
-    c->lm_last.clear(); c->rob_last.clear();
+    const bool recip = r.recip = reciprocal_on(c);      // reciprocal rejection: the same form, k_reciprocal between the matcher and the post stage
+    c->lm_last.clear(); c->rob_last.clear(); c->rcp_last.clear();
     const bool cvg = r.cvg = !single && c->cvg_opt.enabled != 0;      // icp_iterate ignores the option and leaves the last run's result alone
     if (!single) { c->cvg_trace.clear(); c->cvg_last = icp_convergence_result{0, 0, iters, -1.f, -1.f}; }
     if (robust && lm) { c->err = "the non-linear optimiser does not support robust mode (icp_set_robust_options)"; return ICP_ERR_INVALID_ARG; }
+    if (recip && (rc = reciprocal_check(c))) return rc;
     if (iters == 0) return guard.done();
     if (robust && (rc = robust_prepare(c, iters))) return rc;
+    if (recip && (rc = reciprocal_prepare(c, iters))) return rc;
     const size_t cvg_bytes = cvg ? ((size_t)iters * sizeof(icp_convergence_step) + 255) & ~(size_t)255 : 0;
     r.pin_pose = r.pin_stats + (((size_t)iters * sizeof(icp_iter_stats) + 255) & ~(size_t)255); r.pin_lm = r.pin_pose + 512 + cvg_bytes;
     if ((rc = ensure_pinned(c, lm ? r.pin_lm + (size_t)iters * sizeof(icp_lm_summary) : r.pin_lm))) return rc;
@@ -415,7 +419,7 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     if ((rc = ensure_events(c, (size_t)iters * 4 + 2))) return rc;
     const bool rmse = r.rmse = (p.record_rmse & 1) && c->conv_n > 0;
     const bool fontana = r.fontana = (p.record_rmse & 2) && c->conv_n > 0;
-    bool merged = try_merged && !lm && !robust && !single && iters >= 2 && pl.sorted_levels && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
+    bool merged = try_merged && !lm && !robust && !recip && !single && iters >= 2 && pl.sorted_levels && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
     for (int i = 0; merged && i < iters; i++) if (pl.ns[i] <= 0) merged = false;
     const int tmode = c->stage_timing;
     r.sampled.assign((size_t)iters, 0); r.ev.assign((size_t)iters, IterEvents());
@@ -424,7 +428,10 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     if ((rc = merged ? enqueue_merged(c, r) : enqueue_separate(c, r))) return rc;
     std::vector<icp_robust_stats> rob((size_t)(robust ? iters : 0));
     if (robust) HIPCK(c, hipMemcpyAsync(rob.data(), c->rob_stats.p, (size_t)iters * sizeof(icp_robust_stats), hipMemcpyDeviceToHost, c->stream));
+    std::vector<icp_reciprocal_stats> rcp((size_t)(recip ? iters : 0));      // (an iteration without work keeps the {0, 0} of reciprocal_prepare)
+    if (recip) HIPCK(c, hipMemcpyAsync(rcp.data(), c->rcp_stats.p, (size_t)iters * sizeof(icp_reciprocal_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    c->rcp_last.swap(rcp);
     for (int i = 0; robust && i < iters; i++) if (pl.ns[i] <= 0) rob[(size_t)i] = icp_robust_stats{0, 0, -1.f, -1.f};      // (no work: nothing was written)
     c->rob_last.swap(rob);
     const PoseState* hp = (const PoseState*)((char*)c->pinned + r.pin_pose);
@@ -459,6 +466,7 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
             if (pl.ns[i] <= 0) { memset(&c->lm_last[(size_t)i], 0, sizeof(icp_lm_summary)); c->lm_last[(size_t)i].termination = ICP_LM_NO_RESIDUALS; }
     }
     if (robust) c->rob_last.resize((size_t)n_done);
+    if (recip) c->rcp_last.resize((size_t)n_done);
     const int status = finish_records(pl, n_done, (icp_iter_stats*)((char*)c->pinned + r.pin_stats), pose_in, rmse, fontana, stats, max_stats);
     if (n_run) *n_run = n_done;
     if (!single) { c->cvg_last.converged = stopped; c->cvg_last.iterations_run = n_done; }
@@ -572,24 +580,30 @@ int icp_correspond(icp_ctx* c, const float pose[16], icp_match_t* out, double* s
     if ((rc = gicp_prepare(c))) return rc;
     if ((rc = colored_prepare(c))) return rc;
     const bool robust = robust_on(c);
-    c->rob_last.clear();
+    const bool recip = reciprocal_on(c);
+    c->rob_last.clear(); c->rcp_last.clear();
+    if (recip && (rc = reciprocal_check(c))) return rc;
     if (robust && (rc = robust_prepare(c, 1))) return rc;
+    if (recip && (rc = reciprocal_prepare(c, 1))) return rc;
     if ((rc = write_pose(c, pose))) return rc;
     const int* full_order = nullptr;
     if ((rc = get_full_order(c, &full_order))) return rc;
     QuerySet q{&c->src, nullptr, c->src.n, 0, c->prm.color_icp != 0 && c->prm.matching == ICP_MATCH_KNN, false, full_order};
     if ((rc = launch_match(c, q))) return rc;
+    if (recip && (rc = launch_reciprocal(c, q, c->rcp_stats.as<icp_reciprocal_stats>()))) return rc;
     if ((rc = ensure(c, c->sums, NSUM * 8))) return rc;
     if ((rc = rearm_handover(c))) return rc;
     if ((rc = launch_post_and_solve(c, c->src, nullptr, q.n, nullptr, c->sums.as<double>(), 0, nullptr, 0, robust ? c->rob_stats.as<icp_robust_stats>() : nullptr))) return rc;
     double hs[NSUM]; int fault = 0;
-    icp_robust_stats rs;
+    icp_robust_stats rs; icp_reciprocal_stats rcs;
     if (out) HIPCK(c, hipMemcpyAsync(out, c->matches.p, (size_t)q.n * sizeof(icp_match_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(hs, c->sums.p, NSUM * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(&fault, &c->ps.as<PoseState>()->fault, 4, hipMemcpyDeviceToHost, c->stream));
     if (robust) HIPCK(c, hipMemcpyAsync(&rs, c->rob_stats.p, sizeof(rs), hipMemcpyDeviceToHost, c->stream));
+    if (recip) HIPCK(c, hipMemcpyAsync(&rcs, c->rcp_stats.p, sizeof(rcs), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (robust) c->rob_last.assign(1, rs);
+    if (recip) c->rcp_last.assign(1, rcs);
     if (fault) { c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
     if (sums_out) { memset(sums_out, 0, 64 * 8); memcpy(sums_out, hs, NSUM * 8); }
     if (n_valid_out) *n_valid_out = (int32_t)hs[SUM_N];
@@ -605,6 +619,7 @@ int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_
     if (p.metric == ICP_METRIC_GICP) { c->err = "icp_match_seeded: GICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
     if (p.metric == ICP_METRIC_COLORED) { c->err = "icp_match_seeded: colored ICP has no fused matcher"; return ICP_ERR_INVALID_ARG; }
     if (robust_on(c)) { c->err = "icp_match_seeded: robust mode (icp_set_robust_options) has no fused matcher"; return ICP_ERR_INVALID_ARG; }
+    if (reciprocal_on(c)) { c->err = "icp_match_seeded: reciprocal rejection (icp_set_reciprocal_options) has no fused matcher"; return ICP_ERR_INVALID_ARG; }
     if (p.matching != ICP_MATCH_KNN || p.knn_backend != ICP_KNN_LBVH || p.metric == ICP_METRIC_SYMMETRIC) {
         c->err = "icp_match_seeded: needs k-NN matching on the LBVH backend with the fused point-to-point / point-to-plane matcher"; return ICP_ERR_INVALID_ARG;
     }

@@ -17,6 +17,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
     if (c->lm_on) { c->err = "icp_run_multistart: the non-linear optimiser is not supported"; return ICP_ERR_INVALID_ARG; }
     if (c->prm.metric == ICP_METRIC_GICP) { c->err = "icp_run_multistart: GICP is not supported"; return ICP_ERR_INVALID_ARG; }
     if (c->prm.metric == ICP_METRIC_COLORED) { c->err = "icp_run_multistart: colored ICP is not supported"; return ICP_ERR_INVALID_ARG; }
+    if (reciprocal_on(c)) { c->err = "icp_run_multistart: reciprocal rejection (icp_set_reciprocal_options) is not supported"; return ICP_ERR_INVALID_ARG; }
     if (robust_on(c)) { c->err = "icp_run_multistart: robust mode (icp_set_robust_options) is not supported"; return ICP_ERR_INVALID_ARG; }
     if (c->cvg_opt.enabled) { c->err = "icp_run_multistart: stopping on a converged pose (icp_set_convergence_options) is not supported: the starts share their launches"; return ICP_ERR_INVALID_ARG; }
     int rc;

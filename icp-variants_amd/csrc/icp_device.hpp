@@ -8,7 +8,7 @@
 //
 // Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_converge.hpp, dev_solve.hpp,
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
-// dev_fpfh.hpp
+// dev_fpfh.hpp, dev_reciprocal.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -43,6 +43,8 @@
 //                       quotas and an exact radix select of each bucket's smallest hashes (dev_nss.hpp)
 //   k_fpfh_spfh<K> /    global registration (icp_register_global): FPFH descriptors in two passes, k_feature_match the exact 1-NN in 33
 //   k_fpfh              dimensions through LDS tiles, k_ransac_fit / k_ransac_score the three-point hypotheses and their inlier counts (dev_fpfh.hpp)
+//   k_reciprocal        reciprocal (mutual nearest-neighbour) rejection: a bounded existence walk over the BVH of the source, one launch per
+//                       iteration between the matcher and the post stage (dev_reciprocal.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -73,5 +75,6 @@ namespace icpdev {
 #include "dev_colored.hpp"
 #include "dev_nss.hpp"
 #include "dev_fpfh.hpp"
+#include "dev_reciprocal.hpp"
 
 }  // namespace icpdev

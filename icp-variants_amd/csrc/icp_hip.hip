@@ -84,9 +84,11 @@ int icp_ctx_destroy(icp_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     release(c->tgt); release(c->src); release(c->qry); release(c->conv_src); release(c->conv_ref);
     release(c->nrm_cloud);
-    for (Bvh* b : {&c->bvh, &c->bvh6, &c->nrm_bvh}) { release(b->qnodes); release(b->recs); release(b->pos_of); for (DevBuf& d : b->axl) release(d); release(b->side); release(b->scanr); release(b->axis_of_node); }
-    for (Bvh* b : {&c->bvh6, &c->nrm_bvh}) { release(b->keys); release(b->keys2); release(b->vals); release(b->vals2); release(b->temp); release(b->leaves); release(b->nodes); }
-    release(c->bvh.keys); release(c->bvh.keys2); release(c->bvh.vals); release(c->bvh.vals2); release(c->bvh.temp); release(c->bvh.leaves); release(c->okeys); release(c->okeys2); release(c->ovals); release(c->otemp); release(c->bvh.nodes);
+    for (Bvh* b : {&c->bvh, &c->bvh6, &c->nrm_bvh, &c->src_bvh}) release(*b);      // every buffer of a tree, pos_of included
+    release(c->okeys); release(c->okeys2); release(c->ovals); release(c->otemp);
+    release(c->src_rflag); release(c->src_finite); release(c->rcp_stats);
+    for (DevBuf& d : c->rcp_q) release(d);
+    release(c->rcp_nn);
     for (auto& kv : c->levels) release(kv.second);
     drop_nss(c, false);
     for (DevBuf* d : {&c->nss_bkt, &c->nss_table, &c->nss_quota, &c->nss_thr, &c->nss_state, &c->nss_hist, &c->nss_total}) release(*d);
@@ -224,6 +226,28 @@ int icp_get_robust_stats(const icp_ctx* c, icp_robust_stats* out, int32_t max_ou
     if (!c || max_out < 0 || (!out && max_out > 0)) return ICP_ERR_INVALID_ARG;
     const int32_t n = (int32_t)c->rob_last.size();
     for (int32_t i = 0; i < n && i < max_out; i++) out[i] = c->rob_last[(size_t)i];
+    if (count_out) *count_out = n;
+    return ICP_OK;
+}
+
+int icp_reciprocal_options_default(icp_reciprocal_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    o->enabled = 0;
+    return ICP_OK;
+}
+int icp_set_reciprocal_options(icp_ctx* c, const icp_reciprocal_options* o) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    icp_reciprocal_options v;
+    if (o) v = *o; else icp_reciprocal_options_default(&v);
+    if (v.enabled != 0 && v.enabled != 1) { c->err = "icp_set_reciprocal_options: enabled must be 0 or 1"; return ICP_ERR_INVALID_ARG; }
+    c->rcp_opt = v;
+    return ICP_OK;
+}
+int icp_get_reciprocal_options(const icp_ctx* c, icp_reciprocal_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->rcp_opt; return ICP_OK; }
+int icp_get_reciprocal_stats(const icp_ctx* c, icp_reciprocal_stats* out, int32_t max_out, int32_t* count_out) {
+    if (!c || max_out < 0 || (!out && max_out > 0)) return ICP_ERR_INVALID_ARG;
+    const int32_t n = (int32_t)c->rcp_last.size();
+    for (int32_t i = 0; i < n && i < max_out; i++) out[i] = c->rcp_last[(size_t)i];
     if (count_out) *count_out = n;
     return ICP_OK;
 }

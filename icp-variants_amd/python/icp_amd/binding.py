@@ -148,6 +148,20 @@ ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY = 0, 1, 2, 3
 ROBUST_KERNELS = {"none": ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY, "tukey": ROBUST_TUKEY}
 
 
+class IcpReciprocalOptions(C.Structure):
+    _fields_ = [("enabled", C.c_int32)]
+
+
+class IcpReciprocalStats(C.Structure):
+    _fields_ = [("n_matched", C.c_int32), ("n_mutual", C.c_int32)]
+
+
+def select_reciprocal(ctx, reciprocal):
+    """The runners' `reciprocal=` argument: True -> reciprocal (mutual nearest-neighbour) rejection on, False -> off, None -> unchanged."""
+    if reciprocal is not None:
+        ctx.set_reciprocal_options(enabled=bool(reciprocal))
+
+
 class IcpConvergenceOptions(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("rotation_eps", C.c_float), ("translation_eps", C.c_float), ("min_iterations", C.c_int32), ("patience", C.c_int32)]
 
@@ -222,6 +236,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
            "icp_robust_options_default", "icp_set_robust_options", "icp_get_robust_options", "icp_get_robust_stats",
+           "icp_reciprocal_options_default", "icp_set_reciprocal_options", "icp_get_reciprocal_options", "icp_get_reciprocal_stats",
            "icp_convergence_options_default", "icp_set_convergence_options", "icp_get_convergence_options", "icp_get_convergence", "icp_get_convergence_trace",
            "icp_nss_options_default", "icp_set_nss_options", "icp_get_nss_options", "icp_get_normal_buckets", "icp_get_selection",
            "icp_global_options_default", "icp_set_global_options", "icp_get_global_options", "icp_compute_features", "icp_get_features", "icp_get_spfh",
@@ -402,6 +417,26 @@ class Context:
         buf = (IcpRobustStats * max(n.value, 1))()
         self._ck(self.lib.icp_get_robust_stats(self.h, buf, C.c_int32(n.value), C.byref(n)))
         return [dict(n_entering=b.n_entering, n_kept=b.n_kept, trim_d2=b.trim_d2, sigma=b.sigma) for b in buf[:n.value]]
+
+    def set_reciprocal_options(self, enabled=True):
+        """icp_set_reciprocal_options: reciprocal (mutual nearest-neighbour) rejection: a pair (s, t) is kept only if s is also the nearest
+        source point to t.  set_reciprocal_options(False) turns the option off."""
+        o = IcpReciprocalOptions(int(bool(enabled)))
+        self._ck(self.lib.icp_set_reciprocal_options(self.h, C.byref(o)))
+        return o
+
+    def reciprocal_options(self):
+        o = IcpReciprocalOptions()
+        self._ck(self.lib.icp_get_reciprocal_options(self.h, C.byref(o)))
+        return o
+
+    def reciprocal_stats(self):
+        """icp_get_reciprocal_stats: one dict per ICP iteration of the last icp_iterate / icp_run / icp_correspond (none when the option was off)."""
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_get_reciprocal_stats(self.h, None, C.c_int32(0), C.byref(n)))
+        buf = (IcpReciprocalStats * max(n.value, 1))()
+        self._ck(self.lib.icp_get_reciprocal_stats(self.h, buf, C.c_int32(n.value), C.byref(n)))
+        return [dict(n_matched=b.n_matched, n_mutual=b.n_mutual) for b in buf[:n.value]]
 
     def set_convergence_options(self, rotation=None, translation=None, min_iterations=1, patience=1):
         """icp_set_convergence_options: stop run / batch_run / track_depth_frames on the device once `patience` consecutive eligible
@@ -844,6 +879,8 @@ class LinearICPOptimizer:
     def setGICPOptions(self, epsilon=1e-3, k=20): self.ctx.set_gicp_options(epsilon, k)         # setMetric(METRIC_GICP) selects it
     def setColoredICPOptions(self, lambda_geometric=0.968, k=20): self.ctx.set_colored_options(lambda_geometric, k)   # setMetric(METRIC_COLORED)
     def setRobustOptions(self, kernel="none", tuning=0.0, sigma=0.0, overlap=1.0): self.ctx.set_robust_options(kernel, tuning, sigma, overlap)
+
+    def setUseReciprocalCorrespondences(self, on): self.ctx.set_reciprocal_options(enabled=bool(on))   # PCL's name for the mutual nearest-neighbour test
 
     def setConvergenceCriteria(self, rotation_eps, translation_eps, min_iterations=1, patience=1):
         self.ctx.set_convergence_options(rotation_eps, translation_eps, min_iterations, patience)

@@ -56,11 +56,13 @@ def prepare_pair(ctx, src_xyz, tgt_xyz, benchmark_pose, pose_scaling=0.1, k=5):
                 gt=np.linalg.inv(np.asarray(S, np.float64)), initial=S)
 
 
-def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="identity", **global_options):
+def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="identity", reciprocal=None, **global_options):
     """estimatePose of alignETH (main.cpp:457) on a prepared pair with the context's params: the optimiser the reference's
     USE_LINEAR_ICP picks (main.cpp:26) -- nonlinear True (or an IcpLmOptions): CeresICPOptimizer, False: LinearICPOptimizer, None: the
     context's current choice.  convergence: dict(rotation=..., translation=...[, min_iterations, patience]) stops the run on a converged
     pose (Context.set_convergence_options), False turns that off, None keeps the context's setting.
+    reciprocal: True keeps only mutual nearest-neighbour pairs (Context.set_reciprocal_options), False turns that off, None keeps the
+    context's setting.
     initial: "identity" starts the run from the identity, as the reference does; "global" starts it from the best pose of the global
     registration (Context.register_global with **global_options: FPFH features, feature matching, RANSAC), for pairs whose initial pose
     is not roughly known.  (globalreg.align refines several RANSAC poses at once instead, where multi-start ICP is available.)
@@ -72,6 +74,7 @@ def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="iden
         raise TypeError("global registration options need initial='global'")
     binding.select_optimizer(ctx, nonlinear)
     binding.select_convergence(ctx, convergence)
+    binding.select_reciprocal(ctx, reciprocal)
     ctx.push_params()
     ctx.set_target(pair["tgt_pts"], pair["tgt_nrm"], pair.get("tgt_rgba"))
     ctx.set_source(pair["src_pts"], pair["src_nrm"], pair.get("src_rgba"))

@@ -70,16 +70,19 @@ def reconstruct_room_params(params, K=TUM_K, width=TUM_WIDTH, height=TUM_HEIGHT)
     return params
 
 
-def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None):
+def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None, reciprocal=None):
     """reconstructRoom's loop on the device.  params: the variant's icp_params (metric, matching, colour ICP, weighting, multires, ...;
     ctx.params when None); reconstruct_room_params then sets what reconstructRoom sets on top of them -- 35 iterations, max distance 0.1
     and, for projective matching, the sequence's camera.  Returns (camera poses: the identity for frame 0, then currentCameraToWorld^-1
     after every frame (main.cpp:267-269,318-320), per-frame records, status).  nonlinear: True (or an IcpLmOptions) tracks with the
     non-linear optimiser -- USE_LINEAR_ICP 0 (main.cpp:26) --, False with the linear one, None keeps the context's choice.
     convergence: dict(rotation=..., translation=...[, min_iterations, patience]) stops every frame's run on a converged pose
-    (Context.set_convergence_options; the records' `iterations` say where), False turns that off, None keeps the context's setting."""
+    (Context.set_convergence_options; the records' `iterations` say where), False turns that off, None keeps the context's setting.
+    reciprocal: True keeps only mutual nearest-neighbour pairs in every frame's run (Context.set_reciprocal_options), False turns that off,
+    None keeps the context's setting."""
     binding.select_optimizer(ctx, nonlinear)
     binding.select_convergence(ctx, convergence)
+    binding.select_reciprocal(ctx, reciprocal)
     if params is not None:
         ctx.params = params
     reconstruct_room_params(ctx.params, seq["K"], seq["width"], seq["height"])
@@ -91,12 +94,12 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None)
     return poses, recs, rc
 
 
-def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None):
+def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None):
     """reconstructRoom end to end: `track`, then saveRoomToFile (utils.h:179-193) for every scheduled frame k --
     joinMeshes(SimpleMesh(sensor, pose_k, edge_threshold) on the device, SimpleMesh::camera(pose_k, camera_scale), identity) with pose_k
     the camera pose `track` returned (the identity for frame 0).  With out_dir the meshes are written as mesh_<frame index>.off
     (getCurrentFrameCnt, VirtualSensor.h:142-144).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
-    poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence)
+    poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal)
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)

@@ -428,6 +428,44 @@ int icp_get_convergence(const icp_ctx* ctx, icp_convergence_result* out);
 /* One step per iteration that ran, of the same run; none when the option was off.  out[0 .. min(max_out, count)), *count_out = count. */
 int icp_get_convergence_trace(const icp_ctx* ctx, icp_convergence_step* out, int32_t max_out, int32_t* count_out);
 
+/* -------- Reciprocal (mutual nearest-neighbour) correspondence rejection (extension: the reference has no counterpart), per context --------
+ * The "compatibility" test of Rusinkiewicz and Levoy (3DIM 2001), PCL's setUseReciprocalCorrespondences: a pair (s, t) is kept only if s is
+ * also the nearest source point to t.  Off (the default): nothing changes, every loop form is chosen as without this call.
+ * On, per ICP iteration, behind the matcher and in front of weighting, rejection and the robust chain: every query k of the iteration's
+ * query set (multires level or sample) whose raw match idx = t is >= 0 is JUDGED; i = the query's ORIGINAL source index.  The test runs in
+ * the source's own frame against the full-resolution resident source, whatever level or sample the iteration runs on (P = the pose the
+ * iteration searched at, column-major; every operation one fp32 rounding, no fused contraction):
+ *   d   = t_pos - P[12..14]                                  (three subtractions)
+ *   q_x = (P[0] d_x + P[1] d_y) + P[2] d_z,  q_y with P[4..6],  q_z with P[8..10]   (the transpose of the 3x3 block applied to d)
+ *   d2(j) = (dx dx + dy dy) + dz dz,  dx = q_x - s_j.x, dy = q_y - s_j.y, dz = q_z - s_j.z   (s_j: source point j, untransformed)
+ *   the pair is MUTUAL iff no finite source point j has (d2(j), j) < (d2(i), i) lexicographically -- the library's (distance, lowest index)
+ *   argmin rule: of exact duplicates only the lowest index can be mutual; a NaN d2(i) compares below nothing and above nothing: mutual.
+ * A pair that is not mutual gets the record {-1, 0.f}; its d2 entry (icp_match's d2_out) stays as the matcher wrote it.  The later stages see
+ * the filtered records: icp_iter_stats.n_valid counts what survives them, robust mode ranks the residuals of mutual pairs only.
+ * The pose is taken as RIGID: q = R^T (t - T) is the target point in the source's frame only when the 3x3 block is orthonormal.  For the
+ * poses ICP produces the test then equals the mutual test in the target's frame up to fp32 rounding.  Parity unpinned (no such stage in the
+ * reference); the contract is restated in numpy by tests/reciprocal_restatement.py.
+ * The reverse search always runs on a BVH over the source (built on first use, dropped by every call that replaces the source), with either
+ * k-NN backend and with projective matching.  Supported: icp_run, icp_iterate, icp_correspond, icp_batch_run, icp_track_depth_frames;
+ * every metric, weighting, rejection, multires, selection, robust mode, the convergence stop.  ICP_ERR_INVALID_ARG while on (see
+ * icp_last_error): color_icp = 1 (a 6-D forward search against a 3-D reverse one is not a mutual test), the non-linear optimiser,
+ * icp_run_multistart, icp_match_seeded.  icp_match and icp_query_matches ignore the option. */
+typedef struct icp_reciprocal_options {
+    int32_t enabled;   /* 0 (default): no reciprocal test */
+} icp_reciprocal_options;
+typedef struct icp_reciprocal_stats {   /* one per ICP iteration of the last call */
+    int32_t n_matched;   /* pairs judged: queries whose raw match was >= 0 */
+    int32_t n_mutual;    /* pairs kept */
+} icp_reciprocal_stats;
+int icp_reciprocal_options_default(icp_reciprocal_options* opt);
+/* Validation: enabled in {0, 1}; else ICP_ERR_INVALID_ARG (reason in icp_last_error). */
+int icp_set_reciprocal_options(icp_ctx* ctx, const icp_reciprocal_options* opt);   /* NULL = defaults */
+int icp_get_reciprocal_options(const icp_ctx* ctx, icp_reciprocal_options* opt);
+/* One record per iteration of the last icp_iterate, icp_run or icp_correspond call on the context (icp_track_depth_frames: the last
+ * tracked frame's run; icp_batch_run: each context's own last pair); none when the option was off for that call.  Iterations with no
+ * work: {0, 0}.  out[0 .. min(max_out, count)), *count_out = the number of records. */
+int icp_get_reciprocal_stats(const icp_ctx* ctx, icp_reciprocal_stats* out, int32_t max_out, int32_t* count_out);
+
 /* -------- ConvergenceMeasure (ConvergenceMeasure.h:30-66): known-correspondence RMSE --------
  * src_xyz[i] (moved by the estimated pose) is compared with ref_xyz[i]. */
 int icp_set_convergence_reference(icp_ctx* ctx, const float* src_xyz, const float* ref_xyz, int32_t n);

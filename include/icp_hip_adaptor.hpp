@@ -230,6 +230,13 @@ public:
         icp_robust_options o; o.kernel = (int32_t)kernel; o.tuning = tuning; o.sigma = sigma; o.overlap = overlap;
         return icp_set_robust_options(context(), &o);
     }
+    // Reciprocal (mutual nearest-neighbour) correspondence rejection (an extension, PCL's name): a pair (s, t) is kept only if s is also the
+    // nearest source point to t; icp_set_reciprocal_options.  Returns its status.
+    int setUseReciprocalCorrespondences(bool on) {
+        if (!context()) return ICP_ERR_NO_DEVICE;
+        icp_reciprocal_options o; o.enabled = on ? 1 : 0;
+        return icp_set_reciprocal_options(context(), &o);
+    }
     // Normal-space sampling (setSelectionMethod(NORMAL_SPACE_SAMPLING, proba), an extension): cells per cube-face edge and whether every
     // iteration draws anew; icp_set_nss_options.  Returns its status (ICP_ERR_INVALID_ARG: grid not in {3, 5, 7}).
     int setNormalSpaceOptions(int grid, bool resample) {
