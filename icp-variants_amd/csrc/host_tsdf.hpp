@@ -1,0 +1,364 @@
+// host_tsdf.hpp -- frame-to-model tracking: the context's TSDF volume (icp_tsdf_*), the model as target (icp_set_target_tsdf) and the tracking
+// loop over it (icp_track_depth_model).  Kernels: dev_tsdf.hpp; contract: include/icp_hip.h, DESIGN.md section 6m.
+// Part of icp_hip.hip (included from there, after host_depth.hpp).
+namespace {
+const char* tsdf_options_error(const icp_tsdf_options* o) {
+    if (!o) return "null options";
+    for (int a = 0; a < 3; a++) if (o->dims[a] < 2) return "every dimension must be >= 2";
+    if ((long long)o->dims[0] * o->dims[1] * o->dims[2] > 0x7FFFFFFFll) return "nx * ny * nz must not exceed INT32_MAX";
+    for (int a = 0; a < 3; a++) if (!std::isfinite(o->origin[a])) return "the origin must be finite";
+    if (!(std::isfinite(o->voxel_size) && o->voxel_size > 0.f)) return "voxel_size must be finite and > 0";
+    if (!(std::isfinite(o->truncation) && o->truncation > 0.f)) return "truncation must be finite and > 0";
+    if (!(std::isfinite(o->max_weight) && o->max_weight >= 1.f)) return "max_weight must be finite and >= 1";
+    if (!(std::isfinite(o->min_depth) && std::isfinite(o->max_depth) && o->min_depth > 0.f && o->min_depth < o->max_depth)) return "need 0 < min_depth < max_depth";
+    if (!(o->ray_step == 0.f || (o->ray_step > 0.f && o->ray_step <= o->truncation))) return "ray_step must be 0 (truncation / 2) or in (0, truncation]";
+    const float step = o->ray_step == 0.f ? o->truncation / 2.f : o->ray_step;
+    if (!(((double)o->max_depth - o->min_depth) / step <= 1048576.0)) return "(max_depth - min_depth) / ray_step must not exceed 2^20";      // bounds every ray's march
+    return nullptr;
+}
+bool is_identity16(const float* m) {
+    for (int k = 0; k < 16; k++) if (m[k] != ((k % 5 == 0) ? 1.f : 0.f)) return false;
+    return true;
+}
+int tsdf_check_call(icp_ctx* c, const icp_depth_camera* cam, const float* pose, const char* who) {
+    if (!c->tsdf_on) { c->err = std::string(who) + ": no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    if (!depth_camera_ok(cam) || !pose) { c->err = std::string(who) + ": bad camera or null pose"; return ICP_ERR_INVALID_ARG; }
+    if (!is_identity16(cam->extrinsics)) { c->err = std::string(who) + ": the depth extrinsics must be the identity"; return ICP_ERR_INVALID_ARG; }
+    return ICP_OK;
+}
+size_t tsdf_voxels(const icp_ctx* c) { return (size_t)c->tsdf_opt.dims[0] * c->tsdf_opt.dims[1] * c->tsdf_opt.dims[2]; }
+TsdfVol tsdf_view(const icp_ctx* c) {
+    const icp_tsdf_options& o = c->tsdf_opt;
+    TsdfVol v;
+    v.vox = c->tsdf_vox.as<float2>(); v.nx = o.dims[0]; v.ny = o.dims[1]; v.nz = o.dims[2];
+    v.ox = o.origin[0]; v.oy = o.origin[1]; v.oz = o.origin[2]; v.s = o.voxel_size;
+    v.trunc = o.truncation; v.max_w = o.max_weight; v.min_d = o.min_depth; v.max_d = o.max_depth; v.step = o.ray_step;
+    return v;
+}
+TsdfCam tsdf_cam(const icp_depth_camera& cam) { TsdfCam t; t.width = cam.width; t.height = cam.height; t.fx = cam.fx; t.fy = cam.fy; t.cx = cam.cx; t.cy = cam.cy; return t; }
+
+// The frame in upload slot `slot` fused into the volume at `pose`, enqueued on the context's stream; d_count (optional): zeroed, then the
+// number of voxels written.
+int tsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count) {
+    TsdfMat m; memset(&m, 0, sizeof(m));
+    invert_extrinsics(pose, m.m);                    // the affine inverse in fp64, rounded once: 3x3 row-major, then t
+    const TsdfVol v = tsdf_view(c);
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->depth_up[slot], 0));
+    if (d_count) HIPCK(c, hipMemsetAsync(d_count, 0, 4, c->stream));
+    const dim3 grid((v.nx + 63) / 64, (v.ny + 3) / 4, (v.nz + TSDF_KCHUNK - 1) / TSDF_KCHUNK);
+    hipLaunchKernelGGL(k_tsdf_integrate, grid, dim3(64, 4), 0, c->stream, v, tsdf_cam(cam), m, (const float*)c->depth_dev[slot].as<float>(), d_count);
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+// The ray-cast from `pose`, enqueued; the hit count lands in tsdf_cnt (zeroed first).
+int tsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], bool soa, const TsdfRayOut& o) {
+    int rc;
+    if ((rc = ensure(c, c->tsdf_cnt, 16))) return rc;
+    TsdfMat m; memcpy(m.m, pose, 64);
+    HIPCK(c, hipMemsetAsync(c->tsdf_cnt.p, 0, 4, c->stream));
+    const dim3 grid((cam.width + 15) / 16, (cam.height + 15) / 16);
+    if (soa) hipLaunchKernelGGL(k_tsdf_raycast<true>, grid, dim3(256), 0, c->stream, tsdf_view(c), tsdf_cam(cam), m, o, c->tsdf_cnt.as<int>());
+    else hipLaunchKernelGGL(k_tsdf_raycast<false>, grid, dim3(256), 0, c->stream, tsdf_view(c), tsdf_cam(cam), m, o, c->tsdf_cnt.as<int>());
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+// One 4-byte count back to the host through the page-locked block; waits for the stream.
+int tsdf_read_count(icp_ctx* c, const void* d_count, int* out) {
+    int rc;
+    if ((rc = ensure_pinned(c, 4096))) return rc;
+    int* h = (int*)((char*)c->pinned + 2048);            // (the first bytes of the pinned block stage the pose)
+    HIPCK(c, hipMemcpyAsync(h, d_count, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    *out = *h;
+    return ICP_OK;
+}
+// The model as target, from the arguments already checked: the ray-cast into the target's planes, the hit count, finish_target.
+// *hits_out = 0 with ICP_ERR_NO_TARGET leaves an empty target.
+int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], int* hits_out, const char* who) {
+    int rc;
+    Cloud& tg = c->tgt;
+    const int n = cam.width * cam.height, npad = (n + 63) / 64 * 64;
+    *hits_out = 0;
+    for (DevBuf* pl : {&tg.x, &tg.y, &tg.z, &tg.nx, &tg.ny, &tg.nz}) if ((rc = ensure(c, *pl, (size_t)npad * 4))) return rc;
+    for (DevBuf* pl : {&tg.rgba, &tg.cr, &tg.cg, &tg.cb}) release(*pl);
+    TsdfRayOut o; memset(&o, 0, sizeof(o));
+    o.x = tg.x.as<float>(); o.y = tg.y.as<float>(); o.z = tg.z.as<float>(); o.nx = tg.nx.as<float>(); o.ny = tg.ny.as<float>(); o.nz = tg.nz.as<float>(); o.npad = npad;
+    if ((rc = tsdf_raycast_launch(c, cam, pose, true, o))) return rc;
+    int hits = 0;
+    if ((rc = tsdf_read_count(c, c->tsdf_cnt.p, &hits))) return rc;
+    tg.has_normals = true; tg.has_colors = false;
+    if (hits <= 0) {
+        tg.n = 0; tg.npad = 0; c->bvh.valid = false; c->bvh6.valid = false;
+        c->gicp_ready[0] = false; c->col_ready = false; c->fpfh[0].ready = false;
+        c->err = std::string(who) + ": the ray-cast of the model hits nothing";
+        return ICP_ERR_NO_TARGET;
+    }
+    tg.n = n; tg.npad = npad;
+    *hits_out = hits;
+    return finish_target(c, false);
+}
+// pose <- pose dT: the fp64 product of the two column-major 4x4, rounded once.
+void compose_pose(float pose[16], const float dT[16]) {
+    float out[16];
+    for (int cc = 0; cc < 4; cc++)
+        for (int r = 0; r < 4; r++)
+            out[cc * 4 + r] = (float)((((double)pose[r] * dT[cc * 4] + (double)pose[4 + r] * dT[cc * 4 + 1]) + (double)pose[8 + r] * dT[cc * 4 + 2]) + (double)pose[12 + r] * dT[cc * 4 + 3]);
+    memcpy(pose, out, 64);
+}
+}  // namespace
+
+int icp_tsdf_options_default(icp_tsdf_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    memset(o, 0, sizeof(*o));
+    o->voxel_size = 0.05f; o->truncation = 0.25f; o->max_weight = 64.f; o->min_depth = 0.3f; o->max_depth = 8.f; o->ray_step = 0.f;
+    return ICP_OK;
+}
+int icp_tsdf_options_check(const icp_tsdf_options* o) { return tsdf_options_error(o) ? ICP_ERR_INVALID_ARG : ICP_OK; }
+
+int icp_tsdf_reset(icp_ctx* c) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!c->tsdf_on) { c->err = "icp_tsdf_reset: no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipMemsetAsync(c->tsdf_vox.p, 0, tsdf_voxels(c) * 8, c->stream));      // tsdf 0, weight 0
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+int icp_tsdf_release(icp_ctx* c) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!c->tsdf_on) { c->err = "icp_tsdf_release: no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    release(c->tsdf_vox);
+    c->tsdf_on = false;
+    return ICP_OK;
+}
+int icp_tsdf_create(icp_ctx* c, const icp_tsdf_options* opt) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (const char* why = tsdf_options_error(opt)) { c->err = std::string("icp_tsdf_create: ") + why; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    if (c->tsdf_on) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->tsdf_vox); c->tsdf_on = false; }
+    c->tsdf_opt = *opt;
+    if (c->tsdf_opt.ray_step == 0.f) c->tsdf_opt.ray_step = opt->truncation / 2.f;
+    if ((rc = ensure(c, c->tsdf_vox, tsdf_voxels(c) * 8))) return rc;
+    if ((rc = ensure(c, c->tsdf_cnt, 16))) return rc;
+    c->tsdf_on = true;
+    return icp_tsdf_reset(c);
+}
+
+// The two host arrays and the interleaved device volume, a slab of at most 4 Mi voxels at a time through a host block.
+int icp_tsdf_download(icp_ctx* c, float* tsdf_out, float* weight_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!c->tsdf_on) { c->err = "icp_tsdf_download: no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    const size_t n = tsdf_voxels(c), slab = (size_t)4 << 20;
+    std::vector<float> h(2 * (n < slab ? n : slab));
+    for (size_t at = 0; at < n; at += slab) {
+        const size_t m = n - at < slab ? n - at : slab;
+        HIPCK(c, hipMemcpy(h.data(), c->tsdf_vox.as<float>() + 2 * at, m * 8, hipMemcpyDeviceToHost));
+        if (tsdf_out) for (size_t i = 0; i < m; i++) tsdf_out[at + i] = h[2 * i];
+        if (weight_out) for (size_t i = 0; i < m; i++) weight_out[at + i] = h[2 * i + 1];
+    }
+    return ICP_OK;
+}
+int icp_tsdf_upload(icp_ctx* c, const float* tsdf, const float* weight) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!c->tsdf_on) { c->err = "icp_tsdf_upload: no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    if (!tsdf || !weight) { c->err = "icp_tsdf_upload: null array"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    const size_t n = tsdf_voxels(c), slab = (size_t)4 << 20;
+    std::vector<float> h(2 * (n < slab ? n : slab));
+    for (size_t at = 0; at < n; at += slab) {
+        const size_t m = n - at < slab ? n - at : slab;
+        for (size_t i = 0; i < m; i++) { h[2 * i] = tsdf[at + i]; h[2 * i + 1] = weight[at + i]; }
+        HIPCK(c, hipMemcpy(c->tsdf_vox.as<float>() + 2 * at, h.data(), m * 8, hipMemcpyHostToDevice));
+    }
+    return ICP_OK;
+}
+
+int icp_tsdf_integrate(icp_ctx* c, const float* depth, const icp_depth_camera* cam, const float pose[16], int32_t* n_updated_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (n_updated_out) *n_updated_out = 0;
+    int rc;
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_integrate"))) return rc;
+    if (!depth) { c->err = "icp_tsdf_integrate: null depth frame"; return ICP_ERR_INVALID_ARG; }
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = stage_depth(c, 0, depth, nullptr, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>()))) return rc;
+    int n = 0;
+    if ((rc = tsdf_read_count(c, c->tsdf_cnt.p, &n))) return rc;
+    if (n_updated_out) *n_updated_out = n;
+    return guard.done();
+}
+
+int icp_tsdf_raycast(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], float* depth_out, float* vertices_out, float* normals_out,
+                     int32_t* n_hits_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (n_hits_out) *n_hits_out = 0;
+    int rc;
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_raycast"))) return rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const size_t n = (size_t)cam->width * cam->height;
+    if ((rc = ensure(c, c->staging, n * 28))) return rc;      // [depth 4n | vertices 12n | normals 12n]
+    float* d = c->staging.as<float>();
+    TsdfRayOut o; memset(&o, 0, sizeof(o));
+    o.depth = depth_out ? d : nullptr; o.vert = vertices_out ? d + n : nullptr; o.nrm = normals_out ? d + 4 * n : nullptr;
+    if ((rc = tsdf_raycast_launch(c, *cam, pose, false, o))) return rc;
+    if (depth_out) HIPCK(c, hipMemcpyAsync(depth_out, o.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (vertices_out) HIPCK(c, hipMemcpyAsync(vertices_out, o.vert, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (normals_out) HIPCK(c, hipMemcpyAsync(normals_out, o.nrm, n * 12, hipMemcpyDeviceToHost, c->stream));
+    int hits = 0;
+    if ((rc = tsdf_read_count(c, c->tsdf_cnt.p, &hits))) return rc;
+    if (n_hits_out) *n_hits_out = hits;
+    return guard.done();
+}
+
+int icp_set_target_tsdf(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (n_points_out) *n_points_out = 0;
+    int rc;
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_set_target_tsdf"))) return rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    int hits = 0;
+    rc = set_target_tsdf(c, *cam, pose, &hits, "icp_set_target_tsdf");
+    if (rc == ICP_ERR_NO_TARGET) return guard.done(rc);      // (synchronised by the count read)
+    if (rc) return rc;
+    if (n_points_out) *n_points_out = hits;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+
+int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frames, const icp_depth_camera* cam, const icp_depth_options* source_opt,
+                          const float* gt_frames, float pose_inout[16], icp_track_frame* out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!depth_frames || n_frames < 1 || !pose_inout || (n_frames > 1 && !out)) { c->err = "icp_track_depth_model: bad argument"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = tsdf_check_call(c, cam, pose_inout, "icp_track_depth_model"))) return rc;
+    if ((rc = check_depth_args(c, cam, source_opt, "icp_track_depth_model"))) return rc;
+    const icp_params& p = c->prm;
+    if (p.matching == ICP_MATCH_PROJECTIVE && (p.fx != cam->fx || p.fy != cam->fy || p.cx != cam->cx || p.cy != cam->cy || p.width != cam->width || p.height != cam->height)) {
+        c->err = "icp_track_depth_model: the camera of the params differs from the depth camera"; return ICP_ERR_INVALID_ARG;
+    }
+    if ((p.matching == ICP_MATCH_KNN && p.color_icp) || p.weighting == ICP_WEIGHT_COLORS || p.metric == ICP_METRIC_COLORED) {
+        c->err = "icp_track_depth_model: the model has no colours (colour ICP, colour weighting and the colored metric are not supported)"; return ICP_ERR_INVALID_ARG;
+    }
+    if (p.metric == ICP_METRIC_GICP) { c->err = "icp_track_depth_model: GICP is not supported (its per-target covariance pass would run every frame)"; return ICP_ERR_INVALID_ARG; }
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const int n = cam->width * cam->height;
+    if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream, hipStreamNonBlocking));
+    // frame 0 into the model at the incoming pose; frame 1 goes up meanwhile
+    if ((rc = stage_depth(c, 0, depth_frames, nullptr, n, c->stream))) return rc;
+    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose_inout, nullptr))) return rc;
+    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, nullptr, n, c->depth_stream))) return rc;
+    if (gt_frames && n_frames > 1) {
+        if ((rc = ensure(c, c->track_rmse, (size_t)(n_frames - 1) * 8))) return rc;
+        if (!c->pin_track) HIPCK(c, hipHostMalloc((void**)&c->pin_track, 2 * sizeof(PoseState), hipHostMallocDefault));
+    }
+    static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    int first_err = ICP_OK;
+    auto fail = [&](icp_track_frame& r, int status, const char* why) {
+        r.status = status; memcpy(r.pose, pose_inout, 64);
+        if (first_err == ICP_OK) { first_err = status; c->err = why; }
+    };
+    for (int k = 1; k < n_frames; k++) {
+        icp_track_frame& r = out[k - 1];
+        memset(&r, 0, sizeof(r)); r.initial_rmse = r.final_rmse = -1.f;
+        const int slot = k & 1;
+        int hits = 0, kept = 0;
+        // the model seen from the current pose (the count read waits for the stream: the integration of frame k - 1 has left its slot)
+        const int trc = set_target_tsdf(c, *cam, pose_inout, &hits, "icp_track_depth_model");
+        if (trc != ICP_OK && trc != ICP_ERR_NO_TARGET) return trc;
+        if ((rc = depth_to_cloud(c, slot, *cam, *source_opt, false, c->src, false, &kept))) return rc;
+        // frame k + 1 goes up on the second stream while frame k iterates (its slot was last read by frame k - 1, which has finished)
+        if (k + 1 < n_frames && (rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, nullptr, n, c->depth_stream))) return rc;
+        if ((rc = finish_source(c))) return rc;
+        r.n_src = kept;
+        if (trc == ICP_ERR_NO_TARGET) { fail(r, ICP_ERR_NO_TARGET, "icp_track_depth_model: the ray-cast of the model hits nothing"); continue; }
+        if (kept == 0) { fail(r, ICP_ERR_NO_SOURCE, "icp_track_depth_model: a frame keeps no points"); continue; }
+        float* d_rmse = gt_frames ? c->track_rmse.as<float>() + (size_t)(k - 1) * 2 : nullptr;
+        if (gt_frames) {
+            // the convergence reference: the source moved by pose_before^-1 gt_k, composed in fp64 and rounded once
+            double Ri[9], ti[3];
+            invert_affine(pose_inout, Ri, ti);
+            const float* g = gt_frames + (size_t)(k - 1) * 16;
+            Pose16 G; memset(&G, 0, sizeof(G)); G.m[15] = 1.f;
+            for (int rr = 0; rr < 3; rr++) {
+                for (int cc = 0; cc < 3; cc++) G.m[cc * 4 + rr] = (float)((Ri[rr * 3] * g[cc * 4] + Ri[rr * 3 + 1] * g[cc * 4 + 1]) + Ri[rr * 3 + 2] * g[cc * 4 + 2]);
+                G.m[12 + rr] = (float)(((Ri[rr * 3] * g[12] + Ri[rr * 3 + 1] * g[13]) + Ri[rr * 3 + 2] * g[14]) + ti[rr]);
+            }
+            for (DevBuf* pl : {&c->conv_src.x, &c->conv_src.y, &c->conv_src.z, &c->conv_ref.x, &c->conv_ref.y, &c->conv_ref.z}) if ((rc = ensure(c, *pl, (size_t)kept * 4))) return rc;
+            hipLaunchKernelGGL(k_conv_from_source, dim3((kept + 255) / 256), dim3(256), 0, c->stream, c->src.x.as<float>(), c->src.y.as<float>(), c->src.z.as<float>(), kept, G,
+                               c->conv_src.x.as<float>(), c->conv_src.y.as<float>(), c->conv_src.z.as<float>(), c->conv_ref.x.as<float>(), c->conv_ref.y.as<float>(), c->conv_ref.z.as<float>());
+            HIPCK(c, hipGetLastError());
+            c->conv_n = kept;
+            // (pin_track[0] / [1]: rewritten only by the next frame, after set_target_tsdf has synchronised the stream)
+            if ((rc = write_pose_via(c, &c->pin_track[0], identity))) return rc;
+            if ((rc = enqueue_rmse(c, d_rmse))) return rc;
+        }
+        float dT[16]; memcpy(dT, identity, 64);
+        int32_t iters = 0;
+        rc = run_loop(c, dT, nullptr, 0, &iters, false, c->merge_loop);
+        if (rc == ICP_ERR_HIP) return rc;
+        r.iterations = iters; r.status = rc;
+        if (rc != ICP_OK && first_err == ICP_OK) first_err = rc;      // (the message is run_loop's)
+        if (gt_frames) {
+            if ((rc = write_pose_via(c, &c->pin_track[1], dT))) return rc;
+            if ((rc = enqueue_rmse(c, d_rmse + 1))) return rc;
+        }
+        if (r.status == ICP_OK) {
+            compose_pose(pose_inout, dT);
+            if ((rc = tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr))) return rc;
+        }
+        memcpy(r.pose, pose_inout, 64);
+    }
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    HIPCK(c, hipStreamSynchronize(c->depth_stream));
+    if (gt_frames && n_frames > 1) {
+        std::vector<float> h((size_t)(n_frames - 1) * 2);
+        HIPCK(c, hipMemcpy(h.data(), c->track_rmse.p, h.size() * 4, hipMemcpyDeviceToHost));
+        for (int k = 1; k < n_frames; k++) if (out[k - 1].n_src > 0 && out[k - 1].status != ICP_ERR_NO_TARGET) { out[k - 1].initial_rmse = h[(size_t)(k - 1) * 2]; out[k - 1].final_rmse = h[(size_t)(k - 1) * 2 + 1]; }
+    }
+    guard.ok = true;
+    return first_err;
+}
+
+// Not part of icp_hip.h (tools/time_tsdf.py): the device time of ONE integrate (which = 0, the frame staged outside the bracket) or ONE
+// ray-cast to the host-layout arrays (which = 1) between two events on the context's stream.
+extern "C" int icp_debug_tsdf_time(icp_ctx* c, int32_t which, const float* depth, const icp_depth_camera* cam, const float pose[16], float* ms_out) {
+    if (!c || !ms_out || which < 0 || which > 1) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_debug_tsdf_time"))) return rc;
+    if (which == 0 && !depth) return ICP_ERR_INVALID_ARG;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ensure_events(c, 2))) return rc;
+    const size_t n = (size_t)cam->width * cam->height;
+    if (which == 0) {
+        if ((rc = stage_depth(c, 0, depth, nullptr, (int)n, c->stream))) return rc;
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        HIPCK(c, hipEventRecord(c->events[0], c->stream));
+        if ((rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>()))) return rc;
+    } else {
+        if ((rc = ensure(c, c->staging, n * 28))) return rc;
+        float* d = c->staging.as<float>();
+        TsdfRayOut o; memset(&o, 0, sizeof(o));
+        o.depth = d; o.vert = d + n; o.nrm = d + 4 * n;
+        HIPCK(c, hipEventRecord(c->events[0], c->stream));
+        if ((rc = tsdf_raycast_launch(c, *cam, pose, false, o))) return rc;
+    }
+    HIPCK(c, hipEventRecord(c->events[1], c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
+    return guard.done();
+}

@@ -29,6 +29,7 @@
 #include "host_loop.hpp"
 #include "host_multi.hpp"
 #include "host_depth.hpp"
+#include "host_tsdf.hpp"
 #include "host_global.hpp"
 #include "host_debug.hpp"
 
@@ -110,6 +111,7 @@ int icp_ctx_destroy(icp_ctx* c) {
         if (c->depth_up[k]) (void)hipEventDestroy(c->depth_up[k]);
     }
     release(c->depth_blocks); release(c->track_rmse);
+    release(c->tsdf_vox); release(c->tsdf_cnt);
     if (c->pin_track) (void)hipHostFree(c->pin_track);
     if (c->pin_up) (void)hipHostFree(c->pin_up);
     if (c->up_ev) (void)hipEventDestroy(c->up_ev);

@@ -21,6 +21,7 @@ ERR_NAMES = {1: "INVALID_ARG", 2: "HIP", 3: "NO_TARGET", 4: "NO_SOURCE", 5: "NO_
              7: "COLOR_MISMATCH", 8: "NO_CORRESPONDENCES", 9: "NO_DEVICE", 10: "COMM"}
 ERR_NO_CORRESPONDENCES = 8
 ERR_NO_SOURCE = 4
+ERR_NO_TARGET = 3
 
 
 class IcpError(RuntimeError):
@@ -70,6 +71,29 @@ class IcpDepthOptions(C.Structure):
 class IcpTrackFrame(C.Structure):
     _fields_ = [("n_src", C.c_int32), ("iterations", C.c_int32), ("status", C.c_int32), ("initial_rmse", C.c_float), ("final_rmse", C.c_float),
                 ("pose", C.c_float * 16)]
+
+
+class IcpTsdfOptions(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("origin", C.c_float * 3), ("voxel_size", C.c_float), ("truncation", C.c_float), ("max_weight", C.c_float),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("ray_step", C.c_float)]
+
+
+def tsdf_options(dims=None, origin=None, **kw):
+    """icp_tsdf_options: icp_tsdf_options_default (voxel 0.05, truncation 0.25, max weight 64, depth range 0.3 .. 8, ray step truncation / 2)
+    with dims (nx, ny, nz), origin (the centre of voxel (0, 0, 0)) and any other field overridden by name."""
+    o = IcpTsdfOptions()
+    rc = load_library().icp_tsdf_options_default(C.byref(o))
+    if rc != ICP_OK:
+        raise IcpError(rc, "icp_tsdf_options_default")
+    if dims is not None:
+        o.dims[:] = [int(d) for d in dims]
+    if origin is not None:
+        o.origin[:] = [float(x) for x in origin]
+    for k, v in kw.items():
+        if k in ("dims", "origin") or not any(k == f[0] for f in IcpTsdfOptions._fields_):
+            raise TypeError("icp_tsdf_options has no field %r" % k)
+        setattr(o, k, v)
+    return o
 
 
 class IcpLmOptions(C.Structure):
@@ -232,6 +256,8 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_correspond", "icp_iterate", "icp_run", "icp_run_multistart", "icp_get_timing", "icp_get_iteration_times", "icp_set_stage_timing", "icp_set_convergence_reference", "icp_rmse", "icp_benchmark_error",
            "icp_transform_points", "icp_transform_normals", "icp_version", "icp_schedule", "icp_select_hash", "icp_backproject_depth", "icp_estimate_normals",
            "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames", "icp_depth_mesh",
+           "icp_tsdf_options_default", "icp_tsdf_options_check", "icp_tsdf_create", "icp_tsdf_reset", "icp_tsdf_release", "icp_tsdf_download", "icp_tsdf_upload",
+           "icp_tsdf_integrate", "icp_tsdf_raycast", "icp_set_target_tsdf", "icp_track_depth_model",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
@@ -764,6 +790,87 @@ class Context:
         self._ck(self.lib.icp_depth_mesh(self.h, _ptr(depth), _ptr(rgbx), C.byref(cam), None if color_cam is None else C.byref(color_cam),
                                          _ptr(pose_to_c(camera_pose)), C.c_float(edge_threshold), _ptr(verts), _ptr(cols), _ptr(tris), C.byref(nt)))
         return verts, cols, tris[:nt.value]
+
+    def tsdf_create(self, options=None, **kw):
+        """icp_tsdf_create: the context's TSDF volume (frame-to-model tracking), allocated and cleared.  options: an IcpTsdfOptions, or
+        the arguments of `tsdf_options` (dims, origin, voxel_size, truncation, max_weight, min_depth, max_depth, ray_step)."""
+        o = options if options is not None else tsdf_options(**kw)
+        self._ck(self.lib.icp_tsdf_create(self.h, C.byref(o)))
+        self._tsdf_dims = tuple(o.dims)
+
+    def tsdf_reset(self):
+        self._ck(self.lib.icp_tsdf_reset(self.h))
+
+    def tsdf_release(self):
+        self._ck(self.lib.icp_tsdf_release(self.h))
+        self._tsdf_dims = None
+
+    def _tsdf_shape(self):
+        d = getattr(self, "_tsdf_dims", None)
+        if d is None:
+            raise IcpError(1, "no TSDF volume (tsdf_create)")
+        return (d[2], d[1], d[0])
+
+    def tsdf_volume(self):
+        """icp_tsdf_download: (tsdf, weight), two float32 arrays of shape (nz, ny, nx) (x fastest)."""
+        shape = self._tsdf_shape()
+        t = np.empty(shape, np.float32); w = np.empty(shape, np.float32)
+        self._ck(self.lib.icp_tsdf_download(self.h, _ptr(t), _ptr(w)))
+        return t, w
+
+    def tsdf_upload(self, tsdf, weight):
+        """icp_tsdf_upload: replaces the volume's contents (two arrays of nx*ny*nz values, x fastest)."""
+        shape = self._tsdf_shape()
+        t, w = _f32(tsdf), _f32(weight)
+        if t.size != np.prod(shape) or w.size != t.size:
+            raise ValueError("the arrays must hold nx * ny * nz values")
+        self._ck(self.lib.icp_tsdf_upload(self.h, _ptr(t), _ptr(w)))
+
+    def tsdf_integrate(self, depth, cam, pose):
+        """icp_tsdf_integrate: fuses one depth frame, seen from `pose` (4x4 camera -> world), into the volume.  Returns the voxels written."""
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if depth.size != cam.width * cam.height:
+            raise ValueError("depth frame has %d pixels, the camera %d x %d" % (depth.size, cam.width, cam.height))
+        n = C.c_int32(0)
+        self._ck(self.lib.icp_tsdf_integrate(self.h, _ptr(depth), C.byref(cam), _ptr(pose_to_c(pose)), C.byref(n)))
+        return n.value
+
+    def tsdf_raycast(self, cam, pose):
+        """icp_tsdf_raycast: the volume seen from `pose` as an organised cloud in that camera's frame.  Returns (depth (h, w), vertices
+        (w*h, 3), normals (w*h, 3), number of hits); holes are MINF.  The depth image is a valid input of `depth_mesh`."""
+        n = cam.width * cam.height
+        d = np.empty((cam.height, cam.width), np.float32); v = np.empty((n, 3), np.float32); nr = np.empty((n, 3), np.float32); hits = C.c_int32(0)
+        self._ck(self.lib.icp_tsdf_raycast(self.h, C.byref(cam), _ptr(pose_to_c(pose)), _ptr(d), _ptr(v), _ptr(nr), C.byref(hits)))
+        return d, v, nr, hits.value
+
+    def set_target_tsdf(self, cam, pose, check=True):
+        """icp_set_target_tsdf: the ray-cast of the volume from `pose` as the target (organised, with normals).  Returns the number of hits
+        (and the status with check=False)."""
+        n = C.c_int32(0)
+        rc = self.lib.icp_set_target_tsdf(self.h, C.byref(cam), _ptr(pose_to_c(pose)), C.byref(n))
+        if check:
+            self._ck(rc)
+        self.n_tgt = cam.width * cam.height if rc == ICP_OK else 0
+        return n.value if check else (n.value, rc)
+
+    def track_depth_model(self, depth_frames, cam, source_opt, gt=None, pose=None):
+        """icp_track_depth_model: frame-to-model tracking over frames (n, h, w) against the context's TSDF volume.  gt: (n - 1) 4x4 transforms
+        frame k -> world, or None.  pose: the camera -> world pose of frame 0 (identity by default).  Returns (final pose, records, status)."""
+        d = np.ascontiguousarray(depth_frames, dtype=np.float32)
+        nf = d.shape[0]
+        if d.size != nf * cam.width * cam.height:
+            raise ValueError("depth frames do not match the camera size")
+        g = None if gt is None else np.ascontiguousarray(np.stack([pose_to_c(T) for T in gt]) if len(gt) else np.zeros((0, 16)), dtype=np.float32)
+        if g is not None and len(g) != nf - 1:
+            raise ValueError("gt needs one transform per tracked frame")
+        p = pose_to_c(np.eye(4) if pose is None else pose)
+        out = (IcpTrackFrame * max(nf - 1, 1))()
+        rc = self.lib.icp_track_depth_model(self.h, _ptr(d), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
+        if rc not in (ICP_OK, ERR_NO_TARGET, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
+            self._ck(rc)
+        recs = [dict(n_src=out[i].n_src, iterations=out[i].iterations, status=out[i].status, initial_rmse=out[i].initial_rmse,
+                     final_rmse=out[i].final_rmse, pose=pose_from_c(out[i].pose)) for i in range(nf - 1)]
+        return pose_from_c(p), recs, rc
 
     def estimate_normals(self, xyz, k=5, viewpoint=(0.0, 0.0, 0.0)):
         """PointCloud(pcl cloud): k-NN PCA normals flipped towards the viewpoint (PointCloud.h:41-76)."""

@@ -70,7 +70,7 @@ def reconstruct_room_params(params, K=TUM_K, width=TUM_WIDTH, height=TUM_HEIGHT)
     return params
 
 
-def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None, reciprocal=None):
+def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None, reciprocal=None, model=None, options=None):
     """reconstructRoom's loop on the device.  params: the variant's icp_params (metric, matching, colour ICP, weighting, multires, ...;
     ctx.params when None); reconstruct_room_params then sets what reconstructRoom sets on top of them -- 35 iterations, max distance 0.1
     and, for projective matching, the sequence's camera.  Returns (camera poses: the identity for frame 0, then currentCameraToWorld^-1
@@ -79,7 +79,12 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     convergence: dict(rotation=..., translation=...[, min_iterations, patience]) stops every frame's run on a converged pose
     (Context.set_convergence_options; the records' `iterations` say where), False turns that off, None keeps the context's setting.
     reciprocal: True keeps only mutual nearest-neighbour pairs in every frame's run (Context.set_reciprocal_options), False turns that off,
-    None keeps the context's setting."""
+    None keeps the context's setting.
+    model: None tracks every frame against frame 0, as the reference does.  A dict of `binding.tsdf_options` arguments (dims, origin,
+    voxel_size, truncation, ...) tracks frame-to-model instead (icp_track_depth_model): the frames are fused into a TSDF volume created
+    from those options, in frame 0's camera coordinates, and every frame is aligned to a ray-cast of it -- the track survives the camera
+    turning away from frame 0.  The colour frames are not used on that path.
+    options: (target, source) icp_depth_options instead of reconstruct_room_options' choice (the model path uses the source's only)."""
     binding.select_optimizer(ctx, nonlinear)
     binding.select_convergence(ctx, convergence)
     binding.select_reciprocal(ctx, reciprocal)
@@ -88,18 +93,23 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     reconstruct_room_params(ctx.params, seq["K"], seq["width"], seq["height"])
     ctx.push_params()
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
-    tgt_o, src_o = reconstruct_room_options(ctx.params)
+    tgt_o, src_o = reconstruct_room_options(ctx.params) if options is None else options
+    if model is not None:
+        ctx.tsdf_create(**model)
+        _, recs, rc = ctx.track_depth_model(seq["depth"], cam, src_o, gt=seq["gt"] if with_gt else None)
+        poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
+        return poses, recs, rc
     _, recs, rc = ctx.track_depth_frames(seq["depth"], seq["rgbx"], cam, tgt_o, src_o, gt=seq["gt"] if with_gt else None)
     poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
     return poses, recs, rc
 
 
-def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None):
+def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None):
     """reconstructRoom end to end: `track`, then saveRoomToFile (utils.h:179-193) for every scheduled frame k --
     joinMeshes(SimpleMesh(sensor, pose_k, edge_threshold) on the device, SimpleMesh::camera(pose_k, camera_scale), identity) with pose_k
     the camera pose `track` returned (the identity for frame 0).  With out_dir the meshes are written as mesh_<frame index>.off
-    (getCurrentFrameCnt, VirtualSensor.h:142-144).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
-    poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal)
+    (getCurrentFrameCnt, VirtualSensor.h:142-144).  model: as `track` (frame-to-model tracking; the meshes stay per-frame depth meshes).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model)
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)

@@ -555,6 +555,73 @@ int icp_depth_mesh(icp_ctx* ctx, const float* depth, const uint8_t* rgbx, const 
                    const float camera_pose[16], float edge_threshold, float* vertices_out, uint8_t* colors_out, uint32_t* triangles_out,
                    int32_t* n_triangles_out);
 
+/* -------- frame-to-model tracking (an extension): depth frames fused into a truncated signed distance volume, the volume ray-cast as the
+ * target (Newcombe et al., KinectFusion, ISMAR 2011).  DESIGN.md section 6m. --------
+ * icp_track_depth_frames aligns every frame to frame 0 and loses the track when the camera turns away from it; here every tracked frame is
+ * fused into ONE dense volume per context (device-resident, 8 bytes per voxel) and frame k is aligned to a ray-cast of that volume from the
+ * current pose.  With none of these entry points called nothing else in the library changes behaviour.
+ * The world is whatever frame the poses live in.  cam->extrinsics must be the identity (the TUM sensor), else ICP_ERR_INVALID_ARG.  `pose` is
+ * always camera -> world, column-major (currentCameraToWorld).  Every call but create / options_* needs a volume (ICP_ERR_INVALID_ARG).
+ * All fp32 arithmetic is one rounding per operation in the order written (tests/tsdf_restatement.py restates it, compared bit for bit).
+ *
+ * Integrate: M = pose^-1 (affine inverse in fp64, rounded once).  Voxel (i, j, k): p = (o_x + (float)i s, o_y + (float)j s, o_z + (float)k s);
+ *   x_c = (M_00 p_x + (M_01 p_y + M_02 p_z)) + M_03 (y_c, z_c likewise); skipped unless z_c > 0; u = floorf((fx (x_c / z_c) + cx) + 0.5f), v
+ *   likewise; skipped unless 0 <= u < width and 0 <= v < height (tested in float); d = depth[v width + u]; skipped unless d is finite, d > 0 and
+ *   d <= max_depth; sdf = d - z_c; skipped if sdf < -truncation; f = fminf(1, sdf / truncation); D <- (W D + f) / (W + 1), then
+ *   W <- fminf(W + 1, max_weight).  A skipped voxel is neither read nor written.  *n_updated_out (optional): voxels written.
+ * Ray-cast: outputs width*height entries in pixel order, in the ray-casting camera's frame, holes MINF, as an organised depth cloud; any
+ *   output pointer may be NULL.  Pixel (u, v): a = ((float)u - cx) / fx, b = ((float)v - cy) / fy, dw_r = P_r0 a + (P_r1 b + P_r2 1); at
+ *   camera depth z the world point is q_r = P_r3 + z dw_r.  The field at q: g = (q - o) / s per axis, i0 = floor(g), t = g - i0; the sample is
+ *   VALID iff 0 <= i0 <= n - 2 on every axis and all eight corner weights are > 0; F = the nested lerp a + t (b - a) along x, then y, then z.
+ *   The march: z_k = min_depth + (float)k step for every k with z_k <= max_depth; the ray ends at the first k whose sample is valid with
+ *   F_k <= 0 (a NaN never ends a ray); a hit iff k >= 1 and sample k - 1 was valid with F_(k-1) > 0, anything else a hole;
+ *   z* = z_(k-1) + step (F_(k-1) / (F_(k-1) - F_k)).  The normal at q(z*): the analytic gradient of that cell's trilinear interpolant (G_x =
+ *   the lerp over y then z of the four corner differences along x; G_y over x then z; G_z over x then y; an invalid cell: a hole), n_r =
+ *   -(P_0r G_x + (P_1r G_y + P_2r G_z)), normalised as the depth normals are (sq = x x + (y y + z z), / sqrtf(sq)); a non-finite normal: a
+ *   hole.  The normal points away from the camera on a surface seen from the front, as the depth normals (-du, -dv, 1) do.
+ *   Vertex (a z*, b z*, z*), depth z*, *n_hits_out the number of hits. */
+typedef struct icp_tsdf_options {
+    int32_t dims[3];                 /* nx, ny, nz >= 2, nx*ny*nz <= INT32_MAX */
+    float   origin[3];               /* world position of the CENTRE of voxel (0,0,0) */
+    float   voxel_size;              /* > 0 */
+    float   truncation;              /* > 0 */
+    float   max_weight;              /* >= 1 */
+    float   min_depth, max_depth;    /* ray-cast range and integration cut-off, 0 < min < max */
+    float   ray_step;                /* 0 = truncation / 2; must be <= truncation; (max_depth - min_depth) / ray_step <= 2^20 */
+} icp_tsdf_options;
+/* dims 0 (to be set), origin 0, voxel 0.05, truncation 0.25, max weight 64, depth range 0.3 .. 8, ray_step 0. */
+int icp_tsdf_options_default(icp_tsdf_options* opt);
+/* ICP_OK or ICP_ERR_INVALID_ARG for options icp_tsdf_create would refuse; needs neither a context nor a device. */
+int icp_tsdf_options_check(const icp_tsdf_options* opt);
+/* create: allocates the context's volume (replacing an earlier one) and clears it (tsdf 0, weight 0); bad options: ICP_ERR_INVALID_ARG with
+ * a message.  reset clears it, release frees it (icp_ctx_destroy too). */
+int icp_tsdf_create(icp_ctx* ctx, const icp_tsdf_options* opt);
+int icp_tsdf_reset(icp_ctx* ctx);
+int icp_tsdf_release(icp_ctx* ctx);
+/* Two fp32 arrays of nx*ny*nz values, x fastest; either pointer of download may be NULL.  upload: to ray-cast a crafted volume. */
+int icp_tsdf_download(icp_ctx* ctx, float* tsdf_out, float* weight_out);
+int icp_tsdf_upload(icp_ctx* ctx, const float* tsdf, const float* weight);
+int icp_tsdf_integrate(icp_ctx* ctx, const float* depth, const icp_depth_camera* cam, const float pose[16], int32_t* n_updated_out);
+int icp_tsdf_raycast(icp_ctx* ctx, const icp_depth_camera* cam, const float pose[16], float* depth_out, float* vertices_out, float* normals_out,
+                     int32_t* n_hits_out);
+/* The same ray-cast written straight into the target as an organised width*height cloud: what icp_set_target leaves for the arrays
+ * icp_tsdf_raycast returns, with normals and without colours (index build included); only the hit count comes back (*n_points_out,
+ * optional).  No hits: an empty target and ICP_ERR_NO_TARGET.  Source, params and convergence reference stay untouched. */
+int icp_set_target_tsdf(icp_ctx* ctx, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out);
+/* Frame-to-model tracking; records as icp_track_depth_frames, one per frame k >= 1.  Frame 0 is integrated at pose_inout.  Frame k:
+ * icp_set_target_tsdf at the current pose; frame k becomes the source (source_opt, no colours); one icp_run from the IDENTITY gives dT.  On
+ * ICP_OK pose <- pose dT (the fp64 product, each element ((P_r0 D_0c + P_r1 D_1c) + P_r2 D_2c) + P_r3 D_3c, rounded once) and frame k is
+ * integrated at the new pose.  A model without hits (ICP_ERR_NO_TARGET), a frame that keeps no points (ICP_ERR_NO_SOURCE) or a failed run
+ * (its status): the pose is carried, the frame is not integrated, the status is recorded, tracking goes on; the first error in frame order
+ * is returned.  gt_frames: as icp_track_depth_frames (frame k's camera -> the world of pose_inout's first value); the convergence reference
+ * of frame k is its source moved by pose_before^-1 gt_k (fp64, rounded once), initial_rmse is taken at the identity, final_rmse at dT.
+ * Frame k + 1 goes up while frame k iterates.  With ICP_MATCH_PROJECTIVE the params' camera must equal cam.  Runs with whatever icp_run
+ * accepts on such a pair (the non-linear optimiser, robust mode, reciprocal rejection, the convergence stop, the selections);
+ * ICP_ERR_INVALID_ARG (see icp_last_error) for what needs target colours (colour ICP, colour weighting, ICP_METRIC_COLORED) and for
+ * ICP_METRIC_GICP, whose per-target covariance pass would run every frame. */
+int icp_track_depth_model(icp_ctx* ctx, const float* depth_frames, int32_t n_frames, const icp_depth_camera* cam,
+                          const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out);
+
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
  * towards the viewpoint.  k in {3..8} (else ICP_ERR_INVALID_ARG).  Non-finite points, and every point of a cloud with fewer than

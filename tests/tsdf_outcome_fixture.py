@@ -1,0 +1,84 @@
+"""The outcome fixture of frame-to-model tracking (tests/test_gpu_tsdf.py): a 60 degree pan of the synthetic room, 41
+frames of 320 x 240, which frame-to-frame-0 tracking cannot follow.  `fixture()` builds the frames; run as a script (CPU only, about two
+minutes) it tracks them with the numpy restatement's ray-cast and integrate and the oracle's ICP, and writes the worst rotation and
+translation error to tests/golden/tsdf_outcome.json -- the reference the device's bound is twice of."""
+import json
+import os
+import sys
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+f32 = np.float32
+N_FRAMES, W, H = 41, 320, 240
+VOLUME = dict(dims=(141, 69, 177), origin=(-3.3, -1.7, -1.6), voxel_size=0.05, truncation=0.25, max_weight=64.0, min_depth=0.3, max_depth=8.0, ray_step=0.0)
+SOURCE_FACTOR = 16
+GOLDEN = os.path.join(HERE, "golden", "tsdf_outcome.json")
+
+
+def tum_K(width):
+    s = width / 640.0
+    return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], f32)
+
+
+def fixture(n_frames=N_FRAMES):
+    """(K, depth (n, H, W) with MINF holes, gt: n - 1 transforms frame k -> frame 0)."""
+    from icp_amd import synth
+    K = tum_K(W)
+    T = [synth.camera_pose(0) @ synth.make_pose((0, np.deg2rad(1.5 * k), 0), (0.01 * k, 0, 0)) for k in range(n_frames)]
+    depth = [synth.depth_frame(Tk, K.astype(np.float64), W, H, 0x7A11 + k, 0.05)[0][:, 2].reshape(H, W).copy() for k, Tk in enumerate(T)]
+    gt = [(np.linalg.inv(T[0]) @ Tk).astype(f32) for Tk in T[1:]]
+    return K, np.stack(depth), gt
+
+
+def pose_error(A, B):
+    A = np.asarray(A, np.float64); B = np.asarray(B, np.float64)
+    R = A[:3, :3] @ B[:3, :3].T
+    s = 0.5 * np.linalg.norm([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    return float(np.arctan2(s, (np.trace(R) - 1) / 2)), float(np.linalg.norm(A[:3, 3] - B[:3, 3]))
+
+
+def worst_errors(poses, gt):
+    """Worst (rotation [rad], translation [m]) error over frames 1 .. n - 1, and the last frame's pair."""
+    errs = [pose_error(P, G) for P, G in zip(poses[1:], gt)]
+    return max(e[0] for e in errs), max(e[1] for e in errs), errs[-1]
+
+
+def restatement_track(orc):
+    import tsdf_restatement as TS
+    K, depth, gt = fixture()
+    cam = TS.Camera(K, W, H)
+    vol = TS.Volume(**VOLUME)
+    prm = orc.make_params(metric=1, matching=0, weighting=0, rejection=1, n_iterations=35, max_distance=0.1, solver_mode=1, knn_kdtree=1)
+    eye = np.eye(4, dtype=f32)
+
+    def source_of(k):
+        xyz, nrm, _, valid = orc.backproject(depth[k], None, K, max_distance=0.1)
+        idx = np.arange(0, W * H, SOURCE_FACTOR)
+        sel = idx[valid[idx]]
+        return xyz[sel], nrm[sel]
+
+    def estimate(src, tgt):
+        ok = np.isfinite(tgt[0]).all(1) & np.isfinite(tgt[1]).all(1)
+        try:
+            dT, _ = orc.estimate_pose(prm, src[0], src[1], None, tgt[0][ok], tgt[1][ok], None, eye)
+        except RuntimeError:
+            return None
+        return dT if np.isfinite(dT).all() else None
+    poses = TS.track(vol, depth, cam, eye, source_of, estimate)
+    return poses, gt
+
+
+if __name__ == "__main__":
+    root = os.path.abspath(os.path.join(HERE, ".."))
+    for p in (root, os.path.join(root, "icp-variants_amd", "python"), HERE):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    from oracle import oracle
+    oracle.build()
+    poses, gt = restatement_track(oracle)
+    rot, tr, last = worst_errors(poses, gt)
+    out = dict(worst_rotation_rad=rot, worst_translation_m=tr, last_rotation_rad=last[0], last_translation_m=last[1], frames=N_FRAMES, width=W, height=H)
+    print(json.dumps(out))
+    with open(GOLDEN, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")

@@ -1,0 +1,106 @@
+"""Frame-to-model tracking on the clock, on the synthetic room at 640 x 480:
+  kernels : device time of one icp_tsdf_integrate and of one icp_tsdf_raycast launch (events around the launch, icp_debug_tsdf_time) for a
+            256^3 and a 512^3 volume over the same 8.96 m cube (voxel 35 mm / 17.5 mm, truncation 5 voxels), from a volume holding 4 frames
+  tracking: frames/s of icp_track_depth_model (256^3) against icp_track_depth_frames on the 12-frame sequence of
+            tools/time_depth_tracking.py, same params (point-to-plane k-NN on the LBVH, 35 iterations, max distance 0.1, source (false, 8))
+Repeats are interleaved (every configuration once per round) and the median is reported.  Stage timing is off.
+usage: python tools/time_tsdf.py [--reps 9] [--frames 12] [--skip-512] [--json out.json]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "icp-variants_amd", "python"))
+import numpy as np
+from icp_amd import binding, synth, tum
+
+EXTENT, ORIGIN = 8.96, (-4.2, -4.5, -1.5)          # camera-0 coordinates: the room spans x -2.7 .. 3.3, y -1.3 .. 1.3, z -1.2 .. 6.8
+
+
+def volume_options(n):
+    s = EXTENT / n
+    return dict(dims=(n, n, n), origin=tuple(o + s / 2 for o in ORIGIN), voxel_size=s, truncation=5 * s)
+
+
+def median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--frames", type=int, default=12)
+    ap.add_argument("--skip-512", action="store_true")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    W, H = tum.TUM_WIDTH, tum.TUM_HEIGHT
+    K = tum.TUM_K
+    T = [synth.camera_pose(k) for k in range(a.frames)]
+    depth = np.stack([synth.depth_frame(Tk, K.astype(np.float64), W, H, 0x7A11 + k, 0.05)[0][:, 2].reshape(H, W).copy() for k, Tk in enumerate(T)])
+    gt = [(np.linalg.inv(T[0]) @ Tk).astype(np.float32) for Tk in T]
+    cam = binding.depth_camera(K, W, H)
+    lib = binding.load_library()
+    out = dict(width=W, height=H, reps=a.reps, frames=a.frames, kernels={})
+
+    # kernels
+    sizes = [256] if a.skip_512 else [256, 512]
+    ctxs = {}
+    for n in sizes:
+        c = binding.Context(0)
+        c.tsdf_create(**volume_options(n))
+        updated = [c.tsdf_integrate(depth[k], cam, gt[k]) for k in range(4)]
+        _, _, _, hits = c.tsdf_raycast(cam, gt[1])
+        ctxs[n] = c
+        out["kernels"][str(n)] = dict(voxel_size=EXTENT / n, updated_voxels=updated[-1], hits=hits, integrate_ms=[], raycast_ms=[])
+    d2 = np.ascontiguousarray(depth[2], np.float32); p2 = binding.pose_to_c(gt[2])
+    for rep in range(a.reps + 1):                       # the first round warms up
+        for n in sizes:
+            for which, key in ((0, "integrate_ms"), (1, "raycast_ms")):
+                ms = C.c_float(0)
+                ctxs[n]._ck(lib.icp_debug_tsdf_time(ctxs[n].h, C.c_int32(which), binding._ptr(d2), C.byref(cam), binding._ptr(p2), C.byref(ms)))
+                if rep:
+                    out["kernels"][str(n)][key].append(ms.value)
+    for n in sizes:
+        r = out["kernels"][str(n)]
+        r["integrate_ms_median"] = median(r["integrate_ms"]); r["raycast_ms_median"] = median(r["raycast_ms"])
+        r["integrate_gb_per_s"] = r["updated_voxels"] * 16 / (r["integrate_ms_median"] * 1e-3) / 1e9      # 16 bytes per updated voxel
+        ctxs[n].close()
+
+    # tracking
+    ctx = binding.Context(0)
+    ctx.params.metric = 1; ctx.params.knn_backend = 1
+    tum.reconstruct_room_params(ctx.params)
+    ctx.push_params(); ctx.set_stage_timing(0)
+    to, so = tum.reconstruct_room_options(ctx.params)
+    rgbx = np.zeros((a.frames, W * H, 4), np.uint8)
+    times = dict(model=[], frame0=[])
+    err = {}
+    for rep in range(a.reps + 1):
+        for route in ("model", "frame0"):
+            t0 = time.perf_counter()
+            if route == "model":
+                ctx.tsdf_create(**volume_options(256))
+                pose, recs, rc = ctx.track_depth_model(depth, cam, so)
+            else:
+                pose, recs, rc = ctx.track_depth_frames(depth, None, cam, to, so)
+            dt = time.perf_counter() - t0
+            if rep:
+                times[route].append(dt)
+            err[route] = dict(status=rc, iterations=[r["iterations"] for r in recs],
+                              final_translation_error_m=float(np.linalg.norm(pose[:3, 3].astype(np.float64) - gt[-1][:3, 3])))
+    n = a.frames - 1
+    out["tracking"] = {k: dict(median_s=median(v), frames_per_s_median=n / median(v), frames_per_s_best=n / min(v), **err[k]) for k, v in times.items()}
+    print(json.dumps(out))
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        json.dump(out, open(a.json, "w"), indent=1)
+    ctx.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
