@@ -1,6 +1,6 @@
 // host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
 // and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
-// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_global, host_debug.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_tsdf_mesh, host_global, host_debug.
 using namespace icpdev;
 
 #define HIPCK(ctx, expr)                                                                        \
@@ -120,6 +120,7 @@ struct icp_ctx {
     DevBuf depth_blocks, track_rmse;     // block counts / offsets of the depth compaction; per-frame initial + final RMSE of a tracked sequence
     PoseState* pin_track = nullptr;      // page-locked pose staging of a tracked frame's initial / final RMSE: two slots of its own, apart from `pinned`
     DevBuf tsdf_vox, tsdf_cnt; bool tsdf_on = false; icp_tsdf_options tsdf_opt;   // the TSDF volume of frame-to-model tracking (host_tsdf.hpp): (tsdf, weight) per voxel, the update / hit counter, its options (ray_step resolved)
+    DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
     float cos_reject = 0.5f;
     std::vector<hipEvent_t> events;
     hipEvent_t build_ev[2] = {nullptr, nullptr};   // index-build bracket (build_bvh)

@@ -132,6 +132,7 @@ int icp_tsdf_release(icp_ctx* c) {
     if ((rc = set_device(c))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
     release(c->tsdf_vox);
+    for (DevBuf* d : {&c->tm_bits, &c->tm_mask, &c->tm_base, &c->tm_blk, &c->tm_out}) release(*d);      // the mesh extraction's scratch goes with the volume
     c->tsdf_on = false;
     return ICP_OK;
 }

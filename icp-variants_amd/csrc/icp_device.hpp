@@ -8,7 +8,7 @@
 //
 // Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_converge.hpp, dev_solve.hpp,
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
-// dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf.hpp
+// dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -47,6 +47,8 @@
 //                       iteration between the matcher and the post stage (dev_reciprocal.hpp)
 //   k_tsdf_integrate /  frame-to-model tracking (icp_track_depth_model): depth frames fused into a truncated signed distance volume, and
 //   k_tsdf_raycast      the volume ray-cast from a pose as an organised cloud, to the host or straight into the target (dev_tsdf.hpp)
+//   k_tm_*              the zero level set of that volume as an indexed triangle mesh (icp_tsdf_mesh): marching tetrahedra on the Kuhn
+//                       triangulation of every cell, as bitmap passes and a stable two-pass compaction (dev_tsdf_mesh.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -79,5 +81,6 @@ namespace icpdev {
 #include "dev_fpfh.hpp"
 #include "dev_reciprocal.hpp"
 #include "dev_tsdf.hpp"
+#include "dev_tsdf_mesh.hpp"
 
 }  // namespace icpdev

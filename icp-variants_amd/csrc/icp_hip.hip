@@ -30,6 +30,7 @@
 #include "host_multi.hpp"
 #include "host_depth.hpp"
 #include "host_tsdf.hpp"
+#include "host_tsdf_mesh.hpp"
 #include "host_global.hpp"
 #include "host_debug.hpp"
 
@@ -112,6 +113,7 @@ int icp_ctx_destroy(icp_ctx* c) {
     }
     release(c->depth_blocks); release(c->track_rmse);
     release(c->tsdf_vox); release(c->tsdf_cnt);
+    for (DevBuf* d : {&c->tm_bits, &c->tm_mask, &c->tm_base, &c->tm_blk, &c->tm_out}) release(*d);
     if (c->pin_track) (void)hipHostFree(c->pin_track);
     if (c->pin_up) (void)hipHostFree(c->pin_up);
     if (c->up_ev) (void)hipEventDestroy(c->up_ev);

@@ -257,7 +257,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_transform_points", "icp_transform_normals", "icp_version", "icp_schedule", "icp_select_hash", "icp_backproject_depth", "icp_estimate_normals",
            "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames", "icp_depth_mesh",
            "icp_tsdf_options_default", "icp_tsdf_options_check", "icp_tsdf_create", "icp_tsdf_reset", "icp_tsdf_release", "icp_tsdf_download", "icp_tsdf_upload",
-           "icp_tsdf_integrate", "icp_tsdf_raycast", "icp_set_target_tsdf", "icp_track_depth_model",
+           "icp_tsdf_integrate", "icp_tsdf_raycast", "icp_set_target_tsdf", "icp_track_depth_model", "icp_tsdf_mesh",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
@@ -842,6 +842,18 @@ class Context:
         d = np.empty((cam.height, cam.width), np.float32); v = np.empty((n, 3), np.float32); nr = np.empty((n, 3), np.float32); hits = C.c_int32(0)
         self._ck(self.lib.icp_tsdf_raycast(self.h, C.byref(cam), _ptr(pose_to_c(pose)), _ptr(d), _ptr(v), _ptr(nr), C.byref(hits)))
         return d, v, nr, hits.value
+
+    def tsdf_mesh(self, min_weight=0.0):
+        """icp_tsdf_mesh: the zero level set of the volume as an indexed triangle mesh, extracted on the device (a counting call, then a
+        filling call).  min_weight: voxels below this weight count as unobserved.  Returns (vertices (V, 3) f32 in the world frame,
+        normals (V, 3) f32 pointing into free space, triangles (T, 3) u32, counter-clockwise seen from free space)."""
+        nv, nt = C.c_int32(0), C.c_int32(0)
+        mw = C.c_float(min_weight)
+        self._ck(self.lib.icp_tsdf_mesh(self.h, mw, C.c_int32(0), C.c_int32(0), None, None, None, C.byref(nv), C.byref(nt)))
+        v = np.empty((nv.value, 3), np.float32); n = np.empty((nv.value, 3), np.float32); t = np.empty((nt.value, 3), np.uint32)
+        if nv.value or nt.value:
+            self._ck(self.lib.icp_tsdf_mesh(self.h, mw, C.c_int32(nv.value), C.c_int32(nt.value), _ptr(v), _ptr(n), _ptr(t), C.byref(nv), C.byref(nt)))
+        return v, n, t
 
     def set_target_tsdf(self, cam, pose, check=True):
         """icp_set_target_tsdf: the ray-cast of the volume from `pose` as the target (organised, with normals).  Returns the number of hits

@@ -6,6 +6,7 @@ accumulated in file order; colours of mesh-derived clouds are all zero (PointClo
 Pre-processing outside the timed ICP loop -- plain numpy, fp32.
 write_off / camera_glyph / join_meshes follow writeMesh, camera and joinMeshes (SimpleMesh.h:231-302,336-359): the output side of
 saveRoomToFile (utils.h:179-193).  A mesh is a tuple (vertices (V,3) f32, colors (V,4) u8, triangles (T,3) u32).
+write_ply_mesh / load_ply_mesh: the mesh of the fused model (Context.tsdf_mesh: vertices, normals, triangles) as a binary PLY.
 """
 import numpy as np
 
@@ -106,3 +107,48 @@ def write_off(path, vertices, colors, triangles):
         f.write("COFF\n%d %d 0\n" % (len(v), len(t)))
         f.write("".join(line.tolist()) % tuple(values))
         f.write(("3 %d %d %d\n" * len(t)) % tuple(t.ravel().tolist()))
+
+
+PLY_MESH_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                   "property float nx\nproperty float ny\nproperty float nz\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n")
+_PLY_FACE = np.dtype([("n", "u1"), ("idx", "<i4", (3,))])
+
+
+def write_ply_mesh(path, vertices, normals, triangles):
+    """A triangle mesh with per-vertex normals as a binary little-endian PLY: `float` x y z nx ny nz per vertex, a `uchar int` index list per face."""
+    v = np.asarray(vertices, np.float32).reshape(-1, 3)
+    n = np.asarray(normals, np.float32).reshape(-1, 3)
+    t = np.asarray(triangles, np.uint32).reshape(-1, 3)
+    if len(n) != len(v):
+        raise ValueError("one normal per vertex")
+    if len(t) and int(t.max()) > 0x7FFFFFFF:
+        raise ValueError("a vertex index does not fit the PLY's int")
+    faces = np.empty(len(t), _PLY_FACE)
+    faces["n"] = 3; faces["idx"] = t.astype("<i4")
+    with open(path, "wb") as f:
+        f.write((PLY_MESH_HEADER % (len(v), len(t))).encode("ascii"))
+        f.write(np.concatenate([v, n], axis=1).astype("<f4").tobytes())
+        f.write(faces.tobytes())
+
+
+def load_ply_mesh(path):
+    """Reads what write_ply_mesh writes.  Returns (vertices (V,3) f32, normals (V,3) f32, triangles (T,3) u32)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or lines[1] != "format binary_little_endian 1.0":
+        raise ValueError("not a binary little-endian PLY")
+    nv = nt = None
+    for ln in lines:
+        if ln.startswith("element vertex "):
+            nv = int(ln.split()[2])
+        elif ln.startswith("element face "):
+            nt = int(ln.split()[2])
+    if data[:end].decode("ascii") != PLY_MESH_HEADER % (nv, nt):
+        raise ValueError("not the layout write_ply_mesh writes")
+    vn = np.frombuffer(data, "<f4", nv * 6, end).reshape(nv, 6)
+    faces = np.frombuffer(data, _PLY_FACE, nt, end + nv * 24)
+    if nt and not (faces["n"] == 3).all():
+        raise ValueError("We can only read triangular mesh.")
+    return vn[:, :3].astype(np.float32), vn[:, 3:].astype(np.float32), faces["idx"].astype(np.uint32).reshape(nt, 3)

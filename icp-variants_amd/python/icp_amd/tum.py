@@ -5,6 +5,7 @@ Pure host logic over `formats.py`; the tracking itself is one library call (`icp
   tgt_o, src_o   = reconstruct_room_options(params)           # the reference's choice of clouds, 35 iterations, max distance 0.1
   poses, recs    = track(ctx, seq, params)                    # estimatedPoses (currentCameraToWorld^-1 per frame) + per-frame records
   reconstruct_room(ctx, seq, params, out_dir)                 # track + saveRoomToFile per frame: mesh_<frame>.off (utils.h:179-193)
+  reconstruct_room(..., model=..., model_mesh="model.ply")     # frame-to-model tracking, and the fused volume as one mesh
 Layout on disk, as the reference expects it under Data/: <tum_dir>/depth.txt, rgb.txt, groundtruth.txt and the PNGs they list (TUM RGB-D).
 `write_synthetic_sequence` writes that layout from `synth.depth_frame` / `synth.camera_pose`, for the tests and for rehearsing a real
 freiburg1_xyz run offline.
@@ -104,11 +105,13 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     return poses, recs, rc
 
 
-def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None):
+def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None, model_mesh=None):
     """reconstructRoom end to end: `track`, then saveRoomToFile (utils.h:179-193) for every scheduled frame k --
     joinMeshes(SimpleMesh(sensor, pose_k, edge_threshold) on the device, SimpleMesh::camera(pose_k, camera_scale), identity) with pose_k
     the camera pose `track` returned (the identity for frame 0).  With out_dir the meshes are written as mesh_<frame index>.off
-    (getCurrentFrameCnt, VirtualSensor.h:142-144).  model: as `track` (frame-to-model tracking; the meshes stay per-frame depth meshes).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    (getCurrentFrameCnt, VirtualSensor.h:142-144).  model: as `track` (frame-to-model tracking; the meshes stay per-frame depth meshes).
+    model_mesh: with `model` and `out_dir`, a file name: the fused volume's zero level set (Context.tsdf_mesh, in frame 0's camera coordinates) is
+    written there as a binary PLY after the last frame -- the reconstructed room as ONE mesh; None writes nothing more.  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
     poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model)
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     if out_dir is not None:
@@ -123,6 +126,8 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
             path = os.path.join(out_dir, "mesh_%d.off" % seq["frames"][k])
             meshio.write_off(path, *mesh)
             out.append(path)
+    if model is not None and model_mesh is not None and out_dir is not None:
+        meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh())
     return poses, recs, rc, out
 
 

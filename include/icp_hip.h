@@ -622,6 +622,46 @@ int icp_set_target_tsdf(icp_ctx* ctx, const icp_depth_camera* cam, const float p
 int icp_track_depth_model(icp_ctx* ctx, const float* depth_frames, int32_t n_frames, const icp_depth_camera* cam,
                           const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out);
 
+/* -------- the model as a mesh (an extension): the zero level set of the context's volume as an indexed triangle mesh with per-vertex
+ * normals, extracted on the device; only the mesh crosses to the host.  DESIGN.md section 6n. --------
+ * Method: every cell is cut into the six tetrahedra of the Kuhn (Freudenthal) triangulation and each tetrahedron is marched on its own;
+ * there are no ambiguous cases and neighbouring cells agree on their shared faces, so the mesh of a closed surface is closed and
+ * consistently oriented (about twice the triangles of marching cubes).  All fp32, one rounding per operation in the order written
+ * (tests/tsdf_mesh_restatement.py restates it, compared bit for bit).
+ * Definitions: a voxel is OBSERVED iff W > 0, W >= min_weight and F is finite (min_weight finite and >= 0; at 0 this is the ray-cast's rule
+ *   plus the finiteness test); cell (i, j, k), 0 <= i <= nx - 2 and likewise on the other axes, is VALID iff its eight corners are observed;
+ *   a voxel is NEGATIVE iff F < 0.f (zero is not negative).
+ * Tetrahedra: tetrahedron pi (a permutation of the axes) of a cell has the corners q0 = (0,0,0), q1 = e_pi0, q2 = e_pi0 + e_pi1,
+ *   q3 = (1,1,1); the six come in lexicographic order of pi: xyz, xzy, yxz, yzx, zxy, zyx.  Local edges (0,1), (0,2), (0,3), (1,2), (1,3),
+ *   (2,3) have the ranks 0..5.  Case mask m: bit a set iff q_a is negative; m = 0 and m = 15 give nothing.  One corner alone on its side:
+ *   one triangle, its three edges in ascending rank.  Two and two (negatives a < b, positives c < d): the quad cycle (a,c), (a,d), (b,d),
+ *   (b,c), rotated to start at its smallest rank, as the triangles (e0, e1, e2) and (e0, e2, e3).  Orientation: with every crossing put at
+ *   its edge's midpoint, if the normal of the first triangle (right-hand rule; of the second if the first is degenerate) has a negative dot
+ *   product with (mean of the positive corners - mean of the negative corners), the order is reversed keeping the first edge: e0 e2 e1, or
+ *   e0 e3 e2 e1.  Triangles are therefore counter-clockwise seen from free space (F > 0).
+ * Vertices: every tetrahedron edge runs from a voxel v = (i, j, k) to v + d, d in {0,1}^3 \ {0}; it is owned by v under the code
+ *   d_x + 2 d_y + 4 d_z (1..7: three axis edges, three face diagonals, the body diagonal; all seven lie in cell v).  An edge carries a
+ *   vertex iff exactly one of its ends is negative and at least one valid cell contains it, so every vertex is used by a triangle.  Order:
+ *   ascending owner index (k ny + j) nx + i, then ascending code.  Position: t = F_v / (F_v - F_(v+d)), ts = t s; on axes with d_r = 1
+ *   p_r = (o_r + (float)i_r s) + ts, on the others p_r = o_r + (float)i_r s.
+ * Normals: of the valid cells that contain the edge -- the cells v - off, off_r in {0,1} only on axes with d_r = 0, inside the cell range --
+ *   the first in ascending off_x + 2 off_y + 4 off_z; the analytic gradient G of its trilinear interpolant at the local fractions
+ *   t_r = d_r ? t : (float)off_r, by the ray-cast's formula and lerp order; n = G / sqrtf(Gx Gx + (Gy Gy + Gz Gz)), in the WORLD frame,
+ *   pointing into free space -- the opposite sign convention from icp_tsdf_raycast's camera-frame normal, which points away from the camera,
+ *   into the surface.  A non-finite normal is written as (0, 0, 0).
+ * Triangles: ascending cell index (x fastest over the (nx-1)(ny-1)(nz-1) cells), valid cells only, then tetrahedron order, then the table's
+ *   order; three uint32 vertex indices each.  An exact 0 in the field gives t = 0 or 1: coincident vertices with DISTINCT indices and
+ *   zero-area triangles, which are kept; index triples are never degenerate.
+ * Calling: *n_vertices_out and *n_triangles_out are always written.  With vertices_out, normals_out and triangles_out all NULL the call only
+ *   counts (ICP_OK).  normals_out alone may be NULL.  vertices_out / normals_out: room for max_vertices * 3 floats, triangles_out for
+ *   max_triangles * 3 indices; a count above its capacity: ICP_ERR_INVALID_ARG, a message with both counts, nothing written to the arrays.
+ *   No volume, a bad min_weight, or a volume of more than INT32_MAX / 12 voxels (a cell gives at most 12 triangles; 512^3 fits):
+ *   ICP_ERR_INVALID_ARG.  An empty mesh: ICP_OK with 0 and 0.  Volume, target, source, index, params and convergence reference stay
+ *   untouched; scratch comes from the context (1.4375 bytes per voxel, freed with the volume). */
+int icp_tsdf_mesh(icp_ctx* ctx, float min_weight, int32_t max_vertices, int32_t max_triangles,
+                  float* vertices_out, float* normals_out, uint32_t* triangles_out,
+                  int32_t* n_vertices_out, int32_t* n_triangles_out);
+
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
  * towards the viewpoint.  k in {3..8} (else ICP_ERR_INVALID_ARG).  Non-finite points, and every point of a cloud with fewer than
