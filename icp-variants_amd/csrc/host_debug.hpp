@@ -99,6 +99,94 @@ int icp_debug_poison_handover(icp_ctx* c, int32_t slot, double value) {
     return ICP_OK;
 }
 
+//   icp_debug_loop_sums       : the 34 sums the LOOP reduced, which no entry point of icp_hip.h returns (icp_correspond never fuses: its sums
+//                               come from k_post + k_reduce_solve whatever the matcher).  Runs iteration `iteration` of the plan icp_run makes
+//                               for the context's clouds and params (make_plan: the level's cloud or its `sel` list, its Morton order), at
+//                               `pose`, unseeded, in the form asked for, whatever ICP_HIP_MERGE says:
+//                                 form 0, separate: the launches of enqueue_separate's loop body -- launch_match allowed to fuse, then
+//                                   launch_post_and_solve with SolveParams::sums_out set (k_reduce_solve's optional copy).  Every linear
+//                                   configuration takes it.
+//                                 form 1, merged: enqueue_merged itself on a run of two iterations (the one asked for, then the plan's next, or
+//                                   the same again behind the last): k_knn_bvh_post_ring, the reducer of the first riding in front of the
+//                                   second's matcher blocks, the closing k_ring_reduce_solve.  The sums are row 0 of the totals ring, read
+//                                   back after the run (a granule is the double's bits; the writer flips bit 0 of an all-ones NaN only).
+//                                   Refused (ICP_ERR_INVALID_ARG) unless run_loop would merge: k-NN matching on the LBVH backend,
+//                                   point-to-plane, no random resampling (selection 0, or 2 held), a plan of >= 2 iterations none of which is
+//                                   empty, no rmse / benchmark-error recording.
+//                               Both refuse the non-linear optimiser, robust mode and reciprocal rejection (their loops run other chains).
+//                               sums_out[64]: the layout of icp_correspond's.  pose_out: the pose the iteration composed.  route_out[4]:
+//                               kernel family that accumulated (0 k_post / k_post_gicp / k_post_colored, 1 k_knn_bvh_post, 2
+//                               k_knn_bvh_post_ring), DIM of the matcher, WIDE (0 / 1; -1 for the brute-force and projective matchers), and the
+//                               fault word of the composed pose slot (merged: 2 = the rank guard failed and run_loop would repeat the run in
+//                               the separate form; the sums are the ring's all the same, pose_out is the incoming pose, n_valid sums[0]).
+int icp_debug_loop_sums(icp_ctx* c, const float pose[16], int32_t form, int32_t iteration, double* sums_out, int32_t* n_valid_out, float* pose_out, int32_t* route_out) {
+    if (!c || !pose || !sums_out || !n_valid_out || !pose_out || !route_out || (form != 0 && form != 1)) { if (c) c->err = "icp_debug_loop_sums: bad argument"; return ICP_ERR_INVALID_ARG; }
+    const icp_params& p = c->prm;
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = check_ready(c, true, true))) return rc;
+    if ((rc = gicp_prepare(c))) return rc;
+    if ((rc = colored_prepare(c))) return rc;
+    if (c->lm_on || robust_on(c) || reciprocal_on(c)) { c->err = "icp_debug_loop_sums: the non-linear optimiser, robust mode and reciprocal rejection run other chains"; return ICP_ERR_INVALID_ARG; }
+    RunPlan pl;
+    if ((rc = make_plan(c, false, pl))) return rc;
+    const int iters = pl.iters(), it = iteration;
+    if (it < 0 || it >= iters || pl.ns[it] <= 0) { c->err = "icp_debug_loop_sums: no such iteration in the plan, or it has no queries"; return ICP_ERR_INVALID_ARG; }
+    const bool colors = p.color_icp != 0 && p.matching == ICP_MATCH_KNN;
+    const bool lbvh = p.matching == ICP_MATCH_KNN && p.knn_backend == ICP_KNN_LBVH;
+    double hs[NSUM]; icp_iter_stats st; memset(&st, 0, sizeof(st)); PoseState hp; int family = 0;
+    if (form == 0) {
+        if ((rc = ensure(c, c->stats, 512)) || (rc = ensure(c, c->sums, NSUM * 8))) return rc;
+        if ((rc = rearm_handover(c))) return rc;
+        if ((rc = write_pose(c, pose))) return rc;
+        QuerySet q{pl.clouds[it], pl.sels[it], pl.ns[it], 0, colors, false, pl.orders[it], false};
+        int fused = 0;
+        if ((rc = launch_match(c, q, &fused))) return rc;
+        if ((rc = launch_post_and_solve(c, *pl.clouds[it], pl.sels[it], pl.ns[it], c->stats.as<icp_iter_stats>(), c->sums.as<double>(), 1, nullptr, fused, nullptr))) return rc;
+        family = fused ? 1 : 0;
+        HIPCK(c, hipMemcpyAsync(hs, c->sums.p, NSUM * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipMemcpyAsync(&st, c->stats.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipMemcpyAsync(&hp, c->ps.p, sizeof(hp), hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (hp.fault) { c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
+    } else {
+        const bool rec = (p.record_rmse & 3) && c->conv_n > 0;
+        bool merged = iters >= 2 && pl.sorted_levels && p.metric == ICP_METRIC_POINT_TO_PLANE && !rec;
+        for (int i = 0; merged && i < iters; i++) if (pl.ns[i] <= 0) merged = false;
+        if (!merged) { c->err = "icp_debug_loop_sums: the loop of this configuration does not take the merged form"; return ICP_ERR_INVALID_ARG; }
+        const int two[2] = {it, it + 1 < iters ? it + 1 : it};
+        LoopRun r{};
+        r.pl.sorted_levels = pl.sorted_levels; r.pl.fixed_sets = pl.fixed_sets;
+        for (int k : two) { r.pl.factors.push_back(pl.factors[k]); r.pl.ns.push_back(pl.ns[k]); r.pl.clouds.push_back(pl.clouds[k]); r.pl.sels.push_back(pl.sels[k]); r.pl.orders.push_back(pl.orders[k]); }
+        r.pin_pose = r.pin_stats + (((size_t)2 * sizeof(icp_iter_stats) + 255) & ~(size_t)255); r.pin_lm = r.pin_pose + 512;
+        if ((rc = ensure_pinned(c, r.pin_lm))) return rc;
+        if ((rc = write_pose(c, pose))) return rc;
+        if ((rc = ensure(c, c->stats, r.pin_pose - r.pin_stats + 192))) return rc;
+        if ((rc = ensure_events(c, 2 * 4 + 2))) return rc;
+        r.sampled.assign(2, 0); r.eligible.assign(2, 0); r.ev.assign(2, IterEvents());
+        if ((rc = enqueue_merged(c, r))) return rc;
+        unsigned long long row[NSUM];      // row 0 of the totals ring: behind the 3 pose slots (make_ring)
+        HIPCK(c, hipMemcpyAsync(row, c->ring.as<char>() + (size_t)3 * POSE_REPLICAS * POSE_REPLICA_STRIDE, NSUM * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipMemcpyAsync(&hp, loop_slot(c->ring.as<PoseState>(), 1, 0), sizeof(hp), hipMemcpyDeviceToHost, c->stream));      // slot 1: the pose the first iteration composed
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (*(const int*)((char*)c->pinned + r.pin_pose + 128) || hp.fault == 1) { c->err = "icp_debug_loop_sums: a bounded wait of the merged launches ran out"; return ICP_ERR_HIP; }
+        for (int a = 0; a < NSUM; a++) {
+            if (a < NSUM_USED && row[a] == GRANULE_EMPTY) { c->err = "icp_debug_loop_sums: a total of the ring was never written"; return ICP_ERR_HIP; }
+            if (a < NSUM_USED) memcpy(&hs[a], &row[a], 8); else hs[a] = 0.0;
+        }
+        if (hp.fault) { memcpy(st.pose, pose, 64); st.n_valid = (int)hs[SUM_N]; }      // the chain was cut: no record was written
+        else memcpy(&st, (char*)c->pinned + r.pin_stats, sizeof(st));
+        family = 2;
+    }
+    const Bvh& b = colors ? c->bvh6 : c->bvh;
+    route_out[0] = family; route_out[1] = colors ? 6 : 3; route_out[2] = lbvh ? (b.Lq > 8 ? 1 : 0) : -1; route_out[3] = hp.fault;
+    memset(sums_out, 0, 64 * 8); memcpy(sums_out, hs, NSUM * 8);
+    *n_valid_out = st.n_valid;
+    memcpy(pose_out, st.pose, 64);
+    return guard.done();
+}
+
 //   icp_debug_walk_steps      : the two steps of the shared walk on the caller's arrays, one lane per item, with the device functions the
 //                               matchers run (dev_bvh.hpp: leaf_eval<3>, quad_lb<3>).  Leaves and nodes are 128-byte records in the layouts
 //                               of BvhLeafT<3> / BvhQuadT<3>.  Per leaf: query lq[3], leaf number, state in (best, b2, b3 | bi, bpos, l2) ->

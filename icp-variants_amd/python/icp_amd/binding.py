@@ -644,6 +644,15 @@ class Context:
         self._ck(self.lib.icp_correspond(self.h, _ptr(pose_to_c(pose)), _ptr(out), _ptr(sums), C.byref(nv)))
         return out, sums, nv.value
 
+    def loop_sums(self, pose, form, iteration=0):
+        """icp_debug_loop_sums (test hook, host_debug.hpp): the sums the loop itself reduced in iteration `iteration` of the plan icp_run
+        makes, at `pose`, in the form "separate" or "merged".  Returns (sums[64], n_valid, composed pose, route) with route =
+        dict(family: 0 k_post / 1 k_knn_bvh_post / 2 k_knn_bvh_post_ring, dim, wide, fault)."""
+        sums = np.zeros(64, np.float64); nv = C.c_int32(0); out = np.zeros(16, np.float32); route = (C.c_int32 * 4)()
+        self._ck(self.lib.icp_debug_loop_sums(self.h, _ptr(pose_to_c(pose)), C.c_int32(("separate", "merged").index(form)), C.c_int32(iteration),
+                                              _ptr(sums), C.byref(nv), _ptr(out), route))
+        return sums, nv.value, pose_from_c(out), dict(family=route[0], dim=route[1], wide=route[2], fault=route[3])
+
     def iterate(self, pose):
         p = pose_to_c(pose); st = IcpIterStats()
         self._ck(self.lib.icp_iterate(self.h, _ptr(p), C.byref(st)))

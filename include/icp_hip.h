@@ -467,7 +467,10 @@ int icp_get_reciprocal_options(const icp_ctx* ctx, icp_reciprocal_options* opt);
 int icp_get_reciprocal_stats(const icp_ctx* ctx, icp_reciprocal_stats* out, int32_t max_out, int32_t* count_out);
 
 /* -------- ConvergenceMeasure (ConvergenceMeasure.h:30-66): known-correspondence RMSE --------
- * src_xyz[i] (moved by the estimated pose) is compared with ref_xyz[i]. */
+ * src_xyz[i] (moved by the estimated pose) is compared with ref_xyz[i]; pairs with a non-finite point on either side are skipped.
+ * When NO pair is finite, icp_rmse returns ICP_OK and *rmse_out = NaN, as rmseAlignmentError does (:54-65: 0 / 0 under the root);
+ * so does the rmse of an iteration record.  icp_benchmark_error skips nothing (calculate_error has no filter): one non-finite point
+ * makes it NaN, and a single pair -- its own centroid -- makes it infinite or NaN. */
 int icp_set_convergence_reference(icp_ctx* ctx, const float* src_xyz, const float* ref_xyz, int32_t n);
 int icp_rmse(icp_ctx* ctx, const float pose[16], float* rmse_out);
 /* ConvergenceMeasure::benchmarkError (ConvergenceMeasure.h:104-151): mean |T s_i - r_i| / |T s_i - centroid(T s)|. */

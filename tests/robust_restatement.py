@@ -134,11 +134,12 @@ def _slot_terms(R):
     return np.stack([(R[:, :, a] * R[:, :, c]).sum(1) for a, c in cols], 1)        # (n, 27)
 
 
-def sums(metric, p, tgt, recs, tgt_nrm=None, src_nrm_t=None, means=None, gicp=None):
+def sums(metric, p, tgt, recs, tgt_nrm=None, src_nrm_t=None, means=None, gicp=None, terms=False):
     """The 34 sums of icp_correspond for the final records: [0] n, [1..3] sum s, [4..6] sum d, [7..] the metric's block; and the sums of
     their absolute terms (the scale of a tolerance).  tgt_nrm: target normals (point-to-plane, symmetric); src_nrm_t: source normals moved
     by the pose in fp32 (symmetric); means: (mean s, mean d) fp32 of the symmetric pass (default: from these records); gicp: dict(a, b, eps)
-    (GICP normals of the targets of the records and of the moved sources; sums from tests/gicp_restatement.py)."""
+    (GICP normals of the targets of the records and of the moved sources; sums from tests/gicp_restatement.py).  terms=True (not GICP): also
+    the (n_valid, 34) fp64 terms the sums are folded from, one row per valid pair, and the positions of those pairs."""
     p = np.asarray(p, f32)
     idx = recs["idx"]; j = np.maximum(idx, 0)
     q = np.asarray(tgt, f32)[j]
@@ -163,6 +164,9 @@ def sums(metric, p, tgt, recs, tgt_nrm=None, src_nrm_t=None, means=None, gicp=No
     X = np.concatenate(T, 1)
     out = np.zeros(34); ab = np.zeros(34)
     out[:X.shape[1]] = X.sum(0); ab[:X.shape[1]] = np.abs(X).sum(0)
+    if terms:
+        Xp = np.zeros((len(X), 34)); Xp[:, :X.shape[1]] = X
+        return out, ab, Xp, np.flatnonzero(valid)
     return out, ab
 
 

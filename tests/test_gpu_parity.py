@@ -283,6 +283,73 @@ def test_rmse_matches_oracle(gpu_ctx_factory, orc, small_pair):
     assert abs(c.rmse(np.eye(4)) - orc.rmse(src, ref, np.eye(4))) < 1e-6
 
 
+def measure_pairs(p, n):
+    """n known-correspondence pairs: the small pair's sources and their unperturbed positions, tiled with a shared jitter."""
+    pick = np.arange(n) % len(p["src_pts"])
+    j = np.random.default_rng(n).normal(0, 1e-3, (n, 3))
+    return (p["src_pts"][pick] + j).astype(f32), (p["src_unperturbed"][pick] + j).astype(f32)
+
+
+def rmse_fp64_fold(orc, src, ref, T):
+    """rmseAlignmentError with the pairs' fp32 squared distances folded in fp64 (the oracle folds them in fp32, as the reference does)."""
+    t = orc.transform_points(src, T)
+    ok = np.isfinite(t).all(1) & np.isfinite(ref).all(1)
+    e = (t[ok] - ref[ok]).astype(f32)
+    sq = (e[:, 0] * e[:, 0] + (e[:, 1] * e[:, 1] + e[:, 2] * e[:, 2])).astype(f32)
+    return float(f32(np.sqrt(sq.astype(np.float64).sum() / ok.sum()))) if ok.any() else float("nan")
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 65537])
+def test_measures_at_grid_edges(gpu_ctx_factory, orc, small_pair, n):
+    """k_rmse_partial / k_fontana_centroid / k_fontana_error run a fixed grid of 256 x 256 threads with a grid-stride loop behind it:
+    one pair, a block's tail, one pair past a block, one pair past the grid (65 537).  Tolerances: those of test_rmse_matches_oracle and
+    test_benchmark_error_matches_oracle.  Non-finite pairs at index 0 and n - 1: the RMSE skips them (ConvergenceMeasure.h:59), the
+    benchmark error does not (:133-151: no filter, the centroid and the mean are NaN), on the device as in the oracle.  One pair: its
+    distance to the centroid -- itself -- is 0, the benchmark error is infinite (or NaN for an exact match) in both.
+    The RMSE is held to 1e-6 of the fp64 fold of the same fp32 terms at every size and pose, and to 1e-6 of the oracle wherever the
+    oracle's own fp32 running sum (the reference's) is that good: at 65 537 pairs and an RMSE of 0.456 (the random pose) the oracle is
+    1.7e-6 from the fp64 fold, so that one figure is compared with the fp64 fold only."""
+    src, ref = measure_pairs(small_pair, n)
+    c = gpu_ctx_factory()
+    c.set_convergence_reference(src, ref)
+    poses = (np.eye(4, dtype=f32), small_pair["gt"].astype(f32), rand_pose(4))
+    for T in poses:
+        a, b = c.benchmark_error(T), orc.benchmark_error(src, ref, T)
+        print("n %d benchmark error %r oracle %r" % (n, a, b))
+        if n == 1:
+            assert not np.isfinite(b) and (a == b or (np.isnan(a) and np.isnan(b))), (a, b)
+        else:
+            assert abs(a - b) <= 2e-6 * max(1.0, abs(b)), (a, b)
+        a, b, b64 = c.rmse(T), orc.rmse(src, ref, T), rmse_fp64_fold(orc, src, ref, T)
+        print("n %d rmse %r oracle %r fp64 fold %r" % (n, a, b, b64))
+        assert abs(a - b64) < 1e-6, (a, b64)
+        if n < 65537 or T is not poses[2]:
+            assert abs(a - b) < 1e-6, (a, b)
+    src[0] = np.nan; ref[n - 1] = np.inf
+    c.set_convergence_reference(src, ref)
+    for T in poses:
+        a, b, b64 = c.rmse(T), orc.rmse(src, ref, T), rmse_fp64_fold(orc, src, ref, T)
+        print("n %d with non-finite pairs: rmse %r oracle %r fp64 fold %r" % (n, a, b, b64))
+        if n == 1:
+            assert np.isnan(a) and np.isnan(b) and np.isnan(b64)      # no finite pair: test_rmse_without_a_finite_pair
+        else:
+            assert abs(a - b64) < 1e-6, (a, b64)
+            if n < 65537 or T is not poses[2]:
+                assert abs(a - b) < 1e-6, (a, b)
+        assert np.isnan(c.benchmark_error(T)) and np.isnan(orc.benchmark_error(src, ref, T))
+
+
+def test_rmse_without_a_finite_pair(gpu_ctx_factory, orc, small_pair):
+    """No pair with both points finite: rmseAlignmentError divides 0 by a counter of 0 and returns sqrt(NaN) = NaN
+    (ConvergenceMeasure.h:54-65); icp_rmse returns ICP_OK and NaN (include/icp_hip.h), a recorded rmse is NaN too."""
+    src, ref = measure_pairs(small_pair, 300)
+    src[::2] = np.nan; ref[1::2] = np.inf
+    c = gpu_ctx_factory()
+    c.set_convergence_reference(src, ref)
+    for T in (np.eye(4, dtype=f32), small_pair["gt"].astype(f32)):
+        assert np.isnan(c.rmse(T)) and np.isnan(orc.rmse(src, ref, T))
+
+
 def test_projective_symmetric_run(gpu_ctx_factory, orc, rgbd):
     """Config 3 shape: projective matching + rejection + symmetric linear, organised target with holes."""
     from conftest import pose_error
