@@ -7,6 +7,7 @@ include/icp_hip.h.  Test infrastructure only.
   sums(...)                        the 34 sums of icp_correspond (n, sum s, sum d, upper triangle of H, g) and their absolute sums
   solve(s)                         H x = g
   compose(x, pose)                 the point-to-plane composition in fp32: Rx Ry Rz from three small angles, then dT * pose
+  mul_pose(D, pose)                D * pose in fp32, the product compose ends with
   step(...)                        one ICP step on given correspondences
 """
 import numpy as np
@@ -159,7 +160,12 @@ def delta_f32(x):
 
 def compose(x, pose):
     """dT * pose in fp32, sequential over k (mat4_mul_f32)."""
-    D = delta_f32(x); P = np.asarray(pose, f32)
+    return mul_pose(delta_f32(x), pose)
+
+
+def mul_pose(D, pose):
+    """D * pose in fp32, sequential over k (mat4_mul_f32)."""
+    D = np.asarray(D, f32); P = np.asarray(pose, f32)
     out = np.zeros((4, 4), f32)
     for r in range(4):
         for c in range(4):

@@ -1,0 +1,184 @@
+"""What one ICP iteration on a sub-sampled query set must compute, put together from the restatements (gicp_restatement.py,
+colored_restatement.py, robust_restatement.py, solve_reference.py, nss_restatement.py).  Test infrastructure only; no arithmetic of its
+own beyond gathering rows.
+
+The loop hands the post stage a query set as the resident source, an index list into it, a Morton-sorted copy of a level (with its sorted
+position -> original index map) or a list drawn from a level.  Whatever the form, the iteration must equal the
+restatement applied to the ORIGINAL source rows S of the set:
+
+  level_set(valid, f)                                 the stride rule of a decimation factor (PointCloud::getCoarseResolution)
+  hash_draw(base, proba, seed, i, hash)               RANDOM_SAMPLING's draw of iteration i over a base set
+  iteration_sets(ctx, src_pts, src_nrm)               after an icp_run: the increasing original indices of every iteration's query set
+  expected_step(mode, S, prev, base_recs, data, opts) next pose, n_valid and mode statistics of one iteration on the set S
+  wrong_slot_step(...)                                the same with every source-side array gathered at arange(len(S)): what a kernel that
+                                                      reads a per-point attribute at the slot instead of the original index would compute
+
+mode: "gicp" (metric 3), "colored" (metric 4), "robust" (robust mode on metric opts["metric"] = 0 or 1).
+data: dict(src_pts, src_nrm, src_rgba, tgt_pts, tgt_nrm, tgt_rgba) + gicp_src / gicp_tgt (the GICP normals of the full clouds, metric 3) +
+      grad (the target's colour gradients, metric 4).
+opts: eps (metric 3), lam (metric 4), metric + robust (dict(kernel, tuning, sigma, overlap), kernel as an integer; robust mode);
+      transform_points / transform_normals: callables (xyz, pose) -> fp32 (default: gicp_restatement.transform and the fp64 normal matrix
+      of gicp_restatement.step; the device tests hand in the context's own, as the teacher-forced tests of each mode do).
+base_recs: rows S of the full-resolution records (idx, weight after weighting and rejection, robust mode off) at `prev`.  Matching,
+      weighting and rejection are per-pair operations, so a subset's records are the subset of the records."""
+import numpy as np
+
+import colored_restatement as CR
+import gicp_restatement as G
+import nss_restatement as nss
+import robust_restatement as R
+import solve_reference as SR
+
+f32 = np.float32
+EPS, LAM = 1e-3, 0.968
+TOL = 1e-5                    # the pose tolerance of every restatement-step test of the suite
+MARGIN = 1e-3                 # what a wrong-slot step must differ by at least: 100 x TOL
+
+# The modes of tests/test_gpu_query_sets.py and tests/test_query_sets_host.py.  cloud: the fixture they run on (the shuffled bunny pair or
+# the shuffled 80 x 60 RGB-D pair).
+MODES = {
+    "gicp_k10": dict(mode="gicp", metric=3, weighting=0, rejection=1, covariance_k=10, cloud="bunny", max_distance=0.0003),
+    "gicp_own_colour_weights": dict(mode="gicp", metric=3, weighting=3, rejection=1, covariance_k=0, cloud="bunny", max_distance=0.0003),
+    "colored": dict(mode="colored", metric=4, weighting=0, rejection=1, gradient_k=10, cloud="rgbd", max_distance=0.01),
+    "robust_huber_plane": dict(mode="robust", metric=1, weighting=0, rejection=1, robust=dict(kernel="huber", overlap=0.7), cloud="bunny", max_distance=0.0003),
+    "robust_trim_point": dict(mode="robust", metric=0, weighting=0, rejection=1, robust=dict(kernel="none", overlap=0.6), cloud="bunny", max_distance=0.0003),
+}
+ROBUST_KERNELS = ("none", "huber", "cauchy", "tukey")
+
+
+def shuffled(d, seed=5):
+    """The pair with its source rows permuted (seeded): no slot of a query set and no Morton position equals the original index but by accident."""
+    perm = np.random.default_rng(seed).permutation(len(d["src_pts"]))
+    out = dict(d)
+    for k in ("src_pts", "src_nrm", "src_rgba"):
+        out[k] = np.ascontiguousarray(np.asarray(d[k])[perm])
+    return out
+
+
+def rgbd_pair():
+    """The 80 x 60 synthetic RGB-D pair of tests/test_gpu_colored.py, compacted to its valid points."""
+    from icp_amd import synth
+    K = np.array([[525.0 / 8, 0, 319.5 / 8], [0, 525.0 / 8, 239.5 / 8], [0, 0, 1]])
+    d = synth.rgbd_pair(0, width=80, height=60, K=K)
+    tp, tn, tc = synth.compact_valid(d["tgt_pts"], d["tgt_nrm"], d["tgt_rgba"])
+    sp, sn, sc = synth.compact_valid(d["src_pts"], d["src_nrm"], d["src_rgba"])
+    return dict(src_pts=sp, src_nrm=sn, src_rgba=sc, tgt_pts=tp, tgt_nrm=tn, tgt_rgba=tc)
+
+
+def step_options(cfg, **extra):
+    """The opts of expected_step for a MODES entry."""
+    o = dict(eps=EPS, lam=LAM, metric=cfg["metric"], **extra)
+    if cfg["mode"] == "robust":
+        o["robust"] = dict(cfg["robust"], kernel=ROBUST_KERNELS.index(cfg["robust"]["kernel"]))
+    return o
+
+
+def level_set(valid, f):
+    """Original indices of the level of decimation factor f (0: every point): every f-th point that is finite in point and normal."""
+    n = len(valid)
+    if f == 0:
+        return np.arange(n, dtype=np.int64)
+    c = np.arange(0, n, f, dtype=np.int64)
+    return c[valid[c]]
+
+
+def hash_threshold(proba):
+    """(threshold, take_all) of RANDOM_SAMPLING: proba (an fp32 field) * 2^32, truncated."""
+    th = float(f32(proba)) * 4294967296.0
+    if th >= 4294967296.0:
+        return 0xFFFFFFFF, True
+    return (0 if th <= 0.0 else int(th)), False
+
+
+def hash_draw(base, proba, seed, iteration, hash_fn):
+    """The members k of `base` with hash_fn(seed, iteration, k) < threshold (hash_fn: icp_select_hash of one index)."""
+    base = np.asarray(base, np.int64)
+    thr, take_all = hash_threshold(proba)
+    if take_all:
+        return base
+    h = np.array([int(hash_fn(seed, iteration, int(k))) for k in base], np.int64)
+    return base[h < thr]
+
+
+def iteration_sets(ctx, src_pts, src_nrm):
+    """The query set of every iteration of the icp_run that just ended on `ctx`: increasing original source indices.  Levels from
+    icp_schedule and the stride rule; selection 1 re-derived on the host from icp_select_hash and asserted equal to icp_get_selection;
+    selection 2 asserted against nss_restatement.run_lists."""
+    from icp_amd import binding
+    p = ctx.params
+    n = len(src_pts)
+    factors = binding.schedule(p, n)
+    valid = np.isfinite(np.asarray(src_pts, f32)).all(1) & np.isfinite(np.asarray(src_nrm, f32)).all(1)
+    levels = [level_set(valid, f) for f in factors]
+    if p.selection == 0:
+        return factors, levels
+    dev = [np.asarray(ctx.selection(i), np.int64) for i in range(len(factors))]
+    if p.selection == 1:
+        ref = [hash_draw(levels[i], p.selection_proba, p.selection_seed, i, binding.select_hash) for i in range(len(factors))]
+    else:
+        o = ctx.nss_options()
+        ref = nss.run_lists(src_pts, src_nrm, factors, p.selection_proba, p.selection_seed, grid=o.grid, resample=bool(o.resample))
+    for i, (a, b) in enumerate(zip(dev, ref)):
+        assert np.array_equal(a, b), ("query set of iteration %d" % i, len(a), len(b))
+        assert (np.diff(a) > 0).all() and np.isin(a, levels[i]).all(), i
+    return factors, dev
+
+
+def _normals_f64(nrm, pose):
+    """gicp_restatement.step's source normals at `pose`: the fp64 normal matrix, rounded once."""
+    Rn = np.linalg.inv(np.asarray(pose, np.float64)[:3, :3]).T
+    return (np.asarray(nrm, np.float64) @ Rn.T).astype(f32)
+
+
+def _step(mode, rows, prev, recs, data, opts):
+    prev = np.asarray(prev, f32)
+    tp = opts.get("transform_points") or (lambda xyz, pose: G.transform(pose, xyz))
+    tn = opts.get("transform_normals") or _normals_f64
+    recs = np.asarray(recs)
+    assert len(recs) == len(rows)
+    src = np.asarray(data["src_pts"], f32)[rows]
+    tgt = np.asarray(data["tgt_pts"], f32)
+    idx = recs["idx"]; j = np.maximum(idx, 0)
+    if mode == "gicp":
+        p = tp(src, prev)
+        b = tn(np.asarray(data["gicp_src"], f32)[rows], prev)
+        q = tgt[j]
+        valid = (idx >= 0) & np.isfinite(p).all(1) & np.isfinite(q).all(1)
+        s, sa = G.sums(p, q, np.asarray(data["gicp_tgt"], f32)[j], b, recs["weight"], opts["eps"], valid)
+        return dict(pose=G.compose(G.solve(s), prev), n_valid=int(s[0]), sums=s, sums_abs=sa, stats=None)
+    if mode == "colored":
+        s, sa = CR.record_sums(recs, prev, src, tgt, data["tgt_nrm"], data["grad"], np.asarray(data["src_rgba"])[rows], data["tgt_rgba"], opts["lam"])
+        return dict(pose=CR.compose(CR.solve(s), prev), n_valid=int(s[0]), sums=s, sums_abs=sa, stats=None)
+    if mode != "robust":
+        raise ValueError(mode)
+    metric = opts["metric"]
+    p = tp(src, prev)
+    ref = R.robust(recs, p, tgt, opts["robust"], metric)
+    fin = ref["recs"]
+    s, sa = R.sums(metric, p, tgt, fin, tgt_nrm=data["tgt_nrm"])
+    if metric == 1:
+        pose = G.compose(G.solve(s), prev)
+    elif metric == 0:                                        # Procrustes on the kept pairs, then dT * pose
+        k = (fin["idx"] >= 0) & np.isfinite(p).all(1) & np.isfinite(tgt[np.maximum(fin["idx"], 0)]).all(1)
+        dT = SR.solve_p2p(p[k], tgt[fin["idx"][k]], fin["weight"][k])["pose"]
+        pose = G.mul_pose(dT.astype(f32), prev)
+    else:
+        raise ValueError("robust mode is restated here for metrics 0 and 1")
+    return dict(pose=pose, n_valid=int(s[0]), sums=s, sums_abs=sa, stats=ref["stats"], robust=ref)
+
+
+def expected_step(mode, S, prev_pose, base_recs, data, opts):
+    """The reference's iteration on the query set S (original source indices) from `prev_pose`: dict(pose, n_valid, sums, sums_abs, stats)."""
+    return _step(mode, np.asarray(S, np.int64), prev_pose, base_recs, data, opts)
+
+
+def wrong_slot_step(mode, S, prev_pose, base_recs, data, opts):
+    """The same records with the source's points, normals, colours and GICP normals taken at 0 .. len(S) - 1: the step of a kernel that
+    reads them at the slot.  Only to show that a test's inputs tell the two apart."""
+    return _step(mode, np.arange(len(S), dtype=np.int64), prev_pose, base_recs, data, opts)
+
+
+def slot_differs(S):
+    """Fraction of the slots k of a set with S[k] != k."""
+    S = np.asarray(S, np.int64)
+    return float((S != np.arange(len(S))).mean()) if len(S) else 1.0

@@ -135,6 +135,8 @@ def test_free_running_against_restatement(gpu_ctx_factory, depth_pair):
 
 @pytest.mark.parametrize("multires,selection", [(1, 0), (0, 1), (1, 1)])
 def test_multires_and_sampling_deterministic(gpu_ctx_factory, depth_pair, multires, selection):
+    """Multires levels and random samples: two runs are bit-identical and every iteration has valid pairs.  What a sub-sampled iteration
+    computes (which points' colours it read) is checked in tests/test_gpu_query_sets.py, iteration by iteration against the restatement."""
     ctx = gpu_ctx_factory()
     configure(ctx, n_iterations=10, multires=multires, selection=selection, proba=0.5)
     load(ctx, depth_pair)

@@ -226,8 +226,9 @@ def test_off_is_untouched(gpu_ctx_factory, bunny):
 
 @pytest.mark.parametrize("multires,selection", [(1, 0), (0, 1), (1, 1)])
 def test_free_running(gpu_ctx_factory, bunny, multires, selection):
-    """icp_run with multires / random sampling: every iteration's stats are consistent (K, M, n_valid), and the iterations at full
-    resolution without resampling equal the restatement on the robust-off records at the incoming pose."""
+    """icp_run with multires / random sampling: every iteration's stats are consistent (K, M, n_valid), the iterations at full
+    resolution without resampling equal the restatement on the robust-off records at the incoming pose, and a second run is bit-identical.
+    The iterations on levels and samples are compared with the restatement (stats, n_valid and pose) in tests/test_gpu_query_sets.py."""
     ctx = gpu_ctx_factory()
     configure(ctx, metric=1, n_iterations=6, multires=multires, selection=selection, proba=0.5)
     load(ctx, bunny)
