@@ -177,7 +177,9 @@ int icp_get_timing(const icp_ctx* ctx, icp_timing* out);
  * HIP call fails.  Score of a start, at its final pose, on the FULL-resolution source (no multires level, no random sample): every
  * finite source point moved by the pose (utils.h:113-115) and matched in 3-D against the target's xyz (also with color_icp on) is an
  * inlier when its squared distance is <= max_distance -- exactly when icp_match would return idx >= 0 for it; n_inliers, fitness =
- * n_inliers / finite source points, inlier_rmse = sqrt(sum d^2 / n_inliers) (fp64 sum in a fixed order), -1 without inliers.
+ * n_inliers / finite source points (both exact integers, divided in fp64 and rounded once to fp32; 0 when the source has no finite point:
+ * such a source is not refused, every start reports ICP_ERR_NO_CORRESPONDENCES and keeps its pose), inlier_rmse = sqrt(sum d^2 /
+ * n_inliers) (fp64 sum in a fixed order, one rounding to fp32), -1 without inliers.
  * *best_out (optional): the start with the most inliers, ties to the smaller inlier_rmse, then to the lower index.
  * Supported: k-NN matching on the LBVH backend (3-D or colour 6-D), every metric, weighting, rejection, multires and selection (the draws
  * of RANDOM_SAMPLING and of normal-space sampling are shared between the starts); 1 <= n_starts <= 256.  NOT supported (ICP_ERR_INVALID_ARG, see icp_last_error): projective matching, the
@@ -187,7 +189,7 @@ typedef struct icp_start_result {
     float   pose[16];      /* final pose of this start, column-major */
     int32_t status;        /* what icp_run would have returned for this start alone */
     int32_t n_inliers;     /* full-resolution source points with a 3-D neighbour within max_distance at the final pose */
-    float   fitness;       /* n_inliers / finite source points */
+    float   fitness;       /* n_inliers / finite source points, 0 without a finite source point */
     float   inlier_rmse;   /* sqrt(sum d2 / n_inliers), -1 when n_inliers == 0 */
 } icp_start_result;
 int icp_run_multistart(icp_ctx* ctx, const float* initial_poses, int32_t n_starts, icp_start_result* results, icp_iter_stats* stats,

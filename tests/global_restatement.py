@@ -10,20 +10,25 @@ BINS, DIM = 11, 33
 VALID, REPEATED, EDGES, DEGENERATE = 0, 1, 2, 3
 
 
-def neighbour_lists(pts, k):
+def neighbour_lists(pts, k, rows=None):
     """(idx (n, k) int32, d2 (n, k) float32): the k smallest (fp32 d2, index) pairs over the finite points, the point itself included, in
-    ascending order; unfilled slots (-1, inf); a non-finite point has none.  d2 = (dx dx + dy dy) + dz dz in fp32."""
+    ascending order; unfilled slots (-1, inf); a non-finite point has none.  d2 = (dx dx + dy dy) + dz dz in fp32.  rows: the lists of
+    these points only, (len(rows), k) -- the rows of the full call."""
     p = np.asarray(pts, np.float32)
     n = len(p)
     fin = np.isfinite(p).all(axis=1)
     ids = np.flatnonzero(fin)
-    idx = np.full((n, k), -1, np.int32); d2 = np.full((n, k), np.inf, np.float32)
+    rows = np.arange(n) if rows is None else np.asarray(rows, np.int64)
+    idx = np.full((len(rows), k), -1, np.int32); d2 = np.full((len(rows), k), np.inf, np.float32)
     q = p[ids]
-    for i in ids:
+    for r, i in enumerate(rows):
+        if not fin[i]:
+            continue
         dx = p[i, 0] - q[:, 0]; dy = p[i, 1] - q[:, 1]; dz = p[i, 2] - q[:, 2]
         d = (dx * dx + dy * dy) + dz * dz
-        order = np.lexsort((ids, d))[:k]
-        idx[i, :len(order)] = ids[order]; d2[i, :len(order)] = d[order]
+        cand = np.flatnonzero(d <= np.partition(d, k - 1)[k - 1]) if len(d) > k else np.arange(len(d))      # (the k-th smallest and its ties)
+        order = cand[np.lexsort((ids[cand], d[cand]))][:k]
+        idx[r, :len(order)] = ids[order]; d2[r, :len(order)] = d[order]
     return idx, d2
 
 
@@ -45,7 +50,7 @@ def _bin(x, lo, hi):
 
 def pair_features(p, n_p, q, n_q):
     """Arrays of pairs (fp32 inputs).  Returns dict(ok, bins (.., 3) int, margin (..): the smallest distance of f1, f2, f3 to a bin boundary
-    in bin units, gap (..): ||a1| - |a2||); fp64 throughout."""
+    in bin units, gap (..): ||a1| - |a2||, inf between bit-equal normals); fp64 throughout."""
     with np.errstate(all="ignore"):
         p = np.asarray(p, np.float32); q = np.asarray(q, np.float32); n_p = np.asarray(n_p, np.float32); n_q = np.asarray(n_q, np.float32)
         fin = np.isfinite(p).all(-1) & np.isfinite(q).all(-1) & np.isfinite(n_p).all(-1) & np.isfinite(n_q).all(-1)
@@ -68,23 +73,27 @@ def pair_features(p, n_p, q, n_q):
         bins = np.stack([b1, b2, b3], axis=-1)
         bins = np.where(ok[..., None], bins, 0).astype(np.int64)
         margin = np.where(ok, np.minimum(m1, np.minimum(m2, m3)), np.inf)
-        gap = np.where(fin, np.abs(np.abs(a1) - np.abs(a2)), np.inf)
+        # (bit-equal normals: a1 and a2 are one expression of the same operands, so |a1| < |a2| is false whatever the rounding -- no gap to fall into)
+        gap = np.where(fin & ~(n_p == n_q).all(-1), np.abs(np.abs(a1) - np.abs(a2)), np.inf)
     return dict(ok=ok, bins=bins, margin=margin, gap=gap)
 
 
-def spfh(pts, nrm, nb_idx, nb_d2):
+def spfh(pts, nrm, nb_idx, nb_d2, rows=None):
     """(counts (n, 33) uint8, pairs (n,) int32, margin (n,), gap (n,)): the SPFH of every point from its neighbour list, and per point the
-    smallest bin-boundary distance / ||a1| - |a2|| over its pairs (inf: no pair)."""
+    smallest bin-boundary distance / ||a1| - |a2|| over its pairs (inf: no pair).  rows: nb_idx / nb_d2 are the lists of these points
+    only, and so are the results -- the rows of the full call."""
     p = np.asarray(pts, np.float32); nr = np.asarray(nrm, np.float32)
     n, k = nb_idx.shape
+    own = np.arange(len(p)) if rows is None else np.asarray(rows, np.int64)
+    assert len(own) == n
     use = (nb_idx >= 0) & (nb_d2 > 0)
     j = np.where(use, nb_idx, 0)
-    f = pair_features(p[:, None, :], nr[:, None, :], p[j], nr[j])
+    f = pair_features(p[own][:, None, :], nr[own][:, None, :], p[j], nr[j])
     ok = f["ok"] & use
     counts = np.zeros((n, DIM), np.int64)
-    rows = np.repeat(np.arange(n), k).reshape(n, k)
+    at = np.repeat(np.arange(n), k).reshape(n, k)
     for feat in range(3):
-        np.add.at(counts, (rows[ok], feat * BINS + f["bins"][..., feat][ok]), 1)
+        np.add.at(counts, (at[ok], feat * BINS + f["bins"][..., feat][ok]), 1)
     margin = np.where(ok, f["margin"], np.inf).min(axis=1)
     gap = np.where(ok, f["gap"], np.inf).min(axis=1)
     return counts.astype(np.uint8), ok.sum(axis=1).astype(np.int32), margin, gap

@@ -1,9 +1,11 @@
 """Global registration without a GPU: the structs and defaults of the C ABI, the invariants of the numpy restatement
-(tests/global_restatement.py) that the GPU tests compare the device with, and the resource report of the new kernels."""
+(tests/global_restatement.py) that the GPU tests compare the device with, the properties of the input clouds of tests/global_cases.py that
+those tests rely on (ties in every list, collinear and nearly collinear triples, M = n), and the resource report of the new kernels."""
 import ctypes as C
 import numpy as np
 import pytest
 
+import global_cases as gc
 import global_restatement as gr
 from device_asm import device_asm, kernel_resources
 
@@ -112,6 +114,112 @@ def test_ransac_recovers_a_known_pose_through_outliers():
     o = r["order"]
     key = list(zip(-r["n_inliers"][o].astype(int), r["sum_d2"][o], o))
     assert key == sorted(key) and (r["status"][o] == gr.VALID).all()
+
+
+def test_rows_form_equals_the_full_call(bunny, source_features):
+    """neighbour_lists and spfh with rows = ... give the rows of the full call: what lets a large cloud be checked on a sample."""
+    f = source_features
+    p, nr = bunny["src_pts"], bunny["src_nrm"]
+    rows = np.sort(np.random.default_rng(3).choice(len(p), 100, replace=False))
+    idx, d2 = gr.neighbour_lists(p, 10, rows=rows)
+    assert np.array_equal(idx, f["idx"][rows]) and np.array_equal(d2.view(np.uint32), f["d2"][rows].view(np.uint32))
+    counts, pairs, margin, gap = gr.spfh(p, nr, idx, d2, rows=rows)
+    assert np.array_equal(counts, f["counts"][rows]) and np.array_equal(pairs, f["pairs"][rows])
+    assert np.array_equal(margin, f["margin"][rows]) and np.array_equal(gap, f["gap"][rows])
+    q = p.copy(); q[rows[0]] = np.nan                                    # a non-finite row has no list, in either form
+    a, b = gr.neighbour_lists(q, 10, rows=rows[:3]), gr.neighbour_lists(q, 10)
+    assert (a[0][0] == -1).all() and np.isinf(a[1][0]).all() and np.array_equal(a[0], b[0][rows[:3]])
+
+
+# ---- the conditions the device tests of tests/test_gpu_global.py rely on, proved with the restatement alone ----
+EXCLUDE_MARGIN, EXCLUDE_GAP = 1e-6, 1e-9          # tests/test_gpu_global.py's
+
+
+@pytest.mark.parametrize("k", [5, 10, 20])
+def test_lattices_tie_in_every_list(k):
+    """(a) every neighbour list of the integer lattices holds an exact fp32 distance tie, no point would be excluded from the SPFH
+    comparison, and every point has a feature."""
+    for name, (p, nr) in gc.lattices().items():
+        f = gr.features(p, nr, k)
+        assert (np.diff(f["d2"], axis=1) == 0).any(axis=1).all(), name
+        assert f["margin"].min() >= EXCLUDE_MARGIN and f["gap"].min() >= EXCLUDE_GAP, (name, f["margin"].min(), f["gap"].min())
+        assert not np.isnan(f["F"]).any(), name
+
+
+def strip_pairs(cloud, mutual):
+    p, nr = cloud
+    f = gr.features(p, nr, 10)
+    assert not np.isnan(f["F"]).any() and f["margin"].min() >= EXCLUDE_MARGIN and f["gap"].min() >= EXCLUDE_GAP
+    si, ti = gr.correspondences(f["F"], f["F"], 1, mutual)
+    assert np.array_equal(si, np.arange(len(p))) and np.array_equal(ti, si)          # a cloud against itself: every pair (i, i)
+    return p[si], p[ti]
+
+
+@pytest.mark.parametrize("mutual", [True, False])
+def test_line_cloud_has_repeated_and_degenerate_hypotheses_only(mutual):
+    """(b)"""
+    cs, ct = strip_pairs(gc.line_cloud(), mutual)
+    assert len(cs) >= 3
+    r = gr.ransac(cs, ct, gc.LINE_SEED, gc.LINE_H, 0.9, 0.005)
+    count = np.bincount(r["status"], minlength=4)
+    assert count[gr.VALID] == 0 and count[gr.EDGES] == 0 and count[gr.REPEATED] > 0 and count[gr.DEGENERATE] > 400, count
+    assert len(r["order"]) == 0
+
+
+def test_ribbon_cloud_straddles_the_collinearity_threshold():
+    """(c) both VALID and DEGENERATE, each at least a tenth of the non-repeated hypotheses, and every one of them farther from the threshold
+    than RIBBON_BAND (relative): the device and the restatement evaluate the same fp64 expression, so their statuses must be equal."""
+    cs, ct = strip_pairs(gc.ribbon_cloud(), True)
+    r = gr.ransac(cs, ct, gc.RIBBON_SEED, gc.RIBBON_H, 0.9, 0.005)
+    count = np.bincount(r["status"], minlength=4)
+    tried = count[gr.VALID] + count[gr.DEGENERATE]
+    assert count[gr.EDGES] == 0 and tried == gc.RIBBON_H - count[gr.REPEATED]
+    assert count[gr.VALID] >= 0.1 * tried and count[gr.DEGENERATE] >= 0.1 * tried, count
+    sel = r["status"] != gr.REPEATED
+    for side in (cs, ct):
+        cc, thr = gc.collinearity(np.asarray(side, np.float32)[r["draws"][sel]].astype(np.float64))
+        assert (thr > 0).all() and (np.abs(cc - thr) > gc.RIBBON_BAND * thr).all(), (np.abs(cc - thr) / thr).min()
+        assert np.array_equal(~(cc > thr), r["status"][sel] == gr.DEGENERATE)
+
+
+def test_bunny_sub_clouds_give_m_equal_n(bunny):
+    """(d) without the mutual test n source points against the whole target give M = n, no point near a bin boundary; with the edge test
+    off every case but the two whose pairs share a target point has valid hypotheses."""
+    ft = gr.features(bunny["tgt_pts"], bunny["tgt_nrm"], gc.SUB_K)
+    assert ft["margin"].min() >= EXCLUDE_MARGIN and ft["gap"].min() >= EXCLUDE_GAP
+    assert {n for n, start, H in gc.EDGE_CASES if start == 0} == set(gc.SUB_SIZES)
+    for n, start in sorted({(n, start) for n, start, H in gc.EDGE_CASES}):
+        sp, sn, _, _ = gc.sub_clouds(bunny, n, start)
+        f = gr.features(sp, sn, gc.SUB_K)
+        assert f["margin"].min() >= EXCLUDE_MARGIN and f["gap"].min() >= EXCLUDE_GAP, n
+        si, ti = gr.correspondences(f["F"], ft["F"], 1, False)
+        assert len(si) == n and np.array_equal(si, np.arange(n)), n
+        r = gr.ransac(sp[si], bunny["tgt_pts"][ti], gc.edge_seed(n, start, 512), 512, 0.0, 0.005)
+        count = np.bincount(r["status"], minlength=4)
+        if (n, start) in ((3, 0), (4, 0)):
+            assert count[gr.VALID] == 0 and count[gr.DEGENERATE] > 100, (n, start, count)
+        else:
+            assert count[gr.VALID] > 100, (n, start, count)
+
+
+def test_n_best_case_has_fewer_valid_hypotheses_than_n_best(bunny, source_features):
+    """N_BEST_H hypotheses on the bunny leave between 65 and 255 valid ones: more than one 64-start block of the multi-start score fold,
+    fewer than n_best = 256."""
+    ft = gr.features(bunny["tgt_pts"], bunny["tgt_nrm"], gc.N_BEST_K)
+    si, ti = gr.correspondences(source_features["F"], ft["F"], 1, True)
+    r = gr.ransac(bunny["src_pts"][si], bunny["tgt_pts"][ti], 0, gc.N_BEST_H, 0.9, 0.005)
+    assert 65 <= len(r["order"]) <= 255, len(r["order"])
+
+
+def test_coincident_cloud_has_more_copies_than_k():
+    p, nr, copies = gc.coincident_cloud()
+    assert len(copies) == gc.COPIES > 20 and (p[copies] == p[gc.COPY_AT]).all()
+    f = gr.features(p, nr, 20)
+    assert (f["d2"][copies] == 0).all() and np.isin(f["idx"][copies], copies).all()        # the 20 lowest-index copies, all at d2 = 0
+    assert (f["idx"][copies] == copies[:20]).all()
+    assert (f["pairs"][copies] == 0).all() and np.isnan(f["F"][copies]).all()
+    rest = np.setdiff1d(np.arange(len(p)), copies)
+    assert not np.isnan(f["F"][rest]).any() and f["margin"].min() >= EXCLUDE_MARGIN and f["gap"].min() >= EXCLUDE_GAP
 
 
 MATCHER_VGPR_BUDGET = 96            # DESIGN 6k: the 36 KiB tile allows four blocks (16 waves) per CU; 96 registers keep five waves per SIMD possible

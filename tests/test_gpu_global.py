@@ -4,6 +4,7 @@ the stage before, so every comparison is exact or has a bound that follows from 
 import numpy as np
 import pytest
 
+import global_cases as gc
 import global_restatement as gr
 from conftest import pose_error
 
@@ -242,6 +243,208 @@ def test_ransac_teacher_forced(gpu_ctx_factory, bunny, seed):
         assert np.array_equal(binding.pose_to_c(poses[r]), hyp["pose"][order[r]])
     poses2, recs2, _ = ctx.register_global()                                      # two runs agree bit for bit
     assert hyp.tobytes() == ctx.global_hypotheses().tobytes() and recs.tobytes() == recs2.tobytes()
+
+
+# ---- the feature pass beyond the bunny's shapes: exact ties, sizes around K / the block / a tree level, a deeper tree, coincident points ----
+def load_same(ctx, p, nr, k, knn_backend=1):
+    """one cloud as target and source: the target's lists come from its own tree (knn_backend 1) or the scratch tree (0), the source's
+    always from the scratch tree"""
+    configure(ctx, knn_backend)
+    ctx.set_target(p, nr); ctx.set_source(p, nr)
+    ctx.set_global_options(k=k)
+
+
+def assert_features(ctx, which, p, nr, r, rows=None, label=""):
+    """The device's lists and SPFH of `which` bit for bit against the restatement r (of the points `rows`, default all), its F within 2 ulp
+    of the restatement fed the device's own lists and SPFH (every row), the NaN rows the same.  Returns the largest ulp distance of F."""
+    idx, d2 = ctx.feature_neighbours(which); counts, pairs = ctx.spfh(which); F = ctx.features(which)
+    k = r["idx"].shape[1]
+    assert idx.shape == d2.shape == (len(p), k) and counts.shape == (len(p), 33) and pairs.shape == (len(p),) and F.shape == (len(p), 33), label
+    at = slice(None) if rows is None else rows
+    assert np.array_equal(idx[at], r["idx"]), (label, which)
+    assert np.array_equal(bits(d2[at]), bits(r["d2"])), (label, which)
+    excluded = (r["margin"] < EXCLUDE_MARGIN) | (r["gap"] < EXCLUDE_GAP)
+    assert not excluded.any(), (label, r["margin"].min(), r["gap"].min())      # (a condition on the inputs: tests/test_global_host.py)
+    assert np.array_equal(pairs[at], r["pairs"]), (label, which)
+    assert np.array_equal(counts[at], r["counts"]), (label, which)
+    R = gr.fpfh(p, nr, idx, d2, counts, pairs)
+    assert np.array_equal(np.isnan(F), np.isnan(R)), (label, which)
+    assert np.array_equal(np.isnan(F).any(axis=1), np.isnan(F).all(axis=1))
+    ok = ~np.isnan(F)
+    u = int(ulps(F[ok], R[ok]).max()) if ok.any() else 0
+    assert u <= 2, (label, which, u)
+    return u
+
+
+_CASES = {}
+
+
+def restated_case(name, k, make):
+    if (name, k) not in _CASES:
+        p, nr = make()
+        _CASES[(name, k)] = (p, nr, gr.features(p, nr, k))
+    return _CASES[(name, k)]
+
+
+@pytest.mark.parametrize("knn_backend", [0, 1])
+@pytest.mark.parametrize("k", [5, 10, 20])
+def test_exact_ties_on_lattices(gpu_ctx_factory, k, knn_backend):
+    """Integer lattices: every neighbour list holds an exact fp32 distance tie (tests/test_global_host.py), decided by the lowest index."""
+    ctx = gpu_ctx_factory()
+    for name in ("plane", "block"):
+        p, nr, r = restated_case(name, k, lambda: gc.lattices()[name])
+        load_same(ctx, p, nr, k, knn_backend)
+        for which in ("source", "target"):
+            u = assert_features(ctx, which, p, nr, r, label="%s k=%d backend=%d" % (name, k, knn_backend))
+            print("lattice %s k=%d backend %d %s: max |F - restatement| = %d ulp" % (name, k, knn_backend, which, u))
+
+
+@pytest.mark.parametrize("k", [5, 20])
+def test_sizes_around_k_the_block_and_a_tree_level(gpu_ctx_factory, k):
+    ctx = gpu_ctx_factory()
+    for n in gc.SIZES(k):
+        p, nr = gc.uniform_cloud(n, 1000 * k + n)
+        r = gr.features(p, nr, k)
+        load_same(ctx, p, nr, k)
+        for which in ("source", "target"):
+            u = assert_features(ctx, which, p, nr, r, label="n=%d k=%d" % (n, k))
+            print("uniform n=%d k=%d %s: max |F - restatement| = %d ulp" % (n, k, which, u))
+            idx, d2 = ctx.feature_neighbours(which); _, pairs = ctx.spfh(which); F = ctx.features(which)
+            assert ((idx >= 0).sum(axis=1) == min(n, k)).all() and (idx[:, 0] == np.arange(n)).all() and (d2[:, 0] == 0).all()
+            assert (pairs == min(n, k) - 1).all()
+            if n == 1:                                   # the point itself, no pair, no feature
+                assert idx[0].tolist() == [0] + [-1] * (k - 1) and np.isinf(d2[0, 1:]).all() and pairs[0] == 0 and np.isnan(F).all()
+            if n == 2:                                   # one pair each
+                assert idx[:, :2].tolist() == [[0, 1], [1, 0]] and (idx[:, 2:] == -1).all() and pairs.tolist() == [1, 1] and not np.isnan(F).any()
+
+
+@pytest.mark.parametrize("k", [10, 20])
+def test_a_deeper_tree_on_a_sample_of_rows(gpu_ctx_factory, k):
+    """A 40 800-point scan: lists and SPFH of 2 000 rows against the rows form of the restatement, F of every row against the restatement
+    fed the device's lists and SPFH, the shapes and the NaN pattern of the whole output."""
+    p, nr = gc.deep_scan()
+    assert len(p) == 40800 and np.isfinite(p).all() and np.isfinite(nr).all()
+    rows = gc.deep_rows(len(p))
+    idx, d2 = gr.neighbour_lists(p, k, rows=rows)
+    counts, pairs, margin, gap = gr.spfh(p, nr, idx, d2, rows=rows)
+    r = dict(idx=idx, d2=d2, counts=counts, pairs=pairs, margin=margin, gap=gap)
+    ctx = gpu_ctx_factory()
+    load_same(ctx, p, nr, k)
+    for which in ("source", "target"):
+        u = assert_features(ctx, which, p, nr, r, rows=rows, label="scan k=%d" % k)
+        print("scan k=%d %s: max |F - restatement| = %d ulp" % (k, which, u))
+        _, dev_pairs = ctx.spfh(which)
+        assert np.array_equal(np.isnan(ctx.features(which)).all(axis=1), dev_pairs == 0)
+
+
+def test_more_coincident_points_than_k(gpu_ctx_factory):
+    """25 copies of one point, k = 20: a copy's list is the 20 lowest-index copies at d2 = 0, it has no pair and no feature."""
+    p, nr, copies = gc.coincident_cloud()
+    r = gr.features(p, nr, 20)
+    ctx = gpu_ctx_factory()
+    load_same(ctx, p, nr, 20)
+    for which in ("source", "target"):
+        assert_features(ctx, which, p, nr, r, label="coincident")
+        idx, d2 = ctx.feature_neighbours(which); _, pairs = ctx.spfh(which); F = ctx.features(which)
+        assert (d2[copies] == 0).all() and (idx[copies] == copies[:20]).all()
+        assert (pairs[copies] == 0).all()
+        assert np.isnan(F[copies]).all() and not np.isnan(np.delete(F, copies, axis=0)).any()
+
+
+# ---- RANSAC beyond H in {512, 4096} and M ~ 655 ----
+def teacher_forced_ransac(ctx, src_pts, tgt_pts, seed, H, n_best, edge_similarity=0.9, inlier_distance=0.005, label=""):
+    """test_ransac_teacher_forced's comparisons after ctx.set_global_options(...): draws, statuses, poses, counts, sums, ranking, the
+    number of records, two runs byte for byte.  Returns (hyp, status of the restatement, the ranking, poses, recs, rc)."""
+    from icp_amd import binding
+    poses, recs, rc = ctx.register_global(check=False)
+    hyp = ctx.global_hypotheses()
+    si, ti = ctx.match_features()
+    cs, ct = src_pts[si], tgt_pts[ti]
+    assert len(hyp) == H and len(si) >= 3, label
+    dr = gr.draws(seed, H, len(si))
+    assert np.array_equal(hyp["draw"], dr), label
+    status, rposes = gr.ransac_fit(cs, ct, dr, edge_similarity)
+    assert np.array_equal(hyp["status"], status), (label, np.bincount(hyp["status"], minlength=4), np.bincount(status, minlength=4))
+    valid = status == gr.VALID
+    err = float(np.abs(hyp["pose"][valid] - rposes[valid]).max()) if valid.any() else 0.0
+    eye = np.eye(4, dtype=np.float32).reshape(16)
+    assert (hyp["pose"][~valid] == eye).all() and (hyp["n_inliers"][~valid] == 0).all() and (hyp["sum_d2"][~valid] == 0).all(), label
+    assert (hyp["reserved"] == 0).all()
+    n_in, sums = gr.ransac_score(hyp["pose"], hyp["status"], cs, ct, inlier_distance)      # scored at the DEVICE's fp32 poses
+    rel = float((np.abs(hyp["sum_d2"] - sums) / np.where(sums > 0, sums, 1.0)).max())
+    print("%s: M = %d, H = %d, statuses %s, max |pose - restatement| = %.3g, max relative sum_d2 error = %.3g"
+          % (label, len(si), H, np.bincount(status, minlength=4).tolist(), err, rel))
+    assert err < POSE_TOL, (label, err)
+    assert np.array_equal(hyp["n_inliers"], n_in), label
+    assert np.allclose(hyp["sum_d2"], sums, rtol=1e-12, atol=0.0), label
+    order = gr.ranking(hyp["status"], hyp["n_inliers"], hyp["sum_d2"])            # a host re-sort of the device's records
+    want = min(n_best, len(order))
+    assert rc == (0 if want else binding.ERR_NO_CORRESPONDENCES), label
+    assert len(poses) == want and len(recs) == want, label
+    assert np.array_equal(recs, hyp[order[:want]]), label
+    for r in range(want):
+        assert np.array_equal(binding.pose_to_c(poses[r]), hyp["pose"][order[r]]), label
+    _, recs2, rc2 = ctx.register_global(check=False)                              # two runs agree byte for byte
+    assert rc2 == rc and hyp.tobytes() == ctx.global_hypotheses().tobytes() and recs.tobytes() == recs2.tobytes(), label
+    return hyp, status, order, poses, recs, rc
+
+
+def test_line_cloud_every_hypothesis_degenerate_or_repeated(gpu_ctx_factory):
+    from icp_amd import binding
+    p, nr = gc.line_cloud()
+    ctx = gpu_ctx_factory()
+    for mutual in (1, 0):
+        load_same(ctx, p, nr, 10)
+        ctx.set_global_options(k=10, mutual=mutual, n_hypotheses=gc.LINE_H, seed=gc.LINE_SEED)
+        hyp, status, order, poses, recs, rc = teacher_forced_ransac(ctx, p, p, gc.LINE_SEED, gc.LINE_H, 16, label="line mutual=%d" % mutual)
+        assert np.isin(hyp["status"], (gr.REPEATED, gr.DEGENERATE)).all() and (hyp["status"] == gr.DEGENERATE).sum() > 400
+        assert rc == binding.ERR_NO_CORRESPONDENCES and poses == [] and len(recs) == 0
+        assert "no valid hypothesis" in ctx.lib.icp_last_error(ctx.h).decode()
+        assert (hyp["pose"] == np.eye(4, dtype=np.float32).reshape(16)).all() and (hyp["n_inliers"] == 0).all() and (hyp["sum_d2"] == 0).all()
+
+
+def test_ribbon_cloud_on_both_sides_of_the_collinearity_threshold(gpu_ctx_factory):
+    p, nr = gc.ribbon_cloud()
+    ctx = gpu_ctx_factory()
+    load_same(ctx, p, nr, 10)
+    ctx.set_global_options(k=10, mutual=1, n_hypotheses=gc.RIBBON_H, seed=gc.RIBBON_SEED)
+    hyp, status, order, poses, recs, rc = teacher_forced_ransac(ctx, p, p, gc.RIBBON_SEED, gc.RIBBON_H, 16, label="ribbon")
+    count = np.bincount(hyp["status"], minlength=4)
+    assert rc == 0 and count[gr.VALID] >= 50 and count[gr.DEGENERATE] >= 50 and count[gr.EDGES] == 0, count
+
+
+@pytest.mark.parametrize("n,start,H", gc.EDGE_CASES)
+def test_edges_of_h_and_m(gpu_ctx_factory, bunny, n, start, H):
+    """M = n correspondences (n source points, no mutual test: tests/test_global_host.py) and H hypotheses, with and without the edge test."""
+    sp, sn, tp, tn = gc.sub_clouds(bunny, n, start)
+    seed = gc.edge_seed(n, start, H)
+    ctx = gpu_ctx_factory()
+    configure(ctx)
+    ctx.set_target(tp, tn); ctx.set_source(sp, sn)
+    for es in gc.EDGE_SIMILARITIES:
+        ctx.set_global_options(k=gc.SUB_K, mutual=0, n_hypotheses=H, edge_similarity=es, seed=seed, n_best=16)
+        hyp, status, _, _, _, _ = teacher_forced_ransac(ctx, sp, tp, seed, H, 16, edge_similarity=es, label="M=%d (from %d) H=%d es=%.1f" % (n, start, H, es))
+        assert len(ctx.match_features()[0]) == n
+        assert 0 <= int(hyp["draw"].min()) and int(hyp["draw"].max()) < n
+        if es == 0.0 and H >= 63 and (n, start) not in ((3, 0), (4, 0)):
+            assert (status == gr.VALID).sum() > H // 8
+
+
+def test_n_best_above_the_valid_count_and_the_hand_over_to_multistart(gpu_ctx_factory, bunny):
+    """n_best = 256 with fewer valid hypotheses: every valid one comes back, in the restatement's ranking; then all of them as the starts of
+    one icp_run_multistart -- more than one 64-start block of its score fold -- each against icp_run."""
+    from test_gpu_multistart import assert_matches_icp_run, expected_best
+    ctx = gpu_ctx_factory()
+    configure(ctx, knn_backend=1, metric=1, n_iterations=5, max_distance=0.0003)
+    ctx.set_target(bunny["tgt_pts"], bunny["tgt_nrm"]); ctx.set_source(bunny["src_pts"], bunny["src_nrm"])
+    ctx.set_global_options(k=gc.N_BEST_K, mutual=1, n_hypotheses=gc.N_BEST_H, seed=0, n_best=256)
+    hyp, status, order, poses, recs, rc = teacher_forced_ransac(ctx, bunny["src_pts"], bunny["tgt_pts"], 0, gc.N_BEST_H, 256, label="n_best")
+    count = int((status == gr.VALID).sum())
+    assert rc == 0 and 65 <= count <= 255
+    assert len(poses) == len(recs) == count == len(order)
+    assert np.array_equal(recs, hyp[order])
+    res, _, best = assert_matches_icp_run(ctx, poses)
+    assert len(res) == count and best == expected_best(res)
 
 
 def rigid_fit(a, b):
