@@ -15,10 +15,39 @@ using namespace icpdev;
     } while (0)
 
 namespace {
+// Device bytes held through ensure / release by every context of the process (views not counted): icp_debug_live_bytes.
+std::atomic<long long> g_live_bytes{0};
+
+// What a context owns frees itself: a device buffer, a page-locked host block, an event, a stream.  All move-only, so a record made of them
+// (Cloud, Level, Bvh, NssLevel, NssHeld, FpfhCache, icp_ctx itself) needs no destructor and no list of its members anywhere.
 struct DevBuf {
     void* p = nullptr; size_t cap = 0;
     bool view = false;                   // part of another allocation (a plane of a packed level, a section of the search-state pack): never freed on its own
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), view(o.view) { o.p = nullptr; o.cap = 0; o.view = false; }      // (a view stays a view)
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; view = o.view; o.p = nullptr; o.cap = 0; o.view = false; } return *this; }
+    ~DevBuf() { reset(); }
+    void reset() { if (p && !view) { (void)hipFree(p); g_live_bytes -= (long long)cap; } p = nullptr; cap = 0; view = false; }
     template <class T> T* as() const { return (T*)p; }
+};
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "a copied DevBuf would be freed twice");
+struct PinBuf {                          // page-locked host block (ensure_pin)
+    void* p = nullptr; size_t cap = 0;
+    PinBuf() = default; PinBuf(const PinBuf&) = delete; PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    template <class T> T* as() const { return (T*)p; }
+};
+struct Event {                           // created where it is first needed (&ev.e); passes for the hipEvent_t it holds
+    hipEvent_t e = nullptr;
+    Event() = default; Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; } Event& operator=(Event&& o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+struct Stream {                          // created where it is first needed (&st.s); passes for the hipStream_t it holds
+    hipStream_t s = nullptr;
+    Stream() = default; Stream(const Stream&) = delete; Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
 };
 
 struct Cloud {
@@ -58,11 +87,11 @@ struct Bvh {
 
 struct icp_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
+    Stream own_stream, depth_stream;     // declared first: destroyed after every buffer, block and event below.  depth_stream: the second stream of the depth frames' uploads
+    hipStream_t stream = nullptr;        // own_stream, or the caller's (icp_ctx_create_on_stream), which is left alone
     int stage_timing = 1;                // icp_set_stage_timing: 0 none, 1 every iteration, N > 1 every Nth iteration (scaled)
     unsigned timing_phase = 0;           // rotates the sampled iterations from run to run
-    void* pinned = nullptr; size_t pinned_cap = 0;   // page-locked host staging: pose upload, stats + pose download (truly asynchronous copies)
+    PinBuf pinned;                       // page-locked host staging: pose upload, stats + pose download (truly asynchronous copies)
     bool trace = false;                  // ICP_HIP_TRACE=1: per-iteration stage times on stderr
     bool merge_loop = true;              // point-to-plane loop through the fused BVH matcher: reduce + solve ride in front of the next matcher launch (ICP_HIP_MERGE=0: separate k_reduce_solve launches)
     int merged_runs = 0, merged_fallbacks = 0;   // runs that took the merged loop / that had to be repeated with the separate launches (icp_debug_counters)
@@ -97,7 +126,7 @@ struct icp_ctx {
     Bvh bvh, bvh6;                       // exact kd-ordered BVH of the target over xyz / over xyz+rgb (knn_backend == ICP_KNN_LBVH)
     DevBuf src_flag, src_box;            // per source point: finite point && finite normal (PointCloud.h:334); bounding box of the finite points (ordered bits)
     DevBuf tgt_flag, tgt_finite, nrm_finite, sel_temp, d_count;   // finite filters of the index builds, compaction scratch
-    void* pin_up = nullptr; size_t pin_up_cap = 0; hipEvent_t up_ev = nullptr; bool up_pending = false;   // page-locked upload staging + "copy has left it" event
+    PinBuf pin_up; Event up_ev; bool up_pending = false;   // page-locked upload staging + "copy has left it" event
     DevBuf okeys, okeys2, ovals, otemp;  // scratch of the Morton sort of the queries
     std::map<int, Level> levels;         // multires selections by decimation factor
     DevBuf sel_lists, sel_counts, sel_blocks;            // RANDOM_SAMPLING / normal-space sampling: per-iteration index lists, their sizes, scan scratch
@@ -115,15 +144,14 @@ struct icp_ctx {
     Cloud conv_src, conv_ref; int conv_n = 0;
     // depth frames (icp_set_*_depth, icp_track_depth_frames): two upload slots, each a page-locked staging block + a device copy of
     // [depth 4n | rgbx 4n]; the next frame of a sequence goes up on depth_stream while the current one iterates
-    void* depth_pin[2] = {nullptr, nullptr}; size_t depth_pin_cap[2] = {0, 0}; DevBuf depth_dev[2]; hipEvent_t depth_up[2] = {nullptr, nullptr}; bool depth_pending[2] = {false, false};
-    hipStream_t depth_stream = nullptr;
+    PinBuf depth_pin[2]; DevBuf depth_dev[2]; Event depth_up[2]; bool depth_pending[2] = {false, false};
     DevBuf depth_blocks, track_rmse;     // block counts / offsets of the depth compaction; per-frame initial + final RMSE of a tracked sequence
-    PoseState* pin_track = nullptr;      // page-locked pose staging of a tracked frame's initial / final RMSE: two slots of its own, apart from `pinned`
+    PinBuf pin_track;                    // page-locked pose staging of a tracked frame's initial / final RMSE: two slots of its own, apart from `pinned`
     DevBuf tsdf_vox, tsdf_cnt; bool tsdf_on = false; icp_tsdf_options tsdf_opt;   // the TSDF volume of frame-to-model tracking (host_tsdf.hpp): (tsdf, weight) per voxel, the update / hit counter, its options (ray_step resolved)
     DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
     float cos_reject = 0.5f;
-    std::vector<hipEvent_t> events;
-    hipEvent_t build_ev[2] = {nullptr, nullptr};   // index-build bracket (build_bvh)
+    std::vector<Event> events;
+    Event build_ev[2];                   // index-build bracket (build_bvh)
     icp_timing timing;
     std::vector<float> it_match_ms, it_post_ms, it_solve_ms;   // per iteration of the last run; -1 where the iteration was not bracketed
     std::string err;
@@ -131,9 +159,6 @@ struct icp_ctx {
 
 namespace {
 constexpr int POST_BLOCKS = 512;
-
-// Device bytes held through ensure / release by every context of the process (views not counted): icp_debug_live_bytes.
-std::atomic<long long> g_live_bytes{0};
 
 int ensure(icp_ctx* c, DevBuf& b, size_t bytes) {
     if (bytes <= b.cap && b.p) return ICP_OK;
@@ -144,23 +169,21 @@ int ensure(icp_ctx* c, DevBuf& b, size_t bytes) {
     b.cap = want; g_live_bytes += (long long)want;
     return ICP_OK;
 }
-int ensure_pinned(icp_ctx* c, size_t bytes) {
-    if (bytes <= c->pinned_cap && c->pinned) return ICP_OK;
-    if (c->pinned) { HIPCK(c, hipHostFree(c->pinned)); c->pinned = nullptr; c->pinned_cap = 0; }
-    const size_t want = bytes < 4096 ? 4096 : bytes;
-    HIPCK(c, hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
-    c->pinned_cap = want;
+// A page-locked block of at least `bytes`; one that has to grow becomes max(min_bytes, bytes + bytes / slack_div) (slack_div 0: no slack).
+int ensure_pin(icp_ctx* c, PinBuf& b, size_t bytes, size_t min_bytes, size_t slack_div) {
+    if (bytes <= b.cap && b.p) return ICP_OK;
+    if (b.p) { HIPCK(c, hipHostFree(b.p)); b.p = nullptr; b.cap = 0; }
+    const size_t want = bytes < min_bytes ? min_bytes : bytes + (slack_div ? bytes / slack_div : 0);
+    HIPCK(c, hipHostMalloc(&b.p, want, hipHostMallocDefault));
+    b.cap = want;
     return ICP_OK;
 }
-void release(DevBuf& b) { if (b.p && !b.view) { (void)hipFree(b.p); g_live_bytes -= (long long)b.cap; } b.p = nullptr; b.cap = 0; b.view = false; }
+int ensure_pinned(icp_ctx* c, size_t bytes) { return ensure_pin(c, c->pinned, bytes, 4096, 0); }
+void release(DevBuf& b) { b.reset(); }
 void set_view(DevBuf& b, void* p, size_t bytes) { release(b); b.p = p; b.cap = bytes; b.view = true; }
+// (these also run outside destroy, where the record lives on: a dropped level or draw must not look valid)
 void release(Cloud& c) { release(c.x); release(c.y); release(c.z); release(c.nx); release(c.ny); release(c.nz); release(c.cr); release(c.cg); release(c.cb); release(c.rgba); }
 void release(Level& lv) { release(lv.idx); release(lv.order); release(lv.sorted_idx); release(lv.sorted); release(lv.pack); lv.sorted_valid = false; }
-void release(Bvh& b) {
-    for (DevBuf* d : {&b.keys, &b.keys2, &b.vals, &b.vals2, &b.temp, &b.leaves, &b.recs, &b.nodes, &b.qnodes, &b.pos_of, &b.side, &b.scanr, &b.axis_of_node}) release(*d);
-    for (DevBuf& d : b.axl) release(d);
-    b.valid = false;
-}
 void release(NssLevel& nl) { release(nl.cand); release(nl.seg); release(nl.longs); }
 // the normal-space sampling caches that belong to the resident source (held: only the held draws, which also depend on the options)
 void drop_nss(icp_ctx* c, bool held_only);
@@ -197,12 +220,9 @@ struct DrainOnError {
 // wait is for the previous upload to have left the staging buffer.  (Round 1: pageable copies + one synchronisation per plane.)
 int ensure_pin_up(icp_ctx* c, size_t bytes) {
     if (c->up_pending) { HIPCK(c, hipEventSynchronize(c->up_ev)); c->up_pending = false; }
-    if (bytes <= c->pin_up_cap && c->pin_up) return ICP_OK;
-    if (c->pin_up) { HIPCK(c, hipHostFree(c->pin_up)); c->pin_up = nullptr; c->pin_up_cap = 0; }
-    const size_t want = bytes < 65536 ? 65536 : bytes + bytes / 8;
-    HIPCK(c, hipHostMalloc(&c->pin_up, want, hipHostMallocDefault));
-    c->pin_up_cap = want;
-    if (!c->up_ev) HIPCK(c, hipEventCreateWithFlags(&c->up_ev, hipEventDisableTiming));
+    int rc;
+    if ((rc = ensure_pin(c, c->pin_up, bytes, 65536, 8))) return rc;
+    if (!c->up_ev) HIPCK(c, hipEventCreateWithFlags(&c->up_ev.e, hipEventDisableTiming));
     return ICP_OK;
 }
 int upload_cloud(icp_ctx* c, Cloud& cl, const float* xyz, const float* nrm, const uint8_t* rgba, int n, bool pad_inf) {
@@ -211,7 +231,7 @@ int upload_cloud(icp_ctx* c, Cloud& cl, const float* xyz, const float* nrm, cons
     int rc;
     if ((rc = ensure_pin_up(c, total))) return rc;
     if ((rc = ensure(c, c->staging, total))) return rc;
-    char* h = (char*)c->pin_up;
+    char* h = c->pin_up.as<char>();
     memcpy(h, xyz, b_xyz);
     if (nrm) memcpy(h + b_xyz, nrm, b_nrm);
     if (rgba) memcpy(h + b_xyz + b_nrm, rgba, b_col);
@@ -241,12 +261,30 @@ int upload3(icp_ctx* c, const float* aos, int n, int npad, float pad_value, DevB
     if ((rc = ensure_pin_up(c, (size_t)n * 12))) return rc;
     if ((rc = ensure(c, c->staging, (size_t)n * 12))) return rc;
     for (DevBuf* pl : {&x, &y, &z}) if ((rc = ensure(c, *pl, (size_t)npad * 4))) return rc;
-    memcpy(c->pin_up, aos, (size_t)n * 12);
-    HIPCK(c, hipMemcpyAsync(c->staging.p, c->pin_up, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    memcpy(c->pin_up.p, aos, (size_t)n * 12);
+    HIPCK(c, hipMemcpyAsync(c->staging.p, c->pin_up.p, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipEventRecord(c->up_ev, c->stream)); c->up_pending = true;
     hipLaunchKernelGGL(k_deinterleave3, dim3((npad + 255) / 256), dim3(256), 0, c->stream, c->staging.as<float>(), n, npad, pad_value, x.as<float>(), y.as<float>(), z.as<float>());
     HIPCK(c, hipGetLastError());
     HIPCK(c, hipStreamSynchronize(c->stream));      // staging is reused by the caller's next plane
+    return ICP_OK;
+}
+
+// Small counts the device has produced come back through one slot of the page-locked block, at 2048 (the first bytes of the block stage
+// the pose): n_words 4-byte words.  read_count: one count, copied and waited for.  Where the copy has to go out among others, count_slot
+// gives the slot and the caller enqueues the copy and waits itself.
+int count_slot(icp_ctx* c, int** slot) {
+    int rc;
+    if ((rc = ensure_pinned(c, 4096))) return rc;
+    *slot = (int*)(c->pinned.as<char>() + 2048);
+    return ICP_OK;
+}
+int read_count(icp_ctx* c, const void* d_count, int* out, int n_words = 1) {
+    int rc; int* h;
+    if ((rc = count_slot(c, &h))) return rc;
+    HIPCK(c, hipMemcpyAsync(h, d_count, (size_t)n_words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    memcpy(out, h, (size_t)n_words * 4);
     return ICP_OK;
 }
 
@@ -263,12 +301,7 @@ int compact_flagged(icp_ctx* c, const uint8_t* d_flags, int count, int factor, D
     HIPCK(c, rocprim::select(nullptr, tb, in, d_flags, out.as<int>(), c->d_count.as<int>(), (size_t)count, c->stream));
     if ((rc = ensure(c, c->sel_temp, tb))) return rc;
     HIPCK(c, rocprim::select(c->sel_temp.p, tb, in, d_flags, out.as<int>(), c->d_count.as<int>(), (size_t)count, c->stream));
-    if ((rc = ensure_pinned(c, 4096))) return rc;
-    int* h = (int*)((char*)c->pinned + 2048);            // (the first bytes of the pinned block stage the pose)
-    HIPCK(c, hipMemcpyAsync(h, c->d_count.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    *n_out = *h;
-    return ICP_OK;
+    return read_count(c, c->d_count.p, n_out);
 }
 // finite filter of a cloud that is already on the device -> flag bytes + compacted index list
 int finite_list(icp_ctx* c, const Cloud& cl, bool with_normals, DevBuf& flag, DevBuf& list, int* n_out) {
@@ -296,7 +329,7 @@ int write_pose_via(icp_ctx* c, PoseState* h, const float pose[16]) {
 int write_pose(icp_ctx* c, const float pose[16]) {
     int rc;
     if ((rc = ensure_pinned(c, sizeof(PoseState)))) return rc;
-    return write_pose_via(c, (PoseState*)c->pinned, pose);
+    return write_pose_via(c, c->pinned.as<PoseState>(), pose);
 }
 
 int check_ready(icp_ctx* c, bool need_source, bool full_pipeline) {
@@ -317,7 +350,7 @@ int check_ready(icp_ctx* c, bool need_source, bool full_pipeline) {
 }
 
 int ensure_events(icp_ctx* c, size_t count) {
-    while (c->events.size() < count) { hipEvent_t e; HIPCK(c, hipEventCreate(&e)); c->events.push_back(e); }
+    while (c->events.size() < count) { Event e; HIPCK(c, hipEventCreate(&e.e)); c->events.push_back(std::move(e)); }
     return ICP_OK;
 }
 }  // namespace

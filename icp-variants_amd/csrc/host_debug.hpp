@@ -159,10 +159,10 @@ int icp_debug_loop_sums(icp_ctx* c, const float pose[16], int32_t form, int32_t 
         LoopRun r{};
         r.pl.sorted_levels = pl.sorted_levels; r.pl.fixed_sets = pl.fixed_sets;
         for (int k : two) { r.pl.factors.push_back(pl.factors[k]); r.pl.ns.push_back(pl.ns[k]); r.pl.clouds.push_back(pl.clouds[k]); r.pl.sels.push_back(pl.sels[k]); r.pl.orders.push_back(pl.orders[k]); }
-        r.pin_pose = r.pin_stats + (((size_t)2 * sizeof(icp_iter_stats) + 255) & ~(size_t)255); r.pin_lm = r.pin_pose + 512;
-        if ((rc = ensure_pinned(c, r.pin_lm))) return rc;
+        r.lay_out(2, false, false);
+        if ((rc = ensure_pinned(c, r.pin_bytes))) return rc;
         if ((rc = write_pose(c, pose))) return rc;
-        if ((rc = ensure(c, c->stats, r.pin_pose - r.pin_stats + 192))) return rc;
+        if ((rc = ensure(c, c->stats, r.stats_bytes))) return rc;
         if ((rc = ensure_events(c, 2 * 4 + 2))) return rc;
         r.sampled.assign(2, 0); r.eligible.assign(2, 0); r.ev.assign(2, IterEvents());
         if ((rc = enqueue_merged(c, r))) return rc;
@@ -170,13 +170,13 @@ int icp_debug_loop_sums(icp_ctx* c, const float pose[16], int32_t form, int32_t 
         HIPCK(c, hipMemcpyAsync(row, c->ring.as<char>() + (size_t)3 * POSE_REPLICAS * POSE_REPLICA_STRIDE, NSUM * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCK(c, hipMemcpyAsync(&hp, loop_slot(c->ring.as<PoseState>(), 1, 0), sizeof(hp), hipMemcpyDeviceToHost, c->stream));      // slot 1: the pose the first iteration composed
         HIPCK(c, hipStreamSynchronize(c->stream));
-        if (*(const int*)((char*)c->pinned + r.pin_pose + 128) || hp.fault == 1) { c->err = "icp_debug_loop_sums: a bounded wait of the merged launches ran out"; return ICP_ERR_HIP; }
+        if (r.host_tail(c)->merged_fault || hp.fault == 1) { c->err = "icp_debug_loop_sums: a bounded wait of the merged launches ran out"; return ICP_ERR_HIP; }
         for (int a = 0; a < NSUM; a++) {
             if (a < NSUM_USED && row[a] == GRANULE_EMPTY) { c->err = "icp_debug_loop_sums: a total of the ring was never written"; return ICP_ERR_HIP; }
             if (a < NSUM_USED) memcpy(&hs[a], &row[a], 8); else hs[a] = 0.0;
         }
         if (hp.fault) { memcpy(st.pose, pose, 64); st.n_valid = (int)hs[SUM_N]; }      // the chain was cut: no record was written
-        else memcpy(&st, (char*)c->pinned + r.pin_stats, sizeof(st));
+        else memcpy(&st, r.host_records(c), sizeof(st));
         family = 2;
     }
     const Bvh& b = colors ? c->bvh6 : c->bvh;

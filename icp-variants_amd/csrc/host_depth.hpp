@@ -37,19 +37,16 @@ int check_depth_args(icp_ctx* c, const icp_depth_camera* cam, const icp_depth_op
 // The colour frame has n pixels unless n_color says otherwise (icp_depth_mesh's colour camera).
 int stage_depth(icp_ctx* c, int slot, const float* depth, const uint8_t* rgbx, int n, hipStream_t s, int n_color = -1) {
     if (n_color < 0) n_color = n;
-    if (!c->depth_up[slot]) HIPCK(c, hipEventCreateWithFlags(&c->depth_up[slot], hipEventDisableTiming));
+    if (!c->depth_up[slot]) HIPCK(c, hipEventCreateWithFlags(&c->depth_up[slot].e, hipEventDisableTiming));
     if (c->depth_pending[slot]) { HIPCK(c, hipEventSynchronize(c->depth_up[slot])); c->depth_pending[slot] = false; }
     const size_t bytes = (size_t)n * 4 + (rgbx ? (size_t)n_color * 4 : 0), cap = (size_t)n * 4 + (size_t)(n_color > n ? n_color : n) * 4;
-    if (bytes > c->depth_pin_cap[slot] || !c->depth_pin[slot]) {
-        if (c->depth_pin[slot]) { HIPCK(c, hipHostFree(c->depth_pin[slot])); c->depth_pin[slot] = nullptr; c->depth_pin_cap[slot] = 0; }
-        HIPCK(c, hipHostMalloc(&c->depth_pin[slot], cap, hipHostMallocDefault));
-        c->depth_pin_cap[slot] = cap;
-    }
     int rc;
+    PinBuf& pin = c->depth_pin[slot];
+    if ((rc = ensure_pin(c, pin, bytes, cap, 0))) return rc;      // (a block that has to grow becomes exactly cap >= bytes)
     if ((rc = ensure(c, c->depth_dev[slot], cap))) return rc;
-    memcpy(c->depth_pin[slot], depth, (size_t)n * 4);
-    if (rgbx) memcpy((char*)c->depth_pin[slot] + (size_t)n * 4, rgbx, (size_t)n_color * 4);
-    HIPCK(c, hipMemcpyAsync(c->depth_dev[slot].p, c->depth_pin[slot], bytes, hipMemcpyHostToDevice, s));
+    memcpy(pin.p, depth, (size_t)n * 4);
+    if (rgbx) memcpy(pin.as<char>() + (size_t)n * 4, rgbx, (size_t)n_color * 4);
+    HIPCK(c, hipMemcpyAsync(c->depth_dev[slot].p, pin.p, bytes, hipMemcpyHostToDevice, s));
     HIPCK(c, hipEventRecord(c->depth_up[slot], s)); c->depth_pending[slot] = true;
     return ICP_OK;
 }
@@ -75,7 +72,6 @@ int depth_to_cloud(icp_ctx* c, int slot, const icp_depth_camera& cam, const icp_
     else for (DevBuf* pl : {&cl.rgba, &cl.cr, &cl.cg, &cl.cb}) release(*pl);      // no colour planes of an earlier, differently sized cloud stay behind
     if ((rc = ensure(c, c->depth_blocks, (size_t)nb * 4))) return rc;
     if ((rc = ensure(c, c->d_count, 16))) return rc;
-    if ((rc = ensure_pinned(c, 4096))) return rc;
     DepthOut o;
     o.x = cl.x.as<float>(); o.y = cl.y.as<float>(); o.z = cl.z.as<float>(); o.nx = cl.nx.as<float>(); o.ny = cl.ny.as<float>(); o.nz = cl.nz.as<float>();
     o.cr = with_colors ? cl.cr.as<float>() : nullptr; o.cg = with_colors ? cl.cg.as<float>() : nullptr; o.cb = with_colors ? cl.cb.as<float>() : nullptr;
@@ -84,13 +80,47 @@ int depth_to_cloud(icp_ctx* c, int slot, const icp_depth_camera& cam, const icp_
     hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, c->stream, c->depth_blocks.as<int>(), nb, c->d_count.as<int>());
     hipLaunchKernelGGL(k_depth_scatter, dim3(nb), dim3(256), 0, c->stream, fr, (const int*)c->depth_blocks.as<int>(), (const int*)c->d_count.as<int>(), pad ? 1 : 0, o);
     HIPCK(c, hipGetLastError());
-    int* h = (int*)((char*)c->pinned + 2048);            // (the first bytes of the pinned block stage the pose)
-    HIPCK(c, hipMemcpyAsync(h, c->d_count.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    const int kept = *h;
+    int kept = 0;
+    if ((rc = read_count(c, c->d_count.p, &kept))) return rc;
     cl.n = kept; cl.npad = pad ? (kept + 63) / 64 * 64 : kept;
     cl.has_normals = true; cl.has_colors = with_colors;
     *n_out = kept;
+    return ICP_OK;
+}
+
+// ---- the ground-truth RMSE bracket of a tracked frame, shared by icp_track_depth_frames and icp_track_depth_model ----
+// track_rmse: per tracked frame its initial and final RMSE; pin_track: two page-locked pose slots of their own (see track_rmse_at).
+int track_rmse_prepare(icp_ctx* c, int n_frames) {
+    int rc;
+    if ((rc = ensure(c, c->track_rmse, (size_t)(n_frames - 1) * 8))) return rc;
+    return ensure_pin(c, c->pin_track, 2 * sizeof(PoseState), 0, 0);
+}
+// The convergence reference of the frame: the resident source (its `kept` points) and the same points moved by g.
+int track_reference(icp_ctx* c, int kept, const Pose16& g) {
+    int rc;
+    for (DevBuf* pl : {&c->conv_src.x, &c->conv_src.y, &c->conv_src.z, &c->conv_ref.x, &c->conv_ref.y, &c->conv_ref.z}) if ((rc = ensure(c, *pl, (size_t)kept * 4))) return rc;
+    hipLaunchKernelGGL(k_conv_from_source, dim3((kept + 255) / 256), dim3(256), 0, c->stream, c->src.x.as<float>(), c->src.y.as<float>(), c->src.z.as<float>(), kept, g,
+                       c->conv_src.x.as<float>(), c->conv_src.y.as<float>(), c->conv_src.z.as<float>(), c->conv_ref.x.as<float>(), c->conv_ref.y.as<float>(), c->conv_ref.z.as<float>());
+    HIPCK(c, hipGetLastError());
+    c->conv_n = kept;
+    return ICP_OK;
+}
+// The RMSE of the reference under `pose` into d_out, enqueued; k = 0 before the frame's run, 1 after it.  The pose is staged in
+// pin_track[k], not in `pinned`: run_loop's write_pose rewrites `pinned` right after the initial measure, while this copy may still wait
+// behind the kernels in front of it.  pin_track[0] / [1] are rewritten only by the next frame, after its first count read (depth_to_cloud,
+// set_target_tsdf) has synchronised the stream, i.e. after both copies have left them; the end of the call synchronises before the last
+// ones matter.
+int track_rmse_at(icp_ctx* c, int k, const float pose[16], float* d_out) {
+    int rc;
+    if ((rc = write_pose_via(c, c->pin_track.as<PoseState>() + k, pose))) return rc;
+    return enqueue_rmse(c, d_out);
+}
+// After the stream has drained: the measures back, into the frames that `measured` says had both taken.
+template <class Measured>
+int track_rmse_finish(icp_ctx* c, int n_frames, icp_track_frame* out, Measured measured) {
+    std::vector<float> h((size_t)(n_frames - 1) * 2);
+    HIPCK(c, hipMemcpy(h.data(), c->track_rmse.p, h.size() * 4, hipMemcpyDeviceToHost));
+    for (int k = 1; k < n_frames; k++) if (measured(out[k - 1])) { out[k - 1].initial_rmse = h[(size_t)(k - 1) * 2]; out[k - 1].final_rmse = h[(size_t)(k - 1) * 2 + 1]; }
     return ICP_OK;
 }
 
@@ -177,7 +207,7 @@ int icp_track_depth_frames(icp_ctx* c, const float* depth_frames, const uint8_t*
     const int n = cam->width * cam->height;
     const size_t fbytes = (size_t)n * 4;
     auto frame_rgbx = [&](int k) { return rgbx_frames ? rgbx_frames + (size_t)k * fbytes : nullptr; };
-    if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream, hipStreamNonBlocking));
+    if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     // frame 0 = the target, its index built once (main.cpp:200-207); frame 1 goes up meanwhile
     int kept = 0;
     if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
@@ -191,10 +221,7 @@ int icp_track_depth_frames(icp_ctx* c, const float* depth_frames, const uint8_t*
         return guard.done(ICP_ERR_NO_TARGET);
     }
     if ((rc = finish_target(c, rgbx_frames != nullptr))) return rc;
-    if (gt_frames && n_frames > 1) {
-        if ((rc = ensure(c, c->track_rmse, (size_t)(n_frames - 1) * 8))) return rc;
-        if (!c->pin_track) HIPCK(c, hipHostMalloc((void**)&c->pin_track, 2 * sizeof(PoseState), hipHostMallocDefault));
-    }
+    if (gt_frames && n_frames > 1 && (rc = track_rmse_prepare(c, n_frames))) return rc;
     int first_err = ICP_OK;
     for (int k = 1; k < n_frames; k++) {
         icp_track_frame& r = out[k - 1];
@@ -214,17 +241,8 @@ int icp_track_depth_frames(icp_ctx* c, const float* depth_frames, const uint8_t*
         if (gt_frames) {
             // ConvergenceMeasure(source, transformPoints(source, targetTrajectory * trajectory_k^-1)) (main.cpp:296-305), on the device
             Pose16 g; memcpy(g.m, gt_frames + (size_t)(k - 1) * 16, 64);
-            for (DevBuf* pl : {&c->conv_src.x, &c->conv_src.y, &c->conv_src.z, &c->conv_ref.x, &c->conv_ref.y, &c->conv_ref.z}) if ((rc = ensure(c, *pl, (size_t)kept * 4))) return rc;
-            hipLaunchKernelGGL(k_conv_from_source, dim3((kept + 255) / 256), dim3(256), 0, c->stream, c->src.x.as<float>(), c->src.y.as<float>(), c->src.z.as<float>(), kept, g,
-                               c->conv_src.x.as<float>(), c->conv_src.y.as<float>(), c->conv_src.z.as<float>(), c->conv_ref.x.as<float>(), c->conv_ref.y.as<float>(), c->conv_ref.z.as<float>());
-            HIPCK(c, hipGetLastError());
-            c->conv_n = kept;
-            // initial_rmse = rmseAlignmentError(currentCameraToWorld) (:305).  Its pose is staged in pin_track[0], not in `pinned`: run_loop's
-            // write_pose rewrites `pinned` right after this, while this copy may still wait behind the kernels above.  pin_track[0] / [1]
-            // are rewritten only by the next frame, after depth_to_cloud has synchronised the stream (the count read), i.e. after both
-            // copies have left them; the end of the call synchronises before the last ones matter.
-            if ((rc = write_pose_via(c, &c->pin_track[0], pose_inout))) return rc;
-            if ((rc = enqueue_rmse(c, d_rmse))) return rc;
+            if ((rc = track_reference(c, kept, g))) return rc;
+            if ((rc = track_rmse_at(c, 0, pose_inout, d_rmse))) return rc;      // initial_rmse = rmseAlignmentError(currentCameraToWorld) (:305)
         }
         int32_t iters = 0;
         rc = run_loop(c, pose_inout, nullptr, 0, &iters, false, c->merge_loop);          // estimatePose(source, target, currentCameraToWorld) (:308)
@@ -232,17 +250,10 @@ int icp_track_depth_frames(icp_ctx* c, const float* depth_frames, const uint8_t*
         r.iterations = iters; r.status = rc;
         memcpy(r.pose, pose_inout, 64);
         if (rc != ICP_OK && first_err == ICP_OK) first_err = rc;
-        if (gt_frames) {
-            if ((rc = write_pose_via(c, &c->pin_track[1], pose_inout))) return rc;   // final RMSE (:311)
-            if ((rc = enqueue_rmse(c, d_rmse + 1))) return rc;
-        }
+        if (gt_frames && (rc = track_rmse_at(c, 1, pose_inout, d_rmse + 1))) return rc;      // final RMSE (:311)
     }
     HIPCK(c, hipStreamSynchronize(c->stream));
-    if (gt_frames && n_frames > 1) {
-        std::vector<float> h((size_t)(n_frames - 1) * 2);
-        HIPCK(c, hipMemcpy(h.data(), c->track_rmse.p, h.size() * 4, hipMemcpyDeviceToHost));
-        for (int k = 1; k < n_frames; k++) if (out[k - 1].n_src > 0) { out[k - 1].initial_rmse = h[(size_t)(k - 1) * 2]; out[k - 1].final_rmse = h[(size_t)(k - 1) * 2 + 1]; }
-    }
+    if (gt_frames && n_frames > 1 && (rc = track_rmse_finish(c, n_frames, out, [](const icp_track_frame& r) { return r.n_src > 0; }))) return rc;
     guard.ok = true;
     return first_err;
 }
@@ -295,8 +306,8 @@ int icp_depth_mesh(icp_ctx* c, const float* depth, const uint8_t* rgbx, const ic
     f.depth = c->depth_dev[0].as<float>(); f.rgbx = with_colors ? c->depth_dev[0].as<uint8_t>() + (size_t)n * 4 : nullptr;
     if ((rc = ensure(c, c->staging, (size_t)n * 16 + (size_t)nq * 24))) return rc;
     float* d_xyz = c->staging.as<float>(); uint32_t* d_rgba = (uint32_t*)(d_xyz + (size_t)n * 3); uint32_t* d_tris = d_rgba + n;
-    if ((rc = ensure_pinned(c, 4096))) return rc;
-    int* hn = (int*)((char*)c->pinned + 2048);            // (the first bytes of the pinned block stage the pose)
+    int* hn;
+    if ((rc = count_slot(c, &hn))) return rc;
     *hn = 0;
     hipLaunchKernelGGL(k_mesh_vertices, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, f, d_xyz, with_colors ? d_rgba : nullptr);
     if (nq > 0) {

@@ -28,8 +28,8 @@ int build_query_order(icp_ctx* c, const int* d_sel, int n, DevBuf& out) {
 template <int DIM>
 int build_bvh(icp_ctx* c, Bvh& b, const CoordPtrs<DIM>& cp) {
     int rc;
-    if (!c->build_ev[0]) HIPCK(c, hipEventCreate(&c->build_ev[0]));      // owned by the context: nothing to leak on an error return
-    if (!c->build_ev[1]) HIPCK(c, hipEventCreate(&c->build_ev[1]));
+    if (!c->build_ev[0]) HIPCK(c, hipEventCreate(&c->build_ev[0].e));      // owned by the context: nothing to leak on an error return
+    if (!c->build_ev[1]) HIPCK(c, hipEventCreate(&c->build_ev[1].e));
     const hipEvent_t e0 = c->build_ev[0], e1 = c->build_ev[1];
     HIPCK(c, hipEventRecord(e0, c->stream));
     const int nv = b.n_valid;
@@ -166,7 +166,7 @@ int get_level(icp_ctx* c, int factor, const int** d_idx, int* n_out, const int**
             HIPCK(c, hipGetLastError());
             if ((rc = compact_flagged(c, c->staging.as<uint8_t>(), count, factor, lv.idx, &lv.n))) return rc;
         } else lv.n = c->src.n;                                   // factor 0: every point, no index list
-        it = c->levels.emplace(factor, lv).first;
+        it = c->levels.emplace(factor, std::move(lv)).first;
     }
     *d_idx = it->second.idx.as<int>(); *n_out = it->second.n;
     if (d_order) {

@@ -45,7 +45,7 @@ int nss_level(icp_ctx* c, int factor, const int* base, int n_base, const NssLeve
         hipLaunchKernelGGL(k_nss_level_scatter, dim3(nblocks), dim3(NSS_LEVEL_THREADS), 0, c->stream, base, n_base, bkt, nb, c->nss_table.as<int>(), nblocks, nl.cand.as<int>());
         hipLaunchKernelGGL(k_nss_level_segs, dim3(1), dim3(NSS_QUOTA_THREADS), 0, c->stream, c->nss_table.as<int>(), nblocks, nb, nl.seg.as<int>(), nl.longs.as<NssLongs>());
         if (hipGetLastError() != hipSuccess) { release(nl); c->err = "normal-space sampling: a level launch failed"; return ICP_ERR_HIP; }
-        it = c->nss_levels.emplace(factor, nl).first;
+        it = c->nss_levels.emplace(factor, std::move(nl)).first;
     }
     *out = &it->second;
     return ICP_OK;
@@ -251,17 +251,43 @@ RingParams ring_params(const icp_ctx* c, const Ring& r, int j, int n_prev, PoseS
     return rp;
 }
 
-// What run_loop's prologue hands the form that enqueues the run.  Page-locked staging of the whole run: [pose state up | records down
-// (pin_stats) | pose state down (pin_pose) | LM records down (pin_lm), non-linear runs only]; c->stats is laid out like pin_stats ..
-// pin_pose .. + 128 .. + 192 (records | final pose state | fault word of the merged form).  Stage timing (TimeMeasure.h:20-26): a HIP event
+// The tail of a run's result block: what lies behind the iteration records in c->stats, at the same offsets in the page-locked staging.
+// Device code holds pointers into it (RingParams::final_out / run_fault, ConvergeParams::words / trace): no member may move.
+struct RunTail {
+    PoseState final_pose;                 // the pose state after the last iteration (merged form: written by its closing launch)
+    int merged_fault, spare[3];           // the merged form's fault word; k_run_init clears it and the 15 words behind it
+    int merged_cvg[12];                   // of which these serve as the merged form's convergence control words (CONV_*, dev_converge.hpp)
+    char unused[64];                      // (a run that cannot stop on a converged pose keeps and copies the tail up to here)
+    int cvg_state[CONV_STATE_BYTES / 4];  // the separate form's convergence state block: control words | search pose | final pose state
+    icp_convergence_step* trace() { return (icp_convergence_step*)(this + 1); }      // one step per iteration, behind the tail
+    // the bytes in use: with stopping on a converged pose (cvg, dev_converge.hpp) the whole tail and n_trace steps of the trace
+    static constexpr size_t used_bytes(bool cvg, int n_trace) { return cvg ? sizeof(RunTail) + (size_t)n_trace * sizeof(icp_convergence_step) : offsetof(RunTail, unused); }
+};
+static_assert(offsetof(RunTail, merged_fault) == 128 && offsetof(RunTail, merged_cvg) == 144 && offsetof(RunTail, unused) == 192 && offsetof(RunTail, cvg_state) == 256 && sizeof(RunTail) == 512, "the layout the device was handed");
+
+// What run_loop's prologue hands the form that enqueues the run.  lay_out places the run in the page-locked staging -- [pose state up |
+// records down | tail down | LM records down, non-linear runs only], every part on a 256-byte boundary -- and sizes c->stats (records |
+// tail); the accessors are the host's and the device's views of the parts.  Stage timing (TimeMeasure.h:20-26): a HIP event
 // costs ~4 us of stream time, so mode N > 1 brackets only every Nth iteration (`sampled`, offset rotating from run to run) and scales the
 // sums.  Event slots: 4 per iteration + run start / run end; each form fills ev[i] of a sampled iteration with the ones it records.
-// Stopping on a converged pose (cvg, dev_converge.hpp) adds, at the same offsets behind the records on the device and in the staging:
-// + 144 the merged form's control words (the spare words beside its fault word), + 256 the separate form's state block (control words |
-// search pose | final pose state), + 512 the trace; eligible[i] = the host's half of iteration i's eligibility, from the plan's factors.
+// eligible[i] = the host's half of iteration i's eligibility to stop the run (cvg), from the plan's factors.
 struct IterEvents { hipEvent_t start = nullptr, matched = nullptr, posted = nullptr, end = nullptr; };   // posted / end: nullptr = the form has no such stage to bracket
-struct LoopRun { RunPlan pl; bool lm, robust, recip, rmse, fontana, cvg; size_t pin_stats = 256, pin_pose, pin_lm; std::vector<char> sampled, eligible; std::vector<IterEvents> ev; int n_enqueued = 0; };
-constexpr size_t CVG_MERGED_WORDS = 128 + 16, CVG_STATE = 256, CVG_TRACE = 512;      // offsets from the final pose state
+struct LoopRun {
+    RunPlan pl; bool lm, robust, recip, rmse, fontana, cvg; std::vector<char> sampled, eligible; std::vector<IterEvents> ev; int n_enqueued = 0;
+    size_t pin_stats = 256, pin_tail, pin_lm, pin_bytes, stats_bytes;      // offsets into the staging and its size; the size of c->stats
+    void lay_out(int iters, bool with_lm, bool with_cvg) {
+        auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t trace_pad = with_cvg ? pad((size_t)iters * sizeof(icp_convergence_step)) : 0;
+        pin_tail = pin_stats + pad((size_t)iters * sizeof(icp_iter_stats)); pin_lm = pin_tail + sizeof(RunTail) + trace_pad;
+        pin_bytes = pin_lm + (with_lm ? (size_t)iters * sizeof(icp_lm_summary) : 0);
+        stats_bytes = records_bytes() + (with_cvg ? sizeof(RunTail) + trace_pad : RunTail::used_bytes(false, 0));
+    }
+    size_t records_bytes() const { return pin_tail - pin_stats; }      // the records of every iteration, padded
+    RunTail* dev_tail(const icp_ctx* c) const { return (RunTail*)(c->stats.as<char>() + records_bytes()); }
+    icp_iter_stats* host_records(const icp_ctx* c) const { return (icp_iter_stats*)(c->pinned.as<char>() + pin_stats); }
+    RunTail* host_tail(const icp_ctx* c) const { return (RunTail*)(c->pinned.as<char>() + pin_tail); }
+    icp_lm_summary* host_lm(const icp_ctx* c) const { return (icp_lm_summary*)(c->pinned.as<char>() + pin_lm); }
+};
 // The separate form enqueues a run that may stop in chunks of this many iterations and reads the stop word between them: the chunk size
 // trades host round trips against iterations enqueued in vain.  Time only, never results.  2: the fastest of {1, 2, 4, 8} on the bench
 // pair with GICP (1.17 / 1.16 / 1.19 / 1.17 ms for a run that stops after 13 of 50 iterations; tools/time_converge.py).
@@ -269,14 +295,13 @@ constexpr size_t CVG_MERGED_WORDS = 128 + 16, CVG_STATE = 256, CVG_TRACE = 512; 
 #define ICP_CONVERGE_CHUNK 2
 #endif
 constexpr int CONVERGE_CHUNK = ICP_CONVERGE_CHUNK;
-ConvergeParams converge_params(const icp_ctx* c, const LoopRun& r, int i, size_t words_at) {
+ConvergeParams converge_params(const icp_ctx* c, const LoopRun& r, int i, int* words) {
     ConvergeParams cp; memset(&cp, 0, sizeof(cp));
     if (!r.cvg) return cp;
     const icp_convergence_options& o = c->cvg_opt;
-    char* base = c->stats.as<char>() + (r.pin_pose - r.pin_stats);
     cp.on = 1; cp.eligible = r.eligible[(size_t)i]; cp.index = i; cp.min_iterations = o.min_iterations; cp.patience = o.patience;
     cp.rotation_eps = o.rotation_eps; cp.translation_eps = o.translation_eps;
-    cp.trace = (icp_convergence_step*)(base + CVG_TRACE); cp.words = (int*)(base + words_at);
+    cp.trace = r.dev_tail(c)->trace(); cp.words = words;
     return cp;
 }
 hipEvent_t loop_event(const icp_ctx* c, int i, int k) { return c->events[(size_t)2 + 4 * i + k]; }
@@ -289,17 +314,17 @@ hipEvent_t loop_event(const icp_ctx* c, int i, int k) { return c->events[(size_t
 // from the dispatch itself, no bracket on the stream); a "solve" exists only for the last iteration: the closing launch, up to slot 3.
 int enqueue_merged(icp_ctx* c, LoopRun& r) {
     const icp_params& p = c->prm; const RunPlan& pl = r.pl;
-    const int iters = pl.iters(); const size_t stats_pad = r.pin_pose - r.pin_stats;
+    const int iters = pl.iters(); RunTail* tail = r.dev_tail(c);
     int rc, nbmax = POST_BLOCKS;
     for (int i = 0; i < iters; i++) { const int nb = fused_nblocks(pl.ns[i]); if (nb > nbmax) nbmax = nb; }
     Ring ring;
-    if ((rc = make_ring(c, iters + 1, iters, nbmax, (int*)(c->stats.as<char>() + stats_pad + 128), ring))) return rc;
+    if ((rc = make_ring(c, iters + 1, iters, nbmax, &tail->merged_fault, ring))) return rc;
     const int n_init = (iters + 1) * POSE_REPLICAS * 16 + iters * NSUM + 16;
     hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, c->ps.as<PoseState>(), ring.slots, iters + 1, ring.trows, iters * NSUM, ring.run_fault, 16);
     auto reducer = [&](int i) {                          // of iteration i - 1, riding in launch i (i = iters: the closing launch)
         RingParams rp = ring_params(c, ring, i, i > 0 ? pl.ns[i - 1] : 0, loop_slot(ring.slots, i, 0));
-        if (i > 0) { rp.stats = c->stats.as<icp_iter_stats>() + (i - 1); rp.cv = converge_params(c, r, i - 1, CVG_MERGED_WORDS); }
-        if (i == iters) rp.final_out = (PoseState*)(c->stats.as<char>() + stats_pad);
+        if (i > 0) { rp.stats = c->stats.as<icp_iter_stats>() + (i - 1); rp.cv = converge_params(c, r, i - 1, tail->merged_cvg); }
+        if (i == iters) rp.final_out = &tail->final_pose;
         return rp;
     };
     HIPCK(c, hipEventRecord(c->events[0], c->stream));
@@ -316,7 +341,7 @@ int enqueue_merged(icp_ctx* c, LoopRun& r) {
     if (r.sampled[iters - 1]) { r.ev[iters - 1].end = loop_event(c, iters - 1, 3); HIPCK(c, hipEventRecord(r.ev[iters - 1].end, c->stream)); }
     HIPCK(c, hipEventRecord(c->events[1], c->stream));
     r.n_enqueued = iters;
-    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_stats, c->stats.p, stats_pad + (r.cvg ? CVG_TRACE + (size_t)iters * sizeof(icp_convergence_step) : 192), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(r.host_records(c), c->stats.p, r.records_bytes() + RunTail::used_bytes(r.cvg, iters), hipMemcpyDeviceToHost, c->stream));
     return ICP_OK;
 }
 
@@ -330,18 +355,17 @@ int enqueue_separate(icp_ctx* c, LoopRun& r) {
     const icp_params& p = c->prm; const RunPlan& pl = r.pl;
     const int iters = pl.iters(); int rc;
     if ((rc = rearm_handover(c))) return rc;
-    const size_t stats_pad = r.pin_pose - r.pin_stats;
+    RunTail* tail = r.dev_tail(c); RunTail* htail = r.host_tail(c);
     if (r.cvg) {
-        hipLaunchKernelGGL(k_converge_init, dim3(1), dim3(64), 0, c->stream, c->ps.as<PoseState>(), (int*)(c->stats.as<char>() + stats_pad + CVG_STATE));
+        hipLaunchKernelGGL(k_converge_init, dim3(1), dim3(64), 0, c->stream, c->ps.as<PoseState>(), tail->cvg_state);
         HIPCK(c, hipGetLastError());
     }
     HIPCK(c, hipEventRecord(c->events[0], c->stream));
     int n_enq = 0;
     for (int i = 0; i < iters; i++) {
         if (r.cvg && i > 0 && i % CONVERGE_CHUNK == 0) {      // between two chunks: has the run stopped?
-            const size_t at = stats_pad + CVG_STATE + CONV_STOPPED * 4;
-            const int* stop = (const int*)((char*)c->pinned + r.pin_stats + at);
-            HIPCK(c, hipMemcpyAsync((void*)stop, c->stats.as<char>() + at, 4, hipMemcpyDeviceToHost, c->stream));
+            const int* stop = &htail->cvg_state[CONV_STOPPED];
+            HIPCK(c, hipMemcpyAsync((void*)stop, &tail->cvg_state[CONV_STOPPED], 4, hipMemcpyDeviceToHost, c->stream));
             HIPCK(c, hipStreamSynchronize(c->stream));
             if (*stop) break;
         }
@@ -368,17 +392,17 @@ int enqueue_separate(icp_ctx* c, LoopRun& r) {
         if (r.rmse && (rc = enqueue_rmse(c, &d_st->rmse))) return rc;
         if (r.fontana && (rc = enqueue_fontana(c, &d_st->benchmark_error))) return rc;
         if (r.cvg) {
-            hipLaunchKernelGGL(k_converge_step, dim3(1), dim3(64), 0, c->stream, converge_params(c, r, i, CVG_STATE), c->ps.as<PoseState>(), pl.ns[i] > 0 ? d_st : nullptr);
+            hipLaunchKernelGGL(k_converge_step, dim3(1), dim3(64), 0, c->stream, converge_params(c, r, i, tail->cvg_state), c->ps.as<PoseState>(), pl.ns[i] > 0 ? d_st : nullptr);
             HIPCK(c, hipGetLastError());
         }
         if (ev) HIPCK(c, hipEventRecord(r.ev[i].end, c->stream));
     }
     r.n_enqueued = n_enq;
     HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_stats, c->stats.p, (size_t)n_enq * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_pose, c->ps.p, sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));
-    if (r.cvg) HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_pose + CVG_STATE, c->stats.as<char>() + stats_pad + CVG_STATE, CVG_TRACE - CVG_STATE + (size_t)n_enq * sizeof(icp_convergence_step), hipMemcpyDeviceToHost, c->stream));
-    if (r.lm) HIPCK(c, hipMemcpyAsync((char*)c->pinned + r.pin_lm, c->lm_sums.p, (size_t)n_enq * sizeof(icp_lm_summary), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(r.host_records(c), c->stats.p, (size_t)n_enq * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(&htail->final_pose, c->ps.p, sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));
+    if (r.cvg) HIPCK(c, hipMemcpyAsync(htail->cvg_state, tail->cvg_state, RunTail::used_bytes(true, n_enq) - offsetof(RunTail, cvg_state), hipMemcpyDeviceToHost, c->stream));      // the state block and the trace behind it
+    if (r.lm) HIPCK(c, hipMemcpyAsync(r.host_lm(c), c->lm_sums.p, (size_t)n_enq * sizeof(icp_lm_summary), hipMemcpyDeviceToHost, c->stream));
     return ICP_OK;
 }
 
@@ -407,13 +431,12 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     if (iters == 0) return guard.done();
     if (robust && (rc = robust_prepare(c, iters))) return rc;
     if (recip && (rc = reciprocal_prepare(c, iters))) return rc;
-    const size_t cvg_bytes = cvg ? ((size_t)iters * sizeof(icp_convergence_step) + 255) & ~(size_t)255 : 0;
-    r.pin_pose = r.pin_stats + (((size_t)iters * sizeof(icp_iter_stats) + 255) & ~(size_t)255); r.pin_lm = r.pin_pose + 512 + cvg_bytes;
-    if ((rc = ensure_pinned(c, lm ? r.pin_lm + (size_t)iters * sizeof(icp_lm_summary) : r.pin_lm))) return rc;
+    r.lay_out(iters, lm, cvg);
+    if ((rc = ensure_pinned(c, r.pin_bytes))) return rc;
     if (lm && (rc = ensure(c, c->lm_sums, (size_t)iters * sizeof(icp_lm_summary)))) return rc;
     float pose_in[16]; memcpy(pose_in, pose_inout, 64);        // the record of an empty iteration 0 carries the incoming pose
     if ((rc = write_pose(c, pose_inout))) return rc;
-    if ((rc = ensure(c, c->stats, r.pin_pose - r.pin_stats + (cvg ? CVG_TRACE + cvg_bytes : 192)))) return rc;
+    if ((rc = ensure(c, c->stats, r.stats_bytes))) return rc;
     r.eligible.assign((size_t)iters, 0);
     for (int i = 0; i < iters; i++) r.eligible[(size_t)i] = pl.factors[i] == pl.factors[iters - 1] && (i == 0 || pl.factors[i] == pl.factors[i - 1]);
     if ((rc = ensure_events(c, (size_t)iters * 4 + 2))) return rc;
@@ -434,10 +457,11 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     c->rcp_last.swap(rcp);
     for (int i = 0; robust && i < iters; i++) if (pl.ns[i] <= 0) rob[(size_t)i] = icp_robust_stats{0, 0, -1.f, -1.f};      // (no work: nothing was written)
     c->rob_last.swap(rob);
-    const PoseState* hp = (const PoseState*)((char*)c->pinned + r.pin_pose);
+    RunTail* htail = r.host_tail(c);
+    const PoseState* hp = &htail->final_pose;
     if (merged) {
         c->merged_runs++;
-        const int rf = *(const int*)((char*)c->pinned + r.pin_pose + 128);
+        const int rf = htail->merged_fault;
         if ((hp->fault && hp->fault != SLOT_STOPPED) || rf) {      // (a stopped slot is the run's result, not a fault)
             // the 6 x 6 system failed the rank guard (the eigen-decomposition lives in k_reduce_solve only), or a bounded wait ran out:
             // the same run again, from the incoming pose, in the separate form
@@ -450,7 +474,7 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     }
     int n_done = iters; bool stopped = false;
     if (cvg) {
-        const int* cw = (const int*)((char*)c->pinned + r.pin_pose + (merged ? CVG_MERGED_WORDS : CVG_STATE));
+        const int* cw = merged ? htail->merged_cvg : htail->cvg_state;
         if (cw[CONV_STOPPED]) {
             stopped = true; n_done = cw[CONV_RUN];
             if (n_done < 1 || n_done > r.n_enqueued) { c->err = "the device reports a stop outside the iterations that were enqueued"; return ICP_ERR_HIP; }
@@ -461,17 +485,17 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     if (!merged && hp->fault) { c->err = "reduction hand-over timed out on the device (k_reduce_solve)"; return ICP_ERR_HIP; }
     if (lm) {
         c->lm_last.resize((size_t)n_done);
-        memcpy(c->lm_last.data(), (char*)c->pinned + r.pin_lm, (size_t)n_done * sizeof(icp_lm_summary));
+        memcpy(c->lm_last.data(), r.host_lm(c), (size_t)n_done * sizeof(icp_lm_summary));
         for (int i = 0; i < n_done; i++)
             if (pl.ns[i] <= 0) { memset(&c->lm_last[(size_t)i], 0, sizeof(icp_lm_summary)); c->lm_last[(size_t)i].termination = ICP_LM_NO_RESIDUALS; }
     }
     if (robust) c->rob_last.resize((size_t)n_done);
     if (recip) c->rcp_last.resize((size_t)n_done);
-    const int status = finish_records(pl, n_done, (icp_iter_stats*)((char*)c->pinned + r.pin_stats), pose_in, rmse, fontana, stats, max_stats);
+    const int status = finish_records(pl, n_done, r.host_records(c), pose_in, rmse, fontana, stats, max_stats);
     if (n_run) *n_run = n_done;
     if (!single) { c->cvg_last.converged = stopped; c->cvg_last.iterations_run = n_done; }
     if (cvg) {
-        const icp_convergence_step* tr = (const icp_convergence_step*)((char*)c->pinned + r.pin_pose + CVG_TRACE);
+        const icp_convergence_step* tr = htail->trace();
         c->cvg_trace.assign(tr, tr + n_done);
         c->cvg_last.rotation = tr[n_done - 1].rotation; c->cvg_last.translation = tr[n_done - 1].translation;
     }

@@ -51,7 +51,7 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
     // page-locked staging: [pose states up | records down | results down]
     const size_t pin_rec = (Kz * sizeof(PoseState) + 255) & ~(size_t)255, pin_res = pin_rec + ((Kz * (size_t)ms.stats * sizeof(icp_iter_stats) + 255) & ~(size_t)255);
     if ((rc = ensure_pinned(c, pin_res + Kz * sizeof(icp_start_result)))) return rc;
-    PoseState* hps = (PoseState*)c->pinned;
+    PoseState* hps = c->pinned.as<PoseState>();
     for (int s = 0; s < K; s++) {
         memset(&hps[s], 0, sizeof(PoseState)); memcpy(hps[s].pose, initial_poses + (size_t)16 * s, 64); normal_matrix_from_pose(hps[s].pose, hps[s].nmat);
     }
@@ -112,8 +112,8 @@ int icp_run_multistart(icp_ctx* c, const float* initial_poses, int32_t n_starts,
         hipLaunchKernelGGL(k_score_fold, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, c->stream, c->ms_score.as<double>(), MSCORE_BLOCKS, d_ps, K, c->ms_res.as<icp_start_result>());
         HIPCK(c, hipGetLastError());
     }
-    icp_iter_stats* hrec = (icp_iter_stats*)((char*)c->pinned + pin_rec);
-    icp_start_result* hres = (icp_start_result*)((char*)c->pinned + pin_res);
+    icp_iter_stats* hrec = (icp_iter_stats*)(c->pinned.as<char>() + pin_rec);
+    icp_start_result* hres = (icp_start_result*)(c->pinned.as<char>() + pin_res);
     if (iters > 0) HIPCK(c, hipMemcpyAsync(hrec, c->ms_stats.p, Kz * (size_t)ms.stats * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(hres, c->ms_res.p, Kz * sizeof(icp_start_result), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(hps, d_ps, Kz * sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));     // (the fault words)

@@ -62,16 +62,6 @@ int tsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pos
     HIPCK(c, hipGetLastError());
     return ICP_OK;
 }
-// One 4-byte count back to the host through the page-locked block; waits for the stream.
-int tsdf_read_count(icp_ctx* c, const void* d_count, int* out) {
-    int rc;
-    if ((rc = ensure_pinned(c, 4096))) return rc;
-    int* h = (int*)((char*)c->pinned + 2048);            // (the first bytes of the pinned block stage the pose)
-    HIPCK(c, hipMemcpyAsync(h, d_count, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    *out = *h;
-    return ICP_OK;
-}
 // The model as target, from the arguments already checked: the ray-cast into the target's planes, the hit count, finish_target.
 // *hits_out = 0 with ICP_ERR_NO_TARGET leaves an empty target.
 int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], int* hits_out, const char* who) {
@@ -85,7 +75,7 @@ int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16
     o.x = tg.x.as<float>(); o.y = tg.y.as<float>(); o.z = tg.z.as<float>(); o.nx = tg.nx.as<float>(); o.ny = tg.ny.as<float>(); o.nz = tg.nz.as<float>(); o.npad = npad;
     if ((rc = tsdf_raycast_launch(c, cam, pose, true, o))) return rc;
     int hits = 0;
-    if ((rc = tsdf_read_count(c, c->tsdf_cnt.p, &hits))) return rc;
+    if ((rc = read_count(c, c->tsdf_cnt.p, &hits))) return rc;
     tg.has_normals = true; tg.has_colors = false;
     if (hits <= 0) {
         tg.n = 0; tg.npad = 0; c->bvh.valid = false; c->bvh6.valid = false;
@@ -195,7 +185,7 @@ int icp_tsdf_integrate(icp_ctx* c, const float* depth, const icp_depth_camera* c
     if ((rc = stage_depth(c, 0, depth, nullptr, cam->width * cam->height, c->stream))) return rc;
     if ((rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>()))) return rc;
     int n = 0;
-    if ((rc = tsdf_read_count(c, c->tsdf_cnt.p, &n))) return rc;
+    if ((rc = read_count(c, c->tsdf_cnt.p, &n))) return rc;
     if (n_updated_out) *n_updated_out = n;
     return guard.done();
 }
@@ -218,7 +208,7 @@ int icp_tsdf_raycast(icp_ctx* c, const icp_depth_camera* cam, const float pose[1
     if (vertices_out) HIPCK(c, hipMemcpyAsync(vertices_out, o.vert, n * 12, hipMemcpyDeviceToHost, c->stream));
     if (normals_out) HIPCK(c, hipMemcpyAsync(normals_out, o.nrm, n * 12, hipMemcpyDeviceToHost, c->stream));
     int hits = 0;
-    if ((rc = tsdf_read_count(c, c->tsdf_cnt.p, &hits))) return rc;
+    if ((rc = read_count(c, c->tsdf_cnt.p, &hits))) return rc;
     if (n_hits_out) *n_hits_out = hits;
     return guard.done();
 }
@@ -257,15 +247,12 @@ int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frame
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     const int n = cam->width * cam->height;
-    if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream, hipStreamNonBlocking));
+    if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     // frame 0 into the model at the incoming pose; frame 1 goes up meanwhile
     if ((rc = stage_depth(c, 0, depth_frames, nullptr, n, c->stream))) return rc;
     if ((rc = tsdf_integrate_slot(c, 0, *cam, pose_inout, nullptr))) return rc;
     if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, nullptr, n, c->depth_stream))) return rc;
-    if (gt_frames && n_frames > 1) {
-        if ((rc = ensure(c, c->track_rmse, (size_t)(n_frames - 1) * 8))) return rc;
-        if (!c->pin_track) HIPCK(c, hipHostMalloc((void**)&c->pin_track, 2 * sizeof(PoseState), hipHostMallocDefault));
-    }
+    if (gt_frames && n_frames > 1 && (rc = track_rmse_prepare(c, n_frames))) return rc;
     static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     int first_err = ICP_OK;
     auto fail = [&](icp_track_frame& r, int status, const char* why) {
@@ -298,14 +285,8 @@ int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frame
                 for (int cc = 0; cc < 3; cc++) G.m[cc * 4 + rr] = (float)((Ri[rr * 3] * g[cc * 4] + Ri[rr * 3 + 1] * g[cc * 4 + 1]) + Ri[rr * 3 + 2] * g[cc * 4 + 2]);
                 G.m[12 + rr] = (float)(((Ri[rr * 3] * g[12] + Ri[rr * 3 + 1] * g[13]) + Ri[rr * 3 + 2] * g[14]) + ti[rr]);
             }
-            for (DevBuf* pl : {&c->conv_src.x, &c->conv_src.y, &c->conv_src.z, &c->conv_ref.x, &c->conv_ref.y, &c->conv_ref.z}) if ((rc = ensure(c, *pl, (size_t)kept * 4))) return rc;
-            hipLaunchKernelGGL(k_conv_from_source, dim3((kept + 255) / 256), dim3(256), 0, c->stream, c->src.x.as<float>(), c->src.y.as<float>(), c->src.z.as<float>(), kept, G,
-                               c->conv_src.x.as<float>(), c->conv_src.y.as<float>(), c->conv_src.z.as<float>(), c->conv_ref.x.as<float>(), c->conv_ref.y.as<float>(), c->conv_ref.z.as<float>());
-            HIPCK(c, hipGetLastError());
-            c->conv_n = kept;
-            // (pin_track[0] / [1]: rewritten only by the next frame, after set_target_tsdf has synchronised the stream)
-            if ((rc = write_pose_via(c, &c->pin_track[0], identity))) return rc;
-            if ((rc = enqueue_rmse(c, d_rmse))) return rc;
+            if ((rc = track_reference(c, kept, G))) return rc;
+            if ((rc = track_rmse_at(c, 0, identity, d_rmse))) return rc;
         }
         float dT[16]; memcpy(dT, identity, 64);
         int32_t iters = 0;
@@ -313,10 +294,7 @@ int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frame
         if (rc == ICP_ERR_HIP) return rc;
         r.iterations = iters; r.status = rc;
         if (rc != ICP_OK && first_err == ICP_OK) first_err = rc;      // (the message is run_loop's)
-        if (gt_frames) {
-            if ((rc = write_pose_via(c, &c->pin_track[1], dT))) return rc;
-            if ((rc = enqueue_rmse(c, d_rmse + 1))) return rc;
-        }
+        if (gt_frames && (rc = track_rmse_at(c, 1, dT, d_rmse + 1))) return rc;
         if (r.status == ICP_OK) {
             compose_pose(pose_inout, dT);
             if ((rc = tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr))) return rc;
@@ -325,11 +303,7 @@ int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frame
     }
     HIPCK(c, hipStreamSynchronize(c->stream));
     HIPCK(c, hipStreamSynchronize(c->depth_stream));
-    if (gt_frames && n_frames > 1) {
-        std::vector<float> h((size_t)(n_frames - 1) * 2);
-        HIPCK(c, hipMemcpy(h.data(), c->track_rmse.p, h.size() * 4, hipMemcpyDeviceToHost));
-        for (int k = 1; k < n_frames; k++) if (out[k - 1].n_src > 0 && out[k - 1].status != ICP_ERR_NO_TARGET) { out[k - 1].initial_rmse = h[(size_t)(k - 1) * 2]; out[k - 1].final_rmse = h[(size_t)(k - 1) * 2 + 1]; }
-    }
+    if (gt_frames && n_frames > 1 && (rc = track_rmse_finish(c, n_frames, out, [](const icp_track_frame& r) { return r.n_src > 0 && r.status != ICP_ERR_NO_TARGET; }))) return rc;
     guard.ok = true;
     return first_err;
 }

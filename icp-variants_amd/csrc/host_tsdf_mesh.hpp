@@ -53,16 +53,6 @@ int tm_enqueue_fill(icp_ctx* c, const TmGrid& g, const TmScratch& s, float* d_ve
     HIPCK(c, hipGetLastError());
     return ICP_OK;
 }
-// Both totals back to the host through the page-locked block in one copy; waits for the stream.
-int tm_read_counts(icp_ctx* c, const TmScratch& s, int* nv, int* nt) {
-    int rc;
-    if ((rc = ensure_pinned(c, 4096))) return rc;
-    int* h = (int*)((char*)c->pinned + 2048);            // (the first bytes of the pinned block stage the pose)
-    HIPCK(c, hipMemcpyAsync(h, s.tot, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    *nv = h[0]; *nt = h[1];
-    return ICP_OK;
-}
 int tm_check_call(icp_ctx* c, float min_weight, const char* who) {
     if (!c->tsdf_on) { c->err = std::string(who) + ": no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
     if (!(std::isfinite(min_weight) && min_weight >= 0.f)) { c->err = std::string(who) + ": min_weight must be finite and >= 0"; return ICP_ERR_INVALID_ARG; }
@@ -87,8 +77,9 @@ int icp_tsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t ma
     TmScratch s;
     if ((rc = tm_scratch(c, g, s))) return rc;
     if ((rc = tm_enqueue_count(c, g, s, min_weight))) return rc;
-    int nv = 0, nt = 0;
-    if ((rc = tm_read_counts(c, s, &nv, &nt))) return rc;
+    int tot[2] = {0, 0};                                 // both totals back in one copy
+    if ((rc = read_count(c, s.tot, tot, 2))) return rc;
+    const int nv = tot[0], nt = tot[1];
     if (nv < 0 || nt < 0) { c->err = "icp_tsdf_mesh: count out of range"; return ICP_ERR_HIP; }
     *n_vertices_out = nv; *n_triangles_out = nt;
     if (count_only) return guard.done();
@@ -125,8 +116,9 @@ extern "C" int icp_debug_tsdf_mesh_time(icp_ctx* c, float min_weight, float* ms_
     TmScratch s;
     if ((rc = tm_scratch(c, g, s))) return rc;
     if ((rc = tm_enqueue_count(c, g, s, min_weight))) return rc;
-    int nv = 0, nt = 0;
-    if ((rc = tm_read_counts(c, s, &nv, &nt))) return rc;
+    int tot[2] = {0, 0};                                 // both totals back in one copy
+    if ((rc = read_count(c, s.tot, tot, 2))) return rc;
+    const int nv = tot[0], nt = tot[1];
     const size_t bv = (size_t)nv * 12, bt = (size_t)nt * 12;
     if ((rc = ensure(c, c->tm_out, 2 * bv + bt))) return rc;
     char* d = c->tm_out.as<char>();

@@ -18,6 +18,8 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 #include <map>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 // The host side in pieces, in dependency order (as icp_device.hpp includes dev_*.hpp): ONE translation unit, the device code compiled once.
@@ -65,11 +67,8 @@ int icp_ctx_create_on_stream(int device, void* hip_stream, icp_ctx** out) {
     { const char* e = getenv("ICP_HIP_MERGE"); if (e && e[0] == '0') c->merge_loop = false; }
     { const char* e = getenv("ICP_HIP_TRACE"); if (e && e[0] == '1') c->trace = true; }
     { const char* e = getenv("ICP_HIP_STAGE_EVENTS"); if (e && e[0] >= '0' && e[0] <= '9') c->stage_timing = atoi(e); }
-    if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->owns_stream = false; }
-    else {
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return ICP_ERR_HIP; }
-        c->owns_stream = true;
-    }
+    if (!hip_stream && hipStreamCreateWithFlags(&c->own_stream.s, hipStreamNonBlocking) != hipSuccess) { delete c; return ICP_ERR_HIP; }
+    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream.s;
     c->cos_reject = compute_cos_reject();
     float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     int rc = write_pose(c, ident);
@@ -84,44 +83,8 @@ int icp_ctx_destroy(icp_ctx* c) {
     if (!c) return ICP_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    release(c->tgt); release(c->src); release(c->qry); release(c->conv_src); release(c->conv_ref);
-    release(c->nrm_cloud);
-    for (Bvh* b : {&c->bvh, &c->bvh6, &c->nrm_bvh, &c->src_bvh}) release(*b);      // every buffer of a tree, pos_of included
-    release(c->okeys); release(c->okeys2); release(c->ovals); release(c->otemp);
-    release(c->src_rflag); release(c->src_finite); release(c->rcp_stats);
-    for (DevBuf& d : c->rcp_q) release(d);
-    release(c->rcp_nn);
-    for (auto& kv : c->levels) release(kv.second);
-    drop_nss(c, false);
-    for (DevBuf* d : {&c->nss_bkt, &c->nss_table, &c->nss_quota, &c->nss_thr, &c->nss_state, &c->nss_hist, &c->nss_total}) release(*d);
-    release(c->ps); release(c->matches); release(c->d2); release(c->best64); release(c->nn_raw); release(c->qstate); release(c->qstate2); release(c->qpack); release(c->sel_lists); release(c->sel_counts); release(c->sel_blocks); release(c->partials); release(c->partials2); release(c->ring); release(c->totals); release(c->dbg_steps); release(c->sums);
-    release(c->lm_state); release(c->lm_partials); release(c->lm_sums);
-    for (auto& pl : c->gicp_n) for (DevBuf& d : pl) release(d);
-    for (DevBuf& d : c->col_grad) release(d);
-    release(c->gicp_flag);
-    for (FpfhCache& f : c->fpfh) for (DevBuf* d : {&f.nb_idx, &f.nb_d2, &f.counts, &f.pairs, &f.feat}) release(*d);
-    for (DevBuf* d : {&c->gm_best[0], &c->gm_best[1], &c->gm_fwd, &c->gm_keep, &c->gm_list, &c->gm_idx, &c->gm_pts, &c->gm_hyp}) release(*d);
-    release(c->rob_keys); release(c->rob_state); release(c->rob_stats);
-    for (DevBuf* d : {&c->ms_ps, &c->ms_nn, &c->ms_st, &c->ms_st2, &c->ms_rec, &c->ms_d2, &c->ms_partials, &c->ms_totals, &c->ms_stats, &c->ms_score, &c->ms_res}) release(*d);
-    release(c->stats); release(c->staging); release(c->rmse_partials); release(c->rmse_out); release(c->fontana_partials);
-    for (DevBuf* d : {&c->src_flag, &c->src_box, &c->tgt_flag, &c->tgt_finite, &c->nrm_finite, &c->sel_temp, &c->d_count}) release(*d);
-    if (c->depth_stream) { (void)hipStreamSynchronize(c->depth_stream); (void)hipStreamDestroy(c->depth_stream); }
-    for (int k = 0; k < 2; k++) {
-        release(c->depth_dev[k]);
-        if (c->depth_pin[k]) (void)hipHostFree(c->depth_pin[k]);
-        if (c->depth_up[k]) (void)hipEventDestroy(c->depth_up[k]);
-    }
-    release(c->depth_blocks); release(c->track_rmse);
-    release(c->tsdf_vox); release(c->tsdf_cnt);
-    for (DevBuf* d : {&c->tm_bits, &c->tm_mask, &c->tm_base, &c->tm_blk, &c->tm_out}) release(*d);
-    if (c->pin_track) (void)hipHostFree(c->pin_track);
-    if (c->pin_up) (void)hipHostFree(c->pin_up);
-    if (c->up_ev) (void)hipEventDestroy(c->up_ev);
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->build_ev) if (e) (void)hipEventDestroy(e);
-    if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c->depth_stream) (void)hipStreamSynchronize(c->depth_stream);
+    delete c;                            // every buffer, page-locked block and event frees itself, the owned streams last (host_ctx.hpp)
     return ICP_OK;
 }
 
