@@ -148,6 +148,7 @@ struct icp_ctx {
     DevBuf depth_blocks, track_rmse;     // block counts / offsets of the depth compaction; per-frame initial + final RMSE of a tracked sequence
     PinBuf pin_track;                    // page-locked pose staging of a tracked frame's initial / final RMSE: two slots of its own, apart from `pinned`
     DevBuf tsdf_vox, tsdf_cnt; bool tsdf_on = false; icp_tsdf_options tsdf_opt;   // the TSDF volume of frame-to-model tracking (host_tsdf.hpp): (tsdf, weight) per voxel, the update / hit counter, its options (ray_step resolved)
+    DevBuf tsdf_col; bool tsdf_col_on = false;   // its optional colour array (icp_tsdf_color_create): one float4 (R, G, B, Wc) per voxel, 16 bytes, the indexing of tsdf_vox
     DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
     float cos_reject = 0.5f;
     std::vector<Event> events;

@@ -1,5 +1,7 @@
 // host_tsdf.hpp -- frame-to-model tracking: the context's TSDF volume (icp_tsdf_*), the model as target (icp_set_target_tsdf) and the tracking
-// loop over it (icp_track_depth_model).  Kernels: dev_tsdf.hpp; contract: include/icp_hip.h, DESIGN.md section 6m.
+// loop over it (icp_track_depth_model); the volume's optional colour array and the coloured forms of all three (icp_tsdf_color_*,
+// icp_tsdf_integrate_color, icp_tsdf_raycast_color, icp_set_target_tsdf_color, icp_track_depth_model_color).  Kernels: dev_tsdf.hpp;
+// contract: include/icp_hip.h, DESIGN.md sections 6m and 6p.
 // Part of icp_hip.hip (included from there, after host_depth.hpp).
 namespace {
 const char* tsdf_options_error(const icp_tsdf_options* o) {
@@ -26,6 +28,11 @@ int tsdf_check_call(icp_ctx* c, const icp_depth_camera* cam, const float* pose, 
     if (!is_identity16(cam->extrinsics)) { c->err = std::string(who) + ": the depth extrinsics must be the identity"; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;
 }
+int tsdf_check_color(icp_ctx* c, const char* who) {
+    if (!c->tsdf_on) { c->err = std::string(who) + ": no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    if (!c->tsdf_col_on) { c->err = std::string(who) + ": the volume has no colour array (icp_tsdf_color_create)"; return ICP_ERR_INVALID_ARG; }
+    return ICP_OK;
+}
 size_t tsdf_voxels(const icp_ctx* c) { return (size_t)c->tsdf_opt.dims[0] * c->tsdf_opt.dims[1] * c->tsdf_opt.dims[2]; }
 TsdfVol tsdf_view(const icp_ctx* c) {
     const icp_tsdf_options& o = c->tsdf_opt;
@@ -38,54 +45,64 @@ TsdfVol tsdf_view(const icp_ctx* c) {
 TsdfCam tsdf_cam(const icp_depth_camera& cam) { TsdfCam t; t.width = cam.width; t.height = cam.height; t.fx = cam.fx; t.fy = cam.fy; t.cx = cam.cx; t.cy = cam.cy; return t; }
 
 // The frame in upload slot `slot` fused into the volume at `pose`, enqueued on the context's stream; d_count (optional): zeroed, then the
-// number of voxels written.
-int tsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count) {
+// number of voxels written.  color: the slot's colour frame goes into the colour array as well (d_count[1]: the voxels coloured).
+int tsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count, bool color = false) {
     TsdfMat m; memset(&m, 0, sizeof(m));
     invert_extrinsics(pose, m.m);                    // the affine inverse in fp64, rounded once: 3x3 row-major, then t
     const TsdfVol v = tsdf_view(c);
     HIPCK(c, hipStreamWaitEvent(c->stream, c->depth_up[slot], 0));
-    if (d_count) HIPCK(c, hipMemsetAsync(d_count, 0, 4, c->stream));
+    if (d_count) HIPCK(c, hipMemsetAsync(d_count, 0, color ? 8 : 4, c->stream));
     const dim3 grid((v.nx + 63) / 64, (v.ny + 3) / 4, (v.nz + TSDF_KCHUNK - 1) / TSDF_KCHUNK);
-    hipLaunchKernelGGL(k_tsdf_integrate, grid, dim3(64, 4), 0, c->stream, v, tsdf_cam(cam), m, (const float*)c->depth_dev[slot].as<float>(), d_count);
+    const float* depth = c->depth_dev[slot].as<float>();
+    if (color) hipLaunchKernelGGL(k_tsdf_integrate_color, grid, dim3(64, 4), 0, c->stream, v, tsdf_cam(cam), m, depth, d_count,
+                                  (const uint32_t*)(depth + (size_t)cam.width * cam.height), c->tsdf_col.as<float4>(), d_count ? d_count + 1 : nullptr);
+    else hipLaunchKernelGGL(k_tsdf_integrate, grid, dim3(64, 4), 0, c->stream, v, tsdf_cam(cam), m, depth, d_count);
     HIPCK(c, hipGetLastError());
     return ICP_OK;
 }
-// The ray-cast from `pose`, enqueued; the hit count lands in tsdf_cnt (zeroed first).
-int tsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], bool soa, const TsdfRayOut& o) {
+// The ray-cast from `pose`, enqueued; the hit count lands in tsdf_cnt (zeroed first).  co: with colours, the coloured hits in tsdf_cnt[1].
+int tsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], bool soa, const TsdfRayOut& o, const TsdfColorOut* co = nullptr) {
     int rc;
     if ((rc = ensure(c, c->tsdf_cnt, 16))) return rc;
     TsdfMat m; memcpy(m.m, pose, 64);
-    HIPCK(c, hipMemsetAsync(c->tsdf_cnt.p, 0, 4, c->stream));
+    HIPCK(c, hipMemsetAsync(c->tsdf_cnt.p, 0, co ? 8 : 4, c->stream));
     const dim3 grid((cam.width + 15) / 16, (cam.height + 15) / 16);
-    if (soa) hipLaunchKernelGGL(k_tsdf_raycast<true>, grid, dim3(256), 0, c->stream, tsdf_view(c), tsdf_cam(cam), m, o, c->tsdf_cnt.as<int>());
+    int* cnt = c->tsdf_cnt.as<int>();
+    const float4* col = c->tsdf_col.as<float4>();
+    if (co && soa) hipLaunchKernelGGL(k_tsdf_raycast_color<true>, grid, dim3(256), 0, c->stream, tsdf_view(c), tsdf_cam(cam), m, o, cnt, col, *co, cnt + 1);
+    else if (co) hipLaunchKernelGGL(k_tsdf_raycast_color<false>, grid, dim3(256), 0, c->stream, tsdf_view(c), tsdf_cam(cam), m, o, cnt, col, *co, cnt + 1);
+    else if (soa) hipLaunchKernelGGL(k_tsdf_raycast<true>, grid, dim3(256), 0, c->stream, tsdf_view(c), tsdf_cam(cam), m, o, c->tsdf_cnt.as<int>());
     else hipLaunchKernelGGL(k_tsdf_raycast<false>, grid, dim3(256), 0, c->stream, tsdf_view(c), tsdf_cam(cam), m, o, c->tsdf_cnt.as<int>());
     HIPCK(c, hipGetLastError());
     return ICP_OK;
 }
 // The model as target, from the arguments already checked: the ray-cast into the target's planes, the hit count, finish_target.
-// *hits_out = 0 with ICP_ERR_NO_TARGET leaves an empty target.
-int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], int* hits_out, const char* who) {
+// *hits_out = 0 with ICP_ERR_NO_TARGET leaves an empty target.  color: the coloured ray-cast, colours into the target's colour planes;
+// a hit without colour is a hole and *hits_out counts the coloured hits.
+int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], int* hits_out, const char* who, bool color = false) {
     int rc;
     Cloud& tg = c->tgt;
     const int n = cam.width * cam.height, npad = (n + 63) / 64 * 64;
     *hits_out = 0;
     for (DevBuf* pl : {&tg.x, &tg.y, &tg.z, &tg.nx, &tg.ny, &tg.nz}) if ((rc = ensure(c, *pl, (size_t)npad * 4))) return rc;
-    for (DevBuf* pl : {&tg.rgba, &tg.cr, &tg.cg, &tg.cb}) release(*pl);
+    if (color) { for (DevBuf* pl : {&tg.rgba, &tg.cr, &tg.cg, &tg.cb}) if ((rc = ensure(c, *pl, (size_t)npad * 4))) return rc; }
+    else for (DevBuf* pl : {&tg.rgba, &tg.cr, &tg.cg, &tg.cb}) release(*pl);
     TsdfRayOut o; memset(&o, 0, sizeof(o));
     o.x = tg.x.as<float>(); o.y = tg.y.as<float>(); o.z = tg.z.as<float>(); o.nx = tg.nx.as<float>(); o.ny = tg.ny.as<float>(); o.nz = tg.nz.as<float>(); o.npad = npad;
-    if ((rc = tsdf_raycast_launch(c, cam, pose, true, o))) return rc;
+    const TsdfColorOut co = {tg.rgba.as<uint32_t>(), tg.cr.as<float>(), tg.cg.as<float>(), tg.cb.as<float>()};
+    if ((rc = tsdf_raycast_launch(c, cam, pose, true, o, color ? &co : nullptr))) return rc;
     int hits = 0;
-    if ((rc = read_count(c, c->tsdf_cnt.p, &hits))) return rc;
-    tg.has_normals = true; tg.has_colors = false;
+    if ((rc = read_count(c, c->tsdf_cnt.p, &hits))) return rc;      // (the coloured target's holes are its uncoloured hits: both counts agree)
+    tg.has_normals = true; tg.has_colors = color;
     if (hits <= 0) {
         tg.n = 0; tg.npad = 0; c->bvh.valid = false; c->bvh6.valid = false;
         c->gicp_ready[0] = false; c->col_ready = false; c->fpfh[0].ready = false;
-        c->err = std::string(who) + ": the ray-cast of the model hits nothing";
+        c->err = std::string(who) + (color ? ": the ray-cast of the model hits nothing that has a colour" : ": the ray-cast of the model hits nothing");
         return ICP_ERR_NO_TARGET;
     }
     tg.n = n; tg.npad = npad;
     *hits_out = hits;
-    return finish_target(c, false);
+    return finish_target(c, color);
 }
 // pose <- pose dT: the fp64 product of the two column-major 4x4, rounded once.
 void compose_pose(float pose[16], const float dT[16]) {
@@ -112,6 +129,7 @@ int icp_tsdf_reset(icp_ctx* c) {
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     HIPCK(c, hipMemsetAsync(c->tsdf_vox.p, 0, tsdf_voxels(c) * 8, c->stream));      // tsdf 0, weight 0
+    if (c->tsdf_col_on) HIPCK(c, hipMemsetAsync(c->tsdf_col.p, 0, tsdf_voxels(c) * 16, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return guard.done();
 }
@@ -122,6 +140,7 @@ int icp_tsdf_release(icp_ctx* c) {
     if ((rc = set_device(c))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
     release(c->tsdf_vox);
+    release(c->tsdf_col); c->tsdf_col_on = false;
     for (DevBuf* d : {&c->tm_bits, &c->tm_mask, &c->tm_base, &c->tm_blk, &c->tm_out}) release(*d);      // the mesh extraction's scratch goes with the volume
     c->tsdf_on = false;
     return ICP_OK;
@@ -131,7 +150,7 @@ int icp_tsdf_create(icp_ctx* c, const icp_tsdf_options* opt) {
     if (const char* why = tsdf_options_error(opt)) { c->err = std::string("icp_tsdf_create: ") + why; return ICP_ERR_INVALID_ARG; }
     int rc;
     if ((rc = set_device(c))) return rc;
-    if (c->tsdf_on) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->tsdf_vox); c->tsdf_on = false; }
+    if (c->tsdf_on) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->tsdf_vox); release(c->tsdf_col); c->tsdf_col_on = false; c->tsdf_on = false; }
     c->tsdf_opt = *opt;
     if (c->tsdf_opt.ray_step == 0.f) c->tsdf_opt.ray_step = opt->truncation / 2.f;
     if ((rc = ensure(c, c->tsdf_vox, tsdf_voxels(c) * 8))) return rc;
@@ -174,6 +193,62 @@ int icp_tsdf_upload(icp_ctx* c, const float* tsdf, const float* weight) {
     return ICP_OK;
 }
 
+// ---- the colour array: one float4 (R, G, B, Wc) per voxel next to the geometry's float2
+int icp_tsdf_color_create(icp_ctx* c) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!c->tsdf_on) { c->err = "icp_tsdf_color_create: no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ensure(c, c->tsdf_col, tsdf_voxels(c) * 16))) return rc;
+    c->tsdf_col_on = true;
+    HIPCK(c, hipMemsetAsync(c->tsdf_col.p, 0, tsdf_voxels(c) * 16, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+int icp_tsdf_color_release(icp_ctx* c) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = tsdf_check_color(c, "icp_tsdf_color_release"))) return rc;
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    release(c->tsdf_col); c->tsdf_col_on = false;
+    return ICP_OK;
+}
+// The host arrays (rgb n x 3, weight n) and the interleaved device array, a slab of at most 1 Mi voxels at a time through a host block.
+int icp_tsdf_color_download(icp_ctx* c, float* rgb_out, float* weight_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = tsdf_check_color(c, "icp_tsdf_color_download"))) return rc;
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    const size_t n = tsdf_voxels(c), slab = (size_t)1 << 20;
+    std::vector<float> h(4 * (n < slab ? n : slab));
+    for (size_t at = 0; at < n; at += slab) {
+        const size_t m = n - at < slab ? n - at : slab;
+        HIPCK(c, hipMemcpy(h.data(), c->tsdf_col.as<float>() + 4 * at, m * 16, hipMemcpyDeviceToHost));
+        if (rgb_out) for (size_t i = 0; i < m; i++) for (int q = 0; q < 3; q++) rgb_out[3 * (at + i) + q] = h[4 * i + q];
+        if (weight_out) for (size_t i = 0; i < m; i++) weight_out[at + i] = h[4 * i + 3];
+    }
+    return ICP_OK;
+}
+int icp_tsdf_color_upload(icp_ctx* c, const float* rgb, const float* weight) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = tsdf_check_color(c, "icp_tsdf_color_upload"))) return rc;
+    if (!rgb || !weight) { c->err = "icp_tsdf_color_upload: null array"; return ICP_ERR_INVALID_ARG; }
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    const size_t n = tsdf_voxels(c), slab = (size_t)1 << 20;
+    std::vector<float> h(4 * (n < slab ? n : slab));
+    for (size_t at = 0; at < n; at += slab) {
+        const size_t m = n - at < slab ? n - at : slab;
+        for (size_t i = 0; i < m; i++) { for (int q = 0; q < 3; q++) h[4 * i + q] = rgb[3 * (at + i) + q]; h[4 * i + 3] = weight[at + i]; }
+        HIPCK(c, hipMemcpy(c->tsdf_col.as<float>() + 4 * at, h.data(), m * 16, hipMemcpyHostToDevice));
+    }
+    return ICP_OK;
+}
+
 int icp_tsdf_integrate(icp_ctx* c, const float* depth, const icp_depth_camera* cam, const float pose[16], int32_t* n_updated_out) {
     if (!c) return ICP_ERR_INVALID_ARG;
     if (n_updated_out) *n_updated_out = 0;
@@ -187,6 +262,26 @@ int icp_tsdf_integrate(icp_ctx* c, const float* depth, const icp_depth_camera* c
     int n = 0;
     if ((rc = read_count(c, c->tsdf_cnt.p, &n))) return rc;
     if (n_updated_out) *n_updated_out = n;
+    return guard.done();
+}
+
+int icp_tsdf_integrate_color(icp_ctx* c, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const float pose[16], int32_t* n_updated_out,
+                             int32_t* n_colored_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (n_updated_out) *n_updated_out = 0;
+    if (n_colored_out) *n_colored_out = 0;
+    int rc;
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_integrate_color"))) return rc;
+    if ((rc = tsdf_check_color(c, "icp_tsdf_integrate_color"))) return rc;
+    if (!depth || !rgbx) { c->err = "icp_tsdf_integrate_color: null depth or colour frame"; return ICP_ERR_INVALID_ARG; }
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>(), true))) return rc;
+    int n[2] = {0, 0};
+    if ((rc = read_count(c, c->tsdf_cnt.p, n, 2))) return rc;
+    if (n_updated_out) *n_updated_out = n[0];
+    if (n_colored_out) *n_colored_out = n[1];
     return guard.done();
 }
 
@@ -229,33 +324,87 @@ int icp_set_target_tsdf(icp_ctx* c, const icp_depth_camera* cam, const float pos
     return guard.done();
 }
 
-int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frames, const icp_depth_camera* cam, const icp_depth_options* source_opt,
-                          const float* gt_frames, float pose_inout[16], icp_track_frame* out) {
+int icp_tsdf_raycast_color(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], float* depth_out, float* vertices_out, float* normals_out,
+                           uint8_t* rgba_out, int32_t* n_hits_out, int32_t* n_colored_out) {
     if (!c) return ICP_ERR_INVALID_ARG;
-    if (!depth_frames || n_frames < 1 || !pose_inout || (n_frames > 1 && !out)) { c->err = "icp_track_depth_model: bad argument"; return ICP_ERR_INVALID_ARG; }
+    if (n_hits_out) *n_hits_out = 0;
+    if (n_colored_out) *n_colored_out = 0;
     int rc;
-    if ((rc = tsdf_check_call(c, cam, pose_inout, "icp_track_depth_model"))) return rc;
-    if ((rc = check_depth_args(c, cam, source_opt, "icp_track_depth_model"))) return rc;
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_raycast_color"))) return rc;
+    if ((rc = tsdf_check_color(c, "icp_tsdf_raycast_color"))) return rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const size_t n = (size_t)cam->width * cam->height;
+    if ((rc = ensure(c, c->staging, n * 32))) return rc;      // [depth 4n | vertices 12n | normals 12n | rgba 4n]
+    float* d = c->staging.as<float>();
+    TsdfRayOut o; memset(&o, 0, sizeof(o));
+    o.depth = depth_out ? d : nullptr; o.vert = vertices_out ? d + n : nullptr; o.nrm = normals_out ? d + 4 * n : nullptr;
+    const TsdfColorOut co = {rgba_out ? (uint32_t*)(d + 7 * n) : nullptr, nullptr, nullptr, nullptr};
+    if ((rc = tsdf_raycast_launch(c, *cam, pose, false, o, &co))) return rc;
+    if (depth_out) HIPCK(c, hipMemcpyAsync(depth_out, o.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (vertices_out) HIPCK(c, hipMemcpyAsync(vertices_out, o.vert, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (normals_out) HIPCK(c, hipMemcpyAsync(normals_out, o.nrm, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (rgba_out) HIPCK(c, hipMemcpyAsync(rgba_out, co.rgba, n * 4, hipMemcpyDeviceToHost, c->stream));
+    int cnt[2] = {0, 0};
+    if ((rc = read_count(c, c->tsdf_cnt.p, cnt, 2))) return rc;
+    if (n_hits_out) *n_hits_out = cnt[0];
+    if (n_colored_out) *n_colored_out = cnt[1];
+    return guard.done();
+}
+
+int icp_set_target_tsdf_color(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (n_points_out) *n_points_out = 0;
+    int rc;
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_set_target_tsdf_color"))) return rc;
+    if ((rc = tsdf_check_color(c, "icp_set_target_tsdf_color"))) return rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    int hits = 0;
+    rc = set_target_tsdf(c, *cam, pose, &hits, "icp_set_target_tsdf_color", true);
+    if (rc == ICP_ERR_NO_TARGET) return guard.done(rc);      // (synchronised by the count read)
+    if (rc) return rc;
+    if (n_points_out) *n_points_out = hits;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+
+// Both tracking loops.  color (icp_track_depth_model_color): frames staged with their colour frame, the coloured target, the source with
+// colours, the coloured integration -- and the colour modes, which the geometric loop refuses, accepted.
+static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_t* rgbx_frames, bool color, int32_t n_frames, const icp_depth_camera* cam,
+                             const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out, const std::string& who) {
+    if (!depth_frames || n_frames < 1 || !pose_inout || (n_frames > 1 && !out)) { c->err = who + ": bad argument"; return ICP_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = tsdf_check_call(c, cam, pose_inout, who.c_str()))) return rc;
+    if ((rc = check_depth_args(c, cam, source_opt, who.c_str()))) return rc;
     const icp_params& p = c->prm;
     if (p.matching == ICP_MATCH_PROJECTIVE && (p.fx != cam->fx || p.fy != cam->fy || p.cx != cam->cx || p.cy != cam->cy || p.width != cam->width || p.height != cam->height)) {
-        c->err = "icp_track_depth_model: the camera of the params differs from the depth camera"; return ICP_ERR_INVALID_ARG;
+        c->err = who + ": the camera of the params differs from the depth camera"; return ICP_ERR_INVALID_ARG;
     }
-    if ((p.matching == ICP_MATCH_KNN && p.color_icp) || p.weighting == ICP_WEIGHT_COLORS || p.metric == ICP_METRIC_COLORED) {
-        c->err = "icp_track_depth_model: the model has no colours (colour ICP, colour weighting and the colored metric are not supported)"; return ICP_ERR_INVALID_ARG;
+    if (color) {
+        if (!rgbx_frames) { c->err = who + ": null colour frames"; return ICP_ERR_INVALID_ARG; }
+        if ((rc = tsdf_check_color(c, who.c_str()))) return rc;
+        if (!source_opt->fix_color_index) {
+            c->err = who + ": source_opt->fix_color_index must be set (the model holds each pixel's own bytes, the reference's shifted bytes would compare unlike things)";
+            return ICP_ERR_INVALID_ARG;
+        }
+    } else if ((p.matching == ICP_MATCH_KNN && p.color_icp) || p.weighting == ICP_WEIGHT_COLORS || p.metric == ICP_METRIC_COLORED) {
+        c->err = who + ": the model has no colours (colour ICP, colour weighting and the colored metric are not supported)"; return ICP_ERR_INVALID_ARG;
     }
-    if (p.metric == ICP_METRIC_GICP) { c->err = "icp_track_depth_model: GICP is not supported (its per-target covariance pass would run every frame)"; return ICP_ERR_INVALID_ARG; }
+    if (p.metric == ICP_METRIC_GICP) { c->err = who + ": GICP is not supported (its per-target covariance pass would run every frame)"; return ICP_ERR_INVALID_ARG; }
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     const int n = cam->width * cam->height;
+    auto frame_rgbx = [&](int k) { return color ? rgbx_frames + (size_t)k * n * 4 : nullptr; };
     if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     // frame 0 into the model at the incoming pose; frame 1 goes up meanwhile
-    if ((rc = stage_depth(c, 0, depth_frames, nullptr, n, c->stream))) return rc;
-    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose_inout, nullptr))) return rc;
-    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, nullptr, n, c->depth_stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
+    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose_inout, nullptr, color))) return rc;
+    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream))) return rc;
     if (gt_frames && n_frames > 1 && (rc = track_rmse_prepare(c, n_frames))) return rc;
     static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     int first_err = ICP_OK;
-    auto fail = [&](icp_track_frame& r, int status, const char* why) {
+    auto fail = [&](icp_track_frame& r, int status, const std::string& why) {
         r.status = status; memcpy(r.pose, pose_inout, 64);
         if (first_err == ICP_OK) { first_err = status; c->err = why; }
     };
@@ -265,15 +414,15 @@ int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frame
         const int slot = k & 1;
         int hits = 0, kept = 0;
         // the model seen from the current pose (the count read waits for the stream: the integration of frame k - 1 has left its slot)
-        const int trc = set_target_tsdf(c, *cam, pose_inout, &hits, "icp_track_depth_model");
+        const int trc = set_target_tsdf(c, *cam, pose_inout, &hits, who.c_str(), color);
         if (trc != ICP_OK && trc != ICP_ERR_NO_TARGET) return trc;
-        if ((rc = depth_to_cloud(c, slot, *cam, *source_opt, false, c->src, false, &kept))) return rc;
+        if ((rc = depth_to_cloud(c, slot, *cam, *source_opt, color, c->src, false, &kept))) return rc;
         // frame k + 1 goes up on the second stream while frame k iterates (its slot was last read by frame k - 1, which has finished)
-        if (k + 1 < n_frames && (rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, nullptr, n, c->depth_stream))) return rc;
+        if (k + 1 < n_frames && (rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream))) return rc;
         if ((rc = finish_source(c))) return rc;
         r.n_src = kept;
-        if (trc == ICP_ERR_NO_TARGET) { fail(r, ICP_ERR_NO_TARGET, "icp_track_depth_model: the ray-cast of the model hits nothing"); continue; }
-        if (kept == 0) { fail(r, ICP_ERR_NO_SOURCE, "icp_track_depth_model: a frame keeps no points"); continue; }
+        if (trc == ICP_ERR_NO_TARGET) { fail(r, ICP_ERR_NO_TARGET, who + (color ? ": the ray-cast of the model hits nothing that has a colour" : ": the ray-cast of the model hits nothing")); continue; }
+        if (kept == 0) { fail(r, ICP_ERR_NO_SOURCE, who + ": a frame keeps no points"); continue; }
         float* d_rmse = gt_frames ? c->track_rmse.as<float>() + (size_t)(k - 1) * 2 : nullptr;
         if (gt_frames) {
             // the convergence reference: the source moved by pose_before^-1 gt_k, composed in fp64 and rounded once
@@ -297,7 +446,7 @@ int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frame
         if (gt_frames && (rc = track_rmse_at(c, 1, dT, d_rmse + 1))) return rc;
         if (r.status == ICP_OK) {
             compose_pose(pose_inout, dT);
-            if ((rc = tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr))) return rc;
+            if ((rc = tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, color))) return rc;
         }
         memcpy(r.pose, pose_inout, 64);
     }
@@ -306,6 +455,16 @@ int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frame
     if (gt_frames && n_frames > 1 && (rc = track_rmse_finish(c, n_frames, out, [](const icp_track_frame& r) { return r.n_src > 0 && r.status != ICP_ERR_NO_TARGET; }))) return rc;
     guard.ok = true;
     return first_err;
+}
+int icp_track_depth_model(icp_ctx* c, const float* depth_frames, int32_t n_frames, const icp_depth_camera* cam, const icp_depth_options* source_opt,
+                          const float* gt_frames, float pose_inout[16], icp_track_frame* out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    return track_depth_model(c, depth_frames, nullptr, false, n_frames, cam, source_opt, gt_frames, pose_inout, out, "icp_track_depth_model");
+}
+int icp_track_depth_model_color(icp_ctx* c, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames, const icp_depth_camera* cam,
+                                const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    return track_depth_model(c, depth_frames, rgbx_frames, true, n_frames, cam, source_opt, gt_frames, pose_inout, out, "icp_track_depth_model_color");
 }
 
 // Not part of icp_hip.h (tools/time_tsdf.py): the device time of ONE integrate (which = 0, the frame staged outside the bracket) or ONE
@@ -331,6 +490,39 @@ extern "C" int icp_debug_tsdf_time(icp_ctx* c, int32_t which, const float* depth
         o.depth = d; o.vert = d + n; o.nrm = d + 4 * n;
         HIPCK(c, hipEventRecord(c->events[0], c->stream));
         if ((rc = tsdf_raycast_launch(c, *cam, pose, false, o))) return rc;
+    }
+    HIPCK(c, hipEventRecord(c->events[1], c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
+    return guard.done();
+}
+
+// Not part of icp_hip.h (tools/time_tsdf_color.py): icp_debug_tsdf_time for the coloured kernels -- ONE icp_tsdf_integrate_color (which = 0,
+// the frames staged outside the bracket) or ONE icp_tsdf_raycast_color to the host-layout arrays (which = 1).
+extern "C" int icp_debug_tsdf_color_time(icp_ctx* c, int32_t which, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const float pose[16],
+                                         float* ms_out) {
+    if (!c || !ms_out || which < 0 || which > 1) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_debug_tsdf_color_time"))) return rc;
+    if ((rc = tsdf_check_color(c, "icp_debug_tsdf_color_time"))) return rc;
+    if (which == 0 && (!depth || !rgbx)) return ICP_ERR_INVALID_ARG;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ensure_events(c, 2))) return rc;
+    const size_t n = (size_t)cam->width * cam->height;
+    if (which == 0) {
+        if ((rc = stage_depth(c, 0, depth, rgbx, (int)n, c->stream))) return rc;
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        HIPCK(c, hipEventRecord(c->events[0], c->stream));
+        if ((rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>(), true))) return rc;
+    } else {
+        if ((rc = ensure(c, c->staging, n * 32))) return rc;
+        float* d = c->staging.as<float>();
+        TsdfRayOut o; memset(&o, 0, sizeof(o));
+        o.depth = d; o.vert = d + n; o.nrm = d + 4 * n;
+        const TsdfColorOut co = {(uint32_t*)(d + 7 * n), nullptr, nullptr, nullptr};
+        HIPCK(c, hipEventRecord(c->events[0], c->stream));
+        if ((rc = tsdf_raycast_launch(c, *cam, pose, false, o, &co))) return rc;
     }
     HIPCK(c, hipEventRecord(c->events[1], c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));

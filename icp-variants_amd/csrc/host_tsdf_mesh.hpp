@@ -1,5 +1,6 @@
 // host_tsdf_mesh.hpp -- icp_tsdf_mesh: the zero level set of the context's TSDF volume as an indexed triangle mesh, extracted on the device;
-// only the mesh crosses to the host.  Kernels: dev_tsdf_mesh.hpp; contract: include/icp_hip.h, DESIGN.md section 6n.
+// only the mesh crosses to the host; icp_tsdf_mesh_color: the same mesh with a colour per vertex from the volume's colour array.
+// Kernels: dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp; contract: include/icp_hip.h, DESIGN.md sections 6n and 6p.
 // Part of icp_hip.hip (included from there, after host_tsdf.hpp).
 namespace {
 TmDiv tm_make_div(uint32_t d) {
@@ -59,18 +60,20 @@ int tm_check_call(icp_ctx* c, float min_weight, const char* who) {
     if (tsdf_voxels(c) > (size_t)(INT32_MAX / 12)) { c->err = std::string(who) + ": the volume has more than INT32_MAX / 12 voxels"; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;
 }
-}  // namespace
-
-int icp_tsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint32_t* triangles_out,
-                  int32_t* n_vertices_out, int32_t* n_triangles_out) {
-    if (!c) return ICP_ERR_INVALID_ARG;
+// Both mesh calls.  color (icp_tsdf_mesh_color): needs the colour array; colors_out (optional) receives one packed colour per vertex.
+int tsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out, bool color,
+              uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, const std::string& who) {
     if (n_vertices_out) *n_vertices_out = 0;
     if (n_triangles_out) *n_triangles_out = 0;
     int rc;
-    if ((rc = tm_check_call(c, min_weight, "icp_tsdf_mesh"))) return rc;
-    if (!n_vertices_out || !n_triangles_out) { c->err = "icp_tsdf_mesh: null count pointer"; return ICP_ERR_INVALID_ARG; }
-    const bool count_only = !vertices_out && !normals_out && !triangles_out;
-    if (!count_only && (!vertices_out || !triangles_out)) { c->err = "icp_tsdf_mesh: vertices_out and triangles_out go together (normals_out alone may be NULL)"; return ICP_ERR_INVALID_ARG; }
+    if ((rc = tm_check_call(c, min_weight, who.c_str()))) return rc;
+    if (color && (rc = tsdf_check_color(c, who.c_str()))) return rc;
+    if (!n_vertices_out || !n_triangles_out) { c->err = who + ": null count pointer"; return ICP_ERR_INVALID_ARG; }
+    const bool count_only = !vertices_out && !normals_out && !colors_out && !triangles_out;
+    if (!count_only && (!vertices_out || !triangles_out)) {
+        c->err = who + (color ? ": vertices_out and triangles_out go together (normals_out and colors_out may be NULL)" : ": vertices_out and triangles_out go together (normals_out alone may be NULL)");
+        return ICP_ERR_INVALID_ARG;
+    }
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     const TmGrid g = tm_grid(c);
@@ -80,27 +83,46 @@ int icp_tsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t ma
     int tot[2] = {0, 0};                                 // both totals back in one copy
     if ((rc = read_count(c, s.tot, tot, 2))) return rc;
     const int nv = tot[0], nt = tot[1];
-    if (nv < 0 || nt < 0) { c->err = "icp_tsdf_mesh: count out of range"; return ICP_ERR_HIP; }
+    if (nv < 0 || nt < 0) { c->err = who + ": count out of range"; return ICP_ERR_HIP; }
     *n_vertices_out = nv; *n_triangles_out = nt;
     if (count_only) return guard.done();
     if (nv > max_vertices || nt > max_triangles) {
         char buf[200];
-        snprintf(buf, sizeof(buf), "icp_tsdf_mesh: the mesh has %d vertices and %d triangles, the arrays hold %d and %d", nv, nt, max_vertices, max_triangles);
+        snprintf(buf, sizeof(buf), "%s: the mesh has %d vertices and %d triangles, the arrays hold %d and %d", who.c_str(), nv, nt, max_vertices, max_triangles);
         c->err = buf;
         return guard.done(ICP_ERR_INVALID_ARG);      // (synchronised by the count read)
     }
     if (nv == 0 && nt == 0) return guard.done();
-    // the outputs staged in device arrays of exactly the counted size: [vertices 12 V | normals 12 V | triangles 12 T]
-    const size_t bv = (size_t)nv * 12, bn = normals_out ? bv : 0, bt = (size_t)nt * 12;
-    if ((rc = ensure(c, c->tm_out, bv + bn + bt))) return rc;
+    // the outputs staged in device arrays of exactly the counted size: [vertices 12 V | normals 12 V | triangles 12 T | colours 4 V]
+    const size_t bv = (size_t)nv * 12, bn = normals_out ? bv : 0, bt = (size_t)nt * 12, bc = colors_out ? (size_t)nv * 4 : 0;
+    if ((rc = ensure(c, c->tm_out, bv + bn + bt + bc))) return rc;
     char* d = c->tm_out.as<char>();
     float* d_vert = (float*)d; float* d_nrm = normals_out ? (float*)(d + bv) : nullptr; uint32_t* d_tris = (uint32_t*)(d + bv + bn);
+    uint32_t* d_col = (uint32_t*)(d + bv + bn + bt);
     if ((rc = tm_enqueue_fill(c, g, s, d_vert, d_nrm, d_tris))) return rc;
+    if (colors_out && nv > 0) {
+        hipLaunchKernelGGL(k_tm_colors, dim3((unsigned)tm_blocks(g)), dim3(256), 0, c->stream, tsdf_view(c), (const float4*)c->tsdf_col.as<float4>(), g, (const uint8_t*)s.mask,
+                           (const int*)s.vblk, d_col);
+        HIPCK(c, hipGetLastError());
+        HIPCK(c, hipMemcpyAsync(colors_out, d_col, bc, hipMemcpyDeviceToHost, c->stream));
+    }
     if (nv > 0) HIPCK(c, hipMemcpyAsync(vertices_out, d_vert, bv, hipMemcpyDeviceToHost, c->stream));
     if (nv > 0 && normals_out) HIPCK(c, hipMemcpyAsync(normals_out, d_nrm, bn, hipMemcpyDeviceToHost, c->stream));
     if (nt > 0) HIPCK(c, hipMemcpyAsync(triangles_out, d_tris, bt, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return guard.done();
+}
+}  // namespace
+
+int icp_tsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint32_t* triangles_out,
+                  int32_t* n_vertices_out, int32_t* n_triangles_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    return tsdf_mesh(c, min_weight, max_vertices, max_triangles, vertices_out, normals_out, nullptr, false, triangles_out, n_vertices_out, n_triangles_out, "icp_tsdf_mesh");
+}
+int icp_tsdf_mesh_color(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out,
+                        uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    return tsdf_mesh(c, min_weight, max_vertices, max_triangles, vertices_out, normals_out, colors_out, true, triangles_out, n_vertices_out, n_triangles_out, "icp_tsdf_mesh_color");
 }
 
 // Not part of icp_hip.h (tools/time_tsdf_mesh.py): the device time of ALL passes of one icp_tsdf_mesh (counting, the two scans, scatter, with

@@ -8,7 +8,7 @@
 //
 // Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_converge.hpp, dev_solve.hpp,
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
-// dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp
+// dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf_color.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -49,6 +49,8 @@
 //   k_tsdf_raycast      the volume ray-cast from a pose as an organised cloud, to the host or straight into the target (dev_tsdf.hpp)
 //   k_tm_*              the zero level set of that volume as an indexed triangle mesh (icp_tsdf_mesh): marching tetrahedra on the Kuhn
 //                       triangulation of every cell, as bitmap passes and a stable two-pass compaction (dev_tsdf_mesh.hpp)
+//   k_tsdf_*_color /    the coloured model (icp_tsdf_integrate_color, icp_tsdf_raycast_color, icp_tsdf_mesh_color): a second array of running
+//   k_tm_colors         colour averages per voxel, fused, ray-cast and meshed with the geometry (dev_tsdf.hpp, dev_tsdf_mesh_color.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -80,7 +82,9 @@ namespace icpdev {
 #include "dev_nss.hpp"
 #include "dev_fpfh.hpp"
 #include "dev_reciprocal.hpp"
+#include "dev_tsdf_color.hpp"
 #include "dev_tsdf.hpp"
 #include "dev_tsdf_mesh.hpp"
+#include "dev_tsdf_mesh_color.hpp"
 
 }  // namespace icpdev

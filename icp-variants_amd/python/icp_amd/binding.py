@@ -258,6 +258,8 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_set_target_depth", "icp_set_source_depth", "icp_track_depth_frames", "icp_depth_mesh",
            "icp_tsdf_options_default", "icp_tsdf_options_check", "icp_tsdf_create", "icp_tsdf_reset", "icp_tsdf_release", "icp_tsdf_download", "icp_tsdf_upload",
            "icp_tsdf_integrate", "icp_tsdf_raycast", "icp_set_target_tsdf", "icp_track_depth_model", "icp_tsdf_mesh",
+           "icp_tsdf_color_create", "icp_tsdf_color_release", "icp_tsdf_color_download", "icp_tsdf_color_upload", "icp_tsdf_integrate_color",
+           "icp_tsdf_raycast_color", "icp_set_target_tsdf_color", "icp_track_depth_model_color", "icp_tsdf_mesh_color",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
@@ -800,12 +802,37 @@ class Context:
                                          _ptr(pose_to_c(camera_pose)), C.c_float(edge_threshold), _ptr(verts), _ptr(cols), _ptr(tris), C.byref(nt)))
         return verts, cols, tris[:nt.value]
 
-    def tsdf_create(self, options=None, **kw):
+    def tsdf_create(self, options=None, color=False, **kw):
         """icp_tsdf_create: the context's TSDF volume (frame-to-model tracking), allocated and cleared.  options: an IcpTsdfOptions, or
-        the arguments of `tsdf_options` (dims, origin, voxel_size, truncation, max_weight, min_depth, max_depth, ray_step)."""
+        the arguments of `tsdf_options` (dims, origin, voxel_size, truncation, max_weight, min_depth, max_depth, ray_step).
+        color: also icp_tsdf_color_create, the colour array (16 more bytes per voxel)."""
         o = options if options is not None else tsdf_options(**kw)
         self._ck(self.lib.icp_tsdf_create(self.h, C.byref(o)))
         self._tsdf_dims = tuple(o.dims)
+        if color:
+            self.tsdf_color_create()
+
+    def tsdf_color_create(self):
+        """icp_tsdf_color_create: the volume's colour array, one (R, G, B, Wc) per voxel, allocated and cleared (called again: cleared)."""
+        self._ck(self.lib.icp_tsdf_color_create(self.h))
+
+    def tsdf_color_release(self):
+        self._ck(self.lib.icp_tsdf_color_release(self.h))
+
+    def tsdf_color_volume(self):
+        """icp_tsdf_color_download: (rgb (nz, ny, nx, 3), weight (nz, ny, nx)), float32; rgb holds running averages of byte values 0..255."""
+        shape = self._tsdf_shape()
+        rgb = np.empty(shape + (3,), np.float32); w = np.empty(shape, np.float32)
+        self._ck(self.lib.icp_tsdf_color_download(self.h, _ptr(rgb), _ptr(w)))
+        return rgb, w
+
+    def tsdf_color_upload(self, rgb, weight):
+        """icp_tsdf_color_upload: replaces the colour array's contents (nx*ny*nz x 3 and nx*ny*nz values, x fastest)."""
+        shape = self._tsdf_shape()
+        c, w = _f32(rgb), _f32(weight)
+        if w.size != np.prod(shape) or c.size != 3 * w.size:
+            raise ValueError("the arrays must hold nx * ny * nz x 3 and nx * ny * nz values")
+        self._ck(self.lib.icp_tsdf_color_upload(self.h, _ptr(c), _ptr(w)))
 
     def tsdf_reset(self):
         self._ck(self.lib.icp_tsdf_reset(self.h))
@@ -835,12 +862,21 @@ class Context:
             raise ValueError("the arrays must hold nx * ny * nz values")
         self._ck(self.lib.icp_tsdf_upload(self.h, _ptr(t), _ptr(w)))
 
-    def tsdf_integrate(self, depth, cam, pose):
-        """icp_tsdf_integrate: fuses one depth frame, seen from `pose` (4x4 camera -> world), into the volume.  Returns the voxels written."""
+    def tsdf_integrate(self, depth, cam, pose, rgbx=None):
+        """icp_tsdf_integrate: fuses one depth frame, seen from `pose` (4x4 camera -> world), into the volume.  Returns the voxels written.
+        rgbx (h*w x 4 bytes, the depth frame's size): icp_tsdf_integrate_color, the frame's colours into the colour array as well; returns
+        (voxels written, voxels coloured)."""
         depth = np.ascontiguousarray(depth, dtype=np.float32)
         if depth.size != cam.width * cam.height:
             raise ValueError("depth frame has %d pixels, the camera %d x %d" % (depth.size, cam.width, cam.height))
         n = C.c_int32(0)
+        if rgbx is not None:
+            cols = np.ascontiguousarray(rgbx, dtype=np.uint8)
+            if cols.size != 4 * depth.size:
+                raise ValueError("colour frame must hold 4 bytes per pixel of the depth frame")
+            nc = C.c_int32(0)
+            self._ck(self.lib.icp_tsdf_integrate_color(self.h, _ptr(depth), _ptr(cols), C.byref(cam), _ptr(pose_to_c(pose)), C.byref(n), C.byref(nc)))
+            return n.value, nc.value
         self._ck(self.lib.icp_tsdf_integrate(self.h, _ptr(depth), C.byref(cam), _ptr(pose_to_c(pose)), C.byref(n)))
         return n.value
 
@@ -852,31 +888,51 @@ class Context:
         self._ck(self.lib.icp_tsdf_raycast(self.h, C.byref(cam), _ptr(pose_to_c(pose)), _ptr(d), _ptr(v), _ptr(nr), C.byref(hits)))
         return d, v, nr, hits.value
 
-    def tsdf_mesh(self, min_weight=0.0):
+    def tsdf_raycast_color(self, cam, pose):
+        """icp_tsdf_raycast_color: `tsdf_raycast` with the colour of every hit.  Returns (depth, vertices, normals, rgba (w*h, 4) u8, hits,
+        coloured hits); a hole or a hit without colour is four zero bytes, a coloured pixel has alpha 255."""
+        n = cam.width * cam.height
+        d = np.empty((cam.height, cam.width), np.float32); v = np.empty((n, 3), np.float32); nr = np.empty((n, 3), np.float32)
+        rgba = np.empty((n, 4), np.uint8); hits, ncol = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.icp_tsdf_raycast_color(self.h, C.byref(cam), _ptr(pose_to_c(pose)), _ptr(d), _ptr(v), _ptr(nr), _ptr(rgba), C.byref(hits), C.byref(ncol)))
+        return d, v, nr, rgba, hits.value, ncol.value
+
+    def tsdf_mesh(self, min_weight=0.0, colors=False):
         """icp_tsdf_mesh: the zero level set of the volume as an indexed triangle mesh, extracted on the device (a counting call, then a
         filling call).  min_weight: voxels below this weight count as unobserved.  Returns (vertices (V, 3) f32 in the world frame,
-        normals (V, 3) f32 pointing into free space, triangles (T, 3) u32, counter-clockwise seen from free space)."""
+        normals (V, 3) f32 pointing into free space, triangles (T, 3) u32, counter-clockwise seen from free space).
+        colors: icp_tsdf_mesh_color; a fourth array, (V, 4) u8 RGBA per vertex (four zero bytes where the volume holds no colour)."""
         nv, nt = C.c_int32(0), C.c_int32(0)
         mw = C.c_float(min_weight)
+        if colors:
+            self._ck(self.lib.icp_tsdf_mesh_color(self.h, mw, C.c_int32(0), C.c_int32(0), None, None, None, None, C.byref(nv), C.byref(nt)))
+            v = np.empty((nv.value, 3), np.float32); n = np.empty((nv.value, 3), np.float32); t = np.empty((nt.value, 3), np.uint32)
+            col = np.empty((nv.value, 4), np.uint8)
+            if nv.value or nt.value:
+                self._ck(self.lib.icp_tsdf_mesh_color(self.h, mw, C.c_int32(nv.value), C.c_int32(nt.value), _ptr(v), _ptr(n), _ptr(col), _ptr(t), C.byref(nv), C.byref(nt)))
+            return v, n, t, col
         self._ck(self.lib.icp_tsdf_mesh(self.h, mw, C.c_int32(0), C.c_int32(0), None, None, None, C.byref(nv), C.byref(nt)))
         v = np.empty((nv.value, 3), np.float32); n = np.empty((nv.value, 3), np.float32); t = np.empty((nt.value, 3), np.uint32)
         if nv.value or nt.value:
             self._ck(self.lib.icp_tsdf_mesh(self.h, mw, C.c_int32(nv.value), C.c_int32(nt.value), _ptr(v), _ptr(n), _ptr(t), C.byref(nv), C.byref(nt)))
         return v, n, t
 
-    def set_target_tsdf(self, cam, pose, check=True):
+    def set_target_tsdf(self, cam, pose, check=True, color=False):
         """icp_set_target_tsdf: the ray-cast of the volume from `pose` as the target (organised, with normals).  Returns the number of hits
-        (and the status with check=False)."""
+        (and the status with check=False).  color: icp_set_target_tsdf_color, the target with colours; hits without a colour become holes
+        and the coloured hits are returned."""
         n = C.c_int32(0)
-        rc = self.lib.icp_set_target_tsdf(self.h, C.byref(cam), _ptr(pose_to_c(pose)), C.byref(n))
+        fn = self.lib.icp_set_target_tsdf_color if color else self.lib.icp_set_target_tsdf
+        rc = fn(self.h, C.byref(cam), _ptr(pose_to_c(pose)), C.byref(n))
         if check:
             self._ck(rc)
         self.n_tgt = cam.width * cam.height if rc == ICP_OK else 0
         return n.value if check else (n.value, rc)
 
-    def track_depth_model(self, depth_frames, cam, source_opt, gt=None, pose=None):
+    def track_depth_model(self, depth_frames, cam, source_opt, gt=None, pose=None, rgbx_frames=None):
         """icp_track_depth_model: frame-to-model tracking over frames (n, h, w) against the context's TSDF volume.  gt: (n - 1) 4x4 transforms
-        frame k -> world, or None.  pose: the camera -> world pose of frame 0 (identity by default).  Returns (final pose, records, status)."""
+        frame k -> world, or None.  pose: the camera -> world pose of frame 0 (identity by default).  Returns (final pose, records, status).
+        rgbx_frames (n, h*w, 4): icp_track_depth_model_color, the coloured model (needs the colour array and source_opt.fix_color_index)."""
         d = np.ascontiguousarray(depth_frames, dtype=np.float32)
         nf = d.shape[0]
         if d.size != nf * cam.width * cam.height:
@@ -886,7 +942,13 @@ class Context:
             raise ValueError("gt needs one transform per tracked frame")
         p = pose_to_c(np.eye(4) if pose is None else pose)
         out = (IcpTrackFrame * max(nf - 1, 1))()
-        rc = self.lib.icp_track_depth_model(self.h, _ptr(d), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
+        if rgbx_frames is not None:
+            cols = np.ascontiguousarray(rgbx_frames, dtype=np.uint8)
+            if cols.size != 4 * d.size:
+                raise ValueError("colour frames must hold 4 bytes per pixel")
+            rc = self.lib.icp_track_depth_model_color(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
+        else:
+            rc = self.lib.icp_track_depth_model(self.h, _ptr(d), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
         if rc not in (ICP_OK, ERR_NO_TARGET, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
             self._ck(rc)
         recs = [dict(n_src=out[i].n_src, iterations=out[i].iterations, status=out[i].status, initial_rmse=out[i].initial_rmse,

@@ -6,7 +6,7 @@ accumulated in file order; colours of mesh-derived clouds are all zero (PointClo
 Pre-processing outside the timed ICP loop -- plain numpy, fp32.
 write_off / camera_glyph / join_meshes follow writeMesh, camera and joinMeshes (SimpleMesh.h:231-302,336-359): the output side of
 saveRoomToFile (utils.h:179-193).  A mesh is a tuple (vertices (V,3) f32, colors (V,4) u8, triangles (T,3) u32).
-write_ply_mesh / load_ply_mesh: the mesh of the fused model (Context.tsdf_mesh: vertices, normals, triangles) as a binary PLY.
+write_ply_mesh / load_ply_mesh: the mesh of the fused model (Context.tsdf_mesh: vertices, normals, triangles, optionally colours) as a binary PLY.
 """
 import numpy as np
 
@@ -114,8 +114,13 @@ PLY_MESH_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\npro
 _PLY_FACE = np.dtype([("n", "u1"), ("idx", "<i4", (3,))])
 
 
-def write_ply_mesh(path, vertices, normals, triangles):
-    """A triangle mesh with per-vertex normals as a binary little-endian PLY: `float` x y z nx ny nz per vertex, a `uchar int` index list per face."""
+PLY_COLOR_MESH_HEADER = PLY_MESH_HEADER.replace("property float nz\n", "property float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n")
+_PLY_COLOR_VERTEX = np.dtype([("vn", "<f4", (6,)), ("rgba", "u1", (4,))])
+
+
+def write_ply_mesh(path, vertices, normals, triangles, colors=None):
+    """A triangle mesh with per-vertex normals as a binary little-endian PLY: `float` x y z nx ny nz per vertex, a `uchar int` index list per face.
+    colors ((V, 4) u8, Context.tsdf_mesh(colors=True)): `uchar` red green blue alpha follow the normal of every vertex."""
     v = np.asarray(vertices, np.float32).reshape(-1, 3)
     n = np.asarray(normals, np.float32).reshape(-1, 3)
     t = np.asarray(triangles, np.uint32).reshape(-1, 3)
@@ -125,14 +130,23 @@ def write_ply_mesh(path, vertices, normals, triangles):
         raise ValueError("a vertex index does not fit the PLY's int")
     faces = np.empty(len(t), _PLY_FACE)
     faces["n"] = 3; faces["idx"] = t.astype("<i4")
+    if colors is None:
+        header, body = PLY_MESH_HEADER, np.concatenate([v, n], axis=1).astype("<f4")
+    else:
+        c = np.asarray(colors, np.uint8).reshape(-1, 4)
+        if len(c) != len(v):
+            raise ValueError("one colour per vertex")
+        header, body = PLY_COLOR_MESH_HEADER, np.empty(len(v), _PLY_COLOR_VERTEX)
+        body["vn"] = np.concatenate([v, n], axis=1); body["rgba"] = c
     with open(path, "wb") as f:
-        f.write((PLY_MESH_HEADER % (len(v), len(t))).encode("ascii"))
-        f.write(np.concatenate([v, n], axis=1).astype("<f4").tobytes())
+        f.write((header % (len(v), len(t))).encode("ascii"))
+        f.write(body.tobytes())
         f.write(faces.tobytes())
 
 
-def load_ply_mesh(path):
-    """Reads what write_ply_mesh writes.  Returns (vertices (V,3) f32, normals (V,3) f32, triangles (T,3) u32)."""
+def load_ply_mesh(path, colors=False):
+    """Reads what write_ply_mesh writes.  Returns (vertices (V,3) f32, normals (V,3) f32, triangles (T,3) u32); with colors=True a fourth
+    array, (V, 4) u8, or None for a file without colours."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -145,10 +159,16 @@ def load_ply_mesh(path):
             nv = int(ln.split()[2])
         elif ln.startswith("element face "):
             nt = int(ln.split()[2])
-    if data[:end].decode("ascii") != PLY_MESH_HEADER % (nv, nt):
+    head = data[:end].decode("ascii")
+    if head == PLY_COLOR_MESH_HEADER % (nv, nt):
+        rec = np.frombuffer(data, _PLY_COLOR_VERTEX, nv, end)
+        vn, cols, stride = rec["vn"], rec["rgba"].copy(), 28
+    elif head == PLY_MESH_HEADER % (nv, nt):
+        vn, cols, stride = np.frombuffer(data, "<f4", nv * 6, end).reshape(nv, 6), None, 24
+    else:
         raise ValueError("not the layout write_ply_mesh writes")
-    vn = np.frombuffer(data, "<f4", nv * 6, end).reshape(nv, 6)
-    faces = np.frombuffer(data, _PLY_FACE, nt, end + nv * 24)
+    faces = np.frombuffer(data, _PLY_FACE, nt, end + nv * stride)
     if nt and not (faces["n"] == 3).all():
         raise ValueError("We can only read triangular mesh.")
-    return vn[:, :3].astype(np.float32), vn[:, 3:].astype(np.float32), faces["idx"].astype(np.uint32).reshape(nt, 3)
+    out = (vn[:, :3].astype(np.float32), vn[:, 3:].astype(np.float32), faces["idx"].astype(np.uint32).reshape(nt, 3))
+    return out + (cols,) if colors else out

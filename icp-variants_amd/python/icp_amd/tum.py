@@ -84,7 +84,11 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     model: None tracks every frame against frame 0, as the reference does.  A dict of `binding.tsdf_options` arguments (dims, origin,
     voxel_size, truncation, ...) tracks frame-to-model instead (icp_track_depth_model): the frames are fused into a TSDF volume created
     from those options, in frame 0's camera coordinates, and every frame is aligned to a ray-cast of it -- the track survives the camera
-    turning away from frame 0.  The colour frames are not used on that path.
+    turning away from frame 0.  The colour frames are not used on that path unless the dict also holds color=True: the volume then gets its
+    colour array and the frames are tracked with their colour frames (icp_track_depth_model_color), so the params may ask for colour ICP,
+    colour weighting or the colored metric.  That path sets fix_color_index on (a copy of) the source options itself, whatever the caller
+    or reconstruct_room_options chose: the model holds each pixel's own bytes, and the library refuses a source with the reference's
+    shifted ones.
     options: (target, source) icp_depth_options instead of reconstruct_room_options' choice (the model path uses the source's only)."""
     binding.select_optimizer(ctx, nonlinear)
     binding.select_convergence(ctx, convergence)
@@ -97,7 +101,11 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     tgt_o, src_o = reconstruct_room_options(ctx.params) if options is None else options
     if model is not None:
         ctx.tsdf_create(**model)
-        _, recs, rc = ctx.track_depth_model(seq["depth"], cam, src_o, gt=seq["gt"] if with_gt else None)
+        rgbx = None
+        if model.get("color"):
+            rgbx = seq["rgbx"]
+            src_o = binding.depth_options(bool(src_o.keep_original_size), int(src_o.downsample_factor), float(src_o.max_distance), fix_color_index=True)
+        _, recs, rc = ctx.track_depth_model(seq["depth"], cam, src_o, gt=seq["gt"] if with_gt else None, rgbx_frames=rgbx)
         poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
         return poses, recs, rc
     _, recs, rc = ctx.track_depth_frames(seq["depth"], seq["rgbx"], cam, tgt_o, src_o, gt=seq["gt"] if with_gt else None)
@@ -111,7 +119,8 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
     the camera pose `track` returned (the identity for frame 0).  With out_dir the meshes are written as mesh_<frame index>.off
     (getCurrentFrameCnt, VirtualSensor.h:142-144).  model: as `track` (frame-to-model tracking; the meshes stay per-frame depth meshes).
     model_mesh: with `model` and `out_dir`, a file name: the fused volume's zero level set (Context.tsdf_mesh, in frame 0's camera coordinates) is
-    written there as a binary PLY after the last frame -- the reconstructed room as ONE mesh; None writes nothing more.  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    written there as a binary PLY after the last frame -- the reconstructed room as ONE mesh, with per-vertex colours when the model has them
+    (color=True in `model`); None writes nothing more.  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
     poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model)
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     if out_dir is not None:
@@ -127,7 +136,11 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
             meshio.write_off(path, *mesh)
             out.append(path)
     if model is not None and model_mesh is not None and out_dir is not None:
-        meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh())
+        if model.get("color"):
+            v, n, t, col = ctx.tsdf_mesh(colors=True)
+            meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), v, n, t, colors=col)
+        else:
+            meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh())
     return poses, recs, rc, out
 
 

@@ -667,6 +667,56 @@ int icp_tsdf_mesh(icp_ctx* ctx, float min_weight, int32_t max_vertices, int32_t 
                   float* vertices_out, float* normals_out, uint32_t* triangles_out,
                   int32_t* n_vertices_out, int32_t* n_triangles_out);
 
+/* -------- the coloured model (an extension): a colour array next to the volume, fused, ray-cast, tracked against and meshed with the
+ * geometry.  DESIGN.md section 6p. --------
+ * The volume gets an optional second array, one float4 (R, G, B, Wc) per voxel, x fastest, indexed as the volume is: R, G, B are running
+ * averages of the byte values 0..255 held as floats, Wc is the colour's own weight (its update set is smaller than the geometry's).  fp32 on
+ * purpose: the average keeps its bits against tests/tsdf_color_restatement.py and does not stall at Wc = max_weight; a corner is one
+ * 16-byte load.  MEMORY: 16 bytes per voxel -- at 512^3 the colour array is 2 GiB next to the 1 GiB of geometry.  icp_tsdf_options keeps its
+ * layout: the array is created by its own call.  With none of these entry points called nothing else in the library changes behaviour; every
+ * geometry-only call stays legal on a volume with colours and leaves the colour array alone, except: icp_tsdf_reset also clears it,
+ * icp_tsdf_release, icp_tsdf_create (replacing a volume) and icp_ctx_destroy free it.  Every call below but icp_tsdf_color_create needs the
+ * colour array, else ICP_ERR_INVALID_ARG with a message.  All fp32 arithmetic is one rounding per operation in the order written.
+ *
+ * color_create: needs a volume; allocates and clears (0, 0, 0, 0); called again it clears.  download / upload: rgb n x 3 and weight n floats,
+ *   x fastest, n = nx ny nz; either pointer of download may be NULL.
+ * Integrate: geometry, and *n_updated_out, exactly as icp_tsdf_integrate from the same state.  rgbx: the colour frame of the depth frame's
+ *   size, registered to it (the TUM sensor), 4 bytes per pixel.  A voxel's colour is updated iff the voxel is updated AND !(sdf > truncation)
+ *   -- the band |sdf| <= truncation: free space far in front of a surface would take the colour of what lies behind it.  The pixel is the one
+ *   the geometry used, c_r = (float)rgbx[4 (v width + u) + r]; C_r <- (Wc C_r + c_r) / (Wc + 1) per channel, then
+ *   Wc <- fminf(Wc + 1, max_weight).  A voxel that is not coloured has its float4 neither read nor written.  *n_colored_out (optional):
+ *   voxels coloured.
+ * Ray-cast: march, hit, z*, vertex, normal and the first three arrays exactly as icp_tsdf_raycast.  The colour of a hit comes from the cell
+ *   of q(z*), the cell of the normal, with its fractions t: all eight corners have Wc > 0: the nested lerp a + t (b - a) along x, then y,
+ *   then z, per channel; otherwise the corner nearest the hit, d_r = (t_r >= 0.5f), if its Wc > 0; otherwise no colour.  Byte:
+ *   (uint8_t)(int)floorf(fminf(fmaxf(C, 0.f), 255.f) + 0.5f); a coloured pixel is (R, G, B, 255), a hole or an uncoloured hit four zero
+ *   bytes.  rgba_out: width*height*4 bytes (may be NULL as the others); *n_colored_out: the coloured hits. */
+int icp_tsdf_color_create(icp_ctx* ctx);
+int icp_tsdf_color_release(icp_ctx* ctx);
+int icp_tsdf_color_download(icp_ctx* ctx, float* rgb_out, float* weight_out);
+int icp_tsdf_color_upload(icp_ctx* ctx, const float* rgb, const float* weight);
+int icp_tsdf_integrate_color(icp_ctx* ctx, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const float pose[16],
+                             int32_t* n_updated_out, int32_t* n_colored_out);
+int icp_tsdf_raycast_color(icp_ctx* ctx, const icp_depth_camera* cam, const float pose[16], float* depth_out, float* vertices_out,
+                           float* normals_out, uint8_t* rgba_out, int32_t* n_hits_out, int32_t* n_colored_out);
+/* icp_set_target_tsdf WITH colours: what icp_set_target leaves for the arrays icp_tsdf_raycast_color returns once its uncoloured hits are
+ * turned into holes (every consumer of a coloured target needs the colour; a caller who does not has icp_set_target_tsdf).  *n_points_out:
+ * the coloured hits; none: an empty target and ICP_ERR_NO_TARGET. */
+int icp_set_target_tsdf_color(icp_ctx* ctx, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out);
+/* icp_track_depth_model with four changes: frames are staged with their colour frame (rgbx_frames: n_frames x width*height*4 bytes), the
+ * target comes from icp_set_target_tsdf_color, the source is built with colours, integration is icp_tsdf_integrate_color.  Accepts colour
+ * ICP (6-D k-NN), ICP_WEIGHT_COLORS and ICP_METRIC_COLORED, whose per-target gradient pass then runs every frame.  ICP_ERR_INVALID_ARG for
+ * GICP, null rgbx_frames, a volume without colours, and source_opt->fix_color_index == 0: the model holds each pixel's own bytes, the
+ * reference's shifted bytes on the source side would compare unlike things. */
+int icp_track_depth_model_color(icp_ctx* ctx, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames, const icp_depth_camera* cam,
+                                const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out);
+/* icp_tsdf_mesh with a colour per vertex: counts, vertices, normals and triangles are icp_tsdf_mesh's.  colors_out: max_vertices * 4 bytes,
+ * may be NULL.  The vertex on the edge from v to v + d at its t: both ends have Wc > 0: C_v + t (C_(v+d) - C_v) per channel; one end has:
+ * that end's colour; neither: four zero bytes.  Bytes by the ray-cast's rule, alpha 255. */
+int icp_tsdf_mesh_color(icp_ctx* ctx, float min_weight, int32_t max_vertices, int32_t max_triangles,
+                        float* vertices_out, float* normals_out, uint8_t* colors_out, uint32_t* triangles_out,
+                        int32_t* n_vertices_out, int32_t* n_triangles_out);
+
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
  * towards the viewpoint.  k in {3..8} (else ICP_ERR_INVALID_ARG).  Non-finite points, and every point of a cloud with fewer than
