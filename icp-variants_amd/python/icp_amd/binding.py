@@ -150,14 +150,18 @@ def select_convergence(ctx, convergence):
         ctx.set_convergence_options(**convergence)
 
 
-def depth_camera(K, width, height, extrinsics=None):
-    """icp_depth_camera from a 3x3 intrinsic matrix (K(0,0), K(1,1), K(0,2), K(1,2)) and an optional 4x4 depthExtrinsics."""
+def _camera(cls, K, width, height, extrinsics):
     K = np.asarray(K, dtype=np.float32)
-    cam = IcpDepthCamera(float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), int(width), int(height))
+    cam = cls(float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), int(width), int(height))
     E = pose_to_c(np.eye(4) if extrinsics is None else extrinsics)
     for k in range(16):
         cam.extrinsics[k] = float(E[k])
     return cam
+
+
+def depth_camera(K, width, height, extrinsics=None):
+    """icp_depth_camera from a 3x3 intrinsic matrix (K(0,0), K(1,1), K(0,2), K(1,2)) and an optional 4x4 depthExtrinsics."""
+    return _camera(IcpDepthCamera, K, width, height, extrinsics)
 
 
 class IcpRobustOptions(C.Structure):
@@ -235,12 +239,7 @@ class IcpColorCamera(C.Structure):
 
 def color_camera(K, width, height, extrinsics=None):
     """icp_color_camera: colour intrinsics (K(0,0), K(1,1), K(0,2), K(1,2)), the RGBX frame's size and optional 4x4 colour extrinsics."""
-    K = np.asarray(K, dtype=np.float32)
-    cam = IcpColorCamera(float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), int(width), int(height))
-    E = pose_to_c(np.eye(4) if extrinsics is None else extrinsics)
-    for k in range(16):
-        cam.extrinsics[k] = float(E[k])
-    return cam
+    return _camera(IcpColorCamera, K, width, height, extrinsics)
 
 
 def depth_options(keep_original_size=False, downsample_factor=1, max_distance=0.1, fix_color_index=False):
@@ -286,6 +285,7 @@ def load_library():
         _lib.icp_comm_last_error.restype = C.c_char_p
         _lib.icp_pair_owner.restype = C.c_int32
         _lib.icp_pairs_of_rank.restype = C.c_int32
+        _lib.icp_select_hash.restype = C.c_uint32
     return _lib
 
 
@@ -306,6 +306,38 @@ def pose_from_c(buf):
     return np.array(buf, dtype=np.float32).reshape(4, 4).T.copy()
 
 
+def _record(s):
+    """One record struct as a dict, keys in the order of _fields_: a 16-float `pose` as a 4x4, `x` as a float64 array, `converged` as a bool."""
+    convert = {"pose": pose_from_c, "x": lambda v: np.array(v[:], np.float64), "converged": bool}
+    return {k: convert[k](getattr(s, k)) if k in convert else getattr(s, k) for k, _ in s._fields_}
+
+
+def _depth_in(depth, cam, sequence=False):
+    """The depth frame (or the (n, h, w) frames) as contiguous fp32, checked against the camera's size."""
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    if sequence and d.size != d.shape[0] * cam.width * cam.height:
+        raise ValueError("depth frames do not match the camera size")
+    if not sequence and d.size != cam.width * cam.height:
+        raise ValueError("depth frame has %d pixels, the camera %d x %d" % (d.size, cam.width, cam.height))
+    return d
+
+
+def _rgbx_in(rgbx, n_pixels, message="colour frame must hold 4 bytes per pixel"):
+    """The RGBX frame(s) as contiguous bytes, four per pixel, or None."""
+    c = None if rgbx is None else np.ascontiguousarray(rgbx, dtype=np.uint8)
+    if c is not None and c.size != 4 * n_pixels:
+        raise ValueError(message)
+    return c
+
+
+def _gt_in(gt, nf):
+    """The tracking calls' ground truth: (nf - 1) 4x4 transforms as column-major rows, or None."""
+    g = None if gt is None else np.ascontiguousarray(np.stack([pose_to_c(T) for T in gt]) if len(gt) else np.zeros((0, 16)), dtype=np.float32)
+    if g is not None and len(g) != nf - 1:
+        raise ValueError("gt needs one transform per tracked frame")
+    return g
+
+
 def schedule(params, n_src, max_out=4096):
     """icp_schedule: decimation factor per iteration (host logic only, needs no GPU)."""
     lib = load_library()
@@ -317,8 +349,7 @@ def schedule(params, n_src, max_out=4096):
 
 
 def select_hash(seed, iteration, index):
-    lib = load_library(); lib.icp_select_hash.restype = C.c_uint32
-    return int(lib.icp_select_hash(C.c_uint32(seed), C.c_uint32(iteration), C.c_uint32(index)))
+    return int(load_library().icp_select_hash(C.c_uint32(seed), C.c_uint32(iteration), C.c_uint32(index)))
 
 
 def default_params():
@@ -355,6 +386,20 @@ class Context:
         if rc != ICP_OK:
             raise IcpError(rc, self.lib.icp_last_error(self.h).decode())
 
+    def _counted(self, fn, lead, make, n_out=1):
+        """A count-then-fill getter: fn(h, *lead, None..., 0, &n) reports the count, make(n) gives the output buffer (a tuple of n_out
+        of them when n_out > 1), fn(h, *lead, buffers..., n, &n) fills them.  Returns what make gave."""
+        n = C.c_int32(0)
+        self._ck(fn(self.h, *lead, *([None] * n_out), C.c_int32(0), C.byref(n)))
+        out = make(n.value)
+        bufs = out if n_out > 1 else (out,)
+        self._ck(fn(self.h, *lead, *[_ptr(b) if isinstance(b, np.ndarray) else b for b in bufs], C.c_int32(n.value), C.byref(n)))
+        return out
+
+    def _records(self, fn, struct):
+        """A count-then-fill getter of record structs: one dict per record."""
+        return [_record(b) for b in self._counted(fn, (), lambda n: (struct * n)())]
+
     def set_optimizer(self, options=True, **kw):
         """icp_set_optimizer: options True (the defaults, fields overridden by kw) or an IcpLmOptions selects the non-linear optimiser
         (CeresICPOptimizer); None / False return to the linear one."""
@@ -376,15 +421,7 @@ class Context:
 
     def lm_summaries(self):
         """icp_get_lm_summaries: one dict per ICP iteration of the last run (Solver::Summary of its ceres::Solve), all of them."""
-        n = C.c_int32(0)
-        self._ck(self.lib.icp_get_lm_summaries(self.h, None, C.c_int32(0), C.byref(n)))
-        buf = (IcpLmSummary * max(n.value, 1))()
-        self._ck(self.lib.icp_get_lm_summaries(self.h, buf, C.c_int32(n.value), C.byref(n)))
-        return [dict(iterations=b.iterations, successful_steps=b.successful_steps, unsuccessful_steps=b.unsuccessful_steps,
-                     invalid_steps=b.invalid_steps, termination=b.termination, n_residual_blocks=b.n_residual_blocks,
-                     accepted_steps_mask=b.accepted_steps_mask, invalid_steps_mask=b.invalid_steps_mask,
-                     initial_cost=b.initial_cost, final_cost=b.final_cost, trust_region_radius=b.trust_region_radius, x=np.array(b.x[:], np.float64))
-                for b in buf[:n.value]]
+        return self._records(self.lib.icp_get_lm_summaries, IcpLmSummary)
 
     def set_gicp_options(self, epsilon=1e-3, k=20):
         """icp_set_gicp_options: the plane-to-plane regulariser and the neighbours of the GICP normals (0: the clouds' own normals)."""
@@ -400,11 +437,7 @@ class Context:
     def gicp_normals(self, which="target"):
         """icp_get_gicp_normals: the per-point GICP normals of the target or the source, n x 3 fp32 in the cloud's order (NaN where undefined)."""
         w = {"target": 0, "source": 1}[which]
-        n = C.c_int32(0)
-        self._ck(self.lib.icp_get_gicp_normals(self.h, C.c_int32(w), None, C.c_int32(0), C.byref(n)))
-        out = np.empty((n.value, 3), np.float32)
-        self._ck(self.lib.icp_get_gicp_normals(self.h, C.c_int32(w), _ptr(out), C.c_int32(n.value), C.byref(n)))
-        return out
+        return self._counted(self.lib.icp_get_gicp_normals, (C.c_int32(w),), lambda n: np.empty((n, 3), np.float32))
 
     def set_colored_options(self, lambda_geometric=0.968, k=20):
         """icp_set_colored_options: the weight of the geometric term and the neighbours of the target's colour gradients."""
@@ -419,11 +452,7 @@ class Context:
 
     def color_gradients(self):
         """icp_get_color_gradients: the target's per-point colour gradients, n x 3 fp32 in the cloud's order (NaN where undefined)."""
-        n = C.c_int32(0)
-        self._ck(self.lib.icp_get_color_gradients(self.h, None, C.c_int32(0), C.byref(n)))
-        out = np.empty((n.value, 3), np.float32)
-        self._ck(self.lib.icp_get_color_gradients(self.h, _ptr(out), C.c_int32(n.value), C.byref(n)))
-        return out
+        return self._counted(self.lib.icp_get_color_gradients, (), lambda n: np.empty((n, 3), np.float32))
 
     def set_robust_options(self, kernel="none", tuning=0.0, sigma=0.0, overlap=1.0):
         """icp_set_robust_options: trimmed ICP (overlap < 1) and an M-estimator ("none", "huber", "cauchy", "tukey" or ICP_ROBUST_*) with
@@ -440,11 +469,7 @@ class Context:
 
     def robust_stats(self):
         """icp_get_robust_stats: one dict per ICP iteration of the last icp_iterate / icp_run / icp_correspond (none when robust mode was off)."""
-        n = C.c_int32(0)
-        self._ck(self.lib.icp_get_robust_stats(self.h, None, C.c_int32(0), C.byref(n)))
-        buf = (IcpRobustStats * max(n.value, 1))()
-        self._ck(self.lib.icp_get_robust_stats(self.h, buf, C.c_int32(n.value), C.byref(n)))
-        return [dict(n_entering=b.n_entering, n_kept=b.n_kept, trim_d2=b.trim_d2, sigma=b.sigma) for b in buf[:n.value]]
+        return self._records(self.lib.icp_get_robust_stats, IcpRobustStats)
 
     def set_reciprocal_options(self, enabled=True):
         """icp_set_reciprocal_options: reciprocal (mutual nearest-neighbour) rejection: a pair (s, t) is kept only if s is also the nearest
@@ -460,11 +485,7 @@ class Context:
 
     def reciprocal_stats(self):
         """icp_get_reciprocal_stats: one dict per ICP iteration of the last icp_iterate / icp_run / icp_correspond (none when the option was off)."""
-        n = C.c_int32(0)
-        self._ck(self.lib.icp_get_reciprocal_stats(self.h, None, C.c_int32(0), C.byref(n)))
-        buf = (IcpReciprocalStats * max(n.value, 1))()
-        self._ck(self.lib.icp_get_reciprocal_stats(self.h, buf, C.c_int32(n.value), C.byref(n)))
-        return [dict(n_matched=b.n_matched, n_mutual=b.n_mutual) for b in buf[:n.value]]
+        return self._records(self.lib.icp_get_reciprocal_stats, IcpReciprocalStats)
 
     def set_convergence_options(self, rotation=None, translation=None, min_iterations=1, patience=1):
         """icp_set_convergence_options: stop run / batch_run / track_depth_frames on the device once `patience` consecutive eligible
@@ -489,15 +510,11 @@ class Context:
         translation) of the last iteration that ran (-1 with the option off)."""
         r = IcpConvergenceResult()
         self._ck(self.lib.icp_get_convergence(self.h, C.byref(r)))
-        return dict(converged=bool(r.converged), iterations_run=r.iterations_run, iterations_planned=r.iterations_planned, rotation=r.rotation, translation=r.translation)
+        return _record(r)
 
     def convergence_trace(self):
         """icp_get_convergence_trace: one (rotation, translation, eligible, streak) record per iteration that ran (none with the option off)."""
-        n = C.c_int32(0)
-        self._ck(self.lib.icp_get_convergence_trace(self.h, None, C.c_int32(0), C.byref(n)))
-        out = np.zeros(n.value, CONVERGENCE_STEP_DTYPE)
-        self._ck(self.lib.icp_get_convergence_trace(self.h, _ptr(out), C.c_int32(n.value), C.byref(n)))
-        return out
+        return self._counted(self.lib.icp_get_convergence_trace, (), lambda n: np.zeros(n, CONVERGENCE_STEP_DTYPE))
 
     def set_nss_options(self, grid=5, resample=True):
         """icp_set_nss_options: normal-space sampling (params.selection = SELECT_NORMAL_SPACE): cells per cube-face edge (3, 5 or 7) and
@@ -513,19 +530,11 @@ class Context:
 
     def normal_buckets(self):
         """icp_get_normal_buckets: the normal-space bucket of every source point, uint16 in the cloud's order (0xFFFF: none)."""
-        n = C.c_int32(0)
-        self._ck(self.lib.icp_get_normal_buckets(self.h, None, C.c_int32(0), C.byref(n)))
-        out = np.empty(n.value, np.uint16)
-        self._ck(self.lib.icp_get_normal_buckets(self.h, _ptr(out), C.c_int32(n.value), C.byref(n)))
-        return out
+        return self._counted(self.lib.icp_get_normal_buckets, (), lambda n: np.empty(n, np.uint16))
 
     def selection(self, iteration):
         """icp_get_selection: the query set (original source indices, increasing) of one iteration of the last run with selection 1 or 2."""
-        n = C.c_int32(0)
-        self._ck(self.lib.icp_get_selection(self.h, C.c_int32(iteration), None, C.c_int32(0), C.byref(n)))
-        out = np.empty(n.value, np.int32)
-        self._ck(self.lib.icp_get_selection(self.h, C.c_int32(iteration), _ptr(out), C.c_int32(n.value), C.byref(n)))
-        return out
+        return self._counted(self.lib.icp_get_selection, (C.c_int32(iteration),), lambda n: np.empty(n, np.int32))
 
     def set_global_options(self, **kw):
         """icp_set_global_options: global registration (FPFH features, feature matching, RANSAC).  Keywords: k (5, 10, 20), feature_stride,
@@ -550,28 +559,18 @@ class Context:
 
     def features(self, which="source"):
         """icp_get_features: the FPFH rows of the keypoints, (n_keypoints, 33) float32; row r is point r * feature_stride, NaN rows: no feature."""
-        w = C.c_int32(_cloud(which)); n = C.c_int32(0)
-        self._ck(self.lib.icp_get_features(self.h, w, None, C.c_int32(0), C.byref(n)))
-        out = np.empty((n.value, FPFH_DIM), np.float32)
-        self._ck(self.lib.icp_get_features(self.h, w, _ptr(out), C.c_int32(n.value), C.byref(n)))
-        return out
+        return self._counted(self.lib.icp_get_features, (C.c_int32(_cloud(which)),), lambda n: np.empty((n, FPFH_DIM), np.float32))
 
     def spfh(self, which="source"):
         """icp_get_spfh: (counts (n, 33) uint8, pairs (n,) int32) of every point."""
-        w = C.c_int32(_cloud(which)); n = C.c_int32(0)
-        self._ck(self.lib.icp_get_spfh(self.h, w, None, None, C.c_int32(0), C.byref(n)))
-        counts = np.empty((n.value, FPFH_DIM), np.uint8); pairs = np.empty(n.value, np.int32)
-        self._ck(self.lib.icp_get_spfh(self.h, w, _ptr(counts), _ptr(pairs), C.c_int32(n.value), C.byref(n)))
-        return counts, pairs
+        return self._counted(self.lib.icp_get_spfh, (C.c_int32(_cloud(which)),),
+                             lambda n: (np.empty((n, FPFH_DIM), np.uint8), np.empty(n, np.int32)), n_out=2)
 
     def feature_neighbours(self, which="source"):
         """icp_get_feature_neighbours: (idx (n, k) int32, d2 (n, k) float32), ascending (d2, index) per point; unfilled slots (-1, inf)."""
-        w = C.c_int32(_cloud(which)); n = C.c_int32(0)
         k = self.global_options().k
-        self._ck(self.lib.icp_get_feature_neighbours(self.h, w, None, None, C.c_int32(0), C.byref(n)))
-        idx = np.empty((n.value, k), np.int32); d2 = np.empty((n.value, k), np.float32)
-        self._ck(self.lib.icp_get_feature_neighbours(self.h, w, _ptr(idx), _ptr(d2), C.c_int32(n.value), C.byref(n)))
-        return idx, d2
+        return self._counted(self.lib.icp_get_feature_neighbours, (C.c_int32(_cloud(which)),),
+                             lambda n: (np.empty((n, k), np.int32), np.empty((n, k), np.float32)), n_out=2)
 
     def match_features(self):
         """icp_match_features: (src_idx, tgt_idx) int32 arrays of the feature correspondences, ascending in src_idx."""
@@ -601,11 +600,7 @@ class Context:
 
     def global_hypotheses(self):
         """icp_get_global_hypotheses: every hypothesis of the last register_global, in order of h (GLOBAL_HYPOTHESIS_DTYPE)."""
-        n = C.c_int32(0)
-        self._ck(self.lib.icp_get_global_hypotheses(self.h, None, C.c_int32(0), C.byref(n)))
-        out = np.zeros(n.value, GLOBAL_HYPOTHESIS_DTYPE)
-        self._ck(self.lib.icp_get_global_hypotheses(self.h, _ptr(out), C.c_int32(n.value), C.byref(n)))
-        return out
+        return self._counted(self.lib.icp_get_global_hypotheses, (), lambda n: np.zeros(n, GLOBAL_HYPOTHESIS_DTYPE))
 
     def push_params(self):
         self._ck(self.lib.icp_set_params(self.h, C.byref(self.params)))
@@ -658,16 +653,14 @@ class Context:
     def iterate(self, pose):
         p = pose_to_c(pose); st = IcpIterStats()
         self._ck(self.lib.icp_iterate(self.h, _ptr(p), C.byref(st)))
-        return pose_from_c(p), dict(n_src=st.n_src, n_valid=st.n_valid, pose=pose_from_c(st.pose), rmse=st.rmse, benchmark_error=st.benchmark_error, status=st.status)
+        return pose_from_c(p), _record(st)
 
     def run(self, pose, max_stats=512, check=True):
         p = pose_to_c(pose); st = (IcpIterStats * max_stats)(); n = C.c_int32(0)
         rc = self.lib.icp_run(self.h, _ptr(p), st, C.c_int32(max_stats), C.byref(n))
         if check:
             self._ck(rc)
-        recs = [dict(n_src=st[i].n_src, n_valid=st[i].n_valid, pose=pose_from_c(st[i].pose), rmse=st[i].rmse, benchmark_error=st[i].benchmark_error, status=st[i].status)
-                for i in range(min(n.value, max_stats))]
-        return pose_from_c(p), recs, rc
+        return pose_from_c(p), [_record(st[i]) for i in range(min(n.value, max_stats))], rc
 
     def run_multistart(self, poses, max_stats=512):
         """icp_run_multistart: ICP from every pose of `poses` (K x 4 x 4) at once.  Returns (results, stats, best): one dict per start
@@ -678,10 +671,8 @@ class Context:
         ps = np.ascontiguousarray(np.stack([pose_to_c(p) for p in poses]) if K else np.zeros((0, 16)), dtype=np.float32)
         res = (IcpStartResult * max(K, 1))(); st = (IcpIterStats * max(K * max_stats, 1))(); n = C.c_int32(0); best = C.c_int32(-1)
         self._ck(self.lib.icp_run_multistart(self.h, _ptr(ps) if K else None, C.c_int32(K), res, st, C.c_int32(max_stats), C.byref(n), C.byref(best)))
-        results = [dict(pose=pose_from_c(r.pose), status=r.status, n_inliers=r.n_inliers, fitness=r.fitness, inlier_rmse=r.inlier_rmse) for r in res[:K]]
-        stats = [[dict(n_src=r.n_src, n_valid=r.n_valid, pose=pose_from_c(r.pose), rmse=r.rmse, benchmark_error=r.benchmark_error, status=r.status)
-                  for r in st[k * max_stats:k * max_stats + min(n.value, max_stats)]] for k in range(K)]
-        return results, stats, best.value
+        stats = [[_record(r) for r in st[k * max_stats:k * max_stats + min(n.value, max_stats)]] for k in range(K)]
+        return [_record(r) for r in res[:K]], stats, best.value
 
     def run_raw(self, pose_c16):
         """Timed-loop entry for bench.py: pose buffer in/out (column-major float32[16]), no record marshalling."""
@@ -692,8 +683,7 @@ class Context:
     def timing(self):
         t = IcpTiming()
         self._ck(self.lib.icp_get_timing(self.h, C.byref(t)))
-        return dict(match_ms=t.match_ms, weight_reject_build_ms=t.weight_reject_build_ms, solve_ms=t.solve_ms,
-                    total_ms=t.total_ms, iterations=t.iterations, sampled_iterations=t.sampled_iterations)
+        return _record(t)
 
     def iteration_times(self, max_out=4096):
         """Per-iteration (match, weight/reject/build, solve) device milliseconds of the last run; -1 = iteration not bracketed."""
@@ -733,12 +723,8 @@ class Context:
         return xyz, nrm, rgba, valid.astype(bool)
 
     def _set_depth(self, fn, depth, rgbx, cam, opt, check):
-        depth = np.ascontiguousarray(depth, dtype=np.float32)
-        if depth.size != cam.width * cam.height:
-            raise ValueError("depth frame has %d pixels, the camera %d x %d" % (depth.size, cam.width, cam.height))
-        rgbx = None if rgbx is None else np.ascontiguousarray(rgbx, dtype=np.uint8)
-        if rgbx is not None and rgbx.size != 4 * depth.size:
-            raise ValueError("colour frame must hold 4 bytes per pixel")
+        depth = _depth_in(depth, cam)
+        rgbx = _rgbx_in(rgbx, depth.size)
         n = C.c_int32(0)
         rc = fn(self.h, _ptr(depth), _ptr(rgbx), C.byref(cam), C.byref(opt), C.byref(n))
         if check:
@@ -762,37 +748,25 @@ class Context:
         """icp_track_depth_frames: reconstructRoom's tracking loop (main.cpp:183-341) over frames (n, h, w) [+ colours (n, h*w, 4)].
         gt: (n - 1) 4x4 transforms frame k -> frame 0, or None.  pose: initial currentCameraToWorld (identity by default).
         Returns (final pose, list of per-frame records for frames 1 .. n-1, status)."""
-        d = np.ascontiguousarray(depth_frames, dtype=np.float32)
+        d = _depth_in(depth_frames, cam, sequence=True)
         nf = d.shape[0]
-        if d.size != nf * cam.width * cam.height:
-            raise ValueError("depth frames do not match the camera size")
-        cols = None if rgbx_frames is None else np.ascontiguousarray(rgbx_frames, dtype=np.uint8)
-        if cols is not None and cols.size != 4 * d.size:
-            raise ValueError("colour frames must hold 4 bytes per pixel")
-        g = None if gt is None else np.ascontiguousarray(np.stack([pose_to_c(T) for T in gt]) if len(gt) else np.zeros((0, 16)), dtype=np.float32)
-        if g is not None and len(g) != nf - 1:
-            raise ValueError("gt needs one transform per tracked frame")
+        cols = _rgbx_in(rgbx_frames, d.size, "colour frames must hold 4 bytes per pixel")
+        g = _gt_in(gt, nf)
         p = pose_to_c(np.eye(4) if pose is None else pose)
         out = (IcpTrackFrame * max(nf - 1, 1))()
         rc = self.lib.icp_track_depth_frames(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(target_opt), C.byref(source_opt),
                                              _ptr(g), _ptr(p), out)
         if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
             self._ck(rc)
-        recs = [dict(n_src=out[i].n_src, iterations=out[i].iterations, status=out[i].status, initial_rmse=out[i].initial_rmse,
-                     final_rmse=out[i].final_rmse, pose=pose_from_c(out[i].pose)) for i in range(nf - 1)]
-        return pose_from_c(p), recs, rc
+        return pose_from_c(p), [_record(out[i]) for i in range(nf - 1)], rc
 
     def depth_mesh(self, depth, rgbx, cam, camera_pose, edge_threshold=0.01, color_cam=None):
         """icp_depth_mesh: SimpleMesh(sensor, cameraPose, edgeThreshold) (SimpleMesh.h:36-119) on the device.  depth: the frame of `cam`;
         rgbx: the RGBX colour frame (color_cam's size, or the depth frame's when color_cam is None), or None for no colours;
         camera_pose: 4x4 world -> camera.  Returns (vertices (w*h, 3) f32, colours (w*h, 4) u8 or None, triangles (T, 3) u32)."""
-        depth = np.ascontiguousarray(depth, dtype=np.float32)
-        if depth.size != cam.width * cam.height:
-            raise ValueError("depth frame has %d pixels, the camera %d x %d" % (depth.size, cam.width, cam.height))
+        depth = _depth_in(depth, cam)
         n_color = (color_cam.width * color_cam.height) if color_cam is not None else depth.size
-        rgbx = None if rgbx is None else np.ascontiguousarray(rgbx, dtype=np.uint8)
-        if rgbx is not None and rgbx.size != 4 * n_color:
-            raise ValueError("colour frame must hold 4 bytes per pixel of the colour camera")
+        rgbx = _rgbx_in(rgbx, n_color, "colour frame must hold 4 bytes per pixel of the colour camera")
         n = depth.size
         verts = np.empty((n, 3), np.float32)
         cols = np.empty((n, 4), np.uint8) if rgbx is not None else None
@@ -866,14 +840,10 @@ class Context:
         """icp_tsdf_integrate: fuses one depth frame, seen from `pose` (4x4 camera -> world), into the volume.  Returns the voxels written.
         rgbx (h*w x 4 bytes, the depth frame's size): icp_tsdf_integrate_color, the frame's colours into the colour array as well; returns
         (voxels written, voxels coloured)."""
-        depth = np.ascontiguousarray(depth, dtype=np.float32)
-        if depth.size != cam.width * cam.height:
-            raise ValueError("depth frame has %d pixels, the camera %d x %d" % (depth.size, cam.width, cam.height))
+        depth = _depth_in(depth, cam)
         n = C.c_int32(0)
         if rgbx is not None:
-            cols = np.ascontiguousarray(rgbx, dtype=np.uint8)
-            if cols.size != 4 * depth.size:
-                raise ValueError("colour frame must hold 4 bytes per pixel of the depth frame")
+            cols = _rgbx_in(rgbx, depth.size, "colour frame must hold 4 bytes per pixel of the depth frame")
             nc = C.c_int32(0)
             self._ck(self.lib.icp_tsdf_integrate_color(self.h, _ptr(depth), _ptr(cols), C.byref(cam), _ptr(pose_to_c(pose)), C.byref(n), C.byref(nc)))
             return n.value, nc.value
@@ -903,19 +873,17 @@ class Context:
         normals (V, 3) f32 pointing into free space, triangles (T, 3) u32, counter-clockwise seen from free space).
         colors: icp_tsdf_mesh_color; a fourth array, (V, 4) u8 RGBA per vertex (four zero bytes where the volume holds no colour)."""
         nv, nt = C.c_int32(0), C.c_int32(0)
-        mw = C.c_float(min_weight)
-        if colors:
-            self._ck(self.lib.icp_tsdf_mesh_color(self.h, mw, C.c_int32(0), C.c_int32(0), None, None, None, None, C.byref(nv), C.byref(nt)))
-            v = np.empty((nv.value, 3), np.float32); n = np.empty((nv.value, 3), np.float32); t = np.empty((nt.value, 3), np.uint32)
-            col = np.empty((nv.value, 4), np.uint8)
-            if nv.value or nt.value:
-                self._ck(self.lib.icp_tsdf_mesh_color(self.h, mw, C.c_int32(nv.value), C.c_int32(nt.value), _ptr(v), _ptr(n), _ptr(col), _ptr(t), C.byref(nv), C.byref(nt)))
-            return v, n, t, col
-        self._ck(self.lib.icp_tsdf_mesh(self.h, mw, C.c_int32(0), C.c_int32(0), None, None, None, C.byref(nv), C.byref(nt)))
+        fn = self.lib.icp_tsdf_mesh_color if colors else self.lib.icp_tsdf_mesh
+
+        def call(v, n, col, t):                             # the colour array sits between the normals and the triangles
+            bufs = [_ptr(v), _ptr(n)] + ([_ptr(col)] if colors else []) + [_ptr(t)]
+            self._ck(fn(self.h, C.c_float(min_weight), C.c_int32(nv.value), C.c_int32(nt.value), *bufs, C.byref(nv), C.byref(nt)))
+        call(None, None, None, None)
         v = np.empty((nv.value, 3), np.float32); n = np.empty((nv.value, 3), np.float32); t = np.empty((nt.value, 3), np.uint32)
+        col = np.empty((nv.value, 4), np.uint8)
         if nv.value or nt.value:
-            self._ck(self.lib.icp_tsdf_mesh(self.h, mw, C.c_int32(nv.value), C.c_int32(nt.value), _ptr(v), _ptr(n), _ptr(t), C.byref(nv), C.byref(nt)))
-        return v, n, t
+            call(v, n, col, t)
+        return (v, n, t, col) if colors else (v, n, t)
 
     def set_target_tsdf(self, cam, pose, check=True, color=False):
         """icp_set_target_tsdf: the ray-cast of the volume from `pose` as the target (organised, with normals).  Returns the number of hits
@@ -933,27 +901,19 @@ class Context:
         """icp_track_depth_model: frame-to-model tracking over frames (n, h, w) against the context's TSDF volume.  gt: (n - 1) 4x4 transforms
         frame k -> world, or None.  pose: the camera -> world pose of frame 0 (identity by default).  Returns (final pose, records, status).
         rgbx_frames (n, h*w, 4): icp_track_depth_model_color, the coloured model (needs the colour array and source_opt.fix_color_index)."""
-        d = np.ascontiguousarray(depth_frames, dtype=np.float32)
+        d = _depth_in(depth_frames, cam, sequence=True)
         nf = d.shape[0]
-        if d.size != nf * cam.width * cam.height:
-            raise ValueError("depth frames do not match the camera size")
-        g = None if gt is None else np.ascontiguousarray(np.stack([pose_to_c(T) for T in gt]) if len(gt) else np.zeros((0, 16)), dtype=np.float32)
-        if g is not None and len(g) != nf - 1:
-            raise ValueError("gt needs one transform per tracked frame")
+        g = _gt_in(gt, nf)
         p = pose_to_c(np.eye(4) if pose is None else pose)
         out = (IcpTrackFrame * max(nf - 1, 1))()
         if rgbx_frames is not None:
-            cols = np.ascontiguousarray(rgbx_frames, dtype=np.uint8)
-            if cols.size != 4 * d.size:
-                raise ValueError("colour frames must hold 4 bytes per pixel")
+            cols = _rgbx_in(rgbx_frames, d.size, "colour frames must hold 4 bytes per pixel")
             rc = self.lib.icp_track_depth_model_color(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
         else:
             rc = self.lib.icp_track_depth_model(self.h, _ptr(d), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
         if rc not in (ICP_OK, ERR_NO_TARGET, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
             self._ck(rc)
-        recs = [dict(n_src=out[i].n_src, iterations=out[i].iterations, status=out[i].status, initial_rmse=out[i].initial_rmse,
-                     final_rmse=out[i].final_rmse, pose=pose_from_c(out[i].pose)) for i in range(nf - 1)]
-        return pose_from_c(p), recs, rc
+        return pose_from_c(p), [_record(out[i]) for i in range(nf - 1)], rc
 
     def estimate_normals(self, xyz, k=5, viewpoint=(0.0, 0.0, 0.0)):
         """PointCloud(pcl cloud): k-NN PCA normals flipped towards the viewpoint (PointCloud.h:41-76)."""

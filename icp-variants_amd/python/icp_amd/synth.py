@@ -216,10 +216,59 @@ def rgbd_pair(k=0, width=640, height=480, K=None, seed=0x7A11, hole_frac=0.05):
                 K=K.astype(np.float32), width=width, height=height)
 
 
+def tum_K(width):
+    """The TUM intrinsics (VirtualSensor.h:44-46) scaled to a smaller image of the same aspect."""
+    s = width / 640.0
+    return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], np.float32)
+
+
+def camera_sequence(n, width, height, seed=0x7A11, hole_frac=0.05):
+    """n organised frames of the hand-held camera at tum_K(width): (K, depth (n, H, W) with MINF holes, rgbx (n, W*H, 4) bytes,
+    gt: the n - 1 fp32 transforms frame k -> frame 0)."""
+    K = tum_K(width)
+    T = [camera_pose(k, seed) for k in range(n)]
+    made = [depth_frame(Tk, K.astype(np.float64), width, height, seed + k, hole_frac) for k, Tk in enumerate(T)]
+    depth = np.stack([m[0][:, 2].reshape(height, width).copy() for m in made])
+    gt = [(np.linalg.inv(T[0]) @ Tk).astype(np.float32) for Tk in T[1:]]
+    return K, depth, np.stack([m[2] for m in made]), gt
+
+
+def wavy_depth(W, H, base=1.5):
+    """A smooth depth image with a step: a surface that takes every branch of a TSDF band."""
+    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    return (base + 0.3 * np.sin(u * 0.3) + 0.2 * np.cos(v * 0.4) + 0.5 * (u > 0.7 * W)).astype(np.float32)
+
+
 def compact_valid(pts, nrm, rgba):
     """keepOriginalSize=false filtering of PointCloud(depth...) (PointCloud.h:148-163): drop invalid pixels."""
     ok = np.isfinite(pts).all(axis=1) & np.isfinite(nrm).all(axis=1)
     return pts[ok], nrm[ok], rgba[ok]
+
+
+def compact_rgbd_pair(k=0):
+    """rgbd_pair k at 80 x 60 (the TUM intrinsics / 8) with the holes dropped from both clouds: the pair's dict, plus `organised` (the
+    rgbd_pair itself) and `K`."""
+    K = np.array([[525.0 / 8, 0, 319.5 / 8], [0, 525.0 / 8, 239.5 / 8], [0, 0, 1]])
+    d = rgbd_pair(k, width=80, height=60, K=K)
+    tp, tn, tc = compact_valid(d["tgt_pts"], d["tgt_nrm"], d["tgt_rgba"])
+    sp, sn, sc = compact_valid(d["src_pts"], d["src_nrm"], d["src_rgba"])
+    return dict(src_pts=sp, src_nrm=sn, src_rgba=sc, tgt_pts=tp, tgt_nrm=tn, tgt_rgba=tc, gt=d["gt"], organised=d, K=K)
+
+
+def partial_overlap_pair(k, n_tilt, n_beam, quantile, drop_target_normals):
+    """eth_like_pair k whose target loses every point beyond the `quantile` of the unperturbed source's x, so that share of the source
+    has no counterpart.  Source points with a non-finite coordinate or normal are dropped; target points with a non-finite coordinate
+    too, and with drop_target_normals those with a non-finite normal."""
+    d = eth_like_pair(k, n_tilt=n_tilt, n_beam=n_beam)
+    su = np.asarray(d["src_unperturbed"], np.float64)
+    thr = np.quantile(su[np.isfinite(su).all(1), 0], quantile)
+    tp, tn = np.asarray(d["tgt_pts"]), np.asarray(d["tgt_nrm"])
+    keep = np.isfinite(tp).all(1) & (tp[:, 0] <= thr)
+    if drop_target_normals:
+        keep &= np.isfinite(tn).all(1)
+    sp, sn = np.asarray(d["src_pts"], np.float32), np.asarray(d["src_nrm"], np.float32)
+    ok = np.isfinite(sp).all(1) & np.isfinite(sn).all(1)
+    return dict(src_pts=sp[ok], src_nrm=sn[ok], tgt_pts=tp[keep].astype(np.float32), tgt_nrm=tn[keep].astype(np.float32), gt=d["gt"])
 
 
 def incised_plane(n_grid=160, groove_x=0.37, groove_y=0.61, width=0.02, depth=0.01, sigma=0.0005, normal_sigma=0.02,

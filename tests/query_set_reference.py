@@ -58,11 +58,8 @@ def shuffled(d, seed=5):
 def rgbd_pair():
     """The 80 x 60 synthetic RGB-D pair of tests/test_gpu_colored.py, compacted to its valid points."""
     from icp_amd import synth
-    K = np.array([[525.0 / 8, 0, 319.5 / 8], [0, 525.0 / 8, 239.5 / 8], [0, 0, 1]])
-    d = synth.rgbd_pair(0, width=80, height=60, K=K)
-    tp, tn, tc = synth.compact_valid(d["tgt_pts"], d["tgt_nrm"], d["tgt_rgba"])
-    sp, sn, sc = synth.compact_valid(d["src_pts"], d["src_nrm"], d["src_rgba"])
-    return dict(src_pts=sp, src_nrm=sn, src_rgba=sc, tgt_pts=tp, tgt_nrm=tn, tgt_rgba=tc)
+    d = synth.compact_rgbd_pair()
+    return {k: d[k] for k in ("src_pts", "src_nrm", "src_rgba", "tgt_pts", "tgt_nrm", "tgt_rgba")}
 
 
 def step_options(cfg, **extra):

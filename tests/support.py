@@ -1,0 +1,214 @@
+"""Helpers that are about testing, shared by the test modules (`import support as S`): bit views, the params / cloud plumbing of a
+context, and the checks one test module used to import from another.  Data generators live in icp_amd/synth.py, CPU specifications in
+the *_restatement.py modules; fixtures stay with the module that uses them."""
+import ctypes as C
+import os
+import numpy as np
+
+f32 = np.float32
+LBVH = 1
+POSE_TOL = 1e-5        # north_star: 1e-5 rad / 1e-5 m
+FORMS = ("merged", "separate")
+NRM_TOL = 2e-6
+CURV_TOL = 2e-6
+GAP_REL = 1e-9
+
+
+def bits(a):
+    """The contiguous fp32 cast of `a`, viewed as uint32."""
+    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
+
+
+def u32(a):
+    """`a` as it is (no cast), contiguous, viewed as uint32."""
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def raw_bits(a):
+    """A float32 array viewed as uint32; an array of any other type as it is."""
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def same_bits(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
+def pose_of(angles, t):
+    from icp_amd import synth
+    return synth.make_pose(angles, t).astype(f32)
+
+
+def rand_pose(seed, ang=0.1, tr=0.2):
+    r = np.random.default_rng(seed)
+    return pose_of(r.uniform(-ang, ang, 3), r.uniform(-tr, tr, 3))
+
+
+def configure(ctx, metric=1, weighting=0, rejection=1, color_icp=0, knn_backend=1, n_iterations=10, multires=0, selection=0, proba=1.0,
+              max_distance=0.0003, matching=0, seed=7, K=None, width=0, height=0, **kw):
+    """Sets these fields of ctx.params, then any other field given by name, then the camera fields where projective matching comes with a
+    K (a caller that leaves K out sets them itself), and pushes them."""
+    p = ctx.params
+    p.metric, p.weighting, p.rejection, p.color_icp, p.knn_backend, p.n_iterations = metric, weighting, rejection, color_icp, knn_backend, n_iterations
+    p.multires, p.selection, p.selection_proba, p.selection_seed, p.max_distance, p.matching = multires, selection, proba, seed, max_distance, matching
+    for k, v in kw.items():
+        setattr(p, k, v)
+    if matching == 1 and K is not None:
+        p.fx, p.fy, p.cx, p.cy, p.width, p.height = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), width, height
+    ctx.push_params()
+
+
+def load(ctx, d, colors=True):
+    ctx.set_target(d["tgt_pts"], d["tgt_nrm"], d.get("tgt_rgba") if colors else None)
+    ctx.set_source(d["src_pts"], d["src_nrm"], d.get("src_rgba") if colors else None)
+
+
+def upload(ctx, vol, color=False):
+    """A restatement's volume (tsdf_restatement.Volume, with tsdf_color_restatement's arrays when color) into the context's."""
+    ctx.tsdf_create(color=color, dims=(vol.nx, vol.ny, vol.nz), origin=tuple(float(x) for x in vol.o), voxel_size=float(vol.s))
+    ctx.tsdf_upload(vol.tsdf, vol.weight)
+    if color:
+        ctx.tsdf_color_upload(vol.rgb, vol.wc)
+
+
+def loaded_ctx(factory, tgt, src, **params):
+    """A context with `params` set by name and the (points, normals, colours) triples resident; src may be None."""
+    c = factory()
+    for k, v in params.items():
+        setattr(c.params, k, v)
+    c.push_params()
+    c.set_target(*tgt)
+    if src is not None:
+        c.set_source(*src)
+    return c
+
+
+def make_ctx(factory, form, **params):
+    """A context whose point-to-plane loop takes `form` ("merged" / True, "separate" / False), on the LBVH backend."""
+    if form is True:
+        form = "merged"
+    elif form is False:
+        form = "separate"
+    env = {"ICP_HIP_MERGE": "0" if form == "separate" else "1"}                                              # read once, at icp_ctx_create
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        c = factory()
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+    c.params.knn_backend = LBVH; c.params.metric = 1
+    for k, v in params.items():
+        setattr(c.params, k, v)
+    c.push_params()
+    return c
+
+
+def counters(c):
+    a, b = C.c_int32(0), C.c_int32(0)
+    assert c.lib.icp_debug_counters(c.h, C.byref(a), C.byref(b)) == 0
+    return a.value, b.value
+
+
+def assert_same_run(ra, rb):
+    assert len(ra) == len(rb)
+    for k, (a, b) in enumerate(zip(ra, rb)):
+        assert a["n_valid"] == b["n_valid"] and a["status"] == b["status"] and a["n_src"] == b["n_src"], k
+        assert np.array_equal(a["pose"], b["pose"]), k
+
+
+def check_stats(dev, ref, label):
+    """One iteration's robust stats of the device against the restatement's: counts equal, trim_d2 and sigma bit-equal."""
+    assert dev["n_entering"] == ref["n_entering"] and dev["n_kept"] == ref["n_kept"], (label, dev, ref)
+    assert u32(f32(dev["trim_d2"])) == u32(f32(ref["trim_d2"])) and u32(f32(dev["sigma"])) == u32(f32(ref["sigma"])), (label, dev, ref)
+
+
+def restated_step(c, pair, metric, pose, opts=None):
+    """The non-linear restatement's Solve on the device's records at `pose` -> (x, summary, decisions, new pose)."""
+    import lm_restatement as lm
+    recs, _, _ = c.correspond(pose)
+    st = c.transform_points(pair["src_pts"], pose)
+    nt = c.transform_normals(pair["src_nrm"], pose)
+    b = lm.blocks(metric, st, nt, pair["tgt_pts"], pair["tgt_nrm"], recs)
+    x, summ, dec = lm.solve_blocks(b, opts)
+    newpose = pose if summ["termination"] == lm.NO_RESIDUALS else lm.compose(x, pose)
+    return x, summ, dec, newpose
+
+
+def check_normals(orc, pts, k, vp, nrm, curv, label=""):
+    """Asserts the device's (nrm, curv) against orc.estimate_normals on every point; returns the statistics."""
+    pts = np.ascontiguousarray(pts, f32); vp = np.asarray(vp, f32)
+    on, oc, nb = orc.estimate_normals(pts, k, vp, return_neighbours=True)
+    assert nrm.shape == on.shape and curv.shape == oc.shape
+    nan_n, nan_c = np.isnan(nrm), np.isnan(curv)
+    bad_nan = np.nonzero((nan_n != np.isnan(on)).any(1) | (nan_c != np.isnan(oc)))[0]
+    assert len(bad_nan) == 0, "%s: NaN pattern differs at %s: dev %s orc %s" % (label, bad_nan[:5], nrm[bad_nan[:5]], on[bad_nan[:5]])
+    fin = np.nonzero(~np.isnan(on).any(1))[0]
+    stats = dict(label=label, n=len(pts), n_normals=len(fin), worst_nrm=0.0, worst_curv=0.0, bit_identical=1.0, n_ambiguous=0)
+    if len(fin) == 0:
+        return stats
+    assert np.isfinite(nrm[fin]).all() and np.isfinite(curv[fin]).all()
+    # covariance of the oracle's neighbour sets (fp64; eigenvalues by LAPACK, independent of both Jacobis)
+    ids = nb[fin]; m = ids >= 0; cnt = m.sum(1)
+    X = np.where(m[..., None], pts[np.where(m, ids, 0)].astype(np.float64), 0.0)
+    D = (X - (X.sum(1) / cnt[:, None])[:, None, :]) * m[..., None]
+    C = np.einsum("nki,nkj->nij", D, D) / cnt[:, None, None]
+    w = np.linalg.eigvalsh(C)
+    lmax = w[:, 2]
+    amb = (lmax > 0) & (w[:, 1] - w[:, 0] <= GAP_REL * lmax)
+    nd, no = nrm[fin].astype(np.float64), on[fin].astype(np.float64)
+    dn = np.abs(nd - no).max(1)
+    dn[amb] = 0.0
+    dc = np.abs(curv[fin].astype(np.float64) - oc[fin])
+    stats.update(worst_nrm=float(dn.max()), worst_curv=float(dc.max()), n_ambiguous=int(amb.sum()),
+                 bit_identical=float((nrm[fin].view(np.uint32) == on[fin].view(np.uint32)).all(1).mean()))
+
+    def where(r, what):
+        i = fin[r]
+        return "%s: %s at point %d %s (%d-NN %s): dev n %s curv %r, oracle n %s curv %r, eig %s; %.6f of normals bit-identical" % (
+            label, what, i, pts[i], k, nb[i].tolist(), nrm[i], float(curv[i]), on[i], float(oc[i]), w[r], stats["bit_identical"])
+    r = int(np.argmax(dn))
+    assert dn[r] <= NRM_TOL, where(r, "|n_dev - n_orc| = %.3g" % dn[r])
+    r = int(np.argmax(dc))
+    assert dc[r] <= CURV_TOL, where(r, "|curv_dev - curv_orc| = %.3g" % dc[r])
+    if amb.any():
+        a = np.nonzero(amb)[0]
+        q = np.einsum("ni,nij,nj->n", nd[a], C[a], nd[a])
+        over = q - (w[a, 0] + GAP_REL * lmax[a])
+        r = int(np.argmax(over))
+        assert over[r] <= 0, where(a[r], "n^T C n above the near-null space by %.3g" % over[r])
+        ln = np.abs(np.linalg.norm(nd[a], axis=1) - 1)
+        r = int(np.argmax(ln))
+        assert ln[r] <= 1e-6, where(a[r], "| |n| - 1 | = %.3g" % ln[r])
+        e = (vp[None, :] - pts[fin[a]]).astype(np.float64)
+        flip = (e * nd[a]).sum(1) + 1e-6 * np.linalg.norm(e, axis=1)
+        r = int(np.argmin(flip))
+        assert flip[r] >= 0, where(a[r], "normal points away from the viewpoint")
+    return stats
+
+
+def assert_matches_icp_run(c, starts, max_stats=512):
+    """Every start of ONE multistart call against icp_run from that start on the same context: records and pose, bit for bit."""
+    res, stats, best = c.run_multistart(starts, max_stats=max_stats)
+    assert len(res) == len(starts)
+    for k, s in enumerate(starts):
+        pose, recs, rc = c.run(s, max_stats=max_stats, check=False)
+        assert res[k]["status"] == rc, k
+        assert np.array_equal(res[k]["pose"], pose), k
+        assert len(stats[k]) == len(recs), k
+        for i, (a, b) in enumerate(zip(stats[k], recs)):
+            assert (a["n_src"], a["n_valid"], a["status"]) == (b["n_src"], b["n_valid"], b["status"]), (k, i)
+            assert np.array_equal(a["pose"], b["pose"]), (k, i)
+            assert a["rmse"] == -1.0 and a["benchmark_error"] == -1.0
+    return res, stats, best
+
+
+def expected_best(res):
+    best = 0
+    for k, r in enumerate(res):
+        b = res[best]
+        if r["n_inliers"] > b["n_inliers"] or (r["n_inliers"] == b["n_inliers"] and r["inlier_rmse"] < b["inlier_rmse"]):
+            best = k
+    return best

@@ -2,38 +2,27 @@
 gradients on every point, teacher-forced sums on the device's own records, lambda = 1, free-running runs iteration by iteration, robust
 mode, the textured plane that geometry alone cannot align, the batch and tracking entry points, the refusals, and metrics 0-3 untouched
 by colored options on the same context."""
+import functools
 import numpy as np
 import pytest
 
 import colored_restatement as CR
+import support as S
 from conftest import pose_error
+from support import load
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 LAM = 0.968
 
 
-def configure(ctx, metric=4, weighting=0, rejection=1, color_icp=0, knn_backend=1, n_iterations=10, multires=0, selection=0, proba=1.0,
-              max_distance=0.01, matching=0):
-    p = ctx.params
-    p.metric, p.weighting, p.rejection, p.color_icp, p.knn_backend, p.n_iterations = metric, weighting, rejection, color_icp, knn_backend, n_iterations
-    p.multires, p.selection, p.selection_proba, p.selection_seed, p.max_distance, p.matching = multires, selection, proba, 7, max_distance, matching
-    ctx.push_params()
-
-
-def load(ctx, d):
-    ctx.set_target(d["tgt_pts"], d["tgt_nrm"], d["tgt_rgba"])
-    ctx.set_source(d["src_pts"], d["src_nrm"], d["src_rgba"])
+configure = functools.partial(S.configure, metric=4, max_distance=0.01)          # this file's defaults: the colored metric, 1 cm
 
 
 @pytest.fixture(scope="module")
 def depth_pair():
     from icp_amd import synth
-    K = np.array([[525.0 / 8, 0, 319.5 / 8], [0, 525.0 / 8, 239.5 / 8], [0, 0, 1]])
-    d = synth.rgbd_pair(0, width=80, height=60, K=K)
-    tp, tn, tc = synth.compact_valid(d["tgt_pts"], d["tgt_nrm"], d["tgt_rgba"])
-    sp, sn, sc = synth.compact_valid(d["src_pts"], d["src_nrm"], d["src_rgba"])
-    return dict(src_pts=sp, src_nrm=sn, src_rgba=sc, tgt_pts=tp, tgt_nrm=tn, tgt_rgba=tc, gt=d["gt"])
+    return synth.compact_rgbd_pair()
 
 
 @pytest.fixture(scope="module")

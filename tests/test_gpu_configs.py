@@ -166,7 +166,7 @@ def test_eth_files_to_pose_end_to_end(gpu_ctx_factory, orc, tmp_path):
     perturbation -> 50 point-to-plane iterations; checked against the oracle on the same prepared clouds."""
     from conftest import pose_error
     from icp_amd import eth, binding
-    from test_gpu_normals import check_normals
+    from support import check_normals
     written = _write_eth_dataset(tmp_path)
     rows = eth.load_rows(str(tmp_path), "apartment_global.csv")
     assert len(rows) == 2 and eth.dataset_name("apartment_global.csv") == "apartment" and eth.dataset_name("eth/plain_global.csv") == "eth/plain"

@@ -7,12 +7,13 @@ The bounds of a case are the geometric mean of two successive increments of its 
 that run lies within a factor 1.25 of either bound: rounding cannot decide the outcome.  Trace tolerance: the nine products of dR are
 exact in fp64, what differs between the device and numpy is at most the order of a few fp64 sums and the one fp32 rounding at the end:
 1e-6 relative (fp32 eps = 6e-8 and change), or 1e-12 absolute for measures that cancel to nearly nothing."""
-import ctypes as C
 import os
 import numpy as np
 import pytest
 
 import converge_restatement as R
+import support as S
+from support import counters, u32
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -20,37 +21,12 @@ EYE = np.eye(4, dtype=f32)
 TINY = dict(rotation=1e-30, translation=1e-30)        # never met: the restatement's measures of a whole run
 
 
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+def make_ctx(factory, form="merged", **params):               # this file's defaults: the bunny's threshold, 20 iterations
+    return S.make_ctx(factory, form, **dict(dict(max_distance=0.0003, n_iterations=20), **params))
 
 
-def make_ctx(factory, form="merged", **params):
-    old = os.environ.get("ICP_HIP_MERGE")
-    os.environ["ICP_HIP_MERGE"] = "0" if form == "separate" else "1"        # read once, at icp_ctx_create
-    try:
-        c = factory()
-    finally:
-        if old is None:
-            del os.environ["ICP_HIP_MERGE"]
-        else:
-            os.environ["ICP_HIP_MERGE"] = old
-    kw = dict(knn_backend=1, metric=1, max_distance=0.0003, n_iterations=20)
-    kw.update(params)
-    for k, v in kw.items():
-        setattr(c.params, k, v)
-    c.push_params()
-    return c
-
-
-def load(c, d, colors=False):
-    c.set_target(d["tgt_pts"], d["tgt_nrm"], d["tgt_rgba"] if colors else None)
-    c.set_source(d["src_pts"], d["src_nrm"], d["src_rgba"] if colors else None)
-
-
-def counters(c):
-    a, b = C.c_int32(0), C.c_int32(0)
-    assert c.lib.icp_debug_counters(c.h, C.byref(a), C.byref(b)) == 0
-    return a.value, b.value
+def load(c, d, colors=False):                                 # this file's default: no colours
+    S.load(c, d, colors)
 
 
 def same_record(a, b):

@@ -9,6 +9,8 @@ import gc
 import numpy as np
 import pytest
 
+from support import bits
+
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 LBVH = 1
@@ -29,7 +31,7 @@ def settled():
     return live()
 
 
-def configure(c, **kw):
+def configure(c, **kw):                                         # not support.configure: this one starts from default_params()
     """The defaults, k-NN on the LBVH backend, point-to-plane, a threshold in metres; then what the case asks for."""
     from icp_amd import binding
     c.params = binding.default_params()
@@ -37,10 +39,6 @@ def configure(c, **kw):
     for k, v in kw.items():
         setattr(c.params, k, v)
     c.push_params()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -94,22 +92,12 @@ def test_every_buffer_family_then_destroy(scans):
     assert live() == before
 
 
-def tum_K(width):
-    s = width / 640.0
-    return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], f32)
-
-
 @pytest.fixture(scope="module")
 def frames():
     """Three 64 x 48 frames of the synthetic hand-held camera: depth (MINF holes), RGBX bytes, gt transforms frame k -> frame 0."""
     from icp_amd import synth
-    W, H = 64, 48
-    K = tum_K(W)
-    T = [synth.camera_pose(k) for k in range(3)]
-    made = [synth.depth_frame(Tk, K.astype(np.float64), W, H, 0x7A11 + k, 0.05) for k, Tk in enumerate(T)]
-    depth = np.stack([m[0][:, 2].reshape(H, W).copy() for m in made]); rgbx = np.stack([m[2] for m in made])
-    gt = [(np.linalg.inv(T[0]) @ Tk).astype(f32) for Tk in T[1:]]
-    return K, W, H, depth, rgbx, gt
+    K, depth, rgbx, gt = synth.camera_sequence(3, 64, 48)
+    return K, 64, 48, depth, rgbx, gt
 
 
 def test_depth_and_model_paths_then_destroy(frames):

@@ -1,33 +1,18 @@
 """The depth mesh of reconstructRoom on the device (icp_depth_mesh: SimpleMesh(sensor, cameraPose, edgeThreshold), SimpleMesh.h:36-119)
-against the numpy restatement of tests/test_depth_mesh_host.py, bit for bit: vertices, colours and the triangle list in addFace order.
+against the numpy restatement tests/depth_mesh_restatement.py, bit for bit: vertices, colours and the triangle list in addFace order.
 Also the edge cases, the context it leaves alone, and tum.reconstruct_room end to end (saveRoomToFile, utils.h:179-193)."""
 import ctypes as C
 import os
 import numpy as np
 import pytest
 
-from test_depth_mesh_host import mesh_spec, make_pose
+from depth_mesh_restatement import mesh_spec
+from icp_amd.synth import camera_sequence as synth_frames, tum_K
+from support import pose_of as make_pose
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 MINF = -np.inf
-
-
-def tum_K(width):
-    s = width / 640.0
-    return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], f32)
-
-
-def synth_frames(n, width, height, seed=0x7A11, hole_frac=0.05):
-    from icp_amd import synth
-    K = tum_K(width)
-    depth, rgbx, T = [], [], []
-    for k in range(n):
-        Tk = synth.camera_pose(k, seed)
-        pts, _, rgba = synth.depth_frame(Tk, K.astype(np.float64), width, height, seed + k, hole_frac)
-        depth.append(pts[:, 2].reshape(height, width).copy()); rgbx.append(rgba); T.append(Tk)
-    gt = [(np.linalg.inv(T[0]) @ T[k]).astype(f32) for k in range(1, n)]
-    return K, np.stack(depth), np.stack(rgbx), gt
 
 
 def check(ctx, depth, rgbx, K, pose, thr, color=None):

@@ -1,31 +1,17 @@
 """Depth frames straight into the resident clouds (icp_set_target_depth / icp_set_source_depth) and the RGB-D tracking loop of
 reconstructRoom (icp_track_depth_frames, main.cpp:183-341), against the oracle and against the host route they replace
 (icp_backproject_depth or orc.backproject -> stride + filter on the host -> icp_set_source / icp_set_target -> icp_run)."""
+import functools
 import numpy as np
 import pytest
+
+import support as S
+from icp_amd.synth import camera_sequence as frames, tum_K
+from support import u32 as bits          # the view without a cast
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 ERR_INVALID_ARG, ERR_NO_SOURCE = 1, 4
-
-
-def tum_K(width):
-    """The TUM intrinsics (VirtualSensor.h:44-46) scaled to a smaller image of the same aspect."""
-    s = width / 640.0
-    return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], f32)
-
-
-def frames(n, width, height, hole_frac=0.05, seed=0x7A11):
-    """n organised frames of the synthetic hand-held camera: depth (MINF holes), RGBX bytes, gt transforms frame k -> frame 0."""
-    from icp_amd import synth
-    K = tum_K(width)
-    depth, rgbx, T = [], [], []
-    for k in range(n):
-        Tk = synth.camera_pose(k, seed)
-        pts, _, rgba = synth.depth_frame(Tk, K.astype(np.float64), width, height, seed + k, hole_frac)
-        depth.append(pts[:, 2].reshape(height, width).copy()); rgbx.append(rgba); T.append(Tk)
-    gt = [(np.linalg.inv(T[0]) @ T[k]).astype(f32) for k in range(1, n)]
-    return K, np.stack(depth), np.stack(rgbx), gt
 
 
 def oracle_cloud(orc, depth, rgbx, K, E, opt):
@@ -41,16 +27,8 @@ def close(a, b, tol=1e-6):
     return (np.isnan(a) and np.isnan(b)) or abs(a - b) < tol
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def configure(ctx, metric=1, matching=0, knn_backend=1, color_icp=0, multires=0, K=None, width=0, height=0, n_iterations=35):
-    p = ctx.params
-    p.metric, p.matching, p.knn_backend, p.color_icp, p.multires, p.n_iterations, p.max_distance = metric, matching, knn_backend, color_icp, multires, n_iterations, 0.1
-    if matching == 1:
-        p.fx, p.fy, p.cx, p.cy, p.width, p.height = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), width, height
-    ctx.push_params()
+# this file's defaults: 35 iterations, max_distance 0.1, selection seed 0 (the library's default)
+configure = functools.partial(S.configure, n_iterations=35, max_distance=0.1, seed=0)
 
 
 def _cloud_case(orc, W, H, cases, run_iters=0):

@@ -7,6 +7,7 @@ import pytest
 import global_cases as gc
 import global_restatement as gr
 from conftest import pose_error
+from support import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -14,23 +15,20 @@ POSE_TOL = 1e-5
 EXCLUDE_MARGIN, EXCLUDE_GAP = 1e-6, 1e-9      # a point may be left out of the SPFH comparison only inside these (bin units; ||a1| - |a2||)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def ulps(a, b):
     """distance in fp32 units in the last place between finite arrays of equal sign structure (FPFH values are >= 0)"""
     return np.abs(bits(a).astype(np.int64) - bits(b).astype(np.int64))
 
 
-def configure(ctx, knn_backend=1, metric=1, n_iterations=20, max_distance=0.0003):
+def configure(ctx, knn_backend=1, metric=1, n_iterations=20, max_distance=0.0003):          # not support.configure: the backend comes first and
+                                                                                            # the selection fields are left as they are
     p = ctx.params
     p.metric = metric; p.matching = 0; p.weighting = 0; p.rejection = 1; p.color_icp = 0; p.multires = 0
     p.n_iterations = n_iterations; p.max_distance = max_distance; p.knn_backend = knn_backend
     ctx.push_params()
 
 
-def load(ctx, b, knn_backend=1):
+def load(ctx, b, knn_backend=1):                              # not support.load: configures too, and loads no colours
     configure(ctx, knn_backend)
     ctx.set_target(b["tgt_pts"], b["tgt_nrm"])
     ctx.set_source(b["src_pts"], b["src_nrm"])
@@ -433,7 +431,7 @@ def test_edges_of_h_and_m(gpu_ctx_factory, bunny, n, start, H):
 def test_n_best_above_the_valid_count_and_the_hand_over_to_multistart(gpu_ctx_factory, bunny):
     """n_best = 256 with fewer valid hypotheses: every valid one comes back, in the restatement's ranking; then all of them as the starts of
     one icp_run_multistart -- more than one 64-start block of its score fold -- each against icp_run."""
-    from test_gpu_multistart import assert_matches_icp_run, expected_best
+    from support import assert_matches_icp_run, expected_best
     ctx = gpu_ctx_factory()
     configure(ctx, knn_backend=1, metric=1, n_iterations=5, max_distance=0.0003)
     ctx.set_target(bunny["tgt_pts"], bunny["tgt_nrm"]); ctx.set_source(bunny["src_pts"], bunny["src_nrm"])

@@ -2,13 +2,11 @@
 import numpy as np
 import pytest
 
+from support import bits
+
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 LBVH = 1
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def ctx_with(factory, t, q, thr, backend):

@@ -3,11 +3,18 @@ weight / reject / accumulate epilogue, Morton-sorted source levels, incremental 
 against the oracle and the golden bunny trajectories (the same checks test_gpu_parity.py runs on the scan backend)."""
 import numpy as np
 import pytest
-from test_gpu_parity import make_ctx, rand_pose, POSE_TOL, small_pair  # noqa: F401  (small_pair is a fixture)
+
+from support import POSE_TOL, rand_pose, loaded_ctx as make_ctx
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 LBVH = 1
+
+
+@pytest.fixture(scope="module")
+def small_pair():
+    from icp_amd import synth
+    return synth.eth_like_pair(0, n_tilt=43, n_beam=135)        # 5805 points
 
 
 @pytest.mark.parametrize("metric", [0, 1, 2])

@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import lm_restatement as lm          # noqa: E402
+from support import restated_step          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,17 +28,6 @@ def make_ctx(gpu_ctx_factory, pair, metric, weighting=0, rejection=1, n_iteratio
     if nonlinear:
         c.set_optimizer(True, **(opts or {}))
     return c
-
-
-def restated_step(c, pair, metric, pose, opts=None):
-    """The restatement's Solve on the device's records at `pose` -> (x, summary, decisions, new pose)."""
-    recs, _, _ = c.correspond(pose)
-    st = c.transform_points(pair["src_pts"], pose)
-    nt = c.transform_normals(pair["src_nrm"], pose)
-    b = lm.blocks(metric, st, nt, pair["tgt_pts"], pair["tgt_nrm"], recs)
-    x, summ, dec = lm.solve_blocks(b, opts)
-    newpose = pose if summ["termination"] == lm.NO_RESIDUALS else lm.compose(x, pose)
-    return x, summ, dec, newpose
 
 
 def same_solve(dev, ref, x_tol=1e-9):

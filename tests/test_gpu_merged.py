@@ -5,52 +5,13 @@ solve are the same operations, so every iteration's pose and valid count must be
 up as a different pose.  Plus the routes out of the merged form (rank-deficient system -> repeated with the separate launches; an
 iteration without correspondences) and the re-arming of k_reduce_solve's own hand-over slots."""
 import ctypes as C
-import os
 import numpy as np
 import pytest
 
+from support import FORMS, make_ctx, counters, assert_same_run
+
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-LBVH = 1
-
-
-FORMS = ("merged", "separate")
-
-
-def make_ctx(factory, form, **params):
-    if form is True:
-        form = "merged"
-    elif form is False:
-        form = "separate"
-    env = {"ICP_HIP_MERGE": "0" if form == "separate" else "1"}                                              # read once, at icp_ctx_create
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        c = factory()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-    c.params.knn_backend = LBVH; c.params.metric = 1
-    for k, v in params.items():
-        setattr(c.params, k, v)
-    c.push_params()
-    return c
-
-
-def counters(c):
-    a, b = C.c_int32(0), C.c_int32(0)
-    assert c.lib.icp_debug_counters(c.h, C.byref(a), C.byref(b)) == 0
-    return a.value, b.value
-
-
-def assert_same_run(ra, rb):
-    assert len(ra) == len(rb)
-    for k, (a, b) in enumerate(zip(ra, rb)):
-        assert a["n_valid"] == b["n_valid"] and a["status"] == b["status"] and a["n_src"] == b["n_src"], k
-        assert np.array_equal(a["pose"], b["pose"]), k
 
 
 def test_merged_loop_fullsize_is_bit_identical_to_separate_launches(gpu_ctx_factory):

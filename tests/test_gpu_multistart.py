@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 from conftest import pose_error
+from support import assert_matches_icp_run, expected_best
 
 pytestmark = pytest.mark.gpu
 LBVH = 1
@@ -29,31 +30,6 @@ def bunny_clouds(bunny):
 def bunny_starts(bunny, k=5):
     from icp_amd.multistart import start_poses
     return start_poses(np.eye(4), yaw_deg=[0.0, 4.0, -4.0, 8.0, -8.0][:k], axis=(0, 1, 0), points=bunny["src_pts"])
-
-
-def assert_matches_icp_run(c, starts, max_stats=512):
-    """Every start of ONE multistart call against icp_run from that start on the same context: records and pose, bit for bit."""
-    res, stats, best = c.run_multistart(starts, max_stats=max_stats)
-    assert len(res) == len(starts)
-    for k, s in enumerate(starts):
-        pose, recs, rc = c.run(s, max_stats=max_stats, check=False)
-        assert res[k]["status"] == rc, k
-        assert np.array_equal(res[k]["pose"], pose), k
-        assert len(stats[k]) == len(recs), k
-        for i, (a, b) in enumerate(zip(stats[k], recs)):
-            assert (a["n_src"], a["n_valid"], a["status"]) == (b["n_src"], b["n_valid"], b["status"]), (k, i)
-            assert np.array_equal(a["pose"], b["pose"]), (k, i)
-            assert a["rmse"] == -1.0 and a["benchmark_error"] == -1.0
-    return res, stats, best
-
-
-def expected_best(res):
-    best = 0
-    for k, r in enumerate(res):
-        b = res[best]
-        if r["n_inliers"] > b["n_inliers"] or (r["n_inliers"] == b["n_inliers"] and r["inlier_rmse"] < b["inlier_rmse"]):
-            best = k
-    return best
 
 
 def ulp_distance(a, b):

@@ -15,63 +15,10 @@ known to round like the host's).  PCL parity stays unpinned (PCL absent): see or
 import numpy as np
 import pytest
 
+from support import check_normals
+
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-NRM_TOL = 2e-6
-CURV_TOL = 2e-6
-GAP_REL = 1e-9
-
-
-def check_normals(orc, pts, k, vp, nrm, curv, label=""):
-    """Asserts the device's (nrm, curv) against orc.estimate_normals on every point; returns the statistics."""
-    pts = np.ascontiguousarray(pts, f32); vp = np.asarray(vp, f32)
-    on, oc, nb = orc.estimate_normals(pts, k, vp, return_neighbours=True)
-    assert nrm.shape == on.shape and curv.shape == oc.shape
-    nan_n, nan_c = np.isnan(nrm), np.isnan(curv)
-    bad_nan = np.nonzero((nan_n != np.isnan(on)).any(1) | (nan_c != np.isnan(oc)))[0]
-    assert len(bad_nan) == 0, "%s: NaN pattern differs at %s: dev %s orc %s" % (label, bad_nan[:5], nrm[bad_nan[:5]], on[bad_nan[:5]])
-    fin = np.nonzero(~np.isnan(on).any(1))[0]
-    stats = dict(label=label, n=len(pts), n_normals=len(fin), worst_nrm=0.0, worst_curv=0.0, bit_identical=1.0, n_ambiguous=0)
-    if len(fin) == 0:
-        return stats
-    assert np.isfinite(nrm[fin]).all() and np.isfinite(curv[fin]).all()
-    # covariance of the oracle's neighbour sets (fp64; eigenvalues by LAPACK, independent of both Jacobis)
-    ids = nb[fin]; m = ids >= 0; cnt = m.sum(1)
-    X = np.where(m[..., None], pts[np.where(m, ids, 0)].astype(np.float64), 0.0)
-    D = (X - (X.sum(1) / cnt[:, None])[:, None, :]) * m[..., None]
-    C = np.einsum("nki,nkj->nij", D, D) / cnt[:, None, None]
-    w = np.linalg.eigvalsh(C)
-    lmax = w[:, 2]
-    amb = (lmax > 0) & (w[:, 1] - w[:, 0] <= GAP_REL * lmax)
-    nd, no = nrm[fin].astype(np.float64), on[fin].astype(np.float64)
-    dn = np.abs(nd - no).max(1)
-    dn[amb] = 0.0
-    dc = np.abs(curv[fin].astype(np.float64) - oc[fin])
-    stats.update(worst_nrm=float(dn.max()), worst_curv=float(dc.max()), n_ambiguous=int(amb.sum()),
-                 bit_identical=float((nrm[fin].view(np.uint32) == on[fin].view(np.uint32)).all(1).mean()))
-
-    def where(r, what):
-        i = fin[r]
-        return "%s: %s at point %d %s (%d-NN %s): dev n %s curv %r, oracle n %s curv %r, eig %s; %.6f of normals bit-identical" % (
-            label, what, i, pts[i], k, nb[i].tolist(), nrm[i], float(curv[i]), on[i], float(oc[i]), w[r], stats["bit_identical"])
-    r = int(np.argmax(dn))
-    assert dn[r] <= NRM_TOL, where(r, "|n_dev - n_orc| = %.3g" % dn[r])
-    r = int(np.argmax(dc))
-    assert dc[r] <= CURV_TOL, where(r, "|curv_dev - curv_orc| = %.3g" % dc[r])
-    if amb.any():
-        a = np.nonzero(amb)[0]
-        q = np.einsum("ni,nij,nj->n", nd[a], C[a], nd[a])
-        over = q - (w[a, 0] + GAP_REL * lmax[a])
-        r = int(np.argmax(over))
-        assert over[r] <= 0, where(a[r], "n^T C n above the near-null space by %.3g" % over[r])
-        ln = np.abs(np.linalg.norm(nd[a], axis=1) - 1)
-        r = int(np.argmax(ln))
-        assert ln[r] <= 1e-6, where(a[r], "| |n| - 1 | = %.3g" % ln[r])
-        e = (vp[None, :] - pts[fin[a]]).astype(np.float64)
-        flip = (e * nd[a]).sum(1) + 1e-6 * np.linalg.norm(e, axis=1)
-        r = int(np.argmin(flip))
-        assert flip[r] >= 0, where(a[r], "normal points away from the viewpoint")
-    return stats
 
 
 def dev_vs_oracle(ctx, orc, pts, k, vp=(0.0, 0.0, 0.0), label=""):

@@ -1,10 +1,13 @@
 """Normal-space sampling (params.selection = 2, dev_nss.hpp) on the device against the numpy restatement tests/nss_restatement.py: buckets
 and index lists exactly, teacher-forced iterations against the oracle on the device's own lists, the held form, every loop that takes a
 selection, the paths that must stay untouched, refusals, and the incised plane the feature exists for."""
+import functools
 import numpy as np
 import pytest
 
 import nss_restatement as nss
+import support as S
+from support import bits, load
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -12,20 +15,8 @@ POSE_TOL = 1e-5
 LONG_SEGMENT = 16384          # NSS_LONG (dev_nss.hpp): a bucket with more candidates than this is selected by several blocks of 4096
 
 
-def configure(ctx, metric=1, knn_backend=1, n_iterations=4, multires=0, selection=2, proba=0.5, seed=7, max_distance=0.0003, weighting=0, color_icp=0):
-    p = ctx.params
-    p.metric, p.knn_backend, p.n_iterations, p.multires, p.weighting, p.color_icp = metric, knn_backend, n_iterations, multires, weighting, color_icp
-    p.selection, p.selection_proba, p.selection_seed, p.max_distance, p.matching, p.rejection = selection, proba, seed, max_distance, 0, 1
-    ctx.push_params()
-
-
-def load(ctx, d, colors=True):
-    ctx.set_target(d["tgt_pts"], d["tgt_nrm"], d.get("tgt_rgba") if colors else None)
-    ctx.set_source(d["src_pts"], d["src_nrm"], d.get("src_rgba") if colors else None)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
+# this file's defaults: 4 iterations, normal-space sampling of half the points
+configure = functools.partial(S.configure, n_iterations=4, selection=2, proba=0.5)
 
 
 def factors_of(ctx):

@@ -7,19 +7,10 @@ within 1e-5 (rad / m) of the oracle's solve (north_star tolerance).  PARITY UNPI
 import numpy as np
 import pytest
 
+from support import POSE_TOL, bits, check_normals, rand_pose, loaded_ctx as make_ctx
+
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-POSE_TOL = 1e-5        # north_star: 1e-5 rad / 1e-5 m
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def rand_pose(seed, ang=0.1, tr=0.2):
-    from icp_amd import synth
-    r = np.random.default_rng(seed)
-    return synth.make_pose(r.uniform(-ang, ang, 3), r.uniform(-tr, tr, 3)).astype(f32)
 
 
 @pytest.fixture(scope="module")
@@ -33,17 +24,6 @@ def rgbd():
     from icp_amd import synth
     K = np.array([[131.25, 0, 79.5], [0, 131.25, 59.5], [0, 0, 1]], f32)      # TUM intrinsics / 4
     return synth.rgbd_pair(0, width=160, height=120, K=K, hole_frac=0.05)
-
-
-def make_ctx(factory, tgt, src, **params):
-    c = factory()
-    for k, v in params.items():
-        setattr(c.params, k, v)
-    c.push_params()
-    c.set_target(*tgt)
-    if src is not None:
-        c.set_source(*src)
-    return c
 
 
 # ------------------------------------------------------------------------------------------- k-NN
@@ -488,7 +468,6 @@ def test_estimate_normals_k5(gpu_ctx_factory, orc):
     unpinned; every point checked against the oracle's restatement of the device contract (orc_estimate_normals, itself
     cross-checked against numpy / scipy in tests/test_oracle.py) and against the analytic normals of the synthetic room."""
     from icp_amd import synth
-    from test_gpu_normals import check_normals
     pts, nrm_true, _ = synth.laser_scan(synth.scan_pose(0), 7, n_tilt=60, n_beam=200, sigma=0.0)
     pts = pts.copy(); pts[17] = np.nan
     c = gpu_ctx_factory()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import query_set_reference as Q
+from support import check_stats, load, restated_step, u32
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -33,7 +34,7 @@ def clouds(bunny):
     return dict(bunny=Q.shuffled(bunny), rgbd=Q.shuffled(Q.rgbd_pair()))
 
 
-def configure(ctx, cfg, form=None, robust=True, lm=False):
+def configure(ctx, cfg, form=None, robust=True, lm=False):          # not support.configure: driven by a cfg dict, sets the mode's options too
     multires, selection, resample, knn_backend = FORMS[form] if form else (0, 0, None, 1)
     p = ctx.params
     p.metric, p.weighting, p.rejection, p.color_icp, p.matching, p.knn_backend = cfg["metric"], cfg["weighting"], cfg["rejection"], 0, 0, knn_backend
@@ -52,21 +53,12 @@ def configure(ctx, cfg, form=None, robust=True, lm=False):
         ctx.set_optimizer(True)
 
 
-def load(ctx, d):
-    ctx.set_target(d["tgt_pts"], d["tgt_nrm"], d["tgt_rgba"])
-    ctx.set_source(d["src_pts"], d["src_nrm"], d["src_rgba"])
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def check_form(ctx, form, recs, factors, sets, n):
     """What can be seen from outside of the form a run took: the levels change under multires, a selection exists or not, a list per
     iteration differs from its neighbour, the merged point-to-plane loop was not taken.  (Whether a level was a sorted copy or a list is
     not observable through the C ABI; the two backends that decide it are both in FORMS.)"""
     from icp_amd import binding
-    import test_gpu_merged as M
+    import support as M
     multires, selection, resample, knn_backend = FORMS[form]
     sizes = [r["n_src"] for r in recs]
     if multires:
@@ -87,7 +79,6 @@ def check_form(ctx, form, recs, factors, sets, n):
 @pytest.mark.parametrize("mode", sorted(Q.MODES))
 @pytest.mark.parametrize("form", sorted(FORMS))
 def test_iterations_equal_the_reference_on_the_original_rows(gpu_ctx_factory, clouds, form, mode):
-    import test_gpu_robust as TR
     cfg = Q.MODES[mode]
     d = clouds[cfg["cloud"]]
     n = len(d["src_pts"])
@@ -126,7 +117,7 @@ def test_iterations_equal_the_reference_on_the_original_rows(gpu_ctx_factory, cl
         assert r["n_valid"] == ref["n_valid"] > 0, line
         assert err <= Q.TOL, (line, r["pose"], ref["pose"])
         if cfg["mode"] == "robust":
-            TR.check_stats(stats[i], ref["stats"], line)
+            check_stats(stats[i], ref["stats"], line)
         prev = r["pose"]
     assert np.array_equal(u32(pose), u32(recs[-1]["pose"]))
     pose2, recs2, _ = ctx.run(eye)                            # a second run is bit-identical
@@ -140,7 +131,6 @@ def test_lm_on_normal_space_sets(gpu_ctx_factory, clouds, form):
     iteration: the set of iteration i (icp_get_selection, checked against nss_restatement) becomes the source of a second context whose
     matcher the restatement queries at its own pose."""
     import lm_restatement as lm
-    import test_gpu_lm as TL
     cfg = dict(mode="lm", metric=1, weighting=0, rejection=1, max_distance=0.0003)
     d = clouds["bunny"]
     ctx, q = gpu_ctx_factory(), gpu_ctx_factory()
@@ -157,7 +147,7 @@ def test_lm_on_normal_space_sets(gpu_ctx_factory, clouds, form):
         assert 0 < len(S) < len(d["src_pts"]) and Q.slot_differs(S) > 0.95
         pair = dict(src_pts=d["src_pts"][S], src_nrm=d["src_nrm"][S], tgt_pts=d["tgt_pts"], tgt_nrm=d["tgt_nrm"])
         q.set_source(pair["src_pts"], pair["src_nrm"], d["src_rgba"][S])
-        _, summ, _, pose = TL.restated_step(q, pair, 1, pose)
+        _, summ, _, pose = restated_step(q, pair, 1, pose)
         err = float(np.abs(recs[i]["pose"].astype(np.float64) - pose).max())
         print("%s / lm iteration %d: %d points, LM iterations %d (reference %d), pose error %.3g" % (form, i, len(S), sums[i]["iterations"], summ["iterations"], err))
         assert recs[i]["n_src"] == len(S), i

@@ -9,6 +9,7 @@ import pytest
 import gicp_restatement as G
 import robust_restatement as R
 from conftest import pose_error
+from support import check_stats, configure, load, u32
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -16,36 +17,10 @@ EPS = 1e-3
 KERNELS = ("none", "huber", "cauchy", "tukey")
 
 
-def configure(ctx, metric=1, weighting=0, rejection=1, color_icp=0, knn_backend=1, n_iterations=10, multires=0, selection=0, proba=1.0,
-              max_distance=0.0003, matching=0):
-    p = ctx.params
-    p.metric, p.weighting, p.rejection, p.color_icp, p.knn_backend, p.n_iterations = metric, weighting, rejection, color_icp, knn_backend, n_iterations
-    p.multires, p.selection, p.selection_proba, p.selection_seed, p.max_distance, p.matching = multires, selection, proba, 7, max_distance, matching
-    ctx.push_params()
-
-
-def load(ctx, d, colors=True):
-    ctx.set_target(d["tgt_pts"], d["tgt_nrm"], d.get("tgt_rgba") if colors else None)
-    ctx.set_source(d["src_pts"], d["src_nrm"], d.get("src_rgba") if colors else None)
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 @pytest.fixture(scope="module")
 def depth_pair():
     from icp_amd import synth
-    K = np.array([[525.0 / 8, 0, 319.5 / 8], [0, 525.0 / 8, 239.5 / 8], [0, 0, 1]])
-    d = synth.rgbd_pair(0, width=80, height=60, K=K)
-    tp, tn, tc = synth.compact_valid(d["tgt_pts"], d["tgt_nrm"], d["tgt_rgba"])
-    sp, sn, sc = synth.compact_valid(d["src_pts"], d["src_nrm"], d["src_rgba"])
-    return dict(src_pts=sp, src_nrm=sn, src_rgba=sc, tgt_pts=tp, tgt_nrm=tn, tgt_rgba=tc, gt=d["gt"], organised=d, K=K)
-
-
-def check_stats(dev, ref, label):
-    assert dev["n_entering"] == ref["n_entering"] and dev["n_kept"] == ref["n_kept"], (label, dev, ref)
-    assert u32(f32(dev["trim_d2"])) == u32(f32(ref["trim_d2"])) and u32(f32(dev["sigma"])) == u32(f32(ref["sigma"])), (label, dev, ref)
+    return synth.compact_rgbd_pair()
 
 
 def teacher_forced(ctx, d, pose, metric, opts, label, tol=1e-9):
@@ -204,7 +179,7 @@ def test_selection_edge_cases(gpu_ctx_factory):
 
 
 def test_off_is_untouched(gpu_ctx_factory, bunny):
-    import test_gpu_merged as M
+    import support as M
     eye = np.eye(4, dtype=f32)
     a = gpu_ctx_factory(); configure(a, metric=1, n_iterations=10); load(a, bunny)
     pa, ra, _ = a.run(eye)
@@ -259,14 +234,7 @@ def partial_overlap_fixture():
     """ETH-like pair at 86 x 270 (23 220 source points); the target loses every point beyond the 60 % quantile of the unperturbed
     source's x, so 40 % of the source has no counterpart."""
     from icp_amd import synth
-    d = synth.eth_like_pair(0, n_tilt=86, n_beam=270)
-    su = np.asarray(d["src_unperturbed"], np.float64)
-    thr = np.quantile(su[np.isfinite(su).all(1), 0], 0.6)
-    tp, tn = np.asarray(d["tgt_pts"]), np.asarray(d["tgt_nrm"])
-    keep = np.isfinite(tp).all(1) & (tp[:, 0] <= thr)
-    sp, sn = np.asarray(d["src_pts"], f32), np.asarray(d["src_nrm"], f32)
-    ok = np.isfinite(sp).all(1) & np.isfinite(sn).all(1)
-    return dict(src_pts=sp[ok], src_nrm=sn[ok], tgt_pts=tp[keep].astype(f32), tgt_nrm=tn[keep].astype(f32), gt=d["gt"])
+    return synth.partial_overlap_pair(0, 86, 270, 0.6, drop_target_normals=False)
 
 
 def test_partial_overlap():

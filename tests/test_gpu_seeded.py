@@ -39,7 +39,7 @@ FORMS = ("merged", "separate")
 
 
 def new_ctx(factory, form="merged"):
-    """A context whose icp_run -- and with it icp_match_seeded -- takes `form` (the keys test_gpu_merged.py::make_ctx sets; read once,
+    """A context whose icp_run -- and with it icp_match_seeded -- takes `form` (the keys support.make_ctx sets; read once,
     at icp_ctx_create)."""
     env = {"ICP_HIP_MERGE": "0" if form == "separate" else "1"}
     old = {k: os.environ.get(k) for k in env}

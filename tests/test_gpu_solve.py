@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import solve_reference as sr
-from test_gpu_merged import make_ctx, counters
+from support import make_ctx, counters, same_bits
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -44,10 +44,6 @@ def setup(c, case, metric, backend, weighting, n_iterations=1):
     c.push_params()
     c.set_target(case["tgt_pts"], case["tgt_nrm"]); c.set_source(case["src_pts"], case["src_nrm"])
     return c
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, f32).view(np.uint32), np.asarray(b, f32).view(np.uint32))
 
 
 def reference_of(orc, case, metric, weighting):

@@ -14,12 +14,14 @@ sum s and sum d (slots 1..6; only the means need them, and point-to-plane has no
 exactly that and compare the other 27 sums.  icp_correspond's point-to-plane sums (route 1) carry all 33.
 tests/test_sums_host.py shows that one pair dropped or doubled moves a sum by >= 1.06e-5 at every size."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 import sums_cases as S
-import test_gpu_merged as M
+import support as M
+from support import u32
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -27,17 +29,8 @@ SEED = 7
 ERR_INVALID_ARG = 1
 
 
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def configure(ctx, metric, weighting=0, rejection=1, knn_backend=1, color_icp=0, matching=0, multires=0, selection=0, n_iterations=2):
-    p = ctx.params
-    p.metric, p.weighting, p.rejection, p.knn_backend, p.color_icp, p.matching = metric, weighting, rejection, knn_backend, color_icp, matching
-    p.multires, p.selection, p.selection_proba, p.selection_seed, p.n_iterations, p.max_distance = multires, selection, 0.5, SEED, n_iterations, S.MAX_DIST
-    if matching == 1:
-        p.fx, p.fy, p.cx, p.cy, p.width, p.height = float(S.K8[0, 0]), float(S.K8[1, 1]), float(S.K8[0, 2]), float(S.K8[1, 2]), 80, 60
-    ctx.push_params()
+# this file's defaults: 2 iterations, S.MAX_DIST, half the points under a selection, the 80 x 60 camera under projective matching
+configure = functools.partial(M.configure, n_iterations=2, proba=0.5, seed=SEED, max_distance=S.MAX_DIST, K=S.K8, width=80, height=60)
 
 
 class Case:
@@ -102,7 +95,7 @@ def empty_blocks(lib, case):
     return out
 
 
-def load(ctx, case, colors=True):
+def load(ctx, case, colors=True):                           # not support.load: a Case, not a dict of clouds
     ctx.set_target(case.tgt[0], case.tgt[1], case.tgt[2] if colors else None)
     ctx.set_source(case.pts, case.nrm, case.rgba if colors else None)
 

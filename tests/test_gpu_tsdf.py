@@ -2,12 +2,16 @@
 restatement of the contract (tests/tsdf_restatement.py) bit for bit, the model target against the host route it replaces, the tracking
 loop against a composition of public calls, the refusals, and the outcome on a pan that frame-to-frame-0 tracking cannot follow."""
 import ctypes as C
+import functools
 import json
 import numpy as np
 import pytest
 
+import support as S
 import tsdf_restatement as TS
 import tsdf_outcome_fixture as OF
+from icp_amd.synth import camera_sequence, tum_K, wavy_depth
+from support import bits, same_bits, pose_of
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -15,35 +19,8 @@ MINF = f32(-np.inf)
 ERR_INVALID_ARG, ERR_NO_TARGET, ERR_NO_SOURCE = 1, 3, 4
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-def pose_of(angles, t):
-    from icp_amd import synth
-    return synth.make_pose(angles, t).astype(f32)
-
-
-def wavy_depth(W, H, base=1.5, seed=5):
-    """A smooth surface with a step, so that every branch of the band is taken."""
-    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
-    d = base + 0.3 * np.sin(u * 0.3) + 0.2 * np.cos(v * 0.4) + 0.5 * (u > 0.7 * W)
-    return d.astype(f32)
-
-
-def configure(ctx, metric=1, matching=0, knn_backend=1, n_iterations=35, K=None, width=0, height=0, **kw):
-    p = ctx.params
-    p.metric, p.matching, p.knn_backend, p.color_icp, p.multires, p.n_iterations, p.max_distance = metric, matching, knn_backend, 0, 0, n_iterations, 0.1
-    p.weighting, p.rejection, p.selection, p.selection_proba, p.selection_seed = 0, 1, 0, 1.0, 0
-    for k, v in kw.items():
-        setattr(p, k, v)
-    if matching == 1:
-        p.fx, p.fy, p.cx, p.cy, p.width, p.height = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), width, height
-    ctx.push_params()
+# this file's defaults: 35 iterations, max_distance 0.1, selection seed 0 (the library's default)
+configure = functools.partial(S.configure, n_iterations=35, max_distance=0.1, seed=0)
 
 
 def test_integrate_matches_restatement_bit_for_bit(gpu_ctx_factory):
@@ -53,7 +30,7 @@ def test_integrate_matches_restatement_bit_for_bit(gpu_ctx_factory):
     their bits."""
     from icp_amd import binding
     W, H = 40, 30
-    K = OF.tum_K(W)
+    K = tum_K(W)
     cam, rcam = binding.depth_camera(K, W, H), TS.Camera(K, W, H)
     opts = dict(dims=(37, 21, 29), origin=(-1.8, -1.0, -0.5), voxel_size=0.1, truncation=0.3, max_weight=2.0, min_depth=0.3, max_depth=2.4)
     ctx = gpu_ctx_factory()
@@ -71,7 +48,7 @@ def test_integrate_matches_restatement_bit_for_bit(gpu_ctx_factory):
     d1 = wavy_depth(W, H)
     d1[0, :6] = [MINF, np.nan, np.inf, 0.0, -1.0, 2.5]                        # 2.5 > max_depth
     d1[10:14, 20:24] = MINF
-    d2 = wavy_depth(W, H, base=1.4, seed=6); d2[5, 5] = np.nan
+    d2 = wavy_depth(W, H, base=1.4); d2[5, 5] = np.nan
     poses = [np.eye(4, dtype=f32), pose_of((0.1, -0.25, 0.05), (0.3, -0.1, 0.2))]      # the second: part of the band leaves the image
     total = 0
     for depth, pose in [(d1, poses[0]), (d2, poses[1]), (d1, poses[0]), (d1, poses[0])]:
@@ -128,7 +105,7 @@ def test_raycast_matches_restatement_bit_for_bit(gpu_ctx_factory):
     device, downloaded, and handed to the restatement, so this compares the ray-cast alone."""
     from icp_amd import binding
     W, H = 40, 30
-    K = OF.tum_K(W)
+    K = tum_K(W)
     cam, rcam = binding.depth_camera(K, W, H), TS.Camera(K, W, H)
     ctx = gpu_ctx_factory()
     ctx.tsdf_create(**RAY_OPTS)
@@ -185,15 +162,6 @@ def test_raycast_matches_restatement_bit_for_bit(gpu_ctx_factory):
     check_raycast(ctx, vol, cam, rcam, pose_of((0.1, -0.2, 0.05), (0.1, 0.0, 0.1)), "NaNs and unobserved cells, oblique")
 
 
-def room_frames(n, W, H, hole_frac=0.05):
-    from icp_amd import synth
-    K = OF.tum_K(W)
-    T = [synth.camera_pose(k) for k in range(n)]
-    depth = [synth.depth_frame(Tk, K.astype(np.float64), W, H, 0x7A11 + k, hole_frac)[0][:, 2].reshape(H, W).copy() for k, Tk in enumerate(T)]
-    gt = [(np.linalg.inv(T[0]) @ Tk).astype(f32) for Tk in T[1:]]
-    return K, np.stack(depth), gt
-
-
 ROOM_OPTS = dict(dims=(71, 35, 89), origin=(-3.3, -1.7, -1.6), voxel_size=0.1, truncation=0.4)
 
 
@@ -203,7 +171,7 @@ def test_model_target_matches_host_arrays(gpu_ctx_factory, variant):
     sum for sum; a source, params and a convergence reference set before stay as they were."""
     from icp_amd import binding
     W, H = 160, 120
-    K, depth, gt = room_frames(2, W, H)
+    K, depth, _, gt = camera_sequence(2, W, H)
     cam = binding.depth_camera(K, W, H)
     kw = dict(knn_brute=dict(knn_backend=0), knn_lbvh=dict(knn_backend=1), projective=dict(matching=1, knn_backend=0, K=K, width=W, height=H))[variant]
     a, b = gpu_ctx_factory(), gpu_ctx_factory()
@@ -276,7 +244,7 @@ def python_loop(ctx, K, depth, gt, cam, so, opts):
 def test_track_depth_model_matches_composition_of_public_calls(gpu_ctx_factory, case):
     from icp_amd import binding
     W, H = 80, 60
-    K, depth, gt = room_frames(4, W, H)
+    K, depth, _, gt = camera_sequence(4, W, H)
     if case == "gt_empty_frame":
         depth[2][:] = MINF
     cam = binding.depth_camera(K, W, H)
@@ -311,7 +279,7 @@ def test_track_depth_model_matches_composition_of_public_calls(gpu_ctx_factory, 
 def test_refusals_and_untouched_frame0_path(gpu_ctx_factory):
     from icp_amd import binding, tum
     W, H = 80, 60
-    K, depth, gt = room_frames(3, W, H)
+    K, depth, _, gt = camera_sequence(3, W, H)
     cam = binding.depth_camera(K, W, H)
     so = binding.depth_options(False, 2)
     eye = np.eye(4, dtype=f32)

@@ -4,15 +4,18 @@ icp_track_depth_model_color, icp_tsdf_mesh_color): integrate, ray-cast and mesh 
 composition of public calls, the refusals, the geometry-only paths on a volume that has colours against one that never had, and the
 outcome on a flat textured wall, whose geometry leaves the lateral pose free."""
 import ctypes as C
+import functools
 import json
 import numpy as np
 import pytest
 
+import support as S
 import tsdf_color_outcome_fixture as CF
 import tsdf_color_restatement as TC
 import tsdf_mesh_restatement as TM
-import tsdf_outcome_fixture as OF
 import tsdf_restatement as TS
+from icp_amd.synth import camera_sequence as rgbd_frames, tum_K, wavy_depth
+from support import bits, same_bits, pose_of
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -21,46 +24,9 @@ ERR_INVALID_ARG, ERR_NO_TARGET, ERR_NO_SOURCE = 1, 3, 4
 MODES = dict(colour_weighting=dict(weighting=3), colour_icp=dict(color_icp=1), colored_metric=dict(metric=4))
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-def pose_of(angles, t):
-    from icp_amd import synth
-    return synth.make_pose(angles, t).astype(f32)
-
-
-def wavy_depth(W, H, base=1.5):
-    """A smooth surface with a step, so that every branch of the band is taken (test_gpu_tsdf's)."""
-    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
-    return (base + 0.3 * np.sin(u * 0.3) + 0.2 * np.cos(v * 0.4) + 0.5 * (u > 0.7 * W)).astype(f32)
-
-
-def configure(ctx, metric=1, matching=0, knn_backend=1, n_iterations=35, **kw):
-    p = ctx.params
-    p.metric, p.matching, p.knn_backend, p.color_icp, p.multires, p.n_iterations, p.max_distance = metric, matching, knn_backend, 0, 0, n_iterations, 0.1
-    p.weighting, p.rejection, p.selection, p.selection_proba, p.selection_seed = 0, 1, 0, 1.0, 0
-    for k, v in kw.items():
-        setattr(p, k, v)
-    ctx.push_params()
-
-
-def rgbd_frames(n, W, H, hole_frac=0.05):
-    """The synthetic RGB-D room of the depth-tracking tests: (K, depth (n, H, W), rgbx (n, W*H, 4), gt of frames 1..)."""
-    from icp_amd import synth
-    K = OF.tum_K(W)
-    T = [synth.camera_pose(k) for k in range(n)]
-    depth, rgbx = [], []
-    for k, Tk in enumerate(T):
-        pts, _, rgba = synth.depth_frame(Tk, K.astype(np.float64), W, H, 0x7A11 + k, hole_frac)
-        depth.append(pts[:, 2].reshape(H, W).copy()); rgbx.append(np.ascontiguousarray(rgba, np.uint8))
-    gt = [(np.linalg.inv(T[0]) @ Tk).astype(f32) for Tk in T[1:]]
-    return K, np.stack(depth), np.stack(rgbx), gt
-
+# this file's defaults: 35 iterations, max_distance 0.1, selection seed 0 (the library's default)
+configure = functools.partial(S.configure, n_iterations=35, max_distance=0.1, seed=0)
+upload = functools.partial(S.upload, color=True)
 
 INT_OPTS = dict(dims=(37, 21, 29), origin=(-1.8, -1.0, -0.5), voxel_size=0.1, truncation=0.3, max_weight=2.0, min_depth=0.3, max_depth=2.4)
 
@@ -69,7 +35,7 @@ def integrate_case():
     """The frames and poses of test_integrate_matches_restatement_bit_for_bit, a seeded random colour frame for each, and a crafted start
     for both arrays with NaN payloads where no pose reaches (world z <= -0.3: behind every camera)."""
     W, H = 40, 30
-    K = OF.tum_K(W)
+    K = tum_K(W)
     rng = np.random.default_rng(3)
     shape = (29, 21, 37)
     t0 = rng.uniform(-1, 1, shape).astype(f32); w0 = rng.choice(np.array([0, 1, 1.5], f32), shape)
@@ -150,7 +116,7 @@ def test_raycast_color_matches_restatement_bit_for_bit(gpu_ctx_factory):
     bit-equal to icp_tsdf_raycast; the restatement shows at least 50 pixels on each colour path (eight corners, nearest corner, none)."""
     from icp_amd import binding
     W, H = 40, 30
-    K = OF.tum_K(W)
+    K = tum_K(W)
     cam, rcam = binding.depth_camera(K, W, H), TS.Camera(K, W, H)
     ctx = gpu_ctx_factory()
     ctx.tsdf_create(color=True, **RAY_OPTS)
@@ -403,19 +369,13 @@ def check_mesh(ctx, vol, min_weight, what):
     return v, n, t, col
 
 
-def upload(ctx, vol):
-    ctx.tsdf_create(color=True, dims=(vol.nx, vol.ny, vol.nz), origin=tuple(float(x) for x in vol.o), voxel_size=float(vol.s))
-    ctx.tsdf_upload(vol.tsdf, vol.weight); ctx.tsdf_color_upload(vol.rgb, vol.wc)
-
-
 def test_mesh_colors_match_restatement_bit_for_bit(gpu_ctx_factory):
     """The 37 x 21 x 29 sphere with holes and a crafted colour array (Wc = 0 scattered and in a slab, NaN and out-of-range channels), the
     fused volume of the integrate test, and a many-block volume (70 x 66 x 230: 1038 blocks): colours against the restatement bit for bit,
     the other arrays equal to icp_tsdf_mesh's; colors_out = NULL and the counting call."""
     from icp_amd import binding
-    from test_tsdf_color_host import crafted_sphere
     ctx = gpu_ctx_factory()
-    vol = crafted_sphere()
+    vol = TC.crafted_sphere()
     upload(ctx, vol)
     v, n, t, col = check_mesh(ctx, vol, 0.0, "sphere with holes")
     assert (col[:, 3] == 0).sum() > 20 and (col[:, 3] == 255).sum() > 500

@@ -7,16 +7,13 @@ import pytest
 
 import tsdf_restatement as TS
 import tsdf_mesh_restatement as TM
-import tsdf_outcome_fixture as OF
+from icp_amd.synth import tum_K
+from support import bits, upload
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 MINF = f32(-np.inf)
 ERR_INVALID_ARG = 1
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
 
 
 def check_against_restatement(ctx, vol, min_weight, what):
@@ -29,11 +26,6 @@ def check_against_restatement(ctx, vol, min_weight, what):
     assert np.array_equal(bits(v), bits(rv)), what
     assert np.array_equal(bits(n), bits(rn)), what
     return v, n, t
-
-
-def upload(ctx, vol):
-    ctx.tsdf_create(dims=(vol.nx, vol.ny, vol.nz), origin=tuple(float(x) for x in vol.o), voxel_size=float(vol.s))
-    ctx.tsdf_upload(vol.tsdf, vol.weight)
 
 
 SMALL = dict(dims=(37, 21, 29), s=0.05, origin=(-0.9, -0.5, -0.7))      # no multiple of a 64-voxel run, of nx or of a 1024-voxel block
@@ -86,7 +78,7 @@ def fused_volume(ctx):
     the restatement; returns the restatement's volume."""
     from icp_amd import binding, synth
     W, H = 40, 30
-    K = OF.tum_K(W)
+    K = tum_K(W)
     cam, rcam = binding.depth_camera(K, W, H), TS.Camera(K, W, H)
     opts = dict(dims=(37, 21, 29), origin=(-1.8, -1.0, -0.5), voxel_size=0.1, truncation=0.3, max_weight=2.0, min_depth=0.3, max_depth=2.4)
     ctx.tsdf_create(**opts)
@@ -182,7 +174,7 @@ def test_context_left_alone(gpu_ctx_factory):
     """icp_run on a resident pair gives identical records before and after icp_tsdf_mesh; params and the convergence measure do not change."""
     from icp_amd import binding, synth
     W, H = 160, 120
-    K = OF.tum_K(W)
+    K = tum_K(W)
     T = [synth.camera_pose(k) for k in range(2)]
     depth = [synth.depth_frame(Tk, K.astype(np.float64), W, H, 0x7A11 + k, 0.05)[0][:, 2].reshape(H, W).copy() for k, Tk in enumerate(T)]
     cam = binding.depth_camera(K, W, H)
@@ -215,7 +207,7 @@ def test_model_mesh_through_reconstruct_room(tmp_path, gpu_ctx_factory):
     pytest.importorskip("PIL")
     from icp_amd import binding, meshio, tum
     W, H = 80, 60
-    K = OF.tum_K(W)
+    K = tum_K(W)
     d = str(tmp_path / "seq")
     tum.write_synthetic_sequence(d, 3, width=W, height=H, K=K)
     seq = tum.load_sequence(d, frame_step=1, K=K)

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 import walk_restatement as wr
+from support import raw_bits as bits
 
 pytestmark = pytest.mark.gpu
 N = 4096
@@ -39,10 +40,6 @@ def call(c, leaves=None, nodes=None):
     assert rc == 0, rc
     out = (of[:, 0].copy(), oi[:, 0].copy(), oi[:, 1].copy(), of[:, 1].copy(), oi[:, 2].copy(), of[:, 2].copy()) if nl else None
     return out, oi[:, 3].copy(), bounds if nn else None, (float(empty[0]), float(empty[1]))
-
-
-def bits(a):
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 @pytest.mark.parametrize("category", wr.CATEGORIES)

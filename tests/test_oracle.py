@@ -9,12 +9,13 @@ import numpy as np
 import pytest
 from scipy.spatial import cKDTree
 
+from support import pose_of
+
 f32 = np.float32
 
 
 def rand_pose(rng, ang=0.2, tr=0.5):
-    from icp_amd import synth
-    return synth.make_pose(rng.uniform(-ang, ang, 3), rng.uniform(-tr, tr, 3)).astype(np.float32)
+    return pose_of(rng.uniform(-ang, ang, 3), rng.uniform(-tr, tr, 3))
 
 
 def np_knn3(q, t, max_dist):

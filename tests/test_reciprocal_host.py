@@ -8,14 +8,10 @@ import numpy as np
 
 import reciprocal_restatement as RC
 from device_asm import device_asm, kernel_resources
+from support import pose_of as rigid
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 f32 = np.float32
-
-
-def rigid(angles, t):
-    from icp_amd import synth
-    return synth.make_pose(angles, t).astype(f32)
 
 
 def test_restatement_against_fp64_on_separated_points():

@@ -13,24 +13,13 @@ import tsdf_color_restatement as TC
 import tsdf_mesh_restatement as TM
 import tsdf_restatement as TS
 from device_asm import device_asm, kernel_resources
+from icp_amd.synth import tum_K as small_K, wavy_depth
+from support import bits
+from tsdf_color_restatement import crafted_sphere
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 f32 = np.float32
 MINF = f32(-np.inf)
-
-
-def small_K(width):
-    s = width / 640.0
-    return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], f32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
-
-
-def wavy_depth(W, H, base=1.5):
-    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
-    return (base + 0.3 * np.sin(u * 0.3) + 0.2 * np.cos(v * 0.4) + 0.5 * (u > 0.7 * W)).astype(f32)
 
 
 def test_restated_geometry_equals_the_geometry_restatements():
@@ -307,21 +296,6 @@ def test_vertex_colour_kernel_in_lockstep_on_the_host(tmp_path):
     rnd.tsdf = rng.uniform(-1, 1, (13, 11, 19)).astype(f32); rnd.weight = rng.choice(np.array([0, 1, 1.5], f32), (13, 11, 19), p=[0.1, 0.3, 0.6])
     rnd.rgb = rng.uniform(0, 255, (13, 11, 19, 3)).astype(f32); rnd.wc = rng.choice(np.array([0, 1, 3], f32), (13, 11, 19), p=[0.3, 0.4, 0.3])
     run(rnd, 0.0); run(rnd, 1.5)
-
-
-def crafted_sphere():
-    """The 37 x 21 x 29 sphere with holes of the mesh tests and a crafted colour array."""
-    vol = TM.analytic_volume(TM.sphere((0.05, 0.02, 0.7), 0.4), dims=(37, 21, 29), s=0.05, origin=(-0.9, -0.5, -0.7))
-    rng = np.random.default_rng(11)
-    vol.weight[:, 9, :] = 0; vol.weight[rng.random(vol.weight.shape) < 0.02] = 0
-    vol.tsdf[rng.random(vol.tsdf.shape) < 0.01] = np.nan
-    vol.tsdf[5, 10, 12] = np.inf; vol.tsdf[20, 8, 30] = -np.inf; vol.tsdf[14, 3:8, 4:30] = 0.0
-    TC.add_color(vol)
-    vol.rgb = rng.uniform(-20, 280, vol.rgb.shape).astype(f32)                 # out-of-range channels: the clamp
-    vol.rgb[rng.random(vol.rgb.shape) < 0.01] = np.nan
-    vol.wc = rng.choice(np.array([0, 1, 2.5], f32), vol.wc.shape, p=[0.15, 0.5, 0.35])
-    vol.wc[:, :, 20:24] = 0
-    return vol
 
 
 def test_outcome_fixture_and_its_golden_file():

@@ -8,15 +8,11 @@ import numpy as np
 
 import tsdf_restatement as TS
 from device_asm import device_asm, kernel_resources
+from icp_amd.synth import tum_K as small_K
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 f32 = np.float32
 MINF = f32(-np.inf)
-
-
-def small_K(width):
-    s = width / 640.0
-    return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], f32)
 
 
 def voxel_centres(vol):

@@ -4,12 +4,9 @@ tests/test_gpu_walk_steps.py compares the device code with the same restatement.
 import numpy as np
 import pytest
 import walk_restatement as wr
+from support import raw_bits as bits
 
 N = 100_000
-
-
-def bits(a):
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 @pytest.mark.parametrize("category", wr.CATEGORIES)

@@ -20,11 +20,6 @@ ITERATIONS, MAX_DISTANCE, LAMBDA, GRADIENT_K = 35, 0.1, 0.968, 20
 GOLDEN = os.path.join(HERE, "golden", "tsdf_color_outcome.json")
 
 
-def tum_K(width):
-    s = width / 640.0
-    return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], f32)
-
-
 def texture(x, y):
     """The wall's colour at (x, y) [m], bytes per channel: smooth, deterministic, and not periodic over the field of view (incommensurate
     wavelengths along oblique directions); the shortest wavelength is 0.37 m, more than 9 voxels of 0.04 m."""
@@ -37,7 +32,8 @@ def texture(x, y):
 def fixture(n_frames=N_FRAMES):
     """(K, depth (n, H, W), rgbx (n, W*H, 4), gt: n - 1 transforms frame k -> frame 0).  The depth carries the sensor's noise (sigma 1 mm,
     seeded) and its 1/5000 m quantisation, so that no linear system is exactly singular."""
-    K = tum_K(W)
+    from icp_amd import synth
+    K = synth.tum_K(W)
     fx, fy, cx, cy = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]))
     u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
     depth, rgbx, gt = [], [], []

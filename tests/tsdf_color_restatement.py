@@ -176,3 +176,18 @@ def track(vol, frames, rgbx_frames, cam, pose0, source_of, estimate):
             integrate_color(vol, frames[k], rgbx_frames[k], cam, pose)
         poses.append(pose.copy())
     return poses
+
+
+def crafted_sphere():
+    """The 37 x 21 x 29 sphere with holes of the mesh tests and a crafted colour array."""
+    vol = TM.analytic_volume(TM.sphere((0.05, 0.02, 0.7), 0.4), dims=(37, 21, 29), s=0.05, origin=(-0.9, -0.5, -0.7))
+    rng = np.random.default_rng(11)
+    vol.weight[:, 9, :] = 0; vol.weight[rng.random(vol.weight.shape) < 0.02] = 0
+    vol.tsdf[rng.random(vol.tsdf.shape) < 0.01] = np.nan
+    vol.tsdf[5, 10, 12] = np.inf; vol.tsdf[20, 8, 30] = -np.inf; vol.tsdf[14, 3:8, 4:30] = 0.0
+    add_color(vol)
+    vol.rgb = rng.uniform(-20, 280, vol.rgb.shape).astype(f32)                 # out-of-range channels: the clamp
+    vol.rgb[rng.random(vol.rgb.shape) < 0.01] = np.nan
+    vol.wc = rng.choice(np.array([0, 1, 2.5], f32), vol.wc.shape, p=[0.15, 0.5, 0.35])
+    vol.wc[:, :, 20:24] = 0
+    return vol

@@ -15,15 +15,10 @@ SOURCE_FACTOR = 16
 GOLDEN = os.path.join(HERE, "golden", "tsdf_outcome.json")
 
 
-def tum_K(width):
-    s = width / 640.0
-    return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], f32)
-
-
 def fixture(n_frames=N_FRAMES):
     """(K, depth (n, H, W) with MINF holes, gt: n - 1 transforms frame k -> frame 0)."""
     from icp_amd import synth
-    K = tum_K(W)
+    K = synth.tum_K(W)
     T = [synth.camera_pose(0) @ synth.make_pose((0, np.deg2rad(1.5 * k), 0), (0.01 * k, 0, 0)) for k in range(n_frames)]
     depth = [synth.depth_frame(Tk, K.astype(np.float64), W, H, 0x7A11 + k, 0.05)[0][:, 2].reshape(H, W).copy() for k, Tk in enumerate(T)]
     gt = [(np.linalg.inv(T[0]) @ Tk).astype(f32) for Tk in T[1:]]
