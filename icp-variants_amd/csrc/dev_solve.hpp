@@ -245,8 +245,10 @@ struct SolveParams {
 // the compiler must keep the order (wave_sync).  Measured in the merged launch (tools/dev_ring_times.py): 2.8 us with twelve block barriers,
 // six sequential divisions in the back substitution and the rotation composed by one thread.
 __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+constexpr int SDF_COPY = 4;         // the instantiation of direct SDF tracking (dev_sdf.hpp); 0 .. 3: see dev_fpfh.hpp
+// x_out (SDF_COPY only, shared memory): the solved six-vector, for k_sdf_solve's stop test; every other instantiation ignores it.
 template <int COPY = 0>
-__device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* shared */, const float* pose_in) {
+__device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* shared */, const float* pose_in, double* x_out = nullptr) {
     __shared__ double A[6][7], Lm[6][6], od[6], zs[6], rd[6], hinv[6];
     __shared__ float npose[16];
     __shared__ int okflag, guardflag;
@@ -309,6 +311,9 @@ __device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* sh
 #pragma unroll
                 for (int c = r + 1; c < 6; c++) v = v - Lm[c][r] * x[c];
                 x[r] = v;
+            }
+            if constexpr (COPY == SDF_COPY) {
+                if (tid < 6) x_out[tid] = tid == 0 ? x[0] : tid == 1 ? x[1] : tid == 2 ? x[2] : tid == 3 ? x[3] : tid == 4 ? x[4] : x[5];
             }
             // angles -> sines and cosines: lanes 0..2 take one angle each, the six values travel as scalars (ICPOptimizer.h:768)
             const float ang = (float)(tid == 0 ? x[0] : tid == 1 ? x[1] : x[2]);

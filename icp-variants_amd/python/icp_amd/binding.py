@@ -96,6 +96,34 @@ def tsdf_options(dims=None, origin=None, **kw):
     return o
 
 
+class IcpSdfOptions(C.Structure):
+    _fields_ = [("stride", C.c_int32), ("n_iterations", C.c_int32), ("min_valid", C.c_int32), ("huber", C.c_float), ("stop_rotation", C.c_float),
+                ("stop_translation", C.c_float)]
+
+
+class IcpSdfIter(C.Structure):
+    _fields_ = [("n_valid", C.c_int32), ("status", C.c_int32), ("cost", C.c_double), ("pose", C.c_float * 16)]
+
+
+class IcpSdfFrame(C.Structure):
+    _fields_ = [("n_depth", C.c_int32), ("n_valid_first", C.c_int32), ("n_valid_last", C.c_int32), ("iterations", C.c_int32), ("status", C.c_int32),
+                ("cost_first", C.c_double), ("cost_last", C.c_double), ("pose", C.c_float * 16)]
+
+
+def sdf_options(**kw):
+    """icp_sdf_options: icp_sdf_options_default (stride 1, 20 iterations, min_valid 64, huber off, stops 1e-5 rad / 1e-5 m) with any field
+    overridden by name."""
+    o = IcpSdfOptions()
+    rc = load_library().icp_sdf_options_default(C.byref(o))
+    if rc != ICP_OK:
+        raise IcpError(rc, "icp_sdf_options_default")
+    for k, v in kw.items():
+        if not any(k == f[0] for f in IcpSdfOptions._fields_):
+            raise TypeError("icp_sdf_options has no field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
 class IcpLmOptions(C.Structure):
     _fields_ = [("initial_trust_region_radius", C.c_double), ("max_trust_region_radius", C.c_double), ("min_trust_region_radius", C.c_double),
                 ("min_relative_decrease", C.c_double), ("min_lm_diagonal", C.c_double), ("max_lm_diagonal", C.c_double),
@@ -259,6 +287,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_integrate", "icp_tsdf_raycast", "icp_set_target_tsdf", "icp_track_depth_model", "icp_tsdf_mesh",
            "icp_tsdf_color_create", "icp_tsdf_color_release", "icp_tsdf_color_download", "icp_tsdf_color_upload", "icp_tsdf_integrate_color",
            "icp_tsdf_raycast_color", "icp_set_target_tsdf_color", "icp_track_depth_model_color", "icp_tsdf_mesh_color",
+           "icp_sdf_options_default", "icp_sdf_options_check", "icp_tsdf_sample", "icp_tsdf_sdf_system", "icp_tsdf_align_depth", "icp_track_depth_sdf",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
@@ -912,6 +941,55 @@ class Context:
         else:
             rc = self.lib.icp_track_depth_model(self.h, _ptr(d), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
         if rc not in (ICP_OK, ERR_NO_TARGET, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
+            self._ck(rc)
+        return pose_from_c(p), [_record(out[i]) for i in range(nf - 1)], rc
+
+    def tsdf_sample(self, points):
+        """icp_tsdf_sample: the volume's field and its gradient at world points (n, 3).  Returns (F (n,), G (n, 3) per voxel, valid (n,)
+        bool: the point's cell lies inside the volume with all eight corners observed; elsewhere F and G read 0)."""
+        p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        n = len(p)
+        f = np.empty(n, np.float32); g = np.empty((n, 3), np.float32); ok = np.empty(n, np.uint8)
+        self._ck(self.lib.icp_tsdf_sample(self.h, _ptr(p), C.c_int32(n), _ptr(f), _ptr(g), _ptr(ok)))
+        return f, g, ok.astype(bool)
+
+    def tsdf_sdf_system(self, depth, cam, pose, options=None, **kw):
+        """icp_tsdf_sdf_system: the 28 sums of one direct SDF step of the frame at `pose` (4x4 camera -> world).  options: an
+        IcpSdfOptions, or the arguments of `sdf_options`.  Returns (sums (28,) float64, (n_depth, n_valid))."""
+        o = options if options is not None else sdf_options(**kw)
+        depth = _depth_in(depth, cam)
+        sums = np.empty(28, np.float64); cnt = (C.c_int32 * 2)()
+        self._ck(self.lib.icp_tsdf_sdf_system(self.h, _ptr(depth), C.byref(cam), _ptr(pose_to_c(pose)), C.byref(o), _ptr(sums), cnt))
+        return sums, (cnt[0], cnt[1])
+
+    def tsdf_align_depth(self, depth, cam, pose=None, trace=False, options=None, **kw):
+        """icp_tsdf_align_depth: one depth frame aligned to the volume itself, from `pose` (identity by default).  Returns (pose, record,
+        status), with trace=True (pose, record, status, the records of the iterations that ran); a failed frame (status NO_SOURCE or
+        NO_CORRESPONDENCES) returns the pose it started with."""
+        o = options if options is not None else sdf_options(**kw)
+        depth = _depth_in(depth, cam)
+        p = pose_to_c(np.eye(4) if pose is None else pose)
+        rec = IcpSdfFrame(); tr = (IcpSdfIter * o.n_iterations)() if trace else None
+        rc = self.lib.icp_tsdf_align_depth(self.h, _ptr(depth), C.byref(cam), C.byref(o), _ptr(p), C.byref(rec), tr)
+        if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # the frame's outcome: reported in the record
+            self._ck(rc)
+        r = _record(rec)
+        if trace:
+            return pose_from_c(p), r, rc, [_record(tr[i]) for i in range(r["iterations"])]
+        return pose_from_c(p), r, rc
+
+    def track_depth_sdf(self, depth_frames, cam, pose=None, rgbx_frames=None, options=None, **kw):
+        """icp_track_depth_sdf: direct SDF tracking over frames (n, h, w) against the context's TSDF volume: frame 0 integrated at `pose`
+        (identity by default), every later frame aligned to the volume and, when that succeeds, integrated at the pose found.
+        rgbx_frames (n, h*w, 4): the colours go into the volume's colour array as well.  Returns (final pose, records, status)."""
+        o = options if options is not None else sdf_options(**kw)
+        d = _depth_in(depth_frames, cam, sequence=True)
+        nf = d.shape[0]
+        p = pose_to_c(np.eye(4) if pose is None else pose)
+        cols = _rgbx_in(rgbx_frames, d.size, "colour frames must hold 4 bytes per pixel")
+        out = (IcpSdfFrame * max(nf - 1, 1))()
+        rc = self.lib.icp_track_depth_sdf(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(o), _ptr(p), out)
+        if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
             self._ck(rc)
         return pose_from_c(p), [_record(out[i]) for i in range(nf - 1)], rc
 

@@ -6,6 +6,7 @@ Pure host logic over `formats.py`; the tracking itself is one library call (`icp
   poses, recs    = track(ctx, seq, params)                    # estimatedPoses (currentCameraToWorld^-1 per frame) + per-frame records
   reconstruct_room(ctx, seq, params, out_dir)                 # track + saveRoomToFile per frame: mesh_<frame>.off (utils.h:179-193)
   reconstruct_room(..., model=..., model_mesh="model.ply")     # frame-to-model tracking, and the fused volume as one mesh
+  reconstruct_room(..., model=..., sdf=dict(stride=2))         # the same model, every frame aligned to the volume itself (direct SDF tracking)
 Layout on disk, as the reference expects it under Data/: <tum_dir>/depth.txt, rgb.txt, groundtruth.txt and the PNGs they list (TUM RGB-D).
 `write_synthetic_sequence` writes that layout from `synth.depth_frame` / `synth.camera_pose`, for the tests and for rehearsing a real
 freiburg1_xyz run offline.
@@ -71,7 +72,7 @@ def reconstruct_room_params(params, K=TUM_K, width=TUM_WIDTH, height=TUM_HEIGHT)
     return params
 
 
-def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None, reciprocal=None, model=None, options=None):
+def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None, reciprocal=None, model=None, options=None, sdf=None):
     """reconstructRoom's loop on the device.  params: the variant's icp_params (metric, matching, colour ICP, weighting, multires, ...;
     ctx.params when None); reconstruct_room_params then sets what reconstructRoom sets on top of them -- 35 iterations, max distance 0.1
     and, for projective matching, the sequence's camera.  Returns (camera poses: the identity for frame 0, then currentCameraToWorld^-1
@@ -89,7 +90,14 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     colour weighting or the colored metric.  That path sets fix_color_index on (a copy of) the source options itself, whatever the caller
     or reconstruct_room_options chose: the model holds each pixel's own bytes, and the library refuses a source with the reference's
     shifted ones.
-    options: (target, source) icp_depth_options instead of reconstruct_room_options' choice (the model path uses the source's only)."""
+    options: (target, source) icp_depth_options instead of reconstruct_room_options' choice (the model path uses the source's only).
+    sdf: None leaves every path above as it is.  With `model`, a dict of `binding.sdf_options` arguments (stride, n_iterations, min_valid,
+    huber, stop_rotation, stop_translation; an empty dict for the defaults) tracks every frame directly against the volume instead
+    (icp_track_depth_sdf): no ray-cast, no source cloud, no search, so the params, `options`, `with_gt` and the optimiser choices play no
+    part and the records are icp_sdf_frame's; with color=True in `model` the colour frames are fused as well.  `sdf` without `model` is a
+    ValueError."""
+    if sdf is not None and model is None:
+        raise ValueError("sdf tracking needs a model: pass model=dict(dims=..., origin=..., ...) as well")
     binding.select_optimizer(ctx, nonlinear)
     binding.select_convergence(ctx, convergence)
     binding.select_reciprocal(ctx, reciprocal)
@@ -104,6 +112,11 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
         rgbx = None
         if model.get("color"):
             rgbx = seq["rgbx"]
+        if sdf is not None:
+            _, recs, rc = ctx.track_depth_sdf(seq["depth"], cam, rgbx_frames=rgbx, **sdf)
+            poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
+            return poses, recs, rc
+        if model.get("color"):
             src_o = binding.depth_options(bool(src_o.keep_original_size), int(src_o.downsample_factor), float(src_o.max_distance), fix_color_index=True)
         _, recs, rc = ctx.track_depth_model(seq["depth"], cam, src_o, gt=seq["gt"] if with_gt else None, rgbx_frames=rgbx)
         poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
@@ -113,15 +126,15 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     return poses, recs, rc
 
 
-def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None, model_mesh=None):
+def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None, model_mesh=None, sdf=None):
     """reconstructRoom end to end: `track`, then saveRoomToFile (utils.h:179-193) for every scheduled frame k --
     joinMeshes(SimpleMesh(sensor, pose_k, edge_threshold) on the device, SimpleMesh::camera(pose_k, camera_scale), identity) with pose_k
     the camera pose `track` returned (the identity for frame 0).  With out_dir the meshes are written as mesh_<frame index>.off
     (getCurrentFrameCnt, VirtualSensor.h:142-144).  model: as `track` (frame-to-model tracking; the meshes stay per-frame depth meshes).
     model_mesh: with `model` and `out_dir`, a file name: the fused volume's zero level set (Context.tsdf_mesh, in frame 0's camera coordinates) is
     written there as a binary PLY after the last frame -- the reconstructed room as ONE mesh, with per-vertex colours when the model has them
-    (color=True in `model`); None writes nothing more.  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
-    poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model)
+    (color=True in `model`); None writes nothing more.  sdf: as `track` (direct SDF tracking against the model).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model, sdf=sdf)
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)

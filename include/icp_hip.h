@@ -717,6 +717,72 @@ int icp_tsdf_mesh_color(icp_ctx* ctx, float min_weight, int32_t max_vertices, in
                         float* vertices_out, float* normals_out, uint8_t* colors_out, uint32_t* triangles_out,
                         int32_t* n_vertices_out, int32_t* n_triangles_out);
 
+/* -------- direct SDF tracking (an extension): a depth frame aligned to the volume itself, without ray-cast, target cloud, index or search
+ * (Bylow, Sturm, Kerl, Kahl, Cremers, RSS 2013; Canelhas et al., IROS 2013).  DESIGN.md section 6q. --------
+ * The volume stores a signed distance and its gradient is the surface normal: a depth pixel moved into the world reads its residual and its
+ * normal from the eight voxels around it.  Each Gauss-Newton step is the library's point-to-plane step (row [q x g, g], right-hand side -r).
+ * Needs a volume and identity depth extrinsics as the calls above do; alignment never reads the colour array.  Target, source, index, params
+ * and convergence reference stay untouched.  All fp32 arithmetic is one rounding per operation in the order written; everything after the
+ * conversion to fp64 is fp64, one rounding per operation (tests/sdf_restatement.py restates it).
+ *
+ * Sampled pixels: (u, v) with u % stride == 0 and v % stride == 0.  A sampled pixel is USABLE iff its depth d is finite, d > 0 and
+ *   d <= max_depth (the integrate rule's tests); n_depth counts them.
+ * Field sample: a = ((float)u - cx) / fx, b = ((float)v - cy) / fy, x = a d, y = b d; q_r = (P_r0 x + (P_r1 y + P_r2 d)) + P_r3 with P the
+ *   camera -> world pose.  The cell of q, its validity, F and the analytic gradient (G_x, G_y, G_z) are the ray-cast's (above).  The pixel is
+ *   VALID iff it is usable, its cell is valid and fabsf(F) < 1: a NaN drops out, and a sample clamped at the free-space value carries no
+ *   gradient.  n_valid counts them.
+ * Terms, in fp64: r = (double)F (double)truncation [m]; g = (double)G ((double)truncation / (double)voxel_size);
+ *   J = (q_y g_z - q_z g_y, q_z g_x - q_x g_z, q_x g_y - q_y g_x, g_x, g_y, g_z) with q converted; w = 1, or with huber > 0:
+ *   w = |r| <= huber ? 1 : huber / |r|.
+ * Sums: 28 doubles -- (w J_i) J_j, the upper triangle of sum w J J^T, entry (i, j >= i) at i 6 - i (i - 1) / 2 + (j - i); the six
+ *   -((w J_i) r) at 21 + i; (w r) r at 27.  They are folded in a fixed order without floating-point atomics: bitwise reproducible run to
+ *   run; against another summation order each differs by at most n_valid 2^-52 sum |term|.
+ * Step: fails when n_valid < min_valid.  Else the 27 sums are solved as the point-to-plane metric solves its own (the LDL^T path; where
+ *   its rank guard refuses, the truncated eigen-solve), x = (alpha, beta, gamma, t), and pose <- dT pose with dT = [Rx Ry Rz | t] composed
+ *   in fp32 as there.  A non-finite x or pose fails the step.
+ * Stop: after a successful step, when every |angle| <= stop_rotation and every |t_i| <= stop_translation (fp64 x against the fp32 bounds);
+ *   either bound at 0 turns the stop off.  A frame ends at the stop, at a failed step, or after n_iterations; what is still enqueued of it
+ *   returns at once, and nothing crosses to the host between iterations.
+ * A frame FAILS with no usable pixel (ICP_ERR_NO_SOURCE) or a failed step (ICP_ERR_NO_CORRESPONDENCES): it carries the pose it started with. */
+typedef struct icp_sdf_options {
+    int32_t stride;                  /* >= 1, default 1 */
+    int32_t n_iterations;            /* 1 .. 1000, default 20 */
+    int32_t min_valid;               /* >= 6, default 64 */
+    float   huber;                   /* metres, >= 0, default 0 = off */
+    float   stop_rotation, stop_translation;   /* >= 0, default 1e-5 each */
+} icp_sdf_options;
+typedef struct icp_sdf_iter {
+    int32_t n_valid, status;         /* of the sums taken at the pose BEFORE the step; the step's status */
+    double  cost;                    /* sum w r r there */
+    float   pose[16];                /* the pose AFTER the step (a failed step: the pose it was taken at) */
+} icp_sdf_iter;
+typedef struct icp_sdf_frame {
+    int32_t n_depth, n_valid_first, n_valid_last, iterations, status;   /* iterations: the steps tried, a failed one included */
+    double  cost_first, cost_last;   /* sum w r r at the first and at the last pose the sums were taken at */
+    float   pose[16];
+} icp_sdf_frame;
+int icp_sdf_options_default(icp_sdf_options* opt);
+/* ICP_OK or ICP_ERR_INVALID_ARG; needs neither a context nor a device. */
+int icp_sdf_options_check(const icp_sdf_options* opt);
+/* The field and its gradient at n >= 0 world points (n x 3): f_out n floats, grad_out n x 3 floats (G, per voxel), valid_out n bytes (the
+ * cell is valid); any output may be NULL.  An invalid point reads F = 0, G = 0; a NaN is stored as the canonical quiet NaN 0x7FC00000. */
+int icp_tsdf_sample(icp_ctx* ctx, const float* points, int32_t n, float* f_out, float* grad_out, uint8_t* valid_out);
+/* The sums of ONE step at `pose`: sums_out 28 doubles, counts_out {n_depth, n_valid}; of opt only stride and huber matter. */
+int icp_tsdf_sdf_system(icp_ctx* ctx, const float* depth, const icp_depth_camera* cam, const float pose[16], const icp_sdf_options* opt,
+                        double* sums_out, int32_t* counts_out);
+/* Aligns one frame to the volume from pose_inout.  rec_out (optional): the frame's record; trace_out: NULL, or n_iterations records, those
+ * past the last step tried zeroed.  Returns the frame's status; a failed frame leaves pose_inout as it was. */
+int icp_tsdf_align_depth(icp_ctx* ctx, const float* depth, const icp_depth_camera* cam, const icp_sdf_options* opt, float pose_inout[16],
+                         icp_sdf_frame* rec_out, icp_sdf_iter* trace_out);
+/* Tracking: frame 0 is integrated at pose_inout; frame k >= 1 is aligned from the current pose and, on ICP_OK, integrated at the pose found
+ * (out[k - 1] its record).  A failed frame carries the pose, is not integrated, records its status, and tracking goes on; the first error
+ * in frame order is returned.  rgbx_frames: NULL, or the colour frames (n_frames x width*height*4 bytes) for a volume that has the colour
+ * array: integration is then icp_tsdf_integrate_color.  Frame k + 1 goes up while frame k iterates; the host reads one frame record per
+ * frame.  ICP_ERR_INVALID_ARG (see icp_last_error) for no volume, non-identity depth extrinsics, bad options, or rgbx_frames without a
+ * colour array. */
+int icp_track_depth_sdf(icp_ctx* ctx, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames, const icp_depth_camera* cam,
+                        const icp_sdf_options* opt, float pose_inout[16], icp_sdf_frame* out);
+
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
  * towards the viewpoint.  k in {3..8} (else ICP_ERR_INVALID_ARG).  Non-finite points, and every point of a cloud with fewer than

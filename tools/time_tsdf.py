@@ -2,7 +2,10 @@
   kernels : device time of one icp_tsdf_integrate and of one icp_tsdf_raycast launch (events around the launch, icp_debug_tsdf_time) for a
             256^3 and a 512^3 volume over the same 8.96 m cube (voxel 35 mm / 17.5 mm, truncation 5 voxels), from a volume holding 4 frames
   tracking: frames/s of icp_track_depth_model (256^3) against icp_track_depth_frames on the 12-frame sequence of
-            tools/time_depth_tracking.py, same params (point-to-plane k-NN on the LBVH, 35 iterations, max distance 0.1, source (false, 8))
+            tools/time_depth_tracking.py, same params (point-to-plane k-NN on the LBVH, 35 iterations, max distance 0.1, source (false, 8)),
+            and of icp_track_depth_sdf on the same sequence and volume at stride 1 with 20 iterations: `sdf` with the
+            default stops, `sdf_all` with the stops off (every frame runs its 20 iterations); sdf_pair_ms is the device time of ONE
+            k_sdf_accumulate + k_sdf_solve pair (icp_debug_sdf_time)
 Repeats are interleaved (every configuration once per round) and the median is reported.  Stage timing is off.
 usage: python tools/time_tsdf.py [--reps 9] [--frames 12] [--skip-512] [--json out.json]"""
 import argparse
@@ -77,14 +80,19 @@ def main():
     ctx.push_params(); ctx.set_stage_timing(0)
     to, so = tum.reconstruct_room_options(ctx.params)
     rgbx = np.zeros((a.frames, W * H, 4), np.uint8)
-    times = dict(model=[], frame0=[])
+    times = dict(model=[], frame0=[], sdf=[], sdf_all=[])
     err = {}
+    sdf_opt = dict(sdf=binding.sdf_options(stride=1, n_iterations=20), sdf_all=binding.sdf_options(stride=1, n_iterations=20, stop_rotation=0.0, stop_translation=0.0))
+    pair_ms = []
     for rep in range(a.reps + 1):
-        for route in ("model", "frame0"):
+        for route in ("model", "frame0", "sdf", "sdf_all"):
             t0 = time.perf_counter()
             if route == "model":
                 ctx.tsdf_create(**volume_options(256))
                 pose, recs, rc = ctx.track_depth_model(depth, cam, so)
+            elif route in sdf_opt:
+                ctx.tsdf_create(**volume_options(256))
+                pose, recs, rc = ctx.track_depth_sdf(depth, cam, options=sdf_opt[route])
             else:
                 pose, recs, rc = ctx.track_depth_frames(depth, None, cam, to, so)
             dt = time.perf_counter() - t0
@@ -92,8 +100,14 @@ def main():
                 times[route].append(dt)
             err[route] = dict(status=rc, iterations=[r["iterations"] for r in recs],
                               final_translation_error_m=float(np.linalg.norm(pose[:3, 3].astype(np.float64) - gt[-1][:3, 3])))
+        ms = C.c_float(0)                               # (the volume holds the sequence sdf_all has just fused)
+        ctx._ck(lib.icp_debug_sdf_time(ctx.h, binding._ptr(d2), C.byref(cam), binding._ptr(p2), C.byref(sdf_opt["sdf_all"]), C.byref(ms)))
+        if rep:
+            pair_ms.append(ms.value)
     n = a.frames - 1
     out["tracking"] = {k: dict(median_s=median(v), frames_per_s_median=n / median(v), frames_per_s_best=n / min(v), **err[k]) for k, v in times.items()}
+    out["tracking"]["sdf_pair_ms_median"] = median(pair_ms)
+    out["tracking"]["sdf_over_model"] = out["tracking"]["sdf_all"]["frames_per_s_median"] / out["tracking"]["model"]["frames_per_s_median"]
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
