@@ -246,7 +246,8 @@ struct SolveParams {
 // six sequential divisions in the back substitution and the rotation composed by one thread.
 __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 constexpr int SDF_COPY = 4;         // the instantiation of direct SDF tracking (dev_sdf.hpp); 0 .. 3: see dev_fpfh.hpp
-// x_out (SDF_COPY only, shared memory): the solved six-vector, for k_sdf_solve's stop test; every other instantiation ignores it.
+constexpr int SDF_COLOR_COPY = 5;   // and of its coloured form (dev_sdf_color.hpp): sharing SDF_COPY reordered two instructions of k_sdf_solve
+// x_out (the two SDF copies only, shared memory): the solved six-vector, for k_sdf_solve's stop test; every other instantiation ignores it.
 template <int COPY = 0>
 __device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* shared */, const float* pose_in, double* x_out = nullptr) {
     __shared__ double A[6][7], Lm[6][6], od[6], zs[6], rd[6], hinv[6];
@@ -312,7 +313,7 @@ __device__ __forceinline__ const float* p2plane_lanes_core(const double* m /* sh
                 for (int c = r + 1; c < 6; c++) v = v - Lm[c][r] * x[c];
                 x[r] = v;
             }
-            if constexpr (COPY == SDF_COPY) {
+            if constexpr (COPY == SDF_COPY || COPY == SDF_COLOR_COPY) {
                 if (tid < 6) x_out[tid] = tid == 0 ? x[0] : tid == 1 ? x[1] : tid == 2 ? x[2] : tid == 3 ? x[3] : tid == 4 ? x[4] : x[5];
             }
             // angles -> sines and cosines: lanes 0..2 take one angle each, the six values travel as scalars (ICPOptimizer.h:768)

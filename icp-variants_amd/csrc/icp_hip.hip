@@ -33,6 +33,7 @@
 #include "host_depth.hpp"
 #include "host_tsdf.hpp"
 #include "host_sdf.hpp"
+#include "host_sdf_color.hpp"
 #include "host_tsdf_mesh.hpp"
 #include "host_global.hpp"
 #include "host_debug.hpp"

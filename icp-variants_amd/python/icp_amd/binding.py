@@ -124,6 +124,45 @@ def sdf_options(**kw):
     return o
 
 
+class IcpSdfColorOptions(C.Structure):
+    _fields_ = [("weight", C.c_float), ("huber", C.c_float)]
+
+
+class IcpSdfColorIter(C.Structure):
+    _fields_ = [("n_valid", C.c_int32), ("n_color", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32), ("cost", C.c_double), ("cost_color", C.c_double),
+                ("pose", C.c_float * 16)]
+
+
+class IcpSdfColorFrame(C.Structure):
+    _fields_ = [("n_depth", C.c_int32), ("n_valid_first", C.c_int32), ("n_valid_last", C.c_int32), ("n_color_first", C.c_int32), ("n_color_last", C.c_int32),
+                ("iterations", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32), ("cost_first", C.c_double), ("cost_last", C.c_double),
+                ("cost_color_first", C.c_double), ("cost_color_last", C.c_double), ("pose", C.c_float * 16)]
+
+
+def sdf_color_options(**kw):
+    """icp_sdf_color_options: icp_sdf_color_options_default (weight 0.1 m per unit of intensity, huber off) with any field overridden by name."""
+    o = IcpSdfColorOptions()
+    rc = load_library().icp_sdf_color_options_default(C.byref(o))
+    if rc != ICP_OK:
+        raise IcpError(rc, "icp_sdf_color_options_default")
+    for k, v in kw.items():
+        if not any(k == f[0] for f in IcpSdfColorOptions._fields_):
+            raise TypeError("icp_sdf_color_options has no field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def _sdf_color_in(rgbx, n_pixels, color_weight, color_huber, message):
+    """(colour frame(s), IcpSdfColorOptions) of a direct SDF call with color_weight > 0, (.., None) with color_weight == 0."""
+    if not color_weight >= 0:
+        raise ValueError("color_weight must be >= 0")
+    if color_weight == 0:
+        return None, None
+    if rgbx is None:
+        raise ValueError("color_weight > 0 needs the colour frame(s)")
+    return _rgbx_in(rgbx, n_pixels, message), sdf_color_options(weight=color_weight, huber=color_huber)
+
+
 class IcpLmOptions(C.Structure):
     _fields_ = [("initial_trust_region_radius", C.c_double), ("max_trust_region_radius", C.c_double), ("min_trust_region_radius", C.c_double),
                 ("min_relative_decrease", C.c_double), ("min_lm_diagonal", C.c_double), ("max_lm_diagonal", C.c_double),
@@ -288,6 +327,8 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_color_create", "icp_tsdf_color_release", "icp_tsdf_color_download", "icp_tsdf_color_upload", "icp_tsdf_integrate_color",
            "icp_tsdf_raycast_color", "icp_set_target_tsdf_color", "icp_track_depth_model_color", "icp_tsdf_mesh_color",
            "icp_sdf_options_default", "icp_sdf_options_check", "icp_tsdf_sample", "icp_tsdf_sdf_system", "icp_tsdf_align_depth", "icp_track_depth_sdf",
+           "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
+           "icp_track_depth_sdf_color",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
@@ -953,24 +994,47 @@ class Context:
         self._ck(self.lib.icp_tsdf_sample(self.h, _ptr(p), C.c_int32(n), _ptr(f), _ptr(g), _ptr(ok)))
         return f, g, ok.astype(bool)
 
-    def tsdf_sdf_system(self, depth, cam, pose, options=None, **kw):
+    def tsdf_sample_color(self, points):
+        """icp_tsdf_sample_color: the intensity field S = R + G + B of the colour array and its gradient at world points (n, 3).  Returns
+        (S (n,), H (n, 3) per voxel, valid (n,) bool: the point's cell lies inside the volume with all eight corners coloured; elsewhere S
+        and H read 0)."""
+        p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        n = len(p)
+        f = np.empty(n, np.float32); g = np.empty((n, 3), np.float32); ok = np.empty(n, np.uint8)
+        self._ck(self.lib.icp_tsdf_sample_color(self.h, _ptr(p), C.c_int32(n), _ptr(f), _ptr(g), _ptr(ok)))
+        return f, g, ok.astype(bool)
+
+    def tsdf_sdf_system(self, depth, cam, pose, options=None, rgbx=None, color_weight=0.0, color_huber=0.0, **kw):
         """icp_tsdf_sdf_system: the 28 sums of one direct SDF step of the frame at `pose` (4x4 camera -> world).  options: an
-        IcpSdfOptions, or the arguments of `sdf_options`.  Returns (sums (28,) float64, (n_depth, n_valid))."""
+        IcpSdfOptions, or the arguments of `sdf_options`.  Returns (sums (28,) float64, (n_depth, n_valid)).
+        color_weight > 0 (with rgbx, the frame's colour frame): icp_tsdf_sdf_system_color, the joint system with the photometric term of
+        weight color_weight and Huber bound color_huber.  Returns (sums (29,), (n_depth, n_valid, n_color))."""
         o = options if options is not None else sdf_options(**kw)
         depth = _depth_in(depth, cam)
+        cols, co = _sdf_color_in(rgbx, depth.size, color_weight, color_huber, "colour frame must hold 4 bytes per pixel")
+        if co is not None:
+            sums = np.empty(29, np.float64); cnt = (C.c_int32 * 3)()
+            self._ck(self.lib.icp_tsdf_sdf_system_color(self.h, _ptr(depth), _ptr(cols), C.byref(cam), _ptr(pose_to_c(pose)), C.byref(o), C.byref(co), _ptr(sums), cnt))
+            return sums, (cnt[0], cnt[1], cnt[2])
         sums = np.empty(28, np.float64); cnt = (C.c_int32 * 2)()
         self._ck(self.lib.icp_tsdf_sdf_system(self.h, _ptr(depth), C.byref(cam), _ptr(pose_to_c(pose)), C.byref(o), _ptr(sums), cnt))
         return sums, (cnt[0], cnt[1])
 
-    def tsdf_align_depth(self, depth, cam, pose=None, trace=False, options=None, **kw):
+    def tsdf_align_depth(self, depth, cam, pose=None, trace=False, options=None, rgbx=None, color_weight=0.0, color_huber=0.0, **kw):
         """icp_tsdf_align_depth: one depth frame aligned to the volume itself, from `pose` (identity by default).  Returns (pose, record,
         status), with trace=True (pose, record, status, the records of the iterations that ran); a failed frame (status NO_SOURCE or
-        NO_CORRESPONDENCES) returns the pose it started with."""
+        NO_CORRESPONDENCES) returns the pose it started with.
+        color_weight > 0 (with rgbx): icp_tsdf_align_depth_color, every step with the photometric term; the records are the colour ones."""
         o = options if options is not None else sdf_options(**kw)
         depth = _depth_in(depth, cam)
         p = pose_to_c(np.eye(4) if pose is None else pose)
-        rec = IcpSdfFrame(); tr = (IcpSdfIter * o.n_iterations)() if trace else None
-        rc = self.lib.icp_tsdf_align_depth(self.h, _ptr(depth), C.byref(cam), C.byref(o), _ptr(p), C.byref(rec), tr)
+        cols, co = _sdf_color_in(rgbx, depth.size, color_weight, color_huber, "colour frame must hold 4 bytes per pixel")
+        if co is not None:
+            rec = IcpSdfColorFrame(); tr = (IcpSdfColorIter * o.n_iterations)() if trace else None
+            rc = self.lib.icp_tsdf_align_depth_color(self.h, _ptr(depth), _ptr(cols), C.byref(cam), C.byref(o), C.byref(co), _ptr(p), C.byref(rec), tr)
+        else:
+            rec = IcpSdfFrame(); tr = (IcpSdfIter * o.n_iterations)() if trace else None
+            rc = self.lib.icp_tsdf_align_depth(self.h, _ptr(depth), C.byref(cam), C.byref(o), _ptr(p), C.byref(rec), tr)
         if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # the frame's outcome: reported in the record
             self._ck(rc)
         r = _record(rec)
@@ -978,17 +1042,24 @@ class Context:
             return pose_from_c(p), r, rc, [_record(tr[i]) for i in range(r["iterations"])]
         return pose_from_c(p), r, rc
 
-    def track_depth_sdf(self, depth_frames, cam, pose=None, rgbx_frames=None, options=None, **kw):
+    def track_depth_sdf(self, depth_frames, cam, pose=None, rgbx_frames=None, options=None, color_weight=0.0, color_huber=0.0, **kw):
         """icp_track_depth_sdf: direct SDF tracking over frames (n, h, w) against the context's TSDF volume: frame 0 integrated at `pose`
         (identity by default), every later frame aligned to the volume and, when that succeeds, integrated at the pose found.
-        rgbx_frames (n, h*w, 4): the colours go into the volume's colour array as well.  Returns (final pose, records, status)."""
+        rgbx_frames (n, h*w, 4): the colours go into the volume's colour array as well.  Returns (final pose, records, status).
+        color_weight > 0 (with rgbx_frames): icp_track_depth_sdf_color, every frame aligned with the photometric term as well; the records
+        are the colour ones."""
         o = options if options is not None else sdf_options(**kw)
         d = _depth_in(depth_frames, cam, sequence=True)
         nf = d.shape[0]
         p = pose_to_c(np.eye(4) if pose is None else pose)
-        cols = _rgbx_in(rgbx_frames, d.size, "colour frames must hold 4 bytes per pixel")
-        out = (IcpSdfFrame * max(nf - 1, 1))()
-        rc = self.lib.icp_track_depth_sdf(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(o), _ptr(p), out)
+        cols, co = _sdf_color_in(rgbx_frames, d.size, color_weight, color_huber, "colour frames must hold 4 bytes per pixel")
+        if co is not None:
+            out = (IcpSdfColorFrame * max(nf - 1, 1))()
+            rc = self.lib.icp_track_depth_sdf_color(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(o), C.byref(co), _ptr(p), out)
+        else:
+            cols = _rgbx_in(rgbx_frames, d.size, "colour frames must hold 4 bytes per pixel")
+            out = (IcpSdfFrame * max(nf - 1, 1))()
+            rc = self.lib.icp_track_depth_sdf(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(o), _ptr(p), out)
         if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
             self._ck(rc)
         return pose_from_c(p), [_record(out[i]) for i in range(nf - 1)], rc

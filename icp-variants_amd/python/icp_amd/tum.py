@@ -7,6 +7,7 @@ Pure host logic over `formats.py`; the tracking itself is one library call (`icp
   reconstruct_room(ctx, seq, params, out_dir)                 # track + saveRoomToFile per frame: mesh_<frame>.off (utils.h:179-193)
   reconstruct_room(..., model=..., model_mesh="model.ply")     # frame-to-model tracking, and the fused volume as one mesh
   reconstruct_room(..., model=..., sdf=dict(stride=2))         # the same model, every frame aligned to the volume itself (direct SDF tracking)
+  reconstruct_room(..., model=dict(color=True, ...), sdf=dict(stride=4, color_weight=0.1))   # ... with the photometric term from the colour array
 Layout on disk, as the reference expects it under Data/: <tum_dir>/depth.txt, rgb.txt, groundtruth.txt and the PNGs they list (TUM RGB-D).
 `write_synthetic_sequence` writes that layout from `synth.depth_frame` / `synth.camera_pose`, for the tests and for rehearsing a real
 freiburg1_xyz run offline.
@@ -95,9 +96,13 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     huber, stop_rotation, stop_translation; an empty dict for the defaults) tracks every frame directly against the volume instead
     (icp_track_depth_sdf): no ray-cast, no source cloud, no search, so the params, `options`, `with_gt` and the optimiser choices play no
     part and the records are icp_sdf_frame's; with color=True in `model` the colour frames are fused as well.  `sdf` without `model` is a
-    ValueError."""
+    ValueError.  The dict may also hold color_weight (> 0) and color_huber: every frame is then aligned with the photometric term read from
+    the colour array as well (icp_track_depth_sdf_color; the records are icp_sdf_color_frame's), which holds the pose where the geometry
+    leaves it free; that needs color=True in `model`, else it is a ValueError."""
     if sdf is not None and model is None:
         raise ValueError("sdf tracking needs a model: pass model=dict(dims=..., origin=..., ...) as well")
+    if sdf is not None and sdf.get("color_weight", 0.0) != 0 and not model.get("color"):
+        raise ValueError("sdf tracking with color_weight needs a coloured model: pass color=True in model")
     binding.select_optimizer(ctx, nonlinear)
     binding.select_convergence(ctx, convergence)
     binding.select_reciprocal(ctx, reciprocal)

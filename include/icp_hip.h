@@ -721,7 +721,8 @@ int icp_tsdf_mesh_color(icp_ctx* ctx, float min_weight, int32_t max_vertices, in
  * (Bylow, Sturm, Kerl, Kahl, Cremers, RSS 2013; Canelhas et al., IROS 2013).  DESIGN.md section 6q. --------
  * The volume stores a signed distance and its gradient is the surface normal: a depth pixel moved into the world reads its residual and its
  * normal from the eight voxels around it.  Each Gauss-Newton step is the library's point-to-plane step (row [q x g, g], right-hand side -r).
- * Needs a volume and identity depth extrinsics as the calls above do; alignment never reads the colour array.  Target, source, index, params
+ * Needs a volume and identity depth extrinsics as the calls above do; the alignment of these geometric calls never reads the colour array
+ * (the calls of the next block do).  Target, source, index, params
  * and convergence reference stay untouched.  All fp32 arithmetic is one rounding per operation in the order written; everything after the
  * conversion to fp64 is fp64, one rounding per operation (tests/sdf_restatement.py restates it).
  *
@@ -782,6 +783,67 @@ int icp_tsdf_align_depth(icp_ctx* ctx, const float* depth, const icp_depth_camer
  * colour array. */
 int icp_track_depth_sdf(icp_ctx* ctx, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames, const icp_depth_camera* cam,
                         const icp_sdf_options* opt, float pose_inout[16], icp_sdf_frame* out);
+
+/* -------- direct SDF tracking with a photometric term (an extension): next to its geometric row a pixel adds an intensity row, read from
+ * the colour array in the cell the distance is read in (Bylow, Olsson, Kahl, "Direct Camera Pose Tracking and Mapping With Signed Distance
+ * Functions", 2014).  DESIGN.md section 6r. --------
+ * Where the geometry leaves the pose free (a flat wall) the calls above slide; the texture the volume holds pins it.  Needs the colour array
+ * (icp_tsdf_color_create) and the frame's colour frame next to whatever the calls above need.  Target, source, index, params and the
+ * convergence reference stay untouched.  tests/sdf_color_restatement.py restates what follows.
+ *
+ * Sampling: sampled, usable and valid pixels, q, the cell, F, G, r, g, J and w are exactly those above.  A pixel that is not valid there
+ *   contributes nothing here either.
+ * Intensity field: per corner k of q's cell, in fp32, s_k = (R_k + G_k) + B_k.  S is the nested lerp a + t (b - a) of s along x, then y,
+ *   then z; H = (H_x, H_y, H_z) is the analytic gradient of that interpolant per voxel, of G's form with s in place of the distances.
+ * Colour validity: a valid pixel is COLOURED iff all eight corners have Wc > 0 and S is finite; n_color counts them.  A valid pixel that
+ *   is not coloured contributes its geometric row only.
+ * Terms, in fp64 after the conversions, one rounding per operation: I_p = (double)(R + G + B) / 765.0 from the sampled pixel's own bytes
+ *   rgbx[4 (v width + u) + 0..2] (colored ICP's intensity); r_c = (double)S / 765.0 - I_p; h = (double)H / (765.0 * (double)voxel_size);
+ *   J_c = (q x h, h) with q converted -- J's shape, because both fields are read at the same moved point; w_c = weight^2, with huber > 0
+ *   (of icp_sdf_color_options, in intensity units) multiplied by (|r_c| <= huber ? 1 : huber / |r_c|); weight and huber converted from fp32.
+ *   `weight` is in metres per unit of intensity, so both residuals are lengths.
+ * Sums: 29 doubles.  Entries 0 .. 27 have the layout above for the joint system, each lane term the geometric term + the photometric term
+ *   in that order: (w J_i) J_j + (w_c Jc_i) Jc_j, -((w J_i) r) + -((w_c Jc_i) r_c), (w r) r + (w_c r_c) r_c; a pixel that is not coloured
+ *   contributes the geometric term alone.  Entry 28 is (w_c r_c) r_c alone.  Counts: {n_depth, n_valid, n_color}.  The fold order is fixed,
+ *   without floating-point atomics: bitwise reproducible; against another order each sum differs by at most
+ *   (n_valid + n_color) 2^-52 sum (|geometric term| + |photometric term|).
+ * Step, stop, failure, statuses and pose composition: those above, unchanged, on the entries 0 .. 26. */
+typedef struct icp_sdf_color_options {
+    float weight;                    /* metres per unit of intensity, finite and > 0 (a zero weight belongs to the calls above), default 0.1 */
+    float huber;                     /* intensity units, finite and >= 0, default 0 = off */
+} icp_sdf_color_options;
+typedef struct icp_sdf_color_iter {
+    int32_t n_valid, n_color, status, pad;   /* as icp_sdf_iter; pad 0 */
+    double  cost, cost_color;        /* entry 27 and entry 28 of the sums */
+    float   pose[16];
+} icp_sdf_color_iter;
+typedef struct icp_sdf_color_frame {
+    int32_t n_depth, n_valid_first, n_valid_last, n_color_first, n_color_last, iterations, status, pad;
+    double  cost_first, cost_last, cost_color_first, cost_color_last;
+    float   pose[16];
+} icp_sdf_color_frame;
+#ifdef __cplusplus
+static_assert(sizeof(icp_sdf_color_options) == 8, "icp_sdf_color_options");
+static_assert(sizeof(icp_sdf_color_iter) == 96, "icp_sdf_color_iter");
+static_assert(sizeof(icp_sdf_color_frame) == 128, "icp_sdf_color_frame");
+#endif
+int icp_sdf_color_options_default(icp_sdf_color_options* opt);
+/* ICP_OK or ICP_ERR_INVALID_ARG; needs neither a context nor a device. */
+int icp_sdf_color_options_check(const icp_sdf_color_options* opt);
+/* The intensity field and its gradient at n >= 0 world points: s_out n floats (S), grad_out n x 3 floats (H, per voxel), valid_out n bytes:
+ * the cell lies inside the volume and its eight Wc > 0 (the geometry's weights play no part); any output may be NULL.  An invalid point
+ * reads 0; a NaN is stored as the canonical quiet NaN, as in icp_tsdf_sample. */
+int icp_tsdf_sample_color(icp_ctx* ctx, const float* points, int32_t n, float* s_out, float* grad_out, uint8_t* valid_out);
+/* The sums of ONE joint step at `pose`: sums_out 29 doubles, counts_out {n_depth, n_valid, n_color}; of opt only stride and huber matter. */
+int icp_tsdf_sdf_system_color(icp_ctx* ctx, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const float pose[16],
+                              const icp_sdf_options* opt, const icp_sdf_color_options* copt, double* sums_out, int32_t* counts_out);
+/* icp_tsdf_align_depth with the photometric term. */
+int icp_tsdf_align_depth_color(icp_ctx* ctx, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const icp_sdf_options* opt,
+                               const icp_sdf_color_options* copt, float pose_inout[16], icp_sdf_color_frame* rec_out, icp_sdf_color_iter* trace_out);
+/* icp_track_depth_sdf with the coloured alignment; integration is always icp_tsdf_integrate_color.  All four calls: ICP_ERR_INVALID_ARG
+ * (see icp_last_error) for no volume, no colour array, a null colour frame, bad options of either kind, non-identity depth extrinsics. */
+int icp_track_depth_sdf_color(icp_ctx* ctx, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames, const icp_depth_camera* cam,
+                              const icp_sdf_options* opt, const icp_sdf_color_options* copt, float pose_inout[16], icp_sdf_color_frame* out);
 
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
