@@ -1,6 +1,6 @@
 // host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
 // and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
-// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_sdf, host_sdf_color, host_tsdf_mesh, host_global, host_debug.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_sdf, host_vgicp, host_sdf_color, host_tsdf_mesh, host_global, host_debug.
 using namespace icpdev;
 
 #define HIPCK(ctx, expr)                                                                        \
@@ -151,6 +151,8 @@ struct icp_ctx {
     DevBuf tsdf_col; bool tsdf_col_on = false;   // its optional colour array (icp_tsdf_color_create): one float4 (R, G, B, Wc) per voxel, 16 bytes, the indexing of tsdf_vox
     DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
     DevBuf sdf_state, sdf_partials, sdf_rec; Event sdf_ev;   // direct SDF tracking (host_sdf.hpp, host_sdf_color.hpp): the pose / stop state, partials[28 or 29][blocks] + counts[2 or 3][blocks], the frame record + trace; "the last integration has left its upload slot"
+    DevBuf vg_box, vg_count, vg_sums, vg_cells;   // voxelized GICP (host_vgicp.hpp): the target's voxel grid -- bounds + counters, per cell the count, the nine int64 sums, the 40-byte record
+    bool vg_ready = false; float vg_voxel = 0.f; icp_voxel_grid_info vg_info = {{0, 0, 0}, {0, 0, 0}, 0, 0};   // the grid is current for vg_voxel (dropped with the target's GICP normal cache); its extent
     float cos_reject = 0.5f;
     std::vector<Event> events;
     Event build_ev[2];                   // index-build bracket (build_bvh)

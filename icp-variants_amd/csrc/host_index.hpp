@@ -248,7 +248,7 @@ int finish_target(icp_ctx* c, bool with_colors) {
     Bvh& b = c->bvh;
     c->bvh6.valid = false;
     b.valid = false; b.n_valid = 0;
-    c->gicp_ready[0] = false;
+    c->gicp_ready[0] = false; c->vg_ready = false;
     c->col_ready = false;
     c->fpfh[0].ready = false;
     if ((rc = finite_list(c, c->tgt, false, c->tgt_flag, c->tgt_finite, &b.n_valid))) return rc;

@@ -8,7 +8,7 @@
 //
 // Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_converge.hpp, dev_solve.hpp,
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
-// dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf_color.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp, dev_sdf.hpp, dev_sdf_color.hpp
+// dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf_color.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp, dev_sdf.hpp, dev_sdf_color.hpp, dev_vgicp.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -55,6 +55,8 @@
 //   k_sdf_solve         from the volume's field and gradient, and the fold, solve and pose update behind them (dev_sdf.hpp)
 //   k_sdf_*_color       the same with a photometric row per coloured pixel, read from the colour array in the distance's cell
 //                       (icp_tsdf_align_depth_color, icp_track_depth_sdf_color; dev_sdf_color.hpp)
+//   k_vg_* /            voxelized GICP (icp_voxelize_target, icp_vgicp_align): the target as a dense grid of cells built from integer sums,
+//   k_vgicp_accumulate  and a source point's plane-to-plane sums against the one cell it falls in; k_sdf_solve behind them (dev_vgicp.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -92,5 +94,6 @@ namespace icpdev {
 #include "dev_tsdf_mesh_color.hpp"
 #include "dev_sdf.hpp"
 #include "dev_sdf_color.hpp"
+#include "dev_vgicp.hpp"
 
 }  // namespace icpdev

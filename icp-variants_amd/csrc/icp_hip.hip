@@ -33,6 +33,7 @@
 #include "host_depth.hpp"
 #include "host_tsdf.hpp"
 #include "host_sdf.hpp"
+#include "host_vgicp.hpp"
 #include "host_sdf_color.hpp"
 #include "host_tsdf_mesh.hpp"
 #include "host_global.hpp"
@@ -152,7 +153,7 @@ int icp_set_gicp_options(icp_ctx* c, const icp_gicp_options* o) {
         c->err = "icp_set_gicp_options: need 0 < epsilon <= 1 and covariance_k in {0, 5, 10, 20}"; return ICP_ERR_INVALID_ARG;
     }
     c->gicp_opt = v;
-    c->gicp_ready[0] = c->gicp_ready[1] = false;
+    c->gicp_ready[0] = c->gicp_ready[1] = false; c->vg_ready = false;
     return ICP_OK;
 }
 int icp_get_gicp_options(const icp_ctx* c, icp_gicp_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->gicp_opt; return ICP_OK; }

@@ -124,6 +124,29 @@ def sdf_options(**kw):
     return o
 
 
+class IcpVgicpOptions(C.Structure):
+    _fields_ = [("voxel_size", C.c_float), ("min_points", C.c_int32), ("n_iterations", C.c_int32), ("min_valid", C.c_int32), ("stop_rotation", C.c_float),
+                ("stop_translation", C.c_float)]
+
+
+class IcpVoxelGridInfo(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("n_occupied", C.c_int32), ("n_points", C.c_int32)]
+
+
+def vgicp_options(**kw):
+    """icp_vgicp_options: icp_vgicp_options_default (voxel 0.25 m, min_points 1, 30 iterations, min_valid 64, stops 1e-5 rad / 1e-5 m) with
+    any field overridden by name."""
+    o = IcpVgicpOptions()
+    rc = load_library().icp_vgicp_options_default(C.byref(o))
+    if rc != ICP_OK:
+        raise IcpError(rc, "icp_vgicp_options_default")
+    for k, v in kw.items():
+        if not any(k == f[0] for f in IcpVgicpOptions._fields_):
+            raise TypeError("icp_vgicp_options has no field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
 class IcpSdfColorOptions(C.Structure):
     _fields_ = [("weight", C.c_float), ("huber", C.c_float)]
 
@@ -329,6 +352,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_sdf_options_default", "icp_sdf_options_check", "icp_tsdf_sample", "icp_tsdf_sdf_system", "icp_tsdf_align_depth", "icp_track_depth_sdf",
            "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
            "icp_track_depth_sdf_color",
+           "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
@@ -1063,6 +1087,47 @@ class Context:
         if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
             self._ck(rc)
         return pose_from_c(p), [_record(out[i]) for i in range(nf - 1)], rc
+
+    def voxelize_target(self, options=None, **kw):
+        """icp_voxelize_target: the voxel grid of the resident target (voxelized GICP), built on the device and kept in the context.
+        options: an IcpVgicpOptions, or the arguments of `vgicp_options`.  Returns dict(lo, dims, n_occupied, n_points)."""
+        o = options if options is not None else vgicp_options(**kw)
+        info = IcpVoxelGridInfo()
+        self._ck(self.lib.icp_voxelize_target(self.h, C.byref(o), C.byref(info)))
+        self._vg_dims = tuple(info.dims)
+        return dict(lo=tuple(info.lo), dims=tuple(info.dims), n_occupied=info.n_occupied, n_points=info.n_points)
+
+    def voxel_grid(self, options=None, **kw):
+        """icp_get_voxel_grid of the grid `voxelize_target` gives for these options (built if it is not current): (info, counts (n_cells,)
+        int32, sums (n_cells, 9) int64, cells (n_cells, 9) float32), cell index (z dims_y + y) dims_x + x."""
+        info = self.voxelize_target(options, **kw)
+        n = int(np.prod(info["dims"], dtype=np.int64))
+        counts = np.empty(n, np.int32); sums = np.empty((n, 9), np.int64); cells = np.empty((n, 9), np.float32)
+        self._ck(self.lib.icp_get_voxel_grid(self.h, _ptr(counts), _ptr(sums), _ptr(cells)))
+        return info, counts, sums, cells
+
+    def vgicp_system(self, pose, options=None, **kw):
+        """icp_vgicp_system: the 28 sums of one voxelized GICP step of the resident source at `pose`.  Returns (sums (28,) float64,
+        (considered, valid))."""
+        o = options if options is not None else vgicp_options(**kw)
+        sums = np.empty(28, np.float64); cnt = (C.c_int32 * 2)()
+        self._ck(self.lib.icp_vgicp_system(self.h, _ptr(pose_to_c(pose)), C.byref(o), _ptr(sums), cnt))
+        return sums, (cnt[0], cnt[1])
+
+    def vgicp_align(self, pose=None, trace=False, options=None, **kw):
+        """icp_vgicp_align: the resident source aligned to the voxel grid of the resident target, from `pose` (identity by default).
+        Returns (pose, record, status) and, with trace, the records of the steps tried.  A failed alignment (status ERR_NO_SOURCE or
+        ERR_NO_CORRESPONDENCES) returns the pose it started with; every other error raises."""
+        o = options if options is not None else vgicp_options(**kw)
+        p = pose_to_c(np.eye(4) if pose is None else pose)
+        rec = IcpSdfFrame(); tr = (IcpSdfIter * o.n_iterations)() if trace else None
+        rc = self.lib.icp_vgicp_align(self.h, C.byref(o), _ptr(p), C.byref(rec), tr, C.c_int32(o.n_iterations if trace else 0))
+        if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # the alignment's outcome: reported in the record
+            self._ck(rc)
+        r = _record(rec)
+        if trace:
+            return pose_from_c(p), r, rc, [_record(tr[i]) for i in range(r["iterations"])]
+        return pose_from_c(p), r, rc
 
     def estimate_normals(self, xyz, k=5, viewpoint=(0.0, 0.0, 0.0)):
         """PointCloud(pcl cloud): k-NN PCA normals flipped towards the viewpoint (PointCloud.h:41-76)."""

@@ -56,7 +56,7 @@ def prepare_pair(ctx, src_xyz, tgt_xyz, benchmark_pose, pose_scaling=0.1, k=5):
                 gt=np.linalg.inv(np.asarray(S, np.float64)), initial=S)
 
 
-def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="identity", reciprocal=None, **global_options):
+def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="identity", reciprocal=None, vgicp=None, **global_options):
     """estimatePose of alignETH (main.cpp:457) on a prepared pair with the context's params: the optimiser the reference's
     USE_LINEAR_ICP picks (main.cpp:26) -- nonlinear True (or an IcpLmOptions): CeresICPOptimizer, False: LinearICPOptimizer, None: the
     context's current choice.  convergence: dict(rotation=..., translation=...[, min_iterations, patience]) stops the run on a converged
@@ -66,6 +66,9 @@ def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="iden
     initial: "identity" starts the run from the identity, as the reference does; "global" starts it from the best pose of the global
     registration (Context.register_global with **global_options: FPFH features, feature matching, RANSAC), for pairs whose initial pose
     is not roughly known.  (globalreg.align refines several RANSAC poses at once instead, where multi-start ICP is available.)
+    vgicp: None aligns through icp_run, every path as it was; dict(voxel_size=..., ...) (the fields of binding.vgicp_options) aligns the
+    source to a voxel grid of the target instead (Context.vgicp_align: voxelized GICP with the context's GICP options, no index walk, no
+    search) and returns (4x4 pose, [the alignment's record], status); with check, a failed alignment raises.
     Returns (4x4 pose, per-iteration records, status)."""
     from . import binding
     if initial not in ("identity", "global"):
@@ -82,6 +85,11 @@ def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="iden
     if initial == "global":
         ctx.set_global_options(**global_options)
         start = ctx.register_global()[0][0]
+    if vgicp is not None:
+        pose, rec, rc = ctx.vgicp_align(start, options=binding.vgicp_options(**vgicp))
+        if check and rc != binding.ICP_OK:
+            raise binding.IcpError(rc, ctx.lib.icp_last_error(ctx.h).decode())
+        return pose, [rec], rc
     return ctx.run(start, check=check)
 
 

@@ -845,6 +845,81 @@ int icp_tsdf_align_depth_color(icp_ctx* ctx, const float* depth, const uint8_t* 
 int icp_track_depth_sdf_color(icp_ctx* ctx, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames, const icp_depth_camera* cam,
                               const icp_sdf_options* opt, const icp_sdf_color_options* copt, float pose_inout[16], icp_sdf_color_frame* out);
 
+/* -------- voxelized GICP (an extension): the resident source aligned to a voxel grid of the resident target, without index or search
+ * (Koide, Yokozuka, Oishi, Banno, "Voxelized GICP for Fast and Accurate 3D Point Cloud Registration", ICRA 2021).  DESIGN.md section 6s. --------
+ * The target is reduced once to a dense grid of cells, each a mean and a normalised sum of plane covariances; a moved source point looks up
+ * the ONE cell it falls in and is scored by GICP's plane-to-plane Mahalanobis distance against it.  epsilon and the covariance
+ * neighbourhood are the context's icp_gicp_options; the per-point normals are the cached GICP normals of both clouds (icp_get_gicp_normals;
+ * covariance_k = 0: the clouds' own normals, which both clouds must then have).  Target, source, index, params, convergence reference and
+ * the TSDF volume stay untouched.  tests/vgicp_restatement.py restates what follows.
+ *
+ * Entering points: a target point enters the grid iff its position and its GICP normal are finite.
+ * Cell of a point: per axis c_a = (int)clamp(floorf(p_a / voxel_size), -2^30, 2^30) -- one fp32 division, one rounding; the clamp keeps the
+ *   conversion defined for every finite p.
+ * Extent: lo_a = min c_a over the entering points, dims_a = max c_a - lo_a + 1; the cell of coordinates c has the index
+ *   ((c_z - lo_z) dims_y + (c_y - lo_y)) dims_x + (c_x - lo_x).  dims_x dims_y dims_z <= 2^24, else ICP_ERR_INVALID_ARG with a message that
+ *   names the voxel size (the grid is dense).  No entering point: ICP_ERR_NO_TARGET.
+ * Integer sums per cell (exact in any order: the build uses integer atomics and keeps its bits): count (int32); sum q_a with
+ *   q_a = lrintf(clamp(((p_a - ((float)c_a + 0.5f) voxel_size) / voxel_size) 65536.0f, -32768, 32768)), every fp32 operation rounded once;
+ *   sum m_a m_b for (a, b) = xx xy xz yy yz zz with m_a = lrintf(clamp(n_a, -2, 2) 16384.0f) (the clamp changes nothing for a unit normal;
+ *   it keeps the products in range for any finite one).  Nine int64 per cell, in that order.
+ * Record per cell, fp64 rounded once to fp32, nine floats (mu_x mu_y mu_z S_xx S_xy S_xz S_yy S_yz S_zz):
+ *   mu_a = ((double)c_a + 0.5) (double)voxel_size + ((double)sum q_a / (double)count) ((double)voxel_size / 65536.0);
+ *   S_ab = (double)sum m_a m_b / (double)(sum m_x m_x + sum m_y m_y + sum m_z m_z): a unit trace, eigenvalues in [0, 1] whatever the
+ *   quantisation did, so Sigma below is positive definite for every legal epsilon.  An integer trace of 0 (normals shorter than 2^-15):
+ *   S = 0.  An empty cell: count 0, nine zeros.
+ * One source point at pose P: p = the fp32 point as icp_transform_points moves it; b = the source's GICP normal as icp_transform_normals
+ *   moves it, normalised in fp64 (fp32 components converted, len = sqrt((b_x b_x + b_y b_y) + b_z b_z), b / len).  The point is CONSIDERED
+ *   iff its own position is finite.  It is VALID iff it is considered, p is finite, the cell of p lies inside the grid, that cell's count
+ *   >= min_points, and b is finite with len > 0.  Then in fp64, one rounding per operation: r = mu - p;
+ *   Sigma_aa = 2 - (1 - eps)(S_aa + b_a b_a), Sigma_ab = -((1 - eps)(S_ab + b_a b_b)), eps converted from fp32; M = adj(Sigma) / det(Sigma)
+ *   entry by entry as GICP's; J = [A | I] with A = -[p]x; N = (double)count.
+ * Sums: 28 doubles in icp_tsdf_sdf_system's layout: N (J^T M J)_ij for j >= i at i 6 - i (i - 1) / 2 + (j - i); N (J^T M r)_i at 21 + i;
+ *   N r^T M r at 27.  Counts: {considered, valid}.  Folded in a fixed order without floating-point atomics: bitwise reproducible; against
+ *   another summation order each sum differs by at most n_valid 2^-52 sum |term|.
+ * Step, stop and failure are direct SDF tracking's (above) on these sums: a step fails with fewer than min_valid valid points or a
+ *   non-finite solution; otherwise the point-to-plane solve and the fp32 composition dT pose; the stop test is made on the solved six-vector
+ *   after a successful step; what is still enqueued behind the end returns at once, and nothing crosses to the host between iterations.
+ *   A failed alignment returns the pose it started with and ICP_ERR_NO_CORRESPONDENCES (ICP_ERR_NO_SOURCE when no point is considered). */
+typedef struct icp_vgicp_options {
+    float   voxel_size;              /* metres, finite and > 0, default 0.25 */
+    int32_t min_points;              /* >= 1, default 1: a cell with fewer target points scores nothing */
+    int32_t n_iterations;            /* 1 .. 1000, default 30 */
+    int32_t min_valid;               /* >= 6, default 64 */
+    float   stop_rotation, stop_translation;   /* >= 0, default 1e-5 each; either at 0 turns the stop off */
+} icp_vgicp_options;
+typedef struct icp_voxel_grid_info {
+    int32_t lo[3], dims[3];          /* the extent in cells */
+    int32_t n_occupied, n_points;    /* cells with count > 0; target points that entered */
+} icp_voxel_grid_info;
+/* The records are direct SDF tracking's, field for field: n_depth counts the CONSIDERED points, n_valid_* the valid ones. */
+typedef icp_sdf_iter icp_vgicp_iter;
+typedef icp_sdf_frame icp_vgicp_record;
+#ifdef __cplusplus
+static_assert(sizeof(icp_vgicp_options) == 24, "icp_vgicp_options");
+static_assert(sizeof(icp_voxel_grid_info) == 32, "icp_voxel_grid_info");
+#endif
+int icp_vgicp_options_default(icp_vgicp_options* opt);
+/* ICP_OK or ICP_ERR_INVALID_ARG; needs neither a context nor a device. */
+int icp_vgicp_options_check(const icp_vgicp_options* opt);
+/* Builds the grid of the resident target at opt->voxel_size (computing the target's GICP normals if their cache is cold) and keeps it in
+ * the context; info_out is optional.  Whatever drops the target's GICP normal cache drops the grid: every call that replaces the target,
+ * and icp_set_gicp_options.  A grid that is current for this voxel size is not rebuilt. */
+int icp_voxelize_target(icp_ctx* ctx, const icp_vgicp_options* opt, icp_voxel_grid_info* info_out);
+/* The grid icp_voxelize_target (or an alignment) left: counts_out one int32 per cell, sums_out nine int64 per cell, cells_out nine floats
+ * per cell; any pointer may be NULL.  ICP_ERR_INVALID_ARG without a current grid. */
+int icp_get_voxel_grid(icp_ctx* ctx, int32_t* counts_out, int64_t* sums_out, float* cells_out);
+/* The sums of ONE step of the resident source at `pose`: sums_out 28 doubles, counts_out {considered, valid}; of opt only voxel_size and
+ * min_points matter (the others must still be legal).  Builds the grid if there is none for this voxel size. */
+int icp_vgicp_system(icp_ctx* ctx, const float pose[16], const icp_vgicp_options* opt, double* sums_out, int32_t* counts_out);
+/* Aligns the resident source to the grid from pose_inout: builds the grid if there is none or voxel_size changed, enqueues n_iterations x
+ * (accumulate, solve) at once, stops on the device and reads ONE record back.  rec_out is optional; trace_out: NULL, or max_trace records,
+ * of which min(max_trace, n_iterations) are written, those past the last step tried zeroed.  Returns the record's status.  Refuses with a
+ * reason (icp_last_error): no target (ICP_ERR_NO_TARGET), no source (ICP_ERR_NO_SOURCE), bad options, covariance_k = 0 with a cloud
+ * that has no normals, a grid of more than 2^24 cells (ICP_ERR_INVALID_ARG). */
+int icp_vgicp_align(icp_ctx* ctx, const icp_vgicp_options* opt, float pose_inout[16], icp_vgicp_record* rec_out, icp_vgicp_iter* trace_out,
+                    int32_t max_trace);
+
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
  * towards the viewpoint.  k in {3..8} (else ICP_ERR_INVALID_ARG).  Non-finite points, and every point of a cloud with fewer than
