@@ -124,7 +124,8 @@ def check_system(ctx, vol, cam, rcam, depth, pose, what, **kw):
 def test_system_matches_restatement(gpu_ctx_factory):
     """The sums of one step: counts exactly; every sum within n_valid 2^-52 sum |term| of the restatement's, the bound for any summation
     order of fp64 terms that are themselves identical; two calls give identical bits.  40 x 30 at strides 1 and 3 (3 does not divide 40:
-    partial tiles, one block and several), huber 0 and 0.05, two poses; 70 x 50 at stride 1: 5 x 4 blocks, partial tiles on both axes."""
+    partial tiles, one block and several), huber 0 and 0.05, two poses; 70 x 50 at stride 1: 5 x 4 blocks, partial tiles on both axes.
+    That is 6 and 20 blocks (1 at stride 3): k_sdf_solve's fold beyond 64, 256 and 512 blocks is tests/test_gpu_fold_sizes.py's."""
     from icp_amd import binding
     ctx = gpu_ctx_factory()
     vol, cam, rcam = small_model(ctx)

@@ -167,7 +167,8 @@ def test_system_matches_restatement(gpu_ctx_factory):
     |photometric term|) of the restatement's, the bound for any summation order of fp64 terms that are themselves identical; two calls give
     identical bits.  13 x 11: one block with a partial tile; 75 x 58: 5 x 4 blocks with partial tiles on both axes; strides 1 and 3; the
     geometric Huber and the colour Huber on and off; then a band of the frame valid but uncoloured (0 < n_color < n_valid), and a corner
-    colour that is NaN (the pixel keeps its geometric row: n_valid as before, n_color lower, every sum finite)."""
+    colour that is NaN (the pixel keeps its geometric row: n_valid as before, n_color lower, every sum finite).
+    That is 1 and 20 blocks: k_sdf_solve_color's fold and its row guard beyond 64, 256 and 512 blocks are tests/test_gpu_fold_sizes.py's."""
     from icp_amd import binding
     ctx = gpu_ctx_factory()
     vol, _, _ = small_model(ctx)

@@ -168,7 +168,7 @@ def test_system_matches_restatement(gpu_ctx_factory, bunny):
     """The sums of one step: counts exactly; every sum within n_valid 2^-52 sum |term| of the restatement's; two calls give identical bits.
     4099 source points (9 blocks of 512, the last with 3 points) at both voxel sizes, 300 of them alone (one partial block) and the bunny's 1054 (3 blocks, the last partial) against the
     bunny's own target at 2 cm voxels; poses that leave points outside the grid, in empty cells and in cells below min_points; min_points
-    1 and 3."""
+    1 and 3.  That is 9, 1 and 3 blocks: k_sdf_solve's fold beyond 64, 256 and 512 blocks is tests/test_gpu_fold_sizes.py's."""
     ctx = crafted_ctx(gpu_ctx_factory)
     sp, sn = crafted_source()
     seen = []
