@@ -129,8 +129,30 @@ __global__ __launch_bounds__(256) void k_vg_cells_add(const VgTarget t, const Vg
     }
 }
 
-// Finalise: one cell per lane.  fp64 from the integer sums, each of the nine values rounded once to fp32; the record is nine floats and the
-// count, 40 bytes, written as five 8-byte stores.  The occupied cells and the points that entered are counted here.
+// The record of cell i from its count n and its nine sums: fp64 from the integers, each of the nine values rounded once to fp32; nine
+// floats and the count, 40 bytes, written as five 8-byte stores.  (k_vg_finalise, k_vmap_records)
+__device__ __forceinline__ void vg_record(const VgGrid& g, int i, int n, const long long* __restrict__ sums, float2* __restrict__ cells) {
+    float rec[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (n > 0) {
+        const long long* s = sums + (size_t)i * VG_NSUM;
+        const int ix = i % g.dims[0], iy = (i / g.dims[0]) % g.dims[1], iz = i / (g.dims[0] * g.dims[1]);
+        const int c[3] = {g.lo[0] + ix, g.lo[1] + iy, g.lo[2] + iz};
+        const double vs = (double)g.vs, dn = (double)n;
+#pragma unroll
+        for (int a = 0; a < 3; a++) rec[a] = (float)(((double)c[a] + 0.5) * vs + ((double)s[a] / dn) * (vs / 65536.0));
+        const long long tr = (s[3] + s[6]) + s[8];
+        if (tr > 0) {
+            const double dt = (double)tr;
+#pragma unroll
+            for (int a = 0; a < 6; a++) rec[3 + a] = (float)((double)s[3 + a] / dt);
+        }
+    }
+    float2* o = cells + (size_t)i * 5;
+    o[0] = make_float2(rec[0], rec[1]); o[1] = make_float2(rec[2], rec[3]); o[2] = make_float2(rec[4], rec[5]); o[3] = make_float2(rec[6], rec[7]);
+    o[4] = make_float2(rec[8], __int_as_float(n));
+}
+
+// Finalise: one cell per lane, vg_record.  The occupied cells and the points that entered are counted here.
 __global__ __launch_bounds__(256) void k_vg_finalise(const VgGrid g, int n_cells, const int* __restrict__ count, const long long* __restrict__ sums,
                                                      float2* __restrict__ cells, VgBox* __restrict__ box) {
     const int lane = threadIdx.x & 63;
@@ -138,24 +160,7 @@ __global__ __launch_bounds__(256) void k_vg_finalise(const VgGrid g, int n_cells
     int n = 0;
     if (i < n_cells) {
         n = count[i];
-        float rec[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (n > 0) {
-            const long long* s = sums + (size_t)i * VG_NSUM;
-            const int ix = i % g.dims[0], iy = (i / g.dims[0]) % g.dims[1], iz = i / (g.dims[0] * g.dims[1]);
-            const int c[3] = {g.lo[0] + ix, g.lo[1] + iy, g.lo[2] + iz};
-            const double vs = (double)g.vs, dn = (double)n;
-#pragma unroll
-            for (int a = 0; a < 3; a++) rec[a] = (float)(((double)c[a] + 0.5) * vs + ((double)s[a] / dn) * (vs / 65536.0));
-            const long long tr = (s[3] + s[6]) + s[8];
-            if (tr > 0) {
-                const double dt = (double)tr;
-#pragma unroll
-                for (int a = 0; a < 6; a++) rec[3 + a] = (float)((double)s[3 + a] / dt);
-            }
-        }
-        float2* o = cells + (size_t)i * 5;
-        o[0] = make_float2(rec[0], rec[1]); o[1] = make_float2(rec[2], rec[3]); o[2] = make_float2(rec[4], rec[5]); o[3] = make_float2(rec[6], rec[7]);
-        o[4] = make_float2(rec[8], __int_as_float(n));
+        vg_record(g, i, n, sums, cells);
     }
     // per wave: the occupied cells by ballot, the points by a shuffle sum; one pair of atomics from the waves that have any
     const unsigned long long occ = __ballot(n > 0);

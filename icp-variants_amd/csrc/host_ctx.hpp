@@ -1,6 +1,6 @@
 // host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
 // and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
-// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_sdf, host_vgicp, host_sdf_color, host_tsdf_mesh, host_global, host_debug.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_sdf, host_vgicp, host_vmap, host_sdf_color, host_tsdf_mesh, host_global, host_debug.
 using namespace icpdev;
 
 #define HIPCK(ctx, expr)                                                                        \
@@ -153,6 +153,8 @@ struct icp_ctx {
     DevBuf sdf_state, sdf_partials, sdf_rec; Event sdf_ev;   // direct SDF tracking (host_sdf.hpp, host_sdf_color.hpp): the pose / stop state, partials[28 or 29][blocks] + counts[2 or 3][blocks], the frame record + trace; "the last integration has left its upload slot"
     DevBuf vg_box, vg_count, vg_sums, vg_cells;   // voxelized GICP (host_vgicp.hpp): the target's voxel grid -- bounds + counters, per cell the count, the nine int64 sums, the 40-byte record
     bool vg_ready = false; float vg_voxel = 0.f; icp_voxel_grid_info vg_info = {{0, 0, 0}, {0, 0, 0}, 0, 0};   // the grid is current for vg_voxel (dropped with the target's GICP normal cache); its extent
+    DevBuf vm_count, vm_sums, vm_cells, vm_stamp, vm_list, vm_ctr, vm_box;   // the voxel map (host_vmap.hpp): per cell the count, the nine int64 sums, the 40-byte record and the stamp of the last insert that touched it; the list of the cells an insert touched, the counters, the scratch counters of a full sweep
+    bool vm_on = false; icp_voxel_map_options vm_opt = {0.f, {0, 0, 0}, {0, 0, 0}}; int vm_serial = 0;   // the map exists (icp_voxel_map_create); its voxel size and extent; the serial number of the last insert
     float cos_reject = 0.5f;
     std::vector<Event> events;
     Event build_ev[2];                   // index-build bracket (build_bvh)

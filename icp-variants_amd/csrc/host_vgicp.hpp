@@ -90,12 +90,11 @@ int vgicp_check_call(icp_ctx* c, const icp_vgicp_options* opt, const float* pose
 }
 // What the launches of one alignment share: the grid (built when it is not current), both clouds' GICP normals, the blocks of 256 source
 // points and the device blocks behind them.
-struct VgPlan { VgGrid g; VgSource s; int n_blocks; icp_sdf_options so; };
-int vgicp_plan(icp_ctx* c, const icp_vgicp_options& opt, const char* who, VgPlan* pl) {
+struct VgPlan { VgGrid g; const float2* cells; VgSource s; int n_blocks; icp_sdf_options so; };
+// (the source's half: what the voxel map's alignment shares, host_vmap.hpp; the caller has set pl->g and pl->cells)
+int vgicp_plan_source(icp_ctx* c, const icp_vgicp_options& opt, const char* who, VgPlan* pl) {
     int rc;
-    if ((rc = vg_build(c, opt.voxel_size, who))) return rc;
     if ((rc = gicp_normals(c, 1))) { c->err = std::string(who) + ": " + c->err; return rc; }
-    pl->g = vg_view(c, opt.min_points);
     VgSource& s = pl->s;
     s.x = c->src.x.as<float>(); s.y = c->src.y.as<float>(); s.z = c->src.z.as<float>(); s.n = c->src.n;
     vg_normals(c, 1, &s.nx, &s.ny, &s.nz);
@@ -107,6 +106,12 @@ int vgicp_plan(icp_ctx* c, const icp_vgicp_options& opt, const char* who, VgPlan
     if ((rc = ensure(c, c->sdf_partials, (size_t)pl->n_blocks * (SDF_NSUM * 8 + 2 * 4)))) return rc;
     if ((rc = ensure(c, c->sdf_rec, sizeof(icp_sdf_frame) + (size_t)opt.n_iterations * sizeof(icp_sdf_iter)))) return rc;
     return ICP_OK;
+}
+int vgicp_plan(icp_ctx* c, const icp_vgicp_options& opt, const char* who, VgPlan* pl) {
+    int rc;
+    if ((rc = vg_build(c, opt.voxel_size, who))) return rc;
+    pl->g = vg_view(c, opt.min_points); pl->cells = c->vg_cells.as<float2>();
+    return vgicp_plan_source(c, opt, who, pl);
 }
 // The source against the grid from `pose`, enqueued on the context's stream: the state, then `iterations` pairs of k_vgicp_accumulate and
 // k_sdf_solve (step = false: one pair that only folds).  Nothing here waits; the launches behind the alignment's end drain.
@@ -125,12 +130,58 @@ int vgicp_enqueue(icp_ctx* c, const VgPlan& pl, const float pose[16], bool step,
     sp.stop_rotation = pl.so.stop_rotation; sp.stop_translation = pl.so.stop_translation;
     const int iterations = step ? pl.so.n_iterations : 1;
     for (int it = 0; it < iterations; it++) {
-        hipLaunchKernelGGL(k_vgicp_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.g, (const float2*)c->vg_cells.as<float2>(), pl.s, (const SdfState*)st,
+        hipLaunchKernelGGL(k_vgicp_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.g, pl.cells, pl.s, (const SdfState*)st,
                            partials, counts);
         sp.iter = it;
         hipLaunchKernelGGL(k_sdf_solve, dim3(1), dim3(256), 0, c->stream, sp);
     }
     HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+// One fold at `pose` and the state read back: what icp_vgicp_system does behind its plan.
+int vgicp_system_run(icp_ctx* c, const VgPlan& pl, const float pose[16], double* sums_out, int32_t* counts_out) {
+    int rc;
+    if ((rc = vgicp_enqueue(c, pl, pose, false, false))) return rc;
+    if ((rc = ensure_pinned(c, 2048 + sizeof(SdfState)))) return rc;
+    SdfState* h = (SdfState*)(c->pinned.as<char>() + 2048);
+    HIPCK(c, hipMemcpyAsync(h, c->sdf_state.p, sizeof(SdfState), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    memcpy(sums_out, h->sums, sizeof(h->sums));
+    counts_out[0] = h->counts[0]; counts_out[1] = h->counts[1];
+    return ICP_OK;
+}
+std::string vgicp_failure(const char* who, const icp_sdf_frame& r, int min_valid) {
+    char buf[224];
+    if (r.status == ICP_ERR_NO_SOURCE) snprintf(buf, sizeof(buf), "%s: the source has no point with a finite position", who);
+    else snprintf(buf, sizeof(buf), "%s: step %d failed (%d valid points of %d considered, min_valid %d, or a non-finite solution)", who, r.iterations, r.n_valid_last, r.n_depth, min_valid);
+    return buf;
+}
+// The alignment behind its plan: enqueued at once, ONE record read (with the trace when asked for); returns the record's status.
+int vgicp_align_run(icp_ctx* c, const VgPlan& pl, const icp_vgicp_options& opt, float pose_inout[16], icp_vgicp_record* rec_out, icp_vgicp_iter* trace_out, int32_t max_trace,
+                    const char* who, icp_sdf_frame* r) {
+    int rc;
+    const bool trace = trace_out && max_trace > 0;
+    if ((rc = vgicp_enqueue(c, pl, pose_inout, true, trace))) return rc;
+    std::vector<icp_sdf_iter> tr(trace ? (size_t)opt.n_iterations : 0);
+    if ((rc = sdf_read_record(c, pl.so, r, trace ? tr.data() : nullptr))) return rc;
+    if (trace) memcpy(trace_out, tr.data(), (size_t)(max_trace < opt.n_iterations ? max_trace : opt.n_iterations) * sizeof(icp_sdf_iter));
+    if (rec_out) *rec_out = *r;
+    memcpy(pose_inout, r->pose, 64);
+    if (r->status != ICP_OK) c->err = vgicp_failure(who, *r, opt.min_valid);
+    return ICP_OK;
+}
+// A grid's three arrays to the host (icp_get_voxel_grid, icp_get_voxel_map): any pointer may be null; waits for the stream.
+int vg_download(icp_ctx* c, size_t n_cells, const DevBuf& count, const DevBuf& sums, const DevBuf& cells, int32_t* counts_out, int64_t* sums_out, float* cells_out) {
+    if (counts_out) HIPCK(c, hipMemcpyAsync(counts_out, count.p, n_cells * 4, hipMemcpyDeviceToHost, c->stream));
+    if (sums_out) HIPCK(c, hipMemcpyAsync(sums_out, sums.p, n_cells * VG_NSUM * 8, hipMemcpyDeviceToHost, c->stream));
+    if (cells_out) {
+        // the records without their count word: nine floats per cell
+        std::vector<float> h(n_cells * 10);
+        HIPCK(c, hipMemcpyAsync(h.data(), cells.p, n_cells * 40, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < n_cells; i++) memcpy(cells_out + i * 9, h.data() + i * 10, 36);
+    }
+    HIPCK(c, hipStreamSynchronize(c->stream));
     return ICP_OK;
 }
 }  // namespace
@@ -160,16 +211,7 @@ int icp_get_voxel_grid(icp_ctx* c, int32_t* counts_out, int64_t* sums_out, float
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     const size_t n_cells = (size_t)c->vg_info.dims[0] * c->vg_info.dims[1] * c->vg_info.dims[2];
-    if (counts_out) HIPCK(c, hipMemcpyAsync(counts_out, c->vg_count.p, n_cells * 4, hipMemcpyDeviceToHost, c->stream));
-    if (sums_out) HIPCK(c, hipMemcpyAsync(sums_out, c->vg_sums.p, n_cells * VG_NSUM * 8, hipMemcpyDeviceToHost, c->stream));
-    if (cells_out) {
-        // the records without their count word: nine floats per cell
-        std::vector<float> h(n_cells * 10);
-        HIPCK(c, hipMemcpyAsync(h.data(), c->vg_cells.p, n_cells * 40, hipMemcpyDeviceToHost, c->stream));
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        for (size_t i = 0; i < n_cells; i++) memcpy(cells_out + i * 9, h.data() + i * 10, 36);
-    }
-    HIPCK(c, hipStreamSynchronize(c->stream));
+    if ((rc = vg_download(c, n_cells, c->vg_count, c->vg_sums, c->vg_cells, counts_out, sums_out, cells_out))) return rc;
     return guard.done();
 }
 
@@ -182,13 +224,7 @@ int icp_vgicp_system(icp_ctx* c, const float pose[16], const icp_vgicp_options* 
     if ((rc = set_device(c))) return rc;
     VgPlan pl;
     if ((rc = vgicp_plan(c, *opt, "icp_vgicp_system", &pl))) return rc;
-    if ((rc = vgicp_enqueue(c, pl, pose, false, false))) return rc;
-    if ((rc = ensure_pinned(c, 2048 + sizeof(SdfState)))) return rc;
-    SdfState* h = (SdfState*)(c->pinned.as<char>() + 2048);
-    HIPCK(c, hipMemcpyAsync(h, c->sdf_state.p, sizeof(SdfState), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    memcpy(sums_out, h->sums, sizeof(h->sums));
-    counts_out[0] = h->counts[0]; counts_out[1] = h->counts[1];
+    if ((rc = vgicp_system_run(c, pl, pose, sums_out, counts_out))) return rc;
     return guard.done();
 }
 
@@ -201,20 +237,8 @@ int icp_vgicp_align(icp_ctx* c, const icp_vgicp_options* opt, float pose_inout[1
     if ((rc = set_device(c))) return rc;
     VgPlan pl;
     if ((rc = vgicp_plan(c, *opt, "icp_vgicp_align", &pl))) return rc;
-    const bool trace = trace_out && max_trace > 0;
-    if ((rc = vgicp_enqueue(c, pl, pose_inout, true, trace))) return rc;
     icp_sdf_frame r;
-    std::vector<icp_sdf_iter> tr(trace ? (size_t)opt->n_iterations : 0);
-    if ((rc = sdf_read_record(c, pl.so, &r, trace ? tr.data() : nullptr))) return rc;
-    if (trace) memcpy(trace_out, tr.data(), (size_t)(max_trace < opt->n_iterations ? max_trace : opt->n_iterations) * sizeof(icp_sdf_iter));
-    if (rec_out) *rec_out = r;
-    memcpy(pose_inout, r.pose, 64);
-    if (r.status != ICP_OK) {
-        char buf[224];
-        if (r.status == ICP_ERR_NO_SOURCE) snprintf(buf, sizeof(buf), "icp_vgicp_align: the source has no point with a finite position");
-        else snprintf(buf, sizeof(buf), "icp_vgicp_align: step %d failed (%d valid points of %d considered, min_valid %d, or a non-finite solution)", r.iterations, r.n_valid_last, r.n_depth, opt->min_valid);
-        c->err = buf;
-    }
+    if ((rc = vgicp_align_run(c, pl, *opt, pose_inout, rec_out, trace_out, max_trace, "icp_vgicp_align", &r))) return rc;
     return guard.done(r.status);      // (synchronised by the record read)
 }
 

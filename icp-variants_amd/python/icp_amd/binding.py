@@ -147,6 +147,36 @@ def vgicp_options(**kw):
     return o
 
 
+class IcpVoxelMapOptions(C.Structure):
+    _fields_ = [("voxel_size", C.c_float), ("lo", C.c_int32 * 3), ("dims", C.c_int32 * 3)]
+
+
+class IcpVoxelMapInsertInfo(C.Structure):
+    _fields_ = [("n_considered", C.c_int32), ("n_entered", C.c_int32), ("n_outside", C.c_int32), ("n_cells_touched", C.c_int32), ("n_cells_new", C.c_int32),
+                ("n_occupied", C.c_int32)]
+
+
+class IcpVoxelMapInfo(C.Structure):
+    _fields_ = [("voxel_size", C.c_float), ("lo", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("n_occupied", C.c_int32)]
+
+
+def voxel_map_options(voxel_size, lo, dims):
+    """icp_voxel_map_options: the voxel size in metres and the extent in cells (lowest cell, cells per axis)."""
+    o = IcpVoxelMapOptions()
+    o.voxel_size = voxel_size
+    o.lo = (C.c_int32 * 3)(*[int(v) for v in lo]); o.dims = (C.c_int32 * 3)(*[int(v) for v in dims])
+    return o
+
+
+def voxel_map_extent(lower, upper, voxel_size):
+    """(lo, dims) of the smallest voxel map that holds the box lower .. upper (metres), by the library's cell rule:
+    c = (int)clamp(floorf(p / voxel_size), -2^30, 2^30) in fp32, lo = c(lower), dims = c(upper) - lo + 1."""
+    vs = np.float32(voxel_size)
+    cell = lambda p: np.clip(np.floor(np.asarray(p, np.float32) / vs), -2.0 ** 30, 2.0 ** 30).astype(np.int64)
+    lo = cell(lower); hi = cell(upper)
+    return tuple(int(v) for v in lo), tuple(int(v) for v in hi - lo + 1)
+
+
 class IcpSdfColorOptions(C.Structure):
     _fields_ = [("weight", C.c_float), ("huber", C.c_float)]
 
@@ -353,6 +383,8 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
            "icp_track_depth_sdf_color",
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
+           "icp_voxel_map_options_check", "icp_voxel_map_create", "icp_voxel_map_destroy", "icp_voxel_map_insert", "icp_get_voxel_map", "icp_voxel_map_upload",
+           "icp_voxel_map_system", "icp_voxel_map_align", "icp_track_scans_vmap",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
@@ -1128,6 +1160,82 @@ class Context:
         if trace:
             return pose_from_c(p), r, rc, [_record(tr[i]) for i in range(r["iterations"])]
         return pose_from_c(p), r, rc
+
+    def voxel_map_create(self, voxel_size, lo, dims):
+        """icp_voxel_map_create: the context's voxel map (scan-to-map laser tracking), allocated and cleared: voxel_size in metres, the
+        extent as the lowest cell `lo` and the cells per axis `dims` (see `voxel_map_extent`).  Called again: replaced."""
+        o = voxel_map_options(voxel_size, lo, dims)
+        self._ck(self.lib.icp_voxel_map_create(self.h, C.byref(o)))
+
+    def voxel_map_destroy(self):
+        self._ck(self.lib.icp_voxel_map_destroy(self.h))
+
+    def voxel_map_insert(self, which, pose):
+        """icp_voxel_map_insert: fuses the resident target (which = 0) or source (1) into the map at `pose`.  Returns dict(n_considered,
+        n_entered, n_outside, n_cells_touched, n_cells_new, n_occupied)."""
+        info = IcpVoxelMapInsertInfo()
+        self._ck(self.lib.icp_voxel_map_insert(self.h, C.c_int32(which), _ptr(pose_to_c(pose)), C.byref(info)))
+        return _record(info)
+
+    def voxel_map(self):
+        """icp_get_voxel_map: (info dict(voxel_size, lo, dims, n_occupied), counts (n_cells,) int32, sums (n_cells, 9) int64, cells
+        (n_cells, 9) float32), cell index (z dims_y + y) dims_x + x."""
+        info = IcpVoxelMapInfo()
+        self._ck(self.lib.icp_get_voxel_map(self.h, C.byref(info), None, None, None))
+        n = int(np.prod(tuple(info.dims), dtype=np.int64))
+        counts = np.empty(n, np.int32); sums = np.empty((n, 9), np.int64); cells = np.empty((n, 9), np.float32)
+        self._ck(self.lib.icp_get_voxel_map(self.h, None, _ptr(counts), _ptr(sums), _ptr(cells)))
+        return dict(voxel_size=info.voxel_size, lo=tuple(info.lo), dims=tuple(info.dims), n_occupied=info.n_occupied), counts, sums, cells
+
+    def voxel_map_upload(self, counts, sums):
+        """icp_voxel_map_upload: replaces the map's integer state (counts (n_cells,), sums (n_cells, 9)) and recomputes every record."""
+        info = IcpVoxelMapInfo()
+        self._ck(self.lib.icp_get_voxel_map(self.h, C.byref(info), None, None, None))
+        n = int(np.prod(tuple(info.dims), dtype=np.int64))
+        cn = np.ascontiguousarray(counts, dtype=np.int32); sm = np.ascontiguousarray(sums, dtype=np.int64)
+        if cn.size != n or sm.size != 9 * n:
+            raise ValueError("the map has %d cells: counts needs %d values, sums %d" % (n, n, 9 * n))
+        self._ck(self.lib.icp_voxel_map_upload(self.h, _ptr(cn), _ptr(sm)))
+
+    def voxel_map_system(self, pose, options=None, **kw):
+        """icp_voxel_map_system: the 28 sums of one voxelized GICP step of the resident source at `pose` against the map.  Returns (sums
+        (28,) float64, (considered, valid))."""
+        o = options if options is not None else vgicp_options(**kw)
+        sums = np.empty(28, np.float64); cnt = (C.c_int32 * 2)()
+        self._ck(self.lib.icp_voxel_map_system(self.h, _ptr(pose_to_c(pose)), C.byref(o), _ptr(sums), cnt))
+        return sums, (cnt[0], cnt[1])
+
+    def voxel_map_align(self, pose=None, trace=False, options=None, **kw):
+        """icp_voxel_map_align: the resident source aligned to the map from `pose` (identity by default); `vgicp_align`'s returns."""
+        o = options if options is not None else vgicp_options(**kw)
+        p = pose_to_c(np.eye(4) if pose is None else pose)
+        rec = IcpSdfFrame(); tr = (IcpSdfIter * o.n_iterations)() if trace else None
+        rc = self.lib.icp_voxel_map_align(self.h, C.byref(o), _ptr(p), C.byref(rec), tr, C.c_int32(o.n_iterations if trace else 0))
+        if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # the alignment's outcome: reported in the record
+            self._ck(rc)
+        r = _record(rec)
+        if trace:
+            return pose_from_c(p), r, rc, [_record(tr[i]) for i in range(r["iterations"])]
+        return pose_from_c(p), r, rc
+
+    def track_scans_vmap(self, scans, pose=None, options=None, **kw):
+        """icp_track_scans_vmap: `scans`, a list of (xyz (n, 3), normals (n, 3) or None) in the sensor frame, tracked against the map:
+        scan 0 inserted at `pose` (identity by default), every later scan aligned to the map and, when that succeeds, inserted at the
+        pose found.  Returns (final pose, the records of scans 1 .., status: the first per-scan error, or 0)."""
+        o = options if options is not None else vgicp_options(**kw)
+        ns = len(scans)
+        pts = [_f32(s[0]) for s in scans]
+        nrm = [None if s[1] is None else _f32(s[1]) for s in scans]
+        if any(a.ndim != 2 or a.shape[1] != 3 for a in pts) or any(b is not None and b.shape != a.shape for a, b in zip(pts, nrm)):
+            raise ValueError("a scan is (xyz (n, 3), normals (n, 3) or None)")
+        xp = (C.c_void_p * ns)(*[_ptr(a) for a in pts]); npp = (C.c_void_p * ns)(*[_ptr(b) for b in nrm])
+        cnt = (C.c_int32 * ns)(*[len(a) for a in pts])
+        p = pose_to_c(np.eye(4) if pose is None else pose)
+        out = (IcpSdfFrame * max(ns - 1, 1))()
+        rc = self.lib.icp_track_scans_vmap(self.h, xp, npp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out)
+        if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-scan outcomes: reported in the records
+            self._ck(rc)
+        return pose_from_c(p), [_record(out[i]) for i in range(ns - 1)], rc
 
     def estimate_normals(self, xyz, k=5, viewpoint=(0.0, 0.0, 0.0)):
         """PointCloud(pcl cloud): k-NN PCA normals flipped towards the viewpoint (PointCloud.h:41-76)."""

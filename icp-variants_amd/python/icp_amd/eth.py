@@ -93,6 +93,28 @@ def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="iden
     return ctx.run(start, check=check)
 
 
+def track_map(ctx, scans, start_pose, voxel_size=0.25, extent=None, margin=2.0, **vgicp_options):
+    """Scan-to-map tracking of a laser sequence (Context.track_scans_vmap): `scans` is a list of (xyz, normals) in the sensor frame
+    (normals None where the context's GICP options compute them, covariance_k > 0), `start_pose` the 4x4 pose of scan 0.  A voxel map of
+    `voxel_size` metres is created over `extent` = (lo, dims) in cells (binding.voxel_map_extent); extent None: the bounds of scan 0's
+    finite points at the start pose, grown by `margin` metres on every side.  Scan 0 is fused at the start pose; every later scan is
+    aligned to the map built so far (voxelized GICP with **vgicp_options, the fields of binding.vgicp_options) and fused at the pose
+    found; a scan that fails is skipped and carries the pose.  Returns (poses: one 4x4 per scan, records: one per scan after the first,
+    status: the first per-scan error, or 0).  The map stays in the context (Context.voxel_map)."""
+    from . import binding
+    start = np.asarray(start_pose, np.float32)
+    if extent is None:
+        p0 = np.asarray(scans[0][0], np.float64)
+        p0 = p0[np.isfinite(p0).all(1)]
+        if len(p0) == 0:
+            raise ValueError("scan 0 has no finite point to take the extent from")
+        w = p0 @ start[:3, :3].astype(np.float64).T + start[:3, 3].astype(np.float64)
+        extent = binding.voxel_map_extent(w.min(0) - margin, w.max(0) + margin, voxel_size)
+    ctx.voxel_map_create(voxel_size, *extent)
+    pose, recs, rc = ctx.track_scans_vmap(scans, start, options=binding.vgicp_options(voxel_size=voxel_size, **vgicp_options))
+    return [start.copy()] + [r["pose"] for r in recs], recs, rc
+
+
 def write_synthetic_dataset(eth_dir, csv_name, pairs, binary=True):
     """Writes synthetic scans in the reference's on-disk layout (used by the tests and for rehearsing --eth-dir offline):
     `pairs` = list of dicts with src_unperturbed, tgt_pts and a benchmark `pose` (unscaled perturbation)."""

@@ -920,6 +920,75 @@ int icp_vgicp_system(icp_ctx* ctx, const float pose[16], const icp_vgicp_options
 int icp_vgicp_align(icp_ctx* ctx, const icp_vgicp_options* opt, float pose_inout[16], icp_vgicp_record* rec_out, icp_vgicp_iter* trace_out,
                     int32_t max_trace);
 
+/* -------- scan-to-map laser tracking (an extension): a persistent voxel map that scans are aligned to and fused into.  DESIGN.md section 6t. --------
+ * The laser counterpart of the TSDF volume: voxelized GICP's grid of cells (above) as state of the context with a FIXED extent, which the
+ * resident target or source is fused into at a pose, and which the resident source is aligned to in place of the target's grid.  The
+ * per-cell state is the count and the nine integer sums above, so the map after any set of inserts depends neither on their order nor on
+ * the order of the points within one, and keeps its bits.  The map and the target's grid are separate state: nothing above changes what it
+ * returns.  The map holds sums, not normals: it survives icp_set_target, icp_set_source and icp_set_gicp_options.
+ * tests/vmap_restatement.py restates what follows.
+ *
+ * Extent: lo in cell coordinates by the rule above (c_a = (int)clamp(floorf(p_a / voxel_size), -2^30, 2^30)), dims_a >= 1 cells per axis,
+ *   dims_x dims_y dims_z <= 2^24 (the map is dense); voxel_size finite and > 0.  Anything else: ICP_ERR_INVALID_ARG with a reason.  The
+ *   cell of coordinates c has the index ((c_z - lo_z) dims_y + (c_y - lo_y)) dims_x + (c_x - lo_x).
+ * Insert of a cloud at a pose P.  The normals are the cloud's GICP normals under the context's icp_gicp_options, as above (covariance_k =
+ *   0: its own, which it must then have).  A point is CONSIDERED iff its own position is finite.  It ENTERS iff, in addition,
+ *   p' = icp_transform_points(P, p) (fp32, ((P_r0 x + P_r1 y) + P_r2 z) + P_r3) and n' = icp_transform_normals(P, n) (the fp32 normal
+ *   matrix of the pose) are both finite.  An entering point is quantised exactly as a target point is above, with p' and n' in place of p
+ *   and n: the cell, q_a, m_a and every clamp; n' is not renormalised.  If its cell lies inside the extent the cell's count goes up by one
+ *   and its nine sums by the point's nine integers; otherwise the point is OUTSIDE and dropped.
+ * Records: after an insert the record of every cell with count > 0 is the function of its sums and count given above (fp64 rounded once
+ *   to fp32; S over the integer trace, S = 0 for a zero trace); an empty cell holds nine zeros.
+ * Align: the sums, counts, step, stop, records and failure rules of icp_vgicp_system / icp_vgicp_align, with the map's cells in place of
+ *   the grid's.  opt->voxel_size must equal the map's.  A source and a map are needed, a target is not. */
+typedef struct icp_voxel_map_options {
+    float   voxel_size;              /* metres, finite and > 0 */
+    int32_t lo[3], dims[3];          /* the extent in cells: lowest cell, cells per axis (each >= 1, product <= 2^24) */
+} icp_voxel_map_options;
+typedef struct icp_voxel_map_insert_info {
+    int32_t n_considered, n_entered, n_outside;   /* points of this insert: finite position; finite p' and n' as well; of those, outside the extent */
+    int32_t n_cells_touched, n_cells_new;         /* cells this insert added to; of those, cells whose count was 0 before it */
+    int32_t n_occupied;                           /* cells with count > 0 after it: the running total */
+} icp_voxel_map_insert_info;
+typedef struct icp_voxel_map_info {
+    float   voxel_size;
+    int32_t lo[3], dims[3];
+    int32_t n_occupied;
+} icp_voxel_map_info;
+#ifdef __cplusplus
+static_assert(sizeof(icp_voxel_map_options) == 28, "icp_voxel_map_options");
+static_assert(sizeof(icp_voxel_map_insert_info) == 24, "icp_voxel_map_insert_info");
+static_assert(sizeof(icp_voxel_map_info) == 32, "icp_voxel_map_info");
+#endif
+/* ICP_OK or ICP_ERR_INVALID_ARG; needs neither a context nor a device. */
+int icp_voxel_map_options_check(const icp_voxel_map_options* opt);
+/* Allocates the map (per cell 4 + 72 + 40 bytes of state and a 4-byte stamp) and clears it.  A second create replaces the map. */
+int icp_voxel_map_create(icp_ctx* ctx, const icp_voxel_map_options* opt);
+/* Frees the map (ICP_OK without one). */
+int icp_voxel_map_destroy(icp_ctx* ctx);
+/* Fuses the resident target (which = 0) or source (which = 1) into the map at `pose`; info_out is optional (without it the host reads
+ * nothing back).  Only the records of the cells the insert touched are recomputed.  ICP_ERR_INVALID_ARG without a map, for which outside
+ * {0, 1}, for covariance_k = 0 with a cloud that has no normals; ICP_ERR_NO_TARGET / ICP_ERR_NO_SOURCE without the cloud. */
+int icp_voxel_map_insert(icp_ctx* ctx, int32_t which, const float pose[16], icp_voxel_map_insert_info* info_out);
+/* The map: counts_out one int32 per cell, sums_out nine int64 per cell, cells_out nine floats per cell; any pointer may be NULL.
+ * ICP_ERR_INVALID_ARG without a map. */
+int icp_get_voxel_map(icp_ctx* ctx, icp_voxel_map_info* info_out, int32_t* counts_out, int64_t* sums_out, float* cells_out);
+/* Replaces the integer state (counts >= 0: one int32 per cell; sums: nine int64 per cell) and recomputes every record and n_occupied. */
+int icp_voxel_map_upload(icp_ctx* ctx, const int32_t* counts, const int64_t* sums);
+/* icp_vgicp_system against the map. */
+int icp_voxel_map_system(icp_ctx* ctx, const float pose[16], const icp_vgicp_options* opt, double* sums_out, int32_t* counts_out);
+/* icp_vgicp_align against the map.  Refuses with a reason: no map, opt->voxel_size other than the map's, bad options (ICP_ERR_INVALID_ARG),
+ * no source (ICP_ERR_NO_SOURCE), covariance_k = 0 with a source that has no normals. */
+int icp_voxel_map_align(icp_ctx* ctx, const icp_vgicp_options* opt, float pose_inout[16], icp_vgicp_record* rec_out, icp_vgicp_iter* trace_out,
+                        int32_t max_trace);
+/* Tracking: scan 0 (xyz[0]: n[0] x 3 floats, normals[0] likewise) becomes the source, as icp_set_source(xyz, normals, NULL, n) makes it, and
+ * is inserted at pose_inout; scan k >= 1 becomes the source and is aligned from the current pose; on ICP_OK it is inserted at the pose
+ * found (out[k - 1] its record).  A failed scan carries the pose, is not inserted, records its status, and tracking goes on; the first
+ * error in scan order is returned.  normals, or normals[k], may be NULL when the context's covariance_k > 0.  The host reads one record per
+ * scan.  The last scan stays resident as the source.  out: n_scans - 1 records (may be NULL for n_scans = 1). */
+int icp_track_scans_vmap(icp_ctx* ctx, const float* const* xyz, const float* const* normals, const int32_t* n, int32_t n_scans,
+                         const icp_vgicp_options* opt, float pose_inout[16], icp_vgicp_record* out);
+
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
  * towards the viewpoint.  k in {3..8} (else ICP_ERR_INVALID_ARG).  Non-finite points, and every point of a cloud with fewer than
