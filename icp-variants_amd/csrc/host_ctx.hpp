@@ -155,6 +155,8 @@ struct icp_ctx {
     bool vg_ready = false; float vg_voxel = 0.f; icp_voxel_grid_info vg_info = {{0, 0, 0}, {0, 0, 0}, 0, 0};   // the grid is current for vg_voxel (dropped with the target's GICP normal cache); its extent
     DevBuf vm_count, vm_sums, vm_cells, vm_stamp, vm_list, vm_ctr, vm_box;   // the voxel map (host_vmap.hpp): per cell the count, the nine int64 sums, the 40-byte record and the stamp of the last insert that touched it; the list of the cells an insert touched, the counters, the scratch counters of a full sweep
     bool vm_on = false; icp_voxel_map_options vm_opt = {0.f, {0, 0, 0}, {0, 0, 0}}; int vm_serial = 0;   // the map exists (icp_voxel_map_create); its voxel size and extent; the serial number of the last insert
+    DevBuf vh_keys;                      // the hashed storage of the map (host_hmap.hpp): one 8-byte key per slot; vm_count .. vm_stamp are then indexed by slot
+    bool vm_hashed = false; int vh_log2cap = 0, vh_grown = 0; long long vh_bound = 0;   // the map is hashed (icp_voxel_map_create_hashed; vm_opt holds its voxel size alone); capacity = 2^vh_log2cap; rehashes so far; the host's upper bound on the occupied count
     float cos_reject = 0.5f;
     std::vector<Event> events;
     Event build_ev[2];                   // index-build bracket (build_bvh)

@@ -90,7 +90,7 @@ int vgicp_check_call(icp_ctx* c, const icp_vgicp_options* opt, const float* pose
 }
 // What the launches of one alignment share: the grid (built when it is not current), both clouds' GICP normals, the blocks of 256 source
 // points and the device blocks behind them.
-struct VgPlan { VgGrid g; const float2* cells; VgSource s; int n_blocks; icp_sdf_options so; };
+struct VgPlan { VgGrid g; const float2* cells; VgSource s; int n_blocks; icp_sdf_options so; HmTable h = {nullptr, 0, 0.f, 0}; };      // (h.keys set: the cells are a hashed voxel map's, host_hmap.hpp)
 // (the source's half: what the voxel map's alignment shares, host_vmap.hpp; the caller has set pl->g and pl->cells)
 int vgicp_plan_source(icp_ctx* c, const icp_vgicp_options& opt, const char* who, VgPlan* pl) {
     int rc;
@@ -130,7 +130,8 @@ int vgicp_enqueue(icp_ctx* c, const VgPlan& pl, const float pose[16], bool step,
     sp.stop_rotation = pl.so.stop_rotation; sp.stop_translation = pl.so.stop_translation;
     const int iterations = step ? pl.so.n_iterations : 1;
     for (int it = 0; it < iterations; it++) {
-        hipLaunchKernelGGL(k_vgicp_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.g, pl.cells, pl.s, (const SdfState*)st,
+        if (pl.h.keys) hipLaunchKernelGGL(k_hmap_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.h, pl.cells, pl.s, (const SdfState*)st, partials, counts);
+        else hipLaunchKernelGGL(k_vgicp_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.g, pl.cells, pl.s, (const SdfState*)st,
                            partials, counts);
         sp.iter = it;
         hipLaunchKernelGGL(k_sdf_solve, dim3(1), dim3(256), 0, c->stream, sp);

@@ -37,6 +37,7 @@ int vmap_insert_enqueue(icp_ctx* c, int which, const float pose[16], const char*
     }
     int rc;
     if ((rc = gicp_normals(c, which))) { c->err = std::string(who) + ": " + c->err; return rc; }
+    if (c->vm_hashed) return hmap_insert_enqueue(c, which, pose, who);
     const size_t n_cells = vm_cells(c);
     if (c->vm_serial == INT_MAX) {                     // the serial numbers have run out: every stamp back to "never"
         HIPCK(c, hipMemsetAsync(c->vm_stamp.p, 0, n_cells * 4, c->stream));
@@ -72,6 +73,7 @@ int vmap_plan(icp_ctx* c, const icp_vgicp_options* opt, const float* pose, const
     }
     if (c->src.n <= 0) { c->err = std::string(who) + ": no source cloud (icp_set_source)"; return ICP_ERR_NO_SOURCE; }
     pl->g = vm_view(c, opt->min_points); pl->cells = c->vm_cells.as<float2>();
+    if (c->vm_hashed) hmap_plan(c, opt->min_points, pl);
     return vgicp_plan_source(c, *opt, who, pl);
 }
 }  // namespace
@@ -85,6 +87,7 @@ int icp_voxel_map_create(icp_ctx* c, const icp_voxel_map_options* opt) {
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     c->vm_on = false;
+    if (c->vm_hashed) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->vh_keys); c->vm_hashed = false; }
     c->vm_opt = *opt;
     const size_t n = vm_cells(c);
     if ((rc = ensure(c, c->vm_count, n * 4))) return rc;
@@ -106,8 +109,8 @@ int icp_voxel_map_create(icp_ctx* c, const icp_voxel_map_options* opt) {
 int icp_voxel_map_destroy(icp_ctx* c) {
     if (!c) return ICP_ERR_INVALID_ARG;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf* b : {&c->vm_count, &c->vm_sums, &c->vm_cells, &c->vm_stamp, &c->vm_list, &c->vm_ctr, &c->vm_box}) release(*b);
-    c->vm_on = false;
+    for (DevBuf* b : {&c->vm_count, &c->vm_sums, &c->vm_cells, &c->vm_stamp, &c->vm_list, &c->vm_ctr, &c->vm_box, &c->vh_keys}) release(*b);
+    c->vm_on = false; c->vm_hashed = false;
     return ICP_OK;
 }
 
@@ -120,7 +123,8 @@ int icp_voxel_map_insert(icp_ctx* c, int32_t which, const float pose[16], icp_vo
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if ((rc = vmap_insert_enqueue(c, which, pose, who))) return rc;
-    if (info_out) { if ((rc = read_count(c, c->vm_ctr.p, (int*)info_out, 6))) return rc; }
+    if (c->vm_hashed) { if ((rc = hmap_read_counters(c, (int*)info_out, who))) return rc; }      // (the counter that must stay 0 is read with the info)
+    else if (info_out) { if ((rc = read_count(c, c->vm_ctr.p, (int*)info_out, 6))) return rc; }
     else HIPCK(c, hipStreamSynchronize(c->stream));
     return guard.done();
 }
@@ -129,6 +133,7 @@ int icp_get_voxel_map(icp_ctx* c, icp_voxel_map_info* info_out, int32_t* counts_
     if (!c) return ICP_ERR_INVALID_ARG;
     int rc;
     if ((rc = vmap_check(c, "icp_get_voxel_map"))) return rc;
+    if (c->vm_hashed) { c->err = "icp_get_voxel_map: the voxel map is hashed: use icp_get_voxel_map_hashed"; return ICP_ERR_INVALID_ARG; }
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if (info_out) {
@@ -145,6 +150,7 @@ int icp_voxel_map_upload(icp_ctx* c, const int32_t* counts, const int64_t* sums)
     const char* who = "icp_voxel_map_upload";
     int rc;
     if ((rc = vmap_check(c, who))) return rc;
+    if (c->vm_hashed) { c->err = std::string(who) + ": the voxel map is hashed: use icp_voxel_map_upload_hashed"; return ICP_ERR_INVALID_ARG; }
     if (!counts || !sums) { c->err = std::string(who) + ": null counts or sums"; return ICP_ERR_INVALID_ARG; }
     const size_t n = vm_cells(c);
     for (size_t i = 0; i < n; i++) if (counts[i] < 0) { c->err = std::string(who) + ": a count is negative"; return ICP_ERR_INVALID_ARG; }
@@ -217,7 +223,8 @@ int icp_track_scans_vmap(icp_ctx* c, const float* const* xyz, const float* const
             if ((rc = vmap_plan(c, opt, pose_inout, who, &pl))) return rc;
             icp_sdf_frame& r = out[k - 1];
             if ((rc = vgicp_enqueue(c, pl, pose_inout, true, false))) return rc;
-            if ((rc = sdf_read_record(c, pl.so, &r, nullptr))) return rc;      // the one host read of the scan: the insert takes its pose from the host
+            // the one host read of the scan: the insert takes its pose from the host (a hashed map's occupied count comes with it)
+            if ((rc = c->vm_hashed ? hmap_read_record(c, pl.so, &r, who) : sdf_read_record(c, pl.so, &r, nullptr))) return rc;
             memcpy(pose_inout, r.pose, 64);
             if (r.status != ICP_OK) {
                 if (first_err == ICP_OK) { first_err = r.status; c->err = vgicp_failure(who, r, opt->min_valid); }
@@ -226,7 +233,8 @@ int icp_track_scans_vmap(icp_ctx* c, const float* const* xyz, const float* const
         }
         if ((rc = vmap_insert_enqueue(c, 1, pose_inout, who))) return rc;
     }
-    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (c->vm_hashed) { if ((rc = hmap_read_counters(c, nullptr, who))) return rc; }
+    else HIPCK(c, hipStreamSynchronize(c->stream));
     guard.ok = true;
     return first_err;
 }
@@ -242,6 +250,11 @@ extern "C" int icp_debug_vmap_time(icp_ctx* c, int32_t which, const float pose[1
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if ((rc = ensure_events(c, 2))) return rc;
+    if (c->vm_hashed) {
+        if ((rc = gicp_normals(c, which))) return rc;
+        if ((rc = hmap_debug_time(c, which, pose, insert_ms_out, records_ms_out, who))) return rc;
+        return guard.done();
+    }
     if ((rc = vmap_insert_enqueue(c, which, pose, who))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
     HIPCK(c, hipEventRecord(c->events[0], c->stream));
@@ -258,5 +271,35 @@ extern "C" int icp_debug_vmap_time(icp_ctx* c, int32_t which, const float pose[1
     HIPCK(c, hipEventRecord(c->events[1], c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     HIPCK(c, hipEventElapsedTime(records_ms_out, c->events[0], c->events[1]));
+    return guard.done();
+}
+
+// Not part of icp_hip.h (tools/time_hmap.py): the device time of ONE accumulate launch of the resident source against the map at `pose`
+// (k_vgicp_accumulate for a dense map, k_hmap_accumulate for a hashed one), the mean over `reps` launches between two events, after a
+// fold at that pose that leaves the state's stop word clear.
+extern "C" int icp_debug_vmap_accumulate_time(icp_ctx* c, const float pose[16], const icp_vgicp_options* opt, int32_t reps, float* ms_out) {
+    if (!c || !ms_out || reps < 1) return ICP_ERR_INVALID_ARG;
+    const char* who = "icp_debug_vmap_accumulate_time";
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ensure_events(c, 2))) return rc;
+    VgPlan pl;
+    if ((rc = vmap_plan(c, opt, pose, who, &pl))) return rc;
+    if ((rc = vgicp_enqueue(c, pl, pose, false, false))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    double* partials = c->sdf_partials.as<double>();
+    int* counts = (int*)(partials + (size_t)SDF_NSUM * pl.n_blocks);
+    const SdfState* st = c->sdf_state.as<SdfState>();
+    HIPCK(c, hipEventRecord(c->events[0], c->stream));
+    for (int r = 0; r < reps; r++) {
+        if (pl.h.keys) hipLaunchKernelGGL(k_hmap_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.h, pl.cells, pl.s, st, partials, counts);
+        else hipLaunchKernelGGL(k_vgicp_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.g, pl.cells, pl.s, st, partials, counts);
+    }
+    HIPCK(c, hipEventRecord(c->events[1], c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCK(c, hipEventElapsedTime(&ms, c->events[0], c->events[1]));
+    *ms_out = ms / (float)reps;
     return guard.done();
 }

@@ -34,6 +34,7 @@
 #include "host_tsdf.hpp"
 #include "host_sdf.hpp"
 #include "host_vgicp.hpp"
+#include "host_hmap.hpp"
 #include "host_vmap.hpp"
 #include "host_sdf_color.hpp"
 #include "host_tsdf_mesh.hpp"

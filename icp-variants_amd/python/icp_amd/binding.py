@@ -160,6 +160,11 @@ class IcpVoxelMapInfo(C.Structure):
     _fields_ = [("voxel_size", C.c_float), ("lo", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("n_occupied", C.c_int32)]
 
 
+class IcpVoxelHashMapInfo(C.Structure):
+    _fields_ = [("voxel_size", C.c_float), ("capacity", C.c_int32), ("n_occupied", C.c_int32), ("n_grown", C.c_int32), ("n_unplaced", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 def voxel_map_options(voxel_size, lo, dims):
     """icp_voxel_map_options: the voxel size in metres and the extent in cells (lowest cell, cells per axis)."""
     o = IcpVoxelMapOptions()
@@ -385,6 +390,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
            "icp_voxel_map_options_check", "icp_voxel_map_create", "icp_voxel_map_destroy", "icp_voxel_map_insert", "icp_get_voxel_map", "icp_voxel_map_upload",
            "icp_voxel_map_system", "icp_voxel_map_align", "icp_track_scans_vmap",
+           "icp_voxel_map_create_hashed", "icp_voxel_map_reserve", "icp_get_voxel_map_hashed", "icp_voxel_map_upload_hashed",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
@@ -1196,6 +1202,35 @@ class Context:
         if cn.size != n or sm.size != 9 * n:
             raise ValueError("the map has %d cells: counts needs %d values, sums %d" % (n, n, 9 * n))
         self._ck(self.lib.icp_voxel_map_upload(self.h, _ptr(cn), _ptr(sm)))
+
+    def voxel_map_create_hashed(self, voxel_size, capacity=1 << 16):
+        """icp_voxel_map_create_hashed: the context's voxel map stored in a hash table of cells, without an extent: at least `capacity`
+        slots (rounded up to a power of two, 2^8 .. 2^26); it grows on the device when it fills.  Replaces any map, dense or hashed."""
+        self._ck(self.lib.icp_voxel_map_create_hashed(self.h, C.c_float(voxel_size), C.c_int32(capacity)))
+
+    def voxel_map_reserve(self, capacity):
+        """icp_voxel_map_reserve: rehashes the hashed map into at least `capacity` slots (smaller or equal: nothing happens)."""
+        self._ck(self.lib.icp_voxel_map_reserve(self.h, C.c_int32(capacity)))
+
+    def voxel_map_hashed(self):
+        """icp_get_voxel_map_hashed: (info dict(voxel_size, capacity, n_occupied, n_grown, n_unplaced), coords (n, 3) int32, counts (n,)
+        int32, sums (n, 9) int64, cells (n, 9) float32) of the occupied cells, sorted by key (z, then y, then x)."""
+        info = IcpVoxelHashMapInfo()
+        self._ck(self.lib.icp_get_voxel_map_hashed(self.h, C.byref(info), C.c_int32(0), None, None, None, None))
+        n = info.n_occupied
+        coords = np.empty((n, 3), np.int32); counts = np.empty(n, np.int32); sums = np.empty((n, 9), np.int64); cells = np.empty((n, 9), np.float32)
+        self._ck(self.lib.icp_get_voxel_map_hashed(self.h, C.byref(info), C.c_int32(n), _ptr(coords), _ptr(counts), _ptr(sums), _ptr(cells)))
+        d = {k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"}
+        return d, coords, counts, sums, cells
+
+    def voxel_map_upload_hashed(self, coords, counts, sums):
+        """icp_voxel_map_upload_hashed: replaces the hashed map's state by the cells `coords` (n, 3) with `counts` (n,) and `sums` (n, 9),
+        and computes every record."""
+        cc = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3); cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        sm = np.ascontiguousarray(sums, dtype=np.int64).reshape(-1, 9)
+        if not (len(cc) == len(cn) == len(sm)):
+            raise ValueError("coords (n, 3), counts (n,) and sums (n, 9) must agree in n")
+        self._ck(self.lib.icp_voxel_map_upload_hashed(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(cn), _ptr(sm)))
 
     def voxel_map_system(self, pose, options=None, **kw):
         """icp_voxel_map_system: the 28 sums of one voxelized GICP step of the resident source at `pose` against the map.  Returns (sums

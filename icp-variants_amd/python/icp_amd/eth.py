@@ -93,16 +93,25 @@ def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="iden
     return ctx.run(start, check=check)
 
 
-def track_map(ctx, scans, start_pose, voxel_size=0.25, extent=None, margin=2.0, **vgicp_options):
+def track_map(ctx, scans, start_pose, voxel_size=0.25, extent=None, margin=2.0, hashed=False, capacity=1 << 16, **vgicp_options):
     """Scan-to-map tracking of a laser sequence (Context.track_scans_vmap): `scans` is a list of (xyz, normals) in the sensor frame
     (normals None where the context's GICP options compute them, covariance_k > 0), `start_pose` the 4x4 pose of scan 0.  A voxel map of
     `voxel_size` metres is created over `extent` = (lo, dims) in cells (binding.voxel_map_extent); extent None: the bounds of scan 0's
     finite points at the start pose, grown by `margin` metres on every side.  Scan 0 is fused at the start pose; every later scan is
     aligned to the map built so far (voxelized GICP with **vgicp_options, the fields of binding.vgicp_options) and fused at the pose
     found; a scan that fails is skipped and carries the pose.  Returns (poses: one 4x4 per scan, records: one per scan after the first,
-    status: the first per-scan error, or 0).  The map stays in the context (Context.voxel_map)."""
+    status: the first per-scan error, or 0).  The map stays in the context (Context.voxel_map).
+    hashed=True: the map is a hash table of cells of at least `capacity` slots that grows as it fills (Context.voxel_map_create_hashed):
+    it has no extent, so a trajectory cannot leave it; `extent` and `margin` are not used, and passing an extent is a ValueError.  The
+    map is then read with Context.voxel_map_hashed."""
     from . import binding
     start = np.asarray(start_pose, np.float32)
+    if hashed:
+        if extent is not None:
+            raise ValueError("a hashed map has no extent")
+        ctx.voxel_map_create_hashed(voxel_size, capacity)
+        pose, recs, rc = ctx.track_scans_vmap(scans, start, options=binding.vgicp_options(voxel_size=voxel_size, **vgicp_options))
+        return [start.copy()] + [r["pose"] for r in recs], recs, rc
     if extent is None:
         p0 = np.asarray(scans[0][0], np.float64)
         p0 = p0[np.isfinite(p0).all(1)]

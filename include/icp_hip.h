@@ -971,9 +971,10 @@ int icp_voxel_map_destroy(icp_ctx* ctx);
  * {0, 1}, for covariance_k = 0 with a cloud that has no normals; ICP_ERR_NO_TARGET / ICP_ERR_NO_SOURCE without the cloud. */
 int icp_voxel_map_insert(icp_ctx* ctx, int32_t which, const float pose[16], icp_voxel_map_insert_info* info_out);
 /* The map: counts_out one int32 per cell, sums_out nine int64 per cell, cells_out nine floats per cell; any pointer may be NULL.
- * ICP_ERR_INVALID_ARG without a map. */
+ * ICP_ERR_INVALID_ARG without a map, and for a hashed map (icp_get_voxel_map_hashed). */
 int icp_get_voxel_map(icp_ctx* ctx, icp_voxel_map_info* info_out, int32_t* counts_out, int64_t* sums_out, float* cells_out);
-/* Replaces the integer state (counts >= 0: one int32 per cell; sums: nine int64 per cell) and recomputes every record and n_occupied. */
+/* Replaces the integer state (counts >= 0: one int32 per cell; sums: nine int64 per cell) and recomputes every record and n_occupied.
+ * Dense maps only (a hashed map: icp_voxel_map_upload_hashed). */
 int icp_voxel_map_upload(icp_ctx* ctx, const int32_t* counts, const int64_t* sums);
 /* icp_vgicp_system against the map. */
 int icp_voxel_map_system(icp_ctx* ctx, const float pose[16], const icp_vgicp_options* opt, double* sums_out, int32_t* counts_out);
@@ -988,6 +989,51 @@ int icp_voxel_map_align(icp_ctx* ctx, const icp_vgicp_options* opt, float pose_i
  * scan.  The last scan stays resident as the source.  out: n_scans - 1 records (may be NULL for n_scans = 1). */
 int icp_track_scans_vmap(icp_ctx* ctx, const float* const* xyz, const float* const* normals, const int32_t* n, int32_t n_scans,
                          const icp_vgicp_options* opt, float pose_inout[16], icp_vgicp_record* out);
+
+/* -------- the hashed voxel map (an extension): the same map without an extent.  DESIGN.md section 6u. --------
+ * A second storage for the voxel map above.  The per-cell state, the options and every rule of an insert, of the records and of an
+ * alignment are the ones above, word for word; the cells are addressed by a hash of their coordinates instead of by their place in a box.
+ * The entry points above (icp_voxel_map_insert / _system / _align / _destroy, icp_track_scans_vmap) work on whichever map the context
+ * holds; with a dense map they do exactly what they did.  tests/hmap_restatement.py restates what follows.
+ *
+ * Key: a cell of coordinates c is STORABLE iff -2^20 <= c_a < 2^20 on every axis; its key is
+ *   ((uint64)(c_z + 2^20) << 42) | ((uint64)(c_y + 2^20) << 21) | (uint64)(c_x + 2^20).  An empty slot holds ~0ull, which is never a key.
+ *   An entering point whose cell is not storable is OUTSIDE (n_outside), as beyond a dense extent; a source point whose cell is not
+ *   storable is not valid.
+ * Table: capacity is a power of two, 2^8 .. 2^26 slots.  The home slot of a key is (key * 0x9E3779B97F4A7C15 mod 2^64) >> (64 - log2
+ *   capacity); collisions go to the next slot, wrapping at the end (linear probing); every probe loop is bounded by capacity.  An insert
+ *   claims a slot with a 64-bit atomicCAS(empty -> key) and accepts a slot that already holds its key.  WHERE a cell is stored is not part
+ *   of the contract; the set of (key, count, sums, record) is, exactly: it equals a dense map's over a covering extent bit for bit.
+ * Room rule: before a cloud of n points goes in, the host makes sure that capacity >= 2 (n_occupied + n), with n_occupied exact or the
+ *   host's upper bound on it (the last value read plus the points of every insert since); where the bound fails the true count is read,
+ *   and where that fails the table is doubled until it holds.  Past 2^26 slots the call is refused (ICP_ERR_INVALID_ARG, with a reason)
+ *   before anything is modified.  So an insert always finds room and probe chains stay short.  Points that found no slot are counted all
+ *   the same (n_unplaced, which stays 0); a nonzero value makes the call return ICP_ERR_HIP with a message.
+ * Growth: rehashing allocates and clears a larger table and re-inserts every occupied slot's key, copying its count, sums and record; the
+ *   set of (key, state) is unchanged bit for bit.  n_grown counts the times the table was enlarged.  A table never shrinks.
+ * A capacity that is not a power of two is rounded UP to one (and to 2^8 at least). */
+typedef struct icp_voxel_hash_map_info {
+    float   voxel_size;
+    int32_t capacity, n_occupied, n_grown, n_unplaced, reserved[3];
+} icp_voxel_hash_map_info;
+#ifdef __cplusplus
+static_assert(sizeof(icp_voxel_hash_map_info) == 32, "icp_voxel_hash_map_info");
+#endif
+/* Allocates and clears a hashed map of at least `capacity` slots (8 + 4 + 72 + 40 + 4 bytes per slot); replaces any map, dense or hashed.
+ * ICP_ERR_INVALID_ARG: voxel_size not finite and > 0, capacity < 1 or > 2^26. */
+int icp_voxel_map_create_hashed(icp_ctx* ctx, float voxel_size, int32_t capacity);
+/* Rehashes into a table of at least `capacity` slots; a smaller or equal capacity is a no-op.  Hashed maps only; capacity in 1 .. 2^26. */
+int icp_voxel_map_reserve(icp_ctx* ctx, int32_t capacity);
+/* The occupied entries sorted by key ascending (z, then y, then x): coords_out three int32 per entry, counts_out one, sums_out nine int64,
+ * cells_out nine floats; any pointer may be NULL.  ICP_ERR_INVALID_ARG without a hashed map, or for max_entries < n_occupied while an
+ * array is asked for.  A save path: the host downloads the slots, compacts and sorts them. */
+int icp_get_voxel_map_hashed(icp_ctx* ctx, icp_voxel_hash_map_info* info_out, int32_t max_entries, int32_t* coords_out, int32_t* counts_out,
+                             int64_t* sums_out, float* cells_out);
+/* Replaces the map's state by n entries (coords: three int32 each; counts >= 0; sums: nine int64 each) and computes every record; an
+ * entry with count 0 is an empty cell and is not stored.  The capacity is kept, or grown so that capacity >= 2 n.  Refused with a
+ * reason before anything is modified: n < 0, a negative count, a coordinate that is not storable, a coordinate that occurs twice, n
+ * beyond 2^25. */
+int icp_voxel_map_upload_hashed(icp_ctx* ctx, int32_t n, const int32_t* coords, const int32_t* counts, const int64_t* sums);
 
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
