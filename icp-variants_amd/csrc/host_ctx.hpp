@@ -1,6 +1,6 @@
 // host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
 // and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
-// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_sdf, host_vgicp, host_vmap, host_sdf_color, host_tsdf_mesh, host_global, host_debug.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_sdf, host_vgicp, host_hmap, host_vmap, host_vmap_prune, host_sdf_color, host_tsdf_mesh, host_global, host_debug.
 using namespace icpdev;
 
 #define HIPCK(ctx, expr)                                                                        \
@@ -157,6 +157,7 @@ struct icp_ctx {
     bool vm_on = false; icp_voxel_map_options vm_opt = {0.f, {0, 0, 0}, {0, 0, 0}}; int vm_serial = 0;   // the map exists (icp_voxel_map_create); its voxel size and extent; the serial number of the last insert
     DevBuf vh_keys;                      // the hashed storage of the map (host_hmap.hpp): one 8-byte key per slot; vm_count .. vm_stamp are then indexed by slot
     bool vm_hashed = false; int vh_log2cap = 0, vh_grown = 0; long long vh_bound = 0;   // the map is hashed (icp_voxel_map_create_hashed; vm_opt holds its voxel size alone); capacity = 2^vh_log2cap; rehashes so far; the host's upper bound on the occupied count
+    bool vh_vac = false; int vh_compacted = 0; long long vh_vac_bound = 0;   // local maps (host_vmap_prune.hpp): a prune has been enqueued since the last compaction, so slots may be vacated (false: none is, and every hashed call does what it did before prunes existed); compactions so far; the host's upper bound on the vacated count
     float cos_reject = 0.5f;
     std::vector<Event> events;
     Event build_ev[2];                   // index-build bracket (build_bvh)

@@ -44,11 +44,24 @@ void hmap_adopt(icp_ctx* c, int log2cap, HmBufs& b) {
     c->vh_log2cap = log2cap;
 }
 // Growth: a cleared table of 2^log2cap slots, k_hmap_rehash over the old one, and the old one freed once the kernel has finished.
-int hmap_rehash(icp_ctx* c, int log2cap) {
+// compact: k_hmap_compact in its place, which leaves the slots without points behind (section 6v); the vacated count goes back to 0.
+int hmap_rehash(icp_ctx* c, int log2cap, bool compact = false) {
     int rc;
     HmBufs b;
     if ((rc = hmap_alloc(c, log2cap, b))) return rc;
     const int old_cap = (int)hm_cap(c);
+    if (compact) {
+        hipLaunchKernelGGL(k_hmap_compact, dim3((old_cap + 255) / 256), dim3(256), 0, c->stream, old_cap, (const unsigned long long*)c->vh_keys.as<unsigned long long>(),
+                           (const int*)c->vm_count.as<int>(), (const long long*)c->vm_sums.as<long long>(), (const float2*)c->vm_cells.as<float2>(),
+                           b.keys.as<unsigned long long>(), log2cap, b.count.as<int>(), b.sums.as<long long>(), b.cells.as<float2>(), c->vm_ctr.as<int>());
+        HIPCK(c, hipGetLastError());
+        HIPCK(c, hipMemsetAsync(c->vm_ctr.as<int>() + VM_VACATED, 0, 4, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (log2cap > c->vh_log2cap) c->vh_grown++;
+        hmap_adopt(c, log2cap, b);
+        c->vh_compacted++; c->vh_vac = false; c->vh_vac_bound = 0;
+        return ICP_OK;
+    }
     hipLaunchKernelGGL(k_hmap_rehash, dim3((old_cap + 255) / 256), dim3(256), 0, c->stream, old_cap, (const unsigned long long*)c->vh_keys.as<unsigned long long>(),
                        (const int*)c->vm_count.as<int>(), (const long long*)c->vm_sums.as<long long>(), (const float2*)c->vm_cells.as<float2>(),
                        b.keys.as<unsigned long long>(), log2cap, b.count.as<int>(), b.sums.as<long long>(), b.cells.as<float2>(), c->vm_ctr.as<int>());
@@ -58,24 +71,40 @@ int hmap_rehash(icp_ctx* c, int log2cap) {
     c->vh_grown++;
     return ICP_OK;
 }
-// The room rule: capacity >= 2 (occupied + n) before n points (or entries) go in.  `occupied` is the host's bound; when the bound fails the
-// true count is read (4 bytes), and when that fails too the table is doubled until it holds.  Past 2^26: refused, nothing modified.
+// The room rule: capacity >= 2 (occupied + vacated + n) before n points (or entries) go in.  `occupied` and `vacated` are the host's bounds
+// (vacated is 0 on a map that was never pruned, and then this is the rule of section 6u, read for read); when the bounds fail the true
+// counts are read in one copy, and when those fail too the table is doubled until it holds (nothing vacated) or compacted into the smallest
+// table of at least this capacity with 2 (occupied + n) <= 0.75 capacity (section 6v).  Past 2^26: refused, nothing modified.
+int hmap_read_vacated(icp_ctx* c) {
+    int t[3], rc;
+    if ((rc = read_count(c, c->vm_ctr.as<int>() + VM_OCCUPIED, t, 3))) return rc;
+    c->vh_bound = t[0]; c->vh_vac_bound = t[2]; c->vh_vac = t[2] > 0;
+    return ICP_OK;
+}
 int hmap_room(icp_ctx* c, long long n, const char* who) {
     int rc;
-    if (2 * (c->vh_bound + n) > (long long)hm_cap(c)) {
-        int occ = 0;
-        if ((rc = read_count(c, c->vm_ctr.as<int>() + VM_OCCUPIED, &occ))) return rc;
-        c->vh_bound = occ;
+    if (2 * (c->vh_bound + c->vh_vac_bound + n) > (long long)hm_cap(c)) {
+        if (c->vh_vac) { if ((rc = hmap_read_vacated(c))) return rc; }
+        else {
+            int occ = 0;
+            if ((rc = read_count(c, c->vm_ctr.as<int>() + VM_OCCUPIED, &occ))) return rc;
+            c->vh_bound = occ;
+        }
     }
+    if (2 * (c->vh_bound + c->vh_vac_bound + n) <= (long long)hm_cap(c)) return ICP_OK;
     const long long need = 2 * (c->vh_bound + n);
-    if (need <= (long long)hm_cap(c)) return ICP_OK;
-    const int l = hm_log2_for(need);
+    int l = hm_log2_for(need);
+    if (c->vh_vac_bound > 0) {                         // (exact by now) compaction, with hysteresis
+        l = c->vh_log2cap;
+        while (l <= HM_MAX_LOG2 && 4 * need > 3 * (1ll << l)) l++;
+        if (l > HM_MAX_LOG2) l = -1;
+    }
     if (l < 0) {
         char buf[224];
         snprintf(buf, sizeof(buf), "%s: %lld occupied cells and %lld more points need a table of more than 2^26 slots (capacity >= 2 (occupied + points))", who, c->vh_bound, n);
         c->err = buf; return ICP_ERR_INVALID_ARG;
     }
-    return hmap_rehash(c, l);
+    return hmap_rehash(c, l, c->vh_vac_bound > 0);
 }
 // the counter that must stay 0
 int hmap_unplaced_error(icp_ctx* c, int n_unplaced, const char* who) {
@@ -148,13 +177,13 @@ int icp_voxel_map_create_hashed(icp_ctx* c, float voxel_size, int32_t capacity) 
     const int l = hm_log2_for(capacity);
     HmBufs b;
     if ((rc = hmap_alloc(c, l, b))) return rc;
-    if ((rc = ensure(c, c->vm_ctr, VM_NCTR * 4))) return rc;
+    if ((rc = ensure(c, c->vm_ctr, VM_CTR_WORDS * 4))) return rc;
     HIPCK(c, hipMemsetAsync(c->vm_ctr.p, 0, VM_NCTR * 4, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     hmap_adopt(c, l, b);
     c->vm_opt.voxel_size = voxel_size;
     for (int a = 0; a < 3; a++) { c->vm_opt.lo[a] = 0; c->vm_opt.dims[a] = 0; }
-    c->vm_serial = 0; c->vh_grown = 0; c->vh_bound = 0; c->vm_hashed = true; c->vm_on = true;
+    c->vm_serial = 0; c->vh_grown = 0; c->vh_bound = 0; c->vh_vac = false; c->vh_compacted = 0; c->vh_vac_bound = 0; c->vm_hashed = true; c->vm_on = true;
     return guard.done();
 }
 
@@ -168,7 +197,8 @@ int icp_voxel_map_reserve(icp_ctx* c, int32_t capacity) {
     if (l <= c->vh_log2cap) return ICP_OK;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = hmap_rehash(c, l))) return rc;
+    if (c->vh_vac && (rc = hmap_read_vacated(c))) return rc;      // (a pruned map: compacted on the way when slots are vacated)
+    if ((rc = hmap_rehash(c, l, c->vh_vac))) return rc;
     if ((rc = hmap_read_counters(c, nullptr, who))) return rc;
     return guard.done();
 }
@@ -196,17 +226,18 @@ int icp_get_voxel_map_hashed(icp_ctx* c, icp_voxel_hash_map_info* info_out, int3
     // a save path: the slots to the host, then compacted and sorted by key
     const size_t cap = hm_cap(c);
     std::vector<unsigned long long> keys(cap);
-    std::vector<int32_t> cnt(counts_out ? cap : 0);
+    const bool want_cnt = counts_out || c->vh_vac;      // (a vacated slot has a key and no points: it is no entry)
+    std::vector<int32_t> cnt(want_cnt ? cap : 0);
     std::vector<int64_t> sm(sums_out ? cap * VG_NSUM : 0);
     std::vector<float> rec(cells_out ? cap * 10 : 0);
     HIPCK(c, hipMemcpyAsync(keys.data(), c->vh_keys.p, cap * 8, hipMemcpyDeviceToHost, c->stream));
-    if (counts_out) HIPCK(c, hipMemcpyAsync(cnt.data(), c->vm_count.p, cap * 4, hipMemcpyDeviceToHost, c->stream));
+    if (want_cnt) HIPCK(c, hipMemcpyAsync(cnt.data(), c->vm_count.p, cap * 4, hipMemcpyDeviceToHost, c->stream));
     if (sums_out) HIPCK(c, hipMemcpyAsync(sm.data(), c->vm_sums.p, cap * VG_NSUM * 8, hipMemcpyDeviceToHost, c->stream));
     if (cells_out) HIPCK(c, hipMemcpyAsync(rec.data(), c->vm_cells.p, cap * 40, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     std::vector<std::pair<unsigned long long, uint32_t>> occ;
     occ.reserve((size_t)tail[0]);
-    for (size_t i = 0; i < cap; i++) if (keys[i] != HM_EMPTY) occ.emplace_back(keys[i], (uint32_t)i);
+    for (size_t i = 0; i < cap; i++) if (keys[i] != HM_EMPTY && (!c->vh_vac || cnt[i] > 0)) occ.emplace_back(keys[i], (uint32_t)i);
     if (occ.size() != (size_t)tail[0]) { c->err = std::string(who) + ": the table's keys and its occupied count disagree"; return ICP_ERR_HIP; }
     std::sort(occ.begin(), occ.end());
     for (size_t e = 0; e < occ.size(); e++) {
@@ -251,7 +282,7 @@ int icp_voxel_map_upload_hashed(icp_ctx* c, int32_t n, const int32_t* coords, co
     HIPCK(c, hipMemsetAsync(c->vm_ctr.p, 0, VM_NCTR * 4, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     hmap_adopt(c, log2cap, b);
-    c->vm_serial = 0; c->vh_bound = n;
+    c->vm_serial = 0; c->vh_bound = n; c->vh_vac = false; c->vh_vac_bound = 0;
     if (n > 0) {
         DevBuf up;
         const size_t b_xyz = (size_t)n * 12, b_cnt = (size_t)n * 4, b_sum = (size_t)n * VG_NSUM * 8;

@@ -87,14 +87,14 @@ int icp_voxel_map_create(icp_ctx* c, const icp_voxel_map_options* opt) {
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     c->vm_on = false;
-    if (c->vm_hashed) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->vh_keys); c->vm_hashed = false; }
+    if (c->vm_hashed) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->vh_keys); c->vm_hashed = false; c->vh_vac = false; c->vh_vac_bound = 0; }
     c->vm_opt = *opt;
     const size_t n = vm_cells(c);
     if ((rc = ensure(c, c->vm_count, n * 4))) return rc;
     if ((rc = ensure(c, c->vm_sums, n * VG_NSUM * 8))) return rc;
     if ((rc = ensure(c, c->vm_cells, n * 40))) return rc;
     if ((rc = ensure(c, c->vm_stamp, n * 4))) return rc;
-    if ((rc = ensure(c, c->vm_ctr, VM_NCTR * 4))) return rc;
+    if ((rc = ensure(c, c->vm_ctr, VM_CTR_WORDS * 4))) return rc;
     if ((rc = ensure(c, c->vm_box, sizeof(VgBox)))) return rc;
     HIPCK(c, hipMemsetAsync(c->vm_count.p, 0, n * 4, c->stream));
     HIPCK(c, hipMemsetAsync(c->vm_sums.p, 0, n * VG_NSUM * 8, c->stream));

@@ -9,7 +9,7 @@
 // Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_converge.hpp, dev_solve.hpp,
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
 // dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf_color.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp, dev_sdf.hpp, dev_sdf_color.hpp, dev_vgicp.hpp,
-// dev_vmap.hpp, dev_hmap.hpp
+// dev_vmap.hpp, dev_hmap.hpp, dev_vmap_prune.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -62,6 +62,9 @@
 //   k_vmap_records      those cells, and the records of the cells it touched; the alignment is k_vgicp_accumulate's (dev_vmap.hpp)
 //   k_hmap_*            the same map stored in a hash table of cells, without an extent (icp_voxel_map_create_hashed): insert, records,
 //                       accumulate by probing, growth by rehashing, upload (dev_hmap.hpp)
+//   k_vmap_prune /      forgetting the map's cells beyond a radius of a centre (icp_voxel_map_prune, icp_track_scans_vmap_local), and
+//   k_hmap_prune /      the compaction of a hashed table that has vacated slots (dev_vmap_prune.hpp)
+//   k_hmap_compact
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -102,5 +105,6 @@ namespace icpdev {
 #include "dev_vgicp.hpp"
 #include "dev_vmap.hpp"
 #include "dev_hmap.hpp"
+#include "dev_vmap_prune.hpp"
 
 }  // namespace icpdev

@@ -36,6 +36,7 @@
 #include "host_vgicp.hpp"
 #include "host_hmap.hpp"
 #include "host_vmap.hpp"
+#include "host_vmap_prune.hpp"
 #include "host_sdf_color.hpp"
 #include "host_tsdf_mesh.hpp"
 #include "host_global.hpp"

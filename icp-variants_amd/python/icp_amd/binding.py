@@ -165,6 +165,15 @@ class IcpVoxelHashMapInfo(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class IcpVoxelMapPruneInfo(C.Structure):
+    _fields_ = [("n_removed", C.c_int32), ("n_occupied", C.c_int32), ("n_vacated", C.c_int32), ("n_compacted", C.c_int32), ("capacity", C.c_int32),
+                ("reserved", C.c_int32), ("n_points_removed", C.c_int64)]
+
+
+def _prune_info(info):
+    return {k: int(getattr(info, k)) for k, _ in info._fields_ if k != "reserved"}
+
+
 def voxel_map_options(voxel_size, lo, dims):
     """icp_voxel_map_options: the voxel size in metres and the extent in cells (lowest cell, cells per axis)."""
     o = IcpVoxelMapOptions()
@@ -391,6 +400,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_voxel_map_options_check", "icp_voxel_map_create", "icp_voxel_map_destroy", "icp_voxel_map_insert", "icp_get_voxel_map", "icp_voxel_map_upload",
            "icp_voxel_map_system", "icp_voxel_map_align", "icp_track_scans_vmap",
            "icp_voxel_map_create_hashed", "icp_voxel_map_reserve", "icp_get_voxel_map_hashed", "icp_voxel_map_upload_hashed",
+           "icp_voxel_map_prune", "icp_voxel_map_compact", "icp_track_scans_vmap_local",
            "icp_lm_options_default", "icp_set_optimizer", "icp_get_lm_summaries",
            "icp_gicp_options_default", "icp_set_gicp_options", "icp_get_gicp_options", "icp_get_gicp_normals",
            "icp_colored_options_default", "icp_set_colored_options", "icp_get_colored_options", "icp_get_color_gradients",
@@ -1209,7 +1219,8 @@ class Context:
         self._ck(self.lib.icp_voxel_map_create_hashed(self.h, C.c_float(voxel_size), C.c_int32(capacity)))
 
     def voxel_map_reserve(self, capacity):
-        """icp_voxel_map_reserve: rehashes the hashed map into at least `capacity` slots (smaller or equal: nothing happens)."""
+        """icp_voxel_map_reserve: rehashes the hashed map into at least `capacity` slots (smaller or equal: nothing happens); slots that a prune
+        vacated are dropped on the way."""
         self._ck(self.lib.icp_voxel_map_reserve(self.h, C.c_int32(capacity)))
 
     def voxel_map_hashed(self):
@@ -1232,6 +1243,20 @@ class Context:
             raise ValueError("coords (n, 3), counts (n,) and sums (n, 9) must agree in n")
         self._ck(self.lib.icp_voxel_map_upload_hashed(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(cn), _ptr(sm)))
 
+    def voxel_map_prune(self, centre, radius):
+        """icp_voxel_map_prune: every cell of the map (dense or hashed) whose centre lies beyond `radius` metres of `centre` goes back to
+        the cleared state.  Returns dict(n_removed, n_occupied, n_vacated, n_compacted, capacity, n_points_removed)."""
+        ce = _f32(centre).reshape(-1)
+        if ce.size != 3:
+            raise ValueError("centre is three numbers")
+        info = IcpVoxelMapPruneInfo()
+        self._ck(self.lib.icp_voxel_map_prune(self.h, _ptr(ce), C.c_float(radius), C.byref(info)))
+        return _prune_info(info)
+
+    def voxel_map_compact(self):
+        """icp_voxel_map_compact: drops the slots a prune vacated from the hashed map, at its current capacity (none: nothing happens)."""
+        self._ck(self.lib.icp_voxel_map_compact(self.h))
+
     def voxel_map_system(self, pose, options=None, **kw):
         """icp_voxel_map_system: the 28 sums of one voxelized GICP step of the resident source at `pose` against the map.  Returns (sums
         (28,) float64, (considered, valid))."""
@@ -1253,10 +1278,12 @@ class Context:
             return pose_from_c(p), r, rc, [_record(tr[i]) for i in range(r["iterations"])]
         return pose_from_c(p), r, rc
 
-    def track_scans_vmap(self, scans, pose=None, options=None, **kw):
+    def track_scans_vmap(self, scans, pose=None, keep_radius=None, options=None, **kw):
         """icp_track_scans_vmap: `scans`, a list of (xyz (n, 3), normals (n, 3) or None) in the sensor frame, tracked against the map:
         scan 0 inserted at `pose` (identity by default), every later scan aligned to the map and, when that succeeds, inserted at the
-        pose found.  Returns (final pose, the records of scans 1 .., status: the first per-scan error, or 0)."""
+        pose found.  Returns (final pose, the records of scans 1 .., status: the first per-scan error, or 0).
+        keep_radius (metres): icp_track_scans_vmap_local -- after every insert the map is pruned about the scan's position, so it stays
+        local; then a fourth value is returned, the prune info of every scan (`voxel_map_prune`'s dict; all zero for a skipped scan)."""
         o = options if options is not None else vgicp_options(**kw)
         ns = len(scans)
         pts = [_f32(s[0]) for s in scans]
@@ -1267,10 +1294,16 @@ class Context:
         cnt = (C.c_int32 * ns)(*[len(a) for a in pts])
         p = pose_to_c(np.eye(4) if pose is None else pose)
         out = (IcpSdfFrame * max(ns - 1, 1))()
-        rc = self.lib.icp_track_scans_vmap(self.h, xp, npp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out)
+        if keep_radius is None:
+            rc = self.lib.icp_track_scans_vmap(self.h, xp, npp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out)
+        else:
+            pr = (IcpVoxelMapPruneInfo * max(ns, 1))()
+            rc = self.lib.icp_track_scans_vmap_local(self.h, xp, npp, cnt, C.c_int32(ns), C.byref(o), C.c_float(keep_radius), _ptr(p), out, pr)
         if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-scan outcomes: reported in the records
             self._ck(rc)
-        return pose_from_c(p), [_record(out[i]) for i in range(ns - 1)], rc
+        if keep_radius is None:
+            return pose_from_c(p), [_record(out[i]) for i in range(ns - 1)], rc
+        return pose_from_c(p), [_record(out[i]) for i in range(ns - 1)], rc, [_prune_info(pr[i]) for i in range(ns)]
 
     def estimate_normals(self, xyz, k=5, viewpoint=(0.0, 0.0, 0.0)):
         """PointCloud(pcl cloud): k-NN PCA normals flipped towards the viewpoint (PointCloud.h:41-76)."""

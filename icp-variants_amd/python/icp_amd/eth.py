@@ -93,7 +93,7 @@ def align(ctx, pair, nonlinear=None, check=True, convergence=None, initial="iden
     return ctx.run(start, check=check)
 
 
-def track_map(ctx, scans, start_pose, voxel_size=0.25, extent=None, margin=2.0, hashed=False, capacity=1 << 16, **vgicp_options):
+def track_map(ctx, scans, start_pose, voxel_size=0.25, extent=None, margin=2.0, hashed=False, capacity=1 << 16, keep_radius=None, **vgicp_options):
     """Scan-to-map tracking of a laser sequence (Context.track_scans_vmap): `scans` is a list of (xyz, normals) in the sensor frame
     (normals None where the context's GICP options compute them, covariance_k > 0), `start_pose` the 4x4 pose of scan 0.  A voxel map of
     `voxel_size` metres is created over `extent` = (lo, dims) in cells (binding.voxel_map_extent); extent None: the bounds of scan 0's
@@ -103,15 +103,21 @@ def track_map(ctx, scans, start_pose, voxel_size=0.25, extent=None, margin=2.0, 
     status: the first per-scan error, or 0).  The map stays in the context (Context.voxel_map).
     hashed=True: the map is a hash table of cells of at least `capacity` slots that grows as it fills (Context.voxel_map_create_hashed):
     it has no extent, so a trajectory cannot leave it; `extent` and `margin` are not used, and passing an extent is a ValueError.  The
-    map is then read with Context.voxel_map_hashed."""
+    map is then read with Context.voxel_map_hashed.
+    keep_radius (metres, either storage): the map is kept LOCAL -- after every scan is fused, the cells further than keep_radius from
+    the scan's position are forgotten (Context.voxel_map_prune), so the map's size follows the sensor's range and not the length of the
+    trajectory; a fourth value is then returned, the prune info of every scan."""
     from . import binding
     start = np.asarray(start_pose, np.float32)
+
+    def run():
+        out = ctx.track_scans_vmap(scans, start, keep_radius=keep_radius, options=binding.vgicp_options(voxel_size=voxel_size, **vgicp_options))
+        return ([start.copy()] + [r["pose"] for r in out[1]], out[1]) + tuple(out[2:])
     if hashed:
         if extent is not None:
             raise ValueError("a hashed map has no extent")
         ctx.voxel_map_create_hashed(voxel_size, capacity)
-        pose, recs, rc = ctx.track_scans_vmap(scans, start, options=binding.vgicp_options(voxel_size=voxel_size, **vgicp_options))
-        return [start.copy()] + [r["pose"] for r in recs], recs, rc
+        return run()
     if extent is None:
         p0 = np.asarray(scans[0][0], np.float64)
         p0 = p0[np.isfinite(p0).all(1)]
@@ -120,8 +126,7 @@ def track_map(ctx, scans, start_pose, voxel_size=0.25, extent=None, margin=2.0, 
         w = p0 @ start[:3, :3].astype(np.float64).T + start[:3, 3].astype(np.float64)
         extent = binding.voxel_map_extent(w.min(0) - margin, w.max(0) + margin, voxel_size)
     ctx.voxel_map_create(voxel_size, *extent)
-    pose, recs, rc = ctx.track_scans_vmap(scans, start, options=binding.vgicp_options(voxel_size=voxel_size, **vgicp_options))
-    return [start.copy()] + [r["pose"] for r in recs], recs, rc
+    return run()
 
 
 def write_synthetic_dataset(eth_dir, csv_name, pairs, binary=True):

@@ -1022,11 +1022,13 @@ static_assert(sizeof(icp_voxel_hash_map_info) == 32, "icp_voxel_hash_map_info");
 /* Allocates and clears a hashed map of at least `capacity` slots (8 + 4 + 72 + 40 + 4 bytes per slot); replaces any map, dense or hashed.
  * ICP_ERR_INVALID_ARG: voxel_size not finite and > 0, capacity < 1 or > 2^26. */
 int icp_voxel_map_create_hashed(icp_ctx* ctx, float voxel_size, int32_t capacity);
-/* Rehashes into a table of at least `capacity` slots; a smaller or equal capacity is a no-op.  Hashed maps only; capacity in 1 .. 2^26. */
+/* Rehashes into a table of at least `capacity` slots; a smaller or equal capacity is a no-op.  Hashed maps only; capacity in 1 .. 2^26.
+ * On a pruned map with vacated slots the rehash is a compaction (below). */
 int icp_voxel_map_reserve(icp_ctx* ctx, int32_t capacity);
 /* The occupied entries sorted by key ascending (z, then y, then x): coords_out three int32 per entry, counts_out one, sums_out nine int64,
  * cells_out nine floats; any pointer may be NULL.  ICP_ERR_INVALID_ARG without a hashed map, or for max_entries < n_occupied while an
- * array is asked for.  A save path: the host downloads the slots, compacts and sorts them. */
+ * array is asked for.  A save path: the host downloads the slots, compacts and sorts them.  A slot that a prune vacated (below) is no
+ * entry: only cells with count > 0 are returned. */
 int icp_get_voxel_map_hashed(icp_ctx* ctx, icp_voxel_hash_map_info* info_out, int32_t max_entries, int32_t* coords_out, int32_t* counts_out,
                              int64_t* sums_out, float* cells_out);
 /* Replaces the map's state by n entries (coords: three int32 each; counts >= 0; sums: nine int64 each) and computes every record; an
@@ -1034,6 +1036,54 @@ int icp_get_voxel_map_hashed(icp_ctx* ctx, icp_voxel_hash_map_info* info_out, in
  * reason before anything is modified: n < 0, a negative count, a coordinate that is not storable, a coordinate that occurs twice, n
  * beyond 2^25. */
 int icp_voxel_map_upload_hashed(icp_ctx* ctx, int32_t n, const int32_t* coords, const int32_t* counts, const int64_t* sums);
+
+/* -------- a local map (an extension): forgetting the cells beyond a radius.  DESIGN.md section 6v. --------
+ * A cell is a count and nine integer sums, so REMOVING a cell is putting it back into the cleared state bit for bit: count 0, nine sums
+ * 0, an all-zero 40-byte record, stamp 0 -- exactly what icp_voxel_map_create leaves.  A pruned map therefore equals, exactly, a map
+ * that the removed cells' points never went into.  tests/vmap_prune_restatement.py restates what follows.
+ *
+ * Rule of prune(centre, radius): it applies to every cell with count > 0.  With c the cell's coordinates (dense: lo + its index per axis;
+ *   hashed: from the key), in fp32, operation for operation, without contraction:
+ *     d_a = ((float)c_a + 0.5f) * voxel_size - centre_a  (a = x, y, z),   d2 = (d_x d_x + d_y d_y) + d_z d_z,
+ *   the cell is KEPT iff d2 <= r2, with r2 = radius * radius computed once on the host in fp32; an infinite r2 keeps everything.  Every
+ *   other cell with points is removed.  centre must be finite, radius finite and >= 0: otherwise ICP_ERR_INVALID_ARG with a reason, before
+ *   anything is modified; without a map the call is refused likewise.
+ * Hashed storage: a removed cell KEEPS its key and loses its content -- a VACATED slot.  Keys still only go from empty to a key, probes
+ *   pass the slot, a source point that falls in it reads n = 0 < min_points and is not valid, and a later insert into that cell finds the
+ *   key, sees the count's old value 0 and counts a new cell (n_cells_new, n_occupied), as the dense map does.  n_vacated counts the slots
+ *   vacated since the last compaction; a slot that is occupied again stays counted, so it is an upper bound on the keyed slots without
+ *   points.  The room rule becomes capacity >= 2 (n_occupied + n_vacated + n).  Where it fails with n_vacated = 0 the table grows as
+ *   before.  Where it fails with n_vacated > 0 the table is COMPACTED: rehashed without the slots that have no points, into the
+ *   smallest power of two >= capacity for which 2 (n_occupied + n) <= 0.75 capacity (the 0.75 is hysteresis: a map that sits just under
+ *   the limit is not rebuilt on every scan); then n_vacated = 0 and n_compacted goes up; n_grown goes up when the capacity did.  Past
+ *   2^26 slots the call is refused as before.  icp_voxel_map_reserve to a larger capacity compacts on the way when n_vacated > 0;
+ *   icp_get_voxel_map_hashed returns the entries with count > 0; icp_voxel_map_upload_hashed and a second create reset n_vacated.
+ * A context that never prunes does exactly what it did. */
+typedef struct icp_voxel_map_prune_info {
+    int32_t n_removed;         /* cells this call emptied */
+    int32_t n_occupied;        /* cells with count > 0 after it */
+    int32_t n_vacated;         /* hashed: slots vacated since the last compaction (after the call); dense: 0 */
+    int32_t n_compacted;       /* hashed: compactions over the map's life; dense: 0 */
+    int32_t capacity;          /* hashed: slots; dense: cells of the extent */
+    int32_t reserved;
+    int64_t n_points_removed;  /* the sum of the removed cells' counts */
+} icp_voxel_map_prune_info;
+#ifdef __cplusplus
+static_assert(sizeof(icp_voxel_map_prune_info) == 32, "icp_voxel_map_prune_info");
+#endif
+/* Removes every cell of the map (dense or hashed) whose centre lies beyond `radius` of `centre`, by the rule above.  info_out may be NULL:
+ * then the call is enqueued and the host waits for nothing. */
+int icp_voxel_map_prune(icp_ctx* ctx, const float centre[3], float radius, icp_voxel_map_prune_info* info_out);
+/* Hashed maps only: drops the vacated slots at the current capacity (a no-op with none); the entries keep their bits.  For save paths
+ * and tests; the room rule compacts by itself. */
+int icp_voxel_map_compact(icp_ctx* ctx);
+/* icp_track_scans_vmap with a local map: after every insert, scan 0 included, the map is pruned about the translation of the pose the
+ * scan was inserted at, with keep_radius (finite and > 0).  A scan that fails is carried and skipped as there: no insert, no prune, and
+ * its prune_out entry is all zero.  prune_out: n_scans entries, or NULL.  The host still waits once per scan: a prune's info comes back
+ * with the next scan's record, the last one with the closing wait. */
+int icp_track_scans_vmap_local(icp_ctx* ctx, const float* const* xyz, const float* const* normals, const int32_t* n, int32_t n_scans,
+                               const icp_vgicp_options* opt, float keep_radius, float pose_inout[16], icp_vgicp_record* out,
+                               icp_voxel_map_prune_info* prune_out);
 
 /* PointCloud(pcl::PointCloud<PointXYZ>::Ptr) (PointCloud.h:41-76): normals of an unorganised scan from its k nearest
  * neighbours (pcl::NormalEstimation, setKSearch(5), viewpoint (0,0,0)): exact k-NN on the device, fp64 PCA, normal flipped
