@@ -14,7 +14,7 @@ const char* sdf_options_error(const icp_sdf_options* o) {
 }
 int sdf_check_call(icp_ctx* c, const float* depth, const icp_depth_camera* cam, const float* pose, const icp_sdf_options* opt, const char* who) {
     int rc;
-    if ((rc = tsdf_check_call(c, cam, pose, who))) return rc;
+    if ((rc = tsdf_check_call(c, cam, pose, who, true))) return rc;      // (either storage: sdf_enqueue and sdf_integrate_slot choose the kernels)
     if (!depth) { c->err = std::string(who) + ": null depth frame"; return ICP_ERR_INVALID_ARG; }
     if (const char* why = sdf_options_error(opt)) { c->err = std::string(who) + ": " + why; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;
@@ -45,7 +45,9 @@ int sdf_enqueue(icp_ctx* c, int slot, const SdfPlan& pl, const icp_sdf_options& 
     icp_sdf_iter* tr = (icp_sdf_iter*)(rec + 1);
     double* partials = c->sdf_partials.as<double>();
     int* counts = (int*)(partials + (size_t)SDF_NSUM * pl.n_blocks);
+    const bool hashed = c->tsdf_hashed;
     const TsdfVol v = tsdf_view(c);
+    const HtVol hv = hashed ? htsdf_view(c) : HtVol();
     TsdfMat m; memcpy(m.m, pose, 64);
     HIPCK(c, hipStreamWaitEvent(c->stream, c->depth_up[slot], 0));
     if (trace) HIPCK(c, hipMemsetAsync(tr, 0, (size_t)opt.n_iterations * sizeof(icp_sdf_iter), c->stream));
@@ -56,12 +58,17 @@ int sdf_enqueue(icp_ctx* c, int slot, const SdfPlan& pl, const icp_sdf_options& 
     sp.stop_rotation = opt.stop_rotation; sp.stop_translation = opt.stop_translation;
     const int iterations = step ? opt.n_iterations : 1;
     for (int it = 0; it < iterations; it++) {
-        hipLaunchKernelGGL(k_sdf_accumulate, pl.grid, dim3(256), 0, c->stream, v, f, (const SdfState*)st, partials, counts);
+        if (hashed) hipLaunchKernelGGL(k_hsdf_accumulate, pl.grid, dim3(256), 0, c->stream, hv, f, (const SdfState*)st, partials, counts);
+        else hipLaunchKernelGGL(k_sdf_accumulate, pl.grid, dim3(256), 0, c->stream, v, f, (const SdfState*)st, partials, counts);
         sp.iter = it;
         hipLaunchKernelGGL(k_sdf_solve, dim3(1), dim3(256), 0, c->stream, sp);
     }
     HIPCK(c, hipGetLastError());
     return ICP_OK;
+}
+// tsdf_integrate_slot on whichever storage the volume has (hashed: the touch's counters are read, one more host wait)
+int sdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], bool color, const char* who) {
+    return c->tsdf_hashed ? htsdf_integrate_slot(c, slot, cam, pose, nullptr, who) : tsdf_integrate_slot(c, slot, cam, pose, nullptr, color);
 }
 // The frame's record (and its trace) back through the page-locked block, waited for: the one host read of a frame.
 int sdf_read_record(icp_ctx* c, const icp_sdf_options& opt, icp_sdf_frame* rec_out, icp_sdf_iter* trace_out) {
@@ -101,7 +108,8 @@ int icp_tsdf_sample(icp_ctx* c, const float* points, int32_t n, float* f_out, fl
     if ((rc = ensure(c, c->staging, (size_t)n * 29))) return rc;      // [points 12n | F 4n | G 12n | valid n]
     float* d_pts = c->staging.as<float>(); float* d_f = d_pts + (size_t)n * 3; float* d_g = d_f + n; uint8_t* d_ok = (uint8_t*)(d_g + (size_t)n * 3);
     HIPCK(c, hipMemcpyAsync(d_pts, points, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_tsdf_sample, dim3((n + 255) / 256), dim3(256), 0, c->stream, tsdf_view(c), (const float*)d_pts, (int)n, d_f, d_g, d_ok);
+    if (c->tsdf_hashed) hipLaunchKernelGGL(k_htsdf_sample, dim3((n + 255) / 256), dim3(256), 0, c->stream, htsdf_view(c), (const float*)d_pts, (int)n, d_f, d_g, d_ok);
+    else hipLaunchKernelGGL(k_tsdf_sample, dim3((n + 255) / 256), dim3(256), 0, c->stream, tsdf_view(c), (const float*)d_pts, (int)n, d_f, d_g, d_ok);
     HIPCK(c, hipGetLastError());
     if (f_out) HIPCK(c, hipMemcpyAsync(f_out, d_f, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (grad_out) HIPCK(c, hipMemcpyAsync(grad_out, d_g, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
@@ -169,7 +177,7 @@ int icp_track_depth_sdf(icp_ctx* c, const float* depth_frames, const uint8_t* rg
     if (!c->sdf_ev) HIPCK(c, hipEventCreateWithFlags(&c->sdf_ev.e, hipEventDisableTiming));
     // frame 0 into the model at the incoming pose; frame 1 goes up meanwhile
     if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
-    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose_inout, nullptr, color))) return rc;
+    if ((rc = sdf_integrate_slot(c, 0, *cam, pose_inout, color, who))) return rc;
     HIPCK(c, hipEventRecord(c->sdf_ev, c->stream));
     if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream))) return rc;
     int first_err = ICP_OK;
@@ -186,7 +194,7 @@ int icp_track_depth_sdf(icp_ctx* c, const float* depth_frames, const uint8_t* rg
         if ((rc = sdf_read_record(c, *opt, &r, nullptr))) return rc;
         memcpy(pose_inout, r.pose, 64);
         if (r.status == ICP_OK) {
-            if ((rc = tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, color))) return rc;      // (inverts the pose on the host: why the record is read)
+            if ((rc = sdf_integrate_slot(c, slot, *cam, pose_inout, color, who))) return rc;      // (inverts the pose on the host: why the record is read)
             HIPCK(c, hipEventRecord(c->sdf_ev, c->stream));
         } else if (first_err == ICP_OK) { first_err = r.status; c->err = sdf_failure(who, r, *opt); }
     }

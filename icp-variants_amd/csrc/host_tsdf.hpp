@@ -22,14 +22,25 @@ bool is_identity16(const float* m) {
     for (int k = 0; k < 16; k++) if (m[k] != ((k % 5 == 0) ? 1.f : 0.f)) return false;
     return true;
 }
-int tsdf_check_call(icp_ctx* c, const icp_depth_camera* cam, const float* pose, const char* who) {
+// what host_tsdf_hash.hpp defines for a hashed volume
+int htsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count, const char* who);
+int htsdf_reset(icp_ctx* c);
+void htsdf_drop(icp_ctx* c);
+// the calls that need the dense box: refused on a hashed volume, with nothing touched
+int tsdf_check_dense(icp_ctx* c, const char* who) {
+    if (c->tsdf_on && c->tsdf_hashed) { c->err = std::string(who) + ": not supported on a hashed volume (icp_tsdf_create_hashed): it needs the dense box of icp_tsdf_create"; return ICP_ERR_INVALID_ARG; }
+    return ICP_OK;
+}
+int tsdf_check_call(icp_ctx* c, const icp_depth_camera* cam, const float* pose, const char* who, bool hashed_ok = false) {
     if (!c->tsdf_on) { c->err = std::string(who) + ": no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    if (!hashed_ok) { int rc; if ((rc = tsdf_check_dense(c, who))) return rc; }
     if (!depth_camera_ok(cam) || !pose) { c->err = std::string(who) + ": bad camera or null pose"; return ICP_ERR_INVALID_ARG; }
     if (!is_identity16(cam->extrinsics)) { c->err = std::string(who) + ": the depth extrinsics must be the identity"; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;
 }
 int tsdf_check_color(icp_ctx* c, const char* who) {
     if (!c->tsdf_on) { c->err = std::string(who) + ": no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    { int rc; if ((rc = tsdf_check_dense(c, who))) return rc; }
     if (!c->tsdf_col_on) { c->err = std::string(who) + ": the volume has no colour array (icp_tsdf_color_create)"; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;
 }
@@ -128,6 +139,7 @@ int icp_tsdf_reset(icp_ctx* c) {
     int rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
+    if (c->tsdf_hashed) { if ((rc = htsdf_reset(c))) return rc; return guard.done(); }
     HIPCK(c, hipMemsetAsync(c->tsdf_vox.p, 0, tsdf_voxels(c) * 8, c->stream));      // tsdf 0, weight 0
     if (c->tsdf_col_on) HIPCK(c, hipMemsetAsync(c->tsdf_col.p, 0, tsdf_voxels(c) * 16, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
@@ -141,6 +153,7 @@ int icp_tsdf_release(icp_ctx* c) {
     HIPCK(c, hipStreamSynchronize(c->stream));
     release(c->tsdf_vox);
     release(c->tsdf_col); c->tsdf_col_on = false;
+    if (c->tsdf_hashed) htsdf_drop(c);
     for (DevBuf* d : {&c->tm_bits, &c->tm_mask, &c->tm_base, &c->tm_blk, &c->tm_out}) release(*d);      // the mesh extraction's scratch goes with the volume
     c->tsdf_on = false;
     return ICP_OK;
@@ -150,7 +163,7 @@ int icp_tsdf_create(icp_ctx* c, const icp_tsdf_options* opt) {
     if (const char* why = tsdf_options_error(opt)) { c->err = std::string("icp_tsdf_create: ") + why; return ICP_ERR_INVALID_ARG; }
     int rc;
     if ((rc = set_device(c))) return rc;
-    if (c->tsdf_on) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->tsdf_vox); release(c->tsdf_col); c->tsdf_col_on = false; c->tsdf_on = false; }
+    if (c->tsdf_on) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->tsdf_vox); release(c->tsdf_col); c->tsdf_col_on = false; if (c->tsdf_hashed) htsdf_drop(c); c->tsdf_on = false; }
     c->tsdf_opt = *opt;
     if (c->tsdf_opt.ray_step == 0.f) c->tsdf_opt.ray_step = opt->truncation / 2.f;
     if ((rc = ensure(c, c->tsdf_vox, tsdf_voxels(c) * 8))) return rc;
@@ -163,6 +176,7 @@ int icp_tsdf_create(icp_ctx* c, const icp_tsdf_options* opt) {
 int icp_tsdf_download(icp_ctx* c, float* tsdf_out, float* weight_out) {
     if (!c) return ICP_ERR_INVALID_ARG;
     if (!c->tsdf_on) { c->err = "icp_tsdf_download: no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    if (int rd = tsdf_check_dense(c, "icp_tsdf_download")) return rd;
     int rc;
     if ((rc = set_device(c))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
@@ -179,6 +193,7 @@ int icp_tsdf_download(icp_ctx* c, float* tsdf_out, float* weight_out) {
 int icp_tsdf_upload(icp_ctx* c, const float* tsdf, const float* weight) {
     if (!c) return ICP_ERR_INVALID_ARG;
     if (!c->tsdf_on) { c->err = "icp_tsdf_upload: no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    if (int rd = tsdf_check_dense(c, "icp_tsdf_upload")) return rd;
     if (!tsdf || !weight) { c->err = "icp_tsdf_upload: null array"; return ICP_ERR_INVALID_ARG; }
     int rc;
     if ((rc = set_device(c))) return rc;
@@ -197,6 +212,7 @@ int icp_tsdf_upload(icp_ctx* c, const float* tsdf, const float* weight) {
 int icp_tsdf_color_create(icp_ctx* c) {
     if (!c) return ICP_ERR_INVALID_ARG;
     if (!c->tsdf_on) { c->err = "icp_tsdf_color_create: no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    if (int rd = tsdf_check_dense(c, "icp_tsdf_color_create")) return rd;
     int rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
@@ -253,12 +269,14 @@ int icp_tsdf_integrate(icp_ctx* c, const float* depth, const icp_depth_camera* c
     if (!c) return ICP_ERR_INVALID_ARG;
     if (n_updated_out) *n_updated_out = 0;
     int rc;
-    if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_integrate"))) return rc;
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_integrate", true))) return rc;
     if (!depth) { c->err = "icp_tsdf_integrate: null depth frame"; return ICP_ERR_INVALID_ARG; }
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if ((rc = stage_depth(c, 0, depth, nullptr, cam->width * cam->height, c->stream))) return rc;
-    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>()))) return rc;
+    if (c->tsdf_hashed) rc = htsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>(), "icp_tsdf_integrate");
+    else rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>());
+    if (rc) return rc;
     int n = 0;
     if ((rc = read_count(c, c->tsdf_cnt.p, &n))) return rc;
     if (n_updated_out) *n_updated_out = n;

@@ -56,6 +56,7 @@ int tm_enqueue_fill(icp_ctx* c, const TmGrid& g, const TmScratch& s, float* d_ve
 }
 int tm_check_call(icp_ctx* c, float min_weight, const char* who) {
     if (!c->tsdf_on) { c->err = std::string(who) + ": no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    if (int rd = tsdf_check_dense(c, who)) return rd;
     if (!(std::isfinite(min_weight) && min_weight >= 0.f)) { c->err = std::string(who) + ": min_weight must be finite and >= 0"; return ICP_ERR_INVALID_ARG; }
     if (tsdf_voxels(c) > (size_t)(INT32_MAX / 12)) { c->err = std::string(who) + ": the volume has more than INT32_MAX / 12 voxels"; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;

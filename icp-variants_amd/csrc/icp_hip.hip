@@ -32,6 +32,7 @@
 #include "host_multi.hpp"
 #include "host_depth.hpp"
 #include "host_tsdf.hpp"
+#include "host_tsdf_hash.hpp"
 #include "host_sdf.hpp"
 #include "host_vgicp.hpp"
 #include "host_hmap.hpp"

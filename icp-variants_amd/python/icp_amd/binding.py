@@ -96,6 +96,30 @@ def tsdf_options(dims=None, origin=None, **kw):
     return o
 
 
+class IcpTsdfHashedInfo(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("capacity", C.c_int32), ("n_grown", C.c_int32), ("n_unplaced", C.c_int32), ("n_out_of_range", C.c_int64)]
+
+
+def tsdf_blocks_to_dense(coords, tsdf, weight, lo, dims):
+    """The blocks of a hashed volume (`Context.tsdf_blocks`) as the two dense arrays (nz, ny, nx) `Context.tsdf_upload` takes, on the host:
+    dense voxel (0, 0, 0) is global voxel `lo` (three integers), so the dense volume's origin is origin + lo * voxel_size; voxels no block
+    covers are (0, 0), unobserved, and what lies outside `dims` = (nx, ny, nz) is dropped."""
+    lo = np.asarray(lo, np.int64).reshape(3); nx, ny, nz = (int(d) for d in dims)
+    coords = np.asarray(coords, np.int64).reshape(-1, 3)
+    tsdf = np.asarray(tsdf, np.float32).reshape(-1, 8, 8, 8); weight = np.asarray(weight, np.float32).reshape(-1, 8, 8, 8)
+    if not (len(coords) == len(tsdf) == len(weight)):
+        raise ValueError("coords (B, 3), tsdf and weight (B, 8, 8, 8) must agree in B")
+    T = np.zeros((nz, ny, nx), np.float32); W = np.zeros((nz, ny, nx), np.float32)
+    for b, t, w in zip(coords, tsdf, weight):
+        x0, y0, z0 = (int(v) for v in b * 8 - lo)
+        xs, ys, zs = (slice(max(0, -a), min(8, n - a)) for a, n in ((x0, nx), (y0, ny), (z0, nz)))
+        if xs.start >= xs.stop or ys.start >= ys.stop or zs.start >= zs.stop:
+            continue
+        T[z0 + zs.start:z0 + zs.stop, y0 + ys.start:y0 + ys.stop, x0 + xs.start:x0 + xs.stop] = t[zs, ys, xs]
+        W[z0 + zs.start:z0 + zs.stop, y0 + ys.start:y0 + ys.stop, x0 + xs.start:x0 + xs.stop] = w[zs, ys, xs]
+    return T, W
+
+
 class IcpSdfOptions(C.Structure):
     _fields_ = [("stride", C.c_int32), ("n_iterations", C.c_int32), ("min_valid", C.c_int32), ("huber", C.c_float), ("stop_rotation", C.c_float),
                 ("stop_translation", C.c_float)]
@@ -394,6 +418,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_color_create", "icp_tsdf_color_release", "icp_tsdf_color_download", "icp_tsdf_color_upload", "icp_tsdf_integrate_color",
            "icp_tsdf_raycast_color", "icp_set_target_tsdf_color", "icp_track_depth_model_color", "icp_tsdf_mesh_color",
            "icp_sdf_options_default", "icp_sdf_options_check", "icp_tsdf_sample", "icp_tsdf_sdf_system", "icp_tsdf_align_depth", "icp_track_depth_sdf",
+           "icp_tsdf_create_hashed", "icp_tsdf_reserve_blocks", "icp_tsdf_allocate_blocks", "icp_get_tsdf_hashed", "icp_tsdf_upload_hashed",
            "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
            "icp_track_depth_sdf_color",
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
@@ -927,6 +952,43 @@ class Context:
         self._tsdf_dims = tuple(o.dims)
         if color:
             self.tsdf_color_create()
+
+    def tsdf_create_hashed(self, options=None, block_capacity=1 << 12, **kw):
+        """icp_tsdf_create_hashed: the context's TSDF volume stored in 8 x 8 x 8 voxel blocks behind a hash table, without an extent
+        (DESIGN.md section 6x); `tsdf_options`' arguments without dims (origin, voxel_size, truncation, ...).  block_capacity: blocks of 4 KiB
+        the pool holds before it grows (it doubles on the device when a frame needs more).  Replaces any volume, dense or hashed.
+        `tsdf_integrate`, `tsdf_sample`, `tsdf_sdf_system`, `tsdf_align_depth` and `track_depth_sdf` work on it as on a dense one."""
+        o = options if options is not None else tsdf_options(**kw)
+        self._ck(self.lib.icp_tsdf_create_hashed(self.h, C.byref(o), C.c_int32(block_capacity)))
+        self._tsdf_dims = None
+        self.tsdf_hashed_options = o
+
+    def tsdf_reserve_blocks(self, block_capacity):
+        """icp_tsdf_reserve_blocks: grows the hashed volume's table and pool ahead of time (smaller or equal: nothing happens)."""
+        self._ck(self.lib.icp_tsdf_reserve_blocks(self.h, C.c_int32(block_capacity)))
+
+    def tsdf_allocate_blocks(self, coords):
+        """icp_tsdf_allocate_blocks: allocates the blocks `coords` (n, 3) of the hashed volume (allocated already: no effect)."""
+        cc = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3)
+        self._ck(self.lib.icp_tsdf_allocate_blocks(self.h, C.c_int32(len(cc)), _ptr(cc)))
+
+    def tsdf_blocks(self):
+        """icp_get_tsdf_hashed: (info dict(n_blocks, capacity, n_grown, n_unplaced, n_out_of_range), coords (B, 3) int32, tsdf (B, 8, 8, 8),
+        weight (B, 8, 8, 8) float32, indexed [z, y, x]) of the allocated blocks, sorted by key (z, then y, then x of the block)."""
+        info = IcpTsdfHashedInfo()
+        self._ck(self.lib.icp_get_tsdf_hashed(self.h, C.byref(info), C.c_int32(0), None, None, None))
+        n = info.n_blocks
+        coords = np.empty((n, 3), np.int32); t = np.empty((n, 8, 8, 8), np.float32); w = np.empty((n, 8, 8, 8), np.float32)
+        self._ck(self.lib.icp_get_tsdf_hashed(self.h, C.byref(info), C.c_int32(n), _ptr(coords), _ptr(t), _ptr(w)))
+        return {k: getattr(info, k) for k, _ in info._fields_}, coords, t, w
+
+    def tsdf_upload_blocks(self, coords, tsdf, weight):
+        """icp_tsdf_upload_hashed: replaces the hashed volume's state by the blocks `coords` (B, 3) with `tsdf` and `weight` (B, 8, 8, 8)."""
+        cc = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3)
+        t = _f32(tsdf).reshape(-1, 8, 8, 8); w = _f32(weight).reshape(-1, 8, 8, 8)
+        if not (len(cc) == len(t) == len(w)):
+            raise ValueError("coords (B, 3), tsdf and weight (B, 8, 8, 8) must agree in B")
+        self._ck(self.lib.icp_tsdf_upload_hashed(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(t), _ptr(w)))
 
     def tsdf_color_create(self):
         """icp_tsdf_color_create: the volume's colour array, one (R, G, B, Wc) per voxel, allocated and cleared (called again: cleared)."""

@@ -98,7 +98,18 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     part and the records are icp_sdf_frame's; with color=True in `model` the colour frames are fused as well.  `sdf` without `model` is a
     ValueError.  The dict may also hold color_weight (> 0) and color_huber: every frame is then aligned with the photometric term read from
     the colour array as well (icp_track_depth_sdf_color; the records are icp_sdf_color_frame's), which holds the pose where the geometry
-    leaves it free; that needs color=True in `model`, else it is a ValueError."""
+    leaves it free; that needs color=True in `model`, else it is a ValueError.
+    model=dict(hashed=True, origin=..., voxel_size=..., ...[, block_capacity=...]) together with `sdf` tracks against a HASHED volume
+    (Context.tsdf_create_hashed): no dims, no extent, blocks allocated around the surface as the frames come, so the
+    trajectory need not be known beforehand.  hashed=True without `sdf`, with dims, or with color=True is a ValueError."""
+    hashed = bool(model is not None and model.get("hashed"))
+    if hashed:
+        if sdf is None:
+            raise ValueError("a hashed model is tracked directly (it has no ray-cast): pass sdf=dict(...) as well")
+        if model.get("dims") is not None:
+            raise ValueError("a hashed model has no extent: leave dims out")
+        if model.get("color"):
+            raise ValueError("a hashed model holds no colours: leave color out")
     if sdf is not None and model is None:
         raise ValueError("sdf tracking needs a model: pass model=dict(dims=..., origin=..., ...) as well")
     if sdf is not None and sdf.get("color_weight", 0.0) != 0 and not model.get("color"):
@@ -112,6 +123,11 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     ctx.push_params()
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     tgt_o, src_o = reconstruct_room_options(ctx.params) if options is None else options
+    if hashed:
+        ctx.tsdf_create_hashed(**{k: v for k, v in model.items() if k not in ("hashed", "color", "dims")})
+        _, recs, rc = ctx.track_depth_sdf(seq["depth"], cam, **sdf)
+        poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
+        return poses, recs, rc
     if model is not None:
         ctx.tsdf_create(**model)
         rgbx = None
@@ -138,7 +154,8 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
     (getCurrentFrameCnt, VirtualSensor.h:142-144).  model: as `track` (frame-to-model tracking; the meshes stay per-frame depth meshes).
     model_mesh: with `model` and `out_dir`, a file name: the fused volume's zero level set (Context.tsdf_mesh, in frame 0's camera coordinates) is
     written there as a binary PLY after the last frame -- the reconstructed room as ONE mesh, with per-vertex colours when the model has them
-    (color=True in `model`); None writes nothing more.  sdf: as `track` (direct SDF tracking against the model).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    (color=True in `model`); None writes nothing more.  A hashed model (hashed=True in `model`) is densified over the bounding box of its
+    blocks first (`densify_hashed_model`), which raises when that box does not fit a dense volume.  sdf: as `track` (direct SDF tracking against the model).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
     poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model, sdf=sdf)
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     if out_dir is not None:
@@ -154,12 +171,33 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
             meshio.write_off(path, *mesh)
             out.append(path)
     if model is not None and model_mesh is not None and out_dir is not None:
+        if model.get("hashed"):
+            densify_hashed_model(ctx)
         if model.get("color"):
             v, n, t, col = ctx.tsdf_mesh(colors=True)
             meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), v, n, t, colors=col)
         else:
             meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh())
     return poses, recs, rc, out
+
+
+def densify_hashed_model(ctx):
+    """Replaces the context's hashed volume by a dense one over the bounding box of its blocks, with the same contents (for
+    Context.tsdf_mesh or tsdf_raycast, which need the dense box).  The dense origin is origin + lo * voxel_size, rounded once per axis.
+    Raises ValueError when the volume has no block or the box has more than INT32_MAX voxels."""
+    info, coords, t, w = ctx.tsdf_blocks()
+    if len(coords) == 0:
+        raise ValueError("the hashed model holds no block: nothing to densify")
+    lo = coords.min(0).astype(np.int64) * 8
+    dims = (coords.max(0).astype(np.int64) + 1) * 8 - lo
+    if int(dims[0]) * int(dims[1]) * int(dims[2]) > 0x7FFFFFFF:
+        raise ValueError("the bounding box of the hashed model's blocks, %d x %d x %d voxels, does not fit a dense volume" % tuple(dims))
+    o = ctx.tsdf_hashed_options
+    T, W = binding.tsdf_blocks_to_dense(coords, t, w, lo, dims)
+    origin = [float(np.float32(np.float32(o.origin[a]) + np.float32(lo[a]) * np.float32(o.voxel_size))) for a in range(3)]
+    ctx.tsdf_create(dims=tuple(int(d) for d in dims), origin=origin, voxel_size=o.voxel_size, truncation=o.truncation, max_weight=o.max_weight,
+                    min_depth=o.min_depth, max_depth=o.max_depth, ray_step=o.ray_step)
+    ctx.tsdf_upload(T, W)
 
 
 def _write_list(path, header, rows):

@@ -784,6 +784,60 @@ int icp_tsdf_align_depth(icp_ctx* ctx, const float* depth, const icp_depth_camer
 int icp_track_depth_sdf(icp_ctx* ctx, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames, const icp_depth_camera* cam,
                         const icp_sdf_options* opt, float pose_inout[16], icp_sdf_frame* out);
 
+/* -------- the hashed TSDF volume (an extension): the volume above without a fixed extent, in blocks of 8 x 8 x 8 voxels that a hash table
+ * addresses by block coordinates (Niessner, Zollhoefer, Izadi, Stamminger, "Real-time 3D Reconstruction at Scale using Voxel Hashing",
+ * SIGGRAPH Asia 2013).  DESIGN.md section 6x. --------
+ * The dense volume is a box fixed before the first frame, 8 bytes per voxel whatever the voxel holds; a track that leaves the box is lost
+ * without an error.  The hashed volume allocates blocks on the device from each depth frame, around the surface alone, and direct SDF
+ * tracking runs on it as it is.  A context holds ONE volume, dense or hashed; icp_tsdf_create_hashed replaces either.
+ * tests/htsdf_restatement.py restates what follows, compared bit for bit.
+ *
+ * Storage: a block is 8 x 8 x 8 voxels, one (tsdf, weight) pair each, x fastest (4 KiB).  Voxel g (signed global coordinates) belongs to
+ *   block b = g >> 3 (arithmetic shift) at local index g & 7; its world position is o + (float)g s per axis, the dense formula with a signed
+ *   index.  Options are icp_tsdf_options with dims ignored.  Block coordinates are storable in -2^20 <= b < 2^20.  A table of keys maps a
+ *   block to its index in a POOL of blocks (what costs memory: block_capacity blocks of 4 KiB, plus 12 bytes per table slot and 8 per
+ *   block; the table has at least 2 slots per pool block).  Where a block sits in the pool may depend on a race; what it holds does not.
+ *   A voxel of a block that is not allocated reads as (0, 0): unobserved.
+ * Touch (allocation, in front of every integrate, decided from the depth frame and the pose alone): for each pixel (u, v) with finite d,
+ *   0 < d <= max_depth: a = ((float)u - cx) / fx, b = ((float)v - cy) / fy; for m = 0 .. M, M = ceil(2 truncation / s) (in double):
+ *   z_m = fminf((d - truncation) + (float)m s, d + truncation), skipped unless z_m > 0; q_r = (P_r0 (a z_m) + (P_r1 (b z_m) + P_r2 z_m)) + P_r3;
+ *   the cell is f = floorf((q - o) / s) per axis.  A sample with -2^23 <= f <= 2^23 - 2 on every axis (tested in float; the blocks of its
+ *   eight corners are then storable) allocates the blocks (f + {0, 1}) >> 3 of those corners; any other sample allocates nothing and is
+ *   counted in n_out_of_range.  The SET of blocks is exact and does not depend on the order of anything.
+ * Room: a block that finds no table slot or no pool block is counted (n_unplaced) and gets no storage; the host reads the touch's
+ *   counters, and if anything was unplaced it doubles table and pool (live blocks rehashed, no trace of the failed claims), and runs the
+ *   touch again -- it is idempotent -- until nothing is unplaced; only then is the integrate launched.  Growth beyond 2^22 blocks (16 GiB) is
+ *   refused with ICP_ERR_INVALID_ARG and a message, the volume as it was before the call.
+ * Integrate: the dense rule on every voxel of every allocated block, with (float)g for (float)i; *n_updated_out counts the voxels written.
+ * Field: the dense sample with the cell f tested against -2^23 <= f <= 2^23 - 2 in place of the box; VALID iff the blocks of all eight
+ *   corners exist and all eight weights are > 0.  F, G, the residual, the Jacobian, the sums and the solve are those of direct SDF tracking.
+ * icp_tsdf_reset and icp_tsdf_release work on either storage (reset keeps the capacity); icp_tsdf_integrate, icp_tsdf_sample,
+ *   icp_tsdf_sdf_system, icp_tsdf_align_depth and icp_track_depth_sdf (without colour frames) work on whichever volume the context holds,
+ *   with the same options, records and statuses.  On a hashed volume an integrate waits for the host twice (the touch's counters, the
+ *   update count) and a tracked frame twice (its record, the touch's counters); the dense loop waits once per frame.
+ * Refused on a hashed volume (ICP_ERR_INVALID_ARG, a message that names the hashed volume, no side effect): icp_tsdf_download,
+ *   icp_tsdf_upload, icp_tsdf_raycast*, icp_set_target_tsdf*, icp_track_depth_model*, icp_tsdf_mesh*, icp_tsdf_color_create and every
+ *   *_color call.  A finished model goes into a dense volume block by block (icp_get_tsdf_hashed, then icp_tsdf_upload). */
+typedef struct icp_tsdf_hashed_info {
+    int32_t n_blocks;                /* allocated blocks */
+    int32_t capacity;                /* blocks the pool holds before it grows */
+    int32_t n_grown;                 /* growths since create */
+    int32_t n_unplaced;              /* nonzero: claims of the last touch / allocate found no storage (not a tally; 0 after every successful call) */
+    int64_t n_out_of_range;          /* samples skipped because their cell is not storable, since create / reset / upload */
+} icp_tsdf_hashed_info;
+/* create: opt as for icp_tsdf_create (dims ignored); block_capacity in 1 .. 2^22, rounded up to a power of two. */
+int icp_tsdf_create_hashed(icp_ctx* ctx, const icp_tsdf_options* opt, int32_t block_capacity);
+/* Grows table and pool ahead of time so that `block_capacity` blocks fit without a growth (never shrinks). */
+int icp_tsdf_reserve_blocks(icp_ctx* ctx, int32_t block_capacity);
+/* Allocates the n blocks coords[3 i .. 3 i + 2] (storable, else ICP_ERR_INVALID_ARG; one named twice or allocated already: no effect)
+ * under the room rule. */
+int icp_tsdf_allocate_blocks(icp_ctx* ctx, int32_t n, const int32_t* coords);
+/* The blocks SORTED BY KEY (z, then y, then x of the block coordinate): coords_out n_blocks x 3, tsdf_out and weight_out n_blocks x 8 x 8 x 8
+ * (z, y, x; x fastest).  Every pointer may be NULL; with an array asked for, max_blocks below n_blocks is ICP_ERR_INVALID_ARG. */
+int icp_get_tsdf_hashed(icp_ctx* ctx, icp_tsdf_hashed_info* info_out, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out);
+/* REPLACES the state with n blocks in icp_get_tsdf_hashed's layout (storable, none twice, else ICP_ERR_INVALID_ARG); the counters restart. */
+int icp_tsdf_upload_hashed(icp_ctx* ctx, int32_t n, const int32_t* coords, const float* tsdf, const float* weight);
+
 /* -------- direct SDF tracking with a photometric term (an extension): next to its geometric row a pixel adds an intensity row, read from
  * the colour array in the cell the distance is read in (Bylow, Olsson, Kahl, "Direct Camera Pose Tracking and Mapping With Signed Distance
  * Functions", 2014).  DESIGN.md section 6r. --------
