@@ -1,6 +1,6 @@
 // host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
 // and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
-// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_tsdf_hash, host_sdf, host_vgicp, host_hmap, host_vmap, host_vmap_prune, host_sdf_color, host_tsdf_mesh, host_global, host_debug.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_tsdf_hash, host_sdf, host_vgicp, host_hmap, host_vmap, host_vmap_prune, host_sdf_color, host_tsdf_mesh, host_tsdf_hash_mesh, host_global, host_debug.
 using namespace icpdev;
 
 #define HIPCK(ctx, expr)                                                                        \
@@ -152,6 +152,7 @@ struct icp_ctx {
     DevBuf th_keys, th_vals, th_pool, th_pkey, th_ctr;   // the hashed storage of the volume (host_tsdf_hash.hpp): the table's keys and pool indices, the pool of 4 KiB blocks, every block's key, the counters
     bool tsdf_hashed = false; int th_log2cap = 0, th_pool_cap = 0, th_nblk = 0, th_grown = 0, th_unplaced = 0, th_max_log2 = 22; long long th_oor = 0;   // the volume is hashed (icp_tsdf_create_hashed); table of 2^th_log2cap slots, pool of th_pool_cap blocks; allocated blocks (exact after every call); growths; the last touch's unplaced claims; log2 of the largest pool growth may reach (2^22 blocks; lowered by icp_debug_htsdf_max_blocks alone); samples out of range so far
     DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
+    DevBuf tm_nbr, tm_ord;               // icp_tsdf_mesh_hashed (host_tsdf_hash_mesh.hpp), which also uses the five above: the 27 neighbour ranks of every block; order[rank] -> pool index, then rank_of[pool index]
     DevBuf sdf_state, sdf_partials, sdf_rec; Event sdf_ev;   // direct SDF tracking (host_sdf.hpp, host_sdf_color.hpp): the pose / stop state, partials[28 or 29][blocks] + counts[2 or 3][blocks], the frame record + trace; "the last integration has left its upload slot"
     DevBuf vg_box, vg_count, vg_sums, vg_cells;   // voxelized GICP (host_vgicp.hpp): the target's voxel grid -- bounds + counters, per cell the count, the nine int64 sums, the 40-byte record
     bool vg_ready = false; float vg_voxel = 0.f; icp_voxel_grid_info vg_info = {{0, 0, 0}, {0, 0, 0}, 0, 0};   // the grid is current for vg_voxel (dropped with the target's GICP normal cache); its extent

@@ -154,7 +154,7 @@ int icp_tsdf_release(icp_ctx* c) {
     release(c->tsdf_vox);
     release(c->tsdf_col); c->tsdf_col_on = false;
     if (c->tsdf_hashed) htsdf_drop(c);
-    for (DevBuf* d : {&c->tm_bits, &c->tm_mask, &c->tm_base, &c->tm_blk, &c->tm_out}) release(*d);      // the mesh extraction's scratch goes with the volume
+    for (DevBuf* d : {&c->tm_bits, &c->tm_mask, &c->tm_base, &c->tm_blk, &c->tm_out, &c->tm_nbr, &c->tm_ord}) release(*d);      // the mesh extraction's scratch goes with the volume
     c->tsdf_on = false;
     return ICP_OK;
 }

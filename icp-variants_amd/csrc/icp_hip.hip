@@ -6,6 +6,7 @@
 // =====================================================================================
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
@@ -40,6 +41,7 @@
 #include "host_vmap_prune.hpp"
 #include "host_sdf_color.hpp"
 #include "host_tsdf_mesh.hpp"
+#include "host_tsdf_hash_mesh.hpp"
 #include "host_global.hpp"
 #include "host_debug.hpp"
 

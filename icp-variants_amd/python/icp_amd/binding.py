@@ -419,6 +419,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_raycast_color", "icp_set_target_tsdf_color", "icp_track_depth_model_color", "icp_tsdf_mesh_color",
            "icp_sdf_options_default", "icp_sdf_options_check", "icp_tsdf_sample", "icp_tsdf_sdf_system", "icp_tsdf_align_depth", "icp_track_depth_sdf",
            "icp_tsdf_create_hashed", "icp_tsdf_reserve_blocks", "icp_tsdf_allocate_blocks", "icp_get_tsdf_hashed", "icp_tsdf_upload_hashed",
+           "icp_tsdf_mesh_hashed",
            "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
            "icp_track_depth_sdf_color",
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
@@ -1088,6 +1089,24 @@ class Context:
         if nv.value or nt.value:
             call(v, n, col, t)
         return (v, n, t, col) if colors else (v, n, t)
+
+    def tsdf_mesh_hashed(self, min_weight=0.0, normals=True):
+        """icp_tsdf_mesh_hashed: the zero level set of the HASHED volume as an indexed triangle mesh, extracted on the block pool (a counting
+        call, then a filling call).  The volume stays as it is.  Returns (vertices (V, 3) f32, normals (V, 3) f32 --
+        None with normals=False --, triangles (T, 3) u32); vertices in ascending (block in key order, local voxel, edge code), so the arrays
+        do not depend on where the blocks sit in the pool."""
+        min_weight = float(min_weight)
+        if not (np.isfinite(min_weight) and min_weight >= 0.0):
+            raise ValueError("min_weight must be finite and >= 0")
+        nv, nt = C.c_int32(0), C.c_int32(0)
+
+        def call(v, n, t):
+            self._ck(self.lib.icp_tsdf_mesh_hashed(self.h, C.c_float(min_weight), C.c_int32(nv.value), C.c_int32(nt.value), _ptr(v), _ptr(n), _ptr(t), C.byref(nv), C.byref(nt)))
+        call(None, None, None)
+        v = np.empty((nv.value, 3), np.float32); n = np.empty((nv.value, 3), np.float32) if normals else None; t = np.empty((nt.value, 3), np.uint32)
+        if nv.value or nt.value:
+            call(v, n, t)
+        return v, n, t
 
     def set_target_tsdf(self, cam, pose, check=True, color=False):
         """icp_set_target_tsdf: the ray-cast of the volume from `pose` as the target (organised, with normals).  Returns the number of hits

@@ -147,7 +147,7 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     return poses, recs, rc
 
 
-def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None, model_mesh=None, sdf=None):
+def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None, model_mesh=None, sdf=None, densify=True):
     """reconstructRoom end to end: `track`, then saveRoomToFile (utils.h:179-193) for every scheduled frame k --
     joinMeshes(SimpleMesh(sensor, pose_k, edge_threshold) on the device, SimpleMesh::camera(pose_k, camera_scale), identity) with pose_k
     the camera pose `track` returned (the identity for frame 0).  With out_dir the meshes are written as mesh_<frame index>.off
@@ -155,7 +155,11 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
     model_mesh: with `model` and `out_dir`, a file name: the fused volume's zero level set (Context.tsdf_mesh, in frame 0's camera coordinates) is
     written there as a binary PLY after the last frame -- the reconstructed room as ONE mesh, with per-vertex colours when the model has them
     (color=True in `model`); None writes nothing more.  A hashed model (hashed=True in `model`) is densified over the bounding box of its
-    blocks first (`densify_hashed_model`), which raises when that box does not fit a dense volume.  sdf: as `track` (direct SDF tracking against the model).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    blocks first (`densify_hashed_model`), which raises when that box does not fit a dense volume; densify=False meshes it in place instead
+    (Context.tsdf_mesh_hashed): nothing but the mesh crosses to the host, no box is built and the context keeps its hashed volume.
+    densify=False with a model that is not hashed is a ValueError.  sdf: as `track` (direct SDF tracking against the model).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    if not densify and not (model is not None and model.get("hashed")):
+        raise ValueError("densify=False meshes a hashed model in place: pass model=dict(hashed=True, ...)")
     poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model, sdf=sdf)
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     if out_dir is not None:
@@ -171,6 +175,9 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
             meshio.write_off(path, *mesh)
             out.append(path)
     if model is not None and model_mesh is not None and out_dir is not None:
+        if model.get("hashed") and not densify:
+            meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh_hashed())
+            return poses, recs, rc, out
         if model.get("hashed"):
             densify_hashed_model(ctx)
         if model.get("color"):

@@ -816,8 +816,9 @@ int icp_track_depth_sdf(icp_ctx* ctx, const float* depth_frames, const uint8_t* 
  *   with the same options, records and statuses.  On a hashed volume an integrate waits for the host twice (the touch's counters, the
  *   update count) and a tracked frame twice (its record, the touch's counters); the dense loop waits once per frame.
  * Refused on a hashed volume (ICP_ERR_INVALID_ARG, a message that names the hashed volume, no side effect): icp_tsdf_download,
- *   icp_tsdf_upload, icp_tsdf_raycast*, icp_set_target_tsdf*, icp_track_depth_model*, icp_tsdf_mesh*, icp_tsdf_color_create and every
- *   *_color call.  A finished model goes into a dense volume block by block (icp_get_tsdf_hashed, then icp_tsdf_upload). */
+ *   icp_tsdf_upload, icp_tsdf_raycast*, icp_set_target_tsdf*, icp_track_depth_model*, icp_tsdf_mesh (the hashed volume's own mesh call is icp_tsdf_mesh_hashed,
+ *   below), icp_tsdf_color_create and every *_color call.  A finished model goes into a dense volume block by block (icp_get_tsdf_hashed,
+ *   then icp_tsdf_upload). */
 typedef struct icp_tsdf_hashed_info {
     int32_t n_blocks;                /* allocated blocks */
     int32_t capacity;                /* blocks the pool holds before it grows */
@@ -837,6 +838,39 @@ int icp_tsdf_allocate_blocks(icp_ctx* ctx, int32_t n, const int32_t* coords);
 int icp_get_tsdf_hashed(icp_ctx* ctx, icp_tsdf_hashed_info* info_out, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out);
 /* REPLACES the state with n blocks in icp_get_tsdf_hashed's layout (storable, none twice, else ICP_ERR_INVALID_ARG); the counters restart. */
 int icp_tsdf_upload_hashed(icp_ctx* ctx, int32_t n, const int32_t* coords, const float* tsdf, const float* weight);
+
+/* -------- the hashed model as a mesh (an extension): icp_tsdf_mesh on the block pool -- the zero level set of the context's HASHED volume
+ * as an indexed triangle mesh with per-vertex normals; only the mesh crosses to the host and scratch scales with the blocks in use, not with
+ * an extent.  DESIGN.md section 6y.  tests/htsdf_mesh_restatement.py restates what follows, compared bit for bit. --------
+ * The geometry is icp_tsdf_mesh's (tetrahedra, case table, orientation: see there), read through the hashed volume's addressing:
+ * Definitions: a voxel is a signed global coordinate g; it lies in block b = g >> 3 at local index (g_z & 7) 64 + (g_y & 7) 8 + (g_x & 7).  A
+ *   voxel of a block that does not exist reads (0, 0): unobserved, not negative.  A voxel is OBSERVED iff W > 0, W >= min_weight and F is
+ *   finite, NEGATIVE iff F < 0.f.  Cell g (lowest corner g, corners g + {0,1}^3) is VALID iff its eight corners are observed; it belongs to
+ *   the block of g, its corners may lie in up to 8 blocks.  There is no cell range: a cell exists wherever its lowest corner's block does.
+ * Vertices: the edge v -> v + d, d in {0,1}^3 \ {0}, is owned by v under the code d_x + 2 d_y + 4 d_z; v + d may lie in a neighbouring
+ *   block.  It carries a vertex iff exactly one end is negative and a valid cell v - off, (off & d) == 0, contains it (those cells may lie
+ *   in the lower neighbouring blocks).  Position: t = F_v / (F_v - F_(v+d)), ts = t s; per axis base_r = o_r + (float)g_r s with g the SIGNED
+ *   GLOBAL coordinate of v; p_r = base_r + ts on axes with d_r = 1, p_r = base_r on the others.
+ * Normals: icp_tsdf_mesh's formula and lerp order on the first valid holding cell in ascending off, whose eight corners may span blocks;
+ *   normalised, (0, 0, 0) where not finite.
+ * Order: where a block sits in the pool depends on a race, the output does not.  Blocks come in ascending key order -- z, then y, then x of
+ *   the block coordinate, icp_get_tsdf_hashed's order; a block's position in it is its RANK.  Inside a block voxels come in local linear
+ *   order, x fastest.  Vertices: ascending (rank of the owner's block, local index, code).  Triangles: ascending (rank of the cell's block,
+ *   local index of the cell's lowest corner, tetrahedron, table order).  An exact 0 gives coincident vertices with DISTINCT indices, kept.
+ *   Two volumes with the same blocks give identical arrays, however the blocks were allocated and however often the volume grew.
+ *   As a SET of triangles with their corner positions and normals the result is icp_tsdf_mesh's on the dense volume over the bounding box
+ *   of the blocks (voxels no block covers (0, 0)), bit for bit wherever that volume's shifted origin o + (float)lo s is exact.
+ * Calling: icp_tsdf_mesh's -- the two count pointers are required and always written; all three arrays NULL counts; vertices_out and
+ *   triangles_out go together, normals_out alone may be NULL; a count above its capacity: ICP_ERR_INVALID_ARG, both counts returned, a
+ *   message with the four numbers, nothing written to the arrays; min_weight finite and >= 0.  No volume: ICP_ERR_INVALID_ARG ("no volume").
+ *   A dense volume: ICP_ERR_INVALID_ARG (the message names the dense volume), nothing touched -- icp_tsdf_mesh is the call for it, and it
+ *   keeps refusing a hashed one.  No block, or no sign change: ICP_OK with 0 and 0.  n_blocks * 512 > INT32_MAX / 12: ICP_ERR_INVALID_ARG.
+ *   The volume is never modified (table, pool, counters, options).  The host reads the blocks' keys (8 bytes per block), sorts them and
+ *   uploads the order on every call: one host wait more than icp_tsdf_mesh; nothing is cached between calls.  Scratch comes from the
+ *   context (about 850 bytes per block next to the block's 4 KiB, freed with the volume). */
+int icp_tsdf_mesh_hashed(icp_ctx* ctx, float min_weight, int32_t max_vertices, int32_t max_triangles,
+                         float* vertices_out, float* normals_out, uint32_t* triangles_out,
+                         int32_t* n_vertices_out, int32_t* n_triangles_out);
 
 /* -------- direct SDF tracking with a photometric term (an extension): next to its geometric row a pixel adds an intensity row, read from
  * the colour array in the cell the distance is read in (Bylow, Olsson, Kahl, "Direct Camera Pose Tracking and Mapping With Signed Distance
