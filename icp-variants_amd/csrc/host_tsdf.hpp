@@ -25,6 +25,7 @@ bool is_identity16(const float* m) {
 // what host_tsdf_hash.hpp defines for a hashed volume
 int htsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count, const char* who);
 int htsdf_reset(icp_ctx* c);
+int htsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], bool soa, const TsdfRayOut& o);      // (host_tsdf_hash_raycast.hpp)
 void htsdf_drop(icp_ctx* c);
 // the calls that need the dense box: refused on a hashed volume, with nothing touched
 int tsdf_check_dense(icp_ctx* c, const char* who) {
@@ -89,8 +90,8 @@ int tsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pos
 }
 // The model as target, from the arguments already checked: the ray-cast into the target's planes, the hit count, finish_target.
 // *hits_out = 0 with ICP_ERR_NO_TARGET leaves an empty target.  color: the coloured ray-cast, colours into the target's colour planes;
-// a hit without colour is a hole and *hits_out counts the coloured hits.
-int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], int* hits_out, const char* who, bool color = false) {
+// a hit without colour is a hole and *hits_out counts the coloured hits.  hashed: the ray-cast of the hashed volume (no colours there).
+int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], int* hits_out, const char* who, bool color = false, bool hashed = false) {
     int rc;
     Cloud& tg = c->tgt;
     const int n = cam.width * cam.height, npad = (n + 63) / 64 * 64;
@@ -101,7 +102,7 @@ int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16
     TsdfRayOut o; memset(&o, 0, sizeof(o));
     o.x = tg.x.as<float>(); o.y = tg.y.as<float>(); o.z = tg.z.as<float>(); o.nx = tg.nx.as<float>(); o.ny = tg.ny.as<float>(); o.nz = tg.nz.as<float>(); o.npad = npad;
     const TsdfColorOut co = {tg.rgba.as<uint32_t>(), tg.cr.as<float>(), tg.cg.as<float>(), tg.cb.as<float>()};
-    if ((rc = tsdf_raycast_launch(c, cam, pose, true, o, color ? &co : nullptr))) return rc;
+    if ((rc = hashed ? htsdf_raycast_launch(c, cam, pose, true, o) : tsdf_raycast_launch(c, cam, pose, true, o, color ? &co : nullptr))) return rc;
     int hits = 0;
     if ((rc = read_count(c, c->tsdf_cnt.p, &hits))) return rc;      // (the coloured target's holes are its uncoloured hits: both counts agree)
     tg.has_normals = true; tg.has_colors = color;
@@ -388,12 +389,15 @@ int icp_set_target_tsdf_color(icp_ctx* c, const icp_depth_camera* cam, const flo
 }
 
 // Both tracking loops.  color (icp_track_depth_model_color): frames staged with their colour frame, the coloured target, the source with
-// colours, the coloured integration -- and the colour modes, which the geometric loop refuses, accepted.
+// colours, the coloured integration -- and the colour modes, which the geometric loop refuses, accepted.  hashed
+// (icp_track_depth_model_hashed, never with color): the target from the hashed ray-cast, the integrate htsdf_integrate_slot -- its touch
+// waits for the host once per integrated frame, and once more per growth of the pool.
 static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_t* rgbx_frames, bool color, int32_t n_frames, const icp_depth_camera* cam,
-                             const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out, const std::string& who) {
+                             const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out, const std::string& who,
+                             bool hashed = false) {
     if (!depth_frames || n_frames < 1 || !pose_inout || (n_frames > 1 && !out)) { c->err = who + ": bad argument"; return ICP_ERR_INVALID_ARG; }
     int rc;
-    if ((rc = tsdf_check_call(c, cam, pose_inout, who.c_str()))) return rc;
+    if ((rc = tsdf_check_call(c, cam, pose_inout, who.c_str(), hashed))) return rc;
     if ((rc = check_depth_args(c, cam, source_opt, who.c_str()))) return rc;
     const icp_params& p = c->prm;
     if (p.matching == ICP_MATCH_PROJECTIVE && (p.fx != cam->fx || p.fy != cam->fy || p.cx != cam->cx || p.cy != cam->cy || p.width != cam->width || p.height != cam->height)) {
@@ -414,10 +418,11 @@ static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_
     if ((rc = set_device(c))) return rc;
     const int n = cam->width * cam->height;
     auto frame_rgbx = [&](int k) { return color ? rgbx_frames + (size_t)k * n * 4 : nullptr; };
+    auto integrate = [&](int slot) { return hashed ? htsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, who.c_str()) : tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, color); };
     if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     // frame 0 into the model at the incoming pose; frame 1 goes up meanwhile
     if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
-    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose_inout, nullptr, color))) return rc;
+    if ((rc = integrate(0))) return rc;
     if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream))) return rc;
     if (gt_frames && n_frames > 1 && (rc = track_rmse_prepare(c, n_frames))) return rc;
     static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -432,7 +437,7 @@ static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_
         const int slot = k & 1;
         int hits = 0, kept = 0;
         // the model seen from the current pose (the count read waits for the stream: the integration of frame k - 1 has left its slot)
-        const int trc = set_target_tsdf(c, *cam, pose_inout, &hits, who.c_str(), color);
+        const int trc = set_target_tsdf(c, *cam, pose_inout, &hits, who.c_str(), color, hashed);
         if (trc != ICP_OK && trc != ICP_ERR_NO_TARGET) return trc;
         if ((rc = depth_to_cloud(c, slot, *cam, *source_opt, color, c->src, false, &kept))) return rc;
         // frame k + 1 goes up on the second stream while frame k iterates (its slot was last read by frame k - 1, which has finished)
@@ -464,7 +469,7 @@ static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_
         if (gt_frames && (rc = track_rmse_at(c, 1, dT, d_rmse + 1))) return rc;
         if (r.status == ICP_OK) {
             compose_pose(pose_inout, dT);
-            if ((rc = tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, color))) return rc;
+            if ((rc = integrate(slot))) return rc;
         }
         memcpy(r.pose, pose_inout, 64);
     }

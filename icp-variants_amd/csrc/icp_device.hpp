@@ -9,7 +9,7 @@
 // Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_converge.hpp, dev_solve.hpp,
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
 // dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf_color.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp, dev_sdf.hpp, dev_sdf_color.hpp, dev_vgicp.hpp,
-// dev_vmap.hpp, dev_hmap.hpp, dev_tsdf_hash.hpp, dev_tsdf_hash_mesh.hpp, dev_vmap_prune.hpp
+// dev_vmap.hpp, dev_hmap.hpp, dev_tsdf_hash.hpp, dev_tsdf_hash_raycast.hpp, dev_tsdf_hash_mesh.hpp, dev_vmap_prune.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -64,6 +64,8 @@
 //                       accumulate by probing, growth by rehashing, upload (dev_hmap.hpp)
 //   k_htsdf_* /         the TSDF volume stored in 8 x 8 x 8 voxel blocks behind a hash table, without an extent (icp_tsdf_create_hashed): blocks
 //   k_hsdf_accumulate   allocated from each depth frame, integrate over the pool, the field by lookup, direct SDF tracking on it (dev_tsdf_hash.hpp)
+//   k_htsdf_raycast     the hashed volume seen from a pose (icp_tsdf_raycast_hashed, the target of icp_track_depth_model_hashed): k_tsdf_raycast's
+//                       march with every sample's blocks found by lookup, the lowest corner's block first and remembered per lane (dev_tsdf_hash_raycast.hpp)
 //   k_htm_*             the zero level set of the hashed volume as a triangle mesh (icp_tsdf_mesh_hashed): k_tm_*'s passes indexed by block rank,
 //                       neighbours through a table of ranks, only the mesh crosses to the host (dev_tsdf_hash_mesh.hpp)
 //   k_vmap_prune /      forgetting the map's cells beyond a radius of a centre (icp_voxel_map_prune, icp_track_scans_vmap_local), and
@@ -110,6 +112,7 @@ namespace icpdev {
 #include "dev_vmap.hpp"
 #include "dev_hmap.hpp"
 #include "dev_tsdf_hash.hpp"
+#include "dev_tsdf_hash_raycast.hpp"
 #include "dev_tsdf_hash_mesh.hpp"
 #include "dev_vmap_prune.hpp"
 

@@ -34,6 +34,7 @@
 #include "host_depth.hpp"
 #include "host_tsdf.hpp"
 #include "host_tsdf_hash.hpp"
+#include "host_tsdf_hash_raycast.hpp"
 #include "host_sdf.hpp"
 #include "host_vgicp.hpp"
 #include "host_hmap.hpp"

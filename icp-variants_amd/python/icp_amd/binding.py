@@ -419,7 +419,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_raycast_color", "icp_set_target_tsdf_color", "icp_track_depth_model_color", "icp_tsdf_mesh_color",
            "icp_sdf_options_default", "icp_sdf_options_check", "icp_tsdf_sample", "icp_tsdf_sdf_system", "icp_tsdf_align_depth", "icp_track_depth_sdf",
            "icp_tsdf_create_hashed", "icp_tsdf_reserve_blocks", "icp_tsdf_allocate_blocks", "icp_get_tsdf_hashed", "icp_tsdf_upload_hashed",
-           "icp_tsdf_mesh_hashed",
+           "icp_tsdf_mesh_hashed", "icp_tsdf_raycast_hashed", "icp_set_target_tsdf_hashed", "icp_track_depth_model_hashed",
            "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
            "icp_track_depth_sdf_color",
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
@@ -468,6 +468,13 @@ def _ptr(a):
 def pose_to_c(pose):
     """(4,4) numpy (row, col) -> 16 floats column-major == Eigen::Matrix4f::data()."""
     return np.ascontiguousarray(np.asarray(pose, dtype=np.float32).T).reshape(16).copy()
+
+
+def _pose_in(pose):
+    """A 4x4 pose as the 16 floats the library takes; anything else is a ValueError."""
+    if np.shape(pose) != (4, 4):
+        raise ValueError("the pose must be a 4x4 matrix")
+    return pose_to_c(pose)
 
 
 def pose_from_c(buf):
@@ -1134,6 +1141,41 @@ class Context:
             rc = self.lib.icp_track_depth_model_color(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
         else:
             rc = self.lib.icp_track_depth_model(self.h, _ptr(d), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
+        if rc not in (ICP_OK, ERR_NO_TARGET, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
+            self._ck(rc)
+        return pose_from_c(p), [_record(out[i]) for i in range(nf - 1)], rc
+
+    def tsdf_raycast_hashed(self, cam, pose):
+        """icp_tsdf_raycast_hashed: `tsdf_raycast` on the HASHED volume, read where the blocks lie: no dense box is
+        built and the volume stays as it is.  Returns (depth (h, w), vertices (w*h, 3), normals (w*h, 3), number of hits); holes are MINF.
+        The depth image is a valid input of `depth_mesh`."""
+        p = _pose_in(pose)
+        n = cam.width * cam.height
+        d = np.empty((cam.height, cam.width), np.float32); v = np.empty((n, 3), np.float32); nr = np.empty((n, 3), np.float32); hits = C.c_int32(0)
+        self._ck(self.lib.icp_tsdf_raycast_hashed(self.h, C.byref(cam), _ptr(p), _ptr(d), _ptr(v), _ptr(nr), C.byref(hits)))
+        return d, v, nr, hits.value
+
+    def set_target_tsdf_hashed(self, cam, pose, check=True):
+        """icp_set_target_tsdf_hashed: the ray-cast of the HASHED volume from `pose` as the target (organised, with normals).  Returns the
+        number of hits (and the status with check=False)."""
+        p = _pose_in(pose)
+        n = C.c_int32(0)
+        rc = self.lib.icp_set_target_tsdf_hashed(self.h, C.byref(cam), _ptr(p), C.byref(n))
+        if check:
+            self._ck(rc)
+        self.n_tgt = cam.width * cam.height if rc == ICP_OK else 0
+        return n.value if check else (n.value, rc)
+
+    def track_depth_model_hashed(self, depth_frames, cam, source_opt, gt=None, pose=None):
+        """icp_track_depth_model_hashed: `track_depth_model` against the context's HASHED volume: every frame aligned to a ray-cast of the
+        blocks and, when that succeeds, fused into them (blocks allocated as the frames come; the pool grows on the device).  Returns
+        (final pose, records, status)."""
+        d = _depth_in(depth_frames, cam, sequence=True)
+        nf = d.shape[0]
+        g = _gt_in(gt, nf)
+        p = _pose_in(np.eye(4) if pose is None else pose)
+        out = (IcpTrackFrame * max(nf - 1, 1))()
+        rc = self.lib.icp_track_depth_model_hashed(self.h, _ptr(d), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
         if rc not in (ICP_OK, ERR_NO_TARGET, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
             self._ck(rc)
         return pose_from_c(p), [_record(out[i]) for i in range(nf - 1)], rc

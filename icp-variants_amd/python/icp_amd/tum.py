@@ -101,11 +101,19 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     leaves it free; that needs color=True in `model`, else it is a ValueError.
     model=dict(hashed=True, origin=..., voxel_size=..., ...[, block_capacity=...]) together with `sdf` tracks against a HASHED volume
     (Context.tsdf_create_hashed): no dims, no extent, blocks allocated around the surface as the frames come, so the
-    trajectory need not be known beforehand.  hashed=True without `sdf`, with dims, or with color=True is a ValueError."""
+    trajectory need not be known beforehand.  model=dict(hashed=True, raycast=True, origin=..., ...) with sdf=None tracks frame-to-model on
+    the hashed volume instead (icp_track_depth_model_hashed): every frame against a ray-cast of the blocks, with the
+    params' matcher, the optimiser, convergence and reciprocal choices and `with_gt` as on the dense model path.  hashed=True without `sdf`
+    and without raycast=True, with dims, or with color=True is a ValueError; so is raycast=True together with `sdf` or without hashed=True."""
     hashed = bool(model is not None and model.get("hashed"))
+    raycast = bool(model is not None and model.get("raycast"))
+    if raycast and not hashed:
+        raise ValueError("raycast=True selects the ray-cast loop of a hashed model: pass hashed=True as well (a dense model is ray-cast as it is)")
+    if raycast and sdf is not None:
+        raise ValueError("raycast=True tracks against a ray-cast of the hashed model, sdf=dict(...) directly against it: pass one of them")
     if hashed:
-        if sdf is None:
-            raise ValueError("a hashed model is tracked directly (it has no ray-cast): pass sdf=dict(...) as well")
+        if sdf is None and not raycast:
+            raise ValueError("a hashed model is tracked directly (sdf=dict(...)) or against its ray-cast (raycast=True in model): pass one of them")
         if model.get("dims") is not None:
             raise ValueError("a hashed model has no extent: leave dims out")
         if model.get("color"):
@@ -124,8 +132,11 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     tgt_o, src_o = reconstruct_room_options(ctx.params) if options is None else options
     if hashed:
-        ctx.tsdf_create_hashed(**{k: v for k, v in model.items() if k not in ("hashed", "color", "dims")})
-        _, recs, rc = ctx.track_depth_sdf(seq["depth"], cam, **sdf)
+        ctx.tsdf_create_hashed(**{k: v for k, v in model.items() if k not in ("hashed", "raycast", "color", "dims")})
+        if raycast:
+            _, recs, rc = ctx.track_depth_model_hashed(seq["depth"], cam, src_o, gt=seq["gt"] if with_gt else None)
+        else:
+            _, recs, rc = ctx.track_depth_sdf(seq["depth"], cam, **sdf)
         poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
         return poses, recs, rc
     if model is not None:
@@ -157,7 +168,8 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
     (color=True in `model`); None writes nothing more.  A hashed model (hashed=True in `model`) is densified over the bounding box of its
     blocks first (`densify_hashed_model`), which raises when that box does not fit a dense volume; densify=False meshes it in place instead
     (Context.tsdf_mesh_hashed): nothing but the mesh crosses to the host, no box is built and the context keeps its hashed volume.
-    densify=False with a model that is not hashed is a ValueError.  sdf: as `track` (direct SDF tracking against the model).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    densify=False with a model that is not hashed is a ValueError.  sdf: as `track` (direct SDF tracking against the model); a hashed model
+    with raycast=True and no `sdf` is tracked against its ray-cast instead, as `track` says.  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
     if not densify and not (model is not None and model.get("hashed")):
         raise ValueError("densify=False meshes a hashed model in place: pass model=dict(hashed=True, ...)")
     poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model, sdf=sdf)

@@ -816,7 +816,8 @@ int icp_track_depth_sdf(icp_ctx* ctx, const float* depth_frames, const uint8_t* 
  *   with the same options, records and statuses.  On a hashed volume an integrate waits for the host twice (the touch's counters, the
  *   update count) and a tracked frame twice (its record, the touch's counters); the dense loop waits once per frame.
  * Refused on a hashed volume (ICP_ERR_INVALID_ARG, a message that names the hashed volume, no side effect): icp_tsdf_download,
- *   icp_tsdf_upload, icp_tsdf_raycast*, icp_set_target_tsdf*, icp_track_depth_model*, icp_tsdf_mesh (the hashed volume's own mesh call is icp_tsdf_mesh_hashed,
+ *   icp_tsdf_upload, icp_tsdf_raycast*, icp_set_target_tsdf*, icp_track_depth_model* (the hashed volume's own calls are icp_tsdf_raycast_hashed,
+ *   icp_set_target_tsdf_hashed and icp_track_depth_model_hashed, below), icp_tsdf_mesh (the hashed volume's own mesh call is icp_tsdf_mesh_hashed,
  *   below), icp_tsdf_color_create and every *_color call.  A finished model goes into a dense volume block by block (icp_get_tsdf_hashed,
  *   then icp_tsdf_upload). */
 typedef struct icp_tsdf_hashed_info {
@@ -871,6 +872,46 @@ int icp_tsdf_upload_hashed(icp_ctx* ctx, int32_t n, const int32_t* coords, const
 int icp_tsdf_mesh_hashed(icp_ctx* ctx, float min_weight, int32_t max_vertices, int32_t max_triangles,
                          float* vertices_out, float* normals_out, uint32_t* triangles_out,
                          int32_t* n_vertices_out, int32_t* n_triangles_out);
+
+/* -------- the hashed model seen from a pose, and tracked frame-to-model (an extension): icp_tsdf_raycast, icp_set_target_tsdf and
+ * icp_track_depth_model on the HASHED volume.  DESIGN.md section 6z.  tests/htsdf_raycast_restatement.py restates what follows, compared bit
+ * for bit. --------
+ * The ray-cast is icp_tsdf_raycast's, read through the hashed volume's addressing; nothing else changes.
+ * March: z_k = min_depth + (float)k ray_step while z_k <= max_depth, all from the volume's icp_tsdf_options (ray_step 0 is truncation / 2).
+ *   Every sample of the march is evaluated, in order; none is skipped.
+ * Per sample: the direction, the position q = P[12..14] + z d, the nested lerp (x, then y, then z), the end rule, zh and the analytic
+ *   gradient normal are icp_tsdf_raycast's, operation for operation in the same order.  The end rule: the ray ends at the first VALID
+ *   sample with F <= 0; the crossing is accepted only when the sample before it was valid with F > 0; a NaN never ends a ray; an
+ *   invalid sample clears prev_valid.
+ * Cell: g = (q - o) / s per axis, f = floor(g), fractions g - f; the corner (dx, dy, dz) is the voxel at SIGNED GLOBAL coordinate f + d,
+ *   in block (f + d) >> 3 at local index ((f + d) & 7).
+ * Validity: a sample is VALID iff -2^23 <= f <= 2^23 - 2 on every axis (tested in float, before any cast: a NaN or a coordinate out of
+ *   range is invalid) and all eight corners have W > 0.  A voxel of a block that does not exist reads (0, 0), so a cell that touches a
+ *   missing block is invalid.  There is no box and no cell range beyond storability.
+ * Outputs: icp_tsdf_raycast's -- depth (h, w), vertices and normals (w h, 3) in the camera's frame, -inf in all of them where the ray
+ *   misses, the number of hits; as a target (icp_set_target_tsdf_hashed) the SoA planes with +inf padding to the next multiple of 64.
+ * Determinism: the output is per pixel and reads the volume only through block coordinates: where a block sits in the pool does not
+ *   matter, and two volumes with the same blocks give identical arrays.
+ * Equivalence: on a volume whose blocks all have non-negative coordinates the result equals icp_tsdf_raycast's on the dense volume with the
+ *   same origin and voxel_size that holds the blocks from voxel (0, 0, 0) on and covers every one of them (voxels no block covers (0, 0)),
+ *   bit for bit, array for array.
+ * The volume is never modified (table, pool, counters, options).
+ * icp_tsdf_raycast_hashed: icp_tsdf_raycast's calling rules -- any output may be NULL; one host wait.
+ * icp_set_target_tsdf_hashed: icp_set_target_tsdf's -- the ray-cast straight into the target's planes, the target's index built, the hit
+ *   count alone downloaded; no hit: ICP_ERR_NO_TARGET and an empty target.
+ * icp_track_depth_model_hashed: icp_track_depth_model's loop, arguments, frame records, statuses, carried pose on a failed frame, upload
+ *   overlap and gt RMSE, with the target from the hashed ray-cast and the integrate icp_tsdf_integrate's on a hashed volume (the touch with
+ *   its growth and room rule; growth past 2^22 blocks ends the call with ICP_ERR_INVALID_ARG).  It keeps that loop's refusals: colour ICP,
+ *   colour weighting and the colored metric (the hashed volume holds no colours: there is no *_color form), GICP, and a projective camera
+ *   in the params that differs from the depth camera.  Host waits per tracked frame: icp_track_depth_model's (the hit count, the run's)
+ *   and the touch's counters, plus one per growth of the pool.
+ * All three: no volume, or a dense volume: ICP_ERR_INVALID_ARG with a message that names the call, nothing touched -- the dense volume's
+ *   calls are icp_tsdf_raycast, icp_set_target_tsdf and icp_track_depth_model, which keep refusing a hashed one. */
+int icp_tsdf_raycast_hashed(icp_ctx* ctx, const icp_depth_camera* cam, const float pose[16], float* depth_out, float* vertices_out,
+                            float* normals_out, int32_t* n_hits_out);
+int icp_set_target_tsdf_hashed(icp_ctx* ctx, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out);
+int icp_track_depth_model_hashed(icp_ctx* ctx, const float* depth_frames, int32_t n_frames, const icp_depth_camera* cam,
+                                 const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out);
 
 /* -------- direct SDF tracking with a photometric term (an extension): next to its geometric row a pixel adds an intensity row, read from
  * the colour array in the cell the distance is read in (Bylow, Olsson, Kahl, "Direct Camera Pose Tracking and Mapping With Signed Distance
