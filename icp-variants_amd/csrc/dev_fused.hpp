@@ -319,6 +319,7 @@ __device__ __forceinline__ void fused_matcher_body(const KnnParams& kp, const Bv
         for (int q = 0; q < 9; q++) Nm[q] = nc[q];
     }
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if constexpr (MERGED) { if (rp.st.t0 && blockIdx.x == 0 && tid == 0) *rp.st.t0 = wall_clock64(); }      // the launch's start (block 0 is a matcher block in a run's first launch only)
     const int lb = xcd_contiguous_block(mblock, mgrid);                              // partial slot = logical block -> fixed summation order
     const int wave_slot = fused_wave_slot(lb, w, mgrid);
     const int t = wave_slot * BVH_QPW + lane;
@@ -351,6 +352,7 @@ __device__ __forceinline__ void fused_matcher_body(const KnnParams& kp, const Bv
     }
     double* partials = pp.partials;
     fused_block_epilogue(kp, pp, o, bvh_lbq, tid, wave_slot, [=](int a, double v) { partials[(size_t)a * mgrid + lb] = v; });
+    if constexpr (MERGED) { if (rp.st.block_t1 && tid == 0) rp.st.block_t1[lb] = wall_clock64(); }         // this block's end (RingStamps, dev_solve.hpp)
 }
 template <int DIM, bool WIDE>
 __global__ __launch_bounds__(BVH_THREADS, DIM == 3 ? ICP_FUSED_WAVES : 4) void k_knn_bvh_post(const KnnParams kp, const BvhViewT<DIM> bv, const int* __restrict__ qorder, const PostParams pp) {

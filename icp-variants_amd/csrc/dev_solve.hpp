@@ -530,31 +530,53 @@ __device__ __host__ __forceinline__ PoseState* loop_slot(PoseState* base, int g,
 }
 // One launch in front of a run of the merged loop: slot 0 = the incoming pose in every replica, every other slot's granules
 // and the totals rows "empty", the fault word zero.  (Only the 128 bytes of a replica that are ever read are touched --
-// the replicas sit 4 KB apart.)
-__global__ void k_run_init(const PoseState* __restrict__ src, PoseState* slots, int n_slots, unsigned long long* totals, int n_totals, int* zero_words, int n_zero) {
+// the replicas sit 4 KB apart.)  The incoming pose state travels as an argument -- no copy in front of the run -- and also goes to
+// ps_copy, the context's pose state, which the merged loop itself never touches (nullptr: nowhere; n_slots == 0: src is not read).
+__global__ void k_run_init(const PoseState src, PoseState* ps_copy, PoseState* slots, int n_slots, unsigned long long* totals, int n_totals, int* zero_words, int n_zero,
+                           unsigned long long* stamps, int n_stamps) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int n_slot_granules = n_slots * POSE_REPLICAS * 16;
     if (t < n_slot_granules) {
         const int g = t / (POSE_REPLICAS * 16), r = (t / 16) % POSE_REPLICAS, q = t & 15;
         unsigned long long* dst = (unsigned long long*)loop_slot(slots, g, r) + q;
-        *dst = g == 0 ? ((const unsigned long long*)src)[q] : ~0ull;
+        *dst = g == 0 ? ((const unsigned long long*)&src)[q] : ~0ull;
+        if (g == 0 && r == 0 && ps_copy) ((unsigned long long*)ps_copy)[q] = ((const unsigned long long*)&src)[q];
     } else if (t < n_slot_granules + n_totals) totals[t - n_slot_granules] = ~0ull;
     else if (t < n_slot_granules + n_totals + n_zero) zero_words[t - n_slot_granules - n_totals] = 0;
+    else if (t < n_slot_granules + n_totals + n_zero + n_stamps) stamps[t - n_slot_granules - n_totals - n_zero] = 0ull;      // the run's time stamps (RingStamps below)
 }
 constexpr unsigned long long GRANULE_EMPTY = ~0ull;
 #ifndef ICP_RING_SLEEP
 #define ICP_RING_SLEEP 4           // s_sleep argument (x 64 clocks) between two polls of the pose slot by a matcher wave
 #endif
+// Stage times of a merged run, from the device's own clock: wall_clock64(), a free-running counter whose rate the runtime reports
+// (hipDeviceAttributeWallClockRate).  The launches of a run stamp it themselves -- one scalar clock read and one 8-byte store by one thread
+// of a block -- so timing puts nothing on the stream and breaks no back-to-back dispatch.  Launch j of a run (j = iterations: the closing
+// launch) gets the addresses that concern it; a null pointer = that stamp is not taken.
+//   t0        launch start: thread 0 of block 0 on entry (launch 0: matcher block 0; later launches: reducer block 0).
+//   block_t1  every matcher block's end, behind its partial stores: [matcher blocks], two buffers that alternate like the partials.
+//   prev_t1   the previous launch's end = the maximum of ITS block_t1 (prev_block_t1, red_nblocks of them), folded by reducer block 1
+//             once it has published its own total: off the fold -> totals -> solve -> publish chain of block 0.
+//   end       the closing launch's own end, behind everything it writes.
+// An iteration whose matcher blocks left early (a stopped run, a fault) stamps no block end: its prev_t1 is folded from the stamps of two
+// launches before.  The host never reports it (stamps_to_timing clips to the iterations that ran; a fault repeats the run).
+struct RingStamps {
+    unsigned long long* t0; unsigned long long* block_t1;
+    const unsigned long long* prev_block_t1; unsigned long long* prev_t1;
+    unsigned long long* end;
+};
 struct RingParams {
     const double* red_partials; int red_nblocks;   // partials of the iteration being reduced: [NSUM][red_nblocks]
     unsigned long long* totals_row;                // [NSUM] that iteration's row of the totals ring
     const PoseState* ps_in;                        // the pose that iteration searched at (replica 0 of its slot): complete since the previous launch
     PoseState* ps_out;                             // slot to publish, POSE_REPLICAS copies of it (loop_slot): the pose the matcher blocks of THIS launch wait for
     icp_iter_stats* stats; int n_src;              // record of the reduced iteration
-    PoseState* final_out;                          // the closing launch of a run: the final pose state also goes here (beside the records: ONE copy back); else nullptr
+    PoseState* final_out;                          // the closing launch of a run: the final pose state also goes here (the run's result block); else nullptr
+    int* words_out;                                // the closing launch of a run: the 16 control words at run_fault (fault word, convergence words) are copied here as its last act; else nullptr
     int* run_fault;                                // raised by any waiter that ran out of polls
     int n_red;                                     // reducer blocks in front of this grid: 0 (first launch of a run) or NSUM_USED
     ConvergeParams cv;                             // stopping on a converged pose (dev_converge.hpp), for the reduced iteration; cv.on == 0: off
+    RingStamps st;                                 // the run's time stamps; all null: none (icp_match_seeded's launches)
 };
 __device__ __forceinline__ unsigned long long granule_of(unsigned int lo, unsigned int hi) {
     const unsigned long long g = ((unsigned long long)hi << 32) | lo;
@@ -576,6 +598,20 @@ __device__ int g_ring_dbg[(NSUM_USED + 1) * 8];
 #else
 #define RING_STAMP(a, j)
 #endif
+// The last act of a run's closing launch, by thread 0 of block 0: the control words the device itself reads during the run (they stay in
+// device memory, on the chain) go to the host's result block, then the launch's end is stamped.  Every earlier launch has completed, and
+// within this block the words have one writer, this very thread (converge_step's lane 0, the give-up flag); the loads read behind the L1.
+__device__ __forceinline__ void ring_close(const RingParams& rp) {
+    if (threadIdx.x != 0) return;
+    if (rp.words_out) {
+        int wds[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) wds[k] = __hip_atomic_load(rp.run_fault + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int k = 0; k < 16; k++) rp.words_out[k] = wds[k];
+    }
+    if (rp.st.end) *rp.st.end = wall_clock64();
+}
 __device__ __forceinline__ void ring_reduce_solve(const RingParams& rp) {
     __shared__ double tot[NSUM];
     __shared__ double wsum[4];
@@ -583,9 +619,11 @@ __device__ __forceinline__ void ring_reduce_solve(const RingParams& rp) {
     __shared__ int give_up;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, a = blockIdx.x;
     RING_STAMP(a, 0);
+    if (a == 0 && tid == 0 && rp.st.t0) *rp.st.t0 = wall_clock64();
     if (a == 0 && rp.ps_in->fault) {                      // the chain was cut further up, or the run has stopped (SLOT_STOPPED: the slot is the final pose): pass it on, touch nothing else
         { const unsigned int* src = (const unsigned int*)rp.ps_in; for (int q = tid; q < 16 * POSE_REPLICAS; q += RING_THREADS) __hip_atomic_store((unsigned long long*)loop_slot(rp.ps_out, 0, q >> 4) + (q & 15), granule_of(src[2 * (q & 15)], src[2 * (q & 15) + 1]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (rp.final_out && tid < 32) ((unsigned int*)rp.final_out)[tid] = src[tid]; }
+        ring_close(rp);
         return;
     }
     {
@@ -618,6 +656,16 @@ __device__ __forceinline__ void ring_reduce_solve(const RingParams& rp) {
         __hip_atomic_store(rp.totals_row + a, granule_of((unsigned int)bits, (unsigned int)(bits >> 32)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     RING_STAMP(a, 2);
+    if (a == 1 && rp.st.prev_t1) {                        // the previous launch's end: the latest of its matcher blocks' (uniform: the whole block)
+        static_assert(RING_THREADS == 2 * WAVE, "two wave maxima meet below");
+        __shared__ unsigned long long tmax[RING_THREADS / WAVE];
+        unsigned long long m = 0ull;
+        for (int b = tid; b < rp.red_nblocks; b += RING_THREADS) { const unsigned long long v = rp.st.prev_block_t1[b]; m = v > m ? v : m; }
+        for (int off = 32; off > 0; off >>= 1) { const unsigned long long v = __shfl_down(m, off, WAVE); m = v > m ? v : m; }
+        if (lane == 0) tmax[w] = m;
+        __syncthreads();
+        if (tid == 0) *rp.st.prev_t1 = tmax[0] > tmax[1] ? tmax[0] : tmax[1];
+    }
     if (a != 0) return;
     if (tid == 0) give_up = 0;
     __syncthreads();
@@ -666,6 +714,7 @@ __device__ __forceinline__ void ring_reduce_solve(const RingParams& rp) {
         if (tid < 16) rp.stats->pose[tid] = __uint_as_float(slot_words[tid]);
         if (tid == 16) { rp.stats->n_src = rp.n_src; rp.stats->n_valid = (int)n; rp.stats->rmse = -1.f; rp.stats->benchmark_error = -1.f; rp.stats->status = status; }
     }
+    ring_close(rp);
 }
 // The reducer alone: closes a merged run (the last iteration has no matcher launch behind it to ride in).
 __global__ __launch_bounds__(RING_THREADS) void k_ring_reduce_solve(const RingParams rp) { ring_reduce_solve(rp); }

@@ -31,8 +31,8 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "a copied DevBuf would be freed twice");
-struct PinBuf {                          // page-locked host block (ensure_pin)
-    void* p = nullptr; size_t cap = 0;
+struct PinBuf {                          // page-locked host block (ensure_pin); dev: the address the device writes it at
+    void* p = nullptr; size_t cap = 0; void* dev = nullptr;
     PinBuf() = default; PinBuf(const PinBuf&) = delete; PinBuf& operator=(const PinBuf&) = delete;
     ~PinBuf() { if (p) (void)hipHostFree(p); }
     template <class T> T* as() const { return (T*)p; }
@@ -91,6 +91,7 @@ struct icp_ctx {
     hipStream_t stream = nullptr;        // own_stream, or the caller's (icp_ctx_create_on_stream), which is left alone
     int stage_timing = 1;                // icp_set_stage_timing: 0 none, 1 every iteration, N > 1 every Nth iteration (scaled)
     unsigned timing_phase = 0;           // rotates the sampled iterations from run to run
+    double wall_ticks_per_ms = 0;        // rate of the device's wall clock (hipDeviceAttributeWallClockRate, kHz), asked for by the first merged run
     PinBuf pinned;                       // page-locked host staging: pose upload, stats + pose download (truly asynchronous copies)
     bool trace = false;                  // ICP_HIP_TRACE=1: per-iteration stage times on stderr
     bool merge_loop = true;              // point-to-plane loop through the fused BVH matcher: reduce + solve ride in front of the next matcher launch (ICP_HIP_MERGE=0: separate k_reduce_solve launches)
@@ -141,6 +142,7 @@ struct icp_ctx {
     DevBuf qstate, qstate2;                              // incremental k-NN: per-query anchor + bound on the other targets; bound on the targets outside the neighbour's leaf
     DevBuf dbg_steps;                    // development builds only (ICP_DEBUG_STEPS)
     DevBuf ps, matches, d2, best64, nn_raw, partials, partials2, ring, totals, sums, stats, staging, rmse_partials, rmse_out, fontana_partials;
+    DevBuf block_t1;                     // merged loop: the matcher blocks' end stamps, two buffers that alternate like partials / partials2 (RingStamps, dev_solve.hpp)
     Cloud conv_src, conv_ref; int conv_n = 0;
     // depth frames (icp_set_*_depth, icp_track_depth_frames): two upload slots, each a page-locked staging block + a device copy of
     // [depth 4n | rgbx 4n]; the next frame of a sequence goes up on depth_stream while the current one iterates
@@ -184,10 +186,11 @@ int ensure(icp_ctx* c, DevBuf& b, size_t bytes) {
 // A page-locked block of at least `bytes`; one that has to grow becomes max(min_bytes, bytes + bytes / slack_div) (slack_div 0: no slack).
 int ensure_pin(icp_ctx* c, PinBuf& b, size_t bytes, size_t min_bytes, size_t slack_div) {
     if (bytes <= b.cap && b.p) return ICP_OK;
-    if (b.p) { HIPCK(c, hipHostFree(b.p)); b.p = nullptr; b.cap = 0; }
+    if (b.p) { HIPCK(c, hipHostFree(b.p)); b.p = nullptr; b.cap = 0; b.dev = nullptr; }
     const size_t want = bytes < min_bytes ? min_bytes : bytes + (slack_div ? bytes / slack_div : 0);
     HIPCK(c, hipHostMalloc(&b.p, want, hipHostMallocDefault));
     b.cap = want;
+    HIPCK(c, hipHostGetDevicePointer(&b.dev, b.p, 0));
     return ICP_OK;
 }
 int ensure_pinned(icp_ctx* c, size_t bytes) { return ensure_pin(c, c->pinned, bytes, 4096, 0); }
@@ -329,11 +332,14 @@ int finite_list(icp_ctx* c, const Cloud& cl, bool with_normals, DevBuf& flag, De
 // Upload the pose state.  Staged through the context's page-locked buffer: no synchronisation here -- every entry point
 // that uses the pose synchronises the stream before it returns, so the staging area is free again by the next call.
 // write_pose_via: the same through a page-locked PoseState h the caller owns (and keeps untouched until the stream has passed the copy).
-int write_pose_via(icp_ctx* c, PoseState* h, const float pose[16]) {
-    int rc;
+void make_pose_state(const float pose[16], PoseState* h) {      // the state of a pose nothing has iterated on yet: the pose, its normal matrix, the rest zero
     memset(h, 0, sizeof(*h));
     memcpy(h->pose, pose, 64);
     normal_matrix_from_pose(h->pose, h->nmat);
+}
+int write_pose_via(icp_ctx* c, PoseState* h, const float pose[16]) {
+    int rc;
+    make_pose_state(pose, h);
     if ((rc = ensure(c, c->ps, sizeof(PoseState)))) return rc;
     HIPCK(c, hipMemcpyAsync(c->ps.p, h, sizeof(*h), hipMemcpyHostToDevice, c->stream));
     return ICP_OK;

@@ -52,6 +52,27 @@ int icp_debug_wave_slot(int32_t lb, int32_t w, int32_t mgrid, int32_t* waves_per
     if (lb < 0 || lb >= mgrid || w < 0 || w >= BVH_THREADS / WAVE) return -1;
     return icpdev::fused_wave_slot(lb, w, mgrid);
 }
+//   icp_debug_stamp_times     : the host arithmetic that turns a merged run's device-clock stamps into icp_timing and the per-iteration
+//                               arrays (sample_iterations + stamps_to_timing, host_loop.hpp), on the caller's stamps: t0 / t1 hold
+//                               iters + 1 ticks each (entry iters: the closing launch), n_done iterations ran, the timing mode and the
+//                               context's run counter pick the reported iterations.  The three arrays receive n_done floats.  No GPU needed.
+int icp_debug_stamp_times(const uint64_t* t0, const uint64_t* t1, int32_t iters, int32_t n_done, int32_t mode, uint32_t phase, double ticks_per_ms,
+                          icp_timing* timing, float* match_ms, float* post_ms, float* solve_ms) {
+    if (!t0 || !t1 || !timing || iters < 1 || n_done < 1 || n_done > iters || mode < 0 || !(ticks_per_ms > 0)) return ICP_ERR_INVALID_ARG;
+    std::vector<char> sampled;
+    sample_iterations(mode, phase, iters, sampled);
+    stamps_to_timing((const unsigned long long*)t0, (const unsigned long long*)t1, iters, n_done, sampled.data(), ticks_per_ms, timing, match_ms, post_ms, solve_ms);
+    return ICP_OK;
+}
+//   icp_debug_wall_clock_khz  : the rate of the device's wall clock as the runtime reports it (hipDeviceAttributeWallClockRate), which is
+//                               what the merged loop's stamps are converted with: one tick is 1 / khz milliseconds.
+int icp_debug_wall_clock_khz(icp_ctx* c, int32_t* khz) {
+    if (!c || !khz) return ICP_ERR_INVALID_ARG;
+    int v = 0;
+    HIPCK(c, hipDeviceGetAttribute(&v, hipDeviceAttributeWallClockRate, c->device));
+    *khz = v;
+    return ICP_OK;
+}
 __global__ void k_debug_pos_of(const icpdev::TgtRec* recs, const int* pos_of, int n_slots, int* bad) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_slots && recs[i].idx >= 0 && pos_of[recs[i].idx] != i) atomicAdd(bad, 1);
@@ -161,10 +182,9 @@ int icp_debug_loop_sums(icp_ctx* c, const float pose[16], int32_t form, int32_t 
         for (int k : two) { r.pl.factors.push_back(pl.factors[k]); r.pl.ns.push_back(pl.ns[k]); r.pl.clouds.push_back(pl.clouds[k]); r.pl.sels.push_back(pl.sels[k]); r.pl.orders.push_back(pl.orders[k]); }
         r.lay_out(2, false, false);
         if ((rc = ensure_pinned(c, r.pin_bytes))) return rc;
-        if ((rc = write_pose(c, pose))) return rc;
+        make_pose_state(pose, &r.ps_in);
         if ((rc = ensure(c, c->stats, r.stats_bytes))) return rc;
-        if ((rc = ensure_events(c, 2 * 4 + 2))) return rc;
-        r.sampled.assign(2, 0); r.eligible.assign(2, 0); r.ev.assign(2, IterEvents());
+        r.sampled.assign(2, 0); r.eligible.assign(2, 0);
         if ((rc = enqueue_merged(c, r))) return rc;
         unsigned long long row[NSUM];      // row 0 of the totals ring: behind the 3 pose slots (make_ring)
         HIPCK(c, hipMemcpyAsync(row, c->ring.as<char>() + (size_t)3 * POSE_REPLICAS * POSE_REPLICA_STRIDE, NSUM * 8, hipMemcpyDeviceToHost, c->stream));

@@ -3,7 +3,7 @@
 // the two convergence measures.  Part of icp_hip.hip (included from there, after host_index.hpp).
 namespace {
 // One launch of the merged loop: the pose slot its matcher blocks wait for, where they leave their partials, and the reducer that rides in front.
-struct MergeLaunch { RingParams rp; const PoseState* slot; double* partials; hipEvent_t ev_start = nullptr, ev_stop = nullptr; };   // ev_start / ev_stop: the launch's own start / stop times go into these events (hipExtLaunchKernel: taken from the dispatch itself, no bracket on the stream)
+struct MergeLaunch { RingParams rp; const PoseState* slot; double* partials; };   // (the launch's time stamps travel in rp.st: nothing on the stream brackets it)
 
 // Launch shapes written once.  LDS of the stand-alone BVH matcher: the shared walk's records.  LDS of the fused matcher: the same, reused
 // by the (smaller) block reduction of the post stage once the traversal stacks are dead, + the board of the cross-wave hand-over.
@@ -72,8 +72,7 @@ int launch_bvh_query(icp_ctx* c, Bvh& b, const CoordPtrs<DIM>& cp, const KnnPara
         if (ml) {                                                                  // merged loop: reducer blocks in front, pose through the ring
             kf.ps = ml->slot; pp.ps = ml->slot; pp.partials = ml->partials; kf.fault = ml->rp.run_fault;
             const auto ring = pick_wide(b.Lq, k_knn_bvh_post_ring<DIM, false>, k_knn_bvh_post_ring<DIM, true>);
-            if (ml->ev_start) hipExtLaunchKernelGGL(ring, dim3(nb + ml->rp.n_red), dim3(BVH_THREADS), (uint32_t)lds, c->stream, ml->ev_start, ml->ev_stop, 0, kf, bv, order, pp, ml->rp);
-            else hipLaunchKernelGGL(ring, dim3(nb + ml->rp.n_red), dim3(BVH_THREADS), lds, c->stream, kf, bv, order, pp, ml->rp);
+            hipLaunchKernelGGL(ring, dim3(nb + ml->rp.n_red), dim3(BVH_THREADS), lds, c->stream, kf, bv, order, pp, ml->rp);
         }
         else hipLaunchKernelGGL(pick_wide(b.Lq, k_knn_bvh_post<DIM, false>, k_knn_bvh_post<DIM, true>), dim3(nb), dim3(BVH_THREADS), lds, c->stream, kf, bv, order, pp);
         *fused_blocks = nb;

@@ -257,35 +257,80 @@ struct RunTail {
     PoseState final_pose;                 // the pose state after the last iteration (merged form: written by its closing launch)
     int merged_fault, spare[3];           // the merged form's fault word; k_run_init clears it and the 15 words behind it
     int merged_cvg[12];                   // of which these serve as the merged form's convergence control words (CONV_*, dev_converge.hpp)
-    char unused[64];                      // (a run that cannot stop on a converged pose keeps and copies the tail up to here)
+    char unused[64];
     int cvg_state[CONV_STATE_BYTES / 4];  // the separate form's convergence state block: control words | search pose | final pose state
     icp_convergence_step* trace() { return (icp_convergence_step*)(this + 1); }      // one step per iteration, behind the tail
-    // the bytes in use: with stopping on a converged pose (cvg, dev_converge.hpp) the whole tail and n_trace steps of the trace
-    static constexpr size_t used_bytes(bool cvg, int n_trace) { return cvg ? sizeof(RunTail) + (size_t)n_trace * sizeof(icp_convergence_step) : offsetof(RunTail, unused); }
+    // the bytes in use with stopping on a converged pose (dev_converge.hpp): the whole tail and n_trace steps of the trace
+    static constexpr size_t used_bytes(int n_trace) { return sizeof(RunTail) + (size_t)n_trace * sizeof(icp_convergence_step); }
 };
 static_assert(offsetof(RunTail, merged_fault) == 128 && offsetof(RunTail, merged_cvg) == 144 && offsetof(RunTail, unused) == 192 && offsetof(RunTail, cvg_state) == 256 && sizeof(RunTail) == 512, "the layout the device was handed");
 
+// The merged form's time stamps (RingStamps, dev_solve.hpp) as the host sees them: t0[j] / t1[j] = start / end of launch j, j = 0 ..
+// iters, launch `iters` being the closing one; ticks of the device's wall clock.
+struct RunStamps {
+    static size_t bytes(int iters) { return (size_t)2 * (iters + 1) * 8; }
+    static unsigned long long* t0(void* base) { return (unsigned long long*)base; }
+    static unsigned long long* t1(void* base, int iters) { return (unsigned long long*)base + (iters + 1); }
+};
+// Which iterations of a run of `iters` report their stage times: mode 0 none, 1 all, N > 1 every Nth, the offset rotating with `phase`
+// (the context's run counter).
+void sample_iterations(int mode, unsigned phase, int iters, std::vector<char>& sampled) {
+    sampled.assign((size_t)iters, 0);
+    for (int i = 0; i < iters; i++) sampled[(size_t)i] = mode == 1 || (mode > 1 && (i + (int)(phase % (unsigned)mode)) % mode == 0);
+}
+// The stamps of a merged run -> icp_timing and the per-iteration arrays (n_done entries each; any may be nullptr).  Pure host arithmetic:
+// ticks become milliseconds at ticks_per_ms, the rate the runtime reports for the device.  An iteration IS one launch: match = its span,
+// no post stage of its own (0), and a "solve" only behind the run's last iteration: the closing launch's span.  Only sampled iterations
+// below n_done are reported (the others stay -1; a run that stopped early has real stamps up to n_done only); the sums are scaled by
+// n_done / sampled.  total = the closing launch's end - the first launch's start, whatever the mode.
+void stamps_to_timing(const unsigned long long* t0, const unsigned long long* t1, int iters, int n_done, const char* sampled, double ticks_per_ms,
+                      icp_timing* t, float* match_ms, float* post_ms, float* solve_ms) {
+    auto ms = [&](unsigned long long from, unsigned long long to) { return (double)(long long)(to - from) / ticks_per_ms; };
+    memset(t, 0, sizeof(*t)); t->iterations = n_done;
+    double sum_match = 0, sum_solve = 0; int n_ev = 0;
+    for (int i = 0; i < n_done; i++) {
+        float a = -1.f, b = -1.f, d = -1.f;
+        if (sampled[i]) {
+            n_ev++;
+            a = (float)ms(t0[i], t1[i]); b = 0.f; d = i == iters - 1 ? (float)ms(t0[iters], t1[iters]) : 0.f;
+            sum_match += a; sum_solve += d;
+        }
+        if (match_ms) match_ms[i] = a;
+        if (post_ms) post_ms[i] = b;
+        if (solve_ms) solve_ms[i] = d;
+    }
+    if (n_ev > 0) { const double f = (double)n_done / n_ev; t->match_ms = sum_match * f; t->solve_ms = sum_solve * f; }
+    t->sampled_iterations = n_ev;
+    t->total_ms = ms(t0[0], t1[iters]);
+}
+
 // What run_loop's prologue hands the form that enqueues the run.  lay_out places the run in the page-locked staging -- [pose state up |
-// records down | tail down | LM records down, non-linear runs only], every part on a 256-byte boundary -- and sizes c->stats (records |
-// tail); the accessors are the host's and the device's views of the parts.  Stage timing (TimeMeasure.h:20-26): a HIP event
-// costs ~4 us of stream time, so mode N > 1 brackets only every Nth iteration (`sampled`, offset rotating from run to run) and scales the
-// sums.  Event slots: 4 per iteration + run start / run end; each form fills ev[i] of a sampled iteration with the ones it records.
+// records down | tail down | trace down, runs that may stop | stamps down | LM records down, non-linear runs only], every part on a
+// 256-byte boundary -- and sizes c->stats (records | tail | trace at the same distances: what the separate form copies back, and in
+// either form the control words the device itself reads during the run); the accessors are the host's and the device's views of the parts.  Stage timing (TimeMeasure.h:20-26): mode N > 1 reports only every Nth iteration (`sampled`,
+// offset rotating from run to run) and scales the sums.  The merged form takes its times from the device's clock (RunStamps): nothing on
+// the stream, no cost to the run.  The separate form brackets with HIP events, each ~4 us of stream time: event slots 4 per iteration +
+// run start / run end, and the form fills ev[i] of a sampled iteration with the ones it records.
 // eligible[i] = the host's half of iteration i's eligibility to stop the run (cvg), from the plan's factors.
 struct IterEvents { hipEvent_t start = nullptr, matched = nullptr, posted = nullptr, end = nullptr; };   // posted / end: nullptr = the form has no such stage to bracket
 struct LoopRun {
     RunPlan pl; bool lm, robust, recip, rmse, fontana, cvg; std::vector<char> sampled, eligible; std::vector<IterEvents> ev; int n_enqueued = 0;
-    size_t pin_stats = 256, pin_tail, pin_lm, pin_bytes, stats_bytes;      // offsets into the staging and its size; the size of c->stats
+    bool stamp_blocks = false;           // merged form: the matcher blocks stamp their ends (any timing mode but 0)
+    PoseState ps_in;                     // merged form: the incoming pose state, an argument of its first launch
+    size_t pin_stats = 256, pin_tail, pin_stamps, pin_lm, pin_bytes, stats_bytes;      // offsets into the staging and its size; the size of c->stats
     void lay_out(int iters, bool with_lm, bool with_cvg) {
         auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
         const size_t trace_pad = with_cvg ? pad((size_t)iters * sizeof(icp_convergence_step)) : 0;
-        pin_tail = pin_stats + pad((size_t)iters * sizeof(icp_iter_stats)); pin_lm = pin_tail + sizeof(RunTail) + trace_pad;
+        pin_tail = pin_stats + pad((size_t)iters * sizeof(icp_iter_stats)); pin_stamps = pin_tail + sizeof(RunTail) + trace_pad;
+        pin_lm = pin_stamps + pad(RunStamps::bytes(iters));
         pin_bytes = pin_lm + (with_lm ? (size_t)iters * sizeof(icp_lm_summary) : 0);
-        stats_bytes = records_bytes() + (with_cvg ? sizeof(RunTail) + trace_pad : RunTail::used_bytes(false, 0));
+        stats_bytes = pin_stamps - pin_stats;
     }
     size_t records_bytes() const { return pin_tail - pin_stats; }      // the records of every iteration, padded
     RunTail* dev_tail(const icp_ctx* c) const { return (RunTail*)(c->stats.as<char>() + records_bytes()); }
     icp_iter_stats* host_records(const icp_ctx* c) const { return (icp_iter_stats*)(c->pinned.as<char>() + pin_stats); }
     RunTail* host_tail(const icp_ctx* c) const { return (RunTail*)(c->pinned.as<char>() + pin_tail); }
+    unsigned long long* host_stamps(const icp_ctx* c) const { return (unsigned long long*)(c->pinned.as<char>() + pin_stamps); }
     icp_lm_summary* host_lm(const icp_ctx* c) const { return (icp_lm_summary*)(c->pinned.as<char>() + pin_lm); }
 };
 // The separate form enqueues a run that may stop in chunks of this many iterations and reads the stop word between them: the chunk size
@@ -295,23 +340,28 @@ struct LoopRun {
 #define ICP_CONVERGE_CHUNK 2
 #endif
 constexpr int CONVERGE_CHUNK = ICP_CONVERGE_CHUNK;
-ConvergeParams converge_params(const icp_ctx* c, const LoopRun& r, int i, int* words) {
+ConvergeParams converge_params(const icp_ctx* c, const LoopRun& r, int i, int* words, icp_convergence_step* trace) {
     ConvergeParams cp; memset(&cp, 0, sizeof(cp));
     if (!r.cvg) return cp;
     const icp_convergence_options& o = c->cvg_opt;
     cp.on = 1; cp.eligible = r.eligible[(size_t)i]; cp.index = i; cp.min_iterations = o.min_iterations; cp.patience = o.patience;
     cp.rotation_eps = o.rotation_eps; cp.translation_eps = o.translation_eps;
-    cp.trace = r.dev_tail(c)->trace(); cp.words = words;
+    cp.trace = trace; cp.words = words;
     return cp;
 }
-hipEvent_t loop_event(const icp_ctx* c, int i, int k) { return c->events[(size_t)2 + 4 * i + k]; }
+hipEvent_t loop_event(const icp_ctx* c, int i, int k) { return c->events[(size_t)2 + 4 * i + k]; }      // the separate form's
 
 // The merged form: point-to-plane through the fused BVH matcher on sorted levels, nothing else on the stream between two iterations.
 // Launch i = [reducer of iteration i - 1 | matcher of iteration i]; one reducer-only launch closes the run.  A run that stops on a converged
 // pose (dev_converge.hpp) is still enqueued whole: the launches behind the stop find a stopped slot and drain at launch cost.  Pose slots and totals rows
-// are written once per run; both rings are reset here, so nothing survives an aborted run.  Back comes ONE block: records | final pose
-// state | fault word.  Events: an iteration is ONE launch, whose own start / stop times go into slots 0 / 1 (hipExtLaunchKernel: taken
-// from the dispatch itself, no bracket on the stream); a "solve" exists only for the last iteration: the closing launch, up to slot 3.
+// are written once per run; both rings are reset here, so nothing survives an aborted run.
+// Nothing but launches goes on the stream.  In: the incoming pose state (r.ps_in) is an argument of k_run_init, which also leaves it in
+// c->ps.  Out: the result block -- records | final pose state | fault and convergence words | trace | stamps -- is written by the
+// launches straight into the page-locked staging, which the device addresses (c->pinned.dev): what only the host reads (records, trace
+// steps, final pose state, stamps) by the launch that produces it; the control words the device itself reads stay in c->stats, and the
+// closing launch copies them over as its last act.  The host reads the block behind run_loop's hipStreamSynchronize.
+// Stage times: the launches stamp the device's clock themselves (RingStamps, dev_solve.hpp) -- no event, no bracket on the stream; the
+// launch starts and the run's end in every mode (total_ms), the matcher blocks' ends in every mode but 0.
 int enqueue_merged(icp_ctx* c, LoopRun& r) {
     const icp_params& p = c->prm; const RunPlan& pl = r.pl;
     const int iters = pl.iters(); RunTail* tail = r.dev_tail(c);
@@ -319,29 +369,34 @@ int enqueue_merged(icp_ctx* c, LoopRun& r) {
     for (int i = 0; i < iters; i++) { const int nb = fused_nblocks(pl.ns[i]); if (nb > nbmax) nbmax = nb; }
     Ring ring;
     if ((rc = make_ring(c, iters + 1, iters, nbmax, &tail->merged_fault, ring))) return rc;
-    const int n_init = (iters + 1) * POSE_REPLICAS * 16 + iters * NSUM + 16;
-    hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, c->ps.as<PoseState>(), ring.slots, iters + 1, ring.trows, iters * NSUM, ring.run_fault, 16);
+    if (r.stamp_blocks && (rc = ensure(c, c->block_t1, (size_t)2 * nbmax * 8))) return rc;
+    if ((rc = ensure(c, c->ps, sizeof(PoseState)))) return rc;
+    char* out = (char*)c->pinned.dev;                    // the result block as the device addresses it: the offsets of lay_out
+    icp_iter_stats* out_records = (icp_iter_stats*)(out + r.pin_stats); RunTail* out_tail = (RunTail*)(out + r.pin_tail);
+    unsigned long long* stamps = (unsigned long long*)(out + r.pin_stamps);
+    unsigned long long* t0 = RunStamps::t0(stamps); unsigned long long* t1 = RunStamps::t1(stamps, iters);
+    auto block_t1 = [&](int j) { return r.stamp_blocks ? c->block_t1.as<unsigned long long>() + (size_t)(j & 1) * nbmax : nullptr; };
+    const int n_stamps = 2 * (iters + 1), n_init = (iters + 1) * POSE_REPLICAS * 16 + iters * NSUM + 16 + n_stamps;
+    hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, r.ps_in, c->ps.as<PoseState>(), ring.slots, iters + 1, ring.trows, iters * NSUM, ring.run_fault, 16, stamps, n_stamps);
     auto reducer = [&](int i) {                          // of iteration i - 1, riding in launch i (i = iters: the closing launch)
         RingParams rp = ring_params(c, ring, i, i > 0 ? pl.ns[i - 1] : 0, loop_slot(ring.slots, i, 0));
-        if (i > 0) { rp.stats = c->stats.as<icp_iter_stats>() + (i - 1); rp.cv = converge_params(c, r, i - 1, tail->merged_cvg); }
-        if (i == iters) rp.final_out = &tail->final_pose;
+        if (i > 0) { rp.stats = out_records + (i - 1); rp.cv = converge_params(c, r, i - 1, tail->merged_cvg, out_tail->trace()); }
+        rp.st.t0 = t0 + i;
+        if (i < iters) rp.st.block_t1 = block_t1(i);
+        if (i > 0 && r.stamp_blocks) { rp.st.prev_block_t1 = block_t1(i - 1); rp.st.prev_t1 = t1 + (i - 1); }
+        if (i == iters) { rp.final_out = &out_tail->final_pose; rp.words_out = &out_tail->merged_fault; rp.st.end = t1 + iters; }
         return rp;
     };
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
     for (int i = 0; i < iters; i++) {
         QuerySet q{pl.clouds[i], pl.sels[i], pl.ns[i], 0, p.color_icp != 0 && p.matching == ICP_MATCH_KNN, pl.seeded(i), pl.orders[i]};
         MergeLaunch ml; ml.rp = reducer(i); ml.slot = loop_slot(ring.slots, i, 0); ml.partials = ring_partials(c, i);
-        if (r.sampled[i]) { r.ev[i].start = ml.ev_start = loop_event(c, i, 0); r.ev[i].matched = ml.ev_stop = loop_event(c, i, 1); }
         int fused = 0;
         if ((rc = launch_match(c, q, &fused, &ml))) return rc;
         if (!fused) { c->err = "merged loop: the matcher did not take the fused path"; return ICP_ERR_HIP; }
     }
     hipLaunchKernelGGL(k_ring_reduce_solve, dim3(NSUM_USED), dim3(RING_THREADS), 0, c->stream, reducer(iters));      // nothing behind the last iteration to ride in
     HIPCK(c, hipGetLastError());
-    if (r.sampled[iters - 1]) { r.ev[iters - 1].end = loop_event(c, iters - 1, 3); HIPCK(c, hipEventRecord(r.ev[iters - 1].end, c->stream)); }
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
     r.n_enqueued = iters;
-    HIPCK(c, hipMemcpyAsync(r.host_records(c), c->stats.p, r.records_bytes() + RunTail::used_bytes(r.cvg, iters), hipMemcpyDeviceToHost, c->stream));
     return ICP_OK;
 }
 
@@ -392,7 +447,7 @@ int enqueue_separate(icp_ctx* c, LoopRun& r) {
         if (r.rmse && (rc = enqueue_rmse(c, &d_st->rmse))) return rc;
         if (r.fontana && (rc = enqueue_fontana(c, &d_st->benchmark_error))) return rc;
         if (r.cvg) {
-            hipLaunchKernelGGL(k_converge_step, dim3(1), dim3(64), 0, c->stream, converge_params(c, r, i, tail->cvg_state), c->ps.as<PoseState>(), pl.ns[i] > 0 ? d_st : nullptr);
+            hipLaunchKernelGGL(k_converge_step, dim3(1), dim3(64), 0, c->stream, converge_params(c, r, i, tail->cvg_state, tail->trace()), c->ps.as<PoseState>(), pl.ns[i] > 0 ? d_st : nullptr);
             HIPCK(c, hipGetLastError());
         }
         if (ev) HIPCK(c, hipEventRecord(r.ev[i].end, c->stream));
@@ -401,7 +456,7 @@ int enqueue_separate(icp_ctx* c, LoopRun& r) {
     HIPCK(c, hipEventRecord(c->events[1], c->stream));
     HIPCK(c, hipMemcpyAsync(r.host_records(c), c->stats.p, (size_t)n_enq * sizeof(icp_iter_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(&htail->final_pose, c->ps.p, sizeof(PoseState), hipMemcpyDeviceToHost, c->stream));
-    if (r.cvg) HIPCK(c, hipMemcpyAsync(htail->cvg_state, tail->cvg_state, RunTail::used_bytes(true, n_enq) - offsetof(RunTail, cvg_state), hipMemcpyDeviceToHost, c->stream));      // the state block and the trace behind it
+    if (r.cvg) HIPCK(c, hipMemcpyAsync(htail->cvg_state, tail->cvg_state, RunTail::used_bytes(n_enq) - offsetof(RunTail, cvg_state), hipMemcpyDeviceToHost, c->stream));      // the state block and the trace behind it
     if (r.lm) HIPCK(c, hipMemcpyAsync(r.host_lm(c), c->lm_sums.p, (size_t)n_enq * sizeof(icp_lm_summary), hipMemcpyDeviceToHost, c->stream));
     return ICP_OK;
 }
@@ -435,19 +490,21 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     if ((rc = ensure_pinned(c, r.pin_bytes))) return rc;
     if (lm && (rc = ensure(c, c->lm_sums, (size_t)iters * sizeof(icp_lm_summary)))) return rc;
     float pose_in[16]; memcpy(pose_in, pose_inout, 64);        // the record of an empty iteration 0 carries the incoming pose
-    if ((rc = write_pose(c, pose_inout))) return rc;
     if ((rc = ensure(c, c->stats, r.stats_bytes))) return rc;
     r.eligible.assign((size_t)iters, 0);
     for (int i = 0; i < iters; i++) r.eligible[(size_t)i] = pl.factors[i] == pl.factors[iters - 1] && (i == 0 || pl.factors[i] == pl.factors[i - 1]);
-    if ((rc = ensure_events(c, (size_t)iters * 4 + 2))) return rc;
     const bool rmse = r.rmse = (p.record_rmse & 1) && c->conv_n > 0;
     const bool fontana = r.fontana = (p.record_rmse & 2) && c->conv_n > 0;
     bool merged = try_merged && !lm && !robust && !recip && !single && iters >= 2 && pl.sorted_levels && p.metric == ICP_METRIC_POINT_TO_PLANE && !rmse && !fontana;
     for (int i = 0; merged && i < iters; i++) if (pl.ns[i] <= 0) merged = false;
-    const int tmode = c->stage_timing;
-    r.sampled.assign((size_t)iters, 0); r.ev.assign((size_t)iters, IterEvents());
-    for (int i = 0; i < iters; i++) r.sampled[i] = tmode == 1 || (tmode > 1 && (i + (int)(c->timing_phase % (unsigned)tmode)) % tmode == 0);
-    c->timing_phase++;
+    sample_iterations(c->stage_timing, c->timing_phase++, iters, r.sampled);
+    r.stamp_blocks = c->stage_timing != 0;
+    if (merged) make_pose_state(pose_inout, &r.ps_in);    // (travels with the first launch)
+    else if ((rc = write_pose(c, pose_inout))) return rc;
+    if (merged) {
+        if (c->wall_ticks_per_ms <= 0) { int khz = 0; HIPCK(c, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device)); c->wall_ticks_per_ms = khz; }
+        if (c->wall_ticks_per_ms <= 0) { c->err = "the runtime reports no wall clock rate for the device"; return ICP_ERR_HIP; }
+    } else { r.ev.assign((size_t)iters, IterEvents()); if ((rc = ensure_events(c, (size_t)iters * 4 + 2))) return rc; }
     if ((rc = merged ? enqueue_merged(c, r) : enqueue_separate(c, r))) return rc;
     std::vector<icp_robust_stats> rob((size_t)(robust ? iters : 0));
     if (robust) HIPCK(c, hipMemcpyAsync(rob.data(), c->rob_stats.p, (size_t)iters * sizeof(icp_robust_stats), hipMemcpyDeviceToHost, c->stream));
@@ -501,25 +558,32 @@ int run_loop(icp_ctx* c, float pose_inout[16], icp_iter_stats* stats, int32_t ma
     }
     icp_timing& t = c->timing; memset(&t, 0, sizeof(t)); t.iterations = n_done;
     c->it_match_ms.assign((size_t)n_done, -1.f); c->it_post_ms.assign((size_t)n_done, -1.f); c->it_solve_ms.assign((size_t)n_done, -1.f);
-    double ev_match = 0, ev_post = 0, ev_solve = 0; int n_ev = 0;
-    for (int i = 0; i < n_done; i++) {
-        if (!r.sampled[i]) continue;
-        n_ev++;
-        const IterEvents& e = r.ev[i];
-        float a = 0, b = 0, d = 0;
-        HIPCK(c, hipEventElapsedTime(&a, e.start, e.matched));
-        if (e.posted) HIPCK(c, hipEventElapsedTime(&b, e.matched, e.posted));
-        if (e.end) HIPCK(c, hipEventElapsedTime(&d, e.posted ? e.posted : e.matched, e.end));
-        ev_match += a; ev_post += b; ev_solve += d;
-        c->it_match_ms[(size_t)i] = a; c->it_post_ms[(size_t)i] = b; c->it_solve_ms[(size_t)i] = d;
-        if (c->trace) fprintf(stderr, "[icp_hip] it %2d  n %d  match %.4f  post %.4f  solve %.4f ms\n", i, pl.ns[i], a, b, d);
+    if (merged) {                                         // the device's clock: the stamps lie in the result block
+        unsigned long long* hst = r.host_stamps(c);
+        stamps_to_timing(RunStamps::t0(hst), RunStamps::t1(hst, iters), iters, n_done, r.sampled.data(), c->wall_ticks_per_ms, &t, c->it_match_ms.data(), c->it_post_ms.data(), c->it_solve_ms.data());
+        for (int i = 0; c->trace && i < n_done; i++)
+            if (r.sampled[i]) fprintf(stderr, "[icp_hip] it %2d  n %d  match %.4f  post %.4f  solve %.4f ms\n", i, pl.ns[i], c->it_match_ms[(size_t)i], c->it_post_ms[(size_t)i], c->it_solve_ms[(size_t)i]);
+    } else {
+        double ev_match = 0, ev_post = 0, ev_solve = 0; int n_ev = 0;
+        for (int i = 0; i < n_done; i++) {
+            if (!r.sampled[i]) continue;
+            n_ev++;
+            const IterEvents& e = r.ev[i];
+            float a = 0, b = 0, d = 0;
+            HIPCK(c, hipEventElapsedTime(&a, e.start, e.matched));
+            if (e.posted) HIPCK(c, hipEventElapsedTime(&b, e.matched, e.posted));
+            if (e.end) HIPCK(c, hipEventElapsedTime(&d, e.posted ? e.posted : e.matched, e.end));
+            ev_match += a; ev_post += b; ev_solve += d;
+            c->it_match_ms[(size_t)i] = a; c->it_post_ms[(size_t)i] = b; c->it_solve_ms[(size_t)i] = d;
+            if (c->trace) fprintf(stderr, "[icp_hip] it %2d  n %d  match %.4f  post %.4f  solve %.4f ms\n", i, pl.ns[i], a, b, d);
+        }
+        if (n_ev > 0) {                                   // sampled: scale to all the iterations
+            const double f = (double)n_done / n_ev;
+            t.match_ms += ev_match * f; t.weight_reject_build_ms += ev_post * f; t.solve_ms += ev_solve * f;
+        }
+        t.sampled_iterations = n_ev;
+        float tot = 0; HIPCK(c, hipEventElapsedTime(&tot, c->events[0], c->events[1])); t.total_ms = tot;
     }
-    if (n_ev > 0) {                                       // sampled: scale to all the iterations
-        const double f = (double)n_done / n_ev;
-        t.match_ms += ev_match * f; t.weight_reject_build_ms += ev_post * f; t.solve_ms += ev_solve * f;
-    }
-    t.sampled_iterations = n_ev;
-    float tot = 0; HIPCK(c, hipEventElapsedTime(&tot, c->events[0], c->events[1])); t.total_ms = tot;
     if (status != ICP_OK) c->err = "no valid correspondences in at least one iteration (reference would hang in ASSERT)";
     guard.ok = true;                                     // synchronised above; `status` reports empty iterations, not a HIP failure
     return status;
@@ -676,7 +740,7 @@ int icp_match_seeded(icp_ctx* c, const float* poses, int32_t n_poses, icp_match_
         }
         HIPCK(c, hipMemcpyAsync(rg.slots, slot_image.data(), rg.slot_bytes, hipMemcpyHostToDevice, c->stream));
         const int n_init = n_rows * NSUM + 16;               // the totals rows empty, the fault word zero (k_run_init without its pose slots)
-        hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, nullptr, rg.slots, 0, rg.trows, n_rows * NSUM, rg.run_fault, 16);
+        hipLaunchKernelGGL(k_run_init, dim3((n_init + 255) / 256), dim3(256), 0, c->stream, PoseState{}, nullptr, rg.slots, 0, rg.trows, n_rows * NSUM, rg.run_fault, 16, nullptr, 0);      // (no pose slots: the argument is not read)
         HIPCK(c, hipGetLastError());
     }
     for (int j = 0; j < n_poses; j++) {

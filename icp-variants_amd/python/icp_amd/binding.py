@@ -868,7 +868,8 @@ class Context:
         return a[:k].copy(), b[:k].copy(), d[:k].copy()
 
     def set_stage_timing(self, every_nth):
-        """0: whole-run time only; 1: HIP events around every iteration's stages (default); N > 1: every Nth iteration, scaled."""
+        """0: whole-run time only; 1: the stage times of every iteration (default); N > 1: every Nth iteration, scaled.  The merged loop
+        reads the device's clock inside its launches (no cost to the run); the other forms bracket their stages with HIP events."""
         self._ck(self.lib.icp_set_stage_timing(self.h, C.c_int32(int(every_nth))))
 
     def set_convergence_reference(self, src_xyz, ref_xyz):

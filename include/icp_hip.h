@@ -88,15 +88,18 @@ typedef struct icp_iter_stats {
     int32_t status;          /* ICP_OK or ICP_ERR_NO_CORRESPONDENCES for this iteration */
 } icp_iter_stats;
 
-/* Stage times of the last icp_run, device milliseconds from HIP events: the TimeMeasure breakdown
- * (TimeMeasure.h:20-26).  Weighting, rejection and system build are one fused kernel here. */
+/* Stage times of the last icp_run, device milliseconds: the TimeMeasure breakdown (TimeMeasure.h:20-26).  Weighting, rejection
+ * and system build are one fused kernel here.  A run in the merged form (k-NN on the LBVH backend, point-to-plane: one launch per
+ * iteration) takes them from the device's own clock, stamped by the launches themselves: an iteration is its launch's span from the
+ * first block's entry to the last block's exit, solve_ms the run's closing launch, total_ms from the first launch's start to the
+ * closing launch's end.  Every other run brackets its stages with HIP events on the stream. */
 typedef struct icp_timing {
     double match_ms;         /* matchingTime                                   */
     double weight_reject_build_ms;   /* weighingTime + rejectionTime + system build */
     double solve_ms;         /* reduction + linear solve + pose composition    */
     double total_ms;         /* convergenceTime                                 */
     int32_t iterations;
-    int32_t sampled_iterations;   /* iterations that were bracketed by events (== iterations unless icp_set_stage_timing(N > 1)) */
+    int32_t sampled_iterations;   /* iterations whose stage times were taken (== iterations unless icp_set_stage_timing(N != 1)) */
 } icp_timing;
 
 /* -------- context -------- */
@@ -195,12 +198,13 @@ typedef struct icp_start_result {
 int icp_run_multistart(icp_ctx* ctx, const float* initial_poses, int32_t n_starts, icp_start_result* results, icp_iter_stats* stats,
                        int32_t max_stats, int32_t* n_iterations_run, int32_t* best_out);
 /* The same breakdown iteration by iteration for the last icp_run (what TimeMeasure accumulates, before the sum): entry i is the
- * device time of iteration i in milliseconds, or -1 when that iteration was not bracketed (icp_set_stage_timing(N != 1)).  Any of
+ * device time of iteration i in milliseconds, or -1 when that iteration was not sampled (icp_set_stage_timing(N != 1)).  Any of
  * the three arrays may be NULL; *count_out = iterations of the last run. */
 int icp_get_iteration_times(const icp_ctx* ctx, float* match_ms, float* weight_reject_build_ms, float* solve_ms, int32_t max_out, int32_t* count_out);
-/* How icp_run fills the stage breakdown: 0 = whole-run time only, 1 = every iteration bracketed by HIP events (default;
- * what TimeMeasure does), N > 1 = every Nth iteration (rotating offset), stage sums scaled by iterations / sampled.
- * A HIP event costs about 4 us of stream time, i.e. mode 1 is ~10 % of a 0.07 ms iteration. */
+/* How icp_run fills the stage breakdown: 0 = whole-run time only, 1 = every iteration (default; what TimeMeasure does),
+ * N > 1 = every Nth iteration (rotating offset), stage sums scaled by iterations / sampled.
+ * The merged form reads the device's clock inside its launches: no stream cost, the mode only selects what is reported.  The
+ * other forms bracket with HIP events at about 4 us of stream time each, i.e. mode 1 is ~10 % of a 0.07 ms iteration there. */
 int icp_set_stage_timing(icp_ctx* ctx, int32_t every_nth);
 /* The iteration schedule icp_run will execute (pure host logic, no device needed): one decimation factor per
  * iteration, 0 = full cloud without selection.  ICPOptimizer.h:503-516,540,634-655 / PointCloud.h:325-343. */
