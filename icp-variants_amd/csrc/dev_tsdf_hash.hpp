@@ -6,7 +6,8 @@
 // ------------------------------------------------------------------------------------------------
 // Layout: `keys` (8 bytes per slot, empty = ~0) and `vals` (4 bytes per slot: the block's index in the pool, HT_NONE while the slot has
 // none) are the table; `pool` holds the blocks, 512 float2 each, x fastest (4 KiB; one z-layer is a 512-byte run); `pool_key` records the
-// key of every pool block, so a kernel over the blocks 0 .. n_blocks - 1 never scans the table.  Blocks are only ever appended, and the
+// key of every pool block, so a kernel over the blocks 0 .. n_blocks - 1 never scans the table.  The kernels here only ever append blocks
+// (dev_tsdf_hash_evict.hpp takes blocks out and leaves the pool compact, its tail cleared), and the
 // pool is cleared when it is allocated: a fresh block reads (0, 0), unobserved.  Where a block sits in the pool may depend on a race
 // between two claims; what it holds does not.  Integer atomics and vector stores only.
 constexpr int HT_NONE = -1, HT_TAKEN = -2;          // vals: no block yet; a claim is deciding (or has found the pool full)

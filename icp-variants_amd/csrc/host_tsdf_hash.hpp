@@ -148,11 +148,12 @@ int htsdf_reset(icp_ctx* c) {
     HIPCK(c, hipMemsetAsync(c->th_pkey.p, 0xFF, blocks * 8, c->stream));
     HIPCK(c, hipMemsetAsync(c->th_ctr.p, 0, HT_NCTR * 4, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
-    c->th_nblk = 0; c->th_unplaced = 0; c->th_oor = 0;
+    c->th_nblk = 0; c->th_unplaced = 0; c->th_oor = 0; c->te_held = 0;
     return ICP_OK;
 }
 void htsdf_drop(icp_ctx* c) {
-    for (DevBuf* d : {&c->th_keys, &c->th_vals, &c->th_pool, &c->th_pkey, &c->th_ctr}) release(*d);
+    for (DevBuf* d : {&c->th_keys, &c->th_vals, &c->th_pool, &c->th_pkey, &c->th_ctr, &c->te_work, &c->te_out_pool, &c->te_out_key}) release(*d);
+    c->te_held = 0;
     c->tsdf_hashed = false; c->th_log2cap = 0; c->th_pool_cap = 0; c->th_nblk = 0;
 }
 // block coordinates from the caller: every one storable, or a message
@@ -171,6 +172,65 @@ int htsdf_allocate(icp_ctx* c, int32_t n, const int32_t* coords, DevBuf& d_coord
         return (int)ICP_OK;
     };
     return htsdf_claim(c, alloc, who, nullptr);
+}
+// A save path: n blocks of a pool (this volume's, or the outbox of an evict) to the host SORTED BY KEY -- the keys first, sorted on the host;
+// then the blocks, a slab of at most 4096 (16 MiB) at a time.  Any output may be null.
+int htsdf_download_sorted(icp_ctx* c, int n, const void* d_pkey, const void* d_pool, int32_t* coords_out, float* tsdf_out, float* weight_out) {
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> keys((size_t)n);
+    HIPCK(c, hipMemcpy(keys.data(), d_pkey, (size_t)n * 8, hipMemcpyDeviceToHost));
+    std::vector<std::pair<unsigned long long, int>> order((size_t)n);
+    for (int i = 0; i < n; i++) order[(size_t)i] = {keys[(size_t)i], i};
+    std::sort(order.begin(), order.end());
+    std::vector<int> place((size_t)n);                 // pool index -> position in the sorted output
+    for (int e = 0; e < n; e++) {
+        place[(size_t)order[(size_t)e].second] = e;
+        if (coords_out) for (int a = 0; a < 3; a++) coords_out[3 * (size_t)e + a] = (int32_t)((order[(size_t)e].first >> (21 * a)) & 0x1FFFFFull) - HM_RANGE;
+    }
+    if (!tsdf_out && !weight_out) return ICP_OK;
+    const int slab = 4096;
+    std::vector<float> h((size_t)(n < slab ? n : slab) * 1024);
+    for (int at = 0; at < n; at += slab) {
+        const int m = n - at < slab ? n - at : slab;
+        HIPCK(c, hipMemcpy(h.data(), (const char*)d_pool + (size_t)at * 4096, (size_t)m * 4096, hipMemcpyDeviceToHost));
+        for (int i = 0; i < m; i++) {
+            const size_t e = (size_t)place[(size_t)(at + i)];
+            const float* src = h.data() + (size_t)i * 1024;
+            if (tsdf_out) for (int q = 0; q < 512; q++) tsdf_out[e * 512 + q] = src[2 * q];
+            if (weight_out) for (int q = 0; q < 512; q++) weight_out[e * 512 + q] = src[2 * q + 1];
+        }
+    }
+    return ICP_OK;
+}
+// n block coordinates as sorted keys; false when one occurs twice
+bool htsdf_keys_distinct(int32_t n, const int32_t* coords) {
+    std::vector<unsigned long long> keys((size_t)n);
+    for (int i = 0; i < n; i++) {
+        unsigned long long k = 0;
+        for (int a = 0; a < 3; a++) k |= (unsigned long long)(uint32_t)(coords[3 * (size_t)i + a] + HM_RANGE) << (21 * a);
+        keys[(size_t)i] = k;
+    }
+    std::sort(keys.begin(), keys.end());
+    return std::adjacent_find(keys.begin(), keys.end()) == keys.end();
+}
+// n blocks in icp_get_tsdf_hashed's layout (their coordinates on the device in d_coords, allocated) placed where they sit in the pool, a
+// slab of at most 4096 at a time (waits per slab: the host block and the staging buffer are reused)
+int htsdf_place_blocks(icp_ctx* c, int32_t n, const DevBuf& d_coords, const float* tsdf, const float* weight) {
+    int rc;
+    DevBuf d_in;
+    const int slab = 4096;
+    const int m_max = n < slab ? n : slab;
+    std::vector<float2> h((size_t)m_max * 512);
+    if ((rc = ensure(c, d_in, (size_t)m_max * 4096))) return rc;
+    for (int at = 0; at < n; at += slab) {
+        const int m = n - at < slab ? n - at : slab;
+        for (size_t q = 0; q < (size_t)m * 512; q++) h[q] = make_float2(tsdf[(size_t)at * 512 + q], weight[(size_t)at * 512 + q]);
+        HIPCK(c, hipMemcpyAsync(d_in.p, h.data(), (size_t)m * 4096, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_htsdf_place, dim3(m), dim3(512), 0, c->stream, htsdf_view(c), (const int*)(d_coords.as<int>() + 3 * (size_t)at), (const float2*)d_in.as<float2>());
+        HIPCK(c, hipGetLastError());
+        HIPCK(c, hipStreamSynchronize(c->stream));      // (the host block and d_in are reused by the next slab)
+    }
+    return ICP_OK;
 }
 }  // namespace
 
@@ -251,32 +311,7 @@ int icp_get_tsdf_hashed(icp_ctx* c, icp_tsdf_hashed_info* info_out, int32_t max_
     }
     if (n == 0) return ICP_OK;
     if ((rc = set_device(c))) return rc;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    // a save path: the blocks' keys to the host, sorted; then the blocks, a slab of at most 4096 (16 MiB) at a time
-    std::vector<unsigned long long> keys((size_t)n);
-    HIPCK(c, hipMemcpy(keys.data(), c->th_pkey.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    std::vector<std::pair<unsigned long long, int>> order((size_t)n);
-    for (int i = 0; i < n; i++) order[(size_t)i] = {keys[(size_t)i], i};
-    std::sort(order.begin(), order.end());
-    std::vector<int> place((size_t)n);                 // pool index -> position in the sorted output
-    for (int e = 0; e < n; e++) {
-        place[(size_t)order[(size_t)e].second] = e;
-        if (coords_out) for (int a = 0; a < 3; a++) coords_out[3 * (size_t)e + a] = (int32_t)((order[(size_t)e].first >> (21 * a)) & 0x1FFFFFull) - HM_RANGE;
-    }
-    if (!tsdf_out && !weight_out) return ICP_OK;
-    const int slab = 4096;
-    std::vector<float> h((size_t)(n < slab ? n : slab) * 1024);
-    for (int at = 0; at < n; at += slab) {
-        const int m = n - at < slab ? n - at : slab;
-        HIPCK(c, hipMemcpy(h.data(), c->th_pool.as<char>() + (size_t)at * 4096, (size_t)m * 4096, hipMemcpyDeviceToHost));
-        for (int i = 0; i < m; i++) {
-            const size_t e = (size_t)place[(size_t)(at + i)];
-            const float* src = h.data() + (size_t)i * 1024;
-            if (tsdf_out) for (int q = 0; q < 512; q++) tsdf_out[e * 512 + q] = src[2 * q];
-            if (weight_out) for (int q = 0; q < 512; q++) weight_out[e * 512 + q] = src[2 * q + 1];
-        }
-    }
-    return ICP_OK;
+    return htsdf_download_sorted(c, n, c->th_pkey.p, c->th_pool.p, coords_out, tsdf_out, weight_out);
 }
 
 int icp_tsdf_upload_hashed(icp_ctx* c, int32_t n, const int32_t* coords, const float* tsdf, const float* weight) {
@@ -286,16 +321,7 @@ int icp_tsdf_upload_hashed(icp_ctx* c, int32_t n, const int32_t* coords, const f
     if ((rc = htsdf_check(c, who))) return rc;
     if (n < 0 || (n > 0 && (!coords || !tsdf || !weight))) { c->err = std::string(who) + ": bad argument (n >= 0, coords, tsdf, weight)"; return ICP_ERR_INVALID_ARG; }
     if ((rc = htsdf_check_coords(c, n, coords, who))) return rc;
-    {
-        std::vector<unsigned long long> keys((size_t)n);
-        for (int i = 0; i < n; i++) {
-            unsigned long long k = 0;
-            for (int a = 0; a < 3; a++) k |= (unsigned long long)(uint32_t)(coords[3 * (size_t)i + a] + HM_RANGE) << (21 * a);
-            keys[(size_t)i] = k;
-        }
-        std::sort(keys.begin(), keys.end());
-        if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) { c->err = std::string(who) + ": a block coordinate occurs twice"; return ICP_ERR_INVALID_ARG; }
-    }
+    if (!htsdf_keys_distinct(n, coords)) { c->err = std::string(who) + ": a block coordinate occurs twice"; return ICP_ERR_INVALID_ARG; }
     const int l = ht_log2_for(n);
     if (l < 0) { c->err = std::string(who) + ": more than 2^22 blocks"; return ICP_ERR_INVALID_ARG; }
     DrainOnError guard(c);
@@ -305,20 +331,9 @@ int icp_tsdf_upload_hashed(icp_ctx* c, int32_t n, const int32_t* coords, const f
     if ((rc = htsdf_reset(c))) return rc;
     if (n > c->th_pool_cap && (rc = htsdf_regrow(c, l, 0))) return rc;
     if (n > 0) {
-        DevBuf d_coords, d_in;
+        DevBuf d_coords;
         if ((rc = htsdf_allocate(c, n, coords, d_coords, who))) return rc;
-        const int slab = 4096;
-        const int m_max = n < slab ? n : slab;
-        std::vector<float2> h((size_t)m_max * 512);
-        if ((rc = ensure(c, d_in, (size_t)m_max * 4096))) return rc;
-        for (int at = 0; at < n; at += slab) {
-            const int m = n - at < slab ? n - at : slab;
-            for (size_t q = 0; q < (size_t)m * 512; q++) h[q] = make_float2(tsdf[(size_t)at * 512 + q], weight[(size_t)at * 512 + q]);
-            HIPCK(c, hipMemcpyAsync(d_in.p, h.data(), (size_t)m * 4096, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_htsdf_place, dim3(m), dim3(512), 0, c->stream, htsdf_view(c), (const int*)(d_coords.as<int>() + 3 * (size_t)at), (const float2*)d_in.as<float2>());
-            HIPCK(c, hipGetLastError());
-            HIPCK(c, hipStreamSynchronize(c->stream));      // (the host block and d_in are reused by the next slab)
-        }
+        if ((rc = htsdf_place_blocks(c, n, d_coords, tsdf, weight))) return rc;
     }
     return guard.done();
 }

@@ -100,6 +100,22 @@ class IcpTsdfHashedInfo(C.Structure):
     _fields_ = [("n_blocks", C.c_int32), ("capacity", C.c_int32), ("n_grown", C.c_int32), ("n_unplaced", C.c_int32), ("n_out_of_range", C.c_int64)]
 
 
+class IcpTsdfStreamInfo(C.Structure):
+    _fields_ = [("n_evicted", C.c_int32), ("n_blocks", C.c_int32), ("n_moved", C.c_int32), ("capacity", C.c_int32), ("n_held", C.c_int32),
+                ("n_inserted", C.c_int32), ("n_present", C.c_int32), ("n_grown", C.c_int32)]
+
+
+def tsdf_view_reach(cam, options):
+    """The farthest a block that a frame of `cam` can touch, update or sample has its centre from the camera, with a block diagonal of
+    slack: (max_depth + truncation) * sqrt(1 + a_max^2 + b_max^2) + 8 * voxel_size * sqrt(3), with
+    a_max = max(|0 - cx|, |width - 1 - cx|) / fx and b_max likewise with cy, fy and the height.  `options`: an IcpTsdfOptions, or a dict of
+    `tsdf_options`' arguments.  Infinite when max_depth is."""
+    o = options if isinstance(options, IcpTsdfOptions) else tsdf_options(**{k: v for k, v in dict(options).items() if k != "dims"})
+    a = max(abs(0.0 - cam.cx), abs(cam.width - 1.0 - cam.cx)) / abs(cam.fx)
+    b = max(abs(0.0 - cam.cy), abs(cam.height - 1.0 - cam.cy)) / abs(cam.fy)
+    return (float(o.max_depth) + float(o.truncation)) * float(np.sqrt(1.0 + a * a + b * b)) + 8.0 * float(o.voxel_size) * float(np.sqrt(3.0))
+
+
 def tsdf_blocks_to_dense(coords, tsdf, weight, lo, dims):
     """The blocks of a hashed volume (`Context.tsdf_blocks`) as the two dense arrays (nz, ny, nx) `Context.tsdf_upload` takes, on the host:
     dense voxel (0, 0, 0) is global voxel `lo` (three integers), so the dense volume's origin is origin + lo * voxel_size; voxels no block
@@ -420,6 +436,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_sdf_options_default", "icp_sdf_options_check", "icp_tsdf_sample", "icp_tsdf_sdf_system", "icp_tsdf_align_depth", "icp_track_depth_sdf",
            "icp_tsdf_create_hashed", "icp_tsdf_reserve_blocks", "icp_tsdf_allocate_blocks", "icp_get_tsdf_hashed", "icp_tsdf_upload_hashed",
            "icp_tsdf_mesh_hashed", "icp_tsdf_raycast_hashed", "icp_set_target_tsdf_hashed", "icp_track_depth_model_hashed",
+           "icp_tsdf_evict_blocks", "icp_tsdf_evicted_blocks", "icp_tsdf_insert_blocks",
            "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
            "icp_track_depth_sdf_color",
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
@@ -998,6 +1015,33 @@ class Context:
         if not (len(cc) == len(t) == len(w)):
             raise ValueError("coords (B, 3), tsdf and weight (B, 8, 8, 8) must agree in B")
         self._ck(self.lib.icp_tsdf_upload_hashed(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(t), _ptr(w)))
+
+    def tsdf_evict_blocks(self, centre, radius, hold=True):
+        """icp_tsdf_evict_blocks: every block of the hashed volume whose centre lies beyond `radius` metres of `centre` leaves the device
+        (DESIGN.md section 6za).  Returns (info dict(n_evicted, n_blocks, n_moved, capacity, n_held, n_inserted, n_present, n_grown),
+        coords (E, 3) int32, tsdf (E, 8, 8, 8), weight (E, 8, 8, 8)): the evicted blocks sorted by key (icp_tsdf_evicted_blocks), for the
+        caller to keep; with hold=False they are forgotten and the arrays are empty."""
+        ce = _f32(centre).reshape(-1)
+        if ce.size != 3:
+            raise ValueError("centre is three numbers")
+        info = IcpTsdfStreamInfo()
+        self._ck(self.lib.icp_tsdf_evict_blocks(self.h, _ptr(ce), C.c_float(radius), C.c_int32(1 if hold else 0), C.byref(info)))
+        n = info.n_held
+        coords = np.empty((n, 3), np.int32); t = np.empty((n, 8, 8, 8), np.float32); w = np.empty((n, 8, 8, 8), np.float32)
+        if n:
+            self._ck(self.lib.icp_tsdf_evicted_blocks(self.h, C.c_int32(n), _ptr(coords), _ptr(t), _ptr(w)))
+        return {k: getattr(info, k) for k, _ in info._fields_}, coords, t, w
+
+    def tsdf_insert_blocks(self, coords, tsdf, weight):
+        """icp_tsdf_insert_blocks: ADDS the blocks `coords` (B, 3) with `tsdf` and `weight` (B, 8, 8, 8) to the hashed volume's state
+        (`tsdf_upload_blocks` replaces it); a block that is resident already refuses the call.  Returns the info dict of `tsdf_evict_blocks`."""
+        cc = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3)
+        t = _f32(tsdf).reshape(-1, 8, 8, 8); w = _f32(weight).reshape(-1, 8, 8, 8)
+        if not (len(cc) == len(t) == len(w)):
+            raise ValueError("coords (B, 3), tsdf and weight (B, 8, 8, 8) must agree in B")
+        info = IcpTsdfStreamInfo()
+        self._ck(self.lib.icp_tsdf_insert_blocks(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(t), _ptr(w), C.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
 
     def tsdf_color_create(self):
         """icp_tsdf_color_create: the volume's colour array, one (R, G, B, Wc) per voxel, allocated and cleared (called again: cleared)."""

@@ -15,7 +15,7 @@ freiburg1_xyz run offline.
 import os
 import numpy as np
 
-from . import binding, formats, meshio, synth
+from . import binding, formats, meshio, synth, tsdf_local
 
 TUM_K = np.array([[525.0, 0.0, 319.5], [0.0, 525.0, 239.5], [0.0, 0.0, 1.0]], np.float32)     # VirtualSensor.h:44-46
 TUM_WIDTH, TUM_HEIGHT = 640, 480
@@ -104,9 +104,18 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     trajectory need not be known beforehand.  model=dict(hashed=True, raycast=True, origin=..., ...) with sdf=None tracks frame-to-model on
     the hashed volume instead (icp_track_depth_model_hashed): every frame against a ray-cast of the blocks, with the
     params' matcher, the optimiser, convergence and reciprocal choices and `with_gt` as on the dense model path.  hashed=True without `sdf`
-    and without raycast=True, with dims, or with color=True is a ValueError; so is raycast=True together with `sdf` or without hashed=True."""
+    and without raycast=True, with dims, or with color=True is a ValueError; so is raycast=True together with `sdf` or without hashed=True.
+    model=dict(hashed=True, keep_radius=R, ...) with `sdf` keeps only the blocks within R metres of the camera on the device and streams
+    the rest to the host and back (tsdf_local.track_depth_sdf_local): the poses and records are those of the
+    unbounded run, the stored blocks are left in ctx.tsdf_store (tsdf_local.restore(ctx, ctx.tsdf_store) puts the whole model back).
+    keep_radius without hashed=True, or together with raycast=True, is a ValueError; keep_radius=None, the default, changes nothing."""
     hashed = bool(model is not None and model.get("hashed"))
     raycast = bool(model is not None and model.get("raycast"))
+    keep_radius = model.get("keep_radius") if model is not None else None
+    if keep_radius is not None and not hashed:
+        raise ValueError("keep_radius streams the blocks of a hashed model: pass hashed=True as well")
+    if keep_radius is not None and raycast:
+        raise ValueError("keep_radius streams the directly tracked hashed model (sdf=dict(...)): the ray-cast loop has no streaming")
     if raycast and not hashed:
         raise ValueError("raycast=True selects the ray-cast loop of a hashed model: pass hashed=True as well (a dense model is ray-cast as it is)")
     if raycast and sdf is not None:
@@ -132,9 +141,12 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     tgt_o, src_o = reconstruct_room_options(ctx.params) if options is None else options
     if hashed:
-        ctx.tsdf_create_hashed(**{k: v for k, v in model.items() if k not in ("hashed", "raycast", "color", "dims")})
+        ctx.tsdf_create_hashed(**{k: v for k, v in model.items() if k not in ("hashed", "raycast", "color", "dims", "keep_radius")})
+        ctx.tsdf_store = None
         if raycast:
             _, recs, rc = ctx.track_depth_model_hashed(seq["depth"], cam, src_o, gt=seq["gt"] if with_gt else None)
+        elif keep_radius is not None:
+            _, recs, rc, _, ctx.tsdf_store = tsdf_local.track_depth_sdf_local(ctx, seq["depth"], cam, keep_radius, **sdf)
         else:
             _, recs, rc = ctx.track_depth_sdf(seq["depth"], cam, **sdf)
         poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
@@ -187,6 +199,8 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
             meshio.write_off(path, *mesh)
             out.append(path)
     if model is not None and model_mesh is not None and out_dir is not None:
+        if model.get("hashed") and getattr(ctx, "tsdf_store", None) is not None:
+            tsdf_local.restore(ctx, ctx.tsdf_store)     # (a streamed model: the union of the resident and the stored blocks)
         if model.get("hashed") and not densify:
             meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh_hashed())
             return poses, recs, rc, out

@@ -844,6 +844,48 @@ int icp_get_tsdf_hashed(icp_ctx* ctx, icp_tsdf_hashed_info* info_out, int32_t ma
 /* REPLACES the state with n blocks in icp_get_tsdf_hashed's layout (storable, none twice, else ICP_ERR_INVALID_ARG); the counters restart. */
 int icp_tsdf_upload_hashed(icp_ctx* ctx, int32_t n, const int32_t* coords, const float* tsdf, const float* weight);
 
+/* -------- streaming the hashed volume (an extension): the blocks beyond a radius of the camera leave the device for the host and come back
+ * when the camera returns (Niessner et al., section 5), so device memory and the integrate's cost are bounded by what is in reach while
+ * the model stays complete on the host.  DESIGN.md section 6za.  tests/htsdf_evict_restatement.py restates what follows. --------
+ * Rule of evict(centre, radius): it applies to every pool block 0 .. n_blocks - 1.  With b the block's coordinates (from its key), o and s
+ *   the volume's origin and voxel size, in fp32, operation for operation, without contraction:
+ *     p_a = o_a + ((float)(8 b_a) + 3.5f) * s      (the centre of the block's 512 voxel positions)
+ *     d_a = p_a - centre_a,   d2 = (d_x d_x + d_y d_y) + d_z d_z
+ *   the block is KEPT iff d2 <= r2, with r2 = radius * radius computed once on the host in fp32; an infinite r2 keeps everything.  This
+ *   is icp_voxel_map_prune's rule with a block's centre in place of a cell's.  centre must be finite, radius finite and >= 0.
+ * After icp_tsdf_evict_blocks the volume holds exactly the kept blocks, bit for bit; n_blocks is their number; the pool entries
+ *   n_blocks .. capacity - 1 read (0, 0) and carry no key, as after create, so a later touch hands out fresh blocks; the table holds the
+ *   kept keys and nothing else (it is cleared and rebuilt: linear probing cannot delete a key).  capacity, n_grown and n_out_of_range do
+ *   not change.  The state equals, through every public call, that of a fresh volume that icp_tsdf_upload_hashed filled with the kept
+ *   blocks.  If no block is evicted nothing at all is modified.  Where a kept block sits in the pool afterwards may depend on a race (the
+ *   kept blocks at or above n_blocks move into the holes below it); what the volume holds does not.
+ * hold != 0: the evicted blocks and their keys are first copied into a device-side OUTBOX that the context owns; icp_tsdf_evicted_blocks
+ *   returns it in icp_get_tsdf_hashed's layout, sorted by key (max_blocks below n_held: ICP_ERR_INVALID_ARG, the message names both).  The
+ *   outbox lives until the next evict, reset, release, create or upload.  hold == 0: the evicted blocks are forgotten.
+ * icp_tsdf_insert_blocks ADDS n blocks in icp_get_tsdf_hashed's layout to the existing state (icp_tsdf_upload_hashed REPLACES it).  It
+ *   refuses with ICP_ERR_INVALID_ARG and a reason, before anything is modified: a coordinate that is not storable, one that occurs twice,
+ *   and any key that is resident already (counted on the device; the count is in the message and in n_present).  Otherwise the blocks
+ *   are allocated under the room rule (the pool grows where it must) and their voxels placed.
+ * Both calls refuse a context without a volume and one with a dense volume, with a message that names the call.
+ * Host waits: an evict waits once when nothing leaves (the mark's counters) and twice otherwise; an insert once for the resident count, once
+ *   per room-rule launch and once per slab of 4096 blocks. */
+typedef struct icp_tsdf_stream_info {
+    int32_t n_evicted;               /* evict: blocks that left */
+    int32_t n_blocks;                /* allocated blocks after the call */
+    int32_t n_moved;                 /* evict: kept blocks that changed their place in the pool */
+    int32_t capacity;                /* blocks the pool holds before it grows */
+    int32_t n_held;                  /* evict: blocks in the outbox after the call (n_evicted with hold != 0, else 0) */
+    int32_t n_inserted;              /* insert: blocks added */
+    int32_t n_present;               /* insert: keys that were resident already (nonzero: the call was refused) */
+    int32_t n_grown;                 /* growths since create */
+} icp_tsdf_stream_info;
+#ifdef __cplusplus
+static_assert(sizeof(icp_tsdf_stream_info) == 32, "icp_tsdf_stream_info");
+#endif
+int icp_tsdf_evict_blocks(icp_ctx* ctx, const float centre[3], float radius, int32_t hold, icp_tsdf_stream_info* info_out);
+int icp_tsdf_evicted_blocks(icp_ctx* ctx, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out);
+int icp_tsdf_insert_blocks(icp_ctx* ctx, int32_t n, const int32_t* coords, const float* tsdf, const float* weight, icp_tsdf_stream_info* info_out);
+
 /* -------- the hashed model as a mesh (an extension): icp_tsdf_mesh on the block pool -- the zero level set of the context's HASHED volume
  * as an indexed triangle mesh with per-vertex normals; only the mesh crosses to the host and scratch scales with the blocks in use, not with
  * an extent.  DESIGN.md section 6y.  tests/htsdf_mesh_restatement.py restates what follows, compared bit for bit. --------
