@@ -153,6 +153,8 @@ struct icp_ctx {
     DevBuf tsdf_col; bool tsdf_col_on = false;   // its optional colour array (icp_tsdf_color_create): one float4 (R, G, B, Wc) per voxel, 16 bytes, the indexing of tsdf_vox
     DevBuf th_keys, th_vals, th_pool, th_pkey, th_ctr;   // the hashed storage of the volume (host_tsdf_hash.hpp): the table's keys and pool indices, the pool of 4 KiB blocks, every block's key, the counters
     bool tsdf_hashed = false; int th_log2cap = 0, th_pool_cap = 0, th_nblk = 0, th_grown = 0, th_unplaced = 0, th_max_log2 = 22; long long th_oor = 0;   // the volume is hashed (icp_tsdf_create_hashed); table of 2^th_log2cap slots, pool of th_pool_cap blocks; allocated blocks (exact after every call); growths; the last touch's unplaced claims; log2 of the largest pool growth may reach (2^22 blocks; lowered by icp_debug_htsdf_max_blocks alone); samples out of range so far
+    DevBuf th_cpool; bool th_color = false;   // the colours of the hashed volume (icp_tsdf_create_color_hashed): a second pool, one float4 (R, G, B, Wc) per voxel, 8 KiB per block, by the same pool index
+    DevBuf te_out_cpool;                 // the colours of the outbox (a coloured hashed volume evicted with hold)
     DevBuf te_work, te_out_pool, te_out_key; int te_held = 0;   // streaming the hashed volume (host_tsdf_hash_evict.hpp): an evict's flags, lists and counters; the outbox (evicted blocks and their keys) and the blocks it holds
     DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
     DevBuf tm_nbr, tm_ord;               // icp_tsdf_mesh_hashed (host_tsdf_hash_mesh.hpp), which also uses the five above: the 27 neighbour ranks of every block; order[rank] -> pool index, then rank_of[pool index]

@@ -68,7 +68,7 @@ int sdf_enqueue(icp_ctx* c, int slot, const SdfPlan& pl, const icp_sdf_options& 
 }
 // tsdf_integrate_slot on whichever storage the volume has (hashed: the touch's counters are read, one more host wait)
 int sdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], bool color, const char* who) {
-    return c->tsdf_hashed ? htsdf_integrate_slot(c, slot, cam, pose, nullptr, who) : tsdf_integrate_slot(c, slot, cam, pose, nullptr, color);
+    return c->tsdf_hashed ? htsdf_integrate_slot(c, slot, cam, pose, nullptr, who, color) : tsdf_integrate_slot(c, slot, cam, pose, nullptr, color);
 }
 // The frame's record (and its trace) back through the page-locked block, waited for: the one host read of a frame.
 int sdf_read_record(icp_ctx* c, const icp_sdf_options& opt, icp_sdf_frame* rec_out, icp_sdf_iter* trace_out) {
@@ -166,7 +166,7 @@ int icp_track_depth_sdf(icp_ctx* c, const float* depth_frames, const uint8_t* rg
     int rc;
     if ((rc = sdf_check_call(c, depth_frames, cam, pose_inout, opt, who))) return rc;
     const bool color = rgbx_frames != nullptr;
-    if (color && (rc = tsdf_check_color(c, who))) return rc;
+    if (color && !tsdf_hashed_color(c) && (rc = tsdf_check_color(c, who))) return rc;      // (colour frames need colours: the dense array, or the blocks')
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     const int n = cam->width * cam->height;

@@ -1,6 +1,7 @@
 // host_sdf_color.hpp -- direct SDF tracking with the photometric term: the intensity field sampled at points (icp_tsdf_sample_color), the
 // sums of one joint step (icp_tsdf_sdf_system_color), one frame aligned (icp_tsdf_align_depth_color) and the tracking loop
-// (icp_track_depth_sdf_color).  Kernels: dev_sdf_color.hpp; contract: include/icp_hip.h, DESIGN.md section 6r.  Part of icp_hip.hip
+// (icp_track_depth_sdf_color), on the dense coloured volume or on a coloured hashed one (k_htsdf_sample_color, k_hsdf_accumulate_color:
+// dev_tsdf_hash_color.hpp).  Kernels: dev_sdf_color.hpp; contract: include/icp_hip.h, DESIGN.md section 6r.  Part of icp_hip.hip
 // (included from there, after host_sdf.hpp, whose checks, plan and staging it uses; the state, partials and record buffers are the same
 // ones, sized for the larger records -- every call writes them before it reads them).
 namespace {
@@ -13,8 +14,9 @@ const char* sdf_color_options_error(const icp_sdf_color_options* o) {
 int sdf_color_check_call(icp_ctx* c, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const float* pose, const icp_sdf_options* opt,
                          const icp_sdf_color_options* copt, const char* who) {
     int rc;
-    if ((rc = tsdf_check_call(c, cam, pose, who))) return rc;
-    if ((rc = tsdf_check_color(c, who))) return rc;
+    const bool hcol = tsdf_hashed_color(c);          // (either coloured storage: sdf_color_enqueue and sdf_color_integrate_slot choose the kernels)
+    if ((rc = tsdf_check_call(c, cam, pose, who, hcol))) return rc;
+    if (!hcol && (rc = tsdf_check_color(c, who))) return rc;
     if (!depth) { c->err = std::string(who) + ": null depth frame"; return ICP_ERR_INVALID_ARG; }
     if (!rgbx) { c->err = std::string(who) + ": null colour frame (rgbx)"; return ICP_ERR_INVALID_ARG; }
     if (const char* why = sdf_options_error(opt)) { c->err = std::string(who) + ": " + why; return ICP_ERR_INVALID_ARG; }
@@ -35,13 +37,15 @@ int sdf_color_enqueue(icp_ctx* c, int slot, const SdfPlan& pl, const icp_sdf_opt
     SdfFrame f = pl.f;
     f.depth = c->depth_dev[slot].as<float>();
     SdfColorFrame cf;
-    cf.col = c->tsdf_col.as<float4>(); cf.rgbx = (const uint32_t*)(f.depth + (size_t)f.width * f.height); cf.weight = copt.weight; cf.huber = copt.huber;
+    const bool hashed = c->tsdf_hashed;
+    cf.col = hashed ? c->th_cpool.as<float4>() : c->tsdf_col.as<float4>(); cf.rgbx = (const uint32_t*)(f.depth + (size_t)f.width * f.height); cf.weight = copt.weight; cf.huber = copt.huber;
     SdfColorState* st = c->sdf_state.as<SdfColorState>();
     icp_sdf_color_frame* rec = c->sdf_rec.as<icp_sdf_color_frame>();
     icp_sdf_color_iter* tr = (icp_sdf_color_iter*)(rec + 1);
     double* partials = c->sdf_partials.as<double>();
     int* counts = (int*)(partials + (size_t)SDFC_NSUM * pl.n_blocks);
     const TsdfVol v = tsdf_view(c);
+    const HtVol hv = hashed ? htsdf_view(c) : HtVol();
     TsdfMat m; memcpy(m.m, pose, 64);
     HIPCK(c, hipStreamWaitEvent(c->stream, c->depth_up[slot], 0));
     if (trace) HIPCK(c, hipMemsetAsync(tr, 0, (size_t)opt.n_iterations * sizeof(icp_sdf_color_iter), c->stream));
@@ -52,12 +56,17 @@ int sdf_color_enqueue(icp_ctx* c, int slot, const SdfPlan& pl, const icp_sdf_opt
     sp.stop_rotation = opt.stop_rotation; sp.stop_translation = opt.stop_translation;
     const int iterations = step ? opt.n_iterations : 1;
     for (int it = 0; it < iterations; it++) {
-        hipLaunchKernelGGL(k_sdf_accumulate_color, pl.grid, dim3(256), 0, c->stream, v, f, cf, (const SdfColorState*)st, partials, counts);
+        if (hashed) hipLaunchKernelGGL(k_hsdf_accumulate_color, pl.grid, dim3(256), 0, c->stream, hv, f, cf, (const SdfColorState*)st, partials, counts);
+        else hipLaunchKernelGGL(k_sdf_accumulate_color, pl.grid, dim3(256), 0, c->stream, v, f, cf, (const SdfColorState*)st, partials, counts);
         sp.iter = it;
         hipLaunchKernelGGL(k_sdf_solve_color, dim3(1), dim3(256), 0, c->stream, sp);
     }
     HIPCK(c, hipGetLastError());
     return ICP_OK;
+}
+// the coloured integrate on whichever storage the volume has (hashed: the touch's counters are read, one more host wait)
+int sdf_color_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], const char* who) {
+    return c->tsdf_hashed ? htsdf_integrate_slot(c, slot, cam, pose, nullptr, who, true) : tsdf_integrate_slot(c, slot, cam, pose, nullptr, true);
 }
 int sdf_color_read_record(icp_ctx* c, const icp_sdf_options& opt, icp_sdf_color_frame* rec_out, icp_sdf_color_iter* trace_out) {
     int rc;
@@ -88,7 +97,8 @@ int icp_sdf_color_options_check(const icp_sdf_color_options* o) { return sdf_col
 int icp_tsdf_sample_color(icp_ctx* c, const float* points, int32_t n, float* s_out, float* grad_out, uint8_t* valid_out) {
     if (!c) return ICP_ERR_INVALID_ARG;
     int rc;
-    if ((rc = tsdf_check_color(c, "icp_tsdf_sample_color"))) return rc;
+    const bool hcol = tsdf_hashed_color(c);
+    if (!hcol && (rc = tsdf_check_color(c, "icp_tsdf_sample_color"))) return rc;
     if (n < 0 || (n > 0 && !points)) { c->err = "icp_tsdf_sample_color: bad argument (n >= 0, points)"; return ICP_ERR_INVALID_ARG; }
     if (n == 0) return ICP_OK;
     DrainOnError guard(c);
@@ -96,7 +106,9 @@ int icp_tsdf_sample_color(icp_ctx* c, const float* points, int32_t n, float* s_o
     if ((rc = ensure(c, c->staging, (size_t)n * 29))) return rc;      // [points 12n | S 4n | H 12n | valid n]
     float* d_pts = c->staging.as<float>(); float* d_s = d_pts + (size_t)n * 3; float* d_h = d_s + n; uint8_t* d_ok = (uint8_t*)(d_h + (size_t)n * 3);
     HIPCK(c, hipMemcpyAsync(d_pts, points, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_tsdf_sample_color, dim3((n + 255) / 256), dim3(256), 0, c->stream, tsdf_view(c), (const float4*)c->tsdf_col.as<float4>(), (const float*)d_pts, (int)n,
+    if (hcol) hipLaunchKernelGGL(k_htsdf_sample_color, dim3((n + 255) / 256), dim3(256), 0, c->stream, htsdf_view(c), (const float4*)c->th_cpool.as<float4>(), (const float*)d_pts,
+                                 (int)n, d_s, d_h, d_ok);
+    else hipLaunchKernelGGL(k_tsdf_sample_color, dim3((n + 255) / 256), dim3(256), 0, c->stream, tsdf_view(c), (const float4*)c->tsdf_col.as<float4>(), (const float*)d_pts, (int)n,
                        d_s, d_h, d_ok);
     HIPCK(c, hipGetLastError());
     if (s_out) HIPCK(c, hipMemcpyAsync(s_out, d_s, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -164,7 +176,7 @@ int icp_track_depth_sdf_color(icp_ctx* c, const float* depth_frames, const uint8
     if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     if (!c->sdf_ev) HIPCK(c, hipEventCreateWithFlags(&c->sdf_ev.e, hipEventDisableTiming));
     if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
-    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose_inout, nullptr, true))) return rc;
+    if ((rc = sdf_color_integrate_slot(c, 0, *cam, pose_inout, who))) return rc;
     HIPCK(c, hipEventRecord(c->sdf_ev, c->stream));
     if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream))) return rc;
     int first_err = ICP_OK;
@@ -179,7 +191,7 @@ int icp_track_depth_sdf_color(icp_ctx* c, const float* depth_frames, const uint8
         if ((rc = sdf_color_read_record(c, *opt, &r, nullptr))) return rc;
         memcpy(pose_inout, r.pose, 64);
         if (r.status == ICP_OK) {
-            if ((rc = tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, true))) return rc;
+            if ((rc = sdf_color_integrate_slot(c, slot, *cam, pose_inout, who))) return rc;
             HIPCK(c, hipEventRecord(c->sdf_ev, c->stream));
         } else if (first_err == ICP_OK) { first_err = r.status; c->err = sdf_color_failure(who, r, *opt); }
     }

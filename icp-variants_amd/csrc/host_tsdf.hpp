@@ -23,7 +23,7 @@ bool is_identity16(const float* m) {
     return true;
 }
 // what host_tsdf_hash.hpp defines for a hashed volume
-int htsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count, const char* who);
+int htsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count, const char* who, bool color = false);
 int htsdf_reset(icp_ctx* c);
 int htsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], bool soa, const TsdfRayOut& o);      // (host_tsdf_hash_raycast.hpp)
 void htsdf_drop(icp_ctx* c);
@@ -32,6 +32,16 @@ int tsdf_check_dense(icp_ctx* c, const char* who) {
     if (c->tsdf_on && c->tsdf_hashed) { c->err = std::string(who) + ": not supported on a hashed volume (icp_tsdf_create_hashed): it needs the dense box of icp_tsdf_create"; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;
 }
+// the four calls that address the DENSE colour array: a coloured hashed volume is pointed at the calls that read and write its blocks
+int tsdf_check_dense_colors(icp_ctx* c, const char* who) {
+    if (c->tsdf_on && c->tsdf_hashed && c->th_color) {
+        c->err = std::string(who) + ": not supported on a hashed volume (icp_tsdf_create_color_hashed): it addresses the dense colour array; the colours of the blocks are read and written by icp_get_tsdf_color_hashed and icp_tsdf_upload_color_hashed";
+        return ICP_ERR_INVALID_ARG;
+    }
+    return ICP_OK;
+}
+// the volume is hashed and holds colours: the coloured calls that work on the blocks take it
+bool tsdf_hashed_color(const icp_ctx* c) { return c->tsdf_on && c->tsdf_hashed && c->th_color; }
 int tsdf_check_call(icp_ctx* c, const icp_depth_camera* cam, const float* pose, const char* who, bool hashed_ok = false) {
     if (!c->tsdf_on) { c->err = std::string(who) + ": no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
     if (!hashed_ok) { int rc; if ((rc = tsdf_check_dense(c, who))) return rc; }
@@ -213,6 +223,7 @@ int icp_tsdf_upload(icp_ctx* c, const float* tsdf, const float* weight) {
 int icp_tsdf_color_create(icp_ctx* c) {
     if (!c) return ICP_ERR_INVALID_ARG;
     if (!c->tsdf_on) { c->err = "icp_tsdf_color_create: no volume (icp_tsdf_create)"; return ICP_ERR_INVALID_ARG; }
+    if (int rd = tsdf_check_dense_colors(c, "icp_tsdf_color_create")) return rd;
     if (int rd = tsdf_check_dense(c, "icp_tsdf_color_create")) return rd;
     int rc;
     DrainOnError guard(c);
@@ -226,6 +237,7 @@ int icp_tsdf_color_create(icp_ctx* c) {
 int icp_tsdf_color_release(icp_ctx* c) {
     if (!c) return ICP_ERR_INVALID_ARG;
     int rc;
+    if ((rc = tsdf_check_dense_colors(c, "icp_tsdf_color_release"))) return rc;
     if ((rc = tsdf_check_color(c, "icp_tsdf_color_release"))) return rc;
     if ((rc = set_device(c))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
@@ -236,6 +248,7 @@ int icp_tsdf_color_release(icp_ctx* c) {
 int icp_tsdf_color_download(icp_ctx* c, float* rgb_out, float* weight_out) {
     if (!c) return ICP_ERR_INVALID_ARG;
     int rc;
+    if ((rc = tsdf_check_dense_colors(c, "icp_tsdf_color_download"))) return rc;
     if ((rc = tsdf_check_color(c, "icp_tsdf_color_download"))) return rc;
     if ((rc = set_device(c))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
@@ -252,6 +265,7 @@ int icp_tsdf_color_download(icp_ctx* c, float* rgb_out, float* weight_out) {
 int icp_tsdf_color_upload(icp_ctx* c, const float* rgb, const float* weight) {
     if (!c) return ICP_ERR_INVALID_ARG;
     int rc;
+    if ((rc = tsdf_check_dense_colors(c, "icp_tsdf_color_upload"))) return rc;
     if ((rc = tsdf_check_color(c, "icp_tsdf_color_upload"))) return rc;
     if (!rgb || !weight) { c->err = "icp_tsdf_color_upload: null array"; return ICP_ERR_INVALID_ARG; }
     if ((rc = set_device(c))) return rc;
@@ -290,13 +304,16 @@ int icp_tsdf_integrate_color(icp_ctx* c, const float* depth, const uint8_t* rgbx
     if (n_updated_out) *n_updated_out = 0;
     if (n_colored_out) *n_colored_out = 0;
     int rc;
-    if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_integrate_color"))) return rc;
-    if ((rc = tsdf_check_color(c, "icp_tsdf_integrate_color"))) return rc;
+    const bool hcol = tsdf_hashed_color(c);          // (a hashed volume without colours is refused as every dense-box call is)
+    if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_integrate_color", hcol))) return rc;
+    if (!hcol && (rc = tsdf_check_color(c, "icp_tsdf_integrate_color"))) return rc;
     if (!depth || !rgbx) { c->err = "icp_tsdf_integrate_color: null depth or colour frame"; return ICP_ERR_INVALID_ARG; }
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream))) return rc;
-    if ((rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>(), true))) return rc;
+    if (hcol) rc = htsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>(), "icp_tsdf_integrate_color", true);
+    else rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>(), true);
+    if (rc) return rc;
     int n[2] = {0, 0};
     if ((rc = read_count(c, c->tsdf_cnt.p, n, 2))) return rc;
     if (n_updated_out) *n_updated_out = n[0];

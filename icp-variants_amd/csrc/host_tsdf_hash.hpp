@@ -1,7 +1,8 @@
 // host_tsdf_hash.hpp -- the hashed storage of the TSDF volume: icp_tsdf_create_hashed / reserve_blocks / allocate_blocks / upload_hashed,
 // icp_get_tsdf_hashed, and what host_tsdf.hpp's and host_sdf.hpp's entry points call when the context's volume is hashed (the touch with
 // its room rule in front of an integrate, the growth, reset and release).  Kernels: dev_tsdf_hash.hpp.  Contract: include/icp_hip.h,
-// DESIGN.md section 6x.  Part of icp_hip.hip (included from there, after host_tsdf.hpp, which declares what it calls, and before host_sdf.hpp).
+// DESIGN.md section 6x; the colour pool of a coloured hashed volume (icp_tsdf_create_color_hashed, icp_get_tsdf_color_hashed,
+// icp_tsdf_upload_color_hashed; kernels: dev_tsdf_hash_color.hpp): section 6zb.  Part of icp_hip.hip (included from there, after host_tsdf.hpp, which declares what it calls, and before host_sdf.hpp).
 namespace {
 constexpr int HT_MAX_POOL_LOG2 = 22;                // 2^22 blocks of 4 KiB: 16 GiB
 constexpr int HT_MAX_STEPS = 1024;                  // samples along a ray's truncation band: 2 truncation / voxel_size
@@ -16,7 +17,14 @@ int htsdf_check(icp_ctx* c, const char* who) {
     if (!c->tsdf_hashed) { c->err = std::string(who) + ": the volume is dense (icp_tsdf_create): use icp_tsdf_download / icp_tsdf_upload"; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;
 }
-struct HtBufs { DevBuf keys, vals, pool, pkey; };
+// the calls that need the colour pool
+int htsdf_check_color(icp_ctx* c, const char* who) {
+    int rc;
+    if ((rc = htsdf_check(c, who))) return rc;
+    if (!c->th_color) { c->err = std::string(who) + ": the hashed volume has no colours (icp_tsdf_create_color_hashed)"; return ICP_ERR_INVALID_ARG; }
+    return ICP_OK;
+}
+struct HtBufs { DevBuf keys, vals, pool, pkey, cpool; };
 // a cleared table of 2^(pool_log2 + 1) slots and a cleared pool of 2^pool_log2 blocks (enqueued)
 int htsdf_alloc(icp_ctx* c, int pool_log2, HtBufs& b) {
     const size_t blocks = (size_t)1 << pool_log2, slots = 2 * blocks;
@@ -29,10 +37,15 @@ int htsdf_alloc(icp_ctx* c, int pool_log2, HtBufs& b) {
     HIPCK(c, hipMemsetAsync(b.vals.p, 0xFF, slots * 4, c->stream));      // HT_NONE
     HIPCK(c, hipMemsetAsync(b.pool.p, 0, blocks * 4096, c->stream));      // tsdf 0, weight 0
     HIPCK(c, hipMemsetAsync(b.pkey.p, 0xFF, blocks * 8, c->stream));
+    if (c->th_color) {                                 // the colour pool of a coloured volume: (0, 0, 0, 0), uncoloured
+        if ((rc = ensure(c, b.cpool, blocks * 8192))) return rc;
+        HIPCK(c, hipMemsetAsync(b.cpool.p, 0, blocks * 8192, c->stream));
+    }
     return ICP_OK;
 }
 void htsdf_adopt(icp_ctx* c, int pool_log2, HtBufs& b) {
     c->th_keys = std::move(b.keys); c->th_vals = std::move(b.vals); c->th_pool = std::move(b.pool); c->th_pkey = std::move(b.pkey);
+    if (c->th_color) c->th_cpool = std::move(b.cpool);
     c->th_log2cap = pool_log2 + 1; c->th_pool_cap = 1 << pool_log2;
 }
 HtTable htsdf_table(const icp_ctx* c) {
@@ -73,6 +86,7 @@ int htsdf_regrow(icp_ctx* c, int pool_log2, int n_live) {
     if (n_live > 0) {
         HIPCK(c, hipMemcpyAsync(b.pool.p, c->th_pool.p, (size_t)n_live * 4096, hipMemcpyDeviceToDevice, c->stream));
         HIPCK(c, hipMemcpyAsync(b.pkey.p, c->th_pkey.p, (size_t)n_live * 8, hipMemcpyDeviceToDevice, c->stream));
+        if (c->th_color) HIPCK(c, hipMemcpyAsync(b.cpool.p, c->th_cpool.p, (size_t)n_live * 8192, hipMemcpyDeviceToDevice, c->stream));
     }
     if ((rc = htsdf_rehash_launch(c, n_live, b.keys.as<unsigned long long>(), b.vals.as<int>(), (const unsigned long long*)b.pkey.as<unsigned long long>(), pool_log2 + 1))) return rc;
     if ((rc = htsdf_set_counters(c, n_live))) return rc;      // (waits)
@@ -113,8 +127,9 @@ int htsdf_claim(icp_ctx* c, Launch launch, const char* who, long long* oor_out) 
     }
 }
 // tsdf_integrate_slot for a hashed volume: the touch under the room rule (one host wait, more when the volume grows), then the integrate
-// over the pool, enqueued; d_count (optional): zeroed, then the number of voxels written.
-int htsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count, const char* who) {
+// over the pool, enqueued; d_count (optional): zeroed, then the number of voxels written.  color (a coloured volume only): the slot's colour
+// frame goes into the colour pool as well, k_htsdf_integrate_color in place of k_htsdf_integrate (d_count[1]: the voxels coloured).
+int htsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count, const char* who, bool color) {
     const icp_tsdf_options& o = c->tsdf_opt;
     TsdfMat m; memset(&m, 0, sizeof(m));
     invert_extrinsics(pose, m.m);
@@ -132,9 +147,11 @@ int htsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, cons
     };
     if ((rc = htsdf_claim(c, touch, who, &oor))) return rc;
     c->th_oor += oor;
-    if (d_count) HIPCK(c, hipMemsetAsync(d_count, 0, 4, c->stream));
+    if (d_count) HIPCK(c, hipMemsetAsync(d_count, 0, color ? 8 : 4, c->stream));
     if (c->th_nblk > 0) {
-        hipLaunchKernelGGL(k_htsdf_integrate, dim3(c->th_nblk), dim3(512), 0, c->stream, htsdf_view(c), tsdf_cam(cam), m, depth, d_count);
+        if (color) hipLaunchKernelGGL(k_htsdf_integrate_color, dim3(c->th_nblk), dim3(512), 0, c->stream, htsdf_view(c), tsdf_cam(cam), m, depth, d_count,
+                                      (const uint32_t*)(depth + (size_t)cam.width * cam.height), c->th_cpool.as<float4>(), d_count ? d_count + 1 : nullptr);
+        else hipLaunchKernelGGL(k_htsdf_integrate, dim3(c->th_nblk), dim3(512), 0, c->stream, htsdf_view(c), tsdf_cam(cam), m, depth, d_count);
         HIPCK(c, hipGetLastError());
     }
     return ICP_OK;
@@ -146,14 +163,15 @@ int htsdf_reset(icp_ctx* c) {
     HIPCK(c, hipMemsetAsync(c->th_vals.p, 0xFF, slots * 4, c->stream));
     HIPCK(c, hipMemsetAsync(c->th_pool.p, 0, blocks * 4096, c->stream));
     HIPCK(c, hipMemsetAsync(c->th_pkey.p, 0xFF, blocks * 8, c->stream));
+    if (c->th_color) HIPCK(c, hipMemsetAsync(c->th_cpool.p, 0, blocks * 8192, c->stream));
     HIPCK(c, hipMemsetAsync(c->th_ctr.p, 0, HT_NCTR * 4, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     c->th_nblk = 0; c->th_unplaced = 0; c->th_oor = 0; c->te_held = 0;
     return ICP_OK;
 }
 void htsdf_drop(icp_ctx* c) {
-    for (DevBuf* d : {&c->th_keys, &c->th_vals, &c->th_pool, &c->th_pkey, &c->th_ctr, &c->te_work, &c->te_out_pool, &c->te_out_key}) release(*d);
-    c->te_held = 0;
+    for (DevBuf* d : {&c->th_keys, &c->th_vals, &c->th_pool, &c->th_pkey, &c->th_ctr, &c->te_work, &c->te_out_pool, &c->te_out_key, &c->th_cpool, &c->te_out_cpool}) release(*d);
+    c->te_held = 0; c->th_color = false;
     c->tsdf_hashed = false; c->th_log2cap = 0; c->th_pool_cap = 0; c->th_nblk = 0;
 }
 // block coordinates from the caller: every one storable, or a message
@@ -175,7 +193,9 @@ int htsdf_allocate(icp_ctx* c, int32_t n, const int32_t* coords, DevBuf& d_coord
 }
 // A save path: n blocks of a pool (this volume's, or the outbox of an evict) to the host SORTED BY KEY -- the keys first, sorted on the host;
 // then the blocks, a slab of at most 4096 (16 MiB) at a time.  Any output may be null.
-int htsdf_download_sorted(icp_ctx* c, int n, const void* d_pkey, const void* d_pool, int32_t* coords_out, float* tsdf_out, float* weight_out) {
+// d_cpool with rgb_out (n x 512 x 3) and cweight_out (n x 512): the colour pool's blocks in the same order, a slab of at most 2048 (16 MiB).
+int htsdf_download_sorted(icp_ctx* c, int n, const void* d_pkey, const void* d_pool, int32_t* coords_out, float* tsdf_out, float* weight_out,
+                          const void* d_cpool = nullptr, float* rgb_out = nullptr, float* cweight_out = nullptr) {
     HIPCK(c, hipStreamSynchronize(c->stream));
     std::vector<unsigned long long> keys((size_t)n);
     HIPCK(c, hipMemcpy(keys.data(), d_pkey, (size_t)n * 8, hipMemcpyDeviceToHost));
@@ -187,9 +207,21 @@ int htsdf_download_sorted(icp_ctx* c, int n, const void* d_pkey, const void* d_p
         place[(size_t)order[(size_t)e].second] = e;
         if (coords_out) for (int a = 0; a < 3; a++) coords_out[3 * (size_t)e + a] = (int32_t)((order[(size_t)e].first >> (21 * a)) & 0x1FFFFFull) - HM_RANGE;
     }
+    const int slab = 4096, cslab = 2048;              // 16 MiB either way: 4 KiB of geometry, 8 KiB of colour per block
+    std::vector<float> h((size_t)(n < cslab ? n : cslab) * 2048);
+    if (d_cpool && (rgb_out || cweight_out)) {
+        for (int at = 0; at < n; at += cslab) {
+            const int m = n - at < cslab ? n - at : cslab;
+            HIPCK(c, hipMemcpy(h.data(), (const char*)d_cpool + (size_t)at * 8192, (size_t)m * 8192, hipMemcpyDeviceToHost));
+            for (int i = 0; i < m; i++) {
+                const size_t e = (size_t)place[(size_t)(at + i)];
+                const float* src = h.data() + (size_t)i * 2048;
+                if (rgb_out) for (int q = 0; q < 512; q++) for (int a = 0; a < 3; a++) rgb_out[(e * 512 + q) * 3 + a] = src[4 * q + a];
+                if (cweight_out) for (int q = 0; q < 512; q++) cweight_out[e * 512 + q] = src[4 * q + 3];
+            }
+        }
+    }
     if (!tsdf_out && !weight_out) return ICP_OK;
-    const int slab = 4096;
-    std::vector<float> h((size_t)(n < slab ? n : slab) * 1024);
     for (int at = 0; at < n; at += slab) {
         const int m = n - at < slab ? n - at : slab;
         HIPCK(c, hipMemcpy(h.data(), (const char*)d_pool + (size_t)at * 4096, (size_t)m * 4096, hipMemcpyDeviceToHost));
@@ -232,11 +264,53 @@ int htsdf_place_blocks(icp_ctx* c, int32_t n, const DevBuf& d_coords, const floa
     }
     return ICP_OK;
 }
+// htsdf_place_blocks for the colour pool: rgb n x 512 x 3 and cweight n x 512, a slab of at most 2048 (16 MiB) at a time.
+int htsdf_place_colors(icp_ctx* c, int32_t n, const DevBuf& d_coords, const float* rgb, const float* cweight) {
+    int rc;
+    DevBuf d_in;
+    const int slab = 2048;
+    const int m_max = n < slab ? n : slab;
+    std::vector<float4> h((size_t)m_max * 512);
+    if ((rc = ensure(c, d_in, (size_t)m_max * 8192))) return rc;
+    for (int at = 0; at < n; at += slab) {
+        const int m = n - at < slab ? n - at : slab;
+        for (size_t q = 0; q < (size_t)m * 512; q++) {
+            const float* s3 = rgb + ((size_t)at * 512 + q) * 3;
+            h[q] = make_float4(s3[0], s3[1], s3[2], cweight[(size_t)at * 512 + q]);
+        }
+        HIPCK(c, hipMemcpyAsync(d_in.p, h.data(), (size_t)m * 8192, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_htsdf_place_color, dim3(m), dim3(512), 0, c->stream, htsdf_view(c), c->th_cpool.as<float4>(), (const int*)(d_coords.as<int>() + 3 * (size_t)at),
+                           (const float4*)d_in.as<float4>());
+        HIPCK(c, hipGetLastError());
+        HIPCK(c, hipStreamSynchronize(c->stream));      // (the host block and d_in are reused by the next slab)
+    }
+    return ICP_OK;
+}
+// icp_tsdf_create_hashed and icp_tsdf_create_color_hashed: the second adds the colour pool
+int htsdf_create(icp_ctx* c, const icp_tsdf_options* opt, int32_t block_capacity, bool color, const char* who);
+int htsdf_get(icp_ctx* c, icp_tsdf_hashed_info* info_out, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out, float* rgb_out, float* cweight_out,
+              const char* who);
+int htsdf_upload(icp_ctx* c, int32_t n, const int32_t* coords, const float* tsdf, const float* weight, const float* rgb, const float* cweight, const char* who);
 }  // namespace
 
 int icp_tsdf_create_hashed(icp_ctx* c, const icp_tsdf_options* opt, int32_t block_capacity) {
     if (!c) return ICP_ERR_INVALID_ARG;
-    const char* who = "icp_tsdf_create_hashed";
+    return htsdf_create(c, opt, block_capacity, false, "icp_tsdf_create_hashed");
+}
+int icp_tsdf_create_color_hashed(icp_ctx* c, const icp_tsdf_options* opt, int32_t block_capacity) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    return htsdf_create(c, opt, block_capacity, true, "icp_tsdf_create_color_hashed");
+}
+int icp_tsdf_hashed_has_color(icp_ctx* c, int32_t* has_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = htsdf_check(c, "icp_tsdf_hashed_has_color"))) return rc;
+    if (has_out) *has_out = c->th_color ? 1 : 0;
+    return ICP_OK;
+}
+
+namespace {
+int htsdf_create(icp_ctx* c, const icp_tsdf_options* opt, int32_t block_capacity, bool color, const char* who) {
     if (!opt) { c->err = std::string(who) + ": null options"; return ICP_ERR_INVALID_ARG; }
     icp_tsdf_options o = *opt;
     o.dims[0] = o.dims[1] = o.dims[2] = 2;             // (ignored: a hashed volume has no extent)
@@ -250,6 +324,8 @@ int icp_tsdf_create_hashed(icp_ctx* c, const icp_tsdf_options* opt, int32_t bloc
     o.dims[0] = o.dims[1] = o.dims[2] = 0;
     if (o.ray_step == 0.f) o.ray_step = o.truncation / 2.f;
     c->tsdf_opt = o;
+    c->th_color = color;                               // (htsdf_alloc and htsdf_adopt look at it; cleared again if the allocation fails)
+    struct Undo { icp_ctx* c; bool armed; ~Undo() { if (armed) { release(c->th_cpool); c->th_color = false; } } } undo{c, true};
     HtBufs b;
     const int l = ht_log2_for(block_capacity);
     if ((rc = htsdf_alloc(c, l, b))) return rc;
@@ -260,8 +336,10 @@ int icp_tsdf_create_hashed(icp_ctx* c, const icp_tsdf_options* opt, int32_t bloc
     htsdf_adopt(c, l, b);
     c->th_nblk = 0; c->th_grown = 0; c->th_unplaced = 0; c->th_oor = 0;
     c->tsdf_hashed = true; c->tsdf_on = true;
+    undo.armed = false;
     return guard.done();
 }
+}  // namespace
 
 int icp_tsdf_reserve_blocks(icp_ctx* c, int32_t block_capacity) {
     if (!c) return ICP_ERR_INVALID_ARG;
@@ -295,15 +373,27 @@ int icp_tsdf_allocate_blocks(icp_ctx* c, int32_t n, const int32_t* coords) {
 
 int icp_get_tsdf_hashed(icp_ctx* c, icp_tsdf_hashed_info* info_out, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out) {
     if (!c) return ICP_ERR_INVALID_ARG;
-    const char* who = "icp_get_tsdf_hashed";
     int rc;
-    if ((rc = htsdf_check(c, who))) return rc;
+    if ((rc = htsdf_check(c, "icp_get_tsdf_hashed"))) return rc;
+    return htsdf_get(c, info_out, max_blocks, coords_out, tsdf_out, weight_out, nullptr, nullptr, "icp_get_tsdf_hashed");
+}
+int icp_get_tsdf_color_hashed(icp_ctx* c, icp_tsdf_hashed_info* info_out, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out, float* rgb_out,
+                              float* cweight_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = htsdf_check_color(c, "icp_get_tsdf_color_hashed"))) return rc;
+    return htsdf_get(c, info_out, max_blocks, coords_out, tsdf_out, weight_out, rgb_out, cweight_out, "icp_get_tsdf_color_hashed");
+}
+namespace {
+int htsdf_get(icp_ctx* c, icp_tsdf_hashed_info* info_out, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out, float* rgb_out, float* cweight_out,
+              const char* who) {
+    int rc;
     const int n = c->th_nblk;
     if (info_out) {
         memset(info_out, 0, sizeof(*info_out));
         info_out->n_blocks = n; info_out->capacity = c->th_pool_cap; info_out->n_grown = c->th_grown; info_out->n_unplaced = c->th_unplaced; info_out->n_out_of_range = c->th_oor;
     }
-    if (!coords_out && !tsdf_out && !weight_out) return ICP_OK;
+    if (!coords_out && !tsdf_out && !weight_out && !rgb_out && !cweight_out) return ICP_OK;
     if (max_blocks < n) {
         char buf[160];
         snprintf(buf, sizeof(buf), "%s: max_blocks %d is below the %d allocated blocks", who, max_blocks, n);
@@ -311,8 +401,9 @@ int icp_get_tsdf_hashed(icp_ctx* c, icp_tsdf_hashed_info* info_out, int32_t max_
     }
     if (n == 0) return ICP_OK;
     if ((rc = set_device(c))) return rc;
-    return htsdf_download_sorted(c, n, c->th_pkey.p, c->th_pool.p, coords_out, tsdf_out, weight_out);
+    return htsdf_download_sorted(c, n, c->th_pkey.p, c->th_pool.p, coords_out, tsdf_out, weight_out, c->th_color ? c->th_cpool.p : nullptr, rgb_out, cweight_out);
 }
+}  // namespace
 
 int icp_tsdf_upload_hashed(icp_ctx* c, int32_t n, const int32_t* coords, const float* tsdf, const float* weight) {
     if (!c) return ICP_ERR_INVALID_ARG;
@@ -320,6 +411,19 @@ int icp_tsdf_upload_hashed(icp_ctx* c, int32_t n, const int32_t* coords, const f
     int rc;
     if ((rc = htsdf_check(c, who))) return rc;
     if (n < 0 || (n > 0 && (!coords || !tsdf || !weight))) { c->err = std::string(who) + ": bad argument (n >= 0, coords, tsdf, weight)"; return ICP_ERR_INVALID_ARG; }
+    return htsdf_upload(c, n, coords, tsdf, weight, nullptr, nullptr, who);      // (a coloured volume: every block uncoloured)
+}
+int icp_tsdf_upload_color_hashed(icp_ctx* c, int32_t n, const int32_t* coords, const float* tsdf, const float* weight, const float* rgb, const float* cweight) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    const char* who = "icp_tsdf_upload_color_hashed";
+    int rc;
+    if ((rc = htsdf_check_color(c, who))) return rc;
+    if (n < 0 || (n > 0 && (!coords || !tsdf || !weight || !rgb || !cweight))) { c->err = std::string(who) + ": bad argument (n >= 0, coords, tsdf, weight, rgb, cweight)"; return ICP_ERR_INVALID_ARG; }
+    return htsdf_upload(c, n, coords, tsdf, weight, rgb, cweight, who);
+}
+namespace {
+int htsdf_upload(icp_ctx* c, int32_t n, const int32_t* coords, const float* tsdf, const float* weight, const float* rgb, const float* cweight, const char* who) {
+    int rc;
     if ((rc = htsdf_check_coords(c, n, coords, who))) return rc;
     if (!htsdf_keys_distinct(n, coords)) { c->err = std::string(who) + ": a block coordinate occurs twice"; return ICP_ERR_INVALID_ARG; }
     const int l = ht_log2_for(n);
@@ -334,9 +438,11 @@ int icp_tsdf_upload_hashed(icp_ctx* c, int32_t n, const int32_t* coords, const f
         DevBuf d_coords;
         if ((rc = htsdf_allocate(c, n, coords, d_coords, who))) return rc;
         if ((rc = htsdf_place_blocks(c, n, d_coords, tsdf, weight))) return rc;
+        if (rgb && (rc = htsdf_place_colors(c, n, d_coords, rgb, cweight))) return rc;
     }
     return guard.done();
 }
+}  // namespace
 
 // Not part of icp_hip.h (tests/test_gpu_htsdf.py): lowers the pool size at which this context's hashed volume refuses to grow from 2^22 blocks
 // to 2^log2_blocks, so that the refusal and the restoring of the table can be tested without 16 GiB.
@@ -378,5 +484,35 @@ extern "C" int icp_debug_htsdf_time(icp_ctx* c, const float* depth, const icp_de
     HIPCK(c, hipEventElapsedTime(integrate_ms_out, c->events[1], c->events[2]));
     HIPCK(c, hipMemsetAsync(c->th_ctr.as<int>() + HT_UNPLACED, 0, 8, c->stream));      // (the timed touch counted its samples out of range again)
     HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+
+// Not part of icp_hip.h (tools/time_htsdf_color.py): icp_debug_htsdf_time's integrate figure for ONE k_htsdf_integrate_color launch on a
+// coloured hashed volume, the frames staged and their blocks allocated outside the bracket.
+extern "C" int icp_debug_htsdf_color_time(icp_ctx* c, const float* depth, const uint8_t* rgbx, const icp_depth_camera* cam, const float pose[16], float* integrate_ms_out) {
+    if (!c || !integrate_ms_out || !depth || !rgbx) return ICP_ERR_INVALID_ARG;
+    const char* who = "icp_debug_htsdf_color_time";
+    int rc;
+    if ((rc = htsdf_check_color(c, who))) return rc;
+    if ((rc = tsdf_check_call(c, cam, pose, who, true))) return rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ensure_events(c, 2))) return rc;
+    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = htsdf_integrate_slot(c, 0, *cam, pose, nullptr, who, true))) return rc;      // (warm; allocates)
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    *integrate_ms_out = 0.f;
+    if (c->th_nblk > 0) {
+        TsdfMat m; memset(&m, 0, sizeof(m));
+        invert_extrinsics(pose, m.m);
+        const float* d = c->depth_dev[0].as<float>();
+        HIPCK(c, hipEventRecord(c->events[0], c->stream));
+        hipLaunchKernelGGL(k_htsdf_integrate_color, dim3(c->th_nblk), dim3(512), 0, c->stream, htsdf_view(c), tsdf_cam(*cam), m, d, c->tsdf_cnt.as<int>(),
+                           (const uint32_t*)(d + (size_t)cam->width * cam->height), c->th_cpool.as<float4>(), c->tsdf_cnt.as<int>() + 1);
+        HIPCK(c, hipEventRecord(c->events[1], c->stream));
+        HIPCK(c, hipGetLastError());
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        HIPCK(c, hipEventElapsedTime(integrate_ms_out, c->events[0], c->events[1]));
+    }
     return guard.done();
 }

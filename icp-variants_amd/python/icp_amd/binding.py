@@ -109,7 +109,8 @@ def tsdf_view_reach(cam, options):
     """The farthest a block that a frame of `cam` can touch, update or sample has its centre from the camera, with a block diagonal of
     slack: (max_depth + truncation) * sqrt(1 + a_max^2 + b_max^2) + 8 * voxel_size * sqrt(3), with
     a_max = max(|0 - cx|, |width - 1 - cx|) / fx and b_max likewise with cy, fy and the height.  `options`: an IcpTsdfOptions, or a dict of
-    `tsdf_options`' arguments.  Infinite when max_depth is."""
+    `tsdf_options`' arguments.  Infinite when max_depth is.  A coloured hashed volume has the same reach: its
+    colour is read and written only in cells and voxels the geometry touches."""
     o = options if isinstance(options, IcpTsdfOptions) else tsdf_options(**{k: v for k, v in dict(options).items() if k != "dims"})
     a = max(abs(0.0 - cam.cx), abs(cam.width - 1.0 - cam.cx)) / abs(cam.fx)
     b = max(abs(0.0 - cam.cy), abs(cam.height - 1.0 - cam.cy)) / abs(cam.fy)
@@ -134,6 +135,26 @@ def tsdf_blocks_to_dense(coords, tsdf, weight, lo, dims):
         T[z0 + zs.start:z0 + zs.stop, y0 + ys.start:y0 + ys.stop, x0 + xs.start:x0 + xs.stop] = t[zs, ys, xs]
         W[z0 + zs.start:z0 + zs.stop, y0 + ys.start:y0 + ys.stop, x0 + xs.start:x0 + xs.stop] = w[zs, ys, xs]
     return T, W
+
+
+def tsdf_block_colors_to_dense(coords, rgb, cweight, lo, dims):
+    """The colours of a coloured hashed volume's blocks (`Context.tsdf_blocks(colors=True)`) as the two dense arrays `Context.tsdf_color_upload`
+    takes, rgb (nz, ny, nx, 3) and weight (nz, ny, nx), by `tsdf_blocks_to_dense`'s rule: dense voxel (0, 0, 0) is global voxel `lo`, voxels
+    no block covers are (0, 0, 0, 0), uncoloured, and what lies outside `dims` = (nx, ny, nz) is dropped."""
+    lo = np.asarray(lo, np.int64).reshape(3); nx, ny, nz = (int(d) for d in dims)
+    coords = np.asarray(coords, np.int64).reshape(-1, 3)
+    rgb = np.asarray(rgb, np.float32).reshape(-1, 8, 8, 8, 3); cweight = np.asarray(cweight, np.float32).reshape(-1, 8, 8, 8)
+    if not (len(coords) == len(rgb) == len(cweight)):
+        raise ValueError("coords (B, 3), rgb (B, 8, 8, 8, 3) and cweight (B, 8, 8, 8) must agree in B")
+    Cd = np.zeros((nz, ny, nx, 3), np.float32); W = np.zeros((nz, ny, nx), np.float32)
+    for b, c, w in zip(coords, rgb, cweight):
+        x0, y0, z0 = (int(v) for v in b * 8 - lo)
+        xs, ys, zs = (slice(max(0, -a), min(8, n - a)) for a, n in ((x0, nx), (y0, ny), (z0, nz)))
+        if xs.start >= xs.stop or ys.start >= ys.stop or zs.start >= zs.stop:
+            continue
+        Cd[z0 + zs.start:z0 + zs.stop, y0 + ys.start:y0 + ys.stop, x0 + xs.start:x0 + xs.stop] = c[zs, ys, xs]
+        W[z0 + zs.start:z0 + zs.stop, y0 + ys.start:y0 + ys.stop, x0 + xs.start:x0 + xs.stop] = w[zs, ys, xs]
+    return Cd, W
 
 
 class IcpSdfOptions(C.Structure):
@@ -437,6 +458,8 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_create_hashed", "icp_tsdf_reserve_blocks", "icp_tsdf_allocate_blocks", "icp_get_tsdf_hashed", "icp_tsdf_upload_hashed",
            "icp_tsdf_mesh_hashed", "icp_tsdf_raycast_hashed", "icp_set_target_tsdf_hashed", "icp_track_depth_model_hashed",
            "icp_tsdf_evict_blocks", "icp_tsdf_evicted_blocks", "icp_tsdf_insert_blocks",
+           "icp_tsdf_create_color_hashed", "icp_tsdf_hashed_has_color", "icp_get_tsdf_color_hashed", "icp_tsdf_upload_color_hashed",
+           "icp_tsdf_evicted_blocks_color", "icp_tsdf_insert_blocks_color",
            "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
            "icp_track_depth_sdf_color",
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
@@ -979,15 +1002,24 @@ class Context:
         if color:
             self.tsdf_color_create()
 
-    def tsdf_create_hashed(self, options=None, block_capacity=1 << 12, **kw):
+    def tsdf_create_hashed(self, options=None, block_capacity=1 << 12, color=False, **kw):
         """icp_tsdf_create_hashed: the context's TSDF volume stored in 8 x 8 x 8 voxel blocks behind a hash table, without an extent
         (DESIGN.md section 6x); `tsdf_options`' arguments without dims (origin, voxel_size, truncation, ...).  block_capacity: blocks of 4 KiB
         the pool holds before it grows (it doubles on the device when a frame needs more).  Replaces any volume, dense or hashed.
-        `tsdf_integrate`, `tsdf_sample`, `tsdf_sdf_system`, `tsdf_align_depth` and `track_depth_sdf` work on it as on a dense one."""
+        `tsdf_integrate`, `tsdf_sample`, `tsdf_sdf_system`, `tsdf_align_depth` and `track_depth_sdf` work on it as on a dense one.
+        color: icp_tsdf_create_color_hashed, the blocks with colours (8 KiB more per block); `tsdf_integrate` with
+        rgbx, `tsdf_sample_color` and the calls above with color_weight > 0 then work on it as on a dense coloured volume."""
         o = options if options is not None else tsdf_options(**kw)
-        self._ck(self.lib.icp_tsdf_create_hashed(self.h, C.byref(o), C.c_int32(block_capacity)))
+        create = self.lib.icp_tsdf_create_color_hashed if color else self.lib.icp_tsdf_create_hashed
+        self._ck(create(self.h, C.byref(o), C.c_int32(block_capacity)))
         self._tsdf_dims = None
         self.tsdf_hashed_options = o
+
+    def tsdf_has_color(self):
+        """icp_tsdf_hashed_has_color: whether the context's hashed volume holds colours."""
+        has = C.c_int32(0)
+        self._ck(self.lib.icp_tsdf_hashed_has_color(self.h, C.byref(has)))
+        return bool(has.value)
 
     def tsdf_reserve_blocks(self, block_capacity):
         """icp_tsdf_reserve_blocks: grows the hashed volume's table and pool ahead of time (smaller or equal: nothing happens)."""
@@ -998,29 +1030,60 @@ class Context:
         cc = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3)
         self._ck(self.lib.icp_tsdf_allocate_blocks(self.h, C.c_int32(len(cc)), _ptr(cc)))
 
-    def tsdf_blocks(self):
+    def tsdf_blocks(self, colors=False):
         """icp_get_tsdf_hashed: (info dict(n_blocks, capacity, n_grown, n_unplaced, n_out_of_range), coords (B, 3) int32, tsdf (B, 8, 8, 8),
-        weight (B, 8, 8, 8) float32, indexed [z, y, x]) of the allocated blocks, sorted by key (z, then y, then x of the block)."""
+        weight (B, 8, 8, 8) float32, indexed [z, y, x]) of the allocated blocks, sorted by key (z, then y, then x of the block).
+        colors: icp_get_tsdf_color_hashed, with rgb (B, 8, 8, 8, 3) and cweight (B, 8, 8, 8) of a coloured hashed volume behind them."""
         info = IcpTsdfHashedInfo()
         self._ck(self.lib.icp_get_tsdf_hashed(self.h, C.byref(info), C.c_int32(0), None, None, None))
         n = info.n_blocks
         coords = np.empty((n, 3), np.int32); t = np.empty((n, 8, 8, 8), np.float32); w = np.empty((n, 8, 8, 8), np.float32)
+        if colors:
+            rgb = np.empty((n, 8, 8, 8, 3), np.float32); cw = np.empty((n, 8, 8, 8), np.float32)
+            self._ck(self.lib.icp_get_tsdf_color_hashed(self.h, C.byref(info), C.c_int32(n), _ptr(coords), _ptr(t), _ptr(w), _ptr(rgb), _ptr(cw)))
+            return {k: getattr(info, k) for k, _ in info._fields_}, coords, t, w, rgb, cw
         self._ck(self.lib.icp_get_tsdf_hashed(self.h, C.byref(info), C.c_int32(n), _ptr(coords), _ptr(t), _ptr(w)))
         return {k: getattr(info, k) for k, _ in info._fields_}, coords, t, w
 
-    def tsdf_upload_blocks(self, coords, tsdf, weight):
-        """icp_tsdf_upload_hashed: replaces the hashed volume's state by the blocks `coords` (B, 3) with `tsdf` and `weight` (B, 8, 8, 8)."""
+    @staticmethod
+    def _blocks_in(coords, tsdf, weight, rgb, cweight):
         cc = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3)
         t = _f32(tsdf).reshape(-1, 8, 8, 8); w = _f32(weight).reshape(-1, 8, 8, 8)
         if not (len(cc) == len(t) == len(w)):
             raise ValueError("coords (B, 3), tsdf and weight (B, 8, 8, 8) must agree in B")
-        self._ck(self.lib.icp_tsdf_upload_hashed(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(t), _ptr(w)))
+        if (rgb is None) != (cweight is None):
+            raise ValueError("rgb and cweight go together")
+        if rgb is None:
+            return cc, t, w, None, None
+        c = _f32(rgb).reshape(-1, 8, 8, 8, 3); cw = _f32(cweight).reshape(-1, 8, 8, 8)
+        if not (len(cc) == len(c) == len(cw)):
+            raise ValueError("coords (B, 3), rgb (B, 8, 8, 8, 3) and cweight (B, 8, 8, 8) must agree in B")
+        return cc, t, w, c, cw
+
+    def tsdf_upload_blocks(self, coords, tsdf, weight, rgb=None, cweight=None):
+        """icp_tsdf_upload_hashed: replaces the hashed volume's state by the blocks `coords` (B, 3) with `tsdf` and `weight` (B, 8, 8, 8).
+        rgb (B, 8, 8, 8, 3) and cweight (B, 8, 8, 8): icp_tsdf_upload_color_hashed, the blocks with their colours (a coloured volume);
+        without them a coloured volume's blocks are left uncoloured."""
+        cc, t, w, c, cw = self._blocks_in(coords, tsdf, weight, rgb, cweight)
+        if c is not None:
+            self._ck(self.lib.icp_tsdf_upload_color_hashed(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(t), _ptr(w), _ptr(c), _ptr(cw)))
+        else:
+            self._ck(self.lib.icp_tsdf_upload_hashed(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(t), _ptr(w)))
 
     def tsdf_evict_blocks(self, centre, radius, hold=True):
         """icp_tsdf_evict_blocks: every block of the hashed volume whose centre lies beyond `radius` metres of `centre` leaves the device
         (DESIGN.md section 6za).  Returns (info dict(n_evicted, n_blocks, n_moved, capacity, n_held, n_inserted, n_present, n_grown),
         coords (E, 3) int32, tsdf (E, 8, 8, 8), weight (E, 8, 8, 8)): the evicted blocks sorted by key (icp_tsdf_evicted_blocks), for the
-        caller to keep; with hold=False they are forgotten and the arrays are empty."""
+        caller to keep; with hold=False they are forgotten and the arrays are empty.  On a coloured hashed volume this returns the outbox's
+        geometry; `tsdf_evict_blocks_color` returns the colours too."""
+        return self._evict_blocks(centre, radius, hold, False)
+
+    def tsdf_evict_blocks_color(self, centre, radius, hold=True):
+        """`tsdf_evict_blocks` on a coloured hashed volume with the colours of the evicted blocks (icp_tsdf_evicted_blocks_color): returns
+        (info, coords, tsdf, weight, rgb (E, 8, 8, 8, 3), cweight (E, 8, 8, 8)).  A volume without colours is a ValueError."""
+        return self._evict_blocks(centre, radius, hold, True)
+
+    def _evict_blocks(self, centre, radius, hold, colors):
         ce = _f32(centre).reshape(-1)
         if ce.size != 3:
             raise ValueError("centre is three numbers")
@@ -1028,19 +1091,37 @@ class Context:
         self._ck(self.lib.icp_tsdf_evict_blocks(self.h, _ptr(ce), C.c_float(radius), C.c_int32(1 if hold else 0), C.byref(info)))
         n = info.n_held
         coords = np.empty((n, 3), np.int32); t = np.empty((n, 8, 8, 8), np.float32); w = np.empty((n, 8, 8, 8), np.float32)
+        if colors:
+            if not self.tsdf_has_color():
+                raise ValueError("tsdf_evict_blocks_color needs a coloured hashed volume (tsdf_create_hashed(color=True))")
+            rgb = np.zeros((n, 8, 8, 8, 3), np.float32); cw = np.zeros((n, 8, 8, 8), np.float32)
+            if n:
+                self._ck(self.lib.icp_tsdf_evicted_blocks_color(self.h, C.c_int32(n), _ptr(coords), _ptr(t), _ptr(w), _ptr(rgb), _ptr(cw)))
+            return {k: getattr(info, k) for k, _ in info._fields_}, coords, t, w, rgb, cw
         if n:
             self._ck(self.lib.icp_tsdf_evicted_blocks(self.h, C.c_int32(n), _ptr(coords), _ptr(t), _ptr(w)))
         return {k: getattr(info, k) for k, _ in info._fields_}, coords, t, w
 
     def tsdf_insert_blocks(self, coords, tsdf, weight):
         """icp_tsdf_insert_blocks: ADDS the blocks `coords` (B, 3) with `tsdf` and `weight` (B, 8, 8, 8) to the hashed volume's state
-        (`tsdf_upload_blocks` replaces it); a block that is resident already refuses the call.  Returns the info dict of `tsdf_evict_blocks`."""
-        cc = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3)
-        t = _f32(tsdf).reshape(-1, 8, 8, 8); w = _f32(weight).reshape(-1, 8, 8, 8)
-        if not (len(cc) == len(t) == len(w)):
-            raise ValueError("coords (B, 3), tsdf and weight (B, 8, 8, 8) must agree in B")
+        (`tsdf_upload_blocks` replaces it); a block that is resident already refuses the call.  Returns the info dict of `tsdf_evict_blocks`.
+        On a coloured hashed volume the new blocks are uncoloured; `tsdf_insert_blocks_color` inserts them with their colours."""
+        return self._insert_blocks(coords, tsdf, weight, None, None)
+
+    def tsdf_insert_blocks_color(self, coords, tsdf, weight, rgb, cweight):
+        """icp_tsdf_insert_blocks_color: `tsdf_insert_blocks` on a coloured hashed volume, the blocks with their colours rgb (B, 8, 8, 8, 3)
+        and cweight (B, 8, 8, 8)."""
+        if rgb is None or cweight is None:
+            raise ValueError("tsdf_insert_blocks_color takes rgb and cweight")
+        return self._insert_blocks(coords, tsdf, weight, rgb, cweight)
+
+    def _insert_blocks(self, coords, tsdf, weight, rgb, cweight):
+        cc, t, w, c, cw = self._blocks_in(coords, tsdf, weight, rgb, cweight)
         info = IcpTsdfStreamInfo()
-        self._ck(self.lib.icp_tsdf_insert_blocks(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(t), _ptr(w), C.byref(info)))
+        if c is not None:
+            self._ck(self.lib.icp_tsdf_insert_blocks_color(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(t), _ptr(w), _ptr(c), _ptr(cw), C.byref(info)))
+        else:
+            self._ck(self.lib.icp_tsdf_insert_blocks(self.h, C.c_int32(len(cc)), _ptr(cc), _ptr(t), _ptr(w), C.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
 
     def tsdf_color_create(self):

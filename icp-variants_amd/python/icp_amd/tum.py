@@ -104,7 +104,11 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     trajectory need not be known beforehand.  model=dict(hashed=True, raycast=True, origin=..., ...) with sdf=None tracks frame-to-model on
     the hashed volume instead (icp_track_depth_model_hashed): every frame against a ray-cast of the blocks, with the
     params' matcher, the optimiser, convergence and reciprocal choices and `with_gt` as on the dense model path.  hashed=True without `sdf`
-    and without raycast=True, with dims, or with color=True is a ValueError; so is raycast=True together with `sdf` or without hashed=True.
+    and without raycast=True, or with dims, is a ValueError; so is raycast=True together with `sdf` or without hashed=True.
+    model=dict(hashed=True, color=True, ...) with `sdf` gives the blocks colours (Context.tsdf_create_hashed(color=True), DESIGN.md section
+    6zb): the colour frames are fused, and sdf=dict(..., color_weight=w) aligns every frame with the photometric term as on the dense
+    coloured model; it goes together with keep_radius.  color=True with raycast=True is a ValueError (the ray-cast loop reads no colours),
+    and so is color=True on a sequence without colour frames.
     model=dict(hashed=True, keep_radius=R, ...) with `sdf` keeps only the blocks within R metres of the camera on the device and streams
     the rest to the host and back (tsdf_local.track_depth_sdf_local): the poses and records are those of the
     unbounded run, the stored blocks are left in ctx.tsdf_store (tsdf_local.restore(ctx, ctx.tsdf_store) puts the whole model back).
@@ -125,8 +129,10 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
             raise ValueError("a hashed model is tracked directly (sdf=dict(...)) or against its ray-cast (raycast=True in model): pass one of them")
         if model.get("dims") is not None:
             raise ValueError("a hashed model has no extent: leave dims out")
-        if model.get("color"):
-            raise ValueError("a hashed model holds no colours: leave color out")
+        if model.get("color") and raycast:
+            raise ValueError("the ray-cast loop of a hashed model reads no colours: leave color out, or track directly (sdf=dict(...))")
+        if model.get("color") and seq.get("rgbx") is None:
+            raise ValueError("a coloured hashed model fuses the sequence's colour frames: the sequence has none (rgbx)")
     if sdf is not None and model is None:
         raise ValueError("sdf tracking needs a model: pass model=dict(dims=..., origin=..., ...) as well")
     if sdf is not None and sdf.get("color_weight", 0.0) != 0 and not model.get("color"):
@@ -141,14 +147,15 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     tgt_o, src_o = reconstruct_room_options(ctx.params) if options is None else options
     if hashed:
-        ctx.tsdf_create_hashed(**{k: v for k, v in model.items() if k not in ("hashed", "raycast", "color", "dims", "keep_radius")})
+        ctx.tsdf_create_hashed(color=bool(model.get("color")), **{k: v for k, v in model.items() if k not in ("hashed", "raycast", "color", "dims", "keep_radius")})
         ctx.tsdf_store = None
+        rgbx = seq["rgbx"] if model.get("color") else None
         if raycast:
             _, recs, rc = ctx.track_depth_model_hashed(seq["depth"], cam, src_o, gt=seq["gt"] if with_gt else None)
         elif keep_radius is not None:
-            _, recs, rc, _, ctx.tsdf_store = tsdf_local.track_depth_sdf_local(ctx, seq["depth"], cam, keep_radius, **sdf)
+            _, recs, rc, _, ctx.tsdf_store = tsdf_local.track_depth_sdf_local(ctx, seq["depth"], cam, keep_radius, rgbx_frames=rgbx, **sdf)
         else:
-            _, recs, rc = ctx.track_depth_sdf(seq["depth"], cam, **sdf)
+            _, recs, rc = ctx.track_depth_sdf(seq["depth"], cam, rgbx_frames=rgbx, **sdf)
         poses = [np.eye(4, dtype=np.float32)] + [np.linalg.inv(r["pose"].astype(np.float64)).astype(np.float32) for r in recs]
         return poses, recs, rc
     if model is not None:
@@ -178,7 +185,8 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
     model_mesh: with `model` and `out_dir`, a file name: the fused volume's zero level set (Context.tsdf_mesh, in frame 0's camera coordinates) is
     written there as a binary PLY after the last frame -- the reconstructed room as ONE mesh, with per-vertex colours when the model has them
     (color=True in `model`); None writes nothing more.  A hashed model (hashed=True in `model`) is densified over the bounding box of its
-    blocks first (`densify_hashed_model`), which raises when that box does not fit a dense volume; densify=False meshes it in place instead
+    blocks first (`densify_hashed_model`, which carries a coloured hashed model's colours: the mesh then has them), which raises when that box
+    does not fit a dense volume; densify=False meshes it in place instead, without colours
     (Context.tsdf_mesh_hashed): nothing but the mesh crosses to the host, no box is built and the context keeps its hashed volume.
     densify=False with a model that is not hashed is a ValueError.  sdf: as `track` (direct SDF tracking against the model); a hashed model
     with raycast=True and no `sdf` is tracked against its ray-cast instead, as `track` says.  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
@@ -217,8 +225,11 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
 def densify_hashed_model(ctx):
     """Replaces the context's hashed volume by a dense one over the bounding box of its blocks, with the same contents (for
     Context.tsdf_mesh or tsdf_raycast, which need the dense box).  The dense origin is origin + lo * voxel_size, rounded once per axis.
+    A coloured hashed volume becomes a dense coloured one (Context.tsdf_color_upload): `tsdf_mesh(colors=True)`, `tsdf_raycast_color` and
+    `track_depth_model(..., rgbx_frames=...)` are reachable from a finished hashed coloured model by this route.
     Raises ValueError when the volume has no block or the box has more than INT32_MAX voxels."""
-    info, coords, t, w = ctx.tsdf_blocks()
+    colored = ctx.tsdf_has_color()
+    info, coords, t, w, *col = ctx.tsdf_blocks(colors=True) if colored else ctx.tsdf_blocks()
     if len(coords) == 0:
         raise ValueError("the hashed model holds no block: nothing to densify")
     lo = coords.min(0).astype(np.int64) * 8
@@ -231,6 +242,9 @@ def densify_hashed_model(ctx):
     ctx.tsdf_create(dims=tuple(int(d) for d in dims), origin=origin, voxel_size=o.voxel_size, truncation=o.truncation, max_weight=o.max_weight,
                     min_depth=o.min_depth, max_depth=o.max_depth, ray_step=o.ray_step)
     ctx.tsdf_upload(T, W)
+    if colored:
+        ctx.tsdf_color_create()
+        ctx.tsdf_color_upload(*binding.tsdf_block_colors_to_dense(coords, col[0], col[1], lo, dims))
 
 
 def _write_list(path, header, rows):

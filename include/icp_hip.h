@@ -822,8 +822,8 @@ int icp_track_depth_sdf(icp_ctx* ctx, const float* depth_frames, const uint8_t* 
  * Refused on a hashed volume (ICP_ERR_INVALID_ARG, a message that names the hashed volume, no side effect): icp_tsdf_download,
  *   icp_tsdf_upload, icp_tsdf_raycast*, icp_set_target_tsdf*, icp_track_depth_model* (the hashed volume's own calls are icp_tsdf_raycast_hashed,
  *   icp_set_target_tsdf_hashed and icp_track_depth_model_hashed, below), icp_tsdf_mesh (the hashed volume's own mesh call is icp_tsdf_mesh_hashed,
- *   below), icp_tsdf_color_create and every *_color call.  A finished model goes into a dense volume block by block (icp_get_tsdf_hashed,
- *   then icp_tsdf_upload). */
+ *   below), icp_tsdf_color_create and every *_color call -- on a hashed volume WITHOUT colours; what a coloured one (icp_tsdf_create_color_hashed,
+ *   further below) accepts is listed there.  A finished model goes into a dense volume block by block (icp_get_tsdf_hashed, then icp_tsdf_upload). */
 typedef struct icp_tsdf_hashed_info {
     int32_t n_blocks;                /* allocated blocks */
     int32_t capacity;                /* blocks the pool holds before it grows */
@@ -885,6 +885,53 @@ static_assert(sizeof(icp_tsdf_stream_info) == 32, "icp_tsdf_stream_info");
 int icp_tsdf_evict_blocks(icp_ctx* ctx, const float centre[3], float radius, int32_t hold, icp_tsdf_stream_info* info_out);
 int icp_tsdf_evicted_blocks(icp_ctx* ctx, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out);
 int icp_tsdf_insert_blocks(icp_ctx* ctx, int32_t n, const int32_t* coords, const float* tsdf, const float* weight, icp_tsdf_stream_info* info_out);
+
+/* -------- the coloured hashed volume (an extension): the hashed volume with the colour array of the coloured model (icp_tsdf_color_create)
+ * in its blocks, so that colour fusion and the photometric term of direct SDF tracking work without an extent.  DESIGN.md section 6zb.
+ * tests/htsdf_color_restatement.py restates what follows, compared bit for bit. --------
+ * Storage: icp_tsdf_create_color_hashed is icp_tsdf_create_hashed plus a SECOND POOL: one fp32 (R, G, B, Wc) per voxel, 512 per block
+ *   (8 KiB), x fastest, indexed by the pool index of the geometry block, in a buffer of its own (12 KiB per block in all; the geometry-only
+ *   kernels read and write what they did).  It is cleared to (0, 0, 0, 0) when allocated, grows with the pool (the live prefix of both
+ *   pools is copied), is cleared by icp_tsdf_reset and freed by icp_tsdf_release, create and destroy.  icp_tsdf_hashed_has_color tells
+ *   which kind the context holds (ICP_ERR_INVALID_ARG without a hashed volume).  icp_tsdf_hashed_info is unchanged.
+ *   A hashed volume WITHOUT colours behaves exactly as before: it refuses every *_color call with the message it always gave.
+ * Fusion: icp_tsdf_integrate_color on a coloured hashed volume is the touch under the room rule, then over every allocated block the
+ *   hashed integrate's geometry, operation for operation, and the dense coloured rule: a voxel is painted iff it is updated AND
+ *   !(sdf > truncation), from the pixel the geometry used, C <- (Wc C + c) / (Wc + 1) per channel, Wc <- fminf(Wc + 1, max_weight); a
+ *   voxel that is not painted has its colour neither read nor written.  Both counts as on the dense volume.  icp_tsdf_integrate stays
+ *   legal and leaves the colours alone; icp_track_depth_sdf given colour frames fuses them.
+ * Save and restore: icp_get_tsdf_color_hashed is icp_get_tsdf_hashed with rgb_out (n_blocks x 512 x 3) and cweight_out (n_blocks x 512) in
+ *   the same order and voxel layout, any output NULL; icp_tsdf_upload_color_hashed REPLACES the state with blocks and their colours.
+ *   icp_tsdf_upload_hashed on a coloured volume replaces the state and leaves every block uncoloured.
+ * Intensity field and photometric tracking: icp_tsdf_sample_color, icp_tsdf_sdf_system_color, icp_tsdf_align_depth_color and
+ *   icp_track_depth_sdf_color work on a coloured hashed volume with the same signatures, options, records and statuses.  A colour sample
+ *   is VALID iff the cell is storable (-2^23 <= f <= 2^23 - 2, tested in float), the blocks of all eight corners exist and every corner
+ *   has Wc > 0; the geometry's weights play no part.  The joint step is the hashed geometric row with the dense photometric row added
+ *   into it in that contract's term order; the colour corners are those of the cell the distance was read in.
+ * Streaming: icp_tsdf_evict_blocks compacts both pools by the same plan (a mover's colours go into the hole its geometry goes into), with
+ *   hold != 0 the outbox receives both, and both tails are cleared: afterwards the volume equals, through every public call and bit for
+ *   bit, a fresh coloured volume that icp_tsdf_upload_color_hashed filled with the kept blocks.  icp_tsdf_evicted_blocks_color returns the
+ *   outbox with its colours, icp_tsdf_insert_blocks_color adds blocks with theirs (the same refusals as icp_tsdf_insert_blocks).
+ *   icp_tsdf_evicted_blocks returns the outbox's geometry; icp_tsdf_insert_blocks leaves the new blocks uncoloured.  The reach of a view
+ *   needs no change: the colour is read and written only in cells and voxels the geometry touches.
+ * Still refused on a coloured hashed volume (ICP_ERR_INVALID_ARG, a message that names the call, no side effect): icp_tsdf_color_create,
+ *   icp_tsdf_color_release, icp_tsdf_color_download and icp_tsdf_color_upload (they address the dense array; the message points at the
+ *   calls below), icp_tsdf_raycast_color, icp_set_target_tsdf_color, icp_track_depth_model_color and icp_tsdf_mesh_color, with every
+ *   dense-box call listed above.  There is no coloured ray-cast, target, model loop or mesh of the blocks yet: a finished model goes into a
+ *   dense coloured volume block by block (icp_get_tsdf_color_hashed, then icp_tsdf_upload and icp_tsdf_color_upload).
+ * Legal and geometry-only on a coloured hashed volume: icp_tsdf_mesh_hashed, icp_tsdf_raycast_hashed, icp_set_target_tsdf_hashed and
+ *   icp_track_depth_model_hashed; the model loop's own fusion there leaves the colours alone.
+ * The new calls refuse a context without a volume, one with a dense volume and one with a hashed volume without colours. */
+int icp_tsdf_create_color_hashed(icp_ctx* ctx, const icp_tsdf_options* opt, int32_t block_capacity);
+int icp_tsdf_hashed_has_color(icp_ctx* ctx, int32_t* has_out);
+int icp_get_tsdf_color_hashed(icp_ctx* ctx, icp_tsdf_hashed_info* info_out, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out,
+                              float* rgb_out, float* cweight_out);
+int icp_tsdf_upload_color_hashed(icp_ctx* ctx, int32_t n, const int32_t* coords, const float* tsdf, const float* weight, const float* rgb,
+                                 const float* cweight);
+int icp_tsdf_evicted_blocks_color(icp_ctx* ctx, int32_t max_blocks, int32_t* coords_out, float* tsdf_out, float* weight_out, float* rgb_out,
+                                  float* cweight_out);
+int icp_tsdf_insert_blocks_color(icp_ctx* ctx, int32_t n, const int32_t* coords, const float* tsdf, const float* weight, const float* rgb,
+                                 const float* cweight, icp_tsdf_stream_info* info_out);
 
 /* -------- the hashed model as a mesh (an extension): icp_tsdf_mesh on the block pool -- the zero level set of the context's HASHED volume
  * as an indexed triangle mesh with per-vertex normals; only the mesh crosses to the host and scratch scales with the blocks in use, not with
@@ -948,7 +995,7 @@ int icp_tsdf_mesh_hashed(icp_ctx* ctx, float min_weight, int32_t max_vertices, i
  * icp_track_depth_model_hashed: icp_track_depth_model's loop, arguments, frame records, statuses, carried pose on a failed frame, upload
  *   overlap and gt RMSE, with the target from the hashed ray-cast and the integrate icp_tsdf_integrate's on a hashed volume (the touch with
  *   its growth and room rule; growth past 2^22 blocks ends the call with ICP_ERR_INVALID_ARG).  It keeps that loop's refusals: colour ICP,
- *   colour weighting and the colored metric (the hashed volume holds no colours: there is no *_color form), GICP, and a projective camera
+ *   colour weighting and the colored metric (the loop reads no colours, also on a coloured hashed volume, whose colours its own fusion leaves alone: there is no *_color form), GICP, and a projective camera
  *   in the params that differs from the depth camera.  Host waits per tracked frame: icp_track_depth_model's (the hit count, the run's)
  *   and the touch's counters, plus one per growth of the pool.
  * All three: no volume, or a dense volume: ICP_ERR_INVALID_ARG with a message that names the call, nothing touched -- the dense volume's
