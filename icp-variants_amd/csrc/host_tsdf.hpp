@@ -25,7 +25,8 @@ bool is_identity16(const float* m) {
 // what host_tsdf_hash.hpp defines for a hashed volume
 int htsdf_integrate_slot(icp_ctx* c, int slot, const icp_depth_camera& cam, const float pose[16], int* d_count, const char* who, bool color = false);
 int htsdf_reset(icp_ctx* c);
-int htsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], bool soa, const TsdfRayOut& o);      // (host_tsdf_hash_raycast.hpp)
+int htsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], bool soa, const TsdfRayOut& o, const TsdfColorOut* co = nullptr);      // (host_tsdf_hash_raycast.hpp, DESIGN.md sections 6z and 6zc)
+int htsdf_check_color(icp_ctx* c, const char* who);
 void htsdf_drop(icp_ctx* c);
 // the calls that need the dense box: refused on a hashed volume, with nothing touched
 int tsdf_check_dense(icp_ctx* c, const char* who) {
@@ -100,7 +101,7 @@ int tsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pos
 }
 // The model as target, from the arguments already checked: the ray-cast into the target's planes, the hit count, finish_target.
 // *hits_out = 0 with ICP_ERR_NO_TARGET leaves an empty target.  color: the coloured ray-cast, colours into the target's colour planes;
-// a hit without colour is a hole and *hits_out counts the coloured hits.  hashed: the ray-cast of the hashed volume (no colours there).
+// a hit without colour is a hole and *hits_out counts the coloured hits.  hashed: the ray-cast of the hashed volume (with color: its coloured one).
 int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], int* hits_out, const char* who, bool color = false, bool hashed = false) {
     int rc;
     Cloud& tg = c->tgt;
@@ -112,7 +113,7 @@ int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16
     TsdfRayOut o; memset(&o, 0, sizeof(o));
     o.x = tg.x.as<float>(); o.y = tg.y.as<float>(); o.z = tg.z.as<float>(); o.nx = tg.nx.as<float>(); o.ny = tg.ny.as<float>(); o.nz = tg.nz.as<float>(); o.npad = npad;
     const TsdfColorOut co = {tg.rgba.as<uint32_t>(), tg.cr.as<float>(), tg.cg.as<float>(), tg.cb.as<float>()};
-    if ((rc = hashed ? htsdf_raycast_launch(c, cam, pose, true, o) : tsdf_raycast_launch(c, cam, pose, true, o, color ? &co : nullptr))) return rc;
+    if ((rc = hashed ? htsdf_raycast_launch(c, cam, pose, true, o, color ? &co : nullptr) : tsdf_raycast_launch(c, cam, pose, true, o, color ? &co : nullptr))) return rc;
     int hits = 0;
     if ((rc = read_count(c, c->tsdf_cnt.p, &hits))) return rc;      // (the coloured target's holes are its uncoloured hits: both counts agree)
     tg.has_normals = true; tg.has_colors = color;
@@ -407,8 +408,8 @@ int icp_set_target_tsdf_color(icp_ctx* c, const icp_depth_camera* cam, const flo
 
 // Both tracking loops.  color (icp_track_depth_model_color): frames staged with their colour frame, the coloured target, the source with
 // colours, the coloured integration -- and the colour modes, which the geometric loop refuses, accepted.  hashed
-// (icp_track_depth_model_hashed, never with color): the target from the hashed ray-cast, the integrate htsdf_integrate_slot -- its touch
-// waits for the host once per integrated frame, and once more per growth of the pool.
+// (icp_track_depth_model_hashed; with color icp_track_depth_model_color_hashed): the target from the hashed ray-cast, the integrate
+// htsdf_integrate_slot -- its touch waits for the host once per integrated frame, and once more per growth of the pool.
 static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_t* rgbx_frames, bool color, int32_t n_frames, const icp_depth_camera* cam,
                              const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out, const std::string& who,
                              bool hashed = false) {
@@ -422,7 +423,7 @@ static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_
     }
     if (color) {
         if (!rgbx_frames) { c->err = who + ": null colour frames"; return ICP_ERR_INVALID_ARG; }
-        if ((rc = tsdf_check_color(c, who.c_str()))) return rc;
+        if ((rc = hashed ? htsdf_check_color(c, who.c_str()) : tsdf_check_color(c, who.c_str()))) return rc;
         if (!source_opt->fix_color_index) {
             c->err = who + ": source_opt->fix_color_index must be set (the model holds each pixel's own bytes, the reference's shifted bytes would compare unlike things)";
             return ICP_ERR_INVALID_ARG;
@@ -435,7 +436,7 @@ static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_
     if ((rc = set_device(c))) return rc;
     const int n = cam->width * cam->height;
     auto frame_rgbx = [&](int k) { return color ? rgbx_frames + (size_t)k * n * 4 : nullptr; };
-    auto integrate = [&](int slot) { return hashed ? htsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, who.c_str()) : tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, color); };
+    auto integrate = [&](int slot) { return hashed ? htsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, who.c_str(), color) : tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, color); };
     if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     // frame 0 into the model at the incoming pose; frame 1 goes up meanwhile
     if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;

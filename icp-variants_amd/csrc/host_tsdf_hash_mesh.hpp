@@ -1,6 +1,7 @@
 // host_tsdf_hash_mesh.hpp -- icp_tsdf_mesh_hashed: the zero level set of the context's HASHED TSDF volume as an indexed triangle mesh, extracted
-// on the block pool; only the mesh crosses to the host, scratch scales with the blocks in use.  Kernels: dev_tsdf_hash_mesh.hpp; contract:
-// include/icp_hip.h, DESIGN.md section 6y.  Part of icp_hip.hip (included from there, after host_tsdf_hash.hpp and host_tsdf_mesh.hpp).
+// on the block pool; only the mesh crosses to the host, scratch scales with the blocks in use; icp_tsdf_mesh_color_hashed: the same mesh with
+// a colour per vertex from the colour pool.  Kernels: dev_tsdf_hash_mesh.hpp, dev_tsdf_hash_mesh_color.hpp; contract: include/icp_hip.h,
+// DESIGN.md sections 6y and 6zc.  Part of icp_hip.hip (included from there, after host_tsdf_hash.hpp and host_tsdf_mesh.hpp).
 namespace {
 // The context's scratch, indexed by block rank: [observed | negative | valid] words (8 per block each), the mask bytes, the run bases, the
 // 27 neighbour ranks, the two block tables and the two totals, order[rank] and rank_of[pool index].
@@ -74,19 +75,27 @@ int htm_check_call(icp_ctx* c, float min_weight, const char* who) {
     }
     return ICP_OK;
 }
-}  // namespace
-
-int icp_tsdf_mesh_hashed(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint32_t* triangles_out,
-                         int32_t* n_vertices_out, int32_t* n_triangles_out) {
-    if (!c) return ICP_ERR_INVALID_ARG;
-    const std::string who = "icp_tsdf_mesh_hashed";
+// the colour pass, enqueued after htm_enqueue_fill (it reads the run bases k_htm_vertices wrote): one packed colour per vertex
+int htm_enqueue_colors(icp_ctx* c, int n, const HtmScratch& s, uint32_t* d_col) {
+    hipLaunchKernelGGL(k_htm_colors, dim3((unsigned)n), dim3(512), 0, c->stream, (const float2*)c->th_pool.as<float2>(), (const float4*)c->th_cpool.as<float4>(), (const int*)s.order,
+                       (const int*)s.nbr, (const uint8_t*)s.mask, (const int*)s.base, d_col);
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+// Both mesh calls.  color (icp_tsdf_mesh_color_hashed): needs the colour pool; colors_out (optional) receives one packed colour per vertex.
+int htsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out, bool color,
+               uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, const std::string& who) {
     if (n_vertices_out) *n_vertices_out = 0;
     if (n_triangles_out) *n_triangles_out = 0;
     int rc;
+    if (color && (rc = htsdf_check_color(c, who.c_str()))) return rc;      // no volume; a dense volume; no colours
     if ((rc = htm_check_call(c, min_weight, who.c_str()))) return rc;
     if (!n_vertices_out || !n_triangles_out) { c->err = who + ": null count pointer"; return ICP_ERR_INVALID_ARG; }
-    const bool count_only = !vertices_out && !normals_out && !triangles_out;
-    if (!count_only && (!vertices_out || !triangles_out)) { c->err = who + ": vertices_out and triangles_out go together (normals_out alone may be NULL)"; return ICP_ERR_INVALID_ARG; }
+    const bool count_only = !vertices_out && !normals_out && !colors_out && !triangles_out;
+    if (!count_only && (!vertices_out || !triangles_out)) {
+        c->err = who + (color ? ": vertices_out and triangles_out go together (normals_out and colors_out may be NULL)" : ": vertices_out and triangles_out go together (normals_out alone may be NULL)");
+        return ICP_ERR_INVALID_ARG;
+    }
     const int n = c->th_nblk;
     if (n == 0) return ICP_OK;                           // no block: no surface
     DrainOnError guard(c);
@@ -109,16 +118,69 @@ int icp_tsdf_mesh_hashed(icp_ctx* c, float min_weight, int32_t max_vertices, int
         return guard.done(ICP_ERR_INVALID_ARG);      // (synchronised by the count read)
     }
     if (nv == 0 && nt == 0) return guard.done();
-    // the outputs staged in device arrays of exactly the counted size: [vertices 12 V | normals 12 V | triangles 12 T]
-    const size_t bv = (size_t)nv * 12, bn = normals_out ? bv : 0, bt = (size_t)nt * 12;
-    if ((rc = ensure(c, c->tm_out, bv + bn + bt))) return rc;
+    // the outputs staged in device arrays of exactly the counted size: [vertices 12 V | normals 12 V | triangles 12 T | colours 4 V]
+    const size_t bv = (size_t)nv * 12, bn = normals_out ? bv : 0, bt = (size_t)nt * 12, bc = colors_out ? (size_t)nv * 4 : 0;
+    if ((rc = ensure(c, c->tm_out, bv + bn + bt + bc))) return rc;
     char* d = c->tm_out.as<char>();
     float* d_vert = (float*)d; float* d_nrm = normals_out ? (float*)(d + bv) : nullptr; uint32_t* d_tris = (uint32_t*)(d + bv + bn);
+    uint32_t* d_col = (uint32_t*)(d + bv + bn + bt);
     if ((rc = htm_enqueue_fill(c, n, s, d_vert, d_nrm, d_tris))) return rc;
+    if (colors_out && nv > 0) {
+        if ((rc = htm_enqueue_colors(c, n, s, d_col))) return rc;
+        HIPCK(c, hipMemcpyAsync(colors_out, d_col, bc, hipMemcpyDeviceToHost, c->stream));
+    }
     if (nv > 0) HIPCK(c, hipMemcpyAsync(vertices_out, d_vert, bv, hipMemcpyDeviceToHost, c->stream));
     if (nv > 0 && normals_out) HIPCK(c, hipMemcpyAsync(normals_out, d_nrm, bn, hipMemcpyDeviceToHost, c->stream));
     if (nt > 0) HIPCK(c, hipMemcpyAsync(triangles_out, d_tris, bt, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+}  // namespace
+
+int icp_tsdf_mesh_hashed(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint32_t* triangles_out,
+                         int32_t* n_vertices_out, int32_t* n_triangles_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    return htsdf_mesh(c, min_weight, max_vertices, max_triangles, vertices_out, normals_out, nullptr, false, triangles_out, n_vertices_out, n_triangles_out, "icp_tsdf_mesh_hashed");
+}
+int icp_tsdf_mesh_color_hashed(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out,
+                               uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    return htsdf_mesh(c, min_weight, max_vertices, max_triangles, vertices_out, normals_out, colors_out, true, triangles_out, n_vertices_out, n_triangles_out,
+                      "icp_tsdf_mesh_color_hashed");
+}
+
+// Not part of icp_hip.h (tools/time_htsdf_color_view.py): the device time of ALL passes of one icp_tsdf_mesh_color_hashed (those of
+// icp_debug_htsdf_mesh_time plus the colour pass) between two events on the context's stream; a counting run outside the bracket sizes the arrays.
+extern "C" int icp_debug_htsdf_mesh_color_time(icp_ctx* c, float min_weight, float* device_ms_out) {
+    if (!c || !device_ms_out) return ICP_ERR_INVALID_ARG;
+    const char* who = "icp_debug_htsdf_mesh_color_time";
+    int rc;
+    if ((rc = htsdf_check_color(c, who))) return rc;
+    if ((rc = htm_check_call(c, min_weight, who))) return rc;
+    const int n = c->th_nblk;
+    if (n == 0) { c->err = std::string(who) + ": the volume holds no block"; return ICP_ERR_INVALID_ARG; }
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ensure_events(c, 2))) return rc;
+    HtmScratch s;
+    std::vector<int> h_order;
+    if ((rc = htm_scratch(c, n, s))) return rc;
+    if ((rc = htm_order(c, n, s, h_order))) return rc;
+    if ((rc = htm_enqueue_count(c, n, s, min_weight))) return rc;
+    int tot[2] = {0, 0};
+    if ((rc = read_count(c, s.tot, tot, 2))) return rc;
+    const int nv = tot[0], nt = tot[1];
+    if (nv < 0 || nt < 0) { c->err = std::string(who) + ": count out of range"; return ICP_ERR_HIP; }
+    const size_t bv = (size_t)nv * 12, bt = (size_t)nt * 12;
+    if ((rc = ensure(c, c->tm_out, 2 * bv + bt + (size_t)nv * 4))) return rc;
+    char* d = c->tm_out.as<char>();
+    HIPCK(c, hipEventRecord(c->events[0], c->stream));
+    if ((rc = htm_enqueue_count(c, n, s, min_weight))) return rc;
+    if ((rc = htm_enqueue_fill(c, n, s, (float*)d, (float*)(d + bv), (uint32_t*)(d + 2 * bv)))) return rc;
+    if (nv > 0 && (rc = htm_enqueue_colors(c, n, s, (uint32_t*)(d + 2 * bv + bt)))) return rc;
+    HIPCK(c, hipEventRecord(c->events[1], c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    HIPCK(c, hipEventElapsedTime(device_ms_out, c->events[0], c->events[1]));
     return guard.done();
 }
 

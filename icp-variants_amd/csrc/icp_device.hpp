@@ -10,7 +10,7 @@
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
 // dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf_color.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp, dev_sdf.hpp, dev_sdf_color.hpp, dev_vgicp.hpp,
 // dev_vmap.hpp, dev_hmap.hpp, dev_tsdf_hash.hpp, dev_tsdf_hash_raycast.hpp, dev_tsdf_hash_mesh.hpp, dev_tsdf_hash_evict.hpp, dev_tsdf_hash_color.hpp,
-// dev_vmap_prune.hpp
+// dev_tsdf_hash_raycast_color.hpp, dev_tsdf_hash_mesh_color.hpp, dev_vmap_prune.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -73,6 +73,9 @@
 //   k_htsdf_present     an outbox and the pool compacted by minimal move; the resident keys among blocks that come back counted (dev_tsdf_hash_evict.hpp)
 //   k_htsdf_*_color     the colours of the hashed volume (icp_tsdf_create_color_hashed): a second pool of float4 per voxel by the same pool index --
 //                       fusion, upload, the evict's copies, the intensity sample by lookup (dev_tsdf_hash_color.hpp)
+//   k_htsdf_raycast_color / the coloured hashed model seen from a pose and meshed (icp_tsdf_raycast_color_hashed, icp_tsdf_mesh_color_hashed): the
+//   k_htm_colors        colour of a hit from the blocks its geometry lookup found, a colour per mesh vertex at k_htm_vertices' index
+//                       (dev_tsdf_hash_raycast_color.hpp, dev_tsdf_hash_mesh_color.hpp)
 //   k_vmap_prune /      forgetting the map's cells beyond a radius of a centre (icp_voxel_map_prune, icp_track_scans_vmap_local), and
 //   k_hmap_prune /      the compaction of a hashed table that has vacated slots (dev_vmap_prune.hpp)
 //   k_hmap_compact
@@ -121,6 +124,8 @@ namespace icpdev {
 #include "dev_tsdf_hash_mesh.hpp"
 #include "dev_tsdf_hash_evict.hpp"
 #include "dev_tsdf_hash_color.hpp"
+#include "dev_tsdf_hash_raycast_color.hpp"
+#include "dev_tsdf_hash_mesh_color.hpp"
 #include "dev_vmap_prune.hpp"
 
 }  // namespace icpdev

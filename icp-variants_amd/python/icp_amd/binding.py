@@ -460,6 +460,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_evict_blocks", "icp_tsdf_evicted_blocks", "icp_tsdf_insert_blocks",
            "icp_tsdf_create_color_hashed", "icp_tsdf_hashed_has_color", "icp_get_tsdf_color_hashed", "icp_tsdf_upload_color_hashed",
            "icp_tsdf_evicted_blocks_color", "icp_tsdf_insert_blocks_color",
+           "icp_tsdf_raycast_color_hashed", "icp_set_target_tsdf_color_hashed", "icp_track_depth_model_color_hashed", "icp_tsdf_mesh_color_hashed",
            "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
            "icp_track_depth_sdf_color",
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
@@ -1223,23 +1224,28 @@ class Context:
             call(v, n, col, t)
         return (v, n, t, col) if colors else (v, n, t)
 
-    def tsdf_mesh_hashed(self, min_weight=0.0, normals=True):
+    def tsdf_mesh_hashed(self, min_weight=0.0, normals=True, colors=False):
         """icp_tsdf_mesh_hashed: the zero level set of the HASHED volume as an indexed triangle mesh, extracted on the block pool (a counting
         call, then a filling call).  The volume stays as it is.  Returns (vertices (V, 3) f32, normals (V, 3) f32 --
         None with normals=False --, triangles (T, 3) u32); vertices in ascending (block in key order, local voxel, edge code), so the arrays
-        do not depend on where the blocks sit in the pool."""
+        do not depend on where the blocks sit in the pool.
+        colors: icp_tsdf_mesh_color_hashed on a coloured hashed volume; a fourth array, (V, 4) u8 RGBA per vertex
+        (four zero bytes where neither end of the vertex's edge holds a colour)."""
         min_weight = float(min_weight)
         if not (np.isfinite(min_weight) and min_weight >= 0.0):
             raise ValueError("min_weight must be finite and >= 0")
         nv, nt = C.c_int32(0), C.c_int32(0)
+        fn = self.lib.icp_tsdf_mesh_color_hashed if colors else self.lib.icp_tsdf_mesh_hashed
 
-        def call(v, n, t):
-            self._ck(self.lib.icp_tsdf_mesh_hashed(self.h, C.c_float(min_weight), C.c_int32(nv.value), C.c_int32(nt.value), _ptr(v), _ptr(n), _ptr(t), C.byref(nv), C.byref(nt)))
-        call(None, None, None)
+        def call(v, n, col, t):                             # the colour array sits between the normals and the triangles
+            bufs = [_ptr(v), _ptr(n)] + ([_ptr(col)] if colors else []) + [_ptr(t)]
+            self._ck(fn(self.h, C.c_float(min_weight), C.c_int32(nv.value), C.c_int32(nt.value), *bufs, C.byref(nv), C.byref(nt)))
+        call(None, None, None, None)
         v = np.empty((nv.value, 3), np.float32); n = np.empty((nv.value, 3), np.float32) if normals else None; t = np.empty((nt.value, 3), np.uint32)
+        col = np.empty((nv.value, 4), np.uint8)
         if nv.value or nt.value:
-            call(v, n, t)
-        return v, n, t
+            call(v, n, col, t)
+        return (v, n, t, col) if colors else (v, n, t)
 
     def set_target_tsdf(self, cam, pose, check=True, color=False):
         """icp_set_target_tsdf: the ray-cast of the volume from `pose` as the target (organised, with normals).  Returns the number of hits
@@ -1281,27 +1287,46 @@ class Context:
         self._ck(self.lib.icp_tsdf_raycast_hashed(self.h, C.byref(cam), _ptr(p), _ptr(d), _ptr(v), _ptr(nr), C.byref(hits)))
         return d, v, nr, hits.value
 
-    def set_target_tsdf_hashed(self, cam, pose, check=True):
+    def tsdf_raycast_color_hashed(self, cam, pose):
+        """icp_tsdf_raycast_color_hashed: `tsdf_raycast_hashed` on a coloured hashed volume with the colour of every hit (DESIGN.md section
+        6zc).  Returns (depth, vertices, normals, rgba (w*h, 4) u8, hits, coloured hits); a hole or a hit without colour is four zero
+        bytes, a coloured pixel has alpha 255."""
+        p = _pose_in(pose)
+        n = cam.width * cam.height
+        d = np.empty((cam.height, cam.width), np.float32); v = np.empty((n, 3), np.float32); nr = np.empty((n, 3), np.float32)
+        rgba = np.empty((n, 4), np.uint8); hits, ncol = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.icp_tsdf_raycast_color_hashed(self.h, C.byref(cam), _ptr(p), _ptr(d), _ptr(v), _ptr(nr), _ptr(rgba), C.byref(hits), C.byref(ncol)))
+        return d, v, nr, rgba, hits.value, ncol.value
+
+    def set_target_tsdf_hashed(self, cam, pose, check=True, color=False):
         """icp_set_target_tsdf_hashed: the ray-cast of the HASHED volume from `pose` as the target (organised, with normals).  Returns the
-        number of hits (and the status with check=False)."""
+        number of hits (and the status with check=False).  color: icp_set_target_tsdf_color_hashed, the target with colours from a coloured
+        hashed volume; hits without a colour become holes and the coloured hits are returned."""
         p = _pose_in(pose)
         n = C.c_int32(0)
-        rc = self.lib.icp_set_target_tsdf_hashed(self.h, C.byref(cam), _ptr(p), C.byref(n))
+        fn = self.lib.icp_set_target_tsdf_color_hashed if color else self.lib.icp_set_target_tsdf_hashed
+        rc = fn(self.h, C.byref(cam), _ptr(p), C.byref(n))
         if check:
             self._ck(rc)
         self.n_tgt = cam.width * cam.height if rc == ICP_OK else 0
         return n.value if check else (n.value, rc)
 
-    def track_depth_model_hashed(self, depth_frames, cam, source_opt, gt=None, pose=None):
+    def track_depth_model_hashed(self, depth_frames, cam, source_opt, gt=None, pose=None, rgbx_frames=None):
         """icp_track_depth_model_hashed: `track_depth_model` against the context's HASHED volume: every frame aligned to a ray-cast of the
         blocks and, when that succeeds, fused into them (blocks allocated as the frames come; the pool grows on the device).  Returns
-        (final pose, records, status)."""
+        (final pose, records, status).
+        rgbx_frames (n, h*w, 4): icp_track_depth_model_color_hashed, the coloured hashed model (needs a coloured hashed volume and
+        source_opt.fix_color_index)."""
         d = _depth_in(depth_frames, cam, sequence=True)
         nf = d.shape[0]
         g = _gt_in(gt, nf)
         p = _pose_in(np.eye(4) if pose is None else pose)
         out = (IcpTrackFrame * max(nf - 1, 1))()
-        rc = self.lib.icp_track_depth_model_hashed(self.h, _ptr(d), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
+        if rgbx_frames is not None:
+            cols = _rgbx_in(rgbx_frames, d.size, "colour frames must hold 4 bytes per pixel")
+            rc = self.lib.icp_track_depth_model_color_hashed(self.h, _ptr(d), _ptr(cols), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
+        else:
+            rc = self.lib.icp_track_depth_model_hashed(self.h, _ptr(d), C.c_int32(nf), C.byref(cam), C.byref(source_opt), _ptr(g), _ptr(p), out)
         if rc not in (ICP_OK, ERR_NO_TARGET, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-frame outcomes: reported in the records
             self._ck(rc)
         return pose_from_c(p), [_record(out[i]) for i in range(nf - 1)], rc

@@ -107,8 +107,12 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     and without raycast=True, or with dims, is a ValueError; so is raycast=True together with `sdf` or without hashed=True.
     model=dict(hashed=True, color=True, ...) with `sdf` gives the blocks colours (Context.tsdf_create_hashed(color=True), DESIGN.md section
     6zb): the colour frames are fused, and sdf=dict(..., color_weight=w) aligns every frame with the photometric term as on the dense
-    coloured model; it goes together with keep_radius.  color=True with raycast=True is a ValueError (the ray-cast loop reads no colours),
-    and so is color=True on a sequence without colour frames.
+    coloured model; it goes together with keep_radius.  color=True with raycast=True is a ValueError (the geometric ray-cast loop reads no
+    colours: raycast="color" is the coloured one), and so is color=True on a sequence without colour frames.
+    model=dict(hashed=True, color=True, raycast="color", ...) with sdf=None tracks against the COLOURED ray-cast of the blocks
+    (icp_track_depth_model_color_hashed): the colour frames are fused and the params may ask for colour ICP, colour
+    weighting or the colored metric; fix_color_index is set on (a copy of) the source options, as on the dense coloured model path.
+    raycast="color" without color=True, without hashed=True, with `sdf` or with keep_radius is a ValueError.
     model=dict(hashed=True, keep_radius=R, ...) with `sdf` keeps only the blocks within R metres of the camera on the device and streams
     the rest to the host and back (tsdf_local.track_depth_sdf_local): the poses and records are those of the
     unbounded run, the stored blocks are left in ctx.tsdf_store (tsdf_local.restore(ctx, ctx.tsdf_store) puts the whole model back).
@@ -122,6 +126,11 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
         raise ValueError("keep_radius streams the directly tracked hashed model (sdf=dict(...)): the ray-cast loop has no streaming")
     if raycast and not hashed:
         raise ValueError("raycast=True selects the ray-cast loop of a hashed model: pass hashed=True as well (a dense model is ray-cast as it is)")
+    color_cast = model is not None and isinstance(model.get("raycast"), str) and model.get("raycast") == "color"
+    if raycast and not color_cast and model.get("raycast") is not True:
+        raise ValueError("raycast is True (the geometric ray-cast loop) or \"color\" (the coloured one)")
+    if color_cast and not model.get("color"):
+        raise ValueError("raycast=\"color\" tracks against the coloured ray-cast of a coloured hashed model: pass color=True as well")
     if raycast and sdf is not None:
         raise ValueError("raycast=True tracks against a ray-cast of the hashed model, sdf=dict(...) directly against it: pass one of them")
     if hashed:
@@ -129,8 +138,8 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
             raise ValueError("a hashed model is tracked directly (sdf=dict(...)) or against its ray-cast (raycast=True in model): pass one of them")
         if model.get("dims") is not None:
             raise ValueError("a hashed model has no extent: leave dims out")
-        if model.get("color") and raycast:
-            raise ValueError("the ray-cast loop of a hashed model reads no colours: leave color out, or track directly (sdf=dict(...))")
+        if model.get("color") and raycast and not color_cast:
+            raise ValueError("the ray-cast loop of a hashed model reads no colours: leave color out, track directly (sdf=dict(...)), or pass raycast=\"color\" for the coloured ray-cast loop")
         if model.get("color") and seq.get("rgbx") is None:
             raise ValueError("a coloured hashed model fuses the sequence's colour frames: the sequence has none (rgbx)")
     if sdf is not None and model is None:
@@ -150,7 +159,10 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
         ctx.tsdf_create_hashed(color=bool(model.get("color")), **{k: v for k, v in model.items() if k not in ("hashed", "raycast", "color", "dims", "keep_radius")})
         ctx.tsdf_store = None
         rgbx = seq["rgbx"] if model.get("color") else None
-        if raycast:
+        if color_cast:
+            src_o = binding.depth_options(bool(src_o.keep_original_size), int(src_o.downsample_factor), float(src_o.max_distance), fix_color_index=True)
+            _, recs, rc = ctx.track_depth_model_hashed(seq["depth"], cam, src_o, gt=seq["gt"] if with_gt else None, rgbx_frames=rgbx)
+        elif raycast:
             _, recs, rc = ctx.track_depth_model_hashed(seq["depth"], cam, src_o, gt=seq["gt"] if with_gt else None)
         elif keep_radius is not None:
             _, recs, rc, _, ctx.tsdf_store = tsdf_local.track_depth_sdf_local(ctx, seq["depth"], cam, keep_radius, rgbx_frames=rgbx, **sdf)
@@ -186,8 +198,8 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
     written there as a binary PLY after the last frame -- the reconstructed room as ONE mesh, with per-vertex colours when the model has them
     (color=True in `model`); None writes nothing more.  A hashed model (hashed=True in `model`) is densified over the bounding box of its
     blocks first (`densify_hashed_model`, which carries a coloured hashed model's colours: the mesh then has them), which raises when that box
-    does not fit a dense volume; densify=False meshes it in place instead, without colours
-    (Context.tsdf_mesh_hashed): nothing but the mesh crosses to the host, no box is built and the context keeps its hashed volume.
+    does not fit a dense volume; densify=False meshes it in place instead
+    (Context.tsdf_mesh_hashed, DESIGN.md sections 6y and 6zc; with per-vertex colours when the model has them): nothing but the mesh crosses to the host, no box is built and the context keeps its hashed volume.
     densify=False with a model that is not hashed is a ValueError.  sdf: as `track` (direct SDF tracking against the model); a hashed model
     with raycast=True and no `sdf` is tracked against its ray-cast instead, as `track` says.  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
     if not densify and not (model is not None and model.get("hashed")):
@@ -210,7 +222,11 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
         if model.get("hashed") and getattr(ctx, "tsdf_store", None) is not None:
             tsdf_local.restore(ctx, ctx.tsdf_store)     # (a streamed model: the union of the resident and the stored blocks)
         if model.get("hashed") and not densify:
-            meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh_hashed())
+            if model.get("color"):
+                v, n, t, col = ctx.tsdf_mesh_hashed(colors=True)
+                meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), v, n, t, colors=col)
+            else:
+                meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh_hashed())
             return poses, recs, rc, out
         if model.get("hashed"):
             densify_hashed_model(ctx)

@@ -916,9 +916,9 @@ int icp_tsdf_insert_blocks(icp_ctx* ctx, int32_t n, const int32_t* coords, const
  *   needs no change: the colour is read and written only in cells and voxels the geometry touches.
  * Still refused on a coloured hashed volume (ICP_ERR_INVALID_ARG, a message that names the call, no side effect): icp_tsdf_color_create,
  *   icp_tsdf_color_release, icp_tsdf_color_download and icp_tsdf_color_upload (they address the dense array; the message points at the
- *   calls below), icp_tsdf_raycast_color, icp_set_target_tsdf_color, icp_track_depth_model_color and icp_tsdf_mesh_color, with every
- *   dense-box call listed above.  There is no coloured ray-cast, target, model loop or mesh of the blocks yet: a finished model goes into a
- *   dense coloured volume block by block (icp_get_tsdf_color_hashed, then icp_tsdf_upload and icp_tsdf_color_upload).
+ *   calls below), icp_tsdf_raycast_color, icp_set_target_tsdf_color, icp_track_depth_model_color and icp_tsdf_mesh_color (the dense-named
+ *   calls; their forms on the blocks are icp_tsdf_raycast_color_hashed, icp_set_target_tsdf_color_hashed,
+ *   icp_track_depth_model_color_hashed and icp_tsdf_mesh_color_hashed, further down), with every dense-box call listed above.
  * Legal and geometry-only on a coloured hashed volume: icp_tsdf_mesh_hashed, icp_tsdf_raycast_hashed, icp_set_target_tsdf_hashed and
  *   icp_track_depth_model_hashed; the model loop's own fusion there leaves the colours alone.
  * The new calls refuse a context without a volume, one with a dense volume and one with a hashed volume without colours. */
@@ -995,7 +995,7 @@ int icp_tsdf_mesh_hashed(icp_ctx* ctx, float min_weight, int32_t max_vertices, i
  * icp_track_depth_model_hashed: icp_track_depth_model's loop, arguments, frame records, statuses, carried pose on a failed frame, upload
  *   overlap and gt RMSE, with the target from the hashed ray-cast and the integrate icp_tsdf_integrate's on a hashed volume (the touch with
  *   its growth and room rule; growth past 2^22 blocks ends the call with ICP_ERR_INVALID_ARG).  It keeps that loop's refusals: colour ICP,
- *   colour weighting and the colored metric (the loop reads no colours, also on a coloured hashed volume, whose colours its own fusion leaves alone: there is no *_color form), GICP, and a projective camera
+ *   colour weighting and the colored metric (the loop reads no colours, also on a coloured hashed volume, whose colours its own fusion leaves alone: the coloured loop of the blocks is icp_track_depth_model_color_hashed, below), GICP, and a projective camera
  *   in the params that differs from the depth camera.  Host waits per tracked frame: icp_track_depth_model's (the hit count, the run's)
  *   and the touch's counters, plus one per growth of the pool.
  * All three: no volume, or a dense volume: ICP_ERR_INVALID_ARG with a message that names the call, nothing touched -- the dense volume's
@@ -1005,6 +1005,48 @@ int icp_tsdf_raycast_hashed(icp_ctx* ctx, const icp_depth_camera* cam, const flo
 int icp_set_target_tsdf_hashed(icp_ctx* ctx, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out);
 int icp_track_depth_model_hashed(icp_ctx* ctx, const float* depth_frames, int32_t n_frames, const icp_depth_camera* cam,
                                  const icp_depth_options* source_opt, const float* gt_frames, float pose_inout[16], icp_track_frame* out);
+
+/* -------- the coloured hashed model seen from a pose, as a coloured target, tracked frame-to-model and meshed (an extension):
+ * icp_tsdf_raycast_color, icp_set_target_tsdf_color, icp_track_depth_model_color and icp_tsdf_mesh_color on the blocks of a COLOURED HASHED
+ * volume (icp_tsdf_create_color_hashed).  DESIGN.md section 6zc.  tests/htsdf_color_view_restatement.py restates what follows, compared bit
+ * for bit. --------
+ * Every rule is an existing contract read through the other addressing; there is no new arithmetic.
+ * Coloured ray-cast (icp_tsdf_raycast_color_hashed): the march, validity, end rule, zh, the normal, the first three arrays and the hit
+ *   count are icp_tsdf_raycast_hashed's, operation for operation.  The colour of a hit is icp_tsdf_raycast_color's rule on the cell of
+ *   q(z*), the normal's cell, with its fractions (t_x, t_y, t_z): all eight corners have Wc > 0 -- the nested lerp x, then y, then z, per
+ *   channel; otherwise the corner nearest the hit (t_r >= 0.5f picks the upper one) if its Wc > 0; otherwise none.  Bytes by
+ *   floor(clamp(c, 0, 255) + 0.5), packed R | G << 8 | B << 16 | 255 << 24.  Corner (dx, dy, dz) is the colour-pool entry of the voxel at
+ *   signed global coordinate f + d, read through the block index that the geometry lookup of that same cell found: no second table probe,
+ *   and colour corners are loaded for that one cell per ray only.  A hole or an uncoloured hit is four zero bytes; *n_colored_out counts
+ *   the coloured hits.  Any output may be NULL; one host wait.
+ *   Equivalence: on blocks at non-negative coordinates the result equals icp_tsdf_raycast_color's bit for bit, all four arrays and both
+ *   counts, on the dense coloured volume with the same origin and voxel_size that holds the blocks from voxel (0, 0, 0) on and reads (0, 0) /
+ *   (0, 0, 0, 0) where no block covers a voxel.
+ * Coloured target (icp_set_target_tsdf_color_hashed): icp_set_target_tsdf_color's rule -- the SoA planes plus rgba, cr, cg, cb; an
+ *   uncoloured hit becomes a hole; *n_points_out is the coloured hits; none: ICP_ERR_NO_TARGET with an empty target.
+ * Model loop (icp_track_depth_model_color_hashed): icp_track_depth_model_color's loop with the target from the call above and the
+ *   integrate icp_tsdf_integrate_color's on a coloured hashed volume (the touch, growth and room rule).  It accepts colour ICP,
+ *   ICP_WEIGHT_COLORS and ICP_METRIC_COLORED; it refuses GICP, null rgbx_frames, source_opt->fix_color_index == 0 and a projective camera
+ *   in the params that differs from the depth camera.  Records, statuses and the carried pose of a failed frame are the dense coloured
+ *   loop's; host waits are icp_track_depth_model_hashed's.
+ * Mesh colours (icp_tsdf_mesh_color_hashed): counts, vertices, normals, triangles and their order are icp_tsdf_mesh_hashed's, bit for bit.
+ *   colors_out (max_vertices * 4 bytes, may be NULL) receives one packed colour per vertex: a vertex on the edge v -> v + d takes
+ *   icp_tsdf_mesh_color's rule -- both ends have Wc > 0: the lerp of the two at the vertex's t = F_v / (F_v - F_(v+d)); one end has: that
+ *   end's colour; neither: zero bytes.  v + d may lie in a neighbouring block.  As a SET of triangles with corner positions, normals and
+ *   colours the result equals icp_tsdf_mesh_color's on the dense coloured volume over the blocks' bounding box.
+ * Refusals: all four return ICP_ERR_INVALID_ARG with a message that names the call, and touch nothing, without a volume ("no volume"),
+ *   on a dense volume ("dense") and on a hashed volume without colours ("no colours").  The four dense-named *_color calls keep refusing
+ *   a hashed volume.  The geometry-only hashed calls stay legal on a coloured hashed volume and leave the colours alone.  None of the four
+ *   modifies the volume, except the loop's own fusion. */
+int icp_tsdf_raycast_color_hashed(icp_ctx* ctx, const icp_depth_camera* cam, const float pose[16], float* depth_out, float* vertices_out,
+                                  float* normals_out, uint8_t* rgba_out, int32_t* n_hits_out, int32_t* n_colored_out);
+int icp_set_target_tsdf_color_hashed(icp_ctx* ctx, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out);
+int icp_track_depth_model_color_hashed(icp_ctx* ctx, const float* depth_frames, const uint8_t* rgbx_frames, int32_t n_frames,
+                                       const icp_depth_camera* cam, const icp_depth_options* source_opt, const float* gt_frames,
+                                       float pose_inout[16], icp_track_frame* out);
+int icp_tsdf_mesh_color_hashed(icp_ctx* ctx, float min_weight, int32_t max_vertices, int32_t max_triangles,
+                               float* vertices_out, float* normals_out, uint8_t* colors_out, uint32_t* triangles_out,
+                               int32_t* n_vertices_out, int32_t* n_triangles_out);
 
 /* -------- direct SDF tracking with a photometric term (an extension): next to its geometric row a pixel adds an intensity row, read from
  * the colour array in the cell the distance is read in (Bylow, Olsson, Kahl, "Direct Camera Pose Tracking and Mapping With Signed Distance
