@@ -147,6 +147,10 @@ struct icp_ctx {
     // depth frames (icp_set_*_depth, icp_track_depth_frames): two upload slots, each a page-locked staging block + a device copy of
     // [depth 4n | rgbx 4n]; the next frame of a sequence goes up on depth_stream while the current one iterates
     PinBuf depth_pin[2]; DevBuf depth_dev[2]; Event depth_up[2]; bool depth_pending[2] = {false, false};
+    // the bilateral depth filter (icp_set_depth_filter_options, host_depth.hpp): its options, the device tables [spatial 81 | range 256] and
+    // whether they are current; per upload slot the filtered copy of the depth frame and whether the slot's last frame was filtered
+    icp_depth_filter_options df_opt = {0, 4.5f, 0.03f}; DevBuf df_tables; bool df_tables_ok = false; float df_inv_bin = 0.f;
+    DevBuf depth_filt[2]; bool depth_filtered[2] = {false, false};
     DevBuf depth_blocks, track_rmse;     // block counts / offsets of the depth compaction; per-frame initial + final RMSE of a tracked sequence
     PinBuf pin_track;                    // page-locked pose staging of a tracked frame's initial / final RMSE: two slots of its own, apart from `pinned`
     DevBuf tsdf_vox, tsdf_cnt; bool tsdf_on = false; icp_tsdf_options tsdf_opt;   // the TSDF volume of frame-to-model tracking (host_tsdf.hpp): (tsdf, weight) per voxel, the update / hit counter, its options (ray_step resolved)

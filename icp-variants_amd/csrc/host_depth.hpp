@@ -1,5 +1,6 @@
 // host_depth.hpp -- depth frames as clouds: back-projection, icp_set_target_depth / icp_set_source_depth, the frame-to-reference tracker
-// (icp_track_depth_frames) and the per-frame mesh (icp_depth_mesh).  Part of icp_hip.hip (included from there, after host_multi.hpp).
+// (icp_track_depth_frames), the per-frame mesh (icp_depth_mesh) and the bilateral depth filter in front of the calls that align a frame
+// (icp_set_depth_filter_options, icp_filter_depth).  Part of icp_hip.hip (included from there, after host_multi.hpp).
 namespace {
 // Inverse of a rigid/affine 4x4 (column-major, bottom row ignored) in fp64: 3x3 row-major R^-1 and t^-1 = -R^-1 t.
 void invert_affine(const float* m, double Ri[9], double ti[3]) {
@@ -31,12 +32,66 @@ int check_depth_args(icp_ctx* c, const icp_depth_camera* cam, const icp_depth_op
     return ICP_OK;
 }
 
+// ---- the bilateral depth filter (dev_depth_filter.hpp; contract: include/icp_hip.h) ----
+const char* depth_filter_options_error(const icp_depth_filter_options* o) {
+    if (!o) return "null options";
+    if (o->radius < 0 || o->radius > ICP_DEPTH_FILTER_MAX_RADIUS) return "radius must be in 0 .. 4";
+    if (!(std::isfinite(o->sigma_space) && o->sigma_space > 0.f)) return "sigma_space must be finite and > 0";
+    if (!(std::isfinite(o->sigma_range) && o->sigma_range > 0.f)) return "sigma_range must be finite and > 0";
+    if (!std::isfinite((float)(256.0 / (9.0 * (double)o->sigma_range * (double)o->sigma_range)))) return "sigma_range is too small (256 / (9 sigma_range^2) is not finite in fp32)";
+    return nullptr;
+}
+// The tables of checked options, each entry computed in fp64 and rounded once.
+void depth_filter_tables(const icp_depth_filter_options& o, float* spatial, float* range, float* inv_bin) {
+    const int r = o.radius, w = 2 * r + 1;
+    const double two_ss = 2.0 * (double)o.sigma_space * (double)o.sigma_space;
+    if (spatial && r > 0) for (int dy = -r; dy <= r; dy++) for (int dx = -r; dx <= r; dx++) spatial[(dy + r) * w + (dx + r)] = (float)exp(-(double)(dx * dx + dy * dy) / two_ss);
+    if (range) for (int q = 0; q < ICP_DEPTH_FILTER_RANGE_BINS; q++) range[q] = (float)exp(-4.5 * ((double)q + 0.5) / 256.0);
+    if (inv_bin) *inv_bin = (float)(256.0 / (9.0 * (double)o.sigma_range * (double)o.sigma_range));
+}
+// The device tables [spatial 81 | range 256] of `o`, uploaded on s and waited for (once per change of options, or per icp_filter_depth with
+// options of its own, which leaves the context's tables stale).
+int depth_filter_upload_tables(icp_ctx* c, const icp_depth_filter_options& o, hipStream_t s) {
+    constexpr int NS = (2 * ICP_DEPTH_FILTER_MAX_RADIUS + 1) * (2 * ICP_DEPTH_FILTER_MAX_RADIUS + 1);
+    float h[NS + ICP_DEPTH_FILTER_RANGE_BINS] = {0};
+    depth_filter_tables(o, h, h + NS, &c->df_inv_bin);
+    int rc;
+    if ((rc = ensure(c, c->df_tables, sizeof(h)))) return rc;
+    HIPCK(c, hipMemcpyAsync(c->df_tables.p, h, sizeof(h), hipMemcpyHostToDevice, s));
+    HIPCK(c, hipStreamSynchronize(s));
+    return ICP_OK;
+}
+// One launch of k_depth_filter<radius> on s: width x height floats at `in` -> `out`, with the device tables as they stand.
+int depth_filter_launch(icp_ctx* c, int radius, const float* in, float* out, int width, int height, hipStream_t s) {
+    constexpr int NS = (2 * ICP_DEPTH_FILTER_MAX_RADIUS + 1) * (2 * ICP_DEPTH_FILTER_MAX_RADIUS + 1);
+    DepthFilterArgs a;
+    a.in = in; a.out = out; a.spatial = c->df_tables.as<float>(); a.range = a.spatial + NS; a.width = width; a.height = height; a.inv_bin = c->df_inv_bin;
+    const dim3 grid((width + DF_TW - 1) / DF_TW, (height + DF_TH - 1) / DF_TH), block(DF_TW, DF_TH);
+    switch (radius) {
+        case 1: hipLaunchKernelGGL(k_depth_filter<1>, grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL(k_depth_filter<2>, grid, block, 0, s, a); break;
+        case 3: hipLaunchKernelGGL(k_depth_filter<3>, grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(k_depth_filter<4>, grid, block, 0, s, a); break;
+        default: c->err = "depth filter: no kernel for this radius"; return ICP_ERR_INVALID_ARG;
+    }
+    HIPCK(c, hipGetLastError());
+    return ICP_OK;
+}
+// The depth frame of upload slot `slot` as the consumers that ALIGN a frame read it: the filtered copy where stage_depth made one, else the
+// raw frame.  The consumers that fuse or export a frame, and every reader of the colour frame behind it, read depth_dev[slot] itself.
+const float* aligned_depth(const icp_ctx* c, int slot) { return c->depth_filtered[slot] ? c->depth_filt[slot].as<float>() : c->depth_dev[slot].as<float>(); }
+
 // One depth frame [depth 4n | rgbx 4n] into upload slot `slot`: host -> page-locked block -> device, on stream s (the context's own stream,
 // or depth_stream when the frame goes up while the previous one iterates); depth_up[slot] marks its arrival.  The only host-side wait is for
 // the slot's previous copy to have left the page-locked block.
 // The colour frame has n pixels unless n_color says otherwise (icp_depth_mesh's colour camera).
-int stage_depth(icp_ctx* c, int slot, const float* depth, const uint8_t* rgbx, int n, hipStream_t s, int n_color = -1) {
+// width > 0 (the callers whose frame is aligned): with the context's depth filter on, the frame is filtered on s right behind the copy, into
+// depth_filt[slot], before depth_up[slot] is recorded -- every consumer waits for that event, and the slot's reuse is ordered for the
+// filtered copy as it is for the raw one (its readers are the raw frame's readers).
+int stage_depth(icp_ctx* c, int slot, const float* depth, const uint8_t* rgbx, int n, hipStream_t s, int n_color = -1, int width = 0) {
     if (n_color < 0) n_color = n;
+    const bool filter = width > 0 && c->df_opt.radius > 0;
+    c->depth_filtered[slot] = false;
     if (!c->depth_up[slot]) HIPCK(c, hipEventCreateWithFlags(&c->depth_up[slot].e, hipEventDisableTiming));
     if (c->depth_pending[slot]) { HIPCK(c, hipEventSynchronize(c->depth_up[slot])); c->depth_pending[slot] = false; }
     const size_t bytes = (size_t)n * 4 + (rgbx ? (size_t)n_color * 4 : 0), cap = (size_t)n * 4 + (size_t)(n_color > n ? n_color : n) * 4;
@@ -46,7 +101,15 @@ int stage_depth(icp_ctx* c, int slot, const float* depth, const uint8_t* rgbx, i
     if ((rc = ensure(c, c->depth_dev[slot], cap))) return rc;
     memcpy(pin.p, depth, (size_t)n * 4);
     if (rgbx) memcpy(pin.as<char>() + (size_t)n * 4, rgbx, (size_t)n_color * 4);
+    if (filter) {
+        if ((rc = ensure(c, c->depth_filt[slot], (size_t)n * 4))) return rc;
+        if (!c->df_tables_ok) { if ((rc = depth_filter_upload_tables(c, c->df_opt, s))) return rc; c->df_tables_ok = true; }
+    }
     HIPCK(c, hipMemcpyAsync(c->depth_dev[slot].p, pin.p, bytes, hipMemcpyHostToDevice, s));
+    if (filter) {
+        if ((rc = depth_filter_launch(c, c->df_opt.radius, c->depth_dev[slot].as<float>(), c->depth_filt[slot].as<float>(), width, n / width, s))) return rc;
+        c->depth_filtered[slot] = true;
+    }
     HIPCK(c, hipEventRecord(c->depth_up[slot], s)); c->depth_pending[slot] = true;
     return ICP_OK;
 }
@@ -62,7 +125,7 @@ int depth_to_cloud(icp_ctx* c, int slot, const icp_depth_camera& cam, const icp_
     const int nb = (count + 255) / 256, cap = (count + 63) / 64 * 64;
     HIPCK(c, hipStreamWaitEvent(c->stream, c->depth_up[slot], 0));
     DepthFrame fr;
-    fr.depth = c->depth_dev[slot].as<float>(); fr.rgbx = with_colors ? c->depth_dev[slot].as<uint8_t>() + (size_t)n * 4 : nullptr;
+    fr.depth = aligned_depth(c, slot); fr.rgbx = with_colors ? c->depth_dev[slot].as<uint8_t>() + (size_t)n * 4 : nullptr;
     fr.width = cam.width; fr.height = cam.height; fr.factor = f; fr.count = count;
     fr.fx = cam.fx; fr.fy = cam.fy; fr.cx = cam.cx; fr.cy = cam.cy; fr.max_distance_halved = opt.max_distance / 2.f;
     invert_extrinsics(cam.extrinsics, fr.inv);
@@ -134,7 +197,7 @@ static int set_cloud_depth(icp_ctx* c, bool target, const float* depth, const ui
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     int kept = 0;
-    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream, -1, cam->width))) return rc;
     if ((rc = depth_to_cloud(c, 0, *cam, *opt, rgbx != nullptr, target ? c->tgt : c->src, target, &kept))) return rc;
     if (n_points_out) *n_points_out = kept;
     if (target) {
@@ -210,9 +273,9 @@ int icp_track_depth_frames(icp_ctx* c, const float* depth_frames, const uint8_t*
     if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     // frame 0 = the target, its index built once (main.cpp:200-207); frame 1 goes up meanwhile
     int kept = 0;
-    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream, -1, cam->width))) return rc;
     if ((rc = depth_to_cloud(c, 0, *cam, *target_opt, rgbx_frames != nullptr, c->tgt, true, &kept))) return rc;
-    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream))) return rc;
+    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream, -1, cam->width))) return rc;
     if (kept == 0) {
         c->bvh.valid = false; c->bvh6.valid = false;
         for (int k = 1; k < n_frames; k++) { icp_track_frame& r = out[k - 1]; memset(&r, 0, sizeof(r)); r.status = ICP_ERR_NO_TARGET; r.initial_rmse = r.final_rmse = -1.f; memcpy(r.pose, pose_inout, 64); }
@@ -229,7 +292,7 @@ int icp_track_depth_frames(icp_ctx* c, const float* depth_frames, const uint8_t*
         const int slot = k & 1;
         if ((rc = depth_to_cloud(c, slot, *cam, *source_opt, rgbx_frames != nullptr, c->src, false, &kept))) return rc;
         // frame k + 1 goes up on the second stream while frame k iterates (its slot was last read by frame k - 1, which has finished)
-        if (k + 1 < n_frames && (rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream))) return rc;
+        if (k + 1 < n_frames && (rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream, -1, cam->width))) return rc;
         if ((rc = finish_source(c))) return rc;
         r.n_src = kept;
         if (kept == 0) {                                   // nothing to align: the pose is carried unchanged, tracking goes on
@@ -329,5 +392,93 @@ int icp_depth_mesh(icp_ctx* c, const float* depth, const uint8_t* rgbx, const ic
         HIPCK(c, hipStreamSynchronize(c->stream));
     }
     *n_triangles_out = nt;
+    return guard.done();
+}
+
+int icp_depth_filter_options_default(icp_depth_filter_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    o->radius = 0; o->sigma_space = 4.5f; o->sigma_range = 0.03f;
+    return ICP_OK;
+}
+int icp_depth_filter_options_check(const icp_depth_filter_options* o) { return depth_filter_options_error(o) ? ICP_ERR_INVALID_ARG : ICP_OK; }
+int icp_set_depth_filter_options(icp_ctx* c, const icp_depth_filter_options* o) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    icp_depth_filter_options v;
+    if (o) v = *o; else icp_depth_filter_options_default(&v);
+    if (const char* why = depth_filter_options_error(&v)) { c->err = std::string("icp_set_depth_filter_options: ") + why; return ICP_ERR_INVALID_ARG; }
+    c->df_opt = v; c->df_tables_ok = false;      // (the device tables follow at the next frame that is filtered)
+    return ICP_OK;
+}
+int icp_get_depth_filter_options(const icp_ctx* c, icp_depth_filter_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->df_opt; return ICP_OK; }
+int icp_depth_filter_tables(const icp_depth_filter_options* o, float* spatial_out, float* range_out, float* inv_bin_out) {
+    if (depth_filter_options_error(o)) return ICP_ERR_INVALID_ARG;
+    depth_filter_tables(*o, spatial_out, range_out, inv_bin_out);
+    return ICP_OK;
+}
+
+// Scratch: `staging` = [in 4n | out 4n]; the device tables are left stale for the context's own options when `opt` is given.
+int icp_filter_depth(icp_ctx* c, const float* depth, int32_t width, int32_t height, const icp_depth_filter_options* opt, float* depth_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    if (!depth || !depth_out || width <= 0 || height <= 0 || (long long)width * height > 0x7FFFFFFFll) { c->err = "icp_filter_depth: bad argument (null frame, width, height > 0)"; return ICP_ERR_INVALID_ARG; }
+    const icp_depth_filter_options o = opt ? *opt : c->df_opt;
+    if (const char* why = depth_filter_options_error(&o)) { c->err = std::string("icp_filter_depth: ") + why; return ICP_ERR_INVALID_ARG; }
+    const size_t n = (size_t)width * height;
+    if (o.radius == 0) { if (depth_out != depth) memmove(depth_out, depth, n * 4); return ICP_OK; }
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ensure(c, c->staging, n * 8))) return rc;
+    if (opt || !c->df_tables_ok) { if ((rc = depth_filter_upload_tables(c, o, c->stream))) return rc; c->df_tables_ok = !opt; }
+    float* d_in = c->staging.as<float>(); float* d_out = d_in + n;
+    HIPCK(c, hipMemcpyAsync(d_in, depth, n * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = depth_filter_launch(c, o.radius, d_in, d_out, width, height, c->stream))) return rc;
+    HIPCK(c, hipMemcpyAsync(depth_out, d_out, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+
+// Not part of icp_hip.h (tools/time_depth_filter.py): the device time of `reps` launches of the filter with the context's options (radius
+// > 0) on a frame already on the device, between two events (which = 0), or of as many device-to-device copies of the frame (which = 1).
+extern "C" int icp_debug_depth_filter_time(icp_ctx* c, int32_t which, const float* depth, int32_t width, int32_t height, int32_t reps, float* ms_out) {
+    if (!c || !ms_out || !depth || which < 0 || which > 1 || width <= 0 || height <= 0 || reps < 1 || (which == 0 && c->df_opt.radius < 1)) return ICP_ERR_INVALID_ARG;
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    if ((rc = ensure_events(c, 2))) return rc;
+    const size_t n = (size_t)width * height;
+    if ((rc = ensure(c, c->staging, n * 8))) return rc;
+    if (!c->df_tables_ok && which == 0) { if ((rc = depth_filter_upload_tables(c, c->df_opt, c->stream))) return rc; c->df_tables_ok = true; }
+    float* d_in = c->staging.as<float>(); float* d_out = d_in + n;
+    HIPCK(c, hipMemcpyAsync(d_in, depth, n * 4, hipMemcpyHostToDevice, c->stream));
+    for (int pass = 0; pass < 2; pass++) {               // (pass 0 warm: the first launch loads the code object)
+        HIPCK(c, hipEventRecord(c->events[0], c->stream));
+        for (int k = 0; k < (pass ? reps : 1); k++) {
+            if (which == 0) { if ((rc = depth_filter_launch(c, c->df_opt.radius, d_in, d_out, width, height, c->stream))) return rc; }
+            else HIPCK(c, hipMemcpyAsync(d_out, d_in, n * 4, hipMemcpyDeviceToDevice, c->stream));
+        }
+        HIPCK(c, hipEventRecord(c->events[1], c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+    }
+    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
+    return guard.done();
+}
+
+// Not part of icp_hip.h (tests/test_gpu_depth_filter.py): the resident target (which = 0) or source (1) back on the host as it stands -- the
+// first min(max_points, n) entries of the six planes x y z nx ny nz at planes_out + k * max_points and of the packed colours at rgba_out
+// (either may be NULL); *n_out = n, *flags_out = has_normals | has_colors << 1.
+extern "C" int icp_debug_get_cloud(icp_ctx* c, int32_t which, float* planes_out, uint32_t* rgba_out, int32_t max_points, int32_t* n_out, int32_t* flags_out) {
+    if (!c || which < 0 || which > 1 || max_points < 0 || !n_out) return ICP_ERR_INVALID_ARG;
+    const Cloud& cl = which ? c->src : c->tgt;
+    *n_out = cl.n;
+    if (flags_out) *flags_out = (cl.has_normals ? 1 : 0) | (cl.has_colors ? 2 : 0);
+    const size_t m = (size_t)(cl.n < max_points ? cl.n : max_points);
+    if (m == 0) return ICP_OK;
+    DrainOnError guard(c);
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    const DevBuf* pl[6] = {&cl.x, &cl.y, &cl.z, &cl.nx, &cl.ny, &cl.nz};
+    if (planes_out) for (int k = 0; k < (cl.has_normals ? 6 : 3); k++) HIPCK(c, hipMemcpy(planes_out + (size_t)k * max_points, pl[k]->p, m * 4, hipMemcpyDeviceToHost));
+    if (rgba_out && cl.has_colors) HIPCK(c, hipMemcpy(rgba_out, cl.rgba.p, m * 4, hipMemcpyDeviceToHost));
     return guard.done();
 }

@@ -39,7 +39,7 @@ int sdf_plan(icp_ctx* c, const icp_depth_camera& cam, const icp_sdf_options& opt
 // k_sdf_accumulate and k_sdf_solve (step = false: one pair that only folds).  Nothing here waits; the launches behind the frame's end drain.
 int sdf_enqueue(icp_ctx* c, int slot, const SdfPlan& pl, const icp_sdf_options& opt, const float pose[16], bool step, bool trace) {
     SdfFrame f = pl.f;
-    f.depth = c->depth_dev[slot].as<float>();
+    f.depth = aligned_depth(c, slot);
     SdfState* st = c->sdf_state.as<SdfState>();
     icp_sdf_frame* rec = c->sdf_rec.as<icp_sdf_frame>();
     icp_sdf_iter* tr = (icp_sdf_iter*)(rec + 1);
@@ -128,7 +128,7 @@ int icp_tsdf_sdf_system(icp_ctx* c, const float* depth, const icp_depth_camera* 
     if ((rc = set_device(c))) return rc;
     SdfPlan pl;
     if ((rc = sdf_plan(c, *cam, *opt, &pl))) return rc;
-    if ((rc = stage_depth(c, 0, depth, nullptr, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth, nullptr, cam->width * cam->height, c->stream, -1, cam->width))) return rc;
     if ((rc = sdf_enqueue(c, 0, pl, *opt, pose, false, false))) return rc;
     if ((rc = ensure_pinned(c, 2048 + sizeof(SdfState)))) return rc;
     SdfState* h = (SdfState*)(c->pinned.as<char>() + 2048);
@@ -148,7 +148,7 @@ int icp_tsdf_align_depth(icp_ctx* c, const float* depth, const icp_depth_camera*
     if ((rc = set_device(c))) return rc;
     SdfPlan pl;
     if ((rc = sdf_plan(c, *cam, *opt, &pl))) return rc;
-    if ((rc = stage_depth(c, 0, depth, nullptr, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth, nullptr, cam->width * cam->height, c->stream, -1, cam->width))) return rc;
     if ((rc = sdf_enqueue(c, 0, pl, *opt, pose_inout, true, trace_out != nullptr))) return rc;
     icp_sdf_frame r;
     if ((rc = sdf_read_record(c, *opt, &r, trace_out))) return rc;
@@ -176,10 +176,10 @@ int icp_track_depth_sdf(icp_ctx* c, const float* depth_frames, const uint8_t* rg
     if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     if (!c->sdf_ev) HIPCK(c, hipEventCreateWithFlags(&c->sdf_ev.e, hipEventDisableTiming));
     // frame 0 into the model at the incoming pose; frame 1 goes up meanwhile
-    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream, -1, cam->width))) return rc;
     if ((rc = sdf_integrate_slot(c, 0, *cam, pose_inout, color, who))) return rc;
     HIPCK(c, hipEventRecord(c->sdf_ev, c->stream));
-    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream))) return rc;
+    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream, -1, cam->width))) return rc;
     int first_err = ICP_OK;
     for (int k = 1; k < n_frames; k++) {
         const int slot = k & 1;
@@ -188,7 +188,7 @@ int icp_track_depth_sdf(icp_ctx* c, const float* depth_frames, const uint8_t* rg
         // earlier one), which may still be running -- the copy waits for it on the device, the host does not
         if (k + 1 < n_frames) {
             HIPCK(c, hipStreamWaitEvent(c->depth_stream, c->sdf_ev, 0));
-            if ((rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream))) return rc;
+            if ((rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream, -1, cam->width))) return rc;
         }
         icp_sdf_frame& r = out[k - 1];
         if ((rc = sdf_read_record(c, *opt, &r, nullptr))) return rc;
@@ -215,7 +215,7 @@ extern "C" int icp_debug_sdf_time(icp_ctx* c, const float* depth, const icp_dept
     if ((rc = ensure_events(c, 2))) return rc;
     SdfPlan pl;
     if ((rc = sdf_plan(c, *cam, *opt, &pl))) return rc;
-    if ((rc = stage_depth(c, 0, depth, nullptr, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth, nullptr, cam->width * cam->height, c->stream, -1, cam->width))) return rc;
     icp_sdf_options one = *opt; one.n_iterations = 1;
     if ((rc = sdf_enqueue(c, 0, pl, one, pose, true, false))) return rc;      // (warm: the first launch loads the code object)
     HIPCK(c, hipStreamSynchronize(c->stream));

@@ -35,10 +35,10 @@ int sdf_color_plan(icp_ctx* c, const icp_depth_camera& cam, const icp_sdf_option
 // sdf_enqueue with the coloured kernels: the slot holds the depth frame and, behind it, its colour frame (stage_depth).
 int sdf_color_enqueue(icp_ctx* c, int slot, const SdfPlan& pl, const icp_sdf_options& opt, const icp_sdf_color_options& copt, const float pose[16], bool step, bool trace) {
     SdfFrame f = pl.f;
-    f.depth = c->depth_dev[slot].as<float>();
+    f.depth = aligned_depth(c, slot);
     SdfColorFrame cf;
     const bool hashed = c->tsdf_hashed;
-    cf.col = hashed ? c->th_cpool.as<float4>() : c->tsdf_col.as<float4>(); cf.rgbx = (const uint32_t*)(f.depth + (size_t)f.width * f.height); cf.weight = copt.weight; cf.huber = copt.huber;
+    cf.col = hashed ? c->th_cpool.as<float4>() : c->tsdf_col.as<float4>(); cf.rgbx = (const uint32_t*)(c->depth_dev[slot].as<float>() + (size_t)f.width * f.height); cf.weight = copt.weight; cf.huber = copt.huber;
     SdfColorState* st = c->sdf_state.as<SdfColorState>();
     icp_sdf_color_frame* rec = c->sdf_rec.as<icp_sdf_color_frame>();
     icp_sdf_color_iter* tr = (icp_sdf_color_iter*)(rec + 1);
@@ -128,7 +128,7 @@ int icp_tsdf_sdf_system_color(icp_ctx* c, const float* depth, const uint8_t* rgb
     if ((rc = set_device(c))) return rc;
     SdfPlan pl;
     if ((rc = sdf_color_plan(c, *cam, *opt, &pl))) return rc;
-    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream, -1, cam->width))) return rc;
     if ((rc = sdf_color_enqueue(c, 0, pl, *opt, *copt, pose, false, false))) return rc;
     if ((rc = ensure_pinned(c, 2048 + sizeof(SdfColorState)))) return rc;
     SdfColorState* h = (SdfColorState*)(c->pinned.as<char>() + 2048);
@@ -148,7 +148,7 @@ int icp_tsdf_align_depth_color(icp_ctx* c, const float* depth, const uint8_t* rg
     if ((rc = set_device(c))) return rc;
     SdfPlan pl;
     if ((rc = sdf_color_plan(c, *cam, *opt, &pl))) return rc;
-    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream, -1, cam->width))) return rc;
     if ((rc = sdf_color_enqueue(c, 0, pl, *opt, *copt, pose_inout, true, trace_out != nullptr))) return rc;
     icp_sdf_color_frame r;
     if ((rc = sdf_color_read_record(c, *opt, &r, trace_out))) return rc;
@@ -175,17 +175,17 @@ int icp_track_depth_sdf_color(icp_ctx* c, const float* depth_frames, const uint8
     if ((rc = sdf_color_plan(c, *cam, *opt, &pl))) return rc;
     if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     if (!c->sdf_ev) HIPCK(c, hipEventCreateWithFlags(&c->sdf_ev.e, hipEventDisableTiming));
-    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream, -1, cam->width))) return rc;
     if ((rc = sdf_color_integrate_slot(c, 0, *cam, pose_inout, who))) return rc;
     HIPCK(c, hipEventRecord(c->sdf_ev, c->stream));
-    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream))) return rc;
+    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream, -1, cam->width))) return rc;
     int first_err = ICP_OK;
     for (int k = 1; k < n_frames; k++) {
         const int slot = k & 1;
         if ((rc = sdf_color_enqueue(c, slot, pl, *opt, *copt, pose_inout, true, false))) return rc;
         if (k + 1 < n_frames) {                        // (the other slot was last read by the integration of frame k - 1: the copy waits for it on the device)
             HIPCK(c, hipStreamWaitEvent(c->depth_stream, c->sdf_ev, 0));
-            if ((rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream))) return rc;
+            if ((rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream, -1, cam->width))) return rc;
         }
         icp_sdf_color_frame& r = out[k - 1];
         if ((rc = sdf_color_read_record(c, *opt, &r, nullptr))) return rc;
@@ -212,7 +212,7 @@ extern "C" int icp_debug_sdf_color_time(icp_ctx* c, const float* depth, const ui
     if ((rc = ensure_events(c, 2))) return rc;
     SdfPlan pl;
     if ((rc = sdf_color_plan(c, *cam, *opt, &pl))) return rc;
-    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth, rgbx, cam->width * cam->height, c->stream, -1, cam->width))) return rc;
     icp_sdf_options one = *opt; one.n_iterations = 1;
     if ((rc = sdf_color_enqueue(c, 0, pl, one, *copt, pose, true, false))) return rc;      // (warm: the first launch loads the code object)
     HIPCK(c, hipStreamSynchronize(c->stream));

@@ -439,9 +439,9 @@ static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_
     auto integrate = [&](int slot) { return hashed ? htsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, who.c_str(), color) : tsdf_integrate_slot(c, slot, *cam, pose_inout, nullptr, color); };
     if (!c->depth_stream) HIPCK(c, hipStreamCreateWithFlags(&c->depth_stream.s, hipStreamNonBlocking));
     // frame 0 into the model at the incoming pose; frame 1 goes up meanwhile
-    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream))) return rc;
+    if ((rc = stage_depth(c, 0, depth_frames, frame_rgbx(0), n, c->stream, -1, cam->width))) return rc;
     if ((rc = integrate(0))) return rc;
-    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream))) return rc;
+    if (n_frames > 1 && (rc = stage_depth(c, 1, depth_frames + (size_t)n, frame_rgbx(1), n, c->depth_stream, -1, cam->width))) return rc;
     if (gt_frames && n_frames > 1 && (rc = track_rmse_prepare(c, n_frames))) return rc;
     static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     int first_err = ICP_OK;
@@ -459,7 +459,7 @@ static int track_depth_model(icp_ctx* c, const float* depth_frames, const uint8_
         if (trc != ICP_OK && trc != ICP_ERR_NO_TARGET) return trc;
         if ((rc = depth_to_cloud(c, slot, *cam, *source_opt, color, c->src, false, &kept))) return rc;
         // frame k + 1 goes up on the second stream while frame k iterates (its slot was last read by frame k - 1, which has finished)
-        if (k + 1 < n_frames && (rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream))) return rc;
+        if (k + 1 < n_frames && (rc = stage_depth(c, slot ^ 1, depth_frames + (size_t)(k + 1) * n, frame_rgbx(k + 1), n, c->depth_stream, -1, cam->width))) return rc;
         if ((rc = finish_source(c))) return rc;
         r.n_src = kept;
         if (trc == ICP_ERR_NO_TARGET) { fail(r, ICP_ERR_NO_TARGET, who + (color ? ": the ray-cast of the model hits nothing that has a colour" : ": the ray-cast of the model hits nothing")); continue; }

@@ -6,7 +6,7 @@
 // (oracle/icp_oracle.cpp), so match indices / distances / weights are bit-identical to it.
 // fp32 sqrt and divide are correctly rounded (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt).
 //
-// Files: dev_common.hpp, dev_depth.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_converge.hpp, dev_solve.hpp,
+// Files: dev_common.hpp, dev_depth.hpp, dev_depth_filter.hpp, dev_knn_brute.hpp, dev_bvh.hpp, dev_normals.hpp, dev_projective.hpp, dev_post.hpp, dev_converge.hpp, dev_solve.hpp,
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
 // dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf_color.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp, dev_sdf.hpp, dev_sdf_color.hpp, dev_vgicp.hpp,
 // dev_vmap.hpp, dev_hmap.hpp, dev_tsdf_hash.hpp, dev_tsdf_hash_raycast.hpp, dev_tsdf_hash_mesh.hpp, dev_tsdf_hash_evict.hpp, dev_tsdf_hash_color.hpp,
@@ -33,6 +33,8 @@
 //   k_rmse_partial      ConvergenceMeasure::rmseAlignmentError (ConvergenceMeasure.h:50-66)
 //   k_depth_count /     PointCloud(depthMap, colorFrame, ...) (PointCloud.h:78-165): back-projection, normals, stride and filter of a
 //   k_depth_scatter     depth frame as a stable two-pass compaction straight into a context cloud (dev_depth.hpp)
+//   k_depth_filter<R>   the bilateral depth filter in front of the trackers (icp_set_depth_filter_options): a tile with its halo and the
+//                       two host-built weight tables in LDS, the window of (2R + 1)^2 taps unrolled (dev_depth_filter.hpp)
 //   k_*_multi           multi-start ICP (icp_run_multistart): the matcher, post stage and reduce / solve of every start in ONE launch,
 //                       start = blockIdx.y; k_score_multi / k_score_fold score the final poses (dev_multi.hpp)
 //   k_gicp_normals<K>   Generalized-ICP (plane-to-plane): per-point normals from a K-NN PCA; k_post_gicp weights, rejects and filters as
@@ -92,6 +94,7 @@ namespace icpdev {
 
 #include "dev_common.hpp"
 #include "dev_depth.hpp"
+#include "dev_depth_filter.hpp"
 #include "dev_knn_brute.hpp"
 #include "dev_bvh.hpp"
 #include "dev_normals.hpp"

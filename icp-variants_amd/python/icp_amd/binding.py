@@ -252,6 +252,56 @@ def voxel_map_extent(lower, upper, voxel_size):
     return tuple(int(v) for v in lo), tuple(int(v) for v in hi - lo + 1)
 
 
+class IcpDepthFilterOptions(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("sigma_space", C.c_float), ("sigma_range", C.c_float)]
+
+
+DEPTH_FILTER_TILE = (32, 8)              # ICP_DEPTH_FILTER_TILE_W x ICP_DEPTH_FILTER_TILE_H: the pixels of one block of the filter kernel
+
+
+def depth_filter_options(**kw):
+    """icp_depth_filter_options: icp_depth_filter_options_default (radius 0 = off, sigma_space 4.5 pixels, sigma_range 0.03 m) with any field
+    overridden by name."""
+    o = IcpDepthFilterOptions()
+    rc = load_library().icp_depth_filter_options_default(C.byref(o))
+    if rc != ICP_OK:
+        raise IcpError(rc, "icp_depth_filter_options_default")
+    for k, v in kw.items():
+        if not any(k == f[0] for f in IcpDepthFilterOptions._fields_):
+            raise TypeError("icp_depth_filter_options has no field %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def depth_filter_tables(options=None, **kw):
+    """icp_depth_filter_tables: the tables the device filters with under `options` (an IcpDepthFilterOptions, or `depth_filter_options`'
+    arguments): (spatial (2r + 1, 2r + 1) fp32, range (256,) fp32, inv_bin as an np.float32).  Needs no device."""
+    o = options if options is not None else depth_filter_options(**kw)
+    w = 2 * min(max(int(o.radius), 0), 4) + 1          # (bad options are the library's to refuse)
+    S =np.zeros((w, w), np.float32); R = np.zeros(256, np.float32); ib = C.c_float(0)
+    rc = load_library().icp_depth_filter_tables(C.byref(o), _ptr(S), _ptr(R), C.byref(ib))
+    if rc != ICP_OK:
+        raise IcpError(rc, "icp_depth_filter_tables: bad options")
+    return S, R, np.float32(ib.value)
+
+
+class depth_filter_scope:
+    """The runners' `depth_filter=` argument: the context's depth filter set from a dict of `Context.set_depth_filter` arguments inside
+    the `with` block, the previous setting put back behind it."""
+
+    def __init__(self, ctx, depth_filter):
+        self.ctx, self.new = ctx, dict(depth_filter)
+
+    def __enter__(self):
+        self.old = self.ctx.depth_filter_options()
+        self.ctx.set_depth_filter(**self.new)
+        return self.ctx
+
+    def __exit__(self, *exc):
+        self.ctx.set_depth_filter(self.old.radius, self.old.sigma_space, self.old.sigma_range)
+        return False
+
+
 class IcpSdfColorOptions(C.Structure):
     _fields_ = [("weight", C.c_float), ("huber", C.c_float)]
 
@@ -463,6 +513,8 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_raycast_color_hashed", "icp_set_target_tsdf_color_hashed", "icp_track_depth_model_color_hashed", "icp_tsdf_mesh_color_hashed",
            "icp_sdf_color_options_default", "icp_sdf_color_options_check", "icp_tsdf_sample_color", "icp_tsdf_sdf_system_color", "icp_tsdf_align_depth_color",
            "icp_track_depth_sdf_color",
+           "icp_depth_filter_options_default", "icp_depth_filter_options_check", "icp_set_depth_filter_options", "icp_get_depth_filter_options",
+           "icp_depth_filter_tables", "icp_filter_depth",
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
            "icp_voxel_map_options_check", "icp_voxel_map_create", "icp_voxel_map_destroy", "icp_voxel_map_insert", "icp_get_voxel_map", "icp_voxel_map_upload",
            "icp_voxel_map_system", "icp_voxel_map_align", "icp_track_scans_vmap",
@@ -960,6 +1012,30 @@ class Context:
         n, rc = self._set_depth(self.lib.icp_set_source_depth, depth, rgbx, cam, opt, check)
         self.n_src = n
         return n if check else (n, rc)
+
+    def set_depth_filter(self, radius=3, sigma_space=4.5, sigma_range=0.03):
+        """icp_set_depth_filter_options: the bilateral depth filter in front of every call that aligns a depth frame (DESIGN.md section
+        6zd): window (2 radius + 1)^2, radius 1 .. 4; radius=0 switches it off.  Fusion, the depth mesh and the back-projection keep
+        reading the raw frame."""
+        o = IcpDepthFilterOptions(int(radius), float(sigma_space), float(sigma_range))
+        self._ck(self.lib.icp_set_depth_filter_options(self.h, C.byref(o)))
+        return o
+
+    def depth_filter_options(self):
+        o = IcpDepthFilterOptions()
+        self._ck(self.lib.icp_get_depth_filter_options(self.h, C.byref(o)))
+        return o
+
+    def filter_depth(self, depth, options=None, **kw):
+        """icp_filter_depth: one depth frame (h, w) filtered on the device, host to host.  options: an IcpDepthFilterOptions, or
+        `depth_filter_options`' arguments; neither: the context's options (radius 0: a copy of the frame)."""
+        d = np.ascontiguousarray(depth, dtype=np.float32)
+        if d.ndim != 2:
+            raise ValueError("the depth frame must be a (height, width) image")
+        o = options if options is not None else (depth_filter_options(**kw) if kw else None)
+        out = np.empty_like(d)
+        self._ck(self.lib.icp_filter_depth(self.h, _ptr(d), C.c_int32(d.shape[1]), C.c_int32(d.shape[0]), None if o is None else C.byref(o), _ptr(out)))
+        return out
 
     def track_depth_frames(self, depth_frames, rgbx_frames, cam, target_opt, source_opt, gt=None, pose=None):
         """icp_track_depth_frames: reconstructRoom's tracking loop (main.cpp:183-341) over frames (n, h, w) [+ colours (n, h*w, 4)].

@@ -222,12 +222,12 @@ def tum_K(width):
     return np.array([[525.0 * s, 0, (319.5 + 0.5) * s - 0.5], [0, 525.0 * s, (239.5 + 0.5) * s - 0.5], [0, 0, 1]], np.float32)
 
 
-def camera_sequence(n, width, height, seed=0x7A11, hole_frac=0.05):
+def camera_sequence(n, width, height, seed=0x7A11, hole_frac=0.05, sigma=0.0):
     """n organised frames of the hand-held camera at tum_K(width): (K, depth (n, H, W) with MINF holes, rgbx (n, W*H, 4) bytes,
-    gt: the n - 1 fp32 transforms frame k -> frame 0)."""
+    gt: the n - 1 fp32 transforms frame k -> frame 0).  sigma: `depth_frame`'s Gaussian depth noise in metres (0: none, the frames as ever)."""
     K = tum_K(width)
     T = [camera_pose(k, seed) for k in range(n)]
-    made = [depth_frame(Tk, K.astype(np.float64), width, height, seed + k, hole_frac) for k, Tk in enumerate(T)]
+    made = [depth_frame(Tk, K.astype(np.float64), width, height, seed + k, hole_frac, sigma=sigma) for k, Tk in enumerate(T)]
     depth = np.stack([m[0][:, 2].reshape(height, width).copy() for m in made])
     gt = [(np.linalg.inv(T[0]) @ Tk).astype(np.float32) for Tk in T[1:]]
     return K, depth, np.stack([m[2] for m in made]), gt

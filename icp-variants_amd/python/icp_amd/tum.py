@@ -73,7 +73,7 @@ def reconstruct_room_params(params, K=TUM_K, width=TUM_WIDTH, height=TUM_HEIGHT)
     return params
 
 
-def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None, reciprocal=None, model=None, options=None, sdf=None):
+def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None, reciprocal=None, model=None, options=None, sdf=None, depth_filter=None):
     """reconstructRoom's loop on the device.  params: the variant's icp_params (metric, matching, colour ICP, weighting, multires, ...;
     ctx.params when None); reconstruct_room_params then sets what reconstructRoom sets on top of them -- 35 iterations, max distance 0.1
     and, for projective matching, the sequence's camera.  Returns (camera poses: the identity for frame 0, then currentCameraToWorld^-1
@@ -116,7 +116,13 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     model=dict(hashed=True, keep_radius=R, ...) with `sdf` keeps only the blocks within R metres of the camera on the device and streams
     the rest to the host and back (tsdf_local.track_depth_sdf_local): the poses and records are those of the
     unbounded run, the stored blocks are left in ctx.tsdf_store (tsdf_local.restore(ctx, ctx.tsdf_store) puts the whole model back).
-    keep_radius without hashed=True, or together with raycast=True, is a ValueError; keep_radius=None, the default, changes nothing."""
+    keep_radius without hashed=True, or together with raycast=True, is a ValueError; keep_radius=None, the default, changes nothing.
+    depth_filter: a dict of `Context.set_depth_filter` arguments (radius, sigma_space, sigma_range) tracks with the bilateral depth filter
+     set that way for this call -- every frame is aligned as filtered and fused as it came -- and puts the
+    context's previous setting back; None, the default, touches nothing."""
+    if depth_filter is not None:
+        with binding.depth_filter_scope(ctx, depth_filter):
+            return track(ctx, seq, params, with_gt, nonlinear, convergence, reciprocal, model, options, sdf)
     hashed = bool(model is not None and model.get("hashed"))
     raycast = bool(model is not None and model.get("raycast"))
     keep_radius = model.get("keep_radius") if model is not None else None
@@ -189,7 +195,7 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     return poses, recs, rc
 
 
-def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None, model_mesh=None, sdf=None, densify=True):
+def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None, model_mesh=None, sdf=None, densify=True, depth_filter=None):
     """reconstructRoom end to end: `track`, then saveRoomToFile (utils.h:179-193) for every scheduled frame k --
     joinMeshes(SimpleMesh(sensor, pose_k, edge_threshold) on the device, SimpleMesh::camera(pose_k, camera_scale), identity) with pose_k
     the camera pose `track` returned (the identity for frame 0).  With out_dir the meshes are written as mesh_<frame index>.off
@@ -201,10 +207,10 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
     does not fit a dense volume; densify=False meshes it in place instead
     (Context.tsdf_mesh_hashed, DESIGN.md sections 6y and 6zc; with per-vertex colours when the model has them): nothing but the mesh crosses to the host, no box is built and the context keeps its hashed volume.
     densify=False with a model that is not hashed is a ValueError.  sdf: as `track` (direct SDF tracking against the model); a hashed model
-    with raycast=True and no `sdf` is tracked against its ray-cast instead, as `track` says.  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    with raycast=True and no `sdf` is tracked against its ray-cast instead, as `track` says.  depth_filter: as `track` (the per-frame depth meshes are built from the raw frames).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
     if not densify and not (model is not None and model.get("hashed")):
         raise ValueError("densify=False meshes a hashed model in place: pass model=dict(hashed=True, ...)")
-    poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model, sdf=sdf)
+    poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model, sdf=sdf, depth_filter=depth_filter)
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)

@@ -1436,6 +1436,42 @@ int icp_register_global(icp_ctx* ctx, float* poses_out, icp_global_hypothesis* b
 /* Every hypothesis of the last icp_register_global, in order of h. */
 int icp_get_global_hypotheses(const icp_ctx* ctx, icp_global_hypothesis* out, int32_t max_out, int32_t* count_out);
 
+/* -------- bilateral depth filter: KinectFusion's first stage, in front of every tracker that aligns a depth frame --------
+ * Off by default (radius 0): nothing changes.  With radius > 0 every depth frame a call takes is filtered on the device right after its
+ * upload, into a second buffer, and the consumers that ALIGN a frame read the filtered one: the depth clouds (icp_set_target_depth,
+ * icp_set_source_depth, icp_track_depth_frames, the source of every icp_track_depth_model*), and the direct SDF calls (icp_tsdf_sdf_system,
+ * icp_tsdf_align_depth, icp_track_depth_sdf and their _color forms).  The consumers that FUSE or EXPORT a frame keep reading the raw one:
+ * every integrate (dense and hashed, geometric and coloured, the hashed touch and allocation included), icp_depth_mesh and
+ * icp_backproject_depth.  Colour frames are never filtered.
+ *
+ * Contract (fp32, the operations in the order written, one rounding each; the device evaluates no exp):
+ *   Tables, computed in fp64 and rounded once: S[(dy + r)(2r + 1) + (dx + r)] = (float)exp(-(dx^2 + dy^2) / (2 sigma_space^2));
+ *   R[q] = (float)exp(-4.5 (q + 0.5) / 256), q = 0 .. 255 (the cut-off is 3 sigma_range, so R does not depend on the options);
+ *   inv_bin = (float)(256 / (9 sigma_range^2)).
+ *   A depth is USABLE iff it is finite and > 0.  Pixel (u, v) with centre c: c not usable -> the output is c unchanged (holes stay holes;
+ *   MINF, NaN, +inf, 0 and negatives pass through).  Else num = 0, den = 0; for dy = -r .. r (outer), dx = -r .. r (inner): skip a
+ *   neighbour outside the image; n = its depth, skip unless usable; D = n - c; e = D * D; t = e * inv_bin; skip unless t < 256.0f (which
+ *   also rejects inf and NaN); q = (int)t; w = S[..] * R[q]; num = num + w * n; den = den + w.  The output is num / den (the centre always
+ *   enters with q = 0, so den > 0).  Nothing is filled in, and nothing beyond 3 sigma_range of the centre bleeds across a depth edge. */
+typedef struct icp_depth_filter_options {
+    int32_t radius;        /* 0 = off (default); 1..4: window (2r+1)^2 */
+    float   sigma_space;   /* pixels, > 0, default 4.5 */
+    float   sigma_range;   /* metres, > 0, default 0.03 */
+} icp_depth_filter_options;
+enum { ICP_DEPTH_FILTER_MAX_RADIUS = 4, ICP_DEPTH_FILTER_RANGE_BINS = 256,
+       ICP_DEPTH_FILTER_TILE_W = 32, ICP_DEPTH_FILTER_TILE_H = 8 };   /* the kernel's tile of pixels per block (tests choose shapes around it) */
+int icp_depth_filter_options_default(icp_depth_filter_options* opt);
+/* ICP_OK or ICP_ERR_INVALID_ARG (a radius outside 0 .. 4, a non-finite or non-positive sigma, a sigma_range whose inv_bin is not finite);
+ * needs neither a context nor a device. */
+int icp_depth_filter_options_check(const icp_depth_filter_options* opt);
+int icp_set_depth_filter_options(icp_ctx* ctx, const icp_depth_filter_options* opt);   /* NULL = defaults (off) */
+int icp_get_depth_filter_options(const icp_ctx* ctx, icp_depth_filter_options* opt);
+/* The tables the device will use for `opt`: spatial_out (2r + 1)^2 floats (none with radius 0), range_out 256 floats, *inv_bin_out; any
+ * output may be NULL.  Needs neither a context nor a device. */
+int icp_depth_filter_tables(const icp_depth_filter_options* opt, float* spatial_out, float* range_out, float* inv_bin_out);
+/* Filters one frame, host to host, with `opt` (NULL: the context's options); radius 0 copies the input.  depth_out: width x height floats. */
+int icp_filter_depth(icp_ctx* ctx, const float* depth, int32_t width, int32_t height, const icp_depth_filter_options* opt, float* depth_out);
+
 /* -------- batches of independent scan pairs: the loop over ETH indices, main.cpp:411-498 / experiment.cpp:319-396 --------
  * The reference aligns the pairs one after the other and carries no state between them, so a batch shards with no
  * data-path exchange: pair p belongs to rank p % n_ranks (icp_pair_owner), and the only collective is ONE gather of the
