@@ -150,9 +150,11 @@ def integrate(vol, depth, cam, pose):
     return integrate_allocated(vol, depth, cam, pose)
 
 
-def _cell(vol, qx, qy, qz):
-    """tsdf_restatement._cell on the hashed volume: (valid, corners (8, n), tx, ty, tz).  Valid iff the cell is storable and all eight
-    corner weights are > 0; a voxel of a block that does not exist reads (0, 0)."""
+BOX_LIMIT = 1 << 24                               # voxels of the bounding box beyond which _cell gathers per block instead
+
+
+def _cell_box(vol, qx, qy, qz):
+    """_cell through the dense bounding box of the blocks."""
     lo, T, W = vol.box()
     dims = np.array(T.shape[::-1], np.int64)
     with np.errstate(all="ignore"):
@@ -177,6 +179,55 @@ def _cell(vol, qx, qy, qz):
             else:
                 valid &= False
     return valid, c, t[0], t[1], t[2]
+
+
+def _cell_gather(vol, qx, qy, qz):
+    """_cell without a box: each of the eight corners is read from the block that holds it (g >> 3, local g & 7), found in the dict's keys;
+    a corner whose block does not exist reads (0, 0).  The same g, floor, range test and fractions as _cell_box."""
+    n = len(qx)
+    keys = sorted(vol.blocks, key=lambda b: (b[2], b[1], b[0]))
+    B = np.array(keys, np.int64).reshape(-1, 3)
+    order = ((B[:, 2] + RANGE) << 42) | ((B[:, 1] + RANGE) << 21) | (B[:, 0] + RANGE)      # (ascending: the sort above is the key's order)
+    T = np.stack([vol.blocks[b][0] for b in keys]).reshape(-1, 512) if keys else np.zeros((0, 512), f32)
+    W = np.stack([vol.blocks[b][1] for b in keys]).reshape(-1, 512) if keys else np.zeros((0, 512), f32)
+    with np.errstate(all="ignore"):
+        g = [(q - vol.o[a]) / vol.s for a, q in enumerate((qx, qy, qz))]
+        fl = [np.floor(x) for x in g]
+        ok = np.ones(n, bool)
+        for a in range(3):
+            ok &= (fl[a] >= CELL_LO) & (fl[a] <= CELL_HI)
+        t = [g[a] - fl[a] for a in range(3)]
+        i = [np.where(ok, fl[a], 0).astype(np.int64) for a in range(3)]
+    c = np.zeros((8, n), f32)
+    valid = ok.copy()
+    for k in range(8):
+        j = [i[0] + (k & 1), i[1] + ((k >> 1) & 1), i[2] + (k >> 2)]      # (a storable cell's corners: -2^23 .. 2^23 - 1, blocks in range)
+        if not keys:
+            valid &= False
+            continue
+        key = (((j[2] >> 3) + RANGE) << 42) | (((j[1] >> 3) + RANGE) << 21) | ((j[0] >> 3) + RANGE)
+        at = np.minimum(np.searchsorted(order, key), len(order) - 1)
+        there = order[at] == key
+        loc = (j[2] & 7) * 64 + (j[1] & 7) * 8 + (j[0] & 7)
+        c[k] = np.where(there, T[at, loc], f32(0))
+        valid &= there & (W[at, loc] > 0)
+    return valid, c, t[0], t[1], t[2]
+
+
+def box_voxels(vol):
+    """The voxels of the bounding box of the blocks (a Python int); 0 for a view that brings a box of its own and no blocks."""
+    if not getattr(vol, "blocks", None):
+        return 0
+    B = np.array(list(vol.blocks), np.int64)
+    d = (B.max(0) - B.min(0) + 1) * 8
+    return int(d[0]) * int(d[1]) * int(d[2])
+
+
+def _cell(vol, qx, qy, qz):
+    """tsdf_restatement._cell on the hashed volume: (valid, corners (8, n), tx, ty, tz).  Valid iff the cell is storable and all eight
+    corner weights are > 0; a voxel of a block that does not exist reads (0, 0).  Through the dense bounding box of the blocks, or, where
+    that box would hold more than BOX_LIMIT voxels (blocks at both ends of the storable range), block by block: the two agree bit for bit."""
+    return _cell_gather(vol, qx, qy, qz) if box_voxels(vol) > BOX_LIMIT else _cell_box(vol, qx, qy, qz)
 
 
 _dense_cell = getattr(TS._cell, "dense", TS._cell)      # (the original, also when this module is imported a second time)
