@@ -162,7 +162,7 @@ struct icp_ctx {
     DevBuf te_work, te_out_pool, te_out_key; int te_held = 0;   // streaming the hashed volume (host_tsdf_hash_evict.hpp): an evict's flags, lists and counters; the outbox (evicted blocks and their keys) and the blocks it holds
     DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
     DevBuf tm_nbr, tm_ord;               // icp_tsdf_mesh_hashed (host_tsdf_hash_mesh.hpp), which also uses the five above: the 27 neighbour ranks of every block; order[rank] -> pool index, then rank_of[pool index]
-    DevBuf sdf_state, sdf_partials, sdf_rec; Event sdf_ev;   // direct SDF tracking (host_sdf.hpp, host_sdf_color.hpp): the pose / stop state, partials[28 or 29][blocks] + counts[2 or 3][blocks], the frame record + trace; "the last integration has left its upload slot"
+    DevBuf sdf_state, sdf_partials, sdf_rec; Event sdf_ev;   // direct SDF tracking (host_sdf.hpp's driver, for the record kinds SdfGeo and SdfColor, and host_vgicp.hpp through it): the kind's pose / stop state, partials[NSUM][blocks] + counts[NCOUNT][blocks] (28 + 2 or 29 + 3), the frame record + trace; they only grow, every call writes them before it reads them; "the last integration has left its upload slot"
     DevBuf vg_box, vg_count, vg_sums, vg_cells;   // voxelized GICP (host_vgicp.hpp): the target's voxel grid -- bounds + counters, per cell the count, the nine int64 sums, the 40-byte record
     bool vg_ready = false; float vg_voxel = 0.f; icp_voxel_grid_info vg_info = {{0, 0, 0}, {0, 0, 0}, 0, 0};   // the grid is current for vg_voxel (dropped with the target's GICP normal cache); its extent
     DevBuf vm_count, vm_sums, vm_cells, vm_stamp, vm_list, vm_ctr, vm_box;   // the voxel map (host_vmap.hpp): per cell the count, the nine int64 sums, the 40-byte record and the stamp of the last insert that touched it; the list of the cells an insert touched, the counters, the scratch counters of a full sweep
@@ -376,6 +376,18 @@ int check_ready(icp_ctx* c, bool need_source, bool full_pipeline) {
 
 int ensure_events(icp_ctx* c, size_t count) {
     while (c->events.size() < count) { Event e; HIPCK(c, hipEventCreate(&e.e)); c->events.push_back(std::move(e)); }
+    return ICP_OK;
+}
+// The one timed bracket of the icp_debug_*_time functions: the device time, in milliseconds, of what `enqueue` puts on the context's
+// stream, between two events.  What is staged or warmed outside the bracket is the caller's, in front of this call.
+template <class Enqueue> int timed_ms(icp_ctx* c, float* ms_out, Enqueue&& enqueue) {
+    int rc;
+    if ((rc = ensure_events(c, 2))) return rc;
+    HIPCK(c, hipEventRecord(c->events[0], c->stream));
+    if ((rc = enqueue())) return rc;
+    HIPCK(c, hipEventRecord(c->events[1], c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
     return ICP_OK;
 }
 }  // namespace

@@ -160,7 +160,7 @@ int hmap_read_record(icp_ctx* c, const icp_sdf_options& so, icp_sdf_frame* r, co
     if ((rc = ensure_pinned(c, 4096 + sizeof(icp_sdf_frame)))) return rc;      // (sdf_read_record's block, grown first: it must not move under the copy below)
     int* h = (int*)(c->pinned.as<char>() + 2032);      // (the 16 bytes in front of the record's place)
     HIPCK(c, hipMemcpyAsync(h, c->vm_ctr.as<int>() + VM_OCCUPIED, 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = sdf_read_record(c, so, r, nullptr))) return rc;
+    if ((rc = sdf_read_record<SdfGeo>(c, so, r, nullptr))) return rc;
     c->vh_bound = h[0];
     return hmap_unplaced_error(c, h[1], who);
 }
@@ -304,25 +304,18 @@ int icp_voxel_map_upload_hashed(icp_ctx* c, int32_t n, const int32_t* coords, co
 // this for a hashed map), and the device time of one rehash of the map into a table of the same size (a tool's map: n_grown goes up).
 static int hmap_debug_time(icp_ctx* c, int32_t which, const float pose[16], float* insert_ms_out, float* records_ms_out, const char* who) {
     int rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     if ((rc = hmap_insert_enqueue(c, which, pose, who))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
     if ((rc = hmap_room(c, (which ? c->src : c->tgt).n, who))) return rc;      // (so that the timed insert neither reads nor grows)
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = hmap_insert_enqueue(c, which, pose, who))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(insert_ms_out, c->events[0], c->events[1]));
+    if ((rc = timed_ms(c, insert_ms_out, [&] { return hmap_insert_enqueue(c, which, pose, who); }))) return rc;
     const Cloud& cl = which ? c->src : c->tgt;
     const size_t cap = hm_cap(c);
     const int list_cap = (size_t)cl.n < cap ? cl.n : (int)cap;
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    hipLaunchKernelGGL(k_hmap_records, dim3((list_cap + 255) / 256), dim3(256), 0, c->stream, (const unsigned long long*)c->vh_keys.as<unsigned long long>(), c->vm_opt.voxel_size, list_cap,
-                       (const int*)c->vm_ctr.as<int>(), (const int*)c->vm_list.as<int>(), (const int*)c->vm_count.as<int>(), (const long long*)c->vm_sums.as<long long>(), c->vm_cells.as<float2>());
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(records_ms_out, c->events[0], c->events[1]));
-    return ICP_OK;
+    return timed_ms(c, records_ms_out, [&] {
+        hipLaunchKernelGGL(k_hmap_records, dim3((list_cap + 255) / 256), dim3(256), 0, c->stream, (const unsigned long long*)c->vh_keys.as<unsigned long long>(), c->vm_opt.voxel_size, list_cap,
+                           (const int*)c->vm_ctr.as<int>(), (const int*)c->vm_list.as<int>(), (const int*)c->vm_count.as<int>(), (const long long*)c->vm_sums.as<long long>(), c->vm_cells.as<float2>());
+        return ICP_OK;
+    });
 }
 extern "C" int icp_debug_hmap_rehash_time(icp_ctx* c, float* rehash_ms_out) {
     if (!c || !rehash_ms_out) return ICP_ERR_INVALID_ARG;
@@ -330,12 +323,7 @@ extern "C" int icp_debug_hmap_rehash_time(icp_ctx* c, float* rehash_ms_out) {
     if ((rc = hmap_check(c, "icp_debug_hmap_rehash_time"))) return rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = hmap_rehash(c, c->vh_log2cap))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(rehash_ms_out, c->events[0], c->events[1]));
+    if ((rc = timed_ms(c, rehash_ms_out, [&] { return hmap_rehash(c, c->vh_log2cap); }))) return rc;
     return guard.done();
 }

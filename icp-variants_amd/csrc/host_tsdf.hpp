@@ -1,7 +1,9 @@
 // host_tsdf.hpp -- frame-to-model tracking: the context's TSDF volume (icp_tsdf_*), the model as target (icp_set_target_tsdf) and the tracking
 // loop over it (icp_track_depth_model); the volume's optional colour array and the coloured forms of all three (icp_tsdf_color_*,
 // icp_tsdf_integrate_color, icp_tsdf_raycast_color, icp_set_target_tsdf_color, icp_track_depth_model_color).  Kernels: dev_tsdf.hpp;
-// contract: include/icp_hip.h, DESIGN.md sections 6m and 6p.
+// contract: include/icp_hip.h, DESIGN.md sections 6m and 6p.  One body per call shape, for the dense and the hashed volume, with and
+// without colour: tsdf_raycast_to_host behind the four ray-cast calls, set_target_tsdf_call behind the four targets, track_depth_model
+// behind the four tracking loops; the public functions here and in host_tsdf_hash_raycast.hpp keep their own leading checks.
 // Part of icp_hip.hip (included from there, after host_depth.hpp).
 namespace {
 const char* tsdf_options_error(const icp_tsdf_options* o) {
@@ -99,6 +101,41 @@ int tsdf_raycast_launch(icp_ctx* c, const icp_depth_camera& cam, const float pos
     HIPCK(c, hipGetLastError());
     return ICP_OK;
 }
+// the ray-cast of whichever storage the caller's checks have found
+int tsdf_raycast_any(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], bool soa, const TsdfRayOut& o, const TsdfColorOut* co, bool hashed) {
+    return hashed ? htsdf_raycast_launch(c, cam, pose, soa, o, co) : tsdf_raycast_launch(c, cam, pose, soa, o, co);
+}
+// The staging layout of a ray-cast to the host, [depth 4n | vertices 12n | normals 12n | rgba 4n (color)]: the planes asked for, the rest null.
+int tsdf_ray_stage(icp_ctx* c, size_t n, bool color, bool depth, bool vert, bool nrm, bool rgba, TsdfRayOut* o, TsdfColorOut* co) {
+    int rc;
+    if ((rc = ensure(c, c->staging, n * (color ? 32 : 28)))) return rc;
+    float* d = c->staging.as<float>();
+    memset(o, 0, sizeof(*o));
+    o->depth = depth ? d : nullptr; o->vert = vert ? d + n : nullptr; o->nrm = nrm ? d + 4 * n : nullptr;
+    *co = {rgba ? (uint32_t*)(d + 7 * n) : nullptr, nullptr, nullptr, nullptr};
+    return ICP_OK;
+}
+// The four ray-cast-to-host calls behind their checks: staged, launched (color: the coloured ray-cast; hashed: the hashed volume's), the
+// planes asked for copied back, the count read -- the one host wait.
+int tsdf_raycast_to_host(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], float* depth_out, float* vertices_out, float* normals_out, uint8_t* rgba_out,
+                         int32_t* n_hits_out, int32_t* n_colored_out, bool color, bool hashed) {
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const size_t n = (size_t)cam.width * cam.height;
+    TsdfRayOut o; TsdfColorOut co;
+    if ((rc = tsdf_ray_stage(c, n, color, depth_out, vertices_out, normals_out, rgba_out, &o, &co))) return rc;
+    if ((rc = tsdf_raycast_any(c, cam, pose, false, o, color ? &co : nullptr, hashed))) return rc;
+    if (depth_out) HIPCK(c, hipMemcpyAsync(depth_out, o.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (vertices_out) HIPCK(c, hipMemcpyAsync(vertices_out, o.vert, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (normals_out) HIPCK(c, hipMemcpyAsync(normals_out, o.nrm, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (rgba_out) HIPCK(c, hipMemcpyAsync(rgba_out, co.rgba, n * 4, hipMemcpyDeviceToHost, c->stream));
+    int cnt[2] = {0, 0};
+    if ((rc = read_count(c, c->tsdf_cnt.p, cnt, color ? 2 : 1))) return rc;
+    if (n_hits_out) *n_hits_out = cnt[0];
+    if (n_colored_out) *n_colored_out = cnt[1];
+    return guard.done();
+}
 // The model as target, from the arguments already checked: the ray-cast into the target's planes, the hit count, finish_target.
 // *hits_out = 0 with ICP_ERR_NO_TARGET leaves an empty target.  color: the coloured ray-cast, colours into the target's colour planes;
 // a hit without colour is a hole and *hits_out counts the coloured hits.  hashed: the ray-cast of the hashed volume (with color: its coloured one).
@@ -113,7 +150,7 @@ int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16
     TsdfRayOut o; memset(&o, 0, sizeof(o));
     o.x = tg.x.as<float>(); o.y = tg.y.as<float>(); o.z = tg.z.as<float>(); o.nx = tg.nx.as<float>(); o.ny = tg.ny.as<float>(); o.nz = tg.nz.as<float>(); o.npad = npad;
     const TsdfColorOut co = {tg.rgba.as<uint32_t>(), tg.cr.as<float>(), tg.cg.as<float>(), tg.cb.as<float>()};
-    if ((rc = hashed ? htsdf_raycast_launch(c, cam, pose, true, o, color ? &co : nullptr) : tsdf_raycast_launch(c, cam, pose, true, o, color ? &co : nullptr))) return rc;
+    if ((rc = tsdf_raycast_any(c, cam, pose, true, o, color ? &co : nullptr, hashed))) return rc;
     int hits = 0;
     if ((rc = read_count(c, c->tsdf_cnt.p, &hits))) return rc;      // (the coloured target's holes are its uncoloured hits: both counts agree)
     tg.has_normals = true; tg.has_colors = color;
@@ -126,6 +163,37 @@ int set_target_tsdf(icp_ctx* c, const icp_depth_camera& cam, const float pose[16
     tg.n = n; tg.npad = npad;
     *hits_out = hits;
     return finish_target(c, color);
+}
+// The four icp_set_target_tsdf* calls behind their checks.
+int set_target_tsdf_call(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], int32_t* n_points_out, const char* who, bool color, bool hashed) {
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    int hits = 0;
+    rc = set_target_tsdf(c, cam, pose, &hits, who, color, hashed);
+    if (rc == ICP_ERR_NO_TARGET) return guard.done(rc);      // (synchronised by the count read)
+    if (rc) return rc;
+    if (n_points_out) *n_points_out = hits;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
+// icp_debug_tsdf_time and icp_debug_tsdf_color_time behind their checks: ONE integrate (which = 0, the frame staged outside the bracket) or
+// ONE ray-cast to the host-layout arrays (which = 1) inside timed_ms.
+int tsdf_time(icp_ctx* c, int32_t which, const float* depth, const uint8_t* rgbx, const icp_depth_camera& cam, const float pose[16], float* ms_out, bool color) {
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    const size_t n = (size_t)cam.width * cam.height;
+    if (which == 0) {
+        if ((rc = stage_depth(c, 0, depth, rgbx, (int)n, c->stream))) return rc;
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if ((rc = timed_ms(c, ms_out, [&] { return tsdf_integrate_slot(c, 0, cam, pose, c->tsdf_cnt.as<int>(), color); }))) return rc;
+    } else {
+        TsdfRayOut o; TsdfColorOut co;
+        if ((rc = tsdf_ray_stage(c, n, color, true, true, true, true, &o, &co))) return rc;
+        if ((rc = timed_ms(c, ms_out, [&] { return tsdf_raycast_launch(c, cam, pose, false, o, color ? &co : nullptr); }))) return rc;
+    }
+    return guard.done();
 }
 // pose <- pose dT: the fp64 product of the two column-major 4x4, rounded once.
 void compose_pose(float pose[16], const float dT[16]) {
@@ -328,21 +396,7 @@ int icp_tsdf_raycast(icp_ctx* c, const icp_depth_camera* cam, const float pose[1
     if (n_hits_out) *n_hits_out = 0;
     int rc;
     if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_raycast"))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    const size_t n = (size_t)cam->width * cam->height;
-    if ((rc = ensure(c, c->staging, n * 28))) return rc;      // [depth 4n | vertices 12n | normals 12n]
-    float* d = c->staging.as<float>();
-    TsdfRayOut o; memset(&o, 0, sizeof(o));
-    o.depth = depth_out ? d : nullptr; o.vert = vertices_out ? d + n : nullptr; o.nrm = normals_out ? d + 4 * n : nullptr;
-    if ((rc = tsdf_raycast_launch(c, *cam, pose, false, o))) return rc;
-    if (depth_out) HIPCK(c, hipMemcpyAsync(depth_out, o.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (vertices_out) HIPCK(c, hipMemcpyAsync(vertices_out, o.vert, n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (normals_out) HIPCK(c, hipMemcpyAsync(normals_out, o.nrm, n * 12, hipMemcpyDeviceToHost, c->stream));
-    int hits = 0;
-    if ((rc = read_count(c, c->tsdf_cnt.p, &hits))) return rc;
-    if (n_hits_out) *n_hits_out = hits;
-    return guard.done();
+    return tsdf_raycast_to_host(c, *cam, pose, depth_out, vertices_out, normals_out, nullptr, n_hits_out, nullptr, false, false);
 }
 
 int icp_set_target_tsdf(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out) {
@@ -350,15 +404,7 @@ int icp_set_target_tsdf(icp_ctx* c, const icp_depth_camera* cam, const float pos
     if (n_points_out) *n_points_out = 0;
     int rc;
     if ((rc = tsdf_check_call(c, cam, pose, "icp_set_target_tsdf"))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    int hits = 0;
-    rc = set_target_tsdf(c, *cam, pose, &hits, "icp_set_target_tsdf");
-    if (rc == ICP_ERR_NO_TARGET) return guard.done(rc);      // (synchronised by the count read)
-    if (rc) return rc;
-    if (n_points_out) *n_points_out = hits;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return guard.done();
+    return set_target_tsdf_call(c, *cam, pose, n_points_out, "icp_set_target_tsdf", false, false);
 }
 
 int icp_tsdf_raycast_color(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], float* depth_out, float* vertices_out, float* normals_out,
@@ -369,24 +415,7 @@ int icp_tsdf_raycast_color(icp_ctx* c, const icp_depth_camera* cam, const float 
     int rc;
     if ((rc = tsdf_check_call(c, cam, pose, "icp_tsdf_raycast_color"))) return rc;
     if ((rc = tsdf_check_color(c, "icp_tsdf_raycast_color"))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    const size_t n = (size_t)cam->width * cam->height;
-    if ((rc = ensure(c, c->staging, n * 32))) return rc;      // [depth 4n | vertices 12n | normals 12n | rgba 4n]
-    float* d = c->staging.as<float>();
-    TsdfRayOut o; memset(&o, 0, sizeof(o));
-    o.depth = depth_out ? d : nullptr; o.vert = vertices_out ? d + n : nullptr; o.nrm = normals_out ? d + 4 * n : nullptr;
-    const TsdfColorOut co = {rgba_out ? (uint32_t*)(d + 7 * n) : nullptr, nullptr, nullptr, nullptr};
-    if ((rc = tsdf_raycast_launch(c, *cam, pose, false, o, &co))) return rc;
-    if (depth_out) HIPCK(c, hipMemcpyAsync(depth_out, o.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (vertices_out) HIPCK(c, hipMemcpyAsync(vertices_out, o.vert, n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (normals_out) HIPCK(c, hipMemcpyAsync(normals_out, o.nrm, n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (rgba_out) HIPCK(c, hipMemcpyAsync(rgba_out, co.rgba, n * 4, hipMemcpyDeviceToHost, c->stream));
-    int cnt[2] = {0, 0};
-    if ((rc = read_count(c, c->tsdf_cnt.p, cnt, 2))) return rc;
-    if (n_hits_out) *n_hits_out = cnt[0];
-    if (n_colored_out) *n_colored_out = cnt[1];
-    return guard.done();
+    return tsdf_raycast_to_host(c, *cam, pose, depth_out, vertices_out, normals_out, rgba_out, n_hits_out, n_colored_out, true, false);
 }
 
 int icp_set_target_tsdf_color(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out) {
@@ -395,15 +424,7 @@ int icp_set_target_tsdf_color(icp_ctx* c, const icp_depth_camera* cam, const flo
     int rc;
     if ((rc = tsdf_check_call(c, cam, pose, "icp_set_target_tsdf_color"))) return rc;
     if ((rc = tsdf_check_color(c, "icp_set_target_tsdf_color"))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    int hits = 0;
-    rc = set_target_tsdf(c, *cam, pose, &hits, "icp_set_target_tsdf_color", true);
-    if (rc == ICP_ERR_NO_TARGET) return guard.done(rc);      // (synchronised by the count read)
-    if (rc) return rc;
-    if (n_points_out) *n_points_out = hits;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return guard.done();
+    return set_target_tsdf_call(c, *cam, pose, n_points_out, "icp_set_target_tsdf_color", true, false);
 }
 
 // Both tracking loops.  color (icp_track_depth_model_color): frames staged with their colour frame, the coloured target, the source with
@@ -515,27 +536,7 @@ extern "C" int icp_debug_tsdf_time(icp_ctx* c, int32_t which, const float* depth
     int rc;
     if ((rc = tsdf_check_call(c, cam, pose, "icp_debug_tsdf_time"))) return rc;
     if (which == 0 && !depth) return ICP_ERR_INVALID_ARG;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
-    const size_t n = (size_t)cam->width * cam->height;
-    if (which == 0) {
-        if ((rc = stage_depth(c, 0, depth, nullptr, (int)n, c->stream))) return rc;
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        HIPCK(c, hipEventRecord(c->events[0], c->stream));
-        if ((rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>()))) return rc;
-    } else {
-        if ((rc = ensure(c, c->staging, n * 28))) return rc;
-        float* d = c->staging.as<float>();
-        TsdfRayOut o; memset(&o, 0, sizeof(o));
-        o.depth = d; o.vert = d + n; o.nrm = d + 4 * n;
-        HIPCK(c, hipEventRecord(c->events[0], c->stream));
-        if ((rc = tsdf_raycast_launch(c, *cam, pose, false, o))) return rc;
-    }
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
-    return guard.done();
+    return tsdf_time(c, which, depth, nullptr, *cam, pose, ms_out, false);
 }
 
 // Not part of icp_hip.h (tools/time_tsdf_color.py): icp_debug_tsdf_time for the coloured kernels -- ONE icp_tsdf_integrate_color (which = 0,
@@ -547,26 +548,5 @@ extern "C" int icp_debug_tsdf_color_time(icp_ctx* c, int32_t which, const float*
     if ((rc = tsdf_check_call(c, cam, pose, "icp_debug_tsdf_color_time"))) return rc;
     if ((rc = tsdf_check_color(c, "icp_debug_tsdf_color_time"))) return rc;
     if (which == 0 && (!depth || !rgbx)) return ICP_ERR_INVALID_ARG;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
-    const size_t n = (size_t)cam->width * cam->height;
-    if (which == 0) {
-        if ((rc = stage_depth(c, 0, depth, rgbx, (int)n, c->stream))) return rc;
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        HIPCK(c, hipEventRecord(c->events[0], c->stream));
-        if ((rc = tsdf_integrate_slot(c, 0, *cam, pose, c->tsdf_cnt.as<int>(), true))) return rc;
-    } else {
-        if ((rc = ensure(c, c->staging, n * 32))) return rc;
-        float* d = c->staging.as<float>();
-        TsdfRayOut o; memset(&o, 0, sizeof(o));
-        o.depth = d; o.vert = d + n; o.nrm = d + 4 * n;
-        const TsdfColorOut co = {(uint32_t*)(d + 7 * n), nullptr, nullptr, nullptr};
-        HIPCK(c, hipEventRecord(c->events[0], c->stream));
-        if ((rc = tsdf_raycast_launch(c, *cam, pose, false, o, &co))) return rc;
-    }
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
-    return guard.done();
+    return tsdf_time(c, which, depth, rgbx, *cam, pose, ms_out, true);
 }

@@ -181,13 +181,8 @@ extern "C" int icp_debug_htsdf_evict_time(icp_ctx* c, const float centre[3], flo
     if ((rc = htsdf_check(c, "icp_debug_htsdf_evict_time"))) return rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = icp_tsdf_evict_blocks(c, centre, radius, hold, info_out))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
+    if ((rc = timed_ms(c, ms_out, [&] { return icp_tsdf_evict_blocks(c, centre, radius, hold, info_out); }))) return rc;
     return guard.done();
 }
 extern "C" int icp_debug_htsdf_insert_time(icp_ctx* c, int32_t n, const int32_t* coords, const float* tsdf, const float* weight, icp_tsdf_stream_info* info_out, float* ms_out) {
@@ -196,12 +191,7 @@ extern "C" int icp_debug_htsdf_insert_time(icp_ctx* c, int32_t n, const int32_t*
     if ((rc = htsdf_check(c, "icp_debug_htsdf_insert_time"))) return rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = icp_tsdf_insert_blocks(c, n, coords, tsdf, weight, info_out))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
+    if ((rc = timed_ms(c, ms_out, [&] { return icp_tsdf_insert_blocks(c, n, coords, tsdf, weight, info_out); }))) return rc;
     return guard.done();
 }

@@ -1,7 +1,8 @@
 // host_tsdf_hash_mesh.hpp -- icp_tsdf_mesh_hashed: the zero level set of the context's HASHED TSDF volume as an indexed triangle mesh, extracted
 // on the block pool; only the mesh crosses to the host, scratch scales with the blocks in use; icp_tsdf_mesh_color_hashed: the same mesh with
 // a colour per vertex from the colour pool.  Kernels: dev_tsdf_hash_mesh.hpp, dev_tsdf_hash_mesh_color.hpp; contract: include/icp_hip.h,
-// DESIGN.md sections 6y and 6zc.  Part of icp_hip.hip (included from there, after host_tsdf_hash.hpp and host_tsdf_mesh.hpp).
+// DESIGN.md sections 6y and 6zc.  From the totals on, the mesh call is host_tsdf_mesh.hpp's tm_finish with this file's fill and colour passes.
+// Part of icp_hip.hip (included from there, after host_tsdf_hash.hpp and host_tsdf_mesh.hpp).
 namespace {
 // The context's scratch, indexed by block rank: [observed | negative | valid] words (8 per block each), the mask bytes, the run bases, the
 // 27 neighbour ranks, the two block tables and the two totals, order[rank] and rank_of[pool index].
@@ -105,35 +106,9 @@ int htsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_t
     if ((rc = htm_scratch(c, n, s))) return rc;
     if ((rc = htm_order(c, n, s, h_order))) return rc;
     if ((rc = htm_enqueue_count(c, n, s, min_weight))) return rc;
-    int tot[2] = {0, 0};                                 // both totals back in one copy
-    if ((rc = read_count(c, s.tot, tot, 2))) return rc;
-    const int nv = tot[0], nt = tot[1];
-    if (nv < 0 || nt < 0) { c->err = who + ": count out of range"; return ICP_ERR_HIP; }
-    *n_vertices_out = nv; *n_triangles_out = nt;
-    if (count_only) return guard.done();
-    if (nv > max_vertices || nt > max_triangles) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "%s: the mesh has %d vertices and %d triangles, the arrays hold %d and %d", who.c_str(), nv, nt, max_vertices, max_triangles);
-        c->err = buf;
-        return guard.done(ICP_ERR_INVALID_ARG);      // (synchronised by the count read)
-    }
-    if (nv == 0 && nt == 0) return guard.done();
-    // the outputs staged in device arrays of exactly the counted size: [vertices 12 V | normals 12 V | triangles 12 T | colours 4 V]
-    const size_t bv = (size_t)nv * 12, bn = normals_out ? bv : 0, bt = (size_t)nt * 12, bc = colors_out ? (size_t)nv * 4 : 0;
-    if ((rc = ensure(c, c->tm_out, bv + bn + bt + bc))) return rc;
-    char* d = c->tm_out.as<char>();
-    float* d_vert = (float*)d; float* d_nrm = normals_out ? (float*)(d + bv) : nullptr; uint32_t* d_tris = (uint32_t*)(d + bv + bn);
-    uint32_t* d_col = (uint32_t*)(d + bv + bn + bt);
-    if ((rc = htm_enqueue_fill(c, n, s, d_vert, d_nrm, d_tris))) return rc;
-    if (colors_out && nv > 0) {
-        if ((rc = htm_enqueue_colors(c, n, s, d_col))) return rc;
-        HIPCK(c, hipMemcpyAsync(colors_out, d_col, bc, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (nv > 0) HIPCK(c, hipMemcpyAsync(vertices_out, d_vert, bv, hipMemcpyDeviceToHost, c->stream));
-    if (nv > 0 && normals_out) HIPCK(c, hipMemcpyAsync(normals_out, d_nrm, bn, hipMemcpyDeviceToHost, c->stream));
-    if (nt > 0) HIPCK(c, hipMemcpyAsync(triangles_out, d_tris, bt, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return guard.done();
+    return tm_finish(c, guard, s.tot, max_vertices, max_triangles, vertices_out, normals_out, colors_out, triangles_out, n_vertices_out, n_triangles_out, count_only, who,
+                     [&](float* d_vert, float* d_nrm, uint32_t* d_tris) { return htm_enqueue_fill(c, n, s, d_vert, d_nrm, d_tris); },
+                     [&](uint32_t* d_col) { return htm_enqueue_colors(c, n, s, d_col); });
 }
 }  // namespace
 
@@ -161,7 +136,6 @@ extern "C" int icp_debug_htsdf_mesh_color_time(icp_ctx* c, float min_weight, flo
     if (n == 0) { c->err = std::string(who) + ": the volume holds no block"; return ICP_ERR_INVALID_ARG; }
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     HtmScratch s;
     std::vector<int> h_order;
     if ((rc = htm_scratch(c, n, s))) return rc;
@@ -174,13 +148,13 @@ extern "C" int icp_debug_htsdf_mesh_color_time(icp_ctx* c, float min_weight, flo
     const size_t bv = (size_t)nv * 12, bt = (size_t)nt * 12;
     if ((rc = ensure(c, c->tm_out, 2 * bv + bt + (size_t)nv * 4))) return rc;
     char* d = c->tm_out.as<char>();
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = htm_enqueue_count(c, n, s, min_weight))) return rc;
-    if ((rc = htm_enqueue_fill(c, n, s, (float*)d, (float*)(d + bv), (uint32_t*)(d + 2 * bv)))) return rc;
-    if (nv > 0 && (rc = htm_enqueue_colors(c, n, s, (uint32_t*)(d + 2 * bv + bt)))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(device_ms_out, c->events[0], c->events[1]));
+    rc = timed_ms(c, device_ms_out, [&] {
+        int r = htm_enqueue_count(c, n, s, min_weight);
+        if (!r) r = htm_enqueue_fill(c, n, s, (float*)d, (float*)(d + bv), (uint32_t*)(d + 2 * bv));
+        if (!r && nv > 0) r = htm_enqueue_colors(c, n, s, (uint32_t*)(d + 2 * bv + bt));
+        return r;
+    });
+    if (rc) return rc;
     return guard.done();
 }
 
@@ -215,12 +189,11 @@ extern "C" int icp_debug_htsdf_mesh_time(icp_ctx* c, float min_weight, float* de
     const size_t bv = (size_t)nv * 12, bt = (size_t)nt * 12;
     if ((rc = ensure(c, c->tm_out, 2 * bv + bt))) return rc;
     char* d = c->tm_out.as<char>();
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = htm_enqueue_count(c, n, s, min_weight))) return rc;
-    if ((rc = htm_enqueue_fill(c, n, s, (float*)d, (float*)(d + bv), (uint32_t*)(d + 2 * bv)))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(device_ms_out, c->events[0], c->events[1]));
+    rc = timed_ms(c, device_ms_out, [&] {
+        int r = htm_enqueue_count(c, n, s, min_weight);
+        return r ? r : htm_enqueue_fill(c, n, s, (float*)d, (float*)(d + bv), (uint32_t*)(d + 2 * bv));
+    });
+    if (rc) return rc;
     if (pass_ms_out) {
         HIPCK(c, hipEventRecord(c->events[0], c->stream));
         if ((rc = htm_enqueue_count(c, n, s, min_weight, c->events.data() + 1))) return rc;

@@ -1,8 +1,8 @@
 // host_tsdf_hash_raycast.hpp -- the hashed volume seen from a pose and tracked frame-to-model: icp_tsdf_raycast_hashed,
 // icp_set_target_tsdf_hashed, icp_track_depth_model_hashed, and their coloured forms on a coloured hashed volume:
 // icp_tsdf_raycast_color_hashed, icp_set_target_tsdf_color_hashed, icp_track_depth_model_color_hashed.  Kernels: dev_tsdf_hash_raycast.hpp,
-// dev_tsdf_hash_raycast_color.hpp.  The target and the tracking loop are host_tsdf.hpp's set_target_tsdf and track_depth_model, which launch
-// this file's ray-cast and host_tsdf_hash.hpp's integrate when they are told the volume is hashed.  Contract: include/icp_hip.h, DESIGN.md
+// dev_tsdf_hash_raycast_color.hpp.  The bodies are host_tsdf.hpp's tsdf_raycast_to_host, set_target_tsdf_call and track_depth_model, which launch
+// this file's ray-cast and host_tsdf_hash.hpp's integrate when they are told the volume is hashed; the functions here are their own checks.  Contract: include/icp_hip.h, DESIGN.md
 // sections 6z and 6zc.
 // Part of icp_hip.hip (included from there, after host_tsdf_hash.hpp).
 namespace {
@@ -47,21 +47,7 @@ int icp_tsdf_raycast_hashed(icp_ctx* c, const icp_depth_camera* cam, const float
     int rc;
     if ((rc = htsdf_ray_check(c, who, "icp_tsdf_raycast"))) return rc;
     if ((rc = tsdf_check_call(c, cam, pose, who, true))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    const size_t n = (size_t)cam->width * cam->height;
-    if ((rc = ensure(c, c->staging, n * 28))) return rc;      // [depth 4n | vertices 12n | normals 12n]
-    float* d = c->staging.as<float>();
-    TsdfRayOut o; memset(&o, 0, sizeof(o));
-    o.depth = depth_out ? d : nullptr; o.vert = vertices_out ? d + n : nullptr; o.nrm = normals_out ? d + 4 * n : nullptr;
-    if ((rc = htsdf_raycast_launch(c, *cam, pose, false, o))) return rc;
-    if (depth_out) HIPCK(c, hipMemcpyAsync(depth_out, o.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (vertices_out) HIPCK(c, hipMemcpyAsync(vertices_out, o.vert, n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (normals_out) HIPCK(c, hipMemcpyAsync(normals_out, o.nrm, n * 12, hipMemcpyDeviceToHost, c->stream));
-    int hits = 0;
-    if ((rc = read_count(c, c->tsdf_cnt.p, &hits))) return rc;      // (the one host wait)
-    if (n_hits_out) *n_hits_out = hits;
-    return guard.done();
+    return tsdf_raycast_to_host(c, *cam, pose, depth_out, vertices_out, normals_out, nullptr, n_hits_out, nullptr, false, true);
 }
 
 int icp_set_target_tsdf_hashed(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out) {
@@ -71,15 +57,7 @@ int icp_set_target_tsdf_hashed(icp_ctx* c, const icp_depth_camera* cam, const fl
     int rc;
     if ((rc = htsdf_ray_check(c, who, "icp_set_target_tsdf"))) return rc;
     if ((rc = tsdf_check_call(c, cam, pose, who, true))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    int hits = 0;
-    rc = set_target_tsdf(c, *cam, pose, &hits, who, false, true);
-    if (rc == ICP_ERR_NO_TARGET) return guard.done(rc);      // (synchronised by the count read)
-    if (rc) return rc;
-    if (n_points_out) *n_points_out = hits;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return guard.done();
+    return set_target_tsdf_call(c, *cam, pose, n_points_out, who, false, true);
 }
 
 // track_depth_model with the hashed ray-cast as the target and htsdf_integrate_slot as the integrate.  Host waits per tracked frame: the
@@ -104,24 +82,7 @@ int icp_tsdf_raycast_color_hashed(icp_ctx* c, const icp_depth_camera* cam, const
     int rc;
     if ((rc = htsdf_ray_check_color(c, who, "icp_tsdf_raycast_color"))) return rc;
     if ((rc = tsdf_check_call(c, cam, pose, who, true))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    const size_t n = (size_t)cam->width * cam->height;
-    if ((rc = ensure(c, c->staging, n * 32))) return rc;      // [depth 4n | vertices 12n | normals 12n | rgba 4n]
-    float* d = c->staging.as<float>();
-    TsdfRayOut o; memset(&o, 0, sizeof(o));
-    o.depth = depth_out ? d : nullptr; o.vert = vertices_out ? d + n : nullptr; o.nrm = normals_out ? d + 4 * n : nullptr;
-    const TsdfColorOut co = {rgba_out ? (uint32_t*)(d + 7 * n) : nullptr, nullptr, nullptr, nullptr};
-    if ((rc = htsdf_raycast_launch(c, *cam, pose, false, o, &co))) return rc;
-    if (depth_out) HIPCK(c, hipMemcpyAsync(depth_out, o.depth, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (vertices_out) HIPCK(c, hipMemcpyAsync(vertices_out, o.vert, n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (normals_out) HIPCK(c, hipMemcpyAsync(normals_out, o.nrm, n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (rgba_out) HIPCK(c, hipMemcpyAsync(rgba_out, co.rgba, n * 4, hipMemcpyDeviceToHost, c->stream));
-    int cnt[2] = {0, 0};
-    if ((rc = read_count(c, c->tsdf_cnt.p, cnt, 2))) return rc;      // (the one host wait)
-    if (n_hits_out) *n_hits_out = cnt[0];
-    if (n_colored_out) *n_colored_out = cnt[1];
-    return guard.done();
+    return tsdf_raycast_to_host(c, *cam, pose, depth_out, vertices_out, normals_out, rgba_out, n_hits_out, n_colored_out, true, true);
 }
 
 int icp_set_target_tsdf_color_hashed(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], int32_t* n_points_out) {
@@ -131,15 +92,7 @@ int icp_set_target_tsdf_color_hashed(icp_ctx* c, const icp_depth_camera* cam, co
     int rc;
     if ((rc = htsdf_ray_check_color(c, who, "icp_set_target_tsdf_color"))) return rc;
     if ((rc = tsdf_check_call(c, cam, pose, who, true))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    int hits = 0;
-    rc = set_target_tsdf(c, *cam, pose, &hits, who, true, true);
-    if (rc == ICP_ERR_NO_TARGET) return guard.done(rc);      // (synchronised by the count read)
-    if (rc) return rc;
-    if (n_points_out) *n_points_out = hits;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return guard.done();
+    return set_target_tsdf_call(c, *cam, pose, n_points_out, who, true, true);
 }
 
 // track_depth_model with the coloured hashed ray-cast as the target and the coloured htsdf_integrate_slot as the integrate.  Host waits:
@@ -153,6 +106,17 @@ int icp_track_depth_model_color_hashed(icp_ctx* c, const float* depth_frames, co
     return track_depth_model(c, depth_frames, rgbx_frames, true, n_frames, cam, source_opt, gt_frames, pose_inout, out, who, true);
 }
 
+// icp_debug_htsdf_raycast_time and its coloured form behind their checks: ONE ray-cast of the hashed volume to the host-layout arrays inside timed_ms.
+static int htsdf_raycast_time(icp_ctx* c, const icp_depth_camera& cam, const float pose[16], float* ms_out, bool color) {
+    int rc;
+    DrainOnError guard(c);
+    if ((rc = set_device(c))) return rc;
+    TsdfRayOut o; TsdfColorOut co;
+    if ((rc = tsdf_ray_stage(c, (size_t)cam.width * cam.height, color, true, true, true, true, &o, &co))) return rc;
+    if ((rc = timed_ms(c, ms_out, [&] { return htsdf_raycast_launch(c, cam, pose, false, o, color ? &co : nullptr); }))) return rc;
+    return guard.done();
+}
+
 // Not part of icp_hip.h (tools/time_htsdf_color_view.py): icp_debug_htsdf_raycast_time for ONE coloured ray-cast of the hashed volume.
 extern "C" int icp_debug_htsdf_raycast_color_time(icp_ctx* c, const icp_depth_camera* cam, const float pose[16], float* ms_out) {
     if (!c || !ms_out) return ICP_ERR_INVALID_ARG;
@@ -160,21 +124,7 @@ extern "C" int icp_debug_htsdf_raycast_color_time(icp_ctx* c, const icp_depth_ca
     int rc;
     if ((rc = htsdf_ray_check_color(c, who, "icp_debug_tsdf_color_time"))) return rc;
     if ((rc = tsdf_check_call(c, cam, pose, who, true))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
-    const size_t n = (size_t)cam->width * cam->height;
-    if ((rc = ensure(c, c->staging, n * 32))) return rc;
-    float* d = c->staging.as<float>();
-    TsdfRayOut o; memset(&o, 0, sizeof(o));
-    o.depth = d; o.vert = d + n; o.nrm = d + 4 * n;
-    const TsdfColorOut co = {(uint32_t*)(d + 7 * n), nullptr, nullptr, nullptr};
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = htsdf_raycast_launch(c, *cam, pose, false, o, &co))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
-    return guard.done();
+    return htsdf_raycast_time(c, *cam, pose, ms_out, true);
 }
 
 // Not part of icp_hip.h (tools/time_htsdf_raycast.py): the device time of ONE ray-cast of the hashed volume to the host-layout arrays
@@ -185,18 +135,5 @@ extern "C" int icp_debug_htsdf_raycast_time(icp_ctx* c, const icp_depth_camera* 
     int rc;
     if ((rc = htsdf_ray_check(c, who, "icp_debug_tsdf_time"))) return rc;
     if ((rc = tsdf_check_call(c, cam, pose, who, true))) return rc;
-    DrainOnError guard(c);
-    if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
-    const size_t n = (size_t)cam->width * cam->height;
-    if ((rc = ensure(c, c->staging, n * 28))) return rc;
-    float* d = c->staging.as<float>();
-    TsdfRayOut o; memset(&o, 0, sizeof(o));
-    o.depth = d; o.vert = d + n; o.nrm = d + 4 * n;
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = htsdf_raycast_launch(c, *cam, pose, false, o))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
-    return guard.done();
+    return htsdf_raycast_time(c, *cam, pose, ms_out, false);
 }

@@ -1,6 +1,7 @@
 // host_tsdf_mesh.hpp -- icp_tsdf_mesh: the zero level set of the context's TSDF volume as an indexed triangle mesh, extracted on the device;
 // only the mesh crosses to the host; icp_tsdf_mesh_color: the same mesh with a colour per vertex from the volume's colour array.
 // Kernels: dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp; contract: include/icp_hip.h, DESIGN.md sections 6n and 6p.
+// tm_finish, the tail both storages' mesh calls share from the totals on, lives here (host_tsdf_hash_mesh.hpp passes its own passes in).
 // Part of icp_hip.hip (included from there, after host_tsdf.hpp).
 namespace {
 TmDiv tm_make_div(uint32_t d) {
@@ -61,6 +62,43 @@ int tm_check_call(icp_ctx* c, float min_weight, const char* who) {
     if (tsdf_voxels(c) > (size_t)(INT32_MAX / 12)) { c->err = std::string(who) + ": the volume has more than INT32_MAX / 12 voxels"; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;
 }
+// What both storages' mesh calls do once the counting passes are enqueued: the two totals back in one copy, the counts reported and
+// checked against the arrays, the outputs staged in tm_out, fill(d_vert, d_nrm, d_tris) and -- when colours are asked for --
+// colors(d_col) enqueued, the arrays copied back, the stream waited for.
+template <class Fill, class Colors>
+int tm_finish(icp_ctx* c, DrainOnError& guard, const int* d_tot, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out,
+              uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, bool count_only, const std::string& who, Fill&& fill, Colors&& colors) {
+    int rc;
+    int tot[2] = {0, 0};                                 // both totals back in one copy
+    if ((rc = read_count(c, d_tot, tot, 2))) return rc;
+    const int nv = tot[0], nt = tot[1];
+    if (nv < 0 || nt < 0) { c->err = who + ": count out of range"; return ICP_ERR_HIP; }
+    *n_vertices_out = nv; *n_triangles_out = nt;
+    if (count_only) return guard.done();
+    if (nv > max_vertices || nt > max_triangles) {
+        char buf[200];
+        snprintf(buf, sizeof(buf), "%s: the mesh has %d vertices and %d triangles, the arrays hold %d and %d", who.c_str(), nv, nt, max_vertices, max_triangles);
+        c->err = buf;
+        return guard.done(ICP_ERR_INVALID_ARG);      // (synchronised by the count read)
+    }
+    if (nv == 0 && nt == 0) return guard.done();
+    // the outputs staged in device arrays of exactly the counted size: [vertices 12 V | normals 12 V | triangles 12 T | colours 4 V]
+    const size_t bv = (size_t)nv * 12, bn = normals_out ? bv : 0, bt = (size_t)nt * 12, bc = colors_out ? (size_t)nv * 4 : 0;
+    if ((rc = ensure(c, c->tm_out, bv + bn + bt + bc))) return rc;
+    char* d = c->tm_out.as<char>();
+    float* d_vert = (float*)d; float* d_nrm = normals_out ? (float*)(d + bv) : nullptr; uint32_t* d_tris = (uint32_t*)(d + bv + bn);
+    uint32_t* d_col = (uint32_t*)(d + bv + bn + bt);
+    if ((rc = fill(d_vert, d_nrm, d_tris))) return rc;
+    if (colors_out && nv > 0) {
+        if ((rc = colors(d_col))) return rc;
+        HIPCK(c, hipMemcpyAsync(colors_out, d_col, bc, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (nv > 0) HIPCK(c, hipMemcpyAsync(vertices_out, d_vert, bv, hipMemcpyDeviceToHost, c->stream));
+    if (nv > 0 && normals_out) HIPCK(c, hipMemcpyAsync(normals_out, d_nrm, bn, hipMemcpyDeviceToHost, c->stream));
+    if (nt > 0) HIPCK(c, hipMemcpyAsync(triangles_out, d_tris, bt, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return guard.done();
+}
 // Both mesh calls.  color (icp_tsdf_mesh_color): needs the colour array; colors_out (optional) receives one packed colour per vertex.
 int tsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out, bool color,
               uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, const std::string& who) {
@@ -81,37 +119,14 @@ int tsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_tr
     TmScratch s;
     if ((rc = tm_scratch(c, g, s))) return rc;
     if ((rc = tm_enqueue_count(c, g, s, min_weight))) return rc;
-    int tot[2] = {0, 0};                                 // both totals back in one copy
-    if ((rc = read_count(c, s.tot, tot, 2))) return rc;
-    const int nv = tot[0], nt = tot[1];
-    if (nv < 0 || nt < 0) { c->err = who + ": count out of range"; return ICP_ERR_HIP; }
-    *n_vertices_out = nv; *n_triangles_out = nt;
-    if (count_only) return guard.done();
-    if (nv > max_vertices || nt > max_triangles) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "%s: the mesh has %d vertices and %d triangles, the arrays hold %d and %d", who.c_str(), nv, nt, max_vertices, max_triangles);
-        c->err = buf;
-        return guard.done(ICP_ERR_INVALID_ARG);      // (synchronised by the count read)
-    }
-    if (nv == 0 && nt == 0) return guard.done();
-    // the outputs staged in device arrays of exactly the counted size: [vertices 12 V | normals 12 V | triangles 12 T | colours 4 V]
-    const size_t bv = (size_t)nv * 12, bn = normals_out ? bv : 0, bt = (size_t)nt * 12, bc = colors_out ? (size_t)nv * 4 : 0;
-    if ((rc = ensure(c, c->tm_out, bv + bn + bt + bc))) return rc;
-    char* d = c->tm_out.as<char>();
-    float* d_vert = (float*)d; float* d_nrm = normals_out ? (float*)(d + bv) : nullptr; uint32_t* d_tris = (uint32_t*)(d + bv + bn);
-    uint32_t* d_col = (uint32_t*)(d + bv + bn + bt);
-    if ((rc = tm_enqueue_fill(c, g, s, d_vert, d_nrm, d_tris))) return rc;
-    if (colors_out && nv > 0) {
-        hipLaunchKernelGGL(k_tm_colors, dim3((unsigned)tm_blocks(g)), dim3(256), 0, c->stream, tsdf_view(c), (const float4*)c->tsdf_col.as<float4>(), g, (const uint8_t*)s.mask,
-                           (const int*)s.vblk, d_col);
-        HIPCK(c, hipGetLastError());
-        HIPCK(c, hipMemcpyAsync(colors_out, d_col, bc, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (nv > 0) HIPCK(c, hipMemcpyAsync(vertices_out, d_vert, bv, hipMemcpyDeviceToHost, c->stream));
-    if (nv > 0 && normals_out) HIPCK(c, hipMemcpyAsync(normals_out, d_nrm, bn, hipMemcpyDeviceToHost, c->stream));
-    if (nt > 0) HIPCK(c, hipMemcpyAsync(triangles_out, d_tris, bt, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return guard.done();
+    return tm_finish(c, guard, s.tot, max_vertices, max_triangles, vertices_out, normals_out, colors_out, triangles_out, n_vertices_out, n_triangles_out, count_only, who,
+                     [&](float* d_vert, float* d_nrm, uint32_t* d_tris) { return tm_enqueue_fill(c, g, s, d_vert, d_nrm, d_tris); },
+                     [&](uint32_t* d_col) -> int {
+                         hipLaunchKernelGGL(k_tm_colors, dim3((unsigned)tm_blocks(g)), dim3(256), 0, c->stream, tsdf_view(c), (const float4*)c->tsdf_col.as<float4>(), g, (const uint8_t*)s.mask,
+                                            (const int*)s.vblk, d_col);
+                         HIPCK(c, hipGetLastError());
+                         return ICP_OK;
+                     });
 }
 }  // namespace
 
@@ -134,7 +149,6 @@ extern "C" int icp_debug_tsdf_mesh_time(icp_ctx* c, float min_weight, float* ms_
     if ((rc = tm_check_call(c, min_weight, "icp_debug_tsdf_mesh_time"))) return rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     const TmGrid g = tm_grid(c);
     TmScratch s;
     if ((rc = tm_scratch(c, g, s))) return rc;
@@ -145,12 +159,11 @@ extern "C" int icp_debug_tsdf_mesh_time(icp_ctx* c, float min_weight, float* ms_
     const size_t bv = (size_t)nv * 12, bt = (size_t)nt * 12;
     if ((rc = ensure(c, c->tm_out, 2 * bv + bt))) return rc;
     char* d = c->tm_out.as<char>();
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = tm_enqueue_count(c, g, s, min_weight))) return rc;
-    if ((rc = tm_enqueue_fill(c, g, s, (float*)d, (float*)(d + bv), (uint32_t*)(d + 2 * bv)))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
+    rc = timed_ms(c, ms_out, [&] {
+        int r = tm_enqueue_count(c, g, s, min_weight);
+        return r ? r : tm_enqueue_fill(c, g, s, (float*)d, (float*)(d + bv), (uint32_t*)(d + 2 * bv));
+    });
+    if (rc) return rc;
     return guard.done();
 }
 

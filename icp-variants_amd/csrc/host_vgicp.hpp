@@ -1,7 +1,8 @@
 // host_vgicp.hpp -- voxelized GICP: the target's voxel grid (icp_voxelize_target, icp_get_voxel_grid), the sums of one step
 // (icp_vgicp_system) and one alignment of the resident source to the grid (icp_vgicp_align).  Kernels: dev_vgicp.hpp, and dev_sdf.hpp's
-// k_sdf_init / k_sdf_solve launched as they are; contract: include/icp_hip.h, DESIGN.md section 6s.  Part of icp_hip.hip (included from there,
-// after host_sdf.hpp: the pose state, the partials and the record are that file's buffers, free again whenever an entry point has returned).
+// k_sdf_init / k_sdf_solve launched as they are, through host_sdf.hpp's shared driver (sdf_enqueue_pairs, sdf_read_state, sdf_read_record
+// for the geometric kind); contract: include/icp_hip.h, DESIGN.md section 6s.  Part of icp_hip.hip (included from there, after host_sdf.hpp:
+// the pose state, the partials and the record are that file's buffers, free again whenever an entry point has returned).
 namespace {
 const char* vgicp_options_error(const icp_vgicp_options* o) {
     if (!o) return "null options";
@@ -102,10 +103,7 @@ int vgicp_plan_source(icp_ctx* c, const icp_vgicp_options& opt, const char* who,
     pl->n_blocks = (s.n + 256 * VG_POINTS_PER_LANE - 1) / (256 * VG_POINTS_PER_LANE);
     pl->so.stride = 1; pl->so.n_iterations = opt.n_iterations; pl->so.min_valid = opt.min_valid; pl->so.huber = 0.f;
     pl->so.stop_rotation = opt.stop_rotation; pl->so.stop_translation = opt.stop_translation;
-    if ((rc = ensure(c, c->sdf_state, sizeof(SdfState)))) return rc;
-    if ((rc = ensure(c, c->sdf_partials, (size_t)pl->n_blocks * (SDF_NSUM * 8 + 2 * 4)))) return rc;
-    if ((rc = ensure(c, c->sdf_rec, sizeof(icp_sdf_frame) + (size_t)opt.n_iterations * sizeof(icp_sdf_iter)))) return rc;
-    return ICP_OK;
+    return sdf_buffers<SdfGeo>(c, pl->n_blocks, opt.n_iterations);
 }
 int vgicp_plan(icp_ctx* c, const icp_vgicp_options& opt, const char* who, VgPlan* pl) {
     int rc;
@@ -113,43 +111,20 @@ int vgicp_plan(icp_ctx* c, const icp_vgicp_options& opt, const char* who, VgPlan
     pl->g = vg_view(c, opt.min_points); pl->cells = c->vg_cells.as<float2>();
     return vgicp_plan_source(c, opt, who, pl);
 }
-// The source against the grid from `pose`, enqueued on the context's stream: the state, then `iterations` pairs of k_vgicp_accumulate and
-// k_sdf_solve (step = false: one pair that only folds).  Nothing here waits; the launches behind the alignment's end drain.
+// The source against the grid from `pose`, enqueued on the context's stream: host_sdf.hpp's sdf_enqueue_pairs for the geometric kind with
+// k_vgicp_accumulate (or, on a hashed voxel map's cells, k_hmap_accumulate) as the accumulate.  No upload slot is waited for: the source
+// is resident.  Nothing here waits; the launches behind the alignment's end drain.
 int vgicp_enqueue(icp_ctx* c, const VgPlan& pl, const float pose[16], bool step, bool trace) {
-    SdfState* st = c->sdf_state.as<SdfState>();
-    icp_sdf_frame* rec = c->sdf_rec.as<icp_sdf_frame>();
-    icp_sdf_iter* tr = (icp_sdf_iter*)(rec + 1);
-    double* partials = c->sdf_partials.as<double>();
-    int* counts = (int*)(partials + (size_t)SDF_NSUM * pl.n_blocks);
-    TsdfMat m; memcpy(m.m, pose, 64);
-    if (trace) HIPCK(c, hipMemsetAsync(tr, 0, (size_t)pl.so.n_iterations * sizeof(icp_sdf_iter), c->stream));
-    hipLaunchKernelGGL(k_sdf_init, dim3(1), dim3(64), 0, c->stream, st, m, rec);
-    SdfSolve sp;
-    sp.partials = partials; sp.counts = counts; sp.n_blocks = pl.n_blocks; sp.st = st; sp.rec = rec; sp.trace = trace ? tr : nullptr;
-    sp.n_iterations = pl.so.n_iterations; sp.min_valid = pl.so.min_valid; sp.step = step ? 1 : 0;
-    sp.stop_rotation = pl.so.stop_rotation; sp.stop_translation = pl.so.stop_translation;
-    const int iterations = step ? pl.so.n_iterations : 1;
-    for (int it = 0; it < iterations; it++) {
-        if (pl.h.keys) hipLaunchKernelGGL(k_hmap_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.h, pl.cells, pl.s, (const SdfState*)st, partials, counts);
-        else hipLaunchKernelGGL(k_vgicp_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.g, pl.cells, pl.s, (const SdfState*)st,
-                           partials, counts);
-        sp.iter = it;
-        hipLaunchKernelGGL(k_sdf_solve, dim3(1), dim3(256), 0, c->stream, sp);
-    }
-    HIPCK(c, hipGetLastError());
-    return ICP_OK;
+    return sdf_enqueue_pairs<SdfGeo>(c, pl.n_blocks, pl.so, pose, step, trace, [&](const SdfState* st, double* partials, int* counts) {
+        if (pl.h.keys) hipLaunchKernelGGL(k_hmap_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.h, pl.cells, pl.s, st, partials, counts);
+        else hipLaunchKernelGGL(k_vgicp_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.g, pl.cells, pl.s, st, partials, counts);
+    });
 }
 // One fold at `pose` and the state read back: what icp_vgicp_system does behind its plan.
 int vgicp_system_run(icp_ctx* c, const VgPlan& pl, const float pose[16], double* sums_out, int32_t* counts_out) {
     int rc;
     if ((rc = vgicp_enqueue(c, pl, pose, false, false))) return rc;
-    if ((rc = ensure_pinned(c, 2048 + sizeof(SdfState)))) return rc;
-    SdfState* h = (SdfState*)(c->pinned.as<char>() + 2048);
-    HIPCK(c, hipMemcpyAsync(h, c->sdf_state.p, sizeof(SdfState), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    memcpy(sums_out, h->sums, sizeof(h->sums));
-    counts_out[0] = h->counts[0]; counts_out[1] = h->counts[1];
-    return ICP_OK;
+    return sdf_read_state<SdfGeo>(c, sums_out, counts_out);
 }
 std::string vgicp_failure(const char* who, const icp_sdf_frame& r, int min_valid) {
     char buf[224];
@@ -164,7 +139,7 @@ int vgicp_align_run(icp_ctx* c, const VgPlan& pl, const icp_vgicp_options& opt, 
     const bool trace = trace_out && max_trace > 0;
     if ((rc = vgicp_enqueue(c, pl, pose_inout, true, trace))) return rc;
     std::vector<icp_sdf_iter> tr(trace ? (size_t)opt.n_iterations : 0);
-    if ((rc = sdf_read_record(c, pl.so, r, trace ? tr.data() : nullptr))) return rc;
+    if ((rc = sdf_read_record<SdfGeo>(c, pl.so, r, trace ? tr.data() : nullptr))) return rc;
     if (trace) memcpy(trace_out, tr.data(), (size_t)(max_trace < opt.n_iterations ? max_trace : opt.n_iterations) * sizeof(icp_sdf_iter));
     if (rec_out) *rec_out = *r;
     memcpy(pose_inout, r->pose, 64);
@@ -253,23 +228,14 @@ extern "C" int icp_debug_vgicp_time(icp_ctx* c, const float pose[16], const icp_
     if ((rc = vgicp_check_call(c, opt, pose, "icp_debug_vgicp_time"))) return rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     if ((rc = vg_build(c, opt->voxel_size, "icp_debug_vgicp_time"))) return rc;      // (warm: normals cached, buffers allocated, code loaded)
     c->vg_ready = false;
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = vg_build(c, opt->voxel_size, "icp_debug_vgicp_time"))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(build_ms_out, c->events[0], c->events[1]));
+    if ((rc = timed_ms(c, build_ms_out, [&] { return vg_build(c, opt->voxel_size, "icp_debug_vgicp_time"); }))) return rc;
     VgPlan pl;
     if ((rc = vgicp_plan(c, *opt, "icp_debug_vgicp_time", &pl))) return rc;
     pl.so.n_iterations = 1;
     if ((rc = vgicp_enqueue(c, pl, pose, true, false))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = vgicp_enqueue(c, pl, pose, true, false))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(iter_ms_out, c->events[0], c->events[1]));
+    if ((rc = timed_ms(c, iter_ms_out, [&] { return vgicp_enqueue(c, pl, pose, true, false); }))) return rc;
     return guard.done();
 }

@@ -224,7 +224,7 @@ int icp_track_scans_vmap(icp_ctx* c, const float* const* xyz, const float* const
             icp_sdf_frame& r = out[k - 1];
             if ((rc = vgicp_enqueue(c, pl, pose_inout, true, false))) return rc;
             // the one host read of the scan: the insert takes its pose from the host (a hashed map's occupied count comes with it)
-            if ((rc = c->vm_hashed ? hmap_read_record(c, pl.so, &r, who) : sdf_read_record(c, pl.so, &r, nullptr))) return rc;
+            if ((rc = c->vm_hashed ? hmap_read_record(c, pl.so, &r, who) : sdf_read_record<SdfGeo>(c, pl.so, &r, nullptr))) return rc;
             memcpy(pose_inout, r.pose, 64);
             if (r.status != ICP_OK) {
                 if (first_err == ICP_OK) { first_err = r.status; c->err = vgicp_failure(who, r, opt->min_valid); }
@@ -249,7 +249,6 @@ extern "C" int icp_debug_vmap_time(icp_ctx* c, int32_t which, const float pose[1
     if ((rc = vmap_check(c, who))) return rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     if (c->vm_hashed) {
         if ((rc = gicp_normals(c, which))) return rc;
         if ((rc = hmap_debug_time(c, which, pose, insert_ms_out, records_ms_out, who))) return rc;
@@ -257,20 +256,16 @@ extern "C" int icp_debug_vmap_time(icp_ctx* c, int32_t which, const float pose[1
     }
     if ((rc = vmap_insert_enqueue(c, which, pose, who))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = vmap_insert_enqueue(c, which, pose, who))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(insert_ms_out, c->events[0], c->events[1]));
+    if ((rc = timed_ms(c, insert_ms_out, [&] { return vmap_insert_enqueue(c, which, pose, who); }))) return rc;
     const Cloud& cl = which ? c->src : c->tgt;
     const size_t n_cells = vm_cells(c);
     const int list_cap = (size_t)cl.n < n_cells ? cl.n : (int)n_cells;
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    hipLaunchKernelGGL(k_vmap_records, dim3((list_cap + 255) / 256), dim3(256), 0, c->stream, vm_view(c, 1), list_cap, (const int*)c->vm_ctr.as<int>(),
-                       (const int*)c->vm_list.as<int>(), (const int*)c->vm_count.as<int>(), (const long long*)c->vm_sums.as<long long>(), c->vm_cells.as<float2>());
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(records_ms_out, c->events[0], c->events[1]));
+    rc = timed_ms(c, records_ms_out, [&] {
+        hipLaunchKernelGGL(k_vmap_records, dim3((list_cap + 255) / 256), dim3(256), 0, c->stream, vm_view(c, 1), list_cap, (const int*)c->vm_ctr.as<int>(),
+                           (const int*)c->vm_list.as<int>(), (const int*)c->vm_count.as<int>(), (const long long*)c->vm_sums.as<long long>(), c->vm_cells.as<float2>());
+        return ICP_OK;
+    });
+    if (rc) return rc;
     return guard.done();
 }
 
@@ -283,7 +278,6 @@ extern "C" int icp_debug_vmap_accumulate_time(icp_ctx* c, const float pose[16], 
     int rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     VgPlan pl;
     if ((rc = vmap_plan(c, opt, pose, who, &pl))) return rc;
     if ((rc = vgicp_enqueue(c, pl, pose, false, false))) return rc;
@@ -291,15 +285,15 @@ extern "C" int icp_debug_vmap_accumulate_time(icp_ctx* c, const float pose[16], 
     double* partials = c->sdf_partials.as<double>();
     int* counts = (int*)(partials + (size_t)SDF_NSUM * pl.n_blocks);
     const SdfState* st = c->sdf_state.as<SdfState>();
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    for (int r = 0; r < reps; r++) {
-        if (pl.h.keys) hipLaunchKernelGGL(k_hmap_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.h, pl.cells, pl.s, st, partials, counts);
-        else hipLaunchKernelGGL(k_vgicp_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.g, pl.cells, pl.s, st, partials, counts);
-    }
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
-    HIPCK(c, hipEventElapsedTime(&ms, c->events[0], c->events[1]));
+    rc = timed_ms(c, &ms, [&] {
+        for (int r = 0; r < reps; r++) {
+            if (pl.h.keys) hipLaunchKernelGGL(k_hmap_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.h, pl.cells, pl.s, st, partials, counts);
+            else hipLaunchKernelGGL(k_vgicp_accumulate, dim3(pl.n_blocks), dim3(256), 0, c->stream, pl.g, pl.cells, pl.s, st, partials, counts);
+        }
+        return ICP_OK;
+    });
+    if (rc) return rc;
     *ms_out = ms / (float)reps;
     return guard.done();
 }

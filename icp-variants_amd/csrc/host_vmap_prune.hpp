@@ -46,7 +46,7 @@ int vmap_read_record_local(icp_ctx* c, const icp_sdf_options& so, icp_sdf_frame*
     if ((rc = ensure_pinned(c, 4096 + sizeof(icp_sdf_frame)))) return rc;
     int* h = (int*)(c->pinned.as<char>() + 2016);
     HIPCK(c, hipMemcpyAsync(h, c->vm_ctr.as<int>() + VM_OCCUPIED, VM_TAIL_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = sdf_read_record(c, so, r, nullptr))) return rc;
+    if ((rc = sdf_read_record<SdfGeo>(c, so, r, nullptr))) return rc;
     return vmap_prune_take(c, h, pending, who);
 }
 int vmap_read_prune(icp_ctx* c, icp_voxel_map_prune_info* o, const char* who) {
@@ -146,13 +146,8 @@ extern "C" int icp_debug_vmap_prune_time(icp_ctx* c, const float centre[3], floa
     if ((rc = vmap_check(c, "icp_debug_vmap_prune_time"))) return rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = vmap_prune_enqueue(c, centre, radius * radius))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
+    if ((rc = timed_ms(c, ms_out, [&] { return vmap_prune_enqueue(c, centre, radius * radius); }))) return rc;
     return guard.done();
 }
 extern "C" int icp_debug_hmap_compact_time(icp_ctx* c, float* ms_out) {
@@ -161,12 +156,7 @@ extern "C" int icp_debug_hmap_compact_time(icp_ctx* c, float* ms_out) {
     if ((rc = hmap_check(c, "icp_debug_hmap_compact_time"))) return rc;
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
-    if ((rc = ensure_events(c, 2))) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventRecord(c->events[0], c->stream));
-    if ((rc = hmap_rehash(c, c->vh_log2cap, true))) return rc;
-    HIPCK(c, hipEventRecord(c->events[1], c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    HIPCK(c, hipEventElapsedTime(ms_out, c->events[0], c->events[1]));
+    if ((rc = timed_ms(c, ms_out, [&] { return hmap_rehash(c, c->vh_log2cap, true); }))) return rc;
     return guard.done();
 }

@@ -27,11 +27,15 @@ def test_poses_are_the_neighbours():
 
 def test_block_counts_under_the_hosts_own_formulas():
     """sdf_plan (host_sdf.hpp) and vgicp_plan (host_vgicp.hpp) as they are written, evaluated on the shapes of fold_cases: the table of
-    SDF_CASES and VG_CASES is keyed by the result.  The colour plan takes sdf_plan's grid."""
+    SDF_CASES and VG_CASES is keyed by the result.  The colour kind takes sdf_plan's grid: host_sdf.hpp's driver plans for both kinds."""
     plan = source("host_sdf.hpp")
     assert "f.ws = (cam.width + opt.stride - 1) / opt.stride; f.hs = (cam.height + opt.stride - 1) / opt.stride;" in plan
     assert "pl->grid = dim3((f.ws + 15) / 16, (f.hs + 15) / 16);" in plan and "pl->n_blocks = (int)(pl->grid.x * pl->grid.y);" in plan
-    assert "if ((rc = sdf_plan(c, cam, opt, pl))) return rc;" in source("host_sdf_color.hpp")
+    # the colour kind has no plan of its own: every coloured call goes through the shared driver, which plans with sdf_plan for either kind
+    color = source("host_sdf_color.hpp")
+    assert "if ((rc = sdf_plan<K>(c, cam, opt, pl))) return rc;" in plan and "if ((rc = sdf_plan<K>(c, cam, opt, &pl))) return rc;" in plan
+    assert "pl->grid" not in color and "n_blocks" not in color and "sdf_plan" not in color
+    assert all(call in color for call in ("sdf_system<SdfColor>(", "sdf_align<SdfColor>(", "sdf_track<SdfColor>(", "sdf_time<SdfColor>("))
     for blocks, (w, h, stride) in F.SDF_CASES.items():
         ws, hs = (w + stride - 1) // stride, (h + stride - 1) // stride
         assert ((ws + 15) // 16) * ((hs + 15) // 16) == blocks == F.sdf_blocks(w, h, stride), (blocks, w, h, stride)
