@@ -1,6 +1,6 @@
 // host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
 // and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
-// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_tsdf_hash, host_tsdf_hash_raycast, host_sdf, host_vgicp, host_hmap, host_vmap, host_vmap_prune, host_sdf_color, host_tsdf_mesh, host_tsdf_hash_mesh, host_global, host_debug.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_tsdf_hash, host_tsdf_hash_raycast, host_sdf, host_vgicp, host_hmap, host_vmap, host_vmap_prune, host_sdf_color, host_tsdf_mesh, host_tsdf_hash_mesh, host_tsdf_hash_evict, host_tsdf_cloud, host_global, host_debug.
 using namespace icpdev;
 
 #define HIPCK(ctx, expr)                                                                        \
@@ -160,6 +160,7 @@ struct icp_ctx {
     DevBuf th_cpool; bool th_color = false;   // the colours of the hashed volume (icp_tsdf_create_color_hashed): a second pool, one float4 (R, G, B, Wc) per voxel, 8 KiB per block, by the same pool index
     DevBuf te_out_cpool;                 // the colours of the outbox (a coloured hashed volume evicted with hold)
     DevBuf te_work, te_out_pool, te_out_key; int te_held = 0;   // streaming the hashed volume (host_tsdf_hash_evict.hpp): an evict's flags, lists and counters; the outbox (evicted blocks and their keys) and the blocks it holds
+    DevBuf tc_acc, tc_ctr; size_t tc_voxels = 0;   // icp_tsdf_integrate_cloud (host_tsdf_cloud.hpp): the integer accumulators [S 8 bytes | N 4 bytes] per voxel of the box or the pool, the call's 64-bit counters; the voxels the accumulators are laid out for and all zero over (0: to be made and cleared)
     DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
     DevBuf tm_nbr, tm_ord;               // icp_tsdf_mesh_hashed (host_tsdf_hash_mesh.hpp), which also uses the five above: the 27 neighbour ranks of every block; order[rank] -> pool index, then rank_of[pool index]
     DevBuf sdf_state, sdf_partials, sdf_rec; Event sdf_ev;   // direct SDF tracking (host_sdf.hpp's driver, for the record kinds SdfGeo and SdfColor, and host_vgicp.hpp through it): the kind's pose / stop state, partials[NSUM][blocks] + counts[NCOUNT][blocks] (28 + 2 or 29 + 3), the frame record + trace; they only grow, every call writes them before it reads them; "the last integration has left its upload slot"

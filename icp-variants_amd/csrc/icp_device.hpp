@@ -10,7 +10,7 @@
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
 // dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf_color.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp, dev_sdf.hpp, dev_sdf_color.hpp, dev_vgicp.hpp,
 // dev_vmap.hpp, dev_hmap.hpp, dev_tsdf_hash.hpp, dev_tsdf_hash_raycast.hpp, dev_tsdf_hash_mesh.hpp, dev_tsdf_hash_evict.hpp, dev_tsdf_hash_color.hpp,
-// dev_tsdf_hash_raycast_color.hpp, dev_tsdf_hash_mesh_color.hpp, dev_vmap_prune.hpp
+// dev_tsdf_hash_raycast_color.hpp, dev_tsdf_hash_mesh_color.hpp, dev_vmap_prune.hpp, dev_tsdf_cloud.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -81,6 +81,8 @@
 //   k_vmap_prune /      forgetting the map's cells beyond a radius of a centre (icp_voxel_map_prune, icp_track_scans_vmap_local), and
 //   k_hmap_prune /      the compaction of a hashed table that has vacated slots (dev_vmap_prune.hpp)
 //   k_hmap_compact
+//   k_*tsdf_*_cloud     a laser scan fused into the TSDF volume, dense or hashed (icp_tsdf_integrate_cloud): the blocks of every ray's band
+//                       allocated, the rays' observations summed per voxel in integers, and folded into (tsdf, weight) once (dev_tsdf_cloud.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -130,5 +132,6 @@ namespace icpdev {
 #include "dev_tsdf_hash_raycast_color.hpp"
 #include "dev_tsdf_hash_mesh_color.hpp"
 #include "dev_vmap_prune.hpp"
+#include "dev_tsdf_cloud.hpp"
 
 }  // namespace icpdev

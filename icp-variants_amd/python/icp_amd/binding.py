@@ -100,6 +100,11 @@ class IcpTsdfHashedInfo(C.Structure):
     _fields_ = [("n_blocks", C.c_int32), ("capacity", C.c_int32), ("n_grown", C.c_int32), ("n_unplaced", C.c_int32), ("n_out_of_range", C.c_int64)]
 
 
+class IcpTsdfCloudInfo(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("n_rays", C.c_int32), ("n_updated", C.c_int32), ("n_blocks", C.c_int32), ("n_samples", C.c_int64),
+                ("n_outside", C.c_int64)]
+
+
 class IcpTsdfStreamInfo(C.Structure):
     _fields_ = [("n_evicted", C.c_int32), ("n_blocks", C.c_int32), ("n_moved", C.c_int32), ("capacity", C.c_int32), ("n_held", C.c_int32),
                 ("n_inserted", C.c_int32), ("n_present", C.c_int32), ("n_grown", C.c_int32)]
@@ -507,7 +512,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_sdf_options_default", "icp_sdf_options_check", "icp_tsdf_sample", "icp_tsdf_sdf_system", "icp_tsdf_align_depth", "icp_track_depth_sdf",
            "icp_tsdf_create_hashed", "icp_tsdf_reserve_blocks", "icp_tsdf_allocate_blocks", "icp_get_tsdf_hashed", "icp_tsdf_upload_hashed",
            "icp_tsdf_mesh_hashed", "icp_tsdf_raycast_hashed", "icp_set_target_tsdf_hashed", "icp_track_depth_model_hashed",
-           "icp_tsdf_evict_blocks", "icp_tsdf_evicted_blocks", "icp_tsdf_insert_blocks",
+           "icp_tsdf_evict_blocks", "icp_tsdf_evicted_blocks", "icp_tsdf_insert_blocks", "icp_tsdf_integrate_cloud",
            "icp_tsdf_create_color_hashed", "icp_tsdf_hashed_has_color", "icp_get_tsdf_color_hashed", "icp_tsdf_upload_color_hashed",
            "icp_tsdf_evicted_blocks_color", "icp_tsdf_insert_blocks_color",
            "icp_tsdf_raycast_color_hashed", "icp_set_target_tsdf_color_hashed", "icp_track_depth_model_color_hashed", "icp_tsdf_mesh_color_hashed",
@@ -1264,6 +1269,22 @@ class Context:
             return n.value, nc.value
         self._ck(self.lib.icp_tsdf_integrate(self.h, _ptr(depth), C.byref(cam), _ptr(pose_to_c(pose)), C.byref(n)))
         return n.value
+
+    def tsdf_integrate_cloud(self, which="source", pose=None, sensor_origin=None):
+        """icp_tsdf_integrate_cloud: fuses the resident target ("target" / 0) or source ("source" / 1) -- an unorganised cloud in its sensor
+        frame, a laser scan -- into the volume, dense or hashed, as one observation.  pose: 4x4 scan frame -> world
+        (None: the identity); sensor_origin: the ray origin in the scan frame (None: (0, 0, 0)).  Geometry only: the colours of a coloured
+        volume stay as they are.  Returns dict(n_points, n_rays, n_updated, n_blocks, n_samples, n_outside)."""
+        w = _cloud(which)
+        p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
+        e = None
+        if sensor_origin is not None:
+            e = _f32(sensor_origin).reshape(-1)
+            if e.size != 3:
+                raise ValueError("sensor_origin must hold three numbers")
+        info = IcpTsdfCloudInfo()
+        self._ck(self.lib.icp_tsdf_integrate_cloud(self.h, C.c_int32(w), _ptr(p), _ptr(e), C.byref(info)))
+        return _record(info)
 
     def tsdf_raycast(self, cam, pose):
         """icp_tsdf_raycast: the volume seen from `pose` as an organised cloud in that camera's frame.  Returns (depth (h, w), vertices

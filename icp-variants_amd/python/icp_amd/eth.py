@@ -129,6 +129,51 @@ def track_map(ctx, scans, start_pose, voxel_size=0.25, extent=None, margin=2.0, 
     return run()
 
 
+def fuse_scans(ctx, scans, poses, voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, hashed=True, dims=None):
+    """Laser scans fused into a TSDF volume (Context.tsdf_integrate_cloud): `scans` as track_map takes them (a list
+    of (xyz, normals) in the sensor frame; a bare xyz array will do, the normals are not used), `poses` one 4x4 sensor -> world per scan.
+    A volume of `voxel_size` metres is created -- hashed by default (Context.tsdf_create_hashed with `block_capacity`; it has no extent),
+    or, with hashed=False, the dense box of `dims` voxels whose voxel (0, 0, 0) is centred on `origin` -- with `truncation` (None: 4
+    voxels) and max_depth = `max_range`: a return beyond it is not fused.  Every scan becomes the resident source and is integrated from
+    the sensor's position, one observation per scan.  Returns the info dict of every scan; the volume stays in the context
+    (Context.tsdf_sample, Context.tsdf_mesh_hashed, Context.tsdf_blocks)."""
+    if len(scans) != len(poses):
+        raise ValueError("one pose per scan")
+    if not hashed and dims is None:
+        raise ValueError("a dense volume needs dims")
+    if hashed and dims is not None:
+        raise ValueError("a hashed volume has no extent")
+    opts = dict(origin=tuple(float(x) for x in origin), voxel_size=float(voxel_size), truncation=4.0 * float(voxel_size) if truncation is None else float(truncation),
+                max_depth=float(max_range))
+    if hashed:
+        ctx.tsdf_create_hashed(block_capacity=block_capacity, **opts)
+    else:
+        ctx.tsdf_create(dims=dims, **opts)
+    infos = []
+    for s, T in zip(scans, poses):
+        xyz = s[0] if isinstance(s, (tuple, list)) else s
+        ctx.set_source(np.ascontiguousarray(xyz, np.float32))
+        infos.append(ctx.tsdf_integrate_cloud("source", pose=np.asarray(T, np.float32)))
+    return infos
+
+
+def reconstruct(ctx, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, min_weight=0.0,
+                mesh_path=None, **track_map_options):
+    """A surface from a laser sequence, the laser counterpart of tum.reconstruct_room: the scans tracked against the voxel map
+    (`track_map` with **track_map_options; its voxel_size is the MAP's), fused at the tracked poses into a hashed TSDF volume of
+    `tsdf_voxel_size` (`fuse_scans`), the zero level set extracted on the device (Context.tsdf_mesh_hashed with `min_weight`) and, with
+    mesh_path, written as a PLY (meshio.write_ply_mesh).  Returns (poses, records, status, (vertices, normals, triangles))."""
+    from . import meshio
+    if "keep_radius" in track_map_options and track_map_options["keep_radius"] is not None:
+        raise ValueError("reconstruct tracks against the whole map (keep_radius is not supported)")
+    poses, records, status = track_map(ctx, scans, start_pose, **track_map_options)
+    fuse_scans(ctx, scans, poses, voxel_size=tsdf_voxel_size, truncation=truncation, origin=origin, max_range=max_range, block_capacity=block_capacity)
+    mesh = ctx.tsdf_mesh_hashed(min_weight=min_weight)
+    if mesh_path is not None:
+        meshio.write_ply_mesh(mesh_path, *mesh)
+    return poses, records, status, mesh
+
+
 def write_synthetic_dataset(eth_dir, csv_name, pairs, binary=True):
     """Writes synthetic scans in the reference's on-disk layout (used by the tests and for rehearsing --eth-dir offline):
     `pairs` = list of dicts with src_unperturbed, tgt_pts and a benchmark `pose` (unscaled perturbation)."""

@@ -1472,6 +1472,54 @@ int icp_depth_filter_tables(const icp_depth_filter_options* opt, float* spatial_
 /* Filters one frame, host to host, with `opt` (NULL: the context's options); radius 0 copies the input.  depth_out: width x height floats. */
 int icp_filter_depth(icp_ctx* ctx, const float* depth, int32_t width, int32_t height, const icp_depth_filter_options* opt, float* depth_out);
 
+/* -------- a laser scan into the TSDF volume: icp_tsdf_integrate_cloud --------
+ * Every integrate above takes a depth image and a pinhole camera.  This one takes a RESIDENT cloud, unorganised, in icp_voxel_map_insert's
+ * convention (which = 0: the target, 1: the source), and fuses it as ONE observation, as one depth frame is: every usable point is a ray
+ * from the sensor centre, walked through the truncation band in steps of one voxel, and each sample observes its nearest voxel.  It works
+ * on whichever volume the context holds, dense (icp_tsdf_create) or hashed (icp_tsdf_create_hashed); everything that reads the volume
+ * (icp_tsdf_sample, the ray-casts, icp_tsdf_mesh / icp_tsdf_mesh_hashed, evict and insert) takes the result as it takes fused frames.
+ * On a COLOURED volume the call writes geometry only: the colour array or pool is neither read nor written.
+ * The call carves NO free space in front of the band (as the hashed depth touch allocates none there): a voxel nearer to the sensor than
+ * range - truncation is not observed.  A ray writes a line ONE voxel wide, so a surface becomes watertight only where neighbouring beams
+ * are closer than a voxel at the surface: choose voxel_size for the scanner's angular step and the range of interest.
+ * The result does not depend on the order of the points, nor on any race: the scan is accumulated per voxel in integers (S 64-bit, N
+ * 32-bit, two plain arrays: no limit on the size of the cloud beyond int32 points) and folded into the float state once.  The
+ * accumulators cost 12 bytes per voxel (6 KiB per pool block of a hashed volume, 1.5 x a dense volume), are allocated at the first call
+ * and leave with the volume.
+ *
+ * Contract (fp32, one rounding per operation, in the order written; tests/tsdf_cloud_restatement.py restates it in numpy).  P = pose (scan
+ * frame -> world, column-major, P_rc = pose[4 c + r]), e = sensor_origin (the ray origin in the scan frame; NULL = (0, 0, 0)), o, s,
+ * truncation, max_weight and max_depth the volume's options (min_depth and ray_step are not used).
+ *   Sensor centre: c_r = (P_r0 e_x + (P_r1 e_y + P_r2 e_z)) + P_r3.
+ *   Ray of point p (finite on all three axes, else not usable): w_r = (P_r0 p_x + (P_r1 p_y + P_r2 p_z)) + P_r3; d = w - c per axis;
+ *   r2 = d_x d_x + (d_y d_y + d_z d_z); r = sqrtf(r2); usable iff r is finite, r > 0 and r <= max_depth; u = d / r per axis.
+ *   Samples m = 0 .. M, M = ceil(2 truncation / s) in double (the hashed touch's walk): t_m = fminf((r - truncation) + (float)m s,
+ *   r + truncation), skipped unless t_m > 0; q_a = c_a + t_m u_a; the sample's voxel is the nearest one, g_a = floorf(((q_a - o_a) / s) +
+ *   0.5f).  In range iff, tested in float before any cast, -2^23 <= g_a <= 2^23 - 1 on every axis (hashed) or 0 <= g_a <= n_a - 1 (dense);
+ *   any other sample is counted in n_outside and does nothing.  An in-range sample whose voxel equals that of the ray's previous in-range
+ *   sample is skipped; every other in-range sample is counted in n_samples.
+ *   Observation of voxel g by that sample: x_a = o_a + (float)g_a s; e_a = x_a - c_a; proj = e_x u_x + (e_y u_y + e_z u_z); sdf = r - proj;
+ *   skipped if sdf < -truncation; f = fminf(1, sdf / truncation); k = (int)rintf(f * 32768.f); the voxel's S += k, N += 1.
+ *   Fold, for every voxel with N > 0: fbar = (float)((double)S / ((double)N * 32768.0)); D <- (W D + fbar) / (W + 1); W <- fminf(W + 1,
+ *   max_weight).  n_updated counts these voxels; a voxel with N == 0 is neither read nor written.
+ *   Touch (hashed, before the accumulate, from the cloud and the pose alone): the block g >> 3 of every in-range sample's voxel is
+ *   allocated, whether or not the sdf test skips the sample, under the room rule of icp_tsdf_integrate (table and pool double while a
+ *   claim is unplaced).  The set of blocks is exact.
+ * Returns ICP_ERR_INVALID_ARG (no volume; which not 0 or 1; a null or non-finite pose; a non-finite sensor_origin; a hashed volume that
+ * would have to grow beyond 2^22 blocks) or ICP_ERR_NO_TARGET / ICP_ERR_NO_SOURCE (no such cloud), with a message that names the call and
+ * the volume as it was. */
+typedef struct icp_tsdf_cloud_info {
+    int32_t n_points, n_rays;      /* points of the cloud; those that were usable */
+    int32_t n_updated;             /* voxels written */
+    int32_t n_blocks;              /* hashed: allocated blocks after the call; dense: 0 */
+    int64_t n_samples;             /* in-range samples that reached a voxel */
+    int64_t n_outside;             /* samples outside the box (dense) or not storable (hashed; also added to n_out_of_range) */
+} icp_tsdf_cloud_info;
+#ifdef __cplusplus
+static_assert(sizeof(icp_tsdf_cloud_info) == 32, "icp_tsdf_cloud_info");
+#endif
+int icp_tsdf_integrate_cloud(icp_ctx* ctx, int32_t which, const float pose[16], const float sensor_origin[3], icp_tsdf_cloud_info* info_out);
+
 /* -------- batches of independent scan pairs: the loop over ETH indices, main.cpp:411-498 / experiment.cpp:319-396 --------
  * The reference aligns the pairs one after the other and carries no state between them, so a batch shards with no
  * data-path exchange: pair p belongs to rank p % n_ranks (icp_pair_owner), and the only collective is ONE gather of the
