@@ -70,6 +70,27 @@ def upload(ctx, vol, color=False):
         ctx.tsdf_color_upload(vol.rgb, vol.wc)
 
 
+def tsdf_blocks_equal_restatement(ctx, hv, what):
+    """The context's hashed TSDF volume against an htsdf_restatement.HVolume: coordinates, tsdf and weight bit for bit, nothing unplaced."""
+    info, coords, t, w = ctx.tsdf_blocks()
+    rc, rt, rw = hv.sorted_blocks()
+    assert info["n_blocks"] == len(rc) and info["n_unplaced"] == 0 and info["n_out_of_range"] == hv.n_out_of_range, (what, info, len(rc))
+    assert np.array_equal(coords, rc), what
+    assert same_bits(t, rt) and same_bits(w, rw), what
+    return info
+
+
+def fuse_cloud(ctx, vol, pts, pose, origin=None):
+    """The cloud as the source, fused on the device and by tsdf_cloud_restatement into `vol`; every field of the info equal."""
+    import tsdf_cloud_restatement as CR
+    ctx.set_source(pts)
+    info = ctx.tsdf_integrate_cloud("source", pose=pose, sensor_origin=origin)
+    want = CR.integrate(vol, pts, pose, origin)
+    print("cloud of %d: %s" % (len(pts), info))
+    assert info == want, (info, want)
+    return info
+
+
 def loaded_ctx(factory, tgt, src, **params):
     """A context with `params` set by name and the (points, normals, colours) triples resident; src may be None."""
     c = factory()

@@ -9,43 +9,15 @@ import htsdf_cases as HC
 import htsdf_restatement as HR
 import tsdf_cloud_outcome_fixture as CF
 import tsdf_cloud_restatement as CR
-from support import same_bits, pose_of
+from support import same_bits, pose_of, tsdf_blocks_equal_restatement as assert_equals_restatement, fuse_cloud as fuse
+from tsdf_cloud_cases import cloud, OPTS, DYADIC
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 ERR_INVALID_ARG, ERR_NO_TARGET, ERR_NO_SOURCE = 1, 3, 4
-OPTS = dict(origin=(0.25, 0.15, 1.3), voxel_size=0.1, truncation=0.3, max_weight=64.0, min_depth=0.3, max_depth=6.0)
 ODD = dict(OPTS, truncation=0.22)                   # 2 truncation / s = 4.4: the last sample is the fminf clamp
-DYADIC = dict(origin=(0.0, 0.0, 0.0), voxel_size=0.25, truncation=0.75, max_weight=64.0, min_depth=0.3, max_depth=6.0)
 TILTED = pose_of((0.12, -0.2, 0.07), (0.1, -0.05, 0.02))
 EYE = np.eye(4, dtype=f32)
-
-
-def cloud(n, seed=3):
-    """n points of a wavy wall 1 .. 3 m in front of the sensor, in the sensor frame."""
-    r = np.random.default_rng(seed)
-    a, b = r.uniform(-0.9, 0.9, n), r.uniform(-0.6, 0.6, n)
-    z = 2.0 + 0.8 * np.sin(3 * a) * np.cos(2 * b)
-    return np.stack([np.tan(a) * z, np.tan(b) * z, z], 1).astype(f32)
-
-
-def assert_equals_restatement(ctx, hv, what):
-    info, coords, t, w = ctx.tsdf_blocks()
-    rc, rt, rw = hv.sorted_blocks()
-    assert info["n_blocks"] == len(rc) and info["n_unplaced"] == 0 and info["n_out_of_range"] == hv.n_out_of_range, (what, info, len(rc))
-    assert np.array_equal(coords, rc), what
-    assert same_bits(t, rt) and same_bits(w, rw), what
-    return info
-
-
-def fuse(ctx, vol, pts, pose, origin=None):
-    """The cloud as the source, fused on the device and by the restatement; every field of the info equal."""
-    ctx.set_source(pts)
-    info = ctx.tsdf_integrate_cloud("source", pose=pose, sensor_origin=origin)
-    want = CR.integrate(vol, pts, pose, origin)
-    print("cloud of %d: %s" % (len(pts), info))
-    assert info == want, (info, want)
-    return info
 
 
 def far_pose():
