@@ -1,6 +1,6 @@
 // host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
 // and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
-// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_tsdf_hash, host_tsdf_hash_raycast, host_sdf, host_vgicp, host_hmap, host_vmap, host_vmap_prune, host_sdf_color, host_tsdf_mesh, host_tsdf_hash_mesh, host_tsdf_hash_evict, host_tsdf_cloud, host_global, host_debug.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_tsdf_hash, host_tsdf_hash_raycast, host_sdf, host_vgicp, host_hmap, host_vmap, host_vmap_prune, host_sdf_color, host_tsdf_mesh, host_tsdf_hash_mesh, host_tsdf_hash_evict, host_tsdf_cloud, host_sdf_cloud, host_global, host_debug.
 using namespace icpdev;
 
 #define HIPCK(ctx, expr)                                                                        \

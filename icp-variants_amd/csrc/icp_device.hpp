@@ -83,6 +83,8 @@
 //   k_hmap_compact
 //   k_*tsdf_*_cloud     a laser scan fused into the TSDF volume, dense or hashed (icp_tsdf_integrate_cloud): the blocks of every ray's band
 //                       allocated, the rays' observations summed per voxel in integers, and folded into (tsdf, weight) once (dev_tsdf_cloud.hpp)
+//   k_*sdf_accumulate_cloud  direct SDF tracking of a laser scan (icp_tsdf_align_cloud, icp_track_scans_sdf): the resident cloud's point-to-plane
+//                       sums read from the volume's field and gradient, dense or hashed; k_sdf_solve behind them (dev_sdf_cloud.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -133,5 +135,6 @@ namespace icpdev {
 #include "dev_tsdf_hash_mesh_color.hpp"
 #include "dev_vmap_prune.hpp"
 #include "dev_tsdf_cloud.hpp"
+#include "dev_sdf_cloud.hpp"
 
 }  // namespace icpdev

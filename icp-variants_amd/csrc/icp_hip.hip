@@ -45,6 +45,7 @@
 #include "host_tsdf_hash_mesh.hpp"
 #include "host_tsdf_hash_evict.hpp"
 #include "host_tsdf_cloud.hpp"
+#include "host_sdf_cloud.hpp"
 #include "host_global.hpp"
 #include "host_debug.hpp"
 

@@ -513,6 +513,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_create_hashed", "icp_tsdf_reserve_blocks", "icp_tsdf_allocate_blocks", "icp_get_tsdf_hashed", "icp_tsdf_upload_hashed",
            "icp_tsdf_mesh_hashed", "icp_tsdf_raycast_hashed", "icp_set_target_tsdf_hashed", "icp_track_depth_model_hashed",
            "icp_tsdf_evict_blocks", "icp_tsdf_evicted_blocks", "icp_tsdf_insert_blocks", "icp_tsdf_integrate_cloud",
+           "icp_tsdf_cloud_system", "icp_tsdf_align_cloud", "icp_track_scans_sdf",
            "icp_tsdf_create_color_hashed", "icp_tsdf_hashed_has_color", "icp_get_tsdf_color_hashed", "icp_tsdf_upload_color_hashed",
            "icp_tsdf_evicted_blocks_color", "icp_tsdf_insert_blocks_color",
            "icp_tsdf_raycast_color_hashed", "icp_set_target_tsdf_color_hashed", "icp_track_depth_model_color_hashed", "icp_tsdf_mesh_color_hashed",
@@ -1285,6 +1286,57 @@ class Context:
         info = IcpTsdfCloudInfo()
         self._ck(self.lib.icp_tsdf_integrate_cloud(self.h, C.c_int32(w), _ptr(p), _ptr(e), C.byref(info)))
         return _record(info)
+
+    def tsdf_cloud_system(self, which="source", pose=None, huber=0.0):
+        """icp_tsdf_cloud_system: the 28 sums of one direct SDF step of the resident target ("target" / 0) or source ("source" / 1) -- an
+        unorganised cloud in its sensor frame -- at `pose` (4x4 scan frame -> world; None: the identity) against the volume, dense or
+        hashed.  Returns (sums (28,) float64, (considered, valid))."""
+        w = _cloud(which)
+        p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
+        o = sdf_options(huber=huber)
+        sums = np.empty(28, np.float64); cnt = (C.c_int32 * 2)()
+        self._ck(self.lib.icp_tsdf_cloud_system(self.h, C.c_int32(w), _ptr(p), C.byref(o), _ptr(sums), cnt))
+        return sums, (cnt[0], cnt[1])
+
+    def tsdf_align_cloud(self, which="source", pose=None, n_iterations=20, huber=0.0, min_valid=64, stop_rotation=1e-5, stop_translation=1e-5, trace=False):
+        """icp_tsdf_align_cloud: the resident cloud aligned to the volume itself from `pose` (identity by default): no target cloud, no
+        index, no search.  The field exists only inside the truncation band around the fused surfaces: a point that starts further
+        than the truncation from all of them takes no part (the basin).  `tsdf_align_depth`'s returns: (pose, record, status), with trace=True (pose, record,
+        status, the records of the iterations that ran); a failed alignment (status NO_SOURCE or NO_CORRESPONDENCES) returns the pose it
+        started with."""
+        w = _cloud(which)
+        p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
+        o = sdf_options(n_iterations=n_iterations, huber=huber, min_valid=min_valid, stop_rotation=stop_rotation, stop_translation=stop_translation)
+        rec = IcpSdfFrame(); tr = (IcpSdfIter * o.n_iterations)() if trace else None
+        rc = self.lib.icp_tsdf_align_cloud(self.h, C.c_int32(w), C.byref(o), _ptr(p), C.byref(rec), tr)
+        if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # the alignment's outcome: reported in the record
+            self._ck(rc)
+        r = _record(rec)
+        if trace:
+            return pose_from_c(p), r, rc, [_record(tr[i]) for i in range(r["iterations"])]
+        return pose_from_c(p), r, rc
+
+    def track_scans_sdf(self, scans, pose=None, **options):
+        """icp_track_scans_sdf: `scans`, a list of xyz (n, 3) arrays in the sensor frame (a (xyz, normals) pair as `track_scans_vmap`
+        takes it will do, the normals are not used), tracked against the TSDF volume they are fused into: scan 0 fused at `pose`
+        (identity by default), every later scan aligned to the volume built so far (**options: the fields of `sdf_options`) and, when
+        that succeeds, fused at the pose found; a scan that fails is skipped and carries the pose.  Returns (poses: one 4x4 per scan,
+        the records of scans 1 .., the fuse info of every scan -- all zero for a skipped one --, status: the first per-scan error, or 0)."""
+        o = sdf_options(**options)
+        ns = len(scans)
+        pts = [_f32(s[0] if isinstance(s, (tuple, list)) else s) for s in scans]
+        if any(a.ndim != 2 or a.shape[1] != 3 for a in pts):
+            raise ValueError("a scan is xyz (n, 3)")
+        xp = (C.c_void_p * max(ns, 1))(*[_ptr(a) for a in pts])
+        cnt = (C.c_int32 * max(ns, 1))(*[len(a) for a in pts])
+        p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
+        start = pose_from_c(p)
+        out = (IcpSdfFrame * max(ns - 1, 1))(); infos = (IcpTsdfCloudInfo * max(ns, 1))()
+        rc = self.lib.icp_track_scans_sdf(self.h, xp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out, infos)
+        if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-scan outcomes: reported in the records
+            self._ck(rc)
+        recs = [_record(out[i]) for i in range(ns - 1)]
+        return [start] + [r["pose"] for r in recs], recs, [_record(infos[i]) for i in range(ns)], rc
 
     def tsdf_raycast(self, cam, pose):
         """icp_tsdf_raycast: the volume seen from `pose` as an organised cloud in that camera's frame.  Returns (depth (h, w), vertices

@@ -139,6 +139,17 @@ def fuse_scans(ctx, scans, poses, voxel_size=0.05, truncation=None, origin=(0.0,
     (Context.tsdf_sample, Context.tsdf_mesh_hashed, Context.tsdf_blocks)."""
     if len(scans) != len(poses):
         raise ValueError("one pose per scan")
+    _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims)
+    infos = []
+    for s, T in zip(scans, poses):
+        xyz = s[0] if isinstance(s, (tuple, list)) else s
+        ctx.set_source(np.ascontiguousarray(xyz, np.float32))
+        infos.append(ctx.tsdf_integrate_cloud("source", pose=np.asarray(T, np.float32)))
+    return infos
+
+
+def _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims):
+    """The volume fuse_scans and track_tsdf create: hashed, or the dense box of `dims` voxels."""
     if not hashed and dims is None:
         raise ValueError("a dense volume needs dims")
     if hashed and dims is not None:
@@ -149,21 +160,41 @@ def fuse_scans(ctx, scans, poses, voxel_size=0.05, truncation=None, origin=(0.0,
         ctx.tsdf_create_hashed(block_capacity=block_capacity, **opts)
     else:
         ctx.tsdf_create(dims=dims, **opts)
-    infos = []
-    for s, T in zip(scans, poses):
-        xyz = s[0] if isinstance(s, (tuple, list)) else s
-        ctx.set_source(np.ascontiguousarray(xyz, np.float32))
-        infos.append(ctx.tsdf_integrate_cloud("source", pose=np.asarray(T, np.float32)))
-    return infos
+
+
+def track_tsdf(ctx, scans, start_pose, voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, hashed=True, dims=None,
+               **sdf_options):
+    """Tracking of a laser sequence against the TSDF volume the scans are fused into (Context.track_scans_sdf):
+    one model, no voxel map beside it, every scan uploaded once.  `scans` as fuse_scans takes them, `start_pose` the 4x4 pose of scan 0;
+    the volume is created as fuse_scans creates it.  Scan 0 is fused at the start pose; every later scan is aligned to the volume built
+    so far (direct SDF alignment with **sdf_options, the fields of binding.sdf_options) and fused at the pose found; a scan that fails is
+    skipped and carries the pose.  Nothing is carved in front of the surfaces, so the field exists only within `truncation` of them:
+    that band is the basin of convergence, and the part of the motion between two scans that is normal to the surfaces has to stay
+    inside it (the default is 4 voxels; a faster sensor needs a wider truncation or coarser voxels).  Returns (poses: one 4x4 per scan, records:
+    one per scan after the first, infos: the fuse info of every scan, status: the first per-scan error, or 0).  The volume stays in the
+    context (Context.tsdf_sample, Context.tsdf_mesh_hashed, Context.tsdf_blocks)."""
+    _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims)
+    return ctx.track_scans_sdf(scans, np.asarray(start_pose, np.float32), **sdf_options)
 
 
 def reconstruct(ctx, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, min_weight=0.0,
-                mesh_path=None, **track_map_options):
+                mesh_path=None, tracker="map", **track_map_options):
     """A surface from a laser sequence, the laser counterpart of tum.reconstruct_room: the scans tracked against the voxel map
     (`track_map` with **track_map_options; its voxel_size is the MAP's), fused at the tracked poses into a hashed TSDF volume of
     `tsdf_voxel_size` (`fuse_scans`), the zero level set extracted on the device (Context.tsdf_mesh_hashed with `min_weight`) and, with
-    mesh_path, written as a PLY (meshio.write_ply_mesh).  Returns (poses, records, status, (vertices, normals, triangles))."""
+    mesh_path, written as a PLY (meshio.write_ply_mesh).  Returns (poses, records, status, (vertices, normals, triangles)).
+    tracker="sdf": the scans are tracked against the TSDF volume itself (`track_tsdf`; **track_map_options are then the fields of
+    binding.sdf_options) and that same volume is meshed: one model, one upload of every scan, no second fuse."""
     from . import meshio
+    if tracker not in ("map", "sdf"):
+        raise ValueError("tracker must be 'map' or 'sdf'")
+    if tracker == "sdf":
+        poses, records, _, status = track_tsdf(ctx, scans, start_pose, voxel_size=tsdf_voxel_size, truncation=truncation, origin=origin, max_range=max_range,
+                                               block_capacity=block_capacity, **track_map_options)
+        mesh = ctx.tsdf_mesh_hashed(min_weight=min_weight)
+        if mesh_path is not None:
+            meshio.write_ply_mesh(mesh_path, *mesh)
+        return poses, records, status, mesh
     if "keep_radius" in track_map_options and track_map_options["keep_radius"] is not None:
         raise ValueError("reconstruct tracks against the whole map (keep_radius is not supported)")
     poses, records, status = track_map(ctx, scans, start_pose, **track_map_options)

@@ -1520,6 +1520,49 @@ static_assert(sizeof(icp_tsdf_cloud_info) == 32, "icp_tsdf_cloud_info");
 #endif
 int icp_tsdf_integrate_cloud(icp_ctx* ctx, int32_t which, const float pose[16], const float sensor_origin[3], icp_tsdf_cloud_info* info_out);
 
+/* -------- a laser scan aligned to the TSDF volume itself, and tracked against it --------
+ * Direct SDF tracking (icp_tsdf_align_depth above) for a RESIDENT cloud, unorganised, in icp_voxel_map_insert's and
+ * icp_tsdf_integrate_cloud's convention (which = 0: the target, 1: the source): every point of the scan, moved into the world by the pose,
+ * reads its residual and its normal from the eight voxels around it.  No ray-cast, no target cloud, no index, no search, and no second
+ * model beside the volume the scans are fused into.  The volume is whichever the context holds, dense or hashed.  icp_sdf_options is
+ * reused: huber, n_iterations, min_valid, stop_rotation and stop_translation mean what they mean for a depth frame; stride must be 1 and is
+ * refused otherwise (the order of the resident cloud is internal, so "every s-th point" could not be restated).
+ * icp_tsdf_integrate_cloud carves no free space, so the field exists only inside the truncation band around the fused surfaces: a point
+ * further than the truncation from every surface of the model finds no valid cell and takes no part.  The band is the basin of
+ * convergence: only the points that start inside it pull the scan, so the part of the motion between two scans that is normal to the
+ * surfaces has to stay inside the truncation for enough of them.
+ *
+ * Contract (fp32, one rounding per operation, in the order written; everything after the conversion to fp64 is fp64;
+ * tests/sdf_cloud_restatement.py restates it in numpy).  P = pose (scan frame -> world, column-major, P_rc = pose[4 c + r]).
+ *   Considered: a point (x, y, z) is CONSIDERED iff all three coordinates are finite; n_depth counts the considered points.
+ *   Field sample: q_r = (P_r0 x + (P_r1 y + P_r2 z)) + P_r3 -- the depth form's expression with the point's z in place of d.  The cell of
+ *   q, its validity, F and the gradient (G_x, G_y, G_z) are icp_tsdf_sample's.
+ *   Valid: a point is VALID iff it is considered, its cell is valid and fabsf(F) < 1; n_valid counts the valid points.  There is no
+ *   max_depth test: a point has a position, not a range.
+ *   Terms, sums, step, stop and failure are the depth form's, word for word: r, g, J and w as there, 28 fp64 sums folded in a fixed order
+ *   without floating-point atomics, bitwise reproducible run to run, each within n_valid 2^-52 sum |term| of any other summation order;
+ *   the step fails with n_valid < min_valid or a non-finite solution.  An alignment FAILS with no considered point (ICP_ERR_NO_SOURCE) or
+ *   a failed step (ICP_ERR_NO_CORRESPONDENCES): it carries the pose it started with.
+ *   Order independence: the sums do not depend on the order in which the cloud was uploaded, except by what a summation order may change.
+ * Checks come first, without a device and without side effects: ICP_ERR_INVALID_ARG (no volume; which not 0 or 1; a null or non-finite
+ * pose; bad options, stride != 1 among them; a null output; n_scans < 1; a null or empty scan) or ICP_ERR_NO_TARGET / ICP_ERR_NO_SOURCE
+ * (no such cloud), with a message that names the call.  A refused call leaves the volume bit for bit as it was. */
+/* The sums of ONE step at `pose`: sums_out 28 doubles, counts_out {n_depth, n_valid}; of opt only huber matters (stride must be 1). */
+int icp_tsdf_cloud_system(icp_ctx* ctx, int32_t which, const float pose[16], const icp_sdf_options* opt, double* sums_out, int32_t* counts_out);
+/* Aligns the resident cloud to the volume from pose_inout.  rec_out (optional): the record; trace_out: NULL, or n_iterations records, those
+ * past the last step tried zeroed.  Returns the alignment's status; a failed one leaves pose_inout as it was.  One host read. */
+int icp_tsdf_align_cloud(icp_ctx* ctx, int32_t which, const icp_sdf_options* opt, float pose_inout[16], icp_sdf_frame* rec_out,
+                         icp_sdf_iter* trace_out);
+/* Tracking against the model being built: every scan (xyz[k]: n[k] x 3 floats, in its sensor frame) becomes the resident source by
+ * icp_track_scans_vmap's upload path.  Scan 0 is fused at pose_inout by icp_tsdf_integrate_cloud's rule (sensor origin: the scan frame's
+ * origin); scan k >= 1 is aligned to the volume built so far and, on ICP_OK, fused at the pose found (out[k - 1] its record; out:
+ * n_scans - 1 records).  A scan that fails carries the pose, is not fused, records its status, and tracking goes on; the first error in
+ * scan order is returned.  infos_out: NULL, or n_scans infos of the fuses, a skipped scan's zeroed.  The host waits once per scan for the
+ * record, and as often as icp_tsdf_integrate_cloud does for the fuse.  An error of a fuse (a hashed volume that would have to grow beyond
+ * its limit) ends the call. */
+int icp_track_scans_sdf(icp_ctx* ctx, const float* const* xyz, const int32_t* n, int32_t n_scans, const icp_sdf_options* opt,
+                        float pose_inout[16], icp_sdf_frame* out, icp_tsdf_cloud_info* infos_out);
+
 /* -------- batches of independent scan pairs: the loop over ETH indices, main.cpp:411-498 / experiment.cpp:319-396 --------
  * The reference aligns the pairs one after the other and carries no state between them, so a batch shards with no
  * data-path exchange: pair p belongs to rank p % n_ranks (icp_pair_owner), and the only collective is ONE gather of the
