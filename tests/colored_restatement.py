@@ -40,22 +40,26 @@ def _unit(v, recip=False):
     return u, ok
 
 
-def gradients(pts, nrm, rgba, k):
+def gradients(pts, nrm, rgba, k, nb=None, full=False):
     """Colour gradients (n, 3) fp32 of the target (NaN: non-finite point or normal, zero normal; 0: fewer than 3 neighbours or a
-    determinant at or below the threshold), and det / threshold per point (NaN where no system was solved)."""
+    determinant at or below the threshold), and det / threshold per point (NaN where no system was solved).  nb: G.neighbours(pts, k)
+    when the caller has it; full: as a third result the gradients solved without the threshold (fp32; NaN where det <= 0 or no system
+    was solved) -- what a kernel whose determinant lands on the other side of the threshold returns."""
     pts = np.ascontiguousarray(pts, f32)
     n = len(pts)
     nu, nok = _unit(nrm)
     I = intensity(rgba)
     out = np.full((n, 3), np.nan, f32)
     margin = np.full(n, np.nan)
+    solved = np.full((n, 3), np.nan, f32)
     live = np.isfinite(pts).all(1) & nok
     out[live] = 0.0
-    nb = G.neighbours(pts, k)
+    if nb is None:
+        nb = G.neighbours(pts, k)
     m = nb.shape[1]
     use = live & (nb >= 0).all(1) if m >= 3 else np.zeros(n, bool)
     if not use.any():
-        return out, margin
+        return (out, margin, solved) if full else (out, margin)
     ids = np.nonzero(use)[0]
     P = pts[ids].astype(np.float64); N = nu[ids]
     Q = pts[nb[ids]].astype(np.float64)                              # (u, m, 3)
@@ -77,7 +81,11 @@ def gradients(pts, nrm, rgba, k):
     out[ids] = x.astype(f32)
     with np.errstate(divide="ignore", invalid="ignore"):
         margin[ids] = det / thr
-    return out, margin
+    pos = det > 0
+    free = np.full((len(ids), 3), np.nan)
+    free[pos] = np.einsum("uij,uj->ui", adj[pos], Ab[pos]) / det[pos, None]
+    solved[ids] = free.astype(f32)
+    return (out, margin, solved) if full else (out, margin)
 
 
 def pair_terms(p, q, n, d, di, w, lam):

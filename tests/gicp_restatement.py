@@ -54,15 +54,17 @@ def neighbours(pts, k):
     return out
 
 
-def normals(pts, k):
-    """GICP normals (n, 3) fp32 and the ascending eigenvalues (n, 3) fp64 of every point's neighbourhood covariance (NaN where undefined)."""
+def normals(pts, k, nb=None, cov=False):
+    """GICP normals (n, 3) fp32 and the ascending eigenvalues (n, 3) fp64 of every point's neighbourhood covariance (NaN where undefined).
+    nb: neighbours(pts, k) when the caller has it; cov: the fp64 covariances (n, 3, 3) as a third result."""
     pts = np.ascontiguousarray(pts, f32)
-    nb = neighbours(pts, k)
+    if nb is None:
+        nb = neighbours(pts, k)
     n = len(pts)
-    nrm = np.full((n, 3), np.nan, f32); ev = np.full((n, 3), np.nan)
+    nrm = np.full((n, 3), np.nan, f32); ev = np.full((n, 3), np.nan); covs = np.full((n, 3, 3), np.nan)
     ok = (nb >= 0).all(1) & (nb.shape[1] >= 3)
     if not ok.any():
-        return nrm, ev
+        return (nrm, ev, covs) if cov else (nrm, ev)
     X = pts[nb[ok]].astype(np.float64)                       # (m, k, 3)
     D = X - X.mean(1, keepdims=True)
     C = np.einsum("mki,mkj->mij", D, D) / X.shape[1]
@@ -71,8 +73,8 @@ def normals(pts, k):
     zero = ~(np.abs(C).reshape(len(C), 9) > 0).any(1)         # coincident neighbours: Jacobi's first axis
     v[zero] = (1.0, 0.0, 0.0)
     nrm[ok] = (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(f32)
-    ev[ok] = w
-    return nrm, ev
+    ev[ok] = w; covs[ok] = C
+    return (nrm, ev, covs) if cov else (nrm, ev)
 
 
 def plane_cov(n, eps):

@@ -210,6 +210,115 @@ def check_normals(orc, pts, k, vp, nrm, curv, label=""):
     return stats
 
 
+GICP_EPS = 1e-3        # the epsilon the GICP tests run with, and the one the sign-free measure plane_cov is taken at
+GICP_GAP = 1e-3        # (l1 - l0) / l2 below which a neighbourhood's normal is not unique enough to compare directions
+GRAD_NEAR = (0.5, 2.0)                 # det / threshold: within 2x of the threshold either side is right
+GRAD_BAND = (1e-2, 1e4)                # det / threshold: the fp64 adjugate's determinant differs from numpy's by up to 2.2e-4 / (det / threshold)
+GRAD_SHARE_CAP = 0.02
+
+
+def check_gicp_normals(dev, pts, k, label, ref=None):
+    """Asserts the device's GICP normals against gicp_restatement on EVERY finite point; returns the statistics.
+      * the NaN patterns are identical, and | |n| - 1 | <= 1e-6 on every finite point;
+      * where the reference neighbourhood has a usable eigen-gap ((l1 - l0) / l2 >= GICP_GAP) or no extent at all:
+        |plane_cov(dev) - plane_cov(ref)| <= 1e-5 (sign-free); coincident neighbours give exactly (1, 0, 0);
+      * where it has none (collinear or isotropic neighbours, the direction is not unique): the Rayleigh quotient
+        n_dev^T C n_dev / |n_dev|^2 <= l0 + 1e-9 lmax with C the fp64 covariance of the restatement's neighbour set.
+    ref: (normals, eigenvalues, covariances) of gicp_restatement.normals(pts, k, cov=True) when the caller has them."""
+    import gicp_restatement as G
+    rn, ev, cov = G.normals(pts, k, cov=True) if ref is None else ref
+    assert dev.shape == rn.shape
+    assert np.array_equal(np.isnan(dev), np.isnan(rn)), "%s k=%d: NaN pattern" % (label, k)
+    fin = np.nonzero(~np.isnan(rn).any(1))[0]
+    n_finite = int(np.isfinite(np.asarray(pts, f32)).all(1).sum())
+    assert len(fin) == (n_finite if n_finite >= 3 else 0), "%s k=%d: %d normals for %d finite points" % (label, k, len(fin), n_finite)
+    st = dict(label=label, k=k, n=len(rn), fin=len(fin), gapped=0, ungapped=0, coincident=0, worst_cov=0.0, worst_rayleigh=0.0, worst_len=0.0)
+    if len(fin) == 0:
+        return st
+    nd = dev[fin].astype(np.float64)
+    ln = np.abs(np.linalg.norm(nd, axis=1) - 1)
+    st["worst_len"] = float(ln.max())
+    assert ln.max() <= 1e-6, "%s k=%d: | |n| - 1 | = %.3g at point %d" % (label, k, ln.max(), fin[int(np.argmax(ln))])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        gap = (ev[fin, 1] - ev[fin, 0]) / ev[fin, 2]
+    flat = ~(np.abs(cov[fin]).reshape(len(fin), 9) > 0).any(1)
+    gapped = (gap >= GICP_GAP) | (ev[fin, 2] == 0) | flat
+    use = fin[gapped]
+    if len(use):
+        err = np.abs(G.plane_cov(dev[use], GICP_EPS) - G.plane_cov(rn[use], GICP_EPS)).reshape(len(use), 9).max(1)
+        r = int(np.argmax(err))
+        st["worst_cov"] = float(err[r])
+        assert err[r] <= 1e-5, "%s k=%d: point %d dev %s ref %s eig %s" % (label, k, use[r], dev[use[r]], rn[use[r]], ev[use[r]])
+    co = fin[flat]
+    assert np.array_equal(dev[co], np.tile(f32([1, 0, 0]), (len(co), 1))), "%s k=%d: coincident neighbours" % (label, k)
+    rest = fin[~gapped]
+    if len(rest):
+        n = dev[rest].astype(np.float64)
+        n /= np.linalg.norm(n, axis=1, keepdims=True)         # the Rayleigh quotient: an fp32 normal's |n|^2 is off 1 by up to 1.2e-7, more than
+        q = np.einsum("ni,nij,nj->n", n, cov[rest], n)        # the 1e-9 allows once l0 is of lmax's size (an isotropic neighbourhood); |n| is checked above
+        over = (q - ev[rest, 0]) / ev[rest, 2]
+        r = int(np.argmax(over))
+        st["worst_rayleigh"] = float(over[r])
+        assert over[r] <= 1e-9, "%s k=%d: n^T C n above l0 by %.3g lmax at point %d, dev %s eig %s" % (label, k, over[r], rest[r], dev[rest[r]], ev[rest[r]])
+    st.update(gapped=len(use), ungapped=len(rest), coincident=len(co))
+    assert st["gapped"] + st["ungapped"] == st["fin"], st                     # every finite point was checked by one rule or the other
+    return st
+
+
+def check_color_gradients(dev, pts, nrm, rgba, k, label, ref=None, crafted=False):
+    """Asserts the device's colour gradients against colored_restatement on every point; returns the statistics.
+    On a natural cloud (crafted=False): the points with det / threshold inside GRAD_NEAR are left out, at most GRAD_SHARE_CAP of the
+    cloud; on all others the NaN and zero patterns are identical and |dev - ref| <= 1e-5 max(1, |ref|).
+    On a crafted cloud: no point is left out.  The NaN pattern is identical everywhere; the zero pattern wherever det / threshold is
+    outside GRAD_NEAR; |dev - ref| <= 1e-5 max(1, |ref|) wherever det / threshold >= 1e4; a point inside GRAD_BAND is allowed
+    1e-5 max(1, 1e4 / (det / threshold)) max(1, |ref|) and, inside GRAD_NEAR, either exactly zero or that far from the gradient solved
+    without the threshold; the points inside GRAD_BAND are at most GRAD_SHARE_CAP of the cloud.
+    ref: (gradients, det / threshold, gradients solved without the threshold) of colored_restatement.gradients(..., full=True)."""
+    import colored_restatement as CR
+    rg, margin, solved = CR.gradients(pts, nrm, rgba, k, full=True) if ref is None else ref
+    assert dev.shape == rg.shape
+    n = len(rg)
+    with np.errstate(invalid="ignore"):
+        near = (margin > GRAD_NEAR[0]) & (margin < GRAD_NEAR[1])
+        band = (margin > GRAD_BAND[0]) & (margin < GRAD_BAND[1])
+    far = ~near
+    st = dict(label=label, k=k, n=n, near=int(near.sum()), band=int(band.sum()), checked=0, worst=0.0, worst_band=0.0)
+    if crafted:
+        assert np.array_equal(np.isnan(dev), np.isnan(rg)), "%s k=%d: NaN pattern" % (label, k)
+        assert band.sum() <= GRAD_SHARE_CAP * n, "%s k=%d: %d of %d points in the threshold band" % (label, k, band.sum(), n)
+    else:
+        assert np.array_equal(np.isnan(dev[far]), np.isnan(rg[far])), "%s k=%d: NaN pattern" % (label, k)
+        assert near.sum() <= GRAD_SHARE_CAP * n, "%s k=%d: %d of %d points within 2x of the threshold" % (label, k, near.sum(), n)
+    live = ~np.isnan(rg).any(1)
+    fin = far & live
+    # the zero of the threshold is (0, 0, 0).  A crafted cloud can make ONE component of a solved gradient vanish exactly in one arithmetic and
+    # not in the other (a lattice whose gradient is perpendicular to an axis), so there the pattern is taken per point; the natural clouds
+    # keep the per-component comparison they always had.
+    zd, zr = ((dev[fin] == 0).all(1), (rg[fin] == 0).all(1)) if crafted else ((dev[fin] == 0), (rg[fin] == 0))
+    assert np.array_equal(zd, zr), "%s k=%d: zero pattern at %s" % (label, k, np.nonzero(fin)[0][(zd != zr).reshape(len(zd), -1).any(1)][:5])
+    err = np.abs(dev.astype(np.float64) - rg) / np.maximum(1.0, np.abs(rg.astype(np.float64)))
+    tight = fin & ~band if crafted else fin
+    st["checked"] = int(tight.sum())
+    if tight.any():
+        st["worst"] = float(err[tight].max())
+        assert st["worst"] <= 1e-5, (label, k, st["worst"], int(np.nonzero(tight)[0][np.argmax(err[tight].max(1))]))
+    if crafted and band.any():
+        with np.errstate(invalid="ignore", divide="ignore"):
+            tol = 1e-5 * np.maximum(1.0, 1e4 / margin)
+        b = band & far & live
+        if b.any():
+            rel = err[b].max(1) / tol[b]
+            st["worst_band"] = float(rel.max())
+            assert rel.max() <= 1.0, "%s k=%d: band point %d off by %.3g of its tolerance" % (label, k, np.nonzero(b)[0][int(np.argmax(rel))], rel.max())
+        for i in np.nonzero(near & live)[0]:
+            if (dev[i] == 0).all():
+                continue
+            e = np.abs(dev[i].astype(np.float64) - solved[i]) / np.maximum(1.0, np.abs(solved[i].astype(np.float64)))
+            assert e.max() <= tol[i], "%s k=%d: point %d at det / threshold %.3g is neither zero nor the solved gradient: %s, %s" % (label, k, i, margin[i], dev[i], solved[i])
+        st["checked"] += int((band & live).sum())
+    return st
+
+
 def assert_matches_icp_run(c, starts, max_stats=512):
     """Every start of ONE multistart call against icp_run from that start on the same context: records and pose, bit for bit."""
     res, stats, best = c.run_multistart(starts, max_stats=max_stats)

@@ -13,11 +13,11 @@ from support import load
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-EPS = 1e-3
-GAP = 1e-3
+EPS = S.GICP_EPS
 
 
 configure = functools.partial(S.configure, metric=3)          # this file's default metric: GICP
+check_normals = S.check_gicp_normals                          # every finite point, none skipped
 
 
 @pytest.fixture(scope="module")
@@ -32,34 +32,23 @@ def eth_pair():
     return synth.eth_like_pair(0)
 
 
-def check_normals(dev, pts, k, label):
-    ref, ev = G.normals(pts, k)
-    nan_d, nan_r = np.isnan(dev).any(1), np.isnan(ref).any(1)
-    assert np.array_equal(np.isnan(dev), np.isnan(ref)), "%s k=%d: NaN pattern" % (label, k)
-    fin = np.nonzero(~nan_r)[0]
-    with np.errstate(invalid="ignore", divide="ignore"):
-        gap = (ev[fin, 1] - ev[fin, 0]) / ev[fin, 2]
-    use = fin[(gap >= GAP) | (ev[fin, 2] == 0)]
-    err = np.abs(G.plane_cov(dev[use], EPS) - G.plane_cov(ref[use], EPS)).reshape(len(use), 9).max(1)
-    r = int(np.argmax(err)) if len(use) else 0
-    assert len(use) == 0 or err[r] <= 1e-5, "%s k=%d: point %d dev %s ref %s eig %s" % (label, k, use[r], dev[use[r]], ref[use[r]], ev[use[r]])
-    assert np.abs(np.linalg.norm(dev[fin].astype(np.float64), axis=1) - 1).max() < 1e-6
-    return len(use), len(fin)
-
-
 @pytest.mark.parametrize("k", [5, 10, 20])
 def test_normals_every_point(gpu_ctx_factory, bunny, depth_pair, eth_pair, k):
     ctx = gpu_ctx_factory()
     ctx.set_gicp_options(EPS, k)
     for label, pts, nrm in (("bunny", bunny["tgt_pts"], bunny["tgt_nrm"]), ("depth/8", depth_pair["tgt_pts"], depth_pair["tgt_nrm"]),
                             ("eth 50k", eth_pair["tgt_pts"][:50000], eth_pair["tgt_nrm"][:50000])):
+        ref = G.normals(pts, k, cov=True)
+        n_finite = int(np.isfinite(pts).all(1).sum())
         for knn_backend in (1, 0):                        # the target's own tree / a scratch tree
             configure(ctx, knn_backend=knn_backend)
             ctx.set_target(pts, nrm)
-            used, fin = check_normals(ctx.gicp_normals("target"), pts, k, label + " target")
-            assert used > 0
+            st = check_normals(ctx.gicp_normals("target"), pts, k, label + " target", ref)
+            assert st["gapped"] > 0 and st["gapped"] + st["ungapped"] == n_finite
         ctx.set_source(pts, nrm)
-        check_normals(ctx.gicp_normals("source"), pts, k, label + " source")
+        st = check_normals(ctx.gicp_normals("source"), pts, k, label + " source", ref)
+        assert st["gapped"] > 0 and st["gapped"] + st["ungapped"] == n_finite
+        print("gicp normals %s k=%d: %s" % (label, k, st))
     # a replaced cloud drops the cache; k = 0 gives the cloud's own normals
     ctx.set_target(bunny["src_pts"], bunny["src_nrm"])
     check_normals(ctx.gicp_normals("target"), bunny["src_pts"], k, "replaced target")
