@@ -89,6 +89,7 @@ int icp_track_scans_sdf(icp_ctx* c, const float* const* xyz, const int32_t* n, i
     if (n_scans > 1 && !out) { c->err = std::string(who) + ": null output (out: n_scans - 1 records)"; return ICP_ERR_INVALID_ARG; }
     if (n_scans < 1 || !xyz || !n) { c->err = std::string(who) + ": bad argument (n_scans >= 1, xyz, n)"; return ICP_ERR_INVALID_ARG; }
     for (int k = 0; k < n_scans; k++) if (!xyz[k] || n[k] <= 0) { c->err = std::string(who) + ": a scan has null points or n <= 0"; return ICP_ERR_INVALID_ARG; }
+    { int J; if ((rc = tsdf_carve_steps(c, who, &J))) return rc; }      // (the fuses' carving: refused before any scan is uploaded)
     if (infos_out) memset(infos_out, 0, (size_t)n_scans * sizeof(icp_tsdf_cloud_info));
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;

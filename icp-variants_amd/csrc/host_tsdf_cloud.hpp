@@ -1,5 +1,7 @@
 // host_tsdf_cloud.hpp -- icp_tsdf_integrate_cloud: a resident cloud (a laser scan in its sensor frame) fused into the context's TSDF
 // volume, dense or hashed, as one observation.  Kernels: dev_tsdf_cloud.hpp; the room rule of the hashed touch: host_tsdf_hash.hpp.
+// Free-space carving (icp_set_tsdf_carve_options; kernels: dev_tsdf_carve.hpp) replaces the accumulate launch of
+// every cloud fuse while it is on, and nothing else.
 // Contract: include/icp_hip.h, DESIGN.md section 6ze.  Part of icp_hip.hip (included from there, after host_tsdf_hash_evict.hpp).
 namespace {
 // the voxels the accumulators have to cover: every voxel of the pool, or of the box
@@ -17,6 +19,25 @@ int tsdf_cloud_scratch(icp_ctx* c) {
     return ICP_OK;
 }
 struct TcCall { TcCloud cl; TsdfMat P; float e[3]; TcGrid g; };
+constexpr int TCV_MAX_STEPS = 65536;
+const char* tsdf_carve_options_error(const icp_tsdf_carve_options* o) {
+    if (!o) return "null options";
+    if (!(o->distance >= 0.f)) return "distance must be 0 (off), positive or +inf";
+    if (!(o->min_range >= 0.f) || !std::isfinite(o->min_range)) return "min_range must be finite and >= 0";
+    return nullptr;
+}
+// J of a cloud fuse with the context's carve options on its volume: 0 = off; beyond the cap the call is refused (no device work yet).
+int tsdf_carve_steps(icp_ctx* c, const char* who, int* J) {
+    *J = 0;
+    if (!(c->tcv_opt.distance > 0.f)) return ICP_OK;
+    const double j = std::ceil(std::min((double)c->tcv_opt.distance, (double)c->tsdf_opt.max_depth) / (double)c->tsdf_opt.voxel_size);
+    if (!(j <= (double)TCV_MAX_STEPS)) {
+        c->err = std::string(who) + ": carving would walk more than 65536 steps per ray (min(distance, max_depth) / voxel_size; icp_set_tsdf_carve_options)";
+        return ICP_ERR_INVALID_ARG;
+    }
+    *J = (int)j;
+    return ICP_OK;
+}
 TcCall tsdf_cloud_call(const icp_ctx* c, const Cloud& cl, const float pose[16], const float* e) {
     const icp_tsdf_options& o = c->tsdf_opt;
     TcCall k;
@@ -39,6 +60,18 @@ void tsdf_cloud_accumulate_launch(icp_ctx* c, const TcCall& k) {
     if (c->tsdf_hashed) hipLaunchKernelGGL(k_htsdf_accumulate_cloud, grid, dim3(256), 0, c->stream, htsdf_view(c), k.cl, k.P, k.e[0], k.e[1], k.e[2], k.g, S, N, ctr);
     else hipLaunchKernelGGL(k_tsdf_accumulate_cloud, grid, dim3(256), 0, c->stream, c->tsdf_opt.dims[0], c->tsdf_opt.dims[1], c->tsdf_opt.dims[2], k.cl, k.P, k.e[0], k.e[1],
                             k.e[2], k.g, S, N, ctr);
+}
+// The accumulate with the walk started J steps in front of the band.
+void tsdf_carve_launch(icp_ctx* c, const TcCall& k, int J) {
+    const size_t v = tsdf_cloud_voxels(c);
+    unsigned long long* S = c->tc_acc.as<unsigned long long>();
+    int* N = (int*)(c->tc_acc.as<char>() + v * 8);
+    unsigned long long* ctr = c->tc_ctr.as<unsigned long long>();
+    const dim3 grid((k.cl.n + 255) / 256);
+    const TcCarve cv = {J, c->tcv_opt.min_range};
+    if (c->tsdf_hashed) hipLaunchKernelGGL(k_htsdf_carve_cloud, grid, dim3(256), 0, c->stream, htsdf_view(c), k.cl, k.P, k.e[0], k.e[1], k.e[2], k.g, cv, S, N, ctr);
+    else hipLaunchKernelGGL(k_tsdf_carve_cloud, grid, dim3(256), 0, c->stream, c->tsdf_opt.dims[0], c->tsdf_opt.dims[1], c->tsdf_opt.dims[2], k.cl, k.P, k.e[0], k.e[1],
+                            k.e[2], k.g, cv, S, N, ctr);
 }
 void tsdf_cloud_fold_launch(icp_ctx* c) {
     const size_t v = tsdf_cloud_voxels(c);
@@ -65,23 +98,26 @@ int tsdf_cloud_check(icp_ctx* c, int32_t which, const float* pose, const float* 
         return which ? ICP_ERR_NO_SOURCE : ICP_ERR_NO_TARGET;
     }
     *cl_out = &cl;
-    return ICP_OK;
+    int J;
+    return tsdf_carve_steps(c, who, &J);
 }
 // The call behind its checks.  ms (icp_debug_tsdf_cloud_time): after the call, ONE more touch, accumulate and fold launch, each between
-// events -- the scan is then fused a second time.
+// events -- the scan is then fused a second time.  With carving on (J > 0) the accumulate launch is the carving one, and the fifth
+// counter, read with the other four, is the call's n_carved.
 int tsdf_cloud_run(icp_ctx* c, const Cloud& cl, const float pose[16], const float* e, icp_tsdf_cloud_info* info_out, const char* who, float* ms) {
-    int rc;
+    int rc, J;
+    if ((rc = tsdf_carve_steps(c, who, &J))) return rc;
     const TcCall k = tsdf_cloud_call(c, cl, pose, e);
-    if ((rc = ensure(c, c->tc_ctr, TC_NCTR * 8))) return rc;
+    if ((rc = ensure(c, c->tc_ctr, TCV_NCTR * 8))) return rc;
     if (c->tsdf_hashed) {
         auto touch = [&]() { tsdf_cloud_touch_launch(c, k); return (int)ICP_OK; };
         if ((rc = htsdf_claim(c, touch, who, nullptr))) return rc;      // (a refusal leaves the volume as it was: nothing below has run)
     }
     if ((rc = tsdf_cloud_scratch(c))) return rc;
     const size_t v = c->tc_voxels;
-    unsigned long long h[TC_NCTR];
+    unsigned long long h[TCV_NCTR];
     for (int pass = 0; pass < (ms ? 2 : 1); pass++) {
-        HIPCK(c, hipMemsetAsync(c->tc_ctr.p, 0, TC_NCTR * 8, c->stream));
+        HIPCK(c, hipMemsetAsync(c->tc_ctr.p, 0, TCV_NCTR * 8, c->stream));
         c->tc_voxels = 0;                              // (until the fold has zeroed what the accumulate writes)
         if (pass == 1) {
             if ((rc = ensure_events(c, 4))) return rc;
@@ -89,14 +125,16 @@ int tsdf_cloud_run(icp_ctx* c, const Cloud& cl, const float pose[16], const floa
             if (c->tsdf_hashed) tsdf_cloud_touch_launch(c, k);
             HIPCK(c, hipEventRecord(c->events[1], c->stream));
         }
-        tsdf_cloud_accumulate_launch(c, k);
+        if (J > 0) tsdf_carve_launch(c, k, J);
+        else tsdf_cloud_accumulate_launch(c, k);
         if (pass == 1) HIPCK(c, hipEventRecord(c->events[2], c->stream));
         tsdf_cloud_fold_launch(c);
         if (pass == 1) HIPCK(c, hipEventRecord(c->events[3], c->stream));
         HIPCK(c, hipGetLastError());
-        if ((rc = read_count(c, c->tc_ctr.p, (int*)h, TC_NCTR * 2))) return rc;      // (waits)
+        if ((rc = read_count(c, c->tc_ctr.p, (int*)h, TCV_NCTR * 2))) return rc;      // (waits)
         c->tc_voxels = v;
         if (c->tsdf_hashed) c->th_oor += (long long)h[TC_OUTSIDE];
+        c->tcv_info.n_steps = J; c->tcv_info.n_carved = (int64_t)h[TC_CARVED]; c->tcv_info.n_carved_total += (int64_t)h[TC_CARVED];
     }
     if (ms) {
         for (int q = 0; q < 3; q++) HIPCK(c, hipEventElapsedTime(ms + q, c->events[q], c->events[q + 1]));
@@ -137,4 +175,31 @@ extern "C" int icp_debug_tsdf_cloud_time(icp_ctx* c, int32_t which, const float 
     if ((rc = set_device(c))) return rc;
     if ((rc = tsdf_cloud_run(c, *cl, pose, sensor_origin, nullptr, who, ms_out))) return rc;
     return guard.done();
+}
+
+// ---- free-space carving of the cloud fuses (contract: include/icp_hip.h) ----
+int icp_tsdf_carve_options_default(icp_tsdf_carve_options* o) {
+    if (!o) return ICP_ERR_INVALID_ARG;
+    o->distance = 0.f; o->min_range = 0.f;
+    return ICP_OK;
+}
+int icp_tsdf_carve_options_check(const icp_tsdf_carve_options* o) { return tsdf_carve_options_error(o) ? ICP_ERR_INVALID_ARG : ICP_OK; }
+int icp_set_tsdf_carve_options(icp_ctx* c, const icp_tsdf_carve_options* o) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    icp_tsdf_carve_options v;
+    if (o) v = *o; else icp_tsdf_carve_options_default(&v);
+    if (const char* why = tsdf_carve_options_error(&v)) { c->err = std::string("icp_set_tsdf_carve_options: ") + why; return ICP_ERR_INVALID_ARG; }
+    c->tcv_opt = v;
+    c->tcv_info = icp_tsdf_carve_info{0, 0, 0, 0};
+    return ICP_OK;
+}
+int icp_get_tsdf_carve_options(const icp_ctx* c, icp_tsdf_carve_options* o) { if (!c || !o) return ICP_ERR_INVALID_ARG; *o = c->tcv_opt; return ICP_OK; }
+int icp_tsdf_carve_stats(const icp_ctx* c, icp_tsdf_carve_info* out) { if (!c || !out) return ICP_ERR_INVALID_ARG; *out = c->tcv_info; return ICP_OK; }
+
+// Not part of icp_hip.h (tools/time_tsdf_carve.py): icp_debug_tsdf_cloud_time, which times the carving accumulate as its ONE accumulate
+// launch while carving is on -- and is refused here while it is off, so that a timing named for carving cannot be the plain launch's.
+extern "C" int icp_debug_tsdf_carve_time(icp_ctx* c, int32_t which, const float pose[16], const float sensor_origin[3], float* ms_out) {
+    if (!c || !ms_out) return ICP_ERR_INVALID_ARG;
+    if (!(c->tcv_opt.distance > 0.f)) { c->err = "icp_debug_tsdf_carve_time: carving is off"; return ICP_ERR_INVALID_ARG; }
+    return icp_debug_tsdf_cloud_time(c, which, pose, sensor_origin, ms_out);
 }

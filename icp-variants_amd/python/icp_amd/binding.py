@@ -105,6 +105,14 @@ class IcpTsdfCloudInfo(C.Structure):
                 ("n_outside", C.c_int64)]
 
 
+class IcpTsdfCarveOptions(C.Structure):
+    _fields_ = [("distance", C.c_float), ("min_range", C.c_float)]
+
+
+class IcpTsdfCarveInfo(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("reserved", C.c_int32), ("n_carved", C.c_int64), ("n_carved_total", C.c_int64)]
+
+
 class IcpTsdfStreamInfo(C.Structure):
     _fields_ = [("n_evicted", C.c_int32), ("n_blocks", C.c_int32), ("n_moved", C.c_int32), ("capacity", C.c_int32), ("n_held", C.c_int32),
                 ("n_inserted", C.c_int32), ("n_present", C.c_int32), ("n_grown", C.c_int32)]
@@ -304,6 +312,23 @@ class depth_filter_scope:
 
     def __exit__(self, *exc):
         self.ctx.set_depth_filter(self.old.radius, self.old.sigma_space, self.old.sigma_range)
+        return False
+
+
+class tsdf_carve_scope:
+    """The runners' `carve=` argument: the context's carve options set from a dict of `Context.set_tsdf_carve` arguments inside the
+    `with` block, the previous setting put back behind it."""
+
+    def __init__(self, ctx, carve):
+        self.ctx, self.new = ctx, dict(carve)
+
+    def __enter__(self):
+        self.old = self.ctx.tsdf_carve_options()
+        self.ctx.set_tsdf_carve(**self.new)
+        return self.ctx
+
+    def __exit__(self, *exc):
+        self.ctx.set_tsdf_carve(self.old.distance, self.old.min_range)
         return False
 
 
@@ -521,6 +546,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_track_depth_sdf_color",
            "icp_depth_filter_options_default", "icp_depth_filter_options_check", "icp_set_depth_filter_options", "icp_get_depth_filter_options",
            "icp_depth_filter_tables", "icp_filter_depth",
+           "icp_tsdf_carve_options_default", "icp_tsdf_carve_options_check", "icp_set_tsdf_carve_options", "icp_get_tsdf_carve_options", "icp_tsdf_carve_stats",
            "icp_vgicp_options_default", "icp_vgicp_options_check", "icp_voxelize_target", "icp_get_voxel_grid", "icp_vgicp_system", "icp_vgicp_align",
            "icp_voxel_map_options_check", "icp_voxel_map_create", "icp_voxel_map_destroy", "icp_voxel_map_insert", "icp_get_voxel_map", "icp_voxel_map_upload",
            "icp_voxel_map_system", "icp_voxel_map_align", "icp_track_scans_vmap",
@@ -1286,6 +1312,27 @@ class Context:
         info = IcpTsdfCloudInfo()
         self._ck(self.lib.icp_tsdf_integrate_cloud(self.h, C.c_int32(w), _ptr(p), _ptr(e), C.byref(info)))
         return _record(info)
+
+    def set_tsdf_carve(self, distance=0.0, min_range=0.0):
+        """icp_set_tsdf_carve_options: free space carved by every cloud fuse (`tsdf_integrate_cloud`, the fuses of `track_scans_sdf`;
+        DESIGN.md section 6zg): the voxels up to `distance` metres in front of each return's band (inf: back to the sensor) are observed
+        as free wherever the volume has storage; carve samples nearer to the sensor than `min_range` are skipped.  distance=0 (the
+        default) switches it off.  Setting the options clears the stats."""
+        o = IcpTsdfCarveOptions(float(distance), float(min_range))
+        self._ck(self.lib.icp_set_tsdf_carve_options(self.h, C.byref(o)))
+        return o
+
+    def tsdf_carve_options(self):
+        o = IcpTsdfCarveOptions()
+        self._ck(self.lib.icp_get_tsdf_carve_options(self.h, C.byref(o)))
+        return o
+
+    def tsdf_carve_stats(self):
+        """icp_tsdf_carve_stats: dict(n_steps: J of the last cloud fuse, n_carved: its applied carve observations, n_carved_total: the
+        same since the options were last set)."""
+        o = IcpTsdfCarveInfo()
+        self._ck(self.lib.icp_tsdf_carve_stats(self.h, C.byref(o)))
+        return dict(n_steps=o.n_steps, n_carved=o.n_carved, n_carved_total=o.n_carved_total)
 
     def tsdf_cloud_system(self, which="source", pose=None, huber=0.0):
         """icp_tsdf_cloud_system: the 28 sums of one direct SDF step of the resident target ("target" / 0) or source ("source" / 1) -- an

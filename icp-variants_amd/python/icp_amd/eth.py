@@ -11,6 +11,7 @@ tests drive real files and synthetic scans through the same code.
 Layout on disk, as the reference expects it under Data/: <eth_dir>/<name>_global.csv and <eth_dir>/<name>/<scan>.pcd.
 PCL is absent here: the normals are this repo's exact k-NN + fp64 PCA (parity with pcl::NormalEstimation unpinned, DESIGN.md).
 """
+import functools
 import os
 import numpy as np
 
@@ -129,13 +130,30 @@ def track_map(ctx, scans, start_pose, voxel_size=0.25, extent=None, margin=2.0, 
     return run()
 
 
+def _carving(run):
+    """Gives a runner the keyword `carve`: None (the default) calls it as it is; dict(distance=..., min_range=...) -- the arguments of
+    Context.set_tsdf_carve -- sets the context's carve options for the call and puts the previous setting back behind it, as
+    tum.track(..., depth_filter=...) does for the depth filter.  The runner's own signature stays what it was."""
+    @functools.wraps(run)
+    def with_carve(ctx, *args, carve=None, **kw):
+        if carve is None:
+            return run(ctx, *args, **kw)
+        from . import binding
+        with binding.tsdf_carve_scope(ctx, carve):
+            return run(ctx, *args, **kw)
+    return with_carve
+
+
+@_carving
 def fuse_scans(ctx, scans, poses, voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, hashed=True, dims=None):
     """Laser scans fused into a TSDF volume (Context.tsdf_integrate_cloud): `scans` as track_map takes them (a list
     of (xyz, normals) in the sensor frame; a bare xyz array will do, the normals are not used), `poses` one 4x4 sensor -> world per scan.
     A volume of `voxel_size` metres is created -- hashed by default (Context.tsdf_create_hashed with `block_capacity`; it has no extent),
     or, with hashed=False, the dense box of `dims` voxels whose voxel (0, 0, 0) is centred on `origin` -- with `truncation` (None: 4
     voxels) and max_depth = `max_range`: a return beyond it is not fused.  Every scan becomes the resident source and is integrated from
-    the sensor's position, one observation per scan.  Returns the info dict of every scan; the volume stays in the context
+    the sensor's position, one observation per scan.  Nothing is carved in front of the surfaces unless carving is on: carve=dict(distance=...,
+    min_range=...) (keyword only; the arguments of Context.set_tsdf_carve) fuses with free space carved and puts the
+    context's previous setting back; None changes nothing.  Returns the info dict of every scan; the volume stays in the context
     (Context.tsdf_sample, Context.tsdf_mesh_hashed, Context.tsdf_blocks)."""
     if len(scans) != len(poses):
         raise ValueError("one pose per scan")
@@ -162,13 +180,15 @@ def _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity,
         ctx.tsdf_create(dims=dims, **opts)
 
 
+@_carving
 def track_tsdf(ctx, scans, start_pose, voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, hashed=True, dims=None,
                **sdf_options):
     """Tracking of a laser sequence against the TSDF volume the scans are fused into (Context.track_scans_sdf):
     one model, no voxel map beside it, every scan uploaded once.  `scans` as fuse_scans takes them, `start_pose` the 4x4 pose of scan 0;
     the volume is created as fuse_scans creates it.  Scan 0 is fused at the start pose; every later scan is aligned to the volume built
     so far (direct SDF alignment with **sdf_options, the fields of binding.sdf_options) and fused at the pose found; a scan that fails is
-    skipped and carries the pose.  Nothing is carved in front of the surfaces, so the field exists only within `truncation` of them:
+    skipped and carries the pose.  Unless carving is on (carve=dict(distance=..., min_range=...) as fuse_scans takes it: set for the call, the
+    previous setting put back; None changes nothing) nothing is carved in front of the surfaces, so the field exists only within `truncation` of them:
     that band is the basin of convergence, and the part of the motion between two scans that is normal to the surfaces has to stay
     inside it (the default is 4 voxels; a faster sensor needs a wider truncation or coarser voxels).  Returns (poses: one 4x4 per scan, records:
     one per scan after the first, infos: the fuse info of every scan, status: the first per-scan error, or 0).  The volume stays in the
@@ -177,6 +197,7 @@ def track_tsdf(ctx, scans, start_pose, voxel_size=0.05, truncation=None, origin=
     return ctx.track_scans_sdf(scans, np.asarray(start_pose, np.float32), **sdf_options)
 
 
+@_carving
 def reconstruct(ctx, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, min_weight=0.0,
                 mesh_path=None, tracker="map", **track_map_options):
     """A surface from a laser sequence, the laser counterpart of tum.reconstruct_room: the scans tracked against the voxel map
@@ -184,7 +205,8 @@ def reconstruct(ctx, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, o
     `tsdf_voxel_size` (`fuse_scans`), the zero level set extracted on the device (Context.tsdf_mesh_hashed with `min_weight`) and, with
     mesh_path, written as a PLY (meshio.write_ply_mesh).  Returns (poses, records, status, (vertices, normals, triangles)).
     tracker="sdf": the scans are tracked against the TSDF volume itself (`track_tsdf`; **track_map_options are then the fields of
-    binding.sdf_options) and that same volume is meshed: one model, one upload of every scan, no second fuse."""
+    binding.sdf_options) and that same volume is meshed: one model, one upload of every scan, no second fuse.  carve: as fuse_scans
+    takes it -- the fuses of either tracker carve free space for the call; None changes nothing."""
     from . import meshio
     if tracker not in ("map", "sdf"):
         raise ValueError("tracker must be 'map' or 'sdf'")

@@ -1479,8 +1479,8 @@ int icp_filter_depth(icp_ctx* ctx, const float* depth, int32_t width, int32_t he
  * on whichever volume the context holds, dense (icp_tsdf_create) or hashed (icp_tsdf_create_hashed); everything that reads the volume
  * (icp_tsdf_sample, the ray-casts, icp_tsdf_mesh / icp_tsdf_mesh_hashed, evict and insert) takes the result as it takes fused frames.
  * On a COLOURED volume the call writes geometry only: the colour array or pool is neither read nor written.
- * The call carves NO free space in front of the band (as the hashed depth touch allocates none there): a voxel nearer to the sensor than
- * range - truncation is not observed.  A ray writes a line ONE voxel wide, so a surface becomes watertight only where neighbouring beams
+ * Unless carving is on (icp_set_tsdf_carve_options below, a step of its own, off by default) the call carves NO free space in front of
+ * the band (as the hashed depth touch allocates none there): a voxel nearer to the sensor than range - truncation is not observed.  A ray writes a line ONE voxel wide, so a surface becomes watertight only where neighbouring beams
  * are closer than a voxel at the surface: choose voxel_size for the scanner's angular step and the range of interest.
  * The result does not depend on the order of the points, nor on any race: the scan is accumulated per voxel in integers (S 64-bit, N
  * 32-bit, two plain arrays: no limit on the size of the cloud beyond int32 points) and folded into the float state once.  The
@@ -1520,6 +1520,58 @@ static_assert(sizeof(icp_tsdf_cloud_info) == 32, "icp_tsdf_cloud_info");
 #endif
 int icp_tsdf_integrate_cloud(icp_ctx* ctx, int32_t which, const float pose[16], const float sensor_origin[3], icp_tsdf_cloud_info* info_out);
 
+/* -------- free space carved by the cloud fuses: icp_set_tsdf_carve_options --------
+ * An option of the context, off by default.  A scan observes only the band of +- truncation around each return, so something that was
+ * scanned and has moved away stays in the model, a single noisy return leaves a speck nothing removes, and the cells at the front edge of
+ * the band have unobserved corners.  With distance > 0 every cloud fuse -- icp_tsdf_integrate_cloud and the fuses inside
+ * icp_track_scans_sdf -- also observes the voxels IN FRONT of the band, up to `distance` metres before it, wherever storage exists: the
+ * existing walk, started earlier.  Carving never allocates, exactly as a depth frame's free-space update never does.  With distance 0 every
+ * call launches exactly the kernels it launches without this option.  The options survive new clouds, new volumes and icp_tsdf_reset.
+ *
+ * Contract (fp32, one rounding per operation, in the order written; tests/tsdf_carve_restatement.py restates it in numpy).  Everything not
+ * named here is icp_tsdf_integrate_cloud's, word for word.
+ *   J = ceil(min(distance, max_depth) / s), in double; a call whose J exceeds 65536 is refused (ICP_ERR_INVALID_ARG) before any device work.
+ *   Samples m = -J .. M, in that order, t_m = fminf((r - truncation) + (float)m s, r + truncation) -- the existing expression.  A sample
+ *   with m >= 0 is skipped unless t_m > 0, as without carving; a sample with m < 0 is skipped unless t_m > min_range.  The sample's voxel
+ *   and the in-range test are the existing ones.
+ *   Repeated voxels, ONE rule for the whole walk: an in-range sample whose voxel equals that of the ray's previous in-range sample is
+ *   skipped.  So the ray's first band sample is skipped (and not counted in n_samples) when its voxel was already observed at m = -1; its
+ *   observation is the same k either way, because k depends only on ray and voxel.
+ *   Observation: an m < 0 sample uses the existing one -- the sdf test, f, k, then S += k, N += 1.  Dense: it applies if the voxel is in
+ *   the box.  Hashed: it applies only if the voxel's block is RESIDENT after this call's touch.
+ *   Counters: an m < 0 sample without storage, or out of range, does nothing and is counted nowhere.  n_samples and n_outside count
+ *   m >= 0 samples only; n_carved counts the applied m < 0 observations.
+ *   Touch and fold are unchanged: the hashed touch walks m >= 0 only; n_updated includes the carved voxels.
+ * What follows from these rules (the tests lean on it):
+ *   (a) Every axis of the voxel sequence along a ray is monotone in m -- each operation between m and g_a is monotone in fp32 -- as the
+ *       nearest-voxel sequence of a straight line never returns to a voxel it left (a Voronoi cell is convex).  So a ray observes a voxel
+ *       at most once, and skipping samples that have no storage cannot change any result.
+ *   (b) A voxel seen only by carve samples whose f = 1 has S = 32768 N, so fbar == 1.0f; from W = 0, D == 1.0f and W == 1, exactly, and
+ *       on any voxel W grows by 1.  icp_tsdf_align_cloud's fabsf(F) < 1 drops a point in such a cell; a cell is valid once its corners
+ *       are observed.
+ *   (c) A voxel that one ray hits and another passes is the integer average of both: the ordinary erosion of carving, not a defect. */
+typedef struct icp_tsdf_carve_options {
+    float distance;   /* 0 = off (default); > 0 or +inf: metres in front of the band that are carved */
+    float min_range;  /* >= 0, finite; carve samples with t <= min_range are skipped (default 0) */
+} icp_tsdf_carve_options;
+typedef struct icp_tsdf_carve_info {
+    int32_t n_steps;          /* J of the last cloud fuse (0: carving was off) */
+    int32_t reserved;         /* 0 */
+    int64_t n_carved;         /* the carve observations (m < 0) applied by the last cloud fuse */
+    int64_t n_carved_total;   /* the same, summed since the options were last set */
+} icp_tsdf_carve_info;
+#ifdef __cplusplus
+static_assert(sizeof(icp_tsdf_carve_options) == 8, "icp_tsdf_carve_options");
+static_assert(sizeof(icp_tsdf_carve_info) == 24, "icp_tsdf_carve_info");
+#endif
+enum { ICP_TSDF_CARVE_MAX_STEPS = 65536 };
+int icp_tsdf_carve_options_default(icp_tsdf_carve_options* opt);
+/* ICP_OK or ICP_ERR_INVALID_ARG (a negative or NaN distance; a negative or non-finite min_range); needs neither a context nor a device. */
+int icp_tsdf_carve_options_check(const icp_tsdf_carve_options* opt);
+int icp_set_tsdf_carve_options(icp_ctx* ctx, const icp_tsdf_carve_options* opt);   /* NULL = defaults (off); clears the stats */
+int icp_get_tsdf_carve_options(const icp_ctx* ctx, icp_tsdf_carve_options* opt);
+int icp_tsdf_carve_stats(const icp_ctx* ctx, icp_tsdf_carve_info* info_out);
+
 /* -------- a laser scan aligned to the TSDF volume itself, and tracked against it --------
  * Direct SDF tracking (icp_tsdf_align_depth above) for a RESIDENT cloud, unorganised, in icp_voxel_map_insert's and
  * icp_tsdf_integrate_cloud's convention (which = 0: the target, 1: the source): every point of the scan, moved into the world by the pose,
@@ -1527,7 +1579,7 @@ int icp_tsdf_integrate_cloud(icp_ctx* ctx, int32_t which, const float pose[16], 
  * model beside the volume the scans are fused into.  The volume is whichever the context holds, dense or hashed.  icp_sdf_options is
  * reused: huber, n_iterations, min_valid, stop_rotation and stop_translation mean what they mean for a depth frame; stride must be 1 and is
  * refused otherwise (the order of the resident cloud is internal, so "every s-th point" could not be restated).
- * icp_tsdf_integrate_cloud carves no free space, so the field exists only inside the truncation band around the fused surfaces: a point
+ * Unless carving is on (icp_set_tsdf_carve_options) icp_tsdf_integrate_cloud carves no free space, so the field exists only inside the truncation band around the fused surfaces: a point
  * further than the truncation from every surface of the model finds no valid cell and takes no part.  The band is the basin of
  * convergence: only the points that start inside it pull the scan, so the part of the motion between two scans that is normal to the
  * surfaces has to stay inside the truncation for enough of them.
