@@ -161,6 +161,7 @@ struct icp_ctx {
     DevBuf te_out_cpool;                 // the colours of the outbox (a coloured hashed volume evicted with hold)
     DevBuf te_work, te_out_pool, te_out_key; int te_held = 0;   // streaming the hashed volume (host_tsdf_hash_evict.hpp): an evict's flags, lists and counters; the outbox (evicted blocks and their keys) and the blocks it holds
     DevBuf tc_acc, tc_ctr; size_t tc_voxels = 0;   // icp_tsdf_integrate_cloud (host_tsdf_cloud.hpp): the integer accumulators [S 8 bytes | N 4 bytes] per voxel of the box or the pool, the call's 64-bit counters; the voxels the accumulators are laid out for and all zero over (0: to be made and cleared)
+    DevBuf tcc_acc; size_t tcc_voxels = 0;   // icp_tsdf_integrate_cloud_color (host_tsdf_cloud.hpp): the colour accumulators [SR | SG | SB | NC], 16 bytes per voxel of the box or the pool, made at the first coloured call; the voxels they are laid out for and all zero over (0: to be made and cleared)
     icp_tsdf_carve_options tcv_opt = {0.f, 0.f}; icp_tsdf_carve_info tcv_info = {0, 0, 0, 0};   // free-space carving of the cloud integrate (icp_set_tsdf_carve_options, host_tsdf_cloud.hpp): the options, which outlive clouds, volumes and resets, and the stats of the last cloud fuse
     DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
     DevBuf tm_nbr, tm_ord;               // icp_tsdf_mesh_hashed (host_tsdf_hash_mesh.hpp), which also uses the five above: the 27 neighbour ranks of every block; order[rank] -> pool index, then rank_of[pool index]

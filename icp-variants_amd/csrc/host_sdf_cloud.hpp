@@ -3,6 +3,7 @@
 // aligns every scan to the model built so far and fuses it there (icp_track_scans_sdf).  Kernels: dev_sdf_cloud.hpp, and dev_sdf.hpp's
 // k_sdf_init / k_sdf_solve launched as they are, through host_sdf.hpp's shared driver (sdf_buffers, sdf_enqueue_pairs, sdf_read_state,
 // sdf_read_record for the geometric kind) as host_vgicp.hpp does; the fuse inside the loop is host_tsdf_cloud.hpp's tsdf_cloud_run.
+// icp_track_scans_sdf_color is the same loop with every scan uploaded with its colours and every fuse the coloured one.
 // Contract: include/icp_hip.h, DESIGN.md section 6zf.  Part of icp_hip.hip (included from there, after host_tsdf_cloud.hpp).
 namespace {
 // The checks that need no device, in the order the header states them (pose_only: the loop has no resident cloud to ask for).
@@ -80,23 +81,32 @@ int icp_tsdf_align_cloud(icp_ctx* c, int32_t which, const icp_sdf_options* opt, 
     return guard.done(r.status);      // (synchronised by the record read)
 }
 
-int icp_track_scans_sdf(icp_ctx* c, const float* const* xyz, const int32_t* n, int32_t n_scans, const icp_sdf_options* opt, float pose_inout[16], icp_sdf_frame* out,
-                        icp_tsdf_cloud_info* infos_out) {
-    if (!c) return ICP_ERR_INVALID_ARG;
-    const char* who = "icp_track_scans_sdf";
+namespace {
+// The loop of icp_track_scans_sdf and, with color, of icp_track_scans_sdf_color: rgba[k] goes up with scan k and every fuse is coloured.
+int track_scans_sdf_run(icp_ctx* c, const float* const* xyz, const uint8_t* const* rgba, const int32_t* n, int32_t n_scans, const icp_sdf_options* opt, float pose_inout[16],
+                        icp_sdf_frame* out, icp_tsdf_cloud_info* infos_out, bool color, int32_t* n_colored_out, const char* who) {
     int rc;
     if ((rc = sdf_cloud_check(c, 1, pose_inout, opt, who, true, nullptr))) return rc;
     if (n_scans > 1 && !out) { c->err = std::string(who) + ": null output (out: n_scans - 1 records)"; return ICP_ERR_INVALID_ARG; }
     if (n_scans < 1 || !xyz || !n) { c->err = std::string(who) + ": bad argument (n_scans >= 1, xyz, n)"; return ICP_ERR_INVALID_ARG; }
     for (int k = 0; k < n_scans; k++) if (!xyz[k] || n[k] <= 0) { c->err = std::string(who) + ": a scan has null points or n <= 0"; return ICP_ERR_INVALID_ARG; }
     { int J; if ((rc = tsdf_carve_steps(c, who, &J))) return rc; }      // (the fuses' carving: refused before any scan is uploaded)
+    if (color) {
+        if ((rc = tsdf_cloud_color_check(c, nullptr, who))) return rc;
+        if (!rgba) { c->err = std::string(who) + ": null colours (rgba: one array per scan)"; return ICP_ERR_INVALID_ARG; }
+        for (int k = 0; k < n_scans; k++) {
+            if (!rgba[k]) { c->err = std::string(who) + ": a scan has null colours"; return ICP_ERR_INVALID_ARG; }
+            if (n[k] > ICP_TSDF_CLOUD_COLOR_MAX_POINTS) { c->err = std::string(who) + ": a scan has more than 2^24 points (the colour sums are 32-bit)"; return ICP_ERR_INVALID_ARG; }
+        }
+        if (n_colored_out) memset(n_colored_out, 0, (size_t)n_scans * sizeof(int32_t));
+    }
     if (infos_out) memset(infos_out, 0, (size_t)n_scans * sizeof(icp_tsdf_cloud_info));
     DrainOnError guard(c);
     if ((rc = set_device(c))) return rc;
     int first_err = ICP_OK;
     for (int k = 0; k < n_scans; k++) {
         // the scan becomes the source by icp_set_source's path, without its wait: the upload only waits for the previous scan to have left the staging block
-        if ((rc = upload_cloud(c, c->src, xyz[k], nullptr, nullptr, n[k], false))) return rc;
+        if ((rc = upload_cloud(c, c->src, xyz[k], nullptr, color ? rgba[k] : nullptr, n[k], false))) return rc;
         if ((rc = finish_source(c))) return rc;
         if (k > 0) {
             ScPlan pl;
@@ -111,11 +121,24 @@ int icp_track_scans_sdf(icp_ctx* c, const float* const* xyz, const int32_t* n, i
                 continue;
             }
         }
-        if ((rc = tsdf_cloud_run(c, c->src, pose_inout, nullptr, infos_out ? infos_out + k : nullptr, who, nullptr))) return rc;      // (waits: it reads its counters)
+        if ((rc = tsdf_cloud_run(c, c->src, pose_inout, nullptr, infos_out ? infos_out + k : nullptr, who, nullptr, color, n_colored_out ? n_colored_out + k : nullptr)))
+            return rc;      // (waits: it reads its counters)
     }
     HIPCK(c, hipStreamSynchronize(c->stream));      // (a skipped last scan leaves its bookkeeping launches behind the record read)
     guard.ok = true;
     return first_err;
+}
+}  // namespace
+
+int icp_track_scans_sdf(icp_ctx* c, const float* const* xyz, const int32_t* n, int32_t n_scans, const icp_sdf_options* opt, float pose_inout[16], icp_sdf_frame* out,
+                        icp_tsdf_cloud_info* infos_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    return track_scans_sdf_run(c, xyz, nullptr, n, n_scans, opt, pose_inout, out, infos_out, false, nullptr, "icp_track_scans_sdf");
+}
+int icp_track_scans_sdf_color(icp_ctx* c, const float* const* xyz, const uint8_t* const* rgba, const int32_t* n, int32_t n_scans, const icp_sdf_options* opt,
+                              float pose_inout[16], icp_sdf_frame* out, icp_tsdf_cloud_info* infos_out, int32_t* n_colored_out) {
+    if (!c) return ICP_ERR_INVALID_ARG;
+    return track_scans_sdf_run(c, xyz, rgba, n, n_scans, opt, pose_inout, out, infos_out, true, n_colored_out, "icp_track_scans_sdf_color");
 }
 
 // Not part of icp_hip.h (tools/time_sdf_cloud.py): the device time of ONE cloud accumulate + k_sdf_solve pair at `pose` between two events

@@ -236,6 +236,7 @@ int icp_tsdf_release(icp_ctx* c) {
     if (c->tsdf_hashed) htsdf_drop(c);
     for (DevBuf* d : {&c->tm_bits, &c->tm_mask, &c->tm_base, &c->tm_blk, &c->tm_out, &c->tm_nbr, &c->tm_ord}) release(*d);      // the mesh extraction's scratch goes with the volume
     release(c->tc_acc); c->tc_voxels = 0;             // and the cloud integrate's accumulators
+    release(c->tcc_acc); c->tcc_voxels = 0;
     c->tsdf_on = false;
     return ICP_OK;
 }
@@ -244,7 +245,7 @@ int icp_tsdf_create(icp_ctx* c, const icp_tsdf_options* opt) {
     if (const char* why = tsdf_options_error(opt)) { c->err = std::string("icp_tsdf_create: ") + why; return ICP_ERR_INVALID_ARG; }
     int rc;
     if ((rc = set_device(c))) return rc;
-    if (c->tsdf_on) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->tsdf_vox); release(c->tsdf_col); c->tsdf_col_on = false; if (c->tsdf_hashed) htsdf_drop(c); release(c->tc_acc); c->tc_voxels = 0; c->tsdf_on = false; }
+    if (c->tsdf_on) { HIPCK(c, hipStreamSynchronize(c->stream)); release(c->tsdf_vox); release(c->tsdf_col); c->tsdf_col_on = false; if (c->tsdf_hashed) htsdf_drop(c); release(c->tc_acc); c->tc_voxels = 0; release(c->tcc_acc); c->tcc_voxels = 0; c->tsdf_on = false; }
     c->tsdf_opt = *opt;
     if (c->tsdf_opt.ray_step == 0.f) c->tsdf_opt.ray_step = opt->truncation / 2.f;
     if ((rc = ensure(c, c->tsdf_vox, tsdf_voxels(c) * 8))) return rc;

@@ -7,6 +7,7 @@ This is harness code for tests/ and bench.py; the product is the shared library.
 so the parity tests read like the reference's drivers (main.cpp:43-181, 343-514).
 """
 import ctypes as C
+import functools
 import os
 import numpy as np
 
@@ -332,6 +333,73 @@ class tsdf_carve_scope:
         return False
 
 
+def _colouring(name, colored):
+    """Gives a method the keyword `name`: None or False (the default) calls it as it is; anything else calls `colored(self, value, ...)`
+    with the method's own arguments.  The method's own signature stays what it was, as eth._carving keeps a runner's."""
+    def give(plain):
+        @functools.wraps(plain)
+        def method(self, *args, **kw):
+            value = kw.pop(name, None)
+            if value is None or value is False:
+                return plain(self, *args, **kw)
+            return colored(self, value, *args, **kw)
+        return method
+    return give
+
+
+def _cloud_fuse_in(which, pose, sensor_origin):
+    w = _cloud(which)
+    p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
+    e = None
+    if sensor_origin is not None:
+        e = _f32(sensor_origin).reshape(-1)
+        if e.size != 3:
+            raise ValueError("sensor_origin must hold three numbers")
+    return w, p, e
+
+
+def _integrate_cloud_color(self, _, which="source", pose=None, sensor_origin=None):
+    w, p, e = _cloud_fuse_in(which, pose, sensor_origin)
+    info = IcpTsdfCloudInfo(); nc = C.c_int32(0)
+    self._ck(self.lib.icp_tsdf_integrate_cloud_color(self.h, C.c_int32(w), _ptr(p), _ptr(e), C.byref(info), C.byref(nc)))
+    return dict(_record(info), n_colored=nc.value)
+
+
+def _scans_in(scans):
+    pts = [_f32(s[0] if isinstance(s, (tuple, list)) else s) for s in scans]
+    if any(a.ndim != 2 or a.shape[1] != 3 for a in pts):
+        raise ValueError("a scan is xyz (n, 3)")
+    return pts
+
+
+def _track_scans_sdf(self, colors, scans, pose=None, **options):
+    """Context.track_scans_sdf behind its docstring; colors: None, or one (n, 4) uint8 array per scan (icp_track_scans_sdf_color)."""
+    o = sdf_options(**options)
+    ns = len(scans)
+    pts = _scans_in(scans)
+    xp = (C.c_void_p * max(ns, 1))(*[_ptr(a) for a in pts])
+    cnt = (C.c_int32 * max(ns, 1))(*[len(a) for a in pts])
+    p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
+    start = pose_from_c(p)
+    out = (IcpSdfFrame * max(ns - 1, 1))(); infos = (IcpTsdfCloudInfo * max(ns, 1))()
+    if colors is None:
+        rc = self.lib.icp_track_scans_sdf(self.h, xp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out, infos)
+    else:
+        if len(colors) != ns:
+            raise ValueError("one colour array per scan")
+        cols = [np.ascontiguousarray(c, dtype=np.uint8) for c in colors]
+        if any(c.shape != (len(a), 4) for c, a in zip(cols, pts)):
+            raise ValueError("a scan's colours are rgba (n, 4) bytes, one row per point")
+        cp = (C.c_void_p * max(ns, 1))(*[_ptr(c) for c in cols])
+        ncol = (C.c_int32 * max(ns, 1))()
+        rc = self.lib.icp_track_scans_sdf_color(self.h, xp, cp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out, infos, ncol)
+    if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-scan outcomes: reported in the records
+        self._ck(rc)
+    recs = [_record(out[i]) for i in range(ns - 1)]
+    res = ([start] + [r["pose"] for r in recs], recs, [_record(infos[i]) for i in range(ns)], rc)
+    return res if colors is None else res + ([ncol[i] for i in range(ns)],)
+
+
 class IcpSdfColorOptions(C.Structure):
     _fields_ = [("weight", C.c_float), ("huber", C.c_float)]
 
@@ -538,7 +606,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_create_hashed", "icp_tsdf_reserve_blocks", "icp_tsdf_allocate_blocks", "icp_get_tsdf_hashed", "icp_tsdf_upload_hashed",
            "icp_tsdf_mesh_hashed", "icp_tsdf_raycast_hashed", "icp_set_target_tsdf_hashed", "icp_track_depth_model_hashed",
            "icp_tsdf_evict_blocks", "icp_tsdf_evicted_blocks", "icp_tsdf_insert_blocks", "icp_tsdf_integrate_cloud",
-           "icp_tsdf_cloud_system", "icp_tsdf_align_cloud", "icp_track_scans_sdf",
+           "icp_tsdf_cloud_system", "icp_tsdf_align_cloud", "icp_track_scans_sdf", "icp_tsdf_integrate_cloud_color", "icp_track_scans_sdf_color",
            "icp_tsdf_create_color_hashed", "icp_tsdf_hashed_has_color", "icp_get_tsdf_color_hashed", "icp_tsdf_upload_color_hashed",
            "icp_tsdf_evicted_blocks_color", "icp_tsdf_insert_blocks_color",
            "icp_tsdf_raycast_color_hashed", "icp_set_target_tsdf_color_hashed", "icp_track_depth_model_color_hashed", "icp_tsdf_mesh_color_hashed",
@@ -1297,18 +1365,16 @@ class Context:
         self._ck(self.lib.icp_tsdf_integrate(self.h, _ptr(depth), C.byref(cam), _ptr(pose_to_c(pose)), C.byref(n)))
         return n.value
 
+    @_colouring("color", _integrate_cloud_color)
     def tsdf_integrate_cloud(self, which="source", pose=None, sensor_origin=None):
         """icp_tsdf_integrate_cloud: fuses the resident target ("target" / 0) or source ("source" / 1) -- an unorganised cloud in its sensor
         frame, a laser scan -- into the volume, dense or hashed, as one observation.  pose: 4x4 scan frame -> world
-        (None: the identity); sensor_origin: the ray origin in the scan frame (None: (0, 0, 0)).  Geometry only: the colours of a coloured
-        volume stay as they are.  Returns dict(n_points, n_rays, n_updated, n_blocks, n_samples, n_outside)."""
-        w = _cloud(which)
-        p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
-        e = None
-        if sensor_origin is not None:
-            e = _f32(sensor_origin).reshape(-1)
-            if e.size != 3:
-                raise ValueError("sensor_origin must hold three numbers")
+        (None: the identity); sensor_origin: the ray origin in the scan frame (None: (0, 0, 0)).  Geometry only (unless color=True, below): the colours of a coloured
+        volume stay as they are.  Returns dict(n_points, n_rays, n_updated, n_blocks, n_samples, n_outside).
+        color=True (keyword only): icp_tsdf_integrate_cloud_color -- the volume has colours (`tsdf_create(color=True)`,
+        `tsdf_create_hashed(color=True)`) and the cloud was set with rgba; the scan's colours are fused with its geometry (DESIGN.md
+        section 6zh) and the dict gains n_colored."""
+        w, p, e = _cloud_fuse_in(which, pose, sensor_origin)
         info = IcpTsdfCloudInfo()
         self._ck(self.lib.icp_tsdf_integrate_cloud(self.h, C.c_int32(w), _ptr(p), _ptr(e), C.byref(info)))
         return _record(info)
@@ -1363,27 +1429,17 @@ class Context:
             return pose_from_c(p), r, rc, [_record(tr[i]) for i in range(r["iterations"])]
         return pose_from_c(p), r, rc
 
+    @_colouring("colors", _track_scans_sdf)
     def track_scans_sdf(self, scans, pose=None, **options):
         """icp_track_scans_sdf: `scans`, a list of xyz (n, 3) arrays in the sensor frame (a (xyz, normals) pair as `track_scans_vmap`
         takes it will do, the normals are not used), tracked against the TSDF volume they are fused into: scan 0 fused at `pose`
         (identity by default), every later scan aligned to the volume built so far (**options: the fields of `sdf_options`) and, when
         that succeeds, fused at the pose found; a scan that fails is skipped and carries the pose.  Returns (poses: one 4x4 per scan,
-        the records of scans 1 .., the fuse info of every scan -- all zero for a skipped one --, status: the first per-scan error, or 0)."""
-        o = sdf_options(**options)
-        ns = len(scans)
-        pts = [_f32(s[0] if isinstance(s, (tuple, list)) else s) for s in scans]
-        if any(a.ndim != 2 or a.shape[1] != 3 for a in pts):
-            raise ValueError("a scan is xyz (n, 3)")
-        xp = (C.c_void_p * max(ns, 1))(*[_ptr(a) for a in pts])
-        cnt = (C.c_int32 * max(ns, 1))(*[len(a) for a in pts])
-        p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
-        start = pose_from_c(p)
-        out = (IcpSdfFrame * max(ns - 1, 1))(); infos = (IcpTsdfCloudInfo * max(ns, 1))()
-        rc = self.lib.icp_track_scans_sdf(self.h, xp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out, infos)
-        if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-scan outcomes: reported in the records
-            self._ck(rc)
-        recs = [_record(out[i]) for i in range(ns - 1)]
-        return [start] + [r["pose"] for r in recs], recs, [_record(infos[i]) for i in range(ns)], rc
+        the records of scans 1 .., the fuse info of every scan -- all zero for a skipped one --, status: the first per-scan error, or 0).
+        colors (keyword only): one rgba (n, 4) uint8 array per scan -- icp_track_scans_sdf_color on a coloured volume: every scan goes up
+        with its colours and every fuse is the coloured one; poses, records and infos are the uncoloured loop's,
+        and the tuple gains a fifth value, n_colored of every scan (0 for a skipped one)."""
+        return _track_scans_sdf(self, None, scans, pose, **options)
 
     def tsdf_raycast(self, cam, pose):
         """icp_tsdf_raycast: the volume seen from `pose` as an organised cloud in that camera's frame.  Returns (depth (h, w), vertices

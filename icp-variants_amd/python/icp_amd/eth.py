@@ -144,7 +144,47 @@ def _carving(run):
     return with_carve
 
 
+def _colouring(coloured):
+    """Gives a runner the keyword `colors`: None (the default) calls it as it is; one rgba (n, 4) uint8 array per scan calls
+    `coloured(ctx, colors, ...)` with the runner's own arguments -- the same run on a volume with colours, every scan fused with its
+    colours (Context.tsdf_integrate_cloud(color=True), Context.track_scans_sdf(colors=...)).  The runner's own
+    signature stays what it was."""
+    def give(run):
+        @functools.wraps(run)
+        def with_colors(ctx, *args, colors=None, **kw):
+            if colors is None:
+                return run(ctx, *args, **kw)
+            return coloured(ctx, colors, *args, **kw)
+        return with_colors
+    return give
+
+
+def _scan_colors(scans, colors):
+    if len(colors) != len(scans):
+        raise ValueError("one colour array per scan")
+    return [np.ascontiguousarray(c, np.uint8) for c in colors]
+
+
+def _fuse_scans(ctx, colors, scans, poses, voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, hashed=True, dims=None):
+    """fuse_scans behind its docstring; colors: None, or one rgba array per scan."""
+    if len(scans) != len(poses):
+        raise ValueError("one pose per scan")
+    cols = None if colors is None else _scan_colors(scans, colors)
+    _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims, color=cols is not None)
+    infos = []
+    for k, (s, T) in enumerate(zip(scans, poses)):
+        xyz = s[0] if isinstance(s, (tuple, list)) else s
+        if cols is None:
+            ctx.set_source(np.ascontiguousarray(xyz, np.float32))
+            infos.append(ctx.tsdf_integrate_cloud("source", pose=np.asarray(T, np.float32)))
+        else:
+            ctx.set_source(np.ascontiguousarray(xyz, np.float32), None, cols[k])
+            infos.append(ctx.tsdf_integrate_cloud("source", pose=np.asarray(T, np.float32), color=True))
+    return infos
+
+
 @_carving
+@_colouring(_fuse_scans)
 def fuse_scans(ctx, scans, poses, voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, hashed=True, dims=None):
     """Laser scans fused into a TSDF volume (Context.tsdf_integrate_cloud): `scans` as track_map takes them (a list
     of (xyz, normals) in the sensor frame; a bare xyz array will do, the normals are not used), `poses` one 4x4 sensor -> world per scan.
@@ -153,20 +193,14 @@ def fuse_scans(ctx, scans, poses, voxel_size=0.05, truncation=None, origin=(0.0,
     voxels) and max_depth = `max_range`: a return beyond it is not fused.  Every scan becomes the resident source and is integrated from
     the sensor's position, one observation per scan.  Nothing is carved in front of the surfaces unless carving is on: carve=dict(distance=...,
     min_range=...) (keyword only; the arguments of Context.set_tsdf_carve) fuses with free space carved and puts the
-    context's previous setting back; None changes nothing.  Returns the info dict of every scan; the volume stays in the context
+    context's previous setting back; None changes nothing.  colors (keyword only): one rgba (n, 4) uint8 array per scan -- the volume is
+    created with colours and every scan is fused with its colours (each info dict gains n_colored); None changes
+    nothing.  Returns the info dict of every scan; the volume stays in the context
     (Context.tsdf_sample, Context.tsdf_mesh_hashed, Context.tsdf_blocks)."""
-    if len(scans) != len(poses):
-        raise ValueError("one pose per scan")
-    _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims)
-    infos = []
-    for s, T in zip(scans, poses):
-        xyz = s[0] if isinstance(s, (tuple, list)) else s
-        ctx.set_source(np.ascontiguousarray(xyz, np.float32))
-        infos.append(ctx.tsdf_integrate_cloud("source", pose=np.asarray(T, np.float32)))
-    return infos
+    return _fuse_scans(ctx, None, scans, poses, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims)
 
 
-def _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims):
+def _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims, color=False):
     """The volume fuse_scans and track_tsdf create: hashed, or the dense box of `dims` voxels."""
     if not hashed and dims is None:
         raise ValueError("a dense volume needs dims")
@@ -174,13 +208,25 @@ def _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity,
         raise ValueError("a hashed volume has no extent")
     opts = dict(origin=tuple(float(x) for x in origin), voxel_size=float(voxel_size), truncation=4.0 * float(voxel_size) if truncation is None else float(truncation),
                 max_depth=float(max_range))
+    colour = dict(color=True) if color else {}
     if hashed:
-        ctx.tsdf_create_hashed(block_capacity=block_capacity, **opts)
+        ctx.tsdf_create_hashed(block_capacity=block_capacity, **colour, **opts)
     else:
-        ctx.tsdf_create(dims=dims, **opts)
+        ctx.tsdf_create(dims=dims, **colour, **opts)
+
+
+def _track_tsdf(ctx, colors, scans, start_pose, voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, hashed=True, dims=None,
+                **sdf_options):
+    """track_tsdf behind its docstring; colors: None, or one rgba array per scan."""
+    cols = None if colors is None else _scan_colors(scans, colors)
+    _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims, color=cols is not None)
+    if cols is None:
+        return ctx.track_scans_sdf(scans, np.asarray(start_pose, np.float32), **sdf_options)
+    return ctx.track_scans_sdf(scans, np.asarray(start_pose, np.float32), colors=cols, **sdf_options)
 
 
 @_carving
+@_colouring(_track_tsdf)
 def track_tsdf(ctx, scans, start_pose, voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, hashed=True, dims=None,
                **sdf_options):
     """Tracking of a laser sequence against the TSDF volume the scans are fused into (Context.track_scans_sdf):
@@ -191,13 +237,42 @@ def track_tsdf(ctx, scans, start_pose, voxel_size=0.05, truncation=None, origin=
     previous setting put back; None changes nothing) nothing is carved in front of the surfaces, so the field exists only within `truncation` of them:
     that band is the basin of convergence, and the part of the motion between two scans that is normal to the surfaces has to stay
     inside it (the default is 4 voxels; a faster sensor needs a wider truncation or coarser voxels).  Returns (poses: one 4x4 per scan, records:
-    one per scan after the first, infos: the fuse info of every scan, status: the first per-scan error, or 0).  The volume stays in the
+    one per scan after the first, infos: the fuse info of every scan, status: the first per-scan error, or 0).  colors (keyword only): one
+    rgba (n, 4) uint8 array per scan -- the volume is created with colours, every scan goes up with its colours and every fuse is the
+    coloured one (Context.track_scans_sdf(colors=...)); poses, records and infos are what they are without, and a
+    fifth value is returned, n_colored of every scan; None changes nothing.  The volume stays in the
     context (Context.tsdf_sample, Context.tsdf_mesh_hashed, Context.tsdf_blocks)."""
-    _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims)
-    return ctx.track_scans_sdf(scans, np.asarray(start_pose, np.float32), **sdf_options)
+    return _track_tsdf(ctx, None, scans, start_pose, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims, **sdf_options)
+
+
+def _reconstruct(ctx, colors, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, min_weight=0.0,
+                 mesh_path=None, tracker="map", **track_map_options):
+    """reconstruct behind its docstring; colors: None, or one rgba array per scan."""
+    from . import meshio
+    if tracker not in ("map", "sdf"):
+        raise ValueError("tracker must be 'map' or 'sdf'")
+    coloured = {} if colors is None else dict(colors=colors)
+    if tracker == "sdf":
+        poses, records, _, status = track_tsdf(ctx, scans, start_pose, voxel_size=tsdf_voxel_size, truncation=truncation, origin=origin, max_range=max_range,
+                                               block_capacity=block_capacity, **coloured, **track_map_options)[:4]
+    else:
+        if "keep_radius" in track_map_options and track_map_options["keep_radius"] is not None:
+            raise ValueError("reconstruct tracks against the whole map (keep_radius is not supported)")
+        poses, records, status = track_map(ctx, scans, start_pose, **track_map_options)
+        fuse_scans(ctx, scans, poses, voxel_size=tsdf_voxel_size, truncation=truncation, origin=origin, max_range=max_range, block_capacity=block_capacity, **coloured)
+    if colors is None:
+        mesh = ctx.tsdf_mesh_hashed(min_weight=min_weight)
+        if mesh_path is not None:
+            meshio.write_ply_mesh(mesh_path, *mesh)
+        return poses, records, status, mesh
+    v, n, t, c = ctx.tsdf_mesh_hashed(min_weight=min_weight, colors=True)
+    if mesh_path is not None:
+        meshio.write_ply_mesh(mesh_path, v, n, t, colors=c)
+    return poses, records, status, (v, n, t, c)
 
 
 @_carving
+@_colouring(_reconstruct)
 def reconstruct(ctx, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, min_weight=0.0,
                 mesh_path=None, tracker="map", **track_map_options):
     """A surface from a laser sequence, the laser counterpart of tum.reconstruct_room: the scans tracked against the voxel map
@@ -206,25 +281,11 @@ def reconstruct(ctx, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, o
     mesh_path, written as a PLY (meshio.write_ply_mesh).  Returns (poses, records, status, (vertices, normals, triangles)).
     tracker="sdf": the scans are tracked against the TSDF volume itself (`track_tsdf`; **track_map_options are then the fields of
     binding.sdf_options) and that same volume is meshed: one model, one upload of every scan, no second fuse.  carve: as fuse_scans
-    takes it -- the fuses of either tracker carve free space for the call; None changes nothing."""
-    from . import meshio
-    if tracker not in ("map", "sdf"):
-        raise ValueError("tracker must be 'map' or 'sdf'")
-    if tracker == "sdf":
-        poses, records, _, status = track_tsdf(ctx, scans, start_pose, voxel_size=tsdf_voxel_size, truncation=truncation, origin=origin, max_range=max_range,
-                                               block_capacity=block_capacity, **track_map_options)
-        mesh = ctx.tsdf_mesh_hashed(min_weight=min_weight)
-        if mesh_path is not None:
-            meshio.write_ply_mesh(mesh_path, *mesh)
-        return poses, records, status, mesh
-    if "keep_radius" in track_map_options and track_map_options["keep_radius"] is not None:
-        raise ValueError("reconstruct tracks against the whole map (keep_radius is not supported)")
-    poses, records, status = track_map(ctx, scans, start_pose, **track_map_options)
-    fuse_scans(ctx, scans, poses, voxel_size=tsdf_voxel_size, truncation=truncation, origin=origin, max_range=max_range, block_capacity=block_capacity)
-    mesh = ctx.tsdf_mesh_hashed(min_weight=min_weight)
-    if mesh_path is not None:
-        meshio.write_ply_mesh(mesh_path, *mesh)
-    return poses, records, status, mesh
+    takes it -- the fuses of either tracker carve free space for the call; None changes nothing.  colors (keyword only): one rgba (n, 4)
+    uint8 array per scan -- the model is fused with the scans' colours, meshed with
+    Context.tsdf_mesh_hashed(colors=True), written with meshio.write_ply_mesh(..., colors=...), and the mesh returned is (vertices,
+    normals, triangles, colours (V, 4) uint8: alpha 255 on a coloured vertex); None changes nothing."""
+    return _reconstruct(ctx, None, scans, start_pose, tsdf_voxel_size, truncation, origin, max_range, block_capacity, min_weight, mesh_path, tracker, **track_map_options)
 
 
 def write_synthetic_dataset(eth_dir, csv_name, pairs, binary=True):

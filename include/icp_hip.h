@@ -1478,7 +1478,8 @@ int icp_filter_depth(icp_ctx* ctx, const float* depth, int32_t width, int32_t he
  * from the sensor centre, walked through the truncation band in steps of one voxel, and each sample observes its nearest voxel.  It works
  * on whichever volume the context holds, dense (icp_tsdf_create) or hashed (icp_tsdf_create_hashed); everything that reads the volume
  * (icp_tsdf_sample, the ray-casts, icp_tsdf_mesh / icp_tsdf_mesh_hashed, evict and insert) takes the result as it takes fused frames.
- * On a COLOURED volume the call writes geometry only: the colour array or pool is neither read nor written.
+ * On a COLOURED volume the call writes geometry only: the colour array or pool is neither read nor written.  The scan's colours go in
+ * with icp_tsdf_integrate_cloud_color (below).
  * Unless carving is on (icp_set_tsdf_carve_options below, a step of its own, off by default) the call carves NO free space in front of
  * the band (as the hashed depth touch allocates none there): a voxel nearer to the sensor than range - truncation is not observed.  A ray writes a line ONE voxel wide, so a surface becomes watertight only where neighbouring beams
  * are closer than a voxel at the surface: choose voxel_size for the scanner's angular step and the range of interest.
@@ -1614,6 +1615,51 @@ int icp_tsdf_align_cloud(icp_ctx* ctx, int32_t which, const icp_sdf_options* opt
  * its limit) ends the call. */
 int icp_track_scans_sdf(icp_ctx* ctx, const float* const* xyz, const int32_t* n, int32_t n_scans, const icp_sdf_options* opt,
                         float pose_inout[16], icp_sdf_frame* out, icp_tsdf_cloud_info* infos_out);
+
+/* -------- the colours of a laser scan into the coloured TSDF volume --------
+ * icp_tsdf_integrate_cloud on a volume WITH colours -- dense with its colour array (icp_tsdf_color_create), or hashed with coloured blocks
+ * (icp_tsdf_create_color_hashed) -- and a resident cloud WITH colours (icp_set_target / icp_set_source with rgba): the scan's colours are
+ * fused with its geometry, so that everything that reads the colours (icp_tsdf_sample_color, the coloured ray-casts, targets and model
+ * loops, icp_tsdf_mesh_color / icp_tsdf_mesh_color_hashed, the coloured evict and insert, the photometric direct tracker) takes a model made
+ * from scans as it takes one made from depth frames.
+ * Geometry: exactly icp_tsdf_integrate_cloud from the same state under the context's current carve options -- D, W, the blocks, info_out
+ * and the carve stats are the same bit for bit.
+ * Colour (fp32, one rounding per operation, in the order written; what comes after a cast to double is fp64;
+ * tests/tsdf_cloud_color_restatement.py restates it in numpy).  Everything not named here is icp_tsdf_integrate_cloud's, word for word.
+ *   Point i's colour is the first three bytes of its rgba, c_0 .. c_2; alpha is not read.
+ *   The colour walk of a usable ray is the UNCARVED walk, whatever the carve options are: samples m = 0 .. M with the same t_m, voxel and
+ *   in-range test, and the rule about repeated voxels among the ray's own band samples -- a sample whose voxel equals that of the ray's
+ *   previous in-range sample with m >= 0 is skipped.  Carve samples (m < 0) never colour.
+ *   A band sample colours its voxel iff its observation is not skipped (!(sdf < -truncation)) AND !(sdf > truncation): the band rule of
+ *   icp_tsdf_integrate_color.  A band sample's nearest voxel can lie up to about 0.87 voxels nearer the sensor than the sample, so voxels
+ *   that are updated and not coloured are common.
+ *   The voxel's four integer accumulators take SR += c_0, SG += c_1, SB += c_2, NC += 1.
+ *   Fold, for every voxel with NC > 0, with one read of its float4 (C_0, C_1, C_2, Wc): cbar_r = (float)((double)S_r / (double)NC);
+ *   C_r <- (Wc C_r + cbar_r) / (Wc + 1.f) per channel; Wc <- fminf(Wc + 1.f, max_weight).  A voxel with NC == 0 has its float4 neither
+ *   read nor written.  *n_colored_out (optional) counts the voxels with NC > 0.  The accumulators are all zero outside a call.
+ *   On a hashed volume the colour walk visits only voxels whose block this call's touch has made resident; the touch walks the same
+ *   m >= 0 samples and is exact.
+ *   Limit: the cloud has at most 2^24 points.  By property (a) of the carve contract a ray meets a voxel at most once, so NC <= 2^24 and
+ *   every sum is at most 255 2^24 < 2^32: the accumulators are 32-bit, 16 bytes per voxel (8 KiB per pool block of a hashed volume, as much
+ *   again as a dense colour array), allocated at the first coloured call; they leave with the volume and are re-made when the storage
+ *   they index changes size, as the geometry's accumulators are.
+ * What follows from these rules (the tests lean on it): (1) the colours after a call do not depend on the carve options; (2) nor on the
+ * order of the points; (3) the coloured voxels are a subset of the updated ones; (4) a voxel coloured by one ray from Wc = 0 holds that
+ * point's three bytes exactly, as floats, with Wc == 1.
+ * Refusals: icp_tsdf_integrate_cloud's own checks first, in its order; then, all before any device work, a volume without colours
+ * (ICP_ERR_INVALID_ARG), a cloud without colours (ICP_ERR_COLOR_MISMATCH), more than 2^24 points (ICP_ERR_INVALID_ARG), each with a message
+ * that names the call.  A refused call leaves geometry and colours bit for bit as they were. */
+enum { ICP_TSDF_CLOUD_COLOR_MAX_POINTS = 1 << 24 };
+int icp_tsdf_integrate_cloud_color(icp_ctx* ctx, int32_t which, const float pose[16], const float sensor_origin[3],
+                                   icp_tsdf_cloud_info* info_out, int32_t* n_colored_out);
+/* icp_track_scans_sdf with two changes: every scan is uploaded with its colours (rgba[k]: n[k] x 4 bytes) and every fuse is
+ * icp_tsdf_integrate_cloud_color's.  The alignment is unchanged and reads geometry only, so poses, records and infos equal
+ * icp_track_scans_sdf's on the same scans bit for bit.  n_colored_out: NULL, or n_scans counts, 0 for a skipped scan.  The host waits as
+ * often as in icp_track_scans_sdf: n_colored comes back with the counters the fuse reads anyway.  Refused as icp_track_scans_sdf is, then
+ * (ICP_ERR_INVALID_ARG, before any scan is uploaded) on a volume without colours, a null rgba or rgba[k], a scan of more than 2^24 points. */
+int icp_track_scans_sdf_color(icp_ctx* ctx, const float* const* xyz, const uint8_t* const* rgba, const int32_t* n, int32_t n_scans,
+                              const icp_sdf_options* opt, float pose_inout[16], icp_sdf_frame* out, icp_tsdf_cloud_info* infos_out,
+                              int32_t* n_colored_out);
 
 /* -------- batches of independent scan pairs: the loop over ETH indices, main.cpp:411-498 / experiment.cpp:319-396 --------
  * The reference aligns the pairs one after the other and carries no state between them, so a batch shards with no
