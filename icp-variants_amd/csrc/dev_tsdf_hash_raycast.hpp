@@ -15,6 +15,9 @@ struct HtCache { int bx, by, bz, blk; };
 // htsdf_cell with the block of the LOWEST corner (f >> 3) found first, through the cache: when that block is missing the sample is invalid
 // and nothing is loaded; a cell inside the block (local <= 6 on every axis) costs no further lookup; a cell across a face, an edge or the
 // corner looks the other 1, 3 or 7 blocks up only now.  The validity is htsdf_cell's: all eight corners in existing blocks with W > 0.
+// The address (g, floor, the range test, the fractions, block and local coordinates) is htsdf_cell's text, written out: taken from a
+// helper shared with it, the hashed ray-casts compiled to 75 VGPRs for 92 / 93 and ran 1.1 to 3.1 % slower than the slowest of three
+// runs of the parent on all six hashed medians of tools/time_htsdf_raycast.py, in both of two runs.
 __device__ __forceinline__ bool htsdf_cell_cached(const HtVol& v, HtCache& h, float qx, float qy, float qz, float (&c)[8], float& tx, float& ty, float& tz) {
     const float gx = (qx - v.ox) / v.s, gy = (qy - v.oy) / v.s, gz = (qz - v.oz) / v.s;
     const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);

@@ -318,6 +318,55 @@ def test_color_system_matches_dense_and_restatement(gpu_ctx_factory):
     assert np.array_equal(u64(g), u64(z)) and tuple(gc) == tuple(zc) and len(g) == 28
 
 
+def test_color_system_in_every_class_of_cell(gpu_ctx_factory):
+    """The joint step's cell of BOTH pools where it crosses a face, an edge and the corner: 2 x 2 x 2 blocks with crafted voxels and
+    colours, a 16 x 16 frame (one work-group) behind a camera whose rays are one voxel apart at the frame's depth, pose identity -- pixel
+    (u, w) falls into cell (u, w, 7 or 3), so column 7, row 7 and every other pixel's depth put local coordinate 7 on one, two and three
+    axes, and column and row 15 reach for blocks that do not exist.  The frame as a whole and the pixels of each class alone (the rest
+    MINF, so a class's terms cannot hide among the others'): check_system's comparisons with the dense call and the restatement."""
+    from icp_amd import binding
+    s = f32(1 / 64)
+    opts = dict(origin=(float(-8.3 * s), float(-8.3 * s), float(4 - 7.4 * s)), voxel_size=float(s), truncation=float(3 * s), max_weight=64.0, min_depth=0.3, max_depth=4.5)
+    rng = np.random.default_rng(23)
+    coords = HC.box_coords((0, 0, 0), (2, 2, 2))
+    t = rng.uniform(-0.9, 0.9, (8, 8, 8, 8)).astype(f32); w = np.ones((8, 8, 8, 8), f32)
+    rgb = rng.uniform(0, 255, (8, 8, 8, 8, 3)).astype(f32); cw = rng.choice(np.array([1, 2.5, 7], f32), (8, 8, 8, 8))
+    w[rng.random(w.shape) < 0.01] = 0; cw[rng.random(cw.shape) < 0.01] = 0
+    for e, c in enumerate(coords):                            # the one cell across the corner, (7, 7, 7), is observed and coloured
+        z, y, x = (7 if c[a] == 0 else 0 for a in (2, 1, 0))
+        w[e, z, y, x] = 1; cw[e, z, y, x] = 2.5
+    h, d = gpu_ctx_factory(), gpu_ctx_factory()
+    h.tsdf_create_hashed(block_capacity=8, color=True, **opts)
+    h.tsdf_upload_blocks(coords, t, w, rgb, cw)
+    d.tsdf_create(color=True, dims=(16, 16, 16), **opts)
+    d.tsdf_upload(*binding.tsdf_blocks_to_dense(coords, t, w, (0, 0, 0), (16, 16, 16)))
+    d.tsdf_color_upload(*binding.tsdf_block_colors_to_dense(coords, rgb, cw, (0, 0, 0), (16, 16, 16)))
+    hv = HCR.add_color(HR.HVolume(**opts))
+    for c, tt, ww, cc, cww in zip(coords, t, w, rgb, cw):
+        hv.blocks[tuple(int(x) for x in c)] = [tt, ww]; hv.colors[tuple(int(x) for x in c)] = [cc, cww]
+    K = np.array([[256, 0, 8], [0, 256, 8], [0, 0, 1]], f32)
+    cam, rcam = binding.depth_camera(K, 16, 16), TS.Camera(K, 16, 16)
+    v, u = np.meshgrid(np.arange(16), np.arange(16), indexing="ij")
+    depth = np.where((u + v) % 2 == 0, f32(4), f32(4) - f32(4) * s).astype(f32)
+    pts = np.stack([(u.astype(f32) - f32(8)) / f32(256) * depth, (v.astype(f32) - f32(8)) / f32(256) * depth, depth], -1).reshape(-1, 3).astype(f32)
+    cells = np.floor((pts - np.array(opts["origin"], f32)) / s).astype(int)
+    assert np.array_equal(cells, np.stack([u, v, np.where((u + v) % 2 == 0, 7, 3)], -1).reshape(-1, 3))
+    n_cross = ((cells & 7) == 7).sum(1)
+    ok = h.tsdf_sample(pts)[2].astype(bool)
+    assert not ok[(cells[:, :2] == 15).any(1)].any()          # a corner's block is missing
+    rgbx = crafted_rgbx(16, 16, 5)
+    eye = np.eye(4, dtype=f32)
+    frame = depth.copy(); frame[0, 1], frame[1, 0] = MINF, np.nan
+    counts, sums, _ = check_system(h, d, hv, cam, rcam, frame, rgbx, eye, "16 x 16, every class", color_huber=0.1)
+    assert counts[0] == 254 and 100 < counts[2] < counts[1] < 225
+    for k in range(4):
+        only = np.where((n_cross == k).reshape(16, 16), depth, MINF).astype(f32)
+        counts, sums, _ = check_system(h, d, hv, cam, rcam, only, rgbx, eye, "16 x 16, cells across %d block boundaries" % k, huber=0.01 * k)
+        assert counts[0] == (n_cross == k).sum() and counts[1] == (ok & (n_cross == k)).sum() and 0 < counts[2] <= counts[1] and sums[28] > 0, (k, counts)
+    # (local coordinate 7 is also cell 15's: of the 4 cells across three boundaries only (7, 7, 7) has its eight blocks)
+    assert [(ok & (n_cross == k)).sum() for k in range(4)] == [85, 104, 12, 1] and ok[(cells == 7).all(1)].all()
+
+
 # ---- 7. align and loop
 def python_loop(ctx, depth, cam, rgbx, **kw):
     """icp_track_depth_sdf_color as a composition of public calls (the volume exists)."""
