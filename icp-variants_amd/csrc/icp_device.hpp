@@ -10,7 +10,8 @@
 // dev_fused.hpp, dev_measures.hpp, dev_mesh.hpp, dev_lm.hpp, dev_multi.hpp, dev_gicp.hpp, dev_robust.hpp, dev_colored.hpp, dev_nss.hpp,
 // dev_fpfh.hpp, dev_reciprocal.hpp, dev_tsdf_color.hpp, dev_tsdf.hpp, dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp, dev_sdf.hpp, dev_sdf_color.hpp, dev_vgicp.hpp,
 // dev_vmap.hpp, dev_hmap.hpp, dev_tsdf_hash.hpp, dev_tsdf_hash_raycast.hpp, dev_tsdf_hash_mesh.hpp, dev_tsdf_hash_evict.hpp, dev_tsdf_hash_color.hpp,
-// dev_tsdf_hash_raycast_color.hpp, dev_tsdf_hash_mesh_color.hpp, dev_vmap_prune.hpp, dev_tsdf_cloud.hpp, dev_tsdf_carve.hpp, dev_tsdf_cloud_color.hpp
+// dev_tsdf_hash_raycast_color.hpp, dev_tsdf_hash_mesh_color.hpp, dev_vmap_prune.hpp, dev_tsdf_cloud.hpp, dev_tsdf_carve.hpp, dev_tsdf_cloud_color.hpp, dev_sdf_cloud.hpp,
+// dev_sdf_cloud_color.hpp
 // (included below, in this order, inside namespace icpdev).
 //
 // Kernel map (reference file:line relative to icp-variants/ of the reference):
@@ -89,6 +90,9 @@
 //                       accumulate, the points' bytes summed per voxel in integers, and folded into (R, G, B, Wc) once (dev_tsdf_cloud_color.hpp)
 //   k_*sdf_accumulate_cloud  direct SDF tracking of a laser scan (icp_tsdf_align_cloud, icp_track_scans_sdf): the resident cloud's point-to-plane
 //                       sums read from the volume's field and gradient, dense or hashed; k_sdf_solve behind them (dev_sdf_cloud.hpp)
+//   k_*sdf_accumulate_cloud_color  the same for a coloured scan with a photometric row per coloured point (icp_tsdf_align_cloud_color,
+//                       icp_track_scans_sdf_photometric): the point's own colour against the intensity field of its cell; k_sdf_solve_color
+//                       behind them (dev_sdf_cloud_color.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -142,5 +146,6 @@ namespace icpdev {
 #include "dev_tsdf_carve.hpp"
 #include "dev_tsdf_cloud_color.hpp"
 #include "dev_sdf_cloud.hpp"
+#include "dev_sdf_cloud_color.hpp"
 
 }  // namespace icpdev

@@ -347,6 +347,50 @@ def _colouring(name, colored):
     return give
 
 
+def _color_term(kw):
+    """Takes color_weight and color_huber (0.0 each by default) out of a keyword dict: None for a weight of zero -- the geometric call,
+    made exactly as without the keywords -- or the icp_sdf_color_options of the photometric one."""
+    weight, huber = float(kw.pop("color_weight", 0.0)), float(kw.pop("color_huber", 0.0))
+    if not (np.isfinite(weight) and weight >= 0.0 and np.isfinite(huber) and huber >= 0.0):
+        raise ValueError("color_weight and color_huber must be finite and >= 0")
+    return IcpSdfColorOptions(weight, huber) if weight > 0.0 else None
+
+
+def _photometric(colored):
+    """Gives a method the keywords color_weight and color_huber: a weight of zero (the default) calls it as it is; a positive one calls
+    `colored(self, colour options, ...)` with the method's own arguments.  The method's own signature stays what it was."""
+    def give(plain):
+        @functools.wraps(plain)
+        def method(self, *args, **kw):
+            copt = _color_term(kw)
+            return plain(self, *args, **kw) if copt is None else colored(self, copt, *args, **kw)
+        return method
+    return give
+
+
+def _tsdf_cloud_system_color(self, copt, which="source", pose=None, huber=0.0):
+    w = _cloud(which)
+    p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
+    o = sdf_options(huber=huber)
+    sums = np.empty(29, np.float64); cnt = (C.c_int32 * 3)()
+    self._ck(self.lib.icp_tsdf_cloud_system_color(self.h, C.c_int32(w), _ptr(p), C.byref(o), C.byref(copt), _ptr(sums), cnt))
+    return sums, (cnt[0], cnt[1], cnt[2])
+
+
+def _tsdf_align_cloud_color(self, copt, which="source", pose=None, n_iterations=20, huber=0.0, min_valid=64, stop_rotation=1e-5, stop_translation=1e-5, trace=False):
+    w = _cloud(which)
+    p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
+    o = sdf_options(n_iterations=n_iterations, huber=huber, min_valid=min_valid, stop_rotation=stop_rotation, stop_translation=stop_translation)
+    rec = IcpSdfColorFrame(); tr = (IcpSdfColorIter * o.n_iterations)() if trace else None
+    rc = self.lib.icp_tsdf_align_cloud_color(self.h, C.c_int32(w), C.byref(o), C.byref(copt), _ptr(p), C.byref(rec), tr)
+    if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # the alignment's outcome: reported in the record
+        self._ck(rc)
+    r = _record(rec)
+    if trace:
+        return pose_from_c(p), r, rc, [_record(tr[i]) for i in range(r["iterations"])]
+    return pose_from_c(p), r, rc
+
+
 def _cloud_fuse_in(which, pose, sensor_origin):
     w = _cloud(which)
     p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
@@ -373,7 +417,11 @@ def _scans_in(scans):
 
 
 def _track_scans_sdf(self, colors, scans, pose=None, **options):
-    """Context.track_scans_sdf behind its docstring; colors: None, or one (n, 4) uint8 array per scan (icp_track_scans_sdf_color)."""
+    """Context.track_scans_sdf behind its docstring; colors: None, or one (n, 4) uint8 array per scan (icp_track_scans_sdf_color, or with
+    color_weight > 0 among the options icp_track_scans_sdf_photometric)."""
+    copt = _color_term(options)
+    if copt is not None and colors is None:
+        raise ValueError("color_weight > 0 needs colors: one rgba array per scan")
     o = sdf_options(**options)
     ns = len(scans)
     pts = _scans_in(scans)
@@ -381,7 +429,7 @@ def _track_scans_sdf(self, colors, scans, pose=None, **options):
     cnt = (C.c_int32 * max(ns, 1))(*[len(a) for a in pts])
     p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
     start = pose_from_c(p)
-    out = (IcpSdfFrame * max(ns - 1, 1))(); infos = (IcpTsdfCloudInfo * max(ns, 1))()
+    out = ((IcpSdfFrame if copt is None else IcpSdfColorFrame) * max(ns - 1, 1))(); infos = (IcpTsdfCloudInfo * max(ns, 1))()
     if colors is None:
         rc = self.lib.icp_track_scans_sdf(self.h, xp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out, infos)
     else:
@@ -392,7 +440,10 @@ def _track_scans_sdf(self, colors, scans, pose=None, **options):
             raise ValueError("a scan's colours are rgba (n, 4) bytes, one row per point")
         cp = (C.c_void_p * max(ns, 1))(*[_ptr(c) for c in cols])
         ncol = (C.c_int32 * max(ns, 1))()
-        rc = self.lib.icp_track_scans_sdf_color(self.h, xp, cp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out, infos, ncol)
+        if copt is None:
+            rc = self.lib.icp_track_scans_sdf_color(self.h, xp, cp, cnt, C.c_int32(ns), C.byref(o), _ptr(p), out, infos, ncol)
+        else:
+            rc = self.lib.icp_track_scans_sdf_photometric(self.h, xp, cp, cnt, C.c_int32(ns), C.byref(o), C.byref(copt), _ptr(p), out, infos, ncol)
     if rc not in (ICP_OK, ERR_NO_SOURCE, ERR_NO_CORRESPONDENCES):     # per-scan outcomes: reported in the records
         self._ck(rc)
     recs = [_record(out[i]) for i in range(ns - 1)]
@@ -607,6 +658,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_tsdf_mesh_hashed", "icp_tsdf_raycast_hashed", "icp_set_target_tsdf_hashed", "icp_track_depth_model_hashed",
            "icp_tsdf_evict_blocks", "icp_tsdf_evicted_blocks", "icp_tsdf_insert_blocks", "icp_tsdf_integrate_cloud",
            "icp_tsdf_cloud_system", "icp_tsdf_align_cloud", "icp_track_scans_sdf", "icp_tsdf_integrate_cloud_color", "icp_track_scans_sdf_color",
+           "icp_tsdf_cloud_system_color", "icp_tsdf_align_cloud_color", "icp_track_scans_sdf_photometric",
            "icp_tsdf_create_color_hashed", "icp_tsdf_hashed_has_color", "icp_get_tsdf_color_hashed", "icp_tsdf_upload_color_hashed",
            "icp_tsdf_evicted_blocks_color", "icp_tsdf_insert_blocks_color",
            "icp_tsdf_raycast_color_hashed", "icp_set_target_tsdf_color_hashed", "icp_track_depth_model_color_hashed", "icp_tsdf_mesh_color_hashed",
@@ -1400,10 +1452,14 @@ class Context:
         self._ck(self.lib.icp_tsdf_carve_stats(self.h, C.byref(o)))
         return dict(n_steps=o.n_steps, n_carved=o.n_carved, n_carved_total=o.n_carved_total)
 
+    @_photometric(_tsdf_cloud_system_color)
     def tsdf_cloud_system(self, which="source", pose=None, huber=0.0):
         """icp_tsdf_cloud_system: the 28 sums of one direct SDF step of the resident target ("target" / 0) or source ("source" / 1) -- an
         unorganised cloud in its sensor frame -- at `pose` (4x4 scan frame -> world; None: the identity) against the volume, dense or
-        hashed.  Returns (sums (28,) float64, (considered, valid))."""
+        hashed.  Returns (sums (28,) float64, (considered, valid)).
+        color_weight, color_huber (keyword only, 0.0 each): a positive weight, in metres per unit of intensity, adds the photometric row
+        of a coloured cloud against a coloured volume (icp_tsdf_cloud_system_color); the return is then
+        (sums (29,), (considered, valid, colored)).  A weight of zero changes nothing."""
         w = _cloud(which)
         p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
         o = sdf_options(huber=huber)
@@ -1411,12 +1467,15 @@ class Context:
         self._ck(self.lib.icp_tsdf_cloud_system(self.h, C.c_int32(w), _ptr(p), C.byref(o), _ptr(sums), cnt))
         return sums, (cnt[0], cnt[1])
 
+    @_photometric(_tsdf_align_cloud_color)
     def tsdf_align_cloud(self, which="source", pose=None, n_iterations=20, huber=0.0, min_valid=64, stop_rotation=1e-5, stop_translation=1e-5, trace=False):
         """icp_tsdf_align_cloud: the resident cloud aligned to the volume itself from `pose` (identity by default): no target cloud, no
         index, no search.  The field exists only inside the truncation band around the fused surfaces: a point that starts further
         than the truncation from all of them takes no part (the basin).  `tsdf_align_depth`'s returns: (pose, record, status), with trace=True (pose, record,
         status, the records of the iterations that ran); a failed alignment (status NO_SOURCE or NO_CORRESPONDENCES) returns the pose it
-        started with."""
+        started with.  color_weight, color_huber (keyword only, 0.0 each): a positive weight aligns a coloured cloud to a coloured volume
+        with the photometric term (icp_tsdf_align_cloud_color, DESIGN.md section 6zj: what pins a scan of a flat textured wall); the
+        records are then the colour records.  A weight of zero changes nothing."""
         w = _cloud(which)
         p = _pose_in(np.eye(4, dtype=np.float32) if pose is None else pose)
         o = sdf_options(n_iterations=n_iterations, huber=huber, min_valid=min_valid, stop_rotation=stop_rotation, stop_translation=stop_translation)
@@ -1438,7 +1497,9 @@ class Context:
         the records of scans 1 .., the fuse info of every scan -- all zero for a skipped one --, status: the first per-scan error, or 0).
         colors (keyword only): one rgba (n, 4) uint8 array per scan -- icp_track_scans_sdf_color on a coloured volume: every scan goes up
         with its colours and every fuse is the coloured one; poses, records and infos are the uncoloured loop's,
-        and the tuple gains a fifth value, n_colored of every scan (0 for a skipped one)."""
+        and the tuple gains a fifth value, n_colored of every scan (0 for a skipped one).  color_weight, color_huber (among **options,
+        0.0 each): with colors, a positive weight makes every alignment the photometric one (icp_track_scans_sdf_photometric, DESIGN.md
+        section 6zj) and the records the colour records; without colors it raises ValueError.  A weight of zero changes nothing."""
         return _track_scans_sdf(self, None, scans, pose, **options)
 
     def tsdf_raycast(self, cam, pose):

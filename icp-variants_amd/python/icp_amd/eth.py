@@ -218,6 +218,8 @@ def _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity,
 def _track_tsdf(ctx, colors, scans, start_pose, voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, hashed=True, dims=None,
                 **sdf_options):
     """track_tsdf behind its docstring; colors: None, or one rgba array per scan."""
+    if float(sdf_options.get("color_weight", 0.0)) > 0.0 and colors is None:
+        raise ValueError("color_weight > 0 needs colors: one rgba array per scan")
     cols = None if colors is None else _scan_colors(scans, colors)
     _tsdf_volume(ctx, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims, color=cols is not None)
     if cols is None:
@@ -240,7 +242,9 @@ def track_tsdf(ctx, scans, start_pose, voxel_size=0.05, truncation=None, origin=
     one per scan after the first, infos: the fuse info of every scan, status: the first per-scan error, or 0).  colors (keyword only): one
     rgba (n, 4) uint8 array per scan -- the volume is created with colours, every scan goes up with its colours and every fuse is the
     coloured one (Context.track_scans_sdf(colors=...)); poses, records and infos are what they are without, and a
-    fifth value is returned, n_colored of every scan; None changes nothing.  The volume stays in the
+    fifth value is returned, n_colored of every scan; None changes nothing.  color_weight, color_huber (among **sdf_options): with colors,
+    a positive weight aligns every scan with the photometric term as well (Context.track_scans_sdf(colors=..., color_weight=...), DESIGN.md
+    section 6zj) and the records are the colour records; without colors it raises ValueError.  The volume stays in the
     context (Context.tsdf_sample, Context.tsdf_mesh_hashed, Context.tsdf_blocks)."""
     return _track_tsdf(ctx, None, scans, start_pose, voxel_size, truncation, origin, max_range, block_capacity, hashed, dims, **sdf_options)
 
@@ -251,6 +255,11 @@ def _reconstruct(ctx, colors, scans, start_pose, tsdf_voxel_size=0.05, truncatio
     from . import meshio
     if tracker not in ("map", "sdf"):
         raise ValueError("tracker must be 'map' or 'sdf'")
+    if float(track_map_options.get("color_weight", 0.0)) > 0.0:
+        if tracker != "sdf":
+            raise ValueError("color_weight > 0 needs tracker='sdf' (the voxel-map tracker has no photometric term)")
+        if colors is None:
+            raise ValueError("color_weight > 0 needs colors: one rgba array per scan")
     coloured = {} if colors is None else dict(colors=colors)
     if tracker == "sdf":
         poses, records, _, status = track_tsdf(ctx, scans, start_pose, voxel_size=tsdf_voxel_size, truncation=truncation, origin=origin, max_range=max_range,
@@ -284,7 +293,8 @@ def reconstruct(ctx, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, o
     takes it -- the fuses of either tracker carve free space for the call; None changes nothing.  colors (keyword only): one rgba (n, 4)
     uint8 array per scan -- the model is fused with the scans' colours, meshed with
     Context.tsdf_mesh_hashed(colors=True), written with meshio.write_ply_mesh(..., colors=...), and the mesh returned is (vertices,
-    normals, triangles, colours (V, 4) uint8: alpha 255 on a coloured vertex); None changes nothing."""
+    normals, triangles, colours (V, 4) uint8: alpha 255 on a coloured vertex); None changes nothing.  color_weight (among the options):
+    with tracker="sdf" and colors, the photometric tracker of track_tsdf; with tracker="map" or without colors it raises ValueError."""
     return _reconstruct(ctx, None, scans, start_pose, tsdf_voxel_size, truncation, origin, max_range, block_capacity, min_weight, mesh_path, tracker, **track_map_options)
 
 

@@ -1661,6 +1661,43 @@ int icp_track_scans_sdf_color(icp_ctx* ctx, const float* const* xyz, const uint8
                               const icp_sdf_options* opt, float pose_inout[16], icp_sdf_frame* out, icp_tsdf_cloud_info* infos_out,
                               int32_t* n_colored_out);
 
+/* -------- a coloured laser scan aligned to the coloured TSDF volume with a photometric term --------
+ * icp_tsdf_align_cloud with the second row of icp_tsdf_align_depth_color: where the geometry leaves the pose free (a scan of a flat wall or
+ * of a floor) the calls above do not move at all; the colours that icp_tsdf_integrate_cloud_color put into the volume pin the scan.  Needs a
+ * volume WITH colours, dense (icp_tsdf_color_create) or hashed (icp_tsdf_create_color_hashed), and a resident cloud WITH colours
+ * (icp_set_target / icp_set_source with rgba).  tests/sdf_cloud_color_restatement.py restates what follows.
+ *
+ * Contract (fp32, one rounding per operation, in the order written; everything after a conversion to fp64 is fp64).
+ *   Geometric row: considered and valid points, q, the cell, F, G, r, g, J and w are exactly icp_tsdf_cloud_system's.  A point that is not
+ *   valid there contributes nothing here either.
+ *   Photometric row: icp_tsdf_sdf_system_color's, word for word, with two substitutions -- the moved point q in place of the back-projected
+ *   pixel, and the point's own colour, the first three bytes R, G, B of its rgba, in place of the pixel's; the fourth byte is not read.
+ *   s_k = (R_k + G_k) + B_k at the eight colour corners of q's cell, S and H as there; a valid point is COLOURED iff all eight corners
+ *   have Wc > 0 and S is finite; I_p = (double)(R + G + B) / 765.0; r_c = (double)S / 765.0 - I_p; h = (double)H / (765.0 *
+ *   (double)voxel_size); J_c = (q x h, h); w_c = weight^2, with huber > 0 multiplied by (|r_c| <= huber ? 1 : huber / |r_c|).
+ *   Sums: 29 doubles in icp_tsdf_sdf_system_color's layout.  A coloured point's term is the geometric term + the photometric term in that
+ *   order, a valid point that is not coloured contributes the geometric term alone; entry 28 is (w_c r_c) r_c alone.  Counts: {n_depth,
+ *   n_valid, n_color}.  The fold order is fixed, without floating-point atomics: bitwise reproducible run to run, and each sum within
+ *   n_valid 2^-52 sum |term| of any other summation order of the same terms, the order of the upload included.
+ *   Step, stop, failure, statuses and pose composition: icp_tsdf_align_cloud's, unchanged, on the entries 0 .. 26.
+ * Refusals, all before any device work and with a message that names the call: everything icp_tsdf_cloud_system refuses, in its order;
+ * then bad colour options (icp_sdf_color_options_check; a weight of zero belongs to the calls above), a volume without colours, a cloud
+ * without colours, a null output -- ICP_ERR_INVALID_ARG each. */
+/* The sums of ONE joint step at `pose`: sums_out 29 doubles, counts_out {n_depth, n_valid, n_color}; of opt only huber matters. */
+int icp_tsdf_cloud_system_color(icp_ctx* ctx, int32_t which, const float pose[16], const icp_sdf_options* opt,
+                                const icp_sdf_color_options* copt, double* sums_out, int32_t* counts_out);
+/* icp_tsdf_align_cloud with the photometric term: the same outputs in the colour records, the same statuses, one host read. */
+int icp_tsdf_align_cloud_color(icp_ctx* ctx, int32_t which, const icp_sdf_options* opt, const icp_sdf_color_options* copt,
+                               float pose_inout[16], icp_sdf_color_frame* rec_out, icp_sdf_color_iter* trace_out);
+/* icp_track_scans_sdf_color with the photometric alignment: every scan goes up with its colours, scan k >= 1 is aligned by
+ * icp_tsdf_align_cloud_color's rule to the volume built so far and, on ICP_OK, fused by icp_tsdf_integrate_cloud_color at the pose found;
+ * out: n_scans - 1 colour records.  infos_out, n_colored_out, the carve options, the host waits per scan and the handling of a failed scan
+ * are icp_track_scans_sdf_color's.  Refused as that call is (a volume without colours, a null rgba or rgba[k], a scan of more than 2^24
+ * points among the reasons), and on bad colour options. */
+int icp_track_scans_sdf_photometric(icp_ctx* ctx, const float* const* xyz, const uint8_t* const* rgba, const int32_t* n, int32_t n_scans,
+                                    const icp_sdf_options* opt, const icp_sdf_color_options* copt, float pose_inout[16],
+                                    icp_sdf_color_frame* out, icp_tsdf_cloud_info* infos_out, int32_t* n_colored_out);
+
 /* -------- batches of independent scan pairs: the loop over ETH indices, main.cpp:411-498 / experiment.cpp:319-396 --------
  * The reference aligns the pairs one after the other and carries no state between them, so a batch shards with no
  * data-path exchange: pair p belongs to rank p % n_ranks (icp_pair_owner), and the only collective is ONE gather of the
