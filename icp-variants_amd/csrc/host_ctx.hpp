@@ -1,6 +1,6 @@
 // host_ctx.hpp -- the context behind the C ABI (icp_ctx) and what every entry point leans on: device buffers, the resident clouds, levels
 // and trees as host-side records, page-locked staging, cloud uploads, the finite filter and compaction, the pose upload, readiness checks.
-// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_tsdf_hash, host_tsdf_hash_raycast, host_sdf, host_vgicp, host_hmap, host_vmap, host_vmap_prune, host_sdf_color, host_tsdf_mesh, host_tsdf_hash_mesh, host_tsdf_hash_evict, host_tsdf_cloud, host_sdf_cloud, host_global, host_debug.
+// Part of icp_hip.hip (included from there, first); the pieces after it are host_index, host_launch, host_loop, host_multi, host_depth, host_tsdf, host_tsdf_hash, host_tsdf_hash_raycast, host_sdf, host_vgicp, host_hmap, host_vmap, host_vmap_prune, host_sdf_color, host_tsdf_mesh, host_tsdf_hash_mesh, host_mesh_cluster, host_tsdf_hash_evict, host_tsdf_cloud, host_sdf_cloud, host_global, host_debug.
 using namespace icpdev;
 
 #define HIPCK(ctx, expr)                                                                        \
@@ -165,7 +165,8 @@ struct icp_ctx {
     icp_tsdf_carve_options tcv_opt = {0.f, 0.f}; icp_tsdf_carve_info tcv_info = {0, 0, 0, 0};   // free-space carving of the cloud integrate (icp_set_tsdf_carve_options, host_tsdf_cloud.hpp): the options, which outlive clouds, volumes and resets, and the stats of the last cloud fuse
     DevBuf tm_bits, tm_mask, tm_base, tm_blk, tm_out;   // icp_tsdf_mesh (host_tsdf_mesh.hpp): the three bitmaps, the edge-mask bytes, the run bases, the block tables + totals, the staged mesh
     DevBuf tm_nbr, tm_ord;               // icp_tsdf_mesh_hashed (host_tsdf_hash_mesh.hpp), which also uses the five above: the 27 neighbour ranks of every block; order[rank] -> pool index, then rank_of[pool index]
-    DevBuf sdf_state, sdf_partials, sdf_rec; Event sdf_ev;   // direct SDF tracking (host_sdf.hpp's driver, for the record kinds SdfGeo and SdfColor, and host_vgicp.hpp through it): the kind's pose / stop state, partials[NSUM][blocks] + counts[NCOUNT][blocks] (28 + 2 or 29 + 3), the frame record + trace; they only grow, every call writes them before it reads them; "the last integration has left its upload slot"
+    DevBuf mc_tab, mc_vtx, mc_tri, mc_acc, mc_in, mc_out; bool mc_combine = true;   // vertex clustering (host_mesh_cluster.hpp): the cell table [keys | first members | referenced flag, then rank + 1]; per vertex its slot and per rank the cluster's slot, the leader block table, the counters; per triangle the canonical triple and its slot, the triangle table, the survivor block table; the accumulators by rank; the uploaded input of icp_mesh_cluster; the staged clustered mesh; the accumulate combines neighbouring lanes
+    DevBuf sdf_state, sdf_partials, sdf_rec; Event sdf_ev;  // direct SDF tracking (host_sdf.hpp's driver, for the record kinds SdfGeo and SdfColor, and host_vgicp.hpp through it): the kind's pose / stop state, partials[NSUM][blocks] + counts[NCOUNT][blocks] (28 + 2 or 29 + 3), the frame record + trace; they only grow, every call writes them before it reads them; "the last integration has left its upload slot"
     DevBuf vg_box, vg_count, vg_sums, vg_cells;   // voxelized GICP (host_vgicp.hpp): the target's voxel grid -- bounds + counters, per cell the count, the nine int64 sums, the 40-byte record
     bool vg_ready = false; float vg_voxel = 0.f; icp_voxel_grid_info vg_info = {{0, 0, 0}, {0, 0, 0}, 0, 0};   // the grid is current for vg_voxel (dropped with the target's GICP normal cache); its extent
     DevBuf vm_count, vm_sums, vm_cells, vm_stamp, vm_list, vm_ctr, vm_box;   // the voxel map (host_vmap.hpp): per cell the count, the nine int64 sums, the 40-byte record and the stamp of the last insert that touched it; the list of the cells an insert touched, the counters, the scratch counters of a full sweep

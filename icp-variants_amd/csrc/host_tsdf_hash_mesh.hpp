@@ -85,7 +85,7 @@ int htm_enqueue_colors(icp_ctx* c, int n, const HtmScratch& s, uint32_t* d_col) 
 }
 // Both mesh calls.  color (icp_tsdf_mesh_color_hashed): needs the colour pool; colors_out (optional) receives one packed colour per vertex.
 int htsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out, bool color,
-               uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, const std::string& who) {
+               uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, const std::string& who, const McCall* cluster = nullptr) {
     if (n_vertices_out) *n_vertices_out = 0;
     if (n_triangles_out) *n_triangles_out = 0;
     int rc;
@@ -108,7 +108,7 @@ int htsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_t
     if ((rc = htm_enqueue_count(c, n, s, min_weight))) return rc;
     return tm_finish(c, guard, s.tot, max_vertices, max_triangles, vertices_out, normals_out, colors_out, triangles_out, n_vertices_out, n_triangles_out, count_only, who,
                      [&](float* d_vert, float* d_nrm, uint32_t* d_tris) { return htm_enqueue_fill(c, n, s, d_vert, d_nrm, d_tris); },
-                     [&](uint32_t* d_col) { return htm_enqueue_colors(c, n, s, d_col); });
+                     [&](uint32_t* d_col) { return htm_enqueue_colors(c, n, s, d_col); }, cluster);
 }
 }  // namespace
 

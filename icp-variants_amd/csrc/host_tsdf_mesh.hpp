@@ -1,7 +1,8 @@
 // host_tsdf_mesh.hpp -- icp_tsdf_mesh: the zero level set of the context's TSDF volume as an indexed triangle mesh, extracted on the device;
 // only the mesh crosses to the host; icp_tsdf_mesh_color: the same mesh with a colour per vertex from the volume's colour array.
 // Kernels: dev_tsdf_mesh.hpp, dev_tsdf_mesh_color.hpp; contract: include/icp_hip.h, DESIGN.md sections 6n and 6p.
-// tm_finish, the tail both storages' mesh calls share from the totals on, lives here (host_tsdf_hash_mesh.hpp passes its own passes in).
+// tm_finish, the tail both storages' mesh calls share from the totals on, lives here (host_tsdf_hash_mesh.hpp passes its own passes in);
+// tm_stage is its seam between the mesh filled on the device and the copy back, where icp_tsdf_mesh_clustered takes the mesh over.
 // Part of icp_hip.hip (included from there, after host_tsdf.hpp).
 namespace {
 TmDiv tm_make_div(uint32_t d) {
@@ -62,17 +63,44 @@ int tm_check_call(icp_ctx* c, float min_weight, const char* who) {
     if (tsdf_voxels(c) > (size_t)(INT32_MAX / 12)) { c->err = std::string(who) + ": the volume has more than INT32_MAX / 12 voxels"; return ICP_ERR_INVALID_ARG; }
     return ICP_OK;
 }
+// The seam between "filled on the device" and "copied back": a mesh of the counted sizes staged in tm_out, [vertices 12 V | normals 12 V |
+// triangles 12 T | colours 4 V], with fill(d_vert, d_nrm, d_tris) and -- when colours are asked for -- colors(d_col) enqueued.
+struct TmStaged { float* d_vert; float* d_nrm; uint32_t* d_tris; uint32_t* d_col; size_t bv, bn, bt, bc; };
+template <class Fill, class Colors>
+int tm_stage(icp_ctx* c, int nv, int nt, bool with_normals, bool with_colors, TmStaged& m, Fill&& fill, Colors&& colors) {
+    int rc;
+    m.bv = (size_t)nv * 12; m.bn = with_normals ? m.bv : 0; m.bt = (size_t)nt * 12; m.bc = with_colors ? (size_t)nv * 4 : 0;
+    if ((rc = ensure(c, c->tm_out, m.bv + m.bn + m.bt + m.bc))) return rc;
+    char* d = c->tm_out.as<char>();
+    m.d_vert = (float*)d; m.d_nrm = with_normals ? (float*)(d + m.bv) : nullptr; m.d_tris = (uint32_t*)(d + m.bv + m.bn);
+    m.d_col = (uint32_t*)(d + m.bv + m.bn + m.bt);
+    if ((rc = fill(m.d_vert, m.d_nrm, m.d_tris))) return rc;
+    if (with_colors && nv > 0 && (rc = colors(m.d_col))) return rc;
+    return ICP_OK;
+}
+// The clustered tail (host_mesh_cluster.hpp, icp_tsdf_mesh_clustered): what a mesh call hands the staged mesh to instead of copying it back.
+struct McCall;
+int mc_finish_staged(icp_ctx* c, DrainOnError& guard, const McCall& k, int nv, int nt, const TmStaged* m);
+bool mc_wants_normals(const McCall& k);
+bool mc_wants_colors(const McCall& k);
 // What both storages' mesh calls do once the counting passes are enqueued: the two totals back in one copy, the counts reported and
-// checked against the arrays, the outputs staged in tm_out, fill(d_vert, d_nrm, d_tris) and -- when colours are asked for --
-// colors(d_col) enqueued, the arrays copied back, the stream waited for.
+// checked against the arrays, the outputs staged (tm_stage), the arrays copied back, the stream waited for.  cluster: the staged mesh
+// goes to mc_finish_staged where it lies, and the counts, the capacities and the arrays are that call's.
 template <class Fill, class Colors>
 int tm_finish(icp_ctx* c, DrainOnError& guard, const int* d_tot, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out,
-              uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, bool count_only, const std::string& who, Fill&& fill, Colors&& colors) {
+              uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, bool count_only, const std::string& who, Fill&& fill, Colors&& colors,
+              const McCall* cluster = nullptr) {
     int rc;
     int tot[2] = {0, 0};                                 // both totals back in one copy
     if ((rc = read_count(c, d_tot, tot, 2))) return rc;
     const int nv = tot[0], nt = tot[1];
     if (nv < 0 || nt < 0) { c->err = who + ": count out of range"; return ICP_ERR_HIP; }
+    TmStaged m;
+    if (cluster) {
+        if (nv == 0 && nt == 0) return mc_finish_staged(c, guard, *cluster, 0, 0, nullptr);
+        if ((rc = tm_stage(c, nv, nt, mc_wants_normals(*cluster), mc_wants_colors(*cluster), m, fill, colors))) return rc;
+        return mc_finish_staged(c, guard, *cluster, nv, nt, &m);
+    }
     *n_vertices_out = nv; *n_triangles_out = nt;
     if (count_only) return guard.done();
     if (nv > max_vertices || nt > max_triangles) {
@@ -82,26 +110,17 @@ int tm_finish(icp_ctx* c, DrainOnError& guard, const int* d_tot, int32_t max_ver
         return guard.done(ICP_ERR_INVALID_ARG);      // (synchronised by the count read)
     }
     if (nv == 0 && nt == 0) return guard.done();
-    // the outputs staged in device arrays of exactly the counted size: [vertices 12 V | normals 12 V | triangles 12 T | colours 4 V]
-    const size_t bv = (size_t)nv * 12, bn = normals_out ? bv : 0, bt = (size_t)nt * 12, bc = colors_out ? (size_t)nv * 4 : 0;
-    if ((rc = ensure(c, c->tm_out, bv + bn + bt + bc))) return rc;
-    char* d = c->tm_out.as<char>();
-    float* d_vert = (float*)d; float* d_nrm = normals_out ? (float*)(d + bv) : nullptr; uint32_t* d_tris = (uint32_t*)(d + bv + bn);
-    uint32_t* d_col = (uint32_t*)(d + bv + bn + bt);
-    if ((rc = fill(d_vert, d_nrm, d_tris))) return rc;
-    if (colors_out && nv > 0) {
-        if ((rc = colors(d_col))) return rc;
-        HIPCK(c, hipMemcpyAsync(colors_out, d_col, bc, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (nv > 0) HIPCK(c, hipMemcpyAsync(vertices_out, d_vert, bv, hipMemcpyDeviceToHost, c->stream));
-    if (nv > 0 && normals_out) HIPCK(c, hipMemcpyAsync(normals_out, d_nrm, bn, hipMemcpyDeviceToHost, c->stream));
-    if (nt > 0) HIPCK(c, hipMemcpyAsync(triangles_out, d_tris, bt, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = tm_stage(c, nv, nt, normals_out != nullptr, colors_out != nullptr, m, fill, colors))) return rc;
+    if (colors_out && nv > 0) HIPCK(c, hipMemcpyAsync(colors_out, m.d_col, m.bc, hipMemcpyDeviceToHost, c->stream));
+    if (nv > 0) HIPCK(c, hipMemcpyAsync(vertices_out, m.d_vert, m.bv, hipMemcpyDeviceToHost, c->stream));
+    if (nv > 0 && normals_out) HIPCK(c, hipMemcpyAsync(normals_out, m.d_nrm, m.bn, hipMemcpyDeviceToHost, c->stream));
+    if (nt > 0) HIPCK(c, hipMemcpyAsync(triangles_out, m.d_tris, m.bt, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return guard.done();
 }
 // Both mesh calls.  color (icp_tsdf_mesh_color): needs the colour array; colors_out (optional) receives one packed colour per vertex.
 int tsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out, bool color,
-              uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, const std::string& who) {
+              uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, const std::string& who, const McCall* cluster = nullptr) {
     if (n_vertices_out) *n_vertices_out = 0;
     if (n_triangles_out) *n_triangles_out = 0;
     int rc;
@@ -126,7 +145,8 @@ int tsdf_mesh(icp_ctx* c, float min_weight, int32_t max_vertices, int32_t max_tr
                                             (const int*)s.vblk, d_col);
                          HIPCK(c, hipGetLastError());
                          return ICP_OK;
-                     });
+                     },
+                     cluster);
 }
 }  // namespace
 

@@ -93,6 +93,8 @@
 //   k_*sdf_accumulate_cloud_color  the same for a coloured scan with a photometric row per coloured point (icp_tsdf_align_cloud_color,
 //                       icp_track_scans_sdf_photometric): the point's own colour against the intensity field of its cell; k_sdf_solve_color
 //                       behind them (dev_sdf_cloud_color.hpp)
+//   k_mc_*              vertex clustering of a triangle mesh (icp_mesh_cluster, icp_tsdf_mesh_clustered): the vertices of a grid cell become one,
+//                       found through a hash table of cells, equal triangles through a second table; integer sums by rank (dev_mesh_cluster.hpp)
 //   k_lm_eval /         CeresICPOptimizer (ICPOptimizer.h:181-483): residuals + Jacobian sums of constraints.h at a point, and the
 //   k_lm_step           Levenberg-Marquardt trust-region logic of one ceres::Solve per ICP iteration (dev_lm.hpp)
 // =====================================================================================
@@ -147,5 +149,6 @@ namespace icpdev {
 #include "dev_tsdf_cloud_color.hpp"
 #include "dev_sdf_cloud.hpp"
 #include "dev_sdf_cloud_color.hpp"
+#include "dev_mesh_cluster.hpp"
 
 }  // namespace icpdev

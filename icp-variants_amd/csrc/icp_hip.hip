@@ -43,6 +43,7 @@
 #include "host_sdf_color.hpp"
 #include "host_tsdf_mesh.hpp"
 #include "host_tsdf_hash_mesh.hpp"
+#include "host_mesh_cluster.hpp"
 #include "host_tsdf_hash_evict.hpp"
 #include "host_tsdf_cloud.hpp"
 #include "host_sdf_cloud.hpp"

@@ -347,6 +347,23 @@ def _colouring(name, colored):
     return give
 
 
+def _clustering(*names):
+    """Gives a mesh method the keywords `cluster` (a cell size in metres) and `cluster_origin`: cluster=None (the default) calls it as it
+    is; otherwise icp_tsdf_mesh_clustered returns the same tuple with the mesh clustered on the device, the grid's
+    origin at cluster_origin (the volume's by default).  names: the method's parameters after min_weight (`normals`, where there is one,
+    and `colors`).  The method's own signature stays what it was."""
+    def give(plain):
+        @functools.wraps(plain)
+        def method(self, min_weight=0.0, *args, **kw):
+            cluster, origin = kw.pop("cluster", None), kw.pop("cluster_origin", None)
+            if cluster is None:
+                return plain(self, min_weight, *args, **kw)
+            par = dict(zip(names, args), **kw)
+            return self._tsdf_mesh_clustered(min_weight, bool(par.get("normals", True)), bool(par.get("colors", False)), cluster, origin)
+        return method
+    return give
+
+
 def _color_term(kw):
     """Takes color_weight and color_huber (0.0 each by default) out of a keyword dict: None for a weight of zero -- the geometric call,
     made exactly as without the keywords -- or the icp_sdf_color_options of the photometric one."""
@@ -641,6 +658,26 @@ def depth_options(keep_original_size=False, downsample_factor=1, max_distance=0.
     return IcpDepthOptions(int(bool(keep_original_size)), int(downsample_factor), float(max_distance), int(bool(fix_color_index)))
 
 
+class IcpMeshClusterOptions(C.Structure):
+    _fields_ = [("cell_size", C.c_float), ("origin", C.c_float * 3)]
+
+
+class IcpMeshClusterInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_vertices_in", "n_triangles_in", "n_invalid_vertices", "n_invalid_triangles", "n_cells", "n_vertices", "n_triangles",
+                                         "n_degenerate", "n_duplicate")]
+
+
+MESH_CLUSTER_MAX = 1 << 27
+
+
+def mesh_cluster_options(cell_size, origin=(0.0, 0.0, 0.0)):
+    """icp_mesh_cluster_options: the cell size (metres) and the grid's origin (a corner of cell (0, 0, 0))."""
+    o = IcpMeshClusterOptions()
+    o.cell_size = float(cell_size)
+    o.origin[:] = [float(x) for x in origin]
+    return o
+
+
 COMM_ID_BYTES = 128
 
 # every symbol include/icp_hip.h declares (tests check the library exports all of them)
@@ -681,6 +718,7 @@ EXPORTS = ["icp_ctx_create", "icp_ctx_create_on_stream", "icp_ctx_destroy", "icp
            "icp_nss_options_default", "icp_set_nss_options", "icp_get_nss_options", "icp_get_normal_buckets", "icp_get_selection",
            "icp_global_options_default", "icp_set_global_options", "icp_get_global_options", "icp_compute_features", "icp_get_features", "icp_get_spfh",
            "icp_get_feature_neighbours", "icp_match_features", "icp_register_global", "icp_get_global_hypotheses",
+           "icp_mesh_cluster", "icp_tsdf_mesh_clustered",
            "icp_batch_run", "icp_pair_owner", "icp_pairs_of_rank", "icp_comm_unique_id", "icp_comm_create", "icp_comm_destroy", "icp_gather_poses",
            "icp_comm_last_error"]
 
@@ -699,6 +737,12 @@ def load_library():
         _lib.icp_pair_owner.restype = C.c_int32
         _lib.icp_pairs_of_rank.restype = C.c_int32
         _lib.icp_select_hash.restype = C.c_uint32
+        i32, vp = C.c_int32, C.c_void_p
+        _lib.icp_mesh_cluster.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.POINTER(IcpMeshClusterOptions), i32, i32, vp, vp, vp, vp, C.POINTER(IcpMeshClusterInfo)]
+        _lib.icp_mesh_cluster.restype = i32
+        _lib.icp_tsdf_mesh_clustered.argtypes = [vp, C.c_float, C.POINTER(IcpMeshClusterOptions), i32, i32, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32),
+                                                 C.POINTER(IcpMeshClusterInfo)]
+        _lib.icp_tsdf_mesh_clustered.restype = i32
     return _lib
 
 
@@ -1228,6 +1272,7 @@ class Context:
         o = options if options is not None else tsdf_options(**kw)
         self._ck(self.lib.icp_tsdf_create(self.h, C.byref(o)))
         self._tsdf_dims = tuple(o.dims)
+        self._tsdf_origin = tuple(o.origin)
         if color:
             self.tsdf_color_create()
 
@@ -1242,6 +1287,7 @@ class Context:
         create = self.lib.icp_tsdf_create_color_hashed if color else self.lib.icp_tsdf_create_hashed
         self._ck(create(self.h, C.byref(o), C.c_int32(block_capacity)))
         self._tsdf_dims = None
+        self._tsdf_origin = tuple(o.origin)
         self.tsdf_hashed_options = o
 
     def tsdf_has_color(self):
@@ -1519,11 +1565,55 @@ class Context:
         self._ck(self.lib.icp_tsdf_raycast_color(self.h, C.byref(cam), _ptr(pose_to_c(pose)), _ptr(d), _ptr(v), _ptr(nr), _ptr(rgba), C.byref(hits), C.byref(ncol)))
         return d, v, nr, rgba, hits.value, ncol.value
 
+    def mesh_cluster(self, vertices, triangles, cell_size, normals=None, colors=None, origin=(0, 0, 0)):
+        """icp_mesh_cluster: vertex clustering of an indexed triangle mesh on the device: the vertices of one cell of
+        a grid of `cell_size` with a corner at `origin` become one vertex, triangles that lose a corner are dropped, equal ones kept once.
+        vertices (V, 3) f32, triangles (T, 3) u32, normals (V, 3) f32 and colors (V, 4) u8 optional.  One call with capacities V and T,
+        then slices.  Returns (vertices, normals | None, colors | None, triangles, info dict)."""
+        v = _f32(vertices).reshape(-1, 3); t = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        n = None if normals is None else _f32(normals).reshape(-1, 3)
+        col = None if colors is None else np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 4)
+        if (n is not None and len(n) != len(v)) or (col is not None and len(col) != len(v)):
+            raise ValueError("normals and colors need one row per vertex")
+        ov = np.empty((len(v), 3), np.float32); ot = np.empty((len(t), 3), np.uint32)
+        on = None if n is None else np.empty((len(v), 3), np.float32); oc = None if col is None else np.empty((len(v), 4), np.uint8)
+        info = IcpMeshClusterInfo()
+        self._ck(self.lib.icp_mesh_cluster(self.h, len(v), len(t), _ptr(v), _ptr(n), _ptr(col), _ptr(t), C.byref(mesh_cluster_options(cell_size, origin)), len(v), len(t),
+                                           _ptr(ov), _ptr(on), _ptr(oc), _ptr(ot), C.byref(info)))
+        self._mc_info = _record(info)
+        nv, nt = info.n_vertices, info.n_triangles
+        return ov[:nv], None if on is None else on[:nv], None if oc is None else oc[:nv], ot[:nt], dict(self._mc_info)
+
+    def mesh_cluster_info(self):
+        """The info of the last clustering call on this context (`mesh_cluster`, or a mesh call with `cluster`), as a dict; None before one."""
+        info = getattr(self, "_mc_info", None)
+        return None if info is None else dict(info)
+
+    def _tsdf_mesh_clustered(self, min_weight, normals, colors, cluster, cluster_origin):
+        """icp_tsdf_mesh_clustered (a counting call, then a filling call): the tuple shape of `tsdf_mesh` / `tsdf_mesh_hashed`."""
+        origin = cluster_origin if cluster_origin is not None else (getattr(self, "_tsdf_origin", None) or (0.0, 0.0, 0.0))
+        opt = mesh_cluster_options(cluster, origin)
+        nv, nt, info = C.c_int32(0), C.c_int32(0), IcpMeshClusterInfo()
+
+        def call(v, n, col, t):
+            self._ck(self.lib.icp_tsdf_mesh_clustered(self.h, float(min_weight), C.byref(opt), int(bool(colors)), nv.value, nt.value, _ptr(v), _ptr(n), _ptr(col), _ptr(t),
+                                                      C.byref(nv), C.byref(nt), C.byref(info)))
+        call(None, None, None, None)
+        v = np.empty((nv.value, 3), np.float32); n = np.empty((nv.value, 3), np.float32) if normals else None; t = np.empty((nt.value, 3), np.uint32)
+        col = np.empty((nv.value, 4), np.uint8) if colors else None
+        if nv.value or nt.value:
+            call(v, n, col, t)
+        self._mc_info = _record(info)
+        return (v, n, t, col) if colors else (v, n, t)
+
+    @_clustering("colors")
     def tsdf_mesh(self, min_weight=0.0, colors=False):
         """icp_tsdf_mesh: the zero level set of the volume as an indexed triangle mesh, extracted on the device (a counting call, then a
         filling call).  min_weight: voxels below this weight count as unobserved.  Returns (vertices (V, 3) f32 in the world frame,
         normals (V, 3) f32 pointing into free space, triangles (T, 3) u32, counter-clockwise seen from free space).
-        colors: icp_tsdf_mesh_color; a fourth array, (V, 4) u8 RGBA per vertex (four zero bytes where the volume holds no colour)."""
+        colors: icp_tsdf_mesh_color; a fourth array, (V, 4) u8 RGBA per vertex (four zero bytes where the volume holds no colour).
+        cluster, cluster_origin (keyword only; cluster is a cell size in metres): icp_tsdf_mesh_clustered, the same tuple with the mesh clustered on the device (DESIGN.md section
+        6zk), the grid's origin at cluster_origin (the volume's by default); `mesh_cluster_info` has the counts.  None: exactly the calls above."""
         nv, nt = C.c_int32(0), C.c_int32(0)
         fn = self.lib.icp_tsdf_mesh_color if colors else self.lib.icp_tsdf_mesh
 
@@ -1537,13 +1627,15 @@ class Context:
             call(v, n, col, t)
         return (v, n, t, col) if colors else (v, n, t)
 
+    @_clustering("normals", "colors")
     def tsdf_mesh_hashed(self, min_weight=0.0, normals=True, colors=False):
         """icp_tsdf_mesh_hashed: the zero level set of the HASHED volume as an indexed triangle mesh, extracted on the block pool (a counting
         call, then a filling call).  The volume stays as it is.  Returns (vertices (V, 3) f32, normals (V, 3) f32 --
         None with normals=False --, triangles (T, 3) u32); vertices in ascending (block in key order, local voxel, edge code), so the arrays
         do not depend on where the blocks sit in the pool.
         colors: icp_tsdf_mesh_color_hashed on a coloured hashed volume; a fourth array, (V, 4) u8 RGBA per vertex
-        (four zero bytes where neither end of the vertex's edge holds a colour)."""
+        (four zero bytes where neither end of the vertex's edge holds a colour).
+        cluster, cluster_origin (keyword only): as in `tsdf_mesh` -- icp_tsdf_mesh_clustered on the hashed volume, the same tuple shape."""
         min_weight = float(min_weight)
         if not (np.isfinite(min_weight) and min_weight >= 0.0):
             raise ValueError("min_weight must be finite and >= 0")

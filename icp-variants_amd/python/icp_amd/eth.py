@@ -250,11 +250,13 @@ def track_tsdf(ctx, scans, start_pose, voxel_size=0.05, truncation=None, origin=
 
 
 def _reconstruct(ctx, colors, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, min_weight=0.0,
-                 mesh_path=None, tracker="map", **track_map_options):
+                 mesh_path=None, tracker="map", mesh_cluster=None, **track_map_options):
     """reconstruct behind its docstring; colors: None, or one rgba array per scan."""
     from . import meshio
     if tracker not in ("map", "sdf"):
         raise ValueError("tracker must be 'map' or 'sdf'")
+    if mesh_cluster is not None and mesh_path is None:
+        raise ValueError("mesh_cluster needs a mesh to write: pass mesh_path")
     if float(track_map_options.get("color_weight", 0.0)) > 0.0:
         if tracker != "sdf":
             raise ValueError("color_weight > 0 needs tracker='sdf' (the voxel-map tracker has no photometric term)")
@@ -270,11 +272,11 @@ def _reconstruct(ctx, colors, scans, start_pose, tsdf_voxel_size=0.05, truncatio
         poses, records, status = track_map(ctx, scans, start_pose, **track_map_options)
         fuse_scans(ctx, scans, poses, voxel_size=tsdf_voxel_size, truncation=truncation, origin=origin, max_range=max_range, block_capacity=block_capacity, **coloured)
     if colors is None:
-        mesh = ctx.tsdf_mesh_hashed(min_weight=min_weight)
+        mesh = ctx.tsdf_mesh_hashed(min_weight=min_weight, cluster=mesh_cluster)
         if mesh_path is not None:
             meshio.write_ply_mesh(mesh_path, *mesh)
         return poses, records, status, mesh
-    v, n, t, c = ctx.tsdf_mesh_hashed(min_weight=min_weight, colors=True)
+    v, n, t, c = ctx.tsdf_mesh_hashed(min_weight=min_weight, colors=True, cluster=mesh_cluster)
     if mesh_path is not None:
         meshio.write_ply_mesh(mesh_path, v, n, t, colors=c)
     return poses, records, status, (v, n, t, c)
@@ -283,7 +285,7 @@ def _reconstruct(ctx, colors, scans, start_pose, tsdf_voxel_size=0.05, truncatio
 @_carving
 @_colouring(_reconstruct)
 def reconstruct(ctx, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, origin=(0.0, 0.0, 0.0), max_range=30.0, block_capacity=1 << 14, min_weight=0.0,
-                mesh_path=None, tracker="map", **track_map_options):
+                mesh_path=None, tracker="map", mesh_cluster=None, **track_map_options):
     """A surface from a laser sequence, the laser counterpart of tum.reconstruct_room: the scans tracked against the voxel map
     (`track_map` with **track_map_options; its voxel_size is the MAP's), fused at the tracked poses into a hashed TSDF volume of
     `tsdf_voxel_size` (`fuse_scans`), the zero level set extracted on the device (Context.tsdf_mesh_hashed with `min_weight`) and, with
@@ -294,8 +296,12 @@ def reconstruct(ctx, scans, start_pose, tsdf_voxel_size=0.05, truncation=None, o
     uint8 array per scan -- the model is fused with the scans' colours, meshed with
     Context.tsdf_mesh_hashed(colors=True), written with meshio.write_ply_mesh(..., colors=...), and the mesh returned is (vertices,
     normals, triangles, colours (V, 4) uint8: alpha 255 on a coloured vertex); None changes nothing.  color_weight (among the options):
-    with tracker="sdf" and colors, the photometric tracker of track_tsdf; with tracker="map" or without colors it raises ValueError."""
-    return _reconstruct(ctx, None, scans, start_pose, tsdf_voxel_size, truncation, origin, max_range, block_capacity, min_weight, mesh_path, tracker, **track_map_options)
+    with tracker="sdf" and colors, the photometric tracker of track_tsdf; with tracker="map" or without colors it raises ValueError.
+    mesh_cluster: a cell size in metres -- the mesh is clustered to that resolution on the device before it crosses to the host
+    (Context.tsdf_mesh_hashed with cluster=; ctx.mesh_cluster_info() has the counts), returned and written that
+    way; without mesh_path it is a ValueError; None changes nothing."""
+    return _reconstruct(ctx, None, scans, start_pose, tsdf_voxel_size, truncation, origin, max_range, block_capacity, min_weight, mesh_path, tracker, mesh_cluster,
+                        **track_map_options)
 
 
 def write_synthetic_dataset(eth_dir, csv_name, pairs, binary=True):

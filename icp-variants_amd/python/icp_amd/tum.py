@@ -195,7 +195,7 @@ def track(ctx, seq, params=None, with_gt=True, nonlinear=None, convergence=None,
     return poses, recs, rc
 
 
-def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None, model_mesh=None, sdf=None, densify=True, depth_filter=None):
+def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_threshold=0.1, camera_scale=0.0015, nonlinear=None, convergence=None, reciprocal=None, model=None, model_mesh=None, sdf=None, densify=True, depth_filter=None, mesh_cluster=None):
     """reconstructRoom end to end: `track`, then saveRoomToFile (utils.h:179-193) for every scheduled frame k --
     joinMeshes(SimpleMesh(sensor, pose_k, edge_threshold) on the device, SimpleMesh::camera(pose_k, camera_scale), identity) with pose_k
     the camera pose `track` returned (the identity for frame 0).  With out_dir the meshes are written as mesh_<frame index>.off
@@ -207,9 +207,14 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
     does not fit a dense volume; densify=False meshes it in place instead
     (Context.tsdf_mesh_hashed, DESIGN.md sections 6y and 6zc; with per-vertex colours when the model has them): nothing but the mesh crosses to the host, no box is built and the context keeps its hashed volume.
     densify=False with a model that is not hashed is a ValueError.  sdf: as `track` (direct SDF tracking against the model); a hashed model
-    with raycast=True and no `sdf` is tracked against its ray-cast instead, as `track` says.  depth_filter: as `track` (the per-frame depth meshes are built from the raw frames).  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
+    with raycast=True and no `sdf` is tracked against its ray-cast instead, as `track` says.  depth_filter: as `track` (the per-frame depth meshes are built from the raw frames).
+    mesh_cluster: a cell size in metres -- the model's mesh is clustered to that resolution on the device before it crosses to the host
+    (Context.tsdf_mesh / tsdf_mesh_hashed with cluster=; ctx.mesh_cluster_info() has the counts); without a mesh
+    to write (model, model_mesh and out_dir) it is a ValueError; None changes nothing.  Returns (poses, records, status, the meshes -- or their paths with out_dir)."""
     if not densify and not (model is not None and model.get("hashed")):
         raise ValueError("densify=False meshes a hashed model in place: pass model=dict(hashed=True, ...)")
+    if mesh_cluster is not None and not (model is not None and model_mesh is not None and out_dir is not None):
+        raise ValueError("mesh_cluster needs a mesh to write: pass model, model_mesh and out_dir")
     poses, recs, rc = track(ctx, seq, params, with_gt=with_gt, nonlinear=nonlinear, convergence=convergence, reciprocal=reciprocal, model=model, sdf=sdf, depth_filter=depth_filter)
     cam = binding.depth_camera(seq["K"], seq["width"], seq["height"])
     if out_dir is not None:
@@ -229,18 +234,18 @@ def reconstruct_room(ctx, seq, params=None, out_dir=None, with_gt=True, edge_thr
             tsdf_local.restore(ctx, ctx.tsdf_store)     # (a streamed model: the union of the resident and the stored blocks)
         if model.get("hashed") and not densify:
             if model.get("color"):
-                v, n, t, col = ctx.tsdf_mesh_hashed(colors=True)
+                v, n, t, col = ctx.tsdf_mesh_hashed(colors=True, cluster=mesh_cluster)
                 meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), v, n, t, colors=col)
             else:
-                meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh_hashed())
+                meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh_hashed(cluster=mesh_cluster))
             return poses, recs, rc, out
         if model.get("hashed"):
             densify_hashed_model(ctx)
         if model.get("color"):
-            v, n, t, col = ctx.tsdf_mesh(colors=True)
+            v, n, t, col = ctx.tsdf_mesh(colors=True, cluster=mesh_cluster)
             meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), v, n, t, colors=col)
         else:
-            meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh())
+            meshio.write_ply_mesh(os.path.join(out_dir, model_mesh), *ctx.tsdf_mesh(cluster=mesh_cluster))
     return poses, recs, rc, out
 
 

@@ -1698,6 +1698,66 @@ int icp_track_scans_sdf_photometric(icp_ctx* ctx, const float* const* xyz, const
                                     const icp_sdf_options* opt, const icp_sdf_color_options* copt, float pose_inout[16],
                                     icp_sdf_color_frame* out, icp_tsdf_cloud_info* infos_out, int32_t* n_colored_out);
 
+/* -------- a mesh of a chosen resolution (an extension): vertex clustering on the device (Rossignac and Borrel 1993).  DESIGN.md section
+ * 6zk. --------
+ * The vertices that fall into one cell of a grid become one vertex, a triangle that loses a corner that way is dropped, triangles that
+ * become equal are kept once.  One pass, two hash tables and integer sums: the result is a function of the input arrays alone, whatever
+ * order the device's threads run in; tests/mesh_cluster_restatement.py restates it in numpy.  Every fp32 operation below is rounded once, in
+ * the order written, with no contraction.
+ * Cell of a vertex p: per axis r, g = (p_r - o_r) / cell_size and f = floorf(g).  The vertex is INVALID iff a coordinate is not finite or
+ *   !(-2^20 <= f < 2^20) on some axis.  Its cell is c_r = (int)f, its offset q_r = (int)((g - f) * 65536.f), in 0 .. 65535 (and 65536 where
+ *   g - f rounds up to 1: the cell's far face).
+ * Cluster: the valid vertices of one cell; its identity is its FIRST member, the smallest input index.
+ * Triangle: INVALID iff an index is >= n_vertices or names an invalid vertex (an index is compared before it is used: nothing is read out of
+ *   bounds).  DEGENERATE iff two of its three clusters are equal.  Otherwise it is rotated so that the cluster with the smallest first
+ *   member comes first -- orientation kept, never mirrored --, which is its canonical triple.  Triangles with the same canonical triple are
+ *   DUPLICATES: the one with the smallest input index survives.  Opposite orientations of the same three clusters are distinct; both stay.
+ * Output triangles: the survivors in ascending input index, their corners as written in the input (not rotated), each replaced by the
+ *   output index of its cluster.
+ * Output vertices: the clusters that a surviving triangle references, in ascending first member; unreferenced clusters are dropped.
+ *   n_cells counts all occupied cells, n_vertices the referenced ones.
+ * Position of a cluster of n members with the 64-bit integer sums S_r of q_r: Q_r = (2 S_r + n) / (2 n) by integer division,
+ *   p'_r = o_r + ((float)c_r + (float)Q_r * 0x1p-16f) * cell_size.
+ * Normal (with `normals`): a member whose normal has a non-finite component contributes nothing; otherwise
+ *   m_r = (int)rintf(fminf(fmaxf(n_r, -1.f), 1.f) * 32767.f), summed in 64-bit integers to M; N = (float)M,
+ *   n' = N / sqrtf(Nx Nx + (Ny Ny + Nz Nz)); a non-finite result is written as (0, 0, 0).
+ * Colour (with `colors`, 4 bytes R G B A per vertex): the members with alpha != 0 are the coloured ones, k of them; per channel
+ *   (2 Sum + k) / (2 k) by integer division, alpha 255; k = 0: four zero bytes.
+ * Consistency: n_triangles + n_degenerate + n_duplicate + n_invalid_triangles == n_triangles_in; two calls give identical arrays.
+ * Calling: info_out is required and always written.  All four output arrays NULL: the call only counts.  vertices_out and triangles_out
+ *   go together; normals_out needs normals, colors_out needs colors.  vertices_out / normals_out: room for max_vertices * 3 floats,
+ *   colors_out for max_vertices * 4 bytes, triangles_out for max_triangles * 3 indices; a count above its capacity:
+ *   ICP_ERR_INVALID_ARG, a message with the four numbers, nothing written to the arrays.  cell_size must be finite and > 0, origin finite,
+ *   n_vertices and n_triangles in 0 .. 2^27 (ICP_MESH_CLUSTER_MAX).  An empty input or an empty result: ICP_OK with zeros.  Target, source,
+ *   volume, params and index stay untouched.  Scratch comes from the context: 16 bytes per slot of the cell table (a power of
+ *   two, at least 2 V slots) and 8 per vertex, 4 bytes per slot of the triangle table (at least 2 T) and 20 per triangle, at most 80 per
+ *   output vertex for the sums, and the staged input and output.
+ * Limits: the representative is the members' mean, so sharp edges are rounded; the result need not be manifold; no error metric is
+ *   minimised (quadric error decimation is another algorithm). */
+typedef struct icp_mesh_cluster_options { float cell_size; float origin[3]; } icp_mesh_cluster_options;
+typedef struct icp_mesh_cluster_info {
+    int32_t n_vertices_in, n_triangles_in, n_invalid_vertices, n_invalid_triangles, n_cells, n_vertices, n_triangles, n_degenerate, n_duplicate;
+} icp_mesh_cluster_info;
+enum { ICP_MESH_CLUSTER_MAX = 1 << 27 };
+#ifdef __cplusplus
+static_assert(sizeof(icp_mesh_cluster_options) == 16 && sizeof(icp_mesh_cluster_info) == 36, "ABI layout");
+#endif
+int icp_mesh_cluster(icp_ctx* ctx, int32_t n_vertices, int32_t n_triangles, const float* vertices, const float* normals, const uint8_t* colors,
+                     const uint32_t* triangles, const icp_mesh_cluster_options* opt, int32_t max_vertices, int32_t max_triangles,
+                     float* vertices_out, float* normals_out, uint8_t* colors_out, uint32_t* triangles_out, icp_mesh_cluster_info* info_out);
+/* The model's mesh at a chosen resolution: the extraction of whichever volume the context holds, dense or hashed -- icp_tsdf_mesh,
+ * icp_tsdf_mesh_color (with_colors != 0; needs a volume with colours), icp_tsdf_mesh_hashed or icp_tsdf_mesh_color_hashed: the same kernels,
+ * the same staged device arrays -- clustered where it lies.  Only the clustered mesh and one small record cross to the host; the
+ * full-resolution mesh is never copied.  Contract: the arrays and the info equal, bit for bit and array for array, what icp_mesh_cluster
+ * returns for the output of the matching mesh call with normals.  Calling: icp_tsdf_mesh's -- the two count pointers and info_out are required
+ * and always written (the counts are the clustered mesh's); all four arrays NULL counts; vertices_out and triangles_out go together;
+ * normals_out and colors_out may be NULL, colors_out needs with_colors; capacities and their refusal as above.  No volume, a bad min_weight,
+ * bad options, with_colors on a volume without colours, an intermediate mesh of more than 2^27 vertices or triangles:
+ * ICP_ERR_INVALID_ARG with a message.  The volume stays as it is. */
+int icp_tsdf_mesh_clustered(icp_ctx* ctx, float min_weight, const icp_mesh_cluster_options* opt, int32_t with_colors,
+                            int32_t max_vertices, int32_t max_triangles, float* vertices_out, float* normals_out, uint8_t* colors_out,
+                            uint32_t* triangles_out, int32_t* n_vertices_out, int32_t* n_triangles_out, icp_mesh_cluster_info* info_out);
+
 /* -------- batches of independent scan pairs: the loop over ETH indices, main.cpp:411-498 / experiment.cpp:319-396 --------
  * The reference aligns the pairs one after the other and carries no state between them, so a batch shards with no
  * data-path exchange: pair p belongs to rank p % n_ranks (icp_pair_owner), and the only collective is ONE gather of the
